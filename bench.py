@@ -13,8 +13,7 @@ A step is one pass of the hot path over one batch that is already resident in HB
       ThreadPredictor uses them.  NP = 2 (--predictors): the reference's and this package's default
       Config.PREDICTORS = 2 (Config.py:57, README.md:28-32 "NP: 2"), on the HIP runtime's default number of
       hardware queues -- the configuration a Server with Config defaults runs.  The 1-, 3- and 4-lane figures of
-      the same K steps are reported beside it under "predict_lanes", and the 8-hardware-queue variant (a process-wide
-      runtime setting the package does not make) under "predict_lanes_8_hw_queues", measured in a child process;
+      the same K steps are reported beside it under "predict_lanes";
   train leg (reported under "train"): one ThreadTrainer batch (configs[2]: 128 rows) through forward,
       loss, backward, RCCL all-reduce of the gradient arena when N > 1, RMSProp.
 Per-GPU work is fixed as N grows (weak scaling); predictions need no collective.
@@ -33,7 +32,6 @@ import time
 import numpy as np
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # RCCL across processes needs dmabuf IPC on this stack
-# GPU_MAX_HW_QUEUES is NOT touched: every leg of this process runs on the runtime's default, like the package itself
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "oracle")):
@@ -141,14 +139,15 @@ def main():
     ap.add_argument("--actions", type=int, default=6)
     ap.add_argument("--predictors", type=int, default=2, help="prediction lanes the K predict steps are dealt to (predictor threads; "
                                                                "Config.PREDICTORS = 2 is the reference's and the package's default)")
-    ap.add_argument("--lanes-only", action="store_true",
-                    help="child mode of the 8-hardware-queue extra: print only {lanes: predictions/s} for 1..4 lanes and exit")
     ap.add_argument("--no-lane-sweep", action="store_true",
                     help="skip the extra 1- and 3-lane legs (use with --predictors 1 under rocprofv3 so that kernels never overlap)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample length; 0 disables it")
     ap.add_argument("--e2e-seconds", type=float, default=8.0,
                     help="also run the whole engine (agent processes -> transport -> predictor/trainer threads) this long; 0 disables")
     ap.add_argument("--e2e-agents", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed prediction step returned (p, v) as DIR/<name>.npy (float32); the "
+                         "inputs and weights are seeded, so runs with the same arguments compare output for output")
     ap.add_argument("--device-override", type=int, default=-1,
                     help="rehearsal only: put every rank on this device (RCCL then refuses duplicate GPUs and the "
                          "train leg is reported as null)")
@@ -245,28 +244,12 @@ def main():
         inner_walls.append(inner_s)
         return gpu_s, wall_s
 
-    MIN_TIMED_S, MAX_BLOCKS = 0.05, 400
-    blocks_used = {}
     inner_walls = []
 
-    def timed(mode, steps, lanes=0, tag=None, rows=None):
-        """A K-step block of this path lasts well under a millisecond at the driver's K = 20: the bracketed K-step block is
-        repeated until at least 50 ms have been timed and the MEDIAN block is reported (every rank runs the same number
-        of blocks: the count is decided on rank 0's clock).  Returns (median GPU span, median host wall) in seconds."""
-        gpus, walls, total = [], [], 0.0
-        while True:
-            g, w = timed_block(mode, steps, lanes, rows)
-            gpus.append(g)
-            walls.append(w)
-            total += w
-            more = 1 if (total < MIN_TIMED_S and len(walls) < MAX_BLOCKS) else 0
-            if world > 1:                                  # the count is decided on rank 0's clock
-                more = int(rv.reduce([more if rank == 0 else 0])[0])
-            if not more:
-                break
-        if tag:
-            blocks_used[tag] = len(walls)
-        return float(np.median(gpus)), float(np.median(walls))
+    def timed(mode, steps, lanes=0, rows=None):
+        """ONE bracketed block of exactly `steps` steps (--steps sets the number of timed steps; the warm-up steps are run
+        before).  Returns (GPU span, host wall) of that block in seconds."""
+        return timed_block(mode, steps, lanes, rows)
 
     ev_ms = nat.C.c_float()
     for mode in (0, 1):
@@ -274,14 +257,17 @@ def main():
             nat.check(lib.ga3c_net_time_resident(h, mode, B, W, lr, beta, nat.C.byref(ev_ms)), "warmup")
     if W > 0:
         nat.check(lib.ga3c_net_time_predict_lanes(h, B, W, NP, nat.C.byref(ev_ms)), "warmup")
-    if args.lanes_only:      # child of the 8-hardware-queue extra (see below): the lane sweep and nothing else
-        res = {str(nl): K * B / timed(0, K, lanes=nl)[1] for nl in (1, 2, 3, 4)}
-        net.close()
-        print(json.dumps(dict(res, hardware_queues=os.environ.get("GPU_MAX_HW_QUEUES"))))
-        return
     del inner_walls[:]
-    pred_gpu_s, pred_s = timed(0, K, lanes=NP, tag="predict")      # pred_s: host wall-clock of the median bracketed block
+    pred_gpu_s, pred_s = timed(0, K, lanes=NP)      # pred_s: host wall-clock of the bracketed K-step block
     pred_inner_s = float(np.median(inner_walls))
+    dumped = {}
+    if args.dump_outputs and rank == 0:
+        # what the K-th timed step handed back, read from the lane that ran it (lane l ran the steps l, l + NP, ...)
+        last = (K - 1) % NP
+        for name, n in (("p", B * A), ("v", B)):
+            buf = np.empty(n, dtype=np.float32)
+            nat.check(lib.ga3c_net_fetch_lane(h, last, name.encode(), nat.ptr(buf), n), "fetch_lane")
+            dumped[name] = buf.reshape((B, A) if name == "p" else (B,))
     one_s = timed(0, K, lanes=1)[1]
     sweep = {}
     if not args.no_lane_sweep:
@@ -311,7 +297,7 @@ def main():
         dp_guard.daemon = True
         dp_guard.start()
     if dp_error is None:
-        train_gpu_s, train_s = timed(1, K, tag="train")
+        train_gpu_s, train_s = timed(1, K)
         train_tb_gpu_s, train_tb_s = timed(1, K, rows=TB)   # what the engine's trainers really assemble at MIN = B - 1
     else:                                               # no communicator: the data-parallel train leg is not measured
         train_s, train_gpu_s, train_tb_s, train_tb_gpu_s = None, None, None, None
@@ -346,14 +332,14 @@ def main():
                        "inputs": "resident in HBM (f32 NHWC), outputs p,v left in HBM"},
             "predict_lanes": dict({"1": world * K * B / one_s, str(NP): pps},
                                   **{str(nl): world * K * B / s_ for nl, s_ in sweep.items()},
-                                  unit="predictions/s", hardware_queues=os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)"),
+                                  unit="predictions/s", hardware_queues="runtime default",
                                   note="same K steps dealt to 1 .. 4 prediction lanes (one persistent host thread per lane); "
                                        "`value` is the NP = %d figure, the default of the reference and of this package; lanes "
                                        "beyond three share the three prediction streams (ga3c_net_create: the engine keeps to "
                                        "four normal-priority streams)" % NP),
             "gpu_span_ms_per_step": pred_gpu_s / K * 1e3, "value_gpu_span": world * K * B / pred_gpu_s,
             "inner_wall_ms_per_step": pred_inner_s / K * 1e3,
-            "timing": "ms_per_step / value: HOST WALL-CLOCK (time.perf_counter) of the median bracketed K-step block, max over "
+            "timing": "ms_per_step / value: HOST WALL-CLOCK (time.perf_counter) of the one bracketed K-step block, max over "
                       "ranks: barrier + device synchronisation, the K steps, device synchronisation -- rounds 1 and 2's "
                       "definition; launch latency of the first kernel, the wake-up of the lanes' host threads and of the "
                       "waiting caller are in it.  Each lane's copy of the resident batch is made once per uploaded batch (by "
@@ -373,9 +359,6 @@ def main():
                                          "steps_per_sec": K / train_tb_s if train_tb_s else None,
                                          "note": "the largest batch ThreadTrainer assembles at TRAINING_MIN_BATCH_SIZE = %d "
                                                  "(ThreadTrainer.py:49-59): MIN + TIME_MAX rows" % (B - 1)}},
-            "timed_blocks": dict(blocks_used, min_timed_ms=MIN_TIMED_S * 1e3,
-                                 note="the bracketed K-step block is repeated until >= 50 ms are timed; ms_per_step and "
-                                      "value are those of the MEDIAN block"),
             "data_parallel_error": dp_error,
             "rccl_ranks": comm_ranks if world > 1 else 1,
             "rccl_comm": {"ranks": comm_ranks, "rank": comm_rank, "device": comm_dev,
@@ -472,23 +455,6 @@ def main():
     cpu_theta = net.get_arena(0) if (rank == 0 and world == 1 and args.cpu_seconds > 0) else None
     net.close()
 
-    # ---- extra: the same lane sweep with 8 hardware queues.  GPU_MAX_HW_QUEUES is read once, when HIP initialises, and is
-    # process-wide, so this runs in a child process; the package itself leaves the runtime's default (ga3c_amd/__init__.py)
-    if rank == 0 and world == 1 and not args.no_lane_sweep:
-        import subprocess
-        try:
-            child = subprocess.run([sys.executable, os.path.abspath(__file__), "--lanes-only", "--steps", str(max(K, 100)),
-                                    "--warmup", str(max(W, 10)), "--batch", str(B), "--actions", str(A)],
-                                   env=dict(os.environ, GPU_MAX_HW_QUEUES="8", GA3C_LANE_STREAMS="4"), capture_output=True, text=True, timeout=240)
-            line = [ln for ln in child.stdout.splitlines() if ln.startswith("{")]
-            out["predict_lanes_8_hw_queues"] = dict(json.loads(line[-1]), unit="predictions/s",
-                                                    note="child process with GPU_MAX_HW_QUEUES=8 and GA3C_LANE_STREAMS=4 (a stream "
-                                                         "and a hardware queue per lane, nothing else running): an extra, not "
-                                                         "the product's configuration") if line else \
-                {"error": "child printed no line (rc %d): %s" % (child.returncode, child.stderr[-300:])}
-        except (subprocess.TimeoutExpired, OSError, ValueError) as e:
-            out["predict_lanes_8_hw_queues"] = {"error": repr(e)}
-
     # ---- Hogwild trainers: the reference's default NT = 2 trainer threads update shared weights unlocked (Server.py:132-134)
     if rank == 0 and world == 1:
         hog = Network("gpu:%d" % local_rank, "bench_hogwild", A, (84, 84, 4), max_batch=B, predict_lanes=1, train_lanes=4)
@@ -517,16 +483,13 @@ def main():
             dpn.comm_init(Network.make_comm_id(), 0, 1)
             for rows in (B, TB):
                 nat.check(dpn._lib.ga3c_net_time_resident(dpn._h, 1, rows, max(W, 5), lr, beta, nat.C.byref(ms)), "warmup")
-                walls, spans = [], []
-                while sum(walls) < MIN_TIMED_S and len(walls) < MAX_BLOCKS:
-                    device_sync(dpn._h)
-                    t0 = time.perf_counter()
-                    nat.check(dpn._lib.ga3c_net_time_resident(dpn._h, 1, rows, K, lr, beta, nat.C.byref(ms)), "time_resident")
-                    device_sync(dpn._h)
-                    walls.append(time.perf_counter() - t0)
-                    spans.append(ms.value * 1e-3)
-                dp1["rows_%d" % rows] = {"ms_per_step": float(np.median(walls)) / K * 1e3, "gpu_span_ms_per_step": float(np.median(spans)) / K * 1e3,
-                                         "steps_per_sec": K / float(np.median(walls))}
+                device_sync(dpn._h)
+                t0 = time.perf_counter()
+                nat.check(dpn._lib.ga3c_net_time_resident(dpn._h, 1, rows, K, lr, beta, nat.C.byref(ms)), "time_resident")
+                device_sync(dpn._h)
+                wall = time.perf_counter() - t0
+                dp1["rows_%d" % rows] = {"ms_per_step": wall / K * 1e3, "gpu_span_ms_per_step": ms.value / K,
+                                         "steps_per_sec": K / wall}
             nat.check(dpn._lib.ga3c_net_time_allreduce(dpn._h, 50, nat.C.byref(ms)), "time_allreduce")
             dp1["allreduce_us_one_rank"] = ms.value / 50 * 1e3
             dp1["rccl_comm"] = dict(zip(("ranks", "rank", "device"), dpn.comm_info()))
@@ -661,6 +624,10 @@ def main():
     rv.barrier()
     rv.close()
     if rank == 0:
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
         print(json.dumps(out))
 
 

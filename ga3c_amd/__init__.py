@@ -11,10 +11,8 @@ flat imports work from anywhere; there is exactly one copy of each module.
 import os
 import sys
 
-# HIP streams (prediction lanes, train lanes, frame queues, gradient exchange) are multiplexed onto GPU_MAX_HW_QUEUES hardware
-# queues, 4 unless the environment says otherwise.  On resident batches a queue per lane pays (4 lanes: 7.5 -> 9.3 M
-# predictions/s with 8 queues; bench.py sets it), but the whole engine with 4 predictor threads fell from 344 k to 203 k
-# predictions/s on 8 queues (profiles/README.md): the package leaves the runtime's default alone.
+# HIP streams (prediction lanes, train lanes, frame queues, gradient exchange) are multiplexed onto the HIP runtime's
+# hardware queues, 4 by default.  The package leaves the runtime's queue setting alone (profiles/README.md).
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:

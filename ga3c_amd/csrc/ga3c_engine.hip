@@ -1616,7 +1616,7 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
   }
   int nl = cfg->predict_lanes > 0 ? cfg->predict_lanes : 2;
   if (nl > 16) nl = 16;
-  // Streams.  The runtime multiplexes every HIP stream of the process onto GPU_MAX_HW_QUEUES hardware queues (4 unless the
+  // Streams.  The runtime multiplexes every HIP stream of the process onto its hardware queues (4 unless the
   // environment says otherwise), a new stream taking the least-used queue, and the chip serves four compute queues at a
   // time (tools/qmap.hip; profiles/README.md, "Hardware queues").  A prediction lane that lands on the train stream's
   // queue waits behind whole train steps, and a fifth busy queue makes all of them take turns -- either way the train step
@@ -2933,6 +2933,25 @@ int ga3c_net_fetch(ga3c_net* net, const char* name, float* out, int64_t count) {
     if (strcmp(e.n, name) == 0) {
       if (count < 1 || count > e.cap) return fail(GA3C_EINVAL, "count %lld outside [1,%lld] for '%s'", (long long)count, (long long)e.cap, name);
       HIPCHK(hipStreamSynchronize(t.st));
+      HIPCHK(hipMemcpy(out, e.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+      return GA3C_OK;
+    }
+  }
+  return fail(GA3C_EINVAL, "unknown buffer '%s'", name);
+}
+
+int ga3c_net_fetch_lane(ga3c_net* net, int32_t lane, const char* name, float* out, int64_t count) {
+  if (!net || !name || !out) return fail(GA3C_EINVAL, "null argument");
+  if (lane < 0 || lane >= (int)net->lanes.size()) return fail(GA3C_EINVAL, "no prediction lane %d", (int)lane);
+  HIPCHK(hipSetDevice(net->cfg.device));
+  Lane* L = net->lanes[(size_t)lane];
+  const int64_t B = net->maxB, A = net->A;
+  struct Ent { const char* n; const float* p; int64_t cap; };
+  const Ent ents[] = {{"z", L->f.z, B * A}, {"p", L->f.p, B * A}, {"v", L->f.v, B}};
+  for (const Ent& e : ents) {
+    if (strcmp(e.n, name) == 0) {
+      if (count < 1 || count > e.cap) return fail(GA3C_EINVAL, "count %lld outside [1,%lld] for '%s'", (long long)count, (long long)e.cap, name);
+      HIPCHK(hipStreamSynchronize(L->st));
       HIPCHK(hipMemcpy(out, e.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
       return GA3C_OK;
     }

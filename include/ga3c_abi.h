@@ -159,6 +159,9 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
  * name in {"n1","n2","d1","z","p","v","dz","dv","dd1","dn2","dn1"}.  "dn1" is that of the last ga3c_net_compute_grads
  * (train steps of up to 128 rows consume it on chip and do not store it). */
 int ga3c_net_fetch(ga3c_net* net, const char* name, float* out, int64_t count);
+/* The same for prediction lane `lane` (name in {"z","p","v"}): the outputs of the last step that lane ran, e.g. the
+ * resident steps of ga3c_net_time_predict_lanes, which leave them in HBM. */
+int ga3c_net_fetch_lane(ga3c_net* net, int32_t lane, const char* name, float* out, int64_t count);
 
 /* Zero-copy intake from the shared-memory transport (include/ga3c_host.h): register the whole segment
  * once (hipHostRegister), then a batch is described by one byte offset per row into that segment and the GPU

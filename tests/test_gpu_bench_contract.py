@@ -13,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(300)
 def test_bench_line_contract(tmp_path):
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--cpu-seconds", "1",
-                          "--e2e-seconds", "3", "--e2e-agents", "4"], capture_output=True, text=True, timeout=280, cwd=str(tmp_path))
+                          "--e2e-seconds", "3", "--e2e-agents", "4", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=280, cwd=str(tmp_path))
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines                       # exactly one line on stdout
@@ -37,6 +38,13 @@ def test_bench_line_contract(tmp_path):
     dp1 = d["train"]["train_dp_1rank"]                  # the N-GPU code path timed with a one-rank communicator
     assert "error" not in dp1 and dp1["rccl_comm"]["ranks"] == 1
     assert dp1["rows_128"]["steps_per_sec"] > 100 and dp1["rows_132"]["steps_per_sec"] > 100
+    # --dump-outputs: what the last timed prediction step returned, p f32[128, 6] (softmax rows) and v f32[128]
+    import numpy as np
+    assert sorted(os.listdir(str(tmp_path / "out"))) == ["p.npy", "v.npy"]
+    p, v = np.load(str(tmp_path / "out" / "p.npy")), np.load(str(tmp_path / "out" / "v.npy"))
+    assert p.dtype == np.float32 and p.shape == (128, 6) and v.dtype == np.float32 and v.shape == (128,)
+    assert np.all(np.isfinite(p)) and np.all(np.isfinite(v)) and np.all(p >= 0)
+    assert np.max(np.abs(p.sum(axis=1) - 1.0)) < 1e-5 and np.ptp(v) > 0
 
 
 @pytest.mark.timeout(400)

@@ -1,6 +1,6 @@
 // tools/qmap.hip -- which HIP streams share a hardware queue, and how many queues the chip serves at a time.
 // Development aid behind profiles/README.md ("Hardware queues"); not part of the product.
-//   hipcc -O2 --offload-arch=gfx950 -o tools/qmap tools/qmap.hip && GPU_MAX_HW_QUEUES=4 ./tools/qmap
+//   hipcc -O2 --offload-arch=gfx950 -o tools/qmap tools/qmap.hip && ./tools/qmap
 // 1. pairs: a 300-us spin kernel (ONE workgroup) on stream i, then a trivial kernel on stream j: j finishing after i means
 //    the two streams are multiplexed onto one hardware queue (in-order), j finishing at once means they are not.
 // 2. width: the spin kernel on n streams at once, one workgroup each: wall time / 300 us = how many turns the queues took.
@@ -27,8 +27,7 @@ int main(int argc, char** argv) {
   const int S = argc > 1 ? atoi(argv[1]) : 8;
   int lo = 0, hi = 0;
   CK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  printf("GPU_MAX_HW_QUEUES=%s, %d normal streams + 1 high-priority stream (priority range %d..%d)\n",
-         getenv("GPU_MAX_HW_QUEUES") ? getenv("GPU_MAX_HW_QUEUES") : "default", S, lo, hi);
+  printf("%d normal streams + 1 high-priority stream (priority range %d..%d)\n", S, lo, hi);
   std::vector<hipStream_t> st(S + 1);
   if (argc > 2) {      // any second argument: use the null stream first, as a program that calls hipMemset / hipMemcpy does
     int* p = nullptr;
