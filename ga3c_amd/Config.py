@@ -46,7 +46,7 @@ class Config:
     RMSPROP_DECAY = 0.99
     RMSPROP_MOMENTUM = 0.0
     RMSPROP_EPSILON = 0.1
-    DUAL_RMSPROP = False                # out of scope; must stay False
+    DUAL_RMSPROP = False                # one RMSProp optimizer per cost, cost_p and cost_v (NetworkVP_discrate.py:87-99); DESIGN §8
     USE_GRAD_CLIP = False
     GRAD_CLIP_NORM = 40.0
     LOG_EPSILON = 1e-6

@@ -88,8 +88,6 @@ class Network:
         self.log_epsilon = Config.LOG_EPSILON
         if int(np.prod(state_dim)) != nat.STATE_FLOATS:
             raise ValueError("state_dim %r is not 84x84x4" % (state_dim,))
-        if Config.DUAL_RMSPROP:
-            raise ValueError("DUAL_RMSPROP is out of scope (SURVEY.md section 9, Q7)")
         if max_batch is None:
             max_batch = max(Config.PREDICTION_BATCH_SIZE,
                             Config.TRAIN_ROWS_MAX or (Config.TRAINING_MIN_BATCH_SIZE + Config.TIME_MAX + 1))
@@ -100,7 +98,8 @@ class Network:
         cfg.num_actions = self.num_actions
         cfg.max_batch = self.max_batch
         cfg.flags = (nat.FLAG_LOG_SOFTMAX if Config.USE_LOG_SOFTMAX else 0) | \
-                    (nat.FLAG_GRAD_CLIP if Config.USE_GRAD_CLIP else 0)
+                    (nat.FLAG_GRAD_CLIP if Config.USE_GRAD_CLIP else 0) | \
+                    (nat.FLAG_DUAL_RMSPROP if Config.DUAL_RMSPROP else 0)
         cfg.rmsprop_decay = Config.RMSPROP_DECAY
         cfg.rmsprop_momentum = Config.RMSPROP_MOMENTUM
         cfg.rmsprop_epsilon = Config.RMSPROP_EPSILON
@@ -155,6 +154,8 @@ class Network:
             pass
 
     # ---- arenas -----------------------------------------------------------------------------
+    # which: 0 weights, 1 / 2 RMSProp `ms` / `mom`, 3 last gradient.  With Config.DUAL_RMSPROP, 1 / 2 / 3 belong to cost_p's
+    # optimizer and 4 / 5 / 6 are cost_v's `ms` / `mom` / last gradient (include/ga3c_abi.h)
     def get_arena(self, which):
         out = np.empty(self.param_count, dtype=np.float32)
         nat.check(self._lib.ga3c_net_get_arena(self._h, which, nat.ptr(out), out.size), "ga3c_net_get_arena")

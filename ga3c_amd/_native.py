@@ -15,6 +15,7 @@ STATE_FLOATS = 84 * 84 * 4
 COMM_ID_BYTES = 128
 FLAG_LOG_SOFTMAX = 1
 FLAG_GRAD_CLIP = 2
+FLAG_DUAL_RMSPROP = 4
 
 f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)

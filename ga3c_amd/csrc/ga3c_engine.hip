@@ -209,8 +209,11 @@ struct TrainLane {
   float* h_in = nullptr;    // pinned: x | y_r | a
   float* h_out = nullptr;   // pinned: p | v | z | losses
   int64_t* h_off = nullptr;
-  float* grad = nullptr;    // this lane's gradient arena (lane 0: net->grad, the buffer RCCL all-reduces)
+  float* grad = nullptr;    // this lane's gradient arena (lane 0: net->grad, the buffer RCCL all-reduces); DUAL_RMSPROP: 2n
+                            // floats, the policy gradient at [0, n) and the value gradient at [n, 2n) (one all-reduce for both)
   bool owns_grad = false;
+  float* dd1_v = nullptr;   // DUAL_RMSPROP only: the value term of dd1 (heads_dual_kernel; t.dd1 then holds the policy term)
+  float* zeros = nullptr;   // DUAL_RMSPROP only: maxB * A zeros, the other head's upstream gradient in each backward pass
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool exchanged = false;   // the gradients in `grad` have been all-reduced by the backward pass itself (overlapped exchange)
   bool stepped = false;     // the backward pass has applied RMSProp itself (FusedUpd) into theta[stepped_other]
@@ -302,6 +305,10 @@ struct ga3c_net {
   std::atomic<uint64_t> pred_seq{0};    // prediction steps launched so far; the optimizer records theta_ready only while
   uint64_t pred_seen = 0;               // predictions are arriving (an event per step costs a train-only loop ~3 us)
   float *grad = nullptr, *ms = nullptr, *mom = nullptr;
+  // Config.DUAL_RMSPROP (GA3C_FLAG_DUAL_RMSPROP): ms / mom above are the policy optimizer's slots (it owns cost_p, which stands
+  // in for cost_all), ms_v / mom_v the value optimizer's; grad is 2n floats (TrainLane::grad)
+  bool dual = false;
+  float *ms_v = nullptr, *mom_v = nullptr;
   hipEvent_t theta_ready[NBUF] = {nullptr, nullptr, nullptr};   // recorded on the train stream behind the step that wrote theta[i]
   std::mutex ready_mu;
   std::shared_mutex wmu;   // shared: a forward pass picking/reading theta[cur]; unique: the optimizer flip
@@ -371,6 +378,7 @@ struct ga3c_net {
   int64_t reg_bytes = 0;
   Frames fr;
   TensorTable tt;
+  TensorTable2 tt2;                    // DUAL_RMSPROP: the 10 tensors of the policy gradient, then those of the value gradient
   LaneDrivers drv;
   float lanes_gpu_ms = 0.f;            // GPU-side span of the last ga3c_net_time_predict_lanes block (first start event .. last end event)
   int lanes_gpu_n = 0;
@@ -452,8 +460,10 @@ constexpr int HEADS_WAVES = 1;   // samples (waves) per heads workgroup
 // ---- kernel launch helpers (shape checks live here: every grid is derived from B on the host)
 // stop_ev: recorded behind the step -- as the completion event of its LAST launch (hipExtLaunchKernelGGL), which saves the
 // host the hipEventRecord call and the queue a packet of its own
+// dual (train only): dd1 as its two terms, tl->dd1 (policy) and tl->dd1_v (value), for the two backward passes of DUAL_RMSPROP
 int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, bool train,
-                   const TrainLane* tl, float beta, float* out_p = nullptr, float* out_v = nullptr, hipEvent_t stop_ev = nullptr) {
+                   const TrainLane* tl, float beta, float* out_p = nullptr, float* out_v = nullptr, hipEvent_t stop_ev = nullptr,
+                   bool dual = false) {
   if (B < 1 || B > net->maxB) return fail(GA3C_EINVAL, "batch %d outside [1,%d]", B, net->maxB);
   const int A = net->A;
   const float* th = net->theta[idx];
@@ -504,7 +514,12 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
     if (stop_ev) hipExtLaunchKernelGGL((heads_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, nullptr, stop_ev, 0, h); \
     else hipLaunchKernelGGL((heads_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, h);                                 \
   } while (0)
-  if (A <= 8) { if (train) HEADS(true, 8); else HEADS(false, 8); }
+  if (train && dual) {
+    const dim3 grid((B + HEADS_WAVES - 1) / HEADS_WAVES), block(64 * HEADS_WAVES);
+    if (A <= 8) hipLaunchKernelGGL(heads_dual_kernel<8>, grid, block, 0, st, h, tl->dd1_v);
+    else if (A <= 24) hipLaunchKernelGGL(heads_dual_kernel<24>, grid, block, 0, st, h, tl->dd1_v);
+    else hipLaunchKernelGGL(heads_dual_kernel<64>, grid, block, 0, st, h, tl->dd1_v);
+  } else if (A <= 8) { if (train) HEADS(true, 8); else HEADS(false, 8); }
   else if (A <= 24) { if (train) HEADS(true, 24); else HEADS(false, 24); }
   else { if (train) HEADS(true, 64); else HEADS(false, 64); }
 #undef HEADS
@@ -527,16 +542,20 @@ int conv1_dw_blocks(const ga3c_net* net, int B) {
 // overlap: the caller will apply the gradients right away (train, not compute_grads): start their all-reduce as soon as
 // each part of the arena is final; returns with the train stream already waiting for the exchange
 // keep_dn1: also store dn1 (consumed on chip by the fused conv backward; kept in HBM for ga3c_net_fetch after compute_grads)
-int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, bool overlap = false, const FusedUpd* fu = nullptr, bool keep_dn1 = true) {
+// What flows back: dd1 into the hidden layer, dz / dv into the two heads; the gradient goes to the arena g.  One pass of the
+// summed loss reads t.dd1, t.dz, t.dv and writes t.grad; DUAL_RMSPROP runs two (train_grads).
+struct BwdIo { const float* dd1; const float* dz; const float* dv; float* g; };
+int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io, bool overlap = false, const FusedUpd* fu = nullptr,
+                    bool keep_dn1 = true) {
   const int A = net->A;
   const float* th = net->theta[idx];
   FusedUpd upd;
   memset(&upd, 0, sizeof upd);
   if (fu) upd = *fu;
   hipStream_t st = t.st;
-  float* g = t.grad;
+  float* g = io.g;
   HeadBwdArgs hb;
-  hb.B = B; hb.A = A; hb.d1 = t.f.d1; hb.dz = t.dz; hb.dv = t.dv; hb.lossrow = t.lossrow;
+  hb.B = B; hb.A = A; hb.d1 = t.f.d1; hb.dz = io.dz; hb.dv = io.dv; hb.lossrow = t.lossrow;
   hb.g_wp = g + OFF_WP; hb.g_bp = g + off_bp(A); hb.g_wv = g + OFF_WV; hb.g_bv = g + OFF_BV; hb.losses = t.losses;
   // dense1/w stepped inside conv_bwd, beside its MFMA phases, instead of in dense1_bwd_tile's epilogue: worth 0.5 us of the
   // 128-row step (the step's 24 MB cost conv_bwd 2.2 us where they cost the epilogue 3.5) while every workgroup of conv_bwd
@@ -548,7 +567,7 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, bool overlap = 
   if (upd.on && !fused_cb && B <= net->d1b_tile_max && net->wd_step_in_conv2_dx) upd.defer_wd = 1;
   if (B <= net->d1b_tile_max) {
     Dense1TileArgs d;
-    d.n2 = t.f.n2; d.dd1 = t.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
+    d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
     d.hb = hb;
     d.upd = upd;
     d.role_blocks = A + 2 < 14 ? A + 2 : 14;       // 242 tiles + the roles stay within one round of workgroups on 256 CUs
@@ -562,7 +581,7 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, bool overlap = 
     else hipLaunchKernelGGL(dense1_bwd_tile_kernel<0>, dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d);
   } else {
     Dense1BwdArgs d;
-    d.n2 = t.f.n2; d.dd1 = t.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
+    d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
     d.hb = hb; d.dw_gx = FLAT / 32 + A + 2; d.dw_blocks = 2 * d.dw_gx; d.dx_gx = FLAT / 32;
     d.dx_mt = dense_dx_mt(B);
     const int dx_blocks = d.dx_gx * (((B + 16 * d.dx_mt - 1) / (16 * d.dx_mt) + 3) / 4);
@@ -655,7 +674,7 @@ int launch_rmsprop(ga3c_net* net, const float* grad, float* scales, const float*
   const float omr = 1.0f - net->cfg.rmsprop_decay;
   const int blocks = RMS_WD_BLOCKS + (int)((net->n - (int64_t)FLAT * HID + 255) / 256);
   if (clip)
-    hipLaunchKernelGGL(clip_scale_kernel, dim3(10), dim3(256), 0, st, grad, net->tt, net->cfg.grad_clip_norm, scales);
+    hipLaunchKernelGGL((clip_scale_kernel<true, TensorTable>), dim3(10), dim3(256), 0, st, grad, net->tt, net->cfg.grad_clip_norm, scales);
 #define RMS(C, M)                                                                                                \
   hipLaunchKernelGGL((rmsprop_kernel<C, M>), dim3(blocks), dim3(256), 0, st, tin, tout, net->ms, net->mom,        \
                      grad, net->n, lr, omr, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->tt, scales,  \
@@ -667,6 +686,37 @@ int launch_rmsprop(ga3c_net* net, const float* grad, float* scales, const float*
 #undef RMS
   HIPCHK(hipGetLastError());
   return GA3C_OK;
+}
+
+// the two optimizers' step of DUAL_RMSPROP in one pass (rmsprop_dual_kernel); grad: 2n floats, policy then value.  Both
+// gradients were taken at the same weights; the step is theta' = (theta - D_v) - D_p in f32 -- the value optimizer's step
+// first, then the policy optimizer's, each from its own slots (TF orders the two train ops not at all: DESIGN.md 8c)
+int launch_rmsprop_dual(ga3c_net* net, const float* grad, float* scales, const float* tin, float* tout, float* pk_out,
+                        float lr, hipStream_t st) {
+  const bool clip = net->cfg.flags & GA3C_FLAG_GRAD_CLIP;
+  const bool mom = net->cfg.rmsprop_momentum != 0.0f;
+  const float omr = 1.0f - net->cfg.rmsprop_decay;
+  const int blocks = RMS_WD_BLOCKS + (int)((net->n - (int64_t)FLAT * HID + 255) / 256);
+  if (clip)   // tf.clip_by_norm of every gradient tensor of both costs (NetworkVP_discrate.py:108-117): 20 scales
+    hipLaunchKernelGGL((clip_scale_kernel<false, TensorTable2>), dim3(20), dim3(256), 0, st, grad, net->tt2, net->cfg.grad_clip_norm,
+                       scales);
+#define RMSD(C, M)                                                                                                        \
+  hipLaunchKernelGGL((rmsprop_dual_kernel<C, M>), dim3(blocks), dim3(256), 0, st, tin, tout, net->ms, net->mom, net->ms_v, \
+                     net->mom_v, grad, net->n, lr, omr, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->tt,     \
+                     scales, pk_out)
+  if (clip && mom) RMSD(true, true);
+  else if (clip) RMSD(true, false);
+  else if (mom) RMSD(false, true);
+  else RMSD(false, false);
+#undef RMSD
+  HIPCHK(hipGetLastError());
+  return GA3C_OK;
+}
+
+// the optimizer step of a train lane's gradients: one RMSProp, or the two of DUAL_RMSPROP
+int launch_update(ga3c_net* net, TrainLane& t, const float* tin, float* tout, float* pk_out, float lr) {
+  if (net->dual) return launch_rmsprop_dual(net, t.grad, t.scales, tin, tout, pk_out, lr, t.st);
+  return launch_rmsprop(net, t.grad, t.scales, tin, tout, pk_out, lr, t.st);
 }
 
 // forward on a prediction lane: pick the current weights under the shared lock
@@ -837,7 +887,25 @@ void adopt_buffer(ga3c_net* net, int buf, uint64_t seq) {
 // caller steps the optimizer right away (train, not compute_grads).  Then (a) with a communicator the exchange is started
 // inside the backward pass, and (b) without one, and without clipping, the backward kernels apply RMSProp themselves to
 // the elements whose gradient they complete (FusedUpd): train_apply then has nothing left to launch.
+//
+// DUAL_RMSPROP: one forward pass with the two terms of dd1 apart, then one backward pass per cost, both on the same
+// weights theta[idx]: cost_p's (dd1 = its term, dz, dv = 0) into t.grad[0, n), cost_v's (its term, dz = 0, dv) into
+// t.grad[n, 2n).  A head's gradient under the other cost is zero, so the two halves sum to the single-cost gradient.
+// The optimizers are never fused into the backward kernels and the exchange is one all-reduce of both halves behind them.
 int train_grads(ga3c_net* net, TrainLane& t, int B, float beta, bool will_apply = false, float lr = 0.f) {
+  if (net->dual) {
+    int idx;
+    {
+      std::shared_lock<std::shared_mutex> lk(net->wmu);
+      idx = net->latest;
+    }
+    CHK(launch_forward(net, t.f, idx, B, t.st, true, &t, beta, nullptr, nullptr, nullptr, true));
+    t.exchanged = false;
+    t.stepped = false;
+    CHK(launch_backward(net, t, idx, B, BwdIo{t.dd1, t.dz, t.zeros, t.grad}, false, nullptr, !will_apply));
+    CHK(launch_backward(net, t, idx, B, BwdIo{t.dd1_v, t.zeros, t.dv, t.grad + net->n}, false, nullptr, !will_apply));
+    return GA3C_OK;
+  }
   const bool fuse = will_apply && net->fused_update && !net->comm && !(net->cfg.flags & GA3C_FLAG_GRAD_CLIP) &&
                     B <= net->d1b_tile_max;
   int idx, other;
@@ -856,7 +924,7 @@ int train_grads(ga3c_net* net, TrainLane& t, int B, float beta, bool will_apply 
     fu.lr = lr; fu.omr = 1.0f - net->cfg.rmsprop_decay; fu.mu = net->cfg.rmsprop_momentum; fu.eps = net->cfg.rmsprop_epsilon;
     fu.on = 1;
   }
-  CHK(launch_backward(net, t, idx, B, t.exchanged, fuse ? &fu : nullptr, !will_apply));
+  CHK(launch_backward(net, t, idx, B, BwdIo{t.dd1, t.dz, t.dv, t.grad}, t.exchanged, fuse ? &fu : nullptr, !will_apply));
   t.stepped = fuse;
   t.stepped_other = other;
   return GA3C_OK;
@@ -876,16 +944,16 @@ int train_apply(ga3c_net* net, TrainLane& t, float lr) {
     // (Server.py:132-134, TF use_locking=False): every lane updates theta / ms in place from its own stream; reads by
     // other lanes may see a step half applied, and two optimizer kernels may race on an element.
     const int idx = net->latest;
-    CHK(launch_rmsprop(net, t.grad, t.scales, net->theta[idx], net->theta[idx], net->theta_pk[idx], lr, t.st));
+    CHK(launch_update(net, t, net->theta[idx], net->theta[idx], net->theta_pk[idx], lr));
     net->step.fetch_add(1);
     return GA3C_OK;
   }
   if (net->comm && !t.exchanged)       // (train_grads has already exchanged the gradients when it knew a step would follow)
-    NCCLCHK(ncclAllReduce(t.grad, t.grad, (size_t)net->n, ncclFloat, ncclSum, net->comm, t.st));
+    NCCLCHK(ncclAllReduce(t.grad, t.grad, (size_t)net->n * (net->dual ? 2 : 1), ncclFloat, ncclSum, net->comm, t.st));
   t.exchanged = false;
   int idx, other;
   CHK(claim_other_buffer(net, t, &idx, &other));
-  CHK(launch_rmsprop(net, t.grad, t.scales, net->theta[idx], net->theta[other], net->theta_pk[other], lr, t.st));
+  CHK(launch_update(net, t, net->theta[idx], net->theta[other], net->theta_pk[other], lr));
   return publish_other_buffer(net, t, other);
 }
 
@@ -1351,11 +1419,15 @@ int alloc_train_lane(ga3c_net* net, TrainLane& t, float* shared_grad) {
   CHK(dmalloc(&t.dn1, (size_t)maxB * N1S));
   CHK(dmalloc(&t.slab2, (size_t)256 * SLAB2));   // conv2_dw: at most 256 sample groups
   CHK(dmalloc(&t.slab1, (size_t)512 * SLAB1));   // conv1_dw: at most 512 workgroups
-  CHK(dmalloc(&t.scales, 16));
+  CHK(dmalloc(&t.scales, net->dual ? 32 : 16));
+  if (net->dual) {
+    CHK(dmalloc(&t.dd1_v, (size_t)maxB * HID));
+    CHK(dmalloc(&t.zeros, (size_t)maxB * A));     // never written
+  }
   if (shared_grad) {
     t.grad = shared_grad;
   } else {
-    CHK(dmalloc(&t.grad, (size_t)net->n));
+    CHK(dmalloc(&t.grad, (size_t)net->n * (net->dual ? 2 : 1)));
     t.owns_grad = true;
   }
   HIPCHK(hipHostMalloc((void**)&t.h_out, ((size_t)maxB * (2 * A + 1) + 4) * sizeof(float), hipHostMallocDefault));
@@ -1384,7 +1456,7 @@ void free_train_lane(TrainLane& t) {
   t.f.x = nullptr;
   t.f.xu8 = nullptr;
   free_fwd(t.f);
-  for (float* p : {t.dz, t.dv, t.lossrow, t.dd1, t.dn2, t.dn1, t.slab2, t.slab1, t.scales})
+  for (float* p : {t.dz, t.dv, t.lossrow, t.dd1, t.dn2, t.dn1, t.slab2, t.slab1, t.scales, t.dd1_v, t.zeros})
     if (p) (void)hipFree(p);
   if (t.owns_grad && t.grad) (void)hipFree(t.grad);
   if (t.h_out) (void)hipHostFree(t.h_out);
@@ -1582,6 +1654,12 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
   const int A = net->A, maxB = net->maxB;
   const int64_t offs[11] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WD, OFF_BD, OFF_WV, OFF_BV, OFF_WP, off_bp(A), net->n};
   for (int i = 0; i < 11; ++i) net->tt.off[i] = offs[i];
+  for (int i = 0; i < 10; ++i) {
+    net->tt2.off[i] = offs[i];
+    net->tt2.off[10 + i] = net->n + offs[i];
+  }
+  net->tt2.off[20] = 2 * net->n;
+  net->dual = (cfg->flags & GA3C_FLAG_DUAL_RMSPROP) != 0;
 #define TRY(expr)                    \
   do {                               \
     int _r = (expr);                 \
@@ -1607,12 +1685,17 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
     TRY(dmalloc(&net->theta_pk[i], (size_t)PK_FLOATS));
     TRYHIP(hipEventCreateWithFlags(&net->theta_ready[i], hipEventDisableTiming));
   }
-  TRY(dmalloc(&net->grad, (size_t)net->n));
+  TRY(dmalloc(&net->grad, (size_t)net->n * (net->dual ? 2 : 1)));
   TRY(dmalloc(&net->ms, (size_t)net->n));
   TRY(dmalloc(&net->mom, (size_t)net->n));
+  if (net->dual) {
+    TRY(dmalloc(&net->ms_v, (size_t)net->n));
+    TRY(dmalloc(&net->mom_v, (size_t)net->n));
+  }
   {   // RMSProp `ms` slot starts at ones (TF RMSPropOptimizer._create_slots)
     std::vector<float> ones((size_t)net->n, 1.0f);
     TRYHIP(hipMemcpy(net->ms, ones.data(), (size_t)net->n * sizeof(float), hipMemcpyHostToDevice));
+    if (net->dual) TRYHIP(hipMemcpy(net->ms_v, ones.data(), (size_t)net->n * sizeof(float), hipMemcpyHostToDevice));
   }
   int nl = cfg->predict_lanes > 0 ? cfg->predict_lanes : 2;
   if (nl > 16) nl = 16;
@@ -1703,7 +1786,7 @@ int ga3c_net_destroy(ga3c_net* net) {
     if (net->theta_pk[i]) (void)hipFree(net->theta_pk[i]);
     if (net->theta_ready[i]) (void)hipEventDestroy(net->theta_ready[i]);
   }
-  for (float* p : {net->grad, net->ms, net->mom})
+  for (float* p : {net->grad, net->ms, net->mom, net->ms_v, net->mom_v})
     if (p) (void)hipFree(p);
   delete net;
   return GA3C_OK;
@@ -1715,12 +1798,17 @@ int ga3c_net_param_count(ga3c_net* net, int64_t* count) {
   return GA3C_OK;
 }
 
+// 0 weights, 1 / 2 the `ms` / `mom` slots of the optimizer of cost_all (of cost_p under DUAL_RMSPROP), 3 the last gradient
+// (cost_p's under DUAL_RMSPROP); DUAL_RMSPROP only: 4 / 5 the value optimizer's `ms` / `mom`, 6 the last cost_v gradient
 static float* arena_ptr(ga3c_net* net, int which) {
   switch (which) {
     case 0: return net->theta[net->latest];
     case 1: return net->ms;
     case 2: return net->mom;
     case 3: return net->grad;
+    case 4: return net->dual ? net->ms_v : nullptr;
+    case 5: return net->dual ? net->mom_v : nullptr;
+    case 6: return net->dual ? net->grad + net->n : nullptr;
     default: return nullptr;
   }
 }
@@ -1735,7 +1823,7 @@ int ga3c_net_get_arena(ga3c_net* net, int32_t which, float* out, int64_t count) 
   std::unique_lock<std::shared_mutex> lk(net->wmu);
   CHK(sync_all(net));
   float* src = arena_ptr(net, which);
-  if (!src) return fail(GA3C_EINVAL, "arena selector %d not in [0,3]", which);
+  if (!src) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, net->dual ? 6 : 3);
   HIPCHK(hipMemcpy(out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
   return GA3C_OK;
 }
@@ -1750,7 +1838,7 @@ int ga3c_net_set_arena(ga3c_net* net, int32_t which, const float* in, int64_t co
   std::unique_lock<std::shared_mutex> lk(net->wmu);
   CHK(sync_all(net));
   float* dst = arena_ptr(net, which);
-  if (!dst) return fail(GA3C_EINVAL, "arena selector %d not in [0,3]", which);
+  if (!dst) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, net->dual ? 6 : 3);
   HIPCHK(hipMemcpy(dst, in, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
   if (which == 0) {
     hipLaunchKernelGGL(pack_wd_kernel, dim3(KSTEPS_DENSE), dim3(256), 0, net->tr.st, net->theta[net->latest] + OFF_WD,
@@ -1809,7 +1897,10 @@ static int param_copy(ga3c_net* net, const char* name, int which, float* out, co
   ParamInfo pi;
   if (!param_lookup(net, name, &pi)) return fail(GA3C_EINVAL, "no variable named %s", name);
   if (count != pi.count) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)pi.count, (long long)count);
-  if (which < 0 || which > (in ? 2 : 3)) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, in ? 2 : 3);
+  // set: weights and optimizer slots only (0..2, and 4..5 under DUAL_RMSPROP); get: any arena
+  const bool slot_v = net->dual && (which == 4 || which == 5 || (!in && which == 6));
+  if (!slot_v && (which < 0 || which > (in ? 2 : 3)))
+    return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]%s", which, in ? 2 : 3, net->dual ? (in ? " or [4,5]" : " or [4,6]") : "");
   HIPCHK(hipSetDevice(net->cfg.device));
   std::lock_guard<std::mutex> tl(net->tr.mu);
   std::vector<std::unique_lock<std::mutex>> xl;
@@ -1842,8 +1933,98 @@ int ga3c_net_set_param(ga3c_net* net, const char* name, int32_t which, const flo
   return param_copy(net, name, which, nullptr, in, count);
 }
 
+// The members of a DUAL_RMSPROP checkpoint beside "<name>:0" and "step": (variable, suffix, arena).  Derived, not observed (no
+// TensorFlow here; unverified against a TF run): both branches build the value optimizer first (NetworkVP_discrate.py:109-112
+// and :126), TF-1's RMSPropOptimizer._create_slots makes the `rms` slot, then the `momentum` slot of each variable, both named
+// after the optimizer ("RMSProp"), and uniquifies a repeated name with _1, _2, ...  An optimizer has no slot for a variable
+// its cost has no gradient for.  So the trunk carries the value optimizer's slots as RMSProp / RMSProp_1 and the policy
+// optimizer's as RMSProp_2 / RMSProp_3, logits_v/* the value optimizer's and logits_p/* the policy optimizer's as
+// RMSProp / RMSProp_1 -- the single optimizer's rule (ga3c_net_save) applied twice.
+namespace {
+struct SlotMember { int param; const char* suffix; int which; };
+// (appends to `out`, after the ten "<name>:0" members of arena 0)
+void dual_members(std::vector<SlotMember>& out) {
+  for (int i = 0; i < NPARAMS; ++i) out.push_back({i, ":0", 0});
+  for (int i = 0; i < NPARAMS; ++i) {
+    const std::string base(PARAM_NAMES[i]);
+    if (base.compare(0, 9, "logits_p/") != 0) {     // the value optimizer: every variable but logits_p/*
+      out.push_back({i, "/RMSProp:0", 4});
+      out.push_back({i, "/RMSProp_1:0", 5});
+    }
+    if (base.compare(0, 9, "logits_v/") == 0) continue;
+    const bool trunk = base.compare(0, 7, "logits_") != 0;    // the policy optimizer: every variable but logits_v/*
+    out.push_back({i, trunk ? "/RMSProp_2:0" : "/RMSProp:0", 1});
+    out.push_back({i, trunk ? "/RMSProp_3:0" : "/RMSProp_1:0", 2});
+  }
+}
+
+int save_dual(ga3c_net* net, const char* path) {
+  const int which[5] = {0, 1, 2, 4, 5};
+  std::vector<float> arena[7];
+  for (int w : which) {
+    arena[w].resize((size_t)net->n);
+    CHK(ga3c_net_get_arena(net, w, arena[w].data(), net->n));
+  }
+  std::vector<ga3c_ckpt::Member> members;
+  ga3c_ckpt::Member st;
+  st.name = "step"; st.descr = "<i8";
+  const int64_t step = net->step.load();
+  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
+  members.push_back(st);
+  std::vector<SlotMember> list;
+  dual_members(list);
+  for (const SlotMember& sm : list) {
+    ParamInfo pi;
+    param_lookup(net, PARAM_NAMES[sm.param], &pi);
+    ga3c_ckpt::Member m;
+    m.name = std::string(PARAM_NAMES[sm.param]) + sm.suffix;
+    m.descr = "<f4";
+    m.shape.assign(pi.shape, pi.shape + pi.ndim);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[sm.which].data() + pi.off);
+    m.bytes.assign(src, src + (size_t)pi.count * sizeof(float));
+    members.push_back(std::move(m));
+  }
+  std::string err;
+  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  return GA3C_OK;
+}
+
+// load of a DUAL_RMSPROP checkpoint (the members of save_dual): everything is checked before the first arena is
+// written.  Slot regions no optimizer has a slot for are reset to the slots' initial values (ms = 1, mom = 0).
+int load_dual(ga3c_net* net, const char* path, const std::map<std::string, ga3c_ckpt::Member>& members) {
+  const int which[5] = {0, 1, 2, 4, 5};
+  std::vector<float> arena[7];
+  for (int w : which) arena[w].assign((size_t)net->n, (w == 1 || w == 4) ? 1.0f : 0.0f);
+  std::vector<SlotMember> list;
+  dual_members(list);
+  for (const SlotMember& sm : list) {
+    ParamInfo pi;
+    param_lookup(net, PARAM_NAMES[sm.param], &pi);
+    const std::string key = std::string(PARAM_NAMES[sm.param]) + sm.suffix;
+    auto it = members.find(key);
+    if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s (not a DUAL_RMSPROP checkpoint?)", path, key.c_str());
+    const ga3c_ckpt::Member& m = it->second;
+    int64_t elems = 1;
+    for (int64_t d : m.shape) elems *= d;
+    if (m.descr != "<f4" || elems != pi.count || m.bytes.size() != (size_t)pi.count * sizeof(float))
+      return fail(GA3C_ESTATE, "%s: %s is %s with %lld elements, this network wants <f4 with %lld", path, key.c_str(),
+                  m.descr.c_str(), (long long)elems, (long long)pi.count);
+    memcpy(arena[sm.which].data() + pi.off, m.bytes.data(), m.bytes.size());
+  }
+  auto st = members.find("step");
+  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
+    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
+  int64_t step = 0;
+  memcpy(&step, st->second.bytes.data(), 8);
+  for (int w : which) CHK(ga3c_net_set_arena(net, w, arena[w].data(), net->n));
+  net->step.store(step);
+  return GA3C_OK;
+}
+}  // namespace
+
 int ga3c_net_save(ga3c_net* net, const char* path) {
   if (!net || !path) return fail(GA3C_EINVAL, "null argument");
+  if (net->dual) return save_dual(net, path);
   std::vector<float> arena[3];
   for (int w = 0; w < 3; ++w) {
     arena[w].resize((size_t)net->n);
@@ -1879,6 +2060,10 @@ int ga3c_net_load(ga3c_net* net, const char* path) {
   std::map<std::string, ga3c_ckpt::Member> members;
   std::string err;
   if (!ga3c_ckpt::read_npz(path, &members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  if (net->dual) return load_dual(net, path, members);
+  // a DUAL_RMSPROP checkpoint holds every member of a single-optimizer one (its value optimizer's slots of the trunk under
+  // the single optimizer's names) and more: it is refused, not read as half of itself
+  if (members.count("conv11/w/RMSProp_2:0")) return fail(GA3C_ESTATE, "%s is a DUAL_RMSPROP checkpoint; this network has one optimizer", path);
   const char* suffix[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};
   std::vector<float> arena[3];
   for (int w = 0; w < 3; ++w) arena[w].resize((size_t)net->n);
@@ -3048,7 +3233,7 @@ int ga3c_net_allreduce_grads(ga3c_net* net) {
   if (!net->comm) return fail(GA3C_ESTATE, "no communicator attached");
   HIPCHK(hipSetDevice(net->cfg.device));
   std::lock_guard<std::mutex> tl(net->tr.mu);
-  NCCLCHK(ncclAllReduce(net->grad, net->grad, (size_t)net->n, ncclFloat, ncclSum, net->comm, net->tr.st));
+  NCCLCHK(ncclAllReduce(net->grad, net->grad, (size_t)net->n * (net->dual ? 2 : 1), ncclFloat, ncclSum, net->comm, net->tr.st));
   HIPCHK(hipStreamSynchronize(net->tr.st));
   return GA3C_OK;
 }

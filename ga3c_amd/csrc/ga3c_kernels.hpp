@@ -872,8 +872,9 @@ struct HeadArgs {
 };
 
 // NR rows per wave (rows[j] < 0: none; wave-uniform): every load of every row is requested before the first reduction
-template <bool TRAIN, int AMAX, int NR>
-__device__ __forceinline__ void heads_rows(const HeadArgs& h, const int (&rows)[NR], int lane) {
+// DUAL (heads_dual_kernel): h.dd1 receives the policy term 1[d1>0] dz Wp^T and dd1_v the value term 1[d1>0] dv Wv^T
+template <bool TRAIN, int AMAX, int NR, bool DUAL = false>
+__device__ __forceinline__ void heads_rows(const HeadArgs& h, const int (&rows)[NR], int lane, float* dd1_v = nullptr) {
   // this lane's 4 hidden units x A policy weights are 4*A contiguous floats: issue every load up front
   float wreg[4][AMAX];
   const float* wp = h.wp + (size_t)(4 * lane) * h.A;
@@ -964,7 +965,24 @@ __device__ __forceinline__ void heads_rows(const HeadArgs& h, const int (&rows)[
         dz = s * (gs - dot);
       }
       if (mine) h.dz[(size_t)b * h.A + lane] = dz;
-      {
+      if (DUAL) {     // the two costs' upstream gradients apart (Config.DUAL_RMSPROP): one backward pass each
+        const float dvv = v - yy;
+        f32x4 ddv = {dvv * wv4[0], dvv * wv4[1], dvv * wv4[2], dvv * wv4[3]};
+        f32x4 ddp = zero4();
+#pragma unroll
+        for (int o = 0; o < AMAX; ++o) {
+          const float dzo = __shfl(dz, o, 64);          // 0 for lanes >= A
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ddp[q] += dzo * wreg[q][o];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          ddp[q] = d[q] > 0.f ? ddp[q] : 0.f;
+          ddv[q] = d[q] > 0.f ? ddv[q] : 0.f;
+        }
+        *reinterpret_cast<f32x4*>(h.dd1 + (size_t)b * HID + 4 * lane) = ddp;
+        *reinterpret_cast<f32x4*>(dd1_v + (size_t)b * HID + 4 * lane) = ddv;
+      } else {
         const float dvv = v - yy;
         f32x4 dd = {dvv * wv4[0], dvv * wv4[1], dvv * wv4[2], dvv * wv4[3]};
 #pragma unroll
@@ -993,6 +1011,15 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs h) {
   if (b >= h.B) return;   // wave-uniform
   const int rows[1] = {b};
   heads_rows<TRAIN, AMAX, 1>(h, rows, threadIdx.x & 63);
+}
+
+// heads_kernel<true, AMAX> with dd1 written as its two terms, h.dd1 (policy) and dd1_v (value); losses, dz and dv as there
+template <int AMAX>
+__global__ __launch_bounds__(256) void heads_dual_kernel(HeadArgs h, float* dd1_v) {
+  const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (b >= h.B) return;   // wave-uniform
+  const int rows[1] = {b};
+  heads_rows<true, AMAX, 1, true>(h, rows, threadIdx.x & 63, dd1_v);
 }
 
 // ------------------------------------------------------------------ heads backward (weight gradients)
@@ -2390,16 +2417,21 @@ __global__ __launch_bounds__(1024) void slab_reduce_kernel(SlabSet s0, SlabSet s
 }
 
 // ------------------------------------------------------------------ gradient clipping (optional)
-// tf.clip_by_average_norm per tensor: scale = clip / max(||g||_2 / n, clip).  One block per tensor.
+// AVG: tf.clip_by_average_norm per tensor, scale = clip / max(||g||_2 / n, clip) (NetworkVP_discrate.py:121);
+// otherwise tf.clip_by_norm, scale = clip / max(||g||_2, clip) (the DUAL_RMSPROP branch, :108-117).  One block per
+// tensor of the table TT: TensorTable (the 10 tensors of one gradient arena) or TensorTable2 (the 20 of the policy and
+// the value gradient arena laid end to end).
 struct TensorTable { int64_t off[11]; };
-__global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict__ grad, TensorTable tt, float clip,
+struct TensorTable2 { int64_t off[21]; };
+template <bool AVG, class TT>
+__global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict__ grad, TT tt, float clip,
                                                          float* __restrict__ scales) {
   __shared__ float sh[4];
   const int64_t lo = tt.off[blockIdx.x], hi = tt.off[blockIdx.x + 1];
   float s = 0.f;
   for (int64_t i = lo + threadIdx.x; i < hi; i += 256) s += grad[i] * grad[i];
   s = block_sum_256(s, sh);
-  if (threadIdx.x == 0) scales[blockIdx.x] = clip / fmaxf(sqrtf(s) / (float)(hi - lo), clip);
+  if (threadIdx.x == 0) scales[blockIdx.x] = clip / fmaxf(AVG ? sqrtf(s) / (float)(hi - lo) : sqrtf(s), clip);
 }
 
 // ------------------------------------------------------------------ RMSProp (TF-1.x ApplyRMSProp arithmetic)
@@ -2461,6 +2493,93 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(const float* __restrict__ 
       sc = scales[ti];
     }
     const float tn = rmsprop_one<CLIP, MOM>(i, theta_in, theta_out, ms, mom, grad, lr, one_minus_rho, mu, eps, sc);
+    store_conv_packs(pk_out, i, tn);
+  }
+}
+
+// ------------------------------------------------------------------ two RMSProp optimizers (Config.DUAL_RMSPROP)
+// NetworkVP_discrate.py:87-99,108-117,126-127: cost_p and cost_v each have an RMSProp optimizer of the same lr / decay /
+// momentum / epsilon.  grad holds the policy gradient at [0, n) and the value gradient at [n, 2n), both taken at the same
+// weights.  Element i of theta gets the value step first, then the policy step: theta' = (theta - D_v) - D_p in f32, each D
+// from its own optimizer's slots.  TF-1 drops a variable with no gradient from an optimizer: the value step skips
+// logits_p/* (no path from cost_v), the policy step skips logits_v/* (cost_p sees v only through tf.stop_gradient), and
+// the slots of a skipped region are neither read nor written.  Blocks as rmsprop_kernel: [0, 242) one 16-row group of
+// dense1/w each, plus its fragment-ordered copy; the rest sweep the arena and keep the packed conv filters current.
+// CLIP: scales[0, 10) are the policy tensors' clip_by_norm factors, scales[10, 20) the value tensors'.
+template <bool CLIP, bool MOM>
+__device__ __forceinline__ float rmsprop_dual_one(int64_t i, int64_t n, const float* __restrict__ theta_in,
+                                                  float* __restrict__ theta_out, float* __restrict__ ms_p,
+                                                  float* __restrict__ mom_p, float* __restrict__ ms_v,
+                                                  float* __restrict__ mom_v, const float* __restrict__ grad, float lr,
+                                                  float one_minus_rho, float mu, float eps, float sc_p, float sc_v,
+                                                  bool do_p, bool do_v) {
+  float t = theta_in[i];
+  if (do_v) {
+    float g = grad[n + i];
+    if (CLIP) g *= sc_v;
+    float m = ms_v[i];
+    m += (g * g - m) * one_minus_rho;
+    ms_v[i] = m;
+    float step = (g * lr) / sqrtf(eps + m);
+    if (MOM) {
+      step = mom_v[i] * mu + step;
+      mom_v[i] = step;
+    }
+    t = t - step;
+  }
+  if (do_p) {
+    float g = grad[i];
+    if (CLIP) g *= sc_p;
+    float m = ms_p[i];
+    m += (g * g - m) * one_minus_rho;
+    ms_p[i] = m;
+    float step = (g * lr) / sqrtf(eps + m);
+    if (MOM) {
+      step = mom_p[i] * mu + step;
+      mom_p[i] = step;
+    }
+    t = t - step;
+  }
+  theta_out[i] = t;
+  return t;
+}
+
+template <bool CLIP, bool MOM>
+__global__ __launch_bounds__(256) void rmsprop_dual_kernel(const float* __restrict__ theta_in, float* __restrict__ theta_out,
+                                                           float* __restrict__ ms_p, float* __restrict__ mom_p,
+                                                           float* __restrict__ ms_v, float* __restrict__ mom_v,
+                                                           const float* __restrict__ grad, int64_t n, float lr,
+                                                           float one_minus_rho, float mu, float eps, TensorTable tt,
+                                                           const float* __restrict__ scales, float* __restrict__ pk_out) {
+  if (blockIdx.x < RMS_WD_BLOCKS) {
+    const int s = blockIdx.x, col = threadIdx.x;
+    const float sp = CLIP ? scales[4] : 1.0f, sv = CLIP ? scales[14] : 1.0f;   // tensor 4 = dense1/w
+    float v[16];
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk)
+      v[kk] = rmsprop_dual_one<CLIP, MOM>(OFF_WD + (int64_t)(s * 16 + kk) * HID + col, n, theta_in, theta_out, ms_p, mom_p,
+                                          ms_v, mom_v, grad, lr, one_minus_rho, mu, eps, sp, sv, true, true);
+    float* dst = pk_out + ((size_t)s * HID + col) * 16;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      *reinterpret_cast<f32x4*>(dst + 4 * q) = (f32x4){v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+    return;
+  }
+  const int64_t rest = OFF_WD + (n - OFF_BD);
+  for (int64_t j = (int64_t)(blockIdx.x - RMS_WD_BLOCKS) * 256 + threadIdx.x; j < rest;
+       j += (int64_t)(gridDim.x - RMS_WD_BLOCKS) * 256) {
+    const int64_t i = j < OFF_WD ? j : j - OFF_WD + OFF_BD;
+    float sp = 1.0f, sv = 1.0f;
+    if (CLIP) {
+      int ti = 0;
+#pragma unroll
+      for (int k = 1; k < 10; ++k) ti += (i >= tt.off[k]) ? 1 : 0;
+      sp = scales[ti];
+      sv = scales[10 + ti];
+    }
+    const bool head_v = i >= OFF_WV && i < OFF_WP, head_p = i >= OFF_WP;
+    const float tn = rmsprop_dual_one<CLIP, MOM>(i, n, theta_in, theta_out, ms_p, mom_p, ms_v, mom_v, grad, lr, one_minus_rho,
+                                                 mu, eps, sp, sv, !head_v, !head_p);
     store_conv_packs(pk_out, i, tn);
   }
 }

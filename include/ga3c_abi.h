@@ -31,6 +31,8 @@ extern "C" {
 
 #define GA3C_FLAG_LOG_SOFTMAX 1u   /* Config.USE_LOG_SOFTMAX branch, NetworkVP_discrate.py:64-71 */
 #define GA3C_FLAG_GRAD_CLIP 2u     /* Config.USE_GRAD_CLIP, tf.clip_by_average_norm, :120-123 */
+#define GA3C_FLAG_DUAL_RMSPROP 4u  /* Config.DUAL_RMSPROP: one RMSProp optimizer per cost (cost_p, cost_v), :87-99,108-117,126-127;
+                                      with GA3C_FLAG_GRAD_CLIP, tf.clip_by_norm per gradient tensor instead */
 
 #define GA3C_STATE_FLOATS 28224    /* 84*84*4 (Config.py:90-92) */
 #define GA3C_MAX_ACTIONS 64
@@ -71,7 +73,11 @@ int ga3c_net_destroy(ga3c_net* net);
  * conv11/w[8,8,4,16] conv11/b[16] conv12/w[4,4,16,32] conv12/b[32] dense1/w[3872,256]
  * dense1/b[256] logits_v/w[256,1] logits_v/b[1] logits_p/w[256,A] logits_p/b[A].
  * Replaces get_variable_value / tf.train.Saver (NetworkVP.py:62-64,267-288).
- * which: 0 = weights, 1 = RMSProp `ms` slot, 2 = RMSProp `mom` slot, 3 = last gradient. */
+ * which: 0 = weights, 1 = RMSProp `ms` slot, 2 = RMSProp `mom` slot, 3 = last gradient.
+ * With GA3C_FLAG_DUAL_RMSPROP, 1 / 2 / 3 belong to the optimizer of cost_p (which stands in for cost_all) and
+ * 4 = the value optimizer's `ms`, 5 = its `mom`, 6 = the last cost_v gradient; without the flag 4..6 are GA3C_EINVAL.
+ * Slot regions the reference has no slot for (the value optimizer's on logits_p/{w,b}, the policy optimizer's on
+ * logits_v/{w,b}) keep their initial values (ms = 1, mom = 0): no step writes them. */
 int ga3c_net_param_count(ga3c_net* net, int64_t* count);
 int ga3c_net_get_arena(ga3c_net* net, int32_t which, float* out, int64_t count);
 int ga3c_net_set_arena(ga3c_net* net, int32_t which, const float* in, int64_t count);
@@ -83,7 +89,8 @@ int ga3c_net_set_step(ga3c_net* net, int64_t step);
  *   ga3c_net_param_name(i)       "conv11/w", "conv11/b", "conv12/w", "conv12/b", "dense1/w", "dense1/b", "logits_v/w",
  *                                "logits_v/b", "logits_p/w", "logits_p/b" (i in arena order; NULL outside [0, 10))
  *   ga3c_net_param_info          offset and element count of the variable inside the arena, its rank and shape (<= 4 dims)
- *   ga3c_net_get_param/set_param one variable of arena `which` (0 weights, 1 `ms`, 2 `mom`, 3 last gradient; set: 0..2);
+ *   ga3c_net_get_param/set_param one variable of arena `which` (0 weights, 1 `ms`, 2 `mom`, 3 last gradient; set: 0..2;
+ *                                GA3C_FLAG_DUAL_RMSPROP adds 4 / 5 / 6 as in ga3c_net_get_arena, set: 4..5);
  *                                `count` must equal the variable's element count.  A name may carry TensorFlow's ":0". */
 int32_t ga3c_net_num_params(ga3c_net* net);
 const char* ga3c_net_param_name(ga3c_net* net, int32_t index);
@@ -94,7 +101,12 @@ int ga3c_net_set_param(ga3c_net* net, const char* name, int32_t which, const flo
  * file.  The format is an uncompressed .npz (numpy.savez / numpy.load): members "<name>:0", "<name>/RMSProp:0",
  * "<name>/RMSProp_1:0" with the variable's shape, and "step" (int64 scalar); a TensorFlow checkpoint cannot be written
  * without TensorFlow.  The file name convention checkpoints/<model>_%08d (NetworkVP.py:267-272) is the caller's.  load refuses
- * a file whose shapes do not match this network (another action count) and leaves the network untouched then. */
+ * a file whose shapes do not match this network (another action count) and leaves the network untouched then.
+ * GA3C_FLAG_DUAL_RMSPROP: the slots are named as TF-1 would name two optimizers built value first (derived, not observed):
+ * conv11/ conv12/ dense1/ variables carry the value optimizer's "/RMSProp:0" (ms) and "/RMSProp_1:0" (mom) and the policy
+ * optimizer's "/RMSProp_2:0" and "/RMSProp_3:0"; logits_v/{w,b} the value optimizer's and logits_p/{w,b} the policy optimizer's
+ * "/RMSProp:0" and "/RMSProp_1:0".  A dual network loads only such a file, a single-optimizer network only the other
+ * kind (GA3C_ESTATE otherwise, network untouched). */
 int ga3c_net_save(ga3c_net* net, const char* path);
 int ga3c_net_load(ga3c_net* net, const char* path);
 
@@ -303,6 +315,7 @@ int ga3c_net_comm_info(ga3c_net* net, int32_t* ranks, int32_t* rank, int32_t* de
 /* `iters` back-to-back all-reduces of the gradient arena between two HIP events on the train stream (bench.py's
  * allreduce_us).  Collective: every rank of the communicator calls it. */
 int ga3c_net_time_allreduce(ga3c_net* net, int32_t iters, float* elapsed_ms);
+/* Sums the gradient arena (both halves, 2n floats, under GA3C_FLAG_DUAL_RMSPROP) over the ranks, on the train stream. */
 int ga3c_net_allreduce_grads(ga3c_net* net);
 
 #ifdef __cplusplus
