@@ -53,8 +53,9 @@ class Config:
     TRAINING_MIN_BATCH_SIZE = 0
     MIN_POLICY = 0.0
     USE_LOG_SOFTMAX = False
-    DISCRATE_INPUT = True               # (sic) discrete action space: softmax policy head
-    CONTINUOUS_INPUT = False
+    DISCRATE_INPUT = True               # (sic) discrete action space: softmax policy head; derived, = not CONTINUOUS_INPUT
+    CONTINUOUS_INPUT = False            # angle-output policy head, the action IS the prediction vector in (-1, 1]^A
+                                        # (NetworkVP.py:92,95-105,175-204, ProcessAgent.py:134-137); DESIGN §8d
     USE_DDPG = False
     USE_REPLAY_MEMORY = False
     USE_NETWORK_TESTER = False
@@ -113,3 +114,14 @@ class Config:
     FRAME_HEIGHT = 210
     FRAME_WIDTH = 160
     FRAME_HISTORY = 0                   # planes of history per agent on the device; 0 = derived from the queue bounds
+
+
+def resolve_action_space(explicit=()):
+    """DISCRATE_INPUT = not CONTINUOUS_INPUT, as the reference's Server.py:36-38 sets it.  `explicit`: the keys the command
+    line gave.  DISCRATE_INPUT given alone decides CONTINUOUS_INPUT; both given and contradictory (the same value) raise."""
+    if "DISCRATE_INPUT" in explicit and "CONTINUOUS_INPUT" in explicit:
+        if bool(Config.DISCRATE_INPUT) == bool(Config.CONTINUOUS_INPUT):
+            raise ValueError("DISCRATE_INPUT=%r contradicts CONTINUOUS_INPUT=%r" % (Config.DISCRATE_INPUT, Config.CONTINUOUS_INPUT))
+    elif "DISCRATE_INPUT" in explicit:
+        Config.CONTINUOUS_INPUT = not Config.DISCRATE_INPUT
+    Config.DISCRATE_INPUT = not Config.CONTINUOUS_INPUT

@@ -43,7 +43,10 @@ class Environment:
                 raise ImportError("Config.FRAME_SOURCE = 'gym' needs the gym package with Atari support (%s); the offline "
                                   "sources are 'planes' and 'rgb'" % e)
             self.gym = gym.make(Config.GAME)
-            Config.NUM_ACTIONS = int(self.gym.action_space.n)
+            # a Box action space (CONTINUOUS_INPUT: the action is the prediction vector) has shape[0] components; untested
+            # offline, as the rest of this branch
+            box = getattr(self.gym.action_space, "n", None) is None
+            Config.NUM_ACTIONS = int(self.gym.action_space.shape[0]) if box else int(self.gym.action_space.n)
             shape = self.gym.observation_space.shape
             Config.FRAME_HEIGHT, Config.FRAME_WIDTH = int(shape[0]), int(shape[1])
         self.rgb = Config.FRAME_SOURCE in ('rgb', 'gym')
@@ -91,7 +94,8 @@ class Environment:
     def step(self, action):
         self._t += 1
         if self.gym is not None:
-            res = self.gym.step(int(action))               # (obs, reward, done, info) or (obs, reward, term, trunc, info)
+            act = np.asarray(action, dtype=np.float32) if Config.CONTINUOUS_INPUT else int(action)
+            res = self.gym.step(act)                       # (obs, reward, done, info) or (obs, reward, term, trunc, info)
             self._gym_frame = np.ascontiguousarray(res[0], dtype=np.uint8)
             reward, done = float(res[1]), bool(res[2]) or (len(res) == 5 and bool(res[3]))
         else:

@@ -5,13 +5,16 @@ switched off with an empty value (`KEY=`), because bool("False") is True (SURVEY
 import sys
 
 import _native  # noqa: F401  (fail early if the libraries are not built)
-from Config import Config
+from Config import Config, resolve_action_space
 
 
 def apply_argv(argv):
+    given = set()
     for arg in argv:
         key, value = arg.split('=', 1)
         setattr(Config, key, type(getattr(Config, key))(value))
+        given.add(key)
+    resolve_action_space(given)
     if Config.PLAY_MODE:
         Config.AGENTS = 1
         Config.PREDICTORS = 1

@@ -23,22 +23,40 @@ import _native as nat
 
 PARAM_ORDER = ("conv11/w", "conv11/b", "conv12/w", "conv12/b", "dense1/w", "dense1/b",
                "logits_v/w", "logits_v/b", "logits_p/w", "logits_p/b")
+# Config.CONTINUOUS_INPUT: the angle-output policy head's two dense layers in TF creation order (NetworkVP.py:175-204)
+PARAM_ORDER_CONT = PARAM_ORDER[:8] + ("logits_p/out_x/w", "logits_p/out_x/b", "logits_p/out_y/w", "logits_p/out_y/b")
+CONT_HEAD_INIT = 0.3        # the continuous head's U(-0.3, 0.3), weights and biases alike (NetworkVP.py:194-204)
 
 
-def param_shapes(num_actions):
-    return {"conv11/w": (8, 8, 4, 16), "conv11/b": (16,), "conv12/w": (4, 4, 16, 32), "conv12/b": (32,),
-            "dense1/w": (3872, 256), "dense1/b": (256,), "logits_v/w": (256, 1), "logits_v/b": (1,),
-            "logits_p/w": (256, num_actions), "logits_p/b": (num_actions,)}
+def param_order(continuous=False):
+    return PARAM_ORDER_CONT if continuous else PARAM_ORDER
 
 
-def initial_arena(num_actions, seed):
-    """U(-d, d), d = 1/sqrt(fan_in) (NetworkVP.py:214, NetworkDNav.py:258), flat in TF variable order."""
+def param_shapes(num_actions, continuous=False):
+    shapes = {"conv11/w": (8, 8, 4, 16), "conv11/b": (16,), "conv12/w": (4, 4, 16, 32), "conv12/b": (32,),
+              "dense1/w": (3872, 256), "dense1/b": (256,), "logits_v/w": (256, 1), "logits_v/b": (1,)}
+    if continuous:
+        for xy in ("x", "y"):
+            shapes["logits_p/out_%s/w" % xy] = (256, num_actions)
+            shapes["logits_p/out_%s/b" % xy] = (num_actions,)
+    else:
+        shapes["logits_p/w"] = (256, num_actions)
+        shapes["logits_p/b"] = (num_actions,)
+    return shapes
+
+
+def initial_arena(num_actions, seed, continuous=False):
+    """U(-d, d), d = 1/sqrt(fan_in) (NetworkVP.py:214, NetworkDNav.py:258), flat in TF variable order; the continuous
+    head's variables d = 0.3 (one PCG64 stream, drawn in that order: the trunk and logits_v are the discrete net's)."""
     rng = np.random.Generator(np.random.PCG64(seed))
-    shapes = param_shapes(num_actions)
+    shapes = param_shapes(num_actions, continuous)
     parts = []
-    for name in PARAM_ORDER:
-        base = name.split("/")[0]
-        d = 1.0 / np.sqrt(np.prod(shapes[base + "/w"][:-1]))
+    for name in param_order(continuous):
+        if name.startswith("logits_p/out_"):
+            d = CONT_HEAD_INIT
+        else:
+            base = name.split("/")[0]
+            d = 1.0 / np.sqrt(np.prod(shapes[base + "/w"][:-1]))
         parts.append(rng.uniform(-d, d, size=shapes[name]).astype(np.float32).ravel())
     return np.concatenate(parts)
 
@@ -86,6 +104,9 @@ class Network:
         self.learning_rate = Config.LEARNING_RATE_START
         self.beta = Config.BETA_START
         self.log_epsilon = Config.LOG_EPSILON
+        # Config.CONTINUOUS_INPUT: p is the action vector (the angle output) and z is [hx | hy], B x 2A
+        self.continuous = bool(Config.CONTINUOUS_INPUT)
+        self.z_width = 2 * self.num_actions if self.continuous else self.num_actions
         if int(np.prod(state_dim)) != nat.STATE_FLOATS:
             raise ValueError("state_dim %r is not 84x84x4" % (state_dim,))
         if max_batch is None:
@@ -99,7 +120,8 @@ class Network:
         cfg.max_batch = self.max_batch
         cfg.flags = (nat.FLAG_LOG_SOFTMAX if Config.USE_LOG_SOFTMAX else 0) | \
                     (nat.FLAG_GRAD_CLIP if Config.USE_GRAD_CLIP else 0) | \
-                    (nat.FLAG_DUAL_RMSPROP if Config.DUAL_RMSPROP else 0)
+                    (nat.FLAG_DUAL_RMSPROP if Config.DUAL_RMSPROP else 0) | \
+                    (nat.FLAG_CONTINUOUS if self.continuous else 0)
         cfg.rmsprop_decay = Config.RMSPROP_DECAY
         cfg.rmsprop_momentum = Config.RMSPROP_MOMENTUM
         cfg.rmsprop_epsilon = Config.RMSPROP_EPSILON
@@ -123,12 +145,13 @@ class Network:
         self.param_count = n.value
         self._offsets = {}
         off = 0
-        for name in PARAM_ORDER:
-            size = int(np.prod(param_shapes(self.num_actions)[name]))
+        self.param_order = param_order(self.continuous)
+        for name in self.param_order:
+            size = int(np.prod(param_shapes(self.num_actions, self.continuous)[name]))
             self._offsets[name] = (off, size)
             off += size
         assert off == self.param_count
-        self.set_arena(0, initial_arena(self.num_actions, Config.RANDOM_SEED))
+        self.set_arena(0, initial_arena(self.num_actions, Config.RANDOM_SEED, self.continuous))
         self._pinned = []
         self._log_lock = threading.Lock()
         self.last_losses = None
@@ -198,7 +221,7 @@ class Network:
         b = int(x.shape[0])
         p = np.empty((b, self.num_actions), dtype=np.float32)
         v = np.empty((b,), dtype=np.float32)
-        z = np.empty((b, self.num_actions), dtype=np.float32) if want_z else None
+        z = np.empty((b, self.z_width), dtype=np.float32) if want_z else None
         zp = nat.ptr(z) if want_z else None
         if x.dtype == np.uint8:
             x = np.ascontiguousarray(x)
@@ -508,7 +531,7 @@ class Network:
         c1, c2, cv = (float(t) for t in losses)
         theta = self.get_arena(0)
         hist = {}
-        for name in PARAM_ORDER:
+        for name in self.param_order:
             off, size = self._offsets[name]
             hist["weights_%s:0" % name] = histogram_proto(theta[off:off + size])
         hist["activation_lastdense"] = histogram_proto(d1)

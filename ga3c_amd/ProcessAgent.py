@@ -80,7 +80,10 @@ class ProcessAgent(MP.Process):
         x2_ = np.array([u8_to_f32(e.next_state) if e.next_state.dtype == np.uint8 else e.next_state
                         for e in experiences])
         done_ = np.array([e.done for e in experiences])
-        a_ = np.eye(self.num_actions)[np.array([e.action for e in experiences])].astype(np.float32)
+        if Config.CONTINUOUS_INPUT:         # the action vectors themselves, [T, A] (the reference's [T, 1] at A = 1: SURVEY §9)
+            a_ = np.array([e.action for e in experiences], dtype=np.float32).reshape(len(experiences), self.num_actions)
+        else:
+            a_ = np.eye(self.num_actions)[np.array([e.action for e in experiences])].astype(np.float32)
         r_ = np.array([e.reward for e in experiences])
         return x_, r_, a_, x2_, done_
 
@@ -102,8 +105,10 @@ class ProcessAgent(MP.Process):
         """predict() + select_action() of one step in ONE foreign call (ga3c_pq_round_trip): state (or raw frame) into the
         slot, submit, wait, draw.  The uniform comes from the global RandomState exactly where np.random.choice would draw
         it -- one draw per step, none in PLAY_MODE (ProcessAgent.py:102-115) -- so seeds give the reference's actions.
+        CONTINUOUS_INPUT: the action IS the prediction vector (ProcessAgent.py:134-137) -- no draw, in PLAY_MODE or not.
         -> (prediction, value, action)."""
-        u = -1.0 if Config.PLAY_MODE else np.random.random_sample()
+        cont = Config.CONTINUOUS_INPUT
+        u = -1.0 if (Config.PLAY_MODE or cont) else np.random.random_sample()
         flat = state.reshape(-1)
         rc, p, v, a = self.transport.round_trip(self.id, flat if flat.flags.c_contiguous else np.ascontiguousarray(flat),
                                                 flags, Config.QUEUE_TIMEOUT_MS, u)
@@ -113,6 +118,8 @@ class ProcessAgent(MP.Process):
             if rc == tp.CLOSED or self.exit_flag.value:
                 raise SystemExit(0)
             rc, p, v, a = self.transport.round_trip(self.id, None, flags, Config.QUEUE_TIMEOUT_MS, u, submit=False)
+        if cont:
+            return p, v, p.copy()
         return p, v, int(self.actions[a]) if a >= 0 else int(np.argmax(p))
 
     def push_frame(self, frame, flags):

@@ -12,7 +12,7 @@ import os
 import threading
 import time
 
-from Config import Config
+from Config import Config, resolve_action_space
 import DataParallel
 from Environment import Environment
 from NetworkVP import Network, _device_ordinal
@@ -30,6 +30,7 @@ class Server:
     def __init__(self, model=None, max_agents=None, engine_group=None):
         # one Server per GPU under torch.distributed.run: lock-step training over RCCL (DataParallel.py)
         self.dp = engine_group
+        resolve_action_space()                  # DISCRATE_INPUT = not CONTINUOUS_INPUT (Server.py:36-38)
         self.dp_lock = threading.Lock()
         self.batch_lock = threading.Lock()      # one trainer at a time fills a batch (ThreadTrainer.py)
         self.closing = False
@@ -100,7 +101,8 @@ class Server:
         if slots <= 0:
             slots = slot_count()
         self.transport = tp.Transport.create(tp.unique_name(), self.max_agents, self.num_actions, state_bytes,
-                                             slots, Config.TIME_MAX + 1, row_bytes)
+                                             slots, Config.TIME_MAX + 1, row_bytes,
+                                             float_actions=bool(Config.CONTINUOUS_INPUT))
         if getattr(Config, "AGENT_SPIN_US", 0) > 0:
             self.transport.set_spin(Config.AGENT_SPIN_US)
         if Config.PREDICTION_LINGER_US > 0:

@@ -1,7 +1,8 @@
 """Training batcher (reference: ga3c/ThreadTrainer.py:33-62): take rollouts from the training
 queue until the batch holds MORE than TRAINING_MIN_BATCH_SIZE rows, then one server.train_model().
 
-Rollouts arrive as slots of the shared-memory transport (states, f32 returns, int32 actions);
+Rollouts arrive as slots of the shared-memory transport (states, f32 returns, int32 actions -- or f32 action vectors
+under CONTINUOUS_INPUT, which go to the network as they are instead of as one-hot rows);
 rows are copied once into a staging batch instead of the reference's repeated np.concatenate.
 x2_ and done_ are not transported (unused by the A3C nets, NetworkVP.py:254); train_model gets None.
 
@@ -57,8 +58,17 @@ class ThreadTrainer(Thread):
             x_stage = alloc(shape, np.uint8) if alloc else np.zeros(shape, np.uint8)
         off_stage = np.zeros(cap, np.int64)
         r_stage = np.zeros(cap, np.float32)
-        a_stage = np.zeros(cap, np.int32)
-        eye = np.eye(t.num_actions, dtype=np.float32)
+        if getattr(t, "float_actions", False):         # CONTINUOUS_INPUT: a = the action vectors, [cap, A] f32
+            a_stage = np.zeros((cap, t.num_actions), np.float32)
+
+            def a_rows(n):
+                return a_stage[:n].copy()           # (a fresh array, as eye[...] is)
+        else:
+            a_stage = np.zeros(cap, np.int32)
+            eye = np.eye(t.num_actions, dtype=np.float32)
+
+            def a_rows(n):
+                return eye[a_stage[:n]]
         holding = zero_copy and not on_device
         turn = getattr(self.server, "batch_lock", None) if holding else None
         # zero-copy batches are assembled by ONE native call (ga3c_tq_collect: the loop below, minus the interpreter --
@@ -134,14 +144,14 @@ class ThreadTrainer(Thread):
             if batch_size and Config.TRAIN_MODELS and not self.exit_flag:
                 if on_device:
                     self.server.train_model_frames(agent_stage[:batch_size], seq_stage[:batch_size], r_stage[:batch_size],
-                                                   eye[a_stage[:batch_size]], self.id)
+                                                   a_rows(batch_size), self.id)
                 elif holding and not spilled:
                     self.server.train_model_rows(off_stage[:batch_size], r_stage[:batch_size],
-                                                 eye[a_stage[:batch_size]], self.id)
+                                                 a_rows(batch_size), self.id)
                 else:
                     xb = x_stage[:batch_size] if u8 else x_stage[:batch_size].view(np.float32)
                     self.server.train_model(xb.reshape((batch_size,) + state_dim), r_stage[:batch_size],
-                                            eye[a_stage[:batch_size]], None, None, self.id)
+                                            a_rows(batch_size), None, None, self.id)
             for slot, _, _ in held:
                 t.release(slot)
             if native and cstate[1]:

@@ -26,6 +26,7 @@ class Transport:
         self.max_agents, self.num_actions = cfg.max_agents, cfg.num_actions
         self.state_bytes, self.train_slots, self.train_rows = cfg.state_bytes, cfg.train_slots, cfg.train_rows
         self.row_bytes = cfg.rollout_row_bytes or cfg.state_bytes      # bytes of one rollout row
+        self.float_actions = bool(cfg.float_actions)   # rollout actions: [rows, num_actions] float32 (CONTINUOUS_INPUT), else int32 [rows]
         self.nbytes = self._lib.ga3c_shm_bytes(self._h)
         self.base = self._lib.ga3c_shm_base(self._h)
         self._raw = np.frombuffer((C.c_uint8 * self.nbytes).from_address(self.base), dtype=np.uint8)
@@ -46,8 +47,10 @@ class Transport:
 
     # ---- lifecycle
     @classmethod
-    def create(cls, name, max_agents, num_actions, state_bytes, train_slots, train_rows, rollout_row_bytes=0):
-        cfg = nat.ShmConfig(max_agents, num_actions, state_bytes, train_slots, train_rows, rollout_row_bytes)
+    def create(cls, name, max_agents, num_actions, state_bytes, train_slots, train_rows, rollout_row_bytes=0,
+               float_actions=False):
+        cfg = nat.ShmConfig(max_agents, num_actions, state_bytes, train_slots, train_rows, rollout_row_bytes,
+                            1 if float_actions else 0)
         h = C.c_void_p()
         nat.check_host(nat.host_lib().ga3c_shm_create(name.encode(), C.byref(cfg), C.byref(h)), "ga3c_shm_create")
         t = cls(h, True)
@@ -194,7 +197,11 @@ class Transport:
         rp = self._lib.ga3c_tq_returns(self._h, slot)
         ap = self._lib.ga3c_tq_actions(self._h, slot)
         returns = np.frombuffer((C.c_float * self.train_rows).from_address(rp), dtype=np.float32)
-        actions = np.frombuffer((C.c_int32 * self.train_rows).from_address(ap), dtype=np.int32)
+        if self.float_actions:
+            actions = np.frombuffer((C.c_float * (self.train_rows * self.num_actions)).from_address(ap),
+                                    dtype=np.float32).reshape(self.train_rows, self.num_actions)
+        else:
+            actions = np.frombuffer((C.c_int32 * self.train_rows).from_address(ap), dtype=np.int32)
         return states, returns, actions
 
     def acquire(self, timeout_ms):
@@ -222,7 +229,11 @@ class Transport:
     def collect(self, min_rows, timeout_ms, hold_timeout_ms, state, slots, offsets, returns, actions, seqs=None, agents=None):
         """ThreadTrainer's batch assembly in native code (ga3c_tq_collect).  `state` = int32[2]: rows and slots of the batch
         in progress, kept across calls.  Returns 0 (batch complete), -3 (timeout), -4 (closed) or 1 (starved: give slots back).
-        seqs / agents: the rows name states kept on the device; they are decoded there and the slots released at once."""
+        seqs / agents: the rows name states kept on the device; they are decoded there and the slots released at once.
+        actions: int32 [len(returns)], or float32 [len(returns), num_actions] on a float_actions segment."""
+        want = (np.float32, len(returns) * self.num_actions) if self.float_actions else (np.int32, len(returns))
+        if actions.dtype != want[0] or actions.size < want[1] or not actions.flags.c_contiguous:
+            raise ValueError("collect: actions must be contiguous %s with %d elements" % (np.dtype(want[0]).name, want[1]))
         return nat.check_host(self._lib.ga3c_tq_collect(self._h, min_rows, timeout_ms, hold_timeout_ms, state.ctypes.data,
                                                         state.ctypes.data + 4, slots.ctypes.data, offsets.ctypes.data,
                                                         returns.ctypes.data, actions.ctypes.data, len(returns), len(slots),

@@ -16,6 +16,7 @@ COMM_ID_BYTES = 128
 FLAG_LOG_SOFTMAX = 1
 FLAG_GRAD_CLIP = 2
 FLAG_DUAL_RMSPROP = 4
+FLAG_CONTINUOUS = 8
 
 f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)
@@ -35,7 +36,7 @@ class NetConfig(C.Structure):
 class ShmConfig(C.Structure):
     _fields_ = [("max_agents", C.c_int32), ("num_actions", C.c_int32), ("state_bytes", C.c_int32),
                 ("train_slots", C.c_int32), ("train_rows", C.c_int32), ("rollout_row_bytes", C.c_int32),
-                ("reserved", C.c_int32 * 2)]
+                ("float_actions", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 class ServeStats(C.Structure):     # include/ga3c_host.h: ga3c_serve_stats

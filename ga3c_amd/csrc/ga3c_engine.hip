@@ -309,6 +309,10 @@ struct ga3c_net {
   // in for cost_all), ms_v / mom_v the value optimizer's; grad is 2n floats (TrainLane::grad)
   bool dual = false;
   float *ms_v = nullptr, *mom_v = nullptr;
+  // Config.CONTINUOUS_INPUT (GA3C_FLAG_CONTINUOUS): the angle-output policy head (heads_rows<..., CONT>); the arena ends in
+  // logits_p/out_x/{w,b}, logits_p/out_y/{w,b} instead of logits_p/{w,b}, and z / dz are B x npc = B x 2A ([hx | hy])
+  bool cont = false;
+  int npc = 0;                         // policy-head columns per row: A, or 2A under `cont`
   hipEvent_t theta_ready[NBUF] = {nullptr, nullptr, nullptr};   // recorded on the train stream behind the step that wrote theta[i]
   std::mutex ready_mu;
   std::shared_mutex wmu;   // shared: a forward pass picking/reading theta[cur]; unique: the optimizer flip
@@ -379,6 +383,7 @@ struct ga3c_net {
   Frames fr;
   TensorTable tt;
   TensorTable2 tt2;                    // DUAL_RMSPROP: the 10 tensors of the policy gradient, then those of the value gradient
+  TensorTableC ttc;                    // CONTINUOUS: the 12 tensors (clip_by_average_norm is per variable: out_x and out_y apart)
   LaneDrivers drv;
   float lanes_gpu_ms = 0.f;            // GPU-side span of the last ga3c_net_time_predict_lanes block (first start event .. last end event)
   int lanes_gpu_n = 0;
@@ -400,7 +405,7 @@ int dmalloc(float** p, size_t floats) {
   return GA3C_OK;
 }
 
-int alloc_fwd(Fwd& f, int maxB, int A) {
+int alloc_fwd(Fwd& f, int maxB, int A, int npc) {
   size_t part = 0;
   for (int b : {maxB < 256 ? maxB : 256, maxB < 1024 ? maxB : 1024, maxB}) {
     const size_t need = (size_t)22 * b * HID;   // dense_ks() <= 22
@@ -411,7 +416,7 @@ int alloc_fwd(Fwd& f, int maxB, int A) {
   CHK(dmalloc(&f.n2, (size_t)maxB * FLAT));
   CHK(dmalloc(&f.part, part));
   CHK(dmalloc(&f.d1, (size_t)maxB * HID));
-  CHK(dmalloc(&f.z, (size_t)maxB * A));
+  CHK(dmalloc(&f.z, (size_t)maxB * npc));
   CHK(dmalloc(&f.p, (size_t)maxB * A));
   CHK(dmalloc(&f.v, (size_t)maxB));
   HIPCHK(hipMalloc((void**)&f.xu8, (size_t)maxB * XS));
@@ -500,7 +505,7 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
   HeadArgs h;
   memset(&h, 0, sizeof h);
   h.part = f.part; h.ks = ks; h.B = B; h.A = A;
-  h.bd = th + OFF_BD; h.wv = th + OFF_WV; h.bv = th + OFF_BV; h.wp = th + OFF_WP; h.bp = th + off_bp(A);
+  h.bd = th + OFF_BD; h.wv = th + OFF_WV; h.bv = th + OFF_BV; h.wp = th + OFF_WP; h.bp = net->cont ? nullptr : th + off_bp(A);
   h.d1 = f.d1; h.z = f.z; h.p = out_p ? out_p : f.p; h.v = out_v ? out_v : f.v;   // out_*: pinned host memory, written in place
   h.log_eps = net->cfg.log_epsilon; h.min_policy = net->cfg.min_policy;
   h.log_softmax = (net->cfg.flags & GA3C_FLAG_LOG_SOFTMAX) ? 1 : 0;
@@ -514,7 +519,16 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
     if (stop_ev) hipExtLaunchKernelGGL((heads_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, nullptr, stop_ev, 0, h); \
     else hipLaunchKernelGGL((heads_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, h);                                 \
   } while (0)
-  if (train && dual) {
+#define HEADS_C(T, AM)                                                                                                      \
+  do {                                                                                                                      \
+    if (stop_ev) hipExtLaunchKernelGGL((heads_cont_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, nullptr, stop_ev, 0, h); \
+    else hipLaunchKernelGGL((heads_cont_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, h);                                 \
+  } while (0)
+  if (net->cont) {   // AMAX bounds the 2A columns [x | y]
+    if (2 * A <= 8) { if (train) HEADS_C(true, 8); else HEADS_C(false, 8); }
+    else if (2 * A <= 24) { if (train) HEADS_C(true, 24); else HEADS_C(false, 24); }
+    else { if (train) HEADS_C(true, 64); else HEADS_C(false, 64); }
+  } else if (train && dual) {
     const dim3 grid((B + HEADS_WAVES - 1) / HEADS_WAVES), block(64 * HEADS_WAVES);
     if (A <= 8) hipLaunchKernelGGL(heads_dual_kernel<8>, grid, block, 0, st, h, tl->dd1_v);
     else if (A <= 24) hipLaunchKernelGGL(heads_dual_kernel<24>, grid, block, 0, st, h, tl->dd1_v);
@@ -523,6 +537,7 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
   else if (A <= 24) { if (train) HEADS(true, 24); else HEADS(false, 24); }
   else { if (train) HEADS(true, 64); else HEADS(false, 64); }
 #undef HEADS
+#undef HEADS_C
   HIPCHK(hipGetLastError());
   return GA3C_OK;
 }
@@ -556,29 +571,34 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io
   float* g = io.g;
   HeadBwdArgs hb;
   hb.B = B; hb.A = A; hb.d1 = t.f.d1; hb.dz = io.dz; hb.dv = io.dv; hb.lossrow = t.lossrow;
-  hb.g_wp = g + OFF_WP; hb.g_bp = g + off_bp(A); hb.g_wv = g + OFF_WV; hb.g_bv = g + OFF_BV; hb.losses = t.losses;
+  hb.g_wp = g + OFF_WP; hb.g_bp = net->cont ? nullptr : g + off_bp(A); hb.g_wv = g + OFF_WV; hb.g_bv = g + OFF_BV; hb.losses = t.losses;
+  // the continuous head's roles exist in dense1_bwd_tile only: it takes every batch size (GA3C_D1B_TILE_MAX does not apply)
+  const int d1b_tile_max = net->cont ? (1 << 30) : net->d1b_tile_max;
+  const int roles = net->npc + 2;
   // dense1/w stepped inside conv_bwd, beside its MFMA phases, instead of in dense1_bwd_tile's epilogue: worth 0.5 us of the
   // 128-row step (the step's 24 MB cost conv_bwd 2.2 us where they cost the epilogue 3.5) while every workgroup of conv_bwd
   // steps ONE 16-row group; below 121 rows the groups left over are a tail and it loses 0.2 us (profiles/README.md)
   const bool fused_cb = net->conv_bwd_fused && B <= 128 && B >= net->conv_bwd_min;
-  upd.defer_wd = upd.on && fused_cb && B <= net->d1b_tile_max &&
+  upd.defer_wd = upd.on && fused_cb && B <= d1b_tile_max &&
                  (net->wd_step_in_conv_bwd >= 2 || (net->wd_step_in_conv_bwd == 1 && 2 * B >= KSTEPS_DENSE));
   // beyond the fused conv_bwd the step rides in conv2_dx (conv2_dx_wd_kernel)
-  if (upd.on && !fused_cb && B <= net->d1b_tile_max && net->wd_step_in_conv2_dx) upd.defer_wd = 1;
-  if (B <= net->d1b_tile_max) {
+  if (upd.on && !fused_cb && B <= d1b_tile_max && net->wd_step_in_conv2_dx) upd.defer_wd = 1;
+  if (B <= d1b_tile_max) {
     Dense1TileArgs d;
     d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
     d.hb = hb;
     d.upd = upd;
-    d.role_blocks = A + 2 < 14 ? A + 2 : 14;       // 242 tiles + the roles stay within one round of workgroups on 256 CUs
+    d.role_blocks = roles < 14 ? roles : 14;       // 242 tiles + the roles stay within one round of workgroups on 256 CUs
     d.tail_lds = net->d1b_tail && B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
     const size_t d1b_lds = (d.tail_lds ? D1B_LDS_FLOATS_TAIL : D1B_LDS_FLOATS) * sizeof(float);
-    if (upd.on && upd.defer_wd && d.tail_lds) hipLaunchKernelGGL((dense1_bwd_tile_kernel<2, true>), dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d);
-    else if (upd.on && upd.defer_wd) hipLaunchKernelGGL(dense1_bwd_tile_kernel<2>, dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d);
-    else if (upd.on && d.tail_lds) hipLaunchKernelGGL((dense1_bwd_tile_kernel<1, true>), dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d);
-    else if (upd.on) hipLaunchKernelGGL(dense1_bwd_tile_kernel<1>, dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d);
-    else if (d.tail_lds) hipLaunchKernelGGL((dense1_bwd_tile_kernel<0, true>), dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d);
-    else hipLaunchKernelGGL(dense1_bwd_tile_kernel<0>, dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d);
+    const int u = upd.on ? (upd.defer_wd ? 2 : 1) : 0;
+#define D1B(U, T, C) hipLaunchKernelGGL((dense1_bwd_tile_kernel<U, T, C>), dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d)
+#define D1B_U(T, C) do { if (u == 2) D1B(2, T, C); else if (u == 1) D1B(1, T, C); else D1B(0, T, C); } while (0)
+    if (net->cont) { if (d.tail_lds) D1B_U(true, true); else D1B_U(false, true); }
+    else if (d.tail_lds) D1B_U(true, false);
+    else D1B_U(false, false);
+#undef D1B_U
+#undef D1B
   } else {
     Dense1BwdArgs d;
     d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
@@ -673,17 +693,25 @@ int launch_rmsprop(ga3c_net* net, const float* grad, float* scales, const float*
   const bool mom = net->cfg.rmsprop_momentum != 0.0f;
   const float omr = 1.0f - net->cfg.rmsprop_decay;
   const int blocks = RMS_WD_BLOCKS + (int)((net->n - (int64_t)FLAT * HID + 255) / 256);
-  if (clip)
+  if (clip && net->cont)   // 12 tensors: out_x and out_y are normed apart (clip_by_average_norm per variable)
+    hipLaunchKernelGGL((clip_scale_kernel<true, TensorTableC>), dim3(12), dim3(256), 0, st, grad, net->ttc, net->cfg.grad_clip_norm, scales);
+  else if (clip)
     hipLaunchKernelGGL((clip_scale_kernel<true, TensorTable>), dim3(10), dim3(256), 0, st, grad, net->tt, net->cfg.grad_clip_norm, scales);
 #define RMS(C, M)                                                                                                \
   hipLaunchKernelGGL((rmsprop_kernel<C, M>), dim3(blocks), dim3(256), 0, st, tin, tout, net->ms, net->mom,        \
                      grad, net->n, lr, omr, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->tt, scales,  \
                      pk_out)
-  if (clip && mom) RMS(true, true);
+#define RMSC(M)                                                                                                  \
+  hipLaunchKernelGGL((rmsprop_kernel<true, M, TensorTableC>), dim3(blocks), dim3(256), 0, st, tin, tout, net->ms, \
+                     net->mom, grad, net->n, lr, omr, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->ttc, \
+                     scales, pk_out)
+  if (clip && net->cont) { if (mom) RMSC(true); else RMSC(false); }   // (without clipping the table plays no part)
+  else if (clip && mom) RMS(true, true);
   else if (clip) RMS(true, false);
   else if (mom) RMS(false, true);
   else RMS(false, false);
 #undef RMS
+#undef RMSC
   HIPCHK(hipGetLastError());
   return GA3C_OK;
 }
@@ -907,7 +935,7 @@ int train_grads(ga3c_net* net, TrainLane& t, int B, float beta, bool will_apply 
     return GA3C_OK;
   }
   const bool fuse = will_apply && net->fused_update && !net->comm && !(net->cfg.flags & GA3C_FLAG_GRAD_CLIP) &&
-                    B <= net->d1b_tile_max;
+                    (B <= net->d1b_tile_max || net->cont);
   int idx, other;
   if (fuse && !net->hogwild) {
     CHK(claim_other_buffer(net, t, &idx, &other));
@@ -1226,7 +1254,7 @@ int finish_predict(ga3c_net* net, Lane* L, int B, int mode, float* p, float* v, 
   TraceRange range("ga3c.predict");
   const int64_t t0 = now_ns();
   CHK(lane_forward(net, *L, B, mode, hp, hv));
-  if (z) HIPCHK(hipMemcpyAsync(hz, L->f.z, (size_t)B * A * sizeof(float), hipMemcpyDeviceToHost, L->st));
+  if (z) HIPCHK(hipMemcpyAsync(hz, L->f.z, (size_t)B * net->npc * sizeof(float), hipMemcpyDeviceToHost, L->st));
   const int64_t t1 = now_ns();
   if (z) CHK(lane_wait(L));                                  // the copy is behind the step's own event
   else CHK(lane_wait_step(L));
@@ -1237,7 +1265,7 @@ int finish_predict(ga3c_net* net, Lane* L, int B, int mode, float* p, float* v, 
   stat_add(net, GA3C_STAT_PREDICT_SYNC_NS, now_ns() - t1);
   memcpy(p, hp, (size_t)B * A * sizeof(float));
   memcpy(v, hv, (size_t)B * sizeof(float));
-  if (z) memcpy(z, hz, (size_t)B * A * sizeof(float));
+  if (z) memcpy(z, hz, (size_t)B * net->npc * sizeof(float));
   return GA3C_OK;
 }
 
@@ -1389,7 +1417,7 @@ int alloc_train_lane(ga3c_net* net, TrainLane& t, float* shared_grad) {
     HIPCHK(stream_take(net->cfg.device, !plain, &t.st));
   }
   HIPCHK(stream_take(net->cfg.device, false, &t.gst));
-  CHK(alloc_fwd(t.f, maxB, A));
+  CHK(alloc_fwd(t.f, maxB, A, net->npc));
   for (int k = 0; k < 2; ++k) {
     Intake& in = t.in[k];
     if (k == 0) {                      // intake 0 takes over the x buffers alloc_fwd made
@@ -1411,7 +1439,7 @@ int alloc_train_lane(ga3c_net* net, TrainLane& t, float* shared_grad) {
     memset(in.losses, 0, 4 * sizeof(float));
   }
   bind_intake(t, t.in[0]);
-  CHK(dmalloc(&t.dz, (size_t)maxB * A));
+  CHK(dmalloc(&t.dz, (size_t)maxB * net->npc));
   CHK(dmalloc(&t.dv, maxB));
   CHK(dmalloc(&t.lossrow, (size_t)maxB * 3));
   CHK(dmalloc(&t.dd1, (size_t)maxB * HID));
@@ -1430,7 +1458,7 @@ int alloc_train_lane(ga3c_net* net, TrainLane& t, float* shared_grad) {
     CHK(dmalloc(&t.grad, (size_t)net->n * (net->dual ? 2 : 1)));
     t.owns_grad = true;
   }
-  HIPCHK(hipHostMalloc((void**)&t.h_out, ((size_t)maxB * (2 * A + 1) + 4) * sizeof(float), hipHostMallocDefault));
+  HIPCHK(hipHostMalloc((void**)&t.h_out, ((size_t)maxB * (A + net->npc + 1) + 4) * sizeof(float), hipHostMallocDefault));
   HIPCHK(hipEventCreate(&t.ev0));
   HIPCHK(hipEventCreate(&t.ev1));
   return GA3C_OK;
@@ -1569,6 +1597,10 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
   if (cfg->num_actions < 1 || cfg->num_actions > GA3C_MAX_ACTIONS)
     return fail(GA3C_EINVAL, "num_actions %d outside [1,%d]", cfg->num_actions, GA3C_MAX_ACTIONS);
   if (cfg->max_batch < 1 || cfg->max_batch > 65536) return fail(GA3C_EINVAL, "max_batch %d outside [1,65536]", cfg->max_batch);
+  if ((cfg->flags & GA3C_FLAG_CONTINUOUS) && (cfg->flags & GA3C_FLAG_DUAL_RMSPROP))
+    return fail(GA3C_EINVAL, "CONTINUOUS_INPUT with DUAL_RMSPROP is not supported");
+  if ((cfg->flags & GA3C_FLAG_CONTINUOUS) && cfg->num_actions > GA3C_MAX_ACTIONS / 2)   // the 2A head columns are lanes of one wave
+    return fail(GA3C_EINVAL, "num_actions %d outside [1,%d] for the continuous head", cfg->num_actions, GA3C_MAX_ACTIONS / 2);
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail(GA3C_EINVAL, "device %d not in [0,%d)", cfg->device, ndev);
@@ -1650,8 +1682,15 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
   }
   net->A = cfg->num_actions;
   net->maxB = cfg->max_batch;
-  net->n = arena_floats(net->A);
+  net->cont = (cfg->flags & GA3C_FLAG_CONTINUOUS) != 0;
+  net->npc = net->cont ? 2 * net->A : net->A;
+  net->n = net->cont ? cont_arena_floats(net->A) : arena_floats(net->A);
   const int A = net->A, maxB = net->maxB;
+  {
+    const int64_t bx = OFF_WP + (int64_t)HID * A, wy = bx + A, by = wy + (int64_t)HID * A;
+    const int64_t offc[13] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WD, OFF_BD, OFF_WV, OFF_BV, OFF_WP, bx, wy, by, net->n};
+    for (int i = 0; i < 13; ++i) net->ttc.off[i] = offc[i];
+  }
   const int64_t offs[11] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WD, OFF_BD, OFF_WV, OFF_BV, OFF_WP, off_bp(A), net->n};
   for (int i = 0; i < 11; ++i) net->tt.off[i] = offs[i];
   for (int i = 0; i < 10; ++i) {
@@ -1731,9 +1770,9 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
     TRYHIP(hipEventCreateWithFlags(&L->done, hipEventDisableTiming));
     TRYHIP(hipEventCreate(&L->tm0));
     TRYHIP(hipEventCreate(&L->tm1));
-    TRY(alloc_fwd(L->f, maxB, A));
+    TRY(alloc_fwd(L->f, maxB, A, net->npc));
     TRYHIP(hipHostMalloc((void**)&L->h_in, (size_t)maxB * XS * sizeof(float), hipHostMallocDefault));
-    TRYHIP(hipHostMalloc((void**)&L->h_out, ((size_t)maxB * (2 * A + 1)) * sizeof(float), hipHostMallocDefault));
+    TRYHIP(hipHostMalloc((void**)&L->h_out, ((size_t)maxB * (A + net->npc + 1)) * sizeof(float), hipHostMallocDefault));
     TRYHIP(hipHostMalloc((void**)&L->h_off, (size_t)maxB * sizeof(int64_t), hipHostMallocDefault));
     TRYHIP(hipHostMalloc((void**)&L->cache_dst, (size_t)maxB * sizeof(int64_t), hipHostMallocDefault));
   }
@@ -1855,17 +1894,27 @@ namespace {
 constexpr int NPARAMS = 10;
 const char* const PARAM_NAMES[NPARAMS] = {"conv11/w", "conv11/b", "conv12/w", "conv12/b", "dense1/w", "dense1/b",
                                           "logits_v/w", "logits_v/b", "logits_p/w", "logits_p/b"};
+// the continuous network (GA3C_FLAG_CONTINUOUS): the policy head's variables in TF creation order (NetworkVP.py:175-204)
+constexpr int NPARAMS_C = 12;
+const char* const PARAM_NAMES_C[NPARAMS_C] = {"conv11/w", "conv11/b", "conv12/w", "conv12/b", "dense1/w", "dense1/b",
+                                              "logits_v/w", "logits_v/b", "logits_p/out_x/w", "logits_p/out_x/b",
+                                              "logits_p/out_y/w", "logits_p/out_y/b"};
+int nparams(const ga3c_net* net) { return net->cont ? NPARAMS_C : NPARAMS; }
+const char* param_name(const ga3c_net* net, int i) { return net->cont ? PARAM_NAMES_C[i] : PARAM_NAMES[i]; }
 struct ParamInfo { int64_t off, count; int ndim; int64_t shape[4]; };
 bool param_lookup(ga3c_net* net, const char* name, ParamInfo* pi) {
   const int A = net->A;
-  const int64_t offs[NPARAMS + 1] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WD, OFF_BD, OFF_WV, OFF_BV, OFF_WP, off_bp(A), net->n};
-  const int64_t shapes[NPARAMS][4] = {{8, 8, 4, 16}, {16, 0, 0, 0}, {4, 4, 16, 32}, {32, 0, 0, 0}, {FLAT, HID, 0, 0}, {HID, 0, 0, 0},
-                                      {HID, 1, 0, 0}, {1, 0, 0, 0}, {HID, A, 0, 0}, {A, 0, 0, 0}};
-  const int ndims[NPARAMS] = {4, 1, 4, 1, 2, 1, 2, 1, 2, 1};
+  const int64_t bx = OFF_WP + (int64_t)HID * A;
+  const int64_t offs[NPARAMS_C + 1] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WD, OFF_BD, OFF_WV, OFF_BV, OFF_WP,
+                                       net->cont ? bx : off_bp(A), net->cont ? bx + A : net->n,
+                                       bx + A + (int64_t)HID * A, net->n};
+  const int64_t shapes[NPARAMS_C][4] = {{8, 8, 4, 16}, {16, 0, 0, 0}, {4, 4, 16, 32}, {32, 0, 0, 0}, {FLAT, HID, 0, 0}, {HID, 0, 0, 0},
+                                        {HID, 1, 0, 0}, {1, 0, 0, 0}, {HID, A, 0, 0}, {A, 0, 0, 0}, {HID, A, 0, 0}, {A, 0, 0, 0}};
+  const int ndims[NPARAMS_C] = {4, 1, 4, 1, 2, 1, 2, 1, 2, 1, 2, 1};
   std::string key(name ? name : "");
   if (key.size() > 2 && key.compare(key.size() - 2, 2, ":0") == 0) key.resize(key.size() - 2);
-  for (int i = 0; i < NPARAMS; ++i)
-    if (key == PARAM_NAMES[i]) {
+  for (int i = 0; i < nparams(net); ++i)
+    if (key == param_name(net, i)) {
       pi->off = offs[i]; pi->count = offs[i + 1] - offs[i]; pi->ndim = ndims[i];
       for (int d = 0; d < 4; ++d) pi->shape[d] = shapes[i][d];
       return true;
@@ -1874,10 +1923,10 @@ bool param_lookup(ga3c_net* net, const char* name, ParamInfo* pi) {
 }
 }  // namespace
 
-int32_t ga3c_net_num_params(ga3c_net* net) { return net ? NPARAMS : 0; }
+int32_t ga3c_net_num_params(ga3c_net* net) { return net ? nparams(net) : 0; }
 
 const char* ga3c_net_param_name(ga3c_net* net, int32_t index) {
-  return (net && index >= 0 && index < NPARAMS) ? PARAM_NAMES[index] : nullptr;
+  return (net && index >= 0 && index < nparams(net)) ? param_name(net, index) : nullptr;
 }
 
 int ga3c_net_param_info(ga3c_net* net, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]) {
@@ -2037,12 +2086,12 @@ int ga3c_net_save(ga3c_net* net, const char* path) {
   const int64_t step = net->step.load();
   st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
   members.push_back(st);
-  for (int i = 0; i < NPARAMS; ++i) {
+  for (int i = 0; i < nparams(net); ++i) {
     ParamInfo pi;
-    param_lookup(net, PARAM_NAMES[i], &pi);
+    param_lookup(net, param_name(net, i), &pi);
     for (int w = 0; w < 3; ++w) {
       ga3c_ckpt::Member m;
-      m.name = std::string(PARAM_NAMES[i]) + suffix[w];
+      m.name = std::string(param_name(net, i)) + suffix[w];
       m.descr = "<f4";
       m.shape.assign(pi.shape, pi.shape + pi.ndim);
       const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[w].data() + pi.off);
@@ -2067,11 +2116,13 @@ int ga3c_net_load(ga3c_net* net, const char* path) {
   const char* suffix[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};
   std::vector<float> arena[3];
   for (int w = 0; w < 3; ++w) arena[w].resize((size_t)net->n);
-  for (int i = 0; i < NPARAMS; ++i) {
+  // a continuous file holds no logits_p/w, a discrete one no logits_p/out_x/w: either is refused by the other kind of network
+  // below, before anything is written
+  for (int i = 0; i < nparams(net); ++i) {
     ParamInfo pi;
-    param_lookup(net, PARAM_NAMES[i], &pi);
+    param_lookup(net, param_name(net, i), &pi);
     for (int w = 0; w < 3; ++w) {
-      const std::string key = std::string(PARAM_NAMES[i]) + suffix[w];
+      const std::string key = std::string(param_name(net, i)) + suffix[w];
       auto it = members.find(key);
       if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s", path, key.c_str());
       const ga3c_ckpt::Member& m = it->second;
@@ -2971,6 +3022,7 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
   // execution time on the train lane's stream, without launch gaps.  Buffers hold whatever the last
   // step left there; "rmsprop" runs with lr = 0 but does advance the `ms` slot (use a scratch net).
   if (!net || !kernel || !elapsed_ms) return fail(GA3C_EINVAL, "null argument");
+  if (net->cont) return fail(GA3C_ESTATE, "ga3c_net_time_kernel times the discrete head's kernels only");
   if (iters < 1 || batch < 1 || batch > net->maxB) return fail(GA3C_EINVAL, "bad batch/iters");
   HIPCHK(hipSetDevice(net->cfg.device));
   std::lock_guard<std::mutex> tl(net->tr.mu);
@@ -3111,8 +3163,8 @@ int ga3c_net_fetch(ga3c_net* net, const char* name, float* out, int64_t count) {
   TrainLane& t = net->tr;
   const int64_t B = net->maxB, A = net->A;
   struct Ent { const char* n; const float* p; int64_t cap; };
-  const Ent ents[] = {{"n1", t.f.n1, B * N1S}, {"n2", t.f.n2, B * FLAT}, {"d1", t.f.d1, B * HID}, {"z", t.f.z, B * A},
-                      {"p", t.f.p, B * A}, {"v", t.f.v, B}, {"dz", t.dz, B * A}, {"dv", t.dv, B},
+  const Ent ents[] = {{"n1", t.f.n1, B * N1S}, {"n2", t.f.n2, B * FLAT}, {"d1", t.f.d1, B * HID}, {"z", t.f.z, B * net->npc},
+                      {"p", t.f.p, B * A}, {"v", t.f.v, B}, {"dz", t.dz, B * net->npc}, {"dv", t.dv, B},
                       {"dd1", t.dd1, B * HID}, {"dn2", t.dn2, B * FLAT}, {"dn1", t.dn1, B * N1S}, {"x", t.f.x, B * XS}};
   for (const Ent& e : ents) {
     if (strcmp(e.n, name) == 0) {
@@ -3132,7 +3184,7 @@ int ga3c_net_fetch_lane(ga3c_net* net, int32_t lane, const char* name, float* ou
   Lane* L = net->lanes[(size_t)lane];
   const int64_t B = net->maxB, A = net->A;
   struct Ent { const char* n; const float* p; int64_t cap; };
-  const Ent ents[] = {{"z", L->f.z, B * A}, {"p", L->f.p, B * A}, {"v", L->f.v, B}};
+  const Ent ents[] = {{"z", L->f.z, B * net->npc}, {"p", L->f.p, B * A}, {"v", L->f.v, B}};
   for (const Ent& e : ents) {
     if (strcmp(e.n, name) == 0) {
       if (count < 1 || count > e.cap) return fail(GA3C_EINVAL, "count %lld outside [1,%lld] for '%s'", (long long)count, (long long)e.cap, name);

@@ -197,6 +197,9 @@ uint32_t ring_size(Ring* r) {
 }
 
 constexpr uint64_t MAGIC = 0x4741334353484d31ull;   // "GA3CSHM1"
+// a segment whose rollout actions are float rows (ga3c_shm_config::float_actions): another layout, so another magic -- a
+// reader that knows only int actions refuses it; with the field at 0 the segment is what it always was, "GA3CSHM1" included
+constexpr uint64_t MAGIC_F32_ACTIONS = 0x4741334353484d32ull;   // "GA3CSHM2"
 constexpr int MAXA = 64;
 
 struct AgentMeta {   // lives right behind each agent's state bytes
@@ -584,11 +587,15 @@ int ga3c_frame_preprocess(const uint8_t* rgb, int32_t height, int32_t width, int
   return GA3C_H_OK;
 }
 
+// 4-byte words of one rollout row's action: A float32 (float_actions, Config.CONTINUOUS_INPUT), or one int32 index
+static int action_words(const ga3c_shm_config* cfg) { return cfg->float_actions ? cfg->num_actions : 1; }
+
 int ga3c_shm_create(const char* name, const ga3c_shm_config* cfg, ga3c_shm** out) {
   if (!name || !cfg || !out) return fail(GA3C_H_EINVAL, "null argument");
   if (cfg->max_agents < 1 || cfg->max_agents > 65536 || cfg->num_actions < 1 || cfg->num_actions > MAXA ||
       cfg->state_bytes < 16 || cfg->state_bytes % 16 != 0 || cfg->train_slots < 1 || cfg->train_slots > 65536 ||
-      cfg->train_rows < 1 || cfg->rollout_row_bytes < 0 || cfg->rollout_row_bytes % 16 != 0)
+      cfg->train_rows < 1 || cfg->rollout_row_bytes < 0 || cfg->rollout_row_bytes % 16 != 0 ||
+      (cfg->float_actions != 0 && cfg->float_actions != 1) || cfg->reserved[0] != 0)
     return fail(GA3C_H_EINVAL, "bad shm config");
   const int64_t row_bytes = cfg->rollout_row_bytes ? cfg->rollout_row_bytes : cfg->state_bytes;
   // well above the logical maximum (16 B per cell): a cell whose consumer is momentarily descheduled blocks the producers
@@ -608,7 +615,7 @@ int ga3c_shm_create(const char* name, const ga3c_shm_config* cfg, ga3c_shm** out
   off = round_up(off + lay.agent_stride * cfg->max_agents, 4096);
   lay.ro_returns_off = round_up((int64_t)cfg->train_rows * row_bytes, 256);
   lay.ro_actions_off = lay.ro_returns_off + round_up((int64_t)cfg->train_rows * 4, 64);
-  lay.ro_rows_off = lay.ro_actions_off + round_up((int64_t)cfg->train_rows * 4, 64);
+  lay.ro_rows_off = lay.ro_actions_off + round_up((int64_t)cfg->train_rows * 4 * action_words(cfg), 64);
   lay.rollout_stride = round_up(lay.ro_rows_off + 64, 256);
   lay.rollouts_off = off;
   off = round_up(off + lay.rollout_stride * cfg->train_slots, 4096);
@@ -652,7 +659,7 @@ int ga3c_shm_create(const char* name, const ga3c_shm_config* cfg, ga3c_shm** out
   ring_init(s->base, &h->readyq, tr_cap, ready_cells);
   for (int i = 0; i < cfg->train_slots; ++i) ring_push(s->base, &h->freeq, (uint32_t)i, nullptr);
   std::atomic_thread_fence(std::memory_order_seq_cst);
-  h->magic = MAGIC;
+  h->magic = cfg->float_actions ? MAGIC_F32_ACTIONS : MAGIC;
   *out = s;
   return GA3C_H_OK;
 }
@@ -670,7 +677,7 @@ int ga3c_shm_attach(const char* name, ga3c_shm** out) {
   close(fd);
   if (p == MAP_FAILED) return fail(GA3C_H_ESYS, "mmap: %s", strerror(errno));
   Header* h = (Header*)p;
-  if (h->magic != MAGIC || h->total_bytes != (int64_t)st.st_size) {
+  if ((h->magic != MAGIC && h->magic != MAGIC_F32_ACTIONS) || h->total_bytes != (int64_t)st.st_size) {
     munmap(p, (size_t)st.st_size);
     return fail(GA3C_H_EINVAL, "segment %s is not a ga3c transport", name);
   }
@@ -1384,7 +1391,8 @@ int ga3c_tq_collect(ga3c_shm* shm, int32_t min_rows, int32_t timeout_ms, int32_t
     const int64_t off0 = (int64_t)(ro - shm->base);
     for (int32_t i = 0; i < n; ++i) row_offsets[*rows + i] = off0 + i * row_bytes;
     memcpy(returns + *rows, ro + h->ro_returns_off, (size_t)n * sizeof(float));
-    memcpy(actions + *rows, ro + h->ro_actions_off, (size_t)n * sizeof(int32_t));
+    const int aw = action_words(&h->cfg);                   // float_actions: A f32 per row, else one i32
+    memcpy(actions + (int64_t)*rows * aw, ro + h->ro_actions_off, (size_t)n * aw * sizeof(int32_t));
     if (names) {                                             // (plane sequence number i64, agent id i32) per row; the slot is done
       for (int32_t i = 0; i < n; ++i) {
         memcpy(&row_seq[*rows + i], ro + i * row_bytes, 8);

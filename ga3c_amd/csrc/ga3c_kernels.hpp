@@ -36,6 +36,8 @@ constexpr int64_t OFF_W1 = 0, OFF_B1 = OFF_W1 + 256 * 16, OFF_W2 = OFF_B1 + 16, 
                   OFF_BV = OFF_WV + HID, OFF_WP = OFF_BV + 1;
 __host__ __device__ inline int64_t off_bp(int A) { return OFF_WP + (int64_t)HID * A; }
 __host__ __device__ inline int64_t arena_floats(int A) { return off_bp(A) + A; }
+// the continuous network (Config.CONTINUOUS_INPUT): logits_p/out_x/w [256,A], out_x/b [A], out_y/w [256,A], out_y/b [A] from OFF_WP on
+__host__ __device__ inline int64_t cont_arena_floats(int A) { return OFF_WP + 2 * ((int64_t)HID * A + A); }
 
 // In-kernel time stamps for the DIAGNOSTIC build of tools/kprobe.hip only (-DGA3C_STAMPS): the product library never
 // defines it, so no stamp executes there.  Stamps leave the kernel through a buffer of their own.
@@ -862,6 +864,8 @@ __host__ inline int dense1_fwd_blocks(int B, int ks_total, int mt) {
 // One wave per sample: d1 = relu(sum_ks part + bd); z = d1 Wp + bp; v = d1 Wv + bv; softmax;
 // TRAIN adds the A3C loss terms, the head gradients dz, dv and the gradient that
 // flows back into the hidden layer, dd1 = 1[d1>0] (dz Wp^T + dv Wv^T) -- the wave already holds Wp, Wv, d1.
+constexpr float PI_F = 3.14159265358979f;   // np.pi as the f32 constant TF divides by (NetworkVP.py:190)
+
 struct HeadArgs {
   const float* part; int ks; int B; int A;
   const float* bd; const float* wv; const float* bv; const float* wp; const float* bp;
@@ -873,20 +877,44 @@ struct HeadArgs {
 
 // NR rows per wave (rows[j] < 0: none; wave-uniform): every load of every row is requested before the first reduction
 // DUAL (heads_dual_kernel): h.dd1 receives the policy term 1[d1>0] dz Wp^T and dd1_v the value term 1[d1>0] dv Wv^T
-template <bool TRAIN, int AMAX, int NR, bool DUAL = false>
+// CONT (Config.CONTINUOUS_INPUT, reference NetworkVP.py:92,95-105,175-192): the policy head is the two dense layers
+// logits_p/out_x and logits_p/out_y, laid out from h.wp on as out_x/w [256,A], out_x/b [A], out_y/w [256,A], out_y/b [A]
+// (h.bp unused).  The 2A columns [x | y] take the place of the A logits: wreg column o < A is out_x's column o, column A + o
+// out_y's, so lane o < A ends up with hx_o and lane A + o with hy_o (AMAX >= 2A).  Per action, on lane o < A:
+//   X = sigmoid(hx) - 0.5, Y = sigmoid(hy) - 0.5, p = atan2(Y, X) / pi in (-1, 1]            (p: the action itself)
+//   cost_p_1 = (sum_o p_o a_o) adv, cost_p_2 = -beta sum_o p_o^2  ->  g = dcost_p/dp = -a adv + 2 beta p
+//   dX = -Y g / (pi (X^2 + Y^2)), dY = X g / (pi (X^2 + Y^2))     (TF-1 Atan2Grad: no guard at X = Y = 0, NaN as there)
+//   dz = [dhx | dhy] = [dX sx (1 - sx) | dY sy (1 - sy)]
+// z and dz are B x 2A ([hx | hy] per row); dd1 is the discrete code's sum over the 2A columns.
+template <bool TRAIN, int AMAX, int NR, bool DUAL = false, bool CONT = false>
 __device__ __forceinline__ void heads_rows(const HeadArgs& h, const int (&rows)[NR], int lane, float* dd1_v = nullptr) {
   // this lane's 4 hidden units x A policy weights are 4*A contiguous floats: issue every load up front
   float wreg[4][AMAX];
-  const float* wp = h.wp + (size_t)(4 * lane) * h.A;
+  if constexpr (CONT) {
+    const float* wx = h.wp + (size_t)(4 * lane) * h.A;
+    const float* wy = wx + (size_t)(HID + 1) * h.A;          // out_y/w follows out_x/w and out_x/b
 #pragma unroll
-  for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < 4; ++q)
 #pragma unroll
-    for (int o = 0; o < AMAX; ++o) wreg[q][o] = o < h.A ? wp[q * h.A + o] : 0.f;
+      for (int o = 0; o < AMAX; ++o)
+        wreg[q][o] = o < h.A ? wx[q * h.A + o] : (o < 2 * h.A ? wy[q * h.A + o - h.A] : 0.f);
+  } else {
+    const float* wp = h.wp + (size_t)(4 * lane) * h.A;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int o = 0; o < AMAX; ++o) wreg[q][o] = o < h.A ? wp[q * h.A + o] : 0.f;
+  }
   const f32x4 wv4 = ld4(h.wv + 4 * lane);
   const f32x4 bd4 = ld4(h.bd + 4 * lane);
   // everything the tail needs is requested now, with the slab loads, not after the reductions (one round trip, not three)
   const bool mine = lane < h.A;
-  const float bp_mine = mine ? h.bp[lane] : 0.f;
+  const int npc = CONT ? 2 * h.A : h.A;                       // policy columns
+  float bp_mine;
+  if constexpr (CONT)   // out_x/b at wp + 256 A, out_y/b at wp + 513 A
+    bp_mine = mine ? h.wp[(size_t)HID * h.A + lane] : (lane < npc ? h.wp[(size_t)(2 * HID + 1) * h.A + lane - h.A] : 0.f);
+  else
+    bp_mine = mine ? h.bp[lane] : 0.f;
   const float bv0 = h.bv[0];
   float y[NR], a[NR];
   f32x4 dr[NR];
@@ -926,6 +954,50 @@ __device__ __forceinline__ void heads_rows(const HeadArgs& h, const int (&rows)[
     for (int sh = 32; sh > 0; sh >>= 1)
 #pragma unroll
       for (int o = 0; o < AMAX; ++o) zpart[o] += __shfl_xor(zpart[o], sh, 64);
+    if constexpr (CONT) {
+      float hmine = 0.f;
+#pragma unroll
+      for (int o = 0; o < AMAX; ++o)
+        if (lane == o && o < npc) hmine = zpart[o] + bp_mine;
+      const float hy = __shfl(hmine, (lane + h.A) & 63, 64);         // lane o < A: hy_o next to its hx_o
+      const float sx = 1.0f / (1.0f + expf(-hmine)), sy = 1.0f / (1.0f + expf(-hy));
+      const float X = sx - 0.5f, Y = sy - 0.5f;
+      const float pc = atan2f(Y, X) / PI_F;
+      if (lane < npc) h.z[(size_t)b * npc + lane] = hmine;
+      if (mine) h.p[(size_t)b * h.A + lane] = pc;
+      if (lane == 0) h.v[b] = v;
+      if (TRAIN) {
+        const float yy = y[j], aa = a[j];
+        const float adv = yy - v;
+        const float c1 = wave_sum(mine ? pc * aa : 0.f) * adv;
+        const float c2 = -h.beta * wave_sum(mine ? pc * pc : 0.f);
+        const float g = -aa * adv + 2.0f * h.beta * pc;
+        const float gr = g / (PI_F * (X * X + Y * Y));
+        const float dhx = -Y * gr * (sx * (1.0f - sx));
+        const float dhy = X * gr * (sy * (1.0f - sy));
+        const float dhy_up = __shfl(dhy, (lane + 64 - h.A) & 63, 64);     // lane A + o: dhy_o
+        const float dz = mine ? dhx : (lane < npc ? dhy_up : 0.f);
+        if (lane < npc) h.dz[(size_t)b * npc + lane] = dz;
+        const float dvv = v - yy;
+        f32x4 dd = {dvv * wv4[0], dvv * wv4[1], dvv * wv4[2], dvv * wv4[3]};
+#pragma unroll
+        for (int o = 0; o < AMAX; ++o) {
+          const float dzo = __shfl(dz, o, 64);          // 0 for lanes >= 2A
+#pragma unroll
+          for (int q = 0; q < 4; ++q) dd[q] += dzo * wreg[q][o];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dd[q] = d[q] > 0.f ? dd[q] : 0.f;
+        *reinterpret_cast<f32x4*>(h.dd1 + (size_t)b * HID + 4 * lane) = dd;
+        if (lane == 0) {
+          h.dv[b] = dvv;
+          h.lossrow[(size_t)b * 3 + 0] = c1;
+          h.lossrow[(size_t)b * 3 + 1] = c2;
+          h.lossrow[(size_t)b * 3 + 2] = 0.5f * (yy - v) * (yy - v);
+        }
+      }
+      continue;
+    }
     float zmine = -INFINITY;
 #pragma unroll
     for (int o = 0; o < AMAX; ++o)
@@ -1013,6 +1085,15 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs h) {
   heads_rows<TRAIN, AMAX, 1>(h, rows, threadIdx.x & 63);
 }
 
+// the continuous policy head (heads_rows<..., CONT>): p = the action vector [B,A], z = [hx | hy] [B,2A]; AMAX >= 2A
+template <bool TRAIN, int AMAX>
+__global__ __launch_bounds__(256) void heads_cont_kernel(HeadArgs h) {
+  const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (b >= h.B) return;   // wave-uniform
+  const int rows[1] = {b};
+  heads_rows<TRAIN, AMAX, 1, false, true>(h, rows, threadIdx.x & 63);
+}
+
 // heads_kernel<true, AMAX> with dd1 written as its two terms, h.dd1 (policy) and dd1_v (value); losses, dz and dv as there
 template <int AMAX>
 __global__ __launch_bounds__(256) void heads_dual_kernel(HeadArgs h, float* dd1_v) {
@@ -1040,14 +1121,19 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
   return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
+// CONT (the continuous policy head, heads_rows): 2A + 2 roles.  Role o < 2A is column o of dz = [dhx | dhy]: o < A is
+// logits_p/out_x's column o, A + o out_y's column o; g_wp points at out_x/w, the other three follow it (out_x/b at + 256 A,
+// out_y/w at + 257 A, out_y/b at + 513 A; g_bp unused); role 2A the value head, 2A + 1 the loss sums.
+template <bool CONT = false>
 __device__ __forceinline__ void heads_bwd_role(const HeadBwdArgs& h, int role) {
   __shared__ float sh[4];
   __shared__ f32x4 sacc[4][64];
   const int k = threadIdx.x;
-  if (role <= h.A) {
+  const int npc = CONT ? 2 * h.A : h.A;
+  if (role <= npc) {
     // thread = (4 hidden units kq, batch residue bg): float4 rows of d1, partial sums folded through LDS
     const int o = role;
-    const bool isv = o == h.A;
+    const bool isv = o == npc;
     const int kq = k & 63, bg = k >> 6;
     f32x4 acc = zero4();
     float bsum = 0.f;
@@ -1059,14 +1145,30 @@ __device__ __forceinline__ void heads_bwd_role(const HeadBwdArgs& h, int role) {
         const int b = b0 + 4 * i;
         const bool ok = b < h.B;
         dd[i] = ok ? ld4(h.d1 + (size_t)b * HID + 4 * kq) : zero4();
-        gh[i] = ok ? (isv ? h.dv[b] : h.dz[(size_t)b * h.A + o]) : 0.f;
+        gh[i] = ok ? (isv ? h.dv[b] : h.dz[(size_t)b * npc + o]) : 0.f;
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc += dd[i] * gh[i];
     }
-    for (int b = k; b < h.B; b += 256) bsum += isv ? h.dv[b] : h.dz[(size_t)b * h.A + o];
+    for (int b = k; b < h.B; b += 256) bsum += isv ? h.dv[b] : h.dz[(size_t)b * npc + o];
     sacc[bg][kq] = acc;
     bsum = block_sum_256(bsum, sh);   // contains the barriers that also publish sacc
+    if constexpr (CONT) {
+      const int oc = o < h.A ? o : o - h.A;
+      float* gw = h.g_wp + (o < h.A ? 0 : (size_t)(HID + 1) * h.A);   // out_x/w or out_y/w; its bias follows it
+      if (bg == 0) {
+        const f32x4 tot = (sacc[0][kq] + sacc[1][kq]) + (sacc[2][kq] + sacc[3][kq]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (isv) h.g_wv[4 * kq + q] = tot[q];
+          else gw[(size_t)(4 * kq + q) * h.A + oc] = tot[q];
+        }
+      }
+      if (k == 0) {
+        if (isv) h.g_bv[0] = bsum; else gw[(size_t)HID * h.A + oc] = bsum;
+      }
+      return;
+    }
     if (bg == 0) {
       const f32x4 tot = (sacc[0][kq] + sacc[1][kq]) + (sacc[2][kq] + sacc[3][kq]);
 #pragma unroll
@@ -1089,7 +1191,7 @@ __device__ __forceinline__ void heads_bwd_role(const HeadBwdArgs& h, int role) {
 }
 
 // loss sums alone (Network.log evaluates a batch without a backward pass: NetworkVP.py:259-265)
-__global__ __launch_bounds__(256) void loss_sum_kernel(HeadBwdArgs hb) { heads_bwd_role(hb, hb.A + 1); }
+__global__ __launch_bounds__(256) void loss_sum_kernel(HeadBwdArgs hb) { heads_bwd_role(hb, hb.A + 1); }   // (either head: the same role)
 
 // ------------------------------------------------------------------ dense1 backward: dWd = flat^T dd1
 // M = 3872 (kidx), N = 256, contraction over the batch.  Wave tile 32 x 32 (2 x 2 MFMA tiles).
@@ -1460,8 +1562,9 @@ constexpr int D1B_TAIL_FLOATS = D1B_TAIL_ROWS * D1B_DS + D1B_TAIL_ROWS * D1B_COL
 constexpr int D1B_LDS_FLOATS_TAIL = D1B_LDS_FLOATS + D1B_TAIL_FLOATS;                       // 40932 floats = 163,728 B
 static_assert(D1B_LDS_FLOATS_TAIL * sizeof(float) <= 160 * 1024, "dense1_bwd_tile: the tail area must fit the CU's 160 KB");
 
-// head weight gradients / loss sums for a 1024-thread block (same arithmetic order as heads_bwd_role up to the fold width)
-template <bool UPD>
+// head weight gradients / loss sums for a 1024-thread block (same arithmetic order as heads_bwd_role up to the fold width);
+// CONT: the 2A + 2 roles of the continuous head, as heads_bwd_role<true>
+template <bool UPD, bool CONT = false>
 __device__ __forceinline__ void heads_bwd_role_wide(const HeadBwdArgs& h, int role, float* lds, const FusedUpd& u) {
   f32x4* sacc = reinterpret_cast<f32x4*>(lds);            // [16][64]
   float* sh = lds + 16 * 64 * 4;                           // [16]
@@ -1476,9 +1579,10 @@ __device__ __forceinline__ void heads_bwd_role_wide(const HeadBwdArgs& h, int ro
     for (int i = 0; i < 16; ++i) t += sh[i];
     return t;
   };
-  if (role <= h.A) {
+  const int npc = CONT ? 2 * h.A : h.A;
+  if (role <= npc) {
     const int o = role;
-    const bool isv = o == h.A;
+    const bool isv = o == npc;
     f32x4 acc = zero4();
     float bsum = 0.f;
     for (int b0 = bg; b0 < h.B; b0 += 128) {
@@ -1489,15 +1593,37 @@ __device__ __forceinline__ void heads_bwd_role_wide(const HeadBwdArgs& h, int ro
         const int b = b0 + 16 * i;
         const bool ok = b < h.B;
         dd[i] = ok ? ld4(h.d1 + (size_t)b * HID + 4 * kq) : zero4();
-        gh[i] = ok ? (isv ? h.dv[b] : h.dz[(size_t)b * h.A + o]) : 0.f;
+        gh[i] = ok ? (isv ? h.dv[b] : h.dz[(size_t)b * npc + o]) : 0.f;
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc += dd[i] * gh[i];
     }
-    for (int b = k; b < h.B; b += 1024) bsum += isv ? h.dv[b] : h.dz[(size_t)b * h.A + o];
+    for (int b = k; b < h.B; b += 1024) bsum += isv ? h.dv[b] : h.dz[(size_t)b * npc + o];
     __syncthreads();                                        // a previous role's readers are done with sacc
     sacc[bg * 64 + kq] = acc;
     bsum = block_sum(bsum);                                 // its barriers also publish sacc
+    if constexpr (CONT) {
+      const int oc = o < h.A ? o : o - h.A;
+      const int64_t base = o < h.A ? 0 : (int64_t)(HID + 1) * h.A;   // out_x/w or out_y/w; its bias follows it
+      if (bg == 0) {
+        f32x4 tot = zero4();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) tot += sacc[i * 64 + kq];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int64_t e = base + (int64_t)(4 * kq + q) * h.A + oc;
+          if (isv) h.g_wv[4 * kq + q] = tot[q];
+          else h.g_wp[e] = tot[q];
+          if (UPD) fused_rmsprop(u, isv ? OFF_WV + 4 * kq + q : OFF_WP + e, tot[q]);
+        }
+      }
+      if (k == 0) {
+        const int64_t e = base + (int64_t)HID * h.A + oc;
+        if (isv) h.g_bv[0] = bsum; else h.g_wp[e] = bsum;
+        if (UPD) fused_rmsprop(u, isv ? OFF_BV : OFF_WP + e, bsum);
+      }
+      return;
+    }
     if (bg == 0) {
       f32x4 tot = zero4();
 #pragma unroll
@@ -1538,11 +1664,17 @@ struct Dense1TileArgs {
 // chunk are worked on out of the tail area BESIDE the chunk -- one more step of the batch contraction for the dWd waves, four
 // MFMAs of the rows' dn2 tile for every wave, folded in the epilogue behind barriers that are there anyway -- instead of as a
 // second chunk (two more barriers, a second staging pass and 64 dependent MFMAs on one wave: 9.0 -> 10.9 us at 132 rows)
-template <int UPD, bool TAIL = false>
+// CONT: the head roles are those of the continuous policy head (heads_bwd_role_wide<UPD, true>: 2A + 2 of them)
+template <int UPD, bool TAIL = false, bool CONT = false>
 __global__ __launch_bounds__(1024) void dense1_bwd_tile_kernel(Dense1TileArgs a) {
   extern __shared__ __attribute__((aligned(16))) float d1b_lds[];
   if ((int)blockIdx.x >= D1B_TILES) {                       // block-uniform: the head roles, dealt round-robin
-    for (int role = blockIdx.x - D1B_TILES; role < a.hb.A + 2; role += a.role_blocks) heads_bwd_role_wide<(UPD != 0)>(a.hb, role, d1b_lds, a.upd);
+    if constexpr (CONT) {
+      for (int role = blockIdx.x - D1B_TILES; role < 2 * a.hb.A + 2; role += a.role_blocks)
+        heads_bwd_role_wide<(UPD != 0), true>(a.hb, role, d1b_lds, a.upd);
+    } else {
+      for (int role = blockIdx.x - D1B_TILES; role < a.hb.A + 2; role += a.role_blocks) heads_bwd_role_wide<(UPD != 0)>(a.hb, role, d1b_lds, a.upd);
+    }
     return;
   }
   float* dds = d1b_lds;                                     // [128][260]  dd1 rows of the chunk
@@ -2423,6 +2555,8 @@ __global__ __launch_bounds__(1024) void slab_reduce_kernel(SlabSet s0, SlabSet s
 // the value gradient arena laid end to end).
 struct TensorTable { int64_t off[11]; };
 struct TensorTable2 { int64_t off[21]; };
+struct TensorTableC { int64_t off[13]; };   // the 12 tensors of the continuous network (logits_p/out_{x,y}/{w,b} last)
+template <class TT> constexpr int tt_tensors() { return (int)(sizeof(TT::off) / sizeof(int64_t)) - 1; }
 template <bool AVG, class TT>
 __global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict__ grad, TT tt, float clip,
                                                          float* __restrict__ scales) {
@@ -2460,11 +2594,12 @@ __device__ __forceinline__ float rmsprop_one(int64_t i, const float* __restrict_
 }
 
 constexpr int RMS_WD_BLOCKS = KSTEPS_DENSE;   // 242
-template <bool CLIP, bool MOM>
+// TT: the tensor table CLIP looks the per-tensor scale up in (TensorTable; TensorTableC for the continuous network)
+template <bool CLIP, bool MOM, class TT = TensorTable>
 __global__ __launch_bounds__(256) void rmsprop_kernel(const float* __restrict__ theta_in, float* __restrict__ theta_out,
                                                       float* __restrict__ ms, float* __restrict__ mom,
                                                       const float* __restrict__ grad, int64_t n, float lr,
-                                                      float one_minus_rho, float mu, float eps, TensorTable tt,
+                                                      float one_minus_rho, float mu, float eps, TT tt,
                                                       const float* __restrict__ scales, float* __restrict__ pk_out) {
   if (blockIdx.x < RMS_WD_BLOCKS) {
     const int s = blockIdx.x, col = threadIdx.x;
@@ -2489,7 +2624,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(const float* __restrict__ 
     if (CLIP) {
       int ti = 0;
 #pragma unroll
-      for (int k = 1; k < 10; ++k) ti += (i >= tt.off[k]) ? 1 : 0;
+      for (int k = 1; k < tt_tensors<TT>(); ++k) ti += (i >= tt.off[k]) ? 1 : 0;
       sc = scales[ti];
     }
     const float tn = rmsprop_one<CLIP, MOM>(i, theta_in, theta_out, ms, mom, grad, lr, one_minus_rho, mu, eps, sc);

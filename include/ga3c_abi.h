@@ -33,6 +33,11 @@ extern "C" {
 #define GA3C_FLAG_GRAD_CLIP 2u     /* Config.USE_GRAD_CLIP, tf.clip_by_average_norm, :120-123 */
 #define GA3C_FLAG_DUAL_RMSPROP 4u  /* Config.DUAL_RMSPROP: one RMSProp optimizer per cost (cost_p, cost_v), :87-99,108-117,126-127;
                                       with GA3C_FLAG_GRAD_CLIP, tf.clip_by_norm per gradient tensor instead */
+#define GA3C_FLAG_CONTINUOUS 8u    /* Config.CONTINUOUS_INPUT: the angle-output policy head of reference NetworkVP.py:92,95-105,175-204
+                                      (DESIGN.md 8d).  p = atan2(sigmoid(d1 Wy + by) - 0.5, sigmoid(d1 Wx + bx) - 0.5) / pi is the
+                                      action vector [B,A] (in (-1, 1]); a train batch's `a` is [B,A] float actions; every `z`
+                                      output is [hx | hy], B x 2A (hx = d1 Wx + bx, hy = d1 Wy + by).  num_actions <= 32.
+                                      With GA3C_FLAG_DUAL_RMSPROP: GA3C_EINVAL (not supported yet) */
 
 #define GA3C_STATE_FLOATS 28224    /* 84*84*4 (Config.py:90-92) */
 #define GA3C_MAX_ACTIONS 64
@@ -72,6 +77,8 @@ int ga3c_net_destroy(ga3c_net* net);
 /* Parameter arena.  Flat f32 in TensorFlow variable order and layout:
  * conv11/w[8,8,4,16] conv11/b[16] conv12/w[4,4,16,32] conv12/b[32] dense1/w[3872,256]
  * dense1/b[256] logits_v/w[256,1] logits_v/b[1] logits_p/w[256,A] logits_p/b[A].
+ * GA3C_FLAG_CONTINUOUS: logits_p/{w,b} are replaced by logits_p/out_x/w[256,A] logits_p/out_x/b[A] logits_p/out_y/w[256,A]
+ * logits_p/out_y/b[A] (TF creation order), OFF_WP + 2 (256 A + A) floats in all; names and checkpoints follow (12 variables).
  * Replaces get_variable_value / tf.train.Saver (NetworkVP.py:62-64,267-288).
  * which: 0 = weights, 1 = RMSProp `ms` slot, 2 = RMSProp `mom` slot, 3 = last gradient.
  * With GA3C_FLAG_DUAL_RMSPROP, 1 / 2 / 3 belong to the optimizer of cost_p (which stands in for cost_all) and
@@ -111,7 +118,8 @@ int ga3c_net_save(ga3c_net* net, const char* path);
 int ga3c_net_load(ga3c_net* net, const char* path);
 
 /* predict_p_and_v (NetworkVP.py:248-252): x f32[B,84,84,4] NHWC host buffer ->
- * p f32[B,A] (softmax_p), v f32[B] (logits_v); z f32[B,A] (logits_p) if not NULL. */
+ * p f32[B,A] (softmax_p), v f32[B] (logits_v); z f32[B,A] (logits_p) if not NULL.
+ * GA3C_FLAG_CONTINUOUS: p is the action vector (the angle output) and z f32[B,2A] = [hx | hy] per row. */
 int ga3c_net_predict(ga3c_net* net, const float* x, int32_t batch, float* p, float* v, float* z);
 /* Same, states shipped as the uint8 frames of Environment._preprocess before its
  * `/128 - 1` (Environment.py:59-60); they stay uint8 in HBM and the conv kernels convert while
@@ -120,7 +128,7 @@ int ga3c_net_predict_u8(ga3c_net* net, const uint8_t* x, int32_t batch, float* p
 
 /* train (NetworkVP.py:254-257 = sess.run(train_op)): forward, loss, backward,
  * (all-reduce when a communicator is attached), RMSProp, global_step += 1.
- * y_r f32[B], a f32[B,A] one-hot.  losses (may be NULL) receives
+ * y_r f32[B], a f32[B,A] one-hot (GA3C_FLAG_CONTINUOUS: the float action vectors taken).  losses (may be NULL) receives
  * {cost_p_1_agg, cost_p_2_agg, cost_v} (NetworkVP_discrate.py:61,83-84) of this rank's rows. */
 int ga3c_net_train(ga3c_net* net, const float* x, const float* y_r, const float* a, int32_t batch,
                    float learning_rate, float beta, float* losses);

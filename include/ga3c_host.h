@@ -55,7 +55,7 @@ int ga3c_frame_preprocess(const uint8_t* rgb, int32_t height, int32_t width, int
  *   request ring  lock-free MPMC ring of agent ids (capacity >= max_agents: one request per agent in flight,
  *                 as wait_q = Queue(maxsize=1) in ProcessAgent.py:64)
  *   rollout slots [train_slots] x { rows, states[train_rows x state_bytes], returns f32[train_rows],
- *                 actions i32[train_rows] }, with a free ring and a ready ring (the bound of
+ *                 actions i32[train_rows] (float_actions: f32[train_rows x num_actions]) }, with a free ring and a ready ring (the bound of
  *                 Queue(maxsize=MAX_QUEUE_SIZE), Server.py:73)
  * The whole segment can be registered with HIP (hipHostRegister) so the GPU gathers states
  * straight from the slots.  Blocking uses futexes in the segment; nothing spins.            */
@@ -69,7 +69,10 @@ typedef struct ga3c_shm_config {
   int32_t train_rows;    /* rows per rollout slot (TIME_MAX + 1) */
   int32_t rollout_row_bytes; /* bytes per rollout row; 0 = state_bytes (rows carry whole states).  16 when rows only
                               * name a state kept on the device (agent id + plane sequence, ga3c_net_train_frames) */
-  int32_t reserved[2];
+  int32_t float_actions;   /* 1: a rollout row's action is num_actions float32 (Config.CONTINUOUS_INPUT: the action vector);
+                            * 0: one int32 action index.  A float segment carries another magic ("GA3CSHM2"); at 0 the
+                            * segment is byte for byte the int layout */
+  int32_t reserved[1];
 } ga3c_shm_config;
 
 int ga3c_shm_create(const char* name, const ga3c_shm_config* cfg, ga3c_shm** out);  /* server, before agents start */
@@ -204,7 +207,7 @@ int ga3c_pq_serve_frames_pipelined(ga3c_shm* shm, ga3c_serve_frames_begin_fn beg
 int ga3c_tq_acquire(ga3c_shm* shm, int32_t timeout_ms);                 /* -> free slot id */
 void* ga3c_tq_states(ga3c_shm* shm, int32_t slot);
 float* ga3c_tq_returns(ga3c_shm* shm, int32_t slot);
-int32_t* ga3c_tq_actions(ga3c_shm* shm, int32_t slot);
+int32_t* ga3c_tq_actions(ga3c_shm* shm, int32_t slot);   /* float_actions: float32 [train_rows, num_actions] behind the pointer */
 int ga3c_tq_commit(ga3c_shm* shm, int32_t slot, int32_t rows);
 int ga3c_tq_pop(ga3c_shm* shm, int32_t timeout_ms);                     /* -> ready slot id */
 int ga3c_tq_rows(ga3c_shm* shm, int32_t slot);
@@ -213,7 +216,7 @@ int ga3c_tq_release(ga3c_shm* shm, int32_t slot);
  * of the slots: pop rollouts until the batch holds MORE than min_rows rows.  *rows / *n_slots are the state of the batch in
  * progress (0 / 0 to start one; kept across GA3C_H_ETIMEOUT so that the caller can look at its exit flag and call again).
  * Per rollout: its slot id -> slots[], the byte offsets of its rows in the segment -> row_offsets[], its returns and actions
- * -> returns[] / actions[] (row-aligned).  The slots stay the caller's until ga3c_tq_release(_many).  Waits timeout_ms for the
+ * -> returns[] / actions[] (row-aligned; float_actions: num_actions float32 per row, actions[] then holds cap_rows x num_actions words).  The slots stay the caller's until ga3c_tq_release(_many).  Waits timeout_ms for the
  * first rollout and hold_timeout_ms once slots are held.  GA3C_H_ESTARVED: slots are held, none is free and none is queued
  * -- the agents are blocked on the caller, which must give slots back before asking again. */
 #define GA3C_H_ESTARVED 1
