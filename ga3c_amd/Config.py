@@ -8,7 +8,9 @@ end adds the knobs this engine needs (devices, transport, return mode).
 
 class Config:
     # ---- what to run -------------------------------------------------------------------------
-    GAME = 'PongDeterministic-v4'       # gym id, used by FRAME_SOURCE = 'gym' only; the offline sources are synthetic
+    GAME = 'PongDeterministic-v4'       # gym id, used by FRAME_SOURCE = 'gym' only; the offline sources are synthetic.
+                                        # 'Pendulum-v0' (the fork's own default): the vector-state network and the
+                                        # restated Pendulum (NetworkVP_vector.py, EnvironmentPend.py)
     PLAY_MODE = False                   # greedy actions, no training, one agent (GA3C.py:46-54)
     TRAIN_MODELS = True
     LOAD_CHECKPOINT = False
@@ -116,9 +118,26 @@ class Config:
     FRAME_HISTORY = 0                   # planes of history per agent on the device; 0 = derived from the queue bounds
 
 
+VECTOR_GAMES = ('Pendulum-v0',)         # games whose state is a vector (Server.py:35-38 of the reference)
+
+
+def vector_game():
+    return Config.GAME in VECTOR_GAMES
+
+
 def resolve_action_space(explicit=()):
     """DISCRATE_INPUT = not CONTINUOUS_INPUT, as the reference's Server.py:36-38 sets it.  `explicit`: the keys the command
-    line gave.  DISCRATE_INPUT given alone decides CONTINUOUS_INPUT; both given and contradictory (the same value) raise."""
+    line gave.  DISCRATE_INPUT given alone decides CONTINUOUS_INPUT; both given and contradictory (the same value) raise.
+    GAME = 'Pendulum-v0' sets CONTINUOUS_INPUT = True, as the reference's Server.py:35-38 does; a command line that asks
+    for the discrete head with it raises."""
+    if vector_game():
+        if ("CONTINUOUS_INPUT" in explicit and not Config.CONTINUOUS_INPUT) or \
+                ("DISCRATE_INPUT" in explicit and Config.DISCRATE_INPUT):
+            raise ValueError("GAME=%s has a continuous action space: CONTINUOUS_INPUT=%r / DISCRATE_INPUT=%r contradict it"
+                             % (Config.GAME, Config.CONTINUOUS_INPUT, Config.DISCRATE_INPUT))
+        Config.CONTINUOUS_INPUT = True
+        Config.DISCRATE_INPUT = False
+        return
     if "DISCRATE_INPUT" in explicit and "CONTINUOUS_INPUT" in explicit:
         if bool(Config.DISCRATE_INPUT) == bool(Config.CONTINUOUS_INPUT):
             raise ValueError("DISCRATE_INPUT=%r contradicts CONTINUOUS_INPUT=%r" % (Config.DISCRATE_INPUT, Config.CONTINUOUS_INPUT))

@@ -23,18 +23,27 @@ from datetime import datetime
 
 import numpy as np
 
-from Config import Config
+from Config import Config, vector_game
 from Environment import Environment, u8_to_f32
+import EnvironmentPend
 from Experience import Experience
 import Transport as tp
 
 MP = mp.get_context("forkserver")     # children never inherit the server's HIP state
 # the fork server imports the agent's modules once; every agent then starts as a fork of that warm process
-MP.set_forkserver_preload(["numpy", "Config", "Experience", "Environment", "_native", "Transport", "ProcessAgent"])
+MP.set_forkserver_preload(["numpy", "Config", "Experience", "Environment", "EnvironmentPend", "_native", "Transport",
+                           "ProcessAgent"])
 
 
 def config_snapshot():
+    """Config as the agent process sees it; GAME in it chooses the environment (make_environment)."""
     return {k: v for k, v in vars(Config).items() if k.isupper()}
+
+
+def make_environment(agent_id):
+    """The environment Config.GAME names: the restated Pendulum-v0 (a vector state, f32 in the transport whatever
+    STATE_TRANSPORT says) or the image-state source of Environment.py."""
+    return EnvironmentPend.Environment(agent_id) if vector_game() else Environment(agent_id)
 
 
 class ProcessAgent(MP.Process):
@@ -251,7 +260,7 @@ class ProcessAgent(MP.Process):
         self.transport = tp.Transport.attach(self.transport_name)
         self.names_states = bool(getattr(Config, "STATE_CACHE_ACTIVE", False))
         self.requests = self.transport.request_seq(self.id)   # (not 0 when the id was another agent's before)
-        self.env = Environment(self.id)
+        self.env = make_environment(self.id)
         self.num_actions = self.env.get_num_actions()
         self.actions = np.arange(self.num_actions)
         time.sleep(np.random.rand() * 0.2)                              # staggered start (:167)

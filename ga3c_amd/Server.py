@@ -4,18 +4,20 @@ learning rate and beta; services checkpoint requests (reference: ga3c/Server.py:
 What changed against the reference, and why:
   * prediction_q / training_q / wait_q are one shared-memory Transport (Transport.py) created
     before any agent starts;
-  * the model is the HIP-backed Network (NetworkVP.py), selected where the reference selects its
-    TensorFlow class (Server.py:48-54);
+  * the model is the HIP-backed Network (NetworkVP.py, or NetworkVP_vector.py for GAME = 'Pendulum-v0'), selected where
+    the reference selects its TensorFlow class (Server.py:35-54);
   * agents are started from a forkserver, so they never inherit the server's HIP state.
 """
 import os
 import threading
 import time
 
-from Config import Config, resolve_action_space
+from Config import Config, resolve_action_space, vector_game
 import DataParallel
 from Environment import Environment
+import EnvironmentPend
 from NetworkVP import Network, _device_ordinal
+import NetworkVP_vector
 import Placement
 import _native as nat
 from ProcessAgent import ProcessAgent, config_snapshot
@@ -31,6 +33,16 @@ class Server:
         # one Server per GPU under torch.distributed.run: lock-step training over RCCL (DataParallel.py)
         self.dp = engine_group
         resolve_action_space()                  # DISCRATE_INPUT = not CONTINUOUS_INPUT (Server.py:36-38)
+        # GAME = 'Pendulum-v0': the vector-state network, f32 states of 4 S bytes, no frame front-end or state cache
+        self.vector = vector_game()
+        if self.vector:
+            if Config.HOGWILD:
+                raise ValueError("HOGWILD is not supported by the vector-state network (GAME=%s)" % Config.GAME)
+            if engine_group is not None:
+                raise ValueError("data-parallel training (WORLD_SIZE > 1) is not supported by the vector-state network "
+                                 "(GAME=%s): it has no gradient exchange, the ranks would train apart" % Config.GAME)
+            if Config.FRONTEND == 'device':
+                raise ValueError("FRONTEND = 'device' is for image states; GAME=%s has vector states" % Config.GAME)
         self.dp_lock = threading.Lock()
         self.batch_lock = threading.Lock()      # one trainer at a time fills a batch (ThreadTrainer.py)
         self.closing = False
@@ -44,6 +56,8 @@ class Server:
         self.max_agents = int(max_agents or max(2 * Config.AGENTS, Config.AGENTS + 16))
         n_state = Config.IMAGE_HEIGHT * Config.IMAGE_WIDTH * Config.STACKED_FRAMES
         state_bytes = n_state if Config.STATE_TRANSPORT == 'u8' else 4 * n_state
+        if self.vector:
+            state_bytes = 4 * int(self.state_dim[0])
         # device-side frame front-end: slots carry the emulator's raw frame, rollout rows only name their state
         self.device_frontend = Config.FRONTEND == 'device'
         raw = Config.FRAME_SOURCE in ('rgb', 'gym')         # raw emulator frames; otherwise ready-made 84x84 planes
@@ -56,7 +70,7 @@ class Server:
         # instead of carrying them -- a trainer's batch no longer crosses PCIe a second time (include/ga3c_abi.h).  Only with
         # everything it rests on: the GPU reading the transport itself, uint8 states, the native pipelined predictor loop,
         # plain launches; anything else keeps the states in the rollouts.
-        model_cls = Network if model is None else type(model)
+        model_cls = (NetworkVP_vector.Network if self.vector else Network) if model is None else type(model)
         self.state_cache = bool(getattr(Config, "STATE_CACHE", False) and not self.device_frontend and Config.ZERO_COPY and
                                 Config.STATE_TRANSPORT == 'u8' and getattr(Config, "NATIVE_PREDICTOR", True) and
                                 getattr(Config, "PIPELINED_PREDICTOR", True) and getattr(Config, "NATIVE_TRAINER", True) and
@@ -65,8 +79,8 @@ class Server:
         Config.STATE_CACHE_ACTIVE = self.state_cache         # (the agents read it from their configuration snapshot)
         if self.state_cache:
             row_bytes = 16
-        self.model = model if model is not None else Network(Config.DEVICE, Config.NETWORK_NAME, self.num_actions,
-                                                             self.state_dim)
+        self.model = model if model is not None else model_cls(Config.DEVICE, Config.NETWORK_NAME, self.num_actions,
+                                                               self.state_dim)
         # training_q.get() frees a queue entry at once (ThreadTrainer.py:49); zero-copy trainers keep a rollout's slot
         # until the GPU has read it, so the slots they hold come on top of the queue bound
         slots = int(Config.ROLLOUT_SLOTS)
@@ -340,10 +354,14 @@ class Server:
 
     @staticmethod
     def get_state_dim():
+        if vector_game():
+            return EnvironmentPend.Environment.get_state_dim()
         return Environment.get_state_dim()
 
     @staticmethod
     def get_num_action():
+        if vector_game():
+            return EnvironmentPend.NUM_ACTIONS
         if Config.FRAME_SOURCE == 'gym':       # as the reference asks a throw-away Environment (Server.py:200-202);
             Environment()                      # it also fixes NUM_ACTIONS and the frame size in Config
         return int(Config.NUM_ACTIONS)

@@ -33,6 +33,12 @@ class NetConfig(C.Structure):
                 ("predict_lanes", C.c_int32), ("train_lanes", C.c_int32)]
 
 
+class MlpConfig(C.Structure):     # include/ga3c_abi.h: ga3c_mlp_config
+    _fields_ = [("device", C.c_int32), ("state_dim", C.c_int32), ("num_actions", C.c_int32), ("max_batch", C.c_int32),
+                ("flags", C.c_uint32), ("rmsprop_decay", C.c_float), ("rmsprop_momentum", C.c_float),
+                ("rmsprop_epsilon", C.c_float), ("grad_clip_norm", C.c_float), ("predict_lanes", C.c_int32)]
+
+
 class ShmConfig(C.Structure):
     _fields_ = [("max_agents", C.c_int32), ("num_actions", C.c_int32), ("state_bytes", C.c_int32),
                 ("train_slots", C.c_int32), ("train_rows", C.c_int32), ("rollout_row_bytes", C.c_int32),
@@ -115,6 +121,36 @@ HIP_SIGNATURES = {
     "ga3c_net_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ga3c_net_allreduce_grads": (C.c_int, [C.c_void_p]),
     "ga3c_net_time_allreduce": (C.c_int, [C.c_void_p, C.c_int32, f32p]),
+    # the vector-state network (GAME = 'Pendulum-v0'), include/ga3c_abi.h: ga3c_mlp_*
+    "ga3c_mlp_create": (C.c_int, [C.POINTER(MlpConfig), C.POINTER(C.c_void_p)]),
+    "ga3c_mlp_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_mlp_param_count": (C.c_int, [C.c_void_p, i64p]),
+    "ga3c_mlp_get_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_mlp_set_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_mlp_get_step": (C.c_int, [C.c_void_p, i64p]),
+    "ga3c_mlp_set_step": (C.c_int, [C.c_void_p, C.c_int64]),
+    "ga3c_mlp_num_params": (C.c_int32, [C.c_void_p]),
+    "ga3c_mlp_param_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
+    "ga3c_mlp_param_info": (C.c_int, [C.c_void_p, C.c_char_p, i64p, i64p, i32p, i64p]),
+    "ga3c_mlp_get_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_mlp_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_mlp_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "ga3c_mlp_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "ga3c_mlp_predict": (C.c_int, [C.c_void_p, f32p, C.c_int32, f32p, f32p, f32p]),
+    "ga3c_mlp_train": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
+    "ga3c_mlp_compute_grads": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, f32p]),
+    "ga3c_mlp_apply_grads": (C.c_int, [C.c_void_p, C.c_float]),
+    "ga3c_mlp_evaluate": (C.c_int, [C.c_void_p, f32p, i64p, f32p, f32p, C.c_int32, C.c_float, f32p, f32p, f32p, f32p, f32p,
+                                    f32p]),
+    "ga3c_mlp_register_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "ga3c_mlp_unregister_host": (C.c_int, [C.c_void_p]),
+    "ga3c_mlp_predict_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, f32p, f32p, f32p]),
+    "ga3c_mlp_predict_gather_begin": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, i32p]),
+    "ga3c_mlp_predict_gather_end": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f32p, f32p]),
+    "ga3c_mlp_train_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
+    "ga3c_mlp_upload": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32]),
+    "ga3c_mlp_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
+    "ga3c_mlp_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
 }
 
 HOST_SIGNATURES = {

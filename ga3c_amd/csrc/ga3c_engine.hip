@@ -1571,6 +1571,9 @@ void stop_lane_drivers(ga3c_net* net) {
 
 }  // namespace
 
+// The vector-state network (ga3c_mlp.hip) is linked into this library and reports its errors through the same message.
+__attribute__((visibility("hidden"))) void ga3c_set_last_error(const char* msg) { g_err = msg; }
+
 extern "C" {
 
 const char* ga3c_last_error(void) { return g_err.c_str(); }

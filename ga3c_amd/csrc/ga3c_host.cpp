@@ -593,7 +593,7 @@ static int action_words(const ga3c_shm_config* cfg) { return cfg->float_actions 
 int ga3c_shm_create(const char* name, const ga3c_shm_config* cfg, ga3c_shm** out) {
   if (!name || !cfg || !out) return fail(GA3C_H_EINVAL, "null argument");
   if (cfg->max_agents < 1 || cfg->max_agents > 65536 || cfg->num_actions < 1 || cfg->num_actions > MAXA ||
-      cfg->state_bytes < 16 || cfg->state_bytes % 16 != 0 || cfg->train_slots < 1 || cfg->train_slots > 65536 ||
+      cfg->state_bytes < 4 || cfg->state_bytes % 4 != 0 || cfg->train_slots < 1 || cfg->train_slots > 65536 ||
       cfg->train_rows < 1 || cfg->rollout_row_bytes < 0 || cfg->rollout_row_bytes % 16 != 0 ||
       (cfg->float_actions != 0 && cfg->float_actions != 1) || cfg->reserved[0] != 0)
     return fail(GA3C_H_EINVAL, "bad shm config");

@@ -326,6 +326,81 @@ int ga3c_net_time_allreduce(ga3c_net* net, int32_t iters, float* elapsed_ms);
 /* Sums the gradient arena (both halves, 2n floats, under GA3C_FLAG_DUAL_RMSPROP) over the ranks, on the train stream. */
 int ga3c_net_allreduce_grads(ga3c_net* net);
 
+/* ---- The vector-state network: reference NetworkVP.py:67-105,175-210, the network of GAME = 'Pendulum-v0' (DESIGN.md 8e).
+ * x[B,S] -> dense11_p (4, linear) -> dense12_p (256, linear) -> dense13_p (256, linear) -> dense14_p (100, sigmoid)
+ *        -> dense1 (64, sigmoid) -> logits_v (1) and the angle-output head logits_p/out_x, out_y (A each) of
+ *        GA3C_FLAG_CONTINUOUS; loss, gradient, RMSProp and GA3C_FLAG_GRAD_CLIP as there.
+ * A handle of its own: none of ga3c_net's workspace, lanes or fast paths apply.  Same conventions: int return codes,
+ * ga3c_last_error(), arenas 0 weights / 1 `ms` / 2 `mom` / 3 last gradient.  One HIP stream carries every kernel of the
+ * handle, so a prediction sees the weights before or after a train step, never a mix; train-type calls are serialised.
+ *
+ * Arena (TF creation order, 16 variables, 4 S + 99,305 + 130 A floats): dense11_p/w[S,4] /b[4] dense12_p/w[4,256] /b[256]
+ * dense13_p/w[256,256] /b[256] dense14_p/w[256,100] /b[100] dense1/w[100,64] /b[64] logits_v/w[64,1] /b[1]
+ * logits_p/out_x/w[64,A] /b[A] logits_p/out_y/w[64,A] /b[A].
+ * Checkpoints: the .npz container of ga3c_net_save with these 16 names; an image-network file and a vector-network file
+ * each refuse to load into the other kind of network (GA3C_ESTATE, network untouched). */
+typedef struct ga3c_mlp ga3c_mlp;
+typedef struct ga3c_mlp_config {
+  int32_t device;
+  int32_t state_dim;       /* S, 1..64 (Pendulum: 3) */
+  int32_t num_actions;     /* A, 1..32 (Pendulum: 1) */
+  int32_t max_batch;       /* rows of one predict / train call */
+  uint32_t flags;          /* GA3C_FLAG_CONTINUOUS (required) | GA3C_FLAG_GRAD_CLIP; anything else: GA3C_EINVAL */
+  float rmsprop_decay;
+  float rmsprop_momentum;
+  float rmsprop_epsilon;
+  float grad_clip_norm;
+  int32_t predict_lanes;   /* predictions in flight at once (begun and not ended); 0 -> 4 */
+} ga3c_mlp_config;
+
+int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out);   /* weights zero until set_arena(0) */
+int ga3c_mlp_destroy(ga3c_mlp* net);
+int ga3c_mlp_param_count(ga3c_mlp* net, int64_t* count);
+int ga3c_mlp_get_arena(ga3c_mlp* net, int32_t which, float* out, int64_t count);      /* which 0..3 */
+int ga3c_mlp_set_arena(ga3c_mlp* net, int32_t which, const float* in, int64_t count); /* which 0..2 */
+int ga3c_mlp_get_step(ga3c_mlp* net, int64_t* step);
+int ga3c_mlp_set_step(ga3c_mlp* net, int64_t step);
+int32_t ga3c_mlp_num_params(ga3c_mlp* net);                         /* 16 */
+const char* ga3c_mlp_param_name(ga3c_mlp* net, int32_t index);      /* arena order; NULL outside [0, 16) */
+int ga3c_mlp_param_info(ga3c_mlp* net, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]);
+int ga3c_mlp_get_param(ga3c_mlp* net, const char* name, int32_t which, float* out, int64_t count);
+int ga3c_mlp_set_param(ga3c_mlp* net, const char* name, int32_t which, const float* in, int64_t count);
+int ga3c_mlp_save(ga3c_mlp* net, const char* path);
+int ga3c_mlp_load(ga3c_mlp* net, const char* path);
+/* x f32[B,S] -> p f32[B,A] (the action vector), v f32[B]; z f32[B,2A] = [hx | hy] if not NULL. */
+int ga3c_mlp_predict(ga3c_mlp* net, const float* x, int32_t batch, float* p, float* v, float* z);
+/* One step: y_r f32[B], a f32[B,A] the actions taken; losses (may be NULL) = {cost_p_1_agg, cost_p_2_agg, cost_v}.
+ * 2 launches (3 with GA3C_FLAG_GRAD_CLIP); the row sums run in row order: the same call gives the same bits. */
+int ga3c_mlp_train(ga3c_mlp* net, const float* x, const float* y_r, const float* a, int32_t batch, float learning_rate,
+                   float beta, float* losses);
+int ga3c_mlp_compute_grads(ga3c_mlp* net, const float* x, const float* y_r, const float* a, int32_t batch, float beta,
+                           float* losses);                                     /* gradient into arena 3, no update */
+int ga3c_mlp_apply_grads(ga3c_mlp* net, float learning_rate);                 /* (clip +) RMSProp on arena 3, step += 1 */
+/* Forward + loss, no update: the states are x (host rows) or offsets (rows of the registered segment), exactly one.
+ * pd1 f32[B,4], pd2 f32[B,256], d1 f32[B,64], v f32[B], p f32[B,A] (each may be NULL): what the reference's summary
+ * histograms (NetworkVP.py:164-168) look at. */
+int ga3c_mlp_evaluate(ga3c_mlp* net, const float* x, const int64_t* offsets, const float* y_r, const float* a, int32_t batch,
+                      float beta, float* losses, float* pd1, float* pd2, float* d1, float* v, float* p);
+/* Zero-copy intake: rows are S f32 (4 S bytes, 4-byte aligned, not 16) at byte offsets into the registered segment; u8 must
+ * be 0.  predict_gather / _begin / _end have the signatures of ga3c_predict_rows_fn, ga3c_predict_begin_fn and
+ * ga3c_predict_end_fn (include/ga3c_host.h), so the native predictor loops drive this network unchanged. */
+int ga3c_mlp_register_host(ga3c_mlp* net, void* base, int64_t bytes);
+int ga3c_mlp_unregister_host(ga3c_mlp* net);
+int ga3c_mlp_predict_gather(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v, float* z);
+int ga3c_mlp_predict_gather_begin(void* net, const int64_t* offsets, int32_t batch, int32_t u8, int32_t* ticket);
+int ga3c_mlp_predict_gather_end(void* net, int32_t ticket, int32_t batch, float* p, float* v);
+int ga3c_mlp_train_gather(ga3c_mlp* net, const int64_t* offsets, int32_t u8, const float* y_r, const float* a, int32_t batch,
+                          float learning_rate, float beta, float* losses);
+/* Timing: upload stages a batch in HBM; time_resident runs `iters` steps on its first `batch` rows (mode 0 predict,
+ * 1 train) between two events on the network's stream -> milliseconds. */
+int ga3c_mlp_upload(ga3c_mlp* net, const float* x, const float* y_r, const float* a, int32_t batch);
+int ga3c_mlp_time_resident(ga3c_mlp* net, int32_t mode, int32_t batch, int32_t iters, float learning_rate, float beta,
+                           float* elapsed_ms);
+/* Rows of the last train / compute_grads / evaluate / resident step, for tests: name in {"x", "pd1", "pd2", "pd3", "pd4",
+ * "d1", "v", "z", "p", "dpd1", "dpd2", "dpd3", "dpd4", "dd1" (deltas at the layers' pre-activations), "dv", "dz",
+ * "lossrow"}; count = rows x width. */
+int ga3c_mlp_fetch(ga3c_mlp* net, const char* name, float* out, int64_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,7 +64,8 @@ typedef struct ga3c_shm ga3c_shm;
 typedef struct ga3c_shm_config {
   int32_t max_agents;
   int32_t num_actions;
-  int32_t state_bytes;   /* 28224 (uint8 frames) or 112896 (f32 states) */
+  int32_t state_bytes;   /* 28224 (uint8 frames) or 112896 (f32 states); 4 S for the vector states of GAME = 'Pendulum-v0'
+                            (a multiple of 4: rollout rows of such states are not 16-byte aligned) */
   int32_t train_slots;   /* rollouts in flight (MAX_QUEUE_SIZE) */
   int32_t train_rows;    /* rows per rollout slot (TIME_MAX + 1) */
   int32_t rollout_row_bytes; /* bytes per rollout row; 0 = state_bytes (rows carry whole states).  16 when rows only
