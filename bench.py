@@ -2,9 +2,13 @@
 """bench.py -- the reference's headline metric (predictions/s + training-steps/s, 84x84x4 stacked
 frames, NetworkVP) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-           --master-port P bench.py --gpus N --steps K --warmup W
+           --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run measures the headline alone: set-up, the warm-up, the K timed predict steps, --dump-outputs, and the
+JSON line.  --full also runs every other leg below (lane sweep, train legs, uint8 legs, RCCL, per-kernel roofline,
+CPU baseline, Hogwild, front-end, whole-engine legs) after the headline block and adds them to the same line.
 
 A step is one pass of the hot path over one batch that is already resident in HBM:
   predict leg (the headline `value`): one ThreadPredictor batch (BASELINE.json configs[1]:
@@ -12,9 +16,9 @@ A step is one pass of the hot path over one batch that is already resident in HB
       NP prediction lanes = predictor threads, each lane with its own HIP stream and workspace exactly as
       ThreadPredictor uses them.  NP = 2 (--predictors): the reference's and this package's default
       Config.PREDICTORS = 2 (Config.py:57, README.md:28-32 "NP: 2"), on the HIP runtime's default number of
-      hardware queues -- the configuration a Server with Config defaults runs.  The 1-, 3- and 4-lane figures of
-      the same K steps are reported beside it under "predict_lanes";
-  train leg (reported under "train"): one ThreadTrainer batch (configs[2]: 128 rows) through forward,
+      hardware queues -- the configuration a Server with Config defaults runs.  With --full the 1-, 3- and 4-lane
+      figures of the same K steps are reported beside it under "predict_lanes";
+  train leg (--full, reported under "train"): one ThreadTrainer batch (configs[2]: 128 rows) through forward,
       loss, backward, RCCL all-reduce of the gradient arena when N > 1, RMSProp.
 Per-GPU work is fixed as N grows (weak scaling); predictions need no collective.
 No torch in this process: the device sync is ga3c_net_sync (hipStreamSynchronize on every stream of the
@@ -139,11 +143,16 @@ def main():
     ap.add_argument("--actions", type=int, default=6)
     ap.add_argument("--predictors", type=int, default=2, help="prediction lanes the K predict steps are dealt to (predictor threads; "
                                                                "Config.PREDICTORS = 2 is the reference's and the package's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline block, also run every other leg (lane sweep, train, uint8, RCCL, per-kernel "
+                         "roofline, CPU baseline, Hogwild, front-end, whole engine); a plain run measures the headline alone")
     ap.add_argument("--no-lane-sweep", action="store_true",
-                    help="skip the extra 1- and 3-lane legs (use with --predictors 1 under rocprofv3 so that kernels never overlap)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample length; 0 disables it")
+                    help="--full: skip the extra 1- and 3-lane legs (use with --predictors 1 under rocprofv3 so that kernels "
+                         "never overlap)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU-baseline sample length; 0 disables it")
     ap.add_argument("--e2e-seconds", type=float, default=8.0,
-                    help="also run the whole engine (agent processes -> transport -> predictor/trainer threads) this long; 0 disables")
+                    help="--full: also run the whole engine (agent processes -> transport -> predictor/trainer threads) this "
+                         "long; 0 disables")
     ap.add_argument("--e2e-agents", type=int, default=32)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed prediction step returned (p, v) as DIR/<name>.npy (float32); the "
@@ -189,7 +198,7 @@ def main():
     lib, h = net._lib, net._h
 
     dp_error = None
-    if world > 1:
+    if world > 1 and args.full:                         # the headline's predictions need no communicator
         try:
             DataParallel.attach(net, rank, world)      # RCCL communicator; the 128-byte id travels over the control plane
         except RuntimeError as e:                       # predictions need no collective: keep the headline leg alive
@@ -268,60 +277,60 @@ def main():
             buf = np.empty(n, dtype=np.float32)
             nat.check(lib.ga3c_net_fetch_lane(h, last, name.encode(), nat.ptr(buf), n), "fetch_lane")
             dumped[name] = buf.reshape((B, A) if name == "p" else (B,))
-    one_s = timed(0, K, lanes=1)[1]
-    sweep = {}
-    if not args.no_lane_sweep:
-        for nl in (2, 3, 4):
-            if nl != NP:
-                sweep[nl] = timed(0, K, lanes=nl)[1]
-    dp_guard = None
-    if world > 1:
-        # the collective legs below have never run with N > 1 on hardware in this build's development (one-GPU box): if a
-        # rank never returns from one, the job must still end and leave the driver its line, with the prediction leg measured
-        import threading
+    if args.full:                                   # every leg beyond the headline block
+        one_s = timed(0, K, lanes=1)[1]
+        sweep = {}
+        if not args.no_lane_sweep:
+            for nl in (2, 3, 4):
+                if nl != NP:
+                    sweep[nl] = timed(0, K, lanes=nl)[1]
+        dp_guard = None
+        if world > 1:
+            # the collective legs below are the only ones that can wait on another rank forever: if a rank never returns
+            # from one, the job must still end and print its line, with the prediction leg measured
+            import threading
 
-        def give_up_dp():
-            if rank == 0:
-                print(json.dumps({
-                    "metric": "predictions_per_sec", "value": world * K * B / pred_s, "unit": "predictions/s", "n_gpus": world,
-                    "steps": K, "warmup": W, "ms_per_step": pred_s / K * 1e3, "higher_is_better": True, "scaling": "weak",
-                    "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-                    "config": {"workload": "PongDeterministic-v4 84x84x4 stacked frames, NetworkVP forward, predictor batch=%d, "
-                                           "NP=%d predictor lanes per GPU, A=%d (BASELINE configs[1])" % (B, NP, A),
-                               "global_batch": world * B, "parallelism": "dp%d" % world},
-                    "train": None, "roofline": None, "cpu_baseline": None,
-                    "error": "a data-parallel (RCCL) leg did not finish within 300 s; predictions need no collective and are reported"}),
-                    flush=True)
-            os._exit(3)      # a process that gives up on a GPU collective must not look like a clean run (every rank exits non-zero)
-        dp_guard = threading.Timer(300.0, give_up_dp)
-        dp_guard.daemon = True
-        dp_guard.start()
-    if dp_error is None:
-        train_gpu_s, train_s = timed(1, K)
-        train_tb_gpu_s, train_tb_s = timed(1, K, rows=TB)   # what the engine's trainers really assemble at MIN = B - 1
-    else:                                               # no communicator: the data-parallel train leg is not measured
-        train_s, train_gpu_s, train_tb_s, train_tb_gpu_s = None, None, None, None
-    allreduce_us = None
-    if world > 1 and dp_error is None:      # the exchange step alone: 4.02 MB f32 sum all-reduce, events on the train stream
-        barrier_sync()
-        nat.check(lib.ga3c_net_time_allreduce(h, 50, nat.C.byref(ev_ms)), "time_allreduce")
-        allreduce_us = ev_ms.value / 50 * 1e3
-    # the engine's own intake format: uint8 frames resident in HBM, converted inside the conv kernels (extra figure)
-    xk = np.ascontiguousarray(((x_tb + np.float32(1)) * np.float32(128)).astype(np.uint8))
-    nat.check(lib.ga3c_net_upload_u8(h, nat.ptr(xk, nat.u8p), nat.ptr(y_r_tb), nat.ptr(act_tb), TB), "upload_u8")
-    nat.check(lib.ga3c_net_time_predict_lanes(h, B, max(W, 1), NP, nat.C.byref(ev_ms)), "warmup")
-    u8_s = timed(0, K, lanes=NP)[1]
-    u8_train_s = timed(1, K)[1] if dp_error is None else None
-    u8_train_tb_s = timed(1, K, rows=TB)[1] if dp_error is None else None
-    nat.check(lib.ga3c_net_upload(h, nat.ptr(x_tb), nat.ptr(y_r_tb), nat.ptr(act_tb), TB), "upload")
-    comm_ranks, comm_rank, comm_dev = net.comm_info()
-    if dp_guard is not None:
-        dp_guard.cancel()
+            def give_up_dp():
+                if rank == 0:
+                    print(json.dumps({
+                        "metric": "predictions_per_sec", "value": world * K * B / pred_s, "unit": "predictions/s", "n_gpus": world,
+                        "steps": K, "warmup": W, "ms_per_step": pred_s / K * 1e3, "higher_is_better": True, "scaling": "weak",
+                        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                        "config": {"workload": "PongDeterministic-v4 84x84x4 stacked frames, NetworkVP forward, predictor batch=%d, "
+                                               "NP=%d predictor lanes per GPU, A=%d (BASELINE configs[1])" % (B, NP, A),
+                                   "global_batch": world * B, "parallelism": "dp%d" % world},
+                        "train": None, "roofline": None, "cpu_baseline": None,
+                        "error": "a data-parallel (RCCL) leg did not finish within 300 s; predictions need no collective and are reported"}),
+                        flush=True)
+                os._exit(3)      # a process that gives up on a GPU collective must not look like a clean run (every rank exits non-zero)
+            dp_guard = threading.Timer(300.0, give_up_dp)
+            dp_guard.daemon = True
+            dp_guard.start()
+        if dp_error is None:
+            train_gpu_s, train_s = timed(1, K)
+            train_tb_gpu_s, train_tb_s = timed(1, K, rows=TB)   # what the engine's trainers really assemble at MIN = B - 1
+        else:                                               # no communicator: the data-parallel train leg is not measured
+            train_s, train_gpu_s, train_tb_s, train_tb_gpu_s = None, None, None, None
+        allreduce_us = None
+        if world > 1 and dp_error is None:      # the exchange step alone: 4.02 MB f32 sum all-reduce, events on the train stream
+            barrier_sync()
+            nat.check(lib.ga3c_net_time_allreduce(h, 50, nat.C.byref(ev_ms)), "time_allreduce")
+            allreduce_us = ev_ms.value / 50 * 1e3
+        # the engine's own intake format: uint8 frames resident in HBM, converted inside the conv kernels (extra figure)
+        xk = np.ascontiguousarray(((x_tb + np.float32(1)) * np.float32(128)).astype(np.uint8))
+        nat.check(lib.ga3c_net_upload_u8(h, nat.ptr(xk, nat.u8p), nat.ptr(y_r_tb), nat.ptr(act_tb), TB), "upload_u8")
+        nat.check(lib.ga3c_net_time_predict_lanes(h, B, max(W, 1), NP, nat.C.byref(ev_ms)), "warmup")
+        u8_s = timed(0, K, lanes=NP)[1]
+        u8_train_s = timed(1, K)[1] if dp_error is None else None
+        u8_train_tb_s = timed(1, K, rows=TB)[1] if dp_error is None else None
+        nat.check(lib.ga3c_net_upload(h, nat.ptr(x_tb), nat.ptr(y_r_tb), nat.ptr(act_tb), TB), "upload")
+        comm_ranks, comm_rank, comm_dev = net.comm_info()
+        if dp_guard is not None:
+            dp_guard.cancel()
 
     out = None
     if rank == 0:
         pps = world * K * B / pred_s
-        tps = K / train_s if train_s else None  # synchronous data-parallel: one global step per K
         out = {
             "metric": "predictions_per_sec", "value": pps, "unit": "predictions/s", "n_gpus": world,
             "steps": K, "warmup": W, "ms_per_step": pred_s / K * 1e3, "higher_is_better": True,
@@ -330,13 +339,6 @@ def main():
                                    "predictor batch=%d, NP=%d predictor lanes per GPU, A=%d (BASELINE configs[1])" % (B, NP, A),
                        "global_batch": world * B, "parallelism": "dp%d" % world,
                        "inputs": "resident in HBM (f32 NHWC), outputs p,v left in HBM"},
-            "predict_lanes": dict({"1": world * K * B / one_s, str(NP): pps},
-                                  **{str(nl): world * K * B / s_ for nl, s_ in sweep.items()},
-                                  unit="predictions/s", hardware_queues="runtime default",
-                                  note="same K steps dealt to 1 .. 4 prediction lanes (one persistent host thread per lane); "
-                                       "`value` is the NP = %d figure, the default of the reference and of this package; lanes "
-                                       "beyond three share the three prediction streams (ga3c_net_create: the engine keeps to "
-                                       "four normal-priority streams)" % NP),
             "gpu_span_ms_per_step": pred_gpu_s / K * 1e3, "value_gpu_span": world * K * B / pred_gpu_s,
             "inner_wall_ms_per_step": pred_inner_s / K * 1e3,
             "timing": "ms_per_step / value: HOST WALL-CLOCK (time.perf_counter) of the one bracketed K-step block, max over "
@@ -348,35 +350,46 @@ def main():
                       "last end (round 3's headline).  inner_wall_ms_per_step: the host clock read inside "
                       "ga3c_net_time_predict_lanes, from the release of the lanes to the last lane's wait",
             "cpu_placement": placement, "torch_imported": "torch" in sys.modules,
-            "train": {"metric": "training_steps_per_sec", "value": tps, "unit": "steps/s",
-                      "ms_per_step": train_s / K * 1e3 if train_s else None, "rows_per_step": world * B,
-                      "gpu_span_ms_per_step": train_gpu_s / K * 1e3 if train_gpu_s else None,
-                      "trained_samples_per_sec": world * K * B / train_s if train_s else None,
-                      "workload": "forward+loss+backward%s+RMSProp, %d rows per GPU (BASELINE configs[2])"
-                                  % ("+RCCL all-reduce(sum) of 4.02 MB grads" if world > 1 else "", B),
-                      "train_%d" % TB: {"rows_per_step": world * TB, "ms_per_step": train_tb_s / K * 1e3 if train_tb_s else None,
-                                         "gpu_span_ms_per_step": train_tb_gpu_s / K * 1e3 if train_tb_gpu_s else None,
-                                         "steps_per_sec": K / train_tb_s if train_tb_s else None,
-                                         "note": "the largest batch ThreadTrainer assembles at TRAINING_MIN_BATCH_SIZE = %d "
-                                                 "(ThreadTrainer.py:49-59): MIN + TIME_MAX rows" % (B - 1)}},
-            "data_parallel_error": dp_error,
-            "rccl_ranks": comm_ranks if world > 1 else 1,
-            "rccl_comm": {"ranks": comm_ranks, "rank": comm_rank, "device": comm_dev,
-                          "source": "ncclCommCount / ncclCommUserRank / ncclCommCuDevice of the attached communicator "
-                                    "(ga3c_net_comm_info); 0 / -1 / -1 = no communicator (N = 1 attaches none)"},
-            "allreduce_us": allreduce_us,
-            "allreduce_note": "average of 50 back-to-back ncclAllReduce(sum, f32, 1,005,623 elements = 4.02 MB) on the train "
-                              "stream, HIP events around them; inside a train step the dense1/w part overlaps with the conv "
-                              "backward kernels" if world > 1 else None,
-            "uint8_resident": {"predictions_per_sec": world * K * B / u8_s,
-                               "training_steps_per_sec": K / u8_train_s if u8_train_s else None,
-                               "training_steps_per_sec_%d_rows" % TB: K / u8_train_tb_s if u8_train_tb_s else None,
-                               "note": "same legs with the batch resident as uint8 frames (28,224 B per state), the "
-                                       "format the shared-memory transport delivers; bit-identical results"},
         }
+        if args.full:
+            tps = K / train_s if train_s else None  # synchronous data-parallel: one global step per K
+            out.update({
+                "predict_lanes": dict({"1": world * K * B / one_s, str(NP): pps},
+                                      **{str(nl): world * K * B / s_ for nl, s_ in sweep.items()},
+                                      unit="predictions/s", hardware_queues="runtime default",
+                                      note="same K steps dealt to 1 .. 4 prediction lanes (one persistent host thread per lane); "
+                                           "`value` is the NP = %d figure, the default of the reference and of this package; lanes "
+                                           "beyond three share the three prediction streams (ga3c_net_create: the engine keeps to "
+                                           "four normal-priority streams)" % NP),
+                "train": {"metric": "training_steps_per_sec", "value": tps, "unit": "steps/s",
+                          "ms_per_step": train_s / K * 1e3 if train_s else None, "rows_per_step": world * B,
+                          "gpu_span_ms_per_step": train_gpu_s / K * 1e3 if train_gpu_s else None,
+                          "trained_samples_per_sec": world * K * B / train_s if train_s else None,
+                          "workload": "forward+loss+backward%s+RMSProp, %d rows per GPU (BASELINE configs[2])"
+                                      % ("+RCCL all-reduce(sum) of 4.02 MB grads" if world > 1 else "", B),
+                          "train_%d" % TB: {"rows_per_step": world * TB, "ms_per_step": train_tb_s / K * 1e3 if train_tb_s else None,
+                                             "gpu_span_ms_per_step": train_tb_gpu_s / K * 1e3 if train_tb_gpu_s else None,
+                                             "steps_per_sec": K / train_tb_s if train_tb_s else None,
+                                             "note": "the largest batch ThreadTrainer assembles at TRAINING_MIN_BATCH_SIZE = %d "
+                                                     "(ThreadTrainer.py:49-59): MIN + TIME_MAX rows" % (B - 1)}},
+                "data_parallel_error": dp_error,
+                "rccl_ranks": comm_ranks if world > 1 else 1,
+                "rccl_comm": {"ranks": comm_ranks, "rank": comm_rank, "device": comm_dev,
+                              "source": "ncclCommCount / ncclCommUserRank / ncclCommCuDevice of the attached communicator "
+                                        "(ga3c_net_comm_info); 0 / -1 / -1 = no communicator (N = 1 attaches none)"},
+                "allreduce_us": allreduce_us,
+                "allreduce_note": "average of 50 back-to-back ncclAllReduce(sum, f32, 1,005,623 elements = 4.02 MB) on the train "
+                                  "stream, HIP events around them; inside a train step the dense1/w part overlaps with the conv "
+                                  "backward kernels" if world > 1 else None,
+                "uint8_resident": {"predictions_per_sec": world * K * B / u8_s,
+                                   "training_steps_per_sec": K / u8_train_s if u8_train_s else None,
+                                   "training_steps_per_sec_%d_rows" % TB: K / u8_train_tb_s if u8_train_tb_s else None,
+                                   "note": "same legs with the batch resident as uint8 frames (28,224 B per state), the "
+                                           "format the shared-memory transport delivers; bit-identical results"},
+            })
 
     # ---- roofline of the dominant kernel (conv1 forward: 48% of the forward FLOPs), rank 0 only
-    if rank == 0:
+    if args.full and rank == 0:
         kernels = {}
         iters = 50
         for name in ("conv_stack_fwd", "conv1_fwd", "conv2_fwd", "dense1_fwd", "heads", "dense1_dw", "dense1_dx", "dense1_bwd", "dense1_bwd_tile", "conv2_dw",
@@ -411,7 +424,7 @@ def main():
 
     # ---- CPU baseline: the oracle's C port on this box's host cores, kernel-only, forward and
     # forward-backward + RMSProp at B in {1, 32, 128, 512} (rank 0, N = 1 only).  The headline sample is the bench batch.
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         import ga3c_oracle_cport as oc
         oc.lib().ga3c_oc_set_threads(min(os.cpu_count() or 1, 16))   # a one-GPU box's CPU share is 16 cores
         theta = net.get_arena(0)
@@ -452,11 +465,11 @@ def main():
                                "kernel_only_by_batch": dict(sizes, note="BASELINE.md section 4 item 1: forward and forward-backward + "
                                                             "RMSProp at B in {1, 32, 128, 512}, same C port, same threads")}
 
-    cpu_theta = net.get_arena(0) if (rank == 0 and world == 1 and args.cpu_seconds > 0) else None
+    cpu_theta = net.get_arena(0) if (args.full and rank == 0 and world == 1 and args.cpu_seconds > 0) else None
     net.close()
 
     # ---- Hogwild trainers: the reference's default NT = 2 trainer threads update shared weights unlocked (Server.py:132-134)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         hog = Network("gpu:%d" % local_rank, "bench_hogwild", A, (84, 84, 4), max_batch=B, predict_lanes=1, train_lanes=4)
         nat.check(hog._lib.ga3c_net_upload(hog._h, nat.ptr(x), nat.ptr(y_r), nat.ptr(act), B), "upload")
         ms = nat.C.c_float()
@@ -546,7 +559,7 @@ def main():
         hog.close()
 
     # ---- whole engine, BASELINE configs[1]/[2] shape: agents -> shm transport -> ThreadPredictor / ThreadTrainer -> HIP
-    if rank == 0 and world == 1 and args.e2e_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.e2e_seconds > 0:
         out["e2e"] = dict(run_engine(None, args.e2e_seconds, args.e2e_agents, B, A),
                           note="synthetic Python agents (PCG64 frames) on this box's host cores; predictions served and "
                                "train steps taken by the engine over the steady window of the run (whole_run includes "
@@ -596,7 +609,7 @@ def main():
                      "4 OpenMP threads per calling thread)")
 
     # ---- N-rank engine: one Server per GPU (own agents, own transport), lock-step training over RCCL (DataParallel.EngineGroup)
-    if world > 1 and args.e2e_seconds > 0 and dp_error is None:
+    if args.full and world > 1 and args.e2e_seconds > 0 and dp_error is None:
         import threading
 
         def give_up():      # a rank that never joins a collective would hang the job: the line is printed without this leg

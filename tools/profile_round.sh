@@ -10,11 +10,11 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 100 --warmup 10 --predictors 1 --no-lane-sweep --cpu-seconds 0 --e2e-seconds 0"
+BENCH="python3 $ROOT/bench.py --full --steps 100 --warmup 10 --predictors 1 --no-lane-sweep --cpu-seconds 0 --e2e-seconds 0"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats_bench.json 2> $OUT/stats.err
 echo "stats pass done"
-SHORT="python3 $ROOT/bench.py --steps 20 --warmup 2 --predictors 1 --no-lane-sweep --cpu-seconds 0 --e2e-seconds 0"
+SHORT="python3 $ROOT/bench.py --full --steps 20 --warmup 2 --predictors 1 --no-lane-sweep --cpu-seconds 0 --e2e-seconds 0"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $OUT/pmc_SQ -- $SHORT > /dev/null 2> $OUT/pmc_SQ.err
 echo "SQ pass done"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_FETCH_SIZE -- $SHORT > /dev/null 2> $OUT/pmc_FETCH.err

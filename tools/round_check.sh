@@ -1,17 +1,18 @@
 #!/bin/bash
-# One GPU call that says whether a build is good: the whole -m gpu suite, smoke(), and the driver's bench command line.
-#   usage (through gpurun, from the repo root):  bash tools/round_check.sh [tag]
+# One GPU call that says whether a build is good: the whole -m gpu suite, smoke(), and a `bench.py --full` line.
+#   usage (on the GPU machine, from the repo root):  bash tools/round_check.sh [tag] [output directory, default out]
 set -o pipefail
 TAG=${1:-check}
-mkdir -p gpurun_out
-timeout -k 10 900 python -m pytest tests -m gpu -x -q > gpurun_out/${TAG}_tests.log 2>&1; rc=$?
-echo "pytest rc=$rc"; tail -3 gpurun_out/${TAG}_tests.log
+OUT=${2:-out}
+mkdir -p "$OUT"
+timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$OUT/${TAG}_tests.log" 2>&1; rc=$?
+echo "pytest rc=$rc"; tail -3 "$OUT/${TAG}_tests.log"
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 90 python __graft_entry__.py smoke 2>&1 | tail -1 || exit 1
-timeout -k 10 500 python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_B128_k20.json 2> gpurun_out/${TAG}_bench_k20.err; echo "bench rc=$?"
-python - "$TAG" <<'PY'
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > "$OUT/${TAG}_bench_B128_k20.json" 2> "$OUT/${TAG}_bench_k20.err"; echo "bench rc=$?"
+python - "$OUT/${TAG}_bench_B128_k20.json" <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/%s_bench_B128_k20.json" % sys.argv[1]).read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("value %.3e (wall) / %.3e (GPU span), ms/step %.5f" % (d["value"], d["value_gpu_span"], d["ms_per_step"]),
       {a: round(b / 1e6, 2) for a, b in d["predict_lanes"].items() if a in "1234"})
 t = d["train"]
