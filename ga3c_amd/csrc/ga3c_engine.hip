@@ -234,6 +234,22 @@ int dense_ks(int B) {
 // round on the 256 CUs, sample 129 starts a second one (11.3 us at batch 128, 19.9 us at 132), so above 128 the
 // two-kernel form takes over (train steps/s at 132 rows: 10.3 k fused, 10.8 k split).
 constexpr int FUSED_CONV_MAX_B = 128;
+// conv2_fwd beyond the fused stack: at 129 .. 192 rows in units of four tiles (grid 4 B) instead of eight -- a CU that would
+// hold two 8-tile units pays the second one's MFMA time (7.4 -> 6.6 us at 132 rows).  Same bits.
+constexpr int C2F_QUARTER_MAX_B = 192;
+// Prediction steps of >= D1F_FRAG_MIN_B rows use the register-fragment dense1 (no LDS: it shares a CU with another lane's
+// conv stack, which the 148 KB tile kernel cannot) while at least D1F_FRAG_LANES prediction calls are in flight.  Same bits.
+// Measured, 1 / 2 / 3 / 4 lanes at 128 rows: threshold 3 -> 5.80 / 7.51 / 9.07 / 10.53 M predictions/s,
+// 2 -> 5.81 / 7.79 / 9.01 / 10.60, 1 -> 5.55 / 7.78 / 8.98 / 10.59
+constexpr int D1F_FRAG_MIN_B = 64, D1F_FRAG_LANES = 2;
+// The fused conv backward (conv2_dw + conv2_dx + conv1_dw in one launch, one workgroup per CU) takes CONV_BWD_MIN_B ..
+// CONV_BWD_MAX_B rows: beyond one round the tail of the second costs more than the fusion saves, and below, the split
+// launches are faster (uint8 train step 44.7 / 45.6 / 48.7 / 50.3 / 55.6 us against 49.3 / 50.1 / 51.5 / 52.9 / 56.4 at
+// 5 / 16 / 32 / 48 / 80 rows; 58.2 against 57.4 at 100): a small grid of the one-workgroup-per-CU kernel leaves most of the
+// chip idle, the split kernels spread the same rows over more workgroups
+constexpr int CONV_BWD_MIN_B = 97, CONV_BWD_MAX_B = 128;
+// split conv backward up to this many rows: conv2_dw and conv1_dw side by side in one launch behind conv2_dx (conv_dw_pair)
+constexpr int DW_PAIR_MAX_B = 256;
 // 16-row tiles per wave in dense1_dx (weight fragments are reused across them).  Measured, dense1_bwd per launch:
 // batch 256: 30.4 / 23.3 / 26.3 us with 4 / 2 / 1 tiles; batch 512: 39.6 / 41.4 / 46.3; batch 1024: 71.6 / 76.3 / 87.0.
 int dense_dx_mt(int B) { return B > 384 ? 4 : (B > 192 ? 2 : 1); }
@@ -329,21 +345,8 @@ struct ga3c_net {
   // the gradient) is final after the first backward kernel and is all-reduced on `cst` while the conv gradients are
   // still being computed on the train stream; the 49 KB in front follow when they are done
   hipStream_t cst = nullptr;
-  hipEvent_t ev_tail_ready = nullptr, ev_head_ready = nullptr, ev_comm_done = nullptr;
-  bool head_on_train_stream = true;    // GA3C_COMM_HEAD_INLINE=0: the conv gradients' exchange hops to the comm stream too (round 3)
+  hipEvent_t ev_tail_ready = nullptr, ev_comm_done = nullptr;
   bool comm_overlap = true;            // GA3C_COMM_OVERLAP=0: one blocking all-reduce of the whole arena behind the backward pass
-  bool fused_conv = true;              // conv1+conv2 in one launch (GA3C_SPLIT_CONV=1 selects the two-kernel form)
-  bool fused_update = true;            // single-GPU train steps: RMSProp applied by the kernels that complete each gradient
-                                       // element, no optimizer launch (GA3C_FUSED_UPDATE=0: the rmsprop kernel)
-  int c2dw_occ = 3;                    // conv2_dw up to 256 rows (one sample per workgroup): workgroups per CU its registers are cut for
-                                       // (GA3C_C2DW_OCC=2: the 205-VGPR form with the next sample's loads in flight, which larger batches run;
-                                       // measured 4.5 / 6.0 / 7.5 / 8.0 / 10.2 us against 4.6 / 6.2 / 9.0 / 9.3 / 11.2 at 64 / 128 / 132 / 192 / 256 rows)
-  bool conv_bwd_fused = true;          // conv2_dw + conv2_dx + conv1_dw in one launch (GA3C_CONV_BWD=0: conv2_dx, then the two weight gradients)
-  bool c2f_quarter = true;             // conv2_fwd at 129 .. 192 rows: four tiles per workgroup instead of eight (GA3C_C2F_QUARTER=0)
-  int conv_bwd_min = 97;               // ... from this many rows on (GA3C_CONV_BWD_MIN).  Below, the split launches are faster since round 4
-                                       // (uint8 train step 44.7 / 45.6 / 48.7 / 50.3 / 55.6 us against 49.3 / 50.1 / 51.5 / 52.9 / 56.4 at
-                                       // 5 / 16 / 32 / 48 / 80 rows; 58.2 against 57.4 at 100): a small grid of the one-workgroup-per-CU kernel
-                                       // leaves most of the chip idle, the split kernels spread the same rows over more workgroups
   // State cache (ga3c_net_state_cache_config): the uint8 states the prediction steps read out of the transport, kept in HBM
   // in a ring of `depth` per agent, slot = request number % depth -- a train batch then names its rows (agent, request
   // number) and is gathered HBM to HBM instead of crossing PCIe a second time.
@@ -352,28 +355,10 @@ struct ga3c_net {
   std::mutex cache_mu;
   std::vector<int64_t> cache_newest;   // per agent: the newest request number stored (-1: none)
   std::vector<int64_t> cache_tags;     // [agent][slot]: the request number the slot really holds (-1: nothing yet)
-  bool frames_in_line = true;          // GA3C_FRAMES_IN_LINE=0: rows out of the plane history are staged on the staging stream, beside a step
-  bool stop_events = true;             // GA3C_STOP_EVENTS=0: a prediction step's completion event is a hipEventRecord of its own
   bool offsets_in_args = true;         // GA3C_OFFSETS_IN_ARGS=0: the conv stack reads a scattered batch's offsets out of pinned host memory
   bool time_predictions = false;       // GA3C_TIME_PREDICTIONS=1: timing events around every prediction step (GA3C_STAT_PREDICT_GPU_NS)
-  int c1dw_blocks = 0;                 // conv1_dw workgroups = partial slabs of the split path; 0: conv1_dw_blocks() picks (GA3C_C1DW_BLOCKS)
-  bool dw_pair = true;                 // split path up to 256 rows: conv2_dw and conv1_dw in one launch behind conv2_dx (GA3C_DW_PAIR=0: two)
-  int wd_blocks_first = 0;             // ... at the front (1) or at the back (0) of that grid (GA3C_WD_BLOCKS_FIRST)
-  bool wd_step_in_conv2_dx = true;     // beyond 128 rows (split conv backward): dense1/w stepped by workgroups of their own in conv2_dx's
-                                       // launch instead of in dense1_bwd_tile's epilogue (GA3C_WD_STEP_IN_CONV2_DX=0: the epilogue)
-  int wd_step_in_conv_bwd = 1;         // fused update: dense1/w stepped inside conv_bwd (GA3C_WD_STEP_IN_CONV_BWD: 0 never -- in
-                                       // dense1_bwd_tile's epilogue --, 1 when conv_bwd's grid covers the 242 row groups, 2 always)
-                                       // Measured: 29 us against 5.7 + 5.8 us as two launches (profiles/README.md) -- kept for the record, off
-  int d1f_frag_lanes = 2;              // prediction steps of >= 64 rows use the register-fragment dense1 (no LDS: it shares a CU
-                                       // with another lane's conv stack, which the 148 KB tile kernel cannot) while at least
-                                       // this many prediction calls are in flight (GA3C_D1F_FRAG_LANES; 0 = never).  Same bits.
-                                       // Measured, 1 / 2 / 3 / 4 lanes at 128 rows: threshold 3 -> 5.80 / 7.51 / 9.07 / 10.53 M
-                                       // predictions/s, 2 -> 5.81 / 7.79 / 9.01 / 10.60, 1 -> 5.55 / 7.78 / 8.98 / 10.59
-  std::atomic<int> predict_inflight{0};
+  std::atomic<int> predict_inflight{0};   // prediction calls in flight (D1F_FRAG_LANES)
   bool d1f_tile = true;                // LDS-tiled dense1 forward where its grid is one round (GA3C_D1F_TILE=0: never)
-  bool d1b_tail = true;                // dense1_bwd_tile at 129 .. 133 rows: the rows past the first chunk wait in the LDS a chunk leaves free
-                                       // (D1B_TAIL_ROWS; GA3C_D1B_TAIL=0: a second round of staging loads, as for any larger batch)
-  int d1b_tile_max = 1 << 30;          // largest batch that takes the LDS-tiled dense1 backward (GA3C_D1B_TILE_MAX overrides)
   bool graphs = false;                 // GA3C_GRAPHS=1: prediction steps replayed as hipGraphs.  Off by default: on ROCm 7.2 a
                                        // 4-kernel graph launch costs ~6 us MORE per step than four plain launches and
                                        // two lanes lose 10 % of their overlap (profiles/README.md, round 1)
@@ -387,7 +372,6 @@ struct ga3c_net {
   LaneDrivers drv;
   float lanes_gpu_ms = 0.f;            // GPU-side span of the last ga3c_net_time_predict_lanes block (first start event .. last end event)
   int lanes_gpu_n = 0;
-  int gather_max_blocks = 32;          // workgroups of the PCIe gather (GA3C_GATHER_BLOCKS; ga3c_kernels.hpp: gather_rows_kernel)
   int lane_streams = 3;                // HIP streams the prediction lanes are spread over (GA3C_LANE_STREAMS)
   std::atomic<uint64_t> resident_gen{1};   // moves whenever the train lane's resident batch is (re)written
   std::atomic<int> stream_busy[16];    // lanes at work per prediction stream: take_lane prefers a lane whose stream is idle
@@ -473,8 +457,8 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
   const int A = net->A;
   const float* th = net->theta[idx];
   const void* xin = f.src_off ? (const void*)f.src_base : (f.x_u8 ? (const void*)f.xu8 : (const void*)f.x);
-  if (f.src_off && !(net->fused_conv && B <= FUSED_CONV_MAX_B)) return fail(GA3C_ESTATE, "scattered intake needs the fused conv stack");
-  if (net->fused_conv && B <= FUSED_CONV_MAX_B) {   // one workgroup per CU: pays off only while a batch is a single wave of workgroups
+  if (f.src_off && B > FUSED_CONV_MAX_B) return fail(GA3C_ESTATE, "scattered intake needs the fused conv stack");
+  if (B <= FUSED_CONV_MAX_B) {   // one workgroup per CU: pays off only while a batch is a single wave of workgroups
     const size_t lds = CS_LDS_FLOATS * sizeof(float);
     SrcOffsets so;
     so.n = 0;
@@ -498,7 +482,7 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
       hipLaunchKernelGGL(conv1_fwd_kernel<true>, dim3(B * 7), dim3(256), 0, st, xin, th + OFF_W1, th + OFF_B1, f.n1, B);
     else
       hipLaunchKernelGGL(conv1_fwd_kernel<false>, dim3(B * 7), dim3(256), 0, st, xin, th + OFF_W1, th + OFF_B1, f.n1, B);
-    if (net->c2f_quarter && B > 128 && B <= 192) hipLaunchKernelGGL(conv2_fwd_kernel<true>, dim3(B * 4), dim3(256), 0, st, f.n1, th + OFF_W2, th + OFF_B2, f.n2, B);
+    if (B <= C2F_QUARTER_MAX_B) hipLaunchKernelGGL(conv2_fwd_kernel<true>, dim3(B * 4), dim3(256), 0, st, f.n1, th + OFF_W2, th + OFF_B2, f.n2, B);
     else hipLaunchKernelGGL(conv2_fwd_kernel<false>, dim3(B * 2), dim3(256), 0, st, f.n1, th + OFF_W2, th + OFF_B2, f.n2, B);
   }
   const int ks = dense_ks(B);
@@ -511,8 +495,8 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
   h.log_softmax = (net->cfg.flags & GA3C_FLAG_LOG_SOFTMAX) ? 1 : 0;
   if (train) { h.y_r = tl->yr; h.act = tl->act; h.dz = tl->dz; h.dv = tl->dv; h.lossrow = tl->lossrow; h.dd1 = tl->dd1; h.beta = beta; }
   // several prediction lanes at work: the fragment kernel (no LDS) runs beside the other lanes' conv stacks
-  const bool frag = !train && !net->graphs && net->d1f_frag_lanes > 0 && B >= 64 &&
-                    net->predict_inflight.load(std::memory_order_relaxed) >= net->d1f_frag_lanes;
+  const bool frag = !train && !net->graphs && B >= D1F_FRAG_MIN_B &&
+                    net->predict_inflight.load(std::memory_order_relaxed) >= D1F_FRAG_LANES;
   CHK(launch_dense1_fwd(net, f.n2, net->theta_pk[idx], f.part, B, ks, st, nullptr, nullptr, frag));
 #define HEADS(T, AM)                                                                                                        \
   do {                                                                                                                      \
@@ -543,11 +527,10 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
 }
 
 // conv1_dw workgroups (= partial slabs) of the split conv backward for a batch of B rows (see launch_backward)
-int conv1_dw_blocks(const ga3c_net* net, int B) {
+int conv1_dw_blocks(int B) {
   const int units = B * 7;
   int n = 512;
-  if (net->c1dw_blocks > 0) n = net->c1dw_blocks;
-  else if (B <= 256) {
+  if (B <= 256) {
     const int one_round = 768 - 4 * B;
     n = 5 * one_round >= units ? one_round : 256;
   }
@@ -572,24 +555,20 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io
   HeadBwdArgs hb;
   hb.B = B; hb.A = A; hb.d1 = t.f.d1; hb.dz = io.dz; hb.dv = io.dv; hb.lossrow = t.lossrow;
   hb.g_wp = g + OFF_WP; hb.g_bp = net->cont ? nullptr : g + off_bp(A); hb.g_wv = g + OFF_WV; hb.g_bv = g + OFF_BV; hb.losses = t.losses;
-  // the continuous head's roles exist in dense1_bwd_tile only: it takes every batch size (GA3C_D1B_TILE_MAX does not apply)
-  const int d1b_tile_max = net->cont ? (1 << 30) : net->d1b_tile_max;
   const int roles = net->npc + 2;
-  // dense1/w stepped inside conv_bwd, beside its MFMA phases, instead of in dense1_bwd_tile's epilogue: worth 0.5 us of the
-  // 128-row step (the step's 24 MB cost conv_bwd 2.2 us where they cost the epilogue 3.5) while every workgroup of conv_bwd
-  // steps ONE 16-row group; below 121 rows the groups left over are a tail and it loses 0.2 us (profiles/README.md)
-  const bool fused_cb = net->conv_bwd_fused && B <= 128 && B >= net->conv_bwd_min;
-  upd.defer_wd = upd.on && fused_cb && B <= d1b_tile_max &&
-                 (net->wd_step_in_conv_bwd >= 2 || (net->wd_step_in_conv_bwd == 1 && 2 * B >= KSTEPS_DENSE));
-  // beyond the fused conv_bwd the step rides in conv2_dx (conv2_dx_wd_kernel)
-  if (upd.on && !fused_cb && B <= d1b_tile_max && net->wd_step_in_conv2_dx) upd.defer_wd = 1;
-  if (B <= d1b_tile_max) {
+  const bool fused_cb = B >= CONV_BWD_MIN_B && B <= CONV_BWD_MAX_B;
+  // Under the fused update dense1/w is stepped by a later kernel, beside its MFMA work, instead of in dense1_bwd_tile's
+  // epilogue: inside conv_bwd while every workgroup of conv_bwd steps ONE 16-row group (2 B >= 242: worth 0.5 us of the
+  // 128-row step, whose 24 MB cost conv_bwd 2.2 us where they cost the epilogue 3.5; below 121 rows the groups left over are
+  // a tail and it loses 0.2 us, profiles/README.md), and on the split path in conv2_dx's launch (conv2_dx_wd_kernel)
+  upd.defer_wd = upd.on && (!fused_cb || 2 * B >= KSTEPS_DENSE);
+  {
     Dense1TileArgs d;
     d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
     d.hb = hb;
     d.upd = upd;
     d.role_blocks = roles < 14 ? roles : 14;       // 242 tiles + the roles stay within one round of workgroups on 256 CUs
-    d.tail_lds = net->d1b_tail && B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
+    d.tail_lds = B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
     const size_t d1b_lds = (d.tail_lds ? D1B_LDS_FLOATS_TAIL : D1B_LDS_FLOATS) * sizeof(float);
     const int u = upd.on ? (upd.defer_wd ? 2 : 1) : 0;
 #define D1B(U, T, C) hipLaunchKernelGGL((dense1_bwd_tile_kernel<U, T, C>), dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d)
@@ -599,22 +578,15 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io
     else D1B_U(false, false);
 #undef D1B_U
 #undef D1B
-  } else {
-    Dense1BwdArgs d;
-    d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
-    d.hb = hb; d.dw_gx = FLAT / 32 + A + 2; d.dw_blocks = 2 * d.dw_gx; d.dx_gx = FLAT / 32;
-    d.dx_mt = dense_dx_mt(B);
-    const int dx_blocks = d.dx_gx * (((B + 16 * d.dx_mt - 1) / (16 * d.dx_mt) + 3) / 4);
-    hipLaunchKernelGGL(dense1_bwd_kernel, dim3(d.dw_blocks + dx_blocks), dim3(256), 0, st, d);
   }
   if (overlap) {
     HIPCHK(hipEventRecord(net->ev_tail_ready, st));
     HIPCHK(hipStreamWaitEvent(net->cst, net->ev_tail_ready, 0));
     NCCLCHK(ncclAllReduce(g + OFF_WD, g + OFF_WD, (size_t)(net->n - OFF_WD), ncclFloat, ncclSum, net->comm, net->cst));
-    if (net->head_on_train_stream) HIPCHK(hipEventRecord(net->ev_comm_done, net->cst));   // (waited for below, behind the head's exchange)
+    HIPCHK(hipEventRecord(net->ev_comm_done, net->cst));   // (waited for below, behind the head's exchange)
   }
   int nch1, nch2;
-  if (fused_cb) {   // one workgroup per CU: beyond one round the tail of the second costs more than the fusion saves
+  if (fused_cb) {
     // conv2_dw + conv2_dx + conv1_dw of a sample half in ONE workgroup (conv_bwd_kernel): dn1 never leaves the chip between them
     const int grid = 2 * B;                         // (sample, half); one slab pair per workgroup
     const size_t lds = CB_LDS_FLOATS * sizeof(float);
@@ -638,16 +610,13 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io
     // for it: with dword loads it LOST 1.6 us at 240); 200 workgroups: 67.2.  Past ~142 rows that count would mean more than five
     // units per workgroup: 256 (150 / 160 rows: 74.9 / 75.9 us against 77.0 / 77.9 at 512).  A function of B alone, so that
     // every form of the step (paired or not, uint8 or f32) cuts the slabs alike and gives the same bits.
-    nch1 = conv1_dw_blocks(net, B);
-    const bool pair = net->dw_pair && B <= 256;    // conv2_dw + conv1_dw side by side in one launch, behind conv2_dx
+    nch1 = conv1_dw_blocks(B);
+    const bool pair = B <= DW_PAIR_MAX_B;
     // conv2's two gradients are separate launches: their LDS/VGPR budgets differ too much to share one grid
-    if (!pair) {
-      if (net->c2dw_occ >= 3 && B <= 256) hipLaunchKernelGGL(conv2_dw_kernel<3>, dim3(nch2, 4), dim3(256), 0, st, t.f.n1, t.dn2, t.slab2, B);
-      else hipLaunchKernelGGL(conv2_dw_kernel<2>, dim3(nch2, 4), dim3(256), 0, st, t.f.n1, t.dn2, t.slab2, B);
-    }
+    if (!pair) hipLaunchKernelGGL(conv2_dw_kernel<2>, dim3(nch2, 4), dim3(256), 0, st, t.f.n1, t.dn2, t.slab2, B);
     if (upd.on && upd.defer_wd)
       hipLaunchKernelGGL(conv2_dx_wd_kernel, dim3(B + C2DX_WD_BLOCKS, 2), dim3(512), 0, st, t.dn2, net->theta_pk[idx] + PK_W2DX, t.f.n1, t.dn1, B,
-                         (const float*)(g + OFF_WD), upd, net->wd_blocks_first);
+                         (const float*)(g + OFF_WD), upd);
     else
       hipLaunchKernelGGL(conv2_dx_kernel, dim3(B, 2), dim3(512), 0, st, t.dn2, net->theta_pk[idx] + PK_W2DX, t.f.n1, t.dn1, B);
     if (pair) {
@@ -669,19 +638,13 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io
     else hipLaunchKernelGGL(slab_reduce_kernel<false>, dim3(s1.nblocks + s2.nblocks), dim3(1024), 0, st, s1, s2, upd);
   }
   HIPCHK(hipGetLastError());
-  if (overlap && net->head_on_train_stream) {
+  if (overlap) {
     // The conv gradients (12 k floats) are complete only now, with nothing left to overlap their exchange with: it goes on the
     // TRAIN stream itself, in line, instead of a hop to the comm stream and back (two cross-queue dependencies, ~7 us each on
     // the GPU, and two more API calls on a host that is the bottleneck of this path: profiles/r04_dp_1rank_timeline.txt).
     // RCCL runs the collectives of one communicator in the order they were issued -- identical on every rank --, so this one
     // starts behind the big one on the comm stream; the optimizer step then waits for both.
     NCCLCHK(ncclAllReduce(g, g, (size_t)OFF_WD, ncclFloat, ncclSum, net->comm, st));
-    HIPCHK(hipStreamWaitEvent(st, net->ev_comm_done, 0));
-  } else if (overlap) {
-    HIPCHK(hipEventRecord(net->ev_head_ready, st));
-    HIPCHK(hipStreamWaitEvent(net->cst, net->ev_head_ready, 0));
-    NCCLCHK(ncclAllReduce(g, g, (size_t)OFF_WD, ncclFloat, ncclSum, net->comm, net->cst));
-    HIPCHK(hipEventRecord(net->ev_comm_done, net->cst));
     HIPCHK(hipStreamWaitEvent(st, net->ev_comm_done, 0));
   }
   return GA3C_OK;
@@ -756,7 +719,7 @@ int launch_step(ga3c_net* net, Lane& L, int idx, int B, int mode, float* out_p, 
     const bool u8 = mode != STEP_GATHER_F32;
     const uint8_t* base = mode == STEP_QUEUES ? reinterpret_cast<const uint8_t*>(net->fr.stacks) : net->reg_dev;
     L.f.x_u8 = u8;
-    if (net->fused_conv && B <= FUSED_CONV_MAX_B) {
+    if (B <= FUSED_CONV_MAX_B) {
       // small batches (every engine batch): the conv stack reads the scattered states itself -- one launch less
       L.f.src_base = base;
       L.f.src_off = L.h_off;
@@ -766,8 +729,8 @@ int launch_step(ga3c_net* net, Lane& L, int idx, int B, int mode, float* out_p, 
       const SmallCopy none{nullptr, nullptr, 0, nullptr, nullptr, 0};
       RowOffsets ro;
       ro.n = 0;                                              // (beyond the fused conv stack's range: batches of more than 128 rows)
-      if (u8) hipLaunchKernelGGL(gather_rows_kernel<XS / 16>, dim3(gather_blocks(B, XS / 16, net->gather_max_blocks)), dim3(256), 0, L.st, base, L.h_off, reinterpret_cast<uint4*>(L.f.xu8), B, none, ro);
-      else hipLaunchKernelGGL(gather_rows_kernel<XS / 4>, dim3(gather_blocks(B, XS / 4, net->gather_max_blocks)), dim3(256), 0, L.st, base, L.h_off, reinterpret_cast<uint4*>(L.f.x), B, none, ro);
+      if (u8) hipLaunchKernelGGL(gather_rows_kernel<XS / 16>, dim3(gather_blocks(B, XS / 16)), dim3(256), 0, L.st, base, L.h_off, reinterpret_cast<uint4*>(L.f.xu8), B, none, ro);
+      else hipLaunchKernelGGL(gather_rows_kernel<XS / 4>, dim3(gather_blocks(B, XS / 4)), dim3(256), 0, L.st, base, L.h_off, reinterpret_cast<uint4*>(L.f.x), B, none, ro);
       if (L.cache_on && mode == STEP_GATHER_U8)               // ... and the state cache takes its copy from the gathered batch
         hipLaunchKernelGGL(file_rows_kernel<XS / 16>, dim3((XS / 16 + 255) / 256, B), dim3(256), 0, L.st, reinterpret_cast<const uint4*>(L.f.xu8),
                            net->cache_ring, L.cache_dst, B);
@@ -790,10 +753,7 @@ void drop_graphs(Lane& L) {
 // mark_done: L.done is recorded behind the step (the callers that will wait for it, or let a train step wait for it)
 int lane_step(ga3c_net* net, Lane& L, int idx, int B, int mode, float* out_p, float* out_v, bool mark_done = false) {
   if (!net->graphs) {
-    if (mark_done && net->stop_events) return launch_step(net, L, idx, B, mode, out_p, out_v, L.done);
-    CHK(launch_step(net, L, idx, B, mode, out_p, out_v));
-    if (mark_done) HIPCHK(hipEventRecord(L.done, L.st));
-    return GA3C_OK;
+    return launch_step(net, L, idx, B, mode, out_p, out_v, mark_done ? L.done : nullptr);
   }
   const bool u8 = mode == STEP_RESIDENT ? L.f.x_u8 : mode != STEP_GATHER_F32;
   const int64_t key = ((int64_t)B << 8) | (idx << 5) | (mode << 2) | (u8 ? 2 : 0) | (out_p ? 1 : 0);
@@ -934,8 +894,7 @@ int train_grads(ga3c_net* net, TrainLane& t, int B, float beta, bool will_apply 
     CHK(launch_backward(net, t, idx, B, BwdIo{t.dd1_v, t.zeros, t.dv, t.grad + net->n}, false, nullptr, !will_apply));
     return GA3C_OK;
   }
-  const bool fuse = will_apply && net->fused_update && !net->comm && !(net->cfg.flags & GA3C_FLAG_GRAD_CLIP) &&
-                    (B <= net->d1b_tile_max || net->cont);
+  const bool fuse = will_apply && !net->comm && !(net->cfg.flags & GA3C_FLAG_GRAD_CLIP);
   int idx, other;
   if (fuse && !net->hogwild) {
     CHK(claim_other_buffer(net, t, &idx, &other));
@@ -1104,9 +1063,9 @@ int launch_gather(ga3c_net* net, const int64_t* offsets, int B, bool u8, Stage& 
     ro.n = B;
   }
   if (u8) {
-    hipLaunchKernelGGL(gather_rows_kernel<XS / 16>, dim3(gather_blocks(B, XS / 16, net->gather_max_blocks)), dim3(256), 0, s.st, net->reg_dev, s.h_off, reinterpret_cast<uint4*>(s.xu8), B, sc, ro);
+    hipLaunchKernelGGL(gather_rows_kernel<XS / 16>, dim3(gather_blocks(B, XS / 16)), dim3(256), 0, s.st, net->reg_dev, s.h_off, reinterpret_cast<uint4*>(s.xu8), B, sc, ro);
   } else {
-    hipLaunchKernelGGL(gather_rows_kernel<XS / 4>, dim3(gather_blocks(B, XS / 4, net->gather_max_blocks)), dim3(256), 0, s.st, net->reg_dev, s.h_off, reinterpret_cast<uint4*>(s.x), B, sc, ro);
+    hipLaunchKernelGGL(gather_rows_kernel<XS / 4>, dim3(gather_blocks(B, XS / 4)), dim3(256), 0, s.st, net->reg_dev, s.h_off, reinterpret_cast<uint4*>(s.x), B, sc, ro);
   }
   s.x_u8 = u8;
   HIPCHK(hipGetLastError());
@@ -1622,27 +1581,10 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
   net->cfg = *cfg;
   for (auto& c : net->stat) c.store(0);
   for (auto& c : net->stream_busy) c.store(0);
-  net->fused_conv = getenv("GA3C_SPLIT_CONV") == nullptr;
   net->graphs = getenv("GA3C_GRAPHS") != nullptr;
-  if (const char* e = getenv("GA3C_D1B_TILE_MAX")) net->d1b_tile_max = atoi(e);
-  if (const char* e = getenv("GA3C_D1B_TAIL")) net->d1b_tail = atoi(e) != 0;
   if (const char* e = getenv("GA3C_D1F_TILE")) net->d1f_tile = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_D1F_FRAG_LANES")) net->d1f_frag_lanes = atoi(e);
-  if (const char* e = getenv("GA3C_CONV_BWD")) net->conv_bwd_fused = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_CONV_BWD_MIN")) net->conv_bwd_min = atoi(e);
-  if (const char* e = getenv("GA3C_C2F_QUARTER")) net->c2f_quarter = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_C2DW_OCC")) net->c2dw_occ = atoi(e);
-  if (const char* e = getenv("GA3C_WD_STEP_IN_CONV_BWD")) net->wd_step_in_conv_bwd = atoi(e);
-  if (const char* e = getenv("GA3C_WD_STEP_IN_CONV2_DX")) net->wd_step_in_conv2_dx = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_WD_BLOCKS_FIRST")) net->wd_blocks_first = atoi(e);
-  if (const char* e = getenv("GA3C_DW_PAIR")) net->dw_pair = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_C1DW_BLOCKS")) net->c1dw_blocks = atoi(e) >= 1 && atoi(e) <= 512 ? atoi(e) : 0;
   if (const char* e = getenv("GA3C_TIME_PREDICTIONS")) net->time_predictions = atoi(e) != 0;
   if (const char* e = getenv("GA3C_OFFSETS_IN_ARGS")) net->offsets_in_args = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_STOP_EVENTS")) net->stop_events = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_FRAMES_IN_LINE")) net->frames_in_line = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_FUSED_UPDATE")) net->fused_update = atoi(e) != 0;
-  if (const char* e = getenv("GA3C_GATHER_BLOCKS")) net->gather_max_blocks = atoi(e) > 0 ? atoi(e) : 32;
   for (const void* fn : {reinterpret_cast<const void*>(&conv_bwd_kernel<true, false>), reinterpret_cast<const void*>(&conv_bwd_kernel<false, false>),
                          reinterpret_cast<const void*>(&conv_bwd_kernel<true, true>), reinterpret_cast<const void*>(&conv_bwd_kernel<false, true>)}) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CB_LDS_FLOATS * sizeof(float)));
@@ -1669,7 +1611,7 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
       return fail(GA3C_EHIP, "cannot reserve LDS for dense1_bwd_tile_kernel: %s", hipGetErrorString(e));
     }
   }
-  if (net->fused_conv) {
+  {
     const int lds = (int)(CS_LDS_FLOATS * sizeof(float));
     const void* fns[4] = {reinterpret_cast<const void*>(&conv_stack_fwd_kernel<true, true>),
                           reinterpret_cast<const void*>(&conv_stack_fwd_kernel<true, false>),
@@ -1802,7 +1744,7 @@ int ga3c_net_destroy(ga3c_net* net) {
   if (net->cache_ring) (void)hipFree(net->cache_ring);
   if (net->comm) (void)ncclCommDestroy(net->comm);
   if (net->cst) stream_give_back(net->cst);
-  for (hipEvent_t e : {net->ev_tail_ready, net->ev_head_ready, net->ev_comm_done})
+  for (hipEvent_t e : {net->ev_tail_ready, net->ev_comm_done})
     if (e) (void)hipEventDestroy(e);
   for (Lane* L : net->lanes) {
     drop_graphs(*L);
@@ -2671,7 +2613,7 @@ int ga3c_net_train_frames(ga3c_net* net, const int32_t* agents, const int64_t* s
   if (!net->fr.on || !net->fr.hist) return fail(GA3C_ESTATE, "frames: no plane history configured (ga3c_net_frames_config, history > 0)");
   return with_staged_batch(net, batch, [&](Stage& s) { return stage_history_rows(net, s, agents, seqs, y_r, a, batch); },
                            [&](TrainLane& t, Intake& in) { return train_enqueue(net, t, in, batch, learning_rate, beta); },
-                           [&](TrainLane&, Intake& in) { return train_finish(net, in, losses); }, net->frames_in_line);
+                           [&](TrainLane&, Intake& in) { return train_finish(net, in, losses); }, true);
 }
 
 int ga3c_net_evaluate_frames(ga3c_net* net, const int32_t* agents, const int64_t* seqs, const float* y_r, const float* a,
@@ -3043,7 +2985,7 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
     } else if (k == "conv1_fwd_u8") {
       TL(conv1_fwd_kernel<true>, dim3(B * 7), (const void*)t.f.xu8, th + OFF_W1, th + OFF_B1, t.f.n1, B);
     } else if (k == "conv1_dw_u8") {
-      TL(conv1_dw_kernel<true>, dim3(conv1_dw_blocks(net, B)), (const void*)t.f.xu8, t.dn1, t.slab1, B * 7);
+      TL(conv1_dw_kernel<true>, dim3(conv1_dw_blocks(B)), (const void*)t.f.xu8, t.dn1, t.slab1, B * 7);
     } else if (k == "conv2_fwd") {
       TL(conv2_fwd_kernel<false>, dim3(B * 2), t.f.n1, th + OFF_W2, th + OFF_B2, t.f.n2, B);
     } else if (k == "conv2_fwd_q") {
@@ -3061,20 +3003,14 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
                             t.ev0, t.ev1, 0, (const void*)t.f.xu8, net->theta_pk[net->latest] + PK_W1F, th + OFF_B1, net->theta_pk[net->latest] + PK_W2F, th + OFF_B2, t.f.n1, t.f.n2, B,
                             (const int64_t*)nullptr, SrcOffsets{}, (uint8_t*)nullptr);
     } else if (k == "dense1_fwd" || k == "dense1_fwd_frag") {
-      const bool keep = net->d1f_tile;
-      if (k == "dense1_fwd_frag") net->d1f_tile = false;
-      const int rc = launch_dense1_fwd(net, t.f.n2, net->theta_pk[net->latest], t.f.part, B, dense_ks(B), t.st, t.ev0, t.ev1);
-      net->d1f_tile = keep;
-      CHK(rc);
+      CHK(launch_dense1_fwd(net, t.f.n2, net->theta_pk[net->latest], t.f.part, B, dense_ks(B), t.st, t.ev0, t.ev1, k == "dense1_fwd_frag"));
     } else if (k == "conv1_dw") {
-      TL(conv1_dw_kernel<false>, dim3(conv1_dw_blocks(net, B)), (const void*)t.f.x, t.dn1, t.slab1, B * 7);
+      TL(conv1_dw_kernel<false>, dim3(conv1_dw_blocks(B)), (const void*)t.f.x, t.dn1, t.slab1, B * 7);
     } else if (k == "conv2_dw") {
       TL(conv2_dw_kernel<2>, dim3(B < 256 ? B : 256, 4), t.f.n1, t.dn2, t.slab2, B);
     } else if (k == "conv_dw_pair") {
-      const int nch1 = conv1_dw_blocks(net, B), nch2 = B < 256 ? B : 256;
+      const int nch1 = conv1_dw_blocks(B), nch2 = B < 256 ? B : 256;
       TL(conv_dw_pair_kernel<false>, dim3(nch1 + 4 * nch2), (const void*)t.f.x, t.dn1, t.slab1, B * 7, nch1, t.f.n1, t.dn2, t.slab2, B, nch2);
-    } else if (k == "conv2_dw_occ3") {
-      TL(conv2_dw_kernel<3>, dim3(B < 256 ? B : 256, 4), t.f.n1, t.dn2, t.slab2, B);
     } else if (k == "conv2_dx") {
       hipExtLaunchKernelGGL(conv2_dx_kernel, dim3(B, 2), dim3(512), 0, t.st, t.ev0, t.ev1, 0, t.dn2, net->theta_pk[net->latest] + PK_W2DX, t.f.n1, t.dn1, B);
     } else if (k == "dense1_dw") {
@@ -3093,12 +3029,12 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
       d.dx_mt = dense_dx_mt(B);
       TL(dense1_bwd_kernel, dim3(d.dw_blocks + d.dx_gx * (((B + 16 * d.dx_mt - 1) / (16 * d.dx_mt) + 3) / 4)), d);
     } else if (k == "conv_bwd") {
-      if (B > 128) return fail(GA3C_EINVAL, "conv_bwd runs up to 128 rows");
+      if (B > CONV_BWD_MAX_B) return fail(GA3C_EINVAL, "conv_bwd runs up to %d rows", CONV_BWD_MAX_B);
       hipExtLaunchKernelGGL(conv_bwd_kernel<false>, dim3(2 * B), dim3(1024), CB_LDS_FLOATS * sizeof(float), t.st,
                             t.ev0, t.ev1, 0, (const void*)t.f.x, t.f.n1, t.dn2, net->theta_pk[net->latest] + PK_W2DX, t.dn1, t.slab2,
                             t.slab1, B, (const float*)nullptr, FusedUpd{});
     } else if (k == "conv_bwd_wdstep") {
-      if (B > 128) return fail(GA3C_EINVAL, "conv_bwd runs up to 128 rows");
+      if (B > CONV_BWD_MAX_B) return fail(GA3C_EINVAL, "conv_bwd runs up to %d rows", CONV_BWD_MAX_B);
       FusedUpd fu{};
       const int l = net->latest;
       fu.tin = net->theta[l]; fu.tout = net->theta[l]; fu.ms = net->ms; fu.mom = net->mom; fu.pk = net->theta_pk[l];
@@ -3106,14 +3042,14 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
       hipExtLaunchKernelGGL((conv_bwd_kernel<false, true>), dim3(2 * B), dim3(1024), CB_LDS_FLOATS * sizeof(float), t.st,
                             t.ev0, t.ev1, 0, (const void*)t.f.x, t.f.n1, t.dn2, net->theta_pk[l] + PK_W2DX, t.dn1, t.slab2,
                             t.slab1, B, (const float*)(g + OFF_WD), fu);
-    } else if (k == "dense1_bwd_tile" || k == "dense1_bwd_tile_notail") {
+    } else if (k == "dense1_bwd_tile") {
       Dense1TileArgs d;
       d.n2 = t.f.n2; d.dd1 = t.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
       d.hb.B = B; d.hb.A = net->A; d.hb.d1 = t.f.d1; d.hb.dz = t.dz; d.hb.dv = t.dv; d.hb.lossrow = t.lossrow;
       d.hb.g_wp = g + OFF_WP; d.hb.g_bp = g + off_bp(net->A); d.hb.g_wv = g + OFF_WV; d.hb.g_bv = g + OFF_BV; d.hb.losses = t.losses;
       d.role_blocks = net->A + 2 < 14 ? net->A + 2 : 14;
       memset(&d.upd, 0, sizeof d.upd);
-      d.tail_lds = k == "dense1_bwd_tile" && net->d1b_tail && B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
+      d.tail_lds = B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
       if (d.tail_lds)
         hipExtLaunchKernelGGL((dense1_bwd_tile_kernel<0, true>), dim3(D1B_TILES + d.role_blocks), dim3(1024), D1B_LDS_FLOATS_TAIL * sizeof(float),
                               t.st, t.ev0, t.ev1, 0, d);
@@ -3134,7 +3070,7 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
       else HEADS_T(64);
 #undef HEADS_T
     } else if (k == "slab_reduce") {
-      const int nch1 = conv1_dw_blocks(net, B), nch2 = B < 256 ? B : 256;
+      const int nch1 = conv1_dw_blocks(B), nch2 = B < 256 ? B : 256;
       SlabSet s1{t.slab1, nch1, SLAB1, 256 * 16, g + OFF_W1, g + OFF_B1, (SLAB1 + 63) / 64, OFF_W1, OFF_B1};
       SlabSet s2{t.slab2, nch2, SLAB2, 256 * 32, g + OFF_W2, g + OFF_B2, (SLAB2 + 63) / 64, OFF_W2, OFF_B2};
       FusedUpd noupd;
@@ -3231,9 +3167,8 @@ int ga3c_net_comm_init(ga3c_net* net, const uint8_t id[GA3C_COMM_ID_BYTES], int3
   net->world = world;
   net->rank = rank;
   net->comm_overlap = !(getenv("GA3C_COMM_OVERLAP") && atoi(getenv("GA3C_COMM_OVERLAP")) == 0);
-  net->head_on_train_stream = !(getenv("GA3C_COMM_HEAD_INLINE") && atoi(getenv("GA3C_COMM_HEAD_INLINE")) == 0);
   HIPCHK(stream_take(net->cfg.device, false, &net->cst));
-  for (hipEvent_t* e : {&net->ev_tail_ready, &net->ev_head_ready, &net->ev_comm_done})
+  for (hipEvent_t* e : {&net->ev_tail_ready, &net->ev_comm_done})
     HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
   return GA3C_OK;
 }

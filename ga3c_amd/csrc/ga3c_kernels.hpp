@@ -77,7 +77,7 @@ struct FusedUpd {
   const float* tin; float* tout; float* ms; float* mom; float* pk;   // pk: packed copies (dense1/w, conv12/w) of tout
   float lr, omr, mu, eps; int on;
   int defer_wd;   // dense1/w is NOT stepped by the kernel that completes its gradient (dense1_bwd_tile) but by a later one
-                  // (conv_bwd; conv2_dx_wd beyond 128 rows), beside that kernel's MFMA work: see wd_step_load / wd_step_apply
+                  // (conv_bwd; conv2_dx_wd on the split path), beside that kernel's MFMA work: see wd_step_load / wd_step_apply
 };
 __device__ __forceinline__ float fused_rmsprop(const FusedUpd& u, int64_t i, float g) {
   float m = u.ms[i];
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restric
 //
 // Work item = (row, piece of 256 chunks): the row's offset is uniform over the workgroup (one scalar load out of the
 // pinned offset array instead of a PCIe round trip per thread in front of every data load), four items are in flight per
-// thread, and the grid is NARROW (ga3c_net::gather_max_blocks workgroups of 4 waves).  The kernel waits on the bus, not on the chip:
+// thread, and the grid is NARROW (GATHER_MAX_BLOCKS workgroups of 4 waves).  The kernel waits on the bus, not on the chip:
 // launched as one chunk per thread it was 909 workgroups at 132 rows -- every wave slot of every CU held by waves waiting
 // for PCIe -- and the train step of the OTHER trainer thread, whose kernels are one 16-wave workgroup per CU, could not get
 // resident beside it: the staging of batch n+1 and step n ran one after the other although they sit on two streams.
@@ -145,10 +145,11 @@ __global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restric
 // profiles/README.md) wait behind them; 32 workgroups x 4 x 4 KB in flight still saturate the bus (72 us for 3.6 MB),
 // 16 do not.  Two trainer threads, 128 rows, us per train call at 8 / 16 / 32 / 64 / 128 / 256 workgroups:
 // 200 / 129 / 116 / 123 / 134 / 143.
-inline int gather_blocks(int B, int chunks, int max_blocks) {
+constexpr int GATHER_MAX_BLOCKS = 32;
+inline int gather_blocks(int B, int chunks) {
   const int items = B * ((chunks + 255) / 256);
   const int blocks = (items + 3) / 4;
-  return blocks < max_blocks ? (blocks < 1 ? 1 : blocks) : max_blocks;
+  return blocks < GATHER_MAX_BLOCKS ? (blocks < 1 ? 1 : blocks) : GATHER_MAX_BLOCKS;
 }
 
 // small arrays that ride along with a gather (a batch's returns and one-hot actions, out of the pinned staging array):
@@ -1921,9 +1922,9 @@ __global__ __launch_bounds__(1024) void dense1_bwd_tile_kernel(Dense1TileArgs a)
   }
 }
 
-// ---- launchable forms.  The two gradients of a layer (weights / inputs) only share inputs, so they are also
-// offered as ONE launch whose block range is split between the two bodies: they then run side by side and
-// fill the chip, which neither does alone at small batch (cross-stream events cost more than they save here).
+// ---- launchable forms of the round-1 dense1 backward.  Timing only (ga3c_net_time_kernel: "dense1_dw", "dense1_dx",
+// "dense1_bwd"): every train step runs dense1_bwd_tile_kernel.  dense1_bwd_kernel is the two bodies (weights / inputs) in
+// ONE launch whose block range is split between them.
 __global__ __launch_bounds__(256) void dense1_dw_kernel(const float* __restrict__ flat, const float* __restrict__ dd1,
                                                         float* __restrict__ g_wd, float* __restrict__ g_bd, int B,
                                                         HeadBwdArgs hb) {
@@ -1947,11 +1948,11 @@ __global__ __launch_bounds__(256) void dense1_bwd_kernel(Dense1BwdArgs a) {
     else dense1_dx_body<1>(a.dd1, a.wd, a.n2, a.dn2, a.B, j % a.dx_gx, j / a.dx_gx, a.dx_gx);
   }
 }
-// OCC = workgroups per CU the register budget is cut for.  2: 205 VGPRs, the next sample's loads in flight during the MFMAs:
-// the form for batches whose workgroups walk several samples (B > 256).  3: 149 VGPRs, no loads held across the MFMAs
-// (conv2_dw_body<false>): three workgroups' LDS (3 x 53,248 B) fit a CU, so the 4 B workgroups of a batch are one round up to 192
-// rows instead of 128 -- 132 rows: 9.0 -> 7.5 us -- and it is no slower anywhere up to 256 rows (one sample per workgroup).
-// Same arithmetic, same bits.
+// conv2_dw on its own: the split path beyond 256 rows, whose workgroups walk several samples.  OCC = 2 workgroups per CU
+// (205 VGPRs), the next sample's loads in flight during the MFMAs.  Up to 256 rows conv_dw_pair_kernel runs the same
+// arithmetic as conv2_dw_body<false> (149 VGPRs, no loads held across the MFMAs, three workgroups per CU).
+// Still a template although only <2> is launched: as a plain kernel it is emitted ahead of the train step's kernels and
+// shifts them in the code object, and the 128-row f32 train step measured 0.5 us slower (57.3 against 56.8 us).
 template <int OCC>
 __global__ __launch_bounds__(256, OCC) void conv2_dw_kernel(const float* __restrict__ n1, const float* __restrict__ dn2,
                                                             float* __restrict__ part, int B) {
@@ -2218,18 +2219,17 @@ __device__ __forceinline__ void wd_step_apply(const FusedUpd& u, int s, const Wd
   store_through4(u.pk + ((size_t)s * HID + n) * 16 + 4 * q, tn);
 }
 
-// The same step riding in conv2_dx, for batches beyond the fused conv_bwd's 128 rows (the split path: conv2_dw, conv2_dx,
-// conv1_dw).  There dense1_bwd_tile<1> carried it in its epilogue: 14.8 us in a 132-row step against 10.4 without.  conv2_dx
-// is 264 .. 512 workgroups of which a CU can hold three, bound by its MFMA chains, with 12 MB of traffic in 8.5 us: the 242
-// row groups go to 121 x 2 workgroups of their own at the FRONT of the grid (dispatched first: their loads and stores are
-// under way while the gradient workgroups stage and compute), two passes of two row quads each.
+// The same step riding in conv2_dx, on the split path (conv2_dx, then conv2_dw + conv1_dw: below 97 and beyond 128 rows).
+// There dense1_bwd_tile<1> carried it in its epilogue: 14.8 us in a 132-row step against 10.4 without.  conv2_dx is
+// 2 B workgroups of which a CU can hold three, bound by its MFMA chains, with 12 MB of traffic in 8.5 us at 132 rows: the
+// 242 row groups go to 121 x 2 workgroups of their own at the BACK of the grid (block columns B .. B + 120), two passes of
+// two row quads each.
 constexpr int C2DX_WD_BLOCKS = KSTEPS_DENSE / 2;
 static_assert(KSTEPS_DENSE % 2 == 0, "conv2_dx_wd_kernel deals the row groups of dense1/w to pairs of workgroups");
 __global__ __launch_bounds__(512) void conv2_dx_wd_kernel(const float* __restrict__ dn2, const float* __restrict__ w,
                                                           const float* __restrict__ n1, float* __restrict__ dn1, int B,
-                                                          const float* __restrict__ g_wd, FusedUpd u, int wd_first) {
-  const int bxw = wd_first ? (int)blockIdx.x : (int)blockIdx.x - B;        // index among the step's block columns
-  const int bxc = wd_first ? (int)blockIdx.x - C2DX_WD_BLOCKS : (int)blockIdx.x;
+                                                          const float* __restrict__ g_wd, FusedUpd u) {
+  const int bxw = (int)blockIdx.x - B;                         // index among the step's block columns
   if (bxw >= 0 && bxw < C2DX_WD_BLOCKS) {                      // block-uniform
     const int s = 2 * bxw + blockIdx.y;
     WdStep w0, w1;
@@ -2239,7 +2239,7 @@ __global__ __launch_bounds__(512) void conv2_dx_wd_kernel(const float* __restric
     wd_step_apply(u, s, w1, 2);
     return;
   }
-  conv2_dx_body(dn2, w, n1, dn1, B, bxc, blockIdx.y, gridDim.x - C2DX_WD_BLOCKS);
+  conv2_dx_body(dn2, w, n1, dn1, B, blockIdx.x, blockIdx.y, gridDim.x - C2DX_WD_BLOCKS);
 }
 
 // WD: the launch also applies the optimizer step u to dense1/w, whose gradient g_wd is complete since the previous launch

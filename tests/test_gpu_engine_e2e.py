@@ -108,12 +108,11 @@ def test_gather_from_registered_transport_is_bit_identical_to_host_path():
         t.close()
 
 
-@pytest.mark.parametrize("switch", ["GA3C_OFFSETS_IN_ARGS", "GA3C_STOP_EVENTS"])
+@pytest.mark.parametrize("switch", ["GA3C_OFFSETS_IN_ARGS"])
 def test_alternate_launch_paths_of_a_gathered_step_give_the_same_bits(monkeypatch, switch):
-    """The offsets of a scattered batch travel in the kernel arguments (GA3C_OFFSETS_IN_ARGS=0: read from pinned memory) and
-    a step's completion event is the stop event of its last launch (GA3C_STOP_EVENTS=0: a record of its own): the
-    fallbacks stay in the library (hipGraph replays use the first), so they are held to the default path bit for bit --
-    predictions on transport rows from two threads, and a train call on rollout rows."""
+    """The offsets of a scattered batch travel in the kernel arguments (GA3C_OFFSETS_IN_ARGS=0: read from pinned memory):
+    the fallback stays in the library (hipGraph replays and train gathers of more than 192 rows use it), so it is held to
+    the default path bit for bit -- predictions on transport rows from two threads, and a train call on rollout rows."""
     import threading
     import ga3c_amd  # noqa: F401
     import Transport as tp

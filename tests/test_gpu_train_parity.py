@@ -106,7 +106,7 @@ def test_production_train_step_matches_oracle(nets, num_actions, bsz, fmt):
         off += size
 
 
-@pytest.mark.parametrize("bsz", [128, 132, 134])
+@pytest.mark.parametrize("bsz", [40, 100, 121, 128, 132, 134, 140])
 def test_u8_and_f32_production_steps_give_the_same_bits(nets, bsz):
     net = nets(6)
     xk, x, a, y = _batch(bsz, 6, 4242 + bsz)
@@ -119,104 +119,45 @@ def test_u8_and_f32_production_steps_give_the_same_bits(nets, bsz):
     assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
 
 
-def test_dense1_weight_step_inside_conv_bwd_gives_the_bits_of_the_epilogue_step(nets, monkeypatch):
-    """The fused update steps dense1/w inside conv_bwd (beside its MFMA phases) instead of in dense1_bwd_tile's epilogue
-    (GA3C_WD_STEP_IN_CONV_BWD=0 keeps the epilogue, 2 defers at every batch size, the default from 121 rows on).  Same arithmetic per element: weights, ms and -- through the
-    fragment-ordered copy of dense1/w that predictions read -- the predictions after the steps must be bit-identical, at a
-    full grid (128 rows: one 16-row group per workgroup), at grids below the 242 groups (8, 40, 120 rows: the leftover
-    loop) and with momentum."""
+def test_fused_update_with_momentum_at_the_seams_matches_oracle(monkeypatch):
+    """Three production steps with RMSProp momentum (inputs f32, uint8, f32) at every seam of the train step's launch rules:
+    the split conv backward below 97 rows with dense1/w stepped in conv2_dx's launch (8, 40, 64, 96), the fused conv_bwd
+    with the step in dense1_bwd_tile's epilogue (97, 100, 120) and inside conv_bwd (121, 128), and the split path again
+    beyond 128 rows: dense1_bwd_tile's tail area (129, 133), a second chunk (134, 140), conv2_fwd in units of four tiles.
+    Weights and `mom` to 2e-5 (test_gpu_parity.py: test_config_branches_match_oracle), `ms` to 1e-5 of its largest entry.
+    Then the predictions must equal bit for bit those of a second network handed the stepped weights through set_arena:
+    the fragment-ordered copy of dense1/w that predictions read is written by whichever kernel takes the deferred step."""
     import ga3c_amd  # noqa: F401
     import Config
     from NetworkVP import Network
-    # GA3C_CONV_BWD_MIN=1: the fused conv_bwd at every size up to 128 rows (by default the split launches take batches below
-    # 97 rows since round 4, so the default network is compared from there on)
-    monkeypatch.setenv("GA3C_CONV_BWD_MIN", "1")
-    monkeypatch.setenv("GA3C_WD_STEP_IN_CONV_BWD", "2")
-    ref = Network("gpu:0", "wd_conv_bwd", 6, (84, 84, 4), max_batch=136, predict_lanes=1)
-    monkeypatch.setenv("GA3C_WD_STEP_IN_CONV_BWD", "0")
-    net = Network("gpu:0", "wd_epilogue", 6, (84, 84, 4), max_batch=136, predict_lanes=1)
-    monkeypatch.delenv("GA3C_WD_STEP_IN_CONV_BWD")
-    monkeypatch.delenv("GA3C_CONV_BWD_MIN")
-    dflt = nets(6)
+    mu = 0.5
+    monkeypatch.setattr(Config.Config, "RMSPROP_MOMENTUM", mu)
+    net = Network("gpu:0", "seams_mom", 6, (84, 84, 4), max_batch=148, predict_lanes=1)
+    fresh = Network("gpu:0", "seams_fresh", 6, (84, 84, 4), max_batch=148, predict_lanes=1)
     try:
-        for bsz in (8, 40, 120, 121, 128):
-            xk, x, a, y = _batch(bsz, 6, 9100 + bsz)
-            outs = []
-            for n in (ref, net, dflt):
-                _reset(n, 6)
-                for xin in (x, xk, x):
-                    n.train(xin, y, a)
-                outs.append((n.get_arena(0), n.get_arena(1), n.predict_p_v_logits(x)))
-            for other in outs[1:] if bsz >= 97 else outs[1:2]:
-                assert np.array_equal(outs[0][0], other[0]) and np.array_equal(outs[0][1], other[1]), bsz
-                assert all(np.array_equal(g, w) for g, w in zip(outs[0][2], other[2])), bsz
-            assert not np.array_equal(outs[0][0], _flat(o.init_params(6)).astype(np.float32))
+        for bsz in (8, 40, 64, 96, 97, 100, 120, 121, 128, 129, 133, 134, 140):
+            xk, x, a, y = _batch(bsz, 6, 9300 + bsz)
+            params = o.init_params(6)
+            ms = {k: np.ones_like(v) for k, v in params.items()}
+            mom = {k: np.zeros_like(v) for k, v in params.items()}
+            _reset(net, 6)
+            for xin in (x, xk, x):
+                net.train(xin, y, a)
+                _, g = o.loss_and_grads(params, x.astype(np.float64), y, a.astype(np.float64), BETA)
+                o.rmsprop_update(params, ms, g, LR, decay=Config.Config.RMSPROP_DECAY, eps=Config.Config.RMSPROP_EPSILON,
+                                 momentum=mu, mom=mom)
+            got_w, got_ms, got_mom = net.get_arena(0), net.get_arena(1), net.get_arena(2)
+            want_ms = _flat(ms)
+            assert np.max(np.abs(got_w - _flat(params))) < 2e-5, (bsz, np.max(np.abs(got_w - _flat(params))))
+            assert np.max(np.abs(got_ms - want_ms)) < 1e-5 * max(1.0, np.max(np.abs(want_ms))), bsz
+            assert np.max(np.abs(got_mom - _flat(mom))) < 2e-5, bsz
+            assert np.any(got_mom != 0), bsz
+            fresh.set_arena(0, got_w)
+            xp = x[:min(bsz, 128)]
+            assert all(np.array_equal(g, w) for g, w in zip(net.predict_p_v_logits(xp), fresh.predict_p_v_logits(xp))), bsz
     finally:
         net.close()
-        ref.close()
-    # momentum: a Network reads the optimizer's constants from Config when it is created
-    monkeypatch.setattr(Config.Config, "RMSPROP_MOMENTUM", 0.5)
-    pair = []
-    monkeypatch.setenv("GA3C_CONV_BWD_MIN", "1")
-    for flag in ("2", "0"):
-        monkeypatch.setenv("GA3C_WD_STEP_IN_CONV_BWD", flag)
-        pair.append(Network("gpu:0", "wd_mom" + flag, 6, (84, 84, 4), max_batch=136, predict_lanes=1))
-    monkeypatch.delenv("GA3C_WD_STEP_IN_CONV_BWD")
-    monkeypatch.delenv("GA3C_CONV_BWD_MIN")
-    try:
-        xk, x, a, y = _batch(64, 6, 9164)
-        outs = []
-        for n in pair:
-            _reset(n, 6)
-            for _ in range(3):
-                n.train(x, y, a)
-            outs.append((n.get_arena(0), n.get_arena(1), n.get_arena(2)))
-        assert all(np.array_equal(g, w) for g, w in zip(outs[0], outs[1]))
-        assert np.any(outs[0][2] != 0)
-    finally:
-        for n in pair:
-            n.close()
-
-
-def test_split_path_scheduling_switches_leave_the_bits_alone(monkeypatch):
-    """Beyond the fused conv kernels' 128 rows (round 4): dense1/w stepped by workgroups of their own in conv2_dx's launch
-    (GA3C_WD_STEP_IN_CONV2_DX, at the back or the front of the grid: GA3C_WD_BLOCKS_FIRST), conv2_dw cut for three
-    workgroups per CU (GA3C_C2DW_OCC), dense1_bwd_tile's rows past 128 worked on out of the tail area beside the first chunk
-    (GA3C_D1B_TAIL; off: a second chunk whose dn2 tile is cut over the waves the same way), conv2_dw and conv1_dw side by
-    side in one launch behind conv2_dx (GA3C_DW_PAIR; the number of conv1_dw workgroups = partial slabs is a function of the
-    batch size alone).  Each moves work, none changes an
-    element's arithmetic or a sum's order: weights, `ms`, momentum and -- through the fragment-ordered copy of dense1/w --
-    the predictions after three steps are bit-identical with all of them off, at 129 / 132 / 133 (tail area), 134 / 140
-    (second chunk) and 100 rows (split path below 128: GA3C_CONV_BWD=0)."""
-    import ga3c_amd  # noqa: F401
-    import Config
-    from NetworkVP import Network
-    monkeypatch.setattr(Config.Config, "RMSPROP_MOMENTUM", 0.5)
-    monkeypatch.setenv("GA3C_CONV_BWD", "0")
-    settings = [{}, {"GA3C_WD_STEP_IN_CONV2_DX": "0", "GA3C_C2DW_OCC": "2", "GA3C_D1B_TAIL": "0", "GA3C_DW_PAIR": "0", "GA3C_C2F_QUARTER": "0"},
-                {"GA3C_WD_BLOCKS_FIRST": "1"}]
-    made = []
-    try:
-        for i, env in enumerate(settings):
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            made.append(Network("gpu:0", "split_sw%d" % i, 6, (84, 84, 4), max_batch=140, predict_lanes=1))
-            for k in env:
-                monkeypatch.delenv(k)
-        for bsz in (8, 40, 100, 129, 132, 133, 134, 140):
-            xk, x, a, y = _batch(bsz, 6, 9300 + bsz)
-            outs = []
-            for n in made:
-                _reset(n, 6)
-                for xin in (x, xk, x):
-                    n.train(xin, y, a)
-                outs.append((n.get_arena(0), n.get_arena(1), n.get_arena(2)) + tuple(n.predict_p_v_logits(x[:min(bsz, 128)])))
-            for other in outs[1:]:
-                assert all(np.array_equal(g, w) for g, w in zip(outs[0], other)), bsz
-            assert np.any(outs[0][2] != 0) and not np.array_equal(outs[0][0], _flat(o.init_params(6)).astype(np.float32))
-    finally:
-        for n in made:
-            n.close()
+        fresh.close()
 
 
 @pytest.mark.parametrize("num_actions", [6, 18])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development aid: sha256 of the weights and the RMSProp slots after a few production train steps at the given row counts,
-uint8 and f32 states.  Run it under two settings of an engine switch (section 8b of DESIGN.md) and compare the lines: kernel
-variants that only change scheduling (GA3C_C2DW_OCC, GA3C_D1B_TAIL) must print the same digests.
+uint8 and f32 states.  Compare two builds or two settings (section 8b of DESIGN.md) by their lines: a change that only
+moves work must print the same digests.
 usage: python tools/ab_bits.py [rows ...]      (default 129 132 133)"""
 import hashlib
 import os
