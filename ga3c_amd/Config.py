@@ -4,6 +4,7 @@ Config (/root/reference/ga3c/Config.py:27-202) and overridable from argv as KEY=
 fixes for the 84x84x4 Atari path (the fork's own defaults target Pendulum), and the block at the
 end adds the knobs this engine needs (devices, transport, return mode).
 """
+import os
 
 
 class Config:
@@ -58,8 +59,25 @@ class Config:
     DISCRATE_INPUT = True               # (sic) discrete action space: softmax policy head; derived, = not CONTINUOUS_INPUT
     CONTINUOUS_INPUT = False            # angle-output policy head, the action IS the prediction vector in (-1, 1]^A
                                         # (NetworkVP.py:92,95-105,175-204, ProcessAgent.py:134-137); DESIGN §8d
-    USE_DDPG = False
-    USE_REPLAY_MEMORY = False
+    USE_DDPG = False                    # NetworkDDPG.py with ThreadReplay.py (needs CONTINUOUS_INPUT); resolve_ddpg() applies what
+    USE_REPLAY_MEMORY = False           # it implies (the reference's Config.py:160-178): USE_REPLAY_MEMORY, DISCOUNTING = False
+    add_OUnoise = True                  # (sic) Ornstein-Uhlenbeck noise on every prediction of NetworkDDPG, which alone reads it
+                                        # (the reference sets it True under USE_DDPG); switch off with `add_OUnoise=`
+    add_uncertainity = False            # (sic) an integer added to the prediction: not supported, raises
+    REPLAY_BUFFER_SIZE = 1000000
+    REPLAY_BUFFER_RANDOM_SEED = 12345
+    REPLAY_MIN_QUEUE_SIZE = 2
+    DDPG_FUTURE_REWARD_CALC = True      # y = r + gamma q' on rows that are not done; False: y = r
+    DDPG_CRITIC_LOSS = 'fork'           # 'fork': mean_square(y[B], q[B,1]) broadcasts, the critic regresses on mean(y), as the
+                                        # reference computes it; 'paired': (q_i - y_i)^2
+    tau = 0.001
+    gamma = 0.99
+    actor_lr = 1.0                      # factors on the annealed learning rate; the later of the two assignments in the
+    critic_lr = 10.0                    # reference's class body (Config.py:198-199)
+    RMSPROP = True                      # critic optimizer: RMSProp (True) or Adam
+    OU_SIGMA = 0.3                      # OrnsteinUhlenbeckActionNoise's defaults (NetworkDDPG.py:466)
+    OU_THETA = 0.15
+    OU_DT = 1e-2
     USE_NETWORK_TESTER = False
     RANDOM_SEED = 12345
 
@@ -144,3 +162,30 @@ def resolve_action_space(explicit=()):
     elif "DISCRATE_INPUT" in explicit:
         Config.CONTINUOUS_INPUT = not Config.DISCRATE_INPUT
     Config.DISCRATE_INPUT = not Config.CONTINUOUS_INPUT
+
+
+def resolve_ddpg(explicit=()):
+    """What USE_DDPG implies (the reference's Config.py:160-178) and what it cannot be combined with here.  Call after
+    resolve_action_space.  Without USE_DDPG nothing changes."""
+    if not Config.USE_DDPG:
+        return
+    if not Config.CONTINUOUS_INPUT:
+        raise ValueError("USE_DDPG needs a continuous action space (CONTINUOUS_INPUT); GAME=%s is discrete" % Config.GAME)
+    if not vector_game():
+        raise ValueError("USE_DDPG on an image game is not supported: the DDPG networks read vector states (GAME=Pendulum-v0)")
+    for key, bad in (("DUAL_RMSPROP", True), ("HOGWILD", True), ("add_uncertainity", True)):
+        if getattr(Config, key) == bad:
+            raise ValueError("USE_DDPG with %s=%r is not supported" % (key, bad))
+    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+        raise ValueError("USE_DDPG with WORLD_SIZE > 1 is not supported")
+    if Config.FRONTEND == 'device':
+        raise ValueError("USE_DDPG with FRONTEND='device' is not supported")
+    if Config.DDPG_CRITIC_LOSS not in ('fork', 'paired'):
+        raise ValueError("DDPG_CRITIC_LOSS=%r: 'fork' or 'paired'" % (Config.DDPG_CRITIC_LOSS,))
+    if Config.TRAINING_MIN_BATCH_SIZE < 1:
+        raise ValueError("USE_DDPG samples TRAINING_MIN_BATCH_SIZE rows per train step; the default 0 would train on empty "
+                         "batches, as it does in the reference.  Set it, e.g. TRAINING_MIN_BATCH_SIZE=64")
+    if Config.REPLAY_BUFFER_SIZE <= Config.TRAINING_MIN_BATCH_SIZE:
+        raise ValueError("REPLAY_BUFFER_SIZE must exceed TRAINING_MIN_BATCH_SIZE: a batch is sampled only from more rows than it holds")
+    Config.USE_REPLAY_MEMORY = True
+    Config.DISCOUNTING = False

@@ -5,7 +5,7 @@ switched off with an empty value (`KEY=`), because bool("False") is True (SURVEY
 import sys
 
 import _native  # noqa: F401  (fail early if the libraries are not built)
-from Config import Config, resolve_action_space
+from Config import Config, resolve_action_space, resolve_ddpg
 
 
 def apply_argv(argv):
@@ -15,6 +15,7 @@ def apply_argv(argv):
         setattr(Config, key, type(getattr(Config, key))(value))
         given.add(key)
     resolve_action_space(given)
+    resolve_ddpg(given)
     if Config.PLAY_MODE:
         Config.AGENTS = 1
         Config.PREDICTORS = 1

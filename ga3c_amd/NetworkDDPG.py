@@ -1,0 +1,343 @@
+"""DDPG for vector-state games with continuous actions (Config.USE_DDPG) -- reference NetworkDDPG.py, backed by the
+ga3c_ddpg handle of libga3c_hip.so.
+
+    actor   x[B,S] -> actor_fc1 (400) -> actor_norm1 -> relu -> actor_fc2 (300) -> actor_norm2 -> relu -> actor_output (A, tanh)
+    critic  x -> critic_fc1 (400) -> critic_norm1 -> relu = h;  q = critic_output(relu(h W_fc2 + a W_n2 + b_n2))
+
+Same interface as NetworkVP.Network where Server, ThreadPredictor and ThreadTrainer use it.  The replay memory lives in
+the handle (replay_add*, train_replay); the Ornstein-Uhlenbeck process too, because the native predictor loops call the
+handle without the interpreter.
+"""
+import ctypes as C
+import glob
+import os
+import re
+import threading
+
+import numpy as np
+
+from Config import Config
+from NetworkVP import _device_ordinal
+import _native as nat
+
+H1, H2 = 400, 300
+ACTOR_TRAINABLE = ("actor_fc1/W", "actor_fc1/b", "actor_norm1/beta", "actor_norm1/gamma", "actor_fc2/W", "actor_fc2/b",
+                   "actor_norm2/beta", "actor_norm2/gamma", "actor_output/W", "actor_output/b")
+CRITIC_TRAINABLE = ("critic_fc1/W", "critic_fc1/b", "critic_norm1/beta", "critic_norm1/gamma", "critic_fc2/W", "critic_fc2/b",
+                    "critic_norm2/W", "critic_norm2/b", "critic_output/W", "critic_output/b")
+TRAINABLE = ACTOR_TRAINABLE + CRITIC_TRAINABLE
+VALUE, TARGET, SLOT_A, SLOT_B, GRAD = range(5)
+
+
+def param_shapes(state_dim, num_actions):
+    S, A = int(state_dim), int(num_actions)
+    return {"actor_fc1/W": (S, H1), "actor_fc1/b": (H1,), "actor_norm1/beta": (H1,), "actor_norm1/gamma": (H1,),
+            "actor_fc2/W": (H1, H2), "actor_fc2/b": (H2,), "actor_norm2/beta": (H2,), "actor_norm2/gamma": (H2,),
+            "actor_output/W": (H2, A), "actor_output/b": (A,),
+            "critic_fc1/W": (S, H1), "critic_fc1/b": (H1,), "critic_norm1/beta": (H1,), "critic_norm1/gamma": (H1,),
+            "critic_fc2/W": (H1, H2), "critic_fc2/b": (H2,), "critic_norm2/W": (A, H2), "critic_norm2/b": (H2,),
+            "critic_output/W": (H2, 1), "critic_output/b": (1,)}
+
+
+def _truncated_normal(rng, shape, stddev):
+    out = rng.normal(0.0, stddev, size=shape)
+    bad = np.abs(out) > 2 * stddev
+    while bad.any():                        # resample beyond two standard deviations
+        out[bad] = rng.normal(0.0, stddev, size=int(bad.sum()))
+        bad = np.abs(out) > 2 * stddev
+    return out
+
+
+def _draw(rng, name, shape):
+    """tflearn's defaults as DESIGN.md 8f restates them (the one place): W truncated normal 0.02, the two output layers
+    U(-0.003, 0.003) (NetworkDDPG.py:226,408), b = 0, beta = 0, gamma ~ N(1, 0.002)."""
+    if name in ("actor_output/W", "critic_output/W"):
+        return rng.uniform(-0.003, 0.003, size=shape)
+    if name.endswith("/W"):
+        return _truncated_normal(rng, shape, 0.02)
+    if name.endswith("/gamma"):
+        return rng.normal(1.0, 0.002, size=shape)
+    return np.zeros(shape)
+
+
+def initial_arena(state_dim, num_actions, seed, tau=None):
+    """-> (online, target): dicts of f32 arrays for the 20 trainable variables, drawn from one PCG64(seed) stream in variable
+    order, the online networks first (actor, critic), then independently drawn targets in the same order.  The reference does
+    not copy the online weights: it runs ONE soft update on those targets (NetworkDDPG.py:17-21), restated here."""
+    tau = Config.tau if tau is None else tau
+    rng = np.random.Generator(np.random.PCG64(seed))
+    shapes = param_shapes(state_dim, num_actions)
+    online = {k: _draw(rng, k, shapes[k]).astype(np.float32) for k in TRAINABLE}
+    target0 = {k: _draw(rng, k, shapes[k]).astype(np.float32) for k in TRAINABLE}
+    target = {k: (np.float32(tau) * online[k] + np.float32(1.0 - tau) * target0[k]).astype(np.float32) for k in TRAINABLE}
+    return online, target
+
+
+class Network:
+    def __init__(self, device, model_name, num_actions, state_dim, max_batch=None, predict_lanes=None, replay_capacity=None):
+        self.device = device
+        self.model_name = model_name
+        self.num_actions = int(num_actions)
+        self.state_dim = tuple(state_dim) if np.ndim(state_dim) else (int(state_dim),)
+        if len(self.state_dim) != 1:
+            raise ValueError("state_dim %r is not a vector" % (state_dim,))
+        self.S = int(self.state_dim[0])
+        self.learning_rate = Config.LEARNING_RATE_START
+        self.beta = Config.BETA_START
+        if Config.add_uncertainity:
+            raise ValueError("add_uncertainity is not supported")
+        if Config.DDPG_CRITIC_LOSS not in ('fork', 'paired'):
+            raise ValueError("DDPG_CRITIC_LOSS=%r: 'fork' or 'paired'" % (Config.DDPG_CRITIC_LOSS,))
+        if max_batch is None:
+            max_batch = max(Config.PREDICTION_BATCH_SIZE, Config.TRAINING_MIN_BATCH_SIZE, Config.TIME_MAX + 1)
+        self.max_batch = int(max_batch)
+        self._lib = nat.hip_lib()
+        cfg = nat.DdpgConfig()
+        cfg.device = _device_ordinal(device)
+        cfg.state_dim = self.S
+        cfg.num_actions = self.num_actions
+        cfg.max_batch = self.max_batch
+        cfg.replay_capacity = int(replay_capacity or Config.REPLAY_BUFFER_SIZE)
+        cfg.predict_lanes = int(predict_lanes or 2 * max(Config.PREDICTORS, 4 if Config.DYNAMIC_SETTINGS else 1) + 2)
+        cfg.flags = ((nat.DDPG_FUTURE_REWARD if Config.DDPG_FUTURE_REWARD_CALC else 0)
+                     | (nat.DDPG_LOSS_PAIRED if Config.DDPG_CRITIC_LOSS == 'paired' else 0)
+                     | (nat.DDPG_GRAD_CLIP if Config.USE_GRAD_CLIP else 0)
+                     | (0 if Config.RMSPROP else nat.DDPG_CRITIC_ADAM)
+                     | (nat.DDPG_OU_NOISE if Config.add_OUnoise else 0))
+        cfg.tau, cfg.gamma = Config.tau, Config.gamma
+        cfg.actor_lr, cfg.critic_lr = Config.actor_lr, Config.critic_lr
+        cfg.rmsprop_decay = Config.RMSPROP_DECAY
+        cfg.rmsprop_momentum = Config.RMSPROP_MOMENTUM
+        cfg.rmsprop_epsilon = Config.RMSPROP_EPSILON
+        cfg.grad_clip_norm = Config.GRAD_CLIP_NORM
+        cfg.ou_sigma, cfg.ou_theta, cfg.ou_dt = Config.OU_SIGMA, Config.OU_THETA, Config.OU_DT
+        cfg.seed = Config.RANDOM_SEED
+        handle = C.c_void_p()
+        nat.check(self._lib.ga3c_ddpg_create(C.byref(cfg), C.byref(handle)), "ga3c_ddpg_create")
+        self._h = handle
+        self.replay_capacity = cfg.replay_capacity
+        online, target = initial_arena(self.S, self.num_actions, Config.RANDOM_SEED)
+        for k in TRAINABLE:
+            self.set_variable_value(k, online[k], VALUE)
+            self.set_variable_value(k, target[k], TARGET)
+        self._log_lock = threading.Lock()
+        self.logging = (0.0, 0.0)               # Q_max, Q_avg of the last step (NetworkDDPG.py:98)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ga3c_ddpg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- variables: which = VALUE, TARGET, SLOT_A, SLOT_B (RMSProp ms / mom or Adam m / v), GRAD -----------------------
+    def get_global_step(self):
+        s = C.c_int64()
+        nat.check(self._lib.ga3c_ddpg_get_step(self._h, C.byref(s)))
+        return s.value
+
+    def set_global_step(self, step):
+        nat.check(self._lib.ga3c_ddpg_set_step(self._h, int(step)), "ga3c_ddpg_set_step")
+
+    def get_variables_names(self):
+        n = self._lib.ga3c_ddpg_num_params(self._h)
+        return [self._lib.ga3c_ddpg_param_name(self._h, i).decode() + ":0" for i in range(n)]
+
+    def get_target_names(self):
+        n = self._lib.ga3c_ddpg_num_params(self._h)
+        return [self._lib.ga3c_ddpg_target_name(self._h, i).decode() + ":0" for i in range(n)]
+
+    def _param_info(self, name):
+        count, ndim, trainable = C.c_int64(), C.c_int32(), C.c_int32()
+        shape = (C.c_int64 * 4)()
+        nat.check(self._lib.ga3c_ddpg_param_info(self._h, name.encode(), C.byref(count), C.byref(ndim), shape, C.byref(trainable)),
+                  "ga3c_ddpg_param_info")
+        return count.value, tuple(shape[d] for d in range(ndim.value)), bool(trainable.value)
+
+    def get_variable_value(self, name, which=VALUE):
+        count, shape, _ = self._param_info(name)
+        out = np.empty(count, dtype=np.float32)
+        nat.check(self._lib.ga3c_ddpg_get_param(self._h, name.encode(), which, nat.ptr(out), count), "ga3c_ddpg_get_param")
+        return out.reshape(shape)
+
+    def set_variable_value(self, name, value, which=VALUE):
+        flat = nat.as_f32(value).ravel()
+        nat.check(self._lib.ga3c_ddpg_set_param(self._h, name.encode(), which, nat.ptr(flat), flat.size), "ga3c_ddpg_set_param")
+
+    # ---- noise -----------------------------------------------------------------------------------
+    def _noise_args(self, noise):
+        """noise: None = the handle's own process (one step per call), False = none, or a vector [A]."""
+        if noise is None:
+            return nat.DDPG_NOISE_OWN, None, None
+        if noise is False:
+            return nat.DDPG_NOISE_NONE, None, None
+        v = nat.as_f32(noise).ravel()
+        if v.size != self.num_actions:
+            raise ValueError("noise of %d elements for %d actions" % (v.size, self.num_actions))
+        return nat.DDPG_NOISE_GIVEN, nat.ptr(v), v
+
+    def noise_step(self):
+        """One step of the handle's OU process -> (x[A], n[A]): the new state and the normal draws it used."""
+        x, n = np.empty(self.num_actions, np.float32), np.empty(self.num_actions, np.float32)
+        nat.check(self._lib.ga3c_ddpg_noise_step(self._h, nat.ptr(x), nat.ptr(n)), "ga3c_ddpg_noise_step")
+        return x, n
+
+    # ---- inference ---------------------------------------------------------------------------
+    def _rows(self, x):
+        x = nat.as_f32(x).reshape(-1, self.S)
+        return x, int(x.shape[0])
+
+    def predict(self, x, noise=None):
+        x, b = self._rows(x)
+        mode, nptr, _keep = self._noise_args(noise)
+        a = np.empty((b, self.num_actions), np.float32)
+        nat.check(self._lib.ga3c_ddpg_predict(self._h, nat.ptr(x), b, mode, nptr, nat.ptr(a)), "ga3c_ddpg_predict")
+        return a
+
+    def predict_p_and_v(self, x):
+        """(action, action), as the reference returns it (NetworkDDPG.py:106-111)."""
+        a = self.predict(x)
+        return [a, a]
+
+    def predict_single(self, x):
+        return self.predict(x[None, :])[0]
+
+    # ---- zero-copy intake from the shared-memory transport -------------------------------------------
+    def register_transport(self, transport):
+        nat.check(self._lib.ga3c_ddpg_register_host(self._h, C.c_void_p(transport.base), transport.nbytes),
+                  "ga3c_ddpg_register_host")
+
+    def unregister_transport(self):
+        nat.check(self._lib.ga3c_ddpg_unregister_host(self._h), "ga3c_ddpg_unregister_host")
+
+    def gather_entry(self):
+        return C.cast(self._lib.ga3c_ddpg_predict_gather, C.c_void_p).value, self._h, 0
+
+    def gather_entries_pipelined(self):
+        return (C.cast(self._lib.ga3c_ddpg_predict_gather_begin, C.c_void_p).value,
+                C.cast(self._lib.ga3c_ddpg_predict_gather_end, C.c_void_p).value, self._h, 0)
+
+    def predict_offsets(self, offsets):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        b = offsets.size
+        p = np.empty((b, self.num_actions), np.float32)
+        v = np.empty(b, np.float32)
+        nat.check(self._lib.ga3c_ddpg_predict_gather(self._h, nat.ptr(offsets, nat.i64p), b, 0, nat.ptr(p), nat.ptr(v), None),
+                  "ga3c_ddpg_predict_gather")
+        return [p, p]
+
+    # ---- replay memory (replay_buffer.py:16-55, a ring in HBM) ------------------------------------------
+    def replay_add(self, s, a, r, done, s2):
+        """Appends the rows -> (rows held, rows ever added)."""
+        s, n = self._rows(s)
+        s2, _ = self._rows(s2)
+        a = nat.as_f32(a).reshape(n, self.num_actions)
+        r, done = nat.as_f32(r).ravel(), nat.as_f32(done).ravel()
+        size, total = C.c_int64(), C.c_int64()
+        nat.check(self._lib.ga3c_ddpg_replay_add(self._h, nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(done), nat.ptr(s2), n,
+                                                 C.byref(size), C.byref(total)), "ga3c_ddpg_replay_add")
+        return size.value, total.value
+
+    def replay_add_offsets(self, offsets, r, a):
+        """Rows `s | s2 | done` of the registered transport by byte offset -> (rows held, rows ever added)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.size
+        r, a = nat.as_f32(r).ravel(), nat.as_f32(a).reshape(n, self.num_actions)
+        size, total = C.c_int64(), C.c_int64()
+        nat.check(self._lib.ga3c_ddpg_replay_add_gather(self._h, nat.ptr(offsets, nat.i64p), nat.ptr(r), nat.ptr(a), n,
+                                                        C.byref(size), C.byref(total)), "ga3c_ddpg_replay_add_gather")
+        return size.value, total.value
+
+    def replay_get(self, slot):
+        s, s2 = np.empty(self.S, np.float32), np.empty(self.S, np.float32)
+        a = np.empty(self.num_actions, np.float32)
+        r, done = C.c_float(), C.c_float()
+        nat.check(self._lib.ga3c_ddpg_replay_get(self._h, int(slot), nat.ptr(s), nat.ptr(a), C.byref(r), C.byref(done), nat.ptr(s2)),
+                  "ga3c_ddpg_replay_get")
+        return s, a, np.float32(r.value), np.float32(done.value), s2
+
+    def replay_size(self):
+        size, total = C.c_int64(), C.c_int64()
+        nat.check(self._lib.ga3c_ddpg_replay_size(self._h, C.byref(size), C.byref(total)), "ga3c_ddpg_replay_size")
+        return size.value, total.value
+
+    # ---- training ----------------------------------------------------------------------------
+    def _five(self, x, y_r, a, x2, done):
+        s, b = self._rows(x)
+        s2, _ = self._rows(x2)
+        return (s, nat.as_f32(a).reshape(b, self.num_actions), nat.as_f32(y_r).ravel(), nat.as_f32(done).ravel(), s2, b)
+
+    def train(self, x, y_r, a, x2, done, trainer_id=0, noise=None):
+        """train_DDPG(s = x, a, r = y_r, done, s2 = x2) (NetworkDDPG.py:61-62)."""
+        s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)
+        mode, nptr, _keep = self._noise_args(noise)
+        q = np.empty(2, np.float32)
+        nat.check(self._lib.ga3c_ddpg_train(self._h, nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(d), nat.ptr(s2), b,
+                                            float(self.learning_rate), mode, nptr, nat.ptr(q)), "ga3c_ddpg_train")
+        self.logging = (float(q[0]), float(q[1]))
+        return self.logging
+
+    def train_replay(self, slots, stamp=-1, noise=None):
+        """One step on ring slots; stamp: the ring's `total` when they were sampled (a slot written since raises StateLost)."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        mode, nptr, _keep = self._noise_args(noise)
+        q = np.empty(2, np.float32)
+        nat.check(self._lib.ga3c_ddpg_train_replay(self._h, nat.ptr(slots, nat.i32p), slots.size, int(stamp),
+                                                   float(self.learning_rate), mode, nptr, nat.ptr(q)), "ga3c_ddpg_train_replay")
+        self.logging = (float(q[0]), float(q[1]))
+        return self.logging
+
+    def compute(self, x, y_r, a, x2, done, stop_after, noise=None):
+        s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)
+        mode, nptr, _keep = self._noise_args(noise)
+        q = np.empty(2, np.float32)
+        nat.check(self._lib.ga3c_ddpg_compute(self._h, nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(d), nat.ptr(s2), b,
+                                              float(self.learning_rate), mode, nptr, int(stop_after), nat.ptr(q)),
+                  "ga3c_ddpg_compute")
+        return float(q[0]), float(q[1])
+
+    def fetch(self, name, count):
+        out = np.empty(int(count), np.float32)
+        nat.check(self._lib.ga3c_ddpg_fetch(self._h, name.encode(), nat.ptr(out), out.size), "ga3c_ddpg_fetch")
+        return out
+
+    def time_resident(self, mode, batch, iters):
+        """Milliseconds of `iters` resident calls (mode 0 predict, 1 train_replay) on ring slots 0 .. batch-1."""
+        ms = C.c_float()
+        nat.check(self._lib.ga3c_ddpg_time_resident(self._h, int(mode), int(batch), int(iters), float(self.learning_rate),
+                                                    C.byref(ms)), "ga3c_ddpg_time_resident")
+        return ms.value
+
+    # ---- logging / checkpoints -----------------------------------------------------------------
+    def log(self, x=None, y_r=None, a=None, training_step=0, feed_dict=None, offsets=None, frames=None):
+        """LearningRate, Q_max, Q_avg (NetworkDDPG.py:122,133-134) appended to logs/<model>/scalars.csv."""
+        q_max, q_avg = self.logging
+        os.makedirs("logs/%s" % self.model_name, exist_ok=True)
+        with self._log_lock:
+            with open("logs/%s/scalars.csv" % self.model_name, "a") as f:
+                f.write("%d,%.8g,%.8g,%.8g\n" % (training_step, self.learning_rate, q_max, q_avg))
+
+    def _checkpoint_filename(self, episode):
+        return 'checkpoints/%s_%08d' % (self.model_name, episode)
+
+    def save(self, episode):
+        os.makedirs("checkpoints", exist_ok=True)
+        nat.check(self._lib.ga3c_ddpg_save(self._h, (self._checkpoint_filename(episode) + ".npz").encode()), "ga3c_ddpg_save")
+
+    def load_file(self, filename):
+        nat.check(self._lib.ga3c_ddpg_load(self._h, filename.encode()), "ga3c_ddpg_load")
+
+    def load(self):
+        if Config.LOAD_EPISODE > 0:
+            filename = self._checkpoint_filename(Config.LOAD_EPISODE) + ".npz"
+        else:
+            found = sorted(glob.glob('checkpoints/%s_????????.npz' % self.model_name))
+            if not found:
+                raise FileNotFoundError("no checkpoint for %s" % self.model_name)
+            filename = found[-1]
+        self.load_file(filename)
+        return int(re.split(r'/|_|\.', filename[:-4])[2])

@@ -242,6 +242,13 @@ class ProcessAgent(MP.Process):
             if self.env.on_device or self.names_states:   # row = (plane / request number, agent id): the state itself is in HBM
                 states[i, :8].view(np.int64)[0] = e.state
                 states[i, 8:12].view(np.int32)[0] = self.id
+            elif Config.USE_DDPG:                         # row = s | s2 | done | zero padding, f32 (ThreadReplay.py)
+                row = states[i].view(np.float32)
+                s = e.state.reshape(-1)
+                row[:s.size] = s
+                row[s.size:2 * s.size] = e.next_state.reshape(-1)
+                row[2 * s.size] = 1.0 if e.done else 0.0
+                row[2 * s.size + 1:] = 0.0
             else:
                 states[i] = e.state.reshape(-1).view(np.uint8)
             returns[i] = e.reward               # f64 -> f32 here, as TF's feed does (NetworkVP.py:70,256)

@@ -9,21 +9,24 @@ What changed against the reference, and why:
   * agents are started from a forkserver, so they never inherit the server's HIP state.
 """
 import os
+import queue
 import threading
 import time
 
-from Config import Config, resolve_action_space, vector_game
+from Config import Config, resolve_action_space, resolve_ddpg, vector_game
 import DataParallel
 from Environment import Environment
 import EnvironmentPend
 from NetworkVP import Network, _device_ordinal
 import NetworkVP_vector
+import NetworkDDPG
 import Placement
 import _native as nat
 from ProcessAgent import ProcessAgent, config_snapshot
 from ProcessStats import ProcessStats
 from ThreadDynamicAdjustment import ThreadDynamicAdjustment
 from ThreadPredictor import ThreadPredictor
+from ThreadReplay import ThreadReplay, rollout_row_bytes
 from ThreadTrainer import ThreadTrainer
 import Transport as tp
 
@@ -33,6 +36,11 @@ class Server:
         # one Server per GPU under torch.distributed.run: lock-step training over RCCL (DataParallel.py)
         self.dp = engine_group
         resolve_action_space()                  # DISCRATE_INPUT = not CONTINUOUS_INPUT (Server.py:36-38)
+        resolve_ddpg()                          # what USE_DDPG implies, and what it refuses (Server.py:48-54, Config.py:160-178)
+        # USE_DDPG: NetworkDDPG and the replay thread; trainers take sampled batches of ring slots (ThreadReplay.py)
+        self.ddpg = bool(Config.USE_DDPG)
+        self.replay_q = queue.Queue()
+        self.replay = None
         # GAME = 'Pendulum-v0': the vector-state network, f32 states of 4 S bytes, no frame front-end or state cache
         self.vector = vector_game()
         if self.vector:
@@ -71,6 +79,10 @@ class Server:
         # everything it rests on: the GPU reading the transport itself, uint8 states, the native pipelined predictor loop,
         # plain launches; anything else keeps the states in the rollouts.
         model_cls = (NetworkVP_vector.Network if self.vector else Network) if model is None else type(model)
+        if self.ddpg:
+            if model is None:
+                model_cls = NetworkDDPG.Network
+            row_bytes = rollout_row_bytes(self.state_dim[0])    # a rollout row carries s | s2 | done (ProcessAgent._ship)
         self.state_cache = bool(getattr(Config, "STATE_CACHE", False) and not self.device_frontend and Config.ZERO_COPY and
                                 Config.STATE_TRANSPORT == 'u8' and getattr(Config, "NATIVE_PREDICTOR", True) and
                                 getattr(Config, "PIPELINED_PREDICTOR", True) and getattr(Config, "NATIVE_TRAINER", True) and
@@ -286,12 +298,29 @@ class Server:
                 self.model.train_frames(agents, seqs, r_, a_)
                 self._count_train_step(agents.shape[0], None, r_, a_, frames=(agents, seqs))
 
+    def train_model_replay(self, slots, stamp, trainer_id):
+        """train_model for a batch the replay thread sampled: ring slots, and the ring's row count when they were drawn."""
+        try:
+            self.model.train_replay(slots, stamp)
+        except nat.StateLost as e:              # a slot was overwritten since (GA3C_ELOST): nothing was trained
+            self.lost_train_batches += 1
+            if self.lost_train_batches == 1:
+                print("[replay] %s" % e, flush=True)
+            return
+        self._count_train_step(len(slots), None, None, None)
+
+    def start_replay(self):
+        if self.ddpg and self.replay is None:
+            self.replay = ThreadReplay(self)
+            self.replay.start()
+
     def save_model(self):
         self.model.save(self.stats.episode_count.value)
 
     # ---- main loop (Server.py:155-198) ----------------------------------------------------------
     def main(self, max_seconds=None):
         self.stats.start()
+        self.start_replay()
         self.dynamic_adjustment.start()
         lr_mult = (Config.LEARNING_RATE_END - Config.LEARNING_RATE_START) / Config.ANNEALING_EPISODE_COUNT
         beta_mult = (Config.BETA_END - Config.BETA_START) / Config.ANNEALING_EPISODE_COUNT
@@ -341,6 +370,10 @@ class Server:
             self.remove_predictor()
         while self.trainers:
             self.remove_trainer()
+        if self.replay is not None:
+            self.replay.exit_flag = True
+            self.replay.join(5.0)
+            self.replay = None
         if self.stats.is_alive():
             self.stats.terminate()
         stalled = self.failure is not None and isinstance(self.failure[1], DataParallel.GroupStalled)

@@ -4,7 +4,8 @@ queue until the batch holds MORE than TRAINING_MIN_BATCH_SIZE rows, then one ser
 Rollouts arrive as slots of the shared-memory transport (states, f32 returns, int32 actions -- or f32 action vectors
 under CONTINUOUS_INPUT, which go to the network as they are instead of as one-hot rows);
 rows are copied once into a staging batch instead of the reference's repeated np.concatenate.
-x2_ and done_ are not transported (unused by the A3C nets, NetworkVP.py:254); train_model gets None.
+x2_ and done_ are not transported for the A3C nets (unused there, NetworkVP.py:254); train_model gets None.  Under USE_DDPG
+the rollouts go to the replay thread instead (ThreadReplay.py) and a trainer takes the batches of ring slots it samples.
 
 Zero-copy intake keeps a rollout's slot until the GPU has read its rows, which the reference's queue never does
 (training_q.get() frees the entry).  Two rules keep that from starving the agents of slots: only one trainer at a time
@@ -13,6 +14,7 @@ the agents have none left and nothing is queued SPILLS: it copies the rows it ho
 back and finishes that batch through the host-buffer path.  (Seen as a dead stop with TRAINING_MIN_BATCH_SIZE = 511,
 MAX_QUEUE_SIZE = 100 and two trainers.)
 """
+import queue
 from threading import Thread
 
 import numpy as np
@@ -40,7 +42,19 @@ class ThreadTrainer(Thread):
                 raise
             report("%s %d" % (type(self).__name__, self.id), e)
 
+    def _run_replay(self):
+        """USE_DDPG: ready batches come from the replay thread (ThreadTrainer.py:45-46 of the reference) as ring slots."""
+        while not self.exit_flag:
+            try:
+                slots, stamp = self.server.replay_q.get(timeout=Config.QUEUE_TIMEOUT_MS / 1000.0)
+            except queue.Empty:
+                continue
+            if Config.TRAIN_MODELS:
+                self.server.train_model_replay(slots, stamp, self.id)
+
     def _run(self):
+        if getattr(self.server, "ddpg", False):
+            return self._run_replay()
         t = self.transport
         cap = Config.TRAINING_MIN_BATCH_SIZE + t.train_rows
         state_dim = tuple(self.server.state_dim)

@@ -17,6 +17,8 @@ FLAG_LOG_SOFTMAX = 1
 FLAG_GRAD_CLIP = 2
 FLAG_DUAL_RMSPROP = 4
 FLAG_CONTINUOUS = 8
+DDPG_FUTURE_REWARD, DDPG_LOSS_PAIRED, DDPG_GRAD_CLIP, DDPG_CRITIC_ADAM, DDPG_OU_NOISE = 1, 2, 4, 8, 16
+DDPG_NOISE_OWN, DDPG_NOISE_GIVEN, DDPG_NOISE_NONE = 0, 1, 2
 
 f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)
@@ -37,6 +39,15 @@ class MlpConfig(C.Structure):     # include/ga3c_abi.h: ga3c_mlp_config
     _fields_ = [("device", C.c_int32), ("state_dim", C.c_int32), ("num_actions", C.c_int32), ("max_batch", C.c_int32),
                 ("flags", C.c_uint32), ("rmsprop_decay", C.c_float), ("rmsprop_momentum", C.c_float),
                 ("rmsprop_epsilon", C.c_float), ("grad_clip_norm", C.c_float), ("predict_lanes", C.c_int32)]
+
+
+class DdpgConfig(C.Structure):    # include/ga3c_abi.h: ga3c_ddpg_config
+    _fields_ = [("device", C.c_int32), ("state_dim", C.c_int32), ("num_actions", C.c_int32), ("max_batch", C.c_int32),
+                ("replay_capacity", C.c_int32), ("predict_lanes", C.c_int32), ("flags", C.c_uint32),
+                ("tau", C.c_float), ("gamma", C.c_float), ("actor_lr", C.c_float), ("critic_lr", C.c_float),
+                ("rmsprop_decay", C.c_float), ("rmsprop_momentum", C.c_float), ("rmsprop_epsilon", C.c_float),
+                ("grad_clip_norm", C.c_float), ("ou_sigma", C.c_float), ("ou_theta", C.c_float), ("ou_dt", C.c_float),
+                ("seed", C.c_int64)]
 
 
 class ShmConfig(C.Structure):
@@ -151,6 +162,36 @@ HIP_SIGNATURES = {
     "ga3c_mlp_upload": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32]),
     "ga3c_mlp_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
     "ga3c_mlp_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
+    # DDPG (USE_DDPG), include/ga3c_abi.h: ga3c_ddpg_*
+    "ga3c_ddpg_create": (C.c_int, [C.POINTER(DdpgConfig), C.POINTER(C.c_void_p)]),
+    "ga3c_ddpg_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_num_params": (C.c_int32, [C.c_void_p]),
+    "ga3c_ddpg_param_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
+    "ga3c_ddpg_target_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
+    "ga3c_ddpg_param_info": (C.c_int, [C.c_void_p, C.c_char_p, i64p, i32p, i64p, i32p]),
+    "ga3c_ddpg_get_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_ddpg_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_ddpg_get_step": (C.c_int, [C.c_void_p, i64p]),
+    "ga3c_ddpg_set_step": (C.c_int, [C.c_void_p, C.c_int64]),
+    "ga3c_ddpg_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "ga3c_ddpg_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "ga3c_ddpg_noise_step": (C.c_int, [C.c_void_p, f32p, f32p]),
+    "ga3c_ddpg_predict": (C.c_int, [C.c_void_p, f32p, C.c_int32, C.c_int32, f32p, f32p]),
+    "ga3c_ddpg_register_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "ga3c_ddpg_unregister_host": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_predict_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, f32p, f32p, f32p]),
+    "ga3c_ddpg_predict_gather_begin": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, i32p]),
+    "ga3c_ddpg_predict_gather_end": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f32p, f32p]),
+    "ga3c_ddpg_replay_add": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, f32p, C.c_int32, i64p, i64p]),
+    "ga3c_ddpg_replay_add_gather": (C.c_int, [C.c_void_p, i64p, f32p, f32p, C.c_int32, i64p, i64p]),
+    "ga3c_ddpg_replay_get": (C.c_int, [C.c_void_p, C.c_int64, f32p, f32p, f32p, f32p, f32p]),
+    "ga3c_ddpg_replay_size": (C.c_int, [C.c_void_p, i64p, i64p]),
+    "ga3c_ddpg_train": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, f32p, C.c_int32, C.c_float, C.c_int32, f32p, f32p]),
+    "ga3c_ddpg_train_replay": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int64, C.c_float, C.c_int32, f32p, f32p]),
+    "ga3c_ddpg_compute": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, f32p, C.c_int32, C.c_float, C.c_int32, f32p, C.c_int32,
+                                    f32p]),
+    "ga3c_ddpg_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
+    "ga3c_ddpg_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, f32p]),
 }
 
 HOST_SIGNATURES = {

@@ -1,0 +1,1520 @@
+// ga3c_ddpg.hip -- the DDPG networks of reference NetworkDDPG.py (USE_DDPG with CONTINUOUS_INPUT) on gfx950, their train
+// step (train_DDPG, :64-98), the replay memory of replay_buffer.py as a ring in HBM, and the C ABI ga3c_ddpg_*
+// (include/ga3c_abi.h).  DESIGN.md 8f.
+//
+//   actor   x[B,S] -> actor_fc1 (400) -> actor_norm1 -> relu -> actor_fc2 (300) -> actor_norm2 -> relu -> actor_output (A, tanh)
+//   critic  x -> critic_fc1 (400) -> critic_norm1 -> relu = h;  q = critic_output(relu(h W_fc2 + a W_n2 + b_n2))
+//   batch normalisation: gamma (x - moving_mean) / sqrt(moving_variance + 1e-5) + beta (bn_apply below, the one place)
+//
+// Kernels (all f32, one workgroup of 448 threads per 16-row tile, activations in LDS as [width][16], weights through L2):
+//   ddpg_target_kernel   steps 1-2: actor_target and critic_target on s2, y = r or r + gamma q'
+//   ddpg_critic_kernel   step 3's forward and backward on (s, a): q, dq (either loss form) and the deltas, to HBM
+//   ddpg_wgrad_kernel    one thread per element of a net's trainable variables sums its gradient over the rows in row order
+//                        (no atomics); FUSED applies the optimizer step and the soft update of the element's target copy
+//   ddpg_update_kernel   (GA3C_DDPG_GRAD_CLIP) one block per critic variable: tf.clip_by_norm, the step, the soft update
+//   ddpg_actor_kernel    steps 4-5: actor(s) + noise, dq/da of the updated critic there, the actor's deltas
+//   ddpg_predict_kernel  the online actor alone
+//   ddpg_ring_gather_kernel  rows of the registered transport into ring slots
+// A train step is 5 launches (6 with clipping); its rows are named by ring slot and read where they lie.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <condition_variable>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/ga3c_abi.h"
+#include "ga3c_checkpoint.hpp"
+
+void ga3c_set_last_error(const char* msg);   // ga3c_engine.hip: the thread's ga3c_last_error() message
+
+namespace ga3c_dd {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int TILE = 16;
+constexpr int THREADS = 448;                 // 7 waves: a 300-wide layer and the 400 rows of a backward pass take one pass each
+constexpr int RED = 512;                     // the power of two above it, for the fixed-order trees
+constexpr int MAX_S = 64;
+constexpr int MAX_A = 32;
+constexpr int H1 = 400;
+constexpr int H2 = 300;
+constexpr float BN_EPS = 1e-5f;
+// 1 - beta as the f32 nearest to the real number: 1.0f - 0.999f is off by 1.3e-5 of itself, which Adam's v would carry
+constexpr float ADAM_OMB1 = 0.1f, ADAM_OMB2 = 0.001f, ADAM_EPS = 1e-8f;
+constexpr double ADAM_B1 = 0.9, ADAM_B2 = 0.999;
+
+// Variables, arena order: the actor's trainable ones, the critic's, then the moving statistics.
+enum {
+  A_W1, A_B1, A_BE1, A_GA1, A_W2, A_B2, A_BE2, A_GA2, A_WO, A_BO,
+  C_W1, C_B1, C_BE1, C_GA1, C_W2, C_B2DEAD, C_WN, C_BN, C_WO, C_BO,
+  A_MM1, A_MV1, A_MM2, A_MV2, C_MM1, C_MV1, NVARS
+};
+constexpr int NTRAIN = 20;             // variables 0..19 are trainable
+constexpr int NACTOR = 10;             // ... 0..9 the actor's
+
+const char* const VAR_NAMES[NVARS] = {
+    "actor_fc1/W", "actor_fc1/b", "actor_norm1/beta", "actor_norm1/gamma", "actor_fc2/W", "actor_fc2/b", "actor_norm2/beta",
+    "actor_norm2/gamma", "actor_output/W", "actor_output/b",
+    "critic_fc1/W", "critic_fc1/b", "critic_norm1/beta", "critic_norm1/gamma", "critic_fc2/W", "critic_fc2/b", "critic_norm2/W",
+    "critic_norm2/b", "critic_output/W", "critic_output/b",
+    "actor_norm1/moving_mean", "actor_norm1/moving_variance", "actor_norm2/moving_mean", "actor_norm2/moving_variance",
+    "critic_norm1/moving_mean", "critic_norm1/moving_variance"};
+
+struct Layout {
+  int S, A;
+  int rows[NVARS], cols[NVARS];    // a vector has rows = 0
+  int64_t off[NVARS + 1];
+};
+
+inline Layout make_layout(int S, int A) {
+  Layout L;
+  L.S = S;
+  L.A = A;
+  const int r[NVARS] = {S, 0, 0, 0, H1, 0, 0, 0, H2, 0, S, 0, 0, 0, H1, 0, A, 0, H2, 0, 0, 0, 0, 0, 0, 0};
+  const int c[NVARS] = {H1, H1, H1, H1, H2, H2, H2, H2, A, A, H1, H1, H1, H1, H2, H2, H2, H2, 1, 1, H1, H1, H2, H2, H1, H1};
+  int64_t o = 0;
+  for (int v = 0; v < NVARS; ++v) {
+    L.rows[v] = r[v];
+    L.cols[v] = c[v];
+    L.off[v] = o;
+    o += (int64_t)(r[v] ? r[v] : 1) * c[v];
+  }
+  L.off[NVARS] = o;
+  return L;
+}
+
+// Where a step's rows lie: row i is `rowf` floats at base + (idx ? idx[i] : i) * rowf: s[S] | a[A] | r | done | s2[S].
+struct Rows {
+  const float* base;
+  const int32_t* idx;
+  int rowf;
+};
+
+struct Input {         // a prediction's row r: S floats at base + (off ? off[r] : r * stride) bytes
+  const char* base;
+  const int64_t* off;
+  int64_t stride;
+};
+
+struct Noise {         // by value in the kernel arguments: nothing to copy
+  float v[MAX_A];
+  int wrap;            // GA3C_DDPG_NOISE_NONE: check_bounds(turnaround) on the output
+};
+
+// Per-row buffers of the train workspace, row-major [B][width].
+struct Work {
+  float *y, *qt, *q, *dq;                      // [B]
+  float *c_x, *c_a;                            // [B,S] [B,A]: the critic step's inputs
+  float *c_xh1, *c_c1, *c_dn1, *c_dh1;         // [B,400]
+  float *c_c2, *c_dt;                          // [B,300]
+  float *a_xh1, *a_a1, *a_dn1, *a_dh1;         // [B,400]
+  float *a_xh2, *a_a2, *a_dn2, *a_dh2;         // [B,300]
+  float *a_out, *a_noisy, *g, *dout;           // [B,A]
+  float* qstat;                                // {max q, mean q}
+};
+
+struct Opt {
+  float *theta, *target, *sa, *sb, *grad;
+  int adam;                                    // 0: TF-1 ApplyRMSProp on (sa, sb) = (ms, mom); 1: ApplyAdam on (m, v)
+  float lr;                                    // RMSProp: the rate; Adam: lr sqrt(1 - b2^t) / (1 - b1^t)
+  float omr, mu, eps, clip, tau;
+  int apply, soft;
+};
+
+// out(j, r) = bias[j] + sum_k in[k][r] W[k][j] (+ sum_k in2[k][r] W2[k][j]); thread j owns column j.
+template <class EP>
+__device__ __forceinline__ void dense_fwd(const float* __restrict__ W, const float* __restrict__ bias, int K, int N, const float* in,
+                                          const float* __restrict__ W2, int K2, const float* in2, EP ep) {
+  for (int j = threadIdx.x; j < N; j += THREADS) {
+    float acc[TILE];
+    const float b = bias[j];
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) acc[r] = b;
+    for (int k = 0; k < K; ++k) {
+      const float w = W[(size_t)k * N + j];
+      const f32x4* col = reinterpret_cast<const f32x4*>(in + k * TILE);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 c = col[q];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
+      }
+    }
+    for (int k = 0; k < K2; ++k) {
+      const float w = W2[(size_t)k * N + j];
+      const f32x4* col = reinterpret_cast<const f32x4*>(in2 + k * TILE);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 c = col[q];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) ep(j, r, acc[r]);
+  }
+  __syncthreads();
+}
+
+// ep(k, r, sum_j W[k][j] gout[j][r]) for k < K; thread k owns row k of W and sums in j order.
+template <class EP>
+__device__ __forceinline__ void dense_bwd(const float* __restrict__ W, int K, int N, const float* gout, EP ep) {
+  for (int k = threadIdx.x; k < K; k += THREADS) {
+    float acc[TILE];
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) acc[r] = 0.f;
+    const float* __restrict__ wr = W + (size_t)k * N;
+    for (int j = 0; j < N; ++j) {
+      const float w = wr[j];
+      const f32x4* col = reinterpret_cast<const f32x4*>(gout + j * TILE);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 c = col[q];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) ep(k, r, acc[r]);
+  }
+  __syncthreads();
+}
+
+// The reference's batch normalisation (tflearn with its training flag off): -> the normalised value; *n = gamma xhat + beta.
+__device__ __forceinline__ float bn_apply(const float* th, const Layout& L, int mm, int mv, int be, int ga, int j, float h, float* n) {
+  const float rstd = 1.0f / sqrtf(th[L.off[mv] + j] + BN_EPS);
+  const float xh = (h - th[L.off[mm] + j]) * rstd;
+  *n = th[L.off[ga] + j] * xh + th[L.off[be] + j];
+  return xh;
+}
+__device__ __forceinline__ float bn_scale(const float* th, const Layout& L, int mv, int ga, int j) {
+  return th[L.off[ga] + j] / sqrtf(th[L.off[mv] + j] + BN_EPS);
+}
+
+struct ActorKeep { float *xh1, *a1, *xh2, *a2, *out; };    // all null: nothing kept
+struct CriticKeep { float *xh1, *c1, *c2; };
+
+// xin [S][16] -> bufA = a1 [400][16], bufB = a2 [300][16], act = tanh output [A][16]
+// dact (may be null): 1 - tanh^2 = 4 e / (1 + e)^2 with e = exp(-2 |h|), from h itself: 1 - o * o loses what tanh rounds away
+__device__ void actor_fwd(const Layout& L, const float* __restrict__ th, const float* xin, float* bufA, float* bufB, float* act,
+                          float* dact, ActorKeep kp, int row0, int nrows) {
+  dense_fwd(th + L.off[A_W1], th + L.off[A_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
+    float n;
+    const float xh = bn_apply(th, L, A_MM1, A_MV1, A_BE1, A_GA1, j, h, &n);
+    const float a = fmaxf(n, 0.f);
+    bufA[j * TILE + r] = a;
+    if (kp.a1 && r < nrows) {
+      kp.xh1[(size_t)(row0 + r) * H1 + j] = xh;
+      kp.a1[(size_t)(row0 + r) * H1 + j] = a;
+    }
+  });
+  dense_fwd(th + L.off[A_W2], th + L.off[A_B2], H1, H2, bufA, nullptr, 0, nullptr, [&](int j, int r, float h) {
+    float n;
+    const float xh = bn_apply(th, L, A_MM2, A_MV2, A_BE2, A_GA2, j, h, &n);
+    const float a = fmaxf(n, 0.f);
+    bufB[j * TILE + r] = a;
+    if (kp.a2 && r < nrows) {
+      kp.xh2[(size_t)(row0 + r) * H2 + j] = xh;
+      kp.a2[(size_t)(row0 + r) * H2 + j] = a;
+    }
+  });
+  const int A = L.A;
+  dense_fwd(th + L.off[A_WO], th + L.off[A_BO], H2, A, bufB, nullptr, 0, nullptr, [&](int j, int r, float h) {
+    const float o = tanhf(h);
+    act[j * TILE + r] = o;
+    if (dact) {
+      const float e = expf(-2.0f * fabsf(h));
+      dact[j * TILE + r] = 4.0f * e / ((1.0f + e) * (1.0f + e));
+    }
+    if (kp.out && r < nrows) kp.out[(size_t)(row0 + r) * A + j] = o;
+  });
+}
+
+// xin [S][16], act [A][16] -> bufA = c1 [400][16], bufB = c2 [300][16], qv[16] (LDS)
+__device__ void critic_fwd(const Layout& L, const float* __restrict__ th, const float* xin, const float* act, float* bufA,
+                           float* bufB, float* qv, CriticKeep kp, int row0, int nrows) {
+  dense_fwd(th + L.off[C_W1], th + L.off[C_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
+    float n;
+    const float xh = bn_apply(th, L, C_MM1, C_MV1, C_BE1, C_GA1, j, h, &n);
+    const float c = fmaxf(n, 0.f);
+    bufA[j * TILE + r] = c;
+    if (kp.c1 && r < nrows) {
+      kp.xh1[(size_t)(row0 + r) * H1 + j] = xh;
+      kp.c1[(size_t)(row0 + r) * H1 + j] = c;
+    }
+  });
+  dense_fwd(th + L.off[C_W2], th + L.off[C_BN], H1, H2, bufA, th + L.off[C_WN], L.A, act, [&](int j, int r, float h) {
+    const float c = fmaxf(h, 0.f);
+    bufB[j * TILE + r] = c;
+    if (kp.c2 && r < nrows) kp.c2[(size_t)(row0 + r) * H2 + j] = c;
+  });
+  // q: one thread per row, in j order
+  if (threadIdx.x < TILE) {
+    const int r = threadIdx.x;
+    const float* __restrict__ wo = th + L.off[C_WO];
+    float s = th[L.off[C_BO]];
+    for (int j = 0; j < H2; ++j) s = fmaf(bufB[j * TILE + r], wo[j], s);
+    qv[r] = s;
+  }
+  __syncthreads();
+}
+
+// Loads `width` floats at column offset `col` of the tile's rows into dst [width][16] (zeros beyond nrows).
+__device__ __forceinline__ void load_rows(const Rows& src, int col, int width, float* dst, int row0, int nrows, float* keep) {
+  for (int e = threadIdx.x; e < width * TILE; e += THREADS) {
+    const int r = e / width, c = e % width;
+    float v = 0.f;
+    if (r < nrows) {
+      const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
+      v = src.base[slot * src.rowf + col + c];
+      if (keep) keep[(size_t)(row0 + r) * width + c] = v;
+    }
+    dst[c * TILE + r] = v;
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_target_kernel(Layout L, const float* __restrict__ thT, Rows src, int B, float gamma,
+                                                              int future, Work w) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  __shared__ float qv[TILE];
+  const int S = L.S, A = L.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  if (future) {
+    load_rows(src, S + A + 2, S, xin, row0, nrows, nullptr);
+    __syncthreads();
+    actor_fwd(L, thT, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    critic_fwd(L, thT, xin, act, bufA, bufB, qv, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+  }
+  if (threadIdx.x < nrows) {
+    const int r = threadIdx.x;
+    const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
+    const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
+    float y = rew, qt = 0.f;
+    if (future) {
+      qt = qv[r];
+      if (done == 0.f) y = fmaf(gamma, qt, rew);
+    }
+    w.y[row0 + r] = y;
+    w.qt[row0 + r] = qt;
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const float* __restrict__ th, Rows src, int B, int paired,
+                                                              Work w) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  __shared__ float qv[TILE];
+  __shared__ float dqv[TILE];
+  __shared__ float red[RED];
+  const int S = L.S, A = L.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  // mean(y), the same fixed order in every block: strided partials, then a tree
+  {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B; i += THREADS) s += w.y[i];
+    red[threadIdx.x] = s;
+    if (threadIdx.x + THREADS < RED) red[threadIdx.x + THREADS] = 0.f;
+    __syncthreads();
+    for (int h = RED / 2; h > 0; h >>= 1) {
+      if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+      __syncthreads();
+    }
+  }
+  const float ymean = red[0] / (float)B;
+  load_rows(src, 0, S, xin, row0, nrows, w.c_x);
+  load_rows(src, S, A, act, row0, nrows, w.c_a);
+  __syncthreads();
+  critic_fwd(L, th, xin, act, bufA, bufB, qv, CriticKeep{w.c_xh1, w.c_c1, w.c_c2}, row0, nrows);
+  if (threadIdx.x < TILE) {
+    const int r = threadIdx.x;
+    float dq = 0.f;
+    if (r < nrows) {
+      const float ref = paired ? w.y[row0 + r] : ymean;
+      dq = (2.0f / (float)B) * (qv[r] - ref);
+      w.q[row0 + r] = qv[r];
+      w.dq[row0 + r] = dq;
+    }
+    dqv[r] = dq;
+  }
+  __syncthreads();
+  // delta at t = h W_fc2 + a W_n2 + b_n2, in place over c2
+  const float* __restrict__ wo = th + L.off[C_WO];
+  for (int e = threadIdx.x; e < H2 * TILE; e += THREADS) {
+    const int j = e / TILE, r = e % TILE;
+    const float d = bufB[e] > 0.f ? dqv[r] * wo[j] : 0.f;
+    bufB[e] = d;
+    if (r < nrows) w.c_dt[(size_t)(row0 + r) * H2 + j] = d;
+  }
+  __syncthreads();
+  // delta at critic_norm1's output (in place over c1: thread k reads and writes row k alone) and at critic_fc1's
+  dense_bwd(th + L.off[C_W2], H1, H2, bufB, [&](int k, int r, float s) {
+    const float d = bufA[k * TILE + r] > 0.f ? s : 0.f;
+    bufA[k * TILE + r] = d;
+    if (r < nrows) {
+      w.c_dn1[(size_t)(row0 + r) * H1 + k] = d;
+      w.c_dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, L, C_MV1, C_GA1, k);
+    }
+  });
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const float* __restrict__ th, Rows src, int B, Noise nz,
+                                                             Work w) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];      // tanh output
+  __shared__ __attribute__((aligned(16))) float noisy[MAX_A * TILE];    // + noise; later the delta at the output's pre-activation
+  __shared__ __attribute__((aligned(16))) float dact[MAX_A * TILE];     // 1 - tanh^2
+  __shared__ float qv[TILE];
+  const int S = L.S, A = L.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  load_rows(src, 0, S, xin, row0, nrows, nullptr);
+  __syncthreads();
+  actor_fwd(L, th, xin, bufA, bufB, act, dact, ActorKeep{w.a_xh1, w.a_a1, w.a_xh2, w.a_a2, w.a_out}, row0, nrows);
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const int i = e / TILE, r = e % TILE;
+    float v = act[e] + nz.v[i];
+    if (nz.wrap) {
+      if (v < -1.f) v = 1.f - fmodf(-1.f - v, 2.f);
+      else if (v > 1.f) v = fmodf(v - 1.f, 2.f) - 1.f;
+    }
+    noisy[e] = v;
+    if (r < nrows) w.a_noisy[(size_t)(row0 + r) * A + i] = v;
+  }
+  __syncthreads();
+  // the updated critic at (s, a_out); only the relu mask of t is needed for dq/da
+  critic_fwd(L, th, xin, noisy, bufA, bufB, qv, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+  const float* __restrict__ wo = th + L.off[C_WO];
+  for (int e = threadIdx.x; e < H2 * TILE; e += THREADS) bufB[e] = bufB[e] > 0.f ? wo[e / TILE] : 0.f;
+  __syncthreads();
+  // g = dq/da (per row, no 1/B); the delta at actor_output's pre-activation is -g (1 - out^2)
+  dense_bwd(th + L.off[C_WN], A, H2, bufB, [&](int i, int r, float g) {
+    const float d = -g * dact[i * TILE + r];
+    noisy[i * TILE + r] = r < nrows ? d : 0.f;
+    if (r < nrows) {
+      w.g[(size_t)(row0 + r) * A + i] = g;
+      w.dout[(size_t)(row0 + r) * A + i] = d;
+    }
+  });
+  // back through actor_norm2 / actor_fc2: the relu masks come from the rows this block stored above
+  dense_bwd(th + L.off[A_WO], H2, A, noisy, [&](int k, int r, float s) {
+    float d = 0.f;
+    if (r < nrows) {
+      d = w.a_a2[(size_t)(row0 + r) * H2 + k] > 0.f ? s : 0.f;
+      w.a_dn2[(size_t)(row0 + r) * H2 + k] = d;
+    }
+    const float dh = d * bn_scale(th, L, A_MV2, A_GA2, k);
+    bufB[k * TILE + r] = dh;
+    if (r < nrows) w.a_dh2[(size_t)(row0 + r) * H2 + k] = dh;
+  });
+  dense_bwd(th + L.off[A_W2], H1, H2, bufB, [&](int k, int r, float s) {
+    if (r < nrows) {
+      const float d = w.a_a1[(size_t)(row0 + r) * H1 + k] > 0.f ? s : 0.f;
+      w.a_dn1[(size_t)(row0 + r) * H1 + k] = d;
+      w.a_dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, L, A_MV1, A_GA1, k);
+    }
+  });
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_predict_kernel(Layout L, const float* __restrict__ th, Input in, int B, Noise nz,
+                                                               float* __restrict__ a_out) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  const int S = L.S, A = L.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  for (int e = threadIdx.x; e < S * TILE; e += THREADS) {
+    const int r = e / S, s = e % S;
+    float xv = 0.f;
+    if (r < nrows) {
+      const int64_t ob = in.off ? in.off[row0 + r] : (int64_t)(row0 + r) * in.stride;
+      xv = reinterpret_cast<const float*>(in.base + ob)[s];
+    }
+    xin[s * TILE + r] = xv;
+  }
+  __syncthreads();
+  actor_fwd(L, th, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const int i = e / TILE, r = e % TILE;
+    float v = act[e] + nz.v[i];
+    if (nz.wrap) {
+      if (v < -1.f) v = 1.f - fmodf(-1.f - v, 2.f);
+      else if (v > 1.f) v = fmodf(v - 1.f, 2.f) - 1.f;
+    }
+    if (r < nrows) a_out[(size_t)(row0 + r) * A + i] = v;
+  }
+}
+
+// The gradient of variable v's element: sum over rows of in[r][k] d[r][j] (in null: of d[r][j]; mul: times mul[r][j]).
+struct GradSrc {
+  const float* in[NTRAIN];
+  const float* d[NTRAIN];
+  const float* mul[NTRAIN];
+  int ld_in[NTRAIN], ld_d[NTRAIN];
+};
+
+__device__ __forceinline__ void opt_step(const Opt& o, int64_t i, float g) {
+  if (o.adam) {
+    float m = o.sa[i], v = o.sb[i];
+    m += (g - m) * ADAM_OMB1;
+    v += (g * g - v) * ADAM_OMB2;
+    o.sa[i] = m;
+    o.sb[i] = v;
+    o.theta[i] -= o.lr * m / (sqrtf(v) + ADAM_EPS);
+  } else {
+    float m = o.sa[i];
+    m += (g * g - m) * o.omr;
+    o.sa[i] = m;
+    const float step = o.sb[i] * o.mu + (g * o.lr) / sqrtf(o.eps + m);
+    o.sb[i] = step;
+    o.theta[i] -= step;
+  }
+}
+
+__device__ __forceinline__ void soft_step(const Opt& o, int64_t i) {
+  o.target[i] = o.tau * o.theta[i] + (1.0f - o.tau) * o.target[i];
+}
+
+// Variables v0 .. v1-1 (one net's trainable ones).  FUSED: + the optimizer step (o.apply) and the soft update (o.soft).
+// The critic's launch also leaves {max q, mean q}, summed in row order by one thread.
+template <bool FUSED>
+__global__ __launch_bounds__(THREADS) void ddpg_wgrad_kernel(Layout L, GradSrc src, int v0, int v1, int B, Opt o, Work w) {
+  const int64_t e = L.off[v0] + (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (e < L.off[v1]) {
+    int v = v1 - 1;
+    while (e < L.off[v]) --v;
+    if (v != C_B2DEAD) {
+      const int64_t loc = e - L.off[v];
+      const int N = L.cols[v];
+      const int k = (int)(loc / N), j = (int)(loc % N);
+      const float* __restrict__ d = src.d[v];
+      const float* __restrict__ x = src.in[v];
+      const float* __restrict__ mul = src.mul[v];
+      const int ld = src.ld_d[v], li = src.ld_in[v];
+      float g = 0.f;
+      if (x) {
+        for (int r = 0; r < B; ++r) g = fmaf(x[(size_t)r * li + k], d[(size_t)r * ld + j], g);
+      } else if (mul) {
+        for (int r = 0; r < B; ++r) g = fmaf(mul[(size_t)r * ld + j], d[(size_t)r * ld + j], g);
+      } else {
+        for (int r = 0; r < B; ++r) g += d[(size_t)r * ld + j];
+      }
+      o.grad[e] = g;
+      if (FUSED && o.apply) opt_step(o, e, g);
+    }
+    if (FUSED && o.soft) soft_step(o, e);
+  }
+  if (v0 == NACTOR && blockIdx.x == 0 && threadIdx.x == 0) {
+    float mx = w.q[0], s = 0.f;
+    for (int r = 0; r < B; ++r) {
+      const float q = w.q[r];
+      mx = fmaxf(mx, q);
+      s += q;
+    }
+    w.qstat[0] = mx;
+    w.qstat[1] = s / (float)B;
+  }
+}
+
+// One block per variable v0 + blockIdx.x: tf.clip_by_norm (g clip / max(||g||, clip)), the step, the soft update.
+__global__ __launch_bounds__(THREADS) void ddpg_update_kernel(Layout L, int v0, Opt o) {
+  __shared__ float sh[RED];
+  const int v = v0 + blockIdx.x;
+  const int64_t lo = L.off[v], hi = L.off[v + 1];
+  const bool dead = v == C_B2DEAD;
+  float s = 0.f;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) s += o.grad[i] * o.grad[i];
+  sh[threadIdx.x] = s;
+  if (threadIdx.x + THREADS < RED) sh[threadIdx.x + THREADS] = 0.f;
+  __syncthreads();
+  for (int h = RED / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+    __syncthreads();
+  }
+  const float scale = o.clip / fmaxf(sqrtf(sh[0]), o.clip);
+  for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+    if (!dead && o.apply) opt_step(o, i, o.grad[i] * scale);
+    if (o.soft) soft_step(o, i);
+  }
+}
+
+// Ring slot (first + i) mod cap <- s | a | r | done | s2, from row `s[S] | s2[S] | done` of the transport and the staged r, a.
+__global__ void ddpg_ring_gather_kernel(const char* __restrict__ seg, const int64_t* __restrict__ off, const float* __restrict__ r,
+                                        const float* __restrict__ a, int n, float* __restrict__ ring, int64_t first, int64_t cap,
+                                        int S, int A) {
+  const int rowf = 2 * S + A + 2;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)n * rowf) return;
+  const int i = (int)(e / rowf), c = (int)(e % rowf);
+  const float* __restrict__ row = reinterpret_cast<const float*>(seg + off[i]);
+  float v;
+  if (c < S) v = row[c];
+  else if (c < S + A) v = a[(size_t)i * A + c - S];
+  else if (c == S + A) v = r[i];
+  else if (c == S + A + 1) v = row[2 * S];
+  else v = row[S + c - (S + A + 2)];
+  ring[((first + i) % cap) * rowf + c] = v;
+}
+
+// ------------------------------------------------------------------ host side
+
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  ga3c_set_last_error(buf);
+  return code;
+}
+
+#define HIPCHK(expr)                                                                                  \
+  do {                                                                                                \
+    hipError_t _e = (expr);                                                                           \
+    if (_e != hipSuccess) {                                                                           \
+      (void)hipGetLastError();                                                                        \
+      return fail(GA3C_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    }                                                                                                 \
+  } while (0)
+#define CHK(expr)                 \
+  do {                            \
+    int _r = (expr);              \
+    if (_r != GA3C_OK) return _r; \
+  } while (0)
+
+struct PLane {
+  int64_t* h_off = nullptr; float* h_x = nullptr; float* h_a = nullptr;
+  int64_t* d_off = nullptr; float* d_x = nullptr; float* d_a = nullptr;
+  hipEvent_t ev = nullptr;
+  bool busy = false;
+  int B = 0;
+};
+
+// The handle's normal generator: xoshiro256** seeded through splitmix64, Box-Muller on two uniforms per draw.
+struct NormalGen {
+  uint64_t s[4];
+  void seed(uint64_t x) {
+    for (int i = 0; i < 4; ++i) {
+      x += 0x9E3779B97F4A7C15ull;
+      uint64_t z = x;
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      s[i] = z ^ (z >> 31);
+    }
+  }
+  static uint64_t rotl(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
+  uint64_t next() {
+    const uint64_t r = rotl(s[1] * 5, 7) * 9, t = s[1] << 17;
+    s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t; s[3] = rotl(s[3], 45);
+    return r;
+  }
+  double uniform() { return ((double)(next() >> 11) + 0.5) * (1.0 / 9007199254740992.0); }   // (0, 1)
+  double normal() {
+    const double u1 = uniform(), u2 = uniform();
+    return std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2);
+  }
+};
+
+}  // namespace ga3c_dd
+
+using namespace ga3c_dd;
+
+struct ga3c_ddpg {
+  ga3c_ddpg_config cfg;
+  Layout L;
+  int64_t n = 0;
+  int rowf = 0;
+  hipStream_t st = nullptr;       // every kernel and copy of the handle
+  std::mutex mu;                  // enqueue order on `st`, the lanes' and the ring's bookkeeping
+  std::condition_variable lane_cv;
+  std::mutex train_mu;            // one train-type / variable call at a time (they share the staging below)
+  std::mutex add_mu;              // one replay_add at a time (its own staging)
+  std::mutex noise_mu;
+  std::vector<PLane> lanes;
+  float* arena[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // value, target, slot a, slot b, gradient
+  Work w{};
+  float* work_base = nullptr;
+  float* ring = nullptr;
+  int64_t ring_total = 0;         // rows ever added; row t lies in slot t mod capacity
+  float* h_stage = nullptr; float* d_stage = nullptr;     // train(): B rows in ring layout
+  int32_t* h_idx = nullptr; int32_t* d_idx = nullptr;
+  float* h_q = nullptr;
+  float* h_add = nullptr;                                  // replay_add: rows in ring layout
+  int64_t* h_aoff = nullptr; int64_t* d_aoff = nullptr; float* h_ar = nullptr; float* d_ar = nullptr;
+  float* h_aa = nullptr; float* d_aa = nullptr;
+  hipEvent_t tev = nullptr, aev = nullptr, t0 = nullptr, t1 = nullptr;
+  int last_B = 0;
+  std::atomic<int64_t> step{0};
+  NormalGen gen;
+  std::vector<float> ou_x;
+  const char* reg_host = nullptr;
+  const char* reg_dev = nullptr;
+  int64_t reg_bytes = 0;
+};
+
+namespace {
+
+int tiles(int B) { return (B + TILE - 1) / TILE; }
+
+const char* const WORK_NAMES[] = {"y", "qt", "q", "dq", "c_x", "c_a", "c_xh1", "c_c1", "c_dn1", "c_dh1", "c_c2", "c_dt",
+                                  "a_xh1", "a_a1", "a_dn1", "a_dh1", "a_xh2", "a_a2", "a_dn2", "a_dh2", "a_out", "a_noisy", "g", "do"};
+constexpr int NWORK = sizeof(WORK_NAMES) / sizeof(WORK_NAMES[0]);
+
+void work_table(ga3c_ddpg* m, float*** ptrs, int* widths) {
+  const int S = m->L.S, A = m->L.A;
+  Work& w = m->w;
+  float** p[NWORK] = {&w.y, &w.qt, &w.q, &w.dq, &w.c_x, &w.c_a, &w.c_xh1, &w.c_c1, &w.c_dn1, &w.c_dh1, &w.c_c2, &w.c_dt,
+                      &w.a_xh1, &w.a_a1, &w.a_dn1, &w.a_dh1, &w.a_xh2, &w.a_a2, &w.a_dn2, &w.a_dh2, &w.a_out, &w.a_noisy, &w.g,
+                      &w.dout};
+  const int wd[NWORK] = {1, 1, 1, 1, S, A, H1, H1, H1, H1, H2, H2, H1, H1, H1, H1, H2, H2, H2, H2, A, A, A, A};
+  for (int i = 0; i < NWORK; ++i) {
+    ptrs[i] = p[i];
+    widths[i] = wd[i];
+  }
+}
+
+GradSrc grad_src(ga3c_ddpg* m) {
+  GradSrc g;
+  const Work& w = m->w;
+  const int S = m->L.S, A = m->L.A;
+  for (int v = 0; v < NTRAIN; ++v) {
+    g.in[v] = g.d[v] = g.mul[v] = nullptr;
+    g.ld_in[v] = g.ld_d[v] = 0;
+  }
+  auto set = [&](int v, const float* in, int li, const float* d, int ld, const float* mul) {
+    g.in[v] = in; g.ld_in[v] = li; g.d[v] = d; g.ld_d[v] = ld; g.mul[v] = mul;
+  };
+  set(A_W1, w.c_x, S, w.a_dh1, H1, nullptr);       // the actor step reads the same states the critic step stored
+  set(A_B1, nullptr, 0, w.a_dh1, H1, nullptr);
+  set(A_BE1, nullptr, 0, w.a_dn1, H1, nullptr);
+  set(A_GA1, nullptr, 0, w.a_dn1, H1, w.a_xh1);
+  set(A_W2, w.a_a1, H1, w.a_dh2, H2, nullptr);
+  set(A_B2, nullptr, 0, w.a_dh2, H2, nullptr);
+  set(A_BE2, nullptr, 0, w.a_dn2, H2, nullptr);
+  set(A_GA2, nullptr, 0, w.a_dn2, H2, w.a_xh2);
+  set(A_WO, w.a_a2, H2, w.dout, A, nullptr);
+  set(A_BO, nullptr, 0, w.dout, A, nullptr);
+  set(C_W1, w.c_x, S, w.c_dh1, H1, nullptr);
+  set(C_B1, nullptr, 0, w.c_dh1, H1, nullptr);
+  set(C_BE1, nullptr, 0, w.c_dn1, H1, nullptr);
+  set(C_GA1, nullptr, 0, w.c_dn1, H1, w.c_xh1);
+  set(C_W2, w.c_c1, H1, w.c_dt, H2, nullptr);
+  set(C_WN, w.c_a, A, w.c_dt, H2, nullptr);
+  set(C_BN, nullptr, 0, w.c_dt, H2, nullptr);
+  set(C_WO, w.c_c2, H2, w.dq, 1, nullptr);
+  set(C_BO, nullptr, 0, w.dq, 1, nullptr);
+  return g;
+}
+
+Opt make_opt(ga3c_ddpg* m, bool actor, float lr, int64_t t, bool apply, bool soft) {
+  Opt o;
+  o.theta = m->arena[0]; o.target = m->arena[1]; o.sa = m->arena[2]; o.sb = m->arena[3]; o.grad = m->arena[4];
+  const ga3c_ddpg_config& c = m->cfg;
+  o.adam = actor || (c.flags & GA3C_DDPG_CRITIC_ADAM) ? 1 : 0;
+  const double rate = (double)(actor ? c.actor_lr : c.critic_lr) * (double)lr;
+  if (o.adam) o.lr = (float)(rate * std::sqrt(1.0 - std::pow(ADAM_B2, (double)t)) / (1.0 - std::pow(ADAM_B1, (double)t)));
+  else o.lr = (float)rate;
+  o.omr = 1.0f - c.rmsprop_decay;
+  o.mu = c.rmsprop_momentum;
+  o.eps = c.rmsprop_epsilon;
+  o.clip = c.grad_clip_norm;
+  o.tau = c.tau;
+  o.apply = apply ? 1 : 0;
+  o.soft = soft ? 1 : 0;
+  return o;
+}
+
+int check_batch(ga3c_ddpg* m, int B) {
+  if (B < 1 || B > m->cfg.max_batch) return fail(GA3C_EINVAL, "batch %d outside [1,%d]", B, m->cfg.max_batch);
+  return GA3C_OK;
+}
+
+// offsets of rows in the registered segment: each must hold `floats` whole floats inside it
+int check_offsets(ga3c_ddpg* m, const int64_t* off, int B, int floats) {
+  if (!m->reg_dev) return fail(GA3C_ESTATE, "no host segment registered");
+  const int64_t row = 4 * (int64_t)floats;
+  for (int i = 0; i < B; ++i)
+    if (off[i] < 0 || off[i] % 4 != 0 || off[i] > m->reg_bytes - row)
+      return fail(GA3C_EINVAL, "offset %lld of row %d is not a 4-byte aligned row of %lld bytes inside the %lld-byte segment",
+                  (long long)off[i], i, (long long)row, (long long)m->reg_bytes);
+  return GA3C_OK;
+}
+
+// The noise a predict / step 4 adds: the handle's own OU step, the caller's vector, or none.
+int make_noise(ga3c_ddpg* m, int mode, const float* given, Noise* nz) {
+  const int A = m->L.A;
+  memset(nz, 0, sizeof *nz);
+  if (mode == GA3C_DDPG_NOISE_GIVEN) {
+    if (!given) return fail(GA3C_EINVAL, "GA3C_DDPG_NOISE_GIVEN without a noise vector");
+    memcpy(nz->v, given, sizeof(float) * A);
+  } else if (mode == GA3C_DDPG_NOISE_OWN) {
+    if (m->cfg.flags & GA3C_DDPG_OU_NOISE) CHK(ga3c_ddpg_noise_step(m, nz->v, nullptr));
+    else nz->wrap = 1;
+  } else if (mode == GA3C_DDPG_NOISE_NONE) {
+    nz->wrap = 1;
+  } else {
+    return fail(GA3C_EINVAL, "noise_mode %d not in [0,2]", mode);
+  }
+  return GA3C_OK;
+}
+
+// Steps 1 .. stop_after of train_DDPG on `rows` (caller holds train_mu and mu).  stop_after 6: the whole step.
+int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after) {
+  const ga3c_ddpg_config& c = m->cfg;
+  const int64_t t = m->step.load() + 1;
+  const bool full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
+  const dim3 grid(tiles(B)), block(THREADS);
+  hipLaunchKernelGGL(ddpg_target_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[1], rows, B, c.gamma,
+                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, m->w);
+  hipLaunchKernelGGL(ddpg_critic_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B,
+                     (c.flags & GA3C_DDPG_LOSS_PAIRED) ? 1 : 0, m->w);
+  const GradSrc gs = grad_src(m);
+  const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
+  const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
+  const Opt oc = make_opt(m, false, lr, t, true, full);
+  if (clip) {
+    hipLaunchKernelGGL(ddpg_wgrad_kernel<false>, dim3(cblocks), block, 0, m->st, m->L, gs, NACTOR, NTRAIN, B, oc, m->w);
+    hipLaunchKernelGGL(ddpg_update_kernel, dim3(NTRAIN - NACTOR), block, 0, m->st, m->L, NACTOR, oc);
+  } else {
+    hipLaunchKernelGGL(ddpg_wgrad_kernel<true>, dim3(cblocks), block, 0, m->st, m->L, gs, NACTOR, NTRAIN, B, oc, m->w);
+  }
+  if (stop_after >= 4) {
+    hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, m->w);
+    const Opt oa = make_opt(m, true, lr, t, full, full);
+    hipLaunchKernelGGL(ddpg_wgrad_kernel<true>, dim3(ablocks), block, 0, m->st, m->L, gs, 0, NACTOR, B, oa, m->w);
+  }
+  HIPCHK(hipGetLastError());
+  return GA3C_OK;
+}
+
+int finish_step(ga3c_ddpg* m) {
+  HIPCHK(hipMemcpyAsync(m->h_q, m->w.qstat, 2 * sizeof(float), hipMemcpyDeviceToHost, m->st));
+  HIPCHK(hipEventRecord(m->tev, m->st));
+  return GA3C_OK;
+}
+
+// train / compute on host rows: staged in ring layout, then the same kernels as train_replay
+int step_host(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2, int B, float lr,
+              int mode, const float* noise, int stop_after, float* q_stats) {
+  if (!m || !s || !a || !r || !done || !s2) return fail(GA3C_EINVAL, "null argument");
+  CHK(check_batch(m, B));
+  if (stop_after != 3 && stop_after != 4 && stop_after != 6) return fail(GA3C_EINVAL, "stop_after %d not in {3, 4}", stop_after);
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  Noise nz;
+  CHK(make_noise(m, mode, noise, &nz));
+  const int S = m->L.S, A = m->L.A, rowf = m->rowf;
+  for (int i = 0; i < B; ++i) {
+    float* row = m->h_stage + (size_t)i * rowf;
+    memcpy(row, s + (size_t)i * S, sizeof(float) * S);
+    memcpy(row + S, a + (size_t)i * A, sizeof(float) * A);
+    row[S + A] = r[i];
+    row[S + A + 1] = done[i] != 0.f ? 1.f : 0.f;
+    memcpy(row + S + A + 2, s2 + (size_t)i * S, sizeof(float) * S);
+  }
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipMemcpyAsync(m->d_stage, m->h_stage, sizeof(float) * B * rowf, hipMemcpyHostToDevice, m->st));
+    CHK(enqueue_step(m, Rows{m->d_stage, nullptr, rowf}, B, lr, nz, stop_after));
+    CHK(finish_step(m));
+    m->last_B = B;
+  }
+  HIPCHK(hipEventSynchronize(m->tev));
+  if (q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  if (stop_after >= 6) m->step.fetch_add(1);
+  return GA3C_OK;
+}
+
+PLane* take_lane(ga3c_ddpg* m, std::unique_lock<std::mutex>& lk, int* ticket) {
+  for (;;) {
+    for (size_t i = 0; i < m->lanes.size(); ++i)
+      if (!m->lanes[i].busy) {
+        m->lanes[i].busy = true;
+        *ticket = (int)i;
+        return &m->lanes[i];
+      }
+    m->lane_cv.wait(lk);
+  }
+}
+
+void give_lane(ga3c_ddpg* m, PLane* P) {
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    P->busy = false;
+  }
+  m->lane_cv.notify_one();
+}
+
+int predict_begin(ga3c_ddpg* m, const float* x, const int64_t* off, int B, int mode, const float* noise, int* ticket) {
+  CHK(check_batch(m, B));
+  HIPCHK(hipSetDevice(m->cfg.device));
+  if (off) CHK(check_offsets(m, off, B, m->L.S));
+  Noise nz;
+  CHK(make_noise(m, mode, noise, &nz));        // one step of the process per call, whatever the batch (:242-251)
+  std::unique_lock<std::mutex> lk(m->mu);
+  PLane* P = take_lane(m, lk, ticket);
+  const int S = m->L.S, A = m->L.A;
+  Input in;
+  hipError_t e = hipSuccess;
+  if (off) {
+    memcpy(P->h_off, off, sizeof(int64_t) * B);
+    e = hipMemcpyAsync(P->d_off, P->h_off, sizeof(int64_t) * B, hipMemcpyHostToDevice, m->st);
+    in = Input{m->reg_dev, P->d_off, 0};
+  } else {
+    memcpy(P->h_x, x, sizeof(float) * B * S);
+    e = hipMemcpyAsync(P->d_x, P->h_x, sizeof(float) * B * S, hipMemcpyHostToDevice, m->st);
+    in = Input{reinterpret_cast<const char*>(P->d_x), nullptr, 4 * (int64_t)S};
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(B)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in, B, nz,
+                       P->d_a);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(P->h_a, P->d_a, sizeof(float) * B * A, hipMemcpyDeviceToHost, m->st);
+  if (e == hipSuccess) e = hipEventRecord(P->ev, m->st);
+  if (e != hipSuccess) {
+    P->busy = false;
+    lk.unlock();
+    m->lane_cv.notify_one();
+    (void)hipGetLastError();
+    return fail(GA3C_EHIP, "prediction enqueue failed: %s", hipGetErrorString(e));
+  }
+  P->B = B;
+  return GA3C_OK;
+}
+
+int predict_end(ga3c_ddpg* m, int ticket, int B, float* a, float* v) {
+  if (ticket < 0 || ticket >= (int)m->lanes.size()) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
+  PLane* P = &m->lanes[ticket];
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!P->busy) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
+  }
+  const hipError_t e = hipEventSynchronize(P->ev);
+  if (e == hipSuccess && B != P->B) {
+    give_lane(m, P);
+    return fail(GA3C_EINVAL, "batch %d, begun with %d", B, P->B);
+  }
+  if (e == hipSuccess) {
+    const int A = m->L.A;
+    if (a) memcpy(a, P->h_a, sizeof(float) * B * A);
+    if (v)
+      for (int i = 0; i < B; ++i) v[i] = P->h_a[(size_t)i * A];
+  }
+  give_lane(m, P);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(GA3C_EHIP, "prediction failed: %s", hipGetErrorString(e));
+  }
+  return GA3C_OK;
+}
+
+int param_index(const char* name) {
+  if (!name) return -1;
+  std::string s(name);
+  if (s.size() > 2 && s.compare(s.size() - 2, 2, ":0") == 0) s.resize(s.size() - 2);
+  for (int i = 0; i < NVARS; ++i)
+    if (s == VAR_NAMES[i]) return i;
+  return -1;
+}
+
+// tflearn's name of the target copy: the layer's scope is made a second time, "actor_fc1" -> "actor_fc1_1" (the one place).
+std::string target_name(int i) {
+  const std::string s(VAR_NAMES[i]);
+  const size_t slash = s.find('/');
+  return s.substr(0, slash) + "_1" + s.substr(slash);
+}
+
+void param_shape(const ga3c_ddpg* m, int i, int32_t* ndim, int64_t shape[4]) {
+  if (m->L.rows[i]) {
+    *ndim = 2;
+    shape[0] = m->L.rows[i];
+    shape[1] = m->L.cols[i];
+  } else {
+    *ndim = 1;
+    shape[0] = m->L.cols[i];
+  }
+}
+
+int arena_copy(ga3c_ddpg* m, int which, int64_t off, int64_t count, float* out, const float* in) {
+  if (which < 0 || which > 4 || (in && which > 3)) return fail(GA3C_EINVAL, "selector %d not in [0,%d]", which, in ? 3 : 4);
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  if (out) HIPCHK(hipMemcpy(out, m->arena[which] + off, sizeof(float) * count, hipMemcpyDeviceToHost));
+  else HIPCHK(hipMemcpy(m->arena[which] + off, in, sizeof(float) * count, hipMemcpyHostToDevice));
+  return GA3C_OK;
+}
+
+void free_all(ga3c_ddpg* m) {
+  if (m->st) (void)hipStreamSynchronize(m->st);
+  for (PLane& P : m->lanes) {
+    (void)hipHostFree(P.h_off); (void)hipHostFree(P.h_x); (void)hipHostFree(P.h_a);
+    (void)hipFree(P.d_off); (void)hipFree(P.d_x); (void)hipFree(P.d_a);
+    if (P.ev) (void)hipEventDestroy(P.ev);
+  }
+  for (float*& a : m->arena) (void)hipFree(a);
+  (void)hipFree(m->work_base);
+  (void)hipFree(m->ring);
+  (void)hipHostFree(m->h_stage); (void)hipFree(m->d_stage); (void)hipHostFree(m->h_idx); (void)hipFree(m->d_idx);
+  (void)hipHostFree(m->h_q); (void)hipHostFree(m->h_add);
+  (void)hipHostFree(m->h_aoff); (void)hipFree(m->d_aoff); (void)hipHostFree(m->h_ar); (void)hipFree(m->d_ar);
+  (void)hipHostFree(m->h_aa); (void)hipFree(m->d_aa);
+  for (hipEvent_t e : {m->tev, m->aev, m->t0, m->t1})
+    if (e) (void)hipEventDestroy(e);
+  if (m->reg_host) (void)hipHostUnregister((void*)m->reg_host);
+  if (m->st) (void)hipStreamDestroy(m->st);
+  (void)hipGetLastError();
+}
+
+template <class T>
+int dalloc(T** p, size_t n) {
+  HIPCHK(hipMalloc((void**)p, n * sizeof(T) + 16));
+  return GA3C_OK;
+}
+template <class T>
+int halloc(T** p, size_t n) {
+  HIPCHK(hipHostMalloc((void**)p, n * sizeof(T) + 16, hipHostMallocDefault));
+  return GA3C_OK;
+}
+
+int create(ga3c_ddpg* m) {
+  const ga3c_ddpg_config& c = m->cfg;
+  const size_t B = (size_t)c.max_batch, S = c.state_dim, A = c.num_actions, rowf = (size_t)m->rowf;
+  HIPCHK(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
+  std::vector<float> init((size_t)m->n, 0.f);
+  for (int i = 0; i < 5; ++i) {
+    CHK(dalloc(&m->arena[i], (size_t)m->n));
+    HIPCHK(hipMemset(m->arena[i], 0, sizeof(float) * m->n));
+  }
+  // moving_variance = 1 in both copies; the RMSProp ms slot of the critic starts at 1 (TF-1 RMSPropOptimizer)
+  for (int v : {(int)A_MV1, (int)A_MV2, (int)C_MV1})
+    for (int64_t i = m->L.off[v]; i < m->L.off[v + 1]; ++i) init[(size_t)i] = 1.f;
+  HIPCHK(hipMemcpy(m->arena[0], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(m->arena[1], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
+  if (!(c.flags & GA3C_DDPG_CRITIC_ADAM)) {
+    std::fill(init.begin(), init.end(), 0.f);
+    for (int64_t i = m->L.off[NACTOR]; i < m->L.off[NTRAIN]; ++i) init[(size_t)i] = 1.f;
+    HIPCHK(hipMemcpy(m->arena[2], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
+  }
+  float** ptrs[NWORK];
+  int widths[NWORK];
+  work_table(m, ptrs, widths);
+  size_t total = 0;
+  for (int i = 0; i < NWORK; ++i) total += (B * widths[i] + 3) / 4 * 4;
+  CHK(dalloc(&m->work_base, total + 4));
+  HIPCHK(hipMemset(m->work_base, 0, sizeof(float) * (total + 4)));
+  float* q = m->work_base;
+  for (int i = 0; i < NWORK; ++i) {
+    *ptrs[i] = q;
+    q += (B * widths[i] + 3) / 4 * 4;
+  }
+  m->w.qstat = q;
+  CHK(dalloc(&m->ring, (size_t)c.replay_capacity * rowf));
+  HIPCHK(hipMemset(m->ring, 0, sizeof(float) * (size_t)c.replay_capacity * rowf));
+  CHK(halloc(&m->h_stage, B * rowf)); CHK(dalloc(&m->d_stage, B * rowf));
+  CHK(halloc(&m->h_idx, B)); CHK(dalloc(&m->d_idx, B));
+  CHK(halloc(&m->h_q, 4));
+  CHK(halloc(&m->h_add, B * rowf));
+  CHK(halloc(&m->h_aoff, B)); CHK(dalloc(&m->d_aoff, B)); CHK(halloc(&m->h_ar, B)); CHK(dalloc(&m->d_ar, B));
+  CHK(halloc(&m->h_aa, B * A)); CHK(dalloc(&m->d_aa, B * A));
+  HIPCHK(hipEventCreateWithFlags(&m->tev, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&m->aev, hipEventDisableTiming));
+  HIPCHK(hipEventCreate(&m->t0));
+  HIPCHK(hipEventCreate(&m->t1));
+  m->lanes.resize((size_t)(c.predict_lanes > 0 ? c.predict_lanes : 4));
+  for (PLane& P : m->lanes) {
+    CHK(halloc(&P.h_off, B)); CHK(halloc(&P.h_x, B * S)); CHK(halloc(&P.h_a, B * A));
+    CHK(dalloc(&P.d_off, B)); CHK(dalloc(&P.d_x, B * S)); CHK(dalloc(&P.d_a, B * A));
+    HIPCHK(hipEventCreateWithFlags(&P.ev, hipEventDisableTiming));
+  }
+  return GA3C_OK;
+}
+
+// n rows into the ring at its write position, from `src` (device or pinned host) in ring layout; caller holds mu.
+int ring_copy_in(ga3c_ddpg* m, const float* src, int n, hipMemcpyKind kind) {
+  const int64_t cap = m->cfg.replay_capacity, first = m->ring_total % cap;
+  const int64_t n1 = std::min<int64_t>(n, cap - first);
+  const size_t rowb = sizeof(float) * (size_t)m->rowf;
+  HIPCHK(hipMemcpyAsync(m->ring + first * m->rowf, src, rowb * n1, kind, m->st));
+  if (n1 < n) HIPCHK(hipMemcpyAsync(m->ring, src + n1 * m->rowf, rowb * (n - n1), kind, m->st));
+  return GA3C_OK;
+}
+
+void ring_report(ga3c_ddpg* m, int64_t* size, int64_t* total) {
+  if (size) *size = std::min<int64_t>(m->ring_total, m->cfg.replay_capacity);
+  if (total) *total = m->ring_total;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ga3c_ddpg_create(const ga3c_ddpg_config* cfg, ga3c_ddpg** out) {
+  if (!cfg || !out) return fail(GA3C_EINVAL, "null argument");
+  *out = nullptr;
+  if (cfg->state_dim < 1 || cfg->state_dim > MAX_S) return fail(GA3C_EINVAL, "state_dim %d outside [1,%d]", cfg->state_dim, MAX_S);
+  if (cfg->num_actions < 1 || cfg->num_actions > MAX_A)
+    return fail(GA3C_EINVAL, "num_actions %d outside [1,%d]", cfg->num_actions, MAX_A);
+  if (cfg->max_batch < 1 || cfg->max_batch > 4096) return fail(GA3C_EINVAL, "max_batch %d outside [1,4096]", cfg->max_batch);
+  if (cfg->replay_capacity < 1 || cfg->replay_capacity > (1 << 26))
+    return fail(GA3C_EINVAL, "replay_capacity %d outside [1,%d]", cfg->replay_capacity, 1 << 26);
+  if (cfg->flags & ~(uint32_t)(GA3C_DDPG_FUTURE_REWARD | GA3C_DDPG_LOSS_PAIRED | GA3C_DDPG_GRAD_CLIP | GA3C_DDPG_CRITIC_ADAM |
+                               GA3C_DDPG_OU_NOISE))
+    return fail(GA3C_EINVAL, "flags 0x%x: not GA3C_DDPG_* flags", cfg->flags);
+  if (cfg->predict_lanes < 0 || cfg->predict_lanes > 64) return fail(GA3C_EINVAL, "predict_lanes %d outside [0,64]", cfg->predict_lanes);
+  if (!(cfg->tau >= 0.f && cfg->tau <= 1.f)) return fail(GA3C_EINVAL, "tau %g outside [0,1]", cfg->tau);
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (cfg->device < 0 || cfg->device >= ndev) return fail(GA3C_EINVAL, "device %d not in [0,%d)", cfg->device, ndev);
+  HIPCHK(hipSetDevice(cfg->device));
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(GA3C_ESTATE, "device %d is %s; this library is built for gfx950 only", cfg->device, prop.gcnArchName);
+  ga3c_ddpg* m = new (std::nothrow) ga3c_ddpg();
+  if (!m) return fail(GA3C_EINVAL, "out of host memory");
+  m->cfg = *cfg;
+  m->L = make_layout(cfg->state_dim, cfg->num_actions);
+  m->n = m->L.off[NVARS];
+  m->rowf = 2 * cfg->state_dim + cfg->num_actions + 2;
+  m->gen.seed((uint64_t)cfg->seed);
+  m->ou_x.assign((size_t)cfg->num_actions, 0.f);
+  const int rc = create(m);
+  if (rc != GA3C_OK) {
+    free_all(m);
+    delete m;
+    return rc;
+  }
+  *out = m;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  (void)hipSetDevice(m->cfg.device);
+  free_all(m);
+  delete m;
+  return GA3C_OK;
+}
+
+int32_t ga3c_ddpg_num_params(ga3c_ddpg* m) { return m ? NVARS : 0; }
+
+const char* ga3c_ddpg_param_name(ga3c_ddpg* m, int32_t index) {
+  return (m && index >= 0 && index < NVARS) ? VAR_NAMES[index] : nullptr;
+}
+
+const char* ga3c_ddpg_target_name(ga3c_ddpg* m, int32_t index) {
+  static std::string names[NVARS];
+  static std::once_flag once;
+  std::call_once(once, [] {
+    for (int i = 0; i < NVARS; ++i) names[i] = target_name(i);
+  });
+  return (m && index >= 0 && index < NVARS) ? names[index].c_str() : nullptr;
+}
+
+int ga3c_ddpg_param_info(ga3c_ddpg* m, const char* name, int64_t* count, int32_t* ndim, int64_t shape[4], int32_t* trainable) {
+  if (!m || !name) return fail(GA3C_EINVAL, "null argument");
+  const int i = param_index(name);
+  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
+  if (count) *count = m->L.off[i + 1] - m->L.off[i];
+  int32_t nd;
+  int64_t sh[4] = {0, 0, 0, 0};
+  param_shape(m, i, &nd, sh);
+  if (ndim) *ndim = nd;
+  if (shape) memcpy(shape, sh, sizeof sh);
+  if (trainable) *trainable = i < NTRAIN ? 1 : 0;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_get_param(ga3c_ddpg* m, const char* name, int32_t which, float* out, int64_t count) {
+  if (!m || !name || !out) return fail(GA3C_EINVAL, "null argument");
+  const int i = param_index(name);
+  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
+  const int64_t cnt = m->L.off[i + 1] - m->L.off[i];
+  if (count != cnt) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)cnt, (long long)count);
+  return arena_copy(m, which, m->L.off[i], count, out, nullptr);
+}
+
+int ga3c_ddpg_set_param(ga3c_ddpg* m, const char* name, int32_t which, const float* in, int64_t count) {
+  if (!m || !name || !in) return fail(GA3C_EINVAL, "null argument");
+  const int i = param_index(name);
+  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
+  const int64_t cnt = m->L.off[i + 1] - m->L.off[i];
+  if (count != cnt) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)cnt, (long long)count);
+  return arena_copy(m, which, m->L.off[i], count, nullptr, in);
+}
+
+int ga3c_ddpg_get_step(ga3c_ddpg* m, int64_t* step) {
+  if (!m || !step) return fail(GA3C_EINVAL, "null argument");
+  *step = m->step.load();
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_set_step(ga3c_ddpg* m, int64_t step) {
+  if (!m || step < 0) return fail(GA3C_EINVAL, "bad argument");
+  m->step.store(step);
+  return GA3C_OK;
+}
+
+// Checkpoint members of variable i: (member name, arena) pairs.
+static std::vector<std::pair<std::string, int>> ckpt_members(const ga3c_ddpg* m, int i) {
+  std::vector<std::pair<std::string, int>> v;
+  v.emplace_back(std::string(VAR_NAMES[i]) + ":0", 0);
+  v.emplace_back(target_name(i) + ":0", 1);
+  if (i < NTRAIN) {
+    const bool adam = i < NACTOR || (m->cfg.flags & GA3C_DDPG_CRITIC_ADAM);
+    v.emplace_back(std::string(VAR_NAMES[i]) + (adam ? "/Adam:0" : "/RMSProp:0"), 2);
+    v.emplace_back(std::string(VAR_NAMES[i]) + (adam ? "/Adam_1:0" : "/RMSProp_1:0"), 3);
+  }
+  return v;
+}
+
+int ga3c_ddpg_save(ga3c_ddpg* m, const char* path) {
+  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
+  std::vector<float> arena[4];
+  for (int w = 0; w < 4; ++w) {
+    arena[w].resize((size_t)m->n);
+    CHK(arena_copy(m, w, 0, m->n, arena[w].data(), nullptr));
+  }
+  std::vector<ga3c_ckpt::Member> members;
+  ga3c_ckpt::Member st;
+  st.name = "step";
+  st.descr = "<i8";
+  const int64_t step = m->step.load();
+  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
+  members.push_back(st);
+  for (int i = 0; i < NVARS; ++i) {
+    int32_t nd;
+    int64_t sh[4];
+    param_shape(m, i, &nd, sh);
+    for (const auto& km : ckpt_members(m, i)) {
+      ga3c_ckpt::Member mb;
+      mb.name = km.first;
+      mb.descr = "<f4";
+      mb.shape.assign(sh, sh + nd);
+      const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[km.second].data() + m->L.off[i]);
+      mb.bytes.assign(src, src + (size_t)(m->L.off[i + 1] - m->L.off[i]) * sizeof(float));
+      members.push_back(std::move(mb));
+    }
+  }
+  std::string err;
+  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_load(ga3c_ddpg* m, const char* path) {
+  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
+  std::map<std::string, ga3c_ckpt::Member> members;
+  std::string err;
+  if (!ga3c_ckpt::read_npz(path, &members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  std::vector<float> arena[4];
+  for (int w = 0; w < 4; ++w) {
+    arena[w].resize((size_t)m->n);
+    CHK(arena_copy(m, w, 0, m->n, arena[w].data(), nullptr));     // slots no member names keep their values
+  }
+  for (int i = 0; i < NVARS; ++i) {
+    const int64_t cnt = m->L.off[i + 1] - m->L.off[i];
+    int32_t nd;
+    int64_t sh[4];
+    param_shape(m, i, &nd, sh);
+    for (const auto& km : ckpt_members(m, i)) {
+      auto it = members.find(km.first);
+      if (it == members.end())
+        return fail(GA3C_ESTATE, "%s holds no %s: not a checkpoint of this DDPG network", path, km.first.c_str());
+      const ga3c_ckpt::Member& mb = it->second;
+      const bool shape_ok = mb.shape.size() == (size_t)nd && std::equal(mb.shape.begin(), mb.shape.end(), sh);
+      if (mb.descr != "<f4" || !shape_ok || mb.bytes.size() != (size_t)cnt * sizeof(float))
+        return fail(GA3C_ESTATE, "%s: %s is not <f4 of this network's shape (%lld elements)", path, km.first.c_str(), (long long)cnt);
+      memcpy(arena[km.second].data() + m->L.off[i], mb.bytes.data(), mb.bytes.size());
+    }
+  }
+  auto st = members.find("step");
+  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
+    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
+  int64_t step = 0;
+  memcpy(&step, st->second.bytes.data(), 8);
+  if (step < 0) return fail(GA3C_ESTATE, "%s: step %lld", path, (long long)step);
+  for (int w = 0; w < 4; ++w) CHK(arena_copy(m, w, 0, m->n, nullptr, arena[w].data()));
+  m->step.store(step);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_noise_step(ga3c_ddpg* m, float* x, float* n) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(m->noise_mu);
+  const ga3c_ddpg_config& c = m->cfg;
+  for (int i = 0; i < m->L.A; ++i) {
+    // x' = x + theta (mu - x) dt + sigma sqrt(dt) n with mu = 0 (OrnsteinUhlenbeckActionNoise.__call__, :470-476)
+    const float nn = (float)m->gen.normal();
+    const double xp = m->ou_x[i];
+    m->ou_x[i] = (float)(xp + (double)c.ou_theta * (0.0 - xp) * (double)c.ou_dt +
+                         (double)c.ou_sigma * std::sqrt((double)c.ou_dt) * (double)nn);
+    if (x) x[i] = m->ou_x[i];
+    if (n) n[i] = nn;
+  }
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_predict(ga3c_ddpg* m, const float* x, int32_t batch, int32_t noise_mode, const float* noise, float* a) {
+  if (!m || !x || !a) return fail(GA3C_EINVAL, "null argument");
+  int ticket;
+  CHK(predict_begin(m, x, nullptr, batch, noise_mode, noise, &ticket));
+  return predict_end(m, ticket, batch, a, nullptr);
+}
+
+int ga3c_ddpg_register_host(ga3c_ddpg* m, void* base, int64_t bytes) {
+  if (!m || !base || bytes < 16) return fail(GA3C_EINVAL, "bad argument");
+  if (m->reg_host) return fail(GA3C_ESTATE, "a host segment is already registered");
+  HIPCHK(hipSetDevice(m->cfg.device));
+  HIPCHK(hipHostRegister(base, (size_t)bytes, hipHostRegisterMapped));
+  void* dev = nullptr;
+  hipError_t e = hipHostGetDevicePointer(&dev, base, 0);
+  if (e != hipSuccess) {
+    (void)hipHostUnregister(base);
+    return fail(GA3C_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
+  }
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> al(m->add_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  m->reg_host = static_cast<const char*>(base);
+  m->reg_dev = static_cast<const char*>(dev);
+  m->reg_bytes = bytes;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_unregister_host(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (!m->reg_host) return GA3C_OK;
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> al(m->add_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipHostUnregister((void*)m->reg_host));
+  m->reg_host = m->reg_dev = nullptr;
+  m->reg_bytes = 0;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_predict_gather(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v, float* z) {
+  ga3c_ddpg* m = static_cast<ga3c_ddpg*>(net);
+  (void)z;
+  int ticket;
+  CHK(ga3c_ddpg_predict_gather_begin(net, offsets, batch, u8, &ticket));
+  return predict_end(m, ticket, batch, p, v);
+}
+
+int ga3c_ddpg_predict_gather_begin(void* net, const int64_t* offsets, int32_t batch, int32_t u8, int32_t* ticket) {
+  ga3c_ddpg* m = static_cast<ga3c_ddpg*>(net);
+  if (!m || !offsets || !ticket) return fail(GA3C_EINVAL, "null argument");
+  if (u8) return fail(GA3C_EINVAL, "the DDPG networks read f32 rows (u8 = 0)");
+  return predict_begin(m, nullptr, offsets, batch, GA3C_DDPG_NOISE_OWN, nullptr, ticket);
+}
+
+int ga3c_ddpg_predict_gather_end(void* net, int32_t ticket, int32_t batch, float* p, float* v) {
+  ga3c_ddpg* m = static_cast<ga3c_ddpg*>(net);
+  if (!m || !p || !v) return fail(GA3C_EINVAL, "null argument");
+  return predict_end(m, ticket, batch, p, v);
+}
+
+int ga3c_ddpg_replay_add(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2,
+                         int32_t n, int64_t* size, int64_t* total) {
+  if (!m || !s || !a || !r || !done || !s2) return fail(GA3C_EINVAL, "null argument");
+  if (n < 1 || n > m->cfg.max_batch || n > m->cfg.replay_capacity)
+    return fail(GA3C_EINVAL, "%d rows outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> al(m->add_mu);
+  const int S = m->L.S, A = m->L.A, rowf = m->rowf;
+  for (int i = 0; i < n; ++i) {
+    float* row = m->h_add + (size_t)i * rowf;
+    memcpy(row, s + (size_t)i * S, sizeof(float) * S);
+    memcpy(row + S, a + (size_t)i * A, sizeof(float) * A);
+    row[S + A] = r[i];
+    row[S + A + 1] = done[i] != 0.f ? 1.f : 0.f;
+    memcpy(row + S + A + 2, s2 + (size_t)i * S, sizeof(float) * S);
+  }
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    CHK(ring_copy_in(m, m->h_add, n, hipMemcpyHostToDevice));
+    HIPCHK(hipEventRecord(m->aev, m->st));
+    m->ring_total += n;
+    ring_report(m, size, total);
+  }
+  HIPCHK(hipEventSynchronize(m->aev));
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_replay_add_gather(ga3c_ddpg* m, const int64_t* offsets, const float* r, const float* a, int32_t n, int64_t* size,
+                                int64_t* total) {
+  if (!m || !offsets || !r || !a) return fail(GA3C_EINVAL, "null argument");
+  if (n < 1 || n > m->cfg.max_batch || n > m->cfg.replay_capacity)
+    return fail(GA3C_EINVAL, "%d rows outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> al(m->add_mu);
+  const int S = m->L.S, A = m->L.A;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    CHK(check_offsets(m, offsets, n, 2 * S + 1));
+    memcpy(m->h_aoff, offsets, sizeof(int64_t) * n);
+    memcpy(m->h_ar, r, sizeof(float) * n);
+    memcpy(m->h_aa, a, sizeof(float) * n * A);
+    HIPCHK(hipMemcpyAsync(m->d_aoff, m->h_aoff, sizeof(int64_t) * n, hipMemcpyHostToDevice, m->st));
+    HIPCHK(hipMemcpyAsync(m->d_ar, m->h_ar, sizeof(float) * n, hipMemcpyHostToDevice, m->st));
+    HIPCHK(hipMemcpyAsync(m->d_aa, m->h_aa, sizeof(float) * n * A, hipMemcpyHostToDevice, m->st));
+    const int64_t cap = m->cfg.replay_capacity, elems = (int64_t)n * m->rowf;
+    hipLaunchKernelGGL(ddpg_ring_gather_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, m->st, m->reg_dev,
+                       (const int64_t*)m->d_aoff, (const float*)m->d_ar, (const float*)m->d_aa, n, m->ring, m->ring_total % cap, cap,
+                       S, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->aev, m->st));
+    m->ring_total += n;
+    ring_report(m, size, total);
+  }
+  HIPCHK(hipEventSynchronize(m->aev));
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_replay_get(ga3c_ddpg* m, int64_t slot, float* s, float* a, float* r, float* done, float* s2) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::vector<float> row((size_t)m->rowf);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    const int64_t size = std::min<int64_t>(m->ring_total, m->cfg.replay_capacity);
+    if (slot < 0 || slot >= size) return fail(GA3C_EINVAL, "slot %lld outside the ring's %lld rows", (long long)slot, (long long)size);
+    HIPCHK(hipStreamSynchronize(m->st));
+    HIPCHK(hipMemcpy(row.data(), m->ring + slot * m->rowf, sizeof(float) * m->rowf, hipMemcpyDeviceToHost));
+  }
+  const int S = m->L.S, A = m->L.A;
+  if (s) memcpy(s, row.data(), sizeof(float) * S);
+  if (a) memcpy(a, row.data() + S, sizeof(float) * A);
+  if (r) *r = row[S + A];
+  if (done) *done = row[S + A + 1];
+  if (s2) memcpy(s2, row.data() + S + A + 2, sizeof(float) * S);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_replay_size(ga3c_ddpg* m, int64_t* size, int64_t* total) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(m->mu);
+  ring_report(m, size, total);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_train(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2,
+                    int32_t batch, float learning_rate, int32_t noise_mode, const float* noise, float* q_stats) {
+  return step_host(m, s, a, r, done, s2, batch, learning_rate, noise_mode, noise, 6, q_stats);
+}
+
+int ga3c_ddpg_compute(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2,
+                      int32_t batch, float learning_rate, int32_t noise_mode, const float* noise, int32_t stop_after,
+                      float* q_stats) {
+  if (stop_after != 3 && stop_after != 4) return fail(GA3C_EINVAL, "stop_after %d not in {3, 4}", stop_after);
+  return step_host(m, s, a, r, done, s2, batch, learning_rate, noise_mode, noise, stop_after, q_stats);
+}
+
+int ga3c_ddpg_train_replay(ga3c_ddpg* m, const int32_t* slots, int32_t batch, int64_t stamp, float learning_rate,
+                           int32_t noise_mode, const float* noise, float* q_stats) {
+  if (!m || !slots) return fail(GA3C_EINVAL, "null argument");
+  CHK(check_batch(m, batch));
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    // Validated under the lock that orders ring writes: a slot is refused if a row was written into it after `stamp`.
+    const int64_t cap = m->cfg.replay_capacity, total = m->ring_total, size = std::min(total, cap);
+    for (int i = 0; i < batch; ++i) {
+      const int64_t sl = slots[i];
+      if (sl < 0 || sl >= size) return fail(GA3C_EINVAL, "slot %lld of row %d outside the ring's %lld rows", (long long)sl, i, (long long)size);
+      if (stamp >= 0) {
+        const int64_t last = (total - 1) - ((total - 1 - sl) % cap);     // number of the row that lies in the slot now
+        if (last >= stamp)
+          return fail(GA3C_ELOST, "slot %lld was overwritten by row %lld after the batch was sampled at %lld", (long long)sl,
+                      (long long)last, (long long)stamp);
+      }
+    }
+    Noise nz;
+    CHK(make_noise(m, noise_mode, noise, &nz));
+    memcpy(m->h_idx, slots, sizeof(int32_t) * batch);
+    HIPCHK(hipMemcpyAsync(m->d_idx, m->h_idx, sizeof(int32_t) * batch, hipMemcpyHostToDevice, m->st));
+    CHK(enqueue_step(m, Rows{m->ring, m->d_idx, m->rowf}, batch, learning_rate, nz, 6));
+    CHK(finish_step(m));
+    m->last_B = batch;
+  }
+  HIPCHK(hipEventSynchronize(m->tev));
+  if (q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  m->step.fetch_add(1);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
+  if (!m || !name || !out) return fail(GA3C_EINVAL, "null argument");
+  float** ptrs[NWORK];
+  int widths[NWORK];
+  work_table(m, ptrs, widths);
+  int k = -1;
+  for (int i = 0; i < NWORK; ++i)
+    if (strcmp(name, WORK_NAMES[i]) == 0) k = i;
+  if (k < 0) return fail(GA3C_EINVAL, "no buffer named %s", name);
+  if (count != (int64_t)widths[k] * m->last_B)
+    return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)widths[k] * m->last_B, (long long)count);
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipMemcpy(out, *ptrs[k], sizeof(float) * count, hipMemcpyDeviceToHost));
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_time_resident(ga3c_ddpg* m, int32_t mode, int32_t batch, int32_t iters, float learning_rate, float* elapsed_ms) {
+  if (!m || !elapsed_ms || iters < 1 || (mode != 0 && mode != 1)) return fail(GA3C_EINVAL, "bad argument");
+  CHK(check_batch(m, batch));
+  HIPCHK(hipSetDevice(m->cfg.device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (batch > std::min<int64_t>(m->ring_total, m->cfg.replay_capacity))
+      return fail(GA3C_ESTATE, "batch %d: the ring holds %lld rows", batch, (long long)std::min<int64_t>(m->ring_total, m->cfg.replay_capacity));
+    for (int i = 0; i < batch; ++i) m->h_idx[i] = i;
+    HIPCHK(hipMemcpyAsync(m->d_idx, m->h_idx, sizeof(int32_t) * batch, hipMemcpyHostToDevice, m->st));
+    Noise nz;
+    memset(&nz, 0, sizeof nz);
+    const Rows rows{m->ring, m->d_idx, m->rowf};
+    const Input in{reinterpret_cast<const char*>(m->ring), nullptr, 4 * (int64_t)m->rowf};
+    HIPCHK(hipEventRecord(m->t0, m->st));
+    for (int i = 0; i < iters; ++i) {
+      if (mode == 0) {
+        hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(batch)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in,
+                           batch, nz, m->w.a_out);
+      } else {
+        CHK(enqueue_step(m, rows, batch, learning_rate, nz, 6));
+        m->step.fetch_add(1);
+      }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->t1, m->st));
+    m->last_B = batch;
+  }
+  HIPCHK(hipEventSynchronize(m->t1));
+  HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
+  return GA3C_OK;
+}
+
+}  // extern "C"

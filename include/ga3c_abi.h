@@ -401,6 +401,103 @@ int ga3c_mlp_time_resident(ga3c_mlp* net, int32_t mode, int32_t batch, int32_t i
  * "lossrow"}; count = rows x width. */
 int ga3c_mlp_fetch(ga3c_mlp* net, const char* name, float* out, int64_t count);
 
+/* ---- DDPG: reference NetworkDDPG.py (USE_DDPG with CONTINUOUS_INPUT), with the replay memory in HBM.
+ *   actor   x[B,S] -> actor_fc1 (400) -> actor_norm1 -> relu -> actor_fc2 (300) -> actor_norm2 -> relu -> actor_output (A, tanh)
+ *   critic  x -> critic_fc1 (400) -> critic_norm1 -> relu = h;  q = critic_output(relu(h W_fc2 + a W_n2 + b_n2)), W_n2 / b_n2
+ *           being the dense layer the reference names critic_norm2; critic_fc2/b is a variable that no kernel reads.
+ *   Batch normalisation is gamma (x - moving_mean) / sqrt(moving_variance + 1e-5) + beta; no kernel writes the moving
+ *   statistics (0 and 1 after create).
+ * A handle of its own with ga3c_mlp's conventions: int return codes, ga3c_last_error(), one HIP stream for every kernel
+ * and copy (a prediction sees the weights before or after a step, never a mix; ring writes and train steps are ordered),
+ * a lane per prediction in flight, train-type calls serialised.
+ *
+ * 26 variables, arena order: the actor's ten trainable ones (actor_fc1/W[S,400] /b actor_norm1/beta /gamma actor_fc2/W[400,300]
+ * /b actor_norm2/beta /gamma actor_output/W[300,A] /b), the critic's ten (critic_fc1/W[S,400] /b critic_norm1/beta /gamma
+ * critic_fc2/W[400,300] /b critic_norm2/W[A,300] /b critic_output/W[300,1] /b), then actor_norm1/moving_mean /moving_variance,
+ * actor_norm2/..., critic_norm1/....  `which` of get / set_param: 0 value, 1 target network's value, 2 / 3 optimizer slots
+ * (RMSProp ms / mom for the critic, Adam m / v under GA3C_DDPG_CRITIC_ADAM and for the actor), 4 last gradient (get only).
+ * Checkpoints: the .npz container of ga3c_net_save: "<var>:0", the target copy under tflearn's second-scope name
+ * ("actor_fc1_1/W:0"), the slots as "<var>/RMSProp:0", "/RMSProp_1:0" or "/Adam:0", "/Adam_1:0", and "step", which Adam's
+ * bias correction reads.  A file of another network is refused with GA3C_ESTATE and the handle untouched. */
+#define GA3C_DDPG_FUTURE_REWARD 1u  /* Config.DDPG_FUTURE_REWARD_CALC: y = r + gamma q' on rows that are not done; else y = r */
+#define GA3C_DDPG_LOSS_PAIRED 2u    /* DDPG_CRITIC_LOSS = 'paired': dL/dq_i = (2/B)(q_i - y_i).  Without it the fork's form: y[B]
+                                       against q[B,1] broadcasts to [B,B], dL/dq_i = (2/B)(q_i - mean(y)) (NetworkDDPG.py:32,409) */
+#define GA3C_DDPG_GRAD_CLIP 4u      /* Config.USE_GRAD_CLIP: tf.clip_by_norm per critic gradient tensor (:354-357) */
+#define GA3C_DDPG_CRITIC_ADAM 8u    /* Config.RMSPROP = False: Adam for the critic as for the actor */
+#define GA3C_DDPG_OU_NOISE 16u      /* Config.add_OUnoise: the handle's Ornstein-Uhlenbeck process (:463-482) */
+#define GA3C_DDPG_NOISE_OWN 0       /* noise_mode: one step of the handle's process (nothing without GA3C_DDPG_OU_NOISE) */
+#define GA3C_DDPG_NOISE_GIVEN 1     /*   the caller's noise[A], added to every row */
+#define GA3C_DDPG_NOISE_NONE 2      /*   none; the output is wrapped into [-1, 1] elementwise (check_bounds, turnaround) */
+typedef struct ga3c_ddpg ga3c_ddpg;
+typedef struct ga3c_ddpg_config {
+  int32_t device;
+  int32_t state_dim;        /* S, 1..64 */
+  int32_t num_actions;      /* A, 1..32 */
+  int32_t max_batch;        /* rows of one predict / train / replay_add call, 1..4096 */
+  int32_t replay_capacity;  /* rows of the ring in HBM, (2 S + A + 2) floats each */
+  int32_t predict_lanes;    /* 0 -> 4 */
+  uint32_t flags;           /* GA3C_DDPG_* */
+  float tau, gamma;         /* Config.tau, Config.gamma */
+  float actor_lr, critic_lr;/* Config.actor_lr, Config.critic_lr: factors on the step's learning_rate */
+  float rmsprop_decay, rmsprop_momentum, rmsprop_epsilon, grad_clip_norm;
+  float ou_sigma, ou_theta, ou_dt;
+  int64_t seed;             /* of the handle's normal generator (Config.RANDOM_SEED) */
+} ga3c_ddpg_config;
+
+int ga3c_ddpg_create(const ga3c_ddpg_config* cfg, ga3c_ddpg** out);   /* every variable zero, ms 1, moving_variance 1 */
+int ga3c_ddpg_destroy(ga3c_ddpg* net);
+int32_t ga3c_ddpg_num_params(ga3c_ddpg* net);                          /* 26 */
+const char* ga3c_ddpg_param_name(ga3c_ddpg* net, int32_t index);
+const char* ga3c_ddpg_target_name(ga3c_ddpg* net, int32_t index);      /* the checkpoint name of the target copy */
+int ga3c_ddpg_param_info(ga3c_ddpg* net, const char* name, int64_t* count, int32_t* ndim, int64_t shape[4], int32_t* trainable);
+int ga3c_ddpg_get_param(ga3c_ddpg* net, const char* name, int32_t which, float* out, int64_t count);
+int ga3c_ddpg_set_param(ga3c_ddpg* net, const char* name, int32_t which, const float* in, int64_t count);
+int ga3c_ddpg_get_step(ga3c_ddpg* net, int64_t* step);
+int ga3c_ddpg_set_step(ga3c_ddpg* net, int64_t step);
+int ga3c_ddpg_save(ga3c_ddpg* net, const char* path);
+int ga3c_ddpg_load(ga3c_ddpg* net, const char* path);
+/* One step of the handle's OU process: x[A] the new state, n[A] the normal draws it used (each may be NULL). */
+int ga3c_ddpg_noise_step(ga3c_ddpg* net, float* x, float* n);
+/* x f32[B,S] -> a f32[B,A] = actor(x) + noise, online actor only, one launch. */
+int ga3c_ddpg_predict(ga3c_ddpg* net, const float* x, int32_t batch, int32_t noise_mode, const float* noise, float* a);
+/* Zero-copy intake, as ga3c_mlp_*: rows of the registered segment by byte offset (4-byte aligned; the first S floats are the
+ * state).  The three gather entries have the signatures of the native predictor loops and take GA3C_DDPG_NOISE_OWN; p is the
+ * action [B,A], v[B] its first component (predict_p_and_v returns (action, action), NetworkDDPG.py:106-111). */
+int ga3c_ddpg_register_host(ga3c_ddpg* net, void* base, int64_t bytes);
+int ga3c_ddpg_unregister_host(ga3c_ddpg* net);
+int ga3c_ddpg_predict_gather(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v, float* z);
+int ga3c_ddpg_predict_gather_begin(void* net, const int64_t* offsets, int32_t batch, int32_t u8, int32_t* ticket);
+int ga3c_ddpg_predict_gather_end(void* net, int32_t ticket, int32_t batch, float* p, float* v);
+/* The replay ring (replay_buffer.py:16-55): n rows appended, the oldest dropped beyond the capacity.  size: rows held;
+ * total: rows ever added (row number t lies in slot t mod capacity).  Both return after the device has read the rows.
+ * replay_add_gather reads rows `s[S] | s2[S] | done` (f32) at byte offsets of the registered segment. */
+int ga3c_ddpg_replay_add(ga3c_ddpg* net, const float* s, const float* a, const float* r, const float* done, const float* s2,
+                         int32_t n, int64_t* size, int64_t* total);
+int ga3c_ddpg_replay_add_gather(ga3c_ddpg* net, const int64_t* offsets, const float* r, const float* a, int32_t n, int64_t* size,
+                                int64_t* total);
+int ga3c_ddpg_replay_get(ga3c_ddpg* net, int64_t slot, float* s, float* a, float* r, float* done, float* s2);
+int ga3c_ddpg_replay_size(ga3c_ddpg* net, int64_t* size, int64_t* total);
+/* train_DDPG (NetworkDDPG.py:64-98): targets, critic step, action gradient of the updated critic, actor step, soft update of
+ * both target networks.  5 launches (6 with GA3C_DDPG_GRAD_CLIP) on the handle's stream and one wait, for q_stats =
+ * {max, mean} of q as predicted before the update.  Sums over rows run in row order: the same call on the same state
+ * gives the same bits.  train_replay names ring slots; stamp >= 0 is the ring's `total` when they were sampled, and a slot
+ * written since is refused with GA3C_ELOST (nothing trained); stamp < 0: no such check. */
+int ga3c_ddpg_train(ga3c_ddpg* net, const float* s, const float* a, const float* r, const float* done, const float* s2,
+                    int32_t batch, float learning_rate, int32_t noise_mode, const float* noise, float* q_stats);
+int ga3c_ddpg_train_replay(ga3c_ddpg* net, const int32_t* slots, int32_t batch, int64_t stamp, float learning_rate,
+                           int32_t noise_mode, const float* noise, float* q_stats);
+/* For tests: the same kernels stopped after step 3 (the critic's update applied) or step 4 (+ the action gradient and the
+ * actor's gradient, not applied); no soft update, the step counter stays. */
+int ga3c_ddpg_compute(ga3c_ddpg* net, const float* s, const float* a, const float* r, const float* done, const float* s2,
+                      int32_t batch, float learning_rate, int32_t noise_mode, const float* noise, int32_t stop_after,
+                      float* q_stats);
+/* Rows of the last train-type call: "y", "qt" (q'), "q", "dq" [B]; "c_xh1", "c_c1", "c_dn1", "c_dh1" [B,400]; "c_c2", "c_dt"
+ * [B,300]; "a_xh1", "a_a1", "a_dn1", "a_dh1" [B,400]; "a_xh2", "a_a2", "a_dn2", "a_dh2" [B,300]; "a_out", "a_noisy", "g", "do" [B,A]. */
+int ga3c_ddpg_fetch(ga3c_ddpg* net, const char* name, float* out, int64_t count);
+/* `iters` calls between two events on the handle's stream -> milliseconds: mode 0 predict on ring rows' states, 1 train_replay,
+ * both on slots 0 .. batch-1 (the ring must hold them), without noise. */
+int ga3c_ddpg_time_resident(ga3c_ddpg* net, int32_t mode, int32_t batch, int32_t iters, float learning_rate, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,56 @@
+#!/usr/bin/env python3
+"""Development aid: step times of the DDPG handle (USE_DDPG, ga3c_ddpg_*), rows resident in the replay ring, device-
+synchronised timing (ga3c_ddpg_time_resident: HIP events around `iters` back-to-back calls on ring slots 0 .. rows-1;
+mode 0 = predict, 1 = train_replay).  Median and min over rounds, one JSON line per configuration.  Launches per call:
+predict 1, train_replay 5 (6 with USE_GRAD_CLIP).
+usage: python tools/ddpg_step.py [--predict 1 128] [--train 64 128 256] [--rounds 5] [--iters 200] [--clip]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--predict", type=int, nargs="+", default=[1, 128])
+    ap.add_argument("--train", type=int, nargs="+", default=[64, 128, 256])
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--state-dim", type=int, default=3)
+    ap.add_argument("--actions", type=int, default=1)
+    ap.add_argument("--clip", action="store_true")
+    args = ap.parse_args()
+    import ga3c_amd  # noqa: F401
+    from Config import Config
+    from NetworkDDPG import Network
+    Config.USE_GRAD_CLIP = args.clip
+    S, A = args.state_dim, args.actions
+    maxB = max(args.predict + args.train)
+    net = Network("gpu:0", "ddpg_step", A, (S,), max_batch=maxB, replay_capacity=max(maxB, 1024))
+    rng = np.random.Generator(np.random.PCG64(1))
+    net.replay_add(rng.uniform(-1, 1, (maxB, S)), rng.uniform(-1, 1, (maxB, A)), rng.uniform(-1, 0, maxB),
+                   rng.uniform(size=maxB) < 0.1, rng.uniform(-1, 1, (maxB, S)))
+    net.learning_rate = 1e-6
+    jobs = [(0, b) for b in args.predict] + [(1, b) for b in args.train]
+    res = {j: [] for j in jobs}
+    for mode, b in jobs:
+        net.time_resident(mode, b, 20)                  # warm-up
+    for _ in range(args.rounds):
+        for mode, b in jobs:
+            res[(mode, b)].append(net.time_resident(mode, b, args.iters) / args.iters * 1e3)
+    for (mode, b), v in res.items():
+        v = sorted(v)
+        print(json.dumps({"step": "train_replay" if mode else "predict", "rows": b, "state_dim": S, "actions": A,
+                          "grad_clip": bool(args.clip), "launches": (6 if args.clip else 5) if mode else 1,
+                          "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2), "rounds": args.rounds,
+                          "iters": args.iters}), flush=True)
+    net.close()
+
+
+if __name__ == "__main__":
+    main()
