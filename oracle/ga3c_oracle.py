@@ -142,7 +142,8 @@ def forward(params, x, min_policy=0.0, use_log_softmax=False, keep=False):
     n2pre, cols2 = _conv_fwd(n1, params["conv12/w"], params["conv12/b"], CONV2)
     n2 = np.maximum(n2pre, 0)
     flat = n2.reshape(bsz, FLAT)                 # index (h*11+w)*32+c  (NetworkDNav.py:86-89)
-    d1 = np.maximum(flat @ params["dense1/w"] + params["dense1/b"], 0)
+    d1pre = flat @ params["dense1/w"] + params["dense1/b"]
+    d1 = np.maximum(d1pre, 0)
     v = (d1 @ params["logits_v/w"] + params["logits_v/b"])[:, 0]
     z = d1 @ params["logits_p/w"] + params["logits_p/b"]
     zs = z - z.max(axis=1, keepdims=True)
@@ -155,19 +156,24 @@ def forward(params, x, min_policy=0.0, use_log_softmax=False, keep=False):
         p = (s + min_policy) / (1.0 + min_policy * num_actions)   # :73-74
     out = dict(z=z, p=p, v=v)
     if keep:
-        out.update(x=x, cols1=cols1, n1=n1, cols2=cols2, n2=n2, flat=flat, d1=d1, s=s, zs=zs, e=e)
+        out.update(x=x, cols1=cols1, n1=n1, cols2=cols2, n2=n2, flat=flat, d1=d1, s=s, zs=zs, e=e,
+                   n1pre=n1pre, n2pre=n2pre, d1pre=d1pre)
     return out
 
 
 # ---------------------------------------------------------------- loss + grads
 def loss_and_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_log_softmax=False,
-                   adv_const=None):
+                   adv_const=None, relu_on=None):
     """Sum-over-batch A3C loss of NetworkVP_discrate.py:61-85,100 and its gradient.
 
     Returns (losses, grads): losses = dict(cost_p_1_agg, cost_p_2_agg, cost_v, cost_all);
     grads = dict keyed like params, plus 'dz','dv' per-sample head gradients.
     `adv_const` replaces y_r - v by a constant so that a numerical derivative of
     cost_all sees what tf.stop_gradient makes autodiff see.
+    `relu_on` = dict(d1=, n2=, n1=) of boolean arrays replaces the units through which the backward pass flows
+    (default: those with a positive output).  A unit whose input lies within rounding of zero is on in one precision and
+    off in another, and both are right: a comparison hands the oracle the units its counterpart had on
+    (tests/closeness.py) instead of counting the unit's whole gradient as an error.
     """
     f = forward(params, x, min_policy, use_log_softmax, keep=True)
     dt = f["z"].dtype
@@ -191,8 +197,11 @@ def loss_and_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_lo
         logp = np.log(np.maximum(p, log_eps))
         cost_p_2 = -beta * (logp * p).sum(axis=1)
         # tf.maximum routes the gradient to x when x >= eps
-        g_sel = np.where(sel >= log_eps, 1.0 / np.maximum(sel, log_eps), 0.0)
-        g_p = -(adv * g_sel)[:, None] * a + beta * (logp + np.where(p >= log_eps, 1.0, 0.0))
+        # np.where turns a Python scalar into a float64 array: every branch is given in `dt`, so that a float32 run stays
+        # float32 behind the loss as well
+        one, zero = dt.type(1.0), dt.type(0.0)
+        g_sel = np.where(sel >= log_eps, one / np.maximum(sel, log_eps), zero)
+        g_p = -(adv * g_sel)[:, None] * a + beta * (logp + np.where(p >= log_eps, one, zero))
         g_s = g_p / (1.0 + min_policy * num_actions)
         dz = s * (g_s - (g_s * s).sum(axis=1, keepdims=True))
     dv = v - y_r
@@ -201,17 +210,18 @@ def loss_and_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_lo
     losses = dict(cost_p_1_agg=c1, cost_p_2_agg=c2, cost_v=cost_v, cost_all=-(c1 + c2) + cost_v)
 
     d1, flat, n2, n1 = f["d1"], f["flat"], f["n2"], f["n1"]
+    on = {k: np.asarray(relu_on[k]).reshape(f[k].shape) if relu_on is not None else f[k] > 0 for k in ("d1", "n2", "n1")}
     g = {}
     g["logits_p/w"] = d1.T @ dz
     g["logits_p/b"] = dz.sum(axis=0)
     g["logits_v/w"] = d1.T @ dv[:, None]
     g["logits_v/b"] = dv.sum(keepdims=True)
-    dd1 = (dz @ params["logits_p/w"].T + dv[:, None] @ params["logits_v/w"].T) * (d1 > 0)
+    dd1 = (dz @ params["logits_p/w"].T + dv[:, None] @ params["logits_v/w"].T) * on["d1"]
     g["dense1/w"] = flat.T @ dd1
     g["dense1/b"] = dd1.sum(axis=0)
-    dn2 = (dd1 @ params["dense1/w"].T).reshape(n2.shape) * (n2 > 0)
+    dn2 = (dd1 @ params["dense1/w"].T).reshape(n2.shape) * on["n2"]
     g["conv12/w"], g["conv12/b"], dn1 = _conv_bwd(dn2, f["cols2"], params["conv12/w"], CONV2, 21, True)
-    dn1 = dn1 * (n1 > 0)
+    dn1 = dn1 * on["n1"]
     g["conv11/w"], g["conv11/b"], _ = _conv_bwd(dn1, f["cols1"], params["conv11/w"], CONV1, 84, False)
     g["dz"], g["dv"], g["dd1"], g["dn2"], g["dn1"] = dz, dv, dd1, dn2, dn1
     return losses, g

@@ -9,6 +9,9 @@ Reference NetworkDDPG.py (USE_DDPG with CONTINUOUS_INPUT), restated in DESIGN.md
 
 Batch normalisation is the inference form only (the reference never switches tflearn's training flag on), stated once
 in bn(): gamma (x - moving_mean) / sqrt(moving_variance + BN_EPS) + beta.
+
+Every function follows the dtype of the weights it is given: float64 is the statement, float32 weights give the
+like-for-like restatement that tests/closeness.py's bound is measured with.
 """
 import numpy as np
 
@@ -63,7 +66,7 @@ def bn(P, name, h):
 
 
 def actor_forward(P, x):
-    x = np.asarray(x, np.float64)
+    x = np.asarray(x, P["actor_fc1/W"].dtype)
     h1 = x @ P["actor_fc1/W"] + P["actor_fc1/b"]
     xh1, rs1, n1 = bn(P, "actor_norm1", h1)
     a1 = np.maximum(n1, 0.0)
@@ -75,7 +78,7 @@ def actor_forward(P, x):
 
 
 def critic_forward(P, x, a):
-    x, a = np.asarray(x, np.float64), np.asarray(a, np.float64)
+    x, a = np.asarray(x, P["critic_fc1/W"].dtype), np.asarray(a, P["critic_fc1/W"].dtype)
     h1 = x @ P["critic_fc1/W"] + P["critic_fc1/b"]
     xh1, rs1, n1 = bn(P, "critic_norm1", h1)
     c1 = np.maximum(n1, 0.0)
@@ -100,7 +103,7 @@ def relu_margin(online, target, s, a, s2):
 
 def targets(T, s2, r, done, gamma, future=True):
     """Steps 1-2: y_i = r_i if done_i else r_i + gamma q'_i;  q' = critic_target(s2, actor_target(s2))."""
-    r = np.asarray(r, np.float64)
+    r = np.asarray(r, T["critic_fc1/W"].dtype)
     if not future:
         return r.copy(), None
     qt = critic_forward(T, s2, actor_forward(T, s2)["out"])["q"][:, 0]
@@ -113,7 +116,7 @@ def critic_grads(P, s, a, y, form="fork"):
     f = critic_forward(P, s, a)
     B = f["q"].shape[0]
     q = f["q"][:, 0]
-    ref = np.mean(y) if form == "fork" else np.asarray(y, np.float64)
+    ref = np.mean(y) if form == "fork" else np.asarray(y, q.dtype)
     dq = (2.0 / B) * (q - ref)
     g = {}
     g["critic_output/W"] = f["c2"].T @ dq[:, None]
@@ -122,7 +125,7 @@ def critic_grads(P, s, a, y, form="fork"):
     g["critic_fc2/W"] = f["c1"].T @ dt
     g["critic_norm2/W"] = f["a"].T @ dt
     g["critic_norm2/b"] = dt.sum(0)
-    g["critic_fc2/b"] = np.zeros(H2)
+    g["critic_fc2/b"] = np.zeros(H2, q.dtype)
     dn1 = (dt @ P["critic_fc2/W"].T) * (f["n1"] > 0)
     g["critic_norm1/beta"] = dn1.sum(0)
     g["critic_norm1/gamma"] = (dn1 * f["xh1"]).sum(0)
@@ -143,7 +146,7 @@ def action_gradient(P, s, a):
 def actor_grads(P, s, g):
     """Step 5: d(out)/d(var) contracted with -g, summed over rows (:182-183)."""
     f = actor_forward(P, s)
-    do = -np.asarray(g, np.float64) * (1.0 - f["out"] ** 2)
+    do = -np.asarray(g, f["out"].dtype) * (1.0 - f["out"] ** 2)
     G = {"actor_output/W": f["a2"].T @ do, "actor_output/b": do.sum(0)}
     dn2 = (do @ P["actor_output/W"].T) * (f["n2"] > 0)
     G["actor_norm2/beta"] = dn2.sum(0)
@@ -220,7 +223,7 @@ def train_step(st, s, a, r, done, s2, lr, noise=None, *, actor_lr=1.0, critic_lr
     if stop_after <= 3:
         return out
     fa0 = actor_forward(O, s)
-    a_out = fa0["out"] + (0.0 if noise is None else np.asarray(noise, np.float64)[None, :])
+    a_out = fa0["out"] + (0.0 if noise is None else np.asarray(noise, fa0["out"].dtype)[None, :])
     g = action_gradient(O, s, a_out)
     fa, ga = actor_grads(O, s, g)
     out.update(a_out=a_out, g=g, actor_grads=ga, actor_fwd=fa)

@@ -1,4 +1,6 @@
-"""f64 statement of the vector-state network for the tests (not collected: no test_ prefix).
+"""f64 statement of the vector-state network for the tests (not collected: no test_ prefix).  forward / loss_and_grads
+follow the dtype of the weights: float64 is the statement, float32 weights give the like-for-like restatement that
+tests/closeness.py's bound is measured with.
 
 Reference NetworkVP.py:67-105,175-210 (GAME = 'Pendulum-v0'): dense_layer = x W + b with U(-0.3, 0.3) weights and biases,
     pd1 = x W11 + b11, pd2 = pd1 W12 + b12, pd3 = pd2 W13 + b13, pd4 = sigmoid(pd3 W14 + b14), d1 = sigmoid(pd4 W1 + b1)
@@ -43,7 +45,8 @@ def _sigmoid(h):
 
 def forward(params, x):
     """-> dict(o [B,A], v [B], z [B,2A] = [hx | hy], pd1..pd4, d1, and the head intermediates)."""
-    h = np.asarray(x, np.float64)
+    dt = params["dense1/w"].dtype
+    h = np.asarray(x, dt)
     out = {"x": h}
     keys = ("pd1", "pd2", "pd3", "pd4", "d1")
     for (name, _, sig), key in zip(TRUNK, keys):
@@ -56,8 +59,8 @@ def forward(params, x):
     hx = d1 @ params["logits_p/out_x/w"] + params["logits_p/out_x/b"]
     hy = d1 @ params["logits_p/out_y/w"] + params["logits_p/out_y/b"]
     sx, sy = _sigmoid(hx), _sigmoid(hy)
-    X, Y = sx - 0.5, sy - 0.5
-    out.update(o=np.arctan2(Y, X) / np.pi, v=v, z=np.concatenate([hx, hy], axis=1), sx=sx, sy=sy, X=X, Y=Y)
+    X, Y = sx - dt.type(0.5), sy - dt.type(0.5)
+    out.update(o=np.arctan2(Y, X) / dt.type(np.pi), v=v, z=np.concatenate([hx, hy], axis=1), sx=sx, sy=sy, X=X, Y=Y)
     return out
 
 
@@ -66,16 +69,18 @@ def loss_and_grads(params, x, y_r, a, beta, adv_const=None):
     per-row deltas at every pre-activation: 'dv', 'dz' [B,2A], 'dd1', 'dpd4', 'dpd3', 'dpd2', 'dpd1'.
     adv_const freezes y_r - v for finite differences (tf.stop_gradient)."""
     f = forward(params, x)
-    y_r, a = np.asarray(y_r, np.float64), np.asarray(a, np.float64)
+    dt = f["v"].dtype
+    y_r, a = np.asarray(y_r, dt), np.asarray(a, dt)
     out, v = f["o"], f["v"]
-    adv = y_r - v if adv_const is None else np.asarray(adv_const, np.float64)
+    adv = y_r - v if adv_const is None else np.asarray(adv_const, dt)
     cost_p_1 = (out * a).sum(axis=1) * adv
     cost_p_2 = -beta * (out * out).sum(axis=1)
     g_o = -a * adv[:, None] + 2.0 * beta * out
     X, Y = f["X"], f["Y"]
     r2 = X * X + Y * Y
-    dhx = (-Y * g_o / (np.pi * r2)) * f["sx"] * (1.0 - f["sx"])
-    dhy = (X * g_o / (np.pi * r2)) * f["sy"] * (1.0 - f["sy"])
+    pi = dt.type(np.pi)
+    dhx = (-Y * g_o / (pi * r2)) * f["sx"] * (1.0 - f["sx"])
+    dhy = (X * g_o / (pi * r2)) * f["sy"] * (1.0 - f["sy"])
     dv = v - y_r
     c1, c2 = cost_p_1.sum(), cost_p_2.sum()
     cost_v = 0.5 * np.sum((y_r - v) ** 2)

@@ -157,6 +157,45 @@ def test_every_intermediate_and_gradient(S, A, B):
         net.close()
 
 
+@pytest.mark.parametrize("S,A", SHAPES)
+@pytest.mark.parametrize("B", SIZES)
+def test_backward_tensors_relative_to_their_largest_entry(S, A, B):
+    """TOL x max(1, max|want|) is absolute below 1, and the critic's deltas shrink with 2 / B: dq, c_dt and c_dn1 are below 0.1
+    from 128 rows on, a_dn2 at most sizes (tests/README.md, "how large the tensors are").  Every delta and gradient of steps
+    3-4 once more with tests/closeness.py: max|got - want| / max|want| against max(16 x e32, 2^-20), e32 from the oracle run
+    in float32 on the same rows (the rows keep every relu unit 1e-4 away from zero: _select)."""
+    import closeness as c
+    noise = np.linspace(-0.2, 0.3, A).astype(np.float32)
+    online, target, batch = _case(S, A, B, 100 + B + S, stats=True, noise=noise)
+
+    def tensors(out):
+        fc, fa = out["critic_fwd"], out["actor_fwd"]
+        t = {"dq": out["dq"], "c_dt": fc["dt"], "c_dn1": fc["dn1"], "g": out["g"], "do": fa["do"], "a_dn2": fa["dn2"],
+             "a_dn1": fa["dn1"]}
+        t.update({"grad " + k: out["critic_grads"][k] for k in o.CRITIC_TRAINABLE if k != o.DEAD})
+        t.update({"grad " + k: out["actor_grads"][k] for k in o.ACTOR_TRAINABLE})
+        return t
+
+    want = tensors(o.train_step(o.new_state(online, target), *_f64(batch), LR, noise.astype(np.float64), stop_after=4))
+    f32 = lambda P: {k: v.astype(np.float32) for k, v in P.items()}     # noqa: E731
+    w32 = tensors(o.train_step(o.new_state(f32(online), f32(target)), *batch, LR, noise, stop_after=4))
+    net = _net(S, A)
+    try:
+        _load(net, online, target)
+        net.compute(batch[0], batch[2], batch[1], batch[4], batch[3], 4, noise=noise)
+        failed = []
+        for name, ref in want.items():
+            assert np.asarray(w32[name]).dtype == np.float32, name
+            got = net.get_variable_value(name[5:], 4) if name.startswith("grad ") else net.fetch(name, np.size(ref))
+            e32 = c.rel_err(w32[name], ref)
+            err = c.report("ddpg S=%d A=%d B=%d" % (S, A, B), name, got, ref, e32, c.bound(e32))
+            if not err <= c.bound(e32):
+                failed.append((name, err, c.bound(e32)))
+        assert not failed, failed
+    finally:
+        net.close()
+
+
 @pytest.mark.parametrize("cfg", [dict(DDPG_CRITIC_LOSS="paired"), dict(DDPG_FUTURE_REWARD_CALC=False), dict(USE_GRAD_CLIP=True),
                                  dict(RMSPROP=False)], ids=lambda c: "-".join("%s=%s" % kv for kv in c.items()))
 def test_loss_forms_and_flags_without_noise(cfg):

@@ -100,6 +100,49 @@ def test_forward_losses_and_gradients_against_the_oracle(state_dim):
         net.close()
 
 
+@pytest.mark.parametrize("state_dim", [3, 7])
+def test_backward_tensors_relative_to_their_largest_entry(state_dim):
+    """TOL x max(1, max|want|) is absolute below 1, and here dpd3 / dpd4 stay below 0.1 at every size and every gradient at
+    B = 1 (tests/README.md, "how large the tensors are").  Every delta and gradient once more with tests/closeness.py:
+    max|got - want| / max|want| against max(16 x e32, 2^-20), e32 from the oracle run in float32 on the same rows.  A bias
+    gradient of ONE element (logits_v/b; out_x/b and out_y/b when A = 1) takes the larger of that single draw and what the
+    float32 error of the delta it sums implies (closeness.e32_of_row_sum, where the reason is written): out_y/b at
+    B = 15, A = 1 came out at rel_err 2.5e-6 with a single draw of 3e-8, while out_y/w -- the same delta summed with weights in
+    (0, 1) -- has e32 2.3e-7 and rel_err 2.5e-6 as well; the delta's own error gives 1.1e-6 for the bias."""
+    import closeness as c
+    A = 1 if state_dim == 3 else 3
+    params = _params(state_dim, A)
+    p32 = {k: v.astype(np.float32) for k, v in params.items()}
+    net = _net(state_dim, A)
+    try:
+        _reset(net, params)
+        net.beta = 0.01
+        failed = []
+        for bsz in SIZES:
+            x, y, a = _batch(params, bsz, state_dim, A, 100 + bsz)
+            net.compute_grads(x, y, a)
+            _, g = m.loss_and_grads(params, x.astype(np.float64), y.astype(np.float64), a.astype(np.float64), 0.01)
+            _, g32 = m.loss_and_grads(p32, x, y, a, 0.01)
+            grad = net.get_arena(3)
+            got = {name: net.fetch(name, bsz * width) for name, width in (("dv", 1), ("dz", 2 * A), ("dd1", 64), ("dpd4", 100),
+                                                                          ("dpd3", 256), ("dpd2", 256), ("dpd1", 4))}
+            got.update({k: grad[net._offsets[k][0]:net._offsets[k][0] + net._offsets[k][1]] for k in m.PARAM_ORDER})
+            for name in got:
+                assert np.asarray(g32[name]).dtype == np.float32, name
+                e32 = c.rel_err(g32[name], g[name])
+                sums = {"logits_v/b": ("dv", slice(None)), "logits_p/out_x/b": ("dz", (slice(None), slice(0, A))),
+                        "logits_p/out_y/b": ("dz", (slice(None), slice(A, 2 * A)))}
+                if name in sums and np.size(g[name]) == 1:
+                    col = sums[name]
+                    e32 = max(e32, c.e32_of_row_sum(np.asarray(g32[col[0]])[col[1]], np.asarray(g[col[0]])[col[1]]))
+                err = c.report("vector S=%d B=%d" % (state_dim, bsz), name, got[name], g[name], e32, c.bound(e32))
+                if not err <= c.bound(e32):
+                    failed.append((bsz, name, err, c.bound(e32)))
+        assert not failed, failed
+    finally:
+        net.close()
+
+
 @pytest.mark.parametrize("kind", ["plain", "clip", "momentum"])
 def test_two_train_steps_against_the_oracle(kind):
     kw = {"USE_GRAD_CLIP": kind == "clip", "GRAD_CLIP_NORM": 2e-4 if kind == "clip" else 40.0,

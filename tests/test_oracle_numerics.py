@@ -119,3 +119,19 @@ def test_f32_restatement_close_to_f64():
     assert f32["p"].dtype == np.float32
     assert np.max(np.abs(f64["p"] - f32["p"])) < 1e-5
     assert np.max(np.abs(f64["v"] - f32["v"])) < 1e-5
+
+
+@pytest.mark.parametrize("use_log_softmax,min_policy", [(False, 0.0), (False, 0.01), (True, 0.0)])
+def test_f32_restatement_is_f32_throughout(use_log_softmax, min_policy):
+    """Handed float32 weights and rows, loss_and_grads returns float32 for every loss and tensor: nothing behind the loss
+    is silently upcast (np.where with a Python scalar was), so its distance from the float64 run is what float32 costs."""
+    p64, x, y, a = _case(4, 6, 5)
+    p32 = {k: v.astype(np.float32) for k, v in p64.items()}
+    kw = dict(use_log_softmax=use_log_softmax, min_policy=min_policy)
+    l32, g32 = o.loss_and_grads(p32, x.astype(np.float32), y.astype(np.float32), a.astype(np.float32), 0.01, **kw)
+    _, g64 = o.loss_and_grads(p64, x, y.astype(np.float32).astype(np.float64), a, 0.01, **kw)
+    assert all(np.asarray(v).dtype == np.float32 for v in l32.values())
+    for name, t in g32.items():
+        assert np.asarray(t).dtype == np.float32, name
+        scale = np.max(np.abs(g64[name]))
+        assert 0 < np.max(np.abs(t - g64[name])) / scale < 1e-5, name      # close, and not the float64 run in disguise
