@@ -11,7 +11,9 @@ class Config:
     # ---- what to run -------------------------------------------------------------------------
     GAME = 'PongDeterministic-v4'       # gym id, used by FRAME_SOURCE = 'gym' only; the offline sources are synthetic.
                                         # 'Pendulum-v0' (the fork's own default): the vector-state network and the
-                                        # restated Pendulum (NetworkVP_vector.py, EnvironmentPend.py)
+                                        # restated Pendulum (NetworkVP_vector.py, EnvironmentPend.py).
+                                        # 'CartPole-v0': the softmax head on a vector state and the restated CartPole
+                                        # (NetworkVP_discrate.py, EnvironmentCart.py)
     PLAY_MODE = False                   # greedy actions, no training, one agent (GA3C.py:46-54)
     TRAIN_MODELS = True
     LOAD_CHECKPOINT = False
@@ -78,6 +80,10 @@ class Config:
     OU_SIGMA = 0.3                      # OrnsteinUhlenbeckActionNoise's defaults (NetworkDDPG.py:466)
     OU_THETA = 0.15
     OU_DT = 1e-2
+    DENSE_LAYERS = (10, 10, 10, 10)     # widths of NetworkVP_discrate's dense layers (GAME = 'CartPole-v0'); `DENSE_LAYERS=64,64`
+    DENSE_STACK = 'fork'                # 'fork': every layer reads the state and only the last reaches the heads, as the
+                                        # reference builds them (NetworkVP_discrate.py:52-56); 'chained': layer i reads
+                                        # layer i - 1
     USE_NETWORK_TESTER = False
     RANDOM_SEED = 12345
 
@@ -136,18 +142,36 @@ class Config:
     FRAME_HISTORY = 0                   # planes of history per agent on the device; 0 = derived from the queue bounds
 
 
-VECTOR_GAMES = ('Pendulum-v0',)         # games whose state is a vector (Server.py:35-38 of the reference)
+VECTOR_GAMES = ('Pendulum-v0', 'CartPole-v0')      # games whose state is a vector (Server.py:35-43 of the reference)
+VECTOR_GAME_CONTINUOUS = {'Pendulum-v0': True, 'CartPole-v0': False}   # ... and which of them has a continuous action space
 
 
 def vector_game():
     return Config.GAME in VECTOR_GAMES
 
 
+def discrete_vector_game():
+    return vector_game() and not VECTOR_GAME_CONTINUOUS[Config.GAME]
+
+
 def resolve_action_space(explicit=()):
     """DISCRATE_INPUT = not CONTINUOUS_INPUT, as the reference's Server.py:36-38 sets it.  `explicit`: the keys the command
     line gave.  DISCRATE_INPUT given alone decides CONTINUOUS_INPUT; both given and contradictory (the same value) raise.
     GAME = 'Pendulum-v0' sets CONTINUOUS_INPUT = True, as the reference's Server.py:35-38 does; a command line that asks
-    for the discrete head with it raises."""
+    for the discrete head with it raises.  GAME = 'CartPole-v0' sets CONTINUOUS_INPUT = False (Server.py:40-43) and raises
+    on a command line that asks for the continuous head; DENSE_STACK is checked with it."""
+    if discrete_vector_game():
+        if ("CONTINUOUS_INPUT" in explicit and Config.CONTINUOUS_INPUT) or \
+                ("DISCRATE_INPUT" in explicit and not Config.DISCRATE_INPUT):
+            raise ValueError("GAME=%s has a discrete action space: CONTINUOUS_INPUT=%r / DISCRATE_INPUT=%r contradict it"
+                             % (Config.GAME, Config.CONTINUOUS_INPUT, Config.DISCRATE_INPUT))
+        if Config.DENSE_STACK not in ('fork', 'chained'):
+            raise ValueError("DENSE_STACK=%r: 'fork' or 'chained'" % (Config.DENSE_STACK,))
+        if Config.DUAL_RMSPROP:
+            raise ValueError("DUAL_RMSPROP with GAME=%s is not supported" % Config.GAME)
+        Config.CONTINUOUS_INPUT = False
+        Config.DISCRATE_INPUT = True
+        return
     if vector_game():
         if ("CONTINUOUS_INPUT" in explicit and not Config.CONTINUOUS_INPUT) or \
                 ("DISCRATE_INPUT" in explicit and Config.DISCRATE_INPUT):

@@ -12,7 +12,11 @@ def apply_argv(argv):
     given = set()
     for arg in argv:
         key, value = arg.split('=', 1)
-        setattr(Config, key, type(getattr(Config, key))(value))
+        current = getattr(Config, key)
+        if isinstance(current, tuple):      # DENSE_LAYERS=64,64 -> (64, 64); tuple("64,64") would give characters
+            setattr(Config, key, tuple(type(current[0])(v) for v in value.split(',') if v.strip()))
+        else:
+            setattr(Config, key, type(current)(value))
         given.add(key)
     resolve_action_space(given)
     resolve_ddpg(given)

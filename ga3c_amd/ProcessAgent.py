@@ -23,16 +23,17 @@ from datetime import datetime
 
 import numpy as np
 
-from Config import Config, vector_game
+from Config import Config, discrete_vector_game, vector_game
 from Environment import Environment, u8_to_f32
+import EnvironmentCart
 import EnvironmentPend
 from Experience import Experience
 import Transport as tp
 
 MP = mp.get_context("forkserver")     # children never inherit the server's HIP state
 # the fork server imports the agent's modules once; every agent then starts as a fork of that warm process
-MP.set_forkserver_preload(["numpy", "Config", "Experience", "Environment", "EnvironmentPend", "_native", "Transport",
-                           "ProcessAgent"])
+MP.set_forkserver_preload(["numpy", "Config", "Experience", "Environment", "EnvironmentPend", "EnvironmentCart", "_native",
+                           "Transport", "ProcessAgent"])
 
 
 def config_snapshot():
@@ -41,8 +42,10 @@ def config_snapshot():
 
 
 def make_environment(agent_id):
-    """The environment Config.GAME names: the restated Pendulum-v0 (a vector state, f32 in the transport whatever
-    STATE_TRANSPORT says) or the image-state source of Environment.py."""
+    """The environment Config.GAME names: the restated Pendulum-v0 or CartPole-v0 (a vector state, f32 in the transport
+    whatever STATE_TRANSPORT says) or the image-state source of Environment.py."""
+    if discrete_vector_game():
+        return EnvironmentCart.Environment(agent_id)
     return EnvironmentPend.Environment(agent_id) if vector_game() else Environment(agent_id)
 
 

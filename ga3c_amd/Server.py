@@ -4,8 +4,8 @@ learning rate and beta; services checkpoint requests (reference: ga3c/Server.py:
 What changed against the reference, and why:
   * prediction_q / training_q / wait_q are one shared-memory Transport (Transport.py) created
     before any agent starts;
-  * the model is the HIP-backed Network (NetworkVP.py, or NetworkVP_vector.py for GAME = 'Pendulum-v0'), selected where
-    the reference selects its TensorFlow class (Server.py:35-54);
+  * the model is the HIP-backed Network (NetworkVP.py, NetworkVP_vector.py for GAME = 'Pendulum-v0', NetworkVP_discrate.py
+    for GAME = 'CartPole-v0'), selected where the reference selects its TensorFlow class (Server.py:35-54);
   * agents are started from a forkserver, so they never inherit the server's HIP state.
 """
 import os
@@ -13,11 +13,13 @@ import queue
 import threading
 import time
 
-from Config import Config, resolve_action_space, resolve_ddpg, vector_game
+from Config import Config, discrete_vector_game, resolve_action_space, resolve_ddpg, vector_game
 import DataParallel
 from Environment import Environment
+import EnvironmentCart
 import EnvironmentPend
 from NetworkVP import Network, _device_ordinal
+import NetworkVP_discrate
 import NetworkVP_vector
 import NetworkDDPG
 import Placement
@@ -41,7 +43,7 @@ class Server:
         self.ddpg = bool(Config.USE_DDPG)
         self.replay_q = queue.Queue()
         self.replay = None
-        # GAME = 'Pendulum-v0': the vector-state network, f32 states of 4 S bytes, no frame front-end or state cache
+        # GAME = 'Pendulum-v0' / 'CartPole-v0': a vector-state network, f32 states of 4 S bytes, no frame front-end or state cache
         self.vector = vector_game()
         if self.vector:
             if Config.HOGWILD:
@@ -78,7 +80,8 @@ class Server:
         # instead of carrying them -- a trainer's batch no longer crosses PCIe a second time (include/ga3c_abi.h).  Only with
         # everything it rests on: the GPU reading the transport itself, uint8 states, the native pipelined predictor loop,
         # plain launches; anything else keeps the states in the rollouts.
-        model_cls = (NetworkVP_vector.Network if self.vector else Network) if model is None else type(model)
+        vector_cls = NetworkVP_discrate.Network if discrete_vector_game() else NetworkVP_vector.Network
+        model_cls = (vector_cls if self.vector else Network) if model is None else type(model)
         if self.ddpg:
             if model is None:
                 model_cls = NetworkDDPG.Network
@@ -387,12 +390,16 @@ class Server:
 
     @staticmethod
     def get_state_dim():
+        if discrete_vector_game():
+            return EnvironmentCart.Environment.get_state_dim()
         if vector_game():
             return EnvironmentPend.Environment.get_state_dim()
         return Environment.get_state_dim()
 
     @staticmethod
     def get_num_action():
+        if discrete_vector_game():
+            return EnvironmentCart.NUM_ACTIONS
         if vector_game():
             return EnvironmentPend.NUM_ACTIONS
         if Config.FRAME_SOURCE == 'gym':       # as the reference asks a throw-away Environment (Server.py:200-202);

@@ -41,6 +41,14 @@ class MlpConfig(C.Structure):     # include/ga3c_abi.h: ga3c_mlp_config
                 ("rmsprop_epsilon", C.c_float), ("grad_clip_norm", C.c_float), ("predict_lanes", C.c_int32)]
 
 
+class DmlpConfig(C.Structure):    # include/ga3c_abi.h: ga3c_dmlp_config
+    _fields_ = [("device", C.c_int32), ("state_dim", C.c_int32), ("num_actions", C.c_int32), ("max_batch", C.c_int32),
+                ("num_layers", C.c_int32), ("widths", C.c_int32 * 8), ("chained", C.c_int32), ("flags", C.c_uint32),
+                ("rmsprop_decay", C.c_float), ("rmsprop_momentum", C.c_float), ("rmsprop_epsilon", C.c_float),
+                ("grad_clip_norm", C.c_float), ("log_epsilon", C.c_float), ("min_policy", C.c_float),
+                ("predict_lanes", C.c_int32)]
+
+
 class DdpgConfig(C.Structure):    # include/ga3c_abi.h: ga3c_ddpg_config
     _fields_ = [("device", C.c_int32), ("state_dim", C.c_int32), ("num_actions", C.c_int32), ("max_batch", C.c_int32),
                 ("replay_capacity", C.c_int32), ("predict_lanes", C.c_int32), ("flags", C.c_uint32),
@@ -162,6 +170,35 @@ HIP_SIGNATURES = {
     "ga3c_mlp_upload": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32]),
     "ga3c_mlp_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
     "ga3c_mlp_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
+    # the discrete-action vector-state network (GAME = 'CartPole-v0'), include/ga3c_abi.h: ga3c_dmlp_*
+    "ga3c_dmlp_create": (C.c_int, [C.POINTER(DmlpConfig), C.POINTER(C.c_void_p)]),
+    "ga3c_dmlp_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_dmlp_param_count": (C.c_int, [C.c_void_p, i64p]),
+    "ga3c_dmlp_get_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_dmlp_set_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_dmlp_get_step": (C.c_int, [C.c_void_p, i64p]),
+    "ga3c_dmlp_set_step": (C.c_int, [C.c_void_p, C.c_int64]),
+    "ga3c_dmlp_num_params": (C.c_int32, [C.c_void_p]),
+    "ga3c_dmlp_param_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
+    "ga3c_dmlp_param_info": (C.c_int, [C.c_void_p, C.c_char_p, i64p, i64p, i32p, i64p]),
+    "ga3c_dmlp_get_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_dmlp_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "ga3c_dmlp_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "ga3c_dmlp_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "ga3c_dmlp_predict": (C.c_int, [C.c_void_p, f32p, C.c_int32, f32p, f32p, f32p]),
+    "ga3c_dmlp_train": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
+    "ga3c_dmlp_compute_grads": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, f32p]),
+    "ga3c_dmlp_apply_grads": (C.c_int, [C.c_void_p, C.c_float]),
+    "ga3c_dmlp_evaluate": (C.c_int, [C.c_void_p, f32p, i64p, f32p, f32p, C.c_int32, C.c_float, f32p, f32p, f32p, f32p]),
+    "ga3c_dmlp_register_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "ga3c_dmlp_unregister_host": (C.c_int, [C.c_void_p]),
+    "ga3c_dmlp_predict_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, f32p, f32p, f32p]),
+    "ga3c_dmlp_predict_gather_begin": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, i32p]),
+    "ga3c_dmlp_predict_gather_end": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f32p, f32p]),
+    "ga3c_dmlp_train_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
+    "ga3c_dmlp_upload": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32]),
+    "ga3c_dmlp_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
+    "ga3c_dmlp_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
     # DDPG (USE_DDPG), include/ga3c_abi.h: ga3c_ddpg_*
     "ga3c_ddpg_create": (C.c_int, [C.POINTER(DdpgConfig), C.POINTER(C.c_void_p)]),
     "ga3c_ddpg_destroy": (C.c_int, [C.c_void_p]),

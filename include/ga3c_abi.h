@@ -401,6 +401,91 @@ int ga3c_mlp_time_resident(ga3c_mlp* net, int32_t mode, int32_t batch, int32_t i
  * "lossrow"}; count = rows x width. */
 int ga3c_mlp_fetch(ga3c_mlp* net, const char* name, float* out, int64_t count);
 
+/* ---- The discrete-action vector-state network: reference NetworkVP_discrate.py:39-130, the network of GAME = 'CartPole-v0'
+ * (DESIGN.md 8g).  x[B,S] -> dense1_<i>_p (w_i, sigmoid), i = 1..L -> logits_v (1) and logits_p (A) -> softmax; both loss
+ * branches (GA3C_FLAG_LOG_SOFTMAX, min_policy, log_epsilon), gradient, RMSProp and GA3C_FLAG_GRAD_CLIP as there.
+ *   chained = 0 (the reference, :52-56): every layer is [S, w_i] and reads x; only layer L reaches the heads.  Layers
+ *     1..L-1 are variables that nothing reads: their gradient is exactly 0, and train / apply_grads / the clip pass leave
+ *     their value, `ms` and `mom` untouched (TF-1 drops a variable whose gradient is None).  The reference's clip branch
+ *     (:120-122) would raise on them; skipping them there too is this library's definition.
+ *   chained = 1: layer i reads layer i - 1 ([w_{i-1}, w_i]); every variable is live.
+ * A handle of its own with ga3c_mlp's conventions: int return codes, ga3c_last_error(), arenas 0 weights / 1 `ms` / 2 `mom`
+ * / 3 last gradient, one HIP stream for every kernel and copy (a prediction sees the weights before or after a train step,
+ * never a mix), a lane per prediction in flight, train-type calls serialised.
+ *
+ * Arena (TF creation order, 2 L + 4 variables): dense1_1_p/w /b ... dense1_L_p/w /b logits_v/w[w_L,1] /b[1]
+ * logits_p/w[w_L,A] /b[A]; 4 x 50 + 11 + 11 A floats at S = 4 and the default widths (10, 10, 10, 10).
+ * Checkpoints: the .npz container of ga3c_net_save with these names.  A file of another network kind, or of this kind with
+ * a variable missing, of another shape, or with more layers, refuses to load (GA3C_ESTATE, network untouched); the file
+ * carries variables, not the graph, so two wirings whose shapes coincide load into each other. */
+#define GA3C_DMLP_MAX_LAYERS 8
+typedef struct ga3c_dmlp ga3c_dmlp;
+typedef struct ga3c_dmlp_config {
+  int32_t device;
+  int32_t state_dim;       /* S, 1..64 (CartPole: 4) */
+  int32_t num_actions;     /* A, 1..32 (CartPole: 2) */
+  int32_t max_batch;       /* rows of one predict / train call */
+  int32_t num_layers;      /* L, 1..8 (Config.DENSE_LAYERS) */
+  int32_t widths[GA3C_DMLP_MAX_LAYERS];   /* w_1..w_L, 1..256 each */
+  int32_t chained;         /* 0: the reference's wiring; 1: layer i reads layer i - 1 */
+  uint32_t flags;          /* GA3C_FLAG_LOG_SOFTMAX | GA3C_FLAG_GRAD_CLIP; anything else: GA3C_EINVAL */
+  float rmsprop_decay;
+  float rmsprop_momentum;
+  float rmsprop_epsilon;
+  float grad_clip_norm;
+  float log_epsilon;
+  float min_policy;
+  int32_t predict_lanes;   /* predictions in flight at once (begun and not ended); 0 -> 4 */
+} ga3c_dmlp_config;
+
+int ga3c_dmlp_create(const ga3c_dmlp_config* cfg, ga3c_dmlp** out);   /* weights zero until set_arena(0) */
+int ga3c_dmlp_destroy(ga3c_dmlp* net);
+int ga3c_dmlp_param_count(ga3c_dmlp* net, int64_t* count);
+int ga3c_dmlp_get_arena(ga3c_dmlp* net, int32_t which, float* out, int64_t count);      /* which 0..3 */
+int ga3c_dmlp_set_arena(ga3c_dmlp* net, int32_t which, const float* in, int64_t count); /* which 0..2 */
+int ga3c_dmlp_get_step(ga3c_dmlp* net, int64_t* step);
+int ga3c_dmlp_set_step(ga3c_dmlp* net, int64_t step);
+int32_t ga3c_dmlp_num_params(ga3c_dmlp* net);                         /* 2 L + 4 */
+const char* ga3c_dmlp_param_name(ga3c_dmlp* net, int32_t index);      /* arena order; NULL outside [0, 2 L + 4) */
+int ga3c_dmlp_param_info(ga3c_dmlp* net, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]);
+int ga3c_dmlp_get_param(ga3c_dmlp* net, const char* name, int32_t which, float* out, int64_t count);
+int ga3c_dmlp_set_param(ga3c_dmlp* net, const char* name, int32_t which, const float* in, int64_t count);
+int ga3c_dmlp_save(ga3c_dmlp* net, const char* path);
+int ga3c_dmlp_load(ga3c_dmlp* net, const char* path);
+/* x f32[B,S] -> p f32[B,A] (the policy), v f32[B]; z f32[B,A] the logits if not NULL.  1 launch. */
+int ga3c_dmlp_predict(ga3c_dmlp* net, const float* x, int32_t batch, float* p, float* v, float* z);
+/* One step: y_r f32[B], a f32[B,A] one-hot rows of the actions taken; losses (may be NULL) = {cost_p_1_agg, cost_p_2_agg,
+ * cost_v}.  2 launches (3 with GA3C_FLAG_GRAD_CLIP); the row sums run in row order: the same call gives the same bits. */
+int ga3c_dmlp_train(ga3c_dmlp* net, const float* x, const float* y_r, const float* a, int32_t batch, float learning_rate,
+                    float beta, float* losses);
+int ga3c_dmlp_compute_grads(ga3c_dmlp* net, const float* x, const float* y_r, const float* a, int32_t batch, float beta,
+                            float* losses);                                    /* gradient into arena 3, no update */
+int ga3c_dmlp_apply_grads(ga3c_dmlp* net, float learning_rate);               /* (clip +) RMSProp on arena 3, step += 1 */
+/* Forward + loss, no update (2 launches): the states are x (host rows) or offsets (rows of the registered segment), exactly
+ * one.  lastdense f32[B,w_L], v f32[B], p f32[B,A] (each may be NULL): what the reference's summary histograms
+ * (NetworkVP_discrate.py:143-146) look at. */
+int ga3c_dmlp_evaluate(ga3c_dmlp* net, const float* x, const int64_t* offsets, const float* y_r, const float* a, int32_t batch,
+                       float beta, float* losses, float* lastdense, float* v, float* p);
+/* Zero-copy intake, as ga3c_mlp_*: rows are S f32 at 4-byte aligned byte offsets into the registered segment; u8 must be 0.
+ * predict_gather / _begin / _end have the signatures of ga3c_predict_rows_fn, ga3c_predict_begin_fn and ga3c_predict_end_fn
+ * (include/ga3c_host.h), so the native predictor loops drive this network unchanged. */
+int ga3c_dmlp_register_host(ga3c_dmlp* net, void* base, int64_t bytes);
+int ga3c_dmlp_unregister_host(ga3c_dmlp* net);
+int ga3c_dmlp_predict_gather(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v, float* z);
+int ga3c_dmlp_predict_gather_begin(void* net, const int64_t* offsets, int32_t batch, int32_t u8, int32_t* ticket);
+int ga3c_dmlp_predict_gather_end(void* net, int32_t ticket, int32_t batch, float* p, float* v);
+int ga3c_dmlp_train_gather(ga3c_dmlp* net, const int64_t* offsets, int32_t u8, const float* y_r, const float* a, int32_t batch,
+                           float learning_rate, float beta, float* losses);
+/* Timing: upload stages a batch in HBM; time_resident runs `iters` steps on its first `batch` rows (mode 0 predict,
+ * 1 train) between two events on the network's stream -> milliseconds. */
+int ga3c_dmlp_upload(ga3c_dmlp* net, const float* x, const float* y_r, const float* a, int32_t batch);
+int ga3c_dmlp_time_resident(ga3c_dmlp* net, int32_t mode, int32_t batch, int32_t iters, float learning_rate, float beta,
+                            float* elapsed_ms);
+/* Rows of the last train / compute_grads / evaluate / resident step, for tests: name in {"x", "h<i>" (output of layer
+ * i = 1..L), "dh<i>" (the delta at its pre-activation), "v", "z", "p", "dv", "dz", "lossrow"}; count = rows x width.  A layer
+ * nothing reads has neither rows nor a name here (GA3C_EINVAL). */
+int ga3c_dmlp_fetch(ga3c_dmlp* net, const char* name, float* out, int64_t count);
+
 /* ---- DDPG: reference NetworkDDPG.py (USE_DDPG with CONTINUOUS_INPUT), with the replay memory in HBM.
  *   actor   x[B,S] -> actor_fc1 (400) -> actor_norm1 -> relu -> actor_fc2 (300) -> actor_norm2 -> relu -> actor_output (A, tanh)
  *   critic  x -> critic_fc1 (400) -> critic_norm1 -> relu = h;  q = critic_output(relu(h W_fc2 + a W_n2 + b_n2)), W_n2 / b_n2
