@@ -140,65 +140,13 @@ HIP_SIGNATURES = {
     "ga3c_net_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ga3c_net_allreduce_grads": (C.c_int, [C.c_void_p]),
     "ga3c_net_time_allreduce": (C.c_int, [C.c_void_p, C.c_int32, f32p]),
-    # the vector-state network (GAME = 'Pendulum-v0'), include/ga3c_abi.h: ga3c_mlp_*
+    # the vector-state networks, include/ga3c_abi.h: ga3c_mlp_* (GAME = 'Pendulum-v0') and ga3c_dmlp_* (GAME = 'CartPole-v0').
+    # What the two lists share is VECNET_SIGNATURES below; create and evaluate are each network's own.
     "ga3c_mlp_create": (C.c_int, [C.POINTER(MlpConfig), C.POINTER(C.c_void_p)]),
-    "ga3c_mlp_destroy": (C.c_int, [C.c_void_p]),
-    "ga3c_mlp_param_count": (C.c_int, [C.c_void_p, i64p]),
-    "ga3c_mlp_get_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_mlp_set_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_mlp_get_step": (C.c_int, [C.c_void_p, i64p]),
-    "ga3c_mlp_set_step": (C.c_int, [C.c_void_p, C.c_int64]),
-    "ga3c_mlp_num_params": (C.c_int32, [C.c_void_p]),
-    "ga3c_mlp_param_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
-    "ga3c_mlp_param_info": (C.c_int, [C.c_void_p, C.c_char_p, i64p, i64p, i32p, i64p]),
-    "ga3c_mlp_get_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_mlp_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_mlp_save": (C.c_int, [C.c_void_p, C.c_char_p]),
-    "ga3c_mlp_load": (C.c_int, [C.c_void_p, C.c_char_p]),
-    "ga3c_mlp_predict": (C.c_int, [C.c_void_p, f32p, C.c_int32, f32p, f32p, f32p]),
-    "ga3c_mlp_train": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
-    "ga3c_mlp_compute_grads": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, f32p]),
-    "ga3c_mlp_apply_grads": (C.c_int, [C.c_void_p, C.c_float]),
     "ga3c_mlp_evaluate": (C.c_int, [C.c_void_p, f32p, i64p, f32p, f32p, C.c_int32, C.c_float, f32p, f32p, f32p, f32p, f32p,
                                     f32p]),
-    "ga3c_mlp_register_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
-    "ga3c_mlp_unregister_host": (C.c_int, [C.c_void_p]),
-    "ga3c_mlp_predict_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, f32p, f32p, f32p]),
-    "ga3c_mlp_predict_gather_begin": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, i32p]),
-    "ga3c_mlp_predict_gather_end": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f32p, f32p]),
-    "ga3c_mlp_train_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
-    "ga3c_mlp_upload": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32]),
-    "ga3c_mlp_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
-    "ga3c_mlp_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
-    # the discrete-action vector-state network (GAME = 'CartPole-v0'), include/ga3c_abi.h: ga3c_dmlp_*
     "ga3c_dmlp_create": (C.c_int, [C.POINTER(DmlpConfig), C.POINTER(C.c_void_p)]),
-    "ga3c_dmlp_destroy": (C.c_int, [C.c_void_p]),
-    "ga3c_dmlp_param_count": (C.c_int, [C.c_void_p, i64p]),
-    "ga3c_dmlp_get_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_dmlp_set_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_dmlp_get_step": (C.c_int, [C.c_void_p, i64p]),
-    "ga3c_dmlp_set_step": (C.c_int, [C.c_void_p, C.c_int64]),
-    "ga3c_dmlp_num_params": (C.c_int32, [C.c_void_p]),
-    "ga3c_dmlp_param_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
-    "ga3c_dmlp_param_info": (C.c_int, [C.c_void_p, C.c_char_p, i64p, i64p, i32p, i64p]),
-    "ga3c_dmlp_get_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_dmlp_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
-    "ga3c_dmlp_save": (C.c_int, [C.c_void_p, C.c_char_p]),
-    "ga3c_dmlp_load": (C.c_int, [C.c_void_p, C.c_char_p]),
-    "ga3c_dmlp_predict": (C.c_int, [C.c_void_p, f32p, C.c_int32, f32p, f32p, f32p]),
-    "ga3c_dmlp_train": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
-    "ga3c_dmlp_compute_grads": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, f32p]),
-    "ga3c_dmlp_apply_grads": (C.c_int, [C.c_void_p, C.c_float]),
     "ga3c_dmlp_evaluate": (C.c_int, [C.c_void_p, f32p, i64p, f32p, f32p, C.c_int32, C.c_float, f32p, f32p, f32p, f32p]),
-    "ga3c_dmlp_register_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
-    "ga3c_dmlp_unregister_host": (C.c_int, [C.c_void_p]),
-    "ga3c_dmlp_predict_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, f32p, f32p, f32p]),
-    "ga3c_dmlp_predict_gather_begin": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, i32p]),
-    "ga3c_dmlp_predict_gather_end": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f32p, f32p]),
-    "ga3c_dmlp_train_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
-    "ga3c_dmlp_upload": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32]),
-    "ga3c_dmlp_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
-    "ga3c_dmlp_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
     # DDPG (USE_DDPG), include/ga3c_abi.h: ga3c_ddpg_*
     "ga3c_ddpg_create": (C.c_int, [C.POINTER(DdpgConfig), C.POINTER(C.c_void_p)]),
     "ga3c_ddpg_destroy": (C.c_int, [C.c_void_p]),
@@ -230,6 +178,37 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
     "ga3c_ddpg_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, f32p]),
 }
+
+VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first
+    "destroy": (C.c_int, [C.c_void_p]),
+    "param_count": (C.c_int, [C.c_void_p, i64p]),
+    "get_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
+    "set_arena": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_int64]),
+    "get_step": (C.c_int, [C.c_void_p, i64p]),
+    "set_step": (C.c_int, [C.c_void_p, C.c_int64]),
+    "num_params": (C.c_int32, [C.c_void_p]),
+    "param_name": (C.c_char_p, [C.c_void_p, C.c_int32]),
+    "param_info": (C.c_int, [C.c_void_p, C.c_char_p, i64p, i64p, i32p, i64p]),
+    "get_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, f32p, C.c_int64]),
+    "save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "predict": (C.c_int, [C.c_void_p, f32p, C.c_int32, f32p, f32p, f32p]),
+    "train": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
+    "compute_grads": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32, C.c_float, f32p]),
+    "apply_grads": (C.c_int, [C.c_void_p, C.c_float]),
+    "register_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "unregister_host": (C.c_int, [C.c_void_p]),
+    "predict_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, f32p, f32p, f32p]),
+    "predict_gather_begin": (C.c_int, [C.c_void_p, i64p, C.c_int32, C.c_int32, i32p]),
+    "predict_gather_end": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f32p, f32p]),
+    "train_gather": (C.c_int, [C.c_void_p, i64p, C.c_int32, f32p, f32p, C.c_int32, C.c_float, C.c_float, f32p]),
+    "upload": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int32]),
+    "time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
+    "fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
+}
+HIP_SIGNATURES.update(("%s_%s" % (prefix, entry), sig) for prefix in ("ga3c_mlp", "ga3c_dmlp")
+                      for entry, sig in VECNET_SIGNATURES.items())
 
 HOST_SIGNATURES = {
     "ga3c_host_last_error": (C.c_char_p, []),

@@ -17,24 +17,17 @@
 // A train step is 2 launches without USE_GRAD_CLIP and 3 with it; a prediction is 1.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <map>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
-#include "../../include/ga3c_abi.h"
-#include "ga3c_checkpoint.hpp"
-
-void ga3c_set_last_error(const char* msg);   // ga3c_engine.hip: the thread's ga3c_last_error() message
+#include "ga3c_vecnet.hpp"
 
 namespace ga3c_vec {
+
+using namespace ga3c_vecnet;   // Input, Opt, PREDICT / EVAL / TRAIN and the host half
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -103,19 +96,6 @@ struct Work {
   float* lossrow;      // [B,3]
   float* losses;       // [3]
 };
-
-struct Input {         // row r of the batch: S floats at base + (off ? off[r] : r * stride) bytes
-  const char* base;
-  const int64_t* off;
-  int64_t stride;
-};
-
-struct Opt {           // TF-1 ApplyRMSProp: ms += (g*g - ms)(1-rho); mom = mom*mu + g*lr/sqrt(eps+ms); theta -= mom
-  float* theta; float* ms; float* mom; float* grad;
-  float lr, omr, mu, eps, clip;
-};
-
-enum { PREDICT = 0, EVAL = 1, TRAIN = 2 };
 
 __device__ __forceinline__ float sigm(float h) { return 1.0f / (1.0f + expf(-h)); }
 
@@ -415,66 +395,61 @@ __global__ void mlp_loss_kernel(Work w, int B) {
 
 // ------------------------------------------------------------------ host side
 
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  ga3c_set_last_error(buf);
-  return code;
-}
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) {                                                                           \
-      (void)hipGetLastError();                                                                        \
-      return fail(GA3C_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    }                                                                                                 \
-  } while (0)
-#define CHK(expr)                 \
-  do {                            \
-    int _r = (expr);              \
-    if (_r != GA3C_OK) return _r; \
-  } while (0)
-
-struct PLane {                    // one prediction in flight: pinned staging + device outputs + completion event
-  int64_t* h_off = nullptr; float* h_x = nullptr; float* h_p = nullptr; float* h_v = nullptr; float* h_z = nullptr;
-  int64_t* d_off = nullptr; float* d_x = nullptr; float* d_p = nullptr; float* d_v = nullptr; float* d_z = nullptr;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
-  int B = 0;
-};
-
 }  // namespace ga3c_vec
 
 using namespace ga3c_vec;
 
-struct ga3c_mlp {
+struct ga3c_mlp : Net {
   ga3c_mlp_config cfg;
   Layout L;
-  int64_t n = 0;
-  bool clip = false;
-  hipStream_t st = nullptr;       // every kernel and copy of the network: a prediction sees the weights before or after a
-                                  // train step, never a mix, and needs no second buffer
-  std::mutex mu;                  // enqueue order on `st` and the lanes' bookkeeping
-  std::condition_variable lane_cv;
-  std::mutex train_mu;            // one train / evaluate / arena call at a time (they share the staging below)
-  std::vector<PLane> lanes;
-  float* arena[4] = {nullptr, nullptr, nullptr, nullptr};   // theta, ms, mom, grad
   Work w{};
   float* work_base = nullptr;
-  // train staging: pinned host + device
-  float* h_x = nullptr; float* h_y = nullptr; float* h_a = nullptr; int64_t* h_off = nullptr; float* h_loss = nullptr;
-  float* d_x = nullptr; float* d_y = nullptr; float* d_a = nullptr; int64_t* d_off = nullptr;
-  hipEvent_t tev = nullptr, t0 = nullptr, t1 = nullptr;
-  int last_B = 0;                 // rows of the last train / evaluate / resident step (fetch)
-  int res_B = 0;                  // rows uploaded for the resident path
-  std::atomic<int64_t> step{0};
-  const char* reg_host = nullptr;
-  const char* reg_dev = nullptr;
-  int64_t reg_bytes = 0;
+
+  int alloc_work(size_t B) {      // per-row workspace, one block
+    const size_t S = L.S, A = L.A;
+    return carve_rows(B, {S, 4, 256, 256, 100, 64, 4, 256, 256, 100, 64, 1, 2 * A, A, 1, 2 * A, 3},
+                      {&w.x, &w.act[0], &w.act[1], &w.act[2], &w.act[3], &w.act[4], &w.del[0], &w.del[1], &w.del[2], &w.del[3],
+                       &w.del[4], &w.v, &w.z, &w.p, &w.dv, &w.dz, &w.lossrow},
+                      &work_base, &w.losses);
+  }
+
+  void free_work() { (void)hipFree(work_base); }
+
+  GradSrc grad_src() const {
+    GradSrc g;
+    const int A = L.A;
+    g.in[0] = w.x;
+    for (int l = 1; l < NTRUNK; ++l) g.in[l] = w.act[l - 1];
+    g.in[5] = g.in[6] = g.in[7] = w.act[4];
+    for (int l = 0; l < NTRUNK; ++l) {
+      g.d[l] = w.del[l];
+      g.d_ld[l] = TRUNK_OUT[l];
+    }
+    g.d[5] = w.dv;       g.d_ld[5] = 1;
+    g.d[6] = w.dz;       g.d_ld[6] = 2 * A;
+    g.d[7] = w.dz + A;   g.d_ld[7] = 2 * A;
+    return g;
+  }
+
+  void rows(int mode, const Input& in, int B, float beta, float* p, float* v, float* z) {
+    const auto kernel = mode == PREDICT ? mlp_tile_kernel<PREDICT> : mode == EVAL ? mlp_tile_kernel<EVAL> : mlp_tile_kernel<TRAIN>;
+    const float* y = mode == PREDICT ? nullptr : d_y;
+    const float* a = mode == PREDICT ? nullptr : d_a;
+    hipLaunchKernelGGL(kernel, dim3((B + TILE - 1) / TILE), dim3(THREADS), 0, st, L, (const float*)arena[0], in, y, a, B, beta, w,
+                       p, v, z);
+  }
+
+  void wgrad(int B, const Opt& o, bool fused) {
+    const auto kernel = fused ? mlp_wgrad_kernel<true> : mlp_wgrad_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((int)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, L, grad_src(), B, o, w);
+  }
+
+  void update(const Opt& o, bool clipped) {
+    const auto kernel = clipped ? mlp_update_kernel<true> : mlp_update_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(NVARS), dim3(THREADS), 0, st, L, o);
+  }
+
+  void loss(int B) { hipLaunchKernelGGL(mlp_loss_kernel, dim3(1), dim3(64), 0, st, w, B); }
 };
 
 namespace {
@@ -509,319 +484,6 @@ float* work_ptr(ga3c_mlp* m, const std::string& name) {
   return nullptr;
 }
 
-GradSrc grad_src(ga3c_mlp* m) {
-  GradSrc g;
-  const int A = m->L.A;
-  g.in[0] = m->w.x;
-  for (int l = 1; l < NTRUNK; ++l) g.in[l] = m->w.act[l - 1];
-  g.in[5] = g.in[6] = g.in[7] = m->w.act[4];
-  for (int l = 0; l < NTRUNK; ++l) {
-    g.d[l] = m->w.del[l];
-    g.d_ld[l] = TRUNK_OUT[l];
-  }
-  g.d[5] = m->w.dv;       g.d_ld[5] = 1;
-  g.d[6] = m->w.dz;       g.d_ld[6] = 2 * A;
-  g.d[7] = m->w.dz + A;   g.d_ld[7] = 2 * A;
-  return g;
-}
-
-Opt make_opt(ga3c_mlp* m, float lr) {
-  Opt o;
-  o.theta = m->arena[0]; o.ms = m->arena[1]; o.mom = m->arena[2]; o.grad = m->arena[3];
-  o.lr = lr;
-  o.omr = 1.0f - m->cfg.rmsprop_decay;
-  o.mu = m->cfg.rmsprop_momentum;
-  o.eps = m->cfg.rmsprop_epsilon;
-  o.clip = m->cfg.grad_clip_norm;
-  return o;
-}
-
-int tiles(int B) { return (B + TILE - 1) / TILE; }
-
-// Enqueue the row kernel on `in` (caller holds mu).  TRAIN: + the weight gradients and, apply != 0, the update.
-int enqueue_train(ga3c_mlp* m, const Input& in, int B, float beta, bool apply, float lr) {
-  hipLaunchKernelGGL(mlp_tile_kernel<TRAIN>, dim3(tiles(B)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in,
-                     (const float*)m->d_y, (const float*)m->d_a, B, beta, m->w, m->w.p, m->w.v, m->w.z);
-  const Opt o = make_opt(m, lr);
-  const int gblocks = (int)((m->n + THREADS - 1) / THREADS);
-  if (apply && !m->clip)
-    hipLaunchKernelGGL(mlp_wgrad_kernel<true>, dim3(gblocks), dim3(THREADS), 0, m->st, m->L, grad_src(m), B, o, m->w);
-  else
-    hipLaunchKernelGGL(mlp_wgrad_kernel<false>, dim3(gblocks), dim3(THREADS), 0, m->st, m->L, grad_src(m), B, o, m->w);
-  if (apply && m->clip) hipLaunchKernelGGL(mlp_update_kernel<true>, dim3(NVARS), dim3(THREADS), 0, m->st, m->L, o);
-  HIPCHK(hipGetLastError());
-  return GA3C_OK;
-}
-
-int enqueue_apply(ga3c_mlp* m, float lr) {
-  const Opt o = make_opt(m, lr);
-  if (m->clip) hipLaunchKernelGGL(mlp_update_kernel<true>, dim3(NVARS), dim3(THREADS), 0, m->st, m->L, o);
-  else hipLaunchKernelGGL(mlp_update_kernel<false>, dim3(NVARS), dim3(THREADS), 0, m->st, m->L, o);
-  HIPCHK(hipGetLastError());
-  return GA3C_OK;
-}
-
-int check_batch(ga3c_mlp* m, int B) {
-  if (B < 1 || B > m->cfg.max_batch) return fail(GA3C_EINVAL, "batch %d outside [1,%d]", B, m->cfg.max_batch);
-  return GA3C_OK;
-}
-
-// offsets of rows in the registered segment: each must hold S whole floats inside it
-int check_offsets(ga3c_mlp* m, const int64_t* off, int B) {
-  if (!m->reg_dev) return fail(GA3C_ESTATE, "no host segment registered");
-  const int64_t row = 4 * (int64_t)m->L.S;
-  for (int i = 0; i < B; ++i)
-    if (off[i] < 0 || off[i] % 4 != 0 || off[i] > m->reg_bytes - row)
-      return fail(GA3C_EINVAL, "offset %lld of row %d is not a 4-byte aligned row of %lld bytes inside the %lld-byte segment",
-                  (long long)off[i], i, (long long)row, (long long)m->reg_bytes);
-  return GA3C_OK;
-}
-
-// Stages y_r / a and the states (x: host rows, or offsets into the registered segment) of a train-type call; caller holds
-// train_mu.  Returns the Input the row kernel reads.
-int stage_train(ga3c_mlp* m, const float* x, const int64_t* off, const float* y, const float* a, int B, Input* in) {
-  const int S = m->L.S, A = m->L.A;
-  memcpy(m->h_y, y, sizeof(float) * B);
-  memcpy(m->h_a, a, sizeof(float) * B * A);
-  HIPCHK(hipMemcpyAsync(m->d_y, m->h_y, sizeof(float) * B, hipMemcpyHostToDevice, m->st));
-  HIPCHK(hipMemcpyAsync(m->d_a, m->h_a, sizeof(float) * B * A, hipMemcpyHostToDevice, m->st));
-  if (off) {
-    CHK(check_offsets(m, off, B));
-    memcpy(m->h_off, off, sizeof(int64_t) * B);
-    HIPCHK(hipMemcpyAsync(m->d_off, m->h_off, sizeof(int64_t) * B, hipMemcpyHostToDevice, m->st));
-    *in = Input{m->reg_dev, m->d_off, 0};
-  } else {
-    memcpy(m->h_x, x, sizeof(float) * B * S);
-    HIPCHK(hipMemcpyAsync(m->d_x, m->h_x, sizeof(float) * B * S, hipMemcpyHostToDevice, m->st));
-    *in = Input{reinterpret_cast<const char*>(m->d_x), nullptr, 4 * (int64_t)S};
-  }
-  return GA3C_OK;
-}
-
-int finish_train(ga3c_mlp* m, float* losses) {
-  HIPCHK(hipMemcpyAsync(m->h_loss, m->w.losses, 3 * sizeof(float), hipMemcpyDeviceToHost, m->st));
-  HIPCHK(hipEventRecord(m->tev, m->st));
-  return GA3C_OK;
-}
-
-int wait_train(ga3c_mlp* m, float* losses) {
-  HIPCHK(hipEventSynchronize(m->tev));
-  if (losses) memcpy(losses, m->h_loss, 3 * sizeof(float));
-  return GA3C_OK;
-}
-
-// train / compute_grads on host rows or on offsets
-int train_common(ga3c_mlp* m, const float* x, const int64_t* off, const float* y, const float* a, int B, bool apply, float lr,
-                 float beta, float* losses) {
-  if (!m || (!x && !off) || !y || !a) return fail(GA3C_EINVAL, "null argument");
-  CHK(check_batch(m, B));
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    Input in;
-    CHK(stage_train(m, x, off, y, a, B, &in));
-    CHK(enqueue_train(m, in, B, beta, apply, lr));
-    CHK(finish_train(m, losses));
-    m->last_B = B;
-  }
-  CHK(wait_train(m, losses));
-  if (apply) m->step.fetch_add(1);
-  return GA3C_OK;
-}
-
-PLane* take_lane(ga3c_mlp* m, std::unique_lock<std::mutex>& lk, int* ticket) {
-  for (;;) {
-    for (size_t i = 0; i < m->lanes.size(); ++i)
-      if (!m->lanes[i].busy) {
-        m->lanes[i].busy = true;
-        *ticket = (int)i;
-        return &m->lanes[i];
-      }
-    m->lane_cv.wait(lk);
-  }
-}
-
-void give_lane(ga3c_mlp* m, PLane* P) {
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    P->busy = false;
-  }
-  m->lane_cv.notify_one();
-}
-
-// Enqueues one prediction on a lane of its own (x: host rows; off: rows of the registered segment).
-int predict_begin(ga3c_mlp* m, const float* x, const int64_t* off, int B, int* ticket) {
-  CHK(check_batch(m, B));
-  HIPCHK(hipSetDevice(m->cfg.device));
-  if (off) {
-    CHK(check_offsets(m, off, B));
-  }
-  std::unique_lock<std::mutex> lk(m->mu);
-  PLane* P = take_lane(m, lk, ticket);
-  const int S = m->L.S, A = m->L.A;
-  Input in;
-  hipError_t e = hipSuccess;
-  if (off) {
-    memcpy(P->h_off, off, sizeof(int64_t) * B);
-    e = hipMemcpyAsync(P->d_off, P->h_off, sizeof(int64_t) * B, hipMemcpyHostToDevice, m->st);
-    in = Input{m->reg_dev, P->d_off, 0};
-  } else {
-    memcpy(P->h_x, x, sizeof(float) * B * S);
-    e = hipMemcpyAsync(P->d_x, P->h_x, sizeof(float) * B * S, hipMemcpyHostToDevice, m->st);
-    in = Input{reinterpret_cast<const char*>(P->d_x), nullptr, 4 * (int64_t)S};
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(mlp_tile_kernel<PREDICT>, dim3(tiles(B)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in,
-                       (const float*)nullptr, (const float*)nullptr, B, 0.f, m->w, P->d_p, P->d_v, P->d_z);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(P->h_p, P->d_p, sizeof(float) * B * A, hipMemcpyDeviceToHost, m->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(P->h_v, P->d_v, sizeof(float) * B, hipMemcpyDeviceToHost, m->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(P->h_z, P->d_z, sizeof(float) * B * 2 * A, hipMemcpyDeviceToHost, m->st);
-  if (e == hipSuccess) e = hipEventRecord(P->ev, m->st);
-  if (e != hipSuccess) {
-    P->busy = false;
-    lk.unlock();
-    m->lane_cv.notify_one();
-    (void)hipGetLastError();
-    return fail(GA3C_EHIP, "prediction enqueue failed: %s", hipGetErrorString(e));
-  }
-  P->B = B;
-  return GA3C_OK;
-}
-
-int predict_end(ga3c_mlp* m, int ticket, int B, float* p, float* v, float* z) {
-  if (ticket < 0 || ticket >= (int)m->lanes.size()) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
-  PLane* P = &m->lanes[ticket];
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!P->busy) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
-  }
-  const hipError_t e = hipEventSynchronize(P->ev);     // the lane's staging is free for the next begin only after this
-  if (e == hipSuccess && B != P->B) {
-    give_lane(m, P);
-    return fail(GA3C_EINVAL, "batch %d, begun with %d", B, P->B);
-  }
-  if (e == hipSuccess) {
-    const int A = m->L.A;
-    if (p) memcpy(p, P->h_p, sizeof(float) * B * A);
-    if (v) memcpy(v, P->h_v, sizeof(float) * B);
-    if (z) memcpy(z, P->h_z, sizeof(float) * B * 2 * A);
-  }
-  give_lane(m, P);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(GA3C_EHIP, "prediction failed: %s", hipGetErrorString(e));
-  }
-  return GA3C_OK;
-}
-
-int param_index(const char* name) {
-  if (!name) return -1;
-  std::string s(name);
-  if (s.size() > 2 && s.compare(s.size() - 2, 2, ":0") == 0) s.resize(s.size() - 2);
-  for (int i = 0; i < NVARS; ++i)
-    if (s == VAR_NAMES[i]) return i;
-  return -1;
-}
-
-void param_shape(const ga3c_mlp* m, int i, int32_t* ndim, int64_t shape[4]) {
-  const int l = i / 2;
-  if (i & 1) {
-    *ndim = 1;
-    shape[0] = m->L.out[l];
-  } else {
-    *ndim = 2;
-    shape[0] = m->L.in[l];
-    shape[1] = m->L.out[l];
-  }
-}
-
-int arena_copy(ga3c_mlp* m, int which, int64_t off, int64_t count, float* out, const float* in) {
-  if (which < 0 || which > 3 || (in && which > 2)) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, in ? 2 : 3);
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  if (out) HIPCHK(hipMemcpy(out, m->arena[which] + off, sizeof(float) * count, hipMemcpyDeviceToHost));
-  else HIPCHK(hipMemcpy(m->arena[which] + off, in, sizeof(float) * count, hipMemcpyHostToDevice));
-  return GA3C_OK;
-}
-
-void free_all(ga3c_mlp* m) {
-  if (m->st) (void)hipStreamSynchronize(m->st);
-  for (PLane& P : m->lanes) {
-    (void)hipHostFree(P.h_off); (void)hipHostFree(P.h_x); (void)hipHostFree(P.h_p); (void)hipHostFree(P.h_v);
-    (void)hipHostFree(P.h_z);
-    (void)hipFree(P.d_off); (void)hipFree(P.d_x); (void)hipFree(P.d_p); (void)hipFree(P.d_v); (void)hipFree(P.d_z);
-    if (P.ev) (void)hipEventDestroy(P.ev);
-  }
-  for (float*& a : m->arena) (void)hipFree(a);
-  (void)hipFree(m->work_base);
-  (void)hipHostFree(m->h_x); (void)hipHostFree(m->h_y); (void)hipHostFree(m->h_a); (void)hipHostFree(m->h_off);
-  (void)hipHostFree(m->h_loss);
-  (void)hipFree(m->d_x); (void)hipFree(m->d_y); (void)hipFree(m->d_a); (void)hipFree(m->d_off);
-  for (hipEvent_t e : {m->tev, m->t0, m->t1})
-    if (e) (void)hipEventDestroy(e);
-  if (m->reg_host) (void)hipHostUnregister((void*)m->reg_host);
-  if (m->st) (void)hipStreamDestroy(m->st);
-  (void)hipGetLastError();
-}
-
-template <class T>
-int dalloc(T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, n * sizeof(T) + 16));
-  return GA3C_OK;
-}
-template <class T>
-int halloc(T** p, size_t n) {
-  HIPCHK(hipHostMalloc((void**)p, n * sizeof(T) + 16, hipHostMallocDefault));
-  return GA3C_OK;
-}
-
-int create(ga3c_mlp* m) {
-  const ga3c_mlp_config& c = m->cfg;
-  const size_t B = (size_t)c.max_batch, S = c.state_dim, A = c.num_actions;
-  HIPCHK(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
-  for (int i = 0; i < 4; ++i) {
-    CHK(dalloc(&m->arena[i], (size_t)m->n));
-    HIPCHK(hipMemset(m->arena[i], 0, sizeof(float) * m->n));
-  }
-  std::vector<float> ones((size_t)m->n, 1.0f);     // the RMSProp ms slot starts at 1 (TF-1 RMSPropOptimizer)
-  HIPCHK(hipMemcpy(m->arena[1], ones.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
-  // per-row workspace, one block
-  const size_t widths[] = {S, 4, 256, 256, 100, 64, 4, 256, 256, 100, 64, 1, 2 * A, A, 1, 2 * A, 3};
-  size_t total = 0;
-  for (size_t wd : widths) total += (B * wd + 3) / 4 * 4;
-  CHK(dalloc(&m->work_base, total + 4));
-  HIPCHK(hipMemset(m->work_base, 0, sizeof(float) * (total + 4)));
-  float* q = m->work_base;
-  float** dst[] = {&m->w.x, &m->w.act[0], &m->w.act[1], &m->w.act[2], &m->w.act[3], &m->w.act[4], &m->w.del[0],
-                   &m->w.del[1], &m->w.del[2], &m->w.del[3], &m->w.del[4], &m->w.v, &m->w.z, &m->w.p, &m->w.dv, &m->w.dz,
-                   &m->w.lossrow};
-  for (size_t i = 0; i < sizeof(widths) / sizeof(widths[0]); ++i) {
-    *dst[i] = q;
-    q += (B * widths[i] + 3) / 4 * 4;
-  }
-  m->w.losses = q;
-  CHK(halloc(&m->h_x, B * S)); CHK(halloc(&m->h_y, B)); CHK(halloc(&m->h_a, B * A)); CHK(halloc(&m->h_off, B));
-  CHK(halloc(&m->h_loss, 4));
-  CHK(dalloc(&m->d_x, B * S)); CHK(dalloc(&m->d_y, B)); CHK(dalloc(&m->d_a, B * A)); CHK(dalloc(&m->d_off, B));
-  HIPCHK(hipEventCreateWithFlags(&m->tev, hipEventDisableTiming));
-  HIPCHK(hipEventCreate(&m->t0));
-  HIPCHK(hipEventCreate(&m->t1));
-  m->lanes.resize((size_t)(c.predict_lanes > 0 ? c.predict_lanes : 4));
-  for (PLane& P : m->lanes) {
-    CHK(halloc(&P.h_off, B)); CHK(halloc(&P.h_x, B * S)); CHK(halloc(&P.h_p, B * A)); CHK(halloc(&P.h_v, B));
-    CHK(halloc(&P.h_z, 2 * B * A));
-    CHK(dalloc(&P.d_off, B)); CHK(dalloc(&P.d_x, B * S)); CHK(dalloc(&P.d_p, B * A)); CHK(dalloc(&P.d_v, B));
-    CHK(dalloc(&P.d_z, 2 * B * A));
-    HIPCHK(hipEventCreateWithFlags(&P.ev, hipEventDisableTiming));
-  }
-  return GA3C_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -829,191 +491,58 @@ extern "C" {
 int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out) {
   if (!cfg || !out) return fail(GA3C_EINVAL, "null argument");
   *out = nullptr;
-  if (cfg->state_dim < 1 || cfg->state_dim > MAX_S) return fail(GA3C_EINVAL, "state_dim %d outside [1,%d]", cfg->state_dim, MAX_S);
-  if (cfg->num_actions < 1 || cfg->num_actions > MAX_A)
-    return fail(GA3C_EINVAL, "num_actions %d outside [1,%d]", cfg->num_actions, MAX_A);
-  if (cfg->max_batch < 1 || cfg->max_batch > 65536) return fail(GA3C_EINVAL, "max_batch %d outside [1,65536]", cfg->max_batch);
+  CHK(check_dims(*cfg, MAX_S, MAX_A));
   if (!(cfg->flags & GA3C_FLAG_CONTINUOUS))
     return fail(GA3C_EINVAL, "the vector-state network has the angle-output head only: GA3C_FLAG_CONTINUOUS is required");
   if (cfg->flags & ~(uint32_t)(GA3C_FLAG_CONTINUOUS | GA3C_FLAG_GRAD_CLIP))
     return fail(GA3C_EINVAL, "flags 0x%x: only GA3C_FLAG_CONTINUOUS and GA3C_FLAG_GRAD_CLIP apply to the vector-state network",
                 cfg->flags);
-  if (cfg->predict_lanes < 0 || cfg->predict_lanes > 64) return fail(GA3C_EINVAL, "predict_lanes %d outside [0,64]", cfg->predict_lanes);
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(GA3C_EINVAL, "device %d not in [0,%d)", cfg->device, ndev);
-  HIPCHK(hipSetDevice(cfg->device));
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(GA3C_ESTATE, "device %d is %s; this library is built for gfx950 only", cfg->device, prop.gcnArchName);
+  CHK(check_device(*cfg));
   ga3c_mlp* m = new (std::nothrow) ga3c_mlp();
   if (!m) return fail(GA3C_EINVAL, "out of host memory");
   m->cfg = *cfg;
+  m->kind = "vector-state network";
+  m->ZW = 2 * cfg->num_actions;
   m->L = make_layout(cfg->state_dim, cfg->num_actions);
-  m->n = m->L.off[NVARS];
-  m->clip = (cfg->flags & GA3C_FLAG_GRAD_CLIP) != 0;
-  const int rc = create(m);
-  if (rc != GA3C_OK) {
-    free_all(m);
-    delete m;
-    return rc;
-  }
-  *out = m;
-  return GA3C_OK;
+  for (int l = 0; l < NLAYERS; ++l) m->add_dense(VAR_NAMES[2 * l], VAR_NAMES[2 * l + 1], m->L.off[2 * l], m->L.in[l], m->L.out[l]);
+  return create(m, out);
 }
 
-int ga3c_mlp_destroy(ga3c_mlp* m) {
-  if (!m) return fail(GA3C_EINVAL, "null argument");
-  (void)hipSetDevice(m->cfg.device);
-  free_all(m);
-  delete m;
-  return GA3C_OK;
-}
+int ga3c_mlp_destroy(ga3c_mlp* m) { return destroy(m); }
 
-int ga3c_mlp_param_count(ga3c_mlp* m, int64_t* count) {
-  if (!m || !count) return fail(GA3C_EINVAL, "null argument");
-  *count = m->n;
-  return GA3C_OK;
-}
+int ga3c_mlp_param_count(ga3c_mlp* m, int64_t* count) { return param_count(m, count); }
 
-int ga3c_mlp_get_arena(ga3c_mlp* m, int32_t which, float* out, int64_t count) {
-  if (!m || !out) return fail(GA3C_EINVAL, "null argument");
-  if (count != m->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)m->n);
-  return arena_copy(m, which, 0, count, out, nullptr);
-}
+int ga3c_mlp_get_arena(ga3c_mlp* m, int32_t which, float* out, int64_t count) { return get_arena(m, which, out, count); }
 
-int ga3c_mlp_set_arena(ga3c_mlp* m, int32_t which, const float* in, int64_t count) {
-  if (!m || !in) return fail(GA3C_EINVAL, "null argument");
-  if (count != m->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)m->n);
-  return arena_copy(m, which, 0, count, nullptr, in);
-}
+int ga3c_mlp_set_arena(ga3c_mlp* m, int32_t which, const float* in, int64_t count) { return set_arena(m, which, in, count); }
 
-int ga3c_mlp_get_step(ga3c_mlp* m, int64_t* step) {
-  if (!m || !step) return fail(GA3C_EINVAL, "null argument");
-  *step = m->step.load();
-  return GA3C_OK;
-}
+int ga3c_mlp_get_step(ga3c_mlp* m, int64_t* step) { return get_step(m, step); }
 
-int ga3c_mlp_set_step(ga3c_mlp* m, int64_t step) {
-  if (!m) return fail(GA3C_EINVAL, "null argument");
-  m->step.store(step);
-  return GA3C_OK;
-}
+int ga3c_mlp_set_step(ga3c_mlp* m, int64_t step) { return set_step(m, step); }
 
-int32_t ga3c_mlp_num_params(ga3c_mlp* m) { return m ? NVARS : 0; }
+int32_t ga3c_mlp_num_params(ga3c_mlp* m) { return num_params(m); }
 
-const char* ga3c_mlp_param_name(ga3c_mlp* m, int32_t index) {
-  return (m && index >= 0 && index < NVARS) ? VAR_NAMES[index] : nullptr;
-}
+const char* ga3c_mlp_param_name(ga3c_mlp* m, int32_t index) { return param_name(m, index); }
 
 int ga3c_mlp_param_info(ga3c_mlp* m, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]) {
-  if (!m || !name) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  if (offset) *offset = m->L.off[i];
-  if (count) *count = m->L.off[i + 1] - m->L.off[i];
-  int32_t nd;
-  int64_t sh[4] = {0, 0, 0, 0};
-  param_shape(m, i, &nd, sh);
-  if (ndim) *ndim = nd;
-  if (shape) memcpy(shape, sh, sizeof sh);
-  return GA3C_OK;
+  return param_info(m, name, offset, count, ndim, shape);
 }
 
 int ga3c_mlp_get_param(ga3c_mlp* m, const char* name, int32_t which, float* out, int64_t count) {
-  if (!m || !name || !out) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  if (count != m->L.off[i + 1] - m->L.off[i]) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name,
-                                                          (long long)(m->L.off[i + 1] - m->L.off[i]), (long long)count);
-  return arena_copy(m, which, m->L.off[i], count, out, nullptr);
+  return param_copy(m, name, which, out, nullptr, count);
 }
 
 int ga3c_mlp_set_param(ga3c_mlp* m, const char* name, int32_t which, const float* in, int64_t count) {
-  if (!m || !name || !in) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  if (count != m->L.off[i + 1] - m->L.off[i]) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name,
-                                                          (long long)(m->L.off[i + 1] - m->L.off[i]), (long long)count);
-  return arena_copy(m, which, m->L.off[i], count, nullptr, in);
+  return param_copy(m, name, which, nullptr, in, count);
 }
 
-int ga3c_mlp_save(ga3c_mlp* m, const char* path) {
-  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
-  std::vector<float> arena[3];
-  for (int w = 0; w < 3; ++w) {
-    arena[w].resize((size_t)m->n);
-    CHK(ga3c_mlp_get_arena(m, w, arena[w].data(), m->n));
-  }
-  const char* suffix[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};
-  std::vector<ga3c_ckpt::Member> members;
-  ga3c_ckpt::Member st;
-  st.name = "step";
-  st.descr = "<i8";
-  const int64_t step = m->step.load();
-  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
-  members.push_back(st);
-  for (int i = 0; i < NVARS; ++i) {
-    int32_t nd;
-    int64_t sh[4];
-    param_shape(m, i, &nd, sh);
-    for (int w = 0; w < 3; ++w) {
-      ga3c_ckpt::Member mb;
-      mb.name = std::string(VAR_NAMES[i]) + suffix[w];
-      mb.descr = "<f4";
-      mb.shape.assign(sh, sh + nd);
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[w].data() + m->L.off[i]);
-      mb.bytes.assign(src, src + (size_t)(m->L.off[i + 1] - m->L.off[i]) * sizeof(float));
-      members.push_back(std::move(mb));
-    }
-  }
-  std::string err;
-  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  return GA3C_OK;
-}
+int ga3c_mlp_save(ga3c_mlp* m, const char* path) { return save(m, path); }
 
-int ga3c_mlp_load(ga3c_mlp* m, const char* path) {
-  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
-  std::map<std::string, ga3c_ckpt::Member> members;
-  std::string err;
-  if (!ga3c_ckpt::read_npz(path, &members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  // an image-network file holds no dense11_p/w: refused below before anything is written
-  const char* suffix[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};
-  std::vector<float> arena[3];
-  for (int w = 0; w < 3; ++w) arena[w].resize((size_t)m->n);
-  for (int i = 0; i < NVARS; ++i) {
-    const int64_t cnt = m->L.off[i + 1] - m->L.off[i];
-    int32_t nd;
-    int64_t sh[4];
-    param_shape(m, i, &nd, sh);
-    for (int w = 0; w < 3; ++w) {
-      const std::string key = std::string(VAR_NAMES[i]) + suffix[w];
-      auto it = members.find(key);
-      if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s: not a checkpoint of this vector-state network", path,
-                                           key.c_str());
-      const ga3c_ckpt::Member& mb = it->second;
-      const bool shape_ok = mb.shape.size() == (size_t)nd && std::equal(mb.shape.begin(), mb.shape.end(), sh);
-      if (mb.descr != "<f4" || !shape_ok || mb.bytes.size() != (size_t)cnt * sizeof(float))
-        return fail(GA3C_ESTATE, "%s: %s is not <f4 of this network's shape (%lld elements)", path, key.c_str(), (long long)cnt);
-      memcpy(arena[w].data() + m->L.off[i], mb.bytes.data(), mb.bytes.size());
-    }
-  }
-  auto st = members.find("step");
-  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
-    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
-  int64_t step = 0;
-  memcpy(&step, st->second.bytes.data(), 8);
-  for (int w = 0; w < 3; ++w) CHK(ga3c_mlp_set_arena(m, w, arena[w].data(), m->n));
-  m->step.store(step);
-  return GA3C_OK;
-}
+// an image-network file holds no dense11_p/w: refused before anything is written
+int ga3c_mlp_load(ga3c_mlp* m, const char* path) { return load(m, path); }
 
 int ga3c_mlp_predict(ga3c_mlp* m, const float* x, int32_t batch, float* p, float* v, float* z) {
-  if (!m || !x || !p || !v) return fail(GA3C_EINVAL, "null argument");
-  int ticket;
-  CHK(predict_begin(m, x, nullptr, batch, &ticket));
-  return predict_end(m, ticket, batch, p, v, z);
+  return predict(m, x, batch, p, v, z);
 }
 
 int ga3c_mlp_train(ga3c_mlp* m, const float* x, const float* y_r, const float* a, int32_t batch, float learning_rate,
@@ -1026,160 +555,51 @@ int ga3c_mlp_compute_grads(ga3c_mlp* m, const float* x, const float* y_r, const 
   return train_common(m, x, nullptr, y_r, a, batch, false, 0.f, beta, losses);
 }
 
-int ga3c_mlp_apply_grads(ga3c_mlp* m, float learning_rate) {
-  if (!m) return fail(GA3C_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    CHK(enqueue_apply(m, learning_rate));
-    HIPCHK(hipEventRecord(m->tev, m->st));
-  }
-  HIPCHK(hipEventSynchronize(m->tev));
-  m->step.fetch_add(1);
-  return GA3C_OK;
-}
+int ga3c_mlp_apply_grads(ga3c_mlp* m, float learning_rate) { return apply_grads(m, learning_rate); }
 
 int ga3c_mlp_evaluate(ga3c_mlp* m, const float* x, const int64_t* offsets, const float* y_r, const float* a, int32_t batch,
                       float beta, float* losses, float* pd1, float* pd2, float* d1, float* v, float* p) {
-  if (!m || (!x && !offsets) || (x && offsets) || !y_r || !a) return fail(GA3C_EINVAL, "bad argument");
-  CHK(check_batch(m, batch));
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    Input in;
-    CHK(stage_train(m, x, offsets, y_r, a, batch, &in));
-    hipLaunchKernelGGL(mlp_tile_kernel<EVAL>, dim3(tiles(batch)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in,
-                       (const float*)m->d_y, (const float*)m->d_a, batch, beta, m->w, m->w.p, m->w.v, m->w.z);
-    hipLaunchKernelGGL(mlp_loss_kernel, dim3(1), dim3(64), 0, m->st, m->w, batch);
-    HIPCHK(hipGetLastError());
-    CHK(finish_train(m, losses));
-    m->last_B = batch;
-  }
-  CHK(wait_train(m, losses));
-  const size_t B = (size_t)batch;
-  if (pd1) HIPCHK(hipMemcpy(pd1, m->w.act[0], B * 4 * sizeof(float), hipMemcpyDeviceToHost));
-  if (pd2) HIPCHK(hipMemcpy(pd2, m->w.act[1], B * 256 * sizeof(float), hipMemcpyDeviceToHost));
-  if (d1) HIPCHK(hipMemcpy(d1, m->w.act[4], B * HID * sizeof(float), hipMemcpyDeviceToHost));
-  if (v) HIPCHK(hipMemcpy(v, m->w.v, B * sizeof(float), hipMemcpyDeviceToHost));
-  if (p) HIPCHK(hipMemcpy(p, m->w.p, B * m->L.A * sizeof(float), hipMemcpyDeviceToHost));
-  return GA3C_OK;
+  if (!m) return fail(GA3C_EINVAL, "bad argument");
+  return evaluate(m, x, offsets, y_r, a, batch, beta, losses, {{pd1, m->w.act[0], 4}, {pd2, m->w.act[1], 256}, {d1, m->w.act[4], HID}},
+                  v, p);
 }
 
-int ga3c_mlp_register_host(ga3c_mlp* m, void* base, int64_t bytes) {
-  if (!m || !base || bytes < 16) return fail(GA3C_EINVAL, "bad argument");
-  if (m->reg_host) return fail(GA3C_ESTATE, "a host segment is already registered");
-  HIPCHK(hipSetDevice(m->cfg.device));
-  HIPCHK(hipHostRegister(base, (size_t)bytes, hipHostRegisterMapped));
-  void* dev = nullptr;
-  hipError_t e = hipHostGetDevicePointer(&dev, base, 0);
-  if (e != hipSuccess) {
-    (void)hipHostUnregister(base);
-    return fail(GA3C_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
-  }
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  m->reg_host = static_cast<const char*>(base);
-  m->reg_dev = static_cast<const char*>(dev);
-  m->reg_bytes = bytes;
-  return GA3C_OK;
-}
+int ga3c_mlp_register_host(ga3c_mlp* m, void* base, int64_t bytes) { return register_host(m, base, bytes); }
 
-int ga3c_mlp_unregister_host(ga3c_mlp* m) {
-  if (!m) return fail(GA3C_EINVAL, "null argument");
-  if (!m->reg_host) return GA3C_OK;
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  HIPCHK(hipHostUnregister((void*)m->reg_host));
-  m->reg_host = m->reg_dev = nullptr;
-  m->reg_bytes = 0;
-  return GA3C_OK;
-}
+int ga3c_mlp_unregister_host(ga3c_mlp* m) { return unregister_host(m); }
 
 int ga3c_mlp_predict_gather(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v, float* z) {
-  ga3c_mlp* m = static_cast<ga3c_mlp*>(net);
-  int ticket;
-  CHK(ga3c_mlp_predict_gather_begin(net, offsets, batch, u8, &ticket));
-  return predict_end(m, ticket, batch, p, v, z);
+  return predict_gather(static_cast<ga3c_mlp*>(net), offsets, batch, u8, p, v, z);
 }
 
 int ga3c_mlp_predict_gather_begin(void* net, const int64_t* offsets, int32_t batch, int32_t u8, int32_t* ticket) {
-  ga3c_mlp* m = static_cast<ga3c_mlp*>(net);
-  if (!m || !offsets || !ticket) return fail(GA3C_EINVAL, "null argument");
-  if (u8) return fail(GA3C_EINVAL, "the vector-state network reads f32 rows (u8 = 0)");
-  return predict_begin(m, nullptr, offsets, batch, ticket);
+  return predict_gather_begin(static_cast<ga3c_mlp*>(net), offsets, batch, u8, ticket);
 }
 
 int ga3c_mlp_predict_gather_end(void* net, int32_t ticket, int32_t batch, float* p, float* v) {
-  ga3c_mlp* m = static_cast<ga3c_mlp*>(net);
-  if (!m || !p || !v) return fail(GA3C_EINVAL, "null argument");
-  return predict_end(m, ticket, batch, p, v, nullptr);
+  return predict_gather_end(static_cast<ga3c_mlp*>(net), ticket, batch, p, v);
 }
 
 int ga3c_mlp_train_gather(ga3c_mlp* m, const int64_t* offsets, int32_t u8, const float* y_r, const float* a, int32_t batch,
                           float learning_rate, float beta, float* losses) {
-  if (u8) return fail(GA3C_EINVAL, "the vector-state network reads f32 rows (u8 = 0)");
-  if (!offsets) return fail(GA3C_EINVAL, "null argument");
-  return train_common(m, nullptr, offsets, y_r, a, batch, true, learning_rate, beta, losses);
+  return train_gather(m, offsets, u8, y_r, a, batch, learning_rate, beta, losses);
 }
 
 int ga3c_mlp_upload(ga3c_mlp* m, const float* x, const float* y_r, const float* a, int32_t batch) {
-  if (!m || !x || !y_r || !a) return fail(GA3C_EINVAL, "null argument");
-  CHK(check_batch(m, batch));
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  Input in;
-  CHK(stage_train(m, x, nullptr, y_r, a, batch, &in));
-  HIPCHK(hipStreamSynchronize(m->st));
-  m->res_B = batch;
-  return GA3C_OK;
+  return upload(m, x, y_r, a, batch);
 }
 
 int ga3c_mlp_time_resident(ga3c_mlp* m, int32_t mode, int32_t batch, int32_t iters, float learning_rate, float beta,
                            float* elapsed_ms) {
-  if (!m || !elapsed_ms || iters < 1 || (mode != 0 && mode != 1)) return fail(GA3C_EINVAL, "bad argument");
-  if (batch < 1 || batch > m->res_B) return fail(GA3C_ESTATE, "batch %d: %d rows uploaded", batch, m->res_B);
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    const Input in{reinterpret_cast<const char*>(m->d_x), nullptr, 4 * (int64_t)m->L.S};
-    HIPCHK(hipEventRecord(m->t0, m->st));
-    for (int i = 0; i < iters; ++i) {
-      if (mode == 0)
-        hipLaunchKernelGGL(mlp_tile_kernel<PREDICT>, dim3(tiles(batch)), dim3(THREADS), 0, m->st, m->L,
-                           (const float*)m->arena[0], in, (const float*)nullptr, (const float*)nullptr, batch, 0.f, m->w,
-                           m->w.p, m->w.v, m->w.z);
-      else
-        CHK(enqueue_train(m, in, batch, beta, true, learning_rate));
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->t1, m->st));
-    m->last_B = batch;
-  }
-  HIPCHK(hipEventSynchronize(m->t1));
-  HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
-  if (mode == 1) m->step.fetch_add(iters);
-  return GA3C_OK;
+  return time_resident(m, mode, batch, iters, learning_rate, beta, elapsed_ms);
 }
 
 int ga3c_mlp_fetch(ga3c_mlp* m, const char* name, float* out, int64_t count) {
   if (!m || !name || !out) return fail(GA3C_EINVAL, "null argument");
   const int64_t wd = width_of(m, name);
-  float* src = work_ptr(m, name);
+  const float* src = work_ptr(m, name);
   if (wd < 0 || !src) return fail(GA3C_EINVAL, "no activation named %s", name);
-  if (count != wd * m->last_B)
-    return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)(wd * m->last_B), (long long)count);
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  HIPCHK(hipMemcpy(out, src, sizeof(float) * count, hipMemcpyDeviceToHost));
-  return GA3C_OK;
+  return fetch(m, name, src, wd, out, count);
 }
 
 }  // extern "C"
