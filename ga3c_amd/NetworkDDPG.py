@@ -9,15 +9,14 @@ the handle (replay_add*, train_replay); the Ornstein-Uhlenbeck process too, beca
 handle without the interpreter.
 """
 import ctypes as C
-import glob
 import os
-import re
 import threading
 
 import numpy as np
 
 from Config import Config
 from NetworkVP import _device_ordinal
+from NetworkVP_vecnet import NativeHandle
 import _native as nat
 
 H1, H2 = 400, 300
@@ -73,7 +72,9 @@ def initial_arena(state_dim, num_actions, seed, tau=None):
     return online, target
 
 
-class Network:
+class Network(NativeHandle):
+    PREFIX = "ga3c_ddpg"
+
     def __init__(self, device, model_name, num_actions, state_dim, max_batch=None, predict_lanes=None, replay_capacity=None):
         self.device = device
         self.model_name = model_name
@@ -113,7 +114,7 @@ class Network:
         cfg.ou_sigma, cfg.ou_theta, cfg.ou_dt = Config.OU_SIGMA, Config.OU_THETA, Config.OU_DT
         cfg.seed = Config.RANDOM_SEED
         handle = C.c_void_p()
-        nat.check(self._lib.ga3c_ddpg_create(C.byref(cfg), C.byref(handle)), "ga3c_ddpg_create")
+        nat.check(self._fn("create")(C.byref(cfg), C.byref(handle)), "ga3c_ddpg_create")
         self._h = handle
         self.replay_capacity = cfg.replay_capacity
         online, target = initial_arena(self.S, self.num_actions, Config.RANDOM_SEED)
@@ -123,50 +124,29 @@ class Network:
         self._log_lock = threading.Lock()
         self.logging = (0.0, 0.0)               # Q_max, Q_avg of the last step (NetworkDDPG.py:98)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ga3c_ddpg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # ---- variables: which = VALUE, TARGET, SLOT_A, SLOT_B (RMSProp ms / mom or Adam m / v), GRAD -----------------------
-    def get_global_step(self):
-        s = C.c_int64()
-        nat.check(self._lib.ga3c_ddpg_get_step(self._h, C.byref(s)))
-        return s.value
-
     def set_global_step(self, step):
-        nat.check(self._lib.ga3c_ddpg_set_step(self._h, int(step)), "ga3c_ddpg_set_step")
-
-    def get_variables_names(self):
-        n = self._lib.ga3c_ddpg_num_params(self._h)
-        return [self._lib.ga3c_ddpg_param_name(self._h, i).decode() + ":0" for i in range(n)]
+        self._call("set_step", int(step))
 
     def get_target_names(self):
-        n = self._lib.ga3c_ddpg_num_params(self._h)
-        return [self._lib.ga3c_ddpg_target_name(self._h, i).decode() + ":0" for i in range(n)]
+        n = self._fn("num_params")(self._h)
+        return [self._fn("target_name")(self._h, i).decode() + ":0" for i in range(n)]
 
     def _param_info(self, name):
         count, ndim, trainable = C.c_int64(), C.c_int32(), C.c_int32()
         shape = (C.c_int64 * 4)()
-        nat.check(self._lib.ga3c_ddpg_param_info(self._h, name.encode(), C.byref(count), C.byref(ndim), shape, C.byref(trainable)),
-                  "ga3c_ddpg_param_info")
+        self._call("param_info", name.encode(), C.byref(count), C.byref(ndim), shape, C.byref(trainable))
         return count.value, tuple(shape[d] for d in range(ndim.value)), bool(trainable.value)
 
     def get_variable_value(self, name, which=VALUE):
         count, shape, _ = self._param_info(name)
         out = np.empty(count, dtype=np.float32)
-        nat.check(self._lib.ga3c_ddpg_get_param(self._h, name.encode(), which, nat.ptr(out), count), "ga3c_ddpg_get_param")
+        self._call("get_param", name.encode(), which, nat.ptr(out), count)
         return out.reshape(shape)
 
     def set_variable_value(self, name, value, which=VALUE):
         flat = nat.as_f32(value).ravel()
-        nat.check(self._lib.ga3c_ddpg_set_param(self._h, name.encode(), which, nat.ptr(flat), flat.size), "ga3c_ddpg_set_param")
+        self._call("set_param", name.encode(), which, nat.ptr(flat), flat.size)
 
     # ---- noise -----------------------------------------------------------------------------------
     def _noise_args(self, noise):
@@ -183,19 +163,15 @@ class Network:
     def noise_step(self):
         """One step of the handle's OU process -> (x[A], n[A]): the new state and the normal draws it used."""
         x, n = np.empty(self.num_actions, np.float32), np.empty(self.num_actions, np.float32)
-        nat.check(self._lib.ga3c_ddpg_noise_step(self._h, nat.ptr(x), nat.ptr(n)), "ga3c_ddpg_noise_step")
+        self._call("noise_step", nat.ptr(x), nat.ptr(n))
         return x, n
 
     # ---- inference ---------------------------------------------------------------------------
-    def _rows(self, x):
-        x = nat.as_f32(x).reshape(-1, self.S)
-        return x, int(x.shape[0])
-
     def predict(self, x, noise=None):
         x, b = self._rows(x)
         mode, nptr, _keep = self._noise_args(noise)
         a = np.empty((b, self.num_actions), np.float32)
-        nat.check(self._lib.ga3c_ddpg_predict(self._h, nat.ptr(x), b, mode, nptr, nat.ptr(a)), "ga3c_ddpg_predict")
+        self._call("predict", nat.ptr(x), b, mode, nptr, nat.ptr(a))
         return a
 
     def predict_p_and_v(self, x):
@@ -207,27 +183,12 @@ class Network:
         return self.predict(x[None, :])[0]
 
     # ---- zero-copy intake from the shared-memory transport -------------------------------------------
-    def register_transport(self, transport):
-        nat.check(self._lib.ga3c_ddpg_register_host(self._h, C.c_void_p(transport.base), transport.nbytes),
-                  "ga3c_ddpg_register_host")
-
-    def unregister_transport(self):
-        nat.check(self._lib.ga3c_ddpg_unregister_host(self._h), "ga3c_ddpg_unregister_host")
-
-    def gather_entry(self):
-        return C.cast(self._lib.ga3c_ddpg_predict_gather, C.c_void_p).value, self._h, 0
-
-    def gather_entries_pipelined(self):
-        return (C.cast(self._lib.ga3c_ddpg_predict_gather_begin, C.c_void_p).value,
-                C.cast(self._lib.ga3c_ddpg_predict_gather_end, C.c_void_p).value, self._h, 0)
-
     def predict_offsets(self, offsets):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         b = offsets.size
         p = np.empty((b, self.num_actions), np.float32)
         v = np.empty(b, np.float32)
-        nat.check(self._lib.ga3c_ddpg_predict_gather(self._h, nat.ptr(offsets, nat.i64p), b, 0, nat.ptr(p), nat.ptr(v), None),
-                  "ga3c_ddpg_predict_gather")
+        self._call("predict_gather", nat.ptr(offsets, nat.i64p), b, 0, nat.ptr(p), nat.ptr(v), None)
         return [p, p]
 
     # ---- replay memory (replay_buffer.py:16-55, a ring in HBM) ------------------------------------------
@@ -238,8 +199,8 @@ class Network:
         a = nat.as_f32(a).reshape(n, self.num_actions)
         r, done = nat.as_f32(r).ravel(), nat.as_f32(done).ravel()
         size, total = C.c_int64(), C.c_int64()
-        nat.check(self._lib.ga3c_ddpg_replay_add(self._h, nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(done), nat.ptr(s2), n,
-                                                 C.byref(size), C.byref(total)), "ga3c_ddpg_replay_add")
+        self._call("replay_add", nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(done), nat.ptr(s2), n,
+                   C.byref(size), C.byref(total))
         return size.value, total.value
 
     def replay_add_offsets(self, offsets, r, a):
@@ -248,21 +209,19 @@ class Network:
         n = offsets.size
         r, a = nat.as_f32(r).ravel(), nat.as_f32(a).reshape(n, self.num_actions)
         size, total = C.c_int64(), C.c_int64()
-        nat.check(self._lib.ga3c_ddpg_replay_add_gather(self._h, nat.ptr(offsets, nat.i64p), nat.ptr(r), nat.ptr(a), n,
-                                                        C.byref(size), C.byref(total)), "ga3c_ddpg_replay_add_gather")
+        self._call("replay_add_gather", nat.ptr(offsets, nat.i64p), nat.ptr(r), nat.ptr(a), n, C.byref(size), C.byref(total))
         return size.value, total.value
 
     def replay_get(self, slot):
         s, s2 = np.empty(self.S, np.float32), np.empty(self.S, np.float32)
         a = np.empty(self.num_actions, np.float32)
         r, done = C.c_float(), C.c_float()
-        nat.check(self._lib.ga3c_ddpg_replay_get(self._h, int(slot), nat.ptr(s), nat.ptr(a), C.byref(r), C.byref(done), nat.ptr(s2)),
-                  "ga3c_ddpg_replay_get")
+        self._call("replay_get", int(slot), nat.ptr(s), nat.ptr(a), C.byref(r), C.byref(done), nat.ptr(s2))
         return s, a, np.float32(r.value), np.float32(done.value), s2
 
     def replay_size(self):
         size, total = C.c_int64(), C.c_int64()
-        nat.check(self._lib.ga3c_ddpg_replay_size(self._h, C.byref(size), C.byref(total)), "ga3c_ddpg_replay_size")
+        self._call("replay_size", C.byref(size), C.byref(total))
         return size.value, total.value
 
     # ---- training ----------------------------------------------------------------------------
@@ -276,8 +235,8 @@ class Network:
         s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)
         mode, nptr, _keep = self._noise_args(noise)
         q = np.empty(2, np.float32)
-        nat.check(self._lib.ga3c_ddpg_train(self._h, nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(d), nat.ptr(s2), b,
-                                            float(self.learning_rate), mode, nptr, nat.ptr(q)), "ga3c_ddpg_train")
+        self._call("train", nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(d), nat.ptr(s2), b,
+                   float(self.learning_rate), mode, nptr, nat.ptr(q))
         self.logging = (float(q[0]), float(q[1]))
         return self.logging
 
@@ -286,8 +245,8 @@ class Network:
         slots = np.ascontiguousarray(slots, dtype=np.int32)
         mode, nptr, _keep = self._noise_args(noise)
         q = np.empty(2, np.float32)
-        nat.check(self._lib.ga3c_ddpg_train_replay(self._h, nat.ptr(slots, nat.i32p), slots.size, int(stamp),
-                                                   float(self.learning_rate), mode, nptr, nat.ptr(q)), "ga3c_ddpg_train_replay")
+        self._call("train_replay", nat.ptr(slots, nat.i32p), slots.size, int(stamp),
+                   float(self.learning_rate), mode, nptr, nat.ptr(q))
         self.logging = (float(q[0]), float(q[1]))
         return self.logging
 
@@ -295,21 +254,14 @@ class Network:
         s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)
         mode, nptr, _keep = self._noise_args(noise)
         q = np.empty(2, np.float32)
-        nat.check(self._lib.ga3c_ddpg_compute(self._h, nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(d), nat.ptr(s2), b,
-                                              float(self.learning_rate), mode, nptr, int(stop_after), nat.ptr(q)),
-                  "ga3c_ddpg_compute")
+        self._call("compute", nat.ptr(s), nat.ptr(a), nat.ptr(r), nat.ptr(d), nat.ptr(s2), b,
+                   float(self.learning_rate), mode, nptr, int(stop_after), nat.ptr(q))
         return float(q[0]), float(q[1])
-
-    def fetch(self, name, count):
-        out = np.empty(int(count), np.float32)
-        nat.check(self._lib.ga3c_ddpg_fetch(self._h, name.encode(), nat.ptr(out), out.size), "ga3c_ddpg_fetch")
-        return out
 
     def time_resident(self, mode, batch, iters):
         """Milliseconds of `iters` resident calls (mode 0 predict, 1 train_replay) on ring slots 0 .. batch-1."""
         ms = C.c_float()
-        nat.check(self._lib.ga3c_ddpg_time_resident(self._h, int(mode), int(batch), int(iters), float(self.learning_rate),
-                                                    C.byref(ms)), "ga3c_ddpg_time_resident")
+        self._call("time_resident", int(mode), int(batch), int(iters), float(self.learning_rate), C.byref(ms))
         return ms.value
 
     # ---- logging / checkpoints -----------------------------------------------------------------
@@ -320,24 +272,3 @@ class Network:
         with self._log_lock:
             with open("logs/%s/scalars.csv" % self.model_name, "a") as f:
                 f.write("%d,%.8g,%.8g,%.8g\n" % (training_step, self.learning_rate, q_max, q_avg))
-
-    def _checkpoint_filename(self, episode):
-        return 'checkpoints/%s_%08d' % (self.model_name, episode)
-
-    def save(self, episode):
-        os.makedirs("checkpoints", exist_ok=True)
-        nat.check(self._lib.ga3c_ddpg_save(self._h, (self._checkpoint_filename(episode) + ".npz").encode()), "ga3c_ddpg_save")
-
-    def load_file(self, filename):
-        nat.check(self._lib.ga3c_ddpg_load(self._h, filename.encode()), "ga3c_ddpg_load")
-
-    def load(self):
-        if Config.LOAD_EPISODE > 0:
-            filename = self._checkpoint_filename(Config.LOAD_EPISODE) + ".npz"
-        else:
-            found = sorted(glob.glob('checkpoints/%s_????????.npz' % self.model_name))
-            if not found:
-                raise FileNotFoundError("no checkpoint for %s" % self.model_name)
-            filename = found[-1]
-        self.load_file(filename)
-        return int(re.split(r'/|_|\.', filename[:-4])[2])

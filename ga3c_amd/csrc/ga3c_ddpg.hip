@@ -16,27 +16,14 @@
 //   ddpg_predict_kernel  the online actor alone
 //   ddpg_ring_gather_kernel  rows of the registered transport into ring slots
 // A train step is 5 launches (6 with clipping); its rows are named by ring slot and read where they lie.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <new>
-#include <string>
-#include <vector>
 
-#include "../../include/ga3c_abi.h"
-#include "ga3c_checkpoint.hpp"
-
-void ga3c_set_last_error(const char* msg);   // ga3c_engine.hip: the thread's ga3c_last_error() message
+#include "ga3c_vecnet.hpp"
 
 namespace ga3c_dd {
+
+using ga3c_vecnet::Input;      // a prediction's row r: S floats at base + (off ? off[r] : r * stride) bytes
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -97,12 +84,6 @@ struct Rows {
   const float* base;
   const int32_t* idx;
   int rowf;
-};
-
-struct Input {         // a prediction's row r: S floats at base + (off ? off[r] : r * stride) bytes
-  const char* base;
-  const int64_t* off;
-  int64_t stride;
 };
 
 struct Noise {         // by value in the kernel arguments: nothing to copy
@@ -572,38 +553,8 @@ __global__ void ddpg_ring_gather_kernel(const char* __restrict__ seg, const int6
 }
 
 // ------------------------------------------------------------------ host side
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  ga3c_set_last_error(buf);
-  return code;
-}
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) {                                                                           \
-      (void)hipGetLastError();                                                                        \
-      return fail(GA3C_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    }                                                                                                 \
-  } while (0)
-#define CHK(expr)                 \
-  do {                            \
-    int _r = (expr);              \
-    if (_r != GA3C_OK) return _r; \
-  } while (0)
-
-struct PLane {
-  int64_t* h_off = nullptr; float* h_x = nullptr; float* h_a = nullptr;
-  int64_t* d_off = nullptr; float* d_x = nullptr; float* d_a = nullptr;
-  hipEvent_t ev = nullptr;
-  bool busy = false;
-  int B = 0;
-};
+// The handle is a ga3c_vecnet::Core (ga3c_vecnet.hpp): stream, lanes, arenas, variables by name, checkpoint and registered
+// segment are the shared ones.  Its own: the train step, the replay ring, the noise.
 
 // The handle's normal generator: xoshiro256** seeded through splitmix64, Box-Muller on two uniforms per draw.
 struct NormalGen {
@@ -633,20 +584,15 @@ struct NormalGen {
 }  // namespace ga3c_dd
 
 using namespace ga3c_dd;
+namespace vn = ga3c_vecnet;
+using vn::fail;                   // HIPCHK's
 
-struct ga3c_ddpg {
+struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
   ga3c_ddpg_config cfg;
   Layout L;
-  int64_t n = 0;
   int rowf = 0;
-  hipStream_t st = nullptr;       // every kernel and copy of the handle
-  std::mutex mu;                  // enqueue order on `st`, the lanes' and the ring's bookkeeping
-  std::condition_variable lane_cv;
-  std::mutex train_mu;            // one train-type / variable call at a time (they share the staging below)
-  std::mutex add_mu;              // one replay_add at a time (its own staging)
+  std::mutex add_mu;              // one replay_add at a time (its own staging); mu also orders the ring's bookkeeping
   std::mutex noise_mu;
-  std::vector<PLane> lanes;
-  float* arena[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // value, target, slot a, slot b, gradient
   Work w{};
   float* work_base = nullptr;
   float* ring = nullptr;
@@ -657,14 +603,9 @@ struct ga3c_ddpg {
   float* h_add = nullptr;                                  // replay_add: rows in ring layout
   int64_t* h_aoff = nullptr; int64_t* d_aoff = nullptr; float* h_ar = nullptr; float* d_ar = nullptr;
   float* h_aa = nullptr; float* d_aa = nullptr;
-  hipEvent_t tev = nullptr, aev = nullptr, t0 = nullptr, t1 = nullptr;
-  int last_B = 0;
-  std::atomic<int64_t> step{0};
+  hipEvent_t aev = nullptr;
   NormalGen gen;
   std::vector<float> ou_x;
-  const char* reg_host = nullptr;
-  const char* reg_dev = nullptr;
-  int64_t reg_bytes = 0;
 };
 
 namespace {
@@ -675,17 +616,12 @@ const char* const WORK_NAMES[] = {"y", "qt", "q", "dq", "c_x", "c_a", "c_xh1", "
                                   "a_xh1", "a_a1", "a_dn1", "a_dh1", "a_xh2", "a_a2", "a_dn2", "a_dh2", "a_out", "a_noisy", "g", "do"};
 constexpr int NWORK = sizeof(WORK_NAMES) / sizeof(WORK_NAMES[0]);
 
-void work_table(ga3c_ddpg* m, float*** ptrs, int* widths) {
-  const int S = m->L.S, A = m->L.A;
+void work_table(ga3c_ddpg* m, std::vector<float**>* ptrs, std::vector<size_t>* widths) {
+  const size_t S = m->L.S, A = m->L.A;
   Work& w = m->w;
-  float** p[NWORK] = {&w.y, &w.qt, &w.q, &w.dq, &w.c_x, &w.c_a, &w.c_xh1, &w.c_c1, &w.c_dn1, &w.c_dh1, &w.c_c2, &w.c_dt,
-                      &w.a_xh1, &w.a_a1, &w.a_dn1, &w.a_dh1, &w.a_xh2, &w.a_a2, &w.a_dn2, &w.a_dh2, &w.a_out, &w.a_noisy, &w.g,
-                      &w.dout};
-  const int wd[NWORK] = {1, 1, 1, 1, S, A, H1, H1, H1, H1, H2, H2, H1, H1, H1, H1, H2, H2, H2, H2, A, A, A, A};
-  for (int i = 0; i < NWORK; ++i) {
-    ptrs[i] = p[i];
-    widths[i] = wd[i];
-  }
+  *ptrs = {&w.y, &w.qt, &w.q, &w.dq, &w.c_x, &w.c_a, &w.c_xh1, &w.c_c1, &w.c_dn1, &w.c_dh1, &w.c_c2, &w.c_dt,
+           &w.a_xh1, &w.a_a1, &w.a_dn1, &w.a_dh1, &w.a_xh2, &w.a_a2, &w.a_dn2, &w.a_dh2, &w.a_out, &w.a_noisy, &w.g, &w.dout};
+  *widths = {1, 1, 1, 1, S, A, H1, H1, H1, H1, H2, H2, H1, H1, H1, H1, H2, H2, H2, H2, A, A, A, A};
 }
 
 GradSrc grad_src(ga3c_ddpg* m) {
@@ -737,22 +673,6 @@ Opt make_opt(ga3c_ddpg* m, bool actor, float lr, int64_t t, bool apply, bool sof
   o.apply = apply ? 1 : 0;
   o.soft = soft ? 1 : 0;
   return o;
-}
-
-int check_batch(ga3c_ddpg* m, int B) {
-  if (B < 1 || B > m->cfg.max_batch) return fail(GA3C_EINVAL, "batch %d outside [1,%d]", B, m->cfg.max_batch);
-  return GA3C_OK;
-}
-
-// offsets of rows in the registered segment: each must hold `floats` whole floats inside it
-int check_offsets(ga3c_ddpg* m, const int64_t* off, int B, int floats) {
-  if (!m->reg_dev) return fail(GA3C_ESTATE, "no host segment registered");
-  const int64_t row = 4 * (int64_t)floats;
-  for (int i = 0; i < B; ++i)
-    if (off[i] < 0 || off[i] % 4 != 0 || off[i] > m->reg_bytes - row)
-      return fail(GA3C_EINVAL, "offset %lld of row %d is not a 4-byte aligned row of %lld bytes inside the %lld-byte segment",
-                  (long long)off[i], i, (long long)row, (long long)m->reg_bytes);
-  return GA3C_OK;
 }
 
 // The noise a predict / step 4 adds: the handle's own OU step, the caller's vector, or none.
@@ -808,29 +728,35 @@ int finish_step(ga3c_ddpg* m) {
   return GA3C_OK;
 }
 
-// train / compute on host rows: staged in ring layout, then the same kernels as train_replay
-int step_host(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2, int B, float lr,
-              int mode, const float* noise, int stop_after, float* q_stats) {
-  if (!m || !s || !a || !r || !done || !s2) return fail(GA3C_EINVAL, "null argument");
-  CHK(check_batch(m, B));
-  if (stop_after != 3 && stop_after != 4 && stop_after != 6) return fail(GA3C_EINVAL, "stop_after %d not in {3, 4}", stop_after);
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  Noise nz;
-  CHK(make_noise(m, mode, noise, &nz));
+// n rows in ring layout, s | a | r | done | s2, into `dst` (the one place)
+void pack_rows(const ga3c_ddpg* m, float* dst, const float* s, const float* a, const float* r, const float* done, const float* s2,
+               int n) {
   const int S = m->L.S, A = m->L.A, rowf = m->rowf;
-  for (int i = 0; i < B; ++i) {
-    float* row = m->h_stage + (size_t)i * rowf;
+  for (int i = 0; i < n; ++i) {
+    float* row = dst + (size_t)i * rowf;
     memcpy(row, s + (size_t)i * S, sizeof(float) * S);
     memcpy(row + S, a + (size_t)i * A, sizeof(float) * A);
     row[S + A] = r[i];
     row[S + A + 1] = done[i] != 0.f ? 1.f : 0.f;
     memcpy(row + S + A + 2, s2 + (size_t)i * S, sizeof(float) * S);
   }
+}
+
+// train / compute on host rows: staged in ring layout, then the same kernels as train_replay
+int step_host(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2, int B, float lr,
+              int mode, const float* noise, int stop_after, float* q_stats) {
+  if (!m || !s || !a || !r || !done || !s2) return fail(GA3C_EINVAL, "null argument");
+  CHK(vn::check_batch(m, B));
+  if (stop_after != 3 && stop_after != 4 && stop_after != 6) return fail(GA3C_EINVAL, "stop_after %d not in {3, 4}", stop_after);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  Noise nz;
+  CHK(make_noise(m, mode, noise, &nz));
+  pack_rows(m, m->h_stage, s, a, r, done, s2, B);
   {
     std::lock_guard<std::mutex> lk(m->mu);
-    HIPCHK(hipMemcpyAsync(m->d_stage, m->h_stage, sizeof(float) * B * rowf, hipMemcpyHostToDevice, m->st));
-    CHK(enqueue_step(m, Rows{m->d_stage, nullptr, rowf}, B, lr, nz, stop_after));
+    HIPCHK(hipMemcpyAsync(m->d_stage, m->h_stage, sizeof(float) * B * m->rowf, hipMemcpyHostToDevice, m->st));
+    CHK(enqueue_step(m, Rows{m->d_stage, nullptr, m->rowf}, B, lr, nz, stop_after));
     CHK(finish_step(m));
     m->last_B = B;
   }
@@ -840,97 +766,27 @@ int step_host(ga3c_ddpg* m, const float* s, const float* a, const float* r, cons
   return GA3C_OK;
 }
 
-PLane* take_lane(ga3c_ddpg* m, std::unique_lock<std::mutex>& lk, int* ticket) {
-  for (;;) {
-    for (size_t i = 0; i < m->lanes.size(); ++i)
-      if (!m->lanes[i].busy) {
-        m->lanes[i].busy = true;
-        *ticket = (int)i;
-        return &m->lanes[i];
-      }
-    m->lane_cv.wait(lk);
-  }
-}
-
-void give_lane(ga3c_ddpg* m, PLane* P) {
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    P->busy = false;
-  }
-  m->lane_cv.notify_one();
-}
-
 int predict_begin(ga3c_ddpg* m, const float* x, const int64_t* off, int B, int mode, const float* noise, int* ticket) {
-  CHK(check_batch(m, B));
-  HIPCHK(hipSetDevice(m->cfg.device));
-  if (off) CHK(check_offsets(m, off, B, m->L.S));
+  CHK(vn::predict_check(m, off, B));
   Noise nz;
-  CHK(make_noise(m, mode, noise, &nz));        // one step of the process per call, whatever the batch (:242-251)
-  std::unique_lock<std::mutex> lk(m->mu);
-  PLane* P = take_lane(m, lk, ticket);
-  const int S = m->L.S, A = m->L.A;
-  Input in;
-  hipError_t e = hipSuccess;
-  if (off) {
-    memcpy(P->h_off, off, sizeof(int64_t) * B);
-    e = hipMemcpyAsync(P->d_off, P->h_off, sizeof(int64_t) * B, hipMemcpyHostToDevice, m->st);
-    in = Input{m->reg_dev, P->d_off, 0};
-  } else {
-    memcpy(P->h_x, x, sizeof(float) * B * S);
-    e = hipMemcpyAsync(P->d_x, P->h_x, sizeof(float) * B * S, hipMemcpyHostToDevice, m->st);
-    in = Input{reinterpret_cast<const char*>(P->d_x), nullptr, 4 * (int64_t)S};
-  }
-  if (e == hipSuccess) {
+  CHK(make_noise(m, mode, noise, &nz));        // before a lane is taken: one step of the process per call, whatever the batch
+  return vn::predict_begin(m, x, off, B, ticket, [&](const Input& in, vn::PLane& P) {
     hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(B)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in, B, nz,
-                       P->d_a);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(P->h_a, P->d_a, sizeof(float) * B * A, hipMemcpyDeviceToHost, m->st);
-  if (e == hipSuccess) e = hipEventRecord(P->ev, m->st);
-  if (e != hipSuccess) {
-    P->busy = false;
-    lk.unlock();
-    m->lane_cv.notify_one();
-    (void)hipGetLastError();
-    return fail(GA3C_EHIP, "prediction enqueue failed: %s", hipGetErrorString(e));
-  }
-  P->B = B;
-  return GA3C_OK;
+                       P.out[0].d);
+  });
 }
 
+// v, which only the gather entries ask for, is the first action column.
 int predict_end(ga3c_ddpg* m, int ticket, int B, float* a, float* v) {
-  if (ticket < 0 || ticket >= (int)m->lanes.size()) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
-  PLane* P = &m->lanes[ticket];
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!P->busy) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
-  }
-  const hipError_t e = hipEventSynchronize(P->ev);
-  if (e == hipSuccess && B != P->B) {
-    give_lane(m, P);
-    return fail(GA3C_EINVAL, "batch %d, begun with %d", B, P->B);
-  }
-  if (e == hipSuccess) {
-    const int A = m->L.A;
-    if (a) memcpy(a, P->h_a, sizeof(float) * B * A);
-    if (v)
-      for (int i = 0; i < B; ++i) v[i] = P->h_a[(size_t)i * A];
-  }
-  give_lane(m, P);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(GA3C_EHIP, "prediction failed: %s", hipGetErrorString(e));
-  }
+  vn::PLane* P;
+  CHK(vn::predict_end(m, ticket, B, &P));
+  const int A = m->L.A;
+  const float* h_a = P->out[0].h;
+  if (a) memcpy(a, h_a, sizeof(float) * B * A);
+  if (v)
+    for (int i = 0; i < B; ++i) v[i] = h_a[(size_t)i * A];
+  vn::give_lane(m, P);
   return GA3C_OK;
-}
-
-int param_index(const char* name) {
-  if (!name) return -1;
-  std::string s(name);
-  if (s.size() > 2 && s.compare(s.size() - 2, 2, ":0") == 0) s.resize(s.size() - 2);
-  for (int i = 0; i < NVARS; ++i)
-    if (s == VAR_NAMES[i]) return i;
-  return -1;
 }
 
 // tflearn's name of the target copy: the layer's scope is made a second time, "actor_fc1" -> "actor_fc1_1" (the one place).
@@ -940,70 +796,47 @@ std::string target_name(int i) {
   return s.substr(0, slash) + "_1" + s.substr(slash);
 }
 
-void param_shape(const ga3c_ddpg* m, int i, int32_t* ndim, int64_t shape[4]) {
-  if (m->L.rows[i]) {
-    *ndim = 2;
-    shape[0] = m->L.rows[i];
-    shape[1] = m->L.cols[i];
-  } else {
-    *ndim = 1;
-    shape[0] = m->L.cols[i];
+// The variable table: value and target copy of every variable are checkpoint members; the 20 trainable ones also have the
+// two slots of their optimizer, under Adam's names or RMSProp's.
+void fill_vars(ga3c_ddpg* m) {
+  const Layout& L = m->L;
+  for (int i = 0; i < NVARS; ++i) {
+    const std::string name(VAR_NAMES[i]);
+    vn::Var var{name, L.off[i], L.off[i + 1] - L.off[i], 1, {L.cols[i], 0}, {}};
+    if (L.rows[i]) {                                 // a matrix [rows, cols]; a vector has rows = 0
+      var.ndim = 2;
+      var.shape[0] = L.rows[i];
+      var.shape[1] = L.cols[i];
+    }
+    var.ckpt = {{name + ":0", 0}, {target_name(i) + ":0", 1}};
+    if (i < NTRAIN) {
+      const bool adam = i < NACTOR || (m->cfg.flags & GA3C_DDPG_CRITIC_ADAM);
+      var.ckpt.emplace_back(name + (adam ? "/Adam:0" : "/RMSProp:0"), 2);
+      var.ckpt.emplace_back(name + (adam ? "/Adam_1:0" : "/RMSProp_1:0"), 3);
+    }
+    m->vars.push_back(std::move(var));
   }
-}
-
-int arena_copy(ga3c_ddpg* m, int which, int64_t off, int64_t count, float* out, const float* in) {
-  if (which < 0 || which > 4 || (in && which > 3)) return fail(GA3C_EINVAL, "selector %d not in [0,%d]", which, in ? 3 : 4);
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  if (out) HIPCHK(hipMemcpy(out, m->arena[which] + off, sizeof(float) * count, hipMemcpyDeviceToHost));
-  else HIPCHK(hipMemcpy(m->arena[which] + off, in, sizeof(float) * count, hipMemcpyHostToDevice));
-  return GA3C_OK;
+  m->n = L.off[NVARS];
 }
 
 void free_all(ga3c_ddpg* m) {
-  if (m->st) (void)hipStreamSynchronize(m->st);
-  for (PLane& P : m->lanes) {
-    (void)hipHostFree(P.h_off); (void)hipHostFree(P.h_x); (void)hipHostFree(P.h_a);
-    (void)hipFree(P.d_off); (void)hipFree(P.d_x); (void)hipFree(P.d_a);
-    if (P.ev) (void)hipEventDestroy(P.ev);
-  }
-  for (float*& a : m->arena) (void)hipFree(a);
+  vn::free_core(m);
   (void)hipFree(m->work_base);
   (void)hipFree(m->ring);
   (void)hipHostFree(m->h_stage); (void)hipFree(m->d_stage); (void)hipHostFree(m->h_idx); (void)hipFree(m->d_idx);
   (void)hipHostFree(m->h_q); (void)hipHostFree(m->h_add);
   (void)hipHostFree(m->h_aoff); (void)hipFree(m->d_aoff); (void)hipHostFree(m->h_ar); (void)hipFree(m->d_ar);
   (void)hipHostFree(m->h_aa); (void)hipFree(m->d_aa);
-  for (hipEvent_t e : {m->tev, m->aev, m->t0, m->t1})
-    if (e) (void)hipEventDestroy(e);
-  if (m->reg_host) (void)hipHostUnregister((void*)m->reg_host);
-  if (m->st) (void)hipStreamDestroy(m->st);
+  if (m->aev) (void)hipEventDestroy(m->aev);
   (void)hipGetLastError();
 }
 
-template <class T>
-int dalloc(T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, n * sizeof(T) + 16));
-  return GA3C_OK;
-}
-template <class T>
-int halloc(T** p, size_t n) {
-  HIPCHK(hipHostMalloc((void**)p, n * sizeof(T) + 16, hipHostMallocDefault));
-  return GA3C_OK;
-}
-
-int create(ga3c_ddpg* m) {
+int alloc_all(ga3c_ddpg* m) {
   const ga3c_ddpg_config& c = m->cfg;
-  const size_t B = (size_t)c.max_batch, S = c.state_dim, A = c.num_actions, rowf = (size_t)m->rowf;
-  HIPCHK(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
-  std::vector<float> init((size_t)m->n, 0.f);
-  for (int i = 0; i < 5; ++i) {
-    CHK(dalloc(&m->arena[i], (size_t)m->n));
-    HIPCHK(hipMemset(m->arena[i], 0, sizeof(float) * m->n));
-  }
+  const size_t B = (size_t)c.max_batch, A = c.num_actions, rowf = (size_t)m->rowf;
+  CHK(vn::alloc_core(m, c.predict_lanes));
   // moving_variance = 1 in both copies; the RMSProp ms slot of the critic starts at 1 (TF-1 RMSPropOptimizer)
+  std::vector<float> init((size_t)m->n, 0.f);
   for (int v : {(int)A_MV1, (int)A_MV2, (int)C_MV1})
     for (int64_t i = m->L.off[v]; i < m->L.off[v + 1]; ++i) init[(size_t)i] = 1.f;
   HIPCHK(hipMemcpy(m->arena[0], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
@@ -1013,37 +846,19 @@ int create(ga3c_ddpg* m) {
     for (int64_t i = m->L.off[NACTOR]; i < m->L.off[NTRAIN]; ++i) init[(size_t)i] = 1.f;
     HIPCHK(hipMemcpy(m->arena[2], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
   }
-  float** ptrs[NWORK];
-  int widths[NWORK];
-  work_table(m, ptrs, widths);
-  size_t total = 0;
-  for (int i = 0; i < NWORK; ++i) total += (B * widths[i] + 3) / 4 * 4;
-  CHK(dalloc(&m->work_base, total + 4));
-  HIPCHK(hipMemset(m->work_base, 0, sizeof(float) * (total + 4)));
-  float* q = m->work_base;
-  for (int i = 0; i < NWORK; ++i) {
-    *ptrs[i] = q;
-    q += (B * widths[i] + 3) / 4 * 4;
-  }
-  m->w.qstat = q;
-  CHK(dalloc(&m->ring, (size_t)c.replay_capacity * rowf));
+  std::vector<float**> ptrs;
+  std::vector<size_t> widths;
+  work_table(m, &ptrs, &widths);
+  CHK(vn::carve_rows(B, widths, ptrs, &m->work_base, &m->w.qstat));
+  CHK(vn::dalloc(&m->ring, (size_t)c.replay_capacity * rowf));
   HIPCHK(hipMemset(m->ring, 0, sizeof(float) * (size_t)c.replay_capacity * rowf));
-  CHK(halloc(&m->h_stage, B * rowf)); CHK(dalloc(&m->d_stage, B * rowf));
-  CHK(halloc(&m->h_idx, B)); CHK(dalloc(&m->d_idx, B));
-  CHK(halloc(&m->h_q, 4));
-  CHK(halloc(&m->h_add, B * rowf));
-  CHK(halloc(&m->h_aoff, B)); CHK(dalloc(&m->d_aoff, B)); CHK(halloc(&m->h_ar, B)); CHK(dalloc(&m->d_ar, B));
-  CHK(halloc(&m->h_aa, B * A)); CHK(dalloc(&m->d_aa, B * A));
-  HIPCHK(hipEventCreateWithFlags(&m->tev, hipEventDisableTiming));
+  CHK(vn::halloc(&m->h_stage, B * rowf)); CHK(vn::dalloc(&m->d_stage, B * rowf));
+  CHK(vn::halloc(&m->h_idx, B)); CHK(vn::dalloc(&m->d_idx, B));
+  CHK(vn::halloc(&m->h_q, 4));
+  CHK(vn::halloc(&m->h_add, B * rowf));
+  CHK(vn::halloc(&m->h_aoff, B)); CHK(vn::dalloc(&m->d_aoff, B)); CHK(vn::halloc(&m->h_ar, B)); CHK(vn::dalloc(&m->d_ar, B));
+  CHK(vn::halloc(&m->h_aa, B * A)); CHK(vn::dalloc(&m->d_aa, B * A));
   HIPCHK(hipEventCreateWithFlags(&m->aev, hipEventDisableTiming));
-  HIPCHK(hipEventCreate(&m->t0));
-  HIPCHK(hipEventCreate(&m->t1));
-  m->lanes.resize((size_t)(c.predict_lanes > 0 ? c.predict_lanes : 4));
-  for (PLane& P : m->lanes) {
-    CHK(halloc(&P.h_off, B)); CHK(halloc(&P.h_x, B * S)); CHK(halloc(&P.h_a, B * A));
-    CHK(dalloc(&P.d_off, B)); CHK(dalloc(&P.d_x, B * S)); CHK(dalloc(&P.d_a, B * A));
-    HIPCHK(hipEventCreateWithFlags(&P.ev, hipEventDisableTiming));
-  }
   return GA3C_OK;
 }
 
@@ -1069,34 +884,30 @@ extern "C" {
 int ga3c_ddpg_create(const ga3c_ddpg_config* cfg, ga3c_ddpg** out) {
   if (!cfg || !out) return fail(GA3C_EINVAL, "null argument");
   *out = nullptr;
-  if (cfg->state_dim < 1 || cfg->state_dim > MAX_S) return fail(GA3C_EINVAL, "state_dim %d outside [1,%d]", cfg->state_dim, MAX_S);
-  if (cfg->num_actions < 1 || cfg->num_actions > MAX_A)
-    return fail(GA3C_EINVAL, "num_actions %d outside [1,%d]", cfg->num_actions, MAX_A);
-  if (cfg->max_batch < 1 || cfg->max_batch > 4096) return fail(GA3C_EINVAL, "max_batch %d outside [1,4096]", cfg->max_batch);
+  CHK(vn::check_dims(*cfg, MAX_S, MAX_A, 4096));
   if (cfg->replay_capacity < 1 || cfg->replay_capacity > (1 << 26))
     return fail(GA3C_EINVAL, "replay_capacity %d outside [1,%d]", cfg->replay_capacity, 1 << 26);
   if (cfg->flags & ~(uint32_t)(GA3C_DDPG_FUTURE_REWARD | GA3C_DDPG_LOSS_PAIRED | GA3C_DDPG_GRAD_CLIP | GA3C_DDPG_CRITIC_ADAM |
                                GA3C_DDPG_OU_NOISE))
     return fail(GA3C_EINVAL, "flags 0x%x: not GA3C_DDPG_* flags", cfg->flags);
-  if (cfg->predict_lanes < 0 || cfg->predict_lanes > 64) return fail(GA3C_EINVAL, "predict_lanes %d outside [0,64]", cfg->predict_lanes);
   if (!(cfg->tau >= 0.f && cfg->tau <= 1.f)) return fail(GA3C_EINVAL, "tau %g outside [0,1]", cfg->tau);
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(GA3C_EINVAL, "device %d not in [0,%d)", cfg->device, ndev);
-  HIPCHK(hipSetDevice(cfg->device));
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(GA3C_ESTATE, "device %d is %s; this library is built for gfx950 only", cfg->device, prop.gcnArchName);
+  CHK(vn::check_device(*cfg));
   ga3c_ddpg* m = new (std::nothrow) ga3c_ddpg();
   if (!m) return fail(GA3C_EINVAL, "out of host memory");
   m->cfg = *cfg;
+  m->kind = "DDPG network";
+  m->device = cfg->device;
+  m->S = cfg->state_dim;
+  m->max_batch = cfg->max_batch;
+  m->out_widths = {cfg->num_actions};
+  m->narena = 5;
+  m->nwritable = 4;
   m->L = make_layout(cfg->state_dim, cfg->num_actions);
-  m->n = m->L.off[NVARS];
+  fill_vars(m);
   m->rowf = 2 * cfg->state_dim + cfg->num_actions + 2;
   m->gen.seed((uint64_t)cfg->seed);
   m->ou_x.assign((size_t)cfg->num_actions, 0.f);
-  const int rc = create(m);
+  const int rc = alloc_all(m);
   if (rc != GA3C_OK) {
     free_all(m);
     delete m;
@@ -1108,17 +919,15 @@ int ga3c_ddpg_create(const ga3c_ddpg_config* cfg, ga3c_ddpg** out) {
 
 int ga3c_ddpg_destroy(ga3c_ddpg* m) {
   if (!m) return fail(GA3C_EINVAL, "null argument");
-  (void)hipSetDevice(m->cfg.device);
+  (void)hipSetDevice(m->device);
   free_all(m);
   delete m;
   return GA3C_OK;
 }
 
-int32_t ga3c_ddpg_num_params(ga3c_ddpg* m) { return m ? NVARS : 0; }
+int32_t ga3c_ddpg_num_params(ga3c_ddpg* m) { return vn::num_params(m); }
 
-const char* ga3c_ddpg_param_name(ga3c_ddpg* m, int32_t index) {
-  return (m && index >= 0 && index < NVARS) ? VAR_NAMES[index] : nullptr;
-}
+const char* ga3c_ddpg_param_name(ga3c_ddpg* m, int32_t index) { return vn::param_name(m, index); }
 
 const char* ga3c_ddpg_target_name(ga3c_ddpg* m, int32_t index) {
   static std::string names[NVARS];
@@ -1130,130 +939,38 @@ const char* ga3c_ddpg_target_name(ga3c_ddpg* m, int32_t index) {
 }
 
 int ga3c_ddpg_param_info(ga3c_ddpg* m, const char* name, int64_t* count, int32_t* ndim, int64_t shape[4], int32_t* trainable) {
-  if (!m || !name) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  if (count) *count = m->L.off[i + 1] - m->L.off[i];
-  int32_t nd;
-  int64_t sh[4] = {0, 0, 0, 0};
-  param_shape(m, i, &nd, sh);
-  if (ndim) *ndim = nd;
-  if (shape) memcpy(shape, sh, sizeof sh);
-  if (trainable) *trainable = i < NTRAIN ? 1 : 0;
+  CHK(vn::param_info(m, name, nullptr, count, ndim, shape));
+  if (trainable) *trainable = vn::param_index(m, name) < NTRAIN ? 1 : 0;
   return GA3C_OK;
 }
 
 int ga3c_ddpg_get_param(ga3c_ddpg* m, const char* name, int32_t which, float* out, int64_t count) {
-  if (!m || !name || !out) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  const int64_t cnt = m->L.off[i + 1] - m->L.off[i];
-  if (count != cnt) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)cnt, (long long)count);
-  return arena_copy(m, which, m->L.off[i], count, out, nullptr);
+  if (!out) return fail(GA3C_EINVAL, "null argument");
+  return vn::param_copy(m, name, which, out, nullptr, count);
 }
 
 int ga3c_ddpg_set_param(ga3c_ddpg* m, const char* name, int32_t which, const float* in, int64_t count) {
-  if (!m || !name || !in) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  const int64_t cnt = m->L.off[i + 1] - m->L.off[i];
-  if (count != cnt) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)cnt, (long long)count);
-  return arena_copy(m, which, m->L.off[i], count, nullptr, in);
+  if (!in) return fail(GA3C_EINVAL, "null argument");
+  return vn::param_copy(m, name, which, nullptr, in, count);
 }
 
-int ga3c_ddpg_get_step(ga3c_ddpg* m, int64_t* step) {
-  if (!m || !step) return fail(GA3C_EINVAL, "null argument");
-  *step = m->step.load();
-  return GA3C_OK;
-}
+int ga3c_ddpg_get_step(ga3c_ddpg* m, int64_t* step) { return vn::get_step(m, step); }
 
-int ga3c_ddpg_set_step(ga3c_ddpg* m, int64_t step) {
+int ga3c_ddpg_set_step(ga3c_ddpg* m, int64_t step) {      // Adam's t: never below zero
   if (!m || step < 0) return fail(GA3C_EINVAL, "bad argument");
-  m->step.store(step);
-  return GA3C_OK;
+  return vn::set_step(m, step);
 }
 
-// Checkpoint members of variable i: (member name, arena) pairs.
-static std::vector<std::pair<std::string, int>> ckpt_members(const ga3c_ddpg* m, int i) {
-  std::vector<std::pair<std::string, int>> v;
-  v.emplace_back(std::string(VAR_NAMES[i]) + ":0", 0);
-  v.emplace_back(target_name(i) + ":0", 1);
-  if (i < NTRAIN) {
-    const bool adam = i < NACTOR || (m->cfg.flags & GA3C_DDPG_CRITIC_ADAM);
-    v.emplace_back(std::string(VAR_NAMES[i]) + (adam ? "/Adam:0" : "/RMSProp:0"), 2);
-    v.emplace_back(std::string(VAR_NAMES[i]) + (adam ? "/Adam_1:0" : "/RMSProp_1:0"), 3);
-  }
-  return v;
-}
-
-int ga3c_ddpg_save(ga3c_ddpg* m, const char* path) {
-  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
-  std::vector<float> arena[4];
-  for (int w = 0; w < 4; ++w) {
-    arena[w].resize((size_t)m->n);
-    CHK(arena_copy(m, w, 0, m->n, arena[w].data(), nullptr));
-  }
-  std::vector<ga3c_ckpt::Member> members;
-  ga3c_ckpt::Member st;
-  st.name = "step";
-  st.descr = "<i8";
-  const int64_t step = m->step.load();
-  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
-  members.push_back(st);
-  for (int i = 0; i < NVARS; ++i) {
-    int32_t nd;
-    int64_t sh[4];
-    param_shape(m, i, &nd, sh);
-    for (const auto& km : ckpt_members(m, i)) {
-      ga3c_ckpt::Member mb;
-      mb.name = km.first;
-      mb.descr = "<f4";
-      mb.shape.assign(sh, sh + nd);
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[km.second].data() + m->L.off[i]);
-      mb.bytes.assign(src, src + (size_t)(m->L.off[i + 1] - m->L.off[i]) * sizeof(float));
-      members.push_back(std::move(mb));
-    }
-  }
-  std::string err;
-  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  return GA3C_OK;
-}
+int ga3c_ddpg_save(ga3c_ddpg* m, const char* path) { return vn::save(m, path); }
 
 int ga3c_ddpg_load(ga3c_ddpg* m, const char* path) {
   if (!m || !path) return fail(GA3C_EINVAL, "null argument");
   std::map<std::string, ga3c_ckpt::Member> members;
-  std::string err;
-  if (!ga3c_ckpt::read_npz(path, &members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  std::vector<float> arena[4];
-  for (int w = 0; w < 4; ++w) {
-    arena[w].resize((size_t)m->n);
-    CHK(arena_copy(m, w, 0, m->n, arena[w].data(), nullptr));     // slots no member names keep their values
-  }
-  for (int i = 0; i < NVARS; ++i) {
-    const int64_t cnt = m->L.off[i + 1] - m->L.off[i];
-    int32_t nd;
-    int64_t sh[4];
-    param_shape(m, i, &nd, sh);
-    for (const auto& km : ckpt_members(m, i)) {
-      auto it = members.find(km.first);
-      if (it == members.end())
-        return fail(GA3C_ESTATE, "%s holds no %s: not a checkpoint of this DDPG network", path, km.first.c_str());
-      const ga3c_ckpt::Member& mb = it->second;
-      const bool shape_ok = mb.shape.size() == (size_t)nd && std::equal(mb.shape.begin(), mb.shape.end(), sh);
-      if (mb.descr != "<f4" || !shape_ok || mb.bytes.size() != (size_t)cnt * sizeof(float))
-        return fail(GA3C_ESTATE, "%s: %s is not <f4 of this network's shape (%lld elements)", path, km.first.c_str(), (long long)cnt);
-      memcpy(arena[km.second].data() + m->L.off[i], mb.bytes.data(), mb.bytes.size());
-    }
-  }
-  auto st = members.find("step");
-  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
-    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
+  CHK(vn::read_checkpoint(path, &members));
   int64_t step = 0;
-  memcpy(&step, st->second.bytes.data(), 8);
-  if (step < 0) return fail(GA3C_ESTATE, "%s: step %lld", path, (long long)step);
-  for (int w = 0; w < 4; ++w) CHK(arena_copy(m, w, 0, m->n, nullptr, arena[w].data()));
-  m->step.store(step);
-  return GA3C_OK;
+  CHK(vn::checkpoint_step(path, members, &step));
+  if (step < 0) return fail(GA3C_ESTATE, "%s: step %lld", path, (long long)step);      // before anything is written
+  return vn::load(m, path, members);
 }
 
 int ga3c_ddpg_noise_step(ga3c_ddpg* m, float* x, float* n) {
@@ -1279,38 +996,19 @@ int ga3c_ddpg_predict(ga3c_ddpg* m, const float* x, int32_t batch, int32_t noise
   return predict_end(m, ticket, batch, a, nullptr);
 }
 
+// The segment must not change under a replay_add_gather either, so add_mu is held round the shared call, which takes
+// train_mu, then mu.  Every other path takes add_mu -> mu (replay_add*) or train_mu -> mu and never add_mu while it holds
+// train_mu or mu, so the order add_mu -> train_mu -> mu has no cycle.
 int ga3c_ddpg_register_host(ga3c_ddpg* m, void* base, int64_t bytes) {
-  if (!m || !base || bytes < 16) return fail(GA3C_EINVAL, "bad argument");
-  if (m->reg_host) return fail(GA3C_ESTATE, "a host segment is already registered");
-  HIPCHK(hipSetDevice(m->cfg.device));
-  HIPCHK(hipHostRegister(base, (size_t)bytes, hipHostRegisterMapped));
-  void* dev = nullptr;
-  hipError_t e = hipHostGetDevicePointer(&dev, base, 0);
-  if (e != hipSuccess) {
-    (void)hipHostUnregister(base);
-    return fail(GA3C_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
-  }
-  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (!m) return fail(GA3C_EINVAL, "bad argument");
   std::lock_guard<std::mutex> al(m->add_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  m->reg_host = static_cast<const char*>(base);
-  m->reg_dev = static_cast<const char*>(dev);
-  m->reg_bytes = bytes;
-  return GA3C_OK;
+  return vn::register_host(m, base, bytes);
 }
 
 int ga3c_ddpg_unregister_host(ga3c_ddpg* m) {
   if (!m) return fail(GA3C_EINVAL, "null argument");
-  if (!m->reg_host) return GA3C_OK;
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
   std::lock_guard<std::mutex> al(m->add_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  HIPCHK(hipHostUnregister((void*)m->reg_host));
-  m->reg_host = m->reg_dev = nullptr;
-  m->reg_bytes = 0;
-  return GA3C_OK;
+  return vn::unregister_host(m);
 }
 
 int ga3c_ddpg_predict_gather(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v, float* z) {
@@ -1339,17 +1037,9 @@ int ga3c_ddpg_replay_add(ga3c_ddpg* m, const float* s, const float* a, const flo
   if (!m || !s || !a || !r || !done || !s2) return fail(GA3C_EINVAL, "null argument");
   if (n < 1 || n > m->cfg.max_batch || n > m->cfg.replay_capacity)
     return fail(GA3C_EINVAL, "%d rows outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
-  HIPCHK(hipSetDevice(m->cfg.device));
+  HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> al(m->add_mu);
-  const int S = m->L.S, A = m->L.A, rowf = m->rowf;
-  for (int i = 0; i < n; ++i) {
-    float* row = m->h_add + (size_t)i * rowf;
-    memcpy(row, s + (size_t)i * S, sizeof(float) * S);
-    memcpy(row + S, a + (size_t)i * A, sizeof(float) * A);
-    row[S + A] = r[i];
-    row[S + A + 1] = done[i] != 0.f ? 1.f : 0.f;
-    memcpy(row + S + A + 2, s2 + (size_t)i * S, sizeof(float) * S);
-  }
+  pack_rows(m, m->h_add, s, a, r, done, s2, n);
   {
     std::lock_guard<std::mutex> lk(m->mu);
     CHK(ring_copy_in(m, m->h_add, n, hipMemcpyHostToDevice));
@@ -1366,12 +1056,12 @@ int ga3c_ddpg_replay_add_gather(ga3c_ddpg* m, const int64_t* offsets, const floa
   if (!m || !offsets || !r || !a) return fail(GA3C_EINVAL, "null argument");
   if (n < 1 || n > m->cfg.max_batch || n > m->cfg.replay_capacity)
     return fail(GA3C_EINVAL, "%d rows outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
-  HIPCHK(hipSetDevice(m->cfg.device));
+  HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> al(m->add_mu);
   const int S = m->L.S, A = m->L.A;
   {
     std::lock_guard<std::mutex> lk(m->mu);
-    CHK(check_offsets(m, offsets, n, 2 * S + 1));
+    CHK(vn::check_offsets(m, offsets, n, 2 * S + 1));
     memcpy(m->h_aoff, offsets, sizeof(int64_t) * n);
     memcpy(m->h_ar, r, sizeof(float) * n);
     memcpy(m->h_aa, a, sizeof(float) * n * A);
@@ -1393,7 +1083,7 @@ int ga3c_ddpg_replay_add_gather(ga3c_ddpg* m, const int64_t* offsets, const floa
 
 int ga3c_ddpg_replay_get(ga3c_ddpg* m, int64_t slot, float* s, float* a, float* r, float* done, float* s2) {
   if (!m) return fail(GA3C_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(m->cfg.device));
+  HIPCHK(hipSetDevice(m->device));
   std::vector<float> row((size_t)m->rowf);
   {
     std::lock_guard<std::mutex> lk(m->mu);
@@ -1433,8 +1123,8 @@ int ga3c_ddpg_compute(ga3c_ddpg* m, const float* s, const float* a, const float*
 int ga3c_ddpg_train_replay(ga3c_ddpg* m, const int32_t* slots, int32_t batch, int64_t stamp, float learning_rate,
                            int32_t noise_mode, const float* noise, float* q_stats) {
   if (!m || !slots) return fail(GA3C_EINVAL, "null argument");
-  CHK(check_batch(m, batch));
-  HIPCHK(hipSetDevice(m->cfg.device));
+  CHK(vn::check_batch(m, batch));
+  HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> tl(m->train_mu);
   {
     std::lock_guard<std::mutex> lk(m->mu);
@@ -1466,27 +1156,19 @@ int ga3c_ddpg_train_replay(ga3c_ddpg* m, const int32_t* slots, int32_t batch, in
 
 int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
   if (!m || !name || !out) return fail(GA3C_EINVAL, "null argument");
-  float** ptrs[NWORK];
-  int widths[NWORK];
-  work_table(m, ptrs, widths);
-  int k = -1;
+  std::vector<float**> ptrs;
+  std::vector<size_t> widths;
+  work_table(m, &ptrs, &widths);
   for (int i = 0; i < NWORK; ++i)
-    if (strcmp(name, WORK_NAMES[i]) == 0) k = i;
-  if (k < 0) return fail(GA3C_EINVAL, "no buffer named %s", name);
-  if (count != (int64_t)widths[k] * m->last_B)
-    return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)widths[k] * m->last_B, (long long)count);
-  HIPCHK(hipSetDevice(m->cfg.device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  HIPCHK(hipMemcpy(out, *ptrs[k], sizeof(float) * count, hipMemcpyDeviceToHost));
-  return GA3C_OK;
+    if (strcmp(name, WORK_NAMES[i]) == 0) return vn::fetch(m, name, *ptrs[i], (int64_t)widths[i], out, count);
+  return fail(GA3C_EINVAL, "no buffer named %s", name);
 }
 
+// Unlike the actor-critic nets' it advances `step` with every iteration: Adam's t must move.
 int ga3c_ddpg_time_resident(ga3c_ddpg* m, int32_t mode, int32_t batch, int32_t iters, float learning_rate, float* elapsed_ms) {
   if (!m || !elapsed_ms || iters < 1 || (mode != 0 && mode != 1)) return fail(GA3C_EINVAL, "bad argument");
-  CHK(check_batch(m, batch));
-  HIPCHK(hipSetDevice(m->cfg.device));
+  CHK(vn::check_batch(m, batch));
+  HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> tl(m->train_mu);
   {
     std::lock_guard<std::mutex> lk(m->mu);

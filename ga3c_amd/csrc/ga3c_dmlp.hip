@@ -572,7 +572,7 @@ extern "C" {
 int ga3c_dmlp_create(const ga3c_dmlp_config* cfg, ga3c_dmlp** out) {
   if (!cfg || !out) return fail(GA3C_EINVAL, "null argument");
   *out = nullptr;
-  CHK(check_dims(*cfg, MAX_S, MAX_A));
+  CHK(check_dims(*cfg, MAX_S, MAX_A, 65536));
   if (cfg->num_layers < 1 || cfg->num_layers > MAX_L) return fail(GA3C_EINVAL, "num_layers %d outside [1,%d]", cfg->num_layers, MAX_L);
   for (int l = 0; l < cfg->num_layers; ++l)
     if (cfg->widths[l] < 1 || cfg->widths[l] > WIDE)
@@ -632,8 +632,7 @@ int ga3c_dmlp_save(ga3c_dmlp* m, const char* path) { return save(m, path); }
 int ga3c_dmlp_load(ga3c_dmlp* m, const char* path) {
   if (!m || !path) return fail(GA3C_EINVAL, "null argument");
   std::map<std::string, ga3c_ckpt::Member> members;
-  std::string err;
-  if (!ga3c_ckpt::read_npz(path, &members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  CHK(read_checkpoint(path, &members));
   // a file of another network kind holds no dense1_1_p/w; one of this kind with more layers holds dense1_<L+1>_p/w:
   // both refused before anything is written
   if (members.count(layer_name(m->L.L) + "/w:0"))

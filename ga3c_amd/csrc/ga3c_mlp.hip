@@ -491,7 +491,7 @@ extern "C" {
 int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out) {
   if (!cfg || !out) return fail(GA3C_EINVAL, "null argument");
   *out = nullptr;
-  CHK(check_dims(*cfg, MAX_S, MAX_A));
+  CHK(check_dims(*cfg, MAX_S, MAX_A, 65536));
   if (!(cfg->flags & GA3C_FLAG_CONTINUOUS))
     return fail(GA3C_EINVAL, "the vector-state network has the angle-output head only: GA3C_FLAG_CONTINUOUS is required");
   if (cfg->flags & ~(uint32_t)(GA3C_FLAG_CONTINUOUS | GA3C_FLAG_GRAD_CLIP))

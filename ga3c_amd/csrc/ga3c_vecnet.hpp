@@ -1,8 +1,17 @@
-// ga3c_vecnet.hpp -- the host half that the vector-state networks share (ga3c_mlp.hip, ga3c_dmlp.hip):
-// return codes, arenas 0/1/2/3, one stream, a lane per prediction in flight, train-type calls serialised, the variables by
-// name and the .npz checkpoint.
+// ga3c_vecnet.hpp -- the host half that the vector-state handles share, in two layers.
 //
-// A network's handle N derives from Net, fills the variable table (add_dense) before create() and supplies
+// Core: what all three handles have (ga3c_mlp.hip, ga3c_dmlp.hip, ga3c_ddpg.hip) -- return codes, one stream, a lane per
+// prediction in flight, train-type calls serialised, the registered host segment, the arenas, the variables by name and the
+// .npz checkpoint.  A handle fills, before alloc_core,
+//   kind, device, S, max_batch                 what it calls itself in an error text; S: the floats of a prediction row
+//   out_widths                                 the outputs of a lane, floats per row each: p[A], v[1], z[ZW], or DDPG's a[A]
+//   narena, nwritable                          arenas, and how many of them set_* and a checkpoint reach: 4 / 3, or 5 / 4
+//   vars                                       the variable table, each variable with its (checkpoint member, arena) pairs
+// and passes predict_begin the launch of its own row kernel.
+//
+// Net: the actor-critic layer of ga3c_mlp and ga3c_dmlp on top of Core -- TF-1 RMSProp on arenas 0/1/2/3, the train staging
+// and the train-type calls.  A network's handle N derives from Net, fills the variable table (add_dense) before create() and
+// supplies
 //   cfg                                        its ABI config: device, state_dim, num_actions, max_batch, flags,
 //                                              rmsprop_decay / _momentum / _epsilon, grad_clip_norm, predict_lanes
 //   w                                          its Work: the rows p, v, z the train-type calls write and losses[3]
@@ -11,7 +20,8 @@
 //   wgrad(B, opt, fused)                       enqueue the weight gradients and the loss sums; fused: + RMSProp
 //   update(opt, clip)                          enqueue the optimizer step on arena 3
 //   loss(B)                                    enqueue the loss sums alone
-// Everything else the two networks differ in is data of Net.  Nothing here asks which network it serves.
+// struct ga3c_ddpg derives from Core alone: its train step, its replay ring and its noise are its own.
+// Everything else the handles differ in is data of Core or Net.  Nothing here asks which network it serves.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +35,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ga3c_abi.h"
@@ -82,52 +93,465 @@ int halloc(T** p, size_t n) {
   return GA3C_OK;
 }
 
+// ------------------------------------------------------------------ Core: every vector-state handle
+
+struct Out {                      // one output of a lane: B x width floats, pinned host and device
+  float* h; float* d;
+  int width;
+};
+
 struct PLane {                    // one prediction in flight: pinned staging + device outputs + completion event
-  int64_t* h_off = nullptr; float* h_x = nullptr; float* h_p = nullptr; float* h_v = nullptr; float* h_z = nullptr;
-  int64_t* d_off = nullptr; float* d_x = nullptr; float* d_p = nullptr; float* d_v = nullptr; float* d_z = nullptr;
+  int64_t* h_off = nullptr; float* h_x = nullptr;
+  int64_t* d_off = nullptr; float* d_x = nullptr;
+  std::vector<Out> out;           // in the order of Core::out_widths
   hipEvent_t ev = nullptr;
   bool busy = false;
   int B = 0;
 };
 
-struct Var {                      // one variable: its name (no ":0"), its first arena element and its shape
-  std::string name;
+struct Var {                      // one variable: its name (no ":0"), its first arena element, its shape, and the
+  std::string name;               // (member name, arena) pairs a checkpoint keeps it under
   int64_t off, count;
   int32_t ndim;
   int64_t shape[2];
+  std::vector<std::pair<std::string, int>> ckpt;
 };
 
-struct Net {
+struct Core {
   const char* kind = "";          // what the network calls itself in an error text
-  int S = 0, A = 0;
-  int ZW = 0;                     // logits per row
+  int S = 0;                      // floats of a prediction row
   int max_batch = 0, device = 0;
+  std::vector<int> out_widths;    // a lane's outputs, floats per row each
   std::vector<Var> vars;          // arena order
   int64_t n = 0;                  // arena size
-  bool clip = false;
-  Opt opt{};                      // the arenas and the optimizer's constants; lr is the call's
+  int narena = 0, nwritable = 0;  // arenas 0 .. nwritable-1 are what set_* and a checkpoint reach; the others are read only
+  float* arena[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = nullptr;       // every kernel and copy of the network: a prediction sees the weights before or after a
                                   // train step, never a mix, and needs no second buffer
   std::mutex mu;                  // enqueue order on `st` and the lanes' bookkeeping
   std::condition_variable lane_cv;
-  std::mutex train_mu;            // one train / evaluate / arena call at a time (they share the staging below)
+  std::mutex train_mu;            // one train / evaluate / arena call at a time (they share the network's train staging)
   std::vector<PLane> lanes;
-  float* arena[4] = {nullptr, nullptr, nullptr, nullptr};   // theta, ms, mom, grad
-  // train staging: pinned host + device
-  float* h_x = nullptr; float* h_y = nullptr; float* h_a = nullptr; int64_t* h_off = nullptr; float* h_loss = nullptr;
-  float* d_x = nullptr; float* d_y = nullptr; float* d_a = nullptr; int64_t* d_off = nullptr;
   hipEvent_t tev = nullptr, t0 = nullptr, t1 = nullptr;
   int last_B = 0;                 // rows of the last train / evaluate / resident step (fetch)
-  int res_B = 0;                  // rows uploaded for the resident path
   std::atomic<int64_t> step{0};
   const char* reg_host = nullptr;
   const char* reg_dev = nullptr;
   int64_t reg_bytes = 0;
+};
+
+inline int check_batch(const Core* m, int B) {
+  if (B < 1 || B > m->max_batch) return fail(GA3C_EINVAL, "batch %d outside [1,%d]", B, m->max_batch);
+  return GA3C_OK;
+}
+
+// offsets of rows in the registered segment: each must hold `floats` whole floats inside it
+inline int check_offsets(const Core* m, const int64_t* off, int B, int floats) {
+  if (!m->reg_dev) return fail(GA3C_ESTATE, "no host segment registered");
+  const int64_t row = 4 * (int64_t)floats;
+  for (int i = 0; i < B; ++i)
+    if (off[i] < 0 || off[i] % 4 != 0 || off[i] > m->reg_bytes - row)
+      return fail(GA3C_EINVAL, "offset %lld of row %d is not a 4-byte aligned row of %lld bytes inside the %lld-byte segment",
+                  (long long)off[i], i, (long long)row, (long long)m->reg_bytes);
+  return GA3C_OK;
+}
+
+inline PLane* take_lane(Core* m, std::unique_lock<std::mutex>& lk, int* ticket) {
+  for (;;) {
+    for (size_t i = 0; i < m->lanes.size(); ++i)
+      if (!m->lanes[i].busy) {
+        m->lanes[i].busy = true;
+        *ticket = (int)i;
+        return &m->lanes[i];
+      }
+    m->lane_cv.wait(lk);
+  }
+}
+
+inline void give_lane(Core* m, PLane* P) {
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    P->busy = false;
+  }
+  m->lane_cv.notify_one();
+}
+
+// What a prediction is refused for, before the network draws or takes anything for it; leaves its device current.
+inline int predict_check(const Core* m, const int64_t* off, int B) {
+  CHK(check_batch(m, B));
+  HIPCHK(hipSetDevice(m->device));
+  if (off) CHK(check_offsets(m, off, B, m->S));
+  return GA3C_OK;
+}
+
+// Enqueues one prediction that passed predict_check on a lane of its own (x: host rows; off: rows of the registered
+// segment): the input copy, launch(in, lane) -- the network's row kernel from `in` into the lane's out[].d -- and one copy to
+// the host per output, in their order.
+template <class Launch>
+int predict_begin(Core* m, const float* x, const int64_t* off, int B, int* ticket, Launch launch) {
+  std::unique_lock<std::mutex> lk(m->mu);
+  PLane* P = take_lane(m, lk, ticket);
+  const int S = m->S;
+  Input in;
+  hipError_t e = hipSuccess;
+  if (off) {
+    memcpy(P->h_off, off, sizeof(int64_t) * B);
+    e = hipMemcpyAsync(P->d_off, P->h_off, sizeof(int64_t) * B, hipMemcpyHostToDevice, m->st);
+    in = Input{m->reg_dev, P->d_off, 0};
+  } else {
+    memcpy(P->h_x, x, sizeof(float) * B * S);
+    e = hipMemcpyAsync(P->d_x, P->h_x, sizeof(float) * B * S, hipMemcpyHostToDevice, m->st);
+    in = Input{reinterpret_cast<const char*>(P->d_x), nullptr, 4 * (int64_t)S};
+  }
+  if (e == hipSuccess) {
+    launch(in, *P);
+    e = hipGetLastError();
+  }
+  for (const Out& o : P->out)
+    if (e == hipSuccess) e = hipMemcpyAsync(o.h, o.d, sizeof(float) * B * o.width, hipMemcpyDeviceToHost, m->st);
+  if (e == hipSuccess) e = hipEventRecord(P->ev, m->st);
+  if (e != hipSuccess) {
+    P->busy = false;
+    lk.unlock();
+    m->lane_cv.notify_one();
+    (void)hipGetLastError();
+    return fail(GA3C_EHIP, "prediction enqueue failed: %s", hipGetErrorString(e));
+  }
+  P->B = B;
+  return GA3C_OK;
+}
+
+// Waits for the prediction begun under `ticket`.  GA3C_OK: *lane holds its B rows in out[].h and stays the caller's until
+// give_lane; otherwise the lane is free again.
+inline int predict_end(Core* m, int ticket, int B, PLane** lane) {
+  if (ticket < 0 || ticket >= (int)m->lanes.size()) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
+  PLane* P = &m->lanes[ticket];
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!P->busy) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
+  }
+  const hipError_t e = hipEventSynchronize(P->ev);     // the lane's staging is free for the next begin only after this
+  if (e != hipSuccess) {
+    give_lane(m, P);
+    (void)hipGetLastError();
+    return fail(GA3C_EHIP, "prediction failed: %s", hipGetErrorString(e));
+  }
+  if (B != P->B) {
+    give_lane(m, P);
+    return fail(GA3C_EINVAL, "batch %d, begun with %d", B, P->B);
+  }
+  *lane = P;
+  return GA3C_OK;
+}
+
+inline int param_index(const Core* m, const char* name) {
+  if (!name) return -1;
+  std::string s(name);
+  if (s.size() > 2 && s.compare(s.size() - 2, 2, ":0") == 0) s.resize(s.size() - 2);
+  for (size_t i = 0; i < m->vars.size(); ++i)
+    if (s == m->vars[i].name) return (int)i;
+  return -1;
+}
+
+inline int arena_copy(Core* m, int which, int64_t off, int64_t count, float* out, const float* in) {
+  const int last = (in ? m->nwritable : m->narena) - 1;
+  if (which < 0 || which > last) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, last);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  if (out) HIPCHK(hipMemcpy(out, m->arena[which] + off, sizeof(float) * count, hipMemcpyDeviceToHost));
+  else HIPCHK(hipMemcpy(m->arena[which] + off, in, sizeof(float) * count, hipMemcpyHostToDevice));
+  return GA3C_OK;
+}
+
+inline int param_count(Core* m, int64_t* count) {
+  if (!m || !count) return fail(GA3C_EINVAL, "null argument");
+  *count = m->n;
+  return GA3C_OK;
+}
+
+inline int get_arena(Core* m, int32_t which, float* out, int64_t count) {
+  if (!m || !out) return fail(GA3C_EINVAL, "null argument");
+  if (count != m->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)m->n);
+  return arena_copy(m, which, 0, count, out, nullptr);
+}
+
+inline int set_arena(Core* m, int32_t which, const float* in, int64_t count) {
+  if (!m || !in) return fail(GA3C_EINVAL, "null argument");
+  if (count != m->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)m->n);
+  return arena_copy(m, which, 0, count, nullptr, in);
+}
+
+inline int get_step(Core* m, int64_t* step) {
+  if (!m || !step) return fail(GA3C_EINVAL, "null argument");
+  *step = m->step.load();
+  return GA3C_OK;
+}
+
+inline int set_step(Core* m, int64_t step) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  m->step.store(step);
+  return GA3C_OK;
+}
+
+inline int32_t num_params(Core* m) { return m ? (int32_t)m->vars.size() : 0; }
+
+inline const char* param_name(Core* m, int32_t index) {
+  return (m && index >= 0 && index < (int32_t)m->vars.size()) ? m->vars[index].name.c_str() : nullptr;
+}
+
+inline int param_info(Core* m, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]) {
+  if (!m || !name) return fail(GA3C_EINVAL, "null argument");
+  const int i = param_index(m, name);
+  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
+  const Var& var = m->vars[i];
+  if (offset) *offset = var.off;
+  if (count) *count = var.count;
+  if (ndim) *ndim = var.ndim;
+  const int64_t sh[4] = {var.shape[0], var.shape[1], 0, 0};
+  if (shape) memcpy(shape, sh, sizeof sh);
+  return GA3C_OK;
+}
+
+// get_param (out) / set_param (in)
+inline int param_copy(Core* m, const char* name, int32_t which, float* out, const float* in, int64_t count) {
+  if (!m || !name || (!out && !in)) return fail(GA3C_EINVAL, "null argument");
+  const int i = param_index(m, name);
+  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
+  const Var& var = m->vars[i];
+  if (count != var.count) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)var.count, (long long)count);
+  return arena_copy(m, which, var.off, count, out, in);
+}
+
+// The writable arenas on the host, as save writes and load starts from them.
+inline int read_arenas(Core* m, std::vector<std::vector<float>>* arena) {
+  arena->assign((size_t)m->nwritable, std::vector<float>((size_t)m->n));
+  for (int w = 0; w < m->nwritable; ++w) CHK(get_arena(m, w, (*arena)[w].data(), m->n));
+  return GA3C_OK;
+}
+
+// step, then the members of every variable in table order
+inline int save(Core* m, const char* path) {
+  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
+  std::vector<std::vector<float>> arena;
+  CHK(read_arenas(m, &arena));
+  std::vector<ga3c_ckpt::Member> members;
+  ga3c_ckpt::Member st;
+  st.name = "step";
+  st.descr = "<i8";
+  const int64_t step = m->step.load();
+  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
+  members.push_back(st);
+  for (const Var& var : m->vars)
+    for (const auto& km : var.ckpt) {
+      ga3c_ckpt::Member mb;
+      mb.name = km.first;
+      mb.descr = "<f4";
+      mb.shape.assign(var.shape, var.shape + var.ndim);
+      const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[km.second].data() + var.off);
+      mb.bytes.assign(src, src + (size_t)var.count * sizeof(float));
+      members.push_back(std::move(mb));
+    }
+  std::string err;
+  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  return GA3C_OK;
+}
+
+inline int read_checkpoint(const char* path, std::map<std::string, ga3c_ckpt::Member>* members) {
+  std::string err;
+  if (!ga3c_ckpt::read_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  return GA3C_OK;
+}
+
+inline int checkpoint_step(const char* path, const std::map<std::string, ga3c_ckpt::Member>& members, int64_t* step) {
+  auto st = members.find("step");
+  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
+    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
+  memcpy(step, st->second.bytes.data(), 8);
+  return GA3C_OK;
+}
+
+// `members`: the file, read already.  A file of another network kind lacks this one's first variable: refused, as is any
+// member of another shape, before anything is written.  An arena element that no member names keeps its value.
+inline int load(Core* m, const char* path, const std::map<std::string, ga3c_ckpt::Member>& members) {
+  std::vector<std::vector<float>> arena;
+  CHK(read_arenas(m, &arena));
+  for (const Var& var : m->vars)
+    for (const auto& km : var.ckpt) {
+      const std::string& key = km.first;
+      auto it = members.find(key);
+      if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s: not a checkpoint of this %s", path, key.c_str(), m->kind);
+      const ga3c_ckpt::Member& mb = it->second;
+      const bool shape_ok = mb.shape.size() == (size_t)var.ndim && std::equal(mb.shape.begin(), mb.shape.end(), var.shape);
+      if (mb.descr != "<f4" || !shape_ok || mb.bytes.size() != (size_t)var.count * sizeof(float))
+        return fail(GA3C_ESTATE, "%s: %s is not <f4 of this network's shape (%lld elements)", path, key.c_str(),
+                    (long long)var.count);
+      memcpy(arena[km.second].data() + var.off, mb.bytes.data(), mb.bytes.size());
+    }
+  int64_t step = 0;
+  CHK(checkpoint_step(path, members, &step));
+  for (int w = 0; w < m->nwritable; ++w) CHK(set_arena(m, w, arena[w].data(), m->n));
+  m->step.store(step);
+  return GA3C_OK;
+}
+
+inline int load(Core* m, const char* path) {
+  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
+  std::map<std::string, ga3c_ckpt::Member> members;
+  CHK(read_checkpoint(path, &members));
+  return load(m, path, members);
+}
+
+inline int register_host(Core* m, void* base, int64_t bytes) {
+  if (!m || !base || bytes < 16) return fail(GA3C_EINVAL, "bad argument");
+  if (m->reg_host) return fail(GA3C_ESTATE, "a host segment is already registered");
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipHostRegister(base, (size_t)bytes, hipHostRegisterMapped));
+  void* dev = nullptr;
+  hipError_t e = hipHostGetDevicePointer(&dev, base, 0);
+  if (e != hipSuccess) {
+    (void)hipHostUnregister(base);
+    return fail(GA3C_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
+  }
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  m->reg_host = static_cast<const char*>(base);
+  m->reg_dev = static_cast<const char*>(dev);
+  m->reg_bytes = bytes;
+  return GA3C_OK;
+}
+
+inline int unregister_host(Core* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (!m->reg_host) return GA3C_OK;
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipHostUnregister((void*)m->reg_host));
+  m->reg_host = m->reg_dev = nullptr;
+  m->reg_bytes = 0;
+  return GA3C_OK;
+}
+
+// `src`: `name`'s rows of the workspace, `wd` floats each, as the network's own table found them
+inline int fetch(Core* m, const char* name, const float* src, int64_t wd, float* out, int64_t count) {
+  if (count != wd * m->last_B)
+    return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)(wd * m->last_B), (long long)count);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipMemcpy(out, src, sizeof(float) * count, hipMemcpyDeviceToHost));
+  return GA3C_OK;
+}
+
+// One zeroed device block cut into row buffers: *dst[i] gets B x widths[i] floats, rounded up to whole float4s; *end is the
+// four floats behind the last of them.
+inline int carve_rows(size_t B, const std::vector<size_t>& widths, const std::vector<float**>& dst, float** base, float** end) {
+  size_t total = 0;
+  for (size_t wd : widths) total += (B * wd + 3) / 4 * 4;
+  CHK(dalloc(base, total + 4));
+  HIPCHK(hipMemset(*base, 0, sizeof(float) * (total + 4)));
+  float* q = *base;
+  for (size_t i = 0; i < widths.size(); ++i) {
+    *dst[i] = q;
+    q += (B * widths[i] + 3) / 4 * 4;
+  }
+  *end = q;
+  return GA3C_OK;
+}
+
+// The stream, the zeroed arenas, the events and `lanes` lanes (0: four) of a Core whose sizes and outputs are filled.
+inline int alloc_core(Core* m, int lanes) {
+  const size_t B = (size_t)m->max_batch, S = m->S;
+  HIPCHK(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
+  for (int i = 0; i < m->narena; ++i) {
+    CHK(dalloc(&m->arena[i], (size_t)m->n));
+    HIPCHK(hipMemset(m->arena[i], 0, sizeof(float) * m->n));
+  }
+  HIPCHK(hipEventCreateWithFlags(&m->tev, hipEventDisableTiming));
+  HIPCHK(hipEventCreate(&m->t0));
+  HIPCHK(hipEventCreate(&m->t1));
+  m->lanes.resize((size_t)(lanes > 0 ? lanes : 4));
+  for (PLane& P : m->lanes) {
+    CHK(halloc(&P.h_off, B)); CHK(halloc(&P.h_x, B * S));
+    CHK(dalloc(&P.d_off, B)); CHK(dalloc(&P.d_x, B * S));
+    for (int wd : m->out_widths) {
+      P.out.push_back(Out{nullptr, nullptr, wd});
+      CHK(halloc(&P.out.back().h, B * wd));
+      CHK(dalloc(&P.out.back().d, B * wd));
+    }
+    HIPCHK(hipEventCreateWithFlags(&P.ev, hipEventDisableTiming));
+  }
+  return GA3C_OK;
+}
+
+// Waits for the stream, then frees what alloc_core made, however far it came.  The network's own buffers go after it.
+inline void free_core(Core* m) {
+  if (m->st) (void)hipStreamSynchronize(m->st);
+  for (PLane& P : m->lanes) {
+    (void)hipHostFree(P.h_off); (void)hipHostFree(P.h_x);
+    (void)hipFree(P.d_off); (void)hipFree(P.d_x);
+    for (Out& o : P.out) {
+      (void)hipHostFree(o.h);
+      (void)hipFree(o.d);
+    }
+    if (P.ev) (void)hipEventDestroy(P.ev);
+  }
+  for (float*& a : m->arena) (void)hipFree(a);
+  for (hipEvent_t e : {m->tev, m->t0, m->t1})
+    if (e) (void)hipEventDestroy(e);
+  if (m->reg_host) (void)hipHostUnregister((void*)m->reg_host);
+  if (m->st) (void)hipStreamDestroy(m->st);
+  (void)hipGetLastError();
+}
+
+// The checks of a config that come before the network's own: the sizes every layer table is built from.
+template <class C>
+int check_dims(const C& c, int max_s, int max_a, int max_b) {
+  if (c.state_dim < 1 || c.state_dim > max_s) return fail(GA3C_EINVAL, "state_dim %d outside [1,%d]", c.state_dim, max_s);
+  if (c.num_actions < 1 || c.num_actions > max_a) return fail(GA3C_EINVAL, "num_actions %d outside [1,%d]", c.num_actions, max_a);
+  if (c.max_batch < 1 || c.max_batch > max_b) return fail(GA3C_EINVAL, "max_batch %d outside [1,%d]", c.max_batch, max_b);
+  return GA3C_OK;
+}
+
+// ... and those that come after them; leaves the config's device current.
+template <class C>
+int check_device(const C& c) {
+  if (c.predict_lanes < 0 || c.predict_lanes > 64) return fail(GA3C_EINVAL, "predict_lanes %d outside [0,64]", c.predict_lanes);
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (c.device < 0 || c.device >= ndev) return fail(GA3C_EINVAL, "device %d not in [0,%d)", c.device, ndev);
+  HIPCHK(hipSetDevice(c.device));
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, c.device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(GA3C_ESTATE, "device %d is %s; this library is built for gfx950 only", c.device, prop.gcnArchName);
+  return GA3C_OK;
+}
+
+// ------------------------------------------------------------------ Net: the actor-critic layer (ga3c_mlp, ga3c_dmlp)
+
+const char* const CKPT_SUFFIX[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};   // a variable and its two slots, arenas 0..2
+
+struct Net : Core {               // arenas: theta, ms, mom, grad
+  int A = 0;
+  int ZW = 0;                     // logits per row
+  bool clip = false;
+  Opt opt{};                      // the arenas and the optimizer's constants; lr is the call's
+  // train staging: pinned host + device
+  float* h_x = nullptr; float* h_y = nullptr; float* h_a = nullptr; int64_t* h_off = nullptr; float* h_loss = nullptr;
+  float* d_x = nullptr; float* d_y = nullptr; float* d_a = nullptr; int64_t* d_off = nullptr;
+  int res_B = 0;                  // rows uploaded for the resident path
 
   // the w [in, out] at arena element `off` and the b [out] behind it: one dense layer's variables, TF creation order
   void add_dense(const std::string& w_name, const std::string& b_name, int64_t off, int in, int out) {
-    vars.push_back(Var{w_name, off, (int64_t)in * out, 2, {in, out}});
-    vars.push_back(Var{b_name, off + (int64_t)in * out, out, 1, {out, 0}});
+    vars.push_back(Var{w_name, off, (int64_t)in * out, 2, {in, out}, {}});
+    vars.push_back(Var{b_name, off + (int64_t)in * out, out, 1, {out, 0}, {}});
+    for (Var* var : {&vars[vars.size() - 2], &vars.back()})
+      for (int w = 0; w < 3; ++w) var->ckpt.emplace_back(var->name + CKPT_SUFFIX[w], w);
     n = off + (int64_t)in * out + out;
   }
 };
@@ -138,27 +562,11 @@ inline Opt make_opt(const Net* m, float lr) {
   return o;
 }
 
-inline int check_batch(const Net* m, int B) {
-  if (B < 1 || B > m->max_batch) return fail(GA3C_EINVAL, "batch %d outside [1,%d]", B, m->max_batch);
-  return GA3C_OK;
-}
-
-// offsets of rows in the registered segment: each must hold S whole floats inside it
-inline int check_offsets(const Net* m, const int64_t* off, int B) {
-  if (!m->reg_dev) return fail(GA3C_ESTATE, "no host segment registered");
-  const int64_t row = 4 * (int64_t)m->S;
-  for (int i = 0; i < B; ++i)
-    if (off[i] < 0 || off[i] % 4 != 0 || off[i] > m->reg_bytes - row)
-      return fail(GA3C_EINVAL, "offset %lld of row %d is not a 4-byte aligned row of %lld bytes inside the %lld-byte segment",
-                  (long long)off[i], i, (long long)row, (long long)m->reg_bytes);
-  return GA3C_OK;
-}
-
 // Stages y_r / a and the states (x: host rows, or offsets into the registered segment) of a train-type call; caller holds
 // train_mu.  Returns the Input the row kernel reads.
 inline int stage_train(Net* m, const float* x, const int64_t* off, const float* y, const float* a, int B, Input* in) {
   const int S = m->S, A = m->A;
-  if (off) CHK(check_offsets(m, off, B));
+  if (off) CHK(check_offsets(m, off, B, S));
   memcpy(m->h_y, y, sizeof(float) * B);
   memcpy(m->h_a, a, sizeof(float) * B * A);
   HIPCHK(hipMemcpyAsync(m->d_y, m->h_y, sizeof(float) * B, hipMemcpyHostToDevice, m->st));
@@ -276,89 +684,21 @@ int evaluate(N* m, const float* x, const int64_t* offsets, const float* y, const
   return GA3C_OK;
 }
 
-inline PLane* take_lane(Net* m, std::unique_lock<std::mutex>& lk, int* ticket) {
-  for (;;) {
-    for (size_t i = 0; i < m->lanes.size(); ++i)
-      if (!m->lanes[i].busy) {
-        m->lanes[i].busy = true;
-        *ticket = (int)i;
-        return &m->lanes[i];
-      }
-    m->lane_cv.wait(lk);
-  }
-}
-
-inline void give_lane(Net* m, PLane* P) {
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    P->busy = false;
-  }
-  m->lane_cv.notify_one();
-}
-
-// Enqueues one prediction on a lane of its own (x: host rows; off: rows of the registered segment).
+// A lane's outputs are p, v, z.
 template <class N>
 int predict_begin(N* m, const float* x, const int64_t* off, int B, int* ticket) {
-  CHK(check_batch(m, B));
-  HIPCHK(hipSetDevice(m->device));
-  if (off) {
-    CHK(check_offsets(m, off, B));
-  }
-  std::unique_lock<std::mutex> lk(m->mu);
-  PLane* P = take_lane(m, lk, ticket);
-  const int S = m->S, A = m->A;
-  Input in;
-  hipError_t e = hipSuccess;
-  if (off) {
-    memcpy(P->h_off, off, sizeof(int64_t) * B);
-    e = hipMemcpyAsync(P->d_off, P->h_off, sizeof(int64_t) * B, hipMemcpyHostToDevice, m->st);
-    in = Input{m->reg_dev, P->d_off, 0};
-  } else {
-    memcpy(P->h_x, x, sizeof(float) * B * S);
-    e = hipMemcpyAsync(P->d_x, P->h_x, sizeof(float) * B * S, hipMemcpyHostToDevice, m->st);
-    in = Input{reinterpret_cast<const char*>(P->d_x), nullptr, 4 * (int64_t)S};
-  }
-  if (e == hipSuccess) {
-    m->rows(PREDICT, in, B, 0.f, P->d_p, P->d_v, P->d_z);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(P->h_p, P->d_p, sizeof(float) * B * A, hipMemcpyDeviceToHost, m->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(P->h_v, P->d_v, sizeof(float) * B, hipMemcpyDeviceToHost, m->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(P->h_z, P->d_z, sizeof(float) * B * m->ZW, hipMemcpyDeviceToHost, m->st);
-  if (e == hipSuccess) e = hipEventRecord(P->ev, m->st);
-  if (e != hipSuccess) {
-    P->busy = false;
-    lk.unlock();
-    m->lane_cv.notify_one();
-    (void)hipGetLastError();
-    return fail(GA3C_EHIP, "prediction enqueue failed: %s", hipGetErrorString(e));
-  }
-  P->B = B;
-  return GA3C_OK;
+  CHK(predict_check(m, off, B));
+  return predict_begin(m, x, off, B, ticket,
+                       [m, B](const Input& in, PLane& P) { m->rows(PREDICT, in, B, 0.f, P.out[0].d, P.out[1].d, P.out[2].d); });
 }
 
 inline int predict_end(Net* m, int ticket, int B, float* p, float* v, float* z) {
-  if (ticket < 0 || ticket >= (int)m->lanes.size()) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
-  PLane* P = &m->lanes[ticket];
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!P->busy) return fail(GA3C_ESTATE, "no prediction begun under ticket %d", ticket);
-  }
-  const hipError_t e = hipEventSynchronize(P->ev);     // the lane's staging is free for the next begin only after this
-  if (e == hipSuccess && B != P->B) {
-    give_lane(m, P);
-    return fail(GA3C_EINVAL, "batch %d, begun with %d", B, P->B);
-  }
-  if (e == hipSuccess) {
-    if (p) memcpy(p, P->h_p, sizeof(float) * B * m->A);
-    if (v) memcpy(v, P->h_v, sizeof(float) * B);
-    if (z) memcpy(z, P->h_z, sizeof(float) * B * m->ZW);
-  }
+  PLane* P;
+  CHK(predict_end(m, ticket, B, &P));
+  float* const dst[3] = {p, v, z};
+  for (int i = 0; i < 3; ++i)
+    if (dst[i]) memcpy(dst[i], P->out[i].h, sizeof(float) * B * P->out[i].width);
   give_lane(m, P);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(GA3C_EHIP, "prediction failed: %s", hipGetErrorString(e));
-  }
   return GA3C_OK;
 }
 
@@ -387,183 +727,6 @@ int predict_gather(N* m, const int64_t* offsets, int B, int32_t u8, float* p, fl
 inline int predict_gather_end(Net* m, int ticket, int B, float* p, float* v) {
   if (!m || !p || !v) return fail(GA3C_EINVAL, "null argument");
   return predict_end(m, ticket, B, p, v, nullptr);
-}
-
-inline int param_index(const Net* m, const char* name) {
-  if (!name) return -1;
-  std::string s(name);
-  if (s.size() > 2 && s.compare(s.size() - 2, 2, ":0") == 0) s.resize(s.size() - 2);
-  for (size_t i = 0; i < m->vars.size(); ++i)
-    if (s == m->vars[i].name) return (int)i;
-  return -1;
-}
-
-inline int arena_copy(Net* m, int which, int64_t off, int64_t count, float* out, const float* in) {
-  if (which < 0 || which > 3 || (in && which > 2)) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, in ? 2 : 3);
-  HIPCHK(hipSetDevice(m->device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  if (out) HIPCHK(hipMemcpy(out, m->arena[which] + off, sizeof(float) * count, hipMemcpyDeviceToHost));
-  else HIPCHK(hipMemcpy(m->arena[which] + off, in, sizeof(float) * count, hipMemcpyHostToDevice));
-  return GA3C_OK;
-}
-
-inline int param_count(Net* m, int64_t* count) {
-  if (!m || !count) return fail(GA3C_EINVAL, "null argument");
-  *count = m->n;
-  return GA3C_OK;
-}
-
-inline int get_arena(Net* m, int32_t which, float* out, int64_t count) {
-  if (!m || !out) return fail(GA3C_EINVAL, "null argument");
-  if (count != m->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)m->n);
-  return arena_copy(m, which, 0, count, out, nullptr);
-}
-
-inline int set_arena(Net* m, int32_t which, const float* in, int64_t count) {
-  if (!m || !in) return fail(GA3C_EINVAL, "null argument");
-  if (count != m->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)m->n);
-  return arena_copy(m, which, 0, count, nullptr, in);
-}
-
-inline int get_step(Net* m, int64_t* step) {
-  if (!m || !step) return fail(GA3C_EINVAL, "null argument");
-  *step = m->step.load();
-  return GA3C_OK;
-}
-
-inline int set_step(Net* m, int64_t step) {
-  if (!m) return fail(GA3C_EINVAL, "null argument");
-  m->step.store(step);
-  return GA3C_OK;
-}
-
-inline int32_t num_params(Net* m) { return m ? (int32_t)m->vars.size() : 0; }
-
-inline const char* param_name(Net* m, int32_t index) {
-  return (m && index >= 0 && index < (int32_t)m->vars.size()) ? m->vars[index].name.c_str() : nullptr;
-}
-
-inline int param_info(Net* m, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]) {
-  if (!m || !name) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(m, name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  const Var& var = m->vars[i];
-  if (offset) *offset = var.off;
-  if (count) *count = var.count;
-  if (ndim) *ndim = var.ndim;
-  const int64_t sh[4] = {var.shape[0], var.shape[1], 0, 0};
-  if (shape) memcpy(shape, sh, sizeof sh);
-  return GA3C_OK;
-}
-
-// get_param (out) / set_param (in)
-inline int param_copy(Net* m, const char* name, int32_t which, float* out, const float* in, int64_t count) {
-  if (!m || !name || (!out && !in)) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(m, name);
-  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
-  const Var& var = m->vars[i];
-  if (count != var.count) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)var.count, (long long)count);
-  return arena_copy(m, which, var.off, count, out, in);
-}
-
-const char* const CKPT_SUFFIX[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};   // a variable and its two slots, arenas 0..2
-
-inline int save(Net* m, const char* path) {
-  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
-  std::vector<float> arena[3];
-  for (int w = 0; w < 3; ++w) {
-    arena[w].resize((size_t)m->n);
-    CHK(get_arena(m, w, arena[w].data(), m->n));
-  }
-  std::vector<ga3c_ckpt::Member> members;
-  ga3c_ckpt::Member st;
-  st.name = "step";
-  st.descr = "<i8";
-  const int64_t step = m->step.load();
-  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
-  members.push_back(st);
-  for (const Var& var : m->vars)
-    for (int w = 0; w < 3; ++w) {
-      ga3c_ckpt::Member mb;
-      mb.name = var.name + CKPT_SUFFIX[w];
-      mb.descr = "<f4";
-      mb.shape.assign(var.shape, var.shape + var.ndim);
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[w].data() + var.off);
-      mb.bytes.assign(src, src + (size_t)var.count * sizeof(float));
-      members.push_back(std::move(mb));
-    }
-  std::string err;
-  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  return GA3C_OK;
-}
-
-// `members`: the file, read already.  A file of another network kind lacks this one's first variable: refused, as is any
-// member of another shape, before anything is written.
-inline int load(Net* m, const char* path, const std::map<std::string, ga3c_ckpt::Member>& members) {
-  std::vector<float> arena[3];
-  for (int w = 0; w < 3; ++w) arena[w].resize((size_t)m->n);
-  for (const Var& var : m->vars)
-    for (int w = 0; w < 3; ++w) {
-      const std::string key = var.name + CKPT_SUFFIX[w];
-      auto it = members.find(key);
-      if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s: not a checkpoint of this %s", path, key.c_str(), m->kind);
-      const ga3c_ckpt::Member& mb = it->second;
-      const bool shape_ok = mb.shape.size() == (size_t)var.ndim && std::equal(mb.shape.begin(), mb.shape.end(), var.shape);
-      if (mb.descr != "<f4" || !shape_ok || mb.bytes.size() != (size_t)var.count * sizeof(float))
-        return fail(GA3C_ESTATE, "%s: %s is not <f4 of this network's shape (%lld elements)", path, key.c_str(),
-                    (long long)var.count);
-      memcpy(arena[w].data() + var.off, mb.bytes.data(), mb.bytes.size());
-    }
-  auto st = members.find("step");
-  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
-    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
-  int64_t step = 0;
-  memcpy(&step, st->second.bytes.data(), 8);
-  for (int w = 0; w < 3; ++w) CHK(set_arena(m, w, arena[w].data(), m->n));
-  m->step.store(step);
-  return GA3C_OK;
-}
-
-inline int load(Net* m, const char* path) {
-  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
-  std::map<std::string, ga3c_ckpt::Member> members;
-  std::string err;
-  if (!ga3c_ckpt::read_npz(path, &members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  return load(m, path, members);
-}
-
-inline int register_host(Net* m, void* base, int64_t bytes) {
-  if (!m || !base || bytes < 16) return fail(GA3C_EINVAL, "bad argument");
-  if (m->reg_host) return fail(GA3C_ESTATE, "a host segment is already registered");
-  HIPCHK(hipSetDevice(m->device));
-  HIPCHK(hipHostRegister(base, (size_t)bytes, hipHostRegisterMapped));
-  void* dev = nullptr;
-  hipError_t e = hipHostGetDevicePointer(&dev, base, 0);
-  if (e != hipSuccess) {
-    (void)hipHostUnregister(base);
-    return fail(GA3C_EHIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
-  }
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  m->reg_host = static_cast<const char*>(base);
-  m->reg_dev = static_cast<const char*>(dev);
-  m->reg_bytes = bytes;
-  return GA3C_OK;
-}
-
-inline int unregister_host(Net* m) {
-  if (!m) return fail(GA3C_EINVAL, "null argument");
-  if (!m->reg_host) return GA3C_OK;
-  HIPCHK(hipSetDevice(m->device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  HIPCHK(hipHostUnregister((void*)m->reg_host));
-  m->reg_host = m->reg_dev = nullptr;
-  m->reg_bytes = 0;
-  return GA3C_OK;
 }
 
 inline int upload(Net* m, const float* x, const float* y, const float* a, int B) {
@@ -603,63 +766,20 @@ int time_resident(N* m, int32_t mode, int B, int iters, float lr, float beta, fl
   return GA3C_OK;
 }
 
-// `src`: `name`'s rows of the workspace, `wd` floats each, as the network's own work_ptr found them
-inline int fetch(Net* m, const char* name, const float* src, int64_t wd, float* out, int64_t count) {
-  if (count != wd * m->last_B)
-    return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)(wd * m->last_B), (long long)count);
-  HIPCHK(hipSetDevice(m->device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  std::lock_guard<std::mutex> lk(m->mu);
-  HIPCHK(hipStreamSynchronize(m->st));
-  HIPCHK(hipMemcpy(out, src, sizeof(float) * count, hipMemcpyDeviceToHost));
-  return GA3C_OK;
-}
-
-// One zeroed device block cut into row buffers: *dst[i] gets B x widths[i] floats, rounded up to whole float4s; *end is the
-// four floats behind the last of them.
-inline int carve_rows(size_t B, const std::vector<size_t>& widths, const std::vector<float**>& dst, float** base, float** end) {
-  size_t total = 0;
-  for (size_t wd : widths) total += (B * wd + 3) / 4 * 4;
-  CHK(dalloc(base, total + 4));
-  HIPCHK(hipMemset(*base, 0, sizeof(float) * (total + 4)));
-  float* q = *base;
-  for (size_t i = 0; i < widths.size(); ++i) {
-    *dst[i] = q;
-    q += (B * widths[i] + 3) / 4 * 4;
-  }
-  *end = q;
-  return GA3C_OK;
-}
-
 template <class N>
 void free_all(N* m) {
-  if (m->st) (void)hipStreamSynchronize(m->st);
-  for (PLane& P : m->lanes) {
-    (void)hipHostFree(P.h_off); (void)hipHostFree(P.h_x); (void)hipHostFree(P.h_p); (void)hipHostFree(P.h_v);
-    (void)hipHostFree(P.h_z);
-    (void)hipFree(P.d_off); (void)hipFree(P.d_x); (void)hipFree(P.d_p); (void)hipFree(P.d_v); (void)hipFree(P.d_z);
-    if (P.ev) (void)hipEventDestroy(P.ev);
-  }
-  for (float*& a : m->arena) (void)hipFree(a);
+  free_core(m);
   m->free_work();
   (void)hipHostFree(m->h_x); (void)hipHostFree(m->h_y); (void)hipHostFree(m->h_a); (void)hipHostFree(m->h_off);
   (void)hipHostFree(m->h_loss);
   (void)hipFree(m->d_x); (void)hipFree(m->d_y); (void)hipFree(m->d_a); (void)hipFree(m->d_off);
-  for (hipEvent_t e : {m->tev, m->t0, m->t1})
-    if (e) (void)hipEventDestroy(e);
-  if (m->reg_host) (void)hipHostUnregister((void*)m->reg_host);
-  if (m->st) (void)hipStreamDestroy(m->st);
   (void)hipGetLastError();
 }
 
 template <class N>
 int alloc_all(N* m) {
-  const size_t B = (size_t)m->max_batch, S = m->S, A = m->A, ZW = m->ZW;
-  HIPCHK(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
-  for (int i = 0; i < 4; ++i) {
-    CHK(dalloc(&m->arena[i], (size_t)m->n));
-    HIPCHK(hipMemset(m->arena[i], 0, sizeof(float) * m->n));
-  }
+  const size_t B = (size_t)m->max_batch, S = m->S, A = m->A;
+  CHK(alloc_core(m, m->cfg.predict_lanes));
   std::vector<float> ones((size_t)m->n, 1.0f);     // the RMSProp ms slot starts at 1 (TF-1 RMSPropOptimizer)
   HIPCHK(hipMemcpy(m->arena[1], ones.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
   m->opt.theta = m->arena[0]; m->opt.ms = m->arena[1]; m->opt.mom = m->arena[2]; m->opt.grad = m->arena[3];
@@ -667,41 +787,6 @@ int alloc_all(N* m) {
   CHK(halloc(&m->h_x, B * S)); CHK(halloc(&m->h_y, B)); CHK(halloc(&m->h_a, B * A)); CHK(halloc(&m->h_off, B));
   CHK(halloc(&m->h_loss, 4));
   CHK(dalloc(&m->d_x, B * S)); CHK(dalloc(&m->d_y, B)); CHK(dalloc(&m->d_a, B * A)); CHK(dalloc(&m->d_off, B));
-  HIPCHK(hipEventCreateWithFlags(&m->tev, hipEventDisableTiming));
-  HIPCHK(hipEventCreate(&m->t0));
-  HIPCHK(hipEventCreate(&m->t1));
-  m->lanes.resize((size_t)(m->cfg.predict_lanes > 0 ? m->cfg.predict_lanes : 4));
-  for (PLane& P : m->lanes) {
-    CHK(halloc(&P.h_off, B)); CHK(halloc(&P.h_x, B * S)); CHK(halloc(&P.h_p, B * A)); CHK(halloc(&P.h_v, B));
-    CHK(halloc(&P.h_z, B * ZW));
-    CHK(dalloc(&P.d_off, B)); CHK(dalloc(&P.d_x, B * S)); CHK(dalloc(&P.d_p, B * A)); CHK(dalloc(&P.d_v, B));
-    CHK(dalloc(&P.d_z, B * ZW));
-    HIPCHK(hipEventCreateWithFlags(&P.ev, hipEventDisableTiming));
-  }
-  return GA3C_OK;
-}
-
-// The checks of a config that come before the network's own: the sizes every layer table is built from.
-template <class C>
-int check_dims(const C& c, int max_s, int max_a) {
-  if (c.state_dim < 1 || c.state_dim > max_s) return fail(GA3C_EINVAL, "state_dim %d outside [1,%d]", c.state_dim, max_s);
-  if (c.num_actions < 1 || c.num_actions > max_a) return fail(GA3C_EINVAL, "num_actions %d outside [1,%d]", c.num_actions, max_a);
-  if (c.max_batch < 1 || c.max_batch > 65536) return fail(GA3C_EINVAL, "max_batch %d outside [1,65536]", c.max_batch);
-  return GA3C_OK;
-}
-
-// ... and those that come after them; leaves the config's device current.
-template <class C>
-int check_device(const C& c) {
-  if (c.predict_lanes < 0 || c.predict_lanes > 64) return fail(GA3C_EINVAL, "predict_lanes %d outside [0,64]", c.predict_lanes);
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (c.device < 0 || c.device >= ndev) return fail(GA3C_EINVAL, "device %d not in [0,%d)", c.device, ndev);
-  HIPCHK(hipSetDevice(c.device));
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, c.device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(GA3C_ESTATE, "device %d is %s; this library is built for gfx950 only", c.device, prop.gcnArchName);
   return GA3C_OK;
 }
 
@@ -713,6 +798,9 @@ int create(N* m, N** out) {
   m->A = c.num_actions;
   m->max_batch = c.max_batch;
   m->device = c.device;
+  m->out_widths = {m->A, 1, m->ZW};
+  m->narena = 4;
+  m->nwritable = 3;
   m->clip = (c.flags & GA3C_FLAG_GRAD_CLIP) != 0;
   m->opt.omr = 1.0f - c.rmsprop_decay;
   m->opt.mu = c.rmsprop_momentum;
