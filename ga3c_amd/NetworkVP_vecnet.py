@@ -7,8 +7,8 @@ Same interface as NetworkVP.Network where Server, ThreadPredictor and ThreadTrai
 save, load, get_global_step, get_variables_names, get_variable_value, and the zero-copy entries).  There is no frame
 front-end, no state cache and no data-parallel or Hogwild training: Server refuses those settings with these networks.
 
-A subclass states PREFIX, LOGITS_PER_ACTION, ACTIVATION_WIDTHS / ACTIVATION_TAGS (or its own evaluate), DUAL_RMSPROP_REFUSAL,
-_config() and _variables().
+A subclass states PREFIX, LOGITS_PER_ACTION, ACTIVATION_WIDTHS / ACTIVATION_TAGS (or its own evaluate), DUAL_RMSPROP_REFUSAL
+(None where its handle takes the flag), _config() and _variables().
 """
 import ctypes as C
 import glob
@@ -127,7 +127,7 @@ class VectorNetwork(NativeHandle):
         self.S = int(self.state_dim[0])
         self.learning_rate = Config.LEARNING_RATE_START
         self.beta = Config.BETA_START
-        if Config.DUAL_RMSPROP:
+        if Config.DUAL_RMSPROP and self.DUAL_RMSPROP_REFUSAL:
             raise ValueError(self.DUAL_RMSPROP_REFUSAL)
         if max_batch is None:
             max_batch = max(Config.PREDICTION_BATCH_SIZE,
@@ -162,7 +162,8 @@ class VectorNetwork(NativeHandle):
         self._log_lock = threading.Lock()
         self.last_losses = None
 
-    # ---- arenas: 0 weights, 1 / 2 RMSProp `ms` / `mom`, 3 last gradient -------------------------
+    # ---- arenas: 0 weights, 1 / 2 RMSProp `ms` / `mom`, 3 last gradient; with Config.DUAL_RMSPROP (where the network takes
+    # it) these are cost_p's optimizer and 4 / 5 / 6 the value optimizer's `ms` / `mom` and the last cost_v gradient ------
     def get_arena(self, which):
         out = np.empty(self.param_count, dtype=np.float32)
         self._call("get_arena", which, nat.ptr(out), out.size)

@@ -44,11 +44,12 @@ class Network(VectorNetwork):
     LOGITS_PER_ACTION = 2         # z = [hx | hy]
     ACTIVATION_WIDTHS = (4, 256, 64)                                              # pd1, pd2, d1
     ACTIVATION_TAGS = ("activation_pd1", "activation_pd2", "activation_d2")      # NetworkVP.py:150-170
-    DUAL_RMSPROP_REFUSAL = "DUAL_RMSPROP with the continuous head is not supported"
+    DUAL_RMSPROP_REFUSAL = None   # Config.DUAL_RMSPROP: one optimizer per cost, arenas 4 / 5 / 6
 
     def _config(self):
         cfg = nat.MlpConfig()
-        cfg.flags = nat.FLAG_CONTINUOUS | (nat.FLAG_GRAD_CLIP if Config.USE_GRAD_CLIP else 0)
+        cfg.flags = nat.FLAG_CONTINUOUS | (nat.FLAG_GRAD_CLIP if Config.USE_GRAD_CLIP else 0) | \
+            (nat.FLAG_DUAL_RMSPROP if Config.DUAL_RMSPROP else 0)
         return cfg
 
     def _variables(self):

@@ -901,7 +901,7 @@ int ga3c_ddpg_create(const ga3c_ddpg_config* cfg, ga3c_ddpg** out) {
   m->max_batch = cfg->max_batch;
   m->out_widths = {cfg->num_actions};
   m->narena = 5;
-  m->nwritable = 4;
+  m->writable = {0, 1, 2, 3};
   m->L = make_layout(cfg->state_dim, cfg->num_actions);
   fill_vars(m);
   m->rowf = 2 * cfg->state_dim + cfg->num_actions + 2;

@@ -15,6 +15,13 @@
 //                             The extra work of the last thread of block 0: the three loss sums, in row order.
 //   mlp_update_kernel<CLIP>   one block per variable: tf.clip_by_average_norm's norm (fixed-order tree), then RMSProp.
 // A train step is 2 launches without USE_GRAD_CLIP and 3 with it; a prediction is 1.
+//
+// GA3C_FLAG_DUAL_RMSPROP (one RMSProp optimizer per cost) swaps the three train kernels, launch for launch:
+//   mlp_tile_kernel             TRAIN's forward, loss rows, dv and dz, then the trunk backward twice on the same weights:
+//   <TRAIN_DUAL, WorkDual>      from (dv = 0, dz) into Work::del (cost_p) and from (dv, dz = 0) into WorkDual::del_v (cost_v).
+//   mlp_wgrad_dual_kernel<FUSED>  both costs' sums per arena element, the layer input read once per row; arenas 3 and 6;
+//                               FUSED: the value step, then the policy step, each only where its optimizer has a slot.
+//   mlp_update_dual_kernel<CLIP>  one block per variable: both norms, tf.clip_by_norm each, the value step, the policy step.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,6 +43,7 @@ constexpr int THREADS = 256;
 constexpr int MAX_S = 64;
 constexpr int MAX_A = 32;
 constexpr float PI_F = 3.14159265358979f;
+constexpr int TRAIN_DUAL = 3;             // a row-kernel mode of this file: TRAIN with one trunk backward per cost
 
 // The layer table.  Trunk layers 0..4 (reference dense_layer calls, NetworkVP.py:78-85), then the three heads, each of
 // which reads the last trunk layer: logits_v (linear) and logits_p/out_x, out_y (sigmoid, then the angle).
@@ -95,6 +103,10 @@ struct Work {
   float* dz;           // [B,2A] = [dhx | dhy]
   float* lossrow;      // [B,3]
   float* losses;       // [3]
+};
+
+struct WorkDual : Work {       // DUAL_RMSPROP: del holds the policy cost's deltas, del_v the value cost's
+  float* del_v[NTRUNK];
 };
 
 __device__ __forceinline__ float sigm(float h) { return 1.0f / (1.0f + expf(-h)); }
@@ -179,10 +191,12 @@ __device__ void dense_bwd(WF W, int K, int N, const float* gout, const float* ac
 }
 
 // One 16-row tile: forward (all modes), loss rows (EVAL, TRAIN), deltas (TRAIN).  Outputs p[B,A], v[B], z[B,2A] always.
-template <int MODE>
+// TRAIN_DUAL: the head deltas stay in zh (its logits are in HBM by then) and the trunk backward runs once per cost from
+// them, reusing the same LDS buffers: the policy stream to w.del, the value stream to w.del_v (W = WorkDual).
+template <int MODE, class W = Work>
 __global__ __launch_bounds__(THREADS) void mlp_tile_kernel(Layout L, const float* __restrict__ theta, Input in,
                                                            const float* __restrict__ y, const float* __restrict__ a, int B,
-                                                           float beta, Work w, float* __restrict__ p_out,
+                                                           float beta, W w, float* __restrict__ p_out,
                                                            float* __restrict__ v_out, float* __restrict__ z_out) {
   // LDS, [width][16] each (51.8 KB).  xin also holds the d1 delta, bufB the head deltas and then the dense14_p delta.
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
@@ -196,6 +210,7 @@ __global__ __launch_bounds__(THREADS) void mlp_tile_kernel(Layout L, const float
   const int S = L.S, A = L.A, NH = 1 + 2 * A;
   const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
   constexpr bool KEEP = MODE != PREDICT;
+  constexpr bool DELTAS = MODE == TRAIN || MODE == TRAIN_DUAL;
 
   for (int e = threadIdx.x; e < S * TILE; e += THREADS) {
     const int r = e / S, s = e % S;
@@ -242,7 +257,9 @@ __global__ __launch_bounds__(THREADS) void mlp_tile_kernel(Layout L, const float
   __syncthreads();
 
   // per row: the angle output, the loss terms and the head deltas (Atan2Grad / pi, then the sigmoids)
-  float* gz = bufB;                 // [1 + 2A][16]: dv, dhx, dhy (bufB's activations are in HBM already)
+  // [1 + 2A][16]: dv, dhx, dhy (bufB's activations are in HBM already).  TRAIN_DUAL: in place of the logits, which each
+  // thread below has read for its row before it writes that row's deltas.
+  float* gz = MODE == TRAIN_DUAL ? zh : bufB;
   if (threadIdx.x < TILE) {
     const int r = threadIdx.x;
     const bool ok = r < nrows;
@@ -265,7 +282,7 @@ __global__ __launch_bounds__(THREADS) void mlp_tile_kernel(Layout L, const float
         const float aa = ok ? a[(size_t)row * A + i] : 0.f;
         c1 += pc * aa;
         c2 += pc * pc;
-        if (MODE == TRAIN) {
+        if (DELTAS) {
           const float g = -aa * adv + 2.0f * beta * pc;
           const float gr = g / (PI_F * (X * X + Y * Y));
           const float dhx = ok ? -Y * gr * (sx * (1.0f - sx)) : 0.f;
@@ -285,30 +302,51 @@ __global__ __launch_bounds__(THREADS) void mlp_tile_kernel(Layout L, const float
       w.lossrow[(size_t)row * 3 + 1] = -beta * c2;
       w.lossrow[(size_t)row * 3 + 2] = 0.5f * (yy - v) * (yy - v);
     }
-    if (MODE == TRAIN) {
+    if (DELTAS) {
       const float dv = ok ? v - yy : 0.f;
       gz[r] = dv;
       if (ok) w.dv[row] = dv;
     }
   }
   __syncthreads();
-  if (MODE != TRAIN) return;
+  if (!DELTAS) return;
 
   // backward through the trunk; rows >= nrows carry zero deltas
   float* g5 = xin;                  // [64][16]
   float* g4 = bufB + NH * TILE;     // [100][16], behind the head deltas
   const float* th = theta;
   const int64_t ov = L.off[10], ox = L.off[12], oy = L.off[14];
-  dense_bwd<SIG>([=](int k, int j) { return j == 0 ? th[ov + k] : (j <= A ? th[ox + k * A + j - 1] : th[oy + k * A + j - 1 - A]); },
-                 HID, NH, gz, d1, g5, w.del[4], row0, nrows, bufA);
   const float* W4 = theta + L.off[8];
-  dense_bwd<SIG>([=](int k, int j) { return W4[k * HID + j]; }, 100, HID, g5, a4, g4, w.del[3], row0, nrows, bufA);
   const float* W3 = theta + L.off[6];
-  dense_bwd<LIN>([=](int k, int j) { return W3[k * 100 + j]; }, 256, 100, g4, nullptr, bufA, w.del[2], row0, nrows, nullptr);
   const float* W2 = theta + L.off[4];
-  dense_bwd<LIN>([=](int k, int j) { return W2[k * 256 + j]; }, 256, 256, bufA, nullptr, bufB, w.del[1], row0, nrows, nullptr);
   const float* W1 = theta + L.off[2];
-  dense_bwd<LIN>([=](int k, int j) { return W1[k * 256 + j]; }, 4, 256, bufB, nullptr, nullptr, w.del[0], row0, nrows, bufA);
+  if constexpr (MODE == TRAIN) {
+    dense_bwd<SIG>([=](int k, int j) { return j == 0 ? th[ov + k] : (j <= A ? th[ox + k * A + j - 1] : th[oy + k * A + j - 1 - A]); },
+                   HID, NH, gz, d1, g5, w.del[4], row0, nrows, bufA);
+    dense_bwd<SIG>([=](int k, int j) { return W4[k * HID + j]; }, 100, HID, g5, a4, g4, w.del[3], row0, nrows, bufA);
+    dense_bwd<LIN>([=](int k, int j) { return W3[k * 100 + j]; }, 256, 100, g4, nullptr, bufA, w.del[2], row0, nrows, nullptr);
+    dense_bwd<LIN>([=](int k, int j) { return W2[k * 256 + j]; }, 256, 256, bufA, nullptr, bufB, w.del[1], row0, nrows, nullptr);
+    dense_bwd<LIN>([=](int k, int j) { return W1[k * 256 + j]; }, 4, 256, bufB, nullptr, nullptr, w.del[0], row0, nrows, bufA);
+  } else if constexpr (MODE == TRAIN_DUAL) {
+    // One pass per cost, the chain above each time (TRAIN's stays written out: routed through this lambda it compiles to
+    // other code than it had).  The backward is linear in the head deltas, so a stream is that chain started from the deltas
+    // with the other cost's rows zeroed: cost_p from (0, dhx, dhy), then cost_v from (dv, 0, 0).  zh keeps the deltas; bufB,
+    // which a pass overwrites, holds the stream's copy.
+    auto chain = [&](float* const* del) {
+      dense_bwd<SIG>([=](int k, int j) { return j == 0 ? th[ov + k] : (j <= A ? th[ox + k * A + j - 1] : th[oy + k * A + j - 1 - A]); },
+                     HID, NH, bufB, d1, g5, del[4], row0, nrows, bufA);
+      dense_bwd<SIG>([=](int k, int j) { return W4[k * HID + j]; }, 100, HID, g5, a4, g4, del[3], row0, nrows, bufA);
+      dense_bwd<LIN>([=](int k, int j) { return W3[k * 100 + j]; }, 256, 100, g4, nullptr, bufA, del[2], row0, nrows, nullptr);
+      dense_bwd<LIN>([=](int k, int j) { return W2[k * 256 + j]; }, 256, 256, bufA, nullptr, bufB, del[1], row0, nrows, nullptr);
+      dense_bwd<LIN>([=](int k, int j) { return W1[k * 256 + j]; }, 4, 256, bufB, nullptr, nullptr, del[0], row0, nrows, bufA);
+    };
+    for (int e = threadIdx.x; e < NH * TILE; e += THREADS) bufB[e] = e < TILE ? 0.f : zh[e];
+    __syncthreads();
+    chain(w.del);
+    for (int e = threadIdx.x; e < NH * TILE; e += THREADS) bufB[e] = e < TILE ? zh[e] : 0.f;
+    __syncthreads();
+    chain(w.del_v);
+  }
 }
 
 // Where the weight gradient of each layer comes from: its input rows (ld K) and its output deltas (ld, column offset).
@@ -385,6 +423,123 @@ __global__ __launch_bounds__(THREADS) void mlp_update_kernel(Layout L, Opt o) {
   }
 }
 
+// ------------------------------------------------------------------ two optimizers (GA3C_FLAG_DUAL_RMSPROP)
+
+// Which costs reach variable v: cost_p has no path to logits_v/* (tf.stop_gradient), cost_v none to logits_p/*; TF-1 gives
+// an optimizer no slot for a variable without a gradient, so that optimizer neither decays nor applies anything there.
+__device__ __forceinline__ bool has_p(int v) { return v != 10 && v != 11; }
+__device__ __forceinline__ bool has_v(int v) { return v < 12; }
+
+struct GradSrc2 {              // GradSrc with the deltas of both costs; a head has those of its own cost in both
+  GradSrc p;
+  const float* dv[NLAYERS];
+};
+
+// One thread per arena element: g_p into op.grad (arena 3) and g_v into ov.grad (arena 6), each the sum over the rows in
+// row order, exactly 0 where the cost has no path.  On the trunk the two chains share the row's input and are independent.
+// A head element takes mlp_wgrad_kernel's loop as it is: the same products in the same order under its own cost.
+// FUSED: the value optimizer's step, then the policy optimizer's, theta' = (theta - D_v) - D_p.
+template <bool FUSED>
+__global__ __launch_bounds__(THREADS) void mlp_wgrad_dual_kernel(Layout L, GradSrc2 src, int B, Opt op, Opt ov, Work w) {
+  const int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (e < L.off[NVARS]) {
+    int v = NVARS - 1;
+    while (e < L.off[v]) --v;
+    const int l = v / 2, N = L.out[l], K = L.in[l];
+    const bool hp = has_p(v), hv = has_v(v);
+    const int ld = src.p.d_ld[l];
+    float gp = 0.f, gv = 0.f;
+    if (hp && hv) {
+      const float* __restrict__ dp = src.p.d[l];
+      const float* __restrict__ dq = src.dv[l];
+      if (v & 1) {
+        const int j = (int)(e - L.off[v]);
+        for (int r = 0; r < B; ++r) {
+          gp += dp[(size_t)r * ld + j];
+          gv += dq[(size_t)r * ld + j];
+        }
+      } else {
+        const int64_t loc = e - L.off[v];
+        const int k = (int)(loc / N), j = (int)(loc % N);
+        const float* __restrict__ x = src.p.in[l];
+        for (int r = 0; r < B; ++r) {
+          const float xv = x[(size_t)r * K + k];
+          gp = fmaf(xv, dp[(size_t)r * ld + j], gp);
+          gv = fmaf(xv, dq[(size_t)r * ld + j], gv);
+        }
+      }
+    } else {
+      const float* __restrict__ d = src.p.d[l];
+      float g = 0.f;
+      if (v & 1) {
+        const int j = (int)(e - L.off[v]);
+        for (int r = 0; r < B; ++r) g += d[(size_t)r * ld + j];
+      } else {
+        const int64_t loc = e - L.off[v];
+        const int k = (int)(loc / N), j = (int)(loc % N);
+        const float* __restrict__ x = src.p.in[l];
+        for (int r = 0; r < B; ++r) g = fmaf(x[(size_t)r * K + k], d[(size_t)r * ld + j], g);
+      }
+      if (hp) gp = g;
+      else gv = g;
+    }
+    op.grad[e] = gp;
+    ov.grad[e] = gv;
+    if (FUSED) {
+      if (hv) rms_step(ov, e, gv);
+      if (hp) rms_step(op, e, gp);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 3) {
+    float s = 0.f;
+    for (int r = 0; r < B; ++r) s += w.lossrow[(size_t)r * 3 + threadIdx.x];
+    w.losses[threadIdx.x] = s;
+  }
+}
+
+// One block per variable.  CLIP: tf.clip_by_norm on each cost's tensor, scale = clip / max(||g||_2, clip), the two sums of
+// squares in mlp_update_kernel's fixed order.  Then the value step and the policy step, each where its optimizer has a slot.
+template <bool CLIP>
+__global__ __launch_bounds__(THREADS) void mlp_update_dual_kernel(Layout L, Opt op, Opt ov) {
+  __shared__ float shp[THREADS];
+  __shared__ float shv[THREADS];
+  const int var = blockIdx.x;
+  const bool hp = has_p(var), hv = has_v(var);
+  const int64_t lo = L.off[var], hi = L.off[var + 1];
+  float scale_p = 1.f, scale_v = 1.f;
+  if (CLIP) {
+    float sp = 0.f, sv = 0.f;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+      sp += op.grad[i] * op.grad[i];
+      sv += ov.grad[i] * ov.grad[i];
+    }
+    shp[threadIdx.x] = sp;
+    shv[threadIdx.x] = sv;
+    __syncthreads();
+    for (int h = THREADS / 2; h > 0; h >>= 1) {
+      if (threadIdx.x < h) {
+        shp[threadIdx.x] += shp[threadIdx.x + h];
+        shv[threadIdx.x] += shv[threadIdx.x + h];
+      }
+      __syncthreads();
+    }
+    scale_p = op.clip / fmaxf(sqrtf(shp[0]), op.clip);
+    scale_v = ov.clip / fmaxf(sqrtf(shv[0]), ov.clip);
+  }
+  for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+    if (hv) {
+      float g = ov.grad[i];
+      if (CLIP) g *= scale_v;
+      rms_step(ov, i, g);
+    }
+    if (hp) {
+      float g = op.grad[i];
+      if (CLIP) g *= scale_p;
+      rms_step(op, i, g);
+    }
+  }
+}
+
 __global__ void mlp_loss_kernel(Work w, int B) {
   if (threadIdx.x < 3) {
     float s = 0.f;
@@ -402,15 +557,20 @@ using namespace ga3c_vec;
 struct ga3c_mlp : Net {
   ga3c_mlp_config cfg;
   Layout L;
-  Work w{};
+  WorkDual w{};                   // del_v: dual only
   float* work_base = nullptr;
 
   int alloc_work(size_t B) {      // per-row workspace, one block
     const size_t S = L.S, A = L.A;
-    return carve_rows(B, {S, 4, 256, 256, 100, 64, 4, 256, 256, 100, 64, 1, 2 * A, A, 1, 2 * A, 3},
-                      {&w.x, &w.act[0], &w.act[1], &w.act[2], &w.act[3], &w.act[4], &w.del[0], &w.del[1], &w.del[2], &w.del[3],
-                       &w.del[4], &w.v, &w.z, &w.p, &w.dv, &w.dz, &w.lossrow},
-                      &work_base, &w.losses);
+    std::vector<size_t> widths = {S, 4, 256, 256, 100, 64, 4, 256, 256, 100, 64, 1, 2 * A, A, 1, 2 * A, 3};
+    std::vector<float**> dst = {&w.x, &w.act[0], &w.act[1], &w.act[2], &w.act[3], &w.act[4], &w.del[0], &w.del[1], &w.del[2],
+                                &w.del[3], &w.del[4], &w.v, &w.z, &w.p, &w.dv, &w.dz, &w.lossrow};
+    if (dual)
+      for (int l = 0; l < NTRUNK; ++l) {
+        widths.push_back((size_t)TRUNK_OUT[l]);
+        dst.push_back(&w.del_v[l]);
+      }
+    return carve_rows(B, widths, dst, &work_base, &w.losses);
   }
 
   void free_work() { (void)hipFree(work_base); }
@@ -431,20 +591,49 @@ struct ga3c_mlp : Net {
     return g;
   }
 
+  GradSrc2 grad_src2() const {
+    GradSrc2 g;
+    g.p = grad_src();
+    for (int l = 0; l < NLAYERS; ++l) g.dv[l] = l < NTRUNK ? w.del_v[l] : g.p.d[l];
+    return g;
+  }
+
+  Opt value_opt(const Opt& o) const {   // the value optimizer: the policy optimizer's constants on arenas 4 / 5 / 6
+    Opt q = o;
+    q.ms = arena[4]; q.mom = arena[5]; q.grad = arena[6];
+    return q;
+  }
+
   void rows(int mode, const Input& in, int B, float beta, float* p, float* v, float* z) {
+    if (dual && mode == TRAIN) {
+      hipLaunchKernelGGL((mlp_tile_kernel<TRAIN_DUAL, WorkDual>), dim3((B + TILE - 1) / TILE), dim3(THREADS), 0, st, L,
+                         (const float*)arena[0], in, (const float*)d_y, (const float*)d_a, B, beta, w, p, v, z);
+      return;
+    }
     const auto kernel = mode == PREDICT ? mlp_tile_kernel<PREDICT> : mode == EVAL ? mlp_tile_kernel<EVAL> : mlp_tile_kernel<TRAIN>;
     const float* y = mode == PREDICT ? nullptr : d_y;
     const float* a = mode == PREDICT ? nullptr : d_a;
-    hipLaunchKernelGGL(kernel, dim3((B + TILE - 1) / TILE), dim3(THREADS), 0, st, L, (const float*)arena[0], in, y, a, B, beta, w,
-                       p, v, z);
+    hipLaunchKernelGGL(kernel, dim3((B + TILE - 1) / TILE), dim3(THREADS), 0, st, L, (const float*)arena[0], in, y, a, B, beta,
+                       (const Work&)w, p, v, z);
   }
 
   void wgrad(int B, const Opt& o, bool fused) {
+    if (dual) {
+      const auto kernel2 = fused ? mlp_wgrad_dual_kernel<true> : mlp_wgrad_dual_kernel<false>;
+      hipLaunchKernelGGL(kernel2, dim3((int)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, L, grad_src2(), B, o,
+                         value_opt(o), w);
+      return;
+    }
     const auto kernel = fused ? mlp_wgrad_kernel<true> : mlp_wgrad_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((int)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, L, grad_src(), B, o, w);
   }
 
   void update(const Opt& o, bool clipped) {
+    if (dual) {
+      const auto kernel2 = clipped ? mlp_update_dual_kernel<true> : mlp_update_dual_kernel<false>;
+      hipLaunchKernelGGL(kernel2, dim3(NVARS), dim3(THREADS), 0, st, L, o, value_opt(o));
+      return;
+    }
     const auto kernel = clipped ? mlp_update_kernel<true> : mlp_update_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(NVARS), dim3(THREADS), 0, st, L, o);
   }
@@ -454,6 +643,8 @@ struct ga3c_mlp : Net {
 
 namespace {
 
+const char* const DEL_NAMES[NTRUNK] = {"dpd1", "dpd2", "dpd3", "dpd4", "dd1"};
+
 int64_t width_of(const ga3c_mlp* m, const std::string& name) {
   const int S = m->L.S, A = m->L.A;
   static const std::map<std::string, int> fixed = {{"pd1", 4}, {"pd2", 256}, {"pd3", 256}, {"pd4", 100}, {"d1", 64},
@@ -461,6 +652,8 @@ int64_t width_of(const ga3c_mlp* m, const std::string& name) {
                                                    {"v", 1}, {"dv", 1}, {"lossrow", 3}};
   auto it = fixed.find(name);
   if (it != fixed.end()) return it->second;
+  for (int l = 0; l < NTRUNK; ++l)                             // dd1_v, dpd4_v ... dpd1_v: the value stream, dual only
+    if (m->dual && name == std::string(DEL_NAMES[l]) + "_v") return TRUNK_OUT[l];
   if (name == "x") return S;
   if (name == "p") return A;
   if (name == "z" || name == "dz") return 2 * A;
@@ -469,10 +662,10 @@ int64_t width_of(const ga3c_mlp* m, const std::string& name) {
 
 float* work_ptr(ga3c_mlp* m, const std::string& name) {
   const char* acts[NTRUNK] = {"pd1", "pd2", "pd3", "pd4", "d1"};
-  const char* dels[NTRUNK] = {"dpd1", "dpd2", "dpd3", "dpd4", "dd1"};
   for (int l = 0; l < NTRUNK; ++l) {
     if (name == acts[l]) return m->w.act[l];
-    if (name == dels[l]) return m->w.del[l];
+    if (name == DEL_NAMES[l]) return m->w.del[l];
+    if (m->dual && name == std::string(DEL_NAMES[l]) + "_v") return m->w.del_v[l];
   }
   if (name == "x") return m->w.x;
   if (name == "v") return m->w.v;
@@ -494,9 +687,10 @@ int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out) {
   CHK(check_dims(*cfg, MAX_S, MAX_A, 65536));
   if (!(cfg->flags & GA3C_FLAG_CONTINUOUS))
     return fail(GA3C_EINVAL, "the vector-state network has the angle-output head only: GA3C_FLAG_CONTINUOUS is required");
-  if (cfg->flags & ~(uint32_t)(GA3C_FLAG_CONTINUOUS | GA3C_FLAG_GRAD_CLIP))
-    return fail(GA3C_EINVAL, "flags 0x%x: only GA3C_FLAG_CONTINUOUS and GA3C_FLAG_GRAD_CLIP apply to the vector-state network",
-                cfg->flags);
+  if (cfg->flags & ~(uint32_t)(GA3C_FLAG_CONTINUOUS | GA3C_FLAG_GRAD_CLIP | GA3C_FLAG_DUAL_RMSPROP))
+    return fail(GA3C_EINVAL,
+                "flags 0x%x: only GA3C_FLAG_CONTINUOUS, GA3C_FLAG_GRAD_CLIP and GA3C_FLAG_DUAL_RMSPROP apply to the vector-state "
+                "network", cfg->flags);
   CHK(check_device(*cfg));
   ga3c_mlp* m = new (std::nothrow) ga3c_mlp();
   if (!m) return fail(GA3C_EINVAL, "out of host memory");
@@ -505,6 +699,21 @@ int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out) {
   m->ZW = 2 * cfg->num_actions;
   m->L = make_layout(cfg->state_dim, cfg->num_actions);
   for (int l = 0; l < NLAYERS; ++l) m->add_dense(VAR_NAMES[2 * l], VAR_NAMES[2 * l + 1], m->L.off[2 * l], m->L.in[l], m->L.out[l]);
+  m->dual = (cfg->flags & GA3C_FLAG_DUAL_RMSPROP) != 0;
+  if (m->dual)      // two optimizers built value first: TF-1 names the slots /RMSProp, _1, _2, _3 in creation order per variable
+    for (int v = 0; v < NVARS; ++v) {
+      Var& var = m->vars[v];
+      var.ckpt.assign(1, {var.name + ":0", 0});
+      const bool trunk = v < 2 * NTRUNK;
+      if (trunk || v < 2 * NTRUNK + 2) {
+        var.ckpt.emplace_back(var.name + "/RMSProp:0", 4);
+        var.ckpt.emplace_back(var.name + "/RMSProp_1:0", 5);
+      }
+      if (trunk || v >= 2 * NTRUNK + 2) {
+        var.ckpt.emplace_back(var.name + (trunk ? "/RMSProp_2:0" : "/RMSProp:0"), 1);
+        var.ckpt.emplace_back(var.name + (trunk ? "/RMSProp_3:0" : "/RMSProp_1:0"), 2);
+      }
+    }
   return create(m, out);
 }
 
@@ -538,8 +747,17 @@ int ga3c_mlp_set_param(ga3c_mlp* m, const char* name, int32_t which, const float
 
 int ga3c_mlp_save(ga3c_mlp* m, const char* path) { return save(m, path); }
 
-// an image-network file holds no dense11_p/w: refused before anything is written
-int ga3c_mlp_load(ga3c_mlp* m, const char* path) { return load(m, path); }
+// An image-network file holds no dense11_p/w: refused before anything is written.  A two-optimizer file holds every member
+// of a single-optimizer one (the trunk's value slots under the same names), so a single-optimizer network tells it by the
+// policy optimizer's first trunk slot; a single-optimizer file lacks that member and a dual network refuses it for that.
+int ga3c_mlp_load(ga3c_mlp* m, const char* path) {
+  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
+  std::map<std::string, ga3c_ckpt::Member> members;
+  CHK(read_checkpoint(path, &members));
+  if (!m->dual && members.count("dense11_p/w/RMSProp_2:0"))
+    return fail(GA3C_ESTATE, "%s is a DUAL_RMSPROP checkpoint; this network has one optimizer", path);
+  return load(m, path, members);
+}
 
 int ga3c_mlp_predict(ga3c_mlp* m, const float* x, int32_t batch, float* p, float* v, float* z) {
   return predict(m, x, batch, p, v, z);

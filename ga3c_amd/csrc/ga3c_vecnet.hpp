@@ -5,13 +5,15 @@
 // .npz checkpoint.  A handle fills, before alloc_core,
 //   kind, device, S, max_batch                 what it calls itself in an error text; S: the floats of a prediction row
 //   out_widths                                 the outputs of a lane, floats per row each: p[A], v[1], z[ZW], or DDPG's a[A]
-//   narena, nwritable                          arenas, and how many of them set_* and a checkpoint reach: 4 / 3, or 5 / 4
+//   narena, writable                           arenas, and which of them set_* and a checkpoint reach: 4 / {0,1,2}, DDPG's
+//                                              5 / {0,1,2,3}, or 7 / {0,1,2,4,5} with two optimizers (Net::dual)
 //   vars                                       the variable table, each variable with its (checkpoint member, arena) pairs
 // and passes predict_begin the launch of its own row kernel.
 //
 // Net: the actor-critic layer of ga3c_mlp and ga3c_dmlp on top of Core -- TF-1 RMSProp on arenas 0/1/2/3, the train staging
-// and the train-type calls.  A network's handle N derives from Net, fills the variable table (add_dense) before create() and
-// supplies
+// and the train-type calls.  With `dual` set before create() (ga3c_mlp only) it also allocates arenas 4/5/6, the
+// value optimizer's ms / mom / last gradient; the network's own hooks below then step both optimizers.  A network's handle N
+// derives from Net, fills the variable table (add_dense) before create() and supplies
 //   cfg                                        its ABI config: device, state_dim, num_actions, max_batch, flags,
 //                                              rmsprop_decay / _momentum / _epsilon, grad_clip_norm, predict_lanes
 //   w                                          its Work: the rows p, v, z the train-type calls write and losses[3]
@@ -124,8 +126,9 @@ struct Core {
   std::vector<int> out_widths;    // a lane's outputs, floats per row each
   std::vector<Var> vars;          // arena order
   int64_t n = 0;                  // arena size
-  int narena = 0, nwritable = 0;  // arenas 0 .. nwritable-1 are what set_* and a checkpoint reach; the others are read only
-  float* arena[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int narena = 0;
+  std::vector<int> writable;      // the arenas that set_* and a checkpoint reach; the others are read only
+  float* arena[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = nullptr;       // every kernel and copy of the network: a prediction sees the weights before or after a
                                   // train step, never a mix, and needs no second buffer
   std::mutex mu;                  // enqueue order on `st` and the lanes' bookkeeping
@@ -254,8 +257,9 @@ inline int param_index(const Core* m, const char* name) {
 }
 
 inline int arena_copy(Core* m, int which, int64_t off, int64_t count, float* out, const float* in) {
-  const int last = (in ? m->nwritable : m->narena) - 1;
-  if (which < 0 || which > last) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, last);
+  if (which < 0 || which >= m->narena) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, m->narena - 1);
+  if (in && std::find(m->writable.begin(), m->writable.end(), which) == m->writable.end())
+    return fail(GA3C_EINVAL, "arena %d is read only", which);
   HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> tl(m->train_mu);
   std::lock_guard<std::mutex> lk(m->mu);
@@ -324,10 +328,13 @@ inline int param_copy(Core* m, const char* name, int32_t which, float* out, cons
   return arena_copy(m, which, var.off, count, out, in);
 }
 
-// The writable arenas on the host, as save writes and load starts from them.
+// The writable arenas on the host, by arena number, as save writes and load starts from them.
 inline int read_arenas(Core* m, std::vector<std::vector<float>>* arena) {
-  arena->assign((size_t)m->nwritable, std::vector<float>((size_t)m->n));
-  for (int w = 0; w < m->nwritable; ++w) CHK(get_arena(m, w, (*arena)[w].data(), m->n));
+  arena->assign((size_t)m->narena, std::vector<float>());
+  for (int w : m->writable) {
+    (*arena)[w].resize((size_t)m->n);
+    CHK(get_arena(m, w, (*arena)[w].data(), m->n));
+  }
   return GA3C_OK;
 }
 
@@ -391,7 +398,7 @@ inline int load(Core* m, const char* path, const std::map<std::string, ga3c_ckpt
     }
   int64_t step = 0;
   CHK(checkpoint_step(path, members, &step));
-  for (int w = 0; w < m->nwritable; ++w) CHK(set_arena(m, w, arena[w].data(), m->n));
+  for (int w : m->writable) CHK(set_arena(m, w, arena[w].data(), m->n));
   m->step.store(step);
   return GA3C_OK;
 }
@@ -536,8 +543,9 @@ int check_device(const C& c) {
 
 const char* const CKPT_SUFFIX[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};   // a variable and its two slots, arenas 0..2
 
-struct Net : Core {               // arenas: theta, ms, mom, grad
+struct Net : Core {               // arenas: theta, ms, mom, grad; dual: + the value optimizer's ms, mom, grad
   int A = 0;
+  bool dual = false;              // two optimizers, one per cost: arenas 1/2/3 are cost_p's, 4/5/6 cost_v's
   int ZW = 0;                     // logits per row
   bool clip = false;
   Opt opt{};                      // the arenas and the optimizer's constants; lr is the call's
@@ -782,6 +790,7 @@ int alloc_all(N* m) {
   CHK(alloc_core(m, m->cfg.predict_lanes));
   std::vector<float> ones((size_t)m->n, 1.0f);     // the RMSProp ms slot starts at 1 (TF-1 RMSPropOptimizer)
   HIPCHK(hipMemcpy(m->arena[1], ones.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
+  if (m->dual) HIPCHK(hipMemcpy(m->arena[4], ones.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
   m->opt.theta = m->arena[0]; m->opt.ms = m->arena[1]; m->opt.mom = m->arena[2]; m->opt.grad = m->arena[3];
   CHK(m->alloc_work(B));
   CHK(halloc(&m->h_x, B * S)); CHK(halloc(&m->h_y, B)); CHK(halloc(&m->h_a, B * A)); CHK(halloc(&m->h_off, B));
@@ -799,8 +808,9 @@ int create(N* m, N** out) {
   m->max_batch = c.max_batch;
   m->device = c.device;
   m->out_widths = {m->A, 1, m->ZW};
-  m->narena = 4;
-  m->nwritable = 3;
+  m->narena = m->dual ? 7 : 4;
+  m->writable = {0, 1, 2};
+  if (m->dual) m->writable.insert(m->writable.end(), {4, 5});
   m->clip = (c.flags & GA3C_FLAG_GRAD_CLIP) != 0;
   m->opt.omr = 1.0f - c.rmsprop_decay;
   m->opt.mu = c.rmsprop_momentum;

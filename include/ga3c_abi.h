@@ -37,7 +37,8 @@ extern "C" {
                                       (DESIGN.md 8d).  p = atan2(sigmoid(d1 Wy + by) - 0.5, sigmoid(d1 Wx + bx) - 0.5) / pi is the
                                       action vector [B,A] (in (-1, 1]); a train batch's `a` is [B,A] float actions; every `z`
                                       output is [hx | hy], B x 2A (hx = d1 Wx + bx, hy = d1 Wy + by).  num_actions <= 32.
-                                      With GA3C_FLAG_DUAL_RMSPROP: GA3C_EINVAL (not supported yet) */
+                                      With GA3C_FLAG_DUAL_RMSPROP: GA3C_EINVAL on ga3c_net (not supported yet); the
+                                      vector-state network ga3c_mlp takes both */
 
 #define GA3C_STATE_FLOATS 28224    /* 84*84*4 (Config.py:90-92) */
 #define GA3C_MAX_ACTIONS 64
@@ -333,19 +334,29 @@ int ga3c_net_allreduce_grads(ga3c_net* net);
  * A handle of its own: none of ga3c_net's workspace, lanes or fast paths apply.  Same conventions: int return codes,
  * ga3c_last_error(), arenas 0 weights / 1 `ms` / 2 `mom` / 3 last gradient.  One HIP stream carries every kernel of the
  * handle, so a prediction sees the weights before or after a train step, never a mix; train-type calls are serialised.
+ * GA3C_FLAG_DUAL_RMSPROP: one optimizer per cost as on ga3c_net -- the trunk takes the value step and then the
+ * policy step, logits_p/out_{x,y}/{w,b} only the policy optimizer's and logits_v/{w,b} only the value optimizer's; arenas 1 / 2 / 3 are the
+ * policy optimizer's `ms` / `mom` / last cost_p gradient, 4 / 5 the value optimizer's `ms` / `mom`, 6 the last cost_v gradient
+ * (exactly 0 where a cost has no path; slot regions without a slot keep ms = 1, mom = 0).  With GA3C_FLAG_GRAD_CLIP every
+ * gradient tensor of both costs is clipped by tf.clip_by_norm instead.  The step still counts train calls.
  *
  * Arena (TF creation order, 16 variables, 4 S + 99,305 + 130 A floats): dense11_p/w[S,4] /b[4] dense12_p/w[4,256] /b[256]
  * dense13_p/w[256,256] /b[256] dense14_p/w[256,100] /b[100] dense1/w[100,64] /b[64] logits_v/w[64,1] /b[1]
  * logits_p/out_x/w[64,A] /b[A] logits_p/out_y/w[64,A] /b[A].
  * Checkpoints: the .npz container of ga3c_net_save with these 16 names; an image-network file and a vector-network file
- * each refuse to load into the other kind of network (GA3C_ESTATE, network untouched). */
+ * each refuse to load into the other kind of network (GA3C_ESTATE, network untouched).  GA3C_FLAG_DUAL_RMSPROP names the slots
+ * as ga3c_net_save does (derived, not observed): the trunk's variables carry the value optimizer's "/RMSProp:0", "/RMSProp_1:0"
+ * (arenas 4, 5) and the policy optimizer's "/RMSProp_2:0", "/RMSProp_3:0" (arenas 1, 2); logits_v/{w,b} the value optimizer's
+ * and logits_p/out_{x,y}/{w,b} the policy optimizer's "/RMSProp:0", "/RMSProp_1:0".  A dual network loads only such a file, a
+ * single-optimizer network only the other kind (it tells a dual file by dense11_p/w/RMSProp_2:0): GA3C_ESTATE, untouched. */
 typedef struct ga3c_mlp ga3c_mlp;
 typedef struct ga3c_mlp_config {
   int32_t device;
   int32_t state_dim;       /* S, 1..64 (Pendulum: 3) */
   int32_t num_actions;     /* A, 1..32 (Pendulum: 1) */
   int32_t max_batch;       /* rows of one predict / train call */
-  uint32_t flags;          /* GA3C_FLAG_CONTINUOUS (required) | GA3C_FLAG_GRAD_CLIP; anything else: GA3C_EINVAL */
+  uint32_t flags;          /* GA3C_FLAG_CONTINUOUS (required) | GA3C_FLAG_GRAD_CLIP | GA3C_FLAG_DUAL_RMSPROP; anything else:
+                              GA3C_EINVAL */
   float rmsprop_decay;
   float rmsprop_momentum;
   float rmsprop_epsilon;
@@ -356,8 +367,10 @@ typedef struct ga3c_mlp_config {
 int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out);   /* weights zero until set_arena(0) */
 int ga3c_mlp_destroy(ga3c_mlp* net);
 int ga3c_mlp_param_count(ga3c_mlp* net, int64_t* count);
-int ga3c_mlp_get_arena(ga3c_mlp* net, int32_t which, float* out, int64_t count);      /* which 0..3 */
-int ga3c_mlp_set_arena(ga3c_mlp* net, int32_t which, const float* in, int64_t count); /* which 0..2 */
+/* which: 0 weights, 1 `ms`, 2 `mom`, 3 last gradient; GA3C_FLAG_DUAL_RMSPROP adds 4 / 5 / 6 (above), GA3C_EINVAL without it.
+ * get: any of them; set: 0..2 and, with the flag, 4..5 (a gradient arena is read only).  get_param / set_param alike. */
+int ga3c_mlp_get_arena(ga3c_mlp* net, int32_t which, float* out, int64_t count);
+int ga3c_mlp_set_arena(ga3c_mlp* net, int32_t which, const float* in, int64_t count);
 int ga3c_mlp_get_step(ga3c_mlp* net, int64_t* step);
 int ga3c_mlp_set_step(ga3c_mlp* net, int64_t step);
 int32_t ga3c_mlp_num_params(ga3c_mlp* net);                         /* 16 */
@@ -375,7 +388,8 @@ int ga3c_mlp_train(ga3c_mlp* net, const float* x, const float* y_r, const float*
                    float beta, float* losses);
 int ga3c_mlp_compute_grads(ga3c_mlp* net, const float* x, const float* y_r, const float* a, int32_t batch, float beta,
                            float* losses);                                     /* gradient into arena 3, no update */
-int ga3c_mlp_apply_grads(ga3c_mlp* net, float learning_rate);                 /* (clip +) RMSProp on arena 3, step += 1 */
+int ga3c_mlp_apply_grads(ga3c_mlp* net, float learning_rate);                 /* (clip +) RMSProp on arena 3 (dual: 6, then
+                                                                                 3), step += 1 */
 /* Forward + loss, no update: the states are x (host rows) or offsets (rows of the registered segment), exactly one.
  * pd1 f32[B,4], pd2 f32[B,256], d1 f32[B,64], v f32[B], p f32[B,A] (each may be NULL): what the reference's summary
  * histograms (NetworkVP.py:164-168) look at. */
@@ -398,7 +412,8 @@ int ga3c_mlp_time_resident(ga3c_mlp* net, int32_t mode, int32_t batch, int32_t i
                            float* elapsed_ms);
 /* Rows of the last train / compute_grads / evaluate / resident step, for tests: name in {"x", "pd1", "pd2", "pd3", "pd4",
  * "d1", "v", "z", "p", "dpd1", "dpd2", "dpd3", "dpd4", "dd1" (deltas at the layers' pre-activations), "dv", "dz",
- * "lossrow"}; count = rows x width. */
+ * "lossrow"}; count = rows x width.  GA3C_FLAG_DUAL_RMSPROP: "dd1", "dpd4" ... "dpd1" are cost_p's deltas and "dd1_v",
+ * "dpd4_v" ... "dpd1_v" cost_v's (GA3C_EINVAL without the flag). */
 int ga3c_mlp_fetch(ga3c_mlp* net, const char* name, float* out, int64_t count);
 
 /* ---- The discrete-action vector-state network: reference NetworkVP_discrate.py:39-130, the network of GAME = 'CartPole-v0'

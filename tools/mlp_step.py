@@ -3,7 +3,8 @@
 device, device-synchronised timing (ga3c_mlp_time_resident: HIP events around `iters` back-to-back steps; mode 0 =
 predict, 1 = train).  Median and min over rounds, one JSON line per configuration.  Launches per step: predict 1, train 2
 (3 with USE_GRAD_CLIP).
-usage: python tools/mlp_step.py [--predict 1 128] [--train 128 132 201] [--rounds 5] [--iters 200] [--clip]"""
+--dual: Config.DUAL_RMSPROP, one RMSProp optimizer per cost; the same launch counts.
+usage: python tools/mlp_step.py [--predict 1 128] [--train 128 132 201] [--rounds 5] [--iters 200] [--clip] [--dual]"""
 import argparse
 import json
 import os
@@ -24,11 +25,13 @@ def main():
     ap.add_argument("--state-dim", type=int, default=3)
     ap.add_argument("--actions", type=int, default=1)
     ap.add_argument("--clip", action="store_true")
+    ap.add_argument("--dual", action="store_true")
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
     from NetworkVP_vector import Network
     Config.USE_GRAD_CLIP = args.clip
+    Config.DUAL_RMSPROP = args.dual
     S, A = args.state_dim, args.actions
     maxB = max(args.predict + args.train)
     net = Network("gpu:0", "mlp_step", A, (S,), max_batch=maxB)
@@ -48,7 +51,7 @@ def main():
     for (mode, b), v in res.items():
         v = sorted(v)
         print(json.dumps({"step": "train" if mode else "predict", "rows": b, "state_dim": S, "actions": A,
-                          "grad_clip": bool(args.clip), "launches": (3 if args.clip else 2) if mode else 1,
+                          "grad_clip": bool(args.clip), "dual_rmsprop": bool(args.dual), "launches": (3 if args.clip else 2) if mode else 1,
                           "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2), "rounds": args.rounds,
                           "iters": args.iters}), flush=True)
     net.close()
