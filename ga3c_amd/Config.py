@@ -140,6 +140,10 @@ class Config:
     FRAME_HEIGHT = 210
     FRAME_WIDTH = 160
     FRAME_HISTORY = 0                   # planes of history per agent on the device; 0 = derived from the queue bounds
+    DEVICE_AGENTS = 0                   # > 0 (GAME = 'CartPole-v0' only): this many environments, their rollouts and their
+                                        # training rows live in HBM and the server steps them with HIP kernels; no agent
+                                        # process, predictor or trainer is started (ThreadDeviceAgents.py)
+    DEVICE_AGENT_STEPS = 32             # actor steps per native call of that loop (1..64)
 
 
 VECTOR_GAMES = ('Pendulum-v0', 'CartPole-v0')      # games whose state is a vector (Server.py:35-43 of the reference)
@@ -213,3 +217,36 @@ def resolve_ddpg(explicit=()):
         raise ValueError("REPLAY_BUFFER_SIZE must exceed TRAINING_MIN_BATCH_SIZE: a batch is sampled only from more rows than it holds")
     Config.USE_REPLAY_MEMORY = True
     Config.DISCOUNTING = False
+
+
+def resolve_device_agents(explicit=()):
+    """What DEVICE_AGENTS > 0 cannot be combined with.  Call after resolve_action_space and resolve_ddpg.  With
+    DEVICE_AGENTS = 0 nothing is checked and nothing changes."""
+    n = int(Config.DEVICE_AGENTS)
+    if n == 0:
+        return
+    if n < 0:
+        raise ValueError("DEVICE_AGENTS=%d: 0 (off) or the number of environments on the device" % n)
+    if Config.USE_DDPG:
+        raise ValueError("DEVICE_AGENTS with USE_DDPG is not supported: the device actors step CartPole-v0 only")
+    if Config.GAME != 'CartPole-v0':
+        raise ValueError("DEVICE_AGENTS with GAME=%s is not supported: the device actors step CartPole-v0 only "
+                         "(Pendulum-v0 and the image games keep their agent processes)" % Config.GAME)
+    if Config.RETURN_MODE != 'fork':
+        raise ValueError("DEVICE_AGENTS with RETURN_MODE=%r is not supported: the device computes the fork's returns" % Config.RETURN_MODE)
+    if not Config.DISCOUNTING or Config.USE_INTERMEDIATE_REWARD:
+        raise ValueError("DEVICE_AGENTS computes the fork's returns with DISCOUNTING and without USE_INTERMEDIATE_REWARD only")
+    if Config.PLAY_MODE:
+        raise ValueError("DEVICE_AGENTS with PLAY_MODE is not supported: the device actors draw their actions")
+    if Config.DYNAMIC_SETTINGS:
+        raise ValueError("DEVICE_AGENTS with DYNAMIC_SETTINGS is not supported: there are no workers to add or remove")
+    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+        raise ValueError("DEVICE_AGENTS with WORLD_SIZE > 1 is not supported")
+    if Config.TIME_MAX < 1:
+        raise ValueError("DEVICE_AGENTS needs TIME_MAX >= 1")
+    if not 1 <= int(Config.DEVICE_AGENT_STEPS) <= 64:
+        raise ValueError("DEVICE_AGENT_STEPS=%r: 1 to 64 actor steps per call" % (Config.DEVICE_AGENT_STEPS,))
+    rows = n * (Config.TIME_MAX + 1)
+    if rows > 65536:
+        raise ValueError("DEVICE_AGENTS=%d x (TIME_MAX + 1 = %d) = %d rows exceed the 65536 rows a train call of the network "
+                         "can take (its max_batch)" % (n, Config.TIME_MAX + 1, rows))

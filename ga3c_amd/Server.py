@@ -13,7 +13,7 @@ import queue
 import threading
 import time
 
-from Config import Config, discrete_vector_game, resolve_action_space, resolve_ddpg, vector_game
+from Config import Config, discrete_vector_game, resolve_action_space, resolve_ddpg, resolve_device_agents, vector_game
 import DataParallel
 from Environment import Environment
 import EnvironmentCart
@@ -26,6 +26,7 @@ import Placement
 import _native as nat
 from ProcessAgent import ProcessAgent, config_snapshot
 from ProcessStats import ProcessStats
+from ThreadDeviceAgents import ThreadDeviceAgents
 from ThreadDynamicAdjustment import ThreadDynamicAdjustment
 from ThreadPredictor import ThreadPredictor
 from ThreadReplay import ThreadReplay, rollout_row_bytes
@@ -40,6 +41,10 @@ class Server:
         resolve_action_space()                  # DISCRATE_INPUT = not CONTINUOUS_INPUT (Server.py:36-38)
         resolve_ddpg()                          # what USE_DDPG implies, and what it refuses (Server.py:48-54, Config.py:160-178)
         # USE_DDPG: NetworkDDPG and the replay thread; trainers take sampled batches of ring slots (ThreadReplay.py)
+        resolve_device_agents()                 # what DEVICE_AGENTS refuses
+        # DEVICE_AGENTS: the environments live on the device and one thread drives them (ThreadDeviceAgents.py)
+        self.device_agent_count = int(Config.DEVICE_AGENTS)
+        self.device_agents = None
         self.ddpg = bool(Config.USE_DDPG)
         self.replay_q = queue.Queue()
         self.replay = None
@@ -94,8 +99,13 @@ class Server:
         Config.STATE_CACHE_ACTIVE = self.state_cache         # (the agents read it from their configuration snapshot)
         if self.state_cache:
             row_bytes = 16
+        # (device agents: a train call takes every environment's rollout at once)
+        model_kw = {"max_batch": max(Config.PREDICTION_BATCH_SIZE, self.device_agent_count * (Config.TIME_MAX + 1))} \
+            if self.device_agent_count else {}
         self.model = model if model is not None else model_cls(Config.DEVICE, Config.NETWORK_NAME, self.num_actions,
-                                                               self.state_dim)
+                                                               self.state_dim, **model_kw)
+        if self.device_agent_count and not hasattr(self.model, "actors_run"):
+            raise RuntimeError("DEVICE_AGENTS needs a model with the actors_* entry points (NetworkVP_discrate.Network)")
         # training_q.get() frees a queue entry at once (ThreadTrainer.py:49); zero-copy trainers keep a rollout's slot
         # until the GPU has read it, so the slots they hold come on top of the queue bound
         slots = int(Config.ROLLOUT_SLOTS)
@@ -212,7 +222,8 @@ class Server:
 
     @property
     def predictions_served(self):
-        return self._served_by_retired + sum(p.served for p in self.predictors)
+        on_device = self.device_agents.served if self.device_agents is not None else 0
+        return self._served_by_retired + sum(p.served for p in self.predictors) + on_device
 
     def add_trainer(self):
         self.trainers.append(ThreadTrainer(self, len(self.trainers)))
@@ -317,6 +328,14 @@ class Server:
             self.replay = ThreadReplay(self)
             self.replay.start()
 
+    def start_device_agents(self):
+        """DEVICE_AGENTS: the one worker; the status line shows NT 0, NP 0 and the environments as NA."""
+        self.stats.trainer_count.value = 0
+        self.stats.predictor_count.value = 0
+        self.stats.agent_count.value = self.device_agent_count
+        self.device_agents = ThreadDeviceAgents(self)
+        self.device_agents.start()
+
     def save_model(self):
         self.model.save(self.stats.episode_count.value)
 
@@ -324,7 +343,10 @@ class Server:
     def main(self, max_seconds=None):
         self.stats.start()
         self.start_replay()
-        self.dynamic_adjustment.start()
+        if self.device_agent_count:
+            self.start_device_agents()          # and nothing else: no agent process, predictor or trainer
+        else:
+            self.dynamic_adjustment.start()
         lr_mult = (Config.LEARNING_RATE_END - Config.LEARNING_RATE_START) / Config.ANNEALING_EPISODE_COUNT
         beta_mult = (Config.BETA_END - Config.BETA_START) / Config.ANNEALING_EPISODE_COUNT
         t0 = time.time()
@@ -364,6 +386,9 @@ class Server:
         self.dynamic_adjustment.exit_flag = True
         if self.dynamic_adjustment.is_alive():      # it may still be starting workers (a run that ends at once)
             self.dynamic_adjustment.join(timeout=30)
+        if self.device_agents is not None:
+            self.device_agents.exit_flag = True
+            self.device_agents.join(None if self.failure is None else 5.0)
         for a in self.agents:
             a.exit_flag.value = True
         self.transport.shutdown()

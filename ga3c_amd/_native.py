@@ -19,6 +19,7 @@ FLAG_DUAL_RMSPROP = 4
 FLAG_CONTINUOUS = 8
 DDPG_FUTURE_REWARD, DDPG_LOSS_PAIRED, DDPG_GRAD_CLIP, DDPG_CRITIC_ADAM, DDPG_OU_NOISE = 1, 2, 4, 8, 16
 DDPG_NOISE_OWN, DDPG_NOISE_GIVEN, DDPG_NOISE_NONE = 0, 1, 2
+ACTORS_MAX_STEPS = 64             # GA3C_ACTORS_MAX_STEPS: actor steps of one ga3c_dmlp_actors_run call
 
 f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)
@@ -147,6 +148,13 @@ HIP_SIGNATURES = {
                                     f32p]),
     "ga3c_dmlp_create": (C.c_int, [C.POINTER(DmlpConfig), C.POINTER(C.c_void_p)]),
     "ga3c_dmlp_evaluate": (C.c_int, [C.c_void_p, f32p, i64p, f32p, f32p, C.c_int32, C.c_float, f32p, f32p, f32p, f32p]),
+    # device actors of the CartPole network (Config.DEVICE_AGENTS), include/ga3c_abi.h: ga3c_dmlp_actors_*
+    "ga3c_dmlp_actors_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int64]),
+    "ga3c_dmlp_actors_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_dmlp_actors_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, i64p]),
+    "ga3c_dmlp_actors_episodes": (C.c_int, [C.c_void_p, f64p, i64p, C.c_int32, i32p]),
+    "ga3c_dmlp_actors_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "ga3c_dmlp_actors_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     # DDPG (USE_DDPG), include/ga3c_abi.h: ga3c_ddpg_*
     "ga3c_ddpg_create": (C.c_int, [C.POINTER(DdpgConfig), C.POINTER(C.c_void_p)]),
     "ga3c_ddpg_destroy": (C.c_int, [C.c_void_p]),

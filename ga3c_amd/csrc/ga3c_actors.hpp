@@ -1,0 +1,559 @@
+// ga3c_actors.hpp -- actors that live on the device (Config.DEVICE_AGENTS): N environments, their rollouts and
+// their training rows stay in HBM, and a vector-state network's handle steps them with the kernels below between its own
+// predict and train kernels, which it reaches through the Net hooks of ga3c_vecnet.hpp (rows, enqueue_train).  Nothing here
+// asks which network it serves; the one game-specific piece is the Env parameter (CartPole below).
+//
+// One actor step of the handle, all on its one stream:
+//   rows(PREDICT) on the observation buffer             the network's own kernel, untouched
+//   actors_step_kernel<Env>   one thread per environment: draw the action (action 0 on an environment's first ever step),
+//                             f64 physics, reward, done, append to the rollout ring, cut the rollout (done, or
+//                             time_count == TIME_MAX), its returns, the episode record and the reset
+//   actors_compact_kernel     one workgroup: an exclusive scan over the environments' cut rollouts and finished episodes
+//                             lays the rows out as one batch in environment order (offsets into the rings, y_r, one-hot
+//                             actions) and appends the episode records to the episode ring in environment order
+//   enqueue_train on the batch, when the step cut any rollout
+// The host reads the batch's row count between the two halves (one 12-byte copy and an event wait per step): the train
+// kernels take their row count as an argument.  No kernel is persistent, none waits for another workgroup, none launches
+// from the device, and every loop is bounded by an argument.  No float atomics: the same seed gives the same bits.
+//
+// What the step restates is ProcessAgent.run_episode / run over EnvironmentCart.Environment with ga3c_returns_fork and
+// ga3c_select_action (ga3c_host.cpp); tests/device_agents_oracle.py is the same statement in numpy.  The f64 arithmetic is
+// compiled with contraction off, as the host library's is.  The uniforms are the one deviation: a stateless function of
+// (seed, environment, draw number), actor_uniform below.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <deque>
+#include <new>
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "ga3c_vecnet.hpp"
+
+namespace ga3c_actors {
+
+using namespace ga3c_vecnet;
+
+constexpr int STEP_THREADS = 256;
+constexpr int SCAN_THREADS = 1024;
+constexpr int MAX_STEPS = GA3C_ACTORS_MAX_STEPS;     // actor steps of one actors_run call: bounds the episode ring
+
+// splitmix64's finalizer
+__host__ __device__ inline uint64_t mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// Uniform number `draw` of environment `env` under `seed`: 53 bits to a double in [0, 1).  All sums wrap at 2^64.
+__host__ __device__ inline double actor_uniform(uint64_t seed, uint64_t env, uint64_t draw) {
+  const uint64_t golden = 0x9E3779B97F4A7C15ull;
+  const uint64_t stream = mix64(seed + golden * (env + 1));
+  const uint64_t bits = mix64(stream + golden * (draw + 1));
+  return (double)(bits >> 11) * 0x1.0p-53;
+}
+
+// ga3c_select_action (ga3c_host.cpp): sequential f64 cumulative sum of the f32 policy, the first index with
+// u < cdf[i] / cdf[n - 1], clamped to n - 1.  The sum is run twice instead of being kept: the same additions, the same bits.
+__device__ inline int select_action(const float* p, int n, double u) {
+#pragma clang fp contract(off)
+  double last = 0.0;
+  for (int i = 0; i < n; ++i) last += (double)p[i];
+  double acc = 0.0;
+  for (int i = 0; i < n; ++i) {
+    acc += (double)p[i];
+    if (u < acc / last) return i;
+  }
+  return n - 1;
+}
+
+// gym's CartPole-v0 under its TimeLimit, as EnvironmentCart.py restates it, with the reference's wrapper: reward r * 0.005 - 1.
+struct CartPole {
+  static constexpr int S = 4;          // observation = f32 of the physics
+  static constexpr int A = 2;
+  static constexpr int RESET_DRAWS = 4;
+
+  __device__ static void step(double* s, int action, int* elapsed, double* reward, int* done) {
+#pragma clang fp contract(off)
+    const double gravity = 9.8, masscart = 1.0, masspole = 0.1, length = 0.5, force_mag = 10.0, tau = 0.02;
+    const double total_mass = masspole + masscart, polemass_length = masspole * length;
+    const double theta_limit = 12 * 2 * 3.141592653589793 / 360, x_limit = 2.4;
+    double x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+    const double force = action == 1 ? force_mag : -force_mag;
+    const double costheta = cos(theta), sintheta = sin(theta);
+    const double temp = (force + polemass_length * (theta_dot * theta_dot) * sintheta) / total_mass;
+    const double thetaacc = (gravity * sintheta - costheta * temp) /
+                            (length * (4.0 / 3.0 - masspole * (costheta * costheta) / total_mass));
+    const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
+    x = x + tau * x_dot;
+    x_dot = x_dot + tau * xacc;
+    theta = theta + tau * theta_dot;
+    theta_dot = theta_dot + tau * thetaacc;
+    s[0] = x; s[1] = x_dot; s[2] = theta; s[3] = theta_dot;
+    *elapsed += 1;
+    const bool fell = x < -x_limit || x > x_limit || theta < -theta_limit || theta > theta_limit;
+    *done = (fell || *elapsed >= 200) ? 1 : 0;
+    *reward = 1.0 * 0.005 - 1.0;
+  }
+
+  // U(-0.05, 0.05)^4 as numpy draws it, low + (high - low) u; the observation is left alone
+  __host__ __device__ static void reset(double* s, int* elapsed, const double* u) {
+#pragma clang fp contract(off)
+    const double low = -0.05, high = 0.05;
+    for (int k = 0; k < 4; ++k) s[k] = low + (high - low) * u[k];
+    *elapsed = 0;
+  }
+};
+
+// Everything the kernels touch, by device address.  Per environment unless said otherwise; T1 = TIME_MAX + 1.
+struct State {
+  int N, T1, S, A, time_max, ep_cap;
+  double gamma;
+  uint64_t seed;
+  double* phys;              // [N][S] f64 physics
+  int* elapsed;
+  int* time_count;
+  int* started;              // 0 until the first ever step: no observation yet (the host's current_state is None)
+  uint64_t* draws;           // uniforms drawn so far
+  float* obs;                // [N][S] what the network reads
+  float* ring_x;             // [N][T1][S] the rollout: states, ...
+  int* ring_a;               // [N][T1]    actions, ...
+  double* ring_r;            // [N][T1]    rewards; row t of the rollout is slot (head + t) % T1
+  int* head;
+  int* rlen;
+  double* reward_sum;        // since the last cut
+  double* total_reward;      // of the running episode, as ProcessAgent.run counts them
+  long long* total_length;
+  float* p; float* v; float* z;   // [N][A], [N], [N][ZW]: the last prediction
+  double* u;                 // the last step's uniform (-1: none drawn), action, reward, done
+  int* action;
+  double* reward;
+  int* done;
+  int* cut;                  // rows of the rollout this step cut (0: none), where it starts in the ring, its returns [N][T1]
+  int* cut_head;
+  float* cut_y;
+  int* ep_flag;              // this step finished an episode: its record
+  double* ep_reward;
+  long long* ep_length;
+  int64_t* off;              // [N T1] the batch: byte offsets of its rows from ring_x, environment order
+  float* by;                 // [N T1] y_r     (the handle's train staging)
+  float* ba;                 // [N T1][A] one-hot
+  int* counts;               // [3]: rows of the batch, records in the episode ring, episodes this step finished
+  double* ring_ep_reward;    // [ep_cap] the episode ring, in the order the episodes finished
+  long long* ring_ep_length;
+};
+
+template <class Env>
+__global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * STEP_THREADS + threadIdx.x;
+  if (i >= a.N) return;
+  constexpr int S = Env::S;
+  const int T1 = a.T1;
+  double s[S];
+  for (int k = 0; k < S; ++k) s[k] = a.phys[(size_t)i * S + k];
+  int elapsed = a.elapsed[i];
+  uint64_t draws = a.draws[i];
+  const bool started = a.started[i] != 0;
+  a.cut[i] = 0;
+  a.ep_flag[i] = 0;
+
+  int action = 0;
+  double u = -1.0;
+  if (started) {
+    u = actor_uniform(a.seed, (uint64_t)i, draws++);
+    action = select_action(a.p + (size_t)i * a.A, a.A, u);
+  }
+  double reward;
+  int done;
+  Env::step(s, action, &elapsed, &reward, &done);
+  a.u[i] = u;
+  a.action[i] = action;
+  a.reward[i] = reward;
+  a.done[i] = done;
+  float* obs = a.obs + (size_t)i * S;
+  if (!started) {                       // the host's step(None): no experience, and its `done` is not looked at
+    for (int k = 0; k < S; ++k) {
+      a.phys[(size_t)i * S + k] = s[k];
+      obs[k] = (float)s[k];
+    }
+    a.elapsed[i] = elapsed;
+    a.started[i] = 1;
+    return;
+  }
+
+  int head = a.head[i], rlen = a.rlen[i], tc = a.time_count[i];
+  if (rlen < T1) {                      // (always: a rollout is cut at T1 rows at the latest)
+    const int slot = (head + rlen) % T1;
+    float* row = a.ring_x + ((size_t)i * T1 + slot) * S;
+    for (int k = 0; k < S; ++k) row[k] = obs[k];
+    a.ring_a[(size_t)i * T1 + slot] = action;
+    a.ring_r[(size_t)i * T1 + slot] = reward;
+    ++rlen;
+  }
+  for (int k = 0; k < S; ++k) obs[k] = (float)s[k];
+  double rsum = a.reward_sum[i] + reward;
+
+  if (done || tc == a.time_max || rlen == T1) {
+    // ga3c_returns_fork, DISCOUNTING without intermediate rewards: the last row keeps its reward, the others get
+    // gamma^(T-1-t) terminal_reward by sequential products, terminal_reward being the last reward
+    const int T = rlen;
+    float* y = a.cut_y + (size_t)i * T1;
+    y[T - 1] = (float)a.ring_r[(size_t)i * T1 + (head + T - 1) % T1];
+    double acc = reward;
+    for (int t = T - 2; t >= 0; --t) {
+      acc = a.gamma * acc;
+      y[t] = (float)acc;
+    }
+    a.cut[i] = T;
+    a.cut_head[i] = head;
+    double total = a.total_reward[i] + rsum;
+    long long length = a.total_length[i] + (T + 1);
+    rsum = 0.0;
+    tc = 0;
+    if (done) {
+      a.ep_flag[i] = 1;
+      a.ep_reward[i] = total;
+      a.ep_length[i] = length;
+      total = 0.0;
+      length = 0;
+      double ru[Env::RESET_DRAWS];
+      for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = actor_uniform(a.seed, (uint64_t)i, draws++);
+      Env::reset(s, &elapsed, ru);
+      head = 0;
+      rlen = 0;
+    } else {                            // the last experience is row 0 of the next rollout
+      head = (head + T - 1) % T1;
+      rlen = 1;
+    }
+    a.total_reward[i] = total;
+    a.total_length[i] = length;
+  }
+  if (!done) tc += 1;                   // (a new episode starts at time_count 0)
+  for (int k = 0; k < S; ++k) a.phys[(size_t)i * S + k] = s[k];
+  a.elapsed[i] = elapsed;
+  a.draws[i] = draws;
+  a.head[i] = head;
+  a.rlen[i] = rlen;
+  a.time_count[i] = tc;
+  a.reward_sum[i] = rsum;
+}
+
+// One workgroup.  Thread t owns the environments [t c, (t + 1) c), c = ceil(N / SCAN_THREADS); the scan over the threads'
+// sums gives each its first batch row and its first episode record.
+__global__ __launch_bounds__(SCAN_THREADS) void actors_compact_kernel(State a) {
+  __shared__ int srow[SCAN_THREADS];
+  __shared__ int sep[SCAN_THREADS];
+  const int t = threadIdx.x;
+  const int chunk = (a.N + SCAN_THREADS - 1) / SCAN_THREADS;
+  const int lo = min(a.N, t * chunk), hi = min(a.N, lo + chunk);
+  const int ep0 = a.counts[1];
+  int rows = 0, eps = 0;
+  for (int i = lo; i < hi; ++i) {
+    rows += a.cut[i];
+    eps += a.ep_flag[i];
+  }
+  srow[t] = rows;
+  sep[t] = eps;
+  __syncthreads();
+  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
+    const int r = t >= d ? srow[t - d] : 0, e = t >= d ? sep[t - d] : 0;
+    __syncthreads();
+    srow[t] += r;
+    sep[t] += e;
+    __syncthreads();
+  }
+  int row = srow[t] - rows, ep = ep0 + sep[t] - eps;
+  const int T1 = a.T1, A = a.A, cap = a.N * T1;
+  for (int i = lo; i < hi; ++i) {
+    const int T = min(a.cut[i], T1), h = a.cut_head[i];
+    for (int k = 0; k < T && row < cap; ++k, ++row) {
+      const int slot = (h + k) % T1;
+      a.off[row] = ((int64_t)i * T1 + slot) * a.S * (int64_t)sizeof(float);
+      a.by[row] = a.cut_y[(size_t)i * T1 + k];
+      const int act = a.ring_a[(size_t)i * T1 + slot];
+      for (int j = 0; j < A; ++j) a.ba[(size_t)row * A + j] = j == act ? 1.0f : 0.0f;
+    }
+    if (a.ep_flag[i]) {
+      if (ep < a.ep_cap) {
+        a.ring_ep_reward[ep] = a.ep_reward[i];
+        a.ring_ep_length[ep] = a.ep_length[i];
+      }
+      ++ep;
+    }
+  }
+  if (t == SCAN_THREADS - 1) {
+    a.counts[0] = srow[t];
+    a.counts[1] = min(ep0 + sep[t], a.ep_cap);
+    a.counts[2] = sep[t];
+  }
+}
+
+// ------------------------------------------------------------------ host side
+
+struct Field {               // a buffer actors_get / actors_set reach by name
+  const char* name;
+  void* dev;
+  size_t elem;               // bytes of an element
+  size_t per_env;            // elements per environment
+  bool settable;
+};
+
+struct Actors {
+  State d{};
+  char* block = nullptr;     // every device buffer of `d` but by / ba
+  int* h_counts = nullptr;   // pinned
+  std::vector<Field> fields;
+  std::deque<std::pair<double, long long>> finished;   // episode records not yet drained
+  int batch_rows = 0;        // rows of the last step's batch
+};
+
+inline void actors_free(Actors* a) {
+  if (!a) return;
+  (void)hipFree(a->block);
+  (void)hipHostFree(a->h_counts);
+  (void)hipGetLastError();
+  delete a;
+}
+
+// m: a Net-derived handle with cfg and an `Actors* actors` member.  Its train staging d_y / d_a holds the batch's y_r and a.
+template <class Env, class N>
+int actors_create(N* m, int n, int time_max, double discount, int64_t seed) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (m->actors) return fail(GA3C_ESTATE, "this network has device actors already");
+  if (m->S != Env::S || m->A != Env::A)
+    return fail(GA3C_EINVAL, "the environment has %d state floats and %d actions, the network %d and %d", Env::S, Env::A, m->S, m->A);
+  if (n < 1 || time_max < 1) return fail(GA3C_EINVAL, "n %d and time_max %d must be at least 1", n, time_max);
+  const int64_t T1 = (int64_t)time_max + 1;
+  if ((int64_t)n * T1 > m->max_batch)
+    return fail(GA3C_EINVAL, "%d actors x (time_max + 1 = %lld) rows exceed the network's max_batch %d", n, (long long)T1, m->max_batch);
+  HIPCHK(hipSetDevice(m->device));
+  Actors* a = new (std::nothrow) Actors();
+  if (!a) return fail(GA3C_EINVAL, "out of host memory");
+  State& d = a->d;
+  d.N = n; d.T1 = (int)T1; d.S = m->S; d.A = m->A; d.time_max = time_max; d.ep_cap = n * MAX_STEPS;
+  d.gamma = discount;
+  d.seed = (uint64_t)seed;
+  const size_t Nn = (size_t)n, S = (size_t)m->S, A = (size_t)m->A, R = Nn * (size_t)T1, ZW = (size_t)m->ZW;
+  // two passes over one list: sizes, then addresses (each buffer 16-byte aligned)
+  size_t total = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    size_t at = 0;
+    auto carve = [&](auto** p, size_t count) {
+      using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
+      if (pass) *p = reinterpret_cast<T*>(a->block + at);
+      at += (count * sizeof(T) + 15) / 16 * 16;
+    };
+    carve(&d.phys, Nn * S); carve(&d.elapsed, Nn); carve(&d.time_count, Nn); carve(&d.started, Nn); carve(&d.draws, Nn);
+    carve(&d.obs, Nn * S); carve(&d.ring_x, R * S); carve(&d.ring_a, R); carve(&d.ring_r, R); carve(&d.head, Nn);
+    carve(&d.rlen, Nn); carve(&d.reward_sum, Nn); carve(&d.total_reward, Nn); carve(&d.total_length, Nn);
+    carve(&d.p, Nn * A); carve(&d.v, Nn); carve(&d.z, Nn * ZW); carve(&d.u, Nn); carve(&d.action, Nn); carve(&d.reward, Nn);
+    carve(&d.done, Nn); carve(&d.cut, Nn); carve(&d.cut_head, Nn); carve(&d.cut_y, R); carve(&d.ep_flag, Nn);
+    carve(&d.ep_reward, Nn); carve(&d.ep_length, Nn); carve(&d.off, R); carve(&d.counts, 3);
+    carve(&d.ring_ep_reward, (size_t)d.ep_cap); carve(&d.ring_ep_length, (size_t)d.ep_cap);
+    if (!pass) {
+      total = at;
+      if (hipMalloc((void**)&a->block, total) != hipSuccess || hipMemset(a->block, 0, total) != hipSuccess ||
+          hipHostMalloc((void**)&a->h_counts, 3 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        actors_free(a);
+        return fail(GA3C_EHIP, "no memory for %d device actors (%zu bytes)", n, total);
+      }
+    }
+  }
+  d.by = m->d_y;
+  d.ba = m->d_a;
+  // an environment starts as the host's does: reset() when it is made (draws 0..3) and again when its first episode begins
+  // (draws 4..7), no observation
+  std::vector<double> phys(Nn * S);
+  std::vector<uint64_t> draws(Nn, 2 * Env::RESET_DRAWS);
+  for (size_t i = 0; i < Nn; ++i) {
+    double ru[Env::RESET_DRAWS];
+    int elapsed = 0;
+    for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = actor_uniform(d.seed, i, (uint64_t)(Env::RESET_DRAWS + k));
+    Env::reset(&phys[i * S], &elapsed, ru);
+  }
+  if (hipMemcpy(d.phys, phys.data(), phys.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d.draws, draws.data(), draws.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    actors_free(a);
+    return fail(GA3C_EHIP, "copy to the device actors failed");
+  }
+  a->fields = {
+      {"phys", d.phys, 8, S, true},          {"elapsed", d.elapsed, 4, 1, true},     {"time_count", d.time_count, 4, 1, true},
+      {"started", d.started, 4, 1, true},    {"draws", d.draws, 8, 1, true},         {"obs", d.obs, 4, S, true},
+      {"rollout_len", d.rlen, 4, 1, false},  {"p", d.p, 4, A, false},                {"v", d.v, 4, 1, false},
+      {"u", d.u, 8, 1, false},               {"action", d.action, 4, 1, false},      {"reward", d.reward, 8, 1, false},
+      {"done", d.done, 4, 1, false},         {"cut", d.cut, 4, 1, false},
+  };
+  m->actors = a;
+  return GA3C_OK;
+}
+
+// Frees the handle's actors, if any, whatever state the stream is in (the handle's own destroy).
+template <class N>
+void actors_drop(N* m) {
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    (void)hipStreamSynchronize(m->st);
+    (void)hipGetLastError();
+  }
+  actors_free(m->actors);
+  m->actors = nullptr;
+}
+
+template <class N>
+int actors_destroy(N* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (!m->actors) return fail(GA3C_ESTATE, "this network has no device actors");
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipStreamSynchronize(m->st));
+  }
+  actors_free(m->actors);
+  m->actors = nullptr;
+  return GA3C_OK;
+}
+
+// `steps` actor steps, each followed by a train step on the rollouts it cut when `train` is set.  stats (may be null):
+// agent steps, train calls, rows trained, episodes finished.
+template <class Env, class N>
+int actors_run(N* m, int steps, float lr, float beta, int train, int64_t* stats) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  Actors* a = m->actors;
+  if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
+  if (steps < 1 || steps > MAX_STEPS) return fail(GA3C_EINVAL, "steps %d outside [1,%d]", steps, MAX_STEPS);
+  const State& d = a->d;
+  int64_t calls = 0, rows_trained = 0, episodes = 0;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipMemsetAsync(d.counts, 0, 3 * sizeof(int), m->st));     // the episode ring starts empty
+  }
+  int rc = GA3C_OK;
+  for (int s = 0; s < steps; ++s) {
+    {
+      std::lock_guard<std::mutex> lk(m->mu);
+      m->rows(PREDICT, Input{reinterpret_cast<const char*>(d.obs), nullptr, 4 * (int64_t)d.S}, d.N, 0.f, d.p, d.v, d.z);
+      hipLaunchKernelGGL(actors_step_kernel<Env>, dim3((d.N + STEP_THREADS - 1) / STEP_THREADS), dim3(STEP_THREADS), 0, m->st, d);
+      hipLaunchKernelGGL(actors_compact_kernel, dim3(1), dim3(SCAN_THREADS), 0, m->st, d);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(a->h_counts, d.counts, 3 * sizeof(int), hipMemcpyDeviceToHost, m->st));
+      HIPCHK(hipEventRecord(m->tev, m->st));
+    }
+    HIPCHK(hipEventSynchronize(m->tev));
+    const int B = a->h_counts[0];
+    if (B < 0 || B > m->max_batch) {      // (cannot happen: the compaction stops at N T1 rows) -- the episodes are still handed on
+      a->batch_rows = 0;
+      rc = fail(GA3C_ESTATE, "the actors laid out %d rows, max_batch is %d", B, m->max_batch);
+      break;
+    }
+    a->batch_rows = B;
+    if (train && B > 0) {
+      std::lock_guard<std::mutex> lk(m->mu);
+      CHK(enqueue_train(m, Input{reinterpret_cast<const char*>(d.ring_x), d.off, 0}, B, beta, true, lr));
+      m->last_B = B;
+      m->step.fetch_add(1);
+      ++calls;
+      rows_trained += B;
+    }
+  }
+  const int ne = std::min(std::max(a->h_counts[1], 0), d.ep_cap);
+  if (ne > 0) {
+    std::vector<double> er((size_t)ne);
+    std::vector<long long> el((size_t)ne);
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipStreamSynchronize(m->st));
+    HIPCHK(hipMemcpy(er.data(), d.ring_ep_reward, sizeof(double) * ne, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(el.data(), d.ring_ep_length, sizeof(long long) * ne, hipMemcpyDeviceToHost));
+    for (int i = 0; i < ne; ++i) a->finished.emplace_back(er[i], el[i]);
+    episodes = ne;
+  }
+  if (stats) {
+    stats[0] = (int64_t)d.N * steps;
+    stats[1] = calls;
+    stats[2] = rows_trained;
+    stats[3] = episodes;
+  }
+  return rc;
+}
+
+// Drains up to `max` finished episodes, oldest first.
+template <class N>
+int actors_episodes(N* m, double* total_reward, int64_t* total_length, int max, int32_t* count) {
+  if (!m || !count || max < 0 || (max > 0 && (!total_reward || !total_length))) return fail(GA3C_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  Actors* a = m->actors;
+  if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
+  int n = 0;
+  for (; n < max && !a->finished.empty(); ++n) {
+    total_reward[n] = a->finished.front().first;
+    total_length[n] = a->finished.front().second;
+    a->finished.pop_front();
+  }
+  *count = n;
+  return GA3C_OK;
+}
+
+// get (out) / set (in) of a buffer by name; `bytes` must be the buffer's size.
+template <class N>
+int actors_access(N* m, const char* name, void* out, const void* in, int64_t bytes) {
+  if (!m || !name || (!out && !in)) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  Actors* a = m->actors;
+  if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  const State& d = a->d;
+  const std::string nm(name);
+  const int B = a->batch_rows;
+  if (out && nm.compare(0, 6, "batch_") == 0) {       // the last step's batch: its row count, x gathered as the train kernel reads it
+    const size_t S = (size_t)d.S, A = (size_t)d.A;
+    const int64_t want = nm == "batch_rows" ? 4 : nm == "batch_x" ? (int64_t)(4 * S * B) : nm == "batch_y_r" ? 4 * (int64_t)B
+                       : nm == "batch_a" ? (int64_t)(4 * A * B) : -1;
+    if (want < 0) return fail(GA3C_EINVAL, "the device actors have nothing named %s", name);
+    if (bytes != want) return fail(GA3C_EINVAL, "%s is %lld bytes, not %lld", name, (long long)want, (long long)bytes);
+    if (nm == "batch_rows") { *static_cast<int32_t*>(out) = B; return GA3C_OK; }
+    if (B == 0) return GA3C_OK;
+    if (nm == "batch_y_r") { HIPCHK(hipMemcpy(out, d.by, (size_t)want, hipMemcpyDeviceToHost)); return GA3C_OK; }
+    if (nm == "batch_a") { HIPCHK(hipMemcpy(out, d.ba, (size_t)want, hipMemcpyDeviceToHost)); return GA3C_OK; }
+    std::vector<int64_t> off((size_t)B);
+    std::vector<float> ring((size_t)d.N * d.T1 * S);
+    HIPCHK(hipMemcpy(off.data(), d.off, sizeof(int64_t) * B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ring.data(), d.ring_x, sizeof(float) * ring.size(), hipMemcpyDeviceToHost));
+    for (int r = 0; r < B; ++r)
+      memcpy(static_cast<float*>(out) + (size_t)r * S, reinterpret_cast<const char*>(ring.data()) + off[r], 4 * S);
+    return GA3C_OK;
+  }
+  for (const Field& f : a->fields) {
+    if (nm != f.name) continue;
+    const int64_t want = (int64_t)(f.elem * f.per_env * (size_t)d.N);
+    if (bytes != want) return fail(GA3C_EINVAL, "%s is %lld bytes, not %lld", name, (long long)want, (long long)bytes);
+    if (out) {
+      HIPCHK(hipMemcpy(out, f.dev, (size_t)want, hipMemcpyDeviceToHost));
+      return GA3C_OK;
+    }
+    if (!f.settable) return fail(GA3C_EINVAL, "%s is read only", name);
+    if (nm == "elapsed" || nm == "time_count" || nm == "started") {
+      const int32_t* v = static_cast<const int32_t*>(in);
+      const int hi = nm == "time_count" ? d.time_max : nm == "started" ? 1 : 1 << 30;
+      for (int i = 0; i < d.N; ++i)
+        if (v[i] < 0 || v[i] > hi) return fail(GA3C_EINVAL, "%s[%d] = %d outside [0,%d]", name, i, v[i], hi);
+    }
+    HIPCHK(hipMemcpy(f.dev, in, (size_t)want, hipMemcpyHostToDevice));
+    return GA3C_OK;
+  }
+  return fail(GA3C_EINVAL, "the device actors have nothing named %s", name);
+}
+
+}  // namespace ga3c_actors

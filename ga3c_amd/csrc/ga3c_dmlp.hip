@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "ga3c_actors.hpp"
 #include "ga3c_vecnet.hpp"
 
 namespace ga3c_dvec {
@@ -481,6 +482,7 @@ struct ga3c_dmlp : Net {
   float* work_base = nullptr;
   Layout* d_layout = nullptr;     // L and w as the row kernel reads them
   Work* d_work = nullptr;
+  ga3c_actors::Actors* actors = nullptr;   // Config.DEVICE_AGENTS: the environments this handle steps itself (ga3c_actors.hpp)
 
   int alloc_work(size_t B) {      // per-row workspace, one block; the dead layers of chained = 0 get no rows
     const size_t S = L.S, A = L.A;
@@ -599,7 +601,13 @@ int ga3c_dmlp_create(const ga3c_dmlp_config* cfg, ga3c_dmlp** out) {
   return create(m, out);
 }
 
-int ga3c_dmlp_destroy(ga3c_dmlp* m) { return destroy(m); }
+int ga3c_dmlp_destroy(ga3c_dmlp* m) {
+  if (m) {
+    (void)hipSetDevice(m->device);
+    ga3c_actors::actors_drop(m);      // whatever state the stream is in: the handle goes on to be destroyed
+  }
+  return destroy(m);
+}
 
 int ga3c_dmlp_param_count(ga3c_dmlp* m, int64_t* count) { return param_count(m, count); }
 
@@ -699,6 +707,32 @@ int ga3c_dmlp_fetch(ga3c_dmlp* m, const char* name, float* out, int64_t count) {
   const float* src = work_ptr(m, name, &wd);
   if (!src) return fail(GA3C_EINVAL, "no activation named %s (a layer nothing reads has none)", name);
   return fetch(m, name, src, wd, out, count);
+}
+
+// ---- device actors: CartPole environments stepped by this handle, ga3c_actors.hpp
+
+int ga3c_dmlp_actors_create(ga3c_dmlp* m, int32_t n, int32_t time_max, double discount, int64_t seed) {
+  return ga3c_actors::actors_create<ga3c_actors::CartPole>(m, n, time_max, discount, seed);
+}
+
+int ga3c_dmlp_actors_destroy(ga3c_dmlp* m) { return ga3c_actors::actors_destroy(m); }
+
+int ga3c_dmlp_actors_run(ga3c_dmlp* m, int32_t steps, float learning_rate, float beta, int32_t train, int64_t* out_stats) {
+  return ga3c_actors::actors_run<ga3c_actors::CartPole>(m, steps, learning_rate, beta, train, out_stats);
+}
+
+int ga3c_dmlp_actors_episodes(ga3c_dmlp* m, double* total_reward, int64_t* total_length, int32_t max, int32_t* count) {
+  return ga3c_actors::actors_episodes(m, total_reward, total_length, max, count);
+}
+
+int ga3c_dmlp_actors_get(ga3c_dmlp* m, const char* name, void* out, int64_t bytes) {
+  if (!out) return fail(GA3C_EINVAL, "null argument");
+  return ga3c_actors::actors_access(m, name, out, nullptr, bytes);
+}
+
+int ga3c_dmlp_actors_set(ga3c_dmlp* m, const char* name, const void* in, int64_t bytes) {
+  if (!in) return fail(GA3C_EINVAL, "null argument");
+  return ga3c_actors::actors_access(m, name, nullptr, in, bytes);
 }
 
 }  // extern "C"

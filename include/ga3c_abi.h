@@ -501,6 +501,39 @@ int ga3c_dmlp_time_resident(ga3c_dmlp* net, int32_t mode, int32_t batch, int32_t
  * nothing reads has neither rows nor a name here (GA3C_EINVAL). */
 int ga3c_dmlp_fetch(ga3c_dmlp* net, const char* name, float* out, int64_t count);
 
+/* ---- Device actors (Config.DEVICE_AGENTS): n CartPole-v0 environments, their rollouts and their training rows
+ * in HBM, stepped by this handle on its one stream between its own predict and train kernels.  What a step does is
+ * ProcessAgent.run_episode / run over EnvironmentCart.Environment with RETURN_MODE = 'fork' (DISCOUNTING, no intermediate
+ * rewards): action 0 without a prediction on an environment's first ever step; the one-draw action of ga3c_select_action;
+ * f64 physics; reward r * 0.005 - 1; a rollout cut on done or time_count == time_max with its last row kept as row 0 of the
+ * next one; the returns of ga3c_returns_fork in f64, cast to f32; a reset that leaves the observation alone.  The uniforms
+ * are u(seed, environment, draw number) = (mix(mix(seed + G (environment + 1)) + G (draw + 1)) >> 11) 2^-53 with splitmix64's
+ * finalizer mix and G = 0x9E3779B97F4A7C15, all sums mod 2^64; an action takes one draw, a reset four (create
+ * stands for the host's two resets before the first step: draws 0..3 are passed over, 4..7 are the first physics).
+ * create: the network must have S = 4 and A = 2 and n (time_max + 1) <= max_batch (GA3C_EINVAL); a second create is
+ * GA3C_ESTATE, as is every other call here without actors.  destroy: also done by ga3c_dmlp_destroy. */
+#define GA3C_ACTORS_MAX_STEPS 64
+int ga3c_dmlp_actors_create(ga3c_dmlp* net, int32_t n, int32_t time_max, double discount, int64_t seed);
+int ga3c_dmlp_actors_destroy(ga3c_dmlp* net);
+/* steps (1..GA3C_ACTORS_MAX_STEPS) actor steps: predict on the observations, step every environment, lay the rollouts the
+ * step cut out as one batch in environment order and, train != 0 and the batch not empty, train on it (one train step, step
+ * += 1).  Returns when they are done.  out_stats (may be NULL) int64[4]: agent steps (n x steps), train calls, rows trained,
+ * episodes finished.  The episode ring holds n x GA3C_ACTORS_MAX_STEPS records and is drained into the handle's host
+ * queue before the call returns: it cannot overflow. */
+int ga3c_dmlp_actors_run(ga3c_dmlp* net, int32_t steps, float learning_rate, float beta, int32_t train, int64_t* out_stats);
+/* Takes up to max finished episodes out of the handle's queue, in the order they finished (step, then environment):
+ * ProcessAgent.run's (total_reward, total_length), the length counting len(rollout) + 1 per rollout. */
+int ga3c_dmlp_actors_episodes(ga3c_dmlp* net, double* total_reward, int64_t* total_length, int32_t max, int32_t* count);
+/* For tests: a buffer by name, bytes = its whole size.  Per environment, get and set: "phys" f64[n,4] (x, xdot, th, thdot),
+ * "elapsed" i32, "time_count" i32 (0..time_max), "started" i32 (0: no observation yet), "draws" u64 (uniforms drawn so far),
+ * "obs" f32[n,4].  Get only, of the last step: "p" f32[n,2], "v" f32[n], "u" f64[n] (-1: no draw), "action" i32, "reward"
+ * f64, "done" i32, "cut" i32 (rows of the rollout the step cut, 0: none), "rollout_len" i32 (rows kept for the next one);
+ * and its batch: "batch_rows" i32[1], "batch_x" f32[rows,4], "batch_y_r" f32[rows], "batch_a" f32[rows,2].  y_r and a lie
+ * in the handle's train staging, which every train-type call on the handle (train, compute_grads, evaluate, upload)
+ * overwrites: read the batch before such a call, or what comes back under these two names is that call's rows. */
+int ga3c_dmlp_actors_get(ga3c_dmlp* net, const char* name, void* out, int64_t bytes);
+int ga3c_dmlp_actors_set(ga3c_dmlp* net, const char* name, const void* in, int64_t bytes);
+
 /* ---- DDPG: reference NetworkDDPG.py (USE_DDPG with CONTINUOUS_INPUT), with the replay memory in HBM.
  *   actor   x[B,S] -> actor_fc1 (400) -> actor_norm1 -> relu -> actor_fc2 (300) -> actor_norm2 -> relu -> actor_output (A, tanh)
  *   critic  x -> critic_fc1 (400) -> critic_norm1 -> relu = h;  q = critic_output(relu(h W_fc2 + a W_n2 + b_n2)), W_n2 / b_n2

@@ -1,0 +1,55 @@
+#!/usr/bin/env python3
+"""Development aid: agent steps per second of the device actors (Config.DEVICE_AGENTS, ga3c_dmlp_actors_run)
+with training on -- every step a prediction for N environments, the actor step, the compaction and, when the step cut a
+rollout, a train step on the cut rows.  Wall-clock around ga3c_dmlp_actors_run (the call returns when its steps are done:
+the host reads a row count per step), median and min over rounds, one JSON line per N.  The figure to set it against is the
+PPS of the status line of `_train.sh GAME=CartPole-v0 AGENTS=16` (profiles/device_agents_step.txt).
+usage: python tools/device_agents_step.py [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--agents", type=int, nargs="+", default=[256, 4096])
+    ap.add_argument("--time-max", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=64, help="actor steps per native call (1..64)")
+    ap.add_argument("--calls", type=int, default=8, help="native calls per round")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--no-train", action="store_true")
+    args = ap.parse_args()
+    import ga3c_amd  # noqa: F401
+    from Config import Config
+    from NetworkVP_discrate import Network
+    for n in args.agents:
+        net = Network("gpu:0", "device_agents_step", 2, (4,), max_batch=max(16, n * (args.time_max + 1)), predict_lanes=1)
+        net.learning_rate, net.beta = Config.LEARNING_RATE_START, Config.BETA_START
+        net.actors_create(n, args.time_max, Config.DISCOUNT, Config.RANDOM_SEED)
+        net.actors_run(args.steps, train=not args.no_train)               # warm-up; the rollouts are in step from here on
+        rates, train_calls, rows, episodes = [], 0, 0, 0
+        for _ in range(args.rounds):
+            t0 = time.perf_counter()
+            steps = 0
+            for _ in range(args.calls):
+                s, c, r, e = net.actors_run(args.steps, train=not args.no_train)
+                steps, train_calls, rows, episodes = steps + s, train_calls + c, rows + r, episodes + e
+            rates.append(steps / (time.perf_counter() - t0))
+            net.actors_episodes()
+        rates.sort()
+        per_step_us = 1e6 * n / rates[len(rates) // 2]
+        print(json.dumps({"agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,
+                          "agent_steps_per_s_median": round(rates[len(rates) // 2]), "agent_steps_per_s_min": round(rates[0]),
+                          "agent_steps_per_s_max": round(rates[-1]), "actor_step_us_median": round(per_step_us, 1),
+                          "train_calls": train_calls, "rows_trained": rows, "episodes": episodes, "rounds": args.rounds}),
+              flush=True)
+        net.close()
+
+
+if __name__ == "__main__":
+    main()
