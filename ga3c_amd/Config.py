@@ -69,6 +69,13 @@ class Config:
     REPLAY_BUFFER_SIZE = 1000000
     REPLAY_BUFFER_RANDOM_SEED = 12345
     REPLAY_MIN_QUEUE_SIZE = 2
+    PRIORITIZED_REPLAY = False          # USE_DDPG only: the device draws a train step's rows in proportion to their TD error
+                                        # (Schaul et al. 2016) instead of the replay thread drawing them uniformly; needs
+                                        # DDPG_CRITIC_LOSS = 'paired' and REPLAY_BUFFER_SIZE <= 1048576
+    PRIORITIZED_REPLAY_ALPHA = 0.6      # priority = (|y - q| + eps) ^ alpha: 0 draws uniformly, 1 in proportion to the error
+    PRIORITIZED_REPLAY_BETA_START = 0.4     # exponent of the importance weights (N P(i)) ^ -beta on the critic's loss, annealed
+    PRIORITIZED_REPLAY_BETA_END = 1.0       # over ANNEALING_EPISODE_COUNT episodes as LEARNING_RATE is; 1 undoes the bias
+    PRIORITIZED_REPLAY_EPS = 0.01       # keeps a row with no error drawable
     DDPG_FUTURE_REWARD_CALC = True      # y = r + gamma q' on rows that are not done; False: y = r
     DDPG_CRITIC_LOSS = 'fork'           # 'fork': mean_square(y[B], q[B,1]) broadcasts, the critic regresses on mean(y), as the
                                         # reference computes it; 'paired': (q_i - y_i)^2
@@ -196,6 +203,8 @@ def resolve_ddpg(explicit=()):
     """What USE_DDPG implies (the reference's Config.py:160-178) and what it cannot be combined with here.  Call after
     resolve_action_space.  Without USE_DDPG nothing changes."""
     if not Config.USE_DDPG:
+        if Config.PRIORITIZED_REPLAY:
+            raise ValueError("PRIORITIZED_REPLAY needs USE_DDPG: only the DDPG handle keeps a replay memory")
         return
     if not Config.CONTINUOUS_INPUT:
         raise ValueError("USE_DDPG needs a continuous action space (CONTINUOUS_INPUT); GAME=%s is discrete" % Config.GAME)
@@ -215,6 +224,21 @@ def resolve_ddpg(explicit=()):
                          "batches, as it does in the reference.  Set it, e.g. TRAINING_MIN_BATCH_SIZE=64")
     if Config.REPLAY_BUFFER_SIZE <= Config.TRAINING_MIN_BATCH_SIZE:
         raise ValueError("REPLAY_BUFFER_SIZE must exceed TRAINING_MIN_BATCH_SIZE: a batch is sampled only from more rows than it holds")
+    if Config.PRIORITIZED_REPLAY:
+        if Config.DDPG_CRITIC_LOSS != 'paired':
+            raise ValueError("PRIORITIZED_REPLAY with DDPG_CRITIC_LOSS=%r is not supported: under the fork's loss the critic "
+                             "regresses on the batch mean of y and a row has no TD error of its own.  Set "
+                             "DDPG_CRITIC_LOSS=paired" % (Config.DDPG_CRITIC_LOSS,))
+        if Config.REPLAY_BUFFER_SIZE > 1048576:
+            raise ValueError("PRIORITIZED_REPLAY covers at most 1048576 rows (1024 chunks of 1024): REPLAY_BUFFER_SIZE=%d"
+                             % Config.REPLAY_BUFFER_SIZE)
+        if not 0.0 <= Config.PRIORITIZED_REPLAY_ALPHA <= 1.0:
+            raise ValueError("PRIORITIZED_REPLAY_ALPHA=%r outside [0, 1]" % (Config.PRIORITIZED_REPLAY_ALPHA,))
+        if not Config.PRIORITIZED_REPLAY_EPS > 0.0:
+            raise ValueError("PRIORITIZED_REPLAY_EPS=%r: a number > 0" % (Config.PRIORITIZED_REPLAY_EPS,))
+        if Config.PRIORITIZED_REPLAY_BETA_START < 0.0 or Config.PRIORITIZED_REPLAY_BETA_END < 0.0:
+            raise ValueError("PRIORITIZED_REPLAY_BETA_START / _END = %r / %r: exponents >= 0"
+                             % (Config.PRIORITIZED_REPLAY_BETA_START, Config.PRIORITIZED_REPLAY_BETA_END))
     Config.USE_REPLAY_MEMORY = True
     Config.DISCOUNTING = False
 

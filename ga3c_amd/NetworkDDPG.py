@@ -6,7 +6,8 @@ ga3c_ddpg handle of libga3c_hip.so.
 
 Same interface as NetworkVP.Network where Server, ThreadPredictor and ThreadTrainer use it.  The replay memory lives in
 the handle (replay_add*, train_replay); the Ornstein-Uhlenbeck process too, because the native predictor loops call the
-handle without the interpreter.
+handle without the interpreter.  Under Config.PRIORITIZED_REPLAY the handle also keeps a priority per ring slot and draws a
+step's rows itself (train_prioritized).
 """
 import ctypes as C
 import os
@@ -123,6 +124,11 @@ class Network(NativeHandle):
             self.set_variable_value(k, target[k], TARGET)
         self._log_lock = threading.Lock()
         self.logging = (0.0, 0.0)               # Q_max, Q_avg of the last step (NetworkDDPG.py:98)
+        self.prioritized = bool(Config.PRIORITIZED_REPLAY)
+        self.replay_beta = Config.PRIORITIZED_REPLAY_BETA_START      # exponent of the importance weights; Server.main anneals it
+        if self.prioritized:
+            self._call("priorities_create", float(Config.PRIORITIZED_REPLAY_ALPHA), float(Config.PRIORITIZED_REPLAY_EPS),
+                       int(Config.REPLAY_BUFFER_RANDOM_SEED))
 
     # ---- variables: which = VALUE, TARGET, SLOT_A, SLOT_B (RMSProp ms / mom or Adam m / v), GRAD -----------------------
     def set_global_step(self, step):
@@ -249,6 +255,42 @@ class Network(NativeHandle):
                    float(self.learning_rate), mode, nptr, nat.ptr(q))
         self.logging = (float(q[0]), float(q[1]))
         return self.logging
+
+    # ---- prioritised replay (Config.PRIORITIZED_REPLAY) ---------------------------------------
+    def train_prioritized(self, batch, noise=None):
+        """One step on `batch` rows the handle draws by priority, weighted by (N P(i)) ^ -replay_beta -> (Q_max, Q_avg).
+        The slots it drew are in last_slots afterwards."""
+        mode, nptr, _keep = self._noise_args(noise)
+        q, slots = np.empty(2, np.float32), np.empty(int(batch), np.int32)
+        self._call("train_prioritized", int(batch), float(self.replay_beta), float(self.learning_rate), mode, nptr,
+                   nat.ptr(q), nat.ptr(slots, nat.i32p))
+        self.last_slots = slots
+        self.logging = (float(q[0]), float(q[1]))
+        return self.logging
+
+    def sample_prioritized(self, batch):
+        """One draw and nothing else -> (slots int32 [batch], weights f32 [batch])."""
+        slots, w = np.empty(int(batch), np.int32), np.empty(int(batch), np.float32)
+        self._call("sample_prioritized", int(batch), float(self.replay_beta), nat.ptr(slots, nat.i32p), nat.ptr(w))
+        return slots, w
+
+    def priorities(self):
+        """-> (pa f32 [replay_capacity]: priority ^ alpha by ring slot, max_pa)."""
+        pa, top = np.empty(self.replay_capacity, np.float32), C.c_float()
+        self._call("priorities_get", nat.ptr(pa), C.byref(top))
+        return pa, np.float32(top.value)
+
+    def set_priorities(self, pa, max_pa):
+        pa = nat.as_f32(pa).ravel()
+        if pa.size != self.replay_capacity:
+            raise ValueError("%d priorities for %d ring slots" % (pa.size, self.replay_capacity))
+        self._call("priorities_set", nat.ptr(pa), float(max_pa))
+
+    def time_prioritized(self, batch, iters):
+        """Milliseconds of `iters` resident prioritised steps of `batch` rows."""
+        ms = C.c_float()
+        self._call("time_prioritized", int(batch), int(iters), float(self.replay_beta), float(self.learning_rate), C.byref(ms))
+        return ms.value
 
     def compute(self, x, y_r, a, x2, done, stop_after, noise=None):
         s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)

@@ -313,7 +313,12 @@ class Server:
                 self._count_train_step(agents.shape[0], None, r_, a_, frames=(agents, seqs))
 
     def train_model_replay(self, slots, stamp, trainer_id):
-        """train_model for a batch the replay thread sampled: ring slots, and the ring's row count when they were drawn."""
+        """train_model for a batch the replay thread sampled: ring slots, and the ring's row count when they were drawn.
+        slots None (PRIORITIZED_REPLAY): the model draws the rows itself as it trains, and nothing can be lost."""
+        if slots is None:
+            self.model.train_prioritized(Config.TRAINING_MIN_BATCH_SIZE)
+            self._count_train_step(Config.TRAINING_MIN_BATCH_SIZE, None, None, None)
+            return
         try:
             self.model.train_replay(slots, stamp)
         except nat.StateLost as e:              # a slot was overwritten since (GA3C_ELOST): nothing was trained
@@ -349,6 +354,8 @@ class Server:
             self.dynamic_adjustment.start()
         lr_mult = (Config.LEARNING_RATE_END - Config.LEARNING_RATE_START) / Config.ANNEALING_EPISODE_COUNT
         beta_mult = (Config.BETA_END - Config.BETA_START) / Config.ANNEALING_EPISODE_COUNT
+        replay_beta_mult = ((Config.PRIORITIZED_REPLAY_BETA_END - Config.PRIORITIZED_REPLAY_BETA_START)
+                            / Config.ANNEALING_EPISODE_COUNT)
         t0 = time.time()
         try:
             while self.dp is not None or self.stats.episode_count.value < Config.EPISODES:
@@ -373,6 +380,8 @@ class Server:
                         break
                 else:
                     self.model.learning_rate, self.model.beta = lr, beta
+                    if Config.PRIORITIZED_REPLAY:
+                        self.model.replay_beta = Config.PRIORITIZED_REPLAY_BETA_START + replay_beta_mult * step
                     if timed_out:
                         break
                 time.sleep(0.01)

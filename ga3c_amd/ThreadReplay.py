@@ -11,6 +11,10 @@ sampled.  The model's train_replay refuses a batch one of whose slots has been w
 and counts it), so a row is never trained on after it was overwritten; ring writes and train steps are ordered on the
 handle's one stream, so a row is never read half written either.
 
+Under Config.PRIORITIZED_REPLAY the thread draws nothing: under the same two rules it queues the token (None, total), and the
+trainer that takes it calls the model's train_prioritized, which draws the rows on the device by their priorities at the
+moment it trains.  No slot is named ahead of time, so no batch can be lost, and self.random is never used.
+
 Rollout rows are `s | s2 | done | padding` in f32 (ProcessAgent._ship), returns carry the un-accumulated rewards
 (DISCOUNTING = False).  With zero-copy intake the device reads the rows where they lie and the slot goes back to the agents
 when replay_add_offsets returns, which is after the device has read them.  The thread holds one rollout at a time.
@@ -60,10 +64,13 @@ class ThreadReplay(Thread):
             report(type(self).__name__, e)
 
     def sample(self):
-        """-> (slots, stamp) of one batch, or None while the memory does not hold MORE than a batch."""
+        """-> (slots, stamp) of one batch, or None while the memory does not hold MORE than a batch.  PRIORITIZED_REPLAY:
+        (None, stamp), the device draws."""
         k = Config.TRAINING_MIN_BATCH_SIZE
         if not self.size > k:
             return None
+        if Config.PRIORITIZED_REPLAY:
+            return None, self.total
         return ring_slots(self.random.sample(range(self.size), k), self.total, self.capacity), self.total
 
     def add(self, slot):

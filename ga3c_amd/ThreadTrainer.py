@@ -43,7 +43,8 @@ class ThreadTrainer(Thread):
             report("%s %d" % (type(self).__name__, self.id), e)
 
     def _run_replay(self):
-        """USE_DDPG: ready batches come from the replay thread (ThreadTrainer.py:45-46 of the reference) as ring slots."""
+        """USE_DDPG: ready batches come from the replay thread (ThreadTrainer.py:45-46 of the reference) as ring slots, or as
+        (None, stamp) under PRIORITIZED_REPLAY: train_model_replay then lets the model draw the rows (train_prioritized)."""
         while not self.exit_flag:
             try:
                 slots, stamp = self.server.replay_q.get(timeout=Config.QUEUE_TIMEOUT_MS / 1000.0)

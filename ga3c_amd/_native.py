@@ -185,6 +185,14 @@ HIP_SIGNATURES = {
                                     f32p]),
     "ga3c_ddpg_fetch": (C.c_int, [C.c_void_p, C.c_char_p, f32p, C.c_int64]),
     "ga3c_ddpg_time_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, f32p]),
+    # prioritised replay of a DDPG handle (Config.PRIORITIZED_REPLAY), include/ga3c_abi.h
+    "ga3c_ddpg_priorities_create": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int64]),
+    "ga3c_ddpg_priorities_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_priorities_get": (C.c_int, [C.c_void_p, f32p, f32p]),
+    "ga3c_ddpg_priorities_set": (C.c_int, [C.c_void_p, f32p, C.c_float]),
+    "ga3c_ddpg_sample_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, i32p, f32p]),
+    "ga3c_ddpg_train_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, f32p, f32p, i32p]),
+    "ga3c_ddpg_time_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

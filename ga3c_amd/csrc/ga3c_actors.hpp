@@ -19,7 +19,7 @@
 // What the step restates is ProcessAgent.run_episode / run over EnvironmentCart.Environment with ga3c_returns_fork and
 // ga3c_select_action (ga3c_host.cpp); tests/device_agents_oracle.py is the same statement in numpy.  The f64 arithmetic is
 // compiled with contraction off, as the host library's is.  The uniforms are the one deviation: a stateless function of
-// (seed, environment, draw number), actor_uniform below.
+// (seed, environment, draw number), actor_uniform (ga3c_uniform.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +32,7 @@
 #include <utility>
 #include <vector>
 
+#include "ga3c_uniform.hpp"
 #include "ga3c_vecnet.hpp"
 
 namespace ga3c_actors {
@@ -42,20 +43,8 @@ constexpr int STEP_THREADS = 256;
 constexpr int SCAN_THREADS = 1024;
 constexpr int MAX_STEPS = GA3C_ACTORS_MAX_STEPS;     // actor steps of one actors_run call: bounds the episode ring
 
-// splitmix64's finalizer
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// Uniform number `draw` of environment `env` under `seed`: 53 bits to a double in [0, 1).  All sums wrap at 2^64.
-__host__ __device__ inline double actor_uniform(uint64_t seed, uint64_t env, uint64_t draw) {
-  const uint64_t golden = 0x9E3779B97F4A7C15ull;
-  const uint64_t stream = mix64(seed + golden * (env + 1));
-  const uint64_t bits = mix64(stream + golden * (draw + 1));
-  return (double)(bits >> 11) * 0x1.0p-53;
-}
+using ga3c_uniform::actor_uniform;          // u(seed, environment, draw number), shared with prioritised replay
+using ga3c_uniform::mix64;
 
 // ga3c_select_action (ga3c_host.cpp): sequential f64 cumulative sum of the f32 policy, the first index with
 // u < cdf[i] / cdf[n - 1], clamped to n - 1.  The sum is run twice instead of being kept: the same additions, the same bits.

@@ -16,9 +16,16 @@
 //   ddpg_predict_kernel  the online actor alone
 //   ddpg_ring_gather_kernel  rows of the registered transport into ring slots
 // A train step is 5 launches (6 with clipping); its rows are named by ring slot and read where they lie.
+// Prioritised replay (ga3c_ddpg_priorities_create; tests/per_oracle.py is the same statement in numpy):
+//   per_fill_kernel       new rows get the largest priority seen
+//   per_chunk_sum_kernel  one f64 sum per 1024 slots, in a fixed order
+//   per_sample_kernel     one workgroup: scan of the chunk sums, the stratified draw, the importance weights
+//   per_update_kernel     one workgroup: pa[slot] = (|y - q| + eps)^alpha from the critic kernel's y and q
+// A prioritised step is 8 launches (9 with clipping) and draws its own rows: no host draw, no stamp, nothing to lose.
 #include <cmath>
 #include <new>
 
+#include "ga3c_uniform.hpp"
 #include "ga3c_vecnet.hpp"
 
 namespace ga3c_dd {
@@ -32,6 +39,7 @@ constexpr int THREADS = 448;                 // 7 waves: a 300-wide layer and th
 constexpr int RED = 512;                     // the power of two above it, for the fixed-order trees
 constexpr int MAX_S = 64;
 constexpr int MAX_A = 32;
+constexpr int MAX_B = 4096;                  // rows of a step: per_update_kernel holds their slots in LDS
 constexpr int H1 = 400;
 constexpr int H2 = 300;
 constexpr float BN_EPS = 1e-5f;
@@ -292,8 +300,9 @@ __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(Layout L, const fl
   }
 }
 
+// per_w (null without priorities): the rows' importance weights, dq_i = (2/B) w_i (q_i - y_i)
 __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const float* __restrict__ th, Rows src, int B, int paired,
-                                                              Work w) {
+                                                              const float* __restrict__ per_w, Work w) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
@@ -326,6 +335,7 @@ __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const fl
     if (r < nrows) {
       const float ref = paired ? w.y[row0 + r] : ymean;
       dq = (2.0f / (float)B) * (qv[r] - ref);
+      if (per_w) dq *= per_w[row0 + r];
       w.q[row0 + r] = qv[r];
       w.dq[row0 + r] = dq;
     }
@@ -552,6 +562,141 @@ __global__ void ddpg_ring_gather_kernel(const char* __restrict__ seg, const int6
   ring[((first + i) % cap) * rowf + c] = v;
 }
 
+// ------------------------------------------------------------------ prioritised replay
+constexpr int PER_CHUNK = 1024;              // slots of one chunk sum
+constexpr int PER_SUM_THREADS = 256;
+constexpr int PER_THREADS = 1024;            // the one-workgroup kernels; also the most chunks a ring may have
+constexpr int PER_WALK = 32;                 // slots a walk loads ahead of its additions (pa holds whole chunks)
+
+using ga3c_uniform::actor_uniform;
+
+// pa of the n slots from `first` on (mod cap) <- max_pa: a row nobody has trained on yet is as urgent as any seen.  n <= cap.
+__global__ void per_fill_kernel(float* __restrict__ pa, const float* __restrict__ max_pa, int64_t first, int n, int64_t cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) pa[(first + i) % cap] = *max_pa;
+}
+
+// csum[c] = the f64 sum of chunk c's slots below `size`: thread t adds slots t, t + 256, t + 512, t + 768 in that order, the
+// 256 partials fold by the halving tree.
+__global__ __launch_bounds__(PER_SUM_THREADS) void per_chunk_sum_kernel(const float* __restrict__ pa, int size,
+                                                                        double* __restrict__ csum) {
+  __shared__ double red[PER_SUM_THREADS];
+  const int t = threadIdx.x, base = blockIdx.x * PER_CHUNK;
+  double s = 0.0;
+  for (int k = 0; k < PER_CHUNK / PER_SUM_THREADS; ++k) {
+    const int j = base + t + k * PER_SUM_THREADS;
+    s += j < size ? (double)pa[j] : 0.0;
+  }
+  red[t] = s;
+  __syncthreads();
+  for (int h = PER_SUM_THREADS / 2; h > 0; h >>= 1) {
+    if (t < h) red[t] += red[t + h];
+    __syncthreads();
+  }
+  if (t == 0) csum[blockIdx.x] = red[0];
+}
+
+// w of row k before the batch's largest divides it: (size pa / total)^-beta
+__device__ __forceinline__ double per_weight(float pa, int size, double total, double beta) {
+  return pow((double)size * (double)pa / total, -beta);
+}
+
+// One workgroup.  The inclusive Hillis-Steele scan of the chunk sums (actors_compact_kernel's pattern, in f64), then row k
+// of the batch: target = (k + u(seed, number, k)) total / B, the first chunk whose scanned sum exceeds it (the last if none
+// does), and within it the first slot at which the running sum, started from the chunk before, exceeds it (the chunk's last
+// slot below `size` if none does: the tree and the walk associate differently).  Every addition is tests/per_oracle.py's.
+__global__ __launch_bounds__(PER_THREADS) void per_sample_kernel(const float* __restrict__ pa, const double* __restrict__ csum,
+                                                                 int size, int B, uint64_t seed, uint64_t number, double beta,
+                                                                 int32_t* __restrict__ slots, float* __restrict__ w) {
+#pragma clang fp contract(off)
+  __shared__ double x[PER_THREADS];
+  __shared__ double wm[PER_THREADS];
+  const int t = threadIdx.x;
+  const int nchunks = (size + PER_CHUNK - 1) / PER_CHUNK;
+  x[t] = t < nchunks ? csum[t] : 0.0;
+  __syncthreads();
+  for (int d = 1; d < PER_THREADS; d <<= 1) {
+    const double v = t >= d ? x[t - d] : 0.0;
+    __syncthreads();
+    if (t >= d) x[t] += v;
+    __syncthreads();
+  }
+  const double total = x[nchunks - 1], seg = total / (double)B;
+  double mx = 0.0;
+  for (int k = t; k < B; k += PER_THREADS) {
+    const double target = ((double)k + actor_uniform(seed, number, (uint64_t)k)) * seg;
+    int c = nchunks - 1;
+    for (int i = 0; i < nchunks; ++i)
+      if (target < x[i]) {
+        c = i;
+        break;
+      }
+    const int lo = c * PER_CHUNK, hi = min(size, lo + PER_CHUNK);
+    double acc = c ? x[c - 1] : 0.0;
+    int slot = hi - 1;
+    bool hit = false;
+    for (int j0 = lo; j0 < hi && !hit; j0 += PER_WALK) {
+      f32x4 v[PER_WALK / 4];                 // the walk waits on memory, not on its additions: one wait per 32 slots
+#pragma unroll
+      for (int i = 0; i < PER_WALK / 4; ++i) v[i] = reinterpret_cast<const f32x4*>(pa + j0)[i];
+#pragma unroll
+      for (int i = 0; i < PER_WALK; ++i)
+        if (!hit && j0 + i < hi) {
+          acc += (double)v[i / 4][i % 4];
+          if (target < acc) {
+            slot = j0 + i;
+            hit = true;
+          }
+        }
+    }
+    slots[k] = slot;
+    mx = fmax(mx, per_weight(pa[slot], size, total, beta));
+  }
+  wm[t] = mx;
+  __syncthreads();
+  for (int h = PER_THREADS / 2; h > 0; h >>= 1) {
+    if (t < h) wm[t] = fmax(wm[t], wm[t + h]);
+    __syncthreads();
+  }
+  const double largest = wm[0];
+  for (int k = t; k < B; k += PER_THREADS) w[k] = (float)(per_weight(pa[slots[k]], size, total, beta) / largest);
+}
+
+// One workgroup, after ddpg_critic_kernel: td_i = |y_i - q_i|, pa[slot_i] = (td_i + eps)^alpha, max_pa = max(max_pa, every
+// new priority).  The batch's slots lie in LDS and row i stores only if no later row names its slot: the last row in batch
+// order wins and no two rows store to one slot.  B <= MAX_B.
+__global__ __launch_bounds__(PER_THREADS) void per_update_kernel(const int32_t* __restrict__ slots, const float* __restrict__ q,
+                                                                 const float* __restrict__ y, int B, float eps, float alpha,
+                                                                 float* __restrict__ pa, float* __restrict__ max_pa,
+                                                                 float* __restrict__ td) {
+  __shared__ int32_t sl[MAX_B];
+  __shared__ float red[PER_THREADS];
+  const int t = threadIdx.x;
+  for (int i = t; i < B; i += PER_THREADS) sl[i] = slots[i];
+  __syncthreads();
+  float mx = 0.f;
+  for (int i = t; i < B; i += PER_THREADS) {
+    const float d = fabsf(y[i] - q[i]);
+    td[i] = d;
+    const float p = powf(d + eps, alpha);
+    mx = fmaxf(mx, p);
+    bool last = true;
+    for (int j = i + 1; j < B; ++j)
+      if (sl[j] == sl[i]) {
+        last = false;
+        break;
+      }
+    if (last) pa[sl[i]] = p;
+  }
+  red[t] = mx;
+  __syncthreads();
+  for (int h = PER_THREADS / 2; h > 0; h >>= 1) {
+    if (t < h) red[t] = fmaxf(red[t], red[t + h]);
+    __syncthreads();
+  }
+  if (t == 0) *max_pa = fmaxf(*max_pa, red[0]);
+}
+
 // ------------------------------------------------------------------ host side
 // The handle is a ga3c_vecnet::Core (ga3c_vecnet.hpp): stream, lanes, arenas, variables by name, checkpoint and registered
 // segment are the shared ones.  Its own: the train step, the replay ring, the noise.
@@ -587,6 +732,18 @@ using namespace ga3c_dd;
 namespace vn = ga3c_vecnet;
 using vn::fail;                   // HIPCHK's
 
+// Prioritised replay of a handle (ga3c_ddpg_priorities_create).  pa holds a whole number of chunks, zero beyond the rows written.
+struct Per {
+  float alpha = 0.f, eps = 0.f;
+  uint64_t seed = 0, samples = 0;       // the draw of sample number n is u(seed, n, row)
+  float* pa = nullptr;                  // [capacity] priority ^ alpha by slot
+  float* max_pa = nullptr;              // device f32: starts at 1, never decreases
+  double* csum = nullptr;               // [PER_THREADS] chunk sums
+  int32_t* slots = nullptr; float* w = nullptr; float* td = nullptr;     // [max_batch]: the last draw, its weights, the last |y - q|
+  int32_t* h_slots = nullptr; float* h_w = nullptr;                      // pinned
+  int w_rows = 0, td_rows = 0;          // rows of the last draw / prioritised step (fetch)
+};
+
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
   ga3c_ddpg_config cfg;
   Layout L;
@@ -606,6 +763,7 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   hipEvent_t aev = nullptr;
   NormalGen gen;
   std::vector<float> ou_x;
+  Per* per = nullptr;             // null: no priorities, and every path is the one it was without them
 };
 
 namespace {
@@ -694,7 +852,7 @@ int make_noise(ga3c_ddpg* m, int mode, const float* given, Noise* nz) {
 }
 
 // Steps 1 .. stop_after of train_DDPG on `rows` (caller holds train_mu and mu).  stop_after 6: the whole step.
-int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after) {
+int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w = nullptr) {
   const ga3c_ddpg_config& c = m->cfg;
   const int64_t t = m->step.load() + 1;
   const bool full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
@@ -702,7 +860,7 @@ int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& n
   hipLaunchKernelGGL(ddpg_target_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[1], rows, B, c.gamma,
                      (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, m->w);
   hipLaunchKernelGGL(ddpg_critic_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B,
-                     (c.flags & GA3C_DDPG_LOSS_PAIRED) ? 1 : 0, m->w);
+                     (c.flags & GA3C_DDPG_LOSS_PAIRED) ? 1 : 0, per_w, m->w);
   const GradSrc gs = grad_src(m);
   const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
   const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
@@ -819,7 +977,18 @@ void fill_vars(ga3c_ddpg* m) {
   m->n = L.off[NVARS];
 }
 
+void per_free(ga3c_ddpg* m) {
+  Per* p = m->per;
+  if (!p) return;
+  (void)hipFree(p->pa); (void)hipFree(p->max_pa); (void)hipFree(p->csum); (void)hipFree(p->slots); (void)hipFree(p->w);
+  (void)hipFree(p->td); (void)hipHostFree(p->h_slots); (void)hipHostFree(p->h_w);
+  (void)hipGetLastError();
+  delete p;
+  m->per = nullptr;
+}
+
 void free_all(ga3c_ddpg* m) {
+  per_free(m);
   vn::free_core(m);
   (void)hipFree(m->work_base);
   (void)hipFree(m->ring);
@@ -872,6 +1041,49 @@ int ring_copy_in(ga3c_ddpg* m, const float* src, int n, hipMemcpyKind kind) {
   return GA3C_OK;
 }
 
+int64_t ring_size(const ga3c_ddpg* m) { return std::min<int64_t>(m->ring_total, m->cfg.replay_capacity); }
+
+// The n rows just written from slot `first` on get max_pa (caller holds mu; right after the ring write, on its stream).
+void per_fill(ga3c_ddpg* m, int64_t first, int64_t n) {
+  if (!m->per || n < 1) return;
+  hipLaunchKernelGGL(per_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->st, m->per->pa,
+                     (const float*)m->per->max_pa, first, (int)n, (int64_t)m->cfg.replay_capacity);
+}
+
+// Sample number per->samples: B slots and their weights into per->slots / per->w (caller holds mu; the ring holds a row).
+void per_enqueue_sample(ga3c_ddpg* m, int B, float beta) {
+  Per* p = m->per;
+  const int size = (int)ring_size(m);
+  hipLaunchKernelGGL(per_chunk_sum_kernel, dim3((size + PER_CHUNK - 1) / PER_CHUNK), dim3(PER_SUM_THREADS), 0, m->st,
+                     (const float*)p->pa, size, p->csum);
+  hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(PER_THREADS), 0, m->st, (const float*)p->pa, (const double*)p->csum, size, B,
+                     p->seed, p->samples, (double)beta, p->slots, p->w);
+  ++p->samples;
+  p->w_rows = B;
+}
+
+// One prioritised step: the draw, train_DDPG on its slots with its weights, the new priorities (caller holds train_mu and mu).
+int per_enqueue_step(ga3c_ddpg* m, int B, float beta, float lr, const Noise& nz) {
+  Per* p = m->per;
+  per_enqueue_sample(m, B, beta);
+  CHK(enqueue_step(m, Rows{m->ring, p->slots, m->rowf}, B, lr, nz, 6, p->w));
+  hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(PER_THREADS), 0, m->st, (const int32_t*)p->slots, (const float*)m->w.q,
+                     (const float*)m->w.y, B, p->eps, p->alpha, p->pa, p->max_pa, p->td);
+  HIPCHK(hipGetLastError());
+  p->td_rows = B;
+  return GA3C_OK;
+}
+
+int per_check(const ga3c_ddpg* m, const char* what) {
+  if (!m->per) return fail(GA3C_ESTATE, "%s: the handle has no priorities (ga3c_ddpg_priorities_create)", what);
+  return GA3C_OK;
+}
+
+int per_check_beta(float beta) {
+  if (!(beta >= 0.f) || std::isinf(beta)) return fail(GA3C_EINVAL, "beta_is %g: a finite exponent >= 0", beta);
+  return GA3C_OK;
+}
+
 void ring_report(ga3c_ddpg* m, int64_t* size, int64_t* total) {
   if (size) *size = std::min<int64_t>(m->ring_total, m->cfg.replay_capacity);
   if (total) *total = m->ring_total;
@@ -884,7 +1096,7 @@ extern "C" {
 int ga3c_ddpg_create(const ga3c_ddpg_config* cfg, ga3c_ddpg** out) {
   if (!cfg || !out) return fail(GA3C_EINVAL, "null argument");
   *out = nullptr;
-  CHK(vn::check_dims(*cfg, MAX_S, MAX_A, 4096));
+  CHK(vn::check_dims(*cfg, MAX_S, MAX_A, MAX_B));
   if (cfg->replay_capacity < 1 || cfg->replay_capacity > (1 << 26))
     return fail(GA3C_EINVAL, "replay_capacity %d outside [1,%d]", cfg->replay_capacity, 1 << 26);
   if (cfg->flags & ~(uint32_t)(GA3C_DDPG_FUTURE_REWARD | GA3C_DDPG_LOSS_PAIRED | GA3C_DDPG_GRAD_CLIP | GA3C_DDPG_CRITIC_ADAM |
@@ -1043,6 +1255,8 @@ int ga3c_ddpg_replay_add(ga3c_ddpg* m, const float* s, const float* a, const flo
   {
     std::lock_guard<std::mutex> lk(m->mu);
     CHK(ring_copy_in(m, m->h_add, n, hipMemcpyHostToDevice));
+    per_fill(m, m->ring_total % m->cfg.replay_capacity, n);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->aev, m->st));
     m->ring_total += n;
     ring_report(m, size, total);
@@ -1072,6 +1286,7 @@ int ga3c_ddpg_replay_add_gather(ga3c_ddpg* m, const int64_t* offsets, const floa
     hipLaunchKernelGGL(ddpg_ring_gather_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, m->st, m->reg_dev,
                        (const int64_t*)m->d_aoff, (const float*)m->d_ar, (const float*)m->d_aa, n, m->ring, m->ring_total % cap, cap,
                        S, A);
+    per_fill(m, m->ring_total % cap, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->aev, m->st));
     m->ring_total += n;
@@ -1159,6 +1374,18 @@ int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
   std::vector<float**> ptrs;
   std::vector<size_t> widths;
   work_table(m, &ptrs, &widths);
+  const bool per_w = strcmp(name, "per_w") == 0;
+  if (per_w || strcmp(name, "per_td") == 0) {       // of the last draw / the last prioritised step, whatever ran since
+    HIPCHK(hipSetDevice(m->device));
+    std::lock_guard<std::mutex> tl(m->train_mu);
+    std::lock_guard<std::mutex> lk(m->mu);
+    CHK(per_check(m, name));
+    const int rows = per_w ? m->per->w_rows : m->per->td_rows;
+    if (count != rows) return fail(GA3C_EINVAL, "%s holds %d floats, not %lld", name, rows, (long long)count);
+    HIPCHK(hipStreamSynchronize(m->st));
+    HIPCHK(hipMemcpy(out, per_w ? m->per->w : m->per->td, sizeof(float) * count, hipMemcpyDeviceToHost));
+    return GA3C_OK;
+  }
   for (int i = 0; i < NWORK; ++i)
     if (strcmp(name, WORK_NAMES[i]) == 0) return vn::fetch(m, name, *ptrs[i], (int64_t)widths[i], out, count);
   return fail(GA3C_EINVAL, "no buffer named %s", name);
@@ -1191,6 +1418,167 @@ int ga3c_ddpg_time_resident(ga3c_ddpg* m, int32_t mode, int32_t batch, int32_t i
       }
     }
     HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->t1, m->st));
+    m->last_B = batch;
+  }
+  HIPCHK(hipEventSynchronize(m->t1));
+  HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
+  return GA3C_OK;
+}
+
+// ---- prioritised replay
+
+int ga3c_ddpg_priorities_create(ga3c_ddpg* m, float alpha, float eps, int64_t seed) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (!(alpha >= 0.f && alpha <= 1.f)) return fail(GA3C_EINVAL, "alpha %g outside [0,1]", alpha);
+  if (!(eps > 0.f) || std::isinf(eps)) return fail(GA3C_EINVAL, "eps %g: a finite number > 0", eps);
+  if (m->cfg.replay_capacity > PER_THREADS * PER_CHUNK)
+    return fail(GA3C_EINVAL, "replay_capacity %d: priorities cover at most %d slots (%d chunks of %d)", m->cfg.replay_capacity,
+                PER_THREADS * PER_CHUNK, PER_THREADS, PER_CHUNK);
+  if (!(m->cfg.flags & GA3C_DDPG_LOSS_PAIRED))
+    return fail(GA3C_ESTATE, "priorities need GA3C_DDPG_LOSS_PAIRED: under the fork's loss the critic regresses on mean(y) "
+                             "and a row has no TD error of its own");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (m->per) return fail(GA3C_ESTATE, "the handle has priorities already");
+  Per* p = new (std::nothrow) Per();
+  if (!p) return fail(GA3C_EINVAL, "out of host memory");
+  m->per = p;
+  p->alpha = alpha;
+  p->eps = eps;
+  p->seed = (uint64_t)seed;
+  const size_t cap = (size_t)m->cfg.replay_capacity, B = (size_t)m->cfg.max_batch;
+  const size_t padded = (cap + PER_CHUNK - 1) / PER_CHUNK * PER_CHUNK;
+  const float one = 1.0f;
+  auto build = [&]() -> int {
+    CHK(vn::dalloc(&p->pa, padded)); CHK(vn::dalloc(&p->max_pa, 1)); CHK(vn::dalloc(&p->csum, PER_THREADS));
+    CHK(vn::dalloc(&p->slots, B)); CHK(vn::dalloc(&p->w, B)); CHK(vn::dalloc(&p->td, B));
+    CHK(vn::halloc(&p->h_slots, B)); CHK(vn::halloc(&p->h_w, B));
+    HIPCHK(hipMemsetAsync(p->pa, 0, sizeof(float) * padded, m->st));
+    HIPCHK(hipMemsetAsync(p->csum, 0, sizeof(double) * PER_THREADS, m->st));
+    HIPCHK(hipMemsetAsync(p->w, 0, sizeof(float) * B, m->st));
+    HIPCHK(hipMemsetAsync(p->td, 0, sizeof(float) * B, m->st));
+    HIPCHK(hipMemsetAsync(p->slots, 0, sizeof(int32_t) * B, m->st));
+    HIPCHK(hipMemcpyAsync(p->max_pa, &one, sizeof(float), hipMemcpyHostToDevice, m->st));
+    per_fill(m, 0, ring_size(m));                  // rows the ring holds already: max_pa = 1
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->st));
+    return GA3C_OK;
+  };
+  const int rc = build();
+  if (rc != GA3C_OK) per_free(m);
+  return rc;
+}
+
+int ga3c_ddpg_priorities_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  CHK(per_check(m, "priorities_destroy"));
+  HIPCHK(hipStreamSynchronize(m->st));
+  per_free(m);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_priorities_get(ga3c_ddpg* m, float* pa, float* max_pa) {
+  if (!m || !pa || !max_pa) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  CHK(per_check(m, "priorities_get"));
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipMemcpy(pa, m->per->pa, sizeof(float) * (size_t)m->cfg.replay_capacity, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(max_pa, m->per->max_pa, sizeof(float), hipMemcpyDeviceToHost));
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_priorities_set(ga3c_ddpg* m, const float* pa, float max_pa) {
+  if (!m || !pa) return fail(GA3C_EINVAL, "null argument");
+  if (!(max_pa > 0.f) || std::isinf(max_pa)) return fail(GA3C_EINVAL, "max_pa %g: a finite number > 0", max_pa);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  CHK(per_check(m, "priorities_set"));
+  const int64_t cap = m->cfg.replay_capacity, size = ring_size(m);
+  for (int64_t i = 0; i < cap; ++i) {
+    if (!(pa[i] >= 0.f) || std::isinf(pa[i])) return fail(GA3C_EINVAL, "pa[%lld] = %g: negative or not a number", (long long)i, pa[i]);
+    if (i < size && pa[i] == 0.f) return fail(GA3C_EINVAL, "pa[%lld] = 0 in a slot that holds a row: it could never be drawn", (long long)i);
+  }
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipMemcpy(m->per->pa, pa, sizeof(float) * (size_t)cap, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(m->per->max_pa, &max_pa, sizeof(float), hipMemcpyHostToDevice));
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_sample_prioritized(ga3c_ddpg* m, int32_t batch, float beta_is, int32_t* slots, float* weights) {
+  if (!m || !slots || !weights) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    CHK(per_check(m, "sample_prioritized"));
+    CHK(vn::check_batch(m, batch));
+    CHK(per_check_beta(beta_is));
+    if (ring_size(m) < 1) return fail(GA3C_ESTATE, "the ring holds no row");
+    per_enqueue_sample(m, batch, beta_is);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(m->per->h_slots, m->per->slots, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipMemcpyAsync(m->per->h_w, m->per->w, sizeof(float) * batch, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipEventRecord(m->tev, m->st));
+  }
+  HIPCHK(hipEventSynchronize(m->tev));
+  memcpy(slots, m->per->h_slots, sizeof(int32_t) * batch);      // (train_mu is held: priorities_destroy waits)
+  memcpy(weights, m->per->h_w, sizeof(float) * batch);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_train_prioritized(ga3c_ddpg* m, int32_t batch, float beta_is, float learning_rate, int32_t noise_mode,
+                                const float* noise, float* q_stats, int32_t* out_slots) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    CHK(per_check(m, "train_prioritized"));
+    CHK(vn::check_batch(m, batch));
+    CHK(per_check_beta(beta_is));
+    if (!(ring_size(m) > batch))                  // ThreadReplay.sample's rule: a batch is drawn from MORE rows than it holds
+      return fail(GA3C_ESTATE, "batch %d: the ring holds %lld rows, not more than a batch", batch, (long long)ring_size(m));
+    Noise nz;
+    CHK(make_noise(m, noise_mode, noise, &nz));
+    CHK(per_enqueue_step(m, batch, beta_is, learning_rate, nz));
+    if (out_slots) HIPCHK(hipMemcpyAsync(m->per->h_slots, m->per->slots, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, m->st));
+    CHK(finish_step(m));
+    m->last_B = batch;
+  }
+  HIPCHK(hipEventSynchronize(m->tev));
+  if (q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  if (out_slots) memcpy(out_slots, m->per->h_slots, sizeof(int32_t) * batch);
+  m->step.fetch_add(1);
+  return GA3C_OK;
+}
+
+// As ga3c_ddpg_time_resident's mode 1, with every step drawing its own rows.
+int ga3c_ddpg_time_prioritized(ga3c_ddpg* m, int32_t batch, int32_t iters, float beta_is, float learning_rate, float* elapsed_ms) {
+  if (!m || !elapsed_ms || iters < 1) return fail(GA3C_EINVAL, "bad argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    CHK(per_check(m, "time_prioritized"));
+    CHK(vn::check_batch(m, batch));
+    CHK(per_check_beta(beta_is));
+    if (!(ring_size(m) > batch))
+      return fail(GA3C_ESTATE, "batch %d: the ring holds %lld rows, not more than a batch", batch, (long long)ring_size(m));
+    Noise nz;
+    memset(&nz, 0, sizeof nz);
+    HIPCHK(hipEventRecord(m->t0, m->st));
+    for (int i = 0; i < iters; ++i) {
+      CHK(per_enqueue_step(m, batch, beta_is, learning_rate, nz));
+      m->step.fetch_add(1);
+    }
     HIPCHK(hipEventRecord(m->t1, m->st));
     m->last_B = batch;
   }

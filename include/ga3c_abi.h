@@ -631,6 +631,37 @@ int ga3c_ddpg_fetch(ga3c_ddpg* net, const char* name, float* out, int64_t count)
  * both on slots 0 .. batch-1 (the ring must hold them), without noise. */
 int ga3c_ddpg_time_resident(ga3c_ddpg* net, int32_t mode, int32_t batch, int32_t iters, float learning_rate, float* elapsed_ms);
 
+/* ---- Proportional prioritised replay on a DDPG handle (Config.PRIORITIZED_REPLAY; tests/per_oracle.py states it
+ * addition by addition).  Attached to a created handle by a call of its own, as the device actors are; a handle without
+ * priorities runs what it ran before, and every call below returns GA3C_ESTATE on it (as fetch does for "per_w" / "per_td").
+ * State: pa[capacity], a slot's priority raised to alpha (0 in a slot never written), max_pa (1 at first, never smaller) and
+ * a sample counter.  replay_add* give the slots they write max_pa; rows the ring holds at create get 1.
+ * A draw of B rows: the f64 sums of the chunks of 1024 slots, their scan, and per row k the slot at which the running sum
+ * first exceeds (k + u(seed, sample number, k)) total / B, u the device actors' counter uniforms with the sample number in the
+ * environment's place; a slot may come up more than once.  w_k = (size pa / total)^-beta_is over the batch's largest.
+ * A step trains with dL/dq_i = (2/B) w_i (q_i - y_i) and then sets pa[slot_i] = (|y_i - q_i| + eps)^alpha, the last row in
+ * batch order where a slot occurs twice, and max_pa = max(max_pa, every new priority).  8 launches (9 with
+ * GA3C_DDPG_GRAD_CLIP) on the handle's stream and one wait; no stamp, and nothing can be lost.
+ * create: GA3C_EINVAL for alpha outside [0,1], eps <= 0, a NaN, or replay_capacity > 1048576 (1024 chunks); GA3C_ESTATE on a
+ * second create and on a handle without GA3C_DDPG_LOSS_PAIRED (under the fork's loss a row has no TD error of its own).
+ * destroy: also done by ga3c_ddpg_destroy.  Checkpoints carry no priorities, as they carry no ring. */
+int ga3c_ddpg_priorities_create(ga3c_ddpg* net, float alpha, float eps, int64_t seed);
+int ga3c_ddpg_priorities_destroy(ga3c_ddpg* net);
+/* For tests.  set refuses a negative or NaN entry, a zero in a slot that holds a row, and max_pa <= 0 (GA3C_EINVAL). */
+int ga3c_ddpg_priorities_get(ga3c_ddpg* net, float* pa, float* max_pa);
+int ga3c_ddpg_priorities_set(ga3c_ddpg* net, const float* pa, float max_pa);
+/* One draw: advances the sample counter and does nothing else.  1 <= batch <= max_batch, beta_is >= 0, and the ring holds a
+ * row (GA3C_ESTATE otherwise). */
+int ga3c_ddpg_sample_prioritized(ga3c_ddpg* net, int32_t batch, float beta_is, int32_t* slots, float* weights);
+/* The draw and the step in one call; out_slots (may be null) gets the slots.  GA3C_ESTATE unless the ring holds MORE than
+ * `batch` rows (ThreadReplay.sample's rule).  Afterwards fetch knows "per_w" [B] (the last draw's weights, of
+ * sample_prioritized too) and "per_td" [B] = |y - q| beside the names above. */
+int ga3c_ddpg_train_prioritized(ga3c_ddpg* net, int32_t batch, float beta_is, float learning_rate, int32_t noise_mode,
+                                const float* noise, float* q_stats, int32_t* out_slots);
+/* `iters` prioritised steps between two events on the handle's stream -> milliseconds, without noise. */
+int ga3c_ddpg_time_prioritized(ga3c_ddpg* net, int32_t batch, int32_t iters, float beta_is, float learning_rate,
+                               float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif
