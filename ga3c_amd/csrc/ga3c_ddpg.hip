@@ -6,7 +6,8 @@
 //   critic  x -> critic_fc1 (400) -> critic_norm1 -> relu = h;  q = critic_output(relu(h W_fc2 + a W_n2 + b_n2))
 //   batch normalisation: gamma (x - moving_mean) / sqrt(moving_variance + 1e-5) + beta (bn_apply below, the one place)
 //
-// Kernels (all f32, one workgroup of 448 threads per 16-row tile, activations in LDS as [width][16], weights through L2):
+// Kernels (all f32, one workgroup of 448 threads per 16-row tile, weights through L2; the tile's layout in LDS, dense_fwd,
+// load_input_tile and the fixed-order block_sum are ga3c_tile.hpp's):
 //   ddpg_target_kernel   steps 1-2: actor_target and critic_target on s2, y = r or r + gamma q'
 //   ddpg_critic_kernel   step 3's forward and backward on (s, a): q, dq (either loss form) and the deltas, to HBM
 //   ddpg_wgrad_kernel    one thread per element of a net's trainable variables sums its gradient over the rows in row order
@@ -25,18 +26,17 @@
 #include <cmath>
 #include <new>
 
+#include "ga3c_tile.hpp"
 #include "ga3c_uniform.hpp"
 #include "ga3c_vecnet.hpp"
 
 namespace ga3c_dd {
 
 using ga3c_vecnet::Input;      // a prediction's row r: S floats at base + (off ? off[r] : r * stride) bytes
+using namespace ga3c_tile;     // TILE and the device half
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TILE = 16;
 constexpr int THREADS = 448;                 // 7 waves: a 300-wide layer and the 400 rows of a backward pass take one pass each
-constexpr int RED = 512;                     // the power of two above it, for the fixed-order trees
+constexpr int RED = 512;                     // the power of two above it: the leaves of block_sum's tree
 constexpr int MAX_S = 64;
 constexpr int MAX_A = 32;
 constexpr int MAX_B = 4096;                  // rows of a step: per_update_kernel holds their slots in LDS
@@ -119,42 +119,8 @@ struct Opt {
   int apply, soft;
 };
 
-// out(j, r) = bias[j] + sum_k in[k][r] W[k][j] (+ sum_k in2[k][r] W2[k][j]); thread j owns column j.
-template <class EP>
-__device__ __forceinline__ void dense_fwd(const float* __restrict__ W, const float* __restrict__ bias, int K, int N, const float* in,
-                                          const float* __restrict__ W2, int K2, const float* in2, EP ep) {
-  for (int j = threadIdx.x; j < N; j += THREADS) {
-    float acc[TILE];
-    const float b = bias[j];
-#pragma unroll
-    for (int r = 0; r < TILE; ++r) acc[r] = b;
-    for (int k = 0; k < K; ++k) {
-      const float w = W[(size_t)k * N + j];
-      const f32x4* col = reinterpret_cast<const f32x4*>(in + k * TILE);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 c = col[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
-      }
-    }
-    for (int k = 0; k < K2; ++k) {
-      const float w = W2[(size_t)k * N + j];
-      const f32x4* col = reinterpret_cast<const f32x4*>(in2 + k * TILE);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 c = col[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < TILE; ++r) ep(j, r, acc[r]);
-  }
-  __syncthreads();
-}
-
-// ep(k, r, sum_j W[k][j] gout[j][r]) for k < K; thread k owns row k of W and sums in j order.
+// ep(k, r, sum_j W[k][j] gout[j][r]) for k < K; thread k owns row k of W and sums in j order.  (Not dense_bwd_split: that
+// would share an A-wide layer's rows among threads and add the partials in another order.)
 template <class EP>
 __device__ __forceinline__ void dense_bwd(const float* __restrict__ W, int K, int N, const float* gout, EP ep) {
   for (int k = threadIdx.x; k < K; k += THREADS) {
@@ -162,16 +128,7 @@ __device__ __forceinline__ void dense_bwd(const float* __restrict__ W, int K, in
 #pragma unroll
     for (int r = 0; r < TILE; ++r) acc[r] = 0.f;
     const float* __restrict__ wr = W + (size_t)k * N;
-    for (int j = 0; j < N; ++j) {
-      const float w = wr[j];
-      const f32x4* col = reinterpret_cast<const f32x4*>(gout + j * TILE);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 c = col[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
-      }
-    }
+    for (int j = 0; j < N; ++j) tile_fma(acc, gout + j * TILE, wr[j]);
 #pragma unroll
     for (int r = 0; r < TILE; ++r) ep(k, r, acc[r]);
   }
@@ -196,7 +153,7 @@ struct CriticKeep { float *xh1, *c1, *c2; };
 // dact (may be null): 1 - tanh^2 = 4 e / (1 + e)^2 with e = exp(-2 |h|), from h itself: 1 - o * o loses what tanh rounds away
 __device__ void actor_fwd(const Layout& L, const float* __restrict__ th, const float* xin, float* bufA, float* bufB, float* act,
                           float* dact, ActorKeep kp, int row0, int nrows) {
-  dense_fwd(th + L.off[A_W1], th + L.off[A_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
+  dense_fwd<THREADS>(th + L.off[A_W1], th + L.off[A_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
     float n;
     const float xh = bn_apply(th, L, A_MM1, A_MV1, A_BE1, A_GA1, j, h, &n);
     const float a = fmaxf(n, 0.f);
@@ -206,7 +163,7 @@ __device__ void actor_fwd(const Layout& L, const float* __restrict__ th, const f
       kp.a1[(size_t)(row0 + r) * H1 + j] = a;
     }
   });
-  dense_fwd(th + L.off[A_W2], th + L.off[A_B2], H1, H2, bufA, nullptr, 0, nullptr, [&](int j, int r, float h) {
+  dense_fwd<THREADS>(th + L.off[A_W2], th + L.off[A_B2], H1, H2, bufA, nullptr, 0, nullptr, [&](int j, int r, float h) {
     float n;
     const float xh = bn_apply(th, L, A_MM2, A_MV2, A_BE2, A_GA2, j, h, &n);
     const float a = fmaxf(n, 0.f);
@@ -217,7 +174,7 @@ __device__ void actor_fwd(const Layout& L, const float* __restrict__ th, const f
     }
   });
   const int A = L.A;
-  dense_fwd(th + L.off[A_WO], th + L.off[A_BO], H2, A, bufB, nullptr, 0, nullptr, [&](int j, int r, float h) {
+  dense_fwd<THREADS>(th + L.off[A_WO], th + L.off[A_BO], H2, A, bufB, nullptr, 0, nullptr, [&](int j, int r, float h) {
     const float o = tanhf(h);
     act[j * TILE + r] = o;
     if (dact) {
@@ -231,7 +188,7 @@ __device__ void actor_fwd(const Layout& L, const float* __restrict__ th, const f
 // xin [S][16], act [A][16] -> bufA = c1 [400][16], bufB = c2 [300][16], qv[16] (LDS)
 __device__ void critic_fwd(const Layout& L, const float* __restrict__ th, const float* xin, const float* act, float* bufA,
                            float* bufB, float* qv, CriticKeep kp, int row0, int nrows) {
-  dense_fwd(th + L.off[C_W1], th + L.off[C_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
+  dense_fwd<THREADS>(th + L.off[C_W1], th + L.off[C_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
     float n;
     const float xh = bn_apply(th, L, C_MM1, C_MV1, C_BE1, C_GA1, j, h, &n);
     const float c = fmaxf(n, 0.f);
@@ -241,7 +198,7 @@ __device__ void critic_fwd(const Layout& L, const float* __restrict__ th, const 
       kp.c1[(size_t)(row0 + r) * H1 + j] = c;
     }
   });
-  dense_fwd(th + L.off[C_W2], th + L.off[C_BN], H1, H2, bufA, th + L.off[C_WN], L.A, act, [&](int j, int r, float h) {
+  dense_fwd<THREADS>(th + L.off[C_W2], th + L.off[C_BN], H1, H2, bufA, th + L.off[C_WN], L.A, act, [&](int j, int r, float h) {
     const float c = fmaxf(h, 0.f);
     bufB[j * TILE + r] = c;
     if (kp.c2 && r < nrows) kp.c2[(size_t)(row0 + r) * H2 + j] = c;
@@ -258,6 +215,15 @@ __device__ void critic_fwd(const Layout& L, const float* __restrict__ th, const 
 }
 
 // Loads `width` floats at column offset `col` of the tile's rows into dst [width][16] (zeros beyond nrows).
+// a + noise; wrap: the reference's check_bounds(turnaround), which folds what leaves [-1, 1] back in from the other end
+__device__ __forceinline__ float wrap_action(float v, int wrap) {
+  if (wrap) {
+    if (v < -1.f) v = 1.f - fmodf(-1.f - v, 2.f);
+    else if (v > 1.f) v = fmodf(v - 1.f, 2.f) - 1.f;
+  }
+  return v;
+}
+
 __device__ __forceinline__ void load_rows(const Rows& src, int col, int width, float* dst, int row0, int nrows, float* keep) {
   for (int e = threadIdx.x; e < width * TILE; e += THREADS) {
     const int r = e / width, c = e % width;
@@ -312,19 +278,10 @@ __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const fl
   __shared__ float red[RED];
   const int S = L.S, A = L.A;
   const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
-  // mean(y), the same fixed order in every block: strided partials, then a tree
-  {
-    float s = 0.f;
-    for (int i = threadIdx.x; i < B; i += THREADS) s += w.y[i];
-    red[threadIdx.x] = s;
-    if (threadIdx.x + THREADS < RED) red[threadIdx.x + THREADS] = 0.f;
-    __syncthreads();
-    for (int h = RED / 2; h > 0; h >>= 1) {
-      if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-      __syncthreads();
-    }
-  }
-  const float ymean = red[0] / (float)B;
+  // mean(y), the same fixed order in every block: strided partials, then block_sum's tree
+  float ysum = 0.f;
+  for (int i = threadIdx.x; i < B; i += THREADS) ysum += w.y[i];
+  const float ymean = block_sum<THREADS>(ysum, red) / (float)B;
   load_rows(src, 0, S, xin, row0, nrows, w.c_x);
   load_rows(src, S, A, act, row0, nrows, w.c_a);
   __syncthreads();
@@ -378,11 +335,7 @@ __global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const flo
   actor_fwd(L, th, xin, bufA, bufB, act, dact, ActorKeep{w.a_xh1, w.a_a1, w.a_xh2, w.a_a2, w.a_out}, row0, nrows);
   for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
     const int i = e / TILE, r = e % TILE;
-    float v = act[e] + nz.v[i];
-    if (nz.wrap) {
-      if (v < -1.f) v = 1.f - fmodf(-1.f - v, 2.f);
-      else if (v > 1.f) v = fmodf(v - 1.f, 2.f) - 1.f;
-    }
+    const float v = wrap_action(act[e] + nz.v[i], nz.wrap);
     noisy[e] = v;
     if (r < nrows) w.a_noisy[(size_t)(row0 + r) * A + i] = v;
   }
@@ -429,24 +382,12 @@ __global__ __launch_bounds__(THREADS) void ddpg_predict_kernel(Layout L, const f
   __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
   const int S = L.S, A = L.A;
   const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
-  for (int e = threadIdx.x; e < S * TILE; e += THREADS) {
-    const int r = e / S, s = e % S;
-    float xv = 0.f;
-    if (r < nrows) {
-      const int64_t ob = in.off ? in.off[row0 + r] : (int64_t)(row0 + r) * in.stride;
-      xv = reinterpret_cast<const float*>(in.base + ob)[s];
-    }
-    xin[s * TILE + r] = xv;
-  }
+  load_input_tile<THREADS, false>(in, S, row0, nrows, xin, nullptr);
   __syncthreads();
   actor_fwd(L, th, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
   for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
     const int i = e / TILE, r = e % TILE;
-    float v = act[e] + nz.v[i];
-    if (nz.wrap) {
-      if (v < -1.f) v = 1.f - fmodf(-1.f - v, 2.f);
-      else if (v > 1.f) v = fmodf(v - 1.f, 2.f) - 1.f;
-    }
+    const float v = wrap_action(act[e] + nz.v[i], nz.wrap);
     if (r < nrows) a_out[(size_t)(row0 + r) * A + i] = v;
   }
 }
@@ -530,14 +471,7 @@ __global__ __launch_bounds__(THREADS) void ddpg_update_kernel(Layout L, int v0, 
   const bool dead = v == C_B2DEAD;
   float s = 0.f;
   for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) s += o.grad[i] * o.grad[i];
-  sh[threadIdx.x] = s;
-  if (threadIdx.x + THREADS < RED) sh[threadIdx.x + THREADS] = 0.f;
-  __syncthreads();
-  for (int h = RED / 2; h > 0; h >>= 1) {
-    if (threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-    __syncthreads();
-  }
-  const float scale = o.clip / fmaxf(sqrtf(sh[0]), o.clip);
+  const float scale = o.clip / fmaxf(sqrtf(block_sum<THREADS>(s, sh)), o.clip);
   for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) {
     if (!dead && o.apply) opt_step(o, i, o.grad[i] * scale);
     if (o.soft) soft_step(o, i);
@@ -1031,6 +965,15 @@ int alloc_all(ga3c_ddpg* m) {
   return GA3C_OK;
 }
 
+int64_t ring_size(const ga3c_ddpg* m) { return std::min<int64_t>(m->ring_total, m->cfg.replay_capacity); }
+
+// the row count of a replay_add / replay_add_gather
+int check_add_rows(const ga3c_ddpg* m, int n) {
+  if (n < 1 || n > m->cfg.max_batch || n > m->cfg.replay_capacity)
+    return fail(GA3C_EINVAL, "%d rows outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
+  return GA3C_OK;
+}
+
 // n rows into the ring at its write position, from `src` (device or pinned host) in ring layout; caller holds mu.
 int ring_copy_in(ga3c_ddpg* m, const float* src, int n, hipMemcpyKind kind) {
   const int64_t cap = m->cfg.replay_capacity, first = m->ring_total % cap;
@@ -1040,8 +983,6 @@ int ring_copy_in(ga3c_ddpg* m, const float* src, int n, hipMemcpyKind kind) {
   if (n1 < n) HIPCHK(hipMemcpyAsync(m->ring, src + n1 * m->rowf, rowb * (n - n1), kind, m->st));
   return GA3C_OK;
 }
-
-int64_t ring_size(const ga3c_ddpg* m) { return std::min<int64_t>(m->ring_total, m->cfg.replay_capacity); }
 
 // The n rows just written from slot `first` on get max_pa (caller holds mu; right after the ring write, on its stream).
 void per_fill(ga3c_ddpg* m, int64_t first, int64_t n) {
@@ -1085,7 +1026,7 @@ int per_check_beta(float beta) {
 }
 
 void ring_report(ga3c_ddpg* m, int64_t* size, int64_t* total) {
-  if (size) *size = std::min<int64_t>(m->ring_total, m->cfg.replay_capacity);
+  if (size) *size = ring_size(m);
   if (total) *total = m->ring_total;
 }
 
@@ -1247,8 +1188,7 @@ int ga3c_ddpg_predict_gather_end(void* net, int32_t ticket, int32_t batch, float
 int ga3c_ddpg_replay_add(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2,
                          int32_t n, int64_t* size, int64_t* total) {
   if (!m || !s || !a || !r || !done || !s2) return fail(GA3C_EINVAL, "null argument");
-  if (n < 1 || n > m->cfg.max_batch || n > m->cfg.replay_capacity)
-    return fail(GA3C_EINVAL, "%d rows outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
+  CHK(check_add_rows(m, n));
   HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> al(m->add_mu);
   pack_rows(m, m->h_add, s, a, r, done, s2, n);
@@ -1268,8 +1208,7 @@ int ga3c_ddpg_replay_add(ga3c_ddpg* m, const float* s, const float* a, const flo
 int ga3c_ddpg_replay_add_gather(ga3c_ddpg* m, const int64_t* offsets, const float* r, const float* a, int32_t n, int64_t* size,
                                 int64_t* total) {
   if (!m || !offsets || !r || !a) return fail(GA3C_EINVAL, "null argument");
-  if (n < 1 || n > m->cfg.max_batch || n > m->cfg.replay_capacity)
-    return fail(GA3C_EINVAL, "%d rows outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
+  CHK(check_add_rows(m, n));
   HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> al(m->add_mu);
   const int S = m->L.S, A = m->L.A;
@@ -1302,7 +1241,7 @@ int ga3c_ddpg_replay_get(ga3c_ddpg* m, int64_t slot, float* s, float* a, float* 
   std::vector<float> row((size_t)m->rowf);
   {
     std::lock_guard<std::mutex> lk(m->mu);
-    const int64_t size = std::min<int64_t>(m->ring_total, m->cfg.replay_capacity);
+    const int64_t size = ring_size(m);
     if (slot < 0 || slot >= size) return fail(GA3C_EINVAL, "slot %lld outside the ring's %lld rows", (long long)slot, (long long)size);
     HIPCHK(hipStreamSynchronize(m->st));
     HIPCHK(hipMemcpy(row.data(), m->ring + slot * m->rowf, sizeof(float) * m->rowf, hipMemcpyDeviceToHost));
@@ -1344,7 +1283,7 @@ int ga3c_ddpg_train_replay(ga3c_ddpg* m, const int32_t* slots, int32_t batch, in
   {
     std::lock_guard<std::mutex> lk(m->mu);
     // Validated under the lock that orders ring writes: a slot is refused if a row was written into it after `stamp`.
-    const int64_t cap = m->cfg.replay_capacity, total = m->ring_total, size = std::min(total, cap);
+    const int64_t cap = m->cfg.replay_capacity, total = m->ring_total, size = ring_size(m);
     for (int i = 0; i < batch; ++i) {
       const int64_t sl = slots[i];
       if (sl < 0 || sl >= size) return fail(GA3C_EINVAL, "slot %lld of row %d outside the ring's %lld rows", (long long)sl, i, (long long)size);
@@ -1399,8 +1338,7 @@ int ga3c_ddpg_time_resident(ga3c_ddpg* m, int32_t mode, int32_t batch, int32_t i
   std::lock_guard<std::mutex> tl(m->train_mu);
   {
     std::lock_guard<std::mutex> lk(m->mu);
-    if (batch > std::min<int64_t>(m->ring_total, m->cfg.replay_capacity))
-      return fail(GA3C_ESTATE, "batch %d: the ring holds %lld rows", batch, (long long)std::min<int64_t>(m->ring_total, m->cfg.replay_capacity));
+    if (batch > ring_size(m)) return fail(GA3C_ESTATE, "batch %d: the ring holds %lld rows", batch, (long long)ring_size(m));
     for (int i = 0; i < batch; ++i) m->h_idx[i] = i;
     HIPCHK(hipMemcpyAsync(m->d_idx, m->h_idx, sizeof(int32_t) * batch, hipMemcpyHostToDevice, m->st));
     Noise nz;

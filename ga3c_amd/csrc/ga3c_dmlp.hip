@@ -7,15 +7,16 @@
 // (:52-56): every layer reads x, only the last one reaches the heads, the others are variables that nothing reads.
 // chained = 1: layer i reads layer i - 1.
 //
-// Kernels (all f32, one workgroup of 256 threads per 16-row tile where rows are involved):
-//   dmlp_tile_kernel<PREDICT>  forward of one tile, activations in LDS ([width][16]); thread j owns output column j.
+// Kernels (all f32, one workgroup of 256 threads per 16-row tile where rows are involved).  The tile's layout in LDS, who
+// owns which sum and the order of its additions are ga3c_tile.hpp's; here are the layer list and the head.
+//   dmlp_tile_kernel<PREDICT>  forward of one tile (load_input_tile, tile_fma).
 //   dmlp_tile_kernel<TRAIN>    the same forward, the softmax head's loss row and dz / dv, and the deltas back through the
-//                              live layers; activations and deltas go to HBM for the weight gradients.  <EVAL>: forward + loss.
-//   dmlp_wgrad_kernel<FUSED>   one thread per arena element sums its gradient over the rows in row order (no atomics: the
-//                              same call gives the same bits); FUSED (no clipping) applies RMSProp to the element at once.
-//                              An element of a dead variable gets gradient 0 and no step.  Threads 0..2 of block 0: the
-//                              three loss sums, in row order.
-//   dmlp_update_kernel<CLIP>   one block per live variable: tf.clip_by_average_norm's norm (fixed-order tree), then RMSProp.
+//                              live layers (dense_bwd_split); activations and deltas go to HBM for the weight gradients.
+//                              <EVAL>: forward + loss.
+//   dmlp_wgrad_kernel<FUSED>   one thread per arena element sums its gradient over the rows in row order (sum_rows,
+//                              dot_rows); FUSED (no clipping) applies rms_step to the element at once.  An element of a dead
+//                              variable gets gradient 0 and no step.  Block 0 also: loss_sums.
+//   dmlp_update_kernel<CLIP>   one block per live variable: clip_and_step (tf.clip_by_average_norm, RMSProp).
 // A train step is 2 launches without USE_GRAD_CLIP and 3 with it; a prediction is 1; an evaluation 2.
 #include <hip/hip_runtime.h>
 
@@ -26,15 +27,14 @@
 #include <vector>
 
 #include "ga3c_actors.hpp"
+#include "ga3c_tile.hpp"
 #include "ga3c_vecnet.hpp"
 
 namespace ga3c_dvec {
 
 using namespace ga3c_vecnet;   // Input, Opt, PREDICT / EVAL / TRAIN and the host half
+using namespace ga3c_tile;     // TILE and the device half
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TILE = 16;                  // rows per workgroup
 constexpr int THREADS = 256;
 constexpr int MAX_S = 64;
 constexpr int MAX_A = 32;
@@ -93,10 +93,10 @@ struct Head {          // the loss of NetworkVP_discrate.py:61-85
   int log_softmax;
 };
 
-__device__ __forceinline__ float sigm(float h) { return 1.0f / (1.0f + expf(-h)); }
-
-// out[j][r] = sigmoid(b[j] + sum_k in[k][r] W[k][j]) for the tile; thread j owns column j (coalesced weight reads).
-// gout (may be null): the same values, row-major [B][N], rows < nrows only.
+// out[j][r] = sigmoid(b[j] + sum_k in[k][r] W[k][j]) for the tile; thread j owns column j (coalesced weight reads) and adds
+// in k order.  gout (may be null): the same values, row-major [B][N], rows < nrows only.  ga3c_tile.hpp's dense_fwd written
+// out: with the sigmoid as that function's epilogue the compiler orders the 16 of them otherwise, and a 128-row prediction
+// through two 256-wide layers took 61.0 us instead of 60.1 (profiles/vecnet_device_half.txt).
 __device__ void dense_fwd(const float* __restrict__ W, const float* __restrict__ bias, int K, int N, const float* in, float* out,
                           float* gout, int row0, int nrows) {
   for (int j = threadIdx.x; j < N; j += THREADS) {
@@ -104,16 +104,7 @@ __device__ void dense_fwd(const float* __restrict__ W, const float* __restrict__
     const float b = bias[j];
 #pragma unroll
     for (int r = 0; r < TILE; ++r) acc[r] = b;
-    for (int k = 0; k < K; ++k) {
-      const float w = W[(size_t)k * N + j];
-      const f32x4* col = reinterpret_cast<const f32x4*>(in + k * TILE);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 c = col[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
-      }
-    }
+    for (int k = 0; k < K; ++k) tile_fma(acc, in + k * TILE, W[(size_t)k * N + j]);
 #pragma unroll
     for (int r = 0; r < TILE; ++r) {
       const float h = sigm(acc[r]);
@@ -124,16 +115,12 @@ __device__ void dense_fwd(const float* __restrict__ W, const float* __restrict__
   __syncthreads();
 }
 
-// gin[k][r] = s (1 - s) sum_j W(k, j) gout[j][r] for k < K <= 256, s = gact[row][k] the layer's sigmoid output as this
-// workgroup wrote it to HBM in the forward pass.  P threads share a k (the largest power of two with P K <= 256), each
-// summing the strided slice j = p, p + P, ...; the P partials meet in `scratch` (P K 16 floats) and are added in p order.
+// gin[k][r] = s (1 - s) sum_j W(k, j) gout[j][r] for k < K <= 256 (dense_bwd_split, ga3c_tile.hpp, whose partials `scratch` holds), s =
+// gact[row][k] the layer's sigmoid output as this workgroup wrote it to HBM in the forward pass.  gin_lds may be null.
 template <class WF>
 __device__ void dense_bwd(WF W, int K, int N, const float* gout, const float* gact, float* gin_lds, float* gin_glob, int row0,
                           int nrows, float* scratch) {
-  int P = 1;
-  while (P * 2 * K <= THREADS) P *= 2;
-  const int t = threadIdx.x;
-  auto finish = [&](int k, int r, float s) {
+  dense_bwd_split<THREADS>(W, K, N, gout, scratch, [&](int k, int r, float s) {
     float g = 0.f;
     if (r < nrows) {
       const float h = gact[(size_t)(row0 + r) * K + k];
@@ -141,40 +128,7 @@ __device__ void dense_bwd(WF W, int K, int N, const float* gout, const float* ga
       gin_glob[(size_t)(row0 + r) * K + k] = g;
     }
     if (gin_lds) gin_lds[k * TILE + r] = g;
-  };
-  if (t < P * K) {
-    const int k = t / P, p = t % P;
-    float acc[TILE];
-#pragma unroll
-    for (int r = 0; r < TILE; ++r) acc[r] = 0.f;
-    for (int j = p; j < N; j += P) {
-      const float w = W(k, j);
-      const f32x4* col = reinterpret_cast<const f32x4*>(gout + j * TILE);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 c = col[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(c[i], w, acc[4 * q + i]);
-      }
-    }
-    if (P == 1) {
-#pragma unroll
-      for (int r = 0; r < TILE; ++r) finish(k, r, acc[r]);
-    } else {
-#pragma unroll
-      for (int r = 0; r < TILE; ++r) scratch[(p * K + k) * TILE + r] = acc[r];
-    }
-  }
-  if (P > 1) {
-    __syncthreads();
-    for (int e = t; e < K * TILE; e += THREADS) {
-      const int k = e / TILE, r = e % TILE;
-      float s = 0.f;
-      for (int p = 0; p < P; ++p) s += scratch[(p * K + k) * TILE + r];
-      finish(k, r, s);
-    }
-  }
-  __syncthreads();
+  });
 }
 
 // One 16-row tile: forward (all modes), loss rows (EVAL, TRAIN), deltas (TRAIN).  Outputs p[B,A], v[B], z[B,A] always.
@@ -201,16 +155,7 @@ __global__ __launch_bounds__(THREADS) void dmlp_tile_kernel(const Layout* __rest
   const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
   constexpr bool KEEP = MODE != PREDICT;
 
-  for (int e = threadIdx.x; e < S * TILE; e += THREADS) {
-    const int r = e / S, s = e % S;
-    float xv = 0.f;
-    if (r < nrows) {
-      const int64_t ob = in.off ? in.off[row0 + r] : (int64_t)(row0 + r) * in.stride;
-      xv = reinterpret_cast<const float*>(in.base + ob)[s];
-      if (KEEP) w.x[(size_t)(row0 + r) * S + s] = xv;
-    }
-    xin[s * TILE + r] = xv;
-  }
+  load_input_tile<THREADS, KEEP>(in, S, row0, nrows, xin, w.x);
   __syncthreads();
 
   // the trunk: every layer when chained, else the last one alone, which reads x as all of them do
@@ -232,16 +177,7 @@ __global__ __launch_bounds__(THREADS) void dmlp_tile_kernel(const Layout* __rest
     const float b = j == 0 ? theta[ovb] : theta[opb + j - 1];
 #pragma unroll
     for (int r = 0; r < TILE; ++r) acc[r] = b;
-    for (int k = 0; k < H; ++k) {
-      const float wk = j == 0 ? theta[ovw + k] : theta[opw + (int64_t)k * A + j - 1];
-      const f32x4* col = reinterpret_cast<const f32x4*>(cur + k * TILE);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 cc = col[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[4 * q + i] = fmaf(cc[i], wk, acc[4 * q + i]);
-      }
-    }
+    for (int k = 0; k < H; ++k) tile_fma(acc, cur + k * TILE, j == 0 ? theta[ovw + k] : theta[opw + (int64_t)k * A + j - 1]);
 #pragma unroll
     for (int r = 0; r < TILE; ++r) zh[j * TILE + r] = acc[r];
   }
@@ -362,54 +298,6 @@ struct GradSrc {
   const float* d[MAX_NL];
 };
 
-__device__ __forceinline__ float rms_step(const Opt& o, int64_t i, float g) {
-  float m = o.ms[i];
-  m += (g * g - m) * o.omr;
-  o.ms[i] = m;
-  float step = (g * o.lr) / sqrtf(o.eps + m);
-  if (o.mu != 0.f) {
-    step = o.mom[i] * o.mu + step;
-    o.mom[i] = step;
-  }
-  o.theta[i] -= step;
-  return step;
-}
-
-// Sums over the batch rows, in row order.  The loads of ROWS_AHEAD rows are issued together and the additions stay one chain:
-// the bits of the plain loop at the latency of B / ROWS_AHEAD round trips to L2 instead of B.
-constexpr int ROWS_AHEAD = 16;
-
-__device__ __forceinline__ float sum_rows(const float* __restrict__ d, int ld, int B) {
-  float g = 0.f;
-  int r = 0;
-  for (; r + ROWS_AHEAD <= B; r += ROWS_AHEAD) {
-    float t[ROWS_AHEAD];
-#pragma unroll
-    for (int i = 0; i < ROWS_AHEAD; ++i) t[i] = d[(size_t)(r + i) * ld];
-#pragma unroll
-    for (int i = 0; i < ROWS_AHEAD; ++i) g += t[i];
-  }
-  for (; r < B; ++r) g += d[(size_t)r * ld];
-  return g;
-}
-
-__device__ __forceinline__ float dot_rows(const float* __restrict__ x, int ldx, const float* __restrict__ d, int ldd, int B) {
-  float g = 0.f;
-  int r = 0;
-  for (; r + ROWS_AHEAD <= B; r += ROWS_AHEAD) {
-    float tx[ROWS_AHEAD], td[ROWS_AHEAD];
-#pragma unroll
-    for (int i = 0; i < ROWS_AHEAD; ++i) {
-      tx[i] = x[(size_t)(r + i) * ldx];
-      td[i] = d[(size_t)(r + i) * ldd];
-    }
-#pragma unroll
-    for (int i = 0; i < ROWS_AHEAD; ++i) g = fmaf(tx[i], td[i], g);
-  }
-  for (; r < B; ++r) g = fmaf(x[(size_t)r * ldx], d[(size_t)r * ldd], g);
-  return g;
-}
-
 template <bool FUSED>
 __global__ __launch_bounds__(THREADS) void dmlp_wgrad_kernel(Layout L, GradSrc src, int B, Opt o, Work w) {
   const int NV = 2 * (L.L + 2);
@@ -435,38 +323,18 @@ __global__ __launch_bounds__(THREADS) void dmlp_wgrad_kernel(Layout L, GradSrc s
       if (FUSED) rms_step(o, e, g);
     }
   }
-  if (blockIdx.x == 0 && threadIdx.x < 3) w.losses[threadIdx.x] = sum_rows(w.lossrow + threadIdx.x, 3, B);
+  loss_sums(w.lossrow, w.losses, B, blockIdx.x == 0);
 }
 
-// One block per variable; a dead variable's block returns at once.  CLIP: scale = clip / max(||g||_2 / n, clip)
-// (tf.clip_by_average_norm), the sum of squares in a fixed order (strided partials, then a tree in LDS).
+// One block per variable; a dead variable's block returns at once.  clip_and_step (ga3c_tile.hpp).
 template <bool CLIP>
 __global__ __launch_bounds__(THREADS) void dmlp_update_kernel(Layout L, Opt o) {
   __shared__ float sh[THREADS];
   if (!L.live[blockIdx.x / 2]) return;
-  const int64_t lo = L.off[blockIdx.x], hi = L.off[blockIdx.x + 1];
-  float scale = 1.f;
-  if (CLIP) {
-    float s = 0.f;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) s += o.grad[i] * o.grad[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = THREADS / 2; h > 0; h >>= 1) {
-      if (threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-      __syncthreads();
-    }
-    scale = o.clip / fmaxf(sqrtf(sh[0]) / (float)(hi - lo), o.clip);
-  }
-  for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) {
-    float g = o.grad[i];
-    if (CLIP) g *= scale;
-    rms_step(o, i, g);
-  }
+  clip_and_step<THREADS, CLIP>(L.off[blockIdx.x], L.off[blockIdx.x + 1], o, sh);
 }
 
-__global__ void dmlp_loss_kernel(Work w, int B) {
-  if (threadIdx.x < 3) w.losses[threadIdx.x] = sum_rows(w.lossrow + threadIdx.x, 3, B);
-}
+__global__ void dmlp_loss_kernel(Work w, int B) { loss_sums(w.lossrow, w.losses, B); }
 
 // ------------------------------------------------------------------ host side
 

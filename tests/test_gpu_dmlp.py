@@ -21,6 +21,8 @@ SIZES = [1, 15, 16, 17, 128, 132, 201, 1024]
 SHAPES = [(4, 2, (10, 10, 10, 10), "fork"), (4, 2, (10, 10, 10, 10), "chained"), (7, 5, (32, 16), "chained"),
           (3, 1, (10,), "fork")]
 SHAPE_IDS = ["fork4x10", "chained4x10", "chained32_16", "one_action"]
+# the backward pass shares a row of W among P = 1, 1, 2, 64 and 256 threads at these widths (the shapes above reach 8 and 16)
+SPLIT_EDGES = (64, 32, (256, 129, 128, 3, 1), "chained")
 HEADS = {"plain": dict(use_log_softmax=False, min_policy=0.0), "log_softmax": dict(use_log_softmax=True, min_policy=0.0),
          "min_policy": dict(use_log_softmax=False, min_policy=0.01)}
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ga3c_amd")
@@ -88,7 +90,7 @@ def _f64(*arrays):
 
 
 @pytest.mark.parametrize("head", list(HEADS))
-@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+@pytest.mark.parametrize("shape", SHAPES + [SPLIT_EDGES], ids=SHAPE_IDS + ["split_edges"])
 def test_forward_losses_and_gradients_against_the_oracle(shape, head):
     S, A, layers, stack = shape
     kw = HEADS[head]
