@@ -147,9 +147,13 @@ class Config:
     FRAME_HEIGHT = 210
     FRAME_WIDTH = 160
     FRAME_HISTORY = 0                   # planes of history per agent on the device; 0 = derived from the queue bounds
-    DEVICE_AGENTS = 0                   # > 0 (GAME = 'CartPole-v0' only): this many environments, their rollouts and their
-                                        # training rows live in HBM and the server steps them with HIP kernels; no agent
-                                        # process, predictor or trainer is started (ThreadDeviceAgents.py)
+    DEVICE_AGENTS = 0                   # > 0 (GAME = 'CartPole-v0', or 'Pendulum-v0' with DEVICE_PENDULUM): this many
+                                        # environments, their rollouts and their training rows live in HBM and the server
+                                        # steps them with HIP kernels; no agent process, predictor or trainer is started
+                                        # (ThreadDeviceAgents.py)
+    DEVICE_PENDULUM = False             # True: DEVICE_AGENTS steps Pendulum-v0.  An opt-in of its own because the regime differs:
+                                        # the environments run in lockstep, one train step of N (TIME_MAX + 1) rows every
+                                        # TIME_MAX actor steps
     DEVICE_AGENT_STEPS = 32             # actor steps per native call of that loop (1..64)
 
 
@@ -251,17 +255,23 @@ def resolve_device_agents(explicit=()):
         return
     if n < 0:
         raise ValueError("DEVICE_AGENTS=%d: 0 (off) or the number of environments on the device" % n)
+    pendulum = bool(getattr(Config, "DEVICE_PENDULUM", False))
     if Config.USE_DDPG:
-        raise ValueError("DEVICE_AGENTS with USE_DDPG is not supported: the device actors step CartPole-v0 only")
-    if Config.GAME != 'CartPole-v0':
-        raise ValueError("DEVICE_AGENTS with GAME=%s is not supported: the device actors step CartPole-v0 only "
-                         "(Pendulum-v0 and the image games keep their agent processes)" % Config.GAME)
+        raise ValueError("DEVICE_AGENTS with USE_DDPG is not supported: the device actors step CartPole-v0 only, or "
+                         "Pendulum-v0 under the actor-critic network (DEVICE_PENDULUM)")
+    if pendulum and Config.GAME != 'Pendulum-v0':
+        raise ValueError("DEVICE_PENDULUM with GAME=%s is not supported: it asks for Pendulum-v0 environments on the device"
+                         % Config.GAME)
+    if Config.GAME != 'CartPole-v0' and not pendulum:
+        raise ValueError("DEVICE_AGENTS with GAME=%s is not supported: the device actors step CartPole-v0 only, and "
+                         "Pendulum-v0 with DEVICE_PENDULUM=True, where they run in lockstep (the image games keep their agent "
+                         "processes)" % Config.GAME)
     if Config.RETURN_MODE != 'fork':
         raise ValueError("DEVICE_AGENTS with RETURN_MODE=%r is not supported: the device computes the fork's returns" % Config.RETURN_MODE)
     if not Config.DISCOUNTING or Config.USE_INTERMEDIATE_REWARD:
         raise ValueError("DEVICE_AGENTS computes the fork's returns with DISCOUNTING and without USE_INTERMEDIATE_REWARD only")
     if Config.PLAY_MODE:
-        raise ValueError("DEVICE_AGENTS with PLAY_MODE is not supported: the device actors draw their actions")
+        raise ValueError("DEVICE_AGENTS with PLAY_MODE is not supported: the device actors train as they step")
     if Config.DYNAMIC_SETTINGS:
         raise ValueError("DEVICE_AGENTS with DYNAMIC_SETTINGS is not supported: there are no workers to add or remove")
     if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:

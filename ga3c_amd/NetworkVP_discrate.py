@@ -11,12 +11,10 @@ histogrammed, never trained.  'chained' feeds layer i - 1 into layer i.
 The interface is NetworkVP_vecnet.VectorNetwork's; this module states the layer list, the initial weights and what
 ga3c_dmlp_create and ga3c_dmlp_evaluate take.
 """
-import ctypes as C
-
 import numpy as np
 
 from Config import Config
-from NetworkVP_vecnet import VectorNetwork
+from NetworkVP_vecnet import DeviceActors, VectorNetwork
 import _native as nat
 
 HEADS = ("logits_v", "logits_p")
@@ -77,11 +75,12 @@ def initial_arena(state_dim, num_actions, seed, layers=None, stack=None):
     return np.concatenate([rng.uniform(-INIT, INIT, size=shapes[k]).astype(np.float32).ravel() for k in param_order(layers)])
 
 
-class Network(VectorNetwork):
+class Network(DeviceActors, VectorNetwork):
     PREFIX = "ga3c_dmlp"
     LOGITS_PER_ACTION = 1
     ACTIVATION_TAGS = ("activation_lastdense",)   # NetworkVP_discrate.py:132-146; the dead variables get histograms too
     DUAL_RMSPROP_REFUSAL = "DUAL_RMSPROP with the discrete vector-state network is not supported"
+    ACTOR_FIELDS = ACTOR_FIELDS   # device actors (Config.DEVICE_AGENTS): ga3c_dmlp_actors_*, CartPole-v0
 
     def _config(self):
         self.layers, self.stack = _layers(), _stack()
@@ -100,46 +99,3 @@ class Network(VectorNetwork):
         self.dead = dead_params(self.layers, self.stack)
         return (param_order(self.layers), param_shapes(self.S, self.num_actions, self.layers, self.stack),
                 initial_arena(self.S, self.num_actions, Config.RANDOM_SEED, self.layers, self.stack))
-
-    # ---- device actors (Config.DEVICE_AGENTS): ga3c_dmlp_actors_* ------------------
-    def actors_create(self, n, time_max=None, discount=None, seed=None):
-        self._call("actors_create", int(n), int(Config.TIME_MAX if time_max is None else time_max),
-                   float(Config.DISCOUNT if discount is None else discount), int(Config.RANDOM_SEED if seed is None else seed))
-        self.num_actors = int(n)
-
-    def actors_destroy(self):
-        self._call("actors_destroy")
-
-    def actors_run(self, steps, train=True):
-        """`steps` actor steps at the model's learning_rate and beta -> (agent steps, train calls, rows trained, episodes
-        finished)."""
-        stats = np.zeros(4, np.int64)
-        self._call("actors_run", int(steps), float(self.learning_rate), float(self.beta), int(bool(train)),
-                   nat.ptr(stats, nat.i64p))
-        return tuple(int(t) for t in stats)
-
-    def actors_episodes(self, max_count=4096):
-        """The finished episodes not yet taken, oldest first -> [(total_reward, total_length)]."""
-        out = []
-        reward, length, count = np.empty(max_count, np.float64), np.empty(max_count, np.int64), C.c_int32()
-        while True:
-            self._call("actors_episodes", nat.ptr(reward, nat.f64p), nat.ptr(length, nat.i64p), max_count, C.byref(count))
-            out += [(float(reward[i]), int(length[i])) for i in range(count.value)]
-            if count.value < max_count:
-                return out
-
-    def actors_get(self, name):
-        if name == "batch_rows":
-            out = np.zeros(1, np.int32)
-            self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
-            return int(out[0])
-        dtype, width = ACTOR_FIELDS[name]
-        width = {"S": self.S, "A": self.num_actions}.get(width, width)
-        rows = self.actors_get("batch_rows") if name.startswith("batch_") else self.num_actors
-        out = np.zeros((rows, width) if width > 1 else (rows,), dtype)
-        self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
-        return out
-
-    def actors_set(self, name, value):
-        value = np.ascontiguousarray(value, dtype=ACTOR_FIELDS[name][0])
-        self._call("actors_set", name.encode(), value.ctypes.data_as(C.c_void_p), value.nbytes)

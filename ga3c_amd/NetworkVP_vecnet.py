@@ -8,7 +8,8 @@ save, load, get_global_step, get_variables_names, get_variable_value, and the ze
 front-end, no state cache and no data-parallel or Hogwild training: Server refuses those settings with these networks.
 
 A subclass states PREFIX, LOGITS_PER_ACTION, ACTIVATION_WIDTHS / ACTIVATION_TAGS (or its own evaluate), DUAL_RMSPROP_REFUSAL
-(None where its handle takes the flag), _config() and _variables().
+(None where its handle takes the flag), _config() and _variables().  DeviceActors is the mixin of the two whose handles
+step their own environments (Config.DEVICE_AGENTS): the actors_* methods over <PREFIX>_actors_*.
 """
 import ctypes as C
 import glob
@@ -304,3 +305,54 @@ class VectorNetwork(NativeHandle):
             np.savez(tmp, **out)
             os.replace(tmp, "logs/%s/histograms_%08d.npz" % (self.model_name, training_step))
         return losses
+
+
+class DeviceActors:
+    """Config.DEVICE_AGENTS: the <PREFIX>_actors_* entries of a vector-state network whose handle steps its
+    environments itself (csrc/ga3c_actors.hpp).  Mixed into NetworkVP_discrate.Network (CartPole-v0) and
+    NetworkVP_vector.Network (Pendulum-v0); each states ACTOR_FIELDS, what <PREFIX>_actors_get names per environment:
+    {name: (dtype, elements -- a number, "S" or "A")}, "batch_*" being rows of the last step's batch instead."""
+    ACTOR_FIELDS = {}
+
+    def actors_create(self, n, time_max=None, discount=None, seed=None):
+        self._call("actors_create", int(n), int(Config.TIME_MAX if time_max is None else time_max),
+                   float(Config.DISCOUNT if discount is None else discount), int(Config.RANDOM_SEED if seed is None else seed))
+        self.num_actors = int(n)
+
+    def actors_destroy(self):
+        self._call("actors_destroy")
+
+    def actors_run(self, steps, train=True):
+        """`steps` actor steps at the model's learning_rate and beta -> (agent steps, train calls, rows trained, episodes
+        finished)."""
+        stats = np.zeros(4, np.int64)
+        self._call("actors_run", int(steps), float(self.learning_rate), float(self.beta), int(bool(train)),
+                   nat.ptr(stats, nat.i64p))
+        return tuple(int(t) for t in stats)
+
+    def actors_episodes(self, max_count=4096):
+        """The finished episodes not yet taken, oldest first -> [(total_reward, total_length)]."""
+        out = []
+        reward, length, count = np.empty(max_count, np.float64), np.empty(max_count, np.int64), C.c_int32()
+        while True:
+            self._call("actors_episodes", nat.ptr(reward, nat.f64p), nat.ptr(length, nat.i64p), max_count, C.byref(count))
+            out += [(float(reward[i]), int(length[i])) for i in range(count.value)]
+            if count.value < max_count:
+                return out
+
+    def actors_get(self, name):
+        if name == "batch_rows":
+            out = np.zeros(1, np.int32)
+            self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
+            return int(out[0])
+        dtype, width = self.ACTOR_FIELDS[name]
+        vector = width != 1                         # "S" / "A" fields are [rows, width] whatever the width, the others [rows]
+        width = {"S": self.S, "A": self.num_actions}.get(width, width)
+        rows = self.actors_get("batch_rows") if name.startswith("batch_") else self.num_actors
+        out = np.zeros((rows, width) if vector else (rows,), dtype)
+        self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
+
+    def actors_set(self, name, value):
+        value = np.ascontiguousarray(value, dtype=self.ACTOR_FIELDS[name][0])
+        self._call("actors_set", name.encode(), value.ctypes.data_as(C.c_void_p), value.nbytes)

@@ -10,12 +10,19 @@ ga3c_mlp_create and ga3c_mlp_evaluate take.
 import numpy as np
 
 from Config import Config
-from NetworkVP_vecnet import VectorNetwork
+from NetworkVP_vecnet import DeviceActors, VectorNetwork
 import _native as nat
 
 TRUNK = (("dense11_p", 4), ("dense12_p", 256), ("dense13_p", 256), ("dense14_p", 100), ("dense1", 64))
 HEADS = ("logits_v", "logits_p/out_x", "logits_p/out_y")
 INIT = 0.3                  # dense_layer's U(-0.3, 0.3), weights and biases alike (NetworkVP.py:194-204)
+# what ga3c_mlp_actors_get names, per environment: dtype and elements ("batch_*": rows of the last step's batch instead).
+# "phys" is (th, thdot); "action" is the action vector, the prediction row the step took; "u" stays -1: no draw for an action
+ACTOR_FIELDS = {"phys": (np.float64, 2), "elapsed": (np.int32, 1), "time_count": (np.int32, 1), "started": (np.int32, 1),
+                "draws": (np.uint64, 1), "obs": (np.float32, "S"), "p": (np.float32, "A"), "v": (np.float32, 1),
+                "u": (np.float64, 1), "action": (np.float32, "A"), "reward": (np.float64, 1), "done": (np.int32, 1),
+                "cut": (np.int32, 1), "rollout_len": (np.int32, 1),
+                "batch_x": (np.float32, "S"), "batch_y_r": (np.float32, 1), "batch_a": (np.float32, "A")}
 
 
 def param_order():
@@ -39,12 +46,13 @@ def initial_arena(state_dim, num_actions, seed):
     return np.concatenate([rng.uniform(-INIT, INIT, size=shapes[k]).astype(np.float32).ravel() for k in param_order()])
 
 
-class Network(VectorNetwork):
+class Network(DeviceActors, VectorNetwork):
     PREFIX = "ga3c_mlp"
     LOGITS_PER_ACTION = 2         # z = [hx | hy]
     ACTIVATION_WIDTHS = (4, 256, 64)                                              # pd1, pd2, d1
     ACTIVATION_TAGS = ("activation_pd1", "activation_pd2", "activation_d2")      # NetworkVP.py:150-170
     DUAL_RMSPROP_REFUSAL = None   # Config.DUAL_RMSPROP: one optimizer per cost, arenas 4 / 5 / 6
+    ACTOR_FIELDS = ACTOR_FIELDS   # device actors (Config.DEVICE_PENDULUM): ga3c_mlp_actors_*, Pendulum-v0
 
     def _config(self):
         cfg = nat.MlpConfig()

@@ -105,7 +105,8 @@ class Server:
         self.model = model if model is not None else model_cls(Config.DEVICE, Config.NETWORK_NAME, self.num_actions,
                                                                self.state_dim, **model_kw)
         if self.device_agent_count and not hasattr(self.model, "actors_run"):
-            raise RuntimeError("DEVICE_AGENTS needs a model with the actors_* entry points (NetworkVP_discrate.Network)")
+            raise RuntimeError("DEVICE_AGENTS needs a model with the actors_* entry points (NetworkVP_discrate.Network, "
+                               "NetworkVP_vector.Network)")
         # training_q.get() frees a queue entry at once (ThreadTrainer.py:49); zero-copy trainers keep a rollout's slot
         # until the GPU has read it, so the slots they hold come on top of the queue bound
         slots = int(Config.ROLLOUT_SLOTS)

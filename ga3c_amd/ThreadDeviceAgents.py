@@ -1,6 +1,7 @@
 """Config.DEVICE_AGENTS > 0: the one worker thread of a server whose agents live on the device.  It stands
-for every ProcessAgent, ThreadPredictor and ThreadTrainer at once: the model steps DEVICE_AGENTS CartPole environments,
-predicts for them and trains on the rollouts they cut, all in HBM (NetworkVP_discrate.Network.actors_run), and this loop
+for every ProcessAgent, ThreadPredictor and ThreadTrainer at once: the model steps DEVICE_AGENTS environments (CartPole-v0,
+or Pendulum-v0 with DEVICE_PENDULUM), predicts for them and trains on the rollouts they cut, all in HBM
+(NetworkVP_vecnet.DeviceActors.actors_run), and this loop
 only asks for the next DEVICE_AGENT_STEPS steps, hands the finished episodes to the statistics process in the order they
 finished and keeps the server's counters.  learning_rate and beta are the model's, which Server.main anneals."""
 import queue
@@ -16,7 +17,7 @@ class ThreadDeviceAgents(Thread):
         self.daemon = True
         self.server = server
         self.exit_flag = False
-        self.served = 0                 # predictions the actors drew an action from
+        self.served = 0                 # predictions the actors took an action from
         self.agent_steps = 0
         self.episodes = 0
 
@@ -46,7 +47,7 @@ class ThreadDeviceAgents(Thread):
             while not self.exit_flag:
                 steps, calls, rows, _ = model.actors_run(chunk, train=bool(Config.TRAIN_MODELS))
                 self.agent_steps += steps
-                self.served += steps - (n if first else 0)      # an environment's first ever step is action 0, unpredicted
+                self.served += steps - (n if first else 0)      # an environment's first ever step is unpredicted
                 first = False
                 server.training_step += calls
                 server.frame_counter += rows

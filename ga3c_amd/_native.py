@@ -155,6 +155,13 @@ HIP_SIGNATURES = {
     "ga3c_dmlp_actors_episodes": (C.c_int, [C.c_void_p, f64p, i64p, C.c_int32, i32p]),
     "ga3c_dmlp_actors_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "ga3c_dmlp_actors_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    # ... and of the Pendulum network (Config.DEVICE_PENDULUM): ga3c_mlp_actors_*, the same six signatures
+    "ga3c_mlp_actors_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int64]),
+    "ga3c_mlp_actors_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_mlp_actors_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, i64p]),
+    "ga3c_mlp_actors_episodes": (C.c_int, [C.c_void_p, f64p, i64p, C.c_int32, i32p]),
+    "ga3c_mlp_actors_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "ga3c_mlp_actors_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     # DDPG (USE_DDPG), include/ga3c_abi.h: ga3c_ddpg_*
     "ga3c_ddpg_create": (C.c_int, [C.POINTER(DdpgConfig), C.POINTER(C.c_void_p)]),
     "ga3c_ddpg_destroy": (C.c_int, [C.c_void_p]),

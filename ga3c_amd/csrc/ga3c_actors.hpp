@@ -1,23 +1,26 @@
 // ga3c_actors.hpp -- actors that live on the device (Config.DEVICE_AGENTS): N environments, their rollouts and
 // their training rows stay in HBM, and a vector-state network's handle steps them with the kernels below between its own
 // predict and train kernels, which it reaches through the Net hooks of ga3c_vecnet.hpp (rows, enqueue_train).  Nothing here
-// asks which network it serves; the one game-specific piece is the Env parameter (CartPole below).
+// asks which network it serves; the one game-specific piece is the Env parameter (CartPole and Pendulum below).
 //
 // One actor step of the handle, all on its one stream:
 //   rows(PREDICT) on the observation buffer             the network's own kernel, untouched
-//   actors_step_kernel<Env>   one thread per environment: draw the action (action 0 on an environment's first ever step),
-//                             f64 physics, reward, done, append to the rollout ring, cut the rollout (done, or
+//   actors_step_kernel<Env>   one thread per environment: draw the action (action 0 on an environment's first ever step;
+//                             Env::CONTINUOUS: no draw, the action is the prediction row, the zero vector on the first
+//                             step), f64 physics, reward, done, append to the rollout ring, cut the rollout (done, or
 //                             time_count == TIME_MAX), its returns, the episode record and the reset
-//   actors_compact_kernel     one workgroup: an exclusive scan over the environments' cut rollouts and finished episodes
+//   actors_compact_kernel<Env>  one workgroup: an exclusive scan over the environments' cut rollouts and finished episodes
 //                             lays the rows out as one batch in environment order (offsets into the rings, y_r, one-hot
-//                             actions) and appends the episode records to the episode ring in environment order
+//                             actions or the action vectors) and appends the episode records to the episode ring in
+//                             environment order
 //   enqueue_train on the batch, when the step cut any rollout
 // The host reads the batch's row count between the two halves (one 12-byte copy and an event wait per step): the train
 // kernels take their row count as an argument.  No kernel is persistent, none waits for another workgroup, none launches
 // from the device, and every loop is bounded by an argument.  No float atomics: the same seed gives the same bits.
 //
-// What the step restates is ProcessAgent.run_episode / run over EnvironmentCart.Environment with ga3c_returns_fork and
-// ga3c_select_action (ga3c_host.cpp); tests/device_agents_oracle.py is the same statement in numpy.  The f64 arithmetic is
+// What the step restates is ProcessAgent.run_episode / run over EnvironmentCart.Environment (EnvironmentPend.Environment for
+// Pendulum) with ga3c_returns_fork and ga3c_select_action (ga3c_host.cpp); tests/device_agents_oracle.py and
+// tests/device_pendulum_oracle.py are the same statement in numpy.  The f64 arithmetic is
 // compiled with contraction off, as the host library's is.  The uniforms are the one deviation: a stateless function of
 // (seed, environment, draw number), actor_uniform (ga3c_uniform.hpp).
 #pragma once
@@ -60,11 +63,17 @@ __device__ inline int select_action(const float* p, int n, double u) {
   return n - 1;
 }
 
+// An Env states: S observation floats, P f64 physics values, A actions (CONTINUOUS: the width of the action vector),
+// RESET_DRAWS uniforms per reset, step (an action index, or CONTINUOUS the f32 action vector), observe (physics -> what the
+// network reads) and reset.
+
 // gym's CartPole-v0 under its TimeLimit, as EnvironmentCart.py restates it, with the reference's wrapper: reward r * 0.005 - 1.
 struct CartPole {
   static constexpr int S = 4;          // observation = f32 of the physics
+  static constexpr int P = 4;
   static constexpr int A = 2;
   static constexpr int RESET_DRAWS = 4;
+  static constexpr bool CONTINUOUS = false;
 
   __device__ static void step(double* s, int action, int* elapsed, double* reward, int* done) {
 #pragma clang fp contract(off)
@@ -89,6 +98,10 @@ struct CartPole {
     *reward = 1.0 * 0.005 - 1.0;
   }
 
+  __device__ static void observe(const double* s, float* obs) {
+    for (int k = 0; k < S; ++k) obs[k] = (float)s[k];
+  }
+
   // U(-0.05, 0.05)^4 as numpy draws it, low + (high - low) u; the observation is left alone
   __host__ __device__ static void reset(double* s, int* elapsed, const double* u) {
 #pragma clang fp contract(off)
@@ -98,19 +111,73 @@ struct CartPole {
   }
 };
 
+// gym's Pendulum-v0 under its TimeLimit, as EnvironmentPend.py restates it (Pendulum.step / reset), with the reference's
+// wrapper (Environment.step): torque 2 a, reward -cost * 0.005 - 1.  Physics (th, thdot); observation [cos th, sin th, thdot].
+// Two branches of the host's statement are absent because the device cannot reach them: the action is the
+// network's atan2f(Y, X) / PI_F, which lies in [-1, 1] (the zero vector on the first step), so check_bounds(a, 1, -1,
+// turnaround) returns it as it is, and 2 a lies in [-2, 2], so clip(u, -2, 2) does too.
+struct Pendulum {
+  static constexpr int S = 3;
+  static constexpr int P = 2;
+  static constexpr int A = 1;
+  static constexpr int RESET_DRAWS = 2;
+  static constexpr bool CONTINUOUS = true;
+
+  // numpy's float remainder: ((x + pi) % (2 pi)) - pi
+  __device__ static double angle_normalize(double x) {
+#pragma clang fp contract(off)
+    const double pi = 3.141592653589793;
+    double m = fmod(x + pi, 2 * pi);
+    if (m < 0) m += 2 * pi;
+    return m - pi;
+  }
+
+  __device__ static void step(double* s, const float* a, int* elapsed, double* reward, int* done) {
+#pragma clang fp contract(off)
+    const double pi = 3.141592653589793, dt = 0.05, max_speed = 8.0;
+    const double th = s[0], thdot = s[1];
+    const double u = (double)a[0] * 2.0;
+    const double an = angle_normalize(th);
+    const double cost = an * an + 0.1 * (thdot * thdot) + 0.001 * (u * u);
+    double newthdot = thdot + (-15.0 * sin(th + pi) + 3.0 * u) * dt;      // -3 g / (2 l) = -15, 3 / (m l^2) = 3
+    const double newth = th + newthdot * dt;
+    newthdot = newthdot < -max_speed ? -max_speed : (newthdot > max_speed ? max_speed : newthdot);   // after th' has used it
+    s[0] = newth; s[1] = newthdot;
+    *elapsed += 1;
+    *done = *elapsed >= 200 ? 1 : 0;
+    *reward = -cost * 0.005 - 1.0;
+  }
+
+  __device__ static void observe(const double* s, float* obs) {
+    obs[0] = (float)cos(s[0]);
+    obs[1] = (float)sin(s[0]);
+    obs[2] = (float)s[1];
+  }
+
+  // th ~ U(-pi, pi), thdot ~ U(-1, 1) as numpy draws them, low + (high - low) u; the observation is left alone
+  __host__ __device__ static void reset(double* s, int* elapsed, const double* u) {
+#pragma clang fp contract(off)
+    const double pi = 3.141592653589793;
+    s[0] = -pi + (pi - -pi) * u[0];
+    s[1] = -1.0 + (1.0 - -1.0) * u[1];
+    *elapsed = 0;
+  }
+};
+
 // Everything the kernels touch, by device address.  Per environment unless said otherwise; T1 = TIME_MAX + 1.
 struct State {
-  int N, T1, S, A, time_max, ep_cap;
+  int N, T1, S, P, A, time_max, ep_cap;
   double gamma;
   uint64_t seed;
-  double* phys;              // [N][S] f64 physics
+  double* phys;              // [N][P] f64 physics
   int* elapsed;
   int* time_count;
   int* started;              // 0 until the first ever step: no observation yet (the host's current_state is None)
   uint64_t* draws;           // uniforms drawn so far
   float* obs;                // [N][S] what the network reads
   float* ring_x;             // [N][T1][S] the rollout: states, ...
-  int* ring_a;               // [N][T1]    actions, ...
+  int* ring_a;               // [N][T1]    actions (Env::CONTINUOUS: none, ring_av [N][T1][A] f32 action vectors), ...
+  float* ring_av;
   double* ring_r;            // [N][T1]    rewards; row t of the rollout is slot (head + t) % T1
   int* head;
   int* rlen;
@@ -119,7 +186,8 @@ struct State {
   long long* total_length;
   float* p; float* v; float* z;   // [N][A], [N], [N][ZW]: the last prediction
   double* u;                 // the last step's uniform (-1: none drawn), action, reward, done
-  int* action;
+  int* action;               // (Env::CONTINUOUS: none, action_v [N][A] f32)
+  float* action_v;
   double* reward;
   int* done;
   int* cut;                  // rows of the rollout this step cut (0: none), where it starts in the ring, its returns [N][T1]
@@ -130,7 +198,7 @@ struct State {
   long long* ep_length;
   int64_t* off;              // [N T1] the batch: byte offsets of its rows from ring_x, environment order
   float* by;                 // [N T1] y_r     (the handle's train staging)
-  float* ba;                 // [N T1][A] one-hot
+  float* ba;                 // [N T1][A] one-hot (Env::CONTINUOUS: the action vectors)
   int* counts;               // [3]: rows of the batch, records in the episode ring, episodes this step finished
   double* ring_ep_reward;    // [ep_cap] the episode ring, in the order the episodes finished
   long long* ring_ep_length;
@@ -141,35 +209,42 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * STEP_THREADS + threadIdx.x;
   if (i >= a.N) return;
-  constexpr int S = Env::S;
+  constexpr int S = Env::S, P = Env::P, A = Env::A;
   const int T1 = a.T1;
-  double s[S];
-  for (int k = 0; k < S; ++k) s[k] = a.phys[(size_t)i * S + k];
+  double s[P];
+  for (int k = 0; k < P; ++k) s[k] = a.phys[(size_t)i * P + k];
   int elapsed = a.elapsed[i];
   uint64_t draws = a.draws[i];
   const bool started = a.started[i] != 0;
   a.cut[i] = 0;
   a.ep_flag[i] = 0;
 
-  int action = 0;
+  [[maybe_unused]] int action = 0;
+  [[maybe_unused]] float av[A];                          // CONTINUOUS: the action is the prediction row, no draw; step(None) is the zero vector
   double u = -1.0;
-  if (started) {
-    u = actor_uniform(a.seed, (uint64_t)i, draws++);
-    action = select_action(a.p + (size_t)i * a.A, a.A, u);
-  }
   double reward;
   int done;
-  Env::step(s, action, &elapsed, &reward, &done);
+  if constexpr (Env::CONTINUOUS) {
+    for (int j = 0; j < A; ++j) {
+      av[j] = started ? a.p[(size_t)i * A + j] : 0.f;
+      a.action_v[(size_t)i * A + j] = av[j];
+    }
+    Env::step(s, av, &elapsed, &reward, &done);
+  } else {
+    if (started) {
+      u = actor_uniform(a.seed, (uint64_t)i, draws++);
+      action = select_action(a.p + (size_t)i * a.A, a.A, u);
+    }
+    Env::step(s, action, &elapsed, &reward, &done);
+    a.action[i] = action;
+  }
   a.u[i] = u;
-  a.action[i] = action;
   a.reward[i] = reward;
   a.done[i] = done;
   float* obs = a.obs + (size_t)i * S;
   if (!started) {                       // the host's step(None): no experience, and its `done` is not looked at
-    for (int k = 0; k < S; ++k) {
-      a.phys[(size_t)i * S + k] = s[k];
-      obs[k] = (float)s[k];
-    }
+    for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
+    Env::observe(s, obs);
     a.elapsed[i] = elapsed;
     a.started[i] = 1;
     return;
@@ -180,11 +255,15 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
     const int slot = (head + rlen) % T1;
     float* row = a.ring_x + ((size_t)i * T1 + slot) * S;
     for (int k = 0; k < S; ++k) row[k] = obs[k];
-    a.ring_a[(size_t)i * T1 + slot] = action;
+    if constexpr (Env::CONTINUOUS) {
+      for (int j = 0; j < A; ++j) a.ring_av[((size_t)i * T1 + slot) * A + j] = av[j];
+    } else {
+      a.ring_a[(size_t)i * T1 + slot] = action;
+    }
     a.ring_r[(size_t)i * T1 + slot] = reward;
     ++rlen;
   }
-  for (int k = 0; k < S; ++k) obs[k] = (float)s[k];
+  Env::observe(s, obs);
   double rsum = a.reward_sum[i] + reward;
 
   if (done || tc == a.time_max || rlen == T1) {
@@ -223,7 +302,7 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
     a.total_length[i] = length;
   }
   if (!done) tc += 1;                   // (a new episode starts at time_count 0)
-  for (int k = 0; k < S; ++k) a.phys[(size_t)i * S + k] = s[k];
+  for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
   a.elapsed[i] = elapsed;
   a.draws[i] = draws;
   a.head[i] = head;
@@ -234,6 +313,7 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
 
 // One workgroup.  Thread t owns the environments [t c, (t + 1) c), c = ceil(N / SCAN_THREADS); the scan over the threads'
 // sums gives each its first batch row and its first episode record.
+template <class Env>
 __global__ __launch_bounds__(SCAN_THREADS) void actors_compact_kernel(State a) {
   __shared__ int srow[SCAN_THREADS];
   __shared__ int sep[SCAN_THREADS];
@@ -264,8 +344,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void actors_compact_kernel(State a) {
       const int slot = (h + k) % T1;
       a.off[row] = ((int64_t)i * T1 + slot) * a.S * (int64_t)sizeof(float);
       a.by[row] = a.cut_y[(size_t)i * T1 + k];
-      const int act = a.ring_a[(size_t)i * T1 + slot];
-      for (int j = 0; j < A; ++j) a.ba[(size_t)row * A + j] = j == act ? 1.0f : 0.0f;
+      if constexpr (Env::CONTINUOUS) {
+        for (int j = 0; j < A; ++j) a.ba[(size_t)row * A + j] = a.ring_av[((size_t)i * T1 + slot) * A + j];
+      } else {
+        const int act = a.ring_a[(size_t)i * T1 + slot];
+        for (int j = 0; j < A; ++j) a.ba[(size_t)row * A + j] = j == act ? 1.0f : 0.0f;
+      }
     }
     if (a.ep_flag[i]) {
       if (ep < a.ep_cap) {
@@ -325,10 +409,11 @@ int actors_create(N* m, int n, int time_max, double discount, int64_t seed) {
   Actors* a = new (std::nothrow) Actors();
   if (!a) return fail(GA3C_EINVAL, "out of host memory");
   State& d = a->d;
-  d.N = n; d.T1 = (int)T1; d.S = m->S; d.A = m->A; d.time_max = time_max; d.ep_cap = n * MAX_STEPS;
+  d.N = n; d.T1 = (int)T1; d.S = m->S; d.P = Env::P; d.A = m->A; d.time_max = time_max; d.ep_cap = n * MAX_STEPS;
   d.gamma = discount;
   d.seed = (uint64_t)seed;
-  const size_t Nn = (size_t)n, S = (size_t)m->S, A = (size_t)m->A, R = Nn * (size_t)T1, ZW = (size_t)m->ZW;
+  const size_t Nn = (size_t)n, S = (size_t)m->S, P = (size_t)Env::P, A = (size_t)m->A, R = Nn * (size_t)T1, ZW = (size_t)m->ZW;
+  const size_t AI = Env::CONTINUOUS ? 0 : 1, AV = Env::CONTINUOUS ? A : 0;      // per row: an action index or an action vector
   // two passes over one list: sizes, then addresses (each buffer 16-byte aligned)
   size_t total = 0;
   for (int pass = 0; pass < 2; ++pass) {
@@ -338,10 +423,10 @@ int actors_create(N* m, int n, int time_max, double discount, int64_t seed) {
       if (pass) *p = reinterpret_cast<T*>(a->block + at);
       at += (count * sizeof(T) + 15) / 16 * 16;
     };
-    carve(&d.phys, Nn * S); carve(&d.elapsed, Nn); carve(&d.time_count, Nn); carve(&d.started, Nn); carve(&d.draws, Nn);
-    carve(&d.obs, Nn * S); carve(&d.ring_x, R * S); carve(&d.ring_a, R); carve(&d.ring_r, R); carve(&d.head, Nn);
+    carve(&d.phys, Nn * P); carve(&d.elapsed, Nn); carve(&d.time_count, Nn); carve(&d.started, Nn); carve(&d.draws, Nn);
+    carve(&d.obs, Nn * S); carve(&d.ring_x, R * S); carve(&d.ring_a, R * AI); carve(&d.ring_av, R * AV); carve(&d.ring_r, R); carve(&d.head, Nn);
     carve(&d.rlen, Nn); carve(&d.reward_sum, Nn); carve(&d.total_reward, Nn); carve(&d.total_length, Nn);
-    carve(&d.p, Nn * A); carve(&d.v, Nn); carve(&d.z, Nn * ZW); carve(&d.u, Nn); carve(&d.action, Nn); carve(&d.reward, Nn);
+    carve(&d.p, Nn * A); carve(&d.v, Nn); carve(&d.z, Nn * ZW); carve(&d.u, Nn); carve(&d.action, Nn * AI); carve(&d.action_v, Nn * AV); carve(&d.reward, Nn);
     carve(&d.done, Nn); carve(&d.cut, Nn); carve(&d.cut_head, Nn); carve(&d.cut_y, R); carve(&d.ep_flag, Nn);
     carve(&d.ep_reward, Nn); carve(&d.ep_length, Nn); carve(&d.off, R); carve(&d.counts, 3);
     carve(&d.ring_ep_reward, (size_t)d.ep_cap); carve(&d.ring_ep_length, (size_t)d.ep_cap);
@@ -357,15 +442,15 @@ int actors_create(N* m, int n, int time_max, double discount, int64_t seed) {
   }
   d.by = m->d_y;
   d.ba = m->d_a;
-  // an environment starts as the host's does: reset() when it is made (draws 0..3) and again when its first episode begins
-  // (draws 4..7), no observation
-  std::vector<double> phys(Nn * S);
+  // an environment starts as the host's does: reset() when it is made (draws 0..RESET_DRAWS-1) and again when its first
+  // episode begins (the next RESET_DRAWS), no observation
+  std::vector<double> phys(Nn * P);
   std::vector<uint64_t> draws(Nn, 2 * Env::RESET_DRAWS);
   for (size_t i = 0; i < Nn; ++i) {
     double ru[Env::RESET_DRAWS];
     int elapsed = 0;
     for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = actor_uniform(d.seed, i, (uint64_t)(Env::RESET_DRAWS + k));
-    Env::reset(&phys[i * S], &elapsed, ru);
+    Env::reset(&phys[i * P], &elapsed, ru);
   }
   if (hipMemcpy(d.phys, phys.data(), phys.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d.draws, draws.data(), draws.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
@@ -374,12 +459,14 @@ int actors_create(N* m, int n, int time_max, double discount, int64_t seed) {
     return fail(GA3C_EHIP, "copy to the device actors failed");
   }
   a->fields = {
-      {"phys", d.phys, 8, S, true},          {"elapsed", d.elapsed, 4, 1, true},     {"time_count", d.time_count, 4, 1, true},
+      {"phys", d.phys, 8, P, true},          {"elapsed", d.elapsed, 4, 1, true},     {"time_count", d.time_count, 4, 1, true},
       {"started", d.started, 4, 1, true},    {"draws", d.draws, 8, 1, true},         {"obs", d.obs, 4, S, true},
       {"rollout_len", d.rlen, 4, 1, false},  {"p", d.p, 4, A, false},                {"v", d.v, 4, 1, false},
-      {"u", d.u, 8, 1, false},               {"action", d.action, 4, 1, false},      {"reward", d.reward, 8, 1, false},
+      {"u", d.u, 8, 1, false},               {"reward", d.reward, 8, 1, false},
       {"done", d.done, 4, 1, false},         {"cut", d.cut, 4, 1, false},
   };
+  if (Env::CONTINUOUS) a->fields.push_back({"action", d.action_v, 4, A, false});
+  else a->fields.push_back({"action", d.action, 4, 1, false});
   m->actors = a;
   return GA3C_OK;
 }
@@ -434,7 +521,7 @@ int actors_run(N* m, int steps, float lr, float beta, int train, int64_t* stats)
       std::lock_guard<std::mutex> lk(m->mu);
       m->rows(PREDICT, Input{reinterpret_cast<const char*>(d.obs), nullptr, 4 * (int64_t)d.S}, d.N, 0.f, d.p, d.v, d.z);
       hipLaunchKernelGGL(actors_step_kernel<Env>, dim3((d.N + STEP_THREADS - 1) / STEP_THREADS), dim3(STEP_THREADS), 0, m->st, d);
-      hipLaunchKernelGGL(actors_compact_kernel, dim3(1), dim3(SCAN_THREADS), 0, m->st, d);
+      hipLaunchKernelGGL(actors_compact_kernel<Env>, dim3(1), dim3(SCAN_THREADS), 0, m->st, d);
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(a->h_counts, d.counts, 3 * sizeof(int), hipMemcpyDeviceToHost, m->st));
       HIPCHK(hipEventRecord(m->tev, m->st));

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "ga3c_actors.hpp"
 #include "ga3c_tile.hpp"
 #include "ga3c_vecnet.hpp"
 
@@ -430,6 +431,7 @@ struct ga3c_mlp : Net {
   Layout L;
   WorkDual w{};                   // del_v: dual only
   float* work_base = nullptr;
+  ga3c_actors::Actors* actors = nullptr;   // Config.DEVICE_AGENTS with DEVICE_PENDULUM: the environments this handle steps itself (ga3c_actors.hpp)
 
   int alloc_work(size_t B) {      // per-row workspace, one block
     const size_t S = L.S, A = L.A;
@@ -588,7 +590,13 @@ int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out) {
   return create(m, out);
 }
 
-int ga3c_mlp_destroy(ga3c_mlp* m) { return destroy(m); }
+int ga3c_mlp_destroy(ga3c_mlp* m) {
+  if (m) {
+    (void)hipSetDevice(m->device);
+    ga3c_actors::actors_drop(m);      // whatever state the stream is in: the handle goes on to be destroyed
+  }
+  return destroy(m);
+}
 
 int ga3c_mlp_param_count(ga3c_mlp* m, int64_t* count) { return param_count(m, count); }
 
@@ -689,6 +697,32 @@ int ga3c_mlp_fetch(ga3c_mlp* m, const char* name, float* out, int64_t count) {
   const float* src = work_ptr(m, name);
   if (wd < 0 || !src) return fail(GA3C_EINVAL, "no activation named %s", name);
   return fetch(m, name, src, wd, out, count);
+}
+
+// ---- device actors: Pendulum environments stepped by this handle, ga3c_actors.hpp
+
+int ga3c_mlp_actors_create(ga3c_mlp* m, int32_t n, int32_t time_max, double discount, int64_t seed) {
+  return ga3c_actors::actors_create<ga3c_actors::Pendulum>(m, n, time_max, discount, seed);
+}
+
+int ga3c_mlp_actors_destroy(ga3c_mlp* m) { return ga3c_actors::actors_destroy(m); }
+
+int ga3c_mlp_actors_run(ga3c_mlp* m, int32_t steps, float learning_rate, float beta, int32_t train, int64_t* out_stats) {
+  return ga3c_actors::actors_run<ga3c_actors::Pendulum>(m, steps, learning_rate, beta, train, out_stats);
+}
+
+int ga3c_mlp_actors_episodes(ga3c_mlp* m, double* total_reward, int64_t* total_length, int32_t max, int32_t* count) {
+  return ga3c_actors::actors_episodes(m, total_reward, total_length, max, count);
+}
+
+int ga3c_mlp_actors_get(ga3c_mlp* m, const char* name, void* out, int64_t bytes) {
+  if (!out) return fail(GA3C_EINVAL, "null argument");
+  return ga3c_actors::actors_access(m, name, out, nullptr, bytes);
+}
+
+int ga3c_mlp_actors_set(ga3c_mlp* m, const char* name, const void* in, int64_t bytes) {
+  if (!in) return fail(GA3C_EINVAL, "null argument");
+  return ga3c_actors::actors_access(m, name, nullptr, in, bytes);
 }
 
 }  // extern "C"

@@ -534,6 +534,25 @@ int ga3c_dmlp_actors_episodes(ga3c_dmlp* net, double* total_reward, int64_t* tot
 int ga3c_dmlp_actors_get(ga3c_dmlp* net, const char* name, void* out, int64_t bytes);
 int ga3c_dmlp_actors_set(ga3c_dmlp* net, const char* name, const void* in, int64_t bytes);
 
+/* ---- Device actors of the Pendulum network (Config.DEVICE_AGENTS with DEVICE_PENDULUM): n Pendulum-v0 environments
+ * on a ga3c_mlp handle.  Signatures, return codes and the step's bookkeeping are those of ga3c_dmlp_actors_* above; what differs
+ * is the environment and the action.  What a step restates is ProcessAgent.run_episode / run over EnvironmentPend.Environment:
+ * there is no draw for an action -- under CONTINUOUS_INPUT the action is the prediction row p (A = 1 f32), the zero vector on an
+ * environment's first ever step -- so "u" stays -1 and "draws" advances only at a reset, which takes two uniforms (th = -pi +
+ * 2 pi u0, thdot = -1 + 2 u1; create passes over draws 0..1, draws 2..3 are the first physics).  Torque 2 a, f64 physics
+ * (th, thdot), observation [cos th, sin th, thdot] computed in f64 and cast, reward -cost * 0.005 - 1, done after 200 steps.
+ * Every episode is 200 steps long, so the environments cut their rollouts on the same steps: one train step of n (time_max + 1)
+ * rows every time_max actor steps.
+ * create: the network must have S = 3 and A = 1 and n (time_max + 1) <= max_batch (GA3C_EINVAL).  destroy: also done by
+ * ga3c_mlp_destroy.  get / set names as above with "phys" f64[n,2], "obs" f32[n,3], "p" f32[n,1], "action" f32[n,1] (the action
+ * vector), "batch_x" f32[rows,3], "batch_a" f32[rows,1] (the action vectors). */
+int ga3c_mlp_actors_create(ga3c_mlp* net, int32_t n, int32_t time_max, double discount, int64_t seed);
+int ga3c_mlp_actors_destroy(ga3c_mlp* net);
+int ga3c_mlp_actors_run(ga3c_mlp* net, int32_t steps, float learning_rate, float beta, int32_t train, int64_t* out_stats);
+int ga3c_mlp_actors_episodes(ga3c_mlp* net, double* total_reward, int64_t* total_length, int32_t max, int32_t* count);
+int ga3c_mlp_actors_get(ga3c_mlp* net, const char* name, void* out, int64_t bytes);
+int ga3c_mlp_actors_set(ga3c_mlp* net, const char* name, const void* in, int64_t bytes);
+
 /* ---- DDPG: reference NetworkDDPG.py (USE_DDPG with CONTINUOUS_INPUT), with the replay memory in HBM.
  *   actor   x[B,S] -> actor_fc1 (400) -> actor_norm1 -> relu -> actor_fc2 (300) -> actor_norm2 -> relu -> actor_output (A, tanh)
  *   critic  x -> critic_fc1 (400) -> critic_norm1 -> relu = h;  q = critic_output(relu(h W_fc2 + a W_n2 + b_n2)), W_n2 / b_n2

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Development aid: agent steps per second of the device actors (Config.DEVICE_AGENTS, ga3c_dmlp_actors_run)
-with training on -- every step a prediction for N environments, the actor step, the compaction and, when the step cut a
-rollout, a train step on the cut rows.  Wall-clock around ga3c_dmlp_actors_run (the call returns when its steps are done:
+"""Development aid: agent steps per second of the device actors (Config.DEVICE_AGENTS; ga3c_dmlp_actors_run for --game
+CartPole-v0; ga3c_mlp_actors_run for --game Pendulum-v0) with training on -- every step a prediction for N environments, the actor step, the compaction and, when the step cut a
+rollout, a train step on the cut rows.  Wall-clock around <prefix>_actors_run (the call returns when its steps are done:
 the host reads a row count per step), median and min over rounds, one JSON line per N.  The figure to set it against is the
-PPS of the status line of `_train.sh GAME=CartPole-v0 AGENTS=16` (profiles/device_agents_step.txt).
-usage: python tools/device_agents_step.py [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]"""
+PPS of the status line of `_train.sh GAME=<game> AGENTS=16` (profiles/device_agents_step.txt, device_agents_pendulum.txt).
+Pendulum's environments run in lockstep: one train step of N (TIME_MAX + 1) rows every TIME_MAX actor steps.
+usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]"""
 import argparse
 import json
 import os
@@ -17,6 +18,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--game", choices=("CartPole-v0", "Pendulum-v0"), default="CartPole-v0")
     ap.add_argument("--agents", type=int, nargs="+", default=[256, 4096])
     ap.add_argument("--time-max", type=int, default=5)
     ap.add_argument("--steps", type=int, default=64, help="actor steps per native call (1..64)")
@@ -26,9 +28,14 @@ def main():
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
-    from NetworkVP_discrate import Network
+    if args.game == "Pendulum-v0":
+        from NetworkVP_vector import Network
+        num_actions, state_dim = 1, (3,)
+    else:
+        from NetworkVP_discrate import Network
+        num_actions, state_dim = 2, (4,)
     for n in args.agents:
-        net = Network("gpu:0", "device_agents_step", 2, (4,), max_batch=max(16, n * (args.time_max + 1)), predict_lanes=1)
+        net = Network("gpu:0", "device_agents_step", num_actions, state_dim, max_batch=max(16, n * (args.time_max + 1)), predict_lanes=1)
         net.learning_rate, net.beta = Config.LEARNING_RATE_START, Config.BETA_START
         net.actors_create(n, args.time_max, Config.DISCOUNT, Config.RANDOM_SEED)
         net.actors_run(args.steps, train=not args.no_train)               # warm-up; the rollouts are in step from here on
@@ -43,7 +50,7 @@ def main():
             net.actors_episodes()
         rates.sort()
         per_step_us = 1e6 * n / rates[len(rates) // 2]
-        print(json.dumps({"agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,
+        print(json.dumps({"game": args.game, "agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,
                           "agent_steps_per_s_median": round(rates[len(rates) // 2]), "agent_steps_per_s_min": round(rates[0]),
                           "agent_steps_per_s_max": round(rates[-1]), "actor_step_us_median": round(per_step_us, 1),
                           "train_calls": train_calls, "rows_trained": rows, "episodes": episodes, "rounds": args.rounds}),
