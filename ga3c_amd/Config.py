@@ -147,7 +147,7 @@ class Config:
     FRAME_HEIGHT = 210
     FRAME_WIDTH = 160
     FRAME_HISTORY = 0                   # planes of history per agent on the device; 0 = derived from the queue bounds
-    DEVICE_AGENTS = 0                   # > 0 (GAME = 'CartPole-v0', or 'Pendulum-v0' with DEVICE_PENDULUM): this many
+    DEVICE_AGENTS = 0                   # > 0 (GAME = 'CartPole-v0', or 'Pendulum-v0' with DEVICE_PENDULUM or DEVICE_DDPG): this many
                                         # environments, their rollouts and their training rows live in HBM and the server
                                         # steps them with HIP kernels; no agent process, predictor or trainer is started
                                         # (ThreadDeviceAgents.py)
@@ -155,6 +155,10 @@ class Config:
                                         # the environments run in lockstep, one train step of N (TIME_MAX + 1) rows every
                                         # TIME_MAX actor steps
     DEVICE_AGENT_STEPS = 32             # actor steps per native call of that loop (1..64)
+    DEVICE_DDPG = False                 # True (USE_DDPG, GAME = 'Pendulum-v0'): DEVICE_AGENTS environments step on the device under
+                                        # DDPG, write their transitions into the replay ring in HBM, and the handle draws its own
+                                        # train rows; no agent process, predictor, trainer or replay thread
+    DEVICE_DDPG_UPDATES = 1             # train steps after each actor step of that loop (1..16)
 
 
 VECTOR_GAMES = ('Pendulum-v0', 'CartPole-v0')      # games whose state is a vector (Server.py:35-43 of the reference)
@@ -247,18 +251,50 @@ def resolve_ddpg(explicit=()):
     Config.DISCOUNTING = False
 
 
+def _resolve_device_ddpg(n, pendulum):
+    """DEVICE_AGENTS = n > 0 with DEVICE_DDPG.  DISCOUNTING, RETURN_MODE, USE_INTERMEDIATE_REWARD and TIME_MAX are
+    not looked at: resolve_ddpg sets DISCOUNTING = False, and returns and rollout cuts play no part in a ring of transitions."""
+    if not Config.USE_DDPG:
+        raise ValueError("DEVICE_DDPG needs USE_DDPG: it puts the DDPG actors, replay writes and draws on the device")
+    if Config.GAME != 'Pendulum-v0':
+        raise ValueError("DEVICE_DDPG with GAME=%s is not supported: the device steps Pendulum-v0 under DDPG" % Config.GAME)
+    if pendulum:
+        raise ValueError("DEVICE_DDPG with DEVICE_PENDULUM is not supported: DEVICE_PENDULUM names the actor-critic regime "
+                         "(lockstep rollouts), DEVICE_DDPG the replay regime; set one of them")
+    if n > 4096:
+        raise ValueError("DEVICE_AGENTS=%d with DEVICE_DDPG: at most 4096 environments, the DDPG handle's max_batch limit" % n)
+    if n > Config.REPLAY_BUFFER_SIZE:
+        raise ValueError("DEVICE_AGENTS=%d exceeds REPLAY_BUFFER_SIZE=%d: one actor step's transitions must fit the ring"
+                         % (n, Config.REPLAY_BUFFER_SIZE))
+    if not 1 <= int(Config.DEVICE_DDPG_UPDATES) <= 16:
+        raise ValueError("DEVICE_DDPG_UPDATES=%r: 1 to 16 train steps per actor step" % (Config.DEVICE_DDPG_UPDATES,))
+    if Config.PLAY_MODE:
+        raise ValueError("DEVICE_AGENTS with PLAY_MODE is not supported: the device actors train as they step")
+    if Config.DYNAMIC_SETTINGS:
+        raise ValueError("DEVICE_AGENTS with DYNAMIC_SETTINGS is not supported: there are no workers to add or remove")
+    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+        raise ValueError("DEVICE_AGENTS with WORLD_SIZE > 1 is not supported")
+    if not 1 <= int(Config.DEVICE_AGENT_STEPS) <= 64:
+        raise ValueError("DEVICE_AGENT_STEPS=%r: 1 to 64 actor steps per call" % (Config.DEVICE_AGENT_STEPS,))
+
+
 def resolve_device_agents(explicit=()):
     """What DEVICE_AGENTS > 0 cannot be combined with.  Call after resolve_action_space and resolve_ddpg.  With
-    DEVICE_AGENTS = 0 nothing is checked and nothing changes."""
+    DEVICE_AGENTS = 0 nothing is checked and nothing changes, except that DEVICE_DDPG, which asks for them, raises."""
     n = int(Config.DEVICE_AGENTS)
     if n == 0:
+        if getattr(Config, "DEVICE_DDPG", False):
+            raise ValueError("DEVICE_DDPG needs DEVICE_AGENTS > 0: the number of environments on the device")
         return
     if n < 0:
         raise ValueError("DEVICE_AGENTS=%d: 0 (off) or the number of environments on the device" % n)
     pendulum = bool(getattr(Config, "DEVICE_PENDULUM", False))
+    if getattr(Config, "DEVICE_DDPG", False):
+        _resolve_device_ddpg(n, pendulum)
+        return
     if Config.USE_DDPG:
         raise ValueError("DEVICE_AGENTS with USE_DDPG is not supported: the device actors step CartPole-v0 only, or "
-                         "Pendulum-v0 under the actor-critic network (DEVICE_PENDULUM)")
+                         "Pendulum-v0 under the actor-critic network (DEVICE_PENDULUM); under DDPG they need DEVICE_DDPG=True")
     if pendulum and Config.GAME != 'Pendulum-v0':
         raise ValueError("DEVICE_PENDULUM with GAME=%s is not supported: it asks for Pendulum-v0 environments on the device"
                          % Config.GAME)

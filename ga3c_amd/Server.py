@@ -102,11 +102,15 @@ class Server:
         # (device agents: a train call takes every environment's rollout at once)
         model_kw = {"max_batch": max(Config.PREDICTION_BATCH_SIZE, self.device_agent_count * (Config.TIME_MAX + 1))} \
             if self.device_agent_count else {}
+        # DEVICE_DDPG: a prediction takes the N observations, a train step TRAINING_MIN_BATCH_SIZE rows of the ring
+        self.device_ddpg = bool(self.device_agent_count and getattr(Config, "DEVICE_DDPG", False))
+        if self.device_ddpg:
+            model_kw = {"max_batch": max(self.device_agent_count, Config.TRAINING_MIN_BATCH_SIZE)}
         self.model = model if model is not None else model_cls(Config.DEVICE, Config.NETWORK_NAME, self.num_actions,
                                                                self.state_dim, **model_kw)
         if self.device_agent_count and not hasattr(self.model, "actors_run"):
             raise RuntimeError("DEVICE_AGENTS needs a model with the actors_* entry points (NetworkVP_discrate.Network, "
-                               "NetworkVP_vector.Network)")
+                               "NetworkVP_vector.Network, NetworkDDPG.Network)")
         # training_q.get() frees a queue entry at once (ThreadTrainer.py:49); zero-copy trainers keep a rollout's slot
         # until the GPU has read it, so the slots they hold come on top of the queue bound
         slots = int(Config.ROLLOUT_SLOTS)
@@ -330,7 +334,7 @@ class Server:
         self._count_train_step(len(slots), None, None, None)
 
     def start_replay(self):
-        if self.ddpg and self.replay is None:
+        if self.ddpg and self.replay is None and not self.device_ddpg:     # DEVICE_DDPG: the ring is written and drawn on the device
             self.replay = ThreadReplay(self)
             self.replay.start()
 

@@ -3,7 +3,9 @@ for every ProcessAgent, ThreadPredictor and ThreadTrainer at once: the model ste
 or Pendulum-v0 with DEVICE_PENDULUM), predicts for them and trains on the rollouts they cut, all in HBM
 (NetworkVP_vecnet.DeviceActors.actors_run), and this loop
 only asks for the next DEVICE_AGENT_STEPS steps, hands the finished episodes to the statistics process in the order they
-finished and keeps the server's counters.  learning_rate and beta are the model's, which Server.main anneals."""
+finished and keeps the server's counters.  learning_rate and beta are the model's, which Server.main anneals.
+With DEVICE_DDPG the model is NetworkDDPG.Network: the environments write transitions into its replay ring, it
+trains on rows it draws itself (ThreadReplay is not started), and the ring's size goes to the status line."""
 import queue
 from datetime import datetime
 from threading import Thread
@@ -52,6 +54,8 @@ class ThreadDeviceAgents(Thread):
                 server.training_step += calls
                 server.frame_counter += rows
                 server.stats.training_count.value += calls
+                if hasattr(model, "replay_size"):       # DEVICE_DDPG: the rows the replay ring holds
+                    server.stats.replay_memory_size.value = model.replay_size()[0]
                 for reward, length in model.actors_episodes():
                     if not self._log_episode(reward, length):
                         break                   # told to stop: the loop ends on exit_flag

@@ -200,6 +200,13 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_sample_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, i32p, f32p]),
     "ga3c_ddpg_train_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, f32p, f32p, i32p]),
     "ga3c_ddpg_time_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
+    # device actors of a DDPG handle (Config.DEVICE_DDPG), include/ga3c_abi.h: ga3c_ddpg_actors_*
+    "ga3c_ddpg_actors_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),
+    "ga3c_ddpg_actors_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_actors_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, f32p, i64p, f32p]),
+    "ga3c_ddpg_actors_episodes": (C.c_int, [C.c_void_p, f64p, i64p, C.c_int32, i32p]),
+    "ga3c_ddpg_actors_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "ga3c_ddpg_actors_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

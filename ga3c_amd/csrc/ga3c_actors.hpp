@@ -132,7 +132,9 @@ struct Pendulum {
     return m - pi;
   }
 
-  __device__ static void step(double* s, const float* a, int* elapsed, double* reward, int* done) {
+  // T: float, the action vector itself; double (PendulumBounded below), the action as check_bounds hands it on
+  template <class T>
+  __device__ static void step(double* s, const T* a, int* elapsed, double* reward, int* done) {
 #pragma clang fp contract(off)
     const double pi = 3.141592653589793, dt = 0.05, max_speed = 8.0;
     const double th = s[0], thdot = s[1];
@@ -161,6 +163,25 @@ struct Pendulum {
     s[0] = -pi + (pi - -pi) * u[0];
     s[1] = -1.0 + (1.0 - -1.0) * u[1];
     *elapsed = 0;
+  }
+};
+
+// Pendulum under an action that can leave [-1, 1]: the DDPG actor's tanh output plus Ornstein-Uhlenbeck noise (Config.DEVICE_DDPG,
+// DESIGN.md 8l).  check_bounds(a, 1, -1, turnaround) is reachable there and is applied as EnvironmentPend.check_bounds applies
+// it, in f64 to the f32 action; its operands are positive, so fmod is Python's %.  What it returns lies in [-1, 1], so
+// clip(u, -2, 2) stays an identity and stays absent.  The arithmetic after it is Pendulum's.
+struct PendulumBounded : Pendulum {
+  __device__ static double check_bounds(float a) {
+#pragma clang fp contract(off)
+    double v = (double)a;
+    if (v < -1.0) v = 1.0 - fmod(-1.0 - v, 2.0);
+    if (v > 1.0) v = fmod(v - 1.0, 2.0) - 1.0;
+    return v;
+  }
+
+  __device__ static void step(double* s, const float* a, int* elapsed, double* reward, int* done) {
+    const double bounded = check_bounds(a[0]);
+    Pendulum::step(s, &bounded, elapsed, reward, done);
   }
 };
 

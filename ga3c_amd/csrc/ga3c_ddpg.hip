@@ -23,9 +23,16 @@
 //   per_sample_kernel     one workgroup: scan of the chunk sums, the stratified draw, the importance weights
 //   per_update_kernel     one workgroup: pa[slot] = (|y - q| + eps)^alpha from the critic kernel's y and q
 // A prioritised step is 8 launches (9 with clipping) and draws its own rows: no host draw, no stamp, nothing to lose.
+// Device actors (ga3c_ddpg_actors_create, Config.DEVICE_DDPG; tests/ddpg_actors_oracle.py is the same statement):
+//   ddpg_actors_step_kernel<Env>   one thread per environment: the step, its transition into the ring, the episode record
+//   ddpg_actors_episodes_kernel    one workgroup: this step's episode records into the episode ring, environment order
+//   ddpg_uniform_slots_kernel      a train step's rows without priorities: a stratified draw in integers, on the device
+// An actor step is predict + 2 launches; every launch argument is known to the host, which waits once per actors_run.
 #include <cmath>
+#include <deque>
 #include <new>
 
+#include "ga3c_actors.hpp"
 #include "ga3c_tile.hpp"
 #include "ga3c_uniform.hpp"
 #include "ga3c_vecnet.hpp"
@@ -631,6 +638,142 @@ __global__ __launch_bounds__(PER_THREADS) void per_update_kernel(const int32_t* 
   if (t == 0) *max_pa = fmaxf(*max_pa, red[0]);
 }
 
+// ------------------------------------------------------------------ device actors
+constexpr int ACT_THREADS = 256;             // the step kernel: one thread per environment
+constexpr int ACT_SCAN = 1024;               // the one-workgroup episode scan
+constexpr int ACT_MAX_UPDATES = 16;
+
+// Everything the actor kernels touch besides the replay ring, by device address; per environment unless said otherwise.
+struct ActState {
+  int N, ep_cap;
+  uint64_t seed;
+  double* phys;              // [N][P] f64 physics
+  int* elapsed;
+  uint64_t* draws;           // uniforms drawn so far
+  float* obs;                // [N][S] what the actor reads
+  float* action;             // [N][A] the last prediction, actor(obs) + noise, as the ring keeps it
+  double* reward;            // the last step's reward and done
+  int* done;
+  double* total_reward;      // of the running episode: the rewards in step order
+  long long* total_length;   // its transitions
+  int* ep_flag;              // this step finished an episode: its record
+  double* ep_reward;
+  long long* ep_length;
+  int* counts;               // [2]: records in the episode ring, episodes this step finished
+  double* ring_ep_reward;    // [ep_cap] the episode ring, in the order the episodes finished
+  long long* ring_ep_length;
+};
+
+// One step of environment i = the thread's index.  first: the handle's first ever step, the host's step(None): the zero action,
+// nothing written to the ring, its done not looked at.  Otherwise the action is a.action's row; the transition
+// obs | a | (f32) reward | done | obs' goes to ring slot (slot0 + i) mod cap (n <= cap: no two threads share a slot) and, with
+// priorities, that slot gets max_pa, which only per_update_kernel writes, earlier on this stream: per_fill_kernel's value.
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState a, int first, float* __restrict__ ring, int64_t slot0,
+                                                                       int64_t cap, float* __restrict__ pa,
+                                                                       const float* __restrict__ max_pa) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * ACT_THREADS + threadIdx.x;
+  if (i >= a.N) return;
+  constexpr int S = Env::S, P = Env::P, A = Env::A;
+  constexpr int rowf = 2 * S + A + 2;
+  double s[P];
+  for (int k = 0; k < P; ++k) s[k] = a.phys[(size_t)i * P + k];
+  int elapsed = a.elapsed[i];
+  float av[A];
+  for (int j = 0; j < A; ++j) av[j] = first ? 0.f : a.action[(size_t)i * A + j];
+  float* obs = a.obs + (size_t)i * S;
+  float before[S], after[S];
+  for (int k = 0; k < S; ++k) before[k] = obs[k];
+  double reward;
+  int done;
+  Env::step(s, av, &elapsed, &reward, &done);
+  Env::observe(s, after);
+  for (int k = 0; k < S; ++k) obs[k] = after[k];
+  a.reward[i] = reward;
+  a.done[i] = done;
+  a.ep_flag[i] = 0;
+  if (first) {
+    for (int j = 0; j < A; ++j) a.action[(size_t)i * A + j] = 0.f;
+    for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
+    a.elapsed[i] = elapsed;
+    return;
+  }
+  const int64_t slot = (slot0 + i) % cap;
+  float* row = ring + slot * rowf;
+  for (int k = 0; k < S; ++k) row[k] = before[k];
+  for (int j = 0; j < A; ++j) row[S + j] = av[j];
+  row[S + A] = (float)reward;
+  row[S + A + 1] = done ? 1.f : 0.f;
+  for (int k = 0; k < S; ++k) row[S + A + 2 + k] = after[k];
+  if (pa) pa[slot] = *max_pa;
+  double total = a.total_reward[i] + reward;
+  long long length = a.total_length[i] + 1;
+  if (done) {                           // ProcessAgent.run's record of an episode shipped as one rollout: len(experiences) + 1
+    a.ep_flag[i] = 1;
+    a.ep_reward[i] = total;
+    a.ep_length[i] = length + 1;
+    total = 0.0;
+    length = 0;
+    uint64_t draws = a.draws[i];
+    double ru[Env::RESET_DRAWS];
+    for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = ga3c_uniform::actor_uniform(a.seed, (uint64_t)i, draws++);
+    Env::reset(s, &elapsed, ru);        // the observation is left alone
+    a.draws[i] = draws;
+  }
+  a.total_reward[i] = total;
+  a.total_length[i] = length;
+  for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
+  a.elapsed[i] = elapsed;
+}
+
+// One workgroup.  Thread t owns the environments [t c, (t + 1) c), c = ceil(N / ACT_SCAN); the inclusive scan over the
+// threads' counts (actors_compact_kernel's pattern) gives each its first record in the episode ring.
+__global__ __launch_bounds__(ACT_SCAN) void ddpg_actors_episodes_kernel(ActState a) {
+  __shared__ int sep[ACT_SCAN];
+  const int t = threadIdx.x;
+  const int chunk = (a.N + ACT_SCAN - 1) / ACT_SCAN;
+  const int lo = min(a.N, t * chunk), hi = min(a.N, lo + chunk);
+  const int ep0 = a.counts[0];
+  int eps = 0;
+  for (int i = lo; i < hi; ++i) eps += a.ep_flag[i];
+  sep[t] = eps;
+  __syncthreads();
+  for (int d = 1; d < ACT_SCAN; d <<= 1) {
+    const int e = t >= d ? sep[t - d] : 0;
+    __syncthreads();
+    sep[t] += e;
+    __syncthreads();
+  }
+  int ep = ep0 + sep[t] - eps;
+  for (int i = lo; i < hi; ++i)
+    if (a.ep_flag[i]) {
+      if (ep < a.ep_cap) {
+        a.ring_ep_reward[ep] = a.ep_reward[i];
+        a.ring_ep_length[ep] = a.ep_length[i];
+      }
+      ++ep;
+    }
+  __syncthreads();                      // every thread has read counts[0]
+  if (t == ACT_SCAN - 1) {
+    a.counts[0] = min(ep0 + sep[t], a.ep_cap);
+    a.counts[1] = sep[t];
+  }
+}
+
+// Row k of a step's B rows from a ring that holds size > B of them: stratum [k size / B, (k + 1) size / B) in integers, and in
+// it the slot lo + min(w - 1, (int64)(u w)), u = u(seed, sample number, k).  The strata are disjoint and none is empty, so the
+// slots are distinct, as random.sample's are.
+__global__ void ddpg_uniform_slots_kernel(int64_t size, int B, uint64_t seed, uint64_t number, int32_t* __restrict__ slots) {
+#pragma clang fp contract(off)
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= B) return;
+  const int64_t lo = (int64_t)k * size / B, hi = ((int64_t)k + 1) * size / B, w = hi - lo;
+  const double u = ga3c_uniform::actor_uniform(seed, number, (uint64_t)k);
+  const int64_t j = (int64_t)(u * (double)w);
+  slots[k] = (int32_t)(lo + (j < w - 1 ? j : w - 1));
+}
+
 // ------------------------------------------------------------------ host side
 // The handle is a ga3c_vecnet::Core (ga3c_vecnet.hpp): stream, lanes, arenas, variables by name, checkpoint and registered
 // segment are the shared ones.  Its own: the train step, the replay ring, the noise.
@@ -678,6 +821,20 @@ struct Per {
   int w_rows = 0, td_rows = 0;          // rows of the last draw / prioritised step (fetch)
 };
 
+// Device actors of a handle (ga3c_ddpg_actors_create).  Everything below is read and written under train_mu.
+struct DActors {
+  ActState d{};
+  char* block = nullptr;                // every device buffer of `d`, and `slots`
+  int* h_counts = nullptr;              // pinned [2]
+  int32_t* slots = nullptr;             // [max_batch] the last draw without priorities
+  int slots_rows = 0;                   // rows of the last draw, either way
+  int updates = 1;                      // train steps after an actor step
+  int batch = 0;                        // rows of a train step ("batch" of actors_set; starts at max_batch)
+  uint64_t draw_seed = 0, samples = 0;  // the draw of sample number n without priorities is u(draw_seed, n, row)
+  bool started = false;                 // the first actor step is the environments' step(None): one flag for all of them
+  std::deque<std::pair<double, long long>> finished;     // episode records not yet drained
+};
+
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
   ga3c_ddpg_config cfg;
   Layout L;
@@ -698,6 +855,7 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   NormalGen gen;
   std::vector<float> ou_x;
   Per* per = nullptr;             // null: no priorities, and every path is the one it was without them
+  DActors* actors = nullptr;      // null: no device actors
 };
 
 namespace {
@@ -921,7 +1079,22 @@ void per_free(ga3c_ddpg* m) {
   m->per = nullptr;
 }
 
+void dactors_free(ga3c_ddpg* m) {
+  DActors* a = m->actors;
+  if (!a) return;
+  (void)hipFree(a->block);
+  (void)hipHostFree(a->h_counts);
+  (void)hipGetLastError();
+  delete a;
+  m->actors = nullptr;
+}
+
 void free_all(ga3c_ddpg* m) {
+  if (m->actors && m->st) {       // live actors: what they enqueued may still run
+    (void)hipStreamSynchronize(m->st);
+    (void)hipGetLastError();
+  }
+  dactors_free(m);
   per_free(m);
   vn::free_core(m);
   (void)hipFree(m->work_base);
@@ -1523,6 +1696,255 @@ int ga3c_ddpg_time_prioritized(ga3c_ddpg* m, int32_t batch, int32_t iters, float
   HIPCHK(hipEventSynchronize(m->t1));
   HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
   return GA3C_OK;
+}
+
+// ---- device actors
+
+using DEnv = ga3c_actors::PendulumBounded;
+
+int ga3c_ddpg_actors_create(ga3c_ddpg* m, int32_t n, int32_t updates, int64_t seed) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  const int most = std::min(m->cfg.max_batch, m->cfg.replay_capacity);
+  if (n < 1 || n > most)
+    return fail(GA3C_EINVAL, "%d actors outside [1, min(max_batch %d, replay_capacity %d)]", n, m->cfg.max_batch, m->cfg.replay_capacity);
+  if (updates < 1 || updates > ACT_MAX_UPDATES) return fail(GA3C_EINVAL, "updates %d outside [1,%d]", updates, ACT_MAX_UPDATES);
+  if (m->L.S != DEnv::S || m->L.A != DEnv::A)
+    return fail(GA3C_EINVAL, "the environment has %d state floats and %d actions, the network %d and %d", DEnv::S, DEnv::A, m->L.S, m->L.A);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (m->actors) return fail(GA3C_ESTATE, "this network has device actors already");
+  DActors* a = new (std::nothrow) DActors();
+  if (!a) return fail(GA3C_EINVAL, "out of host memory");
+  ActState& d = a->d;
+  d.N = n;
+  d.ep_cap = n * GA3C_ACTORS_MAX_STEPS;
+  d.seed = (uint64_t)seed;
+  a->updates = updates;
+  a->batch = m->cfg.max_batch;
+  a->draw_seed = (uint64_t)seed;
+  const size_t Nn = (size_t)n, S = DEnv::S, P = DEnv::P, A = DEnv::A;
+  size_t total = 0;
+  bool ok = true;
+  for (int pass = 0; pass < 2 && ok; ++pass) {      // two passes over one list: sizes, then addresses (16-byte aligned)
+    size_t at = 0;
+    auto carve = [&](auto** p, size_t count) {
+      using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
+      if (pass) *p = reinterpret_cast<T*>(a->block + at);
+      at += (count * sizeof(T) + 15) / 16 * 16;
+    };
+    carve(&d.phys, Nn * P); carve(&d.elapsed, Nn); carve(&d.draws, Nn); carve(&d.obs, Nn * S); carve(&d.action, Nn * A);
+    carve(&d.reward, Nn); carve(&d.done, Nn); carve(&d.total_reward, Nn); carve(&d.total_length, Nn); carve(&d.ep_flag, Nn);
+    carve(&d.ep_reward, Nn); carve(&d.ep_length, Nn); carve(&d.counts, 2);
+    carve(&d.ring_ep_reward, (size_t)d.ep_cap); carve(&d.ring_ep_length, (size_t)d.ep_cap);
+    carve(&a->slots, (size_t)m->cfg.max_batch);
+    if (!pass) {
+      total = at;
+      ok = hipMalloc((void**)&a->block, total) == hipSuccess && hipMemset(a->block, 0, total) == hipSuccess &&
+           hipHostMalloc((void**)&a->h_counts, 2 * sizeof(int), hipHostMallocDefault) == hipSuccess;
+    }
+  }
+  // an environment starts as the host's does: reset() when it is made (draws 0..1) and again when its first episode begins
+  // (draws 2..3), no observation
+  std::vector<double> phys(Nn * P);
+  std::vector<uint64_t> draws(Nn, 2 * DEnv::RESET_DRAWS);
+  for (size_t i = 0; i < Nn; ++i) {
+    double ru[DEnv::RESET_DRAWS];
+    int elapsed = 0;
+    for (int k = 0; k < DEnv::RESET_DRAWS; ++k) ru[k] = ga3c_uniform::actor_uniform(d.seed, i, (uint64_t)(DEnv::RESET_DRAWS + k));
+    DEnv::reset(&phys[i * P], &elapsed, ru);
+  }
+  ok = ok && hipMemcpy(d.phys, phys.data(), phys.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(d.draws, draws.data(), draws.size() * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess;
+  m->actors = a;
+  if (!ok) {
+    (void)hipGetLastError();
+    dactors_free(m);
+    return fail(GA3C_EHIP, "no memory for %d device actors (%zu bytes)", n, total);
+  }
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_actors_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (!m->actors) return fail(GA3C_ESTATE, "this network has no device actors");
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipStreamSynchronize(m->st));
+  }
+  dactors_free(m);
+  return GA3C_OK;
+}
+
+// `steps` actor steps, each followed, when `train` is set and the ring holds MORE than a batch, by `updates` train steps.
+// Everything is enqueued without a wait in between: the host knows every launch argument (N transitions per actor step, B rows
+// per train step).  One wait at the end, a second only when episodes finished and their records are fetched.
+int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float beta_is, int32_t train, int32_t noise_mode,
+                         const float* noise, int64_t* out_stats, float* q_stats) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  DActors* a = m->actors;
+  if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
+  if (steps < 1 || steps > GA3C_ACTORS_MAX_STEPS) return fail(GA3C_EINVAL, "steps %d outside [1,%d]", steps, GA3C_ACTORS_MAX_STEPS);
+  if (noise_mode < 0 || noise_mode > 2) return fail(GA3C_EINVAL, "noise_mode %d not in [0,2]", noise_mode);
+  if (noise_mode == GA3C_DDPG_NOISE_GIVEN && !noise) return fail(GA3C_EINVAL, "GA3C_DDPG_NOISE_GIVEN without a noise vector");
+  if (train && m->per) CHK(per_check_beta(beta_is));
+  const ActState& d = a->d;
+  const int N = d.N, B = a->batch;
+  const int64_t cap = m->cfg.replay_capacity;
+  int64_t calls = 0;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipMemsetAsync(d.counts, 0, 2 * sizeof(int), m->st));     // the episode ring starts empty
+  }
+  for (int s = 0; s < steps; ++s) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    const int first = a->started ? 0 : 1;
+    Noise nz;
+    if (!first) {                       // step(None) asks for no prediction: no step of the noise process either
+      CHK(make_noise(m, noise_mode, noise, &nz));
+      hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(N)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0],
+                         Input{reinterpret_cast<const char*>(d.obs), nullptr, 4 * (int64_t)DEnv::S}, N, nz, d.action);
+    }
+    hipLaunchKernelGGL(ddpg_actors_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
+                       first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
+                       m->per ? (const float*)m->per->max_pa : nullptr);
+    hipLaunchKernelGGL(ddpg_actors_episodes_kernel, dim3(1), dim3(ACT_SCAN), 0, m->st, d);
+    HIPCHK(hipGetLastError());
+    a->started = true;
+    if (!first) m->ring_total += N;
+    if (train && ring_size(m) > B) {    // ThreadReplay.sample's rule: a batch is drawn from MORE rows than it holds
+      for (int k = 0; k < a->updates; ++k) {
+        CHK(make_noise(m, noise_mode, noise, &nz));
+        if (m->per) {
+          CHK(per_enqueue_step(m, B, beta_is, learning_rate, nz));
+        } else {
+          hipLaunchKernelGGL(ddpg_uniform_slots_kernel, dim3((B + 255) / 256), dim3(256), 0, m->st, ring_size(m), B, a->draw_seed,
+                             a->samples, a->slots);
+          ++a->samples;
+          CHK(enqueue_step(m, Rows{m->ring, a->slots, m->rowf}, B, learning_rate, nz, 6));
+        }
+        a->slots_rows = B;
+        m->last_B = B;
+        m->step.fetch_add(1);           // Adam's t is computed per enqueue
+        ++calls;
+      }
+    }
+  }
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (calls) HIPCHK(hipMemcpyAsync(m->h_q, m->w.qstat, 2 * sizeof(float), hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipMemcpyAsync(a->h_counts, d.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipEventRecord(m->tev, m->st));
+  }
+  HIPCHK(hipEventSynchronize(m->tev));
+  if (calls && q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  const int ne = std::min(std::max(a->h_counts[0], 0), d.ep_cap);
+  if (ne > 0) {
+    std::vector<double> er((size_t)ne);
+    std::vector<long long> el((size_t)ne);
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipMemcpy(er.data(), d.ring_ep_reward, sizeof(double) * ne, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(el.data(), d.ring_ep_length, sizeof(long long) * ne, hipMemcpyDeviceToHost));
+    for (int i = 0; i < ne; ++i) a->finished.emplace_back(er[i], el[i]);
+  }
+  if (out_stats) {
+    out_stats[0] = (int64_t)N * steps;
+    out_stats[1] = calls;
+    out_stats[2] = calls * B;
+    out_stats[3] = ne;
+  }
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_actors_episodes(ga3c_ddpg* m, double* total_reward, int64_t* total_length, int32_t max, int32_t* count) {
+  if (!m || !count || max < 0 || (max > 0 && (!total_reward || !total_length))) return fail(GA3C_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  DActors* a = m->actors;
+  if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
+  int n = 0;
+  for (; n < max && !a->finished.empty(); ++n) {
+    total_reward[n] = a->finished.front().first;
+    total_length[n] = a->finished.front().second;
+    a->finished.pop_front();
+  }
+  *count = n;
+  return GA3C_OK;
+}
+
+namespace {
+
+// get (out) / set (in) of an actor buffer by name; `bytes` must be its size.
+int dactors_access(ga3c_ddpg* m, const char* name, void* out, const void* in, int64_t bytes) {
+  if (!m || !name || (!out && !in)) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  DActors* a = m->actors;
+  if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  const ActState& d = a->d;
+  const std::string nm(name);
+  auto sized = [&](int64_t want) {
+    return bytes == want ? GA3C_OK : fail(GA3C_EINVAL, "%s is %lld bytes, not %lld", name, (long long)want, (long long)bytes);
+  };
+  if (nm == "batch") {                  // of the handle, not per environment: the rows of a train step
+    CHK(sized(4));
+    if (out) { *static_cast<int32_t*>(out) = a->batch; return GA3C_OK; }
+    const int32_t v = *static_cast<const int32_t*>(in);
+    if (v < 1 || v > m->cfg.max_batch) return fail(GA3C_EINVAL, "batch %d outside [1, max_batch %d]", v, m->cfg.max_batch);
+    a->batch = v;
+    return GA3C_OK;
+  }
+  if (nm == "draw_seed") {              // ... and the seed of its draws without priorities
+    CHK(sized(8));
+    if (out) *static_cast<int64_t*>(out) = (int64_t)a->draw_seed;
+    else a->draw_seed = (uint64_t)*static_cast<const int64_t*>(in);
+    return GA3C_OK;
+  }
+  if (nm == "slots") {                  // the last draw
+    if (!out) return fail(GA3C_EINVAL, "%s is read only", name);
+    CHK(sized(4 * (int64_t)a->slots_rows));
+    if (a->slots_rows) HIPCHK(hipMemcpy(out, m->per ? m->per->slots : a->slots, (size_t)bytes, hipMemcpyDeviceToHost));
+    return GA3C_OK;
+  }
+  const ga3c_actors::Field fields[] = {
+      {"phys", d.phys, 8, DEnv::P, true},    {"elapsed", d.elapsed, 4, 1, true},   {"draws", d.draws, 8, 1, true},
+      {"obs", d.obs, 4, DEnv::S, true},      {"action", d.action, 4, DEnv::A, false}, {"reward", d.reward, 8, 1, false},
+      {"done", d.done, 4, 1, false},
+  };
+  for (const ga3c_actors::Field& f : fields) {
+    if (nm != f.name) continue;
+    const int64_t want = (int64_t)(f.elem * f.per_env * (size_t)d.N);
+    CHK(sized(want));
+    if (out) {
+      HIPCHK(hipMemcpy(out, f.dev, (size_t)want, hipMemcpyDeviceToHost));
+      return GA3C_OK;
+    }
+    if (!f.settable) return fail(GA3C_EINVAL, "%s is read only", name);
+    if (nm == "elapsed") {
+      const int32_t* v = static_cast<const int32_t*>(in);
+      for (int i = 0; i < d.N; ++i)
+        if (v[i] < 0 || v[i] > (1 << 30)) return fail(GA3C_EINVAL, "%s[%d] = %d outside [0,%d]", name, i, v[i], 1 << 30);
+    }
+    HIPCHK(hipMemcpy(f.dev, in, (size_t)want, hipMemcpyHostToDevice));
+    return GA3C_OK;
+  }
+  return fail(GA3C_EINVAL, "the device actors have nothing named %s", name);
+}
+
+}  // namespace
+
+int ga3c_ddpg_actors_get(ga3c_ddpg* m, const char* name, void* out, int64_t bytes) {
+  if (!out) return fail(GA3C_EINVAL, "null argument");
+  return dactors_access(m, name, out, nullptr, bytes);
+}
+
+int ga3c_ddpg_actors_set(ga3c_ddpg* m, const char* name, const void* in, int64_t bytes) {
+  if (!in) return fail(GA3C_EINVAL, "null argument");
+  return dactors_access(m, name, nullptr, in, bytes);
 }
 
 }  // extern "C"

@@ -681,6 +681,39 @@ int ga3c_ddpg_train_prioritized(ga3c_ddpg* net, int32_t batch, float beta_is, fl
 int ga3c_ddpg_time_prioritized(ga3c_ddpg* net, int32_t batch, int32_t iters, float beta_is, float learning_rate,
                                float* elapsed_ms);
 
+/* ---- Device actors of a DDPG handle (Config.DEVICE_DDPG; tests/ddpg_actors_oracle.py is the same statement in
+ * numpy): n Pendulum-v0 environments in HBM write their transitions into the handle's replay ring and the handle trains on rows
+ * it draws from the ring itself, all on its one stream.  Attached to a created handle, as the priorities are.
+ * An actor step: the online actor on the n observations plus the step's noise (ga3c_ddpg_predict's kernel); per environment
+ * check_bounds(a, 1, -1, turnaround) in f64 on the f32 action, the f64 physics, reward, done and observation, the transition
+ * s | a as predicted | (f32) reward | done | s2 into ring slot (rows ever added + i) mod capacity, which gets max_pa under
+ * priorities; an episode's record (the f64 sum of its rewards in step order, its transitions + 1) and the reset (two counter
+ * uniforms u(seed, environment, draw); the observation is left alone).  The handle's first ever actor step is the host's
+ * step(None): the zero action, no prediction, no noise step, no transition.
+ * Then, when `train` is set and the ring holds MORE than `batch` rows, `updates` train steps of `batch` rows each: with
+ * priorities ga3c_ddpg_train_prioritized's launches; without, slot_k = lo + min(hi - lo - 1, (int64)(u (hi - lo))) with
+ * lo = k size / batch, hi = (k + 1) size / batch in int64 and u = u(draw_seed, sample number, k), then ga3c_ddpg_train_replay's
+ * launches on those slots.  `batch` starts at max_batch and `draw_seed` at `seed`; both are set by name (below).
+ * create: GA3C_EINVAL for n outside [1, min(max_batch, replay_capacity)], updates outside [1,16], or a handle whose
+ * state_dim != 3 or num_actions != 1; GA3C_ESTATE on a second create, as is every other call here without actors.
+ * destroy: also done by ga3c_ddpg_destroy. */
+int ga3c_ddpg_actors_create(ga3c_ddpg* net, int32_t n, int32_t updates, int64_t seed);
+int ga3c_ddpg_actors_destroy(ga3c_ddpg* net);
+/* steps (1..GA3C_ACTORS_MAX_STEPS) actor steps, everything enqueued with no wait in between and one wait at the end.
+ * noise_mode / noise as ga3c_ddpg_predict's, one step of the process per prediction and one per train step's step 4;
+ * GA3C_DDPG_NOISE_GIVEN uses the one vector for all of them.  beta_is is read under priorities only.  out_stats[4] (may be
+ * null): agent steps, train steps, rows trained, episodes finished; q_stats[2] (may be null): {max q, mean q} of the last
+ * train step, untouched when there was none. */
+int ga3c_ddpg_actors_run(ga3c_ddpg* net, int32_t steps, float learning_rate, float beta_is, int32_t train, int32_t noise_mode,
+                         const float* noise, int64_t* out_stats, float* q_stats);
+/* Drains up to `max` finished episodes, oldest first. */
+int ga3c_ddpg_actors_episodes(ga3c_ddpg* net, double* total_reward, int64_t* total_length, int32_t max, int32_t* count);
+/* By name, `bytes` the buffer's size.  Per environment, get and set: "phys" f64 [n][2], "elapsed" i32, "draws" u64, "obs" f32
+ * [n][3]; get only: "action" f32 [n][1] (as predicted), "reward" f64, "done" i32.  Of the handle: "batch" i32 (1..max_batch) and
+ * "draw_seed" i64, get and set; "slots" i32 [batch], the last train step's draw, get only. */
+int ga3c_ddpg_actors_get(ga3c_ddpg* net, const char* name, void* out, int64_t bytes);
+int ga3c_ddpg_actors_set(ga3c_ddpg* net, const char* name, const void* in, int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

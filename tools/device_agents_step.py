@@ -5,7 +5,11 @@ rollout, a train step on the cut rows.  Wall-clock around <prefix>_actors_run (t
 the host reads a row count per step), median and min over rounds, one JSON line per N.  The figure to set it against is the
 PPS of the status line of `_train.sh GAME=<game> AGENTS=16` (profiles/device_agents_step.txt, device_agents_pendulum.txt).
 Pendulum's environments run in lockstep: one train step of N (TIME_MAX + 1) rows every TIME_MAX actor steps.
-usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]"""
+--ddpg (with --game Pendulum-v0; Config.DEVICE_DDPG, ga3c_ddpg_actors_run): the DDPG handle's actors, --updates
+train steps of --batch ring rows after every actor step, --prioritized for the draw by priority; the call waits once, at its
+end (profiles/device_agents_ddpg.txt).
+usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]
+       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000]]"""
 import argparse
 import json
 import os
@@ -25,19 +29,38 @@ def main():
     ap.add_argument("--calls", type=int, default=8, help="native calls per round")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-train", action="store_true")
+    ap.add_argument("--ddpg", action="store_true", help="the DDPG handle's actors (Pendulum-v0)")
+    ap.add_argument("--batch", type=int, default=64, help="--ddpg: rows of a train step")
+    ap.add_argument("--updates", type=int, default=1, help="--ddpg: train steps per actor step")
+    ap.add_argument("--prioritized", action="store_true", help="--ddpg: draw by priority (paired critic loss)")
+    ap.add_argument("--capacity", type=int, default=1000000, help="--ddpg: ring slots")
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
-    if args.game == "Pendulum-v0":
+    if args.ddpg:
+        if args.game != "Pendulum-v0":
+            ap.error("--ddpg steps Pendulum-v0")
+        from NetworkDDPG import Network
+        num_actions, state_dim = 1, (3,)
+        Config.PRIORITIZED_REPLAY = args.prioritized
+        if args.prioritized:
+            Config.DDPG_CRITIC_LOSS = 'paired'
+    elif args.game == "Pendulum-v0":
         from NetworkVP_vector import Network
         num_actions, state_dim = 1, (3,)
     else:
         from NetworkVP_discrate import Network
         num_actions, state_dim = 2, (4,)
     for n in args.agents:
-        net = Network("gpu:0", "device_agents_step", num_actions, state_dim, max_batch=max(16, n * (args.time_max + 1)), predict_lanes=1)
-        net.learning_rate, net.beta = Config.LEARNING_RATE_START, Config.BETA_START
-        net.actors_create(n, args.time_max, Config.DISCOUNT, Config.RANDOM_SEED)
+        if args.ddpg:
+            net = Network("gpu:0", "device_agents_step", num_actions, state_dim, max_batch=max(n, args.batch), predict_lanes=1,
+                          replay_capacity=args.capacity)
+            net.learning_rate = Config.LEARNING_RATE_START
+            net.actors_create(n, seed=Config.RANDOM_SEED, updates=args.updates, batch=args.batch)
+        else:
+            net = Network("gpu:0", "device_agents_step", num_actions, state_dim, max_batch=max(16, n * (args.time_max + 1)), predict_lanes=1)
+            net.learning_rate, net.beta = Config.LEARNING_RATE_START, Config.BETA_START
+            net.actors_create(n, args.time_max, Config.DISCOUNT, Config.RANDOM_SEED)
         net.actors_run(args.steps, train=not args.no_train)               # warm-up; the rollouts are in step from here on
         rates, train_calls, rows, episodes = [], 0, 0, 0
         for _ in range(args.rounds):
@@ -50,7 +73,8 @@ def main():
             net.actors_episodes()
         rates.sort()
         per_step_us = 1e6 * n / rates[len(rates) // 2]
-        print(json.dumps({"game": args.game, "agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,
+        extra = {"ddpg": True, "batch": args.batch, "updates": args.updates, "prioritized": args.prioritized} if args.ddpg else {}
+        print(json.dumps({**extra, "game": args.game, "agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,
                           "agent_steps_per_s_median": round(rates[len(rates) // 2]), "agent_steps_per_s_min": round(rates[0]),
                           "agent_steps_per_s_max": round(rates[-1]), "actor_step_us_median": round(per_step_us, 1),
                           "train_calls": train_calls, "rows_trained": rows, "episodes": episodes, "rounds": args.rounds}),
