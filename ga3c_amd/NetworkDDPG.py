@@ -17,7 +17,7 @@ import numpy as np
 
 from Config import Config
 from NetworkVP import _device_ordinal
-from NetworkVP_vecnet import NativeHandle
+from NetworkVP_vecnet import DeviceActors, NativeHandle
 import _native as nat
 
 H1, H2 = 400, 300
@@ -73,7 +73,7 @@ def initial_arena(state_dim, num_actions, seed, tau=None):
     return online, target
 
 
-class Network(NativeHandle):
+class Network(DeviceActors, NativeHandle):
     PREFIX = "ga3c_ddpg"
 
     def __init__(self, device, model_name, num_actions, state_dim, max_batch=None, predict_lanes=None, replay_capacity=None):
@@ -293,10 +293,11 @@ class Network(NativeHandle):
         return ms.value
 
     # ---- device actors (Config.DEVICE_DDPG) ------------------------------------------------
-    # what ga3c_ddpg_actors_get names: {name: (dtype, elements per environment)}; "slots" has one row per row of a train step
+    # what ga3c_ddpg_actors_get names (NetworkVP_vecnet.DeviceActors); "slots" has one row per row of a train step
     ACTOR_FIELDS = {"phys": (np.float64, 2), "elapsed": (np.int32, 1), "draws": (np.uint64, 1), "obs": (np.float32, 3),
                     "action": (np.float32, "A"), "reward": (np.float64, 1), "done": (np.int32, 1), "slots": (np.int32, 1)}
     ACTOR_SCALARS = {"batch": np.int32, "draw_seed": np.int64}
+    ACTOR_ROWS = {"slots": "batch"}
 
     def actors_create(self, n, time_max=None, discount=None, seed=None, updates=None, batch=None, draw_seed=None):
         """n Pendulum-v0 environments on the handle, with Config's train-step rows, updates per actor step and draw seed unless
@@ -306,9 +307,6 @@ class Network(NativeHandle):
         self.num_actors = int(n)
         self.actors_set("batch", min(self.max_batch, int(Config.TRAINING_MIN_BATCH_SIZE if batch is None else batch)))
         self.actors_set("draw_seed", Config.REPLAY_BUFFER_RANDOM_SEED if draw_seed is None else draw_seed)
-
-    def actors_destroy(self):
-        self._call("actors_destroy")
 
     def actors_run(self, steps, train=True, noise=None):
         """`steps` actor steps, each followed by DEVICE_DDPG_UPDATES train steps once the ring holds more than a batch, at the
@@ -320,34 +318,6 @@ class Network(NativeHandle):
         if stats[1]:
             self.logging = (float(q[0]), float(q[1]))
         return tuple(int(t) for t in stats)
-
-    def actors_episodes(self, max_count=4096):
-        """The finished episodes not yet taken, oldest first -> [(total_reward, total_length)]."""
-        out = []
-        reward, length, count = np.empty(max_count, np.float64), np.empty(max_count, np.int64), C.c_int32()
-        while True:
-            self._call("actors_episodes", nat.ptr(reward, nat.f64p), nat.ptr(length, nat.i64p), max_count, C.byref(count))
-            out += [(float(reward[i]), int(length[i])) for i in range(count.value)]
-            if count.value < max_count:
-                return out
-
-    def actors_get(self, name):
-        if name in self.ACTOR_SCALARS:
-            out = np.zeros(1, self.ACTOR_SCALARS[name])
-            self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
-            return int(out[0])
-        dtype, width = self.ACTOR_FIELDS[name]
-        vector = width != 1
-        width = {"A": self.num_actions}.get(width, width)
-        rows = self.actors_get("batch") if name == "slots" else self.num_actors
-        out = np.zeros((rows, width) if vector else (rows,), dtype)
-        self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
-        return out
-
-    def actors_set(self, name, value):
-        dtype = self.ACTOR_SCALARS[name] if name in self.ACTOR_SCALARS else self.ACTOR_FIELDS[name][0]
-        value = np.ascontiguousarray(value, dtype=dtype).reshape(-1)
-        self._call("actors_set", name.encode(), value.ctypes.data_as(C.c_void_p), value.nbytes)
 
     def compute(self, x, y_r, a, x2, done, stop_after, noise=None):
         s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)

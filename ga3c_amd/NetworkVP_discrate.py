@@ -81,6 +81,8 @@ class Network(DeviceActors, VectorNetwork):
     ACTIVATION_TAGS = ("activation_lastdense",)   # NetworkVP_discrate.py:132-146; the dead variables get histograms too
     DUAL_RMSPROP_REFUSAL = "DUAL_RMSPROP with the discrete vector-state network is not supported"
     ACTOR_FIELDS = ACTOR_FIELDS   # device actors (Config.DEVICE_AGENTS): ga3c_dmlp_actors_*, CartPole-v0
+    ACTOR_SCALARS = {"batch_rows": np.int32}
+    ACTOR_ROWS = dict.fromkeys(("batch_x", "batch_y_r", "batch_a"), "batch_rows")
 
     def _config(self):
         self.layers, self.stack = _layers(), _stack()

@@ -8,8 +8,9 @@ save, load, get_global_step, get_variables_names, get_variable_value, and the ze
 front-end, no state cache and no data-parallel or Hogwild training: Server refuses those settings with these networks.
 
 A subclass states PREFIX, LOGITS_PER_ACTION, ACTIVATION_WIDTHS / ACTIVATION_TAGS (or its own evaluate), DUAL_RMSPROP_REFUSAL
-(None where its handle takes the flag), _config() and _variables().  DeviceActors is the mixin of the two whose handles
-step their own environments (Config.DEVICE_AGENTS): the actors_* methods over <PREFIX>_actors_*.
+(None where its handle takes the flag), _config() and _variables().  DeviceActors is the mixin of the networks whose handles
+step their own environments (Config.DEVICE_AGENTS), NetworkDDPG.Network among them: the actors_* methods over
+<PREFIX>_actors_*.
 """
 import ctypes as C
 import glob
@@ -308,11 +309,16 @@ class VectorNetwork(NativeHandle):
 
 
 class DeviceActors:
-    """Config.DEVICE_AGENTS: the <PREFIX>_actors_* entries of a vector-state network whose handle steps its
-    environments itself (csrc/ga3c_actors.hpp).  Mixed into NetworkVP_discrate.Network (CartPole-v0) and
-    NetworkVP_vector.Network (Pendulum-v0); each states ACTOR_FIELDS, what <PREFIX>_actors_get names per environment:
-    {name: (dtype, elements -- a number, "S" or "A")}, "batch_*" being rows of the last step's batch instead."""
+    """Config.DEVICE_AGENTS: the <PREFIX>_actors_* entries of a network whose handle steps its
+    environments itself (csrc/ga3c_actors.hpp).  Mixed into NetworkVP_discrate.Network (CartPole-v0), NetworkVP_vector.Network
+    (Pendulum-v0) and NetworkDDPG.Network (Pendulum-v0 into a replay ring; its own actors_create and actors_run).  Each states
+    what <PREFIX>_actors_get names:
+      ACTOR_FIELDS   {name: (dtype, elements per row -- a number, "S" or "A")}, one row per environment unless ACTOR_ROWS says otherwise;
+      ACTOR_SCALARS  {name: dtype} of the handle's single values;
+      ACTOR_ROWS     {field name: the scalar that is its row count}."""
     ACTOR_FIELDS = {}
+    ACTOR_SCALARS = {}
+    ACTOR_ROWS = {}
 
     def actors_create(self, n, time_max=None, discount=None, seed=None):
         self._call("actors_create", int(n), int(Config.TIME_MAX if time_max is None else time_max),
@@ -341,18 +347,19 @@ class DeviceActors:
                 return out
 
     def actors_get(self, name):
-        if name == "batch_rows":
-            out = np.zeros(1, np.int32)
+        if name in self.ACTOR_SCALARS:
+            out = np.zeros(1, self.ACTOR_SCALARS[name])
             self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
             return int(out[0])
         dtype, width = self.ACTOR_FIELDS[name]
         vector = width != 1                         # "S" / "A" fields are [rows, width] whatever the width, the others [rows]
         width = {"S": self.S, "A": self.num_actions}.get(width, width)
-        rows = self.actors_get("batch_rows") if name.startswith("batch_") else self.num_actors
+        rows = self.actors_get(self.ACTOR_ROWS[name]) if name in self.ACTOR_ROWS else self.num_actors
         out = np.zeros((rows, width) if vector else (rows,), dtype)
         self._call("actors_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
         return out
 
     def actors_set(self, name, value):
-        value = np.ascontiguousarray(value, dtype=self.ACTOR_FIELDS[name][0])
+        dtype = self.ACTOR_SCALARS[name] if name in self.ACTOR_SCALARS else self.ACTOR_FIELDS[name][0]
+        value = np.ascontiguousarray(value, dtype=dtype)
         self._call("actors_set", name.encode(), value.ctypes.data_as(C.c_void_p), value.nbytes)

@@ -53,6 +53,8 @@ class Network(DeviceActors, VectorNetwork):
     ACTIVATION_TAGS = ("activation_pd1", "activation_pd2", "activation_d2")      # NetworkVP.py:150-170
     DUAL_RMSPROP_REFUSAL = None   # Config.DUAL_RMSPROP: one optimizer per cost, arenas 4 / 5 / 6
     ACTOR_FIELDS = ACTOR_FIELDS   # device actors (Config.DEVICE_PENDULUM): ga3c_mlp_actors_*, Pendulum-v0
+    ACTOR_SCALARS = {"batch_rows": np.int32}
+    ACTOR_ROWS = dict.fromkeys(("batch_x", "batch_y_r", "batch_a"), "batch_rows")
 
     def _config(self):
         cfg = nat.MlpConfig()

@@ -23,6 +23,10 @@
 // tests/device_pendulum_oracle.py are the same statement in numpy.  The f64 arithmetic is
 // compiled with contraction off, as the host library's is.  The uniforms are the one deviation: a stateless function of
 // (seed, environment, draw number), actor_uniform (ga3c_uniform.hpp).
+//
+// The DDPG handle's actors (ga3c_ddpg.hip) write transitions into a replay ring where these cut rollouts, in
+// kernels of their own, and share what does not ask which of the two a step produces: Episodes, load_physics /
+// store_physics, finish_episode and the episode scan on the device; ActorsCore and the functions over it on the host.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -185,9 +189,21 @@ struct PendulumBounded : Pendulum {
   }
 };
 
+// The episodes a step finishes and the ring that keeps their records for the host: the part of the device state that the
+// rollout actors (State below) and the DDPG actors (ActState, ga3c_ddpg.hip) both hold.
+struct Episodes {
+  int ep_cap;
+  int* ep_flag;              // per environment: this step finished an episode, and its record
+  double* ep_reward;
+  long long* ep_length;
+  int* counts;               // [2]: records in the episode ring, episodes this step finished
+  double* ring_ep_reward;    // [ep_cap] the episode ring, in the order the episodes finished
+  long long* ring_ep_length;
+};
+
 // Everything the kernels touch, by device address.  Per environment unless said otherwise; T1 = TIME_MAX + 1.
 struct State {
-  int N, T1, S, P, A, time_max, ep_cap;
+  int N, T1, S, P, A, time_max;
   double gamma;
   uint64_t seed;
   double* phys;              // [N][P] f64 physics
@@ -214,16 +230,41 @@ struct State {
   int* cut;                  // rows of the rollout this step cut (0: none), where it starts in the ring, its returns [N][T1]
   int* cut_head;
   float* cut_y;
-  int* ep_flag;              // this step finished an episode: its record
-  double* ep_reward;
-  long long* ep_length;
   int64_t* off;              // [N T1] the batch: byte offsets of its rows from ring_x, environment order
   float* by;                 // [N T1] y_r     (the handle's train staging)
   float* ba;                 // [N T1][A] one-hot (Env::CONTINUOUS: the action vectors)
-  int* counts;               // [3]: rows of the batch, records in the episode ring, episodes this step finished
-  double* ring_ep_reward;    // [ep_cap] the episode ring, in the order the episodes finished
-  long long* ring_ep_length;
+  int* counts;               // [3]: rows of the batch, then ep.counts' two: what the host copies after a step
+  Episodes ep;               // ep.counts = counts + 1
 };
+
+// The P physics values and `elapsed` of environment i, into and out of a step kernel's registers.
+template <int P>
+__device__ __forceinline__ void load_physics(const double* phys, const int* elapsed, int i, double* s, int& el) {
+  for (int k = 0; k < P; ++k) s[k] = phys[(size_t)i * P + k];
+  el = elapsed[i];
+}
+
+template <int P>
+__device__ __forceinline__ void store_physics(double* phys, int* elapsed, int i, const double* s, int el) {
+  for (int k = 0; k < P; ++k) phys[(size_t)i * P + k] = s[k];
+  elapsed[i] = el;
+}
+
+// The end of environment i's episode: its record for this step's scan, the running totals back to zero, and the reset on the
+// next RESET_DRAWS uniforms of the environment in draw order.  The observation is left alone.
+template <class Env>
+__device__ __forceinline__ void finish_episode(const Episodes& e, int i, uint64_t seed, double& total, long long& length,
+                                               uint64_t& draws, double* s, int& elapsed) {
+#pragma clang fp contract(off)
+  e.ep_flag[i] = 1;
+  e.ep_reward[i] = total;
+  e.ep_length[i] = length;
+  total = 0.0;
+  length = 0;
+  double ru[Env::RESET_DRAWS];
+  for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = actor_uniform(seed, (uint64_t)i, draws++);
+  Env::reset(s, &elapsed, ru);
+}
 
 template <class Env>
 __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
@@ -233,12 +274,12 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
   constexpr int S = Env::S, P = Env::P, A = Env::A;
   const int T1 = a.T1;
   double s[P];
-  for (int k = 0; k < P; ++k) s[k] = a.phys[(size_t)i * P + k];
-  int elapsed = a.elapsed[i];
+  int elapsed;
+  load_physics<P>(a.phys, a.elapsed, i, s, elapsed);
   uint64_t draws = a.draws[i];
   const bool started = a.started[i] != 0;
   a.cut[i] = 0;
-  a.ep_flag[i] = 0;
+  a.ep.ep_flag[i] = 0;
 
   [[maybe_unused]] int action = 0;
   [[maybe_unused]] float av[A];                          // CONTINUOUS: the action is the prediction row, no draw; step(None) is the zero vector
@@ -264,9 +305,8 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
   a.done[i] = done;
   float* obs = a.obs + (size_t)i * S;
   if (!started) {                       // the host's step(None): no experience, and its `done` is not looked at
-    for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
+    store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
     Env::observe(s, obs);
-    a.elapsed[i] = elapsed;
     a.started[i] = 1;
     return;
   }
@@ -305,14 +345,7 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
     rsum = 0.0;
     tc = 0;
     if (done) {
-      a.ep_flag[i] = 1;
-      a.ep_reward[i] = total;
-      a.ep_length[i] = length;
-      total = 0.0;
-      length = 0;
-      double ru[Env::RESET_DRAWS];
-      for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = actor_uniform(a.seed, (uint64_t)i, draws++);
-      Env::reset(s, &elapsed, ru);
+      finish_episode<Env>(a.ep, i, a.seed, total, length, draws, s, elapsed);
       head = 0;
       rlen = 0;
     } else {                            // the last experience is row 0 of the next rollout
@@ -323,8 +356,7 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
     a.total_length[i] = length;
   }
   if (!done) tc += 1;                   // (a new episode starts at time_count 0)
-  for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
-  a.elapsed[i] = elapsed;
+  store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
   a.draws[i] = draws;
   a.head[i] = head;
   a.rlen[i] = rlen;
@@ -332,34 +364,79 @@ __global__ __launch_bounds__(STEP_THREADS) void actors_step_kernel(State a) {
   a.reward_sum[i] = rsum;
 }
 
-// One workgroup.  Thread t owns the environments [t c, (t + 1) c), c = ceil(N / SCAN_THREADS); the scan over the threads'
-// sums gives each its first batch row and its first episode record.
+// Inclusive Hillis-Steele scan over the threads of a workgroup of SCAN_THREADS, of K int[SCAN_THREADS] arrays in LDS at once:
+// thread t has stored its element of each.  Ten rounds, each ending in a barrier.
+template <int K>
+__device__ __forceinline__ void scan_threads(int* const (&s)[K], int t) {
+  __syncthreads();
+  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
+    int add[K];
+    for (int k = 0; k < K; ++k) add[k] = t >= d ? s[k][t - d] : 0;
+    __syncthreads();
+    for (int k = 0; k < K; ++k) s[k][t] += add[k];
+    __syncthreads();
+  }
+}
+
+// A step's finished episodes go to the episode ring in environment order in three parts: count_episodes, a scan_threads
+// that has `sep` among its arrays, append_episodes.  EpisodeScan is what thread t carries from the first to the last: the
+// environments it owns, [lo, hi) = [t c, (t + 1) c) clipped to N, c = ceil(N / SCAN_THREADS) (the last owning thread may have
+// fewer than c and the threads after it none), the records in the ring before this step and the episodes its own finished.
+struct EpisodeScan {
+  int lo, hi, ep0, eps;
+};
+
+__device__ __forceinline__ EpisodeScan count_episodes(const Episodes& e, int N, int t, int* sep) {
+  const int chunk = (N + SCAN_THREADS - 1) / SCAN_THREADS, lo = min(N, t * chunk);
+  EpisodeScan c{lo, min(N, lo + chunk), e.counts[0], 0};
+  for (int i = c.lo; i < c.hi; ++i) c.eps += e.ep_flag[i];
+  sep[t] = c.eps;
+  return c;
+}
+
+// Every thread read counts[0] before the scan, in count_episodes; the last thread writes it here, after the scan.  Each of
+// the scan's barriers is a workgroup fence as well, so every read has returned before any thread is past the first of them:
+// no barrier between the append and the write, in either kernel.
+__device__ __forceinline__ void append_episodes(const Episodes& e, const EpisodeScan& c, int t, const int* sep) {
+  int ep = c.ep0 + sep[t] - c.eps;
+  for (int i = c.lo; i < c.hi; ++i)
+    if (e.ep_flag[i]) {
+      if (ep < e.ep_cap) {
+        e.ring_ep_reward[ep] = e.ep_reward[i];
+        e.ring_ep_length[ep] = e.ep_length[i];
+      }
+      ++ep;
+    }
+  if (t == SCAN_THREADS - 1) {
+    e.counts[0] = min(c.ep0 + sep[t], e.ep_cap);
+    e.counts[1] = sep[t];
+  }
+}
+
+// The three in a row, for a kernel of one workgroup of SCAN_THREADS that scans nothing else; sep: its int[SCAN_THREADS] in LDS.
+__device__ __forceinline__ void scan_append_episodes(const Episodes& e, int N, int* sep) {
+  const int t = threadIdx.x;
+  const EpisodeScan c = count_episodes(e, N, t, sep);
+  int* const arrays[1] = {sep};
+  scan_threads(arrays, t);
+  append_episodes(e, c, t, sep);
+}
+
+// One workgroup.  The scan over the threads' sums gives each its first batch row and, with it, its first episode record.
 template <class Env>
 __global__ __launch_bounds__(SCAN_THREADS) void actors_compact_kernel(State a) {
   __shared__ int srow[SCAN_THREADS];
   __shared__ int sep[SCAN_THREADS];
   const int t = threadIdx.x;
-  const int chunk = (a.N + SCAN_THREADS - 1) / SCAN_THREADS;
-  const int lo = min(a.N, t * chunk), hi = min(a.N, lo + chunk);
-  const int ep0 = a.counts[1];
-  int rows = 0, eps = 0;
-  for (int i = lo; i < hi; ++i) {
-    rows += a.cut[i];
-    eps += a.ep_flag[i];
-  }
+  const EpisodeScan c = count_episodes(a.ep, a.N, t, sep);
+  int rows = 0;
+  for (int i = c.lo; i < c.hi; ++i) rows += a.cut[i];
   srow[t] = rows;
-  sep[t] = eps;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    const int r = t >= d ? srow[t - d] : 0, e = t >= d ? sep[t - d] : 0;
-    __syncthreads();
-    srow[t] += r;
-    sep[t] += e;
-    __syncthreads();
-  }
-  int row = srow[t] - rows, ep = ep0 + sep[t] - eps;
+  int* const arrays[2] = {srow, sep};
+  scan_threads(arrays, t);
+  int row = srow[t] - rows;
   const int T1 = a.T1, A = a.A, cap = a.N * T1;
-  for (int i = lo; i < hi; ++i) {
+  for (int i = c.lo; i < c.hi; ++i) {
     const int T = min(a.cut[i], T1), h = a.cut_head[i];
     for (int k = 0; k < T && row < cap; ++k, ++row) {
       const int slot = (h + k) % T1;
@@ -372,22 +449,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void actors_compact_kernel(State a) {
         for (int j = 0; j < A; ++j) a.ba[(size_t)row * A + j] = j == act ? 1.0f : 0.0f;
       }
     }
-    if (a.ep_flag[i]) {
-      if (ep < a.ep_cap) {
-        a.ring_ep_reward[ep] = a.ep_reward[i];
-        a.ring_ep_length[ep] = a.ep_length[i];
-      }
-      ++ep;
-    }
   }
-  if (t == SCAN_THREADS - 1) {
-    a.counts[0] = srow[t];
-    a.counts[1] = min(ep0 + sep[t], a.ep_cap);
-    a.counts[2] = sep[t];
-  }
+  if (t == SCAN_THREADS - 1) a.counts[0] = srow[t];
+  append_episodes(a.ep, c, t, sep);
 }
 
 // ------------------------------------------------------------------ host side
+
+constexpr int32_t NO_BOUND = -1;
 
 struct Field {               // a buffer actors_get / actors_set reach by name
   const char* name;
@@ -395,23 +464,66 @@ struct Field {               // a buffer actors_get / actors_set reach by name
   size_t elem;               // bytes of an element
   size_t per_env;            // elements per environment
   bool settable;
+  int32_t hi = NO_BOUND;     // a settable int32 field: its values lie in [0, hi]; NO_BOUND: no check
 };
 
-struct Actors {
-  State d{};
-  char* block = nullptr;     // every device buffer of `d` but by / ba
-  int* h_counts = nullptr;   // pinned
+// What a handle's actors keep on the host whichever kernels step them: Actors below, DActors of ga3c_ddpg.hip.
+struct ActorsCore {
+  char* block = nullptr;     // every device buffer the derived struct carved
+  int* h_counts = nullptr;   // pinned: the counts the host copies after a step
   std::vector<Field> fields;
   std::deque<std::pair<double, long long>> finished;   // episode records not yet drained
+};
+
+struct Actors : ActorsCore {
+  State d{};                 // by / ba are the handle's, everything else lies in `block`
   int batch_rows = 0;        // rows of the last step's batch
 };
 
-inline void actors_free(Actors* a) {
+template <class T>           // T: Actors or DActors
+void actors_free(T* a) {
   if (!a) return;
   (void)hipFree(a->block);
   (void)hipHostFree(a->h_counts);
   (void)hipGetLastError();
   delete a;
+}
+
+// One zeroed device block for every buffer that `list` names, and `counts` pinned ints.  list(carve) calls carve(&pointer,
+// elements) once per buffer and is run twice: for the sizes, then for the addresses (each buffer 16-byte aligned).
+// -> false: no memory; *total is the block's size either way.
+template <class List>
+bool carve_block(ActorsCore* a, int counts, size_t* total, List list) {
+  for (int pass = 0; pass < 2; ++pass) {
+    size_t at = 0;
+    list([&](auto** p, size_t count) {
+      using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
+      if (pass) *p = reinterpret_cast<T*>(a->block + at);
+      at += (count * sizeof(T) + 15) / 16 * 16;
+    });
+    if (pass) break;
+    *total = at;
+    if (hipMalloc((void**)&a->block, at) != hipSuccess || hipMemset(a->block, 0, at) != hipSuccess ||
+        hipHostMalloc((void**)&a->h_counts, counts * sizeof(int), hipHostMallocDefault) != hipSuccess)
+      return false;
+  }
+  return true;
+}
+
+// An environment starts as the host's does: reset() when it is made (draws 0..RESET_DRAWS-1) and again when its first
+// episode begins (the next RESET_DRAWS), no observation.  -> false: a copy to the device failed.
+template <class Env>
+bool initial_physics(uint64_t seed, size_t n, double* d_phys, uint64_t* d_draws) {
+  std::vector<double> phys(n * Env::P);
+  std::vector<uint64_t> draws(n, 2 * Env::RESET_DRAWS);
+  for (size_t i = 0; i < n; ++i) {
+    double ru[Env::RESET_DRAWS];
+    int elapsed = 0;
+    for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = actor_uniform(seed, i, (uint64_t)(Env::RESET_DRAWS + k));
+    Env::reset(&phys[i * Env::P], &elapsed, ru);
+  }
+  return hipMemcpy(d_phys, phys.data(), phys.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d_draws, draws.data(), draws.size() * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 // m: a Net-derived handle with cfg and an `Actors* actors` member.  Its train staging d_y / d_a holds the batch's y_r and a.
@@ -430,58 +542,37 @@ int actors_create(N* m, int n, int time_max, double discount, int64_t seed) {
   Actors* a = new (std::nothrow) Actors();
   if (!a) return fail(GA3C_EINVAL, "out of host memory");
   State& d = a->d;
-  d.N = n; d.T1 = (int)T1; d.S = m->S; d.P = Env::P; d.A = m->A; d.time_max = time_max; d.ep_cap = n * MAX_STEPS;
+  Episodes& e = d.ep;
+  d.N = n; d.T1 = (int)T1; d.S = m->S; d.P = Env::P; d.A = m->A; d.time_max = time_max; e.ep_cap = n * MAX_STEPS;
   d.gamma = discount;
   d.seed = (uint64_t)seed;
   const size_t Nn = (size_t)n, S = (size_t)m->S, P = (size_t)Env::P, A = (size_t)m->A, R = Nn * (size_t)T1, ZW = (size_t)m->ZW;
   const size_t AI = Env::CONTINUOUS ? 0 : 1, AV = Env::CONTINUOUS ? A : 0;      // per row: an action index or an action vector
-  // two passes over one list: sizes, then addresses (each buffer 16-byte aligned)
   size_t total = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    size_t at = 0;
-    auto carve = [&](auto** p, size_t count) {
-      using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
-      if (pass) *p = reinterpret_cast<T*>(a->block + at);
-      at += (count * sizeof(T) + 15) / 16 * 16;
-    };
-    carve(&d.phys, Nn * P); carve(&d.elapsed, Nn); carve(&d.time_count, Nn); carve(&d.started, Nn); carve(&d.draws, Nn);
-    carve(&d.obs, Nn * S); carve(&d.ring_x, R * S); carve(&d.ring_a, R * AI); carve(&d.ring_av, R * AV); carve(&d.ring_r, R); carve(&d.head, Nn);
-    carve(&d.rlen, Nn); carve(&d.reward_sum, Nn); carve(&d.total_reward, Nn); carve(&d.total_length, Nn);
-    carve(&d.p, Nn * A); carve(&d.v, Nn); carve(&d.z, Nn * ZW); carve(&d.u, Nn); carve(&d.action, Nn * AI); carve(&d.action_v, Nn * AV); carve(&d.reward, Nn);
-    carve(&d.done, Nn); carve(&d.cut, Nn); carve(&d.cut_head, Nn); carve(&d.cut_y, R); carve(&d.ep_flag, Nn);
-    carve(&d.ep_reward, Nn); carve(&d.ep_length, Nn); carve(&d.off, R); carve(&d.counts, 3);
-    carve(&d.ring_ep_reward, (size_t)d.ep_cap); carve(&d.ring_ep_length, (size_t)d.ep_cap);
-    if (!pass) {
-      total = at;
-      if (hipMalloc((void**)&a->block, total) != hipSuccess || hipMemset(a->block, 0, total) != hipSuccess ||
-          hipHostMalloc((void**)&a->h_counts, 3 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        actors_free(a);
-        return fail(GA3C_EHIP, "no memory for %d device actors (%zu bytes)", n, total);
-      }
-    }
+  if (!carve_block(a, 3, &total, [&](auto carve) {
+        carve(&d.phys, Nn * P); carve(&d.elapsed, Nn); carve(&d.time_count, Nn); carve(&d.started, Nn); carve(&d.draws, Nn);
+        carve(&d.obs, Nn * S); carve(&d.ring_x, R * S); carve(&d.ring_a, R * AI); carve(&d.ring_av, R * AV); carve(&d.ring_r, R); carve(&d.head, Nn);
+        carve(&d.rlen, Nn); carve(&d.reward_sum, Nn); carve(&d.total_reward, Nn); carve(&d.total_length, Nn);
+        carve(&d.p, Nn * A); carve(&d.v, Nn); carve(&d.z, Nn * ZW); carve(&d.u, Nn); carve(&d.action, Nn * AI); carve(&d.action_v, Nn * AV); carve(&d.reward, Nn);
+        carve(&d.done, Nn); carve(&d.cut, Nn); carve(&d.cut_head, Nn); carve(&d.cut_y, R); carve(&e.ep_flag, Nn);
+        carve(&e.ep_reward, Nn); carve(&e.ep_length, Nn); carve(&d.off, R); carve(&d.counts, 3);
+        carve(&e.ring_ep_reward, (size_t)e.ep_cap); carve(&e.ring_ep_length, (size_t)e.ep_cap);
+      })) {
+    (void)hipGetLastError();
+    actors_free(a);
+    return fail(GA3C_EHIP, "no memory for %d device actors (%zu bytes)", n, total);
   }
+  e.counts = d.counts + 1;
   d.by = m->d_y;
   d.ba = m->d_a;
-  // an environment starts as the host's does: reset() when it is made (draws 0..RESET_DRAWS-1) and again when its first
-  // episode begins (the next RESET_DRAWS), no observation
-  std::vector<double> phys(Nn * P);
-  std::vector<uint64_t> draws(Nn, 2 * Env::RESET_DRAWS);
-  for (size_t i = 0; i < Nn; ++i) {
-    double ru[Env::RESET_DRAWS];
-    int elapsed = 0;
-    for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = actor_uniform(d.seed, i, (uint64_t)(Env::RESET_DRAWS + k));
-    Env::reset(&phys[i * P], &elapsed, ru);
-  }
-  if (hipMemcpy(d.phys, phys.data(), phys.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d.draws, draws.data(), draws.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (!initial_physics<Env>(d.seed, Nn, d.phys, d.draws)) {
     (void)hipGetLastError();
     actors_free(a);
     return fail(GA3C_EHIP, "copy to the device actors failed");
   }
   a->fields = {
-      {"phys", d.phys, 8, P, true},          {"elapsed", d.elapsed, 4, 1, true},     {"time_count", d.time_count, 4, 1, true},
-      {"started", d.started, 4, 1, true},    {"draws", d.draws, 8, 1, true},         {"obs", d.obs, 4, S, true},
+      {"phys", d.phys, 8, P, true},          {"elapsed", d.elapsed, 4, 1, true, 1 << 30}, {"time_count", d.time_count, 4, 1, true, time_max},
+      {"started", d.started, 4, 1, true, 1}, {"draws", d.draws, 8, 1, true},         {"obs", d.obs, 4, S, true},
       {"rollout_len", d.rlen, 4, 1, false},  {"p", d.p, 4, A, false},                {"v", d.v, 4, 1, false},
       {"u", d.u, 8, 1, false},               {"reward", d.reward, 8, 1, false},
       {"done", d.done, 4, 1, false},         {"cut", d.cut, 4, 1, false},
@@ -505,6 +596,7 @@ void actors_drop(N* m) {
   m->actors = nullptr;
 }
 
+// From here on m is any handle with device, train_mu, mu, st and an `actors` pointer to a struct derived from ActorsCore.
 template <class N>
 int actors_destroy(N* m) {
   if (!m) return fail(GA3C_EINVAL, "null argument");
@@ -517,6 +609,20 @@ int actors_destroy(N* m) {
   }
   actors_free(m->actors);
   m->actors = nullptr;
+  return GA3C_OK;
+}
+
+// The episode ring's records, `records` of them as the host copied the count, appended to a->finished.  The stream has
+// finished the steps that wrote them: the caller has waited, in its own way.
+inline int fetch_episodes(ActorsCore* a, const Episodes& e, int records, int64_t* fetched) {
+  const int ne = std::min(std::max(records, 0), e.ep_cap);
+  *fetched = ne;
+  if (ne == 0) return GA3C_OK;
+  std::vector<double> er((size_t)ne);
+  std::vector<long long> el((size_t)ne);
+  HIPCHK(hipMemcpy(er.data(), e.ring_ep_reward, sizeof(double) * ne, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(el.data(), e.ring_ep_length, sizeof(long long) * ne, hipMemcpyDeviceToHost));
+  for (int i = 0; i < ne; ++i) a->finished.emplace_back(er[i], el[i]);
   return GA3C_OK;
 }
 
@@ -564,16 +670,10 @@ int actors_run(N* m, int steps, float lr, float beta, int train, int64_t* stats)
       rows_trained += B;
     }
   }
-  const int ne = std::min(std::max(a->h_counts[1], 0), d.ep_cap);
-  if (ne > 0) {
-    std::vector<double> er((size_t)ne);
-    std::vector<long long> el((size_t)ne);
+  if (a->h_counts[1] > 0) {               // the last step's train step may still run
     std::lock_guard<std::mutex> lk(m->mu);
     HIPCHK(hipStreamSynchronize(m->st));
-    HIPCHK(hipMemcpy(er.data(), d.ring_ep_reward, sizeof(double) * ne, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(el.data(), d.ring_ep_length, sizeof(long long) * ne, hipMemcpyDeviceToHost));
-    for (int i = 0; i < ne; ++i) a->finished.emplace_back(er[i], el[i]);
-    episodes = ne;
+    CHK(fetch_episodes(a, d.ep, a->h_counts[1], &episodes));
   }
   if (stats) {
     stats[0] = (int64_t)d.N * steps;
@@ -589,7 +689,7 @@ template <class N>
 int actors_episodes(N* m, double* total_reward, int64_t* total_length, int max, int32_t* count) {
   if (!m || !count || max < 0 || (max > 0 && (!total_reward || !total_length))) return fail(GA3C_EINVAL, "bad argument");
   std::lock_guard<std::mutex> tl(m->train_mu);
-  Actors* a = m->actors;
+  ActorsCore* a = m->actors;
   if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
   int n = 0;
   for (; n < max && !a->finished.empty(); ++n) {
@@ -599,6 +699,29 @@ int actors_episodes(N* m, double* total_reward, int64_t* total_length, int max, 
   }
   *count = n;
   return GA3C_OK;
+}
+
+// get (out) / set (in) of one of a->fields' buffers of n environments by name; `bytes` must be the buffer's size.  The
+// stream is idle.
+inline int field_access(const ActorsCore* a, int n, const char* name, void* out, const void* in, int64_t bytes) {
+  for (const Field& f : a->fields) {
+    if (strcmp(name, f.name) != 0) continue;
+    const int64_t want = (int64_t)(f.elem * f.per_env * (size_t)n);
+    if (bytes != want) return fail(GA3C_EINVAL, "%s is %lld bytes, not %lld", name, (long long)want, (long long)bytes);
+    if (out) {
+      HIPCHK(hipMemcpy(out, f.dev, (size_t)want, hipMemcpyDeviceToHost));
+      return GA3C_OK;
+    }
+    if (!f.settable) return fail(GA3C_EINVAL, "%s is read only", name);
+    if (f.hi != NO_BOUND) {
+      const int32_t* v = static_cast<const int32_t*>(in);
+      for (int i = 0; i < n; ++i)
+        if (v[i] < 0 || v[i] > f.hi) return fail(GA3C_EINVAL, "%s[%d] = %d outside [0,%d]", name, i, v[i], f.hi);
+    }
+    HIPCHK(hipMemcpy(f.dev, in, (size_t)want, hipMemcpyHostToDevice));
+    return GA3C_OK;
+  }
+  return fail(GA3C_EINVAL, "the device actors have nothing named %s", name);
 }
 
 // get (out) / set (in) of a buffer by name; `bytes` must be the buffer's size.
@@ -632,25 +755,7 @@ int actors_access(N* m, const char* name, void* out, const void* in, int64_t byt
       memcpy(static_cast<float*>(out) + (size_t)r * S, reinterpret_cast<const char*>(ring.data()) + off[r], 4 * S);
     return GA3C_OK;
   }
-  for (const Field& f : a->fields) {
-    if (nm != f.name) continue;
-    const int64_t want = (int64_t)(f.elem * f.per_env * (size_t)d.N);
-    if (bytes != want) return fail(GA3C_EINVAL, "%s is %lld bytes, not %lld", name, (long long)want, (long long)bytes);
-    if (out) {
-      HIPCHK(hipMemcpy(out, f.dev, (size_t)want, hipMemcpyDeviceToHost));
-      return GA3C_OK;
-    }
-    if (!f.settable) return fail(GA3C_EINVAL, "%s is read only", name);
-    if (nm == "elapsed" || nm == "time_count" || nm == "started") {
-      const int32_t* v = static_cast<const int32_t*>(in);
-      const int hi = nm == "time_count" ? d.time_max : nm == "started" ? 1 : 1 << 30;
-      for (int i = 0; i < d.N; ++i)
-        if (v[i] < 0 || v[i] > hi) return fail(GA3C_EINVAL, "%s[%d] = %d outside [0,%d]", name, i, v[i], hi);
-    }
-    HIPCHK(hipMemcpy(f.dev, in, (size_t)want, hipMemcpyHostToDevice));
-    return GA3C_OK;
-  }
-  return fail(GA3C_EINVAL, "the device actors have nothing named %s", name);
+  return field_access(a, d.N, name, out, in, bytes);
 }
 
 }  // namespace ga3c_actors

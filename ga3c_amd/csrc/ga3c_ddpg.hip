@@ -28,6 +28,8 @@
 //   ddpg_actors_episodes_kernel    one workgroup: this step's episode records into the episode ring, environment order
 //   ddpg_uniform_slots_kernel      a train step's rows without priorities: a stratified draw in integers, on the device
 // An actor step is predict + 2 launches; every launch argument is known to the host, which waits once per actors_run.
+// The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
+// ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
 #include <deque>
 #include <new>
@@ -640,12 +642,11 @@ __global__ __launch_bounds__(PER_THREADS) void per_update_kernel(const int32_t* 
 
 // ------------------------------------------------------------------ device actors
 constexpr int ACT_THREADS = 256;             // the step kernel: one thread per environment
-constexpr int ACT_SCAN = 1024;               // the one-workgroup episode scan
 constexpr int ACT_MAX_UPDATES = 16;
 
 // Everything the actor kernels touch besides the replay ring, by device address; per environment unless said otherwise.
 struct ActState {
-  int N, ep_cap;
+  int N;
   uint64_t seed;
   double* phys;              // [N][P] f64 physics
   int* elapsed;
@@ -656,12 +657,7 @@ struct ActState {
   int* done;
   double* total_reward;      // of the running episode: the rewards in step order
   long long* total_length;   // its transitions
-  int* ep_flag;              // this step finished an episode: its record
-  double* ep_reward;
-  long long* ep_length;
-  int* counts;               // [2]: records in the episode ring, episodes this step finished
-  double* ring_ep_reward;    // [ep_cap] the episode ring, in the order the episodes finished
-  long long* ring_ep_length;
+  ga3c_actors::Episodes ep;  // this step's finished episodes and the episode ring
 };
 
 // One step of environment i = the thread's index.  first: the handle's first ever step, the host's step(None): the zero action,
@@ -678,8 +674,8 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState 
   constexpr int S = Env::S, P = Env::P, A = Env::A;
   constexpr int rowf = 2 * S + A + 2;
   double s[P];
-  for (int k = 0; k < P; ++k) s[k] = a.phys[(size_t)i * P + k];
-  int elapsed = a.elapsed[i];
+  int elapsed;
+  ga3c_actors::load_physics<P>(a.phys, a.elapsed, i, s, elapsed);
   float av[A];
   for (int j = 0; j < A; ++j) av[j] = first ? 0.f : a.action[(size_t)i * A + j];
   float* obs = a.obs + (size_t)i * S;
@@ -692,11 +688,10 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState 
   for (int k = 0; k < S; ++k) obs[k] = after[k];
   a.reward[i] = reward;
   a.done[i] = done;
-  a.ep_flag[i] = 0;
+  a.ep.ep_flag[i] = 0;
   if (first) {
     for (int j = 0; j < A; ++j) a.action[(size_t)i * A + j] = 0.f;
-    for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
-    a.elapsed[i] = elapsed;
+    ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
     return;
   }
   const int64_t slot = (slot0 + i) % cap;
@@ -710,55 +705,20 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState 
   double total = a.total_reward[i] + reward;
   long long length = a.total_length[i] + 1;
   if (done) {                           // ProcessAgent.run's record of an episode shipped as one rollout: len(experiences) + 1
-    a.ep_flag[i] = 1;
-    a.ep_reward[i] = total;
-    a.ep_length[i] = length + 1;
-    total = 0.0;
-    length = 0;
     uint64_t draws = a.draws[i];
-    double ru[Env::RESET_DRAWS];
-    for (int k = 0; k < Env::RESET_DRAWS; ++k) ru[k] = ga3c_uniform::actor_uniform(a.seed, (uint64_t)i, draws++);
-    Env::reset(s, &elapsed, ru);        // the observation is left alone
+    length += 1;
+    ga3c_actors::finish_episode<Env>(a.ep, i, a.seed, total, length, draws, s, elapsed);
     a.draws[i] = draws;
   }
   a.total_reward[i] = total;
   a.total_length[i] = length;
-  for (int k = 0; k < P; ++k) a.phys[(size_t)i * P + k] = s[k];
-  a.elapsed[i] = elapsed;
+  ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
 }
 
-// One workgroup.  Thread t owns the environments [t c, (t + 1) c), c = ceil(N / ACT_SCAN); the inclusive scan over the
-// threads' counts (actors_compact_kernel's pattern) gives each its first record in the episode ring.
-__global__ __launch_bounds__(ACT_SCAN) void ddpg_actors_episodes_kernel(ActState a) {
-  __shared__ int sep[ACT_SCAN];
-  const int t = threadIdx.x;
-  const int chunk = (a.N + ACT_SCAN - 1) / ACT_SCAN;
-  const int lo = min(a.N, t * chunk), hi = min(a.N, lo + chunk);
-  const int ep0 = a.counts[0];
-  int eps = 0;
-  for (int i = lo; i < hi; ++i) eps += a.ep_flag[i];
-  sep[t] = eps;
-  __syncthreads();
-  for (int d = 1; d < ACT_SCAN; d <<= 1) {
-    const int e = t >= d ? sep[t - d] : 0;
-    __syncthreads();
-    sep[t] += e;
-    __syncthreads();
-  }
-  int ep = ep0 + sep[t] - eps;
-  for (int i = lo; i < hi; ++i)
-    if (a.ep_flag[i]) {
-      if (ep < a.ep_cap) {
-        a.ring_ep_reward[ep] = a.ep_reward[i];
-        a.ring_ep_length[ep] = a.ep_length[i];
-      }
-      ++ep;
-    }
-  __syncthreads();                      // every thread has read counts[0]
-  if (t == ACT_SCAN - 1) {
-    a.counts[0] = min(ep0 + sep[t], a.ep_cap);
-    a.counts[1] = sep[t];
-  }
+// One workgroup: the step's finished episodes go to the episode ring in environment order (ga3c_actors.hpp).
+__global__ __launch_bounds__(ga3c_actors::SCAN_THREADS) void ddpg_actors_episodes_kernel(ActState a) {
+  __shared__ int sep[ga3c_actors::SCAN_THREADS];
+  ga3c_actors::scan_append_episodes(a.ep, a.N, sep);
 }
 
 // Row k of a step's B rows from a ring that holds size > B of them: stratum [k size / B, (k + 1) size / B) in integers, and in
@@ -822,17 +782,14 @@ struct Per {
 };
 
 // Device actors of a handle (ga3c_ddpg_actors_create).  Everything below is read and written under train_mu.
-struct DActors {
+struct DActors : ga3c_actors::ActorsCore {     // block: every device buffer of `d`, and `slots`; h_counts: d.ep.counts' two
   ActState d{};
-  char* block = nullptr;                // every device buffer of `d`, and `slots`
-  int* h_counts = nullptr;              // pinned [2]
   int32_t* slots = nullptr;             // [max_batch] the last draw without priorities
   int slots_rows = 0;                   // rows of the last draw, either way
   int updates = 1;                      // train steps after an actor step
   int batch = 0;                        // rows of a train step ("batch" of actors_set; starts at max_batch)
   uint64_t draw_seed = 0, samples = 0;  // the draw of sample number n without priorities is u(draw_seed, n, row)
   bool started = false;                 // the first actor step is the environments' step(None): one flag for all of them
-  std::deque<std::pair<double, long long>> finished;     // episode records not yet drained
 };
 
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
@@ -1080,12 +1037,7 @@ void per_free(ga3c_ddpg* m) {
 }
 
 void dactors_free(ga3c_ddpg* m) {
-  DActors* a = m->actors;
-  if (!a) return;
-  (void)hipFree(a->block);
-  (void)hipHostFree(a->h_counts);
-  (void)hipGetLastError();
-  delete a;
+  ga3c_actors::actors_free(m->actors);
   m->actors = nullptr;
 }
 
@@ -1716,66 +1668,37 @@ int ga3c_ddpg_actors_create(ga3c_ddpg* m, int32_t n, int32_t updates, int64_t se
   DActors* a = new (std::nothrow) DActors();
   if (!a) return fail(GA3C_EINVAL, "out of host memory");
   ActState& d = a->d;
+  ga3c_actors::Episodes& e = d.ep;
   d.N = n;
-  d.ep_cap = n * GA3C_ACTORS_MAX_STEPS;
+  e.ep_cap = n * GA3C_ACTORS_MAX_STEPS;
   d.seed = (uint64_t)seed;
   a->updates = updates;
   a->batch = m->cfg.max_batch;
   a->draw_seed = (uint64_t)seed;
   const size_t Nn = (size_t)n, S = DEnv::S, P = DEnv::P, A = DEnv::A;
   size_t total = 0;
-  bool ok = true;
-  for (int pass = 0; pass < 2 && ok; ++pass) {      // two passes over one list: sizes, then addresses (16-byte aligned)
-    size_t at = 0;
-    auto carve = [&](auto** p, size_t count) {
-      using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
-      if (pass) *p = reinterpret_cast<T*>(a->block + at);
-      at += (count * sizeof(T) + 15) / 16 * 16;
-    };
-    carve(&d.phys, Nn * P); carve(&d.elapsed, Nn); carve(&d.draws, Nn); carve(&d.obs, Nn * S); carve(&d.action, Nn * A);
-    carve(&d.reward, Nn); carve(&d.done, Nn); carve(&d.total_reward, Nn); carve(&d.total_length, Nn); carve(&d.ep_flag, Nn);
-    carve(&d.ep_reward, Nn); carve(&d.ep_length, Nn); carve(&d.counts, 2);
-    carve(&d.ring_ep_reward, (size_t)d.ep_cap); carve(&d.ring_ep_length, (size_t)d.ep_cap);
-    carve(&a->slots, (size_t)m->cfg.max_batch);
-    if (!pass) {
-      total = at;
-      ok = hipMalloc((void**)&a->block, total) == hipSuccess && hipMemset(a->block, 0, total) == hipSuccess &&
-           hipHostMalloc((void**)&a->h_counts, 2 * sizeof(int), hipHostMallocDefault) == hipSuccess;
-    }
-  }
-  // an environment starts as the host's does: reset() when it is made (draws 0..1) and again when its first episode begins
-  // (draws 2..3), no observation
-  std::vector<double> phys(Nn * P);
-  std::vector<uint64_t> draws(Nn, 2 * DEnv::RESET_DRAWS);
-  for (size_t i = 0; i < Nn; ++i) {
-    double ru[DEnv::RESET_DRAWS];
-    int elapsed = 0;
-    for (int k = 0; k < DEnv::RESET_DRAWS; ++k) ru[k] = ga3c_uniform::actor_uniform(d.seed, i, (uint64_t)(DEnv::RESET_DRAWS + k));
-    DEnv::reset(&phys[i * P], &elapsed, ru);
-  }
-  ok = ok && hipMemcpy(d.phys, phys.data(), phys.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(d.draws, draws.data(), draws.size() * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess;
   m->actors = a;
-  if (!ok) {
+  if (!ga3c_actors::carve_block(a, 2, &total, [&](auto carve) {
+        carve(&d.phys, Nn * P); carve(&d.elapsed, Nn); carve(&d.draws, Nn); carve(&d.obs, Nn * S); carve(&d.action, Nn * A);
+        carve(&d.reward, Nn); carve(&d.done, Nn); carve(&d.total_reward, Nn); carve(&d.total_length, Nn); carve(&e.ep_flag, Nn);
+        carve(&e.ep_reward, Nn); carve(&e.ep_length, Nn); carve(&e.counts, 2);
+        carve(&e.ring_ep_reward, (size_t)e.ep_cap); carve(&e.ring_ep_length, (size_t)e.ep_cap);
+        carve(&a->slots, (size_t)m->cfg.max_batch);
+      }) ||
+      !ga3c_actors::initial_physics<DEnv>(d.seed, Nn, d.phys, d.draws)) {
     (void)hipGetLastError();
     dactors_free(m);
     return fail(GA3C_EHIP, "no memory for %d device actors (%zu bytes)", n, total);
   }
+  a->fields = {
+      {"phys", d.phys, 8, P, true},    {"elapsed", d.elapsed, 4, 1, true, 1 << 30}, {"draws", d.draws, 8, 1, true},
+      {"obs", d.obs, 4, S, true},      {"action", d.action, 4, A, false},           {"reward", d.reward, 8, 1, false},
+      {"done", d.done, 4, 1, false},
+  };
   return GA3C_OK;
 }
 
-int ga3c_ddpg_actors_destroy(ga3c_ddpg* m) {
-  if (!m) return fail(GA3C_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(m->device));
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  if (!m->actors) return fail(GA3C_ESTATE, "this network has no device actors");
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    HIPCHK(hipStreamSynchronize(m->st));
-  }
-  dactors_free(m);
-  return GA3C_OK;
-}
+int ga3c_ddpg_actors_destroy(ga3c_ddpg* m) { return ga3c_actors::actors_destroy(m); }
 
 // `steps` actor steps, each followed, when `train` is set and the ring holds MORE than a batch, by `updates` train steps.
 // Everything is enqueued without a wait in between: the host knows every launch argument (N transitions per actor step, B rows
@@ -1797,7 +1720,7 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
   int64_t calls = 0;
   {
     std::lock_guard<std::mutex> lk(m->mu);
-    HIPCHK(hipMemsetAsync(d.counts, 0, 2 * sizeof(int), m->st));     // the episode ring starts empty
+    HIPCHK(hipMemsetAsync(d.ep.counts, 0, 2 * sizeof(int), m->st));     // the episode ring starts empty
   }
   for (int s = 0; s < steps; ++s) {
     std::lock_guard<std::mutex> lk(m->mu);
@@ -1811,7 +1734,7 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
     hipLaunchKernelGGL(ddpg_actors_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
                        first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
                        m->per ? (const float*)m->per->max_pa : nullptr);
-    hipLaunchKernelGGL(ddpg_actors_episodes_kernel, dim3(1), dim3(ACT_SCAN), 0, m->st, d);
+    hipLaunchKernelGGL(ddpg_actors_episodes_kernel, dim3(1), dim3(ga3c_actors::SCAN_THREADS), 0, m->st, d);
     HIPCHK(hipGetLastError());
     a->started = true;
     if (!first) m->ring_total += N;
@@ -1836,19 +1759,15 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
   {
     std::lock_guard<std::mutex> lk(m->mu);
     if (calls) HIPCHK(hipMemcpyAsync(m->h_q, m->w.qstat, 2 * sizeof(float), hipMemcpyDeviceToHost, m->st));
-    HIPCHK(hipMemcpyAsync(a->h_counts, d.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipMemcpyAsync(a->h_counts, d.ep.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipEventRecord(m->tev, m->st));
   }
   HIPCHK(hipEventSynchronize(m->tev));
   if (calls && q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
-  const int ne = std::min(std::max(a->h_counts[0], 0), d.ep_cap);
-  if (ne > 0) {
-    std::vector<double> er((size_t)ne);
-    std::vector<long long> el((size_t)ne);
+  int64_t ne = 0;
+  {
     std::lock_guard<std::mutex> lk(m->mu);
-    HIPCHK(hipMemcpy(er.data(), d.ring_ep_reward, sizeof(double) * ne, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(el.data(), d.ring_ep_length, sizeof(long long) * ne, hipMemcpyDeviceToHost));
-    for (int i = 0; i < ne; ++i) a->finished.emplace_back(er[i], el[i]);
+    CHK(ga3c_actors::fetch_episodes(a, d.ep, a->h_counts[0], &ne));      // the wait on tev above was the wait for the ring
   }
   if (out_stats) {
     out_stats[0] = (int64_t)N * steps;
@@ -1860,18 +1779,7 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
 }
 
 int ga3c_ddpg_actors_episodes(ga3c_ddpg* m, double* total_reward, int64_t* total_length, int32_t max, int32_t* count) {
-  if (!m || !count || max < 0 || (max > 0 && (!total_reward || !total_length))) return fail(GA3C_EINVAL, "bad argument");
-  std::lock_guard<std::mutex> tl(m->train_mu);
-  DActors* a = m->actors;
-  if (!a) return fail(GA3C_ESTATE, "this network has no device actors");
-  int n = 0;
-  for (; n < max && !a->finished.empty(); ++n) {
-    total_reward[n] = a->finished.front().first;
-    total_length[n] = a->finished.front().second;
-    a->finished.pop_front();
-  }
-  *count = n;
-  return GA3C_OK;
+  return ga3c_actors::actors_episodes(m, total_reward, total_length, max, count);
 }
 
 namespace {
@@ -1910,29 +1818,7 @@ int dactors_access(ga3c_ddpg* m, const char* name, void* out, const void* in, in
     if (a->slots_rows) HIPCHK(hipMemcpy(out, m->per ? m->per->slots : a->slots, (size_t)bytes, hipMemcpyDeviceToHost));
     return GA3C_OK;
   }
-  const ga3c_actors::Field fields[] = {
-      {"phys", d.phys, 8, DEnv::P, true},    {"elapsed", d.elapsed, 4, 1, true},   {"draws", d.draws, 8, 1, true},
-      {"obs", d.obs, 4, DEnv::S, true},      {"action", d.action, 4, DEnv::A, false}, {"reward", d.reward, 8, 1, false},
-      {"done", d.done, 4, 1, false},
-  };
-  for (const ga3c_actors::Field& f : fields) {
-    if (nm != f.name) continue;
-    const int64_t want = (int64_t)(f.elem * f.per_env * (size_t)d.N);
-    CHK(sized(want));
-    if (out) {
-      HIPCHK(hipMemcpy(out, f.dev, (size_t)want, hipMemcpyDeviceToHost));
-      return GA3C_OK;
-    }
-    if (!f.settable) return fail(GA3C_EINVAL, "%s is read only", name);
-    if (nm == "elapsed") {
-      const int32_t* v = static_cast<const int32_t*>(in);
-      for (int i = 0; i < d.N; ++i)
-        if (v[i] < 0 || v[i] > (1 << 30)) return fail(GA3C_EINVAL, "%s[%d] = %d outside [0,%d]", name, i, v[i], 1 << 30);
-    }
-    HIPCHK(hipMemcpy(f.dev, in, (size_t)want, hipMemcpyHostToDevice));
-    return GA3C_OK;
-  }
-  return fail(GA3C_EINVAL, "the device actors have nothing named %s", name);
+  return ga3c_actors::field_access(a, d.N, name, out, in, bytes);
 }
 
 }  // namespace

@@ -40,15 +40,8 @@ def check_bounds(a):
 
 
 def env_step(phys, action):
-    """-> (new (th, thdot), reward): PendulumEnv.step with the wrapped f64 action in the f32 action's place."""
-    th, thdot = np.float64(phys[0]), np.float64(phys[1])
-    u = check_bounds(np.asarray(action, np.float32).reshape(-1)[0]) * po.ACTION_BOUND
-    an = po.angle_normalize(th)
-    cost = an * an + 0.1 * (thdot * thdot) + 0.001 * (u * u)
-    newthdot = thdot + (-3 * po.G / (2 * po.L) * np.sin(th + np.pi) + 3.0 / (po.M * po.L * po.L) * u) * po.DT
-    newth = th + newthdot * po.DT
-    newthdot = min(max(newthdot, -po.MAX_SPEED), po.MAX_SPEED)
-    return np.array([newth, newthdot], np.float64), float(-cost * 0.005 - 1.0)
+    """-> (new (th, thdot), reward): PendulumEnv's physics on the wrapped f64 action in the f32 action's place."""
+    return po.PendulumEnv.physics(phys, check_bounds(np.asarray(action, np.float32).reshape(-1)[0]))
 
 
 class Actor:

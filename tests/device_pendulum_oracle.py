@@ -78,8 +78,14 @@ class PendulumEnv:
     @staticmethod
     def step(phys, action):
         """-> (new (th, thdot), reward) from the f32 action vector."""
+        return PendulumEnv.physics(phys, np.float64(np.float32(np.asarray(action).reshape(-1)[0])))
+
+    @staticmethod
+    def physics(phys, a64):
+        """-> (new (th, thdot), reward) from the action in f64: step's cast, or what check_bounds made of it
+        (ddpg_actors_oracle.env_step)."""
         th, thdot = np.float64(phys[0]), np.float64(phys[1])
-        u = np.float64(np.float32(np.asarray(action).reshape(-1)[0])) * ACTION_BOUND
+        u = np.float64(a64) * ACTION_BOUND
         an = angle_normalize(th)
         cost = an * an + 0.1 * (thdot * thdot) + 0.001 * (u * u)
         newthdot = thdot + (-3 * G / (2 * L) * np.sin(th + np.pi) + 3.0 / (M * L * L) * u) * DT

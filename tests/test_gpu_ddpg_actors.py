@@ -1,6 +1,7 @@
 """-m gpu: the DDPG device actors (Config.DEVICE_DDPG, ga3c_ddpg_actors_*) against tests/ddpg_actors_oracle.py,
 which tests/test_ddpg_actors_cpu.py holds to the real ProcessAgent.  S = 3 and A = 1; N on both sides of the 16-row tile of the
-predict kernel, in one and in two workgroups of the step kernel.
+predict kernel, in one and in two workgroups of the step kernel; N = 1025 and 2500 for the one-workgroup episode scan with two
+and three environments per thread.
 
 Exact: the action (ga3c_ddpg_predict's bits on the same observations and noise), the reward (the wrap, products and one fmod on
 the device's own pre-step physics and action: no transcendental function), done, elapsed, draws, reset physics, the thdot
@@ -21,6 +22,7 @@ import ddpg_oracle as o
 import device_agents_oracle as ao
 import device_pendulum_oracle as po
 from test_gpu_ddpg import PKG, _load, _net, _same, _snapshot
+from test_gpu_device_agents import SCAN_SIZES, _forced
 from test_gpu_device_pendulum import _cases
 from test_gpu_prioritized_replay import _per_net
 
@@ -211,6 +213,44 @@ def test_forty_steps_follow_the_oracle(n, kind):
         assert ring.total == 39 * n and (ring.total > capacity or kind == "large")       # a full ring was overwritten whole
         assert _eq(_ring_rows(net, range(ring.size)), ring.rows[:ring.size])
         assert len(records) == int(np.sum(elapsed > 0)) and len(finished_on) >= (2 if n > 1 else 1)
+    finally:
+        net.close()
+
+
+@pytest.mark.parametrize("n", SCAN_SIZES)
+def test_the_episode_scan_with_several_environments_per_thread(n):
+    """step(None), then one step on which the forced episodes end.  The physics differ by environment (the seed's draws), so
+    the rewards, the rows and the records do: their order is held."""
+    seed, capacity, nz = 31 + n, 2 * n + 3, 0.8
+    net = _net(S, A, max_batch=n, capacity=capacity)
+    _load(net, *_weights(7))
+    forced = _forced(n)
+    try:
+        net.actors_create(n, seed=seed, batch=1, updates=1)
+        ora, ring = do.Actors(n, seed), do.Ring(capacity)
+        assert net.actors_run(1, train=False, noise=[nz]) == (n, 0, 0, 0)
+        ora.step(None)
+        assert net.replay_size() == (0, 0) and net.actors_episodes() == []
+        elapsed = net.actors_get("elapsed")
+        elapsed[forced] = 199
+        net.actors_set("elapsed", elapsed)
+        # the oracle re-seeded from the device's physics and observation, stepped with the device's action
+        for e, ph, ob, el in zip(ora.env, net.actors_get("phys"), net.actors_get("obs"), elapsed):
+            e.phys, e.obs, e.elapsed = ph.copy(), ob.copy(), int(el)
+        stats = net.actors_run(1, train=False, noise=[nz])
+        g = {k: net.actors_get(k) for k in ("obs", "action", "reward", "done", "elapsed", "draws")}
+        rows, eps, outs = ora.step(g["action"])
+        assert _eq(g["reward"], np.array([r["reward"] for r in outs], np.float64))
+        assert np.array_equal(np.flatnonzero(g["done"]), forced)
+        assert np.array_equal(g["elapsed"], np.array([e.elapsed for e in ora.env], np.int32))
+        assert np.array_equal(g["draws"], np.array([e.rng.draws for e in ora.env], np.uint64))
+        assert len(eps) == len(forced) == len(set(eps)) and stats == (n, 0, 0, len(eps))
+        assert net.actors_episodes() == eps               # environment order, bit for bit
+        # the rows as the device must have written them: the oracle's, with the device's own new observation as s2
+        ring.add([(row[0], row[1], row[2], row[3], g["obs"][i]) for i, row in enumerate(rows)])
+        assert net.replay_size() == (n, n) == (ring.size, ring.total)
+        assert _eq(_ring_rows(net, range(n)), ring.rows[:n])
+        assert len(np.unique(ring.rows[:n], axis=0)) == n
     finally:
         net.close()
 

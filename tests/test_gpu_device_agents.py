@@ -1,6 +1,7 @@
 """-m gpu: the device actors (Config.DEVICE_AGENTS, ga3c_dmlp_actors_*) against tests/device_agents_oracle.py,
 which tests/test_device_agents_cpu.py holds to the real ProcessAgent.  Default network, S = 4 and A = 2; N on both sides of
-the 16-row tile of the network's kernels, in one and in several workgroups of the step kernel.
+the 16-row tile of the network's kernels, in one and in several workgroups of the step kernel; N = 1025 and 2500 for the
+one-workgroup scan with two and three environments per thread.
 
 Exact: uniforms, done, elapsed, rewards, counters, observations (the f32 cast of the device's own physics), rollout rows,
 y_r, one-hot rows, batch order, episode records, and the arenas after a train step against ga3c_dmlp_train on the same
@@ -244,6 +245,62 @@ def test_forty_steps_follow_the_oracle(params, n, time_max):
         assert seen["left_out"] <= 0.01 * (seen["left_out"] + seen["compared"])
         if n >= 15:
             assert seen["stale"] and seen["carried"] and seen["limit"] and seen["fell"] and seen["short"], seen
+    finally:
+        net.close()
+
+
+SCAN_SIZES = [1025, 2500]   # environments per thread of the 1024-thread scan: 2 (thread 512 owns the last alone), 3 (thread 833 owns
+                            # the last alone, the 190 threads after it none)
+
+
+def _forced(n):
+    """The environments whose episodes a scan test ends by elapsed = 199: the first, two in one thread's chunk (thread 5), the
+    last of a chunk and the first of the next (threads 6 and 7), one far inside, the last."""
+    chunk = -(-n // 1024)
+    assert chunk >= 2
+    return np.array([0, 5 * chunk, 5 * chunk + 1, 7 * chunk - 1, 7 * chunk, 600 * (chunk - 1) + 1, n - 1])
+
+
+@pytest.mark.parametrize("n", SCAN_SIZES)
+def test_the_scan_with_several_environments_per_thread(params, n):
+    """The first cut at TIME_MAX = 2 is the fourth step, 3 rows of every environment; the forced episodes end on it.  The
+    physics differ by environment (the seed's draws), so the batch's x rows do and their order is held; a CartPole record is
+    (3 rewards of -0.995, 4) whichever environment it is of, so of the records it is the count that is held here."""
+    time_max, seed = 2, 7 + n
+    net = _net(params, 3 * n)
+    forced = _forced(n)
+    try:
+        net.actors_create(n, time_max, GAMMA, seed)
+        ora = o.Actors(n, seed, time_max, GAMMA)
+        for step in range(4):
+            if step == 3:
+                elapsed = net.actors_get("elapsed")
+                elapsed[forced] = 199
+                net.actors_set("elapsed", elapsed)
+                for i in forced:
+                    ora.env[i].elapsed = 199
+            for e, ph in zip(ora.env, net.actors_get("phys")):       # re-seeded from the device's physics before every step
+                e.phys = ph.copy()
+            stats = net.actors_run(1, train=False)
+            g = {k: net.actors_get(k) for k in ("obs", "p", "action", "done", "elapsed", "draws")}
+            res, batch, episodes = ora.step(g["p"], actions=g["action"], dones=None if step == 0 else g["done"])
+            for i, (r, e) in enumerate(zip(res, ora.env)):
+                assert r["own_done"] == bool(g["done"][i]) and e.elapsed == g["elapsed"][i] and e.rng.draws == int(g["draws"][i])
+                e.obs = g["obs"][i].copy()
+            rows = net.actors_get("batch_rows")
+            assert stats == (n, 0, 0, len(episodes))
+            got_eps = net.actors_episodes()
+            assert len(got_eps) == len(episodes)
+            for (gr, gl), (wr, wl) in zip(got_eps, episodes):
+                assert np.float64(gr).view(np.uint64) == np.float64(wr).view(np.uint64) and gl == wl
+            if step < 3:
+                assert rows == 0 and batch is None and not episodes
+                continue
+            assert rows == 3 * n and len(episodes) == len(forced)
+            assert np.array_equal(np.flatnonzero(g["done"]), forced)
+            for name, want in zip(("batch_x", "batch_a", "batch_y_r"), batch):
+                assert _same(net.actors_get(name), want), name
+            assert len(np.unique(batch[0], axis=0)) > n              # the rows tell the environments apart
     finally:
         net.close()
 

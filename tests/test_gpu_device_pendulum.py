@@ -1,7 +1,7 @@
 """-m gpu: the device actors for Pendulum-v0 (Config.DEVICE_PENDULUM, ga3c_mlp_actors_*) against
 tests/device_pendulum_oracle.py, which tests/test_device_pendulum_cpu.py holds to the real ProcessAgent.  The Pendulum
 network, S = 3 and A = 1; N on both sides of the 16-row tile of the network's kernels, in one and in two workgroups of the
-step kernel.
+step kernel; N = 1025 and 2500 for the one-workgroup scan with two and three environments per thread.
 
 Exact: done, elapsed, counters, u == -1, draws (they move only at a reset), the action (the prediction row, bit for bit), the
 reward (products and one fmod on the device's own pre-step physics and action: no transcendental function), the thdot
@@ -19,6 +19,7 @@ import pytest
 import device_agents_oracle as o
 import device_pendulum_oracle as po
 import mlp_oracle as m
+from test_gpu_device_agents import SCAN_SIZES, _forced
 
 pytestmark = pytest.mark.gpu
 
@@ -270,6 +271,50 @@ def test_forty_steps_follow_the_oracle(params, n, time_max):
         assert seen["stale"] and seen["carried"] and seen["limit"] and seen["short"], seen
         if n >= 15:
             assert len(seen["ends"]) > 1, "every episode ended on the same step"
+    finally:
+        net.close()
+
+
+@pytest.mark.parametrize("n", SCAN_SIZES)
+def test_the_scan_with_several_environments_per_thread(params, n):
+    """The first cut at TIME_MAX = 2 is the fourth step, 3 rows of every environment; the forced episodes end on it.  The
+    physics differ by environment (the seed's draws), so the rows and the records do: their order is held."""
+    time_max, seed = 2, 7 + n
+    net = _net(params, 3 * n)
+    forced = _forced(n)
+    try:
+        net.actors_create(n, time_max, GAMMA, seed)
+        ora = po.PendulumActors(n, seed, time_max, GAMMA)
+        for step in range(4):
+            if step == 3:
+                elapsed = net.actors_get("elapsed")
+                elapsed[forced] = 199
+                net.actors_set("elapsed", elapsed)
+                for i in forced:
+                    ora.env[i].elapsed = 199
+            for e, ph in zip(ora.env, net.actors_get("phys")):       # re-seeded from the device's physics before every step
+                e.phys = ph.copy()
+            stats = net.actors_run(1, train=False)
+            g = {k: net.actors_get(k) for k in ("obs", "p", "action", "reward", "done", "elapsed", "draws")}
+            res, batch, episodes = ora.step(g["p"], actions=g["action"], dones=g["done"], rewards=g["reward"])
+            for i, (r, e) in enumerate(zip(res, ora.env)):
+                assert r["own_done"] == bool(g["done"][i]) and e.elapsed == g["elapsed"][i] and e.rng.draws == int(g["draws"][i])
+                assert _same(np.float64(r["own_reward"]), g["reward"][i]), (step, i)
+                e.obs = g["obs"][i].copy()
+            rows = net.actors_get("batch_rows")
+            assert stats == (n, 0, 0, len(episodes))
+            got_eps = net.actors_episodes()
+            assert len(got_eps) == len(episodes)
+            for (gr, gl), (wr, wl) in zip(got_eps, episodes):
+                assert np.float64(gr).view(np.uint64) == np.float64(wr).view(np.uint64) and gl == wl
+            if step < 3:
+                assert rows == 0 and batch is None and not episodes
+                continue
+            assert rows == 3 * n and len(episodes) == len(forced) == len(set(episodes))
+            assert np.array_equal(np.flatnonzero(g["done"]), forced)
+            for name, want in zip(("batch_x", "batch_a", "batch_y_r"), batch):
+                assert _same(net.actors_get(name), want), name
+            assert len(np.unique(batch[0], axis=0)) > n              # the rows tell the environments apart
     finally:
         net.close()
 
