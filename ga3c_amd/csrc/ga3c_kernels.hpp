@@ -63,12 +63,40 @@ __device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x4 zero4() { return (f32x4){0.f, 0.f, 0.f, 0.f}; }
-// Pins a value in a register at this point of the program: an operand fetched from LDS ahead of time stays fetched ahead
-// of time (hipcc otherwise sinks the read down to its use, re-uses one register for all of them and waits lgkmcnt(0) in
-// front of every MFMA pair).
+// Forces a value to HAVE ARRIVED in its register at this point of the program: the empty asm reads and writes it, so the
+// compiler places the s_waitcnt for its load in front of the pin.  That keeps the read from sinking down to its use, but it
+// is no prefetch: a value pinned straight behind its load is waited for straight behind its load.  A loop that wants its
+// next operands in flight under the current MFMAs fences the two groups instead (fenced_ring below, conv_stack_fwd).
 __device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void pin(f32x4& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// Steps s0 .. s1-1 of a contraction through a ring of D operand slots: step s uses slot (s - s0) % D, and the slot is
+// refilled for step s + D as soon as its MFMAs are issued, so D - 1 steps of loads stay in flight under every step's MFMAs.
+// fetch(slot, s) must be UNCONDITIONAL (it clamps s to s1 - 1 itself): a load under a branch makes the wait-count pass give
+// up and drain everything (s_waitcnt 0) once per trip.  The fences keep each step's MFMAs and the refill behind them where
+// they are written; without them the scheduler gathers all waits at the head of the trip and all loads at its end.  The
+// tail (up to D - 1 steps) only consumes.  Steps run in ascending order whatever D is, so the sums do not depend on it.
+template <int D, class Fetch, class Step>
+__device__ __forceinline__ void fenced_ring(int s0, int s1, Fetch fetch, Step step) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) fetch(d, s0 + d);
+  int s = s0;
+  for (; s + D <= s1; s += D) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      __builtin_amdgcn_sched_barrier(0);
+      step(d);
+      fetch(d, s + d + D);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < D - 1; ++d) {
+    if (s + d < s1) step(d);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
 
 // RMSProp applied by the kernel that PRODUCES a gradient element (single-GPU train steps without clipping): the optimizer's
 // own launch, and its pass over the 4 MB dense1/w gradient, disappear.  Same arithmetic as rmsprop_one below
@@ -543,6 +571,10 @@ __global__ __launch_bounds__(1024) void conv_stack_fwd_kernel(const void* __rest
   for (int i = 0; i < 2; ++i)
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w2f + 4 * (threadIdx.x + 1024 * i)),
                                      (__attribute__((address_space(3))) void*)(wl2 + 4 * (threadIdx.x + 1024 * i - lane)), 16, 0, 0);
+  // the two bias values this lane adds in its epilogues ride with the staging loads (item & 1 = wv & 1: items step by 16).
+  // Loaded where they are used, each was a memory round trip of its own between a tile's last MFMA and its stores --
+  // conv2's at the very end of the kernel, with nothing left to hide it.
+  const float bias1 = b1[r], bias2 = b2[(wv & 1) * 16 + r];
   // nothing in the next two statements depends on the loads: they run while the loads are in flight
   for (int idx4 = threadIdx.x; idx4 < CS_N1_FLOATS / 4; idx4 += 1024) *reinterpret_cast<f32x4*>(&n1l[idx4 * 4]) = zero4();
   if (threadIdx.x < 256) {                                   // the divisions of the ragged map, once per pixel
@@ -564,31 +596,34 @@ __global__ __launch_bounds__(1024) void conv_stack_fwd_kernel(const void* __rest
   GA3C_STAMP(4);
   // ---- conv1 over the half's n1 pixels, result into the LDS image (and to HBM when training)
   {
-    const float bv = b1[r];
+    const float bv = bias1;
     const int ntile = (n1npix + 15) >> 4;                    // 15 | 16: one tile per wave
     for (int tile = wv; tile < ntile; tile += 16) {
       const int e = pxmap[tile * 16 + r];
       const int row = e >> 8, col = e & 255;
       const float* base = img + ((4 * (row - n1r0)) * C1_PW + 4 * col + g) * 4;
-      // per pair of k-steps: 2 patch reads (16 B) + 8 filter fragments, fetched and pinned one pair ahead of their 8 MFMAs
+      // per pair of k-steps: 2 patch reads (16 B) + 8 filter fragments, requested one pair ahead of their 8 MFMAs.  The
+      // fences hold the four reads of pair s + 2 in front of the MFMAs of pair s (two register sets, a counted lgkmcnt
+      // that waits for the older pair only); nothing pins the values, which would wait for them where they are read.
       f32x4 pa[2][2], pw[2][2];
       auto load_pair = [&](int s, f32x4 (&a)[2], f32x4 (&w2)[2]) {
         a[0] = ld4(base + ((s >> 1) * C1_PW + (s & 1) * 4) * 4);
         a[1] = ld4(base + (((s + 1) >> 1) * C1_PW + ((s + 1) & 1) * 4) * 4);
         w2[0] = ld4(wl1 + (s * 64 + lane) * 4);
         w2[1] = ld4(wl1 + ((s + 1) * 64 + lane) * 4);
-        pin(a[0]); pin(a[1]); pin(w2[0]); pin(w2[1]);
       };
       f32x4 acc0 = zero4(), acc1 = zero4();
       load_pair(0, pa[0], pw[0]);
 #pragma unroll
       for (int s = 0; s < 16; s += 2) {
         if (s + 2 < 16) load_pair(s + 2, pa[((s >> 1) + 1) & 1], pw[((s >> 1) + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           acc0 = mfma(pa[(s >> 1) & 1][0][t], pw[(s >> 1) & 1][0][t], acc0);
           acc1 = mfma(pa[(s >> 1) & 1][1][t], pw[(s >> 1) & 1][1][t], acc1);
         }
+        __builtin_amdgcn_sched_barrier(0);
       }
       const int4 e4 = *reinterpret_cast<const int4*>(&pxmap[tile * 16 + 4 * g]);
       const int em[4] = {e4.x, e4.y, e4.z, e4.w};
@@ -628,20 +663,22 @@ __global__ __launch_bounds__(1024) void conv_stack_fwd_kernel(const void* __rest
         a[1] = ld4(base + (((s + 1) >> 2) * C2_PW + ((s + 1) & 3)) * C1);
         w2[0] = ld4(wf + (s * 64 + lane) * 4);
         w2[1] = ld4(wf + ((s + 1) * 64 + lane) * 4);
-        pin(a[0]); pin(a[1]); pin(w2[0]); pin(w2[1]);
       };
       f32x4 acc0 = zero4(), acc1 = zero4();
       load_pair(0, pa[0], pw[0]);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int s = 0; s < 16; s += 2) {
+      for (int s = 0; s < 16; s += 2) {                  // fenced as in conv1: pair s + 2 in flight under pair s
         if (s + 2 < 16) load_pair(s + 2, pa[((s >> 1) + 1) & 1], pw[((s >> 1) + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           acc0 = mfma(pa[(s >> 1) & 1][0][t], pw[(s >> 1) & 1][0][t], acc0);
           acc1 = mfma(pa[(s >> 1) & 1][1][t], pw[(s >> 1) & 1][1][t], acc1);
         }
+        __builtin_amdgcn_sched_barrier(0);
       }
-      const float bv = b2[hh * 16 + r];
+      const float bv = bias2;                                // = b2[hh * 16 + r]
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int mr = tile * 16 + 4 * g + q;
@@ -720,7 +757,7 @@ __global__ __launch_bounds__(256) void pack_wd_kernel(const float* __restrict__ 
 
 // ------------------------------------------------------------------ dense1 forward (split-K)
 // part[ks][b][n] = sum_{k in slice ks} flat[b][k] Wd[k][n];  M = B, N = 256, K = 3872 = 242 steps of 16.
-// Wave tile (16*MT rows) x 32 columns, operands as 16-byte loads (flat rows; packed Wd), next step's
+// Wave tile (16*MT rows) x 32 columns, operands as 16-byte loads (flat rows; packed Wd), the next D - 1 steps'
 // operands in flight during the current step's MFMAs.  1-D grid, XCD-aware: blocks are dealt round-robin
 // to the 8 XCDs, so block id -> (xcd = id % 8, j = id / 8); all row blocks that read the same slice of Wd
 // (same ks, same column half) get the same xcd and share that XCD's L2 copy of it.
@@ -753,35 +790,32 @@ __global__ __launch_bounds__(256) void dense1_fwd_kernel(const float* __restrict
   // count can be picked to fill whole rounds of workgroups on the 256 CUs rather than to divide 242
   const int s0 = steps_per_slice > 0 ? ks * steps_per_slice : (ks * KSTEPS_DENSE) / ks_total;
   const int s1 = steps_per_slice > 0 ? s0 + steps_per_slice : ((ks + 1) * KSTEPS_DENSE) / ks_total;
-  // D steps of operands in flight (a ring of register slots, the loop unrolled by D so that slot numbers are compile-time):
-  // a step is a dependent L2 round trip, and one step of prefetch left the wave waiting on most of it
+  // D steps of operands in a ring of register slots (fenced_ring: the loop unrolled by D so that slot numbers are
+  // compile-time): a step is a dependent L2 round trip, so D - 1 of them stay in flight under each step's MFMAs and every
+  // wait is counted (vmcnt of the loads behind the slot in use).  The loads are unconditional: past the slice's end they
+  // repeat its last step into a slot nobody reads, and an invalid row reads row 0 and is zeroed where it is used.
   constexpr int D = MT == 1 ? 4 : 2;
   f32x4 a[D][MT], w0[D], w1[D];
   auto fetch = [&](int slot, int s) {
-    if (s < s1) {
+    const int sc = s < s1 ? s : s1 - 1;
 #pragma unroll
-      for (int mi = 0; mi < MT; ++mi) a[slot][mi] = v[mi] ? ld4(ap[mi] + 16 * s) : zero4();
-      w0[slot] = ld4(w0p + (size_t)s * HID * 16);
-      w1[slot] = ld4(w1p + (size_t)s * HID * 16);
-    }
+    for (int mi = 0; mi < MT; ++mi) a[slot][mi] = ld4(ap[mi] + 16 * sc);
+    w0[slot] = ld4(w0p + (size_t)sc * HID * 16);
+    w1[slot] = ld4(w1p + (size_t)sc * HID * 16);
   };
+  auto step = [&](int d) {
+    f32x4 av[MT];
 #pragma unroll
-  for (int d = 0; d < D; ++d) fetch(d, s0 + d);
-  for (int s = s0; s < s1; s += D) {
+    for (int mi = 0; mi < MT; ++mi) av[mi] = v[mi] ? a[d][mi] : zero4();
 #pragma unroll
-    for (int d = 0; d < D; ++d) {
-      if (s + d < s1) {
+    for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int mi = 0; mi < MT; ++mi) {
-            acc[mi][0][t & 1] = mfma(a[d][mi][t], w0[d][t], acc[mi][0][t & 1]);
-            acc[mi][1][t & 1] = mfma(a[d][mi][t], w1[d][t], acc[mi][1][t & 1]);
-          }
-        fetch(d, s + d + D);
+      for (int mi = 0; mi < MT; ++mi) {
+        acc[mi][0][t & 1] = mfma(av[mi][t], w0[d][t], acc[mi][0][t & 1]);
+        acc[mi][1][t & 1] = mfma(av[mi][t], w1[d][t], acc[mi][1][t & 1]);
       }
-    }
-  }
+  };
+  fenced_ring<D>(s0, s1, fetch, step);
   float* out = part + ((size_t)ks * B) * HID + n0 + r;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi)
@@ -797,8 +831,9 @@ __global__ __launch_bounds__(256) void dense1_fwd_kernel(const float* __restrict
 // ---- the same partial products, LDS-tiled: a workgroup (8 waves) = (16*MT rows, 128 columns, one K slice of <= 16 steps).
 // Its whole working set -- the slice of the packed Wd (<= 128 KB, 1 KB per step and 16 columns = one LDS-DMA wave
 // instruction) and the rows' flat slice (1 KB per row, padded to 260 floats) -- is requested up front and lands in LDS
-// without a VGPR pass; the MFMAs then run from LDS without a memory wait between them.  The register-fragment kernel
-// above has one step of prefetch and pays a memory round trip per step (15 dependent round trips per slice).
+// without a VGPR pass; the MFMAs then run from LDS without a memory wait between them.  Its LDS loop is rolled (two
+// ds_read_b128, lgkmcnt(0), 4 MFMAs per trip): the fenced ring of the kernel above, tried here with three steps of LDS
+// reads in flight, compiled as intended and measured no gain (profiles/README.md, "Forward prefetches"), so it stays.
 constexpr int D1F_AS = 16 * 16 + 4;              // LDS row stride of the flat slice (floats)
 __host__ __device__ constexpr int d1f_lds_floats(int mt, int max_steps) { return max_steps * 8 * 256 + 16 * mt * D1F_AS; }
 
