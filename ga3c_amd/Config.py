@@ -79,6 +79,12 @@ class Config:
     DDPG_FUTURE_REWARD_CALC = True      # y = r + gamma q' on rows that are not done; False: y = r
     DDPG_CRITIC_LOSS = 'fork'           # 'fork': mean_square(y[B], q[B,1]) broadcasts, the critic regresses on mean(y), as the
                                         # reference computes it; 'paired': (q_i - y_i)^2
+    DDPG_TWIN = False                   # USE_DDPG only: two critics, y from the smaller target value at a smoothed target action,
+                                        # the actor and the targets stepped every DDPG_POLICY_DELAY-th train step (Fujimoto et
+                                        # al. 2018, "TD3"); needs DDPG_CRITIC_LOSS = 'paired' 
+    DDPG_POLICY_DELAY = 2               # a policy step every this many train steps (1..16)
+    DDPG_TARGET_NOISE = 0.2             # sigma of the target smoothing: a~ = clip(actor_target(s2) + clip(sigma n, -c, c), -1, 1)
+    DDPG_TARGET_NOISE_CLIP = 0.5        # ... and its c
     tau = 0.001
     gamma = 0.99
     actor_lr = 1.0                      # factors on the annealed learning rate; the later of the two assignments in the
@@ -213,6 +219,8 @@ def resolve_ddpg(explicit=()):
     if not Config.USE_DDPG:
         if Config.PRIORITIZED_REPLAY:
             raise ValueError("PRIORITIZED_REPLAY needs USE_DDPG: only the DDPG handle keeps a replay memory")
+        if Config.DDPG_TWIN:
+            raise ValueError("DDPG_TWIN needs USE_DDPG: the twin critics are the DDPG handle's")
         return
     if not Config.CONTINUOUS_INPUT:
         raise ValueError("USE_DDPG needs a continuous action space (CONTINUOUS_INPUT); GAME=%s is discrete" % Config.GAME)
@@ -247,6 +255,16 @@ def resolve_ddpg(explicit=()):
         if Config.PRIORITIZED_REPLAY_BETA_START < 0.0 or Config.PRIORITIZED_REPLAY_BETA_END < 0.0:
             raise ValueError("PRIORITIZED_REPLAY_BETA_START / _END = %r / %r: exponents >= 0"
                              % (Config.PRIORITIZED_REPLAY_BETA_START, Config.PRIORITIZED_REPLAY_BETA_END))
+    if Config.DDPG_TWIN:
+        if Config.DDPG_CRITIC_LOSS != 'paired':
+            raise ValueError("DDPG_TWIN with DDPG_CRITIC_LOSS=%r is not supported: under the fork's loss the critics regress on "
+                             "the batch mean of y and a row has no target of its own.  Set DDPG_CRITIC_LOSS=paired"
+                             % (Config.DDPG_CRITIC_LOSS,))
+        if not 1 <= int(Config.DDPG_POLICY_DELAY) <= 16:
+            raise ValueError("DDPG_POLICY_DELAY=%r: a policy step every 1 to 16 train steps" % (Config.DDPG_POLICY_DELAY,))
+        if not Config.DDPG_TARGET_NOISE >= 0.0 or not Config.DDPG_TARGET_NOISE_CLIP >= 0.0:
+            raise ValueError("DDPG_TARGET_NOISE / _CLIP = %r / %r: numbers >= 0"
+                             % (Config.DDPG_TARGET_NOISE, Config.DDPG_TARGET_NOISE_CLIP))
     Config.USE_REPLAY_MEMORY = True
     Config.DISCOUNTING = False
 

@@ -7,7 +7,8 @@ ga3c_ddpg handle of libga3c_hip.so.
 Same interface as NetworkVP.Network where Server, ThreadPredictor and ThreadTrainer use it.  The replay memory lives in
 the handle (replay_add*, train_replay); the Ornstein-Uhlenbeck process too, because the native predictor loops call the
 handle without the interpreter.  Under Config.PRIORITIZED_REPLAY the handle also keeps a priority per ring slot and draws a
-step's rows itself (train_prioritized).
+step's rows itself (train_prioritized).  Under Config.DDPG_TWIN it has a second critic, critic2_*, and every
+train-type call runs the twin step (twin_create).
 """
 import ctypes as C
 import os
@@ -26,11 +27,16 @@ ACTOR_TRAINABLE = ("actor_fc1/W", "actor_fc1/b", "actor_norm1/beta", "actor_norm
 CRITIC_TRAINABLE = ("critic_fc1/W", "critic_fc1/b", "critic_norm1/beta", "critic_norm1/gamma", "critic_fc2/W", "critic_fc2/b",
                     "critic_norm2/W", "critic_norm2/b", "critic_output/W", "critic_output/b")
 TRAINABLE = ACTOR_TRAINABLE + CRITIC_TRAINABLE
+TWIN_TRAINABLE = tuple("critic2_" + k[len("critic_"):] for k in CRITIC_TRAINABLE)      # of a handle with twin critics
 VALUE, TARGET, SLOT_A, SLOT_B, GRAD = range(5)
 
 
-def param_shapes(state_dim, num_actions):
+def param_shapes(state_dim, num_actions, twin=False):
     S, A = int(state_dim), int(num_actions)
+    if twin:                                # + critic 2's, shaped as the critic's
+        shapes = param_shapes(S, A)
+        shapes.update(zip(TWIN_TRAINABLE, [shapes[k] for k in CRITIC_TRAINABLE]))
+        return shapes
     return {"actor_fc1/W": (S, H1), "actor_fc1/b": (H1,), "actor_norm1/beta": (H1,), "actor_norm1/gamma": (H1,),
             "actor_fc2/W": (H1, H2), "actor_fc2/b": (H2,), "actor_norm2/beta": (H2,), "actor_norm2/gamma": (H2,),
             "actor_output/W": (H2, A), "actor_output/b": (A,),
@@ -51,7 +57,7 @@ def _truncated_normal(rng, shape, stddev):
 def _draw(rng, name, shape):
     """tflearn's defaults as DESIGN.md 8f restates them (the one place): W truncated normal 0.02, the two output layers
     U(-0.003, 0.003) (NetworkDDPG.py:226,408), b = 0, beta = 0, gamma ~ N(1, 0.002)."""
-    if name in ("actor_output/W", "critic_output/W"):
+    if name in ("actor_output/W", "critic_output/W", "critic2_output/W"):
         return rng.uniform(-0.003, 0.003, size=shape)
     if name.endswith("/W"):
         return _truncated_normal(rng, shape, 0.02)
@@ -60,16 +66,20 @@ def _draw(rng, name, shape):
     return np.zeros(shape)
 
 
-def initial_arena(state_dim, num_actions, seed, tau=None):
+def initial_arena(state_dim, num_actions, seed, tau=None, twin=False):
     """-> (online, target): dicts of f32 arrays for the 20 trainable variables, drawn from one PCG64(seed) stream in variable
     order, the online networks first (actor, critic), then independently drawn targets in the same order.  The reference does
-    not copy the online weights: it runs ONE soft update on those targets (NetworkDDPG.py:17-21), restated here."""
+    not copy the online weights: it runs ONE soft update on those targets (NetworkDDPG.py:17-21), restated here.
+    twin: critic 2's ten as well, drawn after all of those from the same stream (online, then targets), so that the 20 are
+    what they are without it."""
     tau = Config.tau if tau is None else tau
     rng = np.random.Generator(np.random.PCG64(seed))
-    shapes = param_shapes(state_dim, num_actions)
-    online = {k: _draw(rng, k, shapes[k]).astype(np.float32) for k in TRAINABLE}
-    target0 = {k: _draw(rng, k, shapes[k]).astype(np.float32) for k in TRAINABLE}
-    target = {k: (np.float32(tau) * online[k] + np.float32(1.0 - tau) * target0[k]).astype(np.float32) for k in TRAINABLE}
+    shapes = param_shapes(state_dim, num_actions, twin)
+    online, target = {}, {}
+    for names in (TRAINABLE,) + ((TWIN_TRAINABLE,) if twin else ()):
+        online.update({k: _draw(rng, k, shapes[k]).astype(np.float32) for k in names})
+        target0 = {k: _draw(rng, k, shapes[k]).astype(np.float32) for k in names}
+        target.update({k: (np.float32(tau) * online[k] + np.float32(1.0 - tau) * target0[k]).astype(np.float32) for k in names})
     return online, target
 
 
@@ -118,8 +128,12 @@ class Network(DeviceActors, NativeHandle):
         nat.check(self._fn("create")(C.byref(cfg), C.byref(handle)), "ga3c_ddpg_create")
         self._h = handle
         self.replay_capacity = cfg.replay_capacity
-        online, target = initial_arena(self.S, self.num_actions, Config.RANDOM_SEED)
-        for k in TRAINABLE:
+        self.twin = bool(Config.DDPG_TWIN)
+        if self.twin:                           # before the initial values: it adds critic 2's variables
+            self._call("twin_create", int(Config.DDPG_POLICY_DELAY), float(Config.DDPG_TARGET_NOISE),
+                       float(Config.DDPG_TARGET_NOISE_CLIP), int(Config.RANDOM_SEED))
+        online, target = initial_arena(self.S, self.num_actions, Config.RANDOM_SEED, twin=self.twin)
+        for k in TRAINABLE + (TWIN_TRAINABLE if self.twin else ()):
             self.set_variable_value(k, online[k], VALUE)
             self.set_variable_value(k, target[k], TARGET)
         self._log_lock = threading.Lock()

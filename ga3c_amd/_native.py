@@ -200,6 +200,9 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_sample_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, i32p, f32p]),
     "ga3c_ddpg_train_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, f32p, f32p, i32p]),
     "ga3c_ddpg_time_prioritized": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, f32p]),
+    # twin critics of a DDPG handle (Config.DDPG_TWIN), include/ga3c_abi.h
+    "ga3c_ddpg_twin_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int64]),
+    "ga3c_ddpg_twin_destroy": (C.c_int, [C.c_void_p]),
     # device actors of a DDPG handle (Config.DEVICE_DDPG), include/ga3c_abi.h: ga3c_ddpg_actors_*
     "ga3c_ddpg_actors_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),
     "ga3c_ddpg_actors_destroy": (C.c_int, [C.c_void_p]),

@@ -27,6 +27,14 @@
 //   ddpg_actors_step_kernel<Env>   one thread per environment: the step, its transition into the ring, the episode record
 //   ddpg_actors_episodes_kernel    one workgroup: this step's episode records into the episode ring, environment order
 //   ddpg_uniform_slots_kernel      a train step's rows without priorities: a stratified draw in integers, on the device
+// Twin critics (ga3c_ddpg_twin_create, Config.DDPG_TWIN; tests/td3_oracle.py is the same statement):
+//   ddpg_twin_target_kernel    actor_target, the smoothed and clipped target action, both target critics, y from their min
+//   ddpg_twin_critic_kernel    ddpg_critic_kernel's step for critic blockIdx.y
+//   ddpg_twin_wgrad_kernel     ddpg_wgrad_kernel's elements for critic blockIdx.y
+//   ddpg_twin_update_kernel    ddpg_update_kernel's blocks for both critics' variables
+// A twin step is 3 launches (4 with clipping); a policy step, every policy_delay-th, adds ddpg_actor_kernel and the actor's
+// ddpg_wgrad_kernel.  Critic 2's variables lie behind the 26 in every arena and are read through a second Layout whose
+// critic entries name them (twin_view), so the device functions of one critic serve both.
 // An actor step is predict + 2 launches; every launch argument is known to the host, which waits once per actors_run.
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
@@ -73,6 +81,11 @@ const char* const VAR_NAMES[NVARS] = {
     "actor_norm1/moving_mean", "actor_norm1/moving_variance", "actor_norm2/moving_mean", "actor_norm2/moving_variance",
     "critic_norm1/moving_mean", "critic_norm1/moving_variance"};
 
+// ... and the twin's (ga3c_ddpg_twin_create): critic 2's, variables 26..37 of such a handle
+const char* const TWIN_VAR_NAMES[12] = {
+    "critic2_fc1/W", "critic2_fc1/b", "critic2_norm1/beta", "critic2_norm1/gamma", "critic2_fc2/W", "critic2_fc2/b", "critic2_norm2/W",
+    "critic2_norm2/b", "critic2_output/W", "critic2_output/b", "critic2_norm1/moving_mean", "critic2_norm1/moving_variance"};
+
 struct Layout {
   int S, A;
   int rows[NVARS], cols[NVARS];    // a vector has rows = 0
@@ -95,6 +108,26 @@ inline Layout make_layout(int S, int A) {
   L.off[NVARS] = o;
   return L;
 }
+
+// The twin's twelve variables lie behind the 26, in the critic's order: its ten trainable ones, then its moving statistics.
+constexpr int NTWIN = 12;
+constexpr int NCRITIC = NTRAIN - NACTOR;
+
+// L with the critic's entries naming critic 2's variables: off[NACTOR .. NTRAIN] its trainable ones and their end, off[C_MM1],
+// off[C_MV1] its statistics.  The actor's statistics have no meaning in the view; no critic code reads them.
+inline Layout twin_view(const Layout& L) {
+  Layout V = L;
+  const int64_t shift = L.off[NVARS] - L.off[NACTOR];
+  for (int v = NACTOR; v <= NTRAIN; ++v) V.off[v] = L.off[v] + shift;
+  for (int v = NTRAIN + 1; v < C_MM1; ++v) V.off[v] = V.off[NTRAIN];
+  V.off[C_MM1] = V.off[NTRAIN];
+  V.off[C_MV1] = V.off[C_MM1] + H1;
+  V.off[NVARS] = V.off[C_MV1] + H1;
+  return V;
+}
+
+template <class T>
+struct Pair { T v[2]; };       // a kernel argument per critic, chosen by blockIdx.y
 
 // Where a step's rows lie: row i is `rowf` floats at base + (idx ? idx[i] : i) * rowf: s[S] | a[A] | r | done | s2[S].
 struct Rows {
@@ -119,6 +152,17 @@ struct Work {
   float *a_out, *a_noisy, *g, *dout;           // [B,A]
   float* qstat;                                // {max q, mean q}
 };
+
+// ... and the twin's: the target step's rows and critic 2's copy of every c_* buffer.
+struct Work2 {
+  float *qt1, *qt2, *q2, *dq2;                 // [B]
+  float *t_eps, *t_a;                          // [B,A]: the smoothing noise and the target action it gives
+  float *c2_xh1, *c2_c1, *c2_dn1, *c2_dh1;     // [B,400]
+  float *c2_c2, *c2_dt;                        // [B,300]
+};
+
+// What one critic's step writes; x, a null: the inputs are not kept.
+struct CriticRows { float *q, *dq, *x, *a, *xh1, *c1, *dn1, *dh1, *c2, *dt; };
 
 struct Opt {
   float *theta, *target, *sa, *sb, *grad;
@@ -275,9 +319,63 @@ __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(Layout L, const fl
   }
 }
 
+// Steps 1-2 of a twin step.  The target action of row k = row0 + r, action i: a~ = clip(actor_target(s2) + eps,
+// -1, 1), eps = (f32) clip(sigma n, -c, c), n Box-Muller in f64 on uniforms 2j and 2j + 1 of stream `number`, j = k A + i.
+// Both target critics read a~ from `act`, one after the other in the same buffers; y comes from the smaller q'.
+__global__ __launch_bounds__(THREADS) void ddpg_twin_target_kernel(Pair<Layout> L, const float* __restrict__ thT, Rows src, int B,
+                                                                   float gamma, int future, float sigma, float clip, uint64_t seed,
+                                                                   uint64_t number, Work w, Work2 w2) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  __shared__ float qv[TILE];
+  __shared__ float qv2[TILE];
+  const int S = L.v[0].S, A = L.v[0].A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  if (future) {
+    load_rows(src, S + A + 2, S, xin, row0, nrows, nullptr);
+    __syncthreads();
+    actor_fwd(L.v[0], thT, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+      const int i = e / TILE, r = e % TILE;
+      const uint64_t j = (uint64_t)(row0 + r) * (uint64_t)A + (uint64_t)i;
+      const double u1 = 1.0 - ga3c_uniform::actor_uniform(seed, number, 2 * j);
+      const double u2 = ga3c_uniform::actor_uniform(seed, number, 2 * j + 1);
+      const double n = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+      const float eps = (float)fmin(fmax((double)sigma * n, -(double)clip), (double)clip);
+      const float a = fminf(fmaxf(act[e] + eps, -1.f), 1.f);
+      act[e] = a;
+      if (r < nrows) {
+        w2.t_eps[(size_t)(row0 + r) * A + i] = eps;
+        w2.t_a[(size_t)(row0 + r) * A + i] = a;
+      }
+    }
+    __syncthreads();
+    critic_fwd(L.v[0], thT, xin, act, bufA, bufB, qv, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+    critic_fwd(L.v[1], thT, xin, act, bufA, bufB, qv2, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+  }
+  if (threadIdx.x < nrows) {
+    const int r = threadIdx.x;
+    const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
+    const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
+    float y = rew, qt = 0.f, q1 = 0.f, q2 = 0.f;
+    if (future) {
+      q1 = qv[r];
+      q2 = qv2[r];
+      qt = fminf(q1, q2);
+      if (done == 0.f) y = fmaf(gamma, qt, rew);
+    }
+    w.y[row0 + r] = y;
+    w.qt[row0 + r] = qt;
+    w2.qt1[row0 + r] = q1;
+    w2.qt2[row0 + r] = q2;
+  }
+}
+
 // per_w (null without priorities): the rows' importance weights, dq_i = (2/B) w_i (q_i - y_i)
-__global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const float* __restrict__ th, Rows src, int B, int paired,
-                                                              const float* __restrict__ per_w, Work w) {
+__device__ __forceinline__ void critic_step(const Layout& L, const float* __restrict__ th, const Rows& src, int B, int paired,
+                                            const float* __restrict__ per_w, const float* __restrict__ y, const CriticRows& w) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
@@ -289,17 +387,17 @@ __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const fl
   const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
   // mean(y), the same fixed order in every block: strided partials, then block_sum's tree
   float ysum = 0.f;
-  for (int i = threadIdx.x; i < B; i += THREADS) ysum += w.y[i];
+  for (int i = threadIdx.x; i < B; i += THREADS) ysum += y[i];
   const float ymean = block_sum<THREADS>(ysum, red) / (float)B;
-  load_rows(src, 0, S, xin, row0, nrows, w.c_x);
-  load_rows(src, S, A, act, row0, nrows, w.c_a);
+  load_rows(src, 0, S, xin, row0, nrows, w.x);
+  load_rows(src, S, A, act, row0, nrows, w.a);
   __syncthreads();
-  critic_fwd(L, th, xin, act, bufA, bufB, qv, CriticKeep{w.c_xh1, w.c_c1, w.c_c2}, row0, nrows);
+  critic_fwd(L, th, xin, act, bufA, bufB, qv, CriticKeep{w.xh1, w.c1, w.c2}, row0, nrows);
   if (threadIdx.x < TILE) {
     const int r = threadIdx.x;
     float dq = 0.f;
     if (r < nrows) {
-      const float ref = paired ? w.y[row0 + r] : ymean;
+      const float ref = paired ? y[row0 + r] : ymean;
       dq = (2.0f / (float)B) * (qv[r] - ref);
       if (per_w) dq *= per_w[row0 + r];
       w.q[row0 + r] = qv[r];
@@ -314,7 +412,7 @@ __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const fl
     const int j = e / TILE, r = e % TILE;
     const float d = bufB[e] > 0.f ? dqv[r] * wo[j] : 0.f;
     bufB[e] = d;
-    if (r < nrows) w.c_dt[(size_t)(row0 + r) * H2 + j] = d;
+    if (r < nrows) w.dt[(size_t)(row0 + r) * H2 + j] = d;
   }
   __syncthreads();
   // delta at critic_norm1's output (in place over c1: thread k reads and writes row k alone) and at critic_fc1's
@@ -322,10 +420,24 @@ __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const fl
     const float d = bufA[k * TILE + r] > 0.f ? s : 0.f;
     bufA[k * TILE + r] = d;
     if (r < nrows) {
-      w.c_dn1[(size_t)(row0 + r) * H1 + k] = d;
-      w.c_dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, L, C_MV1, C_GA1, k);
+      w.dn1[(size_t)(row0 + r) * H1 + k] = d;
+      w.dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, L, C_MV1, C_GA1, k);
     }
   });
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const float* __restrict__ th, Rows src, int B, int paired,
+                                                              const float* __restrict__ per_w, Work w) {
+  critic_step(L, th, src, B, paired, per_w, w.y, CriticRows{w.q, w.dq, w.c_x, w.c_a, w.c_xh1, w.c_c1, w.c_dn1, w.c_dh1, w.c_c2, w.c_dt});
+}
+
+// Critic blockIdx.y's step on the same rows and the same y, always in the paired form.  Critic 1 keeps the inputs.
+__global__ __launch_bounds__(THREADS) void ddpg_twin_critic_kernel(Pair<Layout> L, const float* __restrict__ th, Rows src, int B,
+                                                                   const float* __restrict__ per_w, Work w, Work2 w2) {
+  const bool two = blockIdx.y != 0;
+  const CriticRows rows = two ? CriticRows{w2.q2, w2.dq2, nullptr, nullptr, w2.c2_xh1, w2.c2_c1, w2.c2_dn1, w2.c2_dh1, w2.c2_c2, w2.c2_dt}
+                              : CriticRows{w.q, w.dq, w.c_x, w.c_a, w.c_xh1, w.c_c1, w.c_dn1, w.c_dh1, w.c_c2, w.c_dt};
+  critic_step(L.v[blockIdx.y], th, src, B, 1, per_w, w.y, rows);
 }
 
 __global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const float* __restrict__ th, Rows src, int B, Noise nz,
@@ -431,10 +543,10 @@ __device__ __forceinline__ void soft_step(const Opt& o, int64_t i) {
   o.target[i] = o.tau * o.theta[i] + (1.0f - o.tau) * o.target[i];
 }
 
-// Variables v0 .. v1-1 (one net's trainable ones).  FUSED: + the optimizer step (o.apply) and the soft update (o.soft).
-// The critic's launch also leaves {max q, mean q}, summed in row order by one thread.
+// The thread's element of variables v0 .. v1-1 (one net's trainable ones, read through L).  FUSED: + the optimizer step
+// (o.apply) and the soft update (o.soft).
 template <bool FUSED>
-__global__ __launch_bounds__(THREADS) void ddpg_wgrad_kernel(Layout L, GradSrc src, int v0, int v1, int B, Opt o, Work w) {
+__device__ __forceinline__ void wgrad_element(const Layout& L, const GradSrc& src, int v0, int v1, int B, const Opt& o) {
   const int64_t e = L.off[v0] + (int64_t)blockIdx.x * THREADS + threadIdx.x;
   if (e < L.off[v1]) {
     int v = v1 - 1;
@@ -460,22 +572,37 @@ __global__ __launch_bounds__(THREADS) void ddpg_wgrad_kernel(Layout L, GradSrc s
     }
     if (FUSED && o.soft) soft_step(o, e);
   }
-  if (v0 == NACTOR && blockIdx.x == 0 && threadIdx.x == 0) {
-    float mx = w.q[0], s = 0.f;
-    for (int r = 0; r < B; ++r) {
-      const float q = w.q[r];
-      mx = fmaxf(mx, q);
-      s += q;
-    }
-    w.qstat[0] = mx;
-    w.qstat[1] = s / (float)B;
-  }
 }
 
-// One block per variable v0 + blockIdx.x: tf.clip_by_norm (g clip / max(||g||, clip)), the step, the soft update.
-__global__ __launch_bounds__(THREADS) void ddpg_update_kernel(Layout L, int v0, Opt o) {
+// {max q, mean q}, summed in row order by the thread that calls it
+__device__ __forceinline__ void q_stats(const Work& w, int B) {
+  float mx = w.q[0], s = 0.f;
+  for (int r = 0; r < B; ++r) {
+    const float q = w.q[r];
+    mx = fmaxf(mx, q);
+    s += q;
+  }
+  w.qstat[0] = mx;
+  w.qstat[1] = s / (float)B;
+}
+
+// The critic's launch also leaves {max q, mean q}.
+template <bool FUSED>
+__global__ __launch_bounds__(THREADS) void ddpg_wgrad_kernel(Layout L, GradSrc src, int v0, int v1, int B, Opt o, Work w) {
+  wgrad_element<FUSED>(L, src, v0, v1, B, o);
+  if (v0 == NACTOR && blockIdx.x == 0 && threadIdx.x == 0) q_stats(w, B);
+}
+
+// The trainable variables of critic blockIdx.y: the arenas are the same, so one Opt serves both.  q_stats are critic 1's.
+template <bool FUSED>
+__global__ __launch_bounds__(THREADS) void ddpg_twin_wgrad_kernel(Pair<Layout> L, Pair<GradSrc> src, int B, Opt o, Work w) {
+  wgrad_element<FUSED>(L.v[blockIdx.y], src.v[blockIdx.y], NACTOR, NTRAIN, B, o);
+  if (blockIdx.y == 0 && blockIdx.x == 0 && threadIdx.x == 0) q_stats(w, B);
+}
+
+// The block's variable v: tf.clip_by_norm (g clip / max(||g||, clip)), the step, the soft update.
+__device__ __forceinline__ void update_variable(const Layout& L, int v, const Opt& o) {
   __shared__ float sh[RED];
-  const int v = v0 + blockIdx.x;
   const int64_t lo = L.off[v], hi = L.off[v + 1];
   const bool dead = v == C_B2DEAD;
   float s = 0.f;
@@ -485,6 +612,14 @@ __global__ __launch_bounds__(THREADS) void ddpg_update_kernel(Layout L, int v0, 
     if (!dead && o.apply) opt_step(o, i, o.grad[i] * scale);
     if (o.soft) soft_step(o, i);
   }
+}
+
+// One block per variable v0 + blockIdx.x.
+__global__ __launch_bounds__(THREADS) void ddpg_update_kernel(Layout L, int v0, Opt o) { update_variable(L, v0 + blockIdx.x, o); }
+
+// Blocks 0..9: critic 1's variables, 10..19: critic 2's.
+__global__ __launch_bounds__(THREADS) void ddpg_twin_update_kernel(Pair<Layout> L, Opt o) {
+  update_variable(L.v[blockIdx.x / NCRITIC], NACTOR + blockIdx.x % NCRITIC, o);
 }
 
 // Ring slot (first + i) mod cap <- s | a | r | done | s2, from row `s[S] | s2[S] | done` of the transport and the staged r, a.
@@ -792,6 +927,16 @@ struct DActors : ga3c_actors::ActorsCore {     // block: every device buffer of 
   bool started = false;                 // the first actor step is the environments' step(None): one flag for all of them
 };
 
+// Twin critics of a handle (ga3c_ddpg_twin_create).  The arenas hold view.off[NVARS] floats while it lives.
+struct Twin {
+  int delay = 1;                        // a policy step when (step + 1) % delay == 0
+  float sigma = 0.f, clip = 0.f;        // the target smoothing
+  uint64_t seed = 0;                    // its draw at step + 1 = t is stream t of this seed
+  Layout view;                          // twin_view(L)
+  Work2 w{};
+  float* work_base = nullptr;
+};
+
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
   ga3c_ddpg_config cfg;
   Layout L;
@@ -813,6 +958,8 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   std::vector<float> ou_x;
   Per* per = nullptr;             // null: no priorities, and every path is the one it was without them
   DActors* actors = nullptr;      // null: no device actors
+  Twin* twin = nullptr;           // null: one critic
+  std::vector<std::string> tnames;      // the target copies' names, by variable
 };
 
 namespace {
@@ -829,6 +976,32 @@ void work_table(ga3c_ddpg* m, std::vector<float**>* ptrs, std::vector<size_t>* w
   *ptrs = {&w.y, &w.qt, &w.q, &w.dq, &w.c_x, &w.c_a, &w.c_xh1, &w.c_c1, &w.c_dn1, &w.c_dh1, &w.c_c2, &w.c_dt,
            &w.a_xh1, &w.a_a1, &w.a_dn1, &w.a_dh1, &w.a_xh2, &w.a_a2, &w.a_dn2, &w.a_dh2, &w.a_out, &w.a_noisy, &w.g, &w.dout};
   *widths = {1, 1, 1, 1, S, A, H1, H1, H1, H1, H2, H2, H1, H1, H1, H1, H2, H2, H2, H2, A, A, A, A};
+}
+
+const char* const WORK2_NAMES[] = {"qt1", "qt2", "q2", "dq2", "t_eps", "t_a", "c2_xh1", "c2_c1", "c2_dn1", "c2_dh1", "c2_c2", "c2_dt"};
+constexpr int NWORK2 = sizeof(WORK2_NAMES) / sizeof(WORK2_NAMES[0]);
+
+void work2_table(ga3c_ddpg* m, std::vector<float**>* ptrs, std::vector<size_t>* widths) {
+  const size_t A = m->L.A;
+  Work2& w = m->twin->w;
+  *ptrs = {&w.qt1, &w.qt2, &w.q2, &w.dq2, &w.t_eps, &w.t_a, &w.c2_xh1, &w.c2_c1, &w.c2_dn1, &w.c2_dh1, &w.c2_c2, &w.c2_dt};
+  *widths = {1, 1, 1, 1, A, A, H1, H1, H1, H1, H2, H2};
+}
+
+// one critic's entries: critic 1's from Work, critic 2's from Work2
+void critic_grad_src(GradSrc* g, int S, int A, const float* x, const float* a, const CriticRows& c) {
+  auto set = [&](int v, const float* in, int li, const float* d, int ld, const float* mul) {
+    g->in[v] = in; g->ld_in[v] = li; g->d[v] = d; g->ld_d[v] = ld; g->mul[v] = mul;
+  };
+  set(C_W1, x, S, c.dh1, H1, nullptr);
+  set(C_B1, nullptr, 0, c.dh1, H1, nullptr);
+  set(C_BE1, nullptr, 0, c.dn1, H1, nullptr);
+  set(C_GA1, nullptr, 0, c.dn1, H1, c.xh1);
+  set(C_W2, c.c1, H1, c.dt, H2, nullptr);
+  set(C_WN, a, A, c.dt, H2, nullptr);
+  set(C_BN, nullptr, 0, c.dt, H2, nullptr);
+  set(C_WO, c.c2, H2, c.dq, 1, nullptr);
+  set(C_BO, nullptr, 0, c.dq, 1, nullptr);
 }
 
 GradSrc grad_src(ga3c_ddpg* m) {
@@ -852,15 +1025,16 @@ GradSrc grad_src(ga3c_ddpg* m) {
   set(A_GA2, nullptr, 0, w.a_dn2, H2, w.a_xh2);
   set(A_WO, w.a_a2, H2, w.dout, A, nullptr);
   set(A_BO, nullptr, 0, w.dout, A, nullptr);
-  set(C_W1, w.c_x, S, w.c_dh1, H1, nullptr);
-  set(C_B1, nullptr, 0, w.c_dh1, H1, nullptr);
-  set(C_BE1, nullptr, 0, w.c_dn1, H1, nullptr);
-  set(C_GA1, nullptr, 0, w.c_dn1, H1, w.c_xh1);
-  set(C_W2, w.c_c1, H1, w.c_dt, H2, nullptr);
-  set(C_WN, w.c_a, A, w.c_dt, H2, nullptr);
-  set(C_BN, nullptr, 0, w.c_dt, H2, nullptr);
-  set(C_WO, w.c_c2, H2, w.dq, 1, nullptr);
-  set(C_BO, nullptr, 0, w.dq, 1, nullptr);
+  critic_grad_src(&g, S, A, w.c_x, w.c_a, CriticRows{w.q, w.dq, nullptr, nullptr, w.c_xh1, w.c_c1, w.c_dn1, w.c_dh1, w.c_c2, w.c_dt});
+  return g;
+}
+
+// ... with critic 2's rows in the critic's entries (the actor's are not read through it)
+GradSrc twin_grad_src(ga3c_ddpg* m) {
+  GradSrc g = grad_src(m);
+  const Work2& w = m->twin->w;
+  critic_grad_src(&g, m->L.S, m->L.A, m->w.c_x, m->w.c_a,
+                  CriticRows{w.q2, w.dq2, nullptr, nullptr, w.c2_xh1, w.c2_c1, w.c2_dn1, w.c2_dh1, w.c2_c2, w.c2_dt});
   return g;
 }
 
@@ -900,8 +1074,41 @@ int make_noise(ga3c_ddpg* m, int mode, const float* given, Noise* nz) {
   return GA3C_OK;
 }
 
+// The twin's step: smoothed targets from the smaller of two target critics, both critics stepped on them, and
+// only when t is a multiple of the delay the actor's step, at its own Adam count, and the soft update of all three nets.
+int enqueue_twin_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w) {
+  const ga3c_ddpg_config& c = m->cfg;
+  const Twin& tw = *m->twin;
+  const int64_t t = m->step.load() + 1;
+  const bool policy = t % tw.delay == 0, full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
+  const dim3 grid(tiles(B)), grid2(tiles(B), 2), block(THREADS);
+  const Pair<Layout> L{{m->L, tw.view}};
+  hipLaunchKernelGGL(ddpg_twin_target_kernel, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma,
+                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, tw.sigma, tw.clip, tw.seed, (uint64_t)t, m->w, tw.w);
+  hipLaunchKernelGGL(ddpg_twin_critic_kernel, grid2, block, 0, m->st, L, (const float*)m->arena[0], rows, B, per_w, m->w, tw.w);
+  const GradSrc gs = grad_src(m);
+  const Pair<GradSrc> gs2{{gs, twin_grad_src(m)}};
+  const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
+  const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
+  const Opt oc = make_opt(m, false, lr, t, true, full && policy);
+  if (clip) {
+    hipLaunchKernelGGL(ddpg_twin_wgrad_kernel<false>, dim3(cblocks, 2), block, 0, m->st, L, gs2, B, oc, m->w);
+    hipLaunchKernelGGL(ddpg_twin_update_kernel, dim3(2 * NCRITIC), block, 0, m->st, L, oc);
+  } else {
+    hipLaunchKernelGGL(ddpg_twin_wgrad_kernel<true>, dim3(cblocks, 2), block, 0, m->st, L, gs2, B, oc, m->w);
+  }
+  if (stop_after >= 4 && policy) {
+    hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, m->w);
+    const Opt oa = make_opt(m, true, lr, t / tw.delay, full, full);
+    hipLaunchKernelGGL(ddpg_wgrad_kernel<true>, dim3(ablocks), block, 0, m->st, m->L, gs, 0, NACTOR, B, oa, m->w);
+  }
+  HIPCHK(hipGetLastError());
+  return GA3C_OK;
+}
+
 // Steps 1 .. stop_after of train_DDPG on `rows` (caller holds train_mu and mu).  stop_after 6: the whole step.
 int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w = nullptr) {
+  if (m->twin) return enqueue_twin_step(m, rows, B, lr, nz, stop_after, per_w);
   const ga3c_ddpg_config& c = m->cfg;
   const int64_t t = m->step.load() + 1;
   const bool full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
@@ -997,33 +1204,50 @@ int predict_end(ga3c_ddpg* m, int ticket, int B, float* a, float* v) {
 }
 
 // tflearn's name of the target copy: the layer's scope is made a second time, "actor_fc1" -> "actor_fc1_1" (the one place).
-std::string target_name(int i) {
-  const std::string s(VAR_NAMES[i]);
+std::string target_name(const std::string& s) {
   const size_t slash = s.find('/');
   return s.substr(0, slash) + "_1" + s.substr(slash);
 }
 
 // The variable table: value and target copy of every variable are checkpoint members; the 20 trainable ones also have the
 // two slots of their optimizer, under Adam's names or RMSProp's.
-void fill_vars(ga3c_ddpg* m) {
-  const Layout& L = m->L;
-  for (int i = 0; i < NVARS; ++i) {
-    const std::string name(VAR_NAMES[i]);
-    vn::Var var{name, L.off[i], L.off[i + 1] - L.off[i], 1, {L.cols[i], 0}, {}};
-    if (L.rows[i]) {                                 // a matrix [rows, cols]; a vector has rows = 0
-      var.ndim = 2;
-      var.shape[0] = L.rows[i];
-      var.shape[1] = L.cols[i];
-    }
-    var.ckpt = {{name + ":0", 0}, {target_name(i) + ":0", 1}};
-    if (i < NTRAIN) {
-      const bool adam = i < NACTOR || (m->cfg.flags & GA3C_DDPG_CRITIC_ADAM);
-      var.ckpt.emplace_back(name + (adam ? "/Adam:0" : "/RMSProp:0"), 2);
-      var.ckpt.emplace_back(name + (adam ? "/Adam_1:0" : "/RMSProp_1:0"), 3);
-    }
-    m->vars.push_back(std::move(var));
+// `name` = variable i of layout `L` (a view: the critic's entries only) at the table's end
+void add_var(ga3c_ddpg* m, const Layout& L, int i, const char* vname) {
+  const std::string name(vname);
+  vn::Var var{name, L.off[i], (int64_t)(L.rows[i] ? L.rows[i] : 1) * L.cols[i], 1, {L.cols[i], 0}, {}};
+  if (L.rows[i]) {                                 // a matrix [rows, cols]; a vector has rows = 0
+    var.ndim = 2;
+    var.shape[0] = L.rows[i];
+    var.shape[1] = L.cols[i];
   }
-  m->n = L.off[NVARS];
+  var.ckpt = {{name + ":0", 0}, {target_name(name) + ":0", 1}};
+  if (i < NTRAIN) {
+    const bool adam = i < NACTOR || (m->cfg.flags & GA3C_DDPG_CRITIC_ADAM);
+    var.ckpt.emplace_back(name + (adam ? "/Adam:0" : "/RMSProp:0"), 2);
+    var.ckpt.emplace_back(name + (adam ? "/Adam_1:0" : "/RMSProp_1:0"), 3);
+  }
+  m->vars.push_back(std::move(var));
+  m->tnames.push_back(target_name(name));
+}
+
+void fill_vars(ga3c_ddpg* m) {
+  for (int i = 0; i < NVARS; ++i) add_var(m, m->L, i, VAR_NAMES[i]);
+  m->n = m->L.off[NVARS];
+}
+
+// variable i of a twin handle's table is trainable: the 20, and critic 2's ten
+bool trainable_var(int i) { return i >= 0 && (i < NTRAIN || (i >= NVARS && i < NVARS + NCRITIC)); }
+
+void twin_free(ga3c_ddpg* m) {
+  Twin* t = m->twin;
+  if (!t) return;
+  (void)hipFree(t->work_base);
+  (void)hipGetLastError();
+  delete t;
+  m->twin = nullptr;
+  m->vars.resize(NVARS);            // the arenas keep their size: nothing names what lies behind the 26
+  m->tnames.resize(NVARS);
+  m->n = m->L.off[NVARS];
 }
 
 void per_free(ga3c_ddpg* m) {
@@ -1048,6 +1272,7 @@ void free_all(ga3c_ddpg* m) {
   }
   dactors_free(m);
   per_free(m);
+  twin_free(m);
   vn::free_core(m);
   (void)hipFree(m->work_base);
   (void)hipFree(m->ring);
@@ -1208,17 +1433,12 @@ int32_t ga3c_ddpg_num_params(ga3c_ddpg* m) { return vn::num_params(m); }
 const char* ga3c_ddpg_param_name(ga3c_ddpg* m, int32_t index) { return vn::param_name(m, index); }
 
 const char* ga3c_ddpg_target_name(ga3c_ddpg* m, int32_t index) {
-  static std::string names[NVARS];
-  static std::once_flag once;
-  std::call_once(once, [] {
-    for (int i = 0; i < NVARS; ++i) names[i] = target_name(i);
-  });
-  return (m && index >= 0 && index < NVARS) ? names[index].c_str() : nullptr;
+  return (m && index >= 0 && index < (int32_t)m->tnames.size()) ? m->tnames[index].c_str() : nullptr;
 }
 
 int ga3c_ddpg_param_info(ga3c_ddpg* m, const char* name, int64_t* count, int32_t* ndim, int64_t shape[4], int32_t* trainable) {
   CHK(vn::param_info(m, name, nullptr, count, ndim, shape));
-  if (trainable) *trainable = vn::param_index(m, name) < NTRAIN ? 1 : 0;
+  if (trainable) *trainable = trainable_var(vn::param_index(m, name)) ? 1 : 0;
   return GA3C_OK;
 }
 
@@ -1248,6 +1468,8 @@ int ga3c_ddpg_load(ga3c_ddpg* m, const char* path) {
   int64_t step = 0;
   CHK(vn::checkpoint_step(path, members, &step));
   if (step < 0) return fail(GA3C_ESTATE, "%s: step %lld", path, (long long)step);      // before anything is written
+  if (!m->twin && members.count(std::string(TWIN_VAR_NAMES[0]) + ":0"))
+    return fail(GA3C_ESTATE, "%s holds %s: the checkpoint of a handle with twin critics, which this one has not", path, TWIN_VAR_NAMES[0]);
   return vn::load(m, path, members);
 }
 
@@ -1452,6 +1674,19 @@ int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
   }
   for (int i = 0; i < NWORK; ++i)
     if (strcmp(name, WORK_NAMES[i]) == 0) return vn::fetch(m, name, *ptrs[i], (int64_t)widths[i], out, count);
+  for (int i = 0; i < NWORK2; ++i)
+    if (strcmp(name, WORK2_NAMES[i]) == 0) {          // under both locks throughout: twin_destroy frees these rows
+      HIPCHK(hipSetDevice(m->device));
+      std::lock_guard<std::mutex> tl(m->train_mu);
+      std::lock_guard<std::mutex> lk(m->mu);
+      if (!m->twin) return fail(GA3C_ESTATE, "%s: the handle has no twin critics (ga3c_ddpg_twin_create)", name);
+      work2_table(m, &ptrs, &widths);
+      const int64_t want = (int64_t)widths[i] * m->last_B;
+      if (count != want) return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)want, (long long)count);
+      HIPCHK(hipStreamSynchronize(m->st));
+      HIPCHK(hipMemcpy(out, *ptrs[i], sizeof(float) * count, hipMemcpyDeviceToHost));
+      return GA3C_OK;
+    }
   return fail(GA3C_EINVAL, "no buffer named %s", name);
 }
 
@@ -1647,6 +1882,82 @@ int ga3c_ddpg_time_prioritized(ga3c_ddpg* m, int32_t batch, int32_t iters, float
   }
   HIPCHK(hipEventSynchronize(m->t1));
   HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
+  return GA3C_OK;
+}
+
+// ---- twin critics
+
+int ga3c_ddpg_twin_create(ga3c_ddpg* m, int32_t policy_delay, float target_sigma, float target_clip, int64_t seed) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (policy_delay < 1 || policy_delay > 16) return fail(GA3C_EINVAL, "policy_delay %d outside [1,16]", policy_delay);
+  if (!(target_sigma >= 0.f) || std::isinf(target_sigma)) return fail(GA3C_EINVAL, "target_sigma %g: a finite number >= 0", target_sigma);
+  if (!(target_clip >= 0.f) || std::isinf(target_clip)) return fail(GA3C_EINVAL, "target_clip %g: a finite number >= 0", target_clip);
+  if (!(m->cfg.flags & GA3C_DDPG_LOSS_PAIRED))
+    return fail(GA3C_ESTATE, "twin critics need GA3C_DDPG_LOSS_PAIRED: under the fork's loss the critics regress on mean(y) and a "
+                             "row has no target of its own");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (m->twin) return fail(GA3C_ESTATE, "the handle has twin critics already");
+  Twin* t = new (std::nothrow) Twin();
+  if (!t) return fail(GA3C_EINVAL, "out of host memory");
+  t->delay = policy_delay;
+  t->sigma = target_sigma;
+  t->clip = target_clip;
+  t->seed = (uint64_t)seed;
+  t->view = twin_view(m->L);
+  const Layout& V = t->view;
+  const int64_t n0 = m->L.off[NVARS], n1 = V.off[NVARS];
+  // Every arena grows by critic 2's variables, which start as ga3c_ddpg_create leaves the others: zero, the variance and the
+  // RMSProp ms slot one.  The 26 keep their values; a prediction in flight has finished before its arena is freed.
+  float* grown[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  m->twin = t;
+  auto build = [&]() -> int {
+    HIPCHK(hipStreamSynchronize(m->st));
+    std::vector<float> init((size_t)(n1 - n0));
+    for (int a = 0; a < m->narena; ++a) {
+      CHK(vn::dalloc(&grown[a], (size_t)n1));
+      HIPCHK(hipMemcpy(grown[a], m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToDevice));
+      std::fill(init.begin(), init.end(), 0.f);
+      if (a <= 1)
+        for (int64_t i = V.off[C_MV1]; i < V.off[NVARS]; ++i) init[(size_t)(i - n0)] = 1.f;
+      if (a == 2 && !(m->cfg.flags & GA3C_DDPG_CRITIC_ADAM))
+        for (int64_t i = V.off[NACTOR]; i < V.off[NTRAIN]; ++i) init[(size_t)(i - n0)] = 1.f;
+      HIPCHK(hipMemcpy(grown[a] + n0, init.data(), sizeof(float) * (n1 - n0), hipMemcpyHostToDevice));
+    }
+    std::vector<float**> ptrs;
+    std::vector<size_t> widths;
+    float* end = nullptr;
+    work2_table(m, &ptrs, &widths);
+    CHK(vn::carve_rows((size_t)m->cfg.max_batch, widths, ptrs, &t->work_base, &end));
+    return GA3C_OK;
+  };
+  const int rc = build();
+  if (rc != GA3C_OK) {
+    for (float* g : grown) (void)hipFree(g);
+    (void)hipGetLastError();
+    twin_free(m);
+    return rc;
+  }
+  for (int a = 0; a < m->narena; ++a) {
+    (void)hipFree(m->arena[a]);
+    m->arena[a] = grown[a];
+  }
+  for (int i = 0; i < NCRITIC; ++i) add_var(m, V, NACTOR + i, TWIN_VAR_NAMES[i]);
+  add_var(m, V, C_MM1, TWIN_VAR_NAMES[NCRITIC]);
+  add_var(m, V, C_MV1, TWIN_VAR_NAMES[NCRITIC + 1]);
+  m->n = n1;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_twin_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!m->twin) return fail(GA3C_ESTATE, "the handle has no twin critics (ga3c_ddpg_twin_create)");
+  HIPCHK(hipStreamSynchronize(m->st));
+  twin_free(m);
   return GA3C_OK;
 }
 

@@ -681,6 +681,31 @@ int ga3c_ddpg_train_prioritized(ga3c_ddpg* net, int32_t batch, float beta_is, fl
 int ga3c_ddpg_time_prioritized(ga3c_ddpg* net, int32_t batch, int32_t iters, float beta_is, float learning_rate,
                                float* elapsed_ms);
 
+/* ---- Twin critics of a DDPG handle (Config.DDPG_TWIN; tests/td3_oracle.py is the same statement in numpy):
+ * clipped double-Q with target policy smoothing and a delayed policy update (Fujimoto et al. 2018).  A handle without them runs
+ * what it ran before.  With them every train-type call (train, train_replay, train_prioritized, compute, time_resident,
+ * time_prioritized, actors_run) runs, with t = step + 1:
+ *   a~ = clip(actor_target(s2) + eps, -1, 1), eps[k][i] = (f32) clip(sigma n, -c, c) for row k of the batch and action i, n
+ *   Box-Muller in f64 on the device actors' counter uniforms: u1 = 1 - u(seed, t, 2j), u2 = u(seed, t, 2j + 1), j = k A + i,
+ *   n = sqrt(-2 ln u1) cos(2 pi u2).  The stream is t: no state, a resumed run draws what the uninterrupted one would.
+ *   q' = min(critic_target(s2, a~), critic2_target(s2, a~)), y from it as before.
+ *   Both critics step on the same y in the paired form, each with its own optimizer slots and its own clip_by_norm.
+ *   Only when t % policy_delay == 0: steps 4-5 against the updated critic 1, the actor's Adam at count t / policy_delay, and
+ *   the soft update of all three nets.  On other steps no target and no actor slot changes, and compute's stop_after = 4 does
+ *   what 3 does.  The handle's noise process advances once per train-type call either way.
+ * 3 launches (4 with GA3C_DDPG_GRAD_CLIP), 5 (6) on a policy step; prioritised steps add their three.
+ * The handle then has 38 variables: the 26, then critic2_fc1/W .. critic2_output/b in the critic's order and
+ * critic2_norm1/moving_mean, /moving_variance, starting as ga3c_ddpg_create leaves the others; every `which` serves them, and a
+ * checkpoint holds their members too.  A twin handle loads only a twin handle's file and a plain handle refuses one
+ * (GA3C_ESTATE, handle untouched).  fetch also knows "qt1", "qt2" [B] (the two target critics; "qt" is their min), "t_eps",
+ * "t_a" [B,A], "q2", "dq2" [B] and "c2_xh1" .. "c2_dt" as critic 1's "c_*"; GA3C_ESTATE without the twin.  "q", q_stats and
+ * "per_td" stay critic 1's.
+ * create: GA3C_EINVAL for policy_delay outside [1,16], a negative or NaN target_sigma / target_clip; GA3C_ESTATE on a second
+ * create and on a handle without GA3C_DDPG_LOSS_PAIRED (under the fork's loss a row has no target of its own).
+ * destroy: also done by ga3c_ddpg_destroy; the handle has its 26 variables again. */
+int ga3c_ddpg_twin_create(ga3c_ddpg* net, int32_t policy_delay, float target_sigma, float target_clip, int64_t seed);
+int ga3c_ddpg_twin_destroy(ga3c_ddpg* net);
+
 /* ---- Device actors of a DDPG handle (Config.DEVICE_DDPG; tests/ddpg_actors_oracle.py is the same statement in
  * numpy): n Pendulum-v0 environments in HBM write their transitions into the handle's replay ring and the handle trains on rows
  * it draws from the ring itself, all on its one stream.  Attached to a created handle, as the priorities are.
