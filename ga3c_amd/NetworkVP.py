@@ -11,7 +11,6 @@ NetworkVP_discrate.py:58-85 heads/loss).  Every numeric step runs in the HIP lib
 marshals numpy buffers.  If the library is missing or no gfx950 device is present it raises.
 """
 import ctypes as C
-import glob
 import os
 import re
 import threading
@@ -19,6 +18,7 @@ import threading
 import numpy as np
 
 from Config import Config
+from NativeHandle import ParamHandle
 import _native as nat
 
 PARAM_ORDER = ("conv11/w", "conv11/b", "conv12/w", "conv12/b", "dense1/w", "dense1/b",
@@ -95,7 +95,10 @@ def _device_ordinal(device):
     return int(m.group(1)) if m else 0
 
 
-class Network:
+class Network(ParamHandle):
+    """The arenas, the variables by name, the step, fetch and the checkpoints are ParamHandle's (NativeHandle.py)."""
+    PREFIX = "ga3c_net"
+
     def __init__(self, device, model_name, num_actions, state_dim, max_batch=None, predict_lanes=None, train_lanes=None):
         self.device = device
         self.model_name = model_name
@@ -163,58 +166,10 @@ class Network:
         return arr
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ga3c_net_destroy(self._h)
-            self._h = None
-            for p in self._pinned:
-                nat.free_pinned(p)
-            self._pinned = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # ---- arenas -----------------------------------------------------------------------------
-    # which: 0 weights, 1 / 2 RMSProp `ms` / `mom`, 3 last gradient.  With Config.DUAL_RMSPROP, 1 / 2 / 3 belong to cost_p's
-    # optimizer and 4 / 5 / 6 are cost_v's `ms` / `mom` / last gradient (include/ga3c_abi.h)
-    def get_arena(self, which):
-        out = np.empty(self.param_count, dtype=np.float32)
-        nat.check(self._lib.ga3c_net_get_arena(self._h, which, nat.ptr(out), out.size), "ga3c_net_get_arena")
-        return out
-
-    def set_arena(self, which, flat):
-        flat = nat.as_f32(flat).ravel()
-        nat.check(self._lib.ga3c_net_set_arena(self._h, which, nat.ptr(flat), flat.size), "ga3c_net_set_arena")
-
-    def get_global_step(self):
-        s = C.c_int64()
-        nat.check(self._lib.ga3c_net_get_step(self._h, C.byref(s)))
-        return s.value
-
-    def get_variables_names(self):
-        """NetworkVP.py:284-285; the names come out of the library's own table (ga3c_net_param_name)."""
-        n = self._lib.ga3c_net_num_params(self._h)
-        return [self._lib.ga3c_net_param_name(self._h, i).decode() + ":0" for i in range(n)]
-
-    def _param_info(self, name):
-        off, count, ndim = C.c_int64(), C.c_int64(), C.c_int32()
-        shape = (C.c_int64 * 4)()
-        nat.check(self._lib.ga3c_net_param_info(self._h, name.encode(), C.byref(off), C.byref(count), C.byref(ndim), shape),
-                  "ga3c_net_param_info")
-        return off.value, count.value, tuple(shape[d] for d in range(ndim.value))
-
-    def get_variable_value(self, name, which=0):
-        """NetworkVP.py:287-288 (which = 1 / 2: the variable's RMSProp slots, 3: its last gradient)."""
-        _, count, shape = self._param_info(name)
-        out = np.empty(count, dtype=np.float32)
-        nat.check(self._lib.ga3c_net_get_param(self._h, name.encode(), which, nat.ptr(out), count), "ga3c_net_get_param")
-        return out.reshape(shape)
-
-    def set_variable_value(self, name, value, which=0):
-        flat = nat.as_f32(value).ravel()
-        nat.check(self._lib.ga3c_net_set_param(self._h, name.encode(), which, nat.ptr(flat), flat.size), "ga3c_net_set_param")
+        super().close()
+        for p in getattr(self, "_pinned", ()):
+            nat.free_pinned(p)
+        self._pinned = []
 
     # ---- inference ---------------------------------------------------------------------------
     def _predict(self, x, want_z=False):
@@ -252,13 +207,8 @@ class Network:
     # ---- zero-copy intake from the shared-memory transport --------------------------------------
     def register_transport(self, transport):
         """Pin the transport's segment for the GPU; afterwards predict_slots / train_rows gather from it."""
-        nat.check(self._lib.ga3c_net_register_host(self._h, C.c_void_p(transport.base), transport.nbytes),
-                  "ga3c_net_register_host")
+        super().register_transport(transport)
         self._transport_u8 = transport.state_bytes == nat.STATE_FLOATS
-
-    def unregister_transport(self):
-        """Unpin the segment (call before the transport is unmapped)."""
-        nat.check(self._lib.ga3c_net_unregister_host(self._h), "ga3c_net_unregister_host")
 
     # ---- frame front-end on the device (Environment.py:52-74; include/ga3c_abi.h: ga3c_net_frames_*) ------------
     def frames_config(self, max_agents, height=210, width=160, channels=3, history=0):
@@ -388,12 +338,11 @@ class Network:
     def gather_entry(self):
         """(address of ga3c_net_predict_gather, engine handle, u8 flag): what the native predictor loop
         (ga3c_pq_serve, include/ga3c_host.h) calls for every batch instead of predict_offsets()."""
-        return C.cast(self._lib.ga3c_net_predict_gather, C.c_void_p).value, self._h, int(self._transport_u8)
+        return super().gather_entry()[:2] + (int(self._transport_u8),)
 
     def gather_entries_pipelined(self):
         """(addresses of ga3c_net_predict_gather_begin / _end, engine handle, u8 flag) for ga3c_pq_serve_pipelined."""
-        return (C.cast(self._lib.ga3c_net_predict_gather_begin, C.c_void_p).value,
-                C.cast(self._lib.ga3c_net_predict_gather_end, C.c_void_p).value, self._h, int(self._transport_u8))
+        return super().gather_entries_pipelined()[:3] + (int(self._transport_u8),)
 
     def state_cache_config(self, max_agents, depth):
         """Keep the uint8 states the pipelined predictor loop reads, `depth` per agent (ga3c_net_state_cache_config): rows of
@@ -454,11 +403,6 @@ class Network:
 
     def apply_grads(self):
         nat.check(self._lib.ga3c_net_apply_grads(self._h, float(self.learning_rate)), "ga3c_net_apply_grads")
-
-    def fetch(self, name, count):
-        out = np.empty(int(count), dtype=np.float32)
-        nat.check(self._lib.ga3c_net_fetch(self._h, name.encode(), nat.ptr(out), out.size), "ga3c_net_fetch")
-        return out
 
     # ---- data-parallel ------------------------------------------------------------------------
     @staticmethod
@@ -550,27 +494,3 @@ class Network:
             np.savez(tmp, **out)
             os.replace(tmp, "logs/%s/histograms_%08d.npz" % (self.model_name, training_step))
         return losses
-
-    def _checkpoint_filename(self, episode):
-        return 'checkpoints/%s_%08d' % (self.model_name, episode)
-
-    def _get_episode_from_filename(self, filename):
-        return int(re.split(r'/|_|\.', filename)[2])
-
-    def save(self, episode):
-        """Own on-disk format (.npz keyed by the TF variable names + RMSProp slots + step):
-        a TF checkpoint cannot be written without TF."""
-        os.makedirs("checkpoints", exist_ok=True)
-        # written by the library itself (ga3c_net_save: an uncompressed .npz, written under a temporary name and renamed)
-        nat.check(self._lib.ga3c_net_save(self._h, (self._checkpoint_filename(episode) + ".npz").encode()), "ga3c_net_save")
-
-    def load(self):
-        if Config.LOAD_EPISODE > 0:
-            filename = self._checkpoint_filename(Config.LOAD_EPISODE) + ".npz"
-        else:
-            found = sorted(glob.glob('checkpoints/%s_????????.npz' % self.model_name))
-            if not found:
-                raise FileNotFoundError("no checkpoint for %s" % self.model_name)
-            filename = found[-1]
-        nat.check(self._lib.ga3c_net_load(self._h, filename.encode()), "ga3c_net_load")
-        return self._get_episode_from_filename(filename[:-4])

@@ -1,7 +1,7 @@
 """What the vector-state networks share on the Python side (NetworkVP_vector.Network, NetworkVP_discrate.Network): the
 handle of libga3c_hip.so behind them has one host implementation (csrc/ga3c_vecnet.hpp) and one entry
-list under two prefixes, so every call but create and evaluate is made here.  NativeHandle is the part of it that
-NetworkDDPG.Network shares as well, as its handle shares the core layer of that header.
+list under two prefixes, so every call but create and evaluate is made here or in NativeHandle.py, whose classes hold the
+part that the image network (ParamHandle) and NetworkDDPG.Network (NativeHandle) share as well.
 
 Same interface as NetworkVP.Network where Server, ThreadPredictor and ThreadTrainer use it (predict_p_and_v, train, log,
 save, load, get_global_step, get_variables_names, get_variable_value, and the zero-copy entries).  There is no frame
@@ -13,99 +13,18 @@ step their own environments (Config.DEVICE_AGENTS), NetworkDDPG.Network among th
 <PREFIX>_actors_*.
 """
 import ctypes as C
-import glob
 import os
-import re
 import threading
 
 import numpy as np
 
 from Config import Config
+from NativeHandle import NativeHandle, ParamHandle  # noqa: F401  (NativeHandle: NetworkDDPG imports it from here)
 from NetworkVP import _device_ordinal, histogram_proto
 import _native as nat
 
 
-class NativeHandle:
-    """A handle of the host half that the vector-state networks and DDPG share (Core of csrc/ga3c_vecnet.hpp) behind the
-    entries <PREFIX>_*: what their Python classes do word for word alike.  A subclass states PREFIX and sets _lib, _h, S and
-    model_name."""
-    PREFIX = None                 # the entries are <PREFIX>_create, <PREFIX>_train, ...
-
-    def _fn(self, entry):
-        return getattr(self._lib, "%s_%s" % (self.PREFIX, entry))
-
-    def _call(self, entry, *args):
-        """<PREFIX>_<entry>(handle, *args), checked."""
-        return nat.check(self._fn(entry)(self._h, *args), "%s_%s" % (self.PREFIX, entry))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._fn("destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _rows(self, x):
-        x = nat.as_f32(x).reshape(-1, self.S)
-        return x, int(x.shape[0])
-
-    def get_global_step(self):
-        s = C.c_int64()
-        nat.check(self._fn("get_step")(self._h, C.byref(s)))
-        return s.value
-
-    def get_variables_names(self):
-        n = self._fn("num_params")(self._h)
-        return [self._fn("param_name")(self._h, i).decode() + ":0" for i in range(n)]
-
-    # ---- zero-copy intake from the shared-memory transport (rows of 4 S bytes) -------------------
-    def register_transport(self, transport):
-        self._call("register_host", C.c_void_p(transport.base), transport.nbytes)
-
-    def unregister_transport(self):
-        self._call("unregister_host")
-
-    def gather_entry(self):
-        """(address of <PREFIX>_predict_gather, handle, u8 = 0) for the native predictor loop (ga3c_pq_serve)."""
-        return C.cast(self._fn("predict_gather"), C.c_void_p).value, self._h, 0
-
-    def gather_entries_pipelined(self):
-        """(addresses of <PREFIX>_predict_gather_begin / _end, handle, u8 = 0) for ga3c_pq_serve_pipelined."""
-        return (C.cast(self._fn("predict_gather_begin"), C.c_void_p).value,
-                C.cast(self._fn("predict_gather_end"), C.c_void_p).value, self._h, 0)
-
-    def fetch(self, name, count):
-        out = np.empty(int(count), np.float32)
-        self._call("fetch", name.encode(), nat.ptr(out), out.size)
-        return out
-
-    def _checkpoint_filename(self, episode):
-        return 'checkpoints/%s_%08d' % (self.model_name, episode)
-
-    def save(self, episode):
-        os.makedirs("checkpoints", exist_ok=True)
-        self._call("save", (self._checkpoint_filename(episode) + ".npz").encode())
-
-    def load_file(self, filename):
-        self._call("load", filename.encode())
-
-    def load(self):
-        if Config.LOAD_EPISODE > 0:
-            filename = self._checkpoint_filename(Config.LOAD_EPISODE) + ".npz"
-        else:
-            found = sorted(glob.glob('checkpoints/%s_????????.npz' % self.model_name))
-            if not found:
-                raise FileNotFoundError("no checkpoint for %s" % self.model_name)
-            filename = found[-1]
-        self.load_file(filename)
-        return int(re.split(r'/|_|\.', filename[:-4])[2])
-
-
-class VectorNetwork(NativeHandle):
+class VectorNetwork(ParamHandle):
     LOGITS_PER_ACTION = None
     ACTIVATION_WIDTHS = ()        # the activation outputs of <PREFIX>_evaluate, and the tags log() gives them
     ACTIVATION_TAGS = ()
@@ -163,33 +82,6 @@ class VectorNetwork(NativeHandle):
         self.set_arena(0, theta)
         self._log_lock = threading.Lock()
         self.last_losses = None
-
-    # ---- arenas: 0 weights, 1 / 2 RMSProp `ms` / `mom`, 3 last gradient; with Config.DUAL_RMSPROP (where the network takes
-    # it) these are cost_p's optimizer and 4 / 5 / 6 the value optimizer's `ms` / `mom` and the last cost_v gradient ------
-    def get_arena(self, which):
-        out = np.empty(self.param_count, dtype=np.float32)
-        self._call("get_arena", which, nat.ptr(out), out.size)
-        return out
-
-    def set_arena(self, which, flat):
-        flat = nat.as_f32(flat).ravel()
-        self._call("set_arena", which, nat.ptr(flat), flat.size)
-
-    def _param_info(self, name):
-        off, count, ndim = C.c_int64(), C.c_int64(), C.c_int32()
-        shape = (C.c_int64 * 4)()
-        self._call("param_info", name.encode(), C.byref(off), C.byref(count), C.byref(ndim), shape)
-        return off.value, count.value, tuple(shape[d] for d in range(ndim.value))
-
-    def get_variable_value(self, name, which=0):
-        _, count, shape = self._param_info(name)
-        out = np.empty(count, dtype=np.float32)
-        self._call("get_param", name.encode(), which, nat.ptr(out), count)
-        return out.reshape(shape)
-
-    def set_variable_value(self, name, value, which=0):
-        flat = nat.as_f32(value).ravel()
-        self._call("set_param", name.encode(), which, nat.ptr(flat), flat.size)
 
     # ---- inference ---------------------------------------------------------------------------
     def predict_p_v_logits(self, x):

@@ -1438,7 +1438,7 @@ const char* ga3c_ddpg_target_name(ga3c_ddpg* m, int32_t index) {
 
 int ga3c_ddpg_param_info(ga3c_ddpg* m, const char* name, int64_t* count, int32_t* ndim, int64_t shape[4], int32_t* trainable) {
   CHK(vn::param_info(m, name, nullptr, count, ndim, shape));
-  if (trainable) *trainable = trainable_var(vn::param_index(m, name)) ? 1 : 0;
+  if (trainable) *trainable = trainable_var(ga3c_ckpt::find_var(m->vars, name)) ? 1 : 0;
   return GA3C_OK;
 }
 

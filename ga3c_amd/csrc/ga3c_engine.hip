@@ -30,7 +30,7 @@
 
 #include "../../include/ga3c_abi.h"
 #include "ga3c_kernels.hpp"
-#include "ga3c_checkpoint.hpp"
+#include "ga3c_vartable.hpp"
 #include "ga3c_frontend.hpp"
 #include "ga3c_resample.hpp"
 
@@ -329,6 +329,7 @@ struct ga3c_net {
   // logits_p/out_x/{w,b}, logits_p/out_y/{w,b} instead of logits_p/{w,b}, and z / dz are B x npc = B x 2A ([hx | hy])
   bool cont = false;
   int npc = 0;                         // policy-head columns per row: A, or 2A under `cont`
+  std::vector<ga3c_ckpt::Var> vars;    // the variables by name, arena order, with their checkpoint members (fill_vars)
   hipEvent_t theta_ready[NBUF] = {nullptr, nullptr, nullptr};   // recorded on the train stream behind the step that wrote theta[i]
   std::mutex ready_mu;
   std::shared_mutex wmu;   // shared: a forward pass picking/reading theta[cur]; unique: the optimizer flip
@@ -1528,6 +1529,38 @@ void stop_lane_drivers(ga3c_net* net) {
   d.th.clear();
 }
 
+// ---- the variables by name (TensorFlow variable names, NetworkDNav.py:81-90, NetworkVP_discrate.py:60,63; the continuous
+// network's policy head in TF creation order, NetworkVP.py:175-204), with the checkpoint members of each
+void fill_vars(ga3c_net* net) {
+  const int64_t A = net->A, bx = OFF_WP + HID * A;
+  auto add = [net](const char* name, int64_t off, int ndim, int64_t s0, int64_t s1 = 0, int64_t s2 = 0, int64_t s3 = 0) {
+    int64_t count = s0;
+    for (int64_t d : {s1, s2, s3}) count *= d ? d : 1;
+    net->vars.push_back(ga3c_ckpt::Var{name, off, count, ndim, {s0, s1, s2, s3}, {}});
+  };
+  add("conv11/w", OFF_W1, 4, 8, 8, 4, 16);
+  add("conv11/b", OFF_B1, 1, 16);
+  add("conv12/w", OFF_W2, 4, 4, 4, 16, 32);
+  add("conv12/b", OFF_B2, 1, 32);
+  add("dense1/w", OFF_WD, 2, FLAT, HID);
+  add("dense1/b", OFF_BD, 1, HID);
+  add("logits_v/w", OFF_WV, 2, HID, 1);
+  add("logits_v/b", OFF_BV, 1, 1);
+  if (net->cont) {
+    add("logits_p/out_x/w", OFF_WP, 2, HID, A);
+    add("logits_p/out_x/b", bx, 1, A);
+    add("logits_p/out_y/w", bx + A, 2, HID, A);
+    add("logits_p/out_y/b", bx + A + HID * A, 1, A);
+  } else {
+    add("logits_p/w", OFF_WP, 2, HID, A);
+    add("logits_p/b", off_bp(net->A), 1, A);
+  }
+  for (size_t i = 0; i < net->vars.size(); ++i) {      // the trunk: six variables; logits_v/*: two; then the policy head
+    if (net->dual) ga3c_ckpt::dual_members(&net->vars[i], i < 8, i < 6 || i >= 8);
+    else ga3c_ckpt::single_members(&net->vars[i]);
+  }
+}
+
 }  // namespace
 
 // The vector-state network (ga3c_mlp.hip) is linked into this library and reports its errors through the same message.
@@ -1644,6 +1677,7 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
   }
   net->tt2.off[20] = 2 * net->n;
   net->dual = (cfg->flags & GA3C_FLAG_DUAL_RMSPROP) != 0;
+  fill_vars(net);
 #define TRY(expr)                    \
   do {                               \
     int _r = (expr);                 \
@@ -1797,33 +1831,22 @@ static float* arena_ptr(ga3c_net* net, int which) {
   }
 }
 
-int ga3c_net_get_arena(ga3c_net* net, int32_t which, float* out, int64_t count) {
-  if (!net || !out) return fail(GA3C_EINVAL, "null argument");
-  if (count != net->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)net->n);
-  HIPCHK(hipSetDevice(net->cfg.device));
-  std::lock_guard<std::mutex> tl(net->tr.mu);
-  std::vector<std::unique_lock<std::mutex>> xl;   // Hogwild: no train lane may be mid-step while the arena is copied
-  for (TrainLane* t : net->xtr) xl.emplace_back(t->mu);
-  std::unique_lock<std::shared_mutex> lk(net->wmu);
-  CHK(sync_all(net));
-  float* src = arena_ptr(net, which);
-  if (!src) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, net->dual ? 6 : 3);
-  HIPCHK(hipMemcpy(out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-  return GA3C_OK;
-}
-
-int ga3c_net_set_arena(ga3c_net* net, int32_t which, const float* in, int64_t count) {
-  if (!net || !in) return fail(GA3C_EINVAL, "null argument");
-  if (count != net->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)net->n);
+// Elements [off, off + count) of arena `which` (a selector its caller has checked) to `out`, or from `in`, with nothing in
+// flight.  Hogwild: no train lane may be mid-step while the arena is copied.  The packed copies of dense1/w and the conv
+// filters follow the weights.
+static int arena_copy(ga3c_net* net, int which, int64_t off, int64_t count, float* out, const float* in) {
   HIPCHK(hipSetDevice(net->cfg.device));
   std::lock_guard<std::mutex> tl(net->tr.mu);
   std::vector<std::unique_lock<std::mutex>> xl;
   for (TrainLane* t : net->xtr) xl.emplace_back(t->mu);
   std::unique_lock<std::shared_mutex> lk(net->wmu);
   CHK(sync_all(net));
-  float* dst = arena_ptr(net, which);
-  if (!dst) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, net->dual ? 6 : 3);
-  HIPCHK(hipMemcpy(dst, in, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
+  float* arena = arena_ptr(net, which) + off;
+  if (out) {
+    HIPCHK(hipMemcpy(out, arena, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    return GA3C_OK;
+  }
+  HIPCHK(hipMemcpy(arena, in, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
   if (which == 0) {
     hipLaunchKernelGGL(pack_wd_kernel, dim3(KSTEPS_DENSE), dim3(256), 0, net->tr.st, net->theta[net->latest] + OFF_WD,
                        net->theta_pk[net->latest]);
@@ -1834,87 +1857,53 @@ int ga3c_net_set_arena(ga3c_net* net, int32_t which, const float* in, int64_t co
   return GA3C_OK;
 }
 
-// ---- the variables by name (TensorFlow variable names, NetworkDNav.py:81-90, NetworkVP_discrate.py:60,63)
-namespace {
-constexpr int NPARAMS = 10;
-const char* const PARAM_NAMES[NPARAMS] = {"conv11/w", "conv11/b", "conv12/w", "conv12/b", "dense1/w", "dense1/b",
-                                          "logits_v/w", "logits_v/b", "logits_p/w", "logits_p/b"};
-// the continuous network (GA3C_FLAG_CONTINUOUS): the policy head's variables in TF creation order (NetworkVP.py:175-204)
-constexpr int NPARAMS_C = 12;
-const char* const PARAM_NAMES_C[NPARAMS_C] = {"conv11/w", "conv11/b", "conv12/w", "conv12/b", "dense1/w", "dense1/b",
-                                              "logits_v/w", "logits_v/b", "logits_p/out_x/w", "logits_p/out_x/b",
-                                              "logits_p/out_y/w", "logits_p/out_y/b"};
-int nparams(const ga3c_net* net) { return net->cont ? NPARAMS_C : NPARAMS; }
-const char* param_name(const ga3c_net* net, int i) { return net->cont ? PARAM_NAMES_C[i] : PARAM_NAMES[i]; }
-struct ParamInfo { int64_t off, count; int ndim; int64_t shape[4]; };
-bool param_lookup(ga3c_net* net, const char* name, ParamInfo* pi) {
-  const int A = net->A;
-  const int64_t bx = OFF_WP + (int64_t)HID * A;
-  const int64_t offs[NPARAMS_C + 1] = {OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WD, OFF_BD, OFF_WV, OFF_BV, OFF_WP,
-                                       net->cont ? bx : off_bp(A), net->cont ? bx + A : net->n,
-                                       bx + A + (int64_t)HID * A, net->n};
-  const int64_t shapes[NPARAMS_C][4] = {{8, 8, 4, 16}, {16, 0, 0, 0}, {4, 4, 16, 32}, {32, 0, 0, 0}, {FLAT, HID, 0, 0}, {HID, 0, 0, 0},
-                                        {HID, 1, 0, 0}, {1, 0, 0, 0}, {HID, A, 0, 0}, {A, 0, 0, 0}, {HID, A, 0, 0}, {A, 0, 0, 0}};
-  const int ndims[NPARAMS_C] = {4, 1, 4, 1, 2, 1, 2, 1, 2, 1, 2, 1};
-  std::string key(name ? name : "");
-  if (key.size() > 2 && key.compare(key.size() - 2, 2, ":0") == 0) key.resize(key.size() - 2);
-  for (int i = 0; i < nparams(net); ++i)
-    if (key == param_name(net, i)) {
-      pi->off = offs[i]; pi->count = offs[i + 1] - offs[i]; pi->ndim = ndims[i];
-      for (int d = 0; d < 4; ++d) pi->shape[d] = shapes[i][d];
-      return true;
-    }
-  return false;
+static int whole_arena(ga3c_net* net, int which, int64_t count) {
+  if (count != net->n) return fail(GA3C_EINVAL, "count %lld != arena size %lld", (long long)count, (long long)net->n);
+  if (which < 0 || which > (net->dual ? 6 : 3)) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, net->dual ? 6 : 3);
+  return GA3C_OK;
 }
-}  // namespace
 
-int32_t ga3c_net_num_params(ga3c_net* net) { return net ? nparams(net) : 0; }
+int ga3c_net_get_arena(ga3c_net* net, int32_t which, float* out, int64_t count) {
+  if (!net || !out) return fail(GA3C_EINVAL, "null argument");
+  CHK(whole_arena(net, which, count));
+  return arena_copy(net, which, 0, count, out, nullptr);
+}
+
+int ga3c_net_set_arena(ga3c_net* net, int32_t which, const float* in, int64_t count) {
+  if (!net || !in) return fail(GA3C_EINVAL, "null argument");
+  CHK(whole_arena(net, which, count));
+  return arena_copy(net, which, 0, count, nullptr, in);
+}
+
+int32_t ga3c_net_num_params(ga3c_net* net) { return net ? (int32_t)net->vars.size() : 0; }
 
 const char* ga3c_net_param_name(ga3c_net* net, int32_t index) {
-  return (net && index >= 0 && index < nparams(net)) ? param_name(net, index) : nullptr;
+  return (net && index >= 0 && index < (int32_t)net->vars.size()) ? net->vars[index].name.c_str() : nullptr;
 }
 
 int ga3c_net_param_info(ga3c_net* net, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]) {
   if (!net || !name) return fail(GA3C_EINVAL, "null argument");
-  ParamInfo pi;
-  if (!param_lookup(net, name, &pi)) return fail(GA3C_EINVAL, "no variable named %s", name);
-  if (offset) *offset = pi.off;
-  if (count) *count = pi.count;
-  if (ndim) *ndim = pi.ndim;
-  if (shape) for (int d = 0; d < 4; ++d) shape[d] = pi.shape[d];
+  const int i = ga3c_ckpt::find_var(net->vars, name);
+  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
+  const ga3c_ckpt::Var& var = net->vars[i];
+  if (offset) *offset = var.off;
+  if (count) *count = var.count;
+  if (ndim) *ndim = var.ndim;
+  if (shape) memcpy(shape, var.shape, sizeof var.shape);
   return GA3C_OK;
 }
 
-// one variable's slice of an arena, under the locks ga3c_net_get_arena / set_arena take (nothing in flight meanwhile)
+// one variable's slice of an arena.  set: weights and optimizer slots only (0..2, and 4..5 under DUAL_RMSPROP); get: any arena
 static int param_copy(ga3c_net* net, const char* name, int which, float* out, const float* in, int64_t count) {
   if (!net || !name || (!out && !in)) return fail(GA3C_EINVAL, "null argument");
-  ParamInfo pi;
-  if (!param_lookup(net, name, &pi)) return fail(GA3C_EINVAL, "no variable named %s", name);
-  if (count != pi.count) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)pi.count, (long long)count);
-  // set: weights and optimizer slots only (0..2, and 4..5 under DUAL_RMSPROP); get: any arena
+  const int i = ga3c_ckpt::find_var(net->vars, name);
+  if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
+  const ga3c_ckpt::Var& var = net->vars[i];
+  if (count != var.count) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)var.count, (long long)count);
   const bool slot_v = net->dual && (which == 4 || which == 5 || (!in && which == 6));
   if (!slot_v && (which < 0 || which > (in ? 2 : 3)))
     return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]%s", which, in ? 2 : 3, net->dual ? (in ? " or [4,5]" : " or [4,6]") : "");
-  HIPCHK(hipSetDevice(net->cfg.device));
-  std::lock_guard<std::mutex> tl(net->tr.mu);
-  std::vector<std::unique_lock<std::mutex>> xl;
-  for (TrainLane* t : net->xtr) xl.emplace_back(t->mu);
-  std::unique_lock<std::shared_mutex> lk(net->wmu);
-  CHK(sync_all(net));
-  float* arena = arena_ptr(net, which);
-  if (out) {
-    HIPCHK(hipMemcpy(out, arena + pi.off, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-    return GA3C_OK;
-  }
-  HIPCHK(hipMemcpy(arena + pi.off, in, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
-  if (which == 0) {                      // the packed copies of dense1/w and the conv filters follow the weights
-    hipLaunchKernelGGL(pack_wd_kernel, dim3(KSTEPS_DENSE), dim3(256), 0, net->tr.st, net->theta[net->latest] + OFF_WD,
-                       net->theta_pk[net->latest]);
-    hipLaunchKernelGGL(pack_conv_kernel, dim3(48), dim3(256), 0, net->tr.st, net->theta[net->latest], net->theta_pk[net->latest]);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(net->tr.st));
-  }
-  return GA3C_OK;
+  return arena_copy(net, which, var.off, count, out, in);
 }
 
 int ga3c_net_get_param(ga3c_net* net, const char* name, int32_t which, float* out, int64_t count) {
@@ -1927,164 +1916,42 @@ int ga3c_net_set_param(ga3c_net* net, const char* name, int32_t which, const flo
   return param_copy(net, name, which, nullptr, in, count);
 }
 
-// The members of a DUAL_RMSPROP checkpoint beside "<name>:0" and "step": (variable, suffix, arena).  Derived, not observed (no
-// TensorFlow here; unverified against a TF run): both branches build the value optimizer first (NetworkVP_discrate.py:109-112
-// and :126), TF-1's RMSPropOptimizer._create_slots makes the `rms` slot, then the `momentum` slot of each variable, both named
-// after the optimizer ("RMSProp"), and uniquifies a repeated name with _1, _2, ...  An optimizer has no slot for a variable
-// its cost has no gradient for.  So the trunk carries the value optimizer's slots as RMSProp / RMSProp_1 and the policy
-// optimizer's as RMSProp_2 / RMSProp_3, logits_v/* the value optimizer's and logits_p/* the policy optimizer's as
-// RMSProp / RMSProp_1 -- the single optimizer's rule (ga3c_net_save) applied twice.
-namespace {
-struct SlotMember { int param; const char* suffix; int which; };
-// (appends to `out`, after the ten "<name>:0" members of arena 0)
-void dual_members(std::vector<SlotMember>& out) {
-  for (int i = 0; i < NPARAMS; ++i) out.push_back({i, ":0", 0});
-  for (int i = 0; i < NPARAMS; ++i) {
-    const std::string base(PARAM_NAMES[i]);
-    if (base.compare(0, 9, "logits_p/") != 0) {     // the value optimizer: every variable but logits_p/*
-      out.push_back({i, "/RMSProp:0", 4});
-      out.push_back({i, "/RMSProp_1:0", 5});
-    }
-    if (base.compare(0, 9, "logits_v/") == 0) continue;
-    const bool trunk = base.compare(0, 7, "logits_") != 0;    // the policy optimizer: every variable but logits_v/*
-    out.push_back({i, trunk ? "/RMSProp_2:0" : "/RMSProp:0", 1});
-    out.push_back({i, trunk ? "/RMSProp_3:0" : "/RMSProp_1:0", 2});
-  }
+// ---- checkpoints: the members of the variable table (ga3c_vartable.hpp) over the arenas a set call reaches
+static std::vector<int> writable_arenas(const ga3c_net* net) {
+  return net->dual ? std::vector<int>{0, 1, 2, 4, 5} : std::vector<int>{0, 1, 2};
 }
-
-int save_dual(ga3c_net* net, const char* path) {
-  const int which[5] = {0, 1, 2, 4, 5};
-  std::vector<float> arena[7];
-  for (int w : which) {
-    arena[w].resize((size_t)net->n);
-    CHK(ga3c_net_get_arena(net, w, arena[w].data(), net->n));
-  }
-  std::vector<ga3c_ckpt::Member> members;
-  ga3c_ckpt::Member st;
-  st.name = "step"; st.descr = "<i8";
-  const int64_t step = net->step.load();
-  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
-  members.push_back(st);
-  std::vector<SlotMember> list;
-  dual_members(list);
-  for (const SlotMember& sm : list) {
-    ParamInfo pi;
-    param_lookup(net, PARAM_NAMES[sm.param], &pi);
-    ga3c_ckpt::Member m;
-    m.name = std::string(PARAM_NAMES[sm.param]) + sm.suffix;
-    m.descr = "<f4";
-    m.shape.assign(pi.shape, pi.shape + pi.ndim);
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[sm.which].data() + pi.off);
-    m.bytes.assign(src, src + (size_t)pi.count * sizeof(float));
-    members.push_back(std::move(m));
-  }
-  std::string err;
-  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  return GA3C_OK;
-}
-
-// load of a DUAL_RMSPROP checkpoint (the members of save_dual): everything is checked before the first arena is
-// written.  Slot regions no optimizer has a slot for are reset to the slots' initial values (ms = 1, mom = 0).
-int load_dual(ga3c_net* net, const char* path, const std::map<std::string, ga3c_ckpt::Member>& members) {
-  const int which[5] = {0, 1, 2, 4, 5};
-  std::vector<float> arena[7];
-  for (int w : which) arena[w].assign((size_t)net->n, (w == 1 || w == 4) ? 1.0f : 0.0f);
-  std::vector<SlotMember> list;
-  dual_members(list);
-  for (const SlotMember& sm : list) {
-    ParamInfo pi;
-    param_lookup(net, PARAM_NAMES[sm.param], &pi);
-    const std::string key = std::string(PARAM_NAMES[sm.param]) + sm.suffix;
-    auto it = members.find(key);
-    if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s (not a DUAL_RMSPROP checkpoint?)", path, key.c_str());
-    const ga3c_ckpt::Member& m = it->second;
-    int64_t elems = 1;
-    for (int64_t d : m.shape) elems *= d;
-    if (m.descr != "<f4" || elems != pi.count || m.bytes.size() != (size_t)pi.count * sizeof(float))
-      return fail(GA3C_ESTATE, "%s: %s is %s with %lld elements, this network wants <f4 with %lld", path, key.c_str(),
-                  m.descr.c_str(), (long long)elems, (long long)pi.count);
-    memcpy(arena[sm.which].data() + pi.off, m.bytes.data(), m.bytes.size());
-  }
-  auto st = members.find("step");
-  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
-    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
-  int64_t step = 0;
-  memcpy(&step, st->second.bytes.data(), 8);
-  for (int w : which) CHK(ga3c_net_set_arena(net, w, arena[w].data(), net->n));
-  net->step.store(step);
-  return GA3C_OK;
-}
-}  // namespace
 
 int ga3c_net_save(ga3c_net* net, const char* path) {
   if (!net || !path) return fail(GA3C_EINVAL, "null argument");
-  if (net->dual) return save_dual(net, path);
-  std::vector<float> arena[3];
-  for (int w = 0; w < 3; ++w) {
+  ga3c_ckpt::Arenas arena(7);
+  for (int w : writable_arenas(net)) {
     arena[w].resize((size_t)net->n);
     CHK(ga3c_net_get_arena(net, w, arena[w].data(), net->n));
   }
-  const char* suffix[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};
-  std::vector<ga3c_ckpt::Member> members;
-  ga3c_ckpt::Member st;
-  st.name = "step"; st.descr = "<i8";
-  const int64_t step = net->step.load();
-  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
-  members.push_back(st);
-  for (int i = 0; i < nparams(net); ++i) {
-    ParamInfo pi;
-    param_lookup(net, param_name(net, i), &pi);
-    for (int w = 0; w < 3; ++w) {
-      ga3c_ckpt::Member m;
-      m.name = std::string(param_name(net, i)) + suffix[w];
-      m.descr = "<f4";
-      m.shape.assign(pi.shape, pi.shape + pi.ndim);
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[w].data() + pi.off);
-      m.bytes.assign(src, src + (size_t)pi.count * sizeof(float));
-      members.push_back(std::move(m));
-    }
-  }
   std::string err;
-  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  if (!ga3c_ckpt::write_npz(path, ga3c_ckpt::pack_members(net->vars, net->step.load(), arena), &err))
+    return fail(GA3C_ESTATE, "%s", err.c_str());
   return GA3C_OK;
 }
 
+// A continuous file holds no logits_p/w, a discrete one no logits_p/out_x/w, a single-optimizer one no second pair of trunk
+// slots: each is refused by the other kind of network before anything is written.  A slot region that no member names
+// (DUAL_RMSPROP: no optimizer has a slot there) is reset to the slots' initial values, ms = 1 and mom = 0.
 int ga3c_net_load(ga3c_net* net, const char* path) {
   if (!net || !path) return fail(GA3C_EINVAL, "null argument");
   std::map<std::string, ga3c_ckpt::Member> members;
   std::string err;
   if (!ga3c_ckpt::read_npz(path, &members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
-  if (net->dual) return load_dual(net, path, members);
   // a DUAL_RMSPROP checkpoint holds every member of a single-optimizer one (its value optimizer's slots of the trunk under
   // the single optimizer's names) and more: it is refused, not read as half of itself
-  if (members.count("conv11/w/RMSProp_2:0")) return fail(GA3C_ESTATE, "%s is a DUAL_RMSPROP checkpoint; this network has one optimizer", path);
-  const char* suffix[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};
-  std::vector<float> arena[3];
-  for (int w = 0; w < 3; ++w) arena[w].resize((size_t)net->n);
-  // a continuous file holds no logits_p/w, a discrete one no logits_p/out_x/w: either is refused by the other kind of network
-  // below, before anything is written
-  for (int i = 0; i < nparams(net); ++i) {
-    ParamInfo pi;
-    param_lookup(net, param_name(net, i), &pi);
-    for (int w = 0; w < 3; ++w) {
-      const std::string key = std::string(param_name(net, i)) + suffix[w];
-      auto it = members.find(key);
-      if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s", path, key.c_str());
-      const ga3c_ckpt::Member& m = it->second;
-      int64_t elems = 1;
-      for (int64_t d : m.shape) elems *= d;
-      if (m.descr != "<f4" || elems != pi.count || m.bytes.size() != (size_t)pi.count * sizeof(float))
-        return fail(GA3C_ESTATE, "%s: %s is %s with %lld elements, this network wants <f4 with %lld", path, key.c_str(),
-                    m.descr.c_str(), (long long)elems, (long long)pi.count);
-      memcpy(arena[w].data() + pi.off, m.bytes.data(), m.bytes.size());
-    }
-  }
-  auto st = members.find("step");
-  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
-    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
+  if (!net->dual && members.count("conv11/w/RMSProp_2:0"))
+    return fail(GA3C_ESTATE, "%s is a DUAL_RMSPROP checkpoint; this network has one optimizer", path);
+  ga3c_ckpt::Arenas arena(7);
+  for (int w : writable_arenas(net)) arena[w].assign((size_t)net->n, (w == 1 || w == 4) ? 1.0f : 0.0f);
   int64_t step = 0;
-  memcpy(&step, st->second.bytes.data(), 8);
-  for (int w = 0; w < 3; ++w) CHK(ga3c_net_set_arena(net, w, arena[w].data(), net->n));
+  if (!ga3c_ckpt::unpack_members(path, "image network", net->vars, members, &arena, &step, &err))
+    return fail(GA3C_ESTATE, "%s", err.c_str());
+  for (int w : writable_arenas(net)) CHK(ga3c_net_set_arena(net, w, arena[w].data(), net->n));
   net->step.store(step);
   return GA3C_OK;
 }

@@ -573,20 +573,10 @@ int ga3c_mlp_create(const ga3c_mlp_config* cfg, ga3c_mlp** out) {
   m->L = make_layout(cfg->state_dim, cfg->num_actions);
   for (int l = 0; l < NLAYERS; ++l) m->add_dense(VAR_NAMES[2 * l], VAR_NAMES[2 * l + 1], m->L.off[2 * l], m->L.in[l], m->L.out[l]);
   m->dual = (cfg->flags & GA3C_FLAG_DUAL_RMSPROP) != 0;
-  if (m->dual)      // two optimizers built value first: TF-1 names the slots /RMSProp, _1, _2, _3 in creation order per variable
-    for (int v = 0; v < NVARS; ++v) {
-      Var& var = m->vars[v];
-      var.ckpt.assign(1, {var.name + ":0", 0});
-      const bool trunk = v < 2 * NTRUNK;
-      if (trunk || v < 2 * NTRUNK + 2) {
-        var.ckpt.emplace_back(var.name + "/RMSProp:0", 4);
-        var.ckpt.emplace_back(var.name + "/RMSProp_1:0", 5);
-      }
-      if (trunk || v >= 2 * NTRUNK + 2) {
-        var.ckpt.emplace_back(var.name + (trunk ? "/RMSProp_2:0" : "/RMSProp:0"), 1);
-        var.ckpt.emplace_back(var.name + (trunk ? "/RMSProp_3:0" : "/RMSProp_1:0"), 2);
-      }
-    }
+  if (m->dual) {    // the trunk has both optimizers' slots; the value head (the two variables behind it) and the policy head their own
+    const int V0 = 2 * NTRUNK, P0 = V0 + 2;
+    for (int v = 0; v < NVARS; ++v) ga3c_ckpt::dual_members(&m->vars[v], v < P0, v < V0 || v >= P0);
+  }
   return create(m, out);
 }
 

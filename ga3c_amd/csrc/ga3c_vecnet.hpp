@@ -41,7 +41,7 @@
 #include <vector>
 
 #include "../../include/ga3c_abi.h"
-#include "ga3c_checkpoint.hpp"
+#include "ga3c_vartable.hpp"
 
 void ga3c_set_last_error(const char* msg);   // ga3c_engine.hip: the thread's ga3c_last_error() message
 
@@ -111,13 +111,7 @@ struct PLane {                    // one prediction in flight: pinned staging + 
   int B = 0;
 };
 
-struct Var {                      // one variable: its name (no ":0"), its first arena element, its shape, and the
-  std::string name;               // (member name, arena) pairs a checkpoint keeps it under
-  int64_t off, count;
-  int32_t ndim;
-  int64_t shape[2];
-  std::vector<std::pair<std::string, int>> ckpt;
-};
+using ga3c_ckpt::Var;             // the variable table and its checkpoint members: ga3c_vartable.hpp
 
 struct Core {
   const char* kind = "";          // what the network calls itself in an error text
@@ -247,15 +241,6 @@ inline int predict_end(Core* m, int ticket, int B, PLane** lane) {
   return GA3C_OK;
 }
 
-inline int param_index(const Core* m, const char* name) {
-  if (!name) return -1;
-  std::string s(name);
-  if (s.size() > 2 && s.compare(s.size() - 2, 2, ":0") == 0) s.resize(s.size() - 2);
-  for (size_t i = 0; i < m->vars.size(); ++i)
-    if (s == m->vars[i].name) return (int)i;
-  return -1;
-}
-
 inline int arena_copy(Core* m, int which, int64_t off, int64_t count, float* out, const float* in) {
   if (which < 0 || which >= m->narena) return fail(GA3C_EINVAL, "arena selector %d not in [0,%d]", which, m->narena - 1);
   if (in && std::find(m->writable.begin(), m->writable.end(), which) == m->writable.end())
@@ -307,21 +292,20 @@ inline const char* param_name(Core* m, int32_t index) {
 
 inline int param_info(Core* m, const char* name, int64_t* offset, int64_t* count, int32_t* ndim, int64_t shape[4]) {
   if (!m || !name) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(m, name);
+  const int i = ga3c_ckpt::find_var(m->vars, name);
   if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
   const Var& var = m->vars[i];
   if (offset) *offset = var.off;
   if (count) *count = var.count;
   if (ndim) *ndim = var.ndim;
-  const int64_t sh[4] = {var.shape[0], var.shape[1], 0, 0};
-  if (shape) memcpy(shape, sh, sizeof sh);
+  if (shape) memcpy(shape, var.shape, sizeof var.shape);
   return GA3C_OK;
 }
 
 // get_param (out) / set_param (in)
 inline int param_copy(Core* m, const char* name, int32_t which, float* out, const float* in, int64_t count) {
   if (!m || !name || (!out && !in)) return fail(GA3C_EINVAL, "null argument");
-  const int i = param_index(m, name);
+  const int i = ga3c_ckpt::find_var(m->vars, name);
   if (i < 0) return fail(GA3C_EINVAL, "no variable named %s", name);
   const Var& var = m->vars[i];
   if (count != var.count) return fail(GA3C_EINVAL, "%s has %lld elements, not %lld", name, (long long)var.count, (long long)count);
@@ -329,7 +313,7 @@ inline int param_copy(Core* m, const char* name, int32_t which, float* out, cons
 }
 
 // The writable arenas on the host, by arena number, as save writes and load starts from them.
-inline int read_arenas(Core* m, std::vector<std::vector<float>>* arena) {
+inline int read_arenas(Core* m, ga3c_ckpt::Arenas* arena) {
   arena->assign((size_t)m->narena, std::vector<float>());
   for (int w : m->writable) {
     (*arena)[w].resize((size_t)m->n);
@@ -338,30 +322,13 @@ inline int read_arenas(Core* m, std::vector<std::vector<float>>* arena) {
   return GA3C_OK;
 }
 
-// step, then the members of every variable in table order
 inline int save(Core* m, const char* path) {
   if (!m || !path) return fail(GA3C_EINVAL, "null argument");
-  std::vector<std::vector<float>> arena;
+  ga3c_ckpt::Arenas arena;
   CHK(read_arenas(m, &arena));
-  std::vector<ga3c_ckpt::Member> members;
-  ga3c_ckpt::Member st;
-  st.name = "step";
-  st.descr = "<i8";
-  const int64_t step = m->step.load();
-  st.bytes.assign(reinterpret_cast<const uint8_t*>(&step), reinterpret_cast<const uint8_t*>(&step) + 8);
-  members.push_back(st);
-  for (const Var& var : m->vars)
-    for (const auto& km : var.ckpt) {
-      ga3c_ckpt::Member mb;
-      mb.name = km.first;
-      mb.descr = "<f4";
-      mb.shape.assign(var.shape, var.shape + var.ndim);
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(arena[km.second].data() + var.off);
-      mb.bytes.assign(src, src + (size_t)var.count * sizeof(float));
-      members.push_back(std::move(mb));
-    }
   std::string err;
-  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  if (!ga3c_ckpt::write_npz(path, ga3c_ckpt::pack_members(m->vars, m->step.load(), arena), &err))
+    return fail(GA3C_ESTATE, "%s", err.c_str());
   return GA3C_OK;
 }
 
@@ -372,32 +339,19 @@ inline int read_checkpoint(const char* path, std::map<std::string, ga3c_ckpt::Me
 }
 
 inline int checkpoint_step(const char* path, const std::map<std::string, ga3c_ckpt::Member>& members, int64_t* step) {
-  auto st = members.find("step");
-  if (st == members.end() || st->second.descr != "<i8" || st->second.bytes.size() != 8)
-    return fail(GA3C_ESTATE, "%s holds no int64 step", path);
-  memcpy(step, st->second.bytes.data(), 8);
+  std::string err;
+  if (!ga3c_ckpt::checkpoint_step(path, members, step, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
   return GA3C_OK;
 }
 
-// `members`: the file, read already.  A file of another network kind lacks this one's first variable: refused, as is any
-// member of another shape, before anything is written.  An arena element that no member names keeps its value.
+// `members`: the file, read already.  What unpack_members refuses is refused before anything is written; an arena element
+// that no member names keeps its value.
 inline int load(Core* m, const char* path, const std::map<std::string, ga3c_ckpt::Member>& members) {
-  std::vector<std::vector<float>> arena;
+  ga3c_ckpt::Arenas arena;
   CHK(read_arenas(m, &arena));
-  for (const Var& var : m->vars)
-    for (const auto& km : var.ckpt) {
-      const std::string& key = km.first;
-      auto it = members.find(key);
-      if (it == members.end()) return fail(GA3C_ESTATE, "%s holds no %s: not a checkpoint of this %s", path, key.c_str(), m->kind);
-      const ga3c_ckpt::Member& mb = it->second;
-      const bool shape_ok = mb.shape.size() == (size_t)var.ndim && std::equal(mb.shape.begin(), mb.shape.end(), var.shape);
-      if (mb.descr != "<f4" || !shape_ok || mb.bytes.size() != (size_t)var.count * sizeof(float))
-        return fail(GA3C_ESTATE, "%s: %s is not <f4 of this network's shape (%lld elements)", path, key.c_str(),
-                    (long long)var.count);
-      memcpy(arena[km.second].data() + var.off, mb.bytes.data(), mb.bytes.size());
-    }
   int64_t step = 0;
-  CHK(checkpoint_step(path, members, &step));
+  std::string err;
+  if (!ga3c_ckpt::unpack_members(path, m->kind, m->vars, members, &arena, &step, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
   for (int w : m->writable) CHK(set_arena(m, w, arena[w].data(), m->n));
   m->step.store(step);
   return GA3C_OK;
@@ -541,8 +495,6 @@ int check_device(const C& c) {
 
 // ------------------------------------------------------------------ Net: the actor-critic layer (ga3c_mlp, ga3c_dmlp)
 
-const char* const CKPT_SUFFIX[3] = {":0", "/RMSProp:0", "/RMSProp_1:0"};   // a variable and its two slots, arenas 0..2
-
 struct Net : Core {               // arenas: theta, ms, mom, grad; dual: + the value optimizer's ms, mom, grad
   int A = 0;
   bool dual = false;              // two optimizers, one per cost: arenas 1/2/3 are cost_p's, 4/5/6 cost_v's
@@ -558,8 +510,7 @@ struct Net : Core {               // arenas: theta, ms, mom, grad; dual: + the v
   void add_dense(const std::string& w_name, const std::string& b_name, int64_t off, int in, int out) {
     vars.push_back(Var{w_name, off, (int64_t)in * out, 2, {in, out}, {}});
     vars.push_back(Var{b_name, off + (int64_t)in * out, out, 1, {out, 0}, {}});
-    for (Var* var : {&vars[vars.size() - 2], &vars.back()})
-      for (int w = 0; w < 3; ++w) var->ckpt.emplace_back(var->name + CKPT_SUFFIX[w], w);
+    for (Var* var : {&vars[vars.size() - 2], &vars.back()}) ga3c_ckpt::single_members(var);
     n = off + (int64_t)in * out + out;
   }
 };

@@ -236,6 +236,123 @@ def test_checkpoint_members_round_trip_and_refusals(tmp_path):
         single.close()
 
 
+# ---- the checkpoint path all networks share (csrc/ga3c_vartable.hpp), on the smallest handle: A = 2, one row, one lane
+WRITABLE = {True: (0, 1, 2, 4, 5), False: (0, 1, 2)}
+
+
+def _fill(net, dual, seed, step):
+    """Every writable arena to values of its own, the step to `step` -> {arena: values}."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    arenas = {w: rng.normal(size=net.param_count).astype(np.float32) for w in WRITABLE[dual]}
+    for w, flat in arenas.items():
+        net.set_arena(w, flat)
+    net._call("set_step", step)
+    return arenas
+
+
+def _head_masks(net):
+    """-> (elements of logits_v/*, elements of logits_p/*)"""
+    masks = []
+    for head in ("logits_v/", "logits_p/"):
+        mask = np.zeros(net.param_count, bool)
+        for k in net.param_order:
+            if k.startswith(head):
+                off, size = net._offsets[k]
+                mask[off:off + size] = True
+        assert mask.any()
+        masks.append(mask)
+    return masks
+
+
+def _dual_members_in_order(parent):
+    """The members of a dual file behind "step": variable-major, as every writer of the project writes them, or (parent) in
+    the order the image network wrote before it shared that path: all ":0" first, then the slots variable by variable."""
+    def slots(k):
+        if k.startswith("logits_"):
+            return [k + "/RMSProp:0", k + "/RMSProp_1:0"]
+        return [k + s for s in ("/RMSProp:0", "/RMSProp_1:0", "/RMSProp_2:0", "/RMSProp_3:0")]
+    if parent:
+        return [k + ":0" for k in o.PARAM_ORDER] + [name for k in o.PARAM_ORDER for name in slots(k)]
+    return [name for k in o.PARAM_ORDER for name in [k + ":0"] + slots(k)]
+
+
+def test_a_member_of_the_right_count_and_another_shape_is_refused(tmp_path):
+    num_actions = 2
+    net = _net(num_actions, 1, dual=False)
+    try:
+        saved = _fill(net, False, 1, 5)
+        good, bad = str(tmp_path / "good.npz"), str(tmp_path / "bad.npz")
+        net._call("save", good.encode())
+        with np.load(good) as z:
+            members = {k: z[k] for k in z.files}
+        assert members["logits_p/w:0"].shape == (256, num_actions)
+        members["logits_p/w:0"] = members["logits_p/w:0"].reshape(num_actions, 256)      # the same 512 elements
+        np.savez(bad, **members)
+        before = _fill(net, False, 2, 9)
+        assert net._lib.ga3c_net_load(net._h, bad.encode()) == -4                        # GA3C_ESTATE
+        for w in (0, 1, 2):
+            assert np.array_equal(net.get_arena(w), before[w]), w
+        assert net.get_global_step() == 9
+        net._call("load", good.encode())                        # the file as written still loads
+        for w in (0, 1, 2):
+            assert np.array_equal(net.get_arena(w), saved[w]), w
+        assert net.get_global_step() == 5
+    finally:
+        net.close()
+
+
+def test_a_dual_file_is_variable_major_and_one_in_the_earlier_member_order_loads_the_same(tmp_path):
+    net = _net(2, 1)
+    try:
+        _fill(net, True, 3, 5)
+        path, parent = str(tmp_path / "dual.npz"), str(tmp_path / "parent_order.npz")
+        net._call("save", path.encode())
+        with np.load(path) as z:
+            assert z.files == ["step"] + _dual_members_in_order(parent=False)
+            members = {k: z[k] for k in z.files}
+        np.savez(parent, **{k: members[k] for k in ["step"] + _dual_members_in_order(parent=True)})
+        with np.load(parent) as z:
+            assert z.files == ["step"] + _dual_members_in_order(parent=True) and z.files != list(members)
+        loaded = []
+        for file in (path, parent):
+            _fill(net, True, 4, 0)
+            net._call("load", file.encode())
+            loaded.append([net.get_arena(w) for w in WRITABLE[True]] + [net.get_global_step()])
+        for got, want in zip(loaded[1][:-1], loaded[0][:-1]):
+            assert np.array_equal(got, want)
+        assert loaded[1][-1] == loaded[0][-1] == 5
+    finally:
+        net.close()
+
+
+def test_a_load_resets_slot_regions_no_member_names_on_the_image_network_and_keeps_them_on_the_vector_network(tmp_path):
+    """Where a load starts from: the image network from the slots' initial values, ms = 1 and mom = 0, the
+    vector-state network from what its arenas hold.  The regions no member names are the policy optimizer's slots (arenas
+    1 / 2) over logits_v/* and the value optimizer's (4 / 5) over logits_p/*."""
+    from NetworkVP_vector import Network as VectorNetwork
+    image = _net(2, 1)
+    with _config(DUAL_RMSPROP=True):
+        vector = VectorNetwork("gpu:0", "vecdual", 1, (3,), max_batch=1, predict_lanes=1)
+    try:
+        for net, unnamed in ((image, {1: 1.0, 2: 0.0, 4: 1.0, 5: 0.0}), (vector, {1: 7.0, 2: 7.0, 4: 7.0, 5: 7.0})):
+            prefix = net.PREFIX
+            saved = _fill(net, True, 6, 5)
+            path = str(tmp_path / (prefix + ".npz"))
+            net._call("save", path.encode())
+            for w in (1, 2, 4, 5):
+                net.set_arena(w, np.full(net.param_count, 7.0, np.float32))
+            net._call("load", path.encode())
+            head_v, head_p = _head_masks(net)
+            assert np.array_equal(net.get_arena(0), saved[0]), prefix
+            for w, mask in ((1, head_v), (2, head_v), (4, head_p), (5, head_p)):
+                got = net.get_arena(w)
+                assert np.all(got[mask] == np.float32(unnamed[w])), (prefix, w)
+                assert np.array_equal(got[~mask], saved[w][~mask]), (prefix, w)
+    finally:
+        image.close()
+        vector.close()
+
+
 def test_one_rank_communicator_and_one_hogwild_lane_give_the_same_bits():
     from NetworkVP import Network
     num_actions = 6
