@@ -85,6 +85,8 @@ class Config:
     DDPG_POLICY_DELAY = 2               # a policy step every this many train steps (1..16)
     DDPG_TARGET_NOISE = 0.2             # sigma of the target smoothing: a~ = clip(actor_target(s2) + clip(sigma n, -c, c), -1, 1)
     DDPG_TARGET_NOISE_CLIP = 0.5        # ... and its c
+    DDPG_NSTEP = 1                      # DEVICE_DDPG only: the ring's rows carry n-step returns, R = sum_{k<m} gamma^k r_k cut at an
+                                        # episode's end, and y = R + gamma^m q'(s_m) (1..16; 1: one-step rows, as without it)
     tau = 0.001
     gamma = 0.99
     actor_lr = 1.0                      # factors on the annealed learning rate; the later of the two assignments in the
@@ -221,6 +223,7 @@ def resolve_ddpg(explicit=()):
             raise ValueError("PRIORITIZED_REPLAY needs USE_DDPG: only the DDPG handle keeps a replay memory")
         if Config.DDPG_TWIN:
             raise ValueError("DDPG_TWIN needs USE_DDPG: the twin critics are the DDPG handle's")
+        _resolve_nstep()
         return
     if not Config.CONTINUOUS_INPUT:
         raise ValueError("USE_DDPG needs a continuous action space (CONTINUOUS_INPUT); GAME=%s is discrete" % Config.GAME)
@@ -265,8 +268,26 @@ def resolve_ddpg(explicit=()):
         if not Config.DDPG_TARGET_NOISE >= 0.0 or not Config.DDPG_TARGET_NOISE_CLIP >= 0.0:
             raise ValueError("DDPG_TARGET_NOISE / _CLIP = %r / %r: numbers >= 0"
                              % (Config.DDPG_TARGET_NOISE, Config.DDPG_TARGET_NOISE_CLIP))
+    _resolve_nstep()
     Config.USE_REPLAY_MEMORY = True
     Config.DISCOUNTING = False
+
+
+def _resolve_nstep():
+    """DDPG_NSTEP: 1 changes nothing anywhere; more needs the device actors of a DDPG handle."""
+    n = Config.DDPG_NSTEP
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 16:
+        raise ValueError("DDPG_NSTEP=%r: a whole number of steps from 1 to 16" % (n,))
+    if n == 1:
+        return
+    if not Config.USE_DDPG:
+        raise ValueError("DDPG_NSTEP=%d needs USE_DDPG: the n-step returns are the DDPG handle's" % n)
+    if not getattr(Config, "DEVICE_DDPG", False):
+        raise ValueError("DDPG_NSTEP=%d needs DEVICE_DDPG: the n-step sum is formed in a per-environment window on the device.  "
+                         "The agent processes ship rollouts cut at TIME_MAX with a repeated first row, and no window spans "
+                         "them; the host path stays one-step" % n)
+    if not Config.DDPG_FUTURE_REWARD_CALC:
+        raise ValueError("DDPG_NSTEP=%d with DDPG_FUTURE_REWARD_CALC=False is not supported: y = r reads no discount" % n)
 
 
 def _resolve_device_ddpg(n, pendulum):

@@ -8,7 +8,8 @@ Same interface as NetworkVP.Network where Server, ThreadPredictor and ThreadTrai
 the handle (replay_add*, train_replay); the Ornstein-Uhlenbeck process too, because the native predictor loops call the
 handle without the interpreter.  Under Config.PRIORITIZED_REPLAY the handle also keeps a priority per ring slot and draws a
 step's rows itself (train_prioritized).  Under Config.DDPG_TWIN it has a second critic, critic2_*, and every
-train-type call runs the twin step (twin_create).
+train-type call runs the twin step (twin_create).  Under Config.DDPG_NSTEP > 1 the device actors write n-step
+returns into the ring and a discount per slot beside them (nstep_create).
 """
 import ctypes as C
 import os
@@ -143,6 +144,9 @@ class Network(DeviceActors, NativeHandle):
         if self.prioritized:
             self._call("priorities_create", float(Config.PRIORITIZED_REPLAY_ALPHA), float(Config.PRIORITIZED_REPLAY_EPS),
                        int(Config.REPLAY_BUFFER_RANDOM_SEED))
+        self.nstep = int(Config.DDPG_NSTEP)
+        if self.nstep > 1:                      # before actors_create, which sizes the environments' windows
+            self._call("nstep_create", self.nstep)
 
     # ---- variables: which = VALUE, TARGET, SLOT_A, SLOT_B (RMSProp ms / mom or Adam m / v), GRAD -----------------------
     def set_global_step(self, step):
@@ -306,11 +310,29 @@ class Network(DeviceActors, NativeHandle):
         self._call("time_prioritized", int(batch), int(iters), float(self.replay_beta), float(self.learning_rate), C.byref(ms))
         return ms.value
 
+    # ---- n-step returns (Config.DDPG_NSTEP) ------------------------------------------------
+    def nstep_create(self, n):
+        """Attaches n-step state to a handle that has none (Config.DDPG_NSTEP = 1) and no device actors yet."""
+        self._call("nstep_create", int(n))
+        self.nstep = int(n)
+
+    def nstep_discounts(self):
+        """-> f32 [replay_capacity]: the discount of the row in each ring slot, gamma^m."""
+        disc = np.empty(self.replay_capacity, np.float32)
+        self._call("nstep_get", nat.ptr(disc), disc.size)
+        return disc
+
+    def set_nstep_discounts(self, disc):
+        disc = nat.as_f32(disc).ravel()
+        if disc.size != self.replay_capacity:
+            raise ValueError("%d discounts for %d ring slots" % (disc.size, self.replay_capacity))
+        self._call("nstep_set", nat.ptr(disc), disc.size)
+
     # ---- device actors (Config.DEVICE_DDPG, DESIGN.md 8l) ------------------------------------------------
     # what ga3c_ddpg_actors_get names (NetworkVP_vecnet.DeviceActors); "slots" has one row per row of a train step
     ACTOR_FIELDS = {"phys": (np.float64, 2), "elapsed": (np.int32, 1), "draws": (np.uint64, 1), "obs": (np.float32, 3),
                     "action": (np.float32, "A"), "reward": (np.float64, 1), "done": (np.int32, 1), "slots": (np.int32, 1)}
-    ACTOR_SCALARS = {"batch": np.int32, "draw_seed": np.int64}
+    ACTOR_SCALARS = {"batch": np.int32, "draw_seed": np.int64, "nstep": np.int32, "nstep_count": np.int64}
     ACTOR_ROWS = {"slots": "batch"}
 
     def actors_create(self, n, time_max=None, discount=None, seed=None, updates=None, batch=None, draw_seed=None):

@@ -210,6 +210,11 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_actors_episodes": (C.c_int, [C.c_void_p, f64p, i64p, C.c_int32, i32p]),
     "ga3c_ddpg_actors_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "ga3c_ddpg_actors_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    # n-step returns of a DDPG handle's device actors (Config.DDPG_NSTEP), include/ga3c_abi.h
+    "ga3c_ddpg_nstep_create": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ga3c_ddpg_nstep_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_nstep_get": (C.c_int, [C.c_void_p, f32p, C.c_int64]),
+    "ga3c_ddpg_nstep_set": (C.c_int, [C.c_void_p, f32p, C.c_int64]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

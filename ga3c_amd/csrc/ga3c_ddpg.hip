@@ -36,6 +36,12 @@
 // ddpg_wgrad_kernel.  Critic 2's variables lie behind the 26 in every arena and are read through a second Layout whose
 // critic entries name them (twin_view), so the device functions of one critic serve both.
 // An actor step is predict + 2 launches; every launch argument is known to the host, which waits once per actors_run.
+// n-step returns (ga3c_ddpg_nstep_create, Config.DDPG_NSTEP; tests/nstep_oracle.py is the same statement):
+//   ddpg_actors_nstep_kernel<Env>  ddpg_actors_step_kernel's step, the transition into the environment's window of n, and from
+//                                  the n-th transition on one ring row per step: the n-step return of the oldest entry, cut at
+//                                  an episode's end, and its discount gamma^m into disc[slot]
+//   nstep_fill_kernel              disc[slot] = gamma for rows added by hand
+// The two target kernels read disc[slot] where a step's rows are ring slots of such a handle, the scalar gamma otherwise.
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -290,8 +296,18 @@ __device__ __forceinline__ void load_rows(const Rows& src, int col, int width, f
   }
 }
 
+// disc (null: the scalar gamma for every row): the discount by ring slot of a handle with n-step returns, whose rows are ring
+// slots; used (null without n-step): the B discounts this step's target took.
+__device__ __forceinline__ float row_discount(const float* __restrict__ disc, float* __restrict__ used, int64_t slot, int row,
+                                              float gamma) {
+  const float g = disc ? disc[slot] : gamma;
+  if (used) used[row] = g;
+  return g;
+}
+
 __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(Layout L, const float* __restrict__ thT, Rows src, int B, float gamma,
-                                                              int future, Work w) {
+                                                              int future, Work w, const float* __restrict__ disc,
+                                                              float* __restrict__ used) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
@@ -309,10 +325,11 @@ __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(Layout L, const fl
     const int r = threadIdx.x;
     const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
     const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
+    const float g = row_discount(disc, used, slot, row0 + r, gamma);
     float y = rew, qt = 0.f;
     if (future) {
       qt = qv[r];
-      if (done == 0.f) y = fmaf(gamma, qt, rew);
+      if (done == 0.f) y = fmaf(g, qt, rew);
     }
     w.y[row0 + r] = y;
     w.qt[row0 + r] = qt;
@@ -324,7 +341,8 @@ __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(Layout L, const fl
 // Both target critics read a~ from `act`, one after the other in the same buffers; y comes from the smaller q'.
 __global__ __launch_bounds__(THREADS) void ddpg_twin_target_kernel(Pair<Layout> L, const float* __restrict__ thT, Rows src, int B,
                                                                    float gamma, int future, float sigma, float clip, uint64_t seed,
-                                                                   uint64_t number, Work w, Work2 w2) {
+                                                                   uint64_t number, Work w, Work2 w2,
+                                                                   const float* __restrict__ disc, float* __restrict__ used) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
@@ -359,12 +377,13 @@ __global__ __launch_bounds__(THREADS) void ddpg_twin_target_kernel(Pair<Layout> 
     const int r = threadIdx.x;
     const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
     const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
+    const float g = row_discount(disc, used, slot, row0 + r, gamma);
     float y = rew, qt = 0.f, q1 = 0.f, q2 = 0.f;
     if (future) {
       q1 = qv[r];
       q2 = qv2[r];
       qt = fminf(q1, q2);
-      if (done == 0.f) y = fmaf(gamma, qt, rew);
+      if (done == 0.f) y = fmaf(g, qt, rew);
     }
     w.y[row0 + r] = y;
     w.qt[row0 + r] = qt;
@@ -623,9 +642,10 @@ __global__ __launch_bounds__(THREADS) void ddpg_twin_update_kernel(Pair<Layout> 
 }
 
 // Ring slot (first + i) mod cap <- s | a | r | done | s2, from row `s[S] | s2[S] | done` of the transport and the staged r, a.
+// disc (null without n-step returns): the slot's discount <- gamma, a one-step row's.
 __global__ void ddpg_ring_gather_kernel(const char* __restrict__ seg, const int64_t* __restrict__ off, const float* __restrict__ r,
                                         const float* __restrict__ a, int n, float* __restrict__ ring, int64_t first, int64_t cap,
-                                        int S, int A) {
+                                        int S, int A, float* __restrict__ disc, float gamma) {
   const int rowf = 2 * S + A + 2;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)n * rowf) return;
@@ -638,6 +658,13 @@ __global__ void ddpg_ring_gather_kernel(const char* __restrict__ seg, const int6
   else if (c == S + A + 1) v = row[2 * S];
   else v = row[S + c - (S + A + 2)];
   ring[((first + i) % cap) * rowf + c] = v;
+  if (disc && c == 0) disc[(first + i) % cap] = gamma;
+}
+
+// disc of the n slots from `first` on (mod cap) <- gamma: rows added by hand are one-step rows.  n <= cap.
+__global__ void nstep_fill_kernel(float* __restrict__ disc, float gamma, int64_t first, int n, int64_t cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) disc[(first + i) % cap] = gamma;
 }
 
 // ------------------------------------------------------------------ prioritised replay
@@ -850,6 +877,98 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState 
   ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
 }
 
+// The environments' windows of a handle with n-step returns: the last n transitions of each, entry-major and
+// environment-minor, so that a wave's loads and stores of one field of one entry are contiguous.
+struct NWindow {
+  int n;                     // entries: transition c lies in entry c mod n
+  float* f;                  // [n][2 S + A + 1][N]: s | a as predicted | done | s2
+  double* r;                 // [n][N] the f64 rewards
+};
+
+// ddpg_actors_step_kernel's step with the ring write delayed by n - 1 transitions.  entry = c mod n for the handle's transition
+// count c (the host's: every environment steps on every step); emit = c >= n - 1.  The transition goes to window entry `entry`.
+// On an emitting step the row of the transition that began at u = c - n + 1, which lies in entry (entry + 1) mod n, goes to ring
+// slot (slot0 + i) mod cap: m = the first k in 1..n whose transition u + k - 1 is done, n if none; R = sum_{k<m} g_k r_{u+k} in
+// f64, ascending k, g_0 = 1 and g_{k+1} = g_k gamma64; the row is s_u | a_u | (f32) R | done_{u+m-1} | s2_{u+m-1} and
+// disc[slot] = (f32) g_m.  Nothing is summed across an episode's end; at n = 1 the row and gamma are ddpg_actors_step_kernel's.
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_nstep_kernel(ActState a, NWindow w, int first, int entry, int emit,
+                                                                        double gamma64, float* __restrict__ ring, int64_t slot0,
+                                                                        int64_t cap, float* __restrict__ disc,
+                                                                        float* __restrict__ pa, const float* __restrict__ max_pa) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * ACT_THREADS + threadIdx.x;
+  if (i >= a.N) return;
+  constexpr int S = Env::S, P = Env::P, A = Env::A;
+  constexpr int rowf = 2 * S + A + 2, W = 2 * S + A + 1;
+  const size_t N = (size_t)a.N;
+  double s[P];
+  int elapsed;
+  ga3c_actors::load_physics<P>(a.phys, a.elapsed, i, s, elapsed);
+  float av[A];
+  for (int j = 0; j < A; ++j) av[j] = first ? 0.f : a.action[(size_t)i * A + j];
+  float* obs = a.obs + (size_t)i * S;
+  float before[S], after[S];
+  for (int k = 0; k < S; ++k) before[k] = obs[k];
+  double reward;
+  int done;
+  Env::step(s, av, &elapsed, &reward, &done);
+  Env::observe(s, after);
+  for (int k = 0; k < S; ++k) obs[k] = after[k];
+  a.reward[i] = reward;
+  a.done[i] = done;
+  a.ep.ep_flag[i] = 0;
+  if (first) {
+    for (int j = 0; j < A; ++j) a.action[(size_t)i * A + j] = 0.f;
+    ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
+    return;
+  }
+  const int n = w.n;
+  {
+    float* e = w.f + (size_t)entry * W * N + i;
+    for (int k = 0; k < S; ++k) e[k * N] = before[k];
+    for (int j = 0; j < A; ++j) e[(S + j) * N] = av[j];
+    e[(S + A) * N] = done ? 1.f : 0.f;
+    for (int k = 0; k < S; ++k) e[(S + A + 1 + k) * N] = after[k];
+    w.r[(size_t)entry * N + i] = reward;
+  }
+  if (emit) {
+    const int oldest = entry + 1 == n ? 0 : entry + 1;
+    int j = oldest, last = oldest;
+    double R = 0.0, g = 1.0;
+    float d = 0.f;
+    for (int k = 0; k < n; ++k) {
+      R = R + g * w.r[(size_t)j * N + i];
+      g = g * gamma64;
+      d = w.f[((size_t)j * W + S + A) * N + i];
+      last = j;
+      if (d != 0.f) break;
+      j = j + 1 == n ? 0 : j + 1;
+    }
+    const int64_t slot = (slot0 + i) % cap;
+    float* row = ring + slot * rowf;
+    const float* eo = w.f + (size_t)oldest * W * N + i;
+    const float* el = w.f + (size_t)last * W * N + i;
+    for (int k = 0; k < S + A; ++k) row[k] = eo[k * N];
+    row[S + A] = (float)R;
+    row[S + A + 1] = d;
+    for (int k = 0; k < S; ++k) row[S + A + 2 + k] = el[(S + A + 1 + k) * N];
+    disc[slot] = (float)g;
+    if (pa) pa[slot] = *max_pa;
+  }
+  double total = a.total_reward[i] + reward;
+  long long length = a.total_length[i] + 1;
+  if (done) {                           // the record is per step, as ddpg_actors_step_kernel's
+    uint64_t draws = a.draws[i];
+    length += 1;
+    ga3c_actors::finish_episode<Env>(a.ep, i, a.seed, total, length, draws, s, elapsed);
+    a.draws[i] = draws;
+  }
+  a.total_reward[i] = total;
+  a.total_length[i] = length;
+  ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
+}
+
 // One workgroup: the step's finished episodes go to the episode ring in environment order (ga3c_actors.hpp).
 __global__ __launch_bounds__(ga3c_actors::SCAN_THREADS) void ddpg_actors_episodes_kernel(ActState a) {
   __shared__ int sep[ga3c_actors::SCAN_THREADS];
@@ -925,6 +1044,8 @@ struct DActors : ga3c_actors::ActorsCore {     // block: every device buffer of 
   int batch = 0;                        // rows of a train step ("batch" of actors_set; starts at max_batch)
   uint64_t draw_seed = 0, samples = 0;  // the draw of sample number n without priorities is u(draw_seed, n, row)
   bool started = false;                 // the first actor step is the environments' step(None): one flag for all of them
+  NWindow win{};                        // of a handle with n-step returns (in `block`); win.n = 0: none
+  int64_t count = 0;                    // transitions every environment has made: the c of the next step
 };
 
 // Twin critics of a handle (ga3c_ddpg_twin_create).  The arenas hold view.off[NVARS] floats while it lives.
@@ -935,6 +1056,13 @@ struct Twin {
   Layout view;                          // twin_view(L)
   Work2 w{};
   float* work_base = nullptr;
+};
+
+// n-step returns of a handle (ga3c_ddpg_nstep_create).  The environments' windows are the actors'.
+struct NStep {
+  int n = 1;
+  float* disc = nullptr;                // [capacity] the discount of the row in a slot: gamma^m, gamma for a row added by hand
+  float* used = nullptr;                // [max_batch] the discounts the last step's target took
 };
 
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
@@ -959,6 +1087,7 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   Per* per = nullptr;             // null: no priorities, and every path is the one it was without them
   DActors* actors = nullptr;      // null: no device actors
   Twin* twin = nullptr;           // null: one critic
+  NStep* nstep = nullptr;         // null: one-step rows, the scalar gamma everywhere
   std::vector<std::string> tnames;      // the target copies' names, by variable
 };
 
@@ -1074,6 +1203,11 @@ int make_noise(ga3c_ddpg* m, int mode, const float* given, Noise* nz) {
   return GA3C_OK;
 }
 
+// The discounts by slot for a step on `rows`: only ring rows have a slot; train, compute and the staged rows keep the scalar.
+const float* row_discounts(const ga3c_ddpg* m, const Rows& rows) {
+  return m->nstep && rows.base == m->ring ? m->nstep->disc : nullptr;
+}
+
 // The twin's step: smoothed targets from the smaller of two target critics, both critics stepped on them, and
 // only when t is a multiple of the delay the actor's step, at its own Adam count, and the soft update of all three nets.
 int enqueue_twin_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w) {
@@ -1084,7 +1218,8 @@ int enqueue_twin_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noi
   const dim3 grid(tiles(B)), grid2(tiles(B), 2), block(THREADS);
   const Pair<Layout> L{{m->L, tw.view}};
   hipLaunchKernelGGL(ddpg_twin_target_kernel, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma,
-                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, tw.sigma, tw.clip, tw.seed, (uint64_t)t, m->w, tw.w);
+                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, tw.sigma, tw.clip, tw.seed, (uint64_t)t, m->w, tw.w,
+                     row_discounts(m, rows), m->nstep ? m->nstep->used : nullptr);
   hipLaunchKernelGGL(ddpg_twin_critic_kernel, grid2, block, 0, m->st, L, (const float*)m->arena[0], rows, B, per_w, m->w, tw.w);
   const GradSrc gs = grad_src(m);
   const Pair<GradSrc> gs2{{gs, twin_grad_src(m)}};
@@ -1114,7 +1249,7 @@ int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& n
   const bool full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
   const dim3 grid(tiles(B)), block(THREADS);
   hipLaunchKernelGGL(ddpg_target_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[1], rows, B, c.gamma,
-                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, m->w);
+                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, m->w, row_discounts(m, rows), m->nstep ? m->nstep->used : nullptr);
   hipLaunchKernelGGL(ddpg_critic_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B,
                      (c.flags & GA3C_DDPG_LOSS_PAIRED) ? 1 : 0, per_w, m->w);
   const GradSrc gs = grad_src(m);
@@ -1260,6 +1395,15 @@ void per_free(ga3c_ddpg* m) {
   m->per = nullptr;
 }
 
+void nstep_free(ga3c_ddpg* m) {
+  NStep* ns = m->nstep;
+  if (!ns) return;
+  (void)hipFree(ns->disc); (void)hipFree(ns->used);
+  (void)hipGetLastError();
+  delete ns;
+  m->nstep = nullptr;
+}
+
 void dactors_free(ga3c_ddpg* m) {
   ga3c_actors::actors_free(m->actors);
   m->actors = nullptr;
@@ -1273,6 +1417,7 @@ void free_all(ga3c_ddpg* m) {
   dactors_free(m);
   per_free(m);
   twin_free(m);
+  nstep_free(m);
   vn::free_core(m);
   (void)hipFree(m->work_base);
   (void)hipFree(m->ring);
@@ -1339,6 +1484,13 @@ void per_fill(ga3c_ddpg* m, int64_t first, int64_t n) {
   if (!m->per || n < 1) return;
   hipLaunchKernelGGL(per_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->st, m->per->pa,
                      (const float*)m->per->max_pa, first, (int)n, (int64_t)m->cfg.replay_capacity);
+}
+
+// ... and, on a handle with n-step returns, the discount of a one-step row: gamma.
+void nstep_fill(ga3c_ddpg* m, int64_t first, int64_t n) {
+  if (!m->nstep || n < 1) return;
+  hipLaunchKernelGGL(nstep_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->st, m->nstep->disc, m->cfg.gamma, first,
+                     (int)n, (int64_t)m->cfg.replay_capacity);
 }
 
 // Sample number per->samples: B slots and their weights into per->slots / per->w (caller holds mu; the ring holds a row).
@@ -1543,6 +1695,7 @@ int ga3c_ddpg_replay_add(ga3c_ddpg* m, const float* s, const float* a, const flo
     std::lock_guard<std::mutex> lk(m->mu);
     CHK(ring_copy_in(m, m->h_add, n, hipMemcpyHostToDevice));
     per_fill(m, m->ring_total % m->cfg.replay_capacity, n);
+    nstep_fill(m, m->ring_total % m->cfg.replay_capacity, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->aev, m->st));
     m->ring_total += n;
@@ -1571,7 +1724,7 @@ int ga3c_ddpg_replay_add_gather(ga3c_ddpg* m, const int64_t* offsets, const floa
     const int64_t cap = m->cfg.replay_capacity, elems = (int64_t)n * m->rowf;
     hipLaunchKernelGGL(ddpg_ring_gather_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, m->st, m->reg_dev,
                        (const int64_t*)m->d_aoff, (const float*)m->d_ar, (const float*)m->d_aa, n, m->ring, m->ring_total % cap, cap,
-                       S, A);
+                       S, A, m->nstep ? m->nstep->disc : nullptr, m->cfg.gamma);
     per_fill(m, m->ring_total % cap, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->aev, m->st));
@@ -1670,6 +1823,16 @@ int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
     if (count != rows) return fail(GA3C_EINVAL, "%s holds %d floats, not %lld", name, rows, (long long)count);
     HIPCHK(hipStreamSynchronize(m->st));
     HIPCHK(hipMemcpy(out, per_w ? m->per->w : m->per->td, sizeof(float) * count, hipMemcpyDeviceToHost));
+    return GA3C_OK;
+  }
+  if (strcmp(name, "disc") == 0) {                  // the discounts the last step's target took, by row
+    HIPCHK(hipSetDevice(m->device));
+    std::lock_guard<std::mutex> tl(m->train_mu);
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->nstep) return fail(GA3C_ESTATE, "%s: the handle has no n-step returns (ga3c_ddpg_nstep_create)", name);
+    if (count != m->last_B) return fail(GA3C_EINVAL, "%s of the last step is %d floats, not %lld", name, m->last_B, (long long)count);
+    HIPCHK(hipStreamSynchronize(m->st));
+    HIPCHK(hipMemcpy(out, m->nstep->used, sizeof(float) * count, hipMemcpyDeviceToHost));
     return GA3C_OK;
   }
   for (int i = 0; i < NWORK; ++i)
@@ -1961,6 +2124,81 @@ int ga3c_ddpg_twin_destroy(ga3c_ddpg* m) {
   return GA3C_OK;
 }
 
+// ---- n-step returns
+
+namespace {
+int nstep_check(const ga3c_ddpg* m, const char* what) {
+  if (!m->nstep) return fail(GA3C_ESTATE, "%s: the handle has no n-step returns (ga3c_ddpg_nstep_create)", what);
+  return GA3C_OK;
+}
+}  // namespace
+
+int ga3c_ddpg_nstep_create(ga3c_ddpg* m, int32_t n) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (n < 1 || n > GA3C_DDPG_NSTEP_MAX) return fail(GA3C_EINVAL, "n %d outside [1,%d]", n, GA3C_DDPG_NSTEP_MAX);
+  if (!(m->cfg.flags & GA3C_DDPG_FUTURE_REWARD))
+    return fail(GA3C_ESTATE, "n-step returns need GA3C_DDPG_FUTURE_REWARD: without it y = r and no discount is read");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (m->nstep) return fail(GA3C_ESTATE, "the handle has n-step returns already");
+  if (m->actors) return fail(GA3C_ESTATE, "the handle has device actors: their windows are sized at actors_create, so n-step comes first");
+  NStep* ns = new (std::nothrow) NStep();
+  if (!ns) return fail(GA3C_EINVAL, "out of host memory");
+  m->nstep = ns;
+  ns->n = n;
+  const size_t cap = (size_t)m->cfg.replay_capacity, B = (size_t)m->cfg.max_batch;
+  auto build = [&]() -> int {
+    CHK(vn::dalloc(&ns->disc, cap)); CHK(vn::dalloc(&ns->used, B));
+    HIPCHK(hipMemsetAsync(ns->used, 0, sizeof(float) * B, m->st));
+    nstep_fill(m, 0, (int64_t)cap);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->st));
+    return GA3C_OK;
+  };
+  const int rc = build();
+  if (rc != GA3C_OK) nstep_free(m);
+  return rc;
+}
+
+int ga3c_ddpg_nstep_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  CHK(nstep_check(m, "nstep_destroy"));
+  if (m->actors) return fail(GA3C_ESTATE, "nstep_destroy: the handle's device actors hold its windows (ga3c_ddpg_actors_destroy first)");
+  HIPCHK(hipStreamSynchronize(m->st));
+  nstep_free(m);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_nstep_get(ga3c_ddpg* m, float* disc, int64_t count) {
+  if (!m || !disc) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  CHK(nstep_check(m, "nstep_get"));
+  if (count != m->cfg.replay_capacity) return fail(GA3C_EINVAL, "disc holds %d floats, not %lld", m->cfg.replay_capacity, (long long)count);
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipMemcpy(disc, m->nstep->disc, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost));
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_nstep_set(ga3c_ddpg* m, const float* disc, int64_t count) {
+  if (!m || !disc) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  CHK(nstep_check(m, "nstep_set"));
+  if (count != m->cfg.replay_capacity) return fail(GA3C_EINVAL, "disc holds %d floats, not %lld", m->cfg.replay_capacity, (long long)count);
+  for (int64_t i = 0; i < count; ++i)
+    if (!(disc[i] >= 0.f && disc[i] <= 1.f)) return fail(GA3C_EINVAL, "disc[%lld] = %g outside [0,1]", (long long)i, disc[i]);
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipMemcpy(m->nstep->disc, disc, sizeof(float) * (size_t)count, hipMemcpyHostToDevice));
+  return GA3C_OK;
+}
+
 // ---- device actors
 
 using DEnv = ga3c_actors::PendulumBounded;
@@ -1987,6 +2225,8 @@ int ga3c_ddpg_actors_create(ga3c_ddpg* m, int32_t n, int32_t updates, int64_t se
   a->batch = m->cfg.max_batch;
   a->draw_seed = (uint64_t)seed;
   const size_t Nn = (size_t)n, S = DEnv::S, P = DEnv::P, A = DEnv::A;
+  const size_t wn = m->nstep ? (size_t)m->nstep->n : 0;      // n-step returns: every environment's window of n transitions
+  a->win.n = (int)wn;
   size_t total = 0;
   m->actors = a;
   if (!ga3c_actors::carve_block(a, 2, &total, [&](auto carve) {
@@ -1995,6 +2235,7 @@ int ga3c_ddpg_actors_create(ga3c_ddpg* m, int32_t n, int32_t updates, int64_t se
         carve(&e.ep_reward, Nn); carve(&e.ep_length, Nn); carve(&e.counts, 2);
         carve(&e.ring_ep_reward, (size_t)e.ep_cap); carve(&e.ring_ep_length, (size_t)e.ep_cap);
         carve(&a->slots, (size_t)m->cfg.max_batch);
+        carve(&a->win.f, wn * (2 * S + A + 1) * Nn); carve(&a->win.r, wn * Nn);
       }) ||
       !ga3c_actors::initial_physics<DEnv>(d.seed, Nn, d.phys, d.draws)) {
     (void)hipGetLastError();
@@ -2042,13 +2283,21 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
       hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(N)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0],
                          Input{reinterpret_cast<const char*>(d.obs), nullptr, 4 * (int64_t)DEnv::S}, N, nz, d.action);
     }
-    hipLaunchKernelGGL(ddpg_actors_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
-                       first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
-                       m->per ? (const float*)m->per->max_pa : nullptr);
+    const int wn = a->win.n;            // n-step returns: a row leaves the window from transition n - 1 on
+    const bool emit = !first && a->count >= wn - 1;
+    if (wn)
+      hipLaunchKernelGGL(ddpg_actors_nstep_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
+                         a->win, first, (int)(a->count % wn), emit ? 1 : 0, (double)m->cfg.gamma, m->ring, m->ring_total % cap, cap,
+                         m->nstep->disc, m->per ? m->per->pa : nullptr, m->per ? (const float*)m->per->max_pa : nullptr);
+    else
+      hipLaunchKernelGGL(ddpg_actors_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
+                         first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
+                         m->per ? (const float*)m->per->max_pa : nullptr);
     hipLaunchKernelGGL(ddpg_actors_episodes_kernel, dim3(1), dim3(ga3c_actors::SCAN_THREADS), 0, m->st, d);
     HIPCHK(hipGetLastError());
     a->started = true;
-    if (!first) m->ring_total += N;
+    if (!first) ++a->count;
+    if (emit) m->ring_total += N;
     if (train && ring_size(m) > B) {    // ThreadReplay.sample's rule: a batch is drawn from MORE rows than it holds
       for (int k = 0; k < a->updates; ++k) {
         CHK(make_noise(m, noise_mode, noise, &nz));
@@ -2121,6 +2370,12 @@ int dactors_access(ga3c_ddpg* m, const char* name, void* out, const void* in, in
     CHK(sized(8));
     if (out) *static_cast<int64_t*>(out) = (int64_t)a->draw_seed;
     else a->draw_seed = (uint64_t)*static_cast<const int64_t*>(in);
+    return GA3C_OK;
+  }
+  if (nm == "nstep" || nm == "nstep_count") {       // the window's entries (1 without n-step returns) and the c of the next step
+    if (!out) return fail(GA3C_EINVAL, "%s is read only", name);
+    if (nm == "nstep") { CHK(sized(4)); *static_cast<int32_t*>(out) = a->win.n ? a->win.n : 1; }
+    else { CHK(sized(8)); *static_cast<int64_t*>(out) = a->count; }
     return GA3C_OK;
   }
   if (nm == "slots") {                  // the last draw

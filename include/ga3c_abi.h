@@ -739,6 +739,33 @@ int ga3c_ddpg_actors_episodes(ga3c_ddpg* net, double* total_reward, int64_t* tot
 int ga3c_ddpg_actors_get(ga3c_ddpg* net, const char* name, void* out, int64_t bytes);
 int ga3c_ddpg_actors_set(ga3c_ddpg* net, const char* name, const void* in, int64_t bytes);
 
+/* ---- n-step returns of a DDPG handle's device actors (Config.DDPG_NSTEP; tests/nstep_oracle.py is the same
+ * statement in numpy).  Attached to a created handle before its device actors, as the priorities and the twin critics are; a
+ * handle without them runs what it ran before.  State: disc[capacity], the discount of the row in each ring slot (gamma at
+ * create), and, in the actors' block, every environment's window of its last n transitions.
+ * With c = 0, 1, .. the transitions every environment has made since actors_create (step(None) makes none): a step with
+ * c < n - 1 writes nothing to the ring and `total` does not move; every later step writes one row per environment as before,
+ * for the transition that began at u = c - n + 1: m = the smallest k in 1..n with done_{u+k-1}, n if none;
+ * R = sum_{k<m} g_k r_{u+k} in f64 with ascending k, g_0 = 1, g_{k+1} = g_k (f64) gamma; the row is
+ * s_u | a_u | (f32) R | done_{u+m-1} | s2_{u+m-1} and disc[slot] = (f32) g_m.  The last n - 1 transitions of an episode so leave
+ * with shortened horizons and done = 1, during the first n - 1 steps of the next one; nothing is summed across an episode's
+ * end; the last n - 1 transitions before actors_destroy are never written.  At n = 1 the rows are the ones a handle without
+ * n-step returns writes and disc stays gamma.  Episode records, reward, done and the train rule are per step and unchanged.
+ * A train step whose rows are ring slots (train_replay, train_prioritized, time_*, actors_run) takes y = r + disc[slot] q' on
+ * rows that are not done; train and compute, whose rows have no slot, keep the scalar gamma.  replay_add* write disc[slot] =
+ * gamma for their rows.  fetch also knows "disc" [B], the discounts the last step's target took (GA3C_ESTATE without n-step);
+ * actors_get knows "nstep" i32 (1 without) and "nstep_count" i64, the c of the next step, both get only.
+ * create: GA3C_EINVAL for n outside [1, GA3C_DDPG_NSTEP_MAX]; GA3C_ESTATE on a second create, on a handle that has device
+ * actors (their windows are sized at actors_create) and on one without GA3C_DDPG_FUTURE_REWARD.
+ * destroy: GA3C_ESTATE while the actors live; also done by ga3c_ddpg_destroy.  Checkpoints carry neither disc nor windows, as
+ * they carry no ring.
+ * get / set: for tests; count must be replay_capacity; set refuses a NaN and a value outside [0,1] (GA3C_EINVAL). */
+#define GA3C_DDPG_NSTEP_MAX 16
+int ga3c_ddpg_nstep_create(ga3c_ddpg* net, int32_t n);
+int ga3c_ddpg_nstep_destroy(ga3c_ddpg* net);
+int ga3c_ddpg_nstep_get(ga3c_ddpg* net, float* disc, int64_t count);
+int ga3c_ddpg_nstep_set(ga3c_ddpg* net, const float* disc, int64_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@ synchronised timing (ga3c_ddpg_time_resident: HIP events around `iters` back-to-
 mode 0 = predict, 1 = train_replay).  Median and min over rounds, one JSON line per configuration.  Launches per call:
 predict 1, train_replay 5 (6 with USE_GRAD_CLIP).  --twin: the handle has twin critics (DDPG_TWIN) and a step that
 is not a policy step is 3 launches (4), so the time is the mean over --delay steps; --delay 1 times the policy step.
-usage: python tools/ddpg_step.py [--predict 1 128] [--train 64 128 256] [--rounds 5] [--iters 200] [--clip] [--twin [--delay N]]"""
+--nstep N > 1: the handle has n-step state (DDPG_NSTEP) and the target kernel reads a discount per ring slot.
+usage: python tools/ddpg_step.py [--predict 1 128] [--train 64 128 256] [--rounds 5] [--iters 200] [--clip] [--twin [--delay N]]
+       [--nstep N]"""
 import argparse
 import json
 import os
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--twin", action="store_true")
     ap.add_argument("--delay", type=int, default=2)
+    ap.add_argument("--nstep", type=int, default=1)
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
@@ -34,6 +37,7 @@ def main():
     Config.USE_GRAD_CLIP = args.clip
     if args.twin:
         Config.DDPG_TWIN, Config.DDPG_CRITIC_LOSS, Config.DDPG_POLICY_DELAY = True, 'paired', args.delay
+    Config.DDPG_NSTEP = args.nstep
     S, A = args.state_dim, args.actions
     maxB = max(args.predict + args.train)
     net = Network("gpu:0", "ddpg_step", A, (S,), max_batch=maxB, replay_capacity=max(maxB, 1024))
@@ -52,7 +56,7 @@ def main():
         v = sorted(v)
         print(json.dumps({"step": "train_replay" if mode else "predict", "rows": b, "state_dim": S, "actions": A,
                           "grad_clip": bool(args.clip), "launches": (6 if args.clip else 5) if mode else 1,
-                          "twin": bool(args.twin), "policy_delay": args.delay if args.twin else None,
+                          "nstep": args.nstep, "twin": bool(args.twin), "policy_delay": args.delay if args.twin else None,
                           "launches_off_policy_step": ((4 if args.clip else 3) if mode else 1) if args.twin else None,
                           "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2), "rounds": args.rounds,
                           "iters": args.iters}), flush=True)

@@ -6,10 +6,10 @@ the host reads a row count per step), median and min over rounds, one JSON line 
 PPS of the status line of `_train.sh GAME=<game> AGENTS=16` (profiles/device_agents_step.txt, device_agents_pendulum.txt).
 Pendulum's environments run in lockstep: one train step of N (TIME_MAX + 1) rows every TIME_MAX actor steps.
 --ddpg (with --game Pendulum-v0; Config.DEVICE_DDPG, ga3c_ddpg_actors_run): the DDPG handle's actors, --updates
-train steps of --batch ring rows after every actor step, --prioritized for the draw by priority; the call waits once, at its
-end (profiles/device_agents_ddpg.txt).
+train steps of --batch ring rows after every actor step, --prioritized for the draw by priority, --nstep N for n-step returns
+(Config.DDPG_NSTEP; profiles/nstep_step.txt); the call waits once, at its end (profiles/device_agents_ddpg.txt).
 usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]
-       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000]]"""
+       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1]]"""
 import argparse
 import json
 import os
@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--updates", type=int, default=1, help="--ddpg: train steps per actor step")
     ap.add_argument("--prioritized", action="store_true", help="--ddpg: draw by priority (paired critic loss)")
     ap.add_argument("--capacity", type=int, default=1000000, help="--ddpg: ring slots")
+    ap.add_argument("--nstep", type=int, default=1, help="--ddpg: steps of the returns the actors write (1..16)")
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
@@ -43,6 +44,7 @@ def main():
         from NetworkDDPG import Network
         num_actions, state_dim = 1, (3,)
         Config.PRIORITIZED_REPLAY = args.prioritized
+        Config.DDPG_NSTEP = args.nstep
         if args.prioritized:
             Config.DDPG_CRITIC_LOSS = 'paired'
     elif args.game == "Pendulum-v0":
@@ -73,7 +75,8 @@ def main():
             net.actors_episodes()
         rates.sort()
         per_step_us = 1e6 * n / rates[len(rates) // 2]
-        extra = {"ddpg": True, "batch": args.batch, "updates": args.updates, "prioritized": args.prioritized} if args.ddpg else {}
+        extra = ({"ddpg": True, "batch": args.batch, "updates": args.updates, "prioritized": args.prioritized, "nstep": args.nstep}
+                 if args.ddpg else {})
         print(json.dumps({**extra, "game": args.game, "agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,
                           "agent_steps_per_s_median": round(rates[len(rates) // 2]), "agent_steps_per_s_min": round(rates[0]),
                           "agent_steps_per_s_max": round(rates[-1]), "actor_step_us_median": round(per_step_us, 1),
