@@ -242,6 +242,10 @@ constexpr int C2F_QUARTER_MAX_B = 192;
 // Measured, 1 / 2 / 3 / 4 lanes at 128 rows: threshold 3 -> 5.80 / 7.51 / 9.07 / 10.53 M predictions/s,
 // 2 -> 5.81 / 7.79 / 9.01 / 10.60, 1 -> 5.55 / 7.78 / 8.98 / 10.59
 constexpr int D1F_FRAG_MIN_B = 64, D1F_FRAG_LANES = 2;
+// The vector-ALU dense1 (dense1_fwd_valu_kernel: no LDS and no MFMA either, so it leaves the conv stack beside it its matrix
+// pipe; same bits) was built to take the fragment kernel's place there and lost at every batch it was tried at: alone 8.5 us
+// against 6.3 at 128 rows (8.1 against 6.2 at 64), beside a conv stack 24 us against 14, two lanes 6.1 M predictions/s
+// against 8.2-8.5 (profiles/README.md, "dense1 on the vector ALU").  No rule picks it; GA3C_D1F_VALU=1 does, for every step.
 // The fused conv backward (conv2_dw + conv2_dx + conv1_dw in one launch, one workgroup per CU) takes CONV_BWD_MIN_B ..
 // CONV_BWD_MAX_B rows: beyond one round the tail of the second costs more than the fusion saves, and below, the split
 // launches are faster (uint8 train step 44.7 / 45.6 / 48.7 / 50.3 / 55.6 us against 49.3 / 50.1 / 51.5 / 52.9 / 56.4 at
@@ -360,6 +364,7 @@ struct ga3c_net {
   bool time_predictions = false;       // GA3C_TIME_PREDICTIONS=1: timing events around every prediction step (GA3C_STAT_PREDICT_GPU_NS)
   std::atomic<int> predict_inflight{0};   // prediction calls in flight (D1F_FRAG_LANES)
   bool d1f_tile = true;                // LDS-tiled dense1 forward where its grid is one round (GA3C_D1F_TILE=0: never)
+  bool d1f_valu = false;               // GA3C_D1F_VALU=1: every dense1 forward of every step on the vector ALU (tests, A/B)
   bool graphs = false;                 // GA3C_GRAPHS=1: prediction steps replayed as hipGraphs.  Off by default: on ROCm 7.2 a
                                        // 4-kernel graph launch costs ~6 us MORE per step than four plain launches and
                                        // two lanes lose 10 % of their overlap (profiles/README.md, round 1)
@@ -423,10 +428,19 @@ bool is_pinned(const void* p) {
   return at.type == hipMemoryTypeHost;
 }
 
+void launch_dense1_fwd_valu(const float* flat, const float* pk, float* part, int B, int ks, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  hipExtLaunchKernelGGL(dense1_fwd_valu_kernel<D1V_DEPTH>, dim3(dense1_fwd_valu_blocks(B, ks)), dim3(256), 0, st, e0, e1, 0, flat, pk, part, B, ks);
+}
+
 // dense1 forward: the LDS-tiled kernel while its grid is one round of workgroups (one workgroup per CU: its LDS image
-// is 120-145 KB), the register-fragment kernel beyond
+// is 120-145 KB), the register-fragment kernel beyond; prefer_frag: an LDS-free kernel (beside another lane's conv stack)
 int launch_dense1_fwd(ga3c_net* net, const float* flat, const float* pk, float* part, int B, int ks, hipStream_t st,
-                      hipEvent_t e0, hipEvent_t e1, bool prefer_frag = false) {
+                      hipEvent_t e0, hipEvent_t e1, bool prefer_frag = false, bool allow_valu = true) {
+  if (allow_valu && net->d1f_valu) {
+    launch_dense1_fwd_valu(flat, pk, part, B, ks, st, e0, e1);
+    HIPCHK(hipGetLastError());
+    return GA3C_OK;
+  }
   const int max_steps = (KSTEPS_DENSE + ks - 1) / ks;
   const int mt = B <= 128 ? 1 : 2;
   const size_t lds = (size_t)d1f_lds_floats(mt, max_steps) * sizeof(float);
@@ -1616,6 +1630,7 @@ int ga3c_net_create(const ga3c_net_config* cfg, ga3c_net** out) {
   for (auto& c : net->stream_busy) c.store(0);
   net->graphs = getenv("GA3C_GRAPHS") != nullptr;
   if (const char* e = getenv("GA3C_D1F_TILE")) net->d1f_tile = atoi(e) != 0;
+  if (const char* e = getenv("GA3C_D1F_VALU")) net->d1f_valu = atoi(e) != 0;
   if (const char* e = getenv("GA3C_TIME_PREDICTIONS")) net->time_predictions = atoi(e) != 0;
   if (const char* e = getenv("GA3C_OFFSETS_IN_ARGS")) net->offsets_in_args = atoi(e) != 0;
   for (const void* fn : {reinterpret_cast<const void*>(&conv_bwd_kernel<true, false>), reinterpret_cast<const void*>(&conv_bwd_kernel<false, false>),
@@ -2870,7 +2885,10 @@ int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32
                             t.ev0, t.ev1, 0, (const void*)t.f.xu8, net->theta_pk[net->latest] + PK_W1F, th + OFF_B1, net->theta_pk[net->latest] + PK_W2F, th + OFF_B2, t.f.n1, t.f.n2, B,
                             (const int64_t*)nullptr, SrcOffsets{}, (uint8_t*)nullptr);
     } else if (k == "dense1_fwd" || k == "dense1_fwd_frag") {
-      CHK(launch_dense1_fwd(net, t.f.n2, net->theta_pk[net->latest], t.f.part, B, dense_ks(B), t.st, t.ev0, t.ev1, k == "dense1_fwd_frag"));
+      CHK(launch_dense1_fwd(net, t.f.n2, net->theta_pk[net->latest], t.f.part, B, dense_ks(B), t.st, t.ev0, t.ev1, k == "dense1_fwd_frag",
+                            k != "dense1_fwd_frag"));
+    } else if (k == "dense1_fwd_valu") {
+      launch_dense1_fwd_valu(t.f.n2, net->theta_pk[net->latest], t.f.part, B, dense_ks(B), t.st, t.ev0, t.ev1);
     } else if (k == "conv1_dw") {
       TL(conv1_dw_kernel<false>, dim3(conv1_dw_blocks(B)), (const void*)t.f.x, t.dn1, t.slab1, B * 7);
     } else if (k == "conv2_dw") {
@@ -2971,7 +2989,8 @@ int ga3c_net_fetch(ga3c_net* net, const char* name, float* out, int64_t count) {
   struct Ent { const char* n; const float* p; int64_t cap; };
   const Ent ents[] = {{"n1", t.f.n1, B * N1S}, {"n2", t.f.n2, B * FLAT}, {"d1", t.f.d1, B * HID}, {"z", t.f.z, B * net->npc},
                       {"p", t.f.p, B * A}, {"v", t.f.v, B}, {"dz", t.dz, B * net->npc}, {"dv", t.dv, B},
-                      {"dd1", t.dd1, B * HID}, {"dn2", t.dn2, B * FLAT}, {"dn1", t.dn1, B * N1S}, {"x", t.f.x, B * XS}};
+                      {"dd1", t.dd1, B * HID}, {"dn2", t.dn2, B * FLAT}, {"dn1", t.dn1, B * N1S}, {"x", t.f.x, B * XS},
+                      {"part", t.f.part, 22 * B * HID}};   // dense1's partial slabs [dense_ks(b)][b][256] of the last step (alloc_fwd)
   for (const Ent& e : ents) {
     if (strcmp(e.n, name) == 0) {
       if (count < 1 || count > e.cap) return fail(GA3C_EINVAL, "count %lld outside [1,%lld] for '%s'", (long long)count, (long long)e.cap, name);

@@ -896,6 +896,95 @@ __host__ inline int dense1_fwd_blocks(int B, int ks_total, int mt) {
   return 8 * nrow * ((ks_total * 2 + 7) / 8);
 }
 
+// ---- the same partial products on the VECTOR ALU: no MFMA and no LDS, so a wave of it takes nothing from the matrix pipe
+// of the conv stack it shares a SIMD with.  A wave = (8 rows, 64 columns, one K slice), the lane is the column; a
+// workgroup's four waves are the four column quarters of one row group.  The row operand is wave-uniform: 16 floats of a
+// row and step are one 64-byte scalar load and feed the FMAs as SGPR pairs; the weights are the lane's 64 bytes of the
+// packed Wd.  The f32 MFMA is bit for bit a k-ordered fmaf chain, so the bits are the two kernels' above: per output an
+// even chain over k = 16 s + {0, 4, 8, 12, 2, 6, 10, 14} and an odd one over {1, 5, 9, 13, 3, 7, 11, 15} (what the MFMAs
+// t = 0, 2 and t = 1, 3 of a step sum, lane group by lane group), the two as the halves of one v_pk_fma_f32, added at the
+// end.  Weights: D steps in a fenced_ring.  Rows: a step's 8 x 16 floats do not fit the SGPRs beside the next step's, and
+// scalar loads return out of order, so a wait for one is a wait for all in flight (lgkmcnt(0)); the rows therefore go
+// through the SGPRs two at a time, the next pair requested behind the wait for the current one and in flight under its 16
+// FMAs.  That is one exposed scalar round trip per 16 FMAs, and it is what the kernel's time is: 8.5 us alone at 128 rows
+// against the fragment kernel's 6.3, 24 us beside a conv stack against 14.  No launch rule picks it (GA3C_D1F_VALU=1
+// does; profiles/README.md, "dense1 on the vector ALU").
+// Grid as dense1_fwd_kernel's: block id -> (xcd = id % 8, j = id / 8), all row groups of a slice on one XCD.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int D1V_ROWS = 8, D1V_DEPTH = 2;                // rows of a wave; steps of weights in the ring
+__device__ __forceinline__ void pin_scalar(f32x16& v) {   // as pin(), for a value that lives in SGPRs: one element names the load
+  float t = v[0];
+  asm volatile("" : "+s"(t));
+  v[0] = t;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void dense1_fwd_valu_kernel(const float* __restrict__ flat, const float* __restrict__ pk,
+                                                              float* __restrict__ part, int B, int ks_total) {
+  constexpr int R = D1V_ROWS;
+  static_assert(R % 4 == 0, "row pairs alternate between the two SGPR buffers: a step's last pair must leave buffer 0 free");
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nrow = (B + R - 1) / R;
+  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+  const int rb = j % nrow, ks = (j / nrow) * 8 + xcd;
+  if (ks >= ks_total) return;
+  const int m0 = rb * R, n = wv * 64 + lane;
+  const int s0 = (ks * KSTEPS_DENSE) / ks_total, s1 = ((ks + 1) * KSTEPS_DENSE) / ks_total;
+  int roff[R];                                             // a row past B reads the last valid row and is not stored
+#pragma unroll
+  for (int r = 0; r < R; ++r) roff[r] = (m0 + r < B ? m0 + r : B - 1) * FLAT;
+  const float* wp = pk + (size_t)n * 16;
+  f32x2 acc[R];                                            // [even chain, odd chain]
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = (f32x2){0.f, 0.f};
+  f32x4 w[D][4];
+  auto fetch = [&](int slot, int s) {
+    const int sc = s < s1 ? s : s1 - 1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[slot][q] = ld4(wp + (size_t)sc * HID * 16 + 4 * q);
+  };
+  f32x16 a[2][2];                                          // two SGPR buffers of two rows
+  auto rows = [&](int buf, int pair, int s) {
+    a[buf][0] = *reinterpret_cast<const f32x16*>(flat + roff[2 * pair] + 16 * s);
+    a[buf][1] = *reinterpret_cast<const f32x16*>(flat + roff[2 * pair + 1] + 16 * s);
+  };
+  int sa = s0;                                             // the step the ring is at
+  rows(0, 0, s0);
+  auto step = [&](int d) {
+    const int sn = sa + 1 < s1 ? sa + 1 : s1 - 1;
+#pragma unroll
+    for (int pair = 0; pair < R / 2; ++pair) {
+      const int buf = pair & 1;
+      pin_scalar(a[buf][0]);
+      pin_scalar(a[buf][1]);
+      if (pair + 1 < R / 2) rows(buf ^ 1, pair + 1, sa);
+      else rows(0, 0, sn);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int r = 0; r < 2; ++r) {
+            const f32x2 av = {a[buf][r][4 * q + 2 * h], a[buf][r][4 * q + 2 * h + 1]};
+            const f32x2 wv2 = {w[d][q][2 * h], w[d][q][2 * h + 1]};
+            acc[2 * pair + r] = __builtin_elementwise_fma(av, wv2, acc[2 * pair + r]);
+          }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    ++sa;
+  };
+  fenced_ring<D>(s0, s1, fetch, step);
+  float* out = part + ((size_t)ks * B) * HID + n;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (m0 + r < B) out[(size_t)(m0 + r) * HID] = acc[r][0] + acc[r][1];
+}
+__host__ inline int dense1_fwd_valu_blocks(int B, int ks_total) {
+  return 8 * ((B + D1V_ROWS - 1) / D1V_ROWS) * ((ks_total + 7) / 8);
+}
+
 // ------------------------------------------------------------------ heads (+ loss)
 // One wave per sample: d1 = relu(sum_ks part + bd); z = d1 Wp + bp; v = d1 Wv + bv; softmax;
 // TRAIN adds the A3C loss terms, the head gradients dz, dv and the gradient that
