@@ -8,11 +8,12 @@
 //
 // Kernels (all f32, one workgroup of 448 threads per 16-row tile, weights through L2; the tile's layout in LDS, dense_fwd,
 // load_input_tile and the fixed-order block_sum are ga3c_tile.hpp's):
-//   ddpg_target_kernel   steps 1-2: actor_target and critic_target on s2, y = r or r + gamma q'
-//   ddpg_critic_kernel   step 3's forward and backward on (s, a): q, dq (either loss form) and the deltas, to HBM
-//   ddpg_wgrad_kernel    one thread per element of a net's trainable variables sums its gradient over the rows in row order
-//                        (no atomics); FUSED applies the optimizer step and the soft update of the element's target copy
-//   ddpg_update_kernel   (GA3C_DDPG_GRAD_CLIP) one block per critic variable: tf.clip_by_norm, the step, the soft update
+// (<NC>: compiled for a handle with one critic and for one with two, below; the critic is blockIdx.y, or blockIdx.x / 10)
+//   ddpg_target_kernel<NC>  steps 1-2: actor_target and critic_target on s2, y = r or r + gamma q'
+//   ddpg_critic_kernel<NC>  step 3's forward and backward on (s, a): q, dq (either loss form) and the deltas, to HBM
+//   ddpg_wgrad_kernel<NC>   one thread per element of a net's trainable variables sums its gradient over the rows in row order
+//                           (no atomics); FUSED applies the optimizer step and the soft update of the element's target copy
+//   ddpg_update_kernel<NC>  (GA3C_DDPG_GRAD_CLIP) one block per critic variable: tf.clip_by_norm, the step, the soft update
 //   ddpg_actor_kernel    steps 4-5: actor(s) + noise, dq/da of the updated critic there, the actor's deltas
 //   ddpg_predict_kernel  the online actor alone
 //   ddpg_ring_gather_kernel  rows of the registered transport into ring slots
@@ -24,24 +25,24 @@
 //   per_update_kernel     one workgroup: pa[slot] = (|y - q| + eps)^alpha from the critic kernel's y and q
 // A prioritised step is 8 launches (9 with clipping) and draws its own rows: no host draw, no stamp, nothing to lose.
 // Device actors (ga3c_ddpg_actors_create, Config.DEVICE_DDPG; tests/ddpg_actors_oracle.py is the same statement):
-//   ddpg_actors_step_kernel<Env>   one thread per environment: the step, its transition into the ring, the episode record
+//   ddpg_actors_step_kernel<Env>   one thread per environment: the step (actor_step, the one statement of it), its transition
+//                                  into the ring, the episode record
 //   ddpg_actors_episodes_kernel    one workgroup: this step's episode records into the episode ring, environment order
 //   ddpg_uniform_slots_kernel      a train step's rows without priorities: a stratified draw in integers, on the device
 // Twin critics (ga3c_ddpg_twin_create, Config.DDPG_TWIN; tests/td3_oracle.py is the same statement):
-//   ddpg_twin_target_kernel    actor_target, the smoothed and clipped target action, both target critics, y from their min
-//   ddpg_twin_critic_kernel    ddpg_critic_kernel's step for critic blockIdx.y
-//   ddpg_twin_wgrad_kernel     ddpg_wgrad_kernel's elements for critic blockIdx.y
-//   ddpg_twin_update_kernel    ddpg_update_kernel's blocks for both critics' variables
+//   ddpg_target_kernel<2>      actor_target, the smoothed and clipped target action, both target critics, y from their min
+//   ddpg_critic_kernel<2>, ddpg_wgrad_kernel<2>, ddpg_update_kernel<2>      both critics' steps, elements and variables at once
 // A twin step is 3 launches (4 with clipping); a policy step, every policy_delay-th, adds ddpg_actor_kernel and the actor's
-// ddpg_wgrad_kernel.  Critic 2's variables lie behind the 26 in every arena and are read through a second Layout whose
-// critic entries name them (twin_view), so the device functions of one critic serve both.
+// ddpg_wgrad_kernel<1>.  Critic 2's variables lie behind the 26 in every arena and are read through a second Layout whose
+// critic entries name them (twin_view), so the device functions of one critic serve both; the host's enqueue_step_nc is one
+// rule for both handles, a plain step being a twin's at delay 1.
 // An actor step is predict + 2 launches; every launch argument is known to the host, which waits once per actors_run.
 // n-step returns (ga3c_ddpg_nstep_create, Config.DDPG_NSTEP; tests/nstep_oracle.py is the same statement):
-//   ddpg_actors_nstep_kernel<Env>  ddpg_actors_step_kernel's step, the transition into the environment's window of n, and from
+//   ddpg_actors_nstep_kernel<Env>  actor_step too, the transition into the environment's window of n, and from
 //                                  the n-th transition on one ring row per step: the n-step return of the oldest entry, cut at
 //                                  an episode's end, and its discount gamma^m into disc[slot]
 //   nstep_fill_kernel              disc[slot] = gamma for rows added by hand
-// The two target kernels read disc[slot] where a step's rows are ring slots of such a handle, the scalar gamma otherwise.
+// The target kernel reads disc[slot] where a step's rows are ring slots of such a handle, the scalar gamma otherwise.
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -132,8 +133,8 @@ inline Layout twin_view(const Layout& L) {
   return V;
 }
 
-template <class T>
-struct Pair { T v[2]; };       // a kernel argument per critic, chosen by blockIdx.y
+template <class T, int NC>
+struct PerCritic { T v[NC]; };     // a kernel argument per critic of a handle with NC of them
 
 // Where a step's rows lie: row i is `rowf` floats at base + (idx ? idx[i] : i) * rowf: s[S] | a[A] | r | done | s2[S].
 struct Rows {
@@ -147,28 +148,26 @@ struct Noise {         // by value in the kernel arguments: nothing to copy
   int wrap;            // GA3C_DDPG_NOISE_NONE: check_bounds(turnaround) on the output
 };
 
-// Per-row buffers of the train workspace, row-major [B][width].
+// What one critic's step writes.
+struct CriticRows {
+  float *q, *dq;                               // [B]
+  float *xh1, *c1, *dn1, *dh1;                 // [B,400]
+  float *c2, *dt;                              // [B,300]
+};
+
+// Per-row buffers of the train workspace, row-major [B][width].  Those marked "twin" exist while the handle has twin critics
+// (work_table below) and are null otherwise.
 struct Work {
-  float *y, *qt, *q, *dq;                      // [B]
-  float *c_x, *c_a;                            // [B,S] [B,A]: the critic step's inputs
-  float *c_xh1, *c_c1, *c_dn1, *c_dh1;         // [B,400]
-  float *c_c2, *c_dt;                          // [B,300]
+  float *y, *qt;                               // [B]
+  float *c_x, *c_a;                            // [B,S] [B,A]: the critic step's inputs, kept once for every critic
+  CriticRows c[2];                             // c[1] twin: critic 2's
+  float *qt1, *qt2;                            // [B] twin: the two target critics' q'
+  float *t_eps, *t_a;                          // [B,A] twin: the smoothing noise and the target action it gives
   float *a_xh1, *a_a1, *a_dn1, *a_dh1;         // [B,400]
   float *a_xh2, *a_a2, *a_dn2, *a_dh2;         // [B,300]
   float *a_out, *a_noisy, *g, *dout;           // [B,A]
   float* qstat;                                // {max q, mean q}
 };
-
-// ... and the twin's: the target step's rows and critic 2's copy of every c_* buffer.
-struct Work2 {
-  float *qt1, *qt2, *q2, *dq2;                 // [B]
-  float *t_eps, *t_a;                          // [B,A]: the smoothing noise and the target action it gives
-  float *c2_xh1, *c2_c1, *c2_dn1, *c2_dh1;     // [B,400]
-  float *c2_c2, *c2_dt;                        // [B,300]
-};
-
-// What one critic's step writes; x, a null: the inputs are not kept.
-struct CriticRows { float *q, *dq, *x, *a, *xh1, *c1, *dn1, *dh1, *c2, *dt; };
 
 struct Opt {
   float *theta, *target, *sa, *sb, *grad;
@@ -305,96 +304,81 @@ __device__ __forceinline__ float row_discount(const float* __restrict__ disc, fl
   return g;
 }
 
-__global__ __launch_bounds__(THREADS) void ddpg_target_kernel(Layout L, const float* __restrict__ thT, Rows src, int B, float gamma,
-                                                              int future, Work w, const float* __restrict__ disc,
-                                                              float* __restrict__ used) {
-  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
-  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
-  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
-  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
-  __shared__ float qv[TILE];
-  const int S = L.S, A = L.A;
-  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
-  if (future) {
-    load_rows(src, S + A + 2, S, xin, row0, nrows, nullptr);
-    __syncthreads();
-    actor_fwd(L, thT, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
-    critic_fwd(L, thT, xin, act, bufA, bufB, qv, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
-  }
-  if (threadIdx.x < nrows) {
-    const int r = threadIdx.x;
-    const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
-    const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
-    const float g = row_discount(disc, used, slot, row0 + r, gamma);
-    float y = rew, qt = 0.f;
-    if (future) {
-      qt = qv[r];
-      if (done == 0.f) y = fmaf(g, qt, rew);
-    }
-    w.y[row0 + r] = y;
-    w.qt[row0 + r] = qt;
-  }
-}
+// What the target step writes and, with two critics, what its smoothing draws from.
+template <int NC>
+struct Target { float *y, *qt; };
+template <>
+struct Target<2> {
+  float *y, *qt, *qt1, *qt2, *t_eps, *t_a;
+  float sigma, clip;
+  uint64_t seed, number;
+};
 
-// Steps 1-2 of a twin step.  The target action of row k = row0 + r, action i: a~ = clip(actor_target(s2) + eps,
-// -1, 1), eps = (f32) clip(sigma n, -c, c), n Box-Muller in f64 on uniforms 2j and 2j + 1 of stream `number`, j = k A + i.
-// Both target critics read a~ from `act`, one after the other in the same buffers; y comes from the smaller q'.
-__global__ __launch_bounds__(THREADS) void ddpg_twin_target_kernel(Pair<Layout> L, const float* __restrict__ thT, Rows src, int B,
-                                                                   float gamma, int future, float sigma, float clip, uint64_t seed,
-                                                                   uint64_t number, Work w, Work2 w2,
-                                                                   const float* __restrict__ disc, float* __restrict__ used) {
+// Steps 1-2: actor_target and the NC target critics on s2, y = r or r + g q' with q' the smallest of their values.
+// NC = 2: the target action of row k = row0 + r, action i is a~ = clip(actor_target(s2) + eps, -1, 1),
+// eps = (f32) clip(sigma n, -c, c), n Box-Muller in f64 on uniforms 2j and 2j + 1 of stream `number`, j = k A + i.  Both target
+// critics read a~ from `act`, one after the other in the same buffers.
+template <int NC>
+__global__ __launch_bounds__(THREADS) void ddpg_target_kernel(PerCritic<Layout, NC> L, const float* __restrict__ thT, Rows src, int B,
+                                                              float gamma, int future, Target<NC> t,
+                                                              const float* __restrict__ disc, float* __restrict__ used) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
   __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
-  __shared__ float qv[TILE];
-  __shared__ float qv2[TILE];
+  __shared__ float qv[NC][TILE];
   const int S = L.v[0].S, A = L.v[0].A;
   const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
   if (future) {
     load_rows(src, S + A + 2, S, xin, row0, nrows, nullptr);
     __syncthreads();
     actor_fwd(L.v[0], thT, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
-    for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
-      const int i = e / TILE, r = e % TILE;
-      const uint64_t j = (uint64_t)(row0 + r) * (uint64_t)A + (uint64_t)i;
-      const double u1 = 1.0 - ga3c_uniform::actor_uniform(seed, number, 2 * j);
-      const double u2 = ga3c_uniform::actor_uniform(seed, number, 2 * j + 1);
-      const double n = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-      const float eps = (float)fmin(fmax((double)sigma * n, -(double)clip), (double)clip);
-      const float a = fminf(fmaxf(act[e] + eps, -1.f), 1.f);
-      act[e] = a;
-      if (r < nrows) {
-        w2.t_eps[(size_t)(row0 + r) * A + i] = eps;
-        w2.t_a[(size_t)(row0 + r) * A + i] = a;
+    if constexpr (NC == 2) {
+      for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+        const int i = e / TILE, r = e % TILE;
+        const uint64_t j = (uint64_t)(row0 + r) * (uint64_t)A + (uint64_t)i;
+        const double u1 = 1.0 - ga3c_uniform::actor_uniform(t.seed, t.number, 2 * j);
+        const double u2 = ga3c_uniform::actor_uniform(t.seed, t.number, 2 * j + 1);
+        const double n = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        const float eps = (float)fmin(fmax((double)t.sigma * n, -(double)t.clip), (double)t.clip);
+        const float a = fminf(fmaxf(act[e] + eps, -1.f), 1.f);
+        act[e] = a;
+        if (r < nrows) {
+          t.t_eps[(size_t)(row0 + r) * A + i] = eps;
+          t.t_a[(size_t)(row0 + r) * A + i] = a;
+        }
       }
+      __syncthreads();
     }
-    __syncthreads();
-    critic_fwd(L.v[0], thT, xin, act, bufA, bufB, qv, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
-    critic_fwd(L.v[1], thT, xin, act, bufA, bufB, qv2, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) critic_fwd(L.v[c], thT, xin, act, bufA, bufB, qv[c], CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
   }
   if (threadIdx.x < nrows) {
     const int r = threadIdx.x;
     const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
     const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
     const float g = row_discount(disc, used, slot, row0 + r, gamma);
-    float y = rew, qt = 0.f, q1 = 0.f, q2 = 0.f;
-    if (future) {
-      q1 = qv[r];
-      q2 = qv2[r];
-      qt = fminf(q1, q2);
-      if (done == 0.f) y = fmaf(g, qt, rew);
+    float q[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) q[c] = future ? qv[c][r] : 0.f;
+    float qt = q[0];
+    if constexpr (NC == 2) qt = fminf(q[0], q[1]);
+    float y = rew;
+    if (future && done == 0.f) y = fmaf(g, qt, rew);
+    t.y[row0 + r] = y;
+    t.qt[row0 + r] = qt;
+    if constexpr (NC == 2) {
+      t.qt1[row0 + r] = q[0];
+      t.qt2[row0 + r] = q[1];
     }
-    w.y[row0 + r] = y;
-    w.qt[row0 + r] = qt;
-    w2.qt1[row0 + r] = q1;
-    w2.qt2[row0 + r] = q2;
   }
 }
 
-// per_w (null without priorities): the rows' importance weights, dq_i = (2/B) w_i (q_i - y_i)
+// per_w (null without priorities): the rows' importance weights, dq_i = (2/B) w_i (q_i - y_i); keep_x, keep_a (null: not kept):
+// where the step's inputs go
 __device__ __forceinline__ void critic_step(const Layout& L, const float* __restrict__ th, const Rows& src, int B, int paired,
-                                            const float* __restrict__ per_w, const float* __restrict__ y, const CriticRows& w) {
+                                            const float* __restrict__ per_w, const float* __restrict__ y, float* keep_x,
+                                            float* keep_a, const CriticRows& w) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
@@ -408,8 +392,8 @@ __device__ __forceinline__ void critic_step(const Layout& L, const float* __rest
   float ysum = 0.f;
   for (int i = threadIdx.x; i < B; i += THREADS) ysum += y[i];
   const float ymean = block_sum<THREADS>(ysum, red) / (float)B;
-  load_rows(src, 0, S, xin, row0, nrows, w.x);
-  load_rows(src, S, A, act, row0, nrows, w.a);
+  load_rows(src, 0, S, xin, row0, nrows, keep_x);
+  load_rows(src, S, A, act, row0, nrows, keep_a);
   __syncthreads();
   critic_fwd(L, th, xin, act, bufA, bufB, qv, CriticKeep{w.xh1, w.c1, w.c2}, row0, nrows);
   if (threadIdx.x < TILE) {
@@ -445,18 +429,12 @@ __device__ __forceinline__ void critic_step(const Layout& L, const float* __rest
   });
 }
 
-__global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(Layout L, const float* __restrict__ th, Rows src, int B, int paired,
-                                                              const float* __restrict__ per_w, Work w) {
-  critic_step(L, th, src, B, paired, per_w, w.y, CriticRows{w.q, w.dq, w.c_x, w.c_a, w.c_xh1, w.c_c1, w.c_dn1, w.c_dh1, w.c_c2, w.c_dt});
-}
-
-// Critic blockIdx.y's step on the same rows and the same y, always in the paired form.  Critic 1 keeps the inputs.
-__global__ __launch_bounds__(THREADS) void ddpg_twin_critic_kernel(Pair<Layout> L, const float* __restrict__ th, Rows src, int B,
-                                                                   const float* __restrict__ per_w, Work w, Work2 w2) {
-  const bool two = blockIdx.y != 0;
-  const CriticRows rows = two ? CriticRows{w2.q2, w2.dq2, nullptr, nullptr, w2.c2_xh1, w2.c2_c1, w2.c2_dn1, w2.c2_dh1, w2.c2_c2, w2.c2_dt}
-                              : CriticRows{w.q, w.dq, w.c_x, w.c_a, w.c_xh1, w.c_c1, w.c_dn1, w.c_dh1, w.c_c2, w.c_dt};
-  critic_step(L.v[blockIdx.y], th, src, B, 1, per_w, w.y, rows);
+// Critic blockIdx.y's step (NC = 1: the one critic's) on the same rows and the same y.  Critic 1 keeps the inputs.
+template <int NC>
+__global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(PerCritic<Layout, NC> L, const float* __restrict__ th, Rows src, int B,
+                                                              int paired, const float* __restrict__ per_w, Work w) {
+  const int c = NC == 1 ? 0 : blockIdx.y;
+  critic_step(L.v[c], th, src, B, paired, per_w, w.y, c ? nullptr : w.c_x, c ? nullptr : w.c_a, w.c[c]);
 }
 
 __global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const float* __restrict__ th, Rows src, int B, Noise nz,
@@ -595,9 +573,9 @@ __device__ __forceinline__ void wgrad_element(const Layout& L, const GradSrc& sr
 
 // {max q, mean q}, summed in row order by the thread that calls it
 __device__ __forceinline__ void q_stats(const Work& w, int B) {
-  float mx = w.q[0], s = 0.f;
+  float mx = w.c[0].q[0], s = 0.f;
   for (int r = 0; r < B; ++r) {
-    const float q = w.q[r];
+    const float q = w.c[0].q[r];
     mx = fmaxf(mx, q);
     s += q;
   }
@@ -605,18 +583,14 @@ __device__ __forceinline__ void q_stats(const Work& w, int B) {
   w.qstat[1] = s / (float)B;
 }
 
-// The critic's launch also leaves {max q, mean q}.
-template <bool FUSED>
-__global__ __launch_bounds__(THREADS) void ddpg_wgrad_kernel(Layout L, GradSrc src, int v0, int v1, int B, Opt o, Work w) {
-  wgrad_element<FUSED>(L, src, v0, v1, B, o);
-  if (v0 == NACTOR && blockIdx.x == 0 && threadIdx.x == 0) q_stats(w, B);
-}
-
-// The trainable variables of critic blockIdx.y: the arenas are the same, so one Opt serves both.  q_stats are critic 1's.
-template <bool FUSED>
-__global__ __launch_bounds__(THREADS) void ddpg_twin_wgrad_kernel(Pair<Layout> L, Pair<GradSrc> src, int B, Opt o, Work w) {
-  wgrad_element<FUSED>(L.v[blockIdx.y], src.v[blockIdx.y], NACTOR, NTRAIN, B, o);
-  if (blockIdx.y == 0 && blockIdx.x == 0 && threadIdx.x == 0) q_stats(w, B);
+// The elements of variables v0 .. v1-1 of critic blockIdx.y (NC = 1: of the one net; the actor's too).  The arenas are the same
+// for every critic, so one Opt serves them all.  The launch for the critics' variables also leaves critic 1's {max q, mean q}.
+template <int NC, bool FUSED>
+__global__ __launch_bounds__(THREADS) void ddpg_wgrad_kernel(PerCritic<Layout, NC> L, PerCritic<GradSrc, NC> src, int v0, int v1,
+                                                             int B, Opt o, Work w) {
+  const int c = NC == 1 ? 0 : blockIdx.y;
+  wgrad_element<FUSED>(L.v[c], src.v[c], v0, v1, B, o);
+  if (v0 == NACTOR && c == 0 && blockIdx.x == 0 && threadIdx.x == 0) q_stats(w, B);
 }
 
 // The block's variable v: tf.clip_by_norm (g clip / max(||g||, clip)), the step, the soft update.
@@ -633,12 +607,10 @@ __device__ __forceinline__ void update_variable(const Layout& L, int v, const Op
   }
 }
 
-// One block per variable v0 + blockIdx.x.
-__global__ __launch_bounds__(THREADS) void ddpg_update_kernel(Layout L, int v0, Opt o) { update_variable(L, v0 + blockIdx.x, o); }
-
-// Blocks 0..9: critic 1's variables, 10..19: critic 2's.
-__global__ __launch_bounds__(THREADS) void ddpg_twin_update_kernel(Pair<Layout> L, Opt o) {
-  update_variable(L.v[blockIdx.x / NCRITIC], NACTOR + blockIdx.x % NCRITIC, o);
+// One block per critic variable: blocks 0..9 critic 1's, with NC = 2 blocks 10..19 critic 2's.
+template <int NC>
+__global__ __launch_bounds__(THREADS) void ddpg_update_kernel(PerCritic<Layout, NC> L, Opt o) {
+  update_variable(L.v[NC == 1 ? 0 : blockIdx.x / NCRITIC], NACTOR + blockIdx.x % NCRITIC, o);
 }
 
 // Ring slot (first + i) mod cap <- s | a | r | done | s2, from row `s[S] | s2[S] | done` of the transport and the staged r, a.
@@ -822,19 +794,16 @@ struct ActState {
   ga3c_actors::Episodes ep;  // this step's finished episodes and the episode ring
 };
 
-// One step of environment i = the thread's index.  first: the handle's first ever step, the host's step(None): the zero action,
-// nothing written to the ring, its done not looked at.  Otherwise the action is a.action's row; the transition
-// obs | a | (f32) reward | done | obs' goes to ring slot (slot0 + i) mod cap (n <= cap: no two threads share a slot) and, with
-// priorities, that slot gets max_pa, which only per_update_kernel writes, earlier on this stream: per_fill_kernel's value.
-template <class Env>
-__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState a, int first, float* __restrict__ ring, int64_t slot0,
-                                                                       int64_t cap, float* __restrict__ pa,
-                                                                       const float* __restrict__ max_pa) {
+// One step of environment i = the thread's index, the one statement of it for both kernels below.  first: the handle's first
+// ever step, the host's step(None): the zero action, nothing kept of the transition, its done not looked at.  Otherwise the
+// action is a.action's row and keep(i, obs, a, reward, done, obs') puts the transition where the kernel wants it, before the
+// episode's totals move.  The f64 physics must not contract; neither may a `keep` that does arithmetic.
+template <class Env, class Keep>
+__device__ __forceinline__ void actor_step(const ActState& a, int first, Keep keep) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * ACT_THREADS + threadIdx.x;
   if (i >= a.N) return;
   constexpr int S = Env::S, P = Env::P, A = Env::A;
-  constexpr int rowf = 2 * S + A + 2;
   double s[P];
   int elapsed;
   ga3c_actors::load_physics<P>(a.phys, a.elapsed, i, s, elapsed);
@@ -856,14 +825,7 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState 
     ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
     return;
   }
-  const int64_t slot = (slot0 + i) % cap;
-  float* row = ring + slot * rowf;
-  for (int k = 0; k < S; ++k) row[k] = before[k];
-  for (int j = 0; j < A; ++j) row[S + j] = av[j];
-  row[S + A] = (float)reward;
-  row[S + A + 1] = done ? 1.f : 0.f;
-  for (int k = 0; k < S; ++k) row[S + A + 2 + k] = after[k];
-  if (pa) pa[slot] = *max_pa;
+  keep(i, before, av, reward, done, after);
   double total = a.total_reward[i] + reward;
   long long length = a.total_length[i] + 1;
   if (done) {                           // ProcessAgent.run's record of an episode shipped as one rollout: len(experiences) + 1
@@ -877,6 +839,29 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState 
   ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
 }
 
+// actor_step with the transition obs | a | (f32) reward | done | obs' into ring slot (slot0 + i) mod cap (n <= cap: no two
+// threads share a slot).  With priorities that slot gets max_pa, which only per_update_kernel writes, earlier on this stream:
+// per_fill_kernel's value.
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState a, int first, float* __restrict__ ring, int64_t slot0,
+                                                                       int64_t cap, float* __restrict__ pa,
+                                                                       const float* __restrict__ max_pa) {
+#pragma clang fp contract(off)
+  constexpr int S = Env::S, A = Env::A;
+  constexpr int rowf = 2 * S + A + 2;
+  actor_step<Env>(a, first, [&](int i, const float* before, const float* av, double reward, int done, const float* after) {
+#pragma clang fp contract(off)
+    const int64_t slot = (slot0 + i) % cap;
+    float* row = ring + slot * rowf;
+    for (int k = 0; k < S; ++k) row[k] = before[k];
+    for (int j = 0; j < A; ++j) row[S + j] = av[j];
+    row[S + A] = (float)reward;
+    row[S + A + 1] = done ? 1.f : 0.f;
+    for (int k = 0; k < S; ++k) row[S + A + 2 + k] = after[k];
+    if (pa) pa[slot] = *max_pa;
+  });
+}
+
 // The environments' windows of a handle with n-step returns: the last n transitions of each, entry-major and
 // environment-minor, so that a wave's loads and stores of one field of one entry are contiguous.
 struct NWindow {
@@ -885,8 +870,8 @@ struct NWindow {
   double* r;                 // [n][N] the f64 rewards
 };
 
-// ddpg_actors_step_kernel's step with the ring write delayed by n - 1 transitions.  entry = c mod n for the handle's transition
-// count c (the host's: every environment steps on every step); emit = c >= n - 1.  The transition goes to window entry `entry`.
+// actor_step with the ring write delayed by n - 1 transitions.  entry = c mod n for the handle's transition count c (the
+// host's: every environment steps on every step); emit = c >= n - 1.  The transition goes to window entry `entry`.
 // On an emitting step the row of the transition that began at u = c - n + 1, which lies in entry (entry + 1) mod n, goes to ring
 // slot (slot0 + i) mod cap: m = the first k in 1..n whose transition u + k - 1 is done, n if none; R = sum_{k<m} g_k r_{u+k} in
 // f64, ascending k, g_0 = 1 and g_{k+1} = g_k gamma64; the row is s_u | a_u | (f32) R | done_{u+m-1} | s2_{u+m-1} and
@@ -897,76 +882,45 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_nstep_kernel(ActState
                                                                         int64_t cap, float* __restrict__ disc,
                                                                         float* __restrict__ pa, const float* __restrict__ max_pa) {
 #pragma clang fp contract(off)
-  const int i = blockIdx.x * ACT_THREADS + threadIdx.x;
-  if (i >= a.N) return;
-  constexpr int S = Env::S, P = Env::P, A = Env::A;
+  constexpr int S = Env::S, A = Env::A;
   constexpr int rowf = 2 * S + A + 2, W = 2 * S + A + 1;
   const size_t N = (size_t)a.N;
-  double s[P];
-  int elapsed;
-  ga3c_actors::load_physics<P>(a.phys, a.elapsed, i, s, elapsed);
-  float av[A];
-  for (int j = 0; j < A; ++j) av[j] = first ? 0.f : a.action[(size_t)i * A + j];
-  float* obs = a.obs + (size_t)i * S;
-  float before[S], after[S];
-  for (int k = 0; k < S; ++k) before[k] = obs[k];
-  double reward;
-  int done;
-  Env::step(s, av, &elapsed, &reward, &done);
-  Env::observe(s, after);
-  for (int k = 0; k < S; ++k) obs[k] = after[k];
-  a.reward[i] = reward;
-  a.done[i] = done;
-  a.ep.ep_flag[i] = 0;
-  if (first) {
-    for (int j = 0; j < A; ++j) a.action[(size_t)i * A + j] = 0.f;
-    ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
-    return;
-  }
-  const int n = w.n;
-  {
-    float* e = w.f + (size_t)entry * W * N + i;
-    for (int k = 0; k < S; ++k) e[k * N] = before[k];
-    for (int j = 0; j < A; ++j) e[(S + j) * N] = av[j];
-    e[(S + A) * N] = done ? 1.f : 0.f;
-    for (int k = 0; k < S; ++k) e[(S + A + 1 + k) * N] = after[k];
-    w.r[(size_t)entry * N + i] = reward;
-  }
-  if (emit) {
-    const int oldest = entry + 1 == n ? 0 : entry + 1;
-    int j = oldest, last = oldest;
-    double R = 0.0, g = 1.0;
-    float d = 0.f;
-    for (int k = 0; k < n; ++k) {
-      R = R + g * w.r[(size_t)j * N + i];
-      g = g * gamma64;
-      d = w.f[((size_t)j * W + S + A) * N + i];
-      last = j;
-      if (d != 0.f) break;
-      j = j + 1 == n ? 0 : j + 1;
+  actor_step<Env>(a, first, [&](int i, const float* before, const float* av, double reward, int done, const float* after) {
+#pragma clang fp contract(off)
+    const int n = w.n;
+    {
+      float* e = w.f + (size_t)entry * W * N + i;
+      for (int k = 0; k < S; ++k) e[k * N] = before[k];
+      for (int j = 0; j < A; ++j) e[(S + j) * N] = av[j];
+      e[(S + A) * N] = done ? 1.f : 0.f;
+      for (int k = 0; k < S; ++k) e[(S + A + 1 + k) * N] = after[k];
+      w.r[(size_t)entry * N + i] = reward;
     }
-    const int64_t slot = (slot0 + i) % cap;
-    float* row = ring + slot * rowf;
-    const float* eo = w.f + (size_t)oldest * W * N + i;
-    const float* el = w.f + (size_t)last * W * N + i;
-    for (int k = 0; k < S + A; ++k) row[k] = eo[k * N];
-    row[S + A] = (float)R;
-    row[S + A + 1] = d;
-    for (int k = 0; k < S; ++k) row[S + A + 2 + k] = el[(S + A + 1 + k) * N];
-    disc[slot] = (float)g;
-    if (pa) pa[slot] = *max_pa;
-  }
-  double total = a.total_reward[i] + reward;
-  long long length = a.total_length[i] + 1;
-  if (done) {                           // the record is per step, as ddpg_actors_step_kernel's
-    uint64_t draws = a.draws[i];
-    length += 1;
-    ga3c_actors::finish_episode<Env>(a.ep, i, a.seed, total, length, draws, s, elapsed);
-    a.draws[i] = draws;
-  }
-  a.total_reward[i] = total;
-  a.total_length[i] = length;
-  ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
+    if (emit) {
+      const int oldest = entry + 1 == n ? 0 : entry + 1;
+      int j = oldest, last = oldest;
+      double R = 0.0, g = 1.0;
+      float d = 0.f;
+      for (int k = 0; k < n; ++k) {
+        R = R + g * w.r[(size_t)j * N + i];
+        g = g * gamma64;
+        d = w.f[((size_t)j * W + S + A) * N + i];
+        last = j;
+        if (d != 0.f) break;
+        j = j + 1 == n ? 0 : j + 1;
+      }
+      const int64_t slot = (slot0 + i) % cap;
+      float* row = ring + slot * rowf;
+      const float* eo = w.f + (size_t)oldest * W * N + i;
+      const float* el = w.f + (size_t)last * W * N + i;
+      for (int k = 0; k < S + A; ++k) row[k] = eo[k * N];
+      row[S + A] = (float)R;
+      row[S + A + 1] = d;
+      for (int k = 0; k < S; ++k) row[S + A + 2 + k] = el[(S + A + 1 + k) * N];
+      disc[slot] = (float)g;
+      if (pa) pa[slot] = *max_pa;
+    }
+  });
 }
 
 // One workgroup: the step's finished episodes go to the episode ring in environment order (ga3c_actors.hpp).
@@ -1054,8 +1008,7 @@ struct Twin {
   float sigma = 0.f, clip = 0.f;        // the target smoothing
   uint64_t seed = 0;                    // its draw at step + 1 = t is stream t of this seed
   Layout view;                          // twin_view(L)
-  Work2 w{};
-  float* work_base = nullptr;
+  float* work_base = nullptr;           // the twin-only rows of the handle's Work
 };
 
 // n-step returns of a handle (ga3c_ddpg_nstep_create).  The environments' windows are the actors'.
@@ -1095,47 +1048,47 @@ namespace {
 
 int tiles(int B) { return (B + TILE - 1) / TILE; }
 
-const char* const WORK_NAMES[] = {"y", "qt", "q", "dq", "c_x", "c_a", "c_xh1", "c_c1", "c_dn1", "c_dh1", "c_c2", "c_dt",
-                                  "a_xh1", "a_a1", "a_dn1", "a_dh1", "a_xh2", "a_a2", "a_dn2", "a_dh2", "a_out", "a_noisy", "g", "do"};
-constexpr int NWORK = sizeof(WORK_NAMES) / sizeof(WORK_NAMES[0]);
+// The rows of the train workspace by the name ga3c_ddpg_fetch knows them under.  twin: the row exists while the handle has twin
+// critics, in a block of its own (Twin::work_base); the others live as long as the handle (work_base).
+struct WorkRow {
+  const char* name;
+  float** ptr;
+  size_t width;
+  bool twin;
+};
 
-void work_table(ga3c_ddpg* m, std::vector<float**>* ptrs, std::vector<size_t>* widths) {
+std::vector<WorkRow> work_table(ga3c_ddpg* m) {
   const size_t S = m->L.S, A = m->L.A;
   Work& w = m->w;
-  *ptrs = {&w.y, &w.qt, &w.q, &w.dq, &w.c_x, &w.c_a, &w.c_xh1, &w.c_c1, &w.c_dn1, &w.c_dh1, &w.c_c2, &w.c_dt,
-           &w.a_xh1, &w.a_a1, &w.a_dn1, &w.a_dh1, &w.a_xh2, &w.a_a2, &w.a_dn2, &w.a_dh2, &w.a_out, &w.a_noisy, &w.g, &w.dout};
-  *widths = {1, 1, 1, 1, S, A, H1, H1, H1, H1, H2, H2, H1, H1, H1, H1, H2, H2, H2, H2, A, A, A, A};
+  CriticRows &c = w.c[0], &d = w.c[1];
+  return {{"y", &w.y, 1, false},           {"qt", &w.qt, 1, false},         {"q", &c.q, 1, false},           {"dq", &c.dq, 1, false},
+          {"c_x", &w.c_x, S, false},       {"c_a", &w.c_a, A, false},       {"c_xh1", &c.xh1, H1, false},    {"c_c1", &c.c1, H1, false},
+          {"c_dn1", &c.dn1, H1, false},    {"c_dh1", &c.dh1, H1, false},    {"c_c2", &c.c2, H2, false},      {"c_dt", &c.dt, H2, false},
+          {"a_xh1", &w.a_xh1, H1, false},  {"a_a1", &w.a_a1, H1, false},    {"a_dn1", &w.a_dn1, H1, false},  {"a_dh1", &w.a_dh1, H1, false},
+          {"a_xh2", &w.a_xh2, H2, false},  {"a_a2", &w.a_a2, H2, false},    {"a_dn2", &w.a_dn2, H2, false},  {"a_dh2", &w.a_dh2, H2, false},
+          {"a_out", &w.a_out, A, false},   {"a_noisy", &w.a_noisy, A, false}, {"g", &w.g, A, false},         {"do", &w.dout, A, false},
+          {"qt1", &w.qt1, 1, true},        {"qt2", &w.qt2, 1, true},        {"q2", &d.q, 1, true},           {"dq2", &d.dq, 1, true},
+          {"t_eps", &w.t_eps, A, true},    {"t_a", &w.t_a, A, true},        {"c2_xh1", &d.xh1, H1, true},    {"c2_c1", &d.c1, H1, true},
+          {"c2_dn1", &d.dn1, H1, true},    {"c2_dh1", &d.dh1, H1, true},    {"c2_c2", &d.c2, H2, true},      {"c2_dt", &d.dt, H2, true}};
 }
 
-const char* const WORK2_NAMES[] = {"qt1", "qt2", "q2", "dq2", "t_eps", "t_a", "c2_xh1", "c2_c1", "c2_dn1", "c2_dh1", "c2_c2", "c2_dt"};
-constexpr int NWORK2 = sizeof(WORK2_NAMES) / sizeof(WORK2_NAMES[0]);
-
-void work2_table(ga3c_ddpg* m, std::vector<float**>* ptrs, std::vector<size_t>* widths) {
-  const size_t A = m->L.A;
-  Work2& w = m->twin->w;
-  *ptrs = {&w.qt1, &w.qt2, &w.q2, &w.dq2, &w.t_eps, &w.t_a, &w.c2_xh1, &w.c2_c1, &w.c2_dn1, &w.c2_dh1, &w.c2_c2, &w.c2_dt};
-  *widths = {1, 1, 1, 1, A, A, H1, H1, H1, H1, H2, H2};
+// One zeroed block for the table's rows with `twin` set, or for those without; *end: the four floats behind them.
+int carve_work(ga3c_ddpg* m, bool twin, float** base, float** end) {
+  std::vector<float**> ptrs;
+  std::vector<size_t> widths;
+  for (const WorkRow& r : work_table(m))
+    if (r.twin == twin) {
+      ptrs.push_back(r.ptr);
+      widths.push_back(r.width);
+    }
+  return vn::carve_rows((size_t)m->cfg.max_batch, widths, ptrs, base, end);
 }
 
-// one critic's entries: critic 1's from Work, critic 2's from Work2
-void critic_grad_src(GradSrc* g, int S, int A, const float* x, const float* a, const CriticRows& c) {
-  auto set = [&](int v, const float* in, int li, const float* d, int ld, const float* mul) {
-    g->in[v] = in; g->ld_in[v] = li; g->d[v] = d; g->ld_d[v] = ld; g->mul[v] = mul;
-  };
-  set(C_W1, x, S, c.dh1, H1, nullptr);
-  set(C_B1, nullptr, 0, c.dh1, H1, nullptr);
-  set(C_BE1, nullptr, 0, c.dn1, H1, nullptr);
-  set(C_GA1, nullptr, 0, c.dn1, H1, c.xh1);
-  set(C_W2, c.c1, H1, c.dt, H2, nullptr);
-  set(C_WN, a, A, c.dt, H2, nullptr);
-  set(C_BN, nullptr, 0, c.dt, H2, nullptr);
-  set(C_WO, c.c2, H2, c.dq, 1, nullptr);
-  set(C_BO, nullptr, 0, c.dq, 1, nullptr);
-}
-
-GradSrc grad_src(ga3c_ddpg* m) {
+// The actor's entries and critic c's.
+GradSrc grad_src(ga3c_ddpg* m, int c) {
   GradSrc g;
   const Work& w = m->w;
+  const CriticRows& cr = w.c[c];
   const int S = m->L.S, A = m->L.A;
   for (int v = 0; v < NTRAIN; ++v) {
     g.in[v] = g.d[v] = g.mul[v] = nullptr;
@@ -1154,16 +1107,15 @@ GradSrc grad_src(ga3c_ddpg* m) {
   set(A_GA2, nullptr, 0, w.a_dn2, H2, w.a_xh2);
   set(A_WO, w.a_a2, H2, w.dout, A, nullptr);
   set(A_BO, nullptr, 0, w.dout, A, nullptr);
-  critic_grad_src(&g, S, A, w.c_x, w.c_a, CriticRows{w.q, w.dq, nullptr, nullptr, w.c_xh1, w.c_c1, w.c_dn1, w.c_dh1, w.c_c2, w.c_dt});
-  return g;
-}
-
-// ... with critic 2's rows in the critic's entries (the actor's are not read through it)
-GradSrc twin_grad_src(ga3c_ddpg* m) {
-  GradSrc g = grad_src(m);
-  const Work2& w = m->twin->w;
-  critic_grad_src(&g, m->L.S, m->L.A, m->w.c_x, m->w.c_a,
-                  CriticRows{w.q2, w.dq2, nullptr, nullptr, w.c2_xh1, w.c2_c1, w.c2_dn1, w.c2_dh1, w.c2_c2, w.c2_dt});
+  set(C_W1, w.c_x, S, cr.dh1, H1, nullptr);
+  set(C_B1, nullptr, 0, cr.dh1, H1, nullptr);
+  set(C_BE1, nullptr, 0, cr.dn1, H1, nullptr);
+  set(C_GA1, nullptr, 0, cr.dn1, H1, cr.xh1);
+  set(C_W2, cr.c1, H1, cr.dt, H2, nullptr);
+  set(C_WN, w.c_a, A, cr.dt, H2, nullptr);
+  set(C_BN, nullptr, 0, cr.dt, H2, nullptr);
+  set(C_WO, cr.c2, H2, cr.dq, 1, nullptr);
+  set(C_BO, nullptr, 0, cr.dq, 1, nullptr);
   return g;
 }
 
@@ -1208,67 +1160,57 @@ const float* row_discounts(const ga3c_ddpg* m, const Rows& rows) {
   return m->nstep && rows.base == m->ring ? m->nstep->disc : nullptr;
 }
 
-// The twin's step: smoothed targets from the smaller of two target critics, both critics stepped on them, and
-// only when t is a multiple of the delay the actor's step, at its own Adam count, and the soft update of all three nets.
-int enqueue_twin_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w) {
+// Steps 1 .. stop_after of train_DDPG on `rows` for a handle with NC critics (caller holds train_mu and mu).  stop_after 6: the
+// whole step.  Twin critics: smoothed targets from the smaller of two target critics, both critics stepped on
+// them in the paired form, and only when t is a multiple of the delay the actor's step, at its own Adam count, and the soft
+// update of all three nets.  One critic is that rule at delay 1, with the loss form the handle's flag names.
+template <int NC>
+int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w) {
   const ga3c_ddpg_config& c = m->cfg;
-  const Twin& tw = *m->twin;
+  const Work& w = m->w;
   const int64_t t = m->step.load() + 1;
-  const bool policy = t % tw.delay == 0, full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
-  const dim3 grid(tiles(B)), grid2(tiles(B), 2), block(THREADS);
-  const Pair<Layout> L{{m->L, tw.view}};
-  hipLaunchKernelGGL(ddpg_twin_target_kernel, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma,
-                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, tw.sigma, tw.clip, tw.seed, (uint64_t)t, m->w, tw.w,
-                     row_discounts(m, rows), m->nstep ? m->nstep->used : nullptr);
-  hipLaunchKernelGGL(ddpg_twin_critic_kernel, grid2, block, 0, m->st, L, (const float*)m->arena[0], rows, B, per_w, m->w, tw.w);
-  const GradSrc gs = grad_src(m);
-  const Pair<GradSrc> gs2{{gs, twin_grad_src(m)}};
+  const int delay = NC == 2 ? m->twin->delay : 1;
+  const bool policy = t % delay == 0, full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
+  const int paired = NC == 2 || (c.flags & GA3C_DDPG_LOSS_PAIRED) ? 1 : 0;
+  PerCritic<Layout, NC> L;
+  PerCritic<GradSrc, NC> gs;
+  Target<NC> tg;
+  L.v[0] = m->L;
+  gs.v[0] = grad_src(m, 0);
+  tg.y = w.y;
+  tg.qt = w.qt;
+  if constexpr (NC == 2) {
+    const Twin& tw = *m->twin;
+    L.v[1] = tw.view;
+    gs.v[1] = grad_src(m, 1);
+    tg.qt1 = w.qt1; tg.qt2 = w.qt2; tg.t_eps = w.t_eps; tg.t_a = w.t_a;
+    tg.sigma = tw.sigma; tg.clip = tw.clip; tg.seed = tw.seed; tg.number = (uint64_t)t;
+  }
+  const dim3 grid(tiles(B)), gridc(tiles(B), NC), block(THREADS);
+  hipLaunchKernelGGL(ddpg_target_kernel<NC>, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma,
+                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, tg, row_discounts(m, rows), m->nstep ? m->nstep->used : nullptr);
+  hipLaunchKernelGGL(ddpg_critic_kernel<NC>, gridc, block, 0, m->st, L, (const float*)m->arena[0], rows, B, paired, per_w, w);
   const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
   const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
   const Opt oc = make_opt(m, false, lr, t, true, full && policy);
   if (clip) {
-    hipLaunchKernelGGL(ddpg_twin_wgrad_kernel<false>, dim3(cblocks, 2), block, 0, m->st, L, gs2, B, oc, m->w);
-    hipLaunchKernelGGL(ddpg_twin_update_kernel, dim3(2 * NCRITIC), block, 0, m->st, L, oc);
+    hipLaunchKernelGGL((ddpg_wgrad_kernel<NC, false>), dim3(cblocks, NC), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
+    hipLaunchKernelGGL(ddpg_update_kernel<NC>, dim3(NC * NCRITIC), block, 0, m->st, L, oc);
   } else {
-    hipLaunchKernelGGL(ddpg_twin_wgrad_kernel<true>, dim3(cblocks, 2), block, 0, m->st, L, gs2, B, oc, m->w);
+    hipLaunchKernelGGL((ddpg_wgrad_kernel<NC, true>), dim3(cblocks, NC), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
   }
   if (stop_after >= 4 && policy) {
-    hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, m->w);
-    const Opt oa = make_opt(m, true, lr, t / tw.delay, full, full);
-    hipLaunchKernelGGL(ddpg_wgrad_kernel<true>, dim3(ablocks), block, 0, m->st, m->L, gs, 0, NACTOR, B, oa, m->w);
+    hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w);
+    const Opt oa = make_opt(m, true, lr, t / delay, full, full);
+    hipLaunchKernelGGL((ddpg_wgrad_kernel<1, true>), dim3(ablocks), block, 0, m->st, PerCritic<Layout, 1>{{m->L}},
+                       PerCritic<GradSrc, 1>{{gs.v[0]}}, 0, NACTOR, B, oa, w);
   }
   HIPCHK(hipGetLastError());
   return GA3C_OK;
 }
 
-// Steps 1 .. stop_after of train_DDPG on `rows` (caller holds train_mu and mu).  stop_after 6: the whole step.
 int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w = nullptr) {
-  if (m->twin) return enqueue_twin_step(m, rows, B, lr, nz, stop_after, per_w);
-  const ga3c_ddpg_config& c = m->cfg;
-  const int64_t t = m->step.load() + 1;
-  const bool full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
-  const dim3 grid(tiles(B)), block(THREADS);
-  hipLaunchKernelGGL(ddpg_target_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[1], rows, B, c.gamma,
-                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, m->w, row_discounts(m, rows), m->nstep ? m->nstep->used : nullptr);
-  hipLaunchKernelGGL(ddpg_critic_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B,
-                     (c.flags & GA3C_DDPG_LOSS_PAIRED) ? 1 : 0, per_w, m->w);
-  const GradSrc gs = grad_src(m);
-  const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
-  const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
-  const Opt oc = make_opt(m, false, lr, t, true, full);
-  if (clip) {
-    hipLaunchKernelGGL(ddpg_wgrad_kernel<false>, dim3(cblocks), block, 0, m->st, m->L, gs, NACTOR, NTRAIN, B, oc, m->w);
-    hipLaunchKernelGGL(ddpg_update_kernel, dim3(NTRAIN - NACTOR), block, 0, m->st, m->L, NACTOR, oc);
-  } else {
-    hipLaunchKernelGGL(ddpg_wgrad_kernel<true>, dim3(cblocks), block, 0, m->st, m->L, gs, NACTOR, NTRAIN, B, oc, m->w);
-  }
-  if (stop_after >= 4) {
-    hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, m->w);
-    const Opt oa = make_opt(m, true, lr, t, full, full);
-    hipLaunchKernelGGL(ddpg_wgrad_kernel<true>, dim3(ablocks), block, 0, m->st, m->L, gs, 0, NACTOR, B, oa, m->w);
-  }
-  HIPCHK(hipGetLastError());
-  return GA3C_OK;
+  return m->twin ? enqueue_step_nc<2>(m, rows, B, lr, nz, stop_after, per_w) : enqueue_step_nc<1>(m, rows, B, lr, nz, stop_after, per_w);
 }
 
 int finish_step(ga3c_ddpg* m) {
@@ -1291,12 +1233,12 @@ void pack_rows(const ga3c_ddpg* m, float* dst, const float* s, const float* a, c
   }
 }
 
-// train / compute on host rows: staged in ring layout, then the same kernels as train_replay
+// train / compute on host rows: staged in ring layout, then the same kernels as train_replay.  stop_after is 6 from train and
+// what ga3c_ddpg_compute checked from there.
 int step_host(ga3c_ddpg* m, const float* s, const float* a, const float* r, const float* done, const float* s2, int B, float lr,
               int mode, const float* noise, int stop_after, float* q_stats) {
   if (!m || !s || !a || !r || !done || !s2) return fail(GA3C_EINVAL, "null argument");
   CHK(vn::check_batch(m, B));
-  if (stop_after != 3 && stop_after != 4 && stop_after != 6) return fail(GA3C_EINVAL, "stop_after %d not in {3, 4}", stop_after);
   HIPCHK(hipSetDevice(m->device));
   std::lock_guard<std::mutex> tl(m->train_mu);
   Noise nz;
@@ -1378,6 +1320,8 @@ void twin_free(ga3c_ddpg* m) {
   if (!t) return;
   (void)hipFree(t->work_base);
   (void)hipGetLastError();
+  for (const WorkRow& r : work_table(m))
+    if (r.twin) *r.ptr = nullptr;
   delete t;
   m->twin = nullptr;
   m->vars.resize(NVARS);            // the arenas keep their size: nothing names what lies behind the 26
@@ -1444,10 +1388,7 @@ int alloc_all(ga3c_ddpg* m) {
     for (int64_t i = m->L.off[NACTOR]; i < m->L.off[NTRAIN]; ++i) init[(size_t)i] = 1.f;
     HIPCHK(hipMemcpy(m->arena[2], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
   }
-  std::vector<float**> ptrs;
-  std::vector<size_t> widths;
-  work_table(m, &ptrs, &widths);
-  CHK(vn::carve_rows(B, widths, ptrs, &m->work_base, &m->w.qstat));
+  CHK(carve_work(m, false, &m->work_base, &m->w.qstat));
   CHK(vn::dalloc(&m->ring, (size_t)c.replay_capacity * rowf));
   HIPCHK(hipMemset(m->ring, 0, sizeof(float) * (size_t)c.replay_capacity * rowf));
   CHK(vn::halloc(&m->h_stage, B * rowf)); CHK(vn::dalloc(&m->d_stage, B * rowf));
@@ -1510,7 +1451,7 @@ int per_enqueue_step(ga3c_ddpg* m, int B, float beta, float lr, const Noise& nz)
   Per* p = m->per;
   per_enqueue_sample(m, B, beta);
   CHK(enqueue_step(m, Rows{m->ring, p->slots, m->rowf}, B, lr, nz, 6, p->w));
-  hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(PER_THREADS), 0, m->st, (const int32_t*)p->slots, (const float*)m->w.q,
+  hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(PER_THREADS), 0, m->st, (const int32_t*)p->slots, (const float*)m->w.c[0].q,
                      (const float*)m->w.y, B, p->eps, p->alpha, p->pa, p->max_pa, p->td);
   HIPCHK(hipGetLastError());
   p->td_rows = B;
@@ -1530,6 +1471,24 @@ int per_check_beta(float beta) {
 void ring_report(ga3c_ddpg* m, int64_t* size, int64_t* total) {
   if (size) *size = ring_size(m);
   if (total) *total = m->ring_total;
+}
+
+// The timed loop of ga3c_ddpg_time_*: `iters` calls of `enqueue` between the events t0 and t1 (caller holds train_mu and mu) ...
+template <class F>
+int timed_loop(ga3c_ddpg* m, int batch, int iters, F enqueue) {
+  HIPCHK(hipEventRecord(m->t0, m->st));
+  for (int i = 0; i < iters; ++i) CHK(enqueue());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(m->t1, m->st));
+  m->last_B = batch;
+  return GA3C_OK;
+}
+
+// ... and, with mu released, the wait for it and the time between the two.
+int timed_wait(ga3c_ddpg* m, float* elapsed_ms) {
+  HIPCHK(hipEventSynchronize(m->t1));
+  HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
+  return GA3C_OK;
 }
 
 }  // namespace
@@ -1810,9 +1769,6 @@ int ga3c_ddpg_train_replay(ga3c_ddpg* m, const int32_t* slots, int32_t batch, in
 
 int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
   if (!m || !name || !out) return fail(GA3C_EINVAL, "null argument");
-  std::vector<float**> ptrs;
-  std::vector<size_t> widths;
-  work_table(m, &ptrs, &widths);
   const bool per_w = strcmp(name, "per_w") == 0;
   if (per_w || strcmp(name, "per_td") == 0) {       // of the last draw / the last prioritised step, whatever ran since
     HIPCHK(hipSetDevice(m->device));
@@ -1835,21 +1791,19 @@ int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
     HIPCHK(hipMemcpy(out, m->nstep->used, sizeof(float) * count, hipMemcpyDeviceToHost));
     return GA3C_OK;
   }
-  for (int i = 0; i < NWORK; ++i)
-    if (strcmp(name, WORK_NAMES[i]) == 0) return vn::fetch(m, name, *ptrs[i], (int64_t)widths[i], out, count);
-  for (int i = 0; i < NWORK2; ++i)
-    if (strcmp(name, WORK2_NAMES[i]) == 0) {          // under both locks throughout: twin_destroy frees these rows
-      HIPCHK(hipSetDevice(m->device));
-      std::lock_guard<std::mutex> tl(m->train_mu);
-      std::lock_guard<std::mutex> lk(m->mu);
-      if (!m->twin) return fail(GA3C_ESTATE, "%s: the handle has no twin critics (ga3c_ddpg_twin_create)", name);
-      work2_table(m, &ptrs, &widths);
-      const int64_t want = (int64_t)widths[i] * m->last_B;
-      if (count != want) return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)want, (long long)count);
-      HIPCHK(hipStreamSynchronize(m->st));
-      HIPCHK(hipMemcpy(out, *ptrs[i], sizeof(float) * count, hipMemcpyDeviceToHost));
-      return GA3C_OK;
-    }
+  for (const WorkRow& r : work_table(m)) {
+    if (strcmp(name, r.name) != 0) continue;
+    if (!r.twin) return vn::fetch(m, name, *r.ptr, (int64_t)r.width, out, count);
+    HIPCHK(hipSetDevice(m->device));                // under both locks throughout: twin_destroy frees these rows
+    std::lock_guard<std::mutex> tl(m->train_mu);
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->twin) return fail(GA3C_ESTATE, "%s: the handle has no twin critics (ga3c_ddpg_twin_create)", name);
+    const int64_t want = (int64_t)r.width * m->last_B;
+    if (count != want) return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)want, (long long)count);
+    HIPCHK(hipStreamSynchronize(m->st));
+    HIPCHK(hipMemcpy(out, *r.ptr, sizeof(float) * count, hipMemcpyDeviceToHost));
+    return GA3C_OK;
+  }
   return fail(GA3C_EINVAL, "no buffer named %s", name);
 }
 
@@ -1868,23 +1822,18 @@ int ga3c_ddpg_time_resident(ga3c_ddpg* m, int32_t mode, int32_t batch, int32_t i
     memset(&nz, 0, sizeof nz);
     const Rows rows{m->ring, m->d_idx, m->rowf};
     const Input in{reinterpret_cast<const char*>(m->ring), nullptr, 4 * (int64_t)m->rowf};
-    HIPCHK(hipEventRecord(m->t0, m->st));
-    for (int i = 0; i < iters; ++i) {
+    CHK(timed_loop(m, batch, iters, [&]() -> int {
       if (mode == 0) {
         hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(batch)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in,
                            batch, nz, m->w.a_out);
-      } else {
-        CHK(enqueue_step(m, rows, batch, learning_rate, nz, 6));
-        m->step.fetch_add(1);
+        return GA3C_OK;
       }
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->t1, m->st));
-    m->last_B = batch;
+      CHK(enqueue_step(m, rows, batch, learning_rate, nz, 6));
+      m->step.fetch_add(1);
+      return GA3C_OK;
+    }));
   }
-  HIPCHK(hipEventSynchronize(m->t1));
-  HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
-  return GA3C_OK;
+  return timed_wait(m, elapsed_ms);
 }
 
 // ---- prioritised replay
@@ -2035,17 +1984,13 @@ int ga3c_ddpg_time_prioritized(ga3c_ddpg* m, int32_t batch, int32_t iters, float
       return fail(GA3C_ESTATE, "batch %d: the ring holds %lld rows, not more than a batch", batch, (long long)ring_size(m));
     Noise nz;
     memset(&nz, 0, sizeof nz);
-    HIPCHK(hipEventRecord(m->t0, m->st));
-    for (int i = 0; i < iters; ++i) {
+    CHK(timed_loop(m, batch, iters, [&]() -> int {
       CHK(per_enqueue_step(m, batch, beta_is, learning_rate, nz));
       m->step.fetch_add(1);
-    }
-    HIPCHK(hipEventRecord(m->t1, m->st));
-    m->last_B = batch;
+      return GA3C_OK;
+    }));
   }
-  HIPCHK(hipEventSynchronize(m->t1));
-  HIPCHK(hipEventElapsedTime(elapsed_ms, m->t0, m->t1));
-  return GA3C_OK;
+  return timed_wait(m, elapsed_ms);
 }
 
 // ---- twin critics
@@ -2088,11 +2033,8 @@ int ga3c_ddpg_twin_create(ga3c_ddpg* m, int32_t policy_delay, float target_sigma
         for (int64_t i = V.off[NACTOR]; i < V.off[NTRAIN]; ++i) init[(size_t)(i - n0)] = 1.f;
       HIPCHK(hipMemcpy(grown[a] + n0, init.data(), sizeof(float) * (n1 - n0), hipMemcpyHostToDevice));
     }
-    std::vector<float**> ptrs;
-    std::vector<size_t> widths;
     float* end = nullptr;
-    work2_table(m, &ptrs, &widths);
-    CHK(vn::carve_rows((size_t)m->cfg.max_batch, widths, ptrs, &t->work_base, &end));
+    CHK(carve_work(m, true, &t->work_base, &end));
     return GA3C_OK;
   };
   const int rc = build();

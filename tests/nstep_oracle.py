@@ -1,5 +1,6 @@
 """Oracle of the n-step returns of the DDPG device actors (Config.DDPG_NSTEP, ga3c_ddpg_nstep_*; the kernel is
-ddpg_actors_nstep_kernel<PendulumBounded> of csrc/ga3c_ddpg.hip), restated in numpy on top of ddpg_actors_oracle.Actors and Ring.
+ddpg_actors_nstep_kernel<PendulumBounded> of csrc/ga3c_ddpg.hip: the step is actor_step, which it shares with
+ddpg_actors_step_kernel, and the window and the emitted row are its own), restated in numpy on top of ddpg_actors_oracle.Actors and Ring.
 
 The rule, as a delay line.  c = 0, 1, 2, .. numbers the transitions an environment has made since its actors were created
 (step(None) makes none; all environments step together, so c is one number).  Each environment keeps its last n transitions
