@@ -87,6 +87,13 @@ class Config:
     DDPG_TARGET_NOISE_CLIP = 0.5        # ... and its c
     DDPG_NSTEP = 1                      # DEVICE_DDPG only: the ring's rows carry n-step returns, R = sum_{k<m} gamma^k r_k cut at an
                                         # episode's end, and y = R + gamma^m q'(s_m) (1..16; 1: one-step rows, as without it)
+    DDPG_DISTRIBUTIONAL = False         # USE_DDPG only: the critic predicts a categorical distribution over DDPG_ATOMS fixed returns,
+                                        # trained by cross-entropy against the projected target distribution; the actor ascends its
+                                        # expectation (Barth-Maron et al. 2018, "D4PG"); needs DDPG_CRITIC_LOSS = 'paired', excludes
+                                        # DDPG_TWIN
+    DDPG_ATOMS = 51                     # atoms of the support (2..64)
+    DDPG_V_MIN = -100.0                 # the support's ends.  EnvironmentPend hands on r 0.005 - 1 in [-1.09, -1]: the gamma = 0.99
+    DDPG_V_MAX = 0.0                    # return over 200 steps lies above -94 and below 0
     tau = 0.001
     gamma = 0.99
     actor_lr = 1.0                      # factors on the annealed learning rate; the later of the two assignments in the
@@ -223,6 +230,8 @@ def resolve_ddpg(explicit=()):
             raise ValueError("PRIORITIZED_REPLAY needs USE_DDPG: only the DDPG handle keeps a replay memory")
         if Config.DDPG_TWIN:
             raise ValueError("DDPG_TWIN needs USE_DDPG: the twin critics are the DDPG handle's")
+        if Config.DDPG_DISTRIBUTIONAL:
+            raise ValueError("DDPG_DISTRIBUTIONAL needs USE_DDPG: the distributional critic is the DDPG handle's")
         _resolve_nstep()
         return
     if not Config.CONTINUOUS_INPUT:
@@ -268,6 +277,18 @@ def resolve_ddpg(explicit=()):
         if not Config.DDPG_TARGET_NOISE >= 0.0 or not Config.DDPG_TARGET_NOISE_CLIP >= 0.0:
             raise ValueError("DDPG_TARGET_NOISE / _CLIP = %r / %r: numbers >= 0"
                              % (Config.DDPG_TARGET_NOISE, Config.DDPG_TARGET_NOISE_CLIP))
+    if Config.DDPG_DISTRIBUTIONAL:
+        if Config.DDPG_CRITIC_LOSS != 'paired':
+            raise ValueError("DDPG_DISTRIBUTIONAL with DDPG_CRITIC_LOSS=%r is not supported: under the fork's loss a row has no "
+                             "target of its own.  Set DDPG_CRITIC_LOSS=paired" % (Config.DDPG_CRITIC_LOSS,))
+        if Config.DDPG_TWIN:
+            raise ValueError("DDPG_DISTRIBUTIONAL with DDPG_TWIN is not supported: two distributions have no smaller one")
+        n = Config.DDPG_ATOMS
+        if isinstance(n, bool) or n != int(n) or not 2 <= int(n) <= 64:
+            raise ValueError("DDPG_ATOMS=%r: a whole number of atoms from 2 to 64" % (n,))
+        if not Config.DDPG_V_MIN < Config.DDPG_V_MAX:
+            raise ValueError("DDPG_V_MIN / DDPG_V_MAX = %r / %r: the support's smaller end first"
+                             % (Config.DDPG_V_MIN, Config.DDPG_V_MAX))
     _resolve_nstep()
     Config.USE_REPLAY_MEMORY = True
     Config.DISCOUNTING = False

@@ -9,7 +9,8 @@ the handle (replay_add*, train_replay); the Ornstein-Uhlenbeck process too, beca
 handle without the interpreter.  Under Config.PRIORITIZED_REPLAY the handle also keeps a priority per ring slot and draws a
 step's rows itself (train_prioritized).  Under Config.DDPG_TWIN it has a second critic, critic2_*, and every
 train-type call runs the twin step (twin_create).  Under Config.DDPG_NSTEP > 1 the device actors write n-step
-returns into the ring and a discount per slot beside them (nstep_create).
+returns into the ring and a discount per slot beside them (nstep_create).  Under Config.DDPG_DISTRIBUTIONAL the
+critic's head has Config.DDPG_ATOMS outputs, a categorical distribution over fixed returns (dist_create).
 """
 import ctypes as C
 import os
@@ -32,8 +33,12 @@ TWIN_TRAINABLE = tuple("critic2_" + k[len("critic_"):] for k in CRITIC_TRAINABLE
 VALUE, TARGET, SLOT_A, SLOT_B, GRAD = range(5)
 
 
-def param_shapes(state_dim, num_actions, twin=False):
+def param_shapes(state_dim, num_actions, twin=False, atoms=None):
     S, A = int(state_dim), int(num_actions)
+    if atoms is not None:                   # a distributional critic: the head has one output per atom
+        shapes = param_shapes(S, A, twin)
+        shapes.update({"critic_output/W": (H2, int(atoms)), "critic_output/b": (int(atoms),)})
+        return shapes
     if twin:                                # + critic 2's, shaped as the critic's
         shapes = param_shapes(S, A)
         shapes.update(zip(TWIN_TRAINABLE, [shapes[k] for k in CRITIC_TRAINABLE]))
@@ -67,15 +72,16 @@ def _draw(rng, name, shape):
     return np.zeros(shape)
 
 
-def initial_arena(state_dim, num_actions, seed, tau=None, twin=False):
+def initial_arena(state_dim, num_actions, seed, tau=None, twin=False, atoms=None):
     """-> (online, target): dicts of f32 arrays for the 20 trainable variables, drawn from one PCG64(seed) stream in variable
     order, the online networks first (actor, critic), then independently drawn targets in the same order.  The reference does
     not copy the online weights: it runs ONE soft update on those targets (NetworkDDPG.py:17-21), restated here.
     twin: critic 2's ten as well, drawn after all of those from the same stream (online, then targets), so that the 20 are
-    what they are without it."""
+    what they are without it.  atoms: critic_output/W and /b at a distributional critic's shapes, drawn in their place of
+    the stream."""
     tau = Config.tau if tau is None else tau
     rng = np.random.Generator(np.random.PCG64(seed))
-    shapes = param_shapes(state_dim, num_actions, twin)
+    shapes = param_shapes(state_dim, num_actions, twin, atoms)
     online, target = {}, {}
     for names in (TRAINABLE,) + ((TWIN_TRAINABLE,) if twin else ()):
         online.update({k: _draw(rng, k, shapes[k]).astype(np.float32) for k in names})
@@ -133,7 +139,11 @@ class Network(DeviceActors, NativeHandle):
         if self.twin:                           # before the initial values: it adds critic 2's variables
             self._call("twin_create", int(Config.DDPG_POLICY_DELAY), float(Config.DDPG_TARGET_NOISE),
                        float(Config.DDPG_TARGET_NOISE_CLIP), int(Config.RANDOM_SEED))
-        online, target = initial_arena(self.S, self.num_actions, Config.RANDOM_SEED, twin=self.twin)
+        self.dist = bool(Config.DDPG_DISTRIBUTIONAL)
+        if self.dist:                           # before the initial values: it reshapes the critic's head
+            self._call("dist_create", int(Config.DDPG_ATOMS), float(Config.DDPG_V_MIN), float(Config.DDPG_V_MAX))
+        online, target = initial_arena(self.S, self.num_actions, Config.RANDOM_SEED, twin=self.twin,
+                                       atoms=int(Config.DDPG_ATOMS) if self.dist else None)
         for k in TRAINABLE + (TWIN_TRAINABLE if self.twin else ()):
             self.set_variable_value(k, online[k], VALUE)
             self.set_variable_value(k, target[k], TARGET)
@@ -309,6 +319,13 @@ class Network(DeviceActors, NativeHandle):
         ms = C.c_float()
         self._call("time_prioritized", int(batch), int(iters), float(self.replay_beta), float(self.learning_rate), C.byref(ms))
         return ms.value
+
+    # ---- distributional critic (Config.DDPG_DISTRIBUTIONAL) ---------------------------------
+    def dist_info(self):
+        """-> (atoms, v_min, v_max) of the handle's critic; atoms = 1 without a distributional one."""
+        n, lo, hi = C.c_int32(), C.c_float(), C.c_float()
+        self._call("dist_info", C.byref(n), C.byref(lo), C.byref(hi))
+        return n.value, lo.value, hi.value
 
     # ---- n-step returns (Config.DDPG_NSTEP, DESIGN.md 8o) ------------------------------------------------
     def nstep_create(self, n):

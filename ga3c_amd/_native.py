@@ -215,6 +215,10 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_nstep_destroy": (C.c_int, [C.c_void_p]),
     "ga3c_ddpg_nstep_get": (C.c_int, [C.c_void_p, f32p, C.c_int64]),
     "ga3c_ddpg_nstep_set": (C.c_int, [C.c_void_p, f32p, C.c_int64]),
+    # distributional critic of a DDPG handle (Config.DDPG_DISTRIBUTIONAL), include/ga3c_abi.h
+    "ga3c_ddpg_dist_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float]),
+    "ga3c_ddpg_dist_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_dist_info": (C.c_int, [C.c_void_p, i32p, f32p, f32p]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

@@ -43,6 +43,12 @@
 //                                  an episode's end, and its discount gamma^m into disc[slot]
 //   nstep_fill_kernel              disc[slot] = gamma for rows added by hand
 // The target kernel reads disc[slot] where a step's rows are ring slots of such a handle, the scalar gamma otherwise.
+// Distributional critic (ga3c_ddpg_dist_create, Config.DDPG_DISTRIBUTIONAL; tests/dist_oracle.py is the same statement):
+//   ddpg_dist_target_kernel  actor_target and the target critic's atom head on s2, the projection of r + g z onto the support in
+//                            gather form (one thread per row and atom, j ascending, no atomics), y and q' as expectations
+//   ddpg_dist_critic_kernel  step 3's forward, the softmax, the cross-entropy and its delta (w / B)(p - m), the trunk's backward
+//   ddpg_dist_actor_kernel   ddpg_actor_kernel's body with dQ/dlogit_k = p_k (z_k - Q) in the scalar weight's place
+// They stand beside the scalar kernels, which compile from the source they had; the launch counts of a step are the same.
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -99,12 +105,13 @@ struct Layout {
   int64_t off[NVARS + 1];
 };
 
-inline Layout make_layout(int S, int A) {
+// N: the outputs of the critic's head, 1 or the atoms of a distributional critic
+inline Layout make_layout(int S, int A, int N = 1) {
   Layout L;
   L.S = S;
   L.A = A;
   const int r[NVARS] = {S, 0, 0, 0, H1, 0, 0, 0, H2, 0, S, 0, 0, 0, H1, 0, A, 0, H2, 0, 0, 0, 0, 0, 0, 0};
-  const int c[NVARS] = {H1, H1, H1, H1, H2, H2, H2, H2, A, A, H1, H1, H1, H1, H2, H2, H2, H2, 1, 1, H1, H1, H2, H2, H1, H1};
+  const int c[NVARS] = {H1, H1, H1, H1, H2, H2, H2, H2, A, A, H1, H1, H1, H1, H2, H2, H2, H2, N, N, H1, H1, H2, H2, H1, H1};
   int64_t o = 0;
   for (int v = 0; v < NVARS; ++v) {
     L.rows[v] = r[v];
@@ -243,9 +250,9 @@ __device__ void actor_fwd(const Layout& L, const float* __restrict__ th, const f
   });
 }
 
-// xin [S][16], act [A][16] -> bufA = c1 [400][16], bufB = c2 [300][16], qv[16] (LDS)
-__device__ void critic_fwd(const Layout& L, const float* __restrict__ th, const float* xin, const float* act, float* bufA,
-                           float* bufB, float* qv, CriticKeep kp, int row0, int nrows) {
+// xin [S][16], act [A][16] -> bufA = c1 [400][16], bufB = c2 [300][16]: the critic below its head
+__device__ __forceinline__ void critic_trunk(const Layout& L, const float* __restrict__ th, const float* xin, const float* act,
+                                             float* bufA, float* bufB, CriticKeep kp, int row0, int nrows) {
   dense_fwd<THREADS>(th + L.off[C_W1], th + L.off[C_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
     float n;
     const float xh = bn_apply(th, L, C_MM1, C_MV1, C_BE1, C_GA1, j, h, &n);
@@ -261,6 +268,12 @@ __device__ void critic_fwd(const Layout& L, const float* __restrict__ th, const 
     bufB[j * TILE + r] = c;
     if (kp.c2 && r < nrows) kp.c2[(size_t)(row0 + r) * H2 + j] = c;
   });
+}
+
+// ... and with the scalar head: -> qv[16] (LDS)
+__device__ void critic_fwd(const Layout& L, const float* __restrict__ th, const float* xin, const float* act, float* bufA,
+                           float* bufB, float* qv, CriticKeep kp, int row0, int nrows) {
+  critic_trunk(L, th, xin, act, bufA, bufB, kp, row0, nrows);
   // q: one thread per row, in j order
   if (threadIdx.x < TILE) {
     const int r = threadIdx.x;
@@ -374,6 +387,20 @@ __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(PerCritic<Layout, 
   }
 }
 
+// bufB = the delta at t [300][16], bufA = c1: the delta at critic_norm1's output (in place over c1: thread k reads and writes
+// row k alone) and at critic_fc1's, to HBM
+__device__ __forceinline__ void critic_bwd1(const Layout& L, const float* __restrict__ th, float* bufA, const float* bufB,
+                                            const CriticRows& w, int row0, int nrows) {
+  dense_bwd(th + L.off[C_W2], H1, H2, bufB, [&](int k, int r, float s) {
+    const float d = bufA[k * TILE + r] > 0.f ? s : 0.f;
+    bufA[k * TILE + r] = d;
+    if (r < nrows) {
+      w.dn1[(size_t)(row0 + r) * H1 + k] = d;
+      w.dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, L, C_MV1, C_GA1, k);
+    }
+  });
+}
+
 // per_w (null without priorities): the rows' importance weights, dq_i = (2/B) w_i (q_i - y_i); keep_x, keep_a (null: not kept):
 // where the step's inputs go
 __device__ __forceinline__ void critic_step(const Layout& L, const float* __restrict__ th, const Rows& src, int B, int paired,
@@ -418,15 +445,7 @@ __device__ __forceinline__ void critic_step(const Layout& L, const float* __rest
     if (r < nrows) w.dt[(size_t)(row0 + r) * H2 + j] = d;
   }
   __syncthreads();
-  // delta at critic_norm1's output (in place over c1: thread k reads and writes row k alone) and at critic_fc1's
-  dense_bwd(th + L.off[C_W2], H1, H2, bufB, [&](int k, int r, float s) {
-    const float d = bufA[k * TILE + r] > 0.f ? s : 0.f;
-    bufA[k * TILE + r] = d;
-    if (r < nrows) {
-      w.dn1[(size_t)(row0 + r) * H1 + k] = d;
-      w.dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, L, C_MV1, C_GA1, k);
-    }
-  });
+  critic_bwd1(L, th, bufA, bufB, w, row0, nrows);
 }
 
 // Critic blockIdx.y's step (NC = 1: the one critic's) on the same rows and the same y.  Critic 1 keeps the inputs.
@@ -437,8 +456,204 @@ __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(PerCritic<Layout, 
   critic_step(L.v[c], th, src, B, paired, per_w, w.y, c ? nullptr : w.c_x, c ? nullptr : w.c_a, w.c[c]);
 }
 
-__global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const float* __restrict__ th, Rows src, int B, Noise nz,
-                                                             Work w) {
+// ------------------------------------------------------------------ distributional critic
+constexpr int ATOMS_MAX = GA3C_DDPG_ATOMS_MAX;
+static_assert(ATOMS_MAX <= MAX_S, "ddpg_dist_critic_kernel keeps the tile's m in the LDS buffer of the states");
+
+// The support, all of it f32: z_k = fmaf((float)k, delta, vmin), delta = (vmax - vmin) / (float)(n - 1) divided once on the host.
+struct Support {
+  int n;
+  float vmin, vmax, delta;
+};
+__device__ __forceinline__ float atom(const Support& z, int k) { return fmaf((float)k, z.delta, z.vmin); }
+
+// What a distributional step writes beside Work's rows: [B,n] each, ce [B].
+struct DistRows { float *pt, *m, *p, *dz, *ce; };
+
+// lg [n][16] <- c2 W_o + b_o on bufB = c2.  dense_fwd's statement (thread k owns atom k and adds in j order from the bias on) with
+// the weights of 15 steps requested at once: the pass is one wave waiting on 300 strided loads, not on its arithmetic.
+__device__ __forceinline__ void dist_logits(const Layout& L, const float* __restrict__ th, const float* bufB, int n, float* lg) {
+  const float* __restrict__ wo = th + L.off[C_WO];
+  for (int k = threadIdx.x; k < n; k += THREADS) {
+    float acc[TILE];
+    const float b = th[L.off[C_BO] + k];
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) acc[r] = b;
+#pragma unroll 15
+    for (int j = 0; j < H2; ++j) tile_fma(acc, bufB + j * TILE, wo[(size_t)j * n + k]);
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) lg[k * TILE + r] = acc[r];
+  }
+  __syncthreads();
+}
+
+// Row r's softmax by the one thread that calls it: the row maximum, the sum of exp(l - max) in k order, p_k = exp(l_k - max) / sum;
+// lg[k][r] <- each(k, p_k, log p_k) with log p_k = (l_k - max) - log(sum), which stays finite where p_k rounds to zero.
+// -> sum_k z_k p_k in k order.
+template <class F>
+__device__ __forceinline__ float dist_softmax(float* lg, int r, const Support& z, F each) {
+  float mx = lg[r];
+  for (int k = 1; k < z.n; ++k) mx = fmaxf(mx, lg[k * TILE + r]);
+  float s = 0.f;
+  for (int k = 0; k < z.n; ++k) s += expf(lg[k * TILE + r] - mx);
+  const float ls = logf(s);
+  float q = 0.f;
+  for (int k = 0; k < z.n; ++k) {
+    const float t = lg[k * TILE + r] - mx;
+    const float p = expf(t) / s;
+    q = fmaf(atom(z, k), p, q);
+    lg[k * TILE + r] = each(k, p, t - ls);
+  }
+  return q;
+}
+
+// bufB [300][16] <- relu'(t_j) sum_k lg[k][r] W_o[j][k]: dense_bwd's statement (thread j owns row j of W_o and adds in k order),
+// 16 of the row's weights requested at once; dt (may be null): the same to HBM
+__device__ __forceinline__ void dist_head_bwd(const Layout& L, const float* __restrict__ th, const float* lg, int n, float* bufB,
+                                              float* dt, int row0, int nrows) {
+  for (int j = threadIdx.x; j < H2; j += THREADS) {
+    float acc[TILE];
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) acc[r] = 0.f;
+    const float* __restrict__ wr = th + L.off[C_WO] + (size_t)j * n;
+#pragma unroll 16
+    for (int k = 0; k < n; ++k) tile_fma(acc, lg + k * TILE, wr[k]);
+#pragma unroll
+    for (int r = 0; r < TILE; ++r) {
+      const float d = bufB[j * TILE + r] > 0.f ? acc[r] : 0.f;
+      bufB[j * TILE + r] = d;
+      if (dt && r < nrows) dt[(size_t)(row0 + r) * H2 + j] = d;
+    }
+  }
+  __syncthreads();
+}
+
+// Steps 1-2 of a distributional step.  p' = softmax of the target critic's head at (s2, actor_target(s2)); per row g = 0 on a
+// done row or without `future`, else the row's discount (row_discount); Tz_j = clip(fmaf(g, z_j, r), vmin, vmax),
+// b_j = (Tz_j - vmin) / delta; m_k = sum_j p'_j max(0, 1 - |b_j - k|), j ascending, by the thread of (row, k); y = sum_k z_k m_k,
+// q' = sum_k z_k p'_k.  Without `future` no net is evaluated: p' and q' are zero and m_k = max(0, 1 - |b - k|), b from r alone.
+// b and m lie over bufA, which the trunk is done with.
+__global__ __launch_bounds__(THREADS) void ddpg_dist_target_kernel(Layout L, const float* __restrict__ thT, Rows src, int B,
+                                                                   float gamma, int future, Support z, float* __restrict__ y,
+                                                                   float* __restrict__ qt, DistRows d,
+                                                                   const float* __restrict__ disc, float* __restrict__ used) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float lg[ATOMS_MAX * TILE];
+  __shared__ float qv[TILE];
+  const int S = L.S, A = L.A, n = z.n;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  if (future) {
+    load_rows(src, S + A + 2, S, xin, row0, nrows, nullptr);
+    __syncthreads();
+    actor_fwd(L, thT, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    critic_trunk(L, thT, xin, act, bufA, bufB, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+    dist_logits(L, thT, bufB, n, lg);
+    if (threadIdx.x < TILE) qv[threadIdx.x] = dist_softmax(lg, threadIdx.x, z, [](int, float p, float) { return p; });
+  } else {
+    for (int e = threadIdx.x; e < n * TILE; e += THREADS) lg[e] = 0.f;
+    if (threadIdx.x < TILE) qv[threadIdx.x] = 0.f;
+  }
+  __syncthreads();
+  float* bb = bufA;
+  float* mm = bufA + ATOMS_MAX * TILE;
+  for (int e = threadIdx.x; e < n * TILE; e += THREADS) {
+    const int j = e / TILE, r = e % TILE;
+    float b = 0.f;
+    if (r < nrows) {
+      const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
+      const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
+      const float disc_r = row_discount(disc, j == 0 ? used : nullptr, slot, row0 + r, gamma);
+      const float g = future && done == 0.f ? disc_r : 0.f;
+      const float tz = fminf(fmaxf(fmaf(g, atom(z, j), rew), z.vmin), z.vmax);
+      b = (tz - z.vmin) / z.delta;
+      d.pt[(size_t)(row0 + r) * n + j] = lg[e];
+    }
+    bb[e] = b;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < n * TILE; e += THREADS) {
+    const int k = e / TILE, r = e % TILE;
+    float m = 0.f;
+    if (future) {
+      for (int j = 0; j < n; ++j) m = fmaf(lg[j * TILE + r], fmaxf(0.f, 1.0f - fabsf(bb[j * TILE + r] - (float)k)), m);
+    } else {
+      m = fmaxf(0.f, 1.0f - fabsf(bb[r] - (float)k));
+    }
+    mm[e] = m;
+    if (r < nrows) d.m[(size_t)(row0 + r) * n + k] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x < nrows) {
+    const int r = threadIdx.x;
+    float s = 0.f;
+    for (int k = 0; k < n; ++k) s = fmaf(atom(z, k), mm[k * TILE + r], s);
+    y[row0 + r] = s;
+    qt[row0 + r] = qv[r];
+  }
+}
+
+// Step 3's forward and backward of a distributional step: p = softmax(logits), q = sum_k z_k p_k, the row's cross-entropy
+// ce = -sum_k m_k log p_k, dz_k = (w / B)(p_k - m_k) (w: per_w's weight, 1 without), the delta at t from dz through W_o, and below
+// that the scalar critic's backward.  "dq" is not written.
+__global__ __launch_bounds__(THREADS) void ddpg_dist_critic_kernel(Layout L, const float* __restrict__ th, Rows src, int B,
+                                                                   const float* __restrict__ per_w, Support z, Work w, DistRows d) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float lg[ATOMS_MAX * TILE];
+  const int S = L.S, A = L.A, n = z.n;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  const CriticRows& cr = w.c[0];
+  load_rows(src, 0, S, xin, row0, nrows, w.c_x);
+  load_rows(src, S, A, act, row0, nrows, w.c_a);
+  __syncthreads();
+  critic_trunk(L, th, xin, act, bufA, bufB, CriticKeep{cr.xh1, cr.c1, cr.c2}, row0, nrows);
+  float* mm = xin;                     // the trunk is done with the states: the tile's m [n][16], read once and coalesced
+  for (int e = threadIdx.x; e < n * TILE; e += THREADS) {
+    const int r = e / n, k = e % n;
+    mm[k * TILE + r] = r < nrows ? d.m[(size_t)(row0 + r) * n + k] : 0.f;
+  }
+  dist_logits(L, th, bufB, n, lg);     // ends in a barrier
+  if (threadIdx.x < TILE) {
+    const int r = threadIdx.x;
+    const bool live = r < nrows;
+    const size_t at = (size_t)(row0 + r) * n;
+    float c = 0.f;
+    if (live) {
+      c = 1.0f / (float)B;
+      if (per_w) c *= per_w[row0 + r];
+    }
+    float ce = 0.f;
+    const float q = dist_softmax(lg, r, z, [&](int k, float p, float logp) {
+      const float m = mm[k * TILE + r];
+      const float dz = c * (p - m);
+      ce = fmaf(-m, logp, ce);
+      if (live) {
+        d.p[at + k] = p;
+        d.dz[at + k] = dz;
+      }
+      return dz;
+    });
+    if (live) {
+      cr.q[row0 + r] = q;
+      d.ce[row0 + r] = ce;
+    }
+  }
+  __syncthreads();
+  dist_head_bwd(L, th, lg, n, bufB, cr.dt, row0, nrows);
+  critic_bwd1(L, th, bufA, bufB, cr, row0, nrows);
+}
+
+// Steps 4-5's rows.  DIST: the critic's head is the atom head and dQ/dlogit_k = p_k (z_k - Q) stands where the scalar head has
+// its weight: bufB[j] = relu'(t_j) sum_k p_k (z_k - Q) W_o[j][k].  lg: [n][16] in LDS, DIST only.  (static: its LDS arrays stay
+// internal to each kernel, so the scalar kernel drops the head's q, which it does not read, as it did.)
+template <bool DIST>
+static __device__ __forceinline__ void actor_rows(const Layout& L, const float* __restrict__ th, const Rows& src, int B, const Noise& nz,
+                                           const Work& w, const Support& z, float* lg) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
@@ -459,10 +674,22 @@ __global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const flo
   }
   __syncthreads();
   // the updated critic at (s, a_out); only the relu mask of t is needed for dq/da
-  critic_fwd(L, th, xin, noisy, bufA, bufB, qv, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
-  const float* __restrict__ wo = th + L.off[C_WO];
-  for (int e = threadIdx.x; e < H2 * TILE; e += THREADS) bufB[e] = bufB[e] > 0.f ? wo[e / TILE] : 0.f;
-  __syncthreads();
+  if constexpr (DIST) {
+    critic_trunk(L, th, xin, noisy, bufA, bufB, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+    dist_logits(L, th, bufB, z.n, lg);
+    if (threadIdx.x < TILE) {
+      const int r = threadIdx.x;
+      const float q = dist_softmax(lg, r, z, [](int, float p, float) { return p; });
+      for (int k = 0; k < z.n; ++k) lg[k * TILE + r] *= atom(z, k) - q;
+    }
+    __syncthreads();
+    dist_head_bwd(L, th, lg, z.n, bufB, nullptr, row0, nrows);
+  } else {
+    critic_fwd(L, th, xin, noisy, bufA, bufB, qv, CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+    const float* __restrict__ wo = th + L.off[C_WO];
+    for (int e = threadIdx.x; e < H2 * TILE; e += THREADS) bufB[e] = bufB[e] > 0.f ? wo[e / TILE] : 0.f;
+    __syncthreads();
+  }
   // g = dq/da (per row, no 1/B); the delta at actor_output's pre-activation is -g (1 - out^2)
   dense_bwd(th + L.off[C_WN], A, H2, bufB, [&](int i, int r, float g) {
     const float d = -g * dact[i * TILE + r];
@@ -490,6 +717,17 @@ __global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const flo
       w.a_dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, L, A_MV1, A_GA1, k);
     }
   });
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_actor_kernel(Layout L, const float* __restrict__ th, Rows src, int B, Noise nz,
+                                                             Work w) {
+  actor_rows<false>(L, th, src, B, nz, w, Support{1, 0.f, 0.f, 0.f}, nullptr);
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_dist_actor_kernel(Layout L, const float* __restrict__ th, Rows src, int B, Noise nz,
+                                                                  Work w, Support z) {
+  __shared__ __attribute__((aligned(16))) float lg[ATOMS_MAX * TILE];
+  actor_rows<true>(L, th, src, B, nz, w, z, lg);
 }
 
 __global__ __launch_bounds__(THREADS) void ddpg_predict_kernel(Layout L, const float* __restrict__ th, Input in, int B, Noise nz,
@@ -1018,6 +1256,12 @@ struct NStep {
   float* used = nullptr;                // [max_batch] the discounts the last step's target took
 };
 
+// A distributional critic of a handle (ga3c_ddpg_dist_create).  The handle's Layout has z.n columns in the critic's head.
+struct Dist {
+  Support z{1, 0.f, 0.f, 0.f};
+  float* work_base = nullptr;           // the rows of the handle's DistRows
+};
+
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
   ga3c_ddpg_config cfg;
   Layout L;
@@ -1041,6 +1285,8 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   DActors* actors = nullptr;      // null: no device actors
   Twin* twin = nullptr;           // null: one critic
   NStep* nstep = nullptr;         // null: one-step rows, the scalar gamma everywhere
+  Dist* dist = nullptr;           // null: the scalar critic
+  DistRows dw{};                  // its rows, null without
   std::vector<std::string> tnames;      // the target copies' names, by variable
 };
 
@@ -1048,36 +1294,42 @@ namespace {
 
 int tiles(int B) { return (B + TILE - 1) / TILE; }
 
-// The rows of the train workspace by the name ga3c_ddpg_fetch knows them under.  twin: the row exists while the handle has twin
-// critics, in a block of its own (Twin::work_base); the others live as long as the handle (work_base).
+// The rows of the train workspace by the name ga3c_ddpg_fetch knows them under.  tag: W_TWIN rows exist while the handle has twin
+// critics, W_DIST rows while it has a distributional critic, each kind in a block of its own (Twin::work_base, Dist::work_base);
+// the others live as long as the handle (work_base).
+enum WorkTag { W_CORE, W_TWIN, W_DIST };
 struct WorkRow {
   const char* name;
   float** ptr;
   size_t width;
-  bool twin;
+  WorkTag tag;
 };
 
 std::vector<WorkRow> work_table(ga3c_ddpg* m) {
   const size_t S = m->L.S, A = m->L.A;
   Work& w = m->w;
   CriticRows &c = w.c[0], &d = w.c[1];
-  return {{"y", &w.y, 1, false},           {"qt", &w.qt, 1, false},         {"q", &c.q, 1, false},           {"dq", &c.dq, 1, false},
-          {"c_x", &w.c_x, S, false},       {"c_a", &w.c_a, A, false},       {"c_xh1", &c.xh1, H1, false},    {"c_c1", &c.c1, H1, false},
-          {"c_dn1", &c.dn1, H1, false},    {"c_dh1", &c.dh1, H1, false},    {"c_c2", &c.c2, H2, false},      {"c_dt", &c.dt, H2, false},
-          {"a_xh1", &w.a_xh1, H1, false},  {"a_a1", &w.a_a1, H1, false},    {"a_dn1", &w.a_dn1, H1, false},  {"a_dh1", &w.a_dh1, H1, false},
-          {"a_xh2", &w.a_xh2, H2, false},  {"a_a2", &w.a_a2, H2, false},    {"a_dn2", &w.a_dn2, H2, false},  {"a_dh2", &w.a_dh2, H2, false},
-          {"a_out", &w.a_out, A, false},   {"a_noisy", &w.a_noisy, A, false}, {"g", &w.g, A, false},         {"do", &w.dout, A, false},
-          {"qt1", &w.qt1, 1, true},        {"qt2", &w.qt2, 1, true},        {"q2", &d.q, 1, true},           {"dq2", &d.dq, 1, true},
-          {"t_eps", &w.t_eps, A, true},    {"t_a", &w.t_a, A, true},        {"c2_xh1", &d.xh1, H1, true},    {"c2_c1", &d.c1, H1, true},
-          {"c2_dn1", &d.dn1, H1, true},    {"c2_dh1", &d.dh1, H1, true},    {"c2_c2", &d.c2, H2, true},      {"c2_dt", &d.dt, H2, true}};
+  DistRows& z = m->dw;
+  const size_t N = m->dist ? (size_t)m->dist->z.n : 0;
+  return {{"y", &w.y, 1, W_CORE},           {"qt", &w.qt, 1, W_CORE},         {"q", &c.q, 1, W_CORE},           {"dq", &c.dq, 1, W_CORE},
+          {"c_x", &w.c_x, S, W_CORE},       {"c_a", &w.c_a, A, W_CORE},       {"c_xh1", &c.xh1, H1, W_CORE},    {"c_c1", &c.c1, H1, W_CORE},
+          {"c_dn1", &c.dn1, H1, W_CORE},    {"c_dh1", &c.dh1, H1, W_CORE},    {"c_c2", &c.c2, H2, W_CORE},      {"c_dt", &c.dt, H2, W_CORE},
+          {"a_xh1", &w.a_xh1, H1, W_CORE},  {"a_a1", &w.a_a1, H1, W_CORE},    {"a_dn1", &w.a_dn1, H1, W_CORE},  {"a_dh1", &w.a_dh1, H1, W_CORE},
+          {"a_xh2", &w.a_xh2, H2, W_CORE},  {"a_a2", &w.a_a2, H2, W_CORE},    {"a_dn2", &w.a_dn2, H2, W_CORE},  {"a_dh2", &w.a_dh2, H2, W_CORE},
+          {"a_out", &w.a_out, A, W_CORE},   {"a_noisy", &w.a_noisy, A, W_CORE}, {"g", &w.g, A, W_CORE},         {"do", &w.dout, A, W_CORE},
+          {"qt1", &w.qt1, 1, W_TWIN},        {"qt2", &w.qt2, 1, W_TWIN},        {"q2", &d.q, 1, W_TWIN},           {"dq2", &d.dq, 1, W_TWIN},
+          {"t_eps", &w.t_eps, A, W_TWIN},    {"t_a", &w.t_a, A, W_TWIN},        {"c2_xh1", &d.xh1, H1, W_TWIN},    {"c2_c1", &d.c1, H1, W_TWIN},
+          {"c2_dn1", &d.dn1, H1, W_TWIN},    {"c2_dh1", &d.dh1, H1, W_TWIN},    {"c2_c2", &d.c2, H2, W_TWIN},      {"c2_dt", &d.dt, H2, W_TWIN},
+          {"d_pt", &z.pt, N, W_DIST},      {"d_m", &z.m, N, W_DIST},        {"d_p", &z.p, N, W_DIST},        {"d_dz", &z.dz, N, W_DIST},
+          {"d_ce", &z.ce, 1, W_DIST}};
 }
 
-// One zeroed block for the table's rows with `twin` set, or for those without; *end: the four floats behind them.
-int carve_work(ga3c_ddpg* m, bool twin, float** base, float** end) {
+// One zeroed block for the table's rows of one tag; *end: the four floats behind them.
+int carve_work(ga3c_ddpg* m, WorkTag tag, float** base, float** end) {
   std::vector<float**> ptrs;
   std::vector<size_t> widths;
   for (const WorkRow& r : work_table(m))
-    if (r.twin == twin) {
+    if (r.tag == tag) {
       ptrs.push_back(r.ptr);
       widths.push_back(r.width);
     }
@@ -1116,6 +1368,10 @@ GradSrc grad_src(ga3c_ddpg* m, int c) {
   set(C_BN, nullptr, 0, cr.dt, H2, nullptr);
   set(C_WO, cr.c2, H2, cr.dq, 1, nullptr);
   set(C_BO, nullptr, 0, cr.dq, 1, nullptr);
+  if (m->dist) {                                   // the head's delta is dz [B,n] (no twin then: c = 0)
+    set(C_WO, cr.c2, H2, m->dw.dz, m->dist->z.n, nullptr);
+    set(C_BO, nullptr, 0, m->dw.dz, m->dist->z.n, nullptr);
+  }
   return g;
 }
 
@@ -1187,9 +1443,19 @@ int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise
     tg.sigma = tw.sigma; tg.clip = tw.clip; tg.seed = tw.seed; tg.number = (uint64_t)t;
   }
   const dim3 grid(tiles(B)), gridc(tiles(B), NC), block(THREADS);
-  hipLaunchKernelGGL(ddpg_target_kernel<NC>, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma,
-                     (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0, tg, row_discounts(m, rows), m->nstep ? m->nstep->used : nullptr);
-  hipLaunchKernelGGL(ddpg_critic_kernel<NC>, gridc, block, 0, m->st, L, (const float*)m->arena[0], rows, B, paired, per_w, w);
+  const Dist* ds = NC == 1 ? m->dist : nullptr;    // a distributional critic: its three kernels in the scalar ones' places
+  const int future = (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0;
+  float* used = m->nstep ? m->nstep->used : nullptr;
+  if (ds) {
+    hipLaunchKernelGGL(ddpg_dist_target_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[1], rows, B, c.gamma, future,
+                       ds->z, w.y, w.qt, m->dw, row_discounts(m, rows), used);
+    hipLaunchKernelGGL(ddpg_dist_critic_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, per_w, ds->z, w,
+                       m->dw);
+  } else {
+    hipLaunchKernelGGL(ddpg_target_kernel<NC>, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma, future, tg,
+                       row_discounts(m, rows), used);
+    hipLaunchKernelGGL(ddpg_critic_kernel<NC>, gridc, block, 0, m->st, L, (const float*)m->arena[0], rows, B, paired, per_w, w);
+  }
   const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
   const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
   const Opt oc = make_opt(m, false, lr, t, true, full && policy);
@@ -1200,7 +1466,8 @@ int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise
     hipLaunchKernelGGL((ddpg_wgrad_kernel<NC, true>), dim3(cblocks, NC), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
   }
   if (stop_after >= 4 && policy) {
-    hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w);
+    if (ds) hipLaunchKernelGGL(ddpg_dist_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w, ds->z);
+    else hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w);
     const Opt oa = make_opt(m, true, lr, t / delay, full, full);
     hipLaunchKernelGGL((ddpg_wgrad_kernel<1, true>), dim3(ablocks), block, 0, m->st, PerCritic<Layout, 1>{{m->L}},
                        PerCritic<GradSrc, 1>{{gs.v[0]}}, 0, NACTOR, B, oa, w);
@@ -1321,7 +1588,7 @@ void twin_free(ga3c_ddpg* m) {
   (void)hipFree(t->work_base);
   (void)hipGetLastError();
   for (const WorkRow& r : work_table(m))
-    if (r.twin) *r.ptr = nullptr;
+    if (r.tag == W_TWIN) *r.ptr = nullptr;
   delete t;
   m->twin = nullptr;
   m->vars.resize(NVARS);            // the arenas keep their size: nothing names what lies behind the 26
@@ -1348,6 +1615,56 @@ void nstep_free(ga3c_ddpg* m) {
   m->nstep = nullptr;
 }
 
+// The five arenas re-laid for a critic head of `atoms` outputs (1: the scalar head).  Every variable keeps its value, target
+// copy, slots and gradient; critic_output/W and /b, whose shapes change, are as ga3c_ddpg_create leaves variables: zero, the
+// RMSProp ms slot one.  The variable table is refilled.  Caller holds train_mu and mu; the handle has no twin critics.
+int relay_head(ga3c_ddpg* m, int atoms) {
+  const Layout L0 = m->L, L1 = make_layout(L0.S, L0.A, atoms);
+  const int64_t n0 = L0.off[NVARS], n1 = L1.off[NVARS];
+  float* laid[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto build = [&]() -> int {
+    HIPCHK(hipStreamSynchronize(m->st));           // a prediction in flight has finished before its arena is freed
+    std::vector<float> a0((size_t)n0), a1((size_t)n1);
+    for (int a = 0; a < m->narena; ++a) {
+      HIPCHK(hipMemcpy(a0.data(), m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToHost));
+      const float head = a == 2 && !(m->cfg.flags & GA3C_DDPG_CRITIC_ADAM) ? 1.f : 0.f;
+      for (int v = 0; v < NVARS; ++v) {
+        if (v == C_WO || v == C_BO) std::fill(a1.begin() + L1.off[v], a1.begin() + L1.off[v + 1], head);
+        else std::copy(a0.begin() + L0.off[v], a0.begin() + L0.off[v + 1], a1.begin() + L1.off[v]);
+      }
+      CHK(vn::dalloc(&laid[a], (size_t)n1));
+      HIPCHK(hipMemcpy(laid[a], a1.data(), sizeof(float) * n1, hipMemcpyHostToDevice));
+    }
+    return GA3C_OK;
+  };
+  const int rc = build();
+  if (rc != GA3C_OK) {
+    for (float* g : laid) (void)hipFree(g);
+    (void)hipGetLastError();
+    return rc;
+  }
+  for (int a = 0; a < m->narena; ++a) {
+    (void)hipFree(m->arena[a]);
+    m->arena[a] = laid[a];
+  }
+  m->L = L1;
+  m->vars.clear();
+  m->tnames.clear();
+  fill_vars(m);
+  return GA3C_OK;
+}
+
+// The state and its rows; the arenas stay as they are laid (dist_destroy re-lays them first, ga3c_ddpg_destroy frees them).
+void dist_free(ga3c_ddpg* m) {
+  Dist* d = m->dist;
+  if (!d) return;
+  (void)hipFree(d->work_base);
+  (void)hipGetLastError();
+  m->dw = DistRows{};
+  delete d;
+  m->dist = nullptr;
+}
+
 void dactors_free(ga3c_ddpg* m) {
   ga3c_actors::actors_free(m->actors);
   m->actors = nullptr;
@@ -1362,6 +1679,7 @@ void free_all(ga3c_ddpg* m) {
   per_free(m);
   twin_free(m);
   nstep_free(m);
+  dist_free(m);
   vn::free_core(m);
   (void)hipFree(m->work_base);
   (void)hipFree(m->ring);
@@ -1388,7 +1706,7 @@ int alloc_all(ga3c_ddpg* m) {
     for (int64_t i = m->L.off[NACTOR]; i < m->L.off[NTRAIN]; ++i) init[(size_t)i] = 1.f;
     HIPCHK(hipMemcpy(m->arena[2], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
   }
-  CHK(carve_work(m, false, &m->work_base, &m->w.qstat));
+  CHK(carve_work(m, W_CORE, &m->work_base, &m->w.qstat));
   CHK(vn::dalloc(&m->ring, (size_t)c.replay_capacity * rowf));
   HIPCHK(hipMemset(m->ring, 0, sizeof(float) * (size_t)c.replay_capacity * rowf));
   CHK(vn::halloc(&m->h_stage, B * rowf)); CHK(vn::dalloc(&m->d_stage, B * rowf));
@@ -1570,7 +1888,24 @@ int ga3c_ddpg_set_step(ga3c_ddpg* m, int64_t step) {      // Adam's t: never bel
   return vn::set_step(m, step);
 }
 
-int ga3c_ddpg_save(ga3c_ddpg* m, const char* path) { return vn::save(m, path); }
+// A distributional handle's file also holds "dist_support", f32 [2]: vmin, vmax (the atoms are critic_output/W's columns).
+int ga3c_ddpg_save(ga3c_ddpg* m, const char* path) {
+  if (!m || !path) return fail(GA3C_EINVAL, "null argument");
+  if (!m->dist) return vn::save(m, path);
+  ga3c_ckpt::Arenas arena;
+  CHK(vn::read_arenas(m, &arena));
+  std::vector<ga3c_ckpt::Member> members = ga3c_ckpt::pack_members(m->vars, m->step.load(), arena);
+  const float support[2] = {m->dist->z.vmin, m->dist->z.vmax};
+  ga3c_ckpt::Member mb;
+  mb.name = "dist_support";
+  mb.descr = "<f4";
+  mb.shape = {2};
+  mb.bytes.assign(reinterpret_cast<const uint8_t*>(support), reinterpret_cast<const uint8_t*>(support) + sizeof support);
+  members.insert(members.begin() + 1, std::move(mb));        // beside "step"
+  std::string err;
+  if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
+  return GA3C_OK;
+}
 
 int ga3c_ddpg_load(ga3c_ddpg* m, const char* path) {
   if (!m || !path) return fail(GA3C_EINVAL, "null argument");
@@ -1581,7 +1916,18 @@ int ga3c_ddpg_load(ga3c_ddpg* m, const char* path) {
   if (step < 0) return fail(GA3C_ESTATE, "%s: step %lld", path, (long long)step);      // before anything is written
   if (!m->twin && members.count(std::string(TWIN_VAR_NAMES[0]) + ":0"))
     return fail(GA3C_ESTATE, "%s holds %s: the checkpoint of a handle with twin critics, which this one has not", path, TWIN_VAR_NAMES[0]);
-  return vn::load(m, path, members);
+  const auto sup = members.find("dist_support");
+  if (!m->dist && sup != members.end())
+    return fail(GA3C_ESTATE, "%s holds dist_support: the checkpoint of a handle with a distributional critic, which this one has not", path);
+  if (m->dist) {
+    float v[2];
+    if (sup == members.end() || sup->second.descr != "<f4" || sup->second.bytes.size() != sizeof v)
+      return fail(GA3C_ESTATE, "%s holds no f32 dist_support [2]: not the checkpoint of a handle with a distributional critic", path);
+    memcpy(v, sup->second.bytes.data(), sizeof v);
+    if (v[0] != m->dist->z.vmin || v[1] != m->dist->z.vmax)
+      return fail(GA3C_ESTATE, "%s: support [%g, %g], this handle's is [%g, %g]", path, v[0], v[1], m->dist->z.vmin, m->dist->z.vmax);
+  }
+  return vn::load(m, path, members);                          // another atom count is another shape of critic_output/W
 }
 
 int ga3c_ddpg_noise_step(ga3c_ddpg* m, float* x, float* n) {
@@ -1793,11 +2139,13 @@ int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
   }
   for (const WorkRow& r : work_table(m)) {
     if (strcmp(name, r.name) != 0) continue;
-    if (!r.twin) return vn::fetch(m, name, *r.ptr, (int64_t)r.width, out, count);
-    HIPCHK(hipSetDevice(m->device));                // under both locks throughout: twin_destroy frees these rows
+    if (r.tag == W_CORE) return vn::fetch(m, name, *r.ptr, (int64_t)r.width, out, count);
+    HIPCHK(hipSetDevice(m->device));                // under both locks throughout: twin_destroy / dist_destroy free these rows
     std::lock_guard<std::mutex> tl(m->train_mu);
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!m->twin) return fail(GA3C_ESTATE, "%s: the handle has no twin critics (ga3c_ddpg_twin_create)", name);
+    if (r.tag == W_TWIN && !m->twin) return fail(GA3C_ESTATE, "%s: the handle has no twin critics (ga3c_ddpg_twin_create)", name);
+    if (r.tag == W_DIST && !m->dist)
+      return fail(GA3C_ESTATE, "%s: the handle has no distributional critic (ga3c_ddpg_dist_create)", name);
     const int64_t want = (int64_t)r.width * m->last_B;
     if (count != want) return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)want, (long long)count);
     HIPCHK(hipStreamSynchronize(m->st));
@@ -2007,6 +2355,7 @@ int ga3c_ddpg_twin_create(ga3c_ddpg* m, int32_t policy_delay, float target_sigma
   std::lock_guard<std::mutex> tl(m->train_mu);
   std::lock_guard<std::mutex> lk(m->mu);
   if (m->twin) return fail(GA3C_ESTATE, "the handle has twin critics already");
+  if (m->dist) return fail(GA3C_ESTATE, "the handle has a distributional critic: two distributions have no smaller one");
   Twin* t = new (std::nothrow) Twin();
   if (!t) return fail(GA3C_EINVAL, "out of host memory");
   t->delay = policy_delay;
@@ -2034,7 +2383,7 @@ int ga3c_ddpg_twin_create(ga3c_ddpg* m, int32_t policy_delay, float target_sigma
       HIPCHK(hipMemcpy(grown[a] + n0, init.data(), sizeof(float) * (n1 - n0), hipMemcpyHostToDevice));
     }
     float* end = nullptr;
-    CHK(carve_work(m, true, &t->work_base, &end));
+    CHK(carve_work(m, W_TWIN, &t->work_base, &end));
     return GA3C_OK;
   };
   const int rc = build();
@@ -2063,6 +2412,54 @@ int ga3c_ddpg_twin_destroy(ga3c_ddpg* m) {
   if (!m->twin) return fail(GA3C_ESTATE, "the handle has no twin critics (ga3c_ddpg_twin_create)");
   HIPCHK(hipStreamSynchronize(m->st));
   twin_free(m);
+  return GA3C_OK;
+}
+
+// ---- distributional critic
+
+int ga3c_ddpg_dist_create(ga3c_ddpg* m, int32_t atoms, float vmin, float vmax) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (atoms < 2 || atoms > GA3C_DDPG_ATOMS_MAX) return fail(GA3C_EINVAL, "atoms %d outside [2,%d]", atoms, GA3C_DDPG_ATOMS_MAX);
+  if (!std::isfinite(vmin) || !std::isfinite(vmax) || !(vmin < vmax))
+    return fail(GA3C_EINVAL, "support [%g, %g]: two finite numbers, the first the smaller", vmin, vmax);
+  const float delta = (vmax - vmin) / (float)(atoms - 1);
+  if (!std::isfinite(delta) || !(delta > 0.f)) return fail(GA3C_EINVAL, "support [%g, %g]: its width is not an f32", vmin, vmax);
+  if (!(m->cfg.flags & GA3C_DDPG_LOSS_PAIRED))
+    return fail(GA3C_ESTATE, "a distributional critic needs GA3C_DDPG_LOSS_PAIRED: under the fork's loss a row has no target of "
+                             "its own");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (m->dist) return fail(GA3C_ESTATE, "the handle has a distributional critic already");
+  if (m->twin) return fail(GA3C_ESTATE, "the handle has twin critics: two distributions have no smaller one");
+  Dist* d = new (std::nothrow) Dist();
+  if (!d) return fail(GA3C_EINVAL, "out of host memory");
+  d->z = Support{atoms, vmin, vmax, delta};
+  m->dist = d;                                     // work_table sizes the rows by it
+  float* end = nullptr;
+  int rc = carve_work(m, W_DIST, &d->work_base, &end);
+  if (rc == GA3C_OK) rc = relay_head(m, atoms);
+  if (rc != GA3C_OK) dist_free(m);
+  return rc;
+}
+
+int ga3c_ddpg_dist_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!m->dist) return fail(GA3C_ESTATE, "the handle has no distributional critic (ga3c_ddpg_dist_create)");
+  CHK(relay_head(m, 1));
+  dist_free(m);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_dist_info(ga3c_ddpg* m, int32_t* atoms, float* vmin, float* vmax) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (atoms) *atoms = m->dist ? m->dist->z.n : 1;
+  if (vmin) *vmin = m->dist ? m->dist->z.vmin : 0.f;
+  if (vmax) *vmax = m->dist ? m->dist->z.vmax : 0.f;
   return GA3C_OK;
 }
 

@@ -766,6 +766,45 @@ int ga3c_ddpg_nstep_destroy(ga3c_ddpg* net);
 int ga3c_ddpg_nstep_get(ga3c_ddpg* net, float* disc, int64_t count);
 int ga3c_ddpg_nstep_set(ga3c_ddpg* net, const float* disc, int64_t count);
 
+/* ---- Distributional critic of a DDPG handle (Config.DDPG_DISTRIBUTIONAL; tests/dist_oracle.py is the same statement
+ * in numpy): the critic predicts a categorical distribution over `atoms` fixed returns and is trained by cross-entropy against
+ * the projected target distribution (Bellemare et al. 2017); the actor ascends its expectation (Barth-Maron et al. 2018).
+ * Attached to a created handle before its initial values are set, as the twin critics are; a handle without it runs what it ran
+ * before.  With N = atoms:
+ *   support  z_k = fmaf((f32) k, delta, vmin), delta = (vmax - vmin) / (f32)(N - 1), k = 0..N-1: everything in f32, from the f32
+ *            vmin and vmax of the call.
+ *   head     critic_output/W is [300,N], /b [N]; logits = c2 W + b, p = softmax(logits) with the row maximum subtracted first,
+ *            q = sum_k z_k p_k in k order.  q is what "q", q_stats and "per_td" see.
+ *   target   p' = softmax of the target critic at (s2, actor_target(s2)); g = 0 on a done row or without GA3C_DDPG_FUTURE_REWARD,
+ *            else the row's discount (disc[slot] where a handle with n-step returns trains on ring slots, gamma otherwise);
+ *            Tz_j = clip(r + g z_j, vmin, vmax), b_j = (Tz_j - vmin) / delta, m_k = sum_j p'_j max(0, 1 - |b_j - k|) with j
+ *            ascending, one thread per (row, k): the C51 projection in gather form, no atomics, continuous in b, and whole where
+ *            a b_j is an integer.  "y" = sum_k z_k m_k, "qt" = sum_k z_k p'_k.  Without GA3C_DDPG_FUTURE_REWARD no target net is
+ *            evaluated: "d_pt" and "qt" are zero and m_k = max(0, 1 - |b - k|) with b from r alone.
+ *   critic   L = (1/B) sum_i w_i ce_i, ce_i = -sum_k m_ik log p_ik, w the importance weights under priorities, else 1;
+ *            dz_ik = (w_i / B)(p_ik - m_ik); the delta at the second layer is relu'(t_j) sum_k dz_ik W_o[j][k] in k order, and below
+ *            it the backward pass, the weight gradients, the clip and the optimizer are the scalar critic's.
+ *   actor    dQ/dlogit_k = p_k (z_k - Q) of the updated critic at (s, actor(s) + noise) stands where the scalar head has its
+ *            weight; the rest of steps 4-5 is unchanged.
+ *   priorities  pa[slot] = (|y - q| + eps)^alpha on the expectations above.
+ * Every train-type call (train, train_replay, train_prioritized, compute, time_resident, time_prioritized, actors_run) runs this
+ * step, in the launches of the scalar one: 5 (6 with GA3C_DDPG_GRAD_CLIP, + 3 prioritised).  Priorities, n-step returns and
+ * device actors combine with it.  The handle keeps its 26 variables and their names; fetch also knows "d_pt" (p'), "d_m", "d_p",
+ * "d_dz" [B,N] and "d_ce" [B] (GA3C_ESTATE without the feature), and "dq" is not written by such a step.
+ * Checkpoints: the same members, critic_output/W:0 being [300,N], and "dist_support", f32 [2] = vmin, vmax, beside "step".  A plain
+ * file into a distributional handle, a distributional file into a plain handle, another N or another support: GA3C_ESTATE, the
+ * handle untouched.
+ * create: GA3C_EINVAL for atoms outside [2, GA3C_DDPG_ATOMS_MAX], vmin >= vmax, a NaN or an infinity; GA3C_ESTATE on a second
+ * create, on a handle without GA3C_DDPG_LOSS_PAIRED (under the fork's loss a row has no target of its own) and on one with twin
+ * critics, as twin_create is on a distributional handle: two distributions have no "min".  The five arenas are re-laid: every
+ * variable keeps its value, target copy, slots and gradient, and critic_output/W, /b are as ga3c_ddpg_create leaves variables.
+ * destroy: re-lays back to the [300,1] head, zeroed; also done by ga3c_ddpg_destroy.
+ * info: atoms = 1 (and a zero support) without the feature; each pointer may be NULL. */
+#define GA3C_DDPG_ATOMS_MAX 64
+int ga3c_ddpg_dist_create(ga3c_ddpg* net, int32_t atoms, float vmin, float vmax);
+int ga3c_ddpg_dist_destroy(ga3c_ddpg* net);
+int ga3c_ddpg_dist_info(ga3c_ddpg* net, int32_t* atoms, float* vmin, float* vmax);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,9 @@ mode 0 = predict, 1 = train_replay).  Median and min over rounds, one JSON line 
 predict 1, train_replay 5 (6 with USE_GRAD_CLIP).  --twin: the handle has twin critics (DDPG_TWIN) and a step that
 is not a policy step is 3 launches (4), so the time is the mean over --delay steps; --delay 1 times the policy step.
 --nstep N > 1: the handle has n-step state (DDPG_NSTEP) and the target kernel reads a discount per ring slot.
+--dist: the handle has a distributional critic (DDPG_DISTRIBUTIONAL) of --atoms atoms; the launches are the same.
 usage: python tools/ddpg_step.py [--predict 1 128] [--train 64 128 256] [--rounds 5] [--iters 200] [--clip] [--twin [--delay N]]
-       [--nstep N]"""
+       [--nstep N] [--dist [--atoms N]]"""
 import argparse
 import json
 import os
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--twin", action="store_true")
     ap.add_argument("--delay", type=int, default=2)
     ap.add_argument("--nstep", type=int, default=1)
+    ap.add_argument("--dist", action="store_true")
+    ap.add_argument("--atoms", type=int, default=51)
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
@@ -38,6 +41,8 @@ def main():
     if args.twin:
         Config.DDPG_TWIN, Config.DDPG_CRITIC_LOSS, Config.DDPG_POLICY_DELAY = True, 'paired', args.delay
     Config.DDPG_NSTEP = args.nstep
+    if args.dist:
+        Config.DDPG_DISTRIBUTIONAL, Config.DDPG_CRITIC_LOSS, Config.DDPG_ATOMS = True, 'paired', args.atoms
     S, A = args.state_dim, args.actions
     maxB = max(args.predict + args.train)
     net = Network("gpu:0", "ddpg_step", A, (S,), max_batch=maxB, replay_capacity=max(maxB, 1024))
@@ -58,7 +63,8 @@ def main():
                           "grad_clip": bool(args.clip), "launches": (6 if args.clip else 5) if mode else 1,
                           "nstep": args.nstep, "twin": bool(args.twin), "policy_delay": args.delay if args.twin else None,
                           "launches_off_policy_step": ((4 if args.clip else 3) if mode else 1) if args.twin else None,
-                          "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2), "rounds": args.rounds,
+                          "atoms": args.atoms if args.dist else None,
+                          "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2), "max_us": round(v[-1], 2), "rounds": args.rounds,
                           "iters": args.iters}), flush=True)
     net.close()
 
