@@ -174,6 +174,12 @@ class Config:
                                         # DDPG, write their transitions into the replay ring in HBM, and the handle draws its own
                                         # train rows; no agent process, predictor, trainer or replay thread
     DEVICE_DDPG_UPDATES = 1             # train steps after each actor step of that loop (1..16)
+    DEVICE_DDPG_EVAL_ENVS = 0           # > 0 (DEVICE_DDPG; at most 4096): this many evaluation environments beside the training ones.
+                                        # The actor walks them without noise for a whole episode from fixed start states, one
+                                        # launch, and the result goes to logs/<model>/eval.csv: the learned policy, where the
+                                        # episode records are the exploring one's
+    DEVICE_DDPG_EVAL_EVERY = 1000       # train steps between two evaluations (>= 1); one more before the first train step
+    DEVICE_DDPG_EVAL_TARGET = False     # True: evaluate the target actor instead of the online one
 
 
 VECTOR_GAMES = ('Pendulum-v0', 'CartPole-v0')      # games whose state is a vector (Server.py:35-43 of the reference)
@@ -336,15 +342,33 @@ def _resolve_device_ddpg(n, pendulum):
         raise ValueError("DEVICE_AGENTS with WORLD_SIZE > 1 is not supported")
     if not 1 <= int(Config.DEVICE_AGENT_STEPS) <= 64:
         raise ValueError("DEVICE_AGENT_STEPS=%r: 1 to 64 actor steps per call" % (Config.DEVICE_AGENT_STEPS,))
+    e = Config.DEVICE_DDPG_EVAL_ENVS
+    if isinstance(e, bool) or not isinstance(e, int) or not 0 <= e <= 4096:
+        raise ValueError("DEVICE_DDPG_EVAL_ENVS=%r: 0 (off) or 1 to 4096 evaluation environments" % (e,))
+    if e:                                   # (off: the two keys beside it are not looked at)
+        k = Config.DEVICE_DDPG_EVAL_EVERY
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError("DEVICE_DDPG_EVAL_EVERY=%r: a whole number of train steps >= 1" % (k,))
+        if not isinstance(Config.DEVICE_DDPG_EVAL_TARGET, bool):
+            raise ValueError("DEVICE_DDPG_EVAL_TARGET=%r: True or False" % (Config.DEVICE_DDPG_EVAL_TARGET,))
+
+
+def _refuse_eval_without_device_ddpg():
+    """DEVICE_DDPG_EVAL_ENVS asks for evaluation episodes of the DDPG handle's device regime."""
+    if getattr(Config, "DEVICE_DDPG_EVAL_ENVS", 0):
+        raise ValueError("DEVICE_DDPG_EVAL_ENVS=%r needs DEVICE_DDPG (with DEVICE_AGENTS > 0): the evaluation episodes are run by "
+                         "the loop that steps the DDPG actors on the device" % (Config.DEVICE_DDPG_EVAL_ENVS,))
 
 
 def resolve_device_agents(explicit=()):
     """What DEVICE_AGENTS > 0 cannot be combined with.  Call after resolve_action_space and resolve_ddpg.  With
-    DEVICE_AGENTS = 0 nothing is checked and nothing changes, except that DEVICE_DDPG, which asks for them, raises."""
+    DEVICE_AGENTS = 0 nothing is checked and nothing changes, except that DEVICE_DDPG, which asks for them, raises, and so
+    does DEVICE_DDPG_EVAL_ENVS > 0, which asks for DEVICE_DDPG."""
     n = int(Config.DEVICE_AGENTS)
     if n == 0:
         if getattr(Config, "DEVICE_DDPG", False):
             raise ValueError("DEVICE_DDPG needs DEVICE_AGENTS > 0: the number of environments on the device")
+        _refuse_eval_without_device_ddpg()
         return
     if n < 0:
         raise ValueError("DEVICE_AGENTS=%d: 0 (off) or the number of environments on the device" % n)
@@ -352,6 +376,7 @@ def resolve_device_agents(explicit=()):
     if getattr(Config, "DEVICE_DDPG", False):
         _resolve_device_ddpg(n, pendulum)
         return
+    _refuse_eval_without_device_ddpg()
     if Config.USE_DDPG:
         raise ValueError("DEVICE_AGENTS with USE_DDPG is not supported: the device actors step CartPole-v0 only, or "
                          "Pendulum-v0 under the actor-critic network (DEVICE_PENDULUM); under DDPG they need DEVICE_DDPG=True")

@@ -11,6 +11,8 @@ step's rows itself (train_prioritized).  Under Config.DDPG_TWIN it
 train-type call runs the twin step (twin_create).  Under Config.DDPG_NSTEP > 1 the device actors write n-step
 returns into the ring and a discount per slot beside them (nstep_create).  Under Config.DDPG_DISTRIBUTIONAL the
 critic's head has Config.DDPG_ATOMS outputs, a categorical distribution over fixed returns (dist_create).
+eval_create attaches environments that the actor walks without noise from fixed start states, an episode per launch: how
+good the actor is right now, with nothing of the training disturbed (Config.DEVICE_DDPG_EVAL_ENVS).
 """
 import ctypes as C
 import os
@@ -371,6 +373,54 @@ class Network(DeviceActors, NativeHandle):
         if stats[1]:
             self.logging = (float(q[0]), float(q[1]))
         return tuple(int(t) for t in stats)
+
+    # ---- evaluation episodes (Config.DEVICE_DDPG_EVAL_ENVS) ---------------------------------
+    # what ga3c_ddpg_eval_get names: (dtype, shape of an environment's row); the trace_* ones need trace=True at eval_create
+    EVAL_STEPS = 200
+    EVAL_FIELDS = {"start": (np.float64, (2,)), "phys": (np.float64, (2,)), "trace_phys": (np.float64, (200, 2)),
+                   "trace_obs": (np.float32, (200, 3)), "trace_action": (np.float32, (200,)),
+                   "trace_reward": (np.float64, (200,))}
+
+    def eval_create(self, n=None, seed=None, trace=False):
+        """n Pendulum-v0 environments for noise-free episodes, whose start states are drawn once from `seed`."""
+        n = int(Config.DEVICE_DDPG_EVAL_ENVS if n is None else n)
+        self._call("eval_create", n, int(Config.RANDOM_SEED + 1 if seed is None else seed), int(bool(trace)))
+        self.num_eval = n
+
+    def eval_destroy(self):
+        self._call("eval_destroy")
+
+    def eval_run(self, steps=200, target=False):
+        """One episode of `steps` steps per environment under the online actor (target: its target copy), from the start
+        states -> f64 [n]: the sum of each environment's rewards."""
+        totals = np.empty(self.num_eval, np.float64)
+        self._call("eval_run", int(steps), int(bool(target)), nat.ptr(totals, nat.f64p))
+        return totals
+
+    def eval_get(self, name):
+        if name == "elapsed_ms":                    # of the last run's kernel, between two events on the handle's stream
+            out = np.zeros(1, np.float32)
+            self._call("eval_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
+            return float(out[0])
+        dtype, shape = self.EVAL_FIELDS[name]
+        out = np.zeros((self.num_eval,) + shape, dtype)
+        self._call("eval_get", name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
+
+    def eval_set(self, name, value):
+        value = np.ascontiguousarray(value, dtype=self.EVAL_FIELDS[name][0])
+        self._call("eval_set", name.encode(), value.ctypes.data_as(C.c_void_p), value.nbytes)
+
+    def log_eval(self, training_step, totals, steps):
+        """training_step, n, steps, mean, min, max, mean_gym_return appended to logs/<model>/eval.csv.  The last undoes the
+        wrapper's r * 0.005 - 1 per step: the return gym's Pendulum-v0 would report for the same episode."""
+        totals = np.asarray(totals, np.float64)
+        mean = float(totals.mean())
+        os.makedirs("logs/%s" % self.model_name, exist_ok=True)
+        with self._log_lock:
+            with open("logs/%s/eval.csv" % self.model_name, "a") as f:
+                f.write("%d,%d,%d,%.17g,%.17g,%.17g,%.17g\n" % (training_step, totals.size, steps, mean, float(totals.min()),
+                                                               float(totals.max()), (mean + steps) / 0.005))
 
     def compute(self, x, y_r, a, x2, done, stop_after, noise=None):
         s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)

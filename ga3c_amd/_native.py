@@ -219,6 +219,12 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_dist_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float]),
     "ga3c_ddpg_dist_destroy": (C.c_int, [C.c_void_p]),
     "ga3c_ddpg_dist_info": (C.c_int, [C.c_void_p, i32p, f32p, f32p]),
+    # evaluation episodes of a DDPG handle (Config.DEVICE_DDPG_EVAL_ENVS), include/ga3c_abi.h: ga3c_ddpg_eval_*
+    "ga3c_ddpg_eval_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32]),
+    "ga3c_ddpg_eval_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_eval_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f64p]),
+    "ga3c_ddpg_eval_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "ga3c_ddpg_eval_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

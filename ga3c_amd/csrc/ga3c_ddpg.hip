@@ -49,6 +49,10 @@
 //   ddpg_dist_critic_kernel  step 3's forward, the softmax, the cross-entropy and its delta (w / B)(p - m), the trunk's backward
 //   ddpg_dist_actor_kernel   ddpg_actor_kernel's body with dQ/dlogit_k = p_k (z_k - Q) in the scalar weight's place
 // They stand beside the scalar kernels, which compile from the source they had; the launch counts of a step are the same.
+// Evaluation episodes (ga3c_ddpg_eval_create, Config.DEVICE_DDPG_EVAL_ENVS; tests/ddpg_eval_oracle.py is the same
+// statement):
+//   ddpg_eval_kernel<Env>    one workgroup per 16 evaluation environments walks a whole episode: actor_fwd without noise, the
+//                            environment's step on the thread's registers, the f64 sum of the rewards; one launch per evaluation
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -1180,6 +1184,78 @@ __global__ void ddpg_uniform_slots_kernel(int64_t size, int B, uint64_t seed, ui
   slots[k] = (int32_t)(lo + (j < w - 1 ? j : w - 1));
 }
 
+// ------------------------------------------------------------------ evaluation episodes
+constexpr int EVAL_MAX_ENVS = GA3C_DDPG_EVAL_MAX_ENVS;
+constexpr int EVAL_MAX_STEPS = GA3C_DDPG_EVAL_MAX_STEPS;       // a Pendulum-v0 episode under its TimeLimit; the trace's row stride
+
+// What a traced evaluation keeps of every step, [n][EVAL_MAX_STEPS][width]; all null: nothing is stored.
+struct EvalTrace {
+  double* phys;              // [..][P] the physics before the step
+  float* obs;                // [..][S] what the actor read
+  float* action;             // [..][A] what it answered
+  double* reward;            // [..]
+};
+
+// A whole noise-free episode of `steps` steps for environments row0 .. row0 + 15, one workgroup: thread r < nrows keeps
+// environment row0 + r's physics, step count and reward sum in registers; every step is actor_fwd on the tile's observations
+// (th: the value arena or the target arena), then Env::step and Env::observe by those threads, as actor_step states them, and
+// the reward added in step order in f64.  Every episode starts from start[i] with elapsed = 0.  Env::step's wrap branch
+// cannot be reached after tanh; it is the training actors' statement, kept whole.  The loop is bounded by `steps` alone.
+// Reads th and start; writes total_out, phys_out and the trace: no ActState, no ring, no priorities, no windows.
+template <class Env>
+__global__ __launch_bounds__(THREADS) void ddpg_eval_kernel(Layout L, const float* __restrict__ th, int n, int steps,
+                                                            const double* __restrict__ start, double* __restrict__ total_out,
+                                                            double* __restrict__ phys_out, EvalTrace tr) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  constexpr int S = Env::S, P = Env::P, A = Env::A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, n - row0);
+  const int r = threadIdx.x;
+  const size_t i = (size_t)row0 + r;                 // the thread's environment, r < nrows
+  double s[P];
+  double total = 0.0;
+  int elapsed = 0;
+  float obs[S];
+  if (r < TILE) {
+    for (int k = 0; k < S; ++k) obs[k] = 0.f;
+    if (r < nrows) {
+      for (int k = 0; k < P; ++k) s[k] = start[i * P + k];
+      Env::observe(s, obs);
+    }
+    for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+  }
+  __syncthreads();
+  for (int t = 0; t < steps; ++t) {
+    // ends in a barrier: act is whole, and no thread reads xin any more
+    actor_fwd(L, th, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    if (r < nrows) {
+      float av[A];
+      for (int j = 0; j < A; ++j) av[j] = act[j * TILE + r];
+      const size_t at = i * EVAL_MAX_STEPS + t;
+      if (tr.phys) {
+        for (int k = 0; k < P; ++k) tr.phys[at * P + k] = s[k];
+        for (int k = 0; k < S; ++k) tr.obs[at * S + k] = obs[k];
+        for (int j = 0; j < A; ++j) tr.action[at * A + j] = av[j];
+      }
+      double reward;
+      int done;
+      Env::step(s, av, &elapsed, &reward, &done);
+      total = total + reward;
+      Env::observe(s, obs);
+      for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+      if (tr.phys) tr.reward[at] = reward;
+    }
+    __syncthreads();                                 // the next step's actor reads these observations
+  }
+  if (r < nrows) {
+    total_out[i] = total;
+    for (int k = 0; k < P; ++k) phys_out[i * P + k] = s[k];
+  }
+}
+
 // ------------------------------------------------------------------ host side
 // The handle is a ga3c_vecnet::Core (ga3c_vecnet.hpp): stream, lanes, arenas, variables by name, checkpoint and registered
 // segment are the shared ones.  Its own: the train step, the replay ring, the noise.
@@ -1262,6 +1338,19 @@ struct Dist {
   float* work_base = nullptr;           // the rows of the handle's DistRows
 };
 
+// Evaluation episodes of a handle (ga3c_ddpg_eval_create).  block: the device buffers below; h_counts: the n f64 totals of the
+// last run, pinned.  Read and written under train_mu.
+struct Eval : ga3c_actors::ActorsCore {
+  int n = 0;
+  bool trace = false;
+  double* start = nullptr;              // [n][2] where every run begins
+  double* phys = nullptr;               // [n][2] where the last run ended
+  double* total = nullptr;              // [n] its reward sums
+  EvalTrace tr{};                       // null without a trace
+  bool timed = false;                   // t0 / t1 hold the last run's kernel
+  double* h_total() const { return reinterpret_cast<double*>(h_counts); }
+};
+
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
   ga3c_ddpg_config cfg;
   Layout L;
@@ -1286,6 +1375,7 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   Twin* twin = nullptr;           // null: one critic
   NStep* nstep = nullptr;         // null: one-step rows, the scalar gamma everywhere
   Dist* dist = nullptr;           // null: the scalar critic
+  Eval* eval = nullptr;           // null: no evaluation episodes
   DistRows dw{};                  // its rows, null without
   std::vector<std::string> tnames;      // the target copies' names, by variable
 };
@@ -1670,12 +1760,18 @@ void dactors_free(ga3c_ddpg* m) {
   m->actors = nullptr;
 }
 
+void eval_free(ga3c_ddpg* m) {
+  ga3c_actors::actors_free(m->eval);
+  m->eval = nullptr;
+}
+
 void free_all(ga3c_ddpg* m) {
   if (m->actors && m->st) {       // live actors: what they enqueued may still run
     (void)hipStreamSynchronize(m->st);
     (void)hipGetLastError();
   }
   dactors_free(m);
+  eval_free(m);
   per_free(m);
   twin_free(m);
   nstep_free(m);
@@ -2736,6 +2832,125 @@ int ga3c_ddpg_actors_get(ga3c_ddpg* m, const char* name, void* out, int64_t byte
 int ga3c_ddpg_actors_set(ga3c_ddpg* m, const char* name, const void* in, int64_t bytes) {
   if (!in) return fail(GA3C_EINVAL, "null argument");
   return dactors_access(m, name, nullptr, in, bytes);
+}
+
+// ---- evaluation episodes
+
+int ga3c_ddpg_eval_create(ga3c_ddpg* m, int32_t n, int64_t seed, int32_t trace) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (n < 1 || n > EVAL_MAX_ENVS) return fail(GA3C_EINVAL, "%d evaluation environments outside [1,%d]", n, EVAL_MAX_ENVS);
+  if (trace != 0 && trace != 1) return fail(GA3C_EINVAL, "trace %d is neither 0 nor 1", trace);
+  if (m->L.S != DEnv::S || m->L.A != DEnv::A)
+    return fail(GA3C_EINVAL, "the environment has %d state floats and %d actions, the network %d and %d", DEnv::S, DEnv::A, m->L.S, m->L.A);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (m->eval) return fail(GA3C_ESTATE, "this network has evaluation episodes already");
+  Eval* e = new (std::nothrow) Eval();
+  if (!e) return fail(GA3C_EINVAL, "out of host memory");
+  e->n = n;
+  e->trace = trace != 0;
+  const size_t Nn = (size_t)n, S = DEnv::S, P = DEnv::P, A = DEnv::A, T = e->trace ? Nn * EVAL_MAX_STEPS : 0;
+  // the start states, drawn once: Pendulum::reset on the first two uniforms of environment i's stream under this seed
+  std::vector<double> start(Nn * P);
+  for (size_t i = 0; i < Nn; ++i) {
+    double ru[DEnv::RESET_DRAWS];
+    int elapsed = 0;
+    for (int k = 0; k < DEnv::RESET_DRAWS; ++k) ru[k] = ga3c_uniform::actor_uniform((uint64_t)seed, i, (uint64_t)k);
+    DEnv::reset(&start[i * P], &elapsed, ru);
+  }
+  size_t total = 0;
+  m->eval = e;
+  if (!ga3c_actors::carve_block(e, (int)(Nn * sizeof(double) / sizeof(int)), &total, [&](auto carve) {
+        carve(&e->start, Nn * P); carve(&e->phys, Nn * P); carve(&e->total, Nn);
+        carve(&e->tr.phys, T * P); carve(&e->tr.obs, T * S); carve(&e->tr.action, T * A); carve(&e->tr.reward, T);
+      }) ||
+      hipMemcpy(e->start, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(e->phys, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    eval_free(m);
+    return fail(GA3C_EHIP, "no memory for %d evaluation environments (%zu bytes)", n, total);
+  }
+  if (!e->trace) e->tr = EvalTrace{nullptr, nullptr, nullptr, nullptr};      // (carved with no elements: not to be stored to)
+  e->fields = {{"start", e->start, 8, P, true}, {"phys", e->phys, 8, P, false}};
+  if (e->trace) {
+    e->fields.push_back({"trace_phys", e->tr.phys, 8, EVAL_MAX_STEPS * P, false});
+    e->fields.push_back({"trace_obs", e->tr.obs, 4, EVAL_MAX_STEPS * S, false});
+    e->fields.push_back({"trace_action", e->tr.action, 4, EVAL_MAX_STEPS * A, false});
+    e->fields.push_back({"trace_reward", e->tr.reward, 8, EVAL_MAX_STEPS, false});
+  }
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_eval_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (!m->eval) return fail(GA3C_ESTATE, "this network has no evaluation episodes");
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipStreamSynchronize(m->st));
+  }
+  eval_free(m);
+  return GA3C_OK;
+}
+
+// One launch, one copy back, one wait.  The kernel stands on the handle's stream between whole train steps, so the arena it
+// reads is that of exactly one of them.
+int ga3c_ddpg_eval_run(ga3c_ddpg* m, int32_t steps, int32_t target, double* total_reward) {
+  if (!m || !total_reward) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  Eval* e = m->eval;
+  if (!e) return fail(GA3C_ESTATE, "this network has no evaluation episodes");
+  if (steps < 1 || steps > EVAL_MAX_STEPS) return fail(GA3C_EINVAL, "steps %d outside [1,%d]", steps, EVAL_MAX_STEPS);
+  if (target != 0 && target != 1) return fail(GA3C_EINVAL, "target %d is neither 0 nor 1", target);
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipEventRecord(m->t0, m->st));
+    hipLaunchKernelGGL(ddpg_eval_kernel<DEnv>, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[target ? 1 : 0],
+                       e->n, (int)steps, (const double*)e->start, e->total, e->phys, e->tr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->t1, m->st));
+    HIPCHK(hipMemcpyAsync(e->h_total(), e->total, sizeof(double) * e->n, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipEventRecord(m->tev, m->st));
+  }
+  HIPCHK(hipEventSynchronize(m->tev));
+  e->timed = true;
+  memcpy(total_reward, e->h_total(), sizeof(double) * e->n);
+  return GA3C_OK;
+}
+
+namespace {
+
+int eval_access(ga3c_ddpg* m, const char* name, void* out, const void* in, int64_t bytes) {
+  if (!m || !name || (!out && !in)) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  Eval* e = m->eval;
+  if (!e) return fail(GA3C_ESTATE, "this network has no evaluation episodes");
+  if (!e->trace && strncmp(name, "trace_", 6) == 0) return fail(GA3C_ESTATE, "%s: the evaluation episodes keep no trace (trace = 1 at create)", name);
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIPCHK(hipStreamSynchronize(m->st));
+  if (strcmp(name, "elapsed_ms") == 0) {             // the last run's kernel between two events on the handle's stream
+    if (!out) return fail(GA3C_EINVAL, "%s is read only", name);
+    if (bytes != 4) return fail(GA3C_EINVAL, "%s is 4 bytes, not %lld", name, (long long)bytes);
+    if (!e->timed) return fail(GA3C_ESTATE, "%s: no evaluation has run", name);
+    HIPCHK(hipEventElapsedTime(static_cast<float*>(out), m->t0, m->t1));
+    return GA3C_OK;
+  }
+  return ga3c_actors::field_access(e, e->n, name, out, in, bytes);
+}
+
+}  // namespace
+
+int ga3c_ddpg_eval_get(ga3c_ddpg* m, const char* name, void* out, int64_t bytes) {
+  if (!out) return fail(GA3C_EINVAL, "null argument");
+  return eval_access(m, name, out, nullptr, bytes);
+}
+
+int ga3c_ddpg_eval_set(ga3c_ddpg* m, const char* name, const void* in, int64_t bytes) {
+  if (!in) return fail(GA3C_EINVAL, "null argument");
+  return eval_access(m, name, nullptr, in, bytes);
 }
 
 }  // extern "C"

@@ -805,6 +805,35 @@ int ga3c_ddpg_dist_create(ga3c_ddpg* net, int32_t atoms, float vmin, float vmax)
 int ga3c_ddpg_dist_destroy(ga3c_ddpg* net);
 int ga3c_ddpg_dist_info(ga3c_ddpg* net, int32_t* atoms, float* vmin, float* vmax);
 
+/* ---- Evaluation episodes of a DDPG handle (Config.DEVICE_DDPG_EVAL_ENVS; tests/ddpg_eval_oracle.py is the same
+ * statement in numpy): n Pendulum-v0 environments that the actor walks without noise from fixed start states, a whole episode
+ * in one launch.  Attached to a created handle, as the priorities, the twin critics, the n-step returns and the device actors
+ * are; it needs none of them and touches none of them: no actor state, no ring row, no priority, no window, no step of the noise
+ * process, no draw counter and not `step`.  A handle without it runs what it ran before.
+ * create draws the start states once: environment i starts at th = -pi + 2 pi u(seed, i, 0), thdot = -1 + 2 u(seed, i, 1), u the
+ * counter uniform of the device actors, and every run starts there with elapsed = 0, so two evaluations differ by the weights
+ * alone.
+ * run: `steps` steps of every environment.  A step is the actor (target = 0: the online one, 1: the target copy) on the
+ * observation [cos th, sin th, thdot] in f32, ga3c_ddpg_predict's arithmetic with GA3C_DDPG_NOISE_NONE, then the device actors'
+ * environment step on that action; total_reward[i] is the f64 sum of environment i's rewards in step order.  One launch on the
+ * handle's stream, one copy back, one wait: it reads the weights that exactly one train step left.
+ * By name, `bytes` the buffer's size: "start" f64 [n][2], get and set; get only: "phys" f64 [n][2], the physics after the last
+ * run; with trace = 1 at create "trace_phys" f64 [n][200][2] (entry t: the physics before step t), "trace_obs" f32 [n][200][3]
+ * (what the actor read at step t), "trace_action" f32 [n][200] and "trace_reward" f64 [n][200], whose entries t < the last run's
+ * `steps` are that run's (GA3C_ESTATE without the trace); "elapsed_ms" f32, the last run's kernel between two events on the
+ * handle's stream, valid until a time_* call records the same events (GA3C_ESTATE before the first run).
+ * create: GA3C_EINVAL for n outside [1, GA3C_DDPG_EVAL_MAX_ENVS], a trace that is neither 0 nor 1, or a handle whose state_dim
+ * != 3 or num_actions != 1; GA3C_ESTATE on a second create, as is every other call here without evaluation episodes.
+ * run: GA3C_EINVAL for steps outside [1, GA3C_DDPG_EVAL_MAX_STEPS] or a target that is neither 0 nor 1.
+ * destroy: also done by ga3c_ddpg_destroy. */
+#define GA3C_DDPG_EVAL_MAX_ENVS 4096
+#define GA3C_DDPG_EVAL_MAX_STEPS 200
+int ga3c_ddpg_eval_create(ga3c_ddpg* net, int32_t n, int64_t seed, int32_t trace);
+int ga3c_ddpg_eval_destroy(ga3c_ddpg* net);
+int ga3c_ddpg_eval_run(ga3c_ddpg* net, int32_t steps, int32_t target, double* total_reward);
+int ga3c_ddpg_eval_get(ga3c_ddpg* net, const char* name, void* out, int64_t bytes);
+int ga3c_ddpg_eval_set(ga3c_ddpg* net, const char* name, const void* in, int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

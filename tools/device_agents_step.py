@@ -7,9 +7,11 @@ PPS of the status line of `_train.sh GAME=<game> AGENTS=16` (profiles/device_age
 Pendulum's environments run in lockstep: one train step of N (TIME_MAX + 1) rows every TIME_MAX actor steps.
 --ddpg (with --game Pendulum-v0; Config.DEVICE_DDPG, ga3c_ddpg_actors_run): the DDPG handle's actors, --updates
 train steps of --batch ring rows after every actor step, --prioritized for the draw by priority, --nstep N for n-step returns
-(Config.DDPG_NSTEP; profiles/nstep_step.txt); the call waits once, at its end (profiles/device_agents_ddpg.txt).
+(Config.DDPG_NSTEP, DESIGN.md 8o; profiles/nstep_step.txt); the call waits once, at its end (profiles/device_agents_ddpg.txt);
+--eval-envs E --eval-every K for an evaluation of E noise-free episodes whenever the train steps pass a multiple of K, as
+ThreadDeviceAgents runs them under DEVICE_DDPG_EVAL_ENVS (profiles/ddpg_eval.txt), inside the timed rounds.
 usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]
-       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1]]"""
+       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1] [--eval-envs 0] [--eval-every 1000]]"""
 import argparse
 import json
 import os
@@ -35,6 +37,8 @@ def main():
     ap.add_argument("--prioritized", action="store_true", help="--ddpg: draw by priority (paired critic loss)")
     ap.add_argument("--capacity", type=int, default=1000000, help="--ddpg: ring slots")
     ap.add_argument("--nstep", type=int, default=1, help="--ddpg: steps of the returns the actors write (1..16)")
+    ap.add_argument("--eval-envs", type=int, default=0, help="--ddpg: evaluation environments (0: none)")
+    ap.add_argument("--eval-every", type=int, default=1000, help="--ddpg: train steps between two evaluations")
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
@@ -59,24 +63,31 @@ def main():
                           replay_capacity=args.capacity)
             net.learning_rate = Config.LEARNING_RATE_START
             net.actors_create(n, seed=Config.RANDOM_SEED, updates=args.updates, batch=args.batch)
+            if args.eval_envs:
+                net.eval_create(args.eval_envs)
         else:
             net = Network("gpu:0", "device_agents_step", num_actions, state_dim, max_batch=max(16, n * (args.time_max + 1)), predict_lanes=1)
             net.learning_rate, net.beta = Config.LEARNING_RATE_START, Config.BETA_START
             net.actors_create(n, args.time_max, Config.DISCOUNT, Config.RANDOM_SEED)
         net.actors_run(args.steps, train=not args.no_train)               # warm-up; the rollouts are in step from here on
-        rates, train_calls, rows, episodes = [], 0, 0, 0
+        rates, train_rates, train_calls, rows, episodes, evaluations = [], [], 0, 0, 0, 0
         for _ in range(args.rounds):
             t0 = time.perf_counter()
-            steps = 0
+            steps, calls0 = 0, train_calls
             for _ in range(args.calls):
                 s, c, r, e = net.actors_run(args.steps, train=not args.no_train)
+                if args.ddpg and args.eval_envs and (train_calls + c) // args.eval_every > train_calls // args.eval_every:
+                    net.eval_run(200)
+                    evaluations += 1
                 steps, train_calls, rows, episodes = steps + s, train_calls + c, rows + r, episodes + e
             rates.append(steps / (time.perf_counter() - t0))
+            train_rates.append((train_calls - calls0) / (time.perf_counter() - t0))
             net.actors_episodes()
         rates.sort()
         per_step_us = 1e6 * n / rates[len(rates) // 2]
-        extra = ({"ddpg": True, "batch": args.batch, "updates": args.updates, "prioritized": args.prioritized, "nstep": args.nstep}
-                 if args.ddpg else {})
+        extra = ({"ddpg": True, "batch": args.batch, "updates": args.updates, "prioritized": args.prioritized, "nstep": args.nstep,
+                  "eval_envs": args.eval_envs, "eval_every": args.eval_every, "evaluations": evaluations,
+                  "train_steps_per_s_median": round(sorted(train_rates)[len(train_rates) // 2])} if args.ddpg else {})
         print(json.dumps({**extra, "game": args.game, "agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,
                           "agent_steps_per_s_median": round(rates[len(rates) // 2]), "agent_steps_per_s_min": round(rates[0]),
                           "agent_steps_per_s_max": round(rates[-1]), "actor_step_us_median": round(per_step_us, 1),
