@@ -428,16 +428,54 @@ bool is_pinned(const void* p) {
   return at.type == hipMemoryTypeHost;
 }
 
-void launch_dense1_fwd_valu(const float* flat, const float* pk, float* part, int B, int ks, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  hipExtLaunchKernelGGL(dense1_fwd_valu_kernel<D1V_DEPTH>, dim3(dense1_fwd_valu_blocks(B, ks)), dim3(256), 0, st, e0, e1, 0, flat, pk, part, B, ks);
+// ---- launching.  One primitive, one launcher per kernel, one builder per argument block that several kernels share.  A
+// launcher owns its kernel's grid, block, LDS size, template selection and arguments (shape checks live here: every grid is
+// derived from B on the host); which launcher runs at which batch is decided by launch_forward / launch_backward /
+// launch_update, and ga3c_net_time_kernel times the same launchers one by one.
+// Ev: the optional event pair of one launch, recorded in front of / behind the kernel by the launch itself
+struct Ev { hipEvent_t start = nullptr, stop = nullptr; };
+
+template <class... P, class... A>
+void launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Ev ev, const A&... a) {
+  if (ev.start || ev.stop) hipExtLaunchKernelGGL(kern, grid, block, lds, st, ev.start, ev.stop, 0, a...);
+  else hipLaunchKernelGGL(kern, grid, block, lds, st, a...);
+}
+
+// the dense batch staged in a workspace, in either input format
+const void* staged_x(const Fwd& f, bool u8) { return u8 ? (const void*)f.xu8 : (const void*)f.x; }
+
+// so: the scattered intake's offsets as kernel arguments (launch_forward); a dense batch passes one with n = n_dst = 0
+void launch_conv_stack_fwd(ga3c_net* net, int idx, const Fwd& f, const void* xin, bool u8, bool train, int B, const SrcOffsets& so,
+                           hipStream_t st, Ev ev = {}) {
+  const float *th = net->theta[idx], *pk = net->theta_pk[idx];
+  launch(train ? (u8 ? conv_stack_fwd_kernel<true, true> : conv_stack_fwd_kernel<true, false>)
+               : (u8 ? conv_stack_fwd_kernel<false, true> : conv_stack_fwd_kernel<false, false>),
+         dim3(B * 2), dim3(1024), CS_LDS_FLOATS * sizeof(float), st, ev, xin, pk + PK_W1F, th + OFF_B1, pk + PK_W2F, th + OFF_B2, f.n1, f.n2, B,
+         f.src_off, so, net->cache_ring);
+}
+
+void launch_conv1_fwd(ga3c_net* net, int idx, const Fwd& f, const void* xin, bool u8, int B, hipStream_t st, Ev ev = {}) {
+  const float* th = net->theta[idx];
+  launch(u8 ? conv1_fwd_kernel<true> : conv1_fwd_kernel<false>, dim3(B * 7), dim3(256), 0, st, ev, xin, th + OFF_W1, th + OFF_B1, f.n1, B);
+}
+
+// quarter: in units of four tiles (grid 4 B) instead of eight (C2F_QUARTER_MAX_B)
+void launch_conv2_fwd(ga3c_net* net, int idx, const Fwd& f, bool quarter, int B, hipStream_t st, Ev ev = {}) {
+  const float* th = net->theta[idx];
+  launch(quarter ? conv2_fwd_kernel<true> : conv2_fwd_kernel<false>, dim3(quarter ? B * 4 : B * 2), dim3(256), 0, st, ev, f.n1, th + OFF_W2,
+         th + OFF_B2, f.n2, B);
+}
+
+void launch_dense1_fwd_valu(const float* flat, const float* pk, float* part, int B, int ks, hipStream_t st, Ev ev = {}) {
+  launch(dense1_fwd_valu_kernel<D1V_DEPTH>, dim3(dense1_fwd_valu_blocks(B, ks)), dim3(256), 0, st, ev, flat, pk, part, B, ks);
 }
 
 // dense1 forward: the LDS-tiled kernel while its grid is one round of workgroups (one workgroup per CU: its LDS image
 // is 120-145 KB), the register-fragment kernel beyond; prefer_frag: an LDS-free kernel (beside another lane's conv stack)
 int launch_dense1_fwd(ga3c_net* net, const float* flat, const float* pk, float* part, int B, int ks, hipStream_t st,
-                      hipEvent_t e0, hipEvent_t e1, bool prefer_frag = false, bool allow_valu = true) {
+                      bool prefer_frag = false, bool allow_valu = true, Ev ev = {}) {
   if (allow_valu && net->d1f_valu) {
-    launch_dense1_fwd_valu(flat, pk, part, B, ks, st, e0, e1);
+    launch_dense1_fwd_valu(flat, pk, part, B, ks, st, ev);
     HIPCHK(hipGetLastError());
     return GA3C_OK;
   }
@@ -445,39 +483,68 @@ int launch_dense1_fwd(ga3c_net* net, const float* flat, const float* pk, float* 
   const int mt = B <= 128 ? 1 : 2;
   const size_t lds = (size_t)d1f_lds_floats(mt, max_steps) * sizeof(float);
   const int tile_blocks = dense1_fwd_blocks(B, ks, mt);
-  if (net->d1f_tile && !prefer_frag && max_steps <= 16 && lds <= 160 * 1024 && tile_blocks <= 256) {
-    if (mt == 1)
-      hipExtLaunchKernelGGL(dense1_fwd_tile_kernel<1>, dim3(tile_blocks), dim3(512), lds, st, e0, e1, 0, flat, pk, part, B, ks, max_steps);
-    else
-      hipExtLaunchKernelGGL(dense1_fwd_tile_kernel<2>, dim3(tile_blocks), dim3(512), lds, st, e0, e1, 0, flat, pk, part, B, ks, max_steps);
-  } else if (B <= 256) {
-    hipExtLaunchKernelGGL(dense1_fwd_kernel<1>, dim3(dense1_fwd_blocks(B, ks, 1)), dim3(256), 0, st, e0, e1, 0, flat, pk, part, B, ks, -1);
-  } else {
-    hipExtLaunchKernelGGL(dense1_fwd_kernel<2>, dim3(dense1_fwd_blocks(B, ks, 2)), dim3(256), 0, st, e0, e1, 0, flat, pk, part, B, ks, -1);
-  }
+  if (net->d1f_tile && !prefer_frag && max_steps <= 16 && lds <= 160 * 1024 && tile_blocks <= 256)
+    launch(mt == 1 ? dense1_fwd_tile_kernel<1> : dense1_fwd_tile_kernel<2>, dim3(tile_blocks), dim3(512), lds, st, ev, flat, pk, part, B, ks,
+           max_steps);
+  else if (B <= 256)
+    launch(dense1_fwd_kernel<1>, dim3(dense1_fwd_blocks(B, ks, 1)), dim3(256), 0, st, ev, flat, pk, part, B, ks, -1);
+  else
+    launch(dense1_fwd_kernel<2>, dim3(dense1_fwd_blocks(B, ks, 2)), dim3(256), 0, st, ev, flat, pk, part, B, ks, -1);
   HIPCHK(hipGetLastError());
   return GA3C_OK;
 }
 
+// tl: the train lane whose targets the heads read and whose deltas they write (nullptr: a prediction step)
+// out_p / out_v: pinned host memory, written in place of f.p / f.v
+HeadArgs head_args(ga3c_net* net, int idx, const Fwd& f, int B, const TrainLane* tl, float beta, float* out_p, float* out_v) {
+  const int A = net->A;
+  const float* th = net->theta[idx];
+  HeadArgs h;
+  memset(&h, 0, sizeof h);
+  h.part = f.part; h.ks = dense_ks(B); h.B = B; h.A = A;
+  h.bd = th + OFF_BD; h.wv = th + OFF_WV; h.bv = th + OFF_BV; h.wp = th + OFF_WP; h.bp = net->cont ? nullptr : th + off_bp(A);
+  h.d1 = f.d1; h.z = f.z; h.p = out_p ? out_p : f.p; h.v = out_v ? out_v : f.v;
+  h.log_eps = net->cfg.log_epsilon; h.min_policy = net->cfg.min_policy;
+  h.log_softmax = (net->cfg.flags & GA3C_FLAG_LOG_SOFTMAX) ? 1 : 0;
+  if (tl) { h.y_r = tl->yr; h.act = tl->act; h.dz = tl->dz; h.dv = tl->dv; h.lossrow = tl->lossrow; h.dd1 = tl->dd1; h.beta = beta; }
+  return h;
+}
 
 constexpr int HEADS_WAVES = 1;   // samples (waves) per heads workgroup
-// ---- kernel launch helpers (shape checks live here: every grid is derived from B on the host)
+// the heads of the net's kind: heads_cont under CONTINUOUS, else heads; dual (train only): heads_dual, dd1 as its two terms,
+// tl->dd1 (policy) and tl->dd1_v (value), for the two backward passes of DUAL_RMSPROP
+void launch_heads(ga3c_net* net, int idx, const Fwd& f, int B, const TrainLane* tl, float beta, bool dual, float* out_p, float* out_v,
+                  hipStream_t st, Ev ev = {}) {
+  const HeadArgs h = head_args(net, idx, f, B, tl, beta, out_p, out_v);
+  const bool train = tl != nullptr;
+  auto go = [&](auto kern, auto... more) {
+    launch(kern, dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, ev, h, more...);
+  };
+#define HEADS(AM)                                                                                          \
+  do {                                                                                                     \
+    if (net->cont) { if (train) go(heads_cont_kernel<true, AM>); else go(heads_cont_kernel<false, AM>); }  \
+    else if (train && dual) go(heads_dual_kernel<AM>, tl->dd1_v);                                          \
+    else if (train) go(heads_kernel<true, AM>);                                                            \
+    else go(heads_kernel<false, AM>);                                                                      \
+  } while (0)
+  if (net->npc <= 8) HEADS(8);   // AMAX bounds the policy head's columns: A, or the 2A of [x | y]
+  else if (net->npc <= 24) HEADS(24);
+  else HEADS(64);
+#undef HEADS
+}
+
 // stop_ev: recorded behind the step -- as the completion event of its LAST launch (hipExtLaunchKernelGGL), which saves the
 // host the hipEventRecord call and the queue a packet of its own
-// dual (train only): dd1 as its two terms, tl->dd1 (policy) and tl->dd1_v (value), for the two backward passes of DUAL_RMSPROP
+// dual (train only): see launch_heads
 int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, bool train,
                    const TrainLane* tl, float beta, float* out_p = nullptr, float* out_v = nullptr, hipEvent_t stop_ev = nullptr,
                    bool dual = false) {
   if (B < 1 || B > net->maxB) return fail(GA3C_EINVAL, "batch %d outside [1,%d]", B, net->maxB);
-  const int A = net->A;
-  const float* th = net->theta[idx];
-  const void* xin = f.src_off ? (const void*)f.src_base : (f.x_u8 ? (const void*)f.xu8 : (const void*)f.x);
+  const void* xin = f.src_off ? (const void*)f.src_base : staged_x(f, f.x_u8);
   if (f.src_off && B > FUSED_CONV_MAX_B) return fail(GA3C_ESTATE, "scattered intake needs the fused conv stack");
   if (B <= FUSED_CONV_MAX_B) {   // one workgroup per CU: pays off only while a batch is a single wave of workgroups
-    const size_t lds = CS_LDS_FLOATS * sizeof(float);
     SrcOffsets so;
-    so.n = 0;
-    so.n_dst = 0;
+    so.n = so.n_dst = 0;
     if (f.src_off && f.src_off_host && !net->graphs && net->offsets_in_args) {   // plain launch: the offsets ride in the kernel arguments
       memcpy(so.off, f.src_off_host, (size_t)B * sizeof(int64_t));
       so.n = B;
@@ -486,62 +553,30 @@ int launch_forward(ga3c_net* net, const Fwd& f, int idx, int B, hipStream_t st, 
       memcpy(so.dst, f.cache_dst, (size_t)B * sizeof(int64_t));
       so.n_dst = B;
     }
-#define CSTACK(T, U)                                                                                                \
-  hipLaunchKernelGGL((conv_stack_fwd_kernel<T, U>), dim3(B * 2), dim3(1024), lds, st, xin, net->theta_pk[idx] + PK_W1F, th + OFF_B1, \
-                     net->theta_pk[idx] + PK_W2F, th + OFF_B2, f.n1, f.n2, B, f.src_off, so, net->cache_ring)
-    if (train) { if (f.x_u8) CSTACK(true, true); else CSTACK(true, false); }
-    else { if (f.x_u8) CSTACK(false, true); else CSTACK(false, false); }
-#undef CSTACK
+    launch_conv_stack_fwd(net, idx, f, xin, f.x_u8, train, B, so, st);
   } else {
-    if (f.x_u8)
-      hipLaunchKernelGGL(conv1_fwd_kernel<true>, dim3(B * 7), dim3(256), 0, st, xin, th + OFF_W1, th + OFF_B1, f.n1, B);
-    else
-      hipLaunchKernelGGL(conv1_fwd_kernel<false>, dim3(B * 7), dim3(256), 0, st, xin, th + OFF_W1, th + OFF_B1, f.n1, B);
-    if (B <= C2F_QUARTER_MAX_B) hipLaunchKernelGGL(conv2_fwd_kernel<true>, dim3(B * 4), dim3(256), 0, st, f.n1, th + OFF_W2, th + OFF_B2, f.n2, B);
-    else hipLaunchKernelGGL(conv2_fwd_kernel<false>, dim3(B * 2), dim3(256), 0, st, f.n1, th + OFF_W2, th + OFF_B2, f.n2, B);
+    launch_conv1_fwd(net, idx, f, xin, f.x_u8, B, st);
+    launch_conv2_fwd(net, idx, f, B <= C2F_QUARTER_MAX_B, B, st);
   }
-  const int ks = dense_ks(B);
-  HeadArgs h;
-  memset(&h, 0, sizeof h);
-  h.part = f.part; h.ks = ks; h.B = B; h.A = A;
-  h.bd = th + OFF_BD; h.wv = th + OFF_WV; h.bv = th + OFF_BV; h.wp = th + OFF_WP; h.bp = net->cont ? nullptr : th + off_bp(A);
-  h.d1 = f.d1; h.z = f.z; h.p = out_p ? out_p : f.p; h.v = out_v ? out_v : f.v;   // out_*: pinned host memory, written in place
-  h.log_eps = net->cfg.log_epsilon; h.min_policy = net->cfg.min_policy;
-  h.log_softmax = (net->cfg.flags & GA3C_FLAG_LOG_SOFTMAX) ? 1 : 0;
-  if (train) { h.y_r = tl->yr; h.act = tl->act; h.dz = tl->dz; h.dv = tl->dv; h.lossrow = tl->lossrow; h.dd1 = tl->dd1; h.beta = beta; }
   // several prediction lanes at work: the fragment kernel (no LDS) runs beside the other lanes' conv stacks
   const bool frag = !train && !net->graphs && B >= D1F_FRAG_MIN_B &&
                     net->predict_inflight.load(std::memory_order_relaxed) >= D1F_FRAG_LANES;
-  CHK(launch_dense1_fwd(net, f.n2, net->theta_pk[idx], f.part, B, ks, st, nullptr, nullptr, frag));
-#define HEADS(T, AM)                                                                                                        \
-  do {                                                                                                                      \
-    if (stop_ev) hipExtLaunchKernelGGL((heads_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, nullptr, stop_ev, 0, h); \
-    else hipLaunchKernelGGL((heads_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, h);                                 \
-  } while (0)
-#define HEADS_C(T, AM)                                                                                                      \
-  do {                                                                                                                      \
-    if (stop_ev) hipExtLaunchKernelGGL((heads_cont_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, nullptr, stop_ev, 0, h); \
-    else hipLaunchKernelGGL((heads_cont_kernel<T, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, st, h);                                 \
-  } while (0)
-  if (net->cont) {   // AMAX bounds the 2A columns [x | y]
-    if (2 * A <= 8) { if (train) HEADS_C(true, 8); else HEADS_C(false, 8); }
-    else if (2 * A <= 24) { if (train) HEADS_C(true, 24); else HEADS_C(false, 24); }
-    else { if (train) HEADS_C(true, 64); else HEADS_C(false, 64); }
-  } else if (train && dual) {
-    const dim3 grid((B + HEADS_WAVES - 1) / HEADS_WAVES), block(64 * HEADS_WAVES);
-    if (A <= 8) hipLaunchKernelGGL(heads_dual_kernel<8>, grid, block, 0, st, h, tl->dd1_v);
-    else if (A <= 24) hipLaunchKernelGGL(heads_dual_kernel<24>, grid, block, 0, st, h, tl->dd1_v);
-    else hipLaunchKernelGGL(heads_dual_kernel<64>, grid, block, 0, st, h, tl->dd1_v);
-  } else if (A <= 8) { if (train) HEADS(true, 8); else HEADS(false, 8); }
-  else if (A <= 24) { if (train) HEADS(true, 24); else HEADS(false, 24); }
-  else { if (train) HEADS(true, 64); else HEADS(false, 64); }
-#undef HEADS
-#undef HEADS_C
+  CHK(launch_dense1_fwd(net, f.n2, net->theta_pk[idx], f.part, B, dense_ks(B), st, frag));
+  launch_heads(net, idx, f, B, train ? tl : nullptr, beta, dual, out_p, out_v, st, Ev{nullptr, stop_ev});
   HIPCHK(hipGetLastError());
   return GA3C_OK;
 }
 
-// conv1_dw workgroups (= partial slabs) of the split conv backward for a batch of B rows (see launch_backward)
+// conv1_dw workgroups (= partial slabs) of the split conv backward for a batch of B rows.  Measured at batch 128 (round 2):
+// 512 / 384 / 256 / 192 / 128 workgroups -> train step 68.8 / 68.7 / 68.0 / 69.8 / 73.0 us: 256 (3.5 units each, 4.2 MB of
+// slabs instead of 8.4) is as fast ... but uint8 states (4-byte loads per pixel, a longer chain per unit) lose 4 % at 256
+// (13.6 k vs 14.2 k steps/s), and the two input formats must cut the units alike to stay bit-identical: 512 for both.
+// Round 4: behind conv2_dx, conv1_dw shares ONE launch with conv2_dw (conv_dw_pair_kernel: three workgroups of either kind
+// per CU = 768 slots).  With 768 - 4 B workgroups -- 240 at 132 rows, 3.9 units each -- the pair is one round and the slab
+// reduction reads half as much: 132-row step 70.2 -> 66.0 us (f32), 70.0 -> 67.1 (uint8, whose staging became 16-byte loads
+// for it: with dword loads it LOST 1.6 us at 240); 200 workgroups: 67.2.  Past ~142 rows that count would mean more than five
+// units per workgroup: 256 (150 / 160 rows: 74.9 / 75.9 us against 77.0 / 77.9 at 512).  A function of B alone, so that
+// every form of the step (paired or not, uint8 or f32) cuts the slabs alike and gives the same bits.
 int conv1_dw_blocks(int B) {
   const int units = B * 7;
   int n = 512;
@@ -552,106 +587,165 @@ int conv1_dw_blocks(int B) {
   return units < n ? units : n;
 }
 
-// overlap: the caller will apply the gradients right away (train, not compute_grads): start their all-reduce as soon as
-// each part of the arena is final; returns with the train stream already waiting for the exchange
-// keep_dn1: also store dn1 (consumed on chip by the fused conv backward; kept in HBM for ga3c_net_fetch after compute_grads)
+// The partial slabs the conv backward of a B-row step leaves for slab_reduce: conv1's and conv2's counts, and which form
+// writes them -- conv_bwd_kernel, one slab pair per (sample, half), or the split kernels (conv1_dw workgroups; conv2_dw sample
+// groups).  split: the split kernels' counts at any B (they cut their work by them wherever they are launched).
+struct SlabGeom { int nch1, nch2; bool fused; };
+SlabGeom slab_geom(int B, bool split = false) {
+  if (!split && B >= CONV_BWD_MIN_B && B <= CONV_BWD_MAX_B) return {2 * B, 2 * B, true};
+  return {conv1_dw_blocks(B), B < 256 ? B : 256, false};
+}
+
 // What flows back: dd1 into the hidden layer, dz / dv into the two heads; the gradient goes to the arena g.  One pass of the
 // summed loss reads t.dd1, t.dz, t.dv and writes t.grad; DUAL_RMSPROP runs two (train_grads).
 struct BwdIo { const float* dd1; const float* dz; const float* dv; float* g; };
+BwdIo lane_io(const TrainLane& t) { return BwdIo{t.dd1, t.dz, t.dv, t.grad}; }
+
+HeadBwdArgs head_bwd_args(ga3c_net* net, const TrainLane& t, const BwdIo& io, int B) {
+  float* g = io.g;
+  HeadBwdArgs hb;
+  hb.B = B; hb.A = net->A; hb.d1 = t.f.d1; hb.dz = io.dz; hb.dv = io.dv; hb.lossrow = t.lossrow;
+  hb.g_wp = g + OFF_WP; hb.g_bp = net->cont ? nullptr : g + off_bp(net->A); hb.g_wv = g + OFF_WV; hb.g_bv = g + OFF_BV; hb.losses = t.losses;
+  return hb;
+}
+
+Dense1TileArgs dense1_tile_args(ga3c_net* net, const TrainLane& t, int idx, int B, const BwdIo& io, const FusedUpd& upd) {
+  const float* th = net->theta[idx];
+  const int roles = net->npc + 2;
+  Dense1TileArgs d;
+  d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = io.g + OFF_WD; d.g_bd = io.g + OFF_BD; d.dn2 = t.dn2; d.B = B;
+  d.hb = head_bwd_args(net, t, io, B);
+  d.upd = upd;
+  d.role_blocks = roles < 14 ? roles : 14;       // 242 tiles + the roles stay within one round of workgroups on 256 CUs
+  d.tail_lds = B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
+  return d;
+}
+
+// the update a fused step applies inside its backward kernels: theta[idx] -> theta[other] (and its packed copies)
+// defer_wd: which kernel steps dense1/w -- launch_backward's rule sets it for a step
+FusedUpd fused_upd(ga3c_net* net, int idx, int other, float lr, bool defer_wd = false) {
+  FusedUpd fu;
+  memset(&fu, 0, sizeof fu);
+  fu.tin = net->theta[idx]; fu.tout = net->theta[other]; fu.ms = net->ms; fu.mom = net->mom; fu.pk = net->theta_pk[other];
+  fu.lr = lr; fu.omr = 1.0f - net->cfg.rmsprop_decay; fu.mu = net->cfg.rmsprop_momentum; fu.eps = net->cfg.rmsprop_epsilon;
+  fu.on = 1;
+  fu.defer_wd = defer_wd;
+  return fu;
+}
+
+void launch_dense1_bwd_tile(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io, const FusedUpd& upd, Ev ev = {}) {
+  const Dense1TileArgs d = dense1_tile_args(net, t, idx, B, io, upd);
+  const size_t lds = (d.tail_lds ? D1B_LDS_FLOATS_TAIL : D1B_LDS_FLOATS) * sizeof(float);
+#define D1B(U)                                                                                                       \
+  (net->cont ? (d.tail_lds ? dense1_bwd_tile_kernel<U, true, true> : dense1_bwd_tile_kernel<U, false, true>)         \
+             : (d.tail_lds ? dense1_bwd_tile_kernel<U, true, false> : dense1_bwd_tile_kernel<U, false, false>))
+  launch(!upd.on ? D1B(0) : (upd.defer_wd ? D1B(2) : D1B(1)), dim3(D1B_TILES + d.role_blocks), dim3(1024), lds, t.st, ev, d);
+#undef D1B
+}
+
+// conv2_dw + conv2_dx + conv1_dw of a sample half in ONE workgroup (conv_bwd_kernel): dn1 never leaves the chip between them
+// keep_dn1: also store dn1 (kept in HBM for ga3c_net_fetch after compute_grads); upd.defer_wd: the launch steps dense1/w
+int launch_conv_bwd(ga3c_net* net, TrainLane& t, int idx, int B, bool u8, bool keep_dn1, float* g, const FusedUpd& upd, Ev ev = {}) {
+  if (B > CONV_BWD_MAX_B) return fail(GA3C_EINVAL, "conv_bwd runs up to %d rows", CONV_BWD_MAX_B);
+  const bool wd = upd.on && upd.defer_wd;
+  launch(u8 ? (wd ? conv_bwd_kernel<true, true> : conv_bwd_kernel<true, false>) : (wd ? conv_bwd_kernel<false, true> : conv_bwd_kernel<false, false>),
+         dim3(2 * B), dim3(1024), CB_LDS_FLOATS * sizeof(float), t.st, ev, staged_x(t.f, u8), t.f.n1, t.dn2, net->theta_pk[idx] + PK_W2DX,
+         keep_dn1 ? t.dn1 : (float*)nullptr, t.slab2, t.slab1, B, g + OFF_WD, upd);
+  return GA3C_OK;
+}
+
+// conv2's two gradients are separate launches: their LDS/VGPR budgets differ too much to share one grid
+void launch_conv2_dw(TrainLane& t, int B, Ev ev = {}) {
+  launch(conv2_dw_kernel<2>, dim3(slab_geom(B, true).nch2, 4), dim3(256), 0, t.st, ev, t.f.n1, t.dn2, t.slab2, B);
+}
+
+// upd.defer_wd: dense1/w is stepped in this launch (conv2_dx_wd_kernel)
+void launch_conv2_dx(ga3c_net* net, TrainLane& t, int idx, int B, float* g, const FusedUpd& upd, Ev ev = {}) {
+  const float* w = net->theta_pk[idx] + PK_W2DX;
+  if (upd.on && upd.defer_wd)
+    launch(conv2_dx_wd_kernel, dim3(B + C2DX_WD_BLOCKS, 2), dim3(512), 0, t.st, ev, t.dn2, w, t.f.n1, t.dn1, B, g + OFF_WD, upd);
+  else
+    launch(conv2_dx_kernel, dim3(B, 2), dim3(512), 0, t.st, ev, t.dn2, w, t.f.n1, t.dn1, B);
+}
+
+// conv2_dw and conv1_dw side by side in one launch behind conv2_dx
+void launch_conv_dw_pair(TrainLane& t, int B, bool u8, Ev ev = {}) {
+  const SlabGeom sg = slab_geom(B, true);
+  launch(u8 ? conv_dw_pair_kernel<true> : conv_dw_pair_kernel<false>, dim3(sg.nch1 + 4 * sg.nch2), dim3(256), 0, t.st, ev, staged_x(t.f, u8),
+         t.dn1, t.slab1, B * 7, sg.nch1, t.f.n1, t.dn2, t.slab2, B, sg.nch2);
+}
+
+void launch_conv1_dw(TrainLane& t, int B, bool u8, Ev ev = {}) {
+  launch(u8 ? conv1_dw_kernel<true> : conv1_dw_kernel<false>, dim3(slab_geom(B, true).nch1), dim3(256), 0, t.st, ev, staged_x(t.f, u8), t.dn1,
+         t.slab1, B * 7);
+}
+
+// the slabs of a B-row step (slab_geom) summed into g; upd.on: and the conv parameters stepped
+void launch_slab_reduce(TrainLane& t, int B, float* g, const FusedUpd& upd, Ev ev = {}) {
+  const SlabGeom sg = slab_geom(B);
+  SlabSet s1{t.slab1, sg.nch1, SLAB1, 256 * 16, g + OFF_W1, g + OFF_B1, (SLAB1 + 63) / 64, OFF_W1, OFF_B1};
+  SlabSet s2{t.slab2, sg.nch2, SLAB2, 256 * 32, g + OFF_W2, g + OFF_B2, (SLAB2 + 63) / 64, OFF_W2, OFF_B2};
+  launch(upd.on ? slab_reduce_kernel<true> : slab_reduce_kernel<false>, dim3(s1.nblocks + s2.nblocks), dim3(1024), 0, t.st, ev, s1, s2, upd);
+}
+
+// loss sums alone (Network.log: a batch evaluated without a backward pass)
+void launch_loss_sum(ga3c_net* net, TrainLane& t, int B, Ev ev = {}) {
+  launch(loss_sum_kernel, dim3(1), dim3(256), 0, t.st, ev, head_bwd_args(net, t, lane_io(t), B));
+}
+
+// The round-1 dense1 backward (dense1_dw + dense1_dx, and the two in one grid), superseded in the step by dense1_bwd_tile and
+// kept for ga3c_net_time_kernel's comparisons; dense1_dw and dense1_bwd carry the discrete head's A + 2 roles only.
+void launch_dense1_dw(ga3c_net* net, TrainLane& t, int B, const BwdIo& io, Ev ev = {}) {
+  launch(dense1_dw_kernel, dim3(FLAT / 32 + net->A + 2, 2), dim3(256), 0, t.st, ev, t.f.n2, io.dd1, io.g + OFF_WD, io.g + OFF_BD, B,
+         head_bwd_args(net, t, io, B));
+}
+
+void launch_dense1_dx(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io, Ev ev = {}) {
+  launch(dense1_dx_kernel, dim3(FLAT / 32, ((B + 15) / 16 + 3) / 4), dim3(256), 0, t.st, ev, io.dd1, net->theta[idx] + OFF_WD, t.f.n2, t.dn2, B);
+}
+
+void launch_dense1_bwd(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io, Ev ev = {}) {
+  Dense1BwdArgs d;
+  d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = net->theta[idx] + OFF_WD; d.g_wd = io.g + OFF_WD; d.g_bd = io.g + OFF_BD; d.dn2 = t.dn2; d.B = B;
+  d.hb = head_bwd_args(net, t, io, B);
+  d.dw_gx = FLAT / 32 + net->A + 2; d.dw_blocks = 2 * d.dw_gx; d.dx_gx = FLAT / 32;
+  d.dx_mt = dense_dx_mt(B);
+  launch(dense1_bwd_kernel, dim3(d.dw_blocks + d.dx_gx * (((B + 16 * d.dx_mt - 1) / (16 * d.dx_mt) + 3) / 4)), dim3(256), 0, t.st, ev, d);
+}
+
+// overlap: the caller will apply the gradients right away (train, not compute_grads): start their all-reduce as soon as
+// each part of the arena is final; returns with the train stream already waiting for the exchange
+// keep_dn1: also store dn1 (consumed on chip by the fused conv backward; kept in HBM for ga3c_net_fetch after compute_grads)
 int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io, bool overlap = false, const FusedUpd* fu = nullptr,
                     bool keep_dn1 = true) {
-  const int A = net->A;
-  const float* th = net->theta[idx];
   FusedUpd upd;
   memset(&upd, 0, sizeof upd);
   if (fu) upd = *fu;
   hipStream_t st = t.st;
   float* g = io.g;
-  HeadBwdArgs hb;
-  hb.B = B; hb.A = A; hb.d1 = t.f.d1; hb.dz = io.dz; hb.dv = io.dv; hb.lossrow = t.lossrow;
-  hb.g_wp = g + OFF_WP; hb.g_bp = net->cont ? nullptr : g + off_bp(A); hb.g_wv = g + OFF_WV; hb.g_bv = g + OFF_BV; hb.losses = t.losses;
-  const int roles = net->npc + 2;
-  const bool fused_cb = B >= CONV_BWD_MIN_B && B <= CONV_BWD_MAX_B;
+  const bool fused_cb = slab_geom(B).fused;
   // Under the fused update dense1/w is stepped by a later kernel, beside its MFMA work, instead of in dense1_bwd_tile's
   // epilogue: inside conv_bwd while every workgroup of conv_bwd steps ONE 16-row group (2 B >= 242: worth 0.5 us of the
   // 128-row step, whose 24 MB cost conv_bwd 2.2 us where they cost the epilogue 3.5; below 121 rows the groups left over are
   // a tail and it loses 0.2 us, profiles/README.md), and on the split path in conv2_dx's launch (conv2_dx_wd_kernel)
   upd.defer_wd = upd.on && (!fused_cb || 2 * B >= KSTEPS_DENSE);
-  {
-    Dense1TileArgs d;
-    d.n2 = t.f.n2; d.dd1 = io.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
-    d.hb = hb;
-    d.upd = upd;
-    d.role_blocks = roles < 14 ? roles : 14;       // 242 tiles + the roles stay within one round of workgroups on 256 CUs
-    d.tail_lds = B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
-    const size_t d1b_lds = (d.tail_lds ? D1B_LDS_FLOATS_TAIL : D1B_LDS_FLOATS) * sizeof(float);
-    const int u = upd.on ? (upd.defer_wd ? 2 : 1) : 0;
-#define D1B(U, T, C) hipLaunchKernelGGL((dense1_bwd_tile_kernel<U, T, C>), dim3(D1B_TILES + d.role_blocks), dim3(1024), d1b_lds, st, d)
-#define D1B_U(T, C) do { if (u == 2) D1B(2, T, C); else if (u == 1) D1B(1, T, C); else D1B(0, T, C); } while (0)
-    if (net->cont) { if (d.tail_lds) D1B_U(true, true); else D1B_U(false, true); }
-    else if (d.tail_lds) D1B_U(true, false);
-    else D1B_U(false, false);
-#undef D1B_U
-#undef D1B
-  }
+  launch_dense1_bwd_tile(net, t, idx, B, io, upd);
   if (overlap) {
     HIPCHK(hipEventRecord(net->ev_tail_ready, st));
     HIPCHK(hipStreamWaitEvent(net->cst, net->ev_tail_ready, 0));
     NCCLCHK(ncclAllReduce(g + OFF_WD, g + OFF_WD, (size_t)(net->n - OFF_WD), ncclFloat, ncclSum, net->comm, net->cst));
     HIPCHK(hipEventRecord(net->ev_comm_done, net->cst));   // (waited for below, behind the head's exchange)
   }
-  int nch1, nch2;
   if (fused_cb) {
-    // conv2_dw + conv2_dx + conv1_dw of a sample half in ONE workgroup (conv_bwd_kernel): dn1 never leaves the chip between them
-    const int grid = 2 * B;                         // (sample, half); one slab pair per workgroup
-    const size_t lds = CB_LDS_FLOATS * sizeof(float);
-#define CONV_BWD(U, W, XP)                                                                                                  \
-  hipLaunchKernelGGL((conv_bwd_kernel<U, W>), dim3(grid), dim3(1024), lds, st, (const void*)(XP), t.f.n1, t.dn2,              \
-                     net->theta_pk[idx] + PK_W2DX, keep_dn1 ? t.dn1 : nullptr, t.slab2, t.slab1, B, g + OFF_WD, upd)
-    const bool wd = upd.on && upd.defer_wd;
-    if (t.f.x_u8) { if (wd) CONV_BWD(true, true, t.f.xu8); else CONV_BWD(true, false, t.f.xu8); }
-    else { if (wd) CONV_BWD(false, true, t.f.x); else CONV_BWD(false, false, t.f.x); }
-#undef CONV_BWD
-    nch1 = nch2 = grid;
+    CHK(launch_conv_bwd(net, t, idx, B, t.f.x_u8, keep_dn1, g, upd));
   } else {
-    nch2 = B < 256 ? B : 256;          // sample groups = partial slabs
-    // workgroups = partial slabs.  Measured at batch 128 (round 2): 512 / 384 / 256 / 192 / 128 workgroups -> train step
-    // 68.8 / 68.7 / 68.0 / 69.8 / 73.0 us: 256 (3.5 units each, 4.2 MB of slabs instead of 8.4) is as fast
-    // ... but uint8 states (4-byte loads per pixel, a longer chain per unit) lose 4 % at 256 (13.6 k vs 14.2 k steps/s), and the
-    // two input formats must cut the units alike to stay bit-identical: 512 for both
-    // Round 4: behind conv2_dx, conv1_dw shares ONE launch with conv2_dw (conv_dw_pair_kernel: three workgroups of either kind
-    // per CU = 768 slots).  With 768 - 4 B workgroups -- 240 at 132 rows, 3.9 units each -- the pair is one round and the slab
-    // reduction reads half as much: 132-row step 70.2 -> 66.0 us (f32), 70.0 -> 67.1 (uint8, whose staging became 16-byte loads
-    // for it: with dword loads it LOST 1.6 us at 240); 200 workgroups: 67.2.  Past ~142 rows that count would mean more than five
-    // units per workgroup: 256 (150 / 160 rows: 74.9 / 75.9 us against 77.0 / 77.9 at 512).  A function of B alone, so that
-    // every form of the step (paired or not, uint8 or f32) cuts the slabs alike and gives the same bits.
-    nch1 = conv1_dw_blocks(B);
     const bool pair = B <= DW_PAIR_MAX_B;
-    // conv2's two gradients are separate launches: their LDS/VGPR budgets differ too much to share one grid
-    if (!pair) hipLaunchKernelGGL(conv2_dw_kernel<2>, dim3(nch2, 4), dim3(256), 0, st, t.f.n1, t.dn2, t.slab2, B);
-    if (upd.on && upd.defer_wd)
-      hipLaunchKernelGGL(conv2_dx_wd_kernel, dim3(B + C2DX_WD_BLOCKS, 2), dim3(512), 0, st, t.dn2, net->theta_pk[idx] + PK_W2DX, t.f.n1, t.dn1, B,
-                         (const float*)(g + OFF_WD), upd);
-    else
-      hipLaunchKernelGGL(conv2_dx_kernel, dim3(B, 2), dim3(512), 0, st, t.dn2, net->theta_pk[idx] + PK_W2DX, t.f.n1, t.dn1, B);
-    if (pair) {
-      if (t.f.x_u8)
-        hipLaunchKernelGGL(conv_dw_pair_kernel<true>, dim3(nch1 + 4 * nch2), dim3(256), 0, st, (const void*)t.f.xu8, t.dn1, t.slab1, B * 7, nch1,
-                           t.f.n1, t.dn2, t.slab2, B, nch2);
-      else
-        hipLaunchKernelGGL(conv_dw_pair_kernel<false>, dim3(nch1 + 4 * nch2), dim3(256), 0, st, (const void*)t.f.x, t.dn1, t.slab1, B * 7, nch1,
-                           t.f.n1, t.dn2, t.slab2, B, nch2);
-    } else if (t.f.x_u8)
-      hipLaunchKernelGGL(conv1_dw_kernel<true>, dim3(nch1), dim3(256), 0, st, (const void*)t.f.xu8, t.dn1, t.slab1, B * 7);
-    else
-      hipLaunchKernelGGL(conv1_dw_kernel<false>, dim3(nch1), dim3(256), 0, st, (const void*)t.f.x, t.dn1, t.slab1, B * 7);
+    if (!pair) launch_conv2_dw(t, B);
+    launch_conv2_dx(net, t, idx, B, g, upd);
+    if (pair) launch_conv_dw_pair(t, B, t.f.x_u8);
+    else launch_conv1_dw(t, B, t.f.x_u8);
   }
-  {
-    SlabSet s1{t.slab1, nch1, SLAB1, 256 * 16, g + OFF_W1, g + OFF_B1, (SLAB1 + 63) / 64, OFF_W1, OFF_B1};
-    SlabSet s2{t.slab2, nch2, SLAB2, 256 * 32, g + OFF_W2, g + OFF_B2, (SLAB2 + 63) / 64, OFF_W2, OFF_B2};
-    if (upd.on) hipLaunchKernelGGL(slab_reduce_kernel<true>, dim3(s1.nblocks + s2.nblocks), dim3(1024), 0, st, s1, s2, upd);
-    else hipLaunchKernelGGL(slab_reduce_kernel<false>, dim3(s1.nblocks + s2.nblocks), dim3(1024), 0, st, s1, s2, upd);
-  }
+  launch_slab_reduce(t, B, g, upd);
   HIPCHK(hipGetLastError());
   if (overlap) {
     // The conv gradients (12 k floats) are complete only now, with nothing left to overlap their exchange with: it goes on the
@@ -665,64 +759,50 @@ int launch_backward(ga3c_net* net, TrainLane& t, int idx, int B, const BwdIo& io
   return GA3C_OK;
 }
 
-int launch_rmsprop(ga3c_net* net, const float* grad, float* scales, const float* tin, float* tout, float* pk_out,
-                   float lr, hipStream_t st) {
-  const bool clip = net->cfg.flags & GA3C_FLAG_GRAD_CLIP;
-  const bool mom = net->cfg.rmsprop_momentum != 0.0f;
-  const float omr = 1.0f - net->cfg.rmsprop_decay;
-  const int blocks = RMS_WD_BLOCKS + (int)((net->n - (int64_t)FLAT * HID + 255) / 256);
-  if (clip && net->cont)   // 12 tensors: out_x and out_y are normed apart (clip_by_average_norm per variable)
-    hipLaunchKernelGGL((clip_scale_kernel<true, TensorTableC>), dim3(12), dim3(256), 0, st, grad, net->ttc, net->cfg.grad_clip_norm, scales);
-  else if (clip)
-    hipLaunchKernelGGL((clip_scale_kernel<true, TensorTable>), dim3(10), dim3(256), 0, st, grad, net->tt, net->cfg.grad_clip_norm, scales);
-#define RMS(C, M)                                                                                                \
-  hipLaunchKernelGGL((rmsprop_kernel<C, M>), dim3(blocks), dim3(256), 0, st, tin, tout, net->ms, net->mom,        \
-                     grad, net->n, lr, omr, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->tt, scales,  \
-                     pk_out)
-#define RMSC(M)                                                                                                  \
-  hipLaunchKernelGGL((rmsprop_kernel<true, M, TensorTableC>), dim3(blocks), dim3(256), 0, st, tin, tout, net->ms, \
-                     net->mom, grad, net->n, lr, omr, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->ttc, \
-                     scales, pk_out)
-  if (clip && net->cont) { if (mom) RMSC(true); else RMSC(false); }   // (without clipping the table plays no part)
-  else if (clip && mom) RMS(true, true);
-  else if (clip) RMS(true, false);
-  else if (mom) RMS(false, true);
-  else RMS(false, false);
-#undef RMS
-#undef RMSC
-  HIPCHK(hipGetLastError());
-  return GA3C_OK;
+// the per-tensor scales of GRAD_CLIP: 10 tensors; CONTINUOUS 12 (out_x and out_y are normed apart: clip_by_average_norm per
+// variable); DUAL_RMSPROP tf.clip_by_norm of every gradient tensor of both costs (NetworkVP_discrate.py:108-117): 20
+void launch_clip_scale(ga3c_net* net, const float* grad, float* scales, hipStream_t st, Ev ev = {}) {
+  const float clip = net->cfg.grad_clip_norm;
+  if (net->dual) launch(clip_scale_kernel<false, TensorTable2>, dim3(20), dim3(256), 0, st, ev, grad, net->tt2, clip, scales);
+  else if (net->cont) launch(clip_scale_kernel<true, TensorTableC>, dim3(12), dim3(256), 0, st, ev, grad, net->ttc, clip, scales);
+  else launch(clip_scale_kernel<true, TensorTable>, dim3(10), dim3(256), 0, st, ev, grad, net->tt, clip, scales);
+}
+
+int rmsprop_blocks(ga3c_net* net) { return RMS_WD_BLOCKS + (int)((net->n - (int64_t)FLAT * HID + 255) / 256); }
+
+// clip: scale every tensor by launch_clip_scale's scales; mom: with the momentum slot
+void launch_rmsprop(ga3c_net* net, bool clip, bool mom, const float* grad, const float* scales, const float* tin, float* tout,
+                    float* pk_out, float lr, hipStream_t st, Ev ev = {}) {
+  auto go = [&](auto kern, const auto& tt) {
+    launch(kern, dim3(rmsprop_blocks(net)), dim3(256), 0, st, ev, tin, tout, net->ms, net->mom, grad, net->n, lr, 1.0f - net->cfg.rmsprop_decay,
+           net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, tt, scales, pk_out);
+  };
+  if (clip && net->cont) { if (mom) go(rmsprop_kernel<true, true, TensorTableC>, net->ttc); else go(rmsprop_kernel<true, false, TensorTableC>, net->ttc); }
+  else if (clip) { if (mom) go(rmsprop_kernel<true, true>, net->tt); else go(rmsprop_kernel<true, false>, net->tt); }
+  else if (mom) go(rmsprop_kernel<false, true>, net->tt);   // (without clipping the table plays no part)
+  else go(rmsprop_kernel<false, false>, net->tt);
 }
 
 // the two optimizers' step of DUAL_RMSPROP in one pass (rmsprop_dual_kernel); grad: 2n floats, policy then value.  Both
 // gradients were taken at the same weights; the step is theta' = (theta - D_v) - D_p in f32 -- the value optimizer's step
 // first, then the policy optimizer's, each from its own slots (TF orders the two train ops not at all: DESIGN.md 8c)
-int launch_rmsprop_dual(ga3c_net* net, const float* grad, float* scales, const float* tin, float* tout, float* pk_out,
-                        float lr, hipStream_t st) {
-  const bool clip = net->cfg.flags & GA3C_FLAG_GRAD_CLIP;
-  const bool mom = net->cfg.rmsprop_momentum != 0.0f;
-  const float omr = 1.0f - net->cfg.rmsprop_decay;
-  const int blocks = RMS_WD_BLOCKS + (int)((net->n - (int64_t)FLAT * HID + 255) / 256);
-  if (clip)   // tf.clip_by_norm of every gradient tensor of both costs (NetworkVP_discrate.py:108-117): 20 scales
-    hipLaunchKernelGGL((clip_scale_kernel<false, TensorTable2>), dim3(20), dim3(256), 0, st, grad, net->tt2, net->cfg.grad_clip_norm,
-                       scales);
-#define RMSD(C, M)                                                                                                        \
-  hipLaunchKernelGGL((rmsprop_dual_kernel<C, M>), dim3(blocks), dim3(256), 0, st, tin, tout, net->ms, net->mom, net->ms_v, \
-                     net->mom_v, grad, net->n, lr, omr, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->tt,     \
-                     scales, pk_out)
-  if (clip && mom) RMSD(true, true);
-  else if (clip) RMSD(true, false);
-  else if (mom) RMSD(false, true);
-  else RMSD(false, false);
-#undef RMSD
-  HIPCHK(hipGetLastError());
-  return GA3C_OK;
+void launch_rmsprop_dual(ga3c_net* net, bool clip, bool mom, const float* grad, const float* scales, const float* tin, float* tout,
+                         float* pk_out, float lr, hipStream_t st, Ev ev = {}) {
+  launch(clip ? (mom ? rmsprop_dual_kernel<true, true> : rmsprop_dual_kernel<true, false>)
+              : (mom ? rmsprop_dual_kernel<false, true> : rmsprop_dual_kernel<false, false>),
+         dim3(rmsprop_blocks(net)), dim3(256), 0, st, ev, tin, tout, net->ms, net->mom, net->ms_v, net->mom_v, grad, net->n, lr,
+         1.0f - net->cfg.rmsprop_decay, net->cfg.rmsprop_momentum, net->cfg.rmsprop_epsilon, net->tt, scales, pk_out);
 }
 
-// the optimizer step of a train lane's gradients: one RMSProp, or the two of DUAL_RMSPROP
+// the optimizer step of a train lane's gradients: the clip scales if the net clips, then one RMSProp, or the two of DUAL_RMSPROP
 int launch_update(ga3c_net* net, TrainLane& t, const float* tin, float* tout, float* pk_out, float lr) {
-  if (net->dual) return launch_rmsprop_dual(net, t.grad, t.scales, tin, tout, pk_out, lr, t.st);
-  return launch_rmsprop(net, t.grad, t.scales, tin, tout, pk_out, lr, t.st);
+  const bool clip = net->cfg.flags & GA3C_FLAG_GRAD_CLIP;
+  const bool mom = net->cfg.rmsprop_momentum != 0.0f;
+  if (clip) launch_clip_scale(net, t.grad, t.scales, t.st);
+  if (net->dual) launch_rmsprop_dual(net, clip, mom, t.grad, t.scales, tin, tout, pk_out, lr, t.st);
+  else launch_rmsprop(net, clip, mom, t.grad, t.scales, tin, tout, pk_out, lr, t.st);
+  HIPCHK(hipGetLastError());
+  return GA3C_OK;
 }
 
 // forward on a prediction lane: pick the current weights under the shared lock
@@ -919,14 +999,8 @@ int train_grads(ga3c_net* net, TrainLane& t, int B, float beta, bool will_apply 
   }
   CHK(launch_forward(net, t.f, idx, B, t.st, true, &t, beta));
   t.exchanged = will_apply && net->comm && net->comm_overlap && !net->hogwild && &t == &net->tr;
-  FusedUpd fu;
-  memset(&fu, 0, sizeof fu);
-  if (fuse) {
-    fu.tin = net->theta[idx]; fu.tout = net->theta[other]; fu.ms = net->ms; fu.mom = net->mom; fu.pk = net->theta_pk[other];
-    fu.lr = lr; fu.omr = 1.0f - net->cfg.rmsprop_decay; fu.mu = net->cfg.rmsprop_momentum; fu.eps = net->cfg.rmsprop_epsilon;
-    fu.on = 1;
-  }
-  CHK(launch_backward(net, t, idx, B, BwdIo{t.dd1, t.dz, t.dv, t.grad}, t.exchanged, fuse ? &fu : nullptr, !will_apply));
+  const FusedUpd fu = fused_upd(net, idx, other, lr);
+  CHK(launch_backward(net, t, idx, B, lane_io(t), t.exchanged, fuse ? &fu : nullptr, !will_apply));
   t.stepped = fuse;
   t.stepped_other = other;
   return GA3C_OK;
@@ -1028,10 +1102,7 @@ int evaluate_staged(ga3c_net* net, TrainLane& t, int B, float beta, float* losse
     idx = net->latest;
   }
   CHK(launch_forward(net, t.f, idx, B, t.st, true, &t, beta));
-  HeadBwdArgs hb;
-  memset(&hb, 0, sizeof hb);
-  hb.B = B; hb.A = net->A; hb.lossrow = t.lossrow; hb.losses = t.losses;
-  hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, t.st, hb);
+  launch_loss_sum(net, t, B);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(t.st));
   if (losses) memcpy(losses, t.losses, 3 * sizeof(float));
@@ -2844,140 +2915,82 @@ int ga3c_net_time_train_lanes(ga3c_net* net, int32_t batch, int32_t iters, int32
   return GA3C_OK;
 }
 
+// ga3c_net_time_kernel's names: each is one launcher of the step on train lane 0, with the variant the name stands for
+// forced and nothing updated (no FusedUpd; "conv_bwd_wdstep" and "rmsprop" run their update with lr = 0)
+struct TimedKernel {
+  const char* name;
+  int (*run)(ga3c_net* net, TrainLane& t, int idx, int B, Ev ev);
+  bool discrete_only;   // a round-1 kernel that knows the discrete head's roles only
+};
+#define TIMED(name, discrete_only, ...) \
+  {name, [](ga3c_net* net, TrainLane& t, int idx, int B, Ev ev) -> int { __VA_ARGS__; return GA3C_OK; }, discrete_only}
+static const TimedKernel TIMED_KERNELS[] = {
+    TIMED("conv_stack_fwd", false, launch_conv_stack_fwd(net, idx, t.f, t.f.x, false, false, B, SrcOffsets{}, t.st, ev)),
+    TIMED("conv_stack_fwd_train", false, launch_conv_stack_fwd(net, idx, t.f, t.f.x, false, true, B, SrcOffsets{}, t.st, ev)),
+    TIMED("conv_stack_fwd_u8", false, launch_conv_stack_fwd(net, idx, t.f, t.f.xu8, true, false, B, SrcOffsets{}, t.st, ev)),
+    TIMED("conv1_fwd", false, launch_conv1_fwd(net, idx, t.f, t.f.x, false, B, t.st, ev)),
+    TIMED("conv1_fwd_u8", false, launch_conv1_fwd(net, idx, t.f, t.f.xu8, true, B, t.st, ev)),
+    TIMED("conv2_fwd", false, launch_conv2_fwd(net, idx, t.f, false, B, t.st, ev)),
+    TIMED("conv2_fwd_q", false, launch_conv2_fwd(net, idx, t.f, true, B, t.st, ev)),
+    TIMED("dense1_fwd", false, return launch_dense1_fwd(net, t.f.n2, net->theta_pk[idx], t.f.part, B, dense_ks(B), t.st, false, true, ev)),
+    TIMED("dense1_fwd_frag", false, return launch_dense1_fwd(net, t.f.n2, net->theta_pk[idx], t.f.part, B, dense_ks(B), t.st, true, false, ev)),
+    TIMED("dense1_fwd_valu", false, launch_dense1_fwd_valu(t.f.n2, net->theta_pk[idx], t.f.part, B, dense_ks(B), t.st, ev)),
+    TIMED("heads", false, launch_heads(net, idx, t.f, B, nullptr, 0.f, false, nullptr, nullptr, t.st, ev)),
+    TIMED("dense1_bwd_tile", false, launch_dense1_bwd_tile(net, t, idx, B, lane_io(t), FusedUpd{}, ev)),
+    TIMED("conv_bwd", false, return launch_conv_bwd(net, t, idx, B, false, true, t.grad, FusedUpd{}, ev)),
+    TIMED("conv_bwd_wdstep", false, return launch_conv_bwd(net, t, idx, B, false, true, t.grad, fused_upd(net, idx, idx, 0.f, true), ev)),
+    TIMED("conv2_dw", false, launch_conv2_dw(t, B, ev)),
+    TIMED("conv2_dx", false, launch_conv2_dx(net, t, idx, B, t.grad, FusedUpd{}, ev)),
+    TIMED("conv_dw_pair", false, launch_conv_dw_pair(t, B, false, ev)),
+    TIMED("conv1_dw", false, launch_conv1_dw(t, B, false, ev)),
+    TIMED("conv1_dw_u8", false, launch_conv1_dw(t, B, true, ev)),
+    TIMED("slab_reduce", false, launch_slab_reduce(t, B, t.grad, FusedUpd{}, ev)),
+    TIMED("rmsprop", false,
+          launch_rmsprop(net, false, false, t.grad, t.scales, net->theta[idx], net->theta[idx], net->theta_pk[idx], 0.f, t.st, ev)),
+    TIMED("dense1_dw", true, launch_dense1_dw(net, t, B, lane_io(t), ev)),
+    TIMED("dense1_dx", false, launch_dense1_dx(net, t, idx, B, lane_io(t), ev)),
+    TIMED("dense1_bwd", true, launch_dense1_bwd(net, t, idx, B, lane_io(t), ev)),
+};
+#undef TIMED
+
 int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32_t iters, float* elapsed_ms) {
-  // Each launch carries its own start/stop events (hipExtLaunchKernelGGL), so the sum is pure kernel
-  // execution time on the train lane's stream, without launch gaps.  Buffers hold whatever the last
-  // step left there; "rmsprop" runs with lr = 0 but does advance the `ms` slot (use a scratch net).
+  // Each launch carries its own start/stop events, so the sum is pure kernel execution time on the train lane's stream, without
+  // launch gaps.  Buffers hold whatever the last step left there; the two names that step do advance `ms` (use a scratch net).
   if (!net || !kernel || !elapsed_ms) return fail(GA3C_EINVAL, "null argument");
-  if (net->cont) return fail(GA3C_ESTATE, "ga3c_net_time_kernel times the discrete head's kernels only");
   if (iters < 1 || batch < 1 || batch > net->maxB) return fail(GA3C_EINVAL, "bad batch/iters");
+  const TimedKernel* k = nullptr;
+  for (const TimedKernel& e : TIMED_KERNELS)
+    if (strcmp(e.name, kernel) == 0) k = &e;
+  if (!k) return fail(GA3C_EINVAL, "unknown kernel '%s'", kernel);
+  if (k->discrete_only && net->cont) return fail(GA3C_ESTATE, "'%s' knows the discrete head only", kernel);
   HIPCHK(hipSetDevice(net->cfg.device));
   std::lock_guard<std::mutex> tl(net->tr.mu);
   TrainLane& t = net->tr;
-  const float* th = net->theta[net->latest];
-  float* g = net->grad;
-  const int B = batch;
-  const std::string k(kernel);
   HIPCHK(hipStreamSynchronize(t.st));
   double total = 0.0;
-#define TL(kern, grid, ...) hipExtLaunchKernelGGL(kern, grid, dim3(256), 0, t.st, t.ev0, t.ev1, 0, __VA_ARGS__)
   for (int i = 0; i < iters; ++i) {
-    if (k == "conv1_fwd") {
-      TL(conv1_fwd_kernel<false>, dim3(B * 7), (const void*)t.f.x, th + OFF_W1, th + OFF_B1, t.f.n1, B);
-    } else if (k == "conv1_fwd_u8") {
-      TL(conv1_fwd_kernel<true>, dim3(B * 7), (const void*)t.f.xu8, th + OFF_W1, th + OFF_B1, t.f.n1, B);
-    } else if (k == "conv1_dw_u8") {
-      TL(conv1_dw_kernel<true>, dim3(conv1_dw_blocks(B)), (const void*)t.f.xu8, t.dn1, t.slab1, B * 7);
-    } else if (k == "conv2_fwd") {
-      TL(conv2_fwd_kernel<false>, dim3(B * 2), t.f.n1, th + OFF_W2, th + OFF_B2, t.f.n2, B);
-    } else if (k == "conv2_fwd_q") {
-      TL(conv2_fwd_kernel<true>, dim3(B * 4), t.f.n1, th + OFF_W2, th + OFF_B2, t.f.n2, B);
-    } else if (k == "conv_stack_fwd") {
-      hipExtLaunchKernelGGL((conv_stack_fwd_kernel<false, false>), dim3(B * 2), dim3(1024), CS_LDS_FLOATS * sizeof(float), t.st,
-                            t.ev0, t.ev1, 0, (const void*)t.f.x, net->theta_pk[net->latest] + PK_W1F, th + OFF_B1, net->theta_pk[net->latest] + PK_W2F, th + OFF_B2, t.f.n1, t.f.n2, B,
-                            (const int64_t*)nullptr, SrcOffsets{}, (uint8_t*)nullptr);
-    } else if (k == "conv_stack_fwd_train") {
-      hipExtLaunchKernelGGL((conv_stack_fwd_kernel<true, false>), dim3(B * 2), dim3(1024), CS_LDS_FLOATS * sizeof(float), t.st,
-                            t.ev0, t.ev1, 0, (const void*)t.f.x, net->theta_pk[net->latest] + PK_W1F, th + OFF_B1, net->theta_pk[net->latest] + PK_W2F, th + OFF_B2, t.f.n1, t.f.n2, B,
-                            (const int64_t*)nullptr, SrcOffsets{}, (uint8_t*)nullptr);
-    } else if (k == "conv_stack_fwd_u8") {
-      hipExtLaunchKernelGGL((conv_stack_fwd_kernel<false, true>), dim3(B * 2), dim3(1024), CS_LDS_FLOATS * sizeof(float), t.st,
-                            t.ev0, t.ev1, 0, (const void*)t.f.xu8, net->theta_pk[net->latest] + PK_W1F, th + OFF_B1, net->theta_pk[net->latest] + PK_W2F, th + OFF_B2, t.f.n1, t.f.n2, B,
-                            (const int64_t*)nullptr, SrcOffsets{}, (uint8_t*)nullptr);
-    } else if (k == "dense1_fwd" || k == "dense1_fwd_frag") {
-      CHK(launch_dense1_fwd(net, t.f.n2, net->theta_pk[net->latest], t.f.part, B, dense_ks(B), t.st, t.ev0, t.ev1, k == "dense1_fwd_frag",
-                            k != "dense1_fwd_frag"));
-    } else if (k == "dense1_fwd_valu") {
-      launch_dense1_fwd_valu(t.f.n2, net->theta_pk[net->latest], t.f.part, B, dense_ks(B), t.st, t.ev0, t.ev1);
-    } else if (k == "conv1_dw") {
-      TL(conv1_dw_kernel<false>, dim3(conv1_dw_blocks(B)), (const void*)t.f.x, t.dn1, t.slab1, B * 7);
-    } else if (k == "conv2_dw") {
-      TL(conv2_dw_kernel<2>, dim3(B < 256 ? B : 256, 4), t.f.n1, t.dn2, t.slab2, B);
-    } else if (k == "conv_dw_pair") {
-      const int nch1 = conv1_dw_blocks(B), nch2 = B < 256 ? B : 256;
-      TL(conv_dw_pair_kernel<false>, dim3(nch1 + 4 * nch2), (const void*)t.f.x, t.dn1, t.slab1, B * 7, nch1, t.f.n1, t.dn2, t.slab2, B, nch2);
-    } else if (k == "conv2_dx") {
-      hipExtLaunchKernelGGL(conv2_dx_kernel, dim3(B, 2), dim3(512), 0, t.st, t.ev0, t.ev1, 0, t.dn2, net->theta_pk[net->latest] + PK_W2DX, t.f.n1, t.dn1, B);
-    } else if (k == "dense1_dw") {
-      HeadBwdArgs hb;
-      hb.B = B; hb.A = net->A; hb.d1 = t.f.d1; hb.dz = t.dz; hb.dv = t.dv; hb.lossrow = t.lossrow;
-      hb.g_wp = g + OFF_WP; hb.g_bp = g + off_bp(net->A); hb.g_wv = g + OFF_WV; hb.g_bv = g + OFF_BV; hb.losses = t.losses;
-      TL(dense1_dw_kernel, dim3(FLAT / 32 + net->A + 2, 2), t.f.n2, t.dd1, g + OFF_WD, g + OFF_BD, B, hb);
-    } else if (k == "dense1_dx") {
-      TL(dense1_dx_kernel, dim3(FLAT / 32, ((B + 15) / 16 + 3) / 4), t.dd1, th + OFF_WD, t.f.n2, t.dn2, B);
-    } else if (k == "dense1_bwd") {
-      Dense1BwdArgs d;
-      d.n2 = t.f.n2; d.dd1 = t.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
-      d.hb.B = B; d.hb.A = net->A; d.hb.d1 = t.f.d1; d.hb.dz = t.dz; d.hb.dv = t.dv; d.hb.lossrow = t.lossrow;
-      d.hb.g_wp = g + OFF_WP; d.hb.g_bp = g + off_bp(net->A); d.hb.g_wv = g + OFF_WV; d.hb.g_bv = g + OFF_BV; d.hb.losses = t.losses;
-      d.dw_gx = FLAT / 32 + net->A + 2; d.dw_blocks = 2 * d.dw_gx; d.dx_gx = FLAT / 32;
-      d.dx_mt = dense_dx_mt(B);
-      TL(dense1_bwd_kernel, dim3(d.dw_blocks + d.dx_gx * (((B + 16 * d.dx_mt - 1) / (16 * d.dx_mt) + 3) / 4)), d);
-    } else if (k == "conv_bwd") {
-      if (B > CONV_BWD_MAX_B) return fail(GA3C_EINVAL, "conv_bwd runs up to %d rows", CONV_BWD_MAX_B);
-      hipExtLaunchKernelGGL(conv_bwd_kernel<false>, dim3(2 * B), dim3(1024), CB_LDS_FLOATS * sizeof(float), t.st,
-                            t.ev0, t.ev1, 0, (const void*)t.f.x, t.f.n1, t.dn2, net->theta_pk[net->latest] + PK_W2DX, t.dn1, t.slab2,
-                            t.slab1, B, (const float*)nullptr, FusedUpd{});
-    } else if (k == "conv_bwd_wdstep") {
-      if (B > CONV_BWD_MAX_B) return fail(GA3C_EINVAL, "conv_bwd runs up to %d rows", CONV_BWD_MAX_B);
-      FusedUpd fu{};
-      const int l = net->latest;
-      fu.tin = net->theta[l]; fu.tout = net->theta[l]; fu.ms = net->ms; fu.mom = net->mom; fu.pk = net->theta_pk[l];
-      fu.lr = 0.f; fu.omr = 0.f; fu.mu = 0.f; fu.eps = net->cfg.rmsprop_epsilon; fu.on = 1; fu.defer_wd = 1;
-      hipExtLaunchKernelGGL((conv_bwd_kernel<false, true>), dim3(2 * B), dim3(1024), CB_LDS_FLOATS * sizeof(float), t.st,
-                            t.ev0, t.ev1, 0, (const void*)t.f.x, t.f.n1, t.dn2, net->theta_pk[l] + PK_W2DX, t.dn1, t.slab2,
-                            t.slab1, B, (const float*)(g + OFF_WD), fu);
-    } else if (k == "dense1_bwd_tile") {
-      Dense1TileArgs d;
-      d.n2 = t.f.n2; d.dd1 = t.dd1; d.wd = th + OFF_WD; d.g_wd = g + OFF_WD; d.g_bd = g + OFF_BD; d.dn2 = t.dn2; d.B = B;
-      d.hb.B = B; d.hb.A = net->A; d.hb.d1 = t.f.d1; d.hb.dz = t.dz; d.hb.dv = t.dv; d.hb.lossrow = t.lossrow;
-      d.hb.g_wp = g + OFF_WP; d.hb.g_bp = g + off_bp(net->A); d.hb.g_wv = g + OFF_WV; d.hb.g_bv = g + OFF_BV; d.hb.losses = t.losses;
-      d.role_blocks = net->A + 2 < 14 ? net->A + 2 : 14;
-      memset(&d.upd, 0, sizeof d.upd);
-      d.tail_lds = B > D1B_ROWS && B <= D1B_ROWS + D1B_TAIL_ROWS;
-      if (d.tail_lds)
-        hipExtLaunchKernelGGL((dense1_bwd_tile_kernel<0, true>), dim3(D1B_TILES + d.role_blocks), dim3(1024), D1B_LDS_FLOATS_TAIL * sizeof(float),
-                              t.st, t.ev0, t.ev1, 0, d);
-      else
-        hipExtLaunchKernelGGL(dense1_bwd_tile_kernel<0>, dim3(D1B_TILES + d.role_blocks), dim3(1024), D1B_LDS_FLOATS * sizeof(float), t.st,
-                              t.ev0, t.ev1, 0, d);
-    } else if (k == "heads") {
-      HeadArgs h;
-      memset(&h, 0, sizeof h);
-      const int ks = dense_ks(B);
-      h.part = t.f.part; h.ks = ks; h.B = B; h.A = net->A;
-      h.bd = th + OFF_BD; h.wv = th + OFF_WV; h.bv = th + OFF_BV; h.wp = th + OFF_WP; h.bp = th + off_bp(net->A);
-      h.d1 = t.f.d1; h.z = t.f.z; h.p = t.f.p; h.v = t.f.v;
-      h.log_eps = net->cfg.log_epsilon; h.min_policy = net->cfg.min_policy;
-#define HEADS_T(AM) hipExtLaunchKernelGGL((heads_kernel<false, AM>), dim3((B + HEADS_WAVES - 1) / HEADS_WAVES), dim3(64 * HEADS_WAVES), 0, t.st, t.ev0, t.ev1, 0, h)
-      if (net->A <= 8) HEADS_T(8);
-      else if (net->A <= 24) HEADS_T(24);
-      else HEADS_T(64);
-#undef HEADS_T
-    } else if (k == "slab_reduce") {
-      const int nch1 = conv1_dw_blocks(B), nch2 = B < 256 ? B : 256;
-      SlabSet s1{t.slab1, nch1, SLAB1, 256 * 16, g + OFF_W1, g + OFF_B1, (SLAB1 + 63) / 64, OFF_W1, OFF_B1};
-      SlabSet s2{t.slab2, nch2, SLAB2, 256 * 32, g + OFF_W2, g + OFF_B2, (SLAB2 + 63) / 64, OFF_W2, OFF_B2};
-      FusedUpd noupd;
-      memset(&noupd, 0, sizeof noupd);
-      hipExtLaunchKernelGGL(slab_reduce_kernel<false>, dim3(s1.nblocks + s2.nblocks), dim3(1024), 0, t.st, t.ev0, t.ev1, 0, s1, s2, noupd);
-    } else if (k == "rmsprop") {
-      const int blocks = RMS_WD_BLOCKS + (int)((net->n - (int64_t)FLAT * HID + 255) / 256);
-      TL((rmsprop_kernel<false, false>), dim3(blocks), th, net->theta[net->latest], net->ms, net->mom, t.grad, net->n,
-         0.0f, 1.0f - net->cfg.rmsprop_decay, 0.0f, net->cfg.rmsprop_epsilon, net->tt, t.scales,
-         net->theta_pk[net->latest]);
-    } else {
-      return fail(GA3C_EINVAL, "unknown kernel '%s'", kernel);
-    }
+    CHK(k->run(net, t, net->latest, batch, Ev{t.ev0, t.ev1}));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventSynchronize(t.ev1));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, t.ev0, t.ev1));
     total += ms;
   }
-#undef TL
   *elapsed_ms = (float)total;
   return GA3C_OK;
+}
+
+// a named device buffer of a lane's workspace (ga3c_net_fetch / ga3c_net_fetch_lane) and how many floats it holds
+struct NamedBuf { const char* name; const float* p; int64_t cap; };
+static int fetch_named(std::initializer_list<NamedBuf> bufs, const char* name, hipStream_t st, float* out, int64_t count) {
+  for (const NamedBuf& e : bufs) {
+    if (strcmp(e.name, name) != 0) continue;
+    if (count < 1 || count > e.cap) return fail(GA3C_EINVAL, "count %lld outside [1,%lld] for '%s'", (long long)count, (long long)e.cap, name);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(out, e.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    return GA3C_OK;
+  }
+  return fail(GA3C_EINVAL, "unknown buffer '%s'", name);
 }
 
 int ga3c_net_fetch(ga3c_net* net, const char* name, float* out, int64_t count) {
@@ -2986,20 +2999,11 @@ int ga3c_net_fetch(ga3c_net* net, const char* name, float* out, int64_t count) {
   ResidentHold hold(net->tr);
   TrainLane& t = net->tr;
   const int64_t B = net->maxB, A = net->A;
-  struct Ent { const char* n; const float* p; int64_t cap; };
-  const Ent ents[] = {{"n1", t.f.n1, B * N1S}, {"n2", t.f.n2, B * FLAT}, {"d1", t.f.d1, B * HID}, {"z", t.f.z, B * net->npc},
+  return fetch_named({{"n1", t.f.n1, B * N1S}, {"n2", t.f.n2, B * FLAT}, {"d1", t.f.d1, B * HID}, {"z", t.f.z, B * net->npc},
                       {"p", t.f.p, B * A}, {"v", t.f.v, B}, {"dz", t.dz, B * net->npc}, {"dv", t.dv, B},
                       {"dd1", t.dd1, B * HID}, {"dn2", t.dn2, B * FLAT}, {"dn1", t.dn1, B * N1S}, {"x", t.f.x, B * XS},
-                      {"part", t.f.part, 22 * B * HID}};   // dense1's partial slabs [dense_ks(b)][b][256] of the last step (alloc_fwd)
-  for (const Ent& e : ents) {
-    if (strcmp(e.n, name) == 0) {
-      if (count < 1 || count > e.cap) return fail(GA3C_EINVAL, "count %lld outside [1,%lld] for '%s'", (long long)count, (long long)e.cap, name);
-      HIPCHK(hipStreamSynchronize(t.st));
-      HIPCHK(hipMemcpy(out, e.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-      return GA3C_OK;
-    }
-  }
-  return fail(GA3C_EINVAL, "unknown buffer '%s'", name);
+                      {"part", t.f.part, 22 * B * HID}},   // dense1's partial slabs [dense_ks(b)][b][256] of the last step (alloc_fwd)
+                     name, t.st, out, count);
 }
 
 int ga3c_net_fetch_lane(ga3c_net* net, int32_t lane, const char* name, float* out, int64_t count) {
@@ -3008,17 +3012,7 @@ int ga3c_net_fetch_lane(ga3c_net* net, int32_t lane, const char* name, float* ou
   HIPCHK(hipSetDevice(net->cfg.device));
   Lane* L = net->lanes[(size_t)lane];
   const int64_t B = net->maxB, A = net->A;
-  struct Ent { const char* n; const float* p; int64_t cap; };
-  const Ent ents[] = {{"z", L->f.z, B * net->npc}, {"p", L->f.p, B * A}, {"v", L->f.v, B}};
-  for (const Ent& e : ents) {
-    if (strcmp(e.n, name) == 0) {
-      if (count < 1 || count > e.cap) return fail(GA3C_EINVAL, "count %lld outside [1,%lld] for '%s'", (long long)count, (long long)e.cap, name);
-      HIPCHK(hipStreamSynchronize(L->st));
-      HIPCHK(hipMemcpy(out, e.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-      return GA3C_OK;
-    }
-  }
-  return fail(GA3C_EINVAL, "unknown buffer '%s'", name);
+  return fetch_named({{"z", L->f.z, B * net->npc}, {"p", L->f.p, B * A}, {"v", L->f.v, B}}, name, L->st, out, count);
 }
 
 int ga3c_host_alloc(void** ptr, int64_t bytes) {

@@ -172,7 +172,21 @@ int ga3c_net_last_lanes_gpu_ms(ga3c_net* net, float* gpu_ms);
  * (nlanes = 1 works on any net); host wall-clock from the first launch to all lanes drained. */
 int ga3c_net_time_train_lanes(ga3c_net* net, int32_t batch, int32_t iters, int32_t nlanes, float learning_rate,
                               float beta, float* elapsed_ms);
-/* Same bracket around ONE kernel of the step (name as in DESIGN.md, e.g. "conv1_fwd"). */
+/* `iters` launches of ONE kernel of the image network's step on train lane 0, each between its own start / stop events; the
+ * sum of the kernel times in milliseconds.  Every name is the step's own launcher of that kernel (grid, LDS, arguments and
+ * whatever depends on `batch` alone are the step's) with the named variant forced at any batch, on the buffers the last step
+ * left:
+ *   forward   "conv_stack_fwd" (prediction form, f32 states), "conv_stack_fwd_train", "conv_stack_fwd_u8", "conv1_fwd",
+ *             "conv1_fwd_u8", "conv2_fwd" (half grid), "conv2_fwd_q" (quarter grid), "dense1_fwd" (the step's choice, tile or
+ *             fragment), "dense1_fwd_frag", "dense1_fwd_valu", "heads" (prediction form of the net's head)
+ *   backward  "dense1_bwd_tile", "conv_bwd" (batch <= 128), "conv_bwd_wdstep" (with the deferred dense1/w step, lr = 0),
+ *             "conv2_dw", "conv2_dx", "conv_dw_pair", "conv1_dw", "conv1_dw_u8", "slab_reduce" (the slabs the step of `batch`
+ *             rows leaves), all without the fused update; "rmsprop" (no clip, no momentum, lr = 0)
+ *   round 1   "dense1_dw", "dense1_dx", "dense1_bwd": kept for comparison, no step launches them; "dense1_dw" and
+ *             "dense1_bwd" are GA3C_ESTATE on a GA3C_FLAG_CONTINUOUS net
+ * "rmsprop" and "conv_bwd_wdstep" step in place with lr = 0: they advance the optimizer's `ms` ("conv_bwd_wdstep" on a net
+ * with momentum also decays `mom` and moves dense1/w by it): use a scratch net.
+ * An unknown name is GA3C_EINVAL. */
 int ga3c_net_time_kernel(ga3c_net* net, const char* kernel, int32_t batch, int32_t iters,
                          float* elapsed_ms);
 
