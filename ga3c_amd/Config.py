@@ -180,6 +180,11 @@ class Config:
                                         # episode records are the exploring one's
     DEVICE_DDPG_EVAL_EVERY = 1000       # train steps between two evaluations (>= 1); one more before the first train step
     DEVICE_DDPG_EVAL_TARGET = False     # True: evaluate the target actor instead of the online one
+    DEVICE_DDPG_NOISE = 'shared'        # 'shared': one step of the handle's noise process per actor step, added to every
+                                        # environment's action; 'per_env' (DEVICE_DDPG with add_OUnoise): every environment has an
+                                        # Ornstein-Uhlenbeck process of its own, as the reference's predicting processes had,
+                                        # stepped inside the predict kernel
+    DEVICE_DDPG_NOISE_RESET = False     # True: under 'per_env' an environment's process restarts at 0 when its episode ends
 
 
 VECTOR_GAMES = ('Pendulum-v0', 'CartPole-v0')      # games whose state is a vector (Server.py:35-43 of the reference)
@@ -351,6 +356,14 @@ def _resolve_device_ddpg(n, pendulum):
             raise ValueError("DEVICE_DDPG_EVAL_EVERY=%r: a whole number of train steps >= 1" % (k,))
         if not isinstance(Config.DEVICE_DDPG_EVAL_TARGET, bool):
             raise ValueError("DEVICE_DDPG_EVAL_TARGET=%r: True or False" % (Config.DEVICE_DDPG_EVAL_TARGET,))
+    mode = Config.DEVICE_DDPG_NOISE
+    if mode not in ('shared', 'per_env'):
+        raise ValueError("DEVICE_DDPG_NOISE=%r: 'shared' or 'per_env'" % (mode,))
+    if mode == 'per_env' and not Config.add_OUnoise:
+        raise ValueError("DEVICE_DDPG_NOISE='per_env' with add_OUnoise=%r is not supported: there is no noise process to give "
+                         "each environment" % (Config.add_OUnoise,))
+    if not isinstance(Config.DEVICE_DDPG_NOISE_RESET, bool):
+        raise ValueError("DEVICE_DDPG_NOISE_RESET=%r: True or False" % (Config.DEVICE_DDPG_NOISE_RESET,))
 
 
 def _refuse_eval_without_device_ddpg():
@@ -360,15 +373,23 @@ def _refuse_eval_without_device_ddpg():
                          "the loop that steps the DDPG actors on the device" % (Config.DEVICE_DDPG_EVAL_ENVS,))
 
 
+def _refuse_env_noise_without_device_ddpg():
+    """DEVICE_DDPG_NOISE = 'per_env'  asks for the noise of the DDPG handle's device actors."""
+    if getattr(Config, "DEVICE_DDPG_NOISE", 'shared') == 'per_env':
+        raise ValueError("DEVICE_DDPG_NOISE='per_env' needs DEVICE_DDPG (with DEVICE_AGENTS > 0): the per-environment noise is "
+                         "that of the DDPG actors stepped on the device")
+
+
 def resolve_device_agents(explicit=()):
     """What DEVICE_AGENTS > 0 cannot be combined with.  Call after resolve_action_space and resolve_ddpg.  With
     DEVICE_AGENTS = 0 nothing is checked and nothing changes, except that DEVICE_DDPG, which asks for them, raises, and so
-    does DEVICE_DDPG_EVAL_ENVS > 0, which asks for DEVICE_DDPG."""
+    do DEVICE_DDPG_EVAL_ENVS > 0 and DEVICE_DDPG_NOISE = 'per_env', which ask for DEVICE_DDPG."""
     n = int(Config.DEVICE_AGENTS)
     if n == 0:
         if getattr(Config, "DEVICE_DDPG", False):
             raise ValueError("DEVICE_DDPG needs DEVICE_AGENTS > 0: the number of environments on the device")
         _refuse_eval_without_device_ddpg()
+        _refuse_env_noise_without_device_ddpg()
         return
     if n < 0:
         raise ValueError("DEVICE_AGENTS=%d: 0 (off) or the number of environments on the device" % n)
@@ -377,6 +398,7 @@ def resolve_device_agents(explicit=()):
         _resolve_device_ddpg(n, pendulum)
         return
     _refuse_eval_without_device_ddpg()
+    _refuse_env_noise_without_device_ddpg()
     if Config.USE_DDPG:
         raise ValueError("DEVICE_AGENTS with USE_DDPG is not supported: the device actors step CartPole-v0 only, or "
                          "Pendulum-v0 under the actor-critic network (DEVICE_PENDULUM); under DDPG they need DEVICE_DDPG=True")

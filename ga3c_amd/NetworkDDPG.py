@@ -13,6 +13,8 @@ returns into the ring and a discount per slot beside them (nstep_create, DESIGN.
 critic's head has Config.DDPG_ATOMS outputs, a categorical distribution over fixed returns (dist_create).
 eval_create attaches environments that the actor walks without noise from fixed start states, an episode per launch: how
 good the actor is right now, with nothing of the training disturbed (Config.DEVICE_DDPG_EVAL_ENVS).
+Under Config.DEVICE_DDPG_NOISE = 'per_env' every device actor has an Ornstein-Uhlenbeck process of its own, stepped in the predict
+kernel (envnoise_create).
 """
 import ctypes as C
 import os
@@ -354,14 +356,45 @@ class Network(DeviceActors, NativeHandle):
     ACTOR_SCALARS = {"batch": np.int32, "draw_seed": np.int64, "nstep": np.int32, "nstep_count": np.int64}
     ACTOR_ROWS = {"slots": "batch"}
 
-    def actors_create(self, n, time_max=None, discount=None, seed=None, updates=None, batch=None, draw_seed=None):
-        """n Pendulum-v0 environments on the handle, with Config's train-step rows, updates per actor step and draw seed unless
-        given.  time_max and discount are ThreadDeviceAgents' call shape: a ring of transitions has neither."""
+    # ... and, on a handle whose actors have per-environment noise (Config.DEVICE_DDPG_NOISE = 'per_env'), these
+    # too; the handle's own ACTOR_FIELDS / ACTOR_SCALARS list them while it has it: without it the library knows no such names
+    NOISE_FIELDS = {"noise_x": (np.float32, "A"), "noise_n": (np.float32, "A")}
+    NOISE_SCALARS = {"noise_count": np.int64}
+
+    def actors_create(self, n, time_max=None, discount=None, seed=None, updates=None, batch=None, draw_seed=None, noise=None,
+                      noise_seed=None, noise_reset=None):
+        """n Pendulum-v0 environments on the handle, with Config's train-step rows, updates per actor step, draw seed and
+        exploration noise ('shared' or 'per_env', its seed RANDOM_SEED + 2: + 1 is the evaluation's) unless given.  time_max and
+        discount are ThreadDeviceAgents' call shape: a ring of transitions has neither."""
+        noise = Config.DEVICE_DDPG_NOISE if noise is None else noise
+        if noise not in ('shared', 'per_env'):
+            raise ValueError("noise=%r: 'shared' or 'per_env'" % (noise,))
         self._call("actors_create", int(n), int(Config.DEVICE_DDPG_UPDATES if updates is None else updates),
                    int(Config.RANDOM_SEED if seed is None else seed))
         self.num_actors = int(n)
         self.actors_set("batch", min(self.max_batch, int(Config.TRAINING_MIN_BATCH_SIZE if batch is None else batch)))
         self.actors_set("draw_seed", Config.REPLAY_BUFFER_RANDOM_SEED if draw_seed is None else draw_seed)
+        if noise == 'per_env':
+            self.envnoise_create(noise_seed, noise_reset)
+
+    def envnoise_create(self, seed=None, reset=None):
+        """Gives every environment of the handle's device actors a noise process of its own."""
+        self._call("envnoise_create", int(Config.RANDOM_SEED + 2 if seed is None else seed),
+                   int(bool(Config.DEVICE_DDPG_NOISE_RESET if reset is None else reset)))
+        self.ACTOR_FIELDS = dict(type(self).ACTOR_FIELDS, **self.NOISE_FIELDS)
+        self.ACTOR_SCALARS = dict(type(self).ACTOR_SCALARS, **self.NOISE_SCALARS)
+
+    def envnoise_destroy(self):
+        self._call("envnoise_destroy")
+        self._forget_envnoise()
+
+    def _forget_envnoise(self):
+        self.__dict__.pop("ACTOR_FIELDS", None)
+        self.__dict__.pop("ACTOR_SCALARS", None)
+
+    def actors_destroy(self):
+        super().actors_destroy()
+        self._forget_envnoise()
 
     def actors_run(self, steps, train=True, noise=None):
         """`steps` actor steps, each followed by DEVICE_DDPG_UPDATES train steps once the ring holds more than a batch, at the

@@ -225,6 +225,9 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_eval_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f64p]),
     "ga3c_ddpg_eval_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "ga3c_ddpg_eval_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    # per-environment noise of a DDPG handle's device actors (Config.DEVICE_DDPG_NOISE), include/ga3c_abi.h
+    "ga3c_ddpg_envnoise_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
+    "ga3c_ddpg_envnoise_destroy": (C.c_int, [C.c_void_p]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

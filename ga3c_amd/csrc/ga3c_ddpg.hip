@@ -53,6 +53,10 @@
 // statement):
 //   ddpg_eval_kernel<Env>    one workgroup per 16 evaluation environments walks a whole episode: actor_fwd without noise, the
 //                            environment's step on the thread's registers, the f64 sum of the rewards; one launch per evaluation
+// Per-environment noise (ga3c_ddpg_envnoise_create, Config.DEVICE_DDPG_NOISE; tests/envnoise_oracle.py is the same
+// statement):
+//   ddpg_predict_envnoise_kernel  ddpg_predict_kernel's body with every environment's own OU step in its epilogue; launched in
+//                                 its place by an actor step under GA3C_DDPG_NOISE_OWN, which stays predict + 2 launches
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -734,21 +738,65 @@ __global__ __launch_bounds__(THREADS) void ddpg_dist_actor_kernel(Layout L, cons
   actor_rows<true>(L, th, src, B, nz, w, z, lg);
 }
 
-__global__ __launch_bounds__(THREADS) void ddpg_predict_kernel(Layout L, const float* __restrict__ th, Input in, int B, Noise nz,
-                                                               float* __restrict__ a_out) {
+// A prediction's rows up to the epilogue: the online actor on the tile's inputs -> its tanh output [A][16] in LDS, complete for
+// every thread.  (static: its LDS arrays stay internal to each kernel.)
+static __device__ __forceinline__ const float* predict_rows(const Layout& L, const float* __restrict__ th, const Input& in,
+                                                            int row0, int nrows) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
   __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
-  const int S = L.S, A = L.A;
-  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
-  load_input_tile<THREADS, false>(in, S, row0, nrows, xin, nullptr);
+  load_input_tile<THREADS, false>(in, L.S, row0, nrows, xin, nullptr);
   __syncthreads();
   actor_fwd(L, th, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+  return act;
+}
+
+__global__ __launch_bounds__(THREADS) void ddpg_predict_kernel(Layout L, const float* __restrict__ th, Input in, int B, Noise nz,
+                                                               float* __restrict__ a_out) {
+  const int A = L.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  const float* act = predict_rows(L, th, in, row0, nrows);
   for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
     const int i = e / TILE, r = e % TILE;
     const float v = wrap_action(act[e] + nz.v[i], nz.wrap);
     if (r < nrows) a_out[(size_t)(row0 + r) * A + i] = v;
+  }
+}
+
+// Per-environment exploration noise of a handle's device actors (ga3c_ddpg_envnoise_create): row i is
+// environment i, x and n are [N][A].  Everything but the two buffers and `done` is a launch argument the host knows.
+struct EnvNoise {
+  float* x;                  // the environments' OU states
+  float* n;                  // their last normal draws
+  const int* done;           // the last step's done, read when `reset` is set
+  uint64_t seed, count;      // the draw of action j at prediction `count` is number k = count A + j of stream i
+  double sigma, theta, dt, sqrt_dt;      // the handle's config as ga3c_ddpg_noise_step reads it: f32 values, sqrt in f64
+  int reset;                 // x restarts at 0 after an episode's end
+};
+
+// ddpg_predict_kernel with 8r's epilogue in the shared process's place: the thread that owns (action j, environment i) steps
+// x_i[j] by ga3c_ddpg_noise_step's expression on 8n's Box-Muller draw and adds it, unwrapped.  Rows >= B touch nothing.
+__global__ __launch_bounds__(THREADS) void ddpg_predict_envnoise_kernel(Layout L, const float* __restrict__ th, Input in, int B,
+                                                                        EnvNoise z, float* __restrict__ a_out) {
+#pragma clang fp contract(off)
+  const int A = L.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  const float* act = predict_rows(L, th, in, row0, nrows);
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const int j = e / TILE, r = e % TILE;
+    if (r >= nrows) continue;
+    const uint64_t i = (uint64_t)(row0 + r);
+    const size_t at = (size_t)i * A + j;
+    const uint64_t k = z.count * (uint64_t)A + (uint64_t)j;
+    const double u1 = 1.0 - ga3c_uniform::actor_uniform(z.seed, i, 2 * k);
+    const double u2 = ga3c_uniform::actor_uniform(z.seed, i, 2 * k + 1);
+    const float nn = (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+    const double xp = z.reset && z.done[i] ? 0.0 : (double)z.x[at];
+    const float xn = (float)(xp + z.theta * (0.0 - xp) * z.dt + z.sigma * z.sqrt_dt * (double)nn);
+    z.x[at] = xn;
+    z.n[at] = nn;
+    a_out[at] = act[e] + xn;
   }
 }
 
@@ -1314,6 +1362,12 @@ struct DActors : ga3c_actors::ActorsCore {     // block: every device buffer of 
   bool started = false;                 // the first actor step is the environments' step(None): one flag for all of them
   NWindow win{};                        // of a handle with n-step returns (in `block`); win.n = 0: none
   int64_t count = 0;                    // transitions every environment has made: the c of the next step
+  EnvNoise noise{};                     // per-environment noise (ga3c_ddpg_envnoise_create): x, n in a block of their own at
+                                        // noise.x; noise.x = null: none, the handle's shared process serves the predictions
+  ~DActors() {
+    (void)hipFree(noise.x);
+    (void)hipGetLastError();
+  }
 };
 
 // Twin critics of a handle (ga3c_ddpg_twin_create).  The arenas hold view.off[NVARS] floats while it lives.
@@ -2714,9 +2768,16 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
     const int first = a->started ? 0 : 1;
     Noise nz;
     if (!first) {                       // step(None) asks for no prediction: no step of the noise process either
-      CHK(make_noise(m, noise_mode, noise, &nz));
-      hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(N)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0],
-                         Input{reinterpret_cast<const char*>(d.obs), nullptr, 4 * (int64_t)DEnv::S}, N, nz, d.action);
+      const Input in{reinterpret_cast<const char*>(d.obs), nullptr, 4 * (int64_t)DEnv::S};
+      if (a->noise.x && noise_mode == GA3C_DDPG_NOISE_OWN) {      // 8r: every environment's own process, stepped by the kernel
+        hipLaunchKernelGGL(ddpg_predict_envnoise_kernel, dim3(tiles(N)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0],
+                           in, N, a->noise, d.action);
+        ++a->noise.count;
+      } else {
+        CHK(make_noise(m, noise_mode, noise, &nz));
+        hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(N)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in, N, nz,
+                           d.action);
+      }
     }
     const int wn = a->win.n;            // n-step returns: a row leaves the window from transition n - 1 on
     const bool emit = !first && a->count >= wn - 1;
@@ -2819,10 +2880,84 @@ int dactors_access(ga3c_ddpg* m, const char* name, void* out, const void* in, in
     if (a->slots_rows) HIPCHK(hipMemcpy(out, m->per ? m->per->slots : a->slots, (size_t)bytes, hipMemcpyDeviceToHost));
     return GA3C_OK;
   }
+  if (nm == "noise_x" || nm == "noise_n" || nm == "noise_count") {      // per-environment noise
+    EnvNoise& z = a->noise;
+    if (!z.x) return fail(GA3C_ESTATE, "%s: the device actors have no per-environment noise (ga3c_ddpg_envnoise_create)", name);
+    if (nm == "noise_count") {          // the c of the next prediction
+      CHK(sized(8));
+      if (out) { *static_cast<int64_t*>(out) = (int64_t)z.count; return GA3C_OK; }
+      const int64_t v = *static_cast<const int64_t*>(in);
+      if (v < 0) return fail(GA3C_EINVAL, "noise_count %lld is negative", (long long)v);
+      z.count = (uint64_t)v;
+      return GA3C_OK;
+    }
+    const size_t cells = (size_t)d.N * m->L.A;
+    CHK(sized(4 * (int64_t)cells));
+    if (out) {
+      HIPCHK(hipMemcpy(out, nm == "noise_x" ? z.x : z.n, (size_t)bytes, hipMemcpyDeviceToHost));
+      return GA3C_OK;
+    }
+    if (nm == "noise_n") return fail(GA3C_EINVAL, "%s is read only", name);
+    const float* v = static_cast<const float*>(in);
+    for (size_t i = 0; i < cells; ++i)
+      if (!std::isfinite(v[i])) return fail(GA3C_EINVAL, "noise_x[%zu] = %g is not finite", i, v[i]);
+    HIPCHK(hipMemcpy(z.x, in, (size_t)bytes, hipMemcpyHostToDevice));
+    return GA3C_OK;
+  }
   return ga3c_actors::field_access(a, d.N, name, out, in, bytes);
 }
 
 }  // namespace
+
+// ---- per-environment exploration noise
+
+int ga3c_ddpg_envnoise_create(ga3c_ddpg* m, int64_t seed, int32_t reset_on_done) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (reset_on_done != 0 && reset_on_done != 1) return fail(GA3C_EINVAL, "reset_on_done %d is neither 0 nor 1", reset_on_done);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  DActors* a = m->actors;
+  if (!a) return fail(GA3C_ESTATE, "envnoise_create: this network has no device actors, whose number sizes the noise state");
+  if (a->noise.x) return fail(GA3C_ESTATE, "the device actors have per-environment noise already");
+  const ga3c_ddpg_config& c = m->cfg;
+  if (!(c.flags & GA3C_DDPG_OU_NOISE))
+    return fail(GA3C_ESTATE, "envnoise_create: the handle has no noise process to give each environment (GA3C_DDPG_OU_NOISE)");
+  const size_t cells = (size_t)a->d.N * m->L.A;
+  float* block = nullptr;
+  if (hipMalloc((void**)&block, 2 * cells * sizeof(float)) != hipSuccess || hipMemset(block, 0, 2 * cells * sizeof(float)) != hipSuccess) {
+    (void)hipFree(block);
+    (void)hipGetLastError();
+    return fail(GA3C_EHIP, "no memory for the noise of %d environments (%zu bytes)", a->d.N, 2 * cells * sizeof(float));
+  }
+  EnvNoise& z = a->noise;
+  z.x = block;
+  z.n = block + cells;
+  z.done = a->d.done;
+  z.seed = (uint64_t)seed;
+  z.count = 0;
+  z.sigma = (double)c.ou_sigma;
+  z.theta = (double)c.ou_theta;
+  z.dt = (double)c.ou_dt;
+  z.sqrt_dt = std::sqrt((double)c.ou_dt);
+  z.reset = reset_on_done;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_envnoise_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  DActors* a = m->actors;
+  if (!a || !a->noise.x) return fail(GA3C_ESTATE, "the device actors have no per-environment noise");
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIPCHK(hipStreamSynchronize(m->st));
+  }
+  (void)hipFree(a->noise.x);
+  (void)hipGetLastError();
+  a->noise = EnvNoise{};
+  return GA3C_OK;
+}
 
 int ga3c_ddpg_actors_get(ga3c_ddpg* m, const char* name, void* out, int64_t bytes) {
   if (!out) return fail(GA3C_EINVAL, "null argument");

@@ -848,6 +848,28 @@ int ga3c_ddpg_eval_run(ga3c_ddpg* net, int32_t steps, int32_t target, double* to
 int ga3c_ddpg_eval_get(ga3c_ddpg* net, const char* name, void* out, int64_t bytes);
 int ga3c_ddpg_eval_set(ga3c_ddpg* net, const char* name, const void* in, int64_t bytes);
 
+/* ---- Per-environment exploration noise of a DDPG handle's device actors (Config.DEVICE_DDPG_NOISE = 'per_env', DESIGN.md 8r;
+ * tests/envnoise_oracle.py is the same statement in numpy).  Attached to a handle's device actors; without it every prediction
+ * of an actor step adds one step of the handle's shared process to all n rows, as before.
+ * State: x[n][A] f32, every environment's Ornstein-Uhlenbeck state, 0 at create; n[n][A], the last normal draws; c, the number
+ * of predictions made with it (step(None) predicts nothing and does not count).
+ * An actor step under GA3C_DDPG_NOISE_OWN then runs, for environment i and action j, with k = c A + j:
+ *   u1 = 1 - u(seed, i, 2k), u2 = u(seed, i, 2k + 1), u the counter uniform of the device actors
+ *   n = (f32)(sqrt(-2 ln u1) cos(2 pi u2)) in f64
+ *   x_prev = 0 if reset_on_done and environment i's last step was done, else x_i[j]
+ *   x' = (f32)(x_prev + theta (0 - x_prev) dt + sigma sqrt(dt) n) in f64 without contraction: ga3c_ddpg_noise_step's expression
+ *   action = actor(obs_i)[j] + x' in f32, not wrapped (the environment step wraps)
+ * in the predict kernel's epilogue: no further launch, no step of the shared process.  GA3C_DDPG_NOISE_GIVEN and
+ * GA3C_DDPG_NOISE_NONE do what they did and leave x, n and c alone.  A train step's step 4 takes one step of the shared process
+ * whichever way the predictions are served.  The seed is this state's own: the environments' draws do not move.
+ * create: GA3C_EINVAL for reset_on_done outside 0..1; GA3C_ESTATE without device actors, on a second create, and on a handle
+ * without GA3C_DDPG_OU_NOISE.  destroy: GA3C_ESTATE without one; also done by ga3c_ddpg_actors_destroy and ga3c_ddpg_destroy.
+ * ga3c_ddpg_actors_get / _set by name: "noise_x" f32 [n][A], get and set (finite values, else GA3C_EINVAL); "noise_n" f32
+ * [n][A], get only; "noise_count" i64, the c of the next prediction, get and set (>= 0).  GA3C_ESTATE for all three on a handle
+ * whose actors have no per-environment noise. */
+int ga3c_ddpg_envnoise_create(ga3c_ddpg* net, int64_t seed, int32_t reset_on_done);
+int ga3c_ddpg_envnoise_destroy(ga3c_ddpg* net);
+
 #ifdef __cplusplus
 }
 #endif

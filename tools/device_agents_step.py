@@ -9,9 +9,10 @@ Pendulum's environments run in lockstep: one train step of N (TIME_MAX + 1) rows
 train steps of --batch ring rows after every actor step, --prioritized for the draw by priority, --nstep N for n-step returns
 (Config.DDPG_NSTEP, DESIGN.md 8o; profiles/nstep_step.txt); the call waits once, at its end (profiles/device_agents_ddpg.txt);
 --eval-envs E --eval-every K for an evaluation of E noise-free episodes whenever the train steps pass a multiple of K, as
-ThreadDeviceAgents runs them under DEVICE_DDPG_EVAL_ENVS (profiles/ddpg_eval.txt), inside the timed rounds.
+ThreadDeviceAgents runs them under DEVICE_DDPG_EVAL_ENVS (DESIGN.md 8q; profiles/ddpg_eval.txt), inside the timed rounds;
+--noise per_env for every environment's own noise process (Config.DEVICE_DDPG_NOISE; profiles/envnoise_step.txt).
 usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]
-       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1] [--eval-envs 0] [--eval-every 1000]]"""
+       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1] [--eval-envs 0] [--eval-every 1000] [--noise shared|per_env]]"""
 import argparse
 import json
 import os
@@ -39,6 +40,7 @@ def main():
     ap.add_argument("--nstep", type=int, default=1, help="--ddpg: steps of the returns the actors write (1..16)")
     ap.add_argument("--eval-envs", type=int, default=0, help="--ddpg: evaluation environments (0: none)")
     ap.add_argument("--eval-every", type=int, default=1000, help="--ddpg: train steps between two evaluations")
+    ap.add_argument("--noise", choices=("shared", "per_env"), default="shared", help="--ddpg: the actors' exploration noise")
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
@@ -49,6 +51,7 @@ def main():
         num_actions, state_dim = 1, (3,)
         Config.PRIORITIZED_REPLAY = args.prioritized
         Config.DDPG_NSTEP = args.nstep
+        Config.DEVICE_DDPG_NOISE = args.noise
         if args.prioritized:
             Config.DDPG_CRITIC_LOSS = 'paired'
     elif args.game == "Pendulum-v0":
@@ -86,6 +89,7 @@ def main():
         rates.sort()
         per_step_us = 1e6 * n / rates[len(rates) // 2]
         extra = ({"ddpg": True, "batch": args.batch, "updates": args.updates, "prioritized": args.prioritized, "nstep": args.nstep,
+                  "noise": args.noise,
                   "eval_envs": args.eval_envs, "eval_every": args.eval_every, "evaluations": evaluations,
                   "train_steps_per_s_median": round(sorted(train_rates)[len(train_rates) // 2])} if args.ddpg else {})
         print(json.dumps({**extra, "game": args.game, "agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,

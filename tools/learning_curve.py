@@ -3,13 +3,13 @@
 with no Server: --actors device actors (Config.DEVICE_DDPG's loop, actors_run(32) at a time, one train step of --batch rows per
 actor step once the ring holds more than a batch), and every --every train steps a noise-free evaluation of --eval-envs episodes
 of 200 steps from fixed start states (eval_run; one more before the first train step).  The variant is given as the product's
-own KEY=VALUE settings and checked by the product's resolvers.  Writes <out-dir>/<name>.csv,
+own KEY=VALUE settings and checked by the product's resolvers; --noise per_env is DEVICE_DDPG_NOISE=per_env.  Writes <out-dir>/<name>.csv,
     training_step, n, steps, mean, min, max, mean_gym_return, wall_s
 (mean_gym_return = (mean + steps) / 0.005 undoes the wrapper's r * 0.005 - 1: gym's number for Pendulum-v0, 0 at best and about
 -1200 to -1500 for a policy that does nothing), and prints one JSON line: the first evaluation, the best, the mean of the last
 five, the wall time.  profiles/learning_curves.md is the record of the variants that exist.
 usage: python tools/learning_curve.py --name paired [--train-steps 60000] [--every 1000] [--actors 256] [--batch 64]
-       [--eval-envs 64] [--out-dir profiles/learning_curves] DDPG_CRITIC_LOSS=paired ..."""
+       [--eval-envs 64] [--noise shared|per_env] [--out-dir profiles/learning_curves] DDPG_CRITIC_LOSS=paired ..."""
 import argparse
 import json
 import os
@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--actors", type=int, default=256)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--eval-envs", type=int, default=64)
+    ap.add_argument("--noise", choices=("shared", "per_env"), default=None, help="DEVICE_DDPG_NOISE, unless the settings give it")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "learning_curves"))
     ap.add_argument("settings", nargs="*", help="KEY=VALUE, as GA3C.py takes them")
     args = ap.parse_args()
@@ -39,6 +40,8 @@ def main():
     Config.GAME, Config.USE_DDPG, Config.DEVICE_DDPG = 'Pendulum-v0', True, True
     Config.DEVICE_AGENTS, Config.TRAINING_MIN_BATCH_SIZE = args.actors, args.batch
     Config.DEVICE_DDPG_EVAL_ENVS, Config.DEVICE_DDPG_EVAL_EVERY = args.eval_envs, args.every
+    if args.noise is not None:
+        Config.DEVICE_DDPG_NOISE = args.noise
     GA3C.apply_argv(args.settings)              # the variant, coerced and resolved as the product does
     resolve_device_agents()
     from NetworkDDPG import Network
