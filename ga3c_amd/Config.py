@@ -94,6 +94,13 @@ class Config:
     DDPG_ATOMS = 51                     # atoms of the support (2..64)
     DDPG_V_MIN = -100.0                 # the support's ends.  EnvironmentPend hands on r 0.005 - 1 in [-1.09, -1]: the gamma = 0.99
     DDPG_V_MAX = 0.0                    # return over 200 steps lies above -94 and below 0
+    DDPG_POPART = False                 # USE_DDPG only: the critic regresses on targets normalised by running statistics of the
+                                        # targets, and its output layer is rescaled whenever they move so that no prediction does
+                                        # (van Hasselt et al. 2016, "PopArt"); needs DDPG_CRITIC_LOSS = 'paired', excludes DDPG_TWIN
+                                        # and DDPG_DISTRIBUTIONAL
+    DDPG_POPART_BETA = 3e-4             # step of the statistics: mu' = (1 - beta) mu + beta mean(y), likewise for mean(y^2) (0..1)
+    DDPG_POPART_SIGMA_MIN = 1e-4        # sigma = sqrt(nu - mu^2) is clamped into [DDPG_POPART_SIGMA_MIN, DDPG_POPART_SIGMA_MAX]
+    DDPG_POPART_SIGMA_MAX = 1e6
     tau = 0.001
     gamma = 0.99
     actor_lr = 1.0                      # factors on the annealed learning rate; the later of the two assignments in the
@@ -243,6 +250,8 @@ def resolve_ddpg(explicit=()):
             raise ValueError("DDPG_TWIN needs USE_DDPG: the twin critics are the DDPG handle's")
         if Config.DDPG_DISTRIBUTIONAL:
             raise ValueError("DDPG_DISTRIBUTIONAL needs USE_DDPG: the distributional critic is the DDPG handle's")
+        if Config.DDPG_POPART:
+            raise ValueError("DDPG_POPART needs USE_DDPG: the normalised critic is the DDPG handle's")
         _resolve_nstep()
         return
     if not Config.CONTINUOUS_INPUT:
@@ -300,6 +309,20 @@ def resolve_ddpg(explicit=()):
         if not Config.DDPG_V_MIN < Config.DDPG_V_MAX:
             raise ValueError("DDPG_V_MIN / DDPG_V_MAX = %r / %r: the support's smaller end first"
                              % (Config.DDPG_V_MIN, Config.DDPG_V_MAX))
+    if Config.DDPG_POPART:
+        if Config.DDPG_CRITIC_LOSS != 'paired':
+            raise ValueError("DDPG_POPART with DDPG_CRITIC_LOSS=%r is not supported: under the fork's loss the critic regresses on "
+                             "the batch mean of y and a row has no target of its own to normalise.  Set DDPG_CRITIC_LOSS=paired"
+                             % (Config.DDPG_CRITIC_LOSS,))
+        if Config.DDPG_TWIN:
+            raise ValueError("DDPG_POPART with DDPG_TWIN is not supported: the statistics normalise one scalar critic")
+        if Config.DDPG_DISTRIBUTIONAL:
+            raise ValueError("DDPG_POPART with DDPG_DISTRIBUTIONAL is not supported: the support fixes the returns' scale")
+        beta, lo, hi = Config.DDPG_POPART_BETA, Config.DDPG_POPART_SIGMA_MIN, Config.DDPG_POPART_SIGMA_MAX
+        if isinstance(beta, bool) or not 0.0 <= beta <= 1.0:
+            raise ValueError("DDPG_POPART_BETA=%r outside [0, 1]" % (beta,))
+        if isinstance(lo, bool) or isinstance(hi, bool) or not 0.0 < lo < hi < float("inf"):
+            raise ValueError("DDPG_POPART_SIGMA_MIN / _MAX = %r / %r: two finite numbers, 0 < the first < the second" % (lo, hi))
     _resolve_nstep()
     Config.USE_REPLAY_MEMORY = True
     Config.DISCOUNTING = False

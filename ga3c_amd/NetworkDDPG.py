@@ -14,7 +14,8 @@ critic's head has Config.DDPG_ATOMS outputs, a categorical distribution over fix
 eval_create attaches environments that the actor walks without noise from fixed start states, an episode per launch: how
 good the actor is right now, with nothing of the training disturbed (Config.DEVICE_DDPG_EVAL_ENVS).
 Under Config.DEVICE_DDPG_NOISE = 'per_env' every device actor has an Ornstein-Uhlenbeck process of its own, stepped in the predict
-kernel (envnoise_create).
+kernel (envnoise_create).  Under Config.DDPG_POPART the critic regresses on normalised targets and the handle has
+two more variables, critic_popart/mu and /nu, the statistics that its output layer is rescaled with (popart_create).
 """
 import ctypes as C
 import os
@@ -37,8 +38,15 @@ TWIN_TRAINABLE = tuple("critic2_" + k[len("critic_"):] for k in CRITIC_TRAINABLE
 VALUE, TARGET, SLOT_A, SLOT_B, GRAD = range(5)
 
 
-def param_shapes(state_dim, num_actions, twin=False, atoms=None):
+POPART_STATS = ("critic_popart/mu", "critic_popart/nu")      # of a handle with PopArt: not trainable, behind the 26
+
+
+def param_shapes(state_dim, num_actions, twin=False, atoms=None, popart=False):
     S, A = int(state_dim), int(num_actions)
+    if popart:                              # + the two statistics (never with a twin or an atom head)
+        shapes = param_shapes(S, A)
+        shapes.update({k: (1,) for k in POPART_STATS})
+        return shapes
     if atoms is not None:                   # a distributional critic: the head has one output per atom
         shapes = param_shapes(S, A, twin)
         shapes.update({"critic_output/W": (H2, int(atoms)), "critic_output/b": (int(atoms),)})
@@ -153,6 +161,10 @@ class Network(DeviceActors, NativeHandle):
             self.set_variable_value(k, target[k], TARGET)
         self._log_lock = threading.Lock()
         self.logging = (0.0, 0.0)               # Q_max, Q_avg of the last step (NetworkDDPG.py:98)
+        self.popart = bool(Config.DDPG_POPART)
+        if self.popart:                         # after the initial values: it adds the two statistics, 0 and 1, and moves no weight
+            self._call("popart_create", float(Config.DDPG_POPART_BETA), float(Config.DDPG_POPART_SIGMA_MIN),
+                       float(Config.DDPG_POPART_SIGMA_MAX))
         self.prioritized = bool(Config.PRIORITIZED_REPLAY)
         self.replay_beta = Config.PRIORITIZED_REPLAY_BETA_START      # exponent of the importance weights; Server.main anneals it
         if self.prioritized:
@@ -331,6 +343,22 @@ class Network(DeviceActors, NativeHandle):
         self._call("dist_info", C.byref(n), C.byref(lo), C.byref(hi))
         return n.value, lo.value, hi.value
 
+    # ---- PopArt (Config.DDPG_POPART) ----------------------------------------------------------
+    def popart_info(self):
+        """-> (beta, mu, nu, sigma): the step of the statistics, the targets' running first and second moment, and the scale
+        they give.  The critic's output n stands for the return sigma n + mu."""
+        beta, mu, nu, sigma = C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        self._call("popart_info", C.byref(beta), C.byref(mu), C.byref(nu), C.byref(sigma))
+        return beta.value, mu.value, nu.value, sigma.value
+
+    def log_popart(self, training_step):
+        """training_step, mu, nu, sigma appended to logs/<model>/popart.csv, beside eval.csv."""
+        _, mu, nu, sigma = self.popart_info()
+        os.makedirs("logs/%s" % self.model_name, exist_ok=True)
+        with self._log_lock:
+            with open("logs/%s/popart.csv" % self.model_name, "a") as f:
+                f.write("%d,%.9g,%.9g,%.9g\n" % (training_step, mu, nu, sigma))
+
     # ---- n-step returns (Config.DDPG_NSTEP, DESIGN.md 8o) ------------------------------------------------
     def nstep_create(self, n):
         """Attaches n-step state to a handle that has none (Config.DDPG_NSTEP = 1) and no device actors yet."""
@@ -477,3 +505,5 @@ class Network(DeviceActors, NativeHandle):
         with self._log_lock:
             with open("logs/%s/scalars.csv" % self.model_name, "a") as f:
                 f.write("%d,%.8g,%.8g,%.8g\n" % (training_step, self.learning_rate, q_max, q_avg))
+        if self.popart:                         # scalars.csv keeps its four columns; Q above is in return units
+            self.log_popart(training_step)

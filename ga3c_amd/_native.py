@@ -228,6 +228,10 @@ HIP_SIGNATURES = {
     # per-environment noise of a DDPG handle's device actors (Config.DEVICE_DDPG_NOISE), include/ga3c_abi.h
     "ga3c_ddpg_envnoise_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "ga3c_ddpg_envnoise_destroy": (C.c_int, [C.c_void_p]),
+    # PopArt on a DDPG handle's critic (Config.DDPG_POPART), include/ga3c_abi.h: ga3c_ddpg_popart_*
+    "ga3c_ddpg_popart_create": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float]),
+    "ga3c_ddpg_popart_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_popart_info": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

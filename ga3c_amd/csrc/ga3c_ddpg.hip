@@ -57,6 +57,12 @@
 // statement):
 //   ddpg_predict_envnoise_kernel  ddpg_predict_kernel's body with every environment's own OU step in its epilogue; launched in
 //                                 its place by an actor step under GA3C_DDPG_NOISE_OWN, which stays predict + 2 launches
+// PopArt (ga3c_ddpg_popart_create, Config.DDPG_POPART; tests/popart_oracle.py is the same statement):
+//   ddpg_popart_kernel   one workgroup between the target and the critic kernel: the f64 sums of y and y^2 in a fixed order, the
+//                        new statistics mu, nu (f32 in both arenas, behind the 26 variables), critic_output/W and /b of both
+//                        arenas rescaled so that sigma n + mu stays what it was, and yn = (y - mu') / sigma' for the critic step
+// The target kernel de-normalises the target critic's output with the statistics it finds; every other kernel runs as it did, on
+// yn where y was.  A popart step is 6 launches (7 with clipping, + 3 prioritised).
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -325,6 +331,19 @@ __device__ __forceinline__ float row_discount(const float* __restrict__ disc, fl
   return g;
 }
 
+// The statistics of a handle with PopArt as the target kernel reads them; stat null: a handle without, whose
+// critic's output is the return itself.
+struct PopStats {
+  const float* stat;         // {mu, nu}, f32, behind the 26 variables of the value arena
+  double smin, smax;
+};
+
+// sigma = clamp(sqrt(max(nu - mu^2, 0)), smin, smax) in f64 from the stored f32 values (mu^2 is exact in f64)
+__device__ __forceinline__ double popart_sigma(float mu, float nu, double smin, double smax) {
+  const double m = (double)mu;
+  return fmin(fmax(sqrt(fmax((double)nu - m * m, 0.0)), smin), smax);
+}
+
 // What the target step writes and, with two critics, what its smoothing draws from.
 template <int NC>
 struct Target { float *y, *qt; };
@@ -339,10 +358,13 @@ struct Target<2> {
 // NC = 2: the target action of row k = row0 + r, action i is a~ = clip(actor_target(s2) + eps, -1, 1),
 // eps = (f32) clip(sigma n, -c, c), n Box-Muller in f64 on uniforms 2j and 2j + 1 of stream `number`, j = k A + i.  Both target
 // critics read a~ from `act`, one after the other in the same buffers.
+// ps (NC = 1, stat not null: a handle with PopArt): the target critic's output n' is a normalised value and
+// q' = fmaf((f32) sigma, n', mu) with the statistics as they stand; "qt" and y are in return units.
 template <int NC>
 __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(PerCritic<Layout, NC> L, const float* __restrict__ thT, Rows src, int B,
                                                               float gamma, int future, Target<NC> t,
-                                                              const float* __restrict__ disc, float* __restrict__ used) {
+                                                              const float* __restrict__ disc, float* __restrict__ used,
+                                                              PopStats ps) {
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
@@ -384,6 +406,12 @@ __global__ __launch_bounds__(THREADS) void ddpg_target_kernel(PerCritic<Layout, 
     for (int c = 0; c < NC; ++c) q[c] = future ? qv[c][r] : 0.f;
     float qt = q[0];
     if constexpr (NC == 2) qt = fminf(q[0], q[1]);
+    if constexpr (NC == 1) {
+      if (ps.stat) {
+        const float mu = ps.stat[0];
+        qt = fmaf((float)popart_sigma(mu, ps.stat[1], ps.smin, ps.smax), qt, mu);
+      }
+    }
     float y = rew;
     if (future && done == 0.f) y = fmaf(g, qt, rew);
     t.y[row0 + r] = y;
@@ -462,6 +490,74 @@ __global__ __launch_bounds__(THREADS) void ddpg_critic_kernel(PerCritic<Layout, 
                                                               int paired, const float* __restrict__ per_w, Work w) {
   const int c = NC == 1 ? 0 : blockIdx.y;
   critic_step(L.v[c], th, src, B, paired, per_w, w.y, c ? nullptr : w.c_x, c ? nullptr : w.c_a, w.c[c]);
+}
+
+// ------------------------------------------------------------------ PopArt
+struct PopArt {
+  float *stat, *stat_t;      // {mu, nu} in the value arena and in the target arena
+  float *wo, *bo;            // critic_output/W [300] and /b of the value arena
+  float *wo_t, *bo_t;        // ... of the target arena
+  const float* y;            // [B] the step's targets, return units
+  float* yn;                 // [B] <- (y - mu') / sigma'
+  float* out;                // {(f32) mu', (f32) sigma'} for the step's returned stats
+  double beta, smin, smax;
+};
+
+// One workgroup, between ddpg_target_kernel and ddpg_critic_kernel.  Thread t sums y_i and y_i^2 in f64 over i = t, t + 448, ...
+// in that order and the partials fold by block_sum's tree (512 leaves).  Thread 0 then moves the statistics,
+// mu' = (1 - beta) mu + beta mean(y) and nu' likewise on mean(y^2) in f64, each rounded to f32 and stored in both arenas, takes
+// sigma' from the STORED values, and forms ratio = (f32)(sigma / sigma'), shift = (f32)((mu - mu') / sigma'), muf' = mu' and
+// isig' = (f32)(1 / sigma').  All threads: W <- W ratio and b <- fmaf(b, ratio, shift) for critic_output of both arenas, so that
+// sigma' n + mu' is what sigma n + mu was, and yn_i = (y_i - muf') isig'.  With beta = 0 on fresh statistics every factor is
+// exactly 1 or 0.  No slot and no gradient is touched.
+__global__ __launch_bounds__(THREADS) void ddpg_popart_kernel(PopArt p, int B) {
+#pragma clang fp contract(off)
+  __shared__ double red[2][RED];
+  __shared__ float k[4];
+  const int t = threadIdx.x;
+  double s1 = 0.0, s2 = 0.0;
+  for (int i = t; i < B; i += THREADS) {
+    const double v = (double)p.y[i];
+    s1 += v;
+    s2 += v * v;
+  }
+  red[0][t] = s1;
+  red[1][t] = s2;
+  if (t + THREADS < RED) red[0][t + THREADS] = red[1][t + THREADS] = 0.0;
+  __syncthreads();
+  for (int h = RED / 2; h > 0; h >>= 1) {
+    if (t < h) {
+      red[0][t] += red[0][t + h];
+      red[1][t] += red[1][t + h];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const float mu = p.stat[0], nu = p.stat[1];
+    const double sigma = popart_sigma(mu, nu, p.smin, p.smax);
+    const float mu1 = (float)((1.0 - p.beta) * (double)mu + p.beta * (red[0][0] / (double)B));
+    const float nu1 = (float)((1.0 - p.beta) * (double)nu + p.beta * (red[1][0] / (double)B));
+    const double sigma1 = popart_sigma(mu1, nu1, p.smin, p.smax);
+    p.stat[0] = p.stat_t[0] = mu1;
+    p.stat[1] = p.stat_t[1] = nu1;
+    k[0] = (float)(sigma / sigma1);
+    k[1] = (float)(((double)mu - (double)mu1) / sigma1);
+    k[2] = mu1;
+    k[3] = (float)(1.0 / sigma1);
+    p.out[0] = mu1;
+    p.out[1] = (float)sigma1;
+  }
+  __syncthreads();
+  const float ratio = k[0], shift = k[1], muf = k[2], isig = k[3];
+  for (int j = t; j < H2; j += THREADS) {
+    p.wo[j] = p.wo[j] * ratio;
+    p.wo_t[j] = p.wo_t[j] * ratio;
+  }
+  if (t == 0) {
+    p.bo[0] = fmaf(p.bo[0], ratio, shift);
+    p.bo_t[0] = fmaf(p.bo_t[0], ratio, shift);
+  }
+  for (int i = t; i < B; i += THREADS) p.yn[i] = (p.y[i] - muf) * isig;
 }
 
 // ------------------------------------------------------------------ distributional critic
@@ -1392,6 +1488,12 @@ struct Dist {
   float* work_base = nullptr;           // the rows of the handle's DistRows
 };
 
+// PopArt of a handle (ga3c_ddpg_popart_create).  The arenas hold two floats behind the 26 variables while it lives: mu, nu.
+struct Pop {
+  float beta = 0.f, smin = 0.f, smax = 0.f;
+  float* work_base = nullptr;           // the row "yn" of the handle's work table
+};
+
 // Evaluation episodes of a handle (ga3c_ddpg_eval_create).  block: the device buffers below; h_counts: the n f64 totals of the
 // last run, pinned.  Read and written under train_mu.
 struct Eval : ga3c_actors::ActorsCore {
@@ -1430,7 +1532,9 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   NStep* nstep = nullptr;         // null: one-step rows, the scalar gamma everywhere
   Dist* dist = nullptr;           // null: the scalar critic
   Eval* eval = nullptr;           // null: no evaluation episodes
-  DistRows dw{};                  // its rows, null without
+  Pop* pop = nullptr;             // null: the critic's output is the return itself
+  float* yn = nullptr;            // [B] its normalised targets, null without
+  DistRows dw{};                  // the distributional critic's rows, null without
   std::vector<std::string> tnames;      // the target copies' names, by variable
 };
 
@@ -1439,9 +1543,10 @@ namespace {
 int tiles(int B) { return (B + TILE - 1) / TILE; }
 
 // The rows of the train workspace by the name ga3c_ddpg_fetch knows them under.  tag: W_TWIN rows exist while the handle has twin
-// critics, W_DIST rows while it has a distributional critic, each kind in a block of its own (Twin::work_base, Dist::work_base);
+// critics, W_DIST rows while it has a distributional critic, W_POP rows while it has PopArt, each kind in a block of its own
+// (Twin::work_base, Dist::work_base, Pop::work_base);
 // the others live as long as the handle (work_base).
-enum WorkTag { W_CORE, W_TWIN, W_DIST };
+enum WorkTag { W_CORE, W_TWIN, W_DIST, W_POP };
 struct WorkRow {
   const char* name;
   float** ptr;
@@ -1465,7 +1570,7 @@ std::vector<WorkRow> work_table(ga3c_ddpg* m) {
           {"t_eps", &w.t_eps, A, W_TWIN},    {"t_a", &w.t_a, A, W_TWIN},        {"c2_xh1", &d.xh1, H1, W_TWIN},    {"c2_c1", &d.c1, H1, W_TWIN},
           {"c2_dn1", &d.dn1, H1, W_TWIN},    {"c2_dh1", &d.dh1, H1, W_TWIN},    {"c2_c2", &d.c2, H2, W_TWIN},      {"c2_dt", &d.dt, H2, W_TWIN},
           {"d_pt", &z.pt, N, W_DIST},      {"d_m", &z.m, N, W_DIST},        {"d_p", &z.p, N, W_DIST},        {"d_dz", &z.dz, N, W_DIST},
-          {"d_ce", &z.ce, 1, W_DIST}};
+          {"d_ce", &z.ce, 1, W_DIST},      {"yn", &m->yn, 1, W_POP}};
 }
 
 // One zeroed block for the table's rows of one tag; *end: the four floats behind them.
@@ -1596,9 +1701,23 @@ int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise
     hipLaunchKernelGGL(ddpg_dist_critic_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, per_w, ds->z, w,
                        m->dw);
   } else {
+    // PopArt: the targets are de-normalised with the statistics as they stand, the one-workgroup kernel moves
+    // them, rescales both output layers and leaves yn, and the critic step runs on yn where y was
+    const Pop* pp = NC == 1 ? m->pop : nullptr;
+    float* stat = pp ? m->arena[0] + m->L.off[NVARS] : nullptr;
     hipLaunchKernelGGL(ddpg_target_kernel<NC>, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma, future, tg,
-                       row_discounts(m, rows), used);
-    hipLaunchKernelGGL(ddpg_critic_kernel<NC>, gridc, block, 0, m->st, L, (const float*)m->arena[0], rows, B, paired, per_w, w);
+                       row_discounts(m, rows), used, PopStats{stat, pp ? (double)pp->smin : 0.0, pp ? (double)pp->smax : 0.0});
+    Work wc = w;
+    if (pp) {
+      float *a0 = m->arena[0], *a1 = m->arena[1];
+      const Layout& K = m->L;
+      hipLaunchKernelGGL(ddpg_popart_kernel, dim3(1), block, 0, m->st,
+                         PopArt{stat, a1 + K.off[NVARS], a0 + K.off[C_WO], a0 + K.off[C_BO], a1 + K.off[C_WO], a1 + K.off[C_BO],
+                                (const float*)w.y, m->yn, w.qstat + 2, (double)pp->beta, (double)pp->smin, (double)pp->smax},
+                         B);
+      wc.y = m->yn;
+    }
+    hipLaunchKernelGGL(ddpg_critic_kernel<NC>, gridc, block, 0, m->st, L, (const float*)m->arena[0], rows, B, paired, per_w, wc);
   }
   const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
   const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
@@ -1624,10 +1743,25 @@ int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& n
   return m->twin ? enqueue_step_nc<2>(m, rows, B, lr, nz, stop_after, per_w) : enqueue_step_nc<1>(m, rows, B, lr, nz, stop_after, per_w);
 }
 
+// {max q, mean q} of the last step enqueued, on their way to the host; with PopArt {mu', sigma'} come behind them in the same copy.
+int copy_qstats(ga3c_ddpg* m) {
+  HIPCHK(hipMemcpyAsync(m->h_q, m->w.qstat, (m->pop ? 4 : 2) * sizeof(float), hipMemcpyDeviceToHost, m->st));
+  return GA3C_OK;
+}
+
 int finish_step(ga3c_ddpg* m) {
-  HIPCHK(hipMemcpyAsync(m->h_q, m->w.qstat, 2 * sizeof(float), hipMemcpyDeviceToHost, m->st));
+  CHK(copy_qstats(m));
   HIPCHK(hipEventRecord(m->tev, m->st));
   return GA3C_OK;
+}
+
+// ... and, after the wait, to the caller (caller holds train_mu).  With PopArt the critic's output is normalised and the stats
+// go out in return units: sigma' max(n) + mu' and sigma' mean(n) + mu'.
+void give_qstats(const ga3c_ddpg* m, float* q_stats) {
+  if (!q_stats) return;
+  memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  if (m->pop)
+    for (int i = 0; i < 2; ++i) q_stats[i] = fmaf(m->h_q[3], m->h_q[i], m->h_q[2]);
 }
 
 // n rows in ring layout, s | a | r | done | s2, into `dst` (the one place)
@@ -1663,7 +1797,7 @@ int step_host(ga3c_ddpg* m, const float* s, const float* a, const float* r, cons
     m->last_B = B;
   }
   HIPCHK(hipEventSynchronize(m->tev));
-  if (q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  give_qstats(m, q_stats);
   if (stop_after >= 6) m->step.fetch_add(1);
   return GA3C_OK;
 }
@@ -1723,8 +1857,23 @@ void fill_vars(ga3c_ddpg* m) {
   m->n = m->L.off[NVARS];
 }
 
-// variable i of a twin handle's table is trainable: the 20, and critic 2's ten
-bool trainable_var(int i) { return i >= 0 && (i < NTRAIN || (i >= NVARS && i < NVARS + NCRITIC)); }
+// variable i of the handle's table is trainable: the 20, and critic 2's ten of a twin handle (PopArt's two are not)
+bool trainable_var(const ga3c_ddpg* m, int i) { return i >= 0 && (i < NTRAIN || (m->twin && i >= NVARS && i < NVARS + NCRITIC)); }
+
+const char* const POP_VAR_NAMES[2] = {"critic_popart/mu", "critic_popart/nu"};
+
+void pop_free(ga3c_ddpg* m) {
+  Pop* p = m->pop;
+  if (!p) return;
+  (void)hipFree(p->work_base);
+  (void)hipGetLastError();
+  m->yn = nullptr;
+  delete p;
+  m->pop = nullptr;
+  m->vars.resize(NVARS);            // the arenas keep their size: nothing names what lies behind the 26
+  m->tnames.resize(NVARS);
+  m->n = m->L.off[NVARS];
+}
 
 void twin_free(ga3c_ddpg* m) {
   Twin* t = m->twin;
@@ -1828,6 +1977,7 @@ void free_all(ga3c_ddpg* m) {
   eval_free(m);
   per_free(m);
   twin_free(m);
+  pop_free(m);
   nstep_free(m);
   dist_free(m);
   vn::free_core(m);
@@ -1919,8 +2069,9 @@ int per_enqueue_step(ga3c_ddpg* m, int B, float beta, float lr, const Noise& nz)
   Per* p = m->per;
   per_enqueue_sample(m, B, beta);
   CHK(enqueue_step(m, Rows{m->ring, p->slots, m->rowf}, B, lr, nz, 6, p->w));
+  // (with PopArt the critic's q is normalised and so is the target it met: |yn - n|, a TD error free of the returns' scale)
   hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(PER_THREADS), 0, m->st, (const int32_t*)p->slots, (const float*)m->w.c[0].q,
-                     (const float*)m->w.y, B, p->eps, p->alpha, p->pa, p->max_pa, p->td);
+                     (const float*)(m->pop ? m->yn : m->w.y), B, p->eps, p->alpha, p->pa, p->max_pa, p->td);
   HIPCHK(hipGetLastError());
   p->td_rows = B;
   return GA3C_OK;
@@ -2017,7 +2168,7 @@ const char* ga3c_ddpg_target_name(ga3c_ddpg* m, int32_t index) {
 
 int ga3c_ddpg_param_info(ga3c_ddpg* m, const char* name, int64_t* count, int32_t* ndim, int64_t shape[4], int32_t* trainable) {
   CHK(vn::param_info(m, name, nullptr, count, ndim, shape));
-  if (trainable) *trainable = trainable_var(ga3c_ckpt::find_var(m->vars, name)) ? 1 : 0;
+  if (trainable) *trainable = trainable_var(m, ga3c_ckpt::find_var(m->vars, name)) ? 1 : 0;
   return GA3C_OK;
 }
 
@@ -2066,6 +2217,8 @@ int ga3c_ddpg_load(ga3c_ddpg* m, const char* path) {
   if (step < 0) return fail(GA3C_ESTATE, "%s: step %lld", path, (long long)step);      // before anything is written
   if (!m->twin && members.count(std::string(TWIN_VAR_NAMES[0]) + ":0"))
     return fail(GA3C_ESTATE, "%s holds %s: the checkpoint of a handle with twin critics, which this one has not", path, TWIN_VAR_NAMES[0]);
+  if (!m->pop && members.count(std::string(POP_VAR_NAMES[0]) + ":0"))
+    return fail(GA3C_ESTATE, "%s holds %s: the checkpoint of a handle with PopArt, which this one has not", path, POP_VAR_NAMES[0]);
   const auto sup = members.find("dist_support");
   if (!m->dist && sup != members.end())
     return fail(GA3C_ESTATE, "%s holds dist_support: the checkpoint of a handle with a distributional critic, which this one has not", path);
@@ -2258,7 +2411,7 @@ int ga3c_ddpg_train_replay(ga3c_ddpg* m, const int32_t* slots, int32_t batch, in
     m->last_B = batch;
   }
   HIPCHK(hipEventSynchronize(m->tev));
-  if (q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  give_qstats(m, q_stats);
   m->step.fetch_add(1);
   return GA3C_OK;
 }
@@ -2296,6 +2449,7 @@ int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
     if (r.tag == W_TWIN && !m->twin) return fail(GA3C_ESTATE, "%s: the handle has no twin critics (ga3c_ddpg_twin_create)", name);
     if (r.tag == W_DIST && !m->dist)
       return fail(GA3C_ESTATE, "%s: the handle has no distributional critic (ga3c_ddpg_dist_create)", name);
+    if (r.tag == W_POP && !m->pop) return fail(GA3C_ESTATE, "%s: the handle has no PopArt (ga3c_ddpg_popart_create)", name);
     const int64_t want = (int64_t)r.width * m->last_B;
     if (count != want) return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)want, (long long)count);
     HIPCHK(hipStreamSynchronize(m->st));
@@ -2462,7 +2616,7 @@ int ga3c_ddpg_train_prioritized(ga3c_ddpg* m, int32_t batch, float beta_is, floa
     m->last_B = batch;
   }
   HIPCHK(hipEventSynchronize(m->tev));
-  if (q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  give_qstats(m, q_stats);
   if (out_slots) memcpy(out_slots, m->per->h_slots, sizeof(int32_t) * batch);
   m->step.fetch_add(1);
   return GA3C_OK;
@@ -2506,6 +2660,7 @@ int ga3c_ddpg_twin_create(ga3c_ddpg* m, int32_t policy_delay, float target_sigma
   std::lock_guard<std::mutex> lk(m->mu);
   if (m->twin) return fail(GA3C_ESTATE, "the handle has twin critics already");
   if (m->dist) return fail(GA3C_ESTATE, "the handle has a distributional critic: two distributions have no smaller one");
+  if (m->pop) return fail(GA3C_ESTATE, "the handle has PopArt, which normalises one scalar critic (ga3c_ddpg_popart_destroy first)");
   Twin* t = new (std::nothrow) Twin();
   if (!t) return fail(GA3C_EINVAL, "out of host memory");
   t->delay = policy_delay;
@@ -2582,6 +2737,7 @@ int ga3c_ddpg_dist_create(ga3c_ddpg* m, int32_t atoms, float vmin, float vmax) {
   std::lock_guard<std::mutex> lk(m->mu);
   if (m->dist) return fail(GA3C_ESTATE, "the handle has a distributional critic already");
   if (m->twin) return fail(GA3C_ESTATE, "the handle has twin critics: two distributions have no smaller one");
+  if (m->pop) return fail(GA3C_ESTATE, "the handle has PopArt, which normalises one scalar critic (ga3c_ddpg_popart_destroy first)");
   Dist* d = new (std::nothrow) Dist();
   if (!d) return fail(GA3C_EINVAL, "out of host memory");
   d->z = Support{atoms, vmin, vmax, delta};
@@ -2610,6 +2766,96 @@ int ga3c_ddpg_dist_info(ga3c_ddpg* m, int32_t* atoms, float* vmin, float* vmax) 
   if (atoms) *atoms = m->dist ? m->dist->z.n : 1;
   if (vmin) *vmin = m->dist ? m->dist->z.vmin : 0.f;
   if (vmax) *vmax = m->dist ? m->dist->z.vmax : 0.f;
+  return GA3C_OK;
+}
+
+// ---- PopArt
+
+int ga3c_ddpg_popart_create(ga3c_ddpg* m, float beta, float sigma_min, float sigma_max) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (!(beta >= 0.f && beta <= 1.f)) return fail(GA3C_EINVAL, "beta %g outside [0,1]", beta);
+  if (!std::isfinite(sigma_min) || !std::isfinite(sigma_max) || !(sigma_min > 0.f) || !(sigma_min < sigma_max))
+    return fail(GA3C_EINVAL, "sigma bounds [%g, %g]: two finite numbers, 0 < the first < the second", sigma_min, sigma_max);
+  if (!(m->cfg.flags & GA3C_DDPG_LOSS_PAIRED))
+    return fail(GA3C_ESTATE, "PopArt needs GA3C_DDPG_LOSS_PAIRED: under the fork's loss the critic regresses on mean(y) and a row "
+                             "has no target of its own to normalise");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (m->pop) return fail(GA3C_ESTATE, "the handle has PopArt already");
+  if (m->twin) return fail(GA3C_ESTATE, "the handle has twin critics: PopArt normalises one scalar critic");
+  if (m->dist) return fail(GA3C_ESTATE, "the handle has a distributional critic: its support fixes the returns' scale");
+  Pop* p = new (std::nothrow) Pop();
+  if (!p) return fail(GA3C_EINVAL, "out of host memory");
+  p->beta = beta;
+  p->smin = sigma_min;
+  p->smax = sigma_max;
+  const int64_t n0 = m->L.off[NVARS], n1 = n0 + 2;
+  // Every arena grows by the two statistics: mu = 0, nu = 1 in the value and the target arena, zero elsewhere.  The 26 keep
+  // their values; a prediction in flight has finished before its arena is freed.
+  float* grown[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  m->pop = p;
+  auto build = [&]() -> int {
+    HIPCHK(hipStreamSynchronize(m->st));
+    for (int a = 0; a < m->narena; ++a) {
+      CHK(vn::dalloc(&grown[a], (size_t)n1));
+      HIPCHK(hipMemcpy(grown[a], m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToDevice));
+      const float init[2] = {0.f, a <= 1 ? 1.f : 0.f};
+      HIPCHK(hipMemcpy(grown[a] + n0, init, sizeof init, hipMemcpyHostToDevice));
+    }
+    float* end = nullptr;
+    CHK(carve_work(m, W_POP, &p->work_base, &end));
+    return GA3C_OK;
+  };
+  const int rc = build();
+  if (rc != GA3C_OK) {
+    for (float* g : grown) (void)hipFree(g);
+    (void)hipGetLastError();
+    pop_free(m);
+    return rc;
+  }
+  for (int a = 0; a < m->narena; ++a) {
+    (void)hipFree(m->arena[a]);
+    m->arena[a] = grown[a];
+  }
+  for (int i = 0; i < 2; ++i) {      // f32 (1,), not trainable: value and target copy in the checkpoint, no slots
+    const std::string name(POP_VAR_NAMES[i]);
+    vn::Var var{name, n0 + i, 1, 1, {1, 0}, {}};
+    var.ckpt = {{name + ":0", 0}, {target_name(name) + ":0", 1}};
+    m->vars.push_back(std::move(var));
+    m->tnames.push_back(target_name(name));
+  }
+  m->n = n1;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_popart_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!m->pop) return fail(GA3C_ESTATE, "the handle has no PopArt (ga3c_ddpg_popart_create)");
+  HIPCHK(hipStreamSynchronize(m->st));
+  pop_free(m);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_popart_info(ga3c_ddpg* m, float* beta, float* mu, float* nu, float* sigma) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!m->pop) return fail(GA3C_ESTATE, "the handle has no PopArt (ga3c_ddpg_popart_create)");
+  float stat[2];
+  HIPCHK(hipStreamSynchronize(m->st));
+  HIPCHK(hipMemcpy(stat, m->arena[0] + m->L.off[NVARS], sizeof stat, hipMemcpyDeviceToHost));
+  if (beta) *beta = m->pop->beta;
+  if (mu) *mu = stat[0];
+  if (nu) *nu = stat[1];
+  if (sigma) {     // the kernels' expression, on the host
+    const double v = std::sqrt(std::fmax((double)stat[1] - (double)stat[0] * (double)stat[0], 0.0));
+    *sigma = (float)std::fmin(std::fmax(v, (double)m->pop->smin), (double)m->pop->smax);
+  }
   return GA3C_OK;
 }
 
@@ -2814,12 +3060,12 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
   }
   {
     std::lock_guard<std::mutex> lk(m->mu);
-    if (calls) HIPCHK(hipMemcpyAsync(m->h_q, m->w.qstat, 2 * sizeof(float), hipMemcpyDeviceToHost, m->st));
+    if (calls) CHK(copy_qstats(m));
     HIPCHK(hipMemcpyAsync(a->h_counts, d.ep.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipEventRecord(m->tev, m->st));
   }
   HIPCHK(hipEventSynchronize(m->tev));
-  if (calls && q_stats) memcpy(q_stats, m->h_q, 2 * sizeof(float));
+  if (calls) give_qstats(m, q_stats);
   int64_t ne = 0;
   {
     std::lock_guard<std::mutex> lk(m->mu);

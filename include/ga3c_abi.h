@@ -870,6 +870,43 @@ int ga3c_ddpg_eval_set(ga3c_ddpg* net, const char* name, const void* in, int64_t
 int ga3c_ddpg_envnoise_create(ga3c_ddpg* net, int64_t seed, int32_t reset_on_done);
 int ga3c_ddpg_envnoise_destroy(ga3c_ddpg* net);
 
+/* ---- PopArt on a DDPG handle's critic (Config.DDPG_POPART; tests/popart_oracle.py is the same statement in
+ * numpy): adaptive normalisation of the critic's targets that preserves its outputs (van Hasselt et al. 2016).  Attached to a
+ * created handle by a call of its own, as the twin critics are; a handle without it runs what it ran before, bit for bit.
+ * The handle then has 28 variables: the 26, then critic_popart/mu and critic_popart/nu, f32 (1,), not trainable, 0 and 1 at
+ * create: the running first and second moment of the targets.  Every `which` serves them (the slots and the gradient stay zero),
+ * the kernels read the value copy and write the same value to the target copy, and a checkpoint holds both copies.
+ * sigma = clamp(sqrt(max(nu - mu^2, 0)), sigma_min, sigma_max) in f64 from the stored f32 values.  The critic's output n is a
+ * normalised value; the return it stands for is sigma n + mu.  Every train-type call (train, train_replay, train_prioritized,
+ * compute, time_resident, time_prioritized, actors_run) then runs, with (mu, nu, sigma) the state before it:
+ *   targets  q' = fmaf((f32) sigma, n', mu), n' the target critic's output; y = r on a done row or without
+ *            GA3C_DDPG_FUTURE_REWARD, else fmaf(g, q', r) with the row's discount g as before.  "y" and "qt" are in return units.
+ *   popart   one workgroup between the target and the critic kernel.  The f64 sums of y and y^2 over the B rows in a fixed
+ *            order (thread t of 448 adds rows t, t + 448, .. in that order; the partials fold by the halving tree over 512 leaves);
+ *            mu' = (f32)((1 - beta) mu + beta mean(y)), nu' = (f32)((1 - beta) nu + beta mean(y^2)) in f64, stored in both
+ *            arenas; sigma' from the STORED mu', nu'; ratio = (f32)(sigma / sigma'), shift = (f32)((mu - mu') / sigma'),
+ *            isig' = (f32)(1 / sigma'); critic_output/W <- W ratio and /b <- fmaf(b, ratio, shift) in the value arena and in the
+ *            target arena (no slot, no gradient), so that sigma' n + mu' is what sigma n + mu was; "yn" = (y - mu') isig'.
+ *   critic   step 3 as before with yn where y was: "q" and "dq" are normalised, the clip and both optimizers are unchanged.
+ *   actor    steps 4-5 as before: the actor ascends the normalised value and "g" is dn/da.
+ *   soft update as before; both output layers were rescaled alike.
+ *   priorities  "per_td" = |yn - n| and pa[slot] = (|yn - n| + eps)^alpha: TD errors free of the returns' scale.
+ *   q_stats  in return units: sigma' max(n) + mu' and sigma' mean(n) + mu', mu' and (f32) sigma' coming back in the step's one
+ *            copy and one wait.
+ * With beta = 0 on fresh statistics every factor is exactly 1 or 0 and the step is the plain paired step's, bit for bit.
+ * 6 launches (7 with GA3C_DDPG_GRAD_CLIP, + 3 prioritised).  Priorities, n-step returns, device actors and evaluation episodes
+ * combine with it; prediction and evaluation read the actor alone.  fetch also knows "yn" [B] (GA3C_ESTATE without the feature).
+ * mu and nu are read and set through ga3c_ddpg_get_param / _set_param by name.  A handle with PopArt loads only such a handle's
+ * file and a plain handle refuses one (GA3C_ESTATE, handle untouched).
+ * create: GA3C_EINVAL for beta outside [0,1], sigma_min <= 0, sigma_min >= sigma_max, a NaN or an infinity; GA3C_ESTATE on a
+ * second create, on a handle without GA3C_DDPG_LOSS_PAIRED (under the fork's loss a row has no target of its own) and on one with
+ * twin critics or a distributional critic, as twin_create and dist_create are on a handle with PopArt.
+ * destroy: also done by ga3c_ddpg_destroy; the handle has its 26 variables again.
+ * info: the value copy's mu and nu and the sigma they give; each pointer may be NULL; GA3C_ESTATE without the feature. */
+int ga3c_ddpg_popart_create(ga3c_ddpg* net, float beta, float sigma_min, float sigma_max);
+int ga3c_ddpg_popart_destroy(ga3c_ddpg* net);
+int ga3c_ddpg_popart_info(ga3c_ddpg* net, float* beta, float* mu, float* nu, float* sigma);
+
 #ifdef __cplusplus
 }
 #endif

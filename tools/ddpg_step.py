@@ -6,8 +6,10 @@ predict 1, train_replay 5 (6 with USE_GRAD_CLIP).  --twin: the handle has twin c
 is not a policy step is 3 launches (4), so the time is the mean over --delay steps; --delay 1 times the policy step.
 --nstep N > 1: the handle has n-step state (DDPG_NSTEP) and the target kernel reads a discount per ring slot.
 --dist: the handle has a distributional critic (DDPG_DISTRIBUTIONAL) of --atoms atoms; the launches are the same.
+KEY=VALUE: the product's own settings, applied after the flags and checked by the product's resolvers, e.g. DDPG_CRITIC_LOSS=paired
+or DDPG_CRITIC_LOSS=paired DDPG_POPART=True (one more launch, a single workgroup).
 usage: python tools/ddpg_step.py [--predict 1 128] [--train 64 128 256] [--rounds 5] [--iters 200] [--clip] [--twin [--delay N]]
-       [--nstep N] [--dist [--atoms N]]"""
+       [--nstep N] [--dist [--atoms N]] [KEY=VALUE ...]"""
 import argparse
 import json
 import os
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--nstep", type=int, default=1)
     ap.add_argument("--dist", action="store_true")
     ap.add_argument("--atoms", type=int, default=51)
+    ap.add_argument("settings", nargs="*", help="KEY=VALUE, as GA3C.py takes them")
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
@@ -45,6 +48,11 @@ def main():
         Config.DDPG_DISTRIBUTIONAL, Config.DDPG_CRITIC_LOSS, Config.DDPG_ATOMS = True, 'paired', args.atoms
     S, A = args.state_dim, args.actions
     maxB = max(args.predict + args.train)
+    if args.settings:
+        import GA3C
+        Config.GAME, Config.USE_DDPG, Config.TRAINING_MIN_BATCH_SIZE = 'Pendulum-v0', True, maxB
+        GA3C.apply_argv(args.settings)
+    popart = bool(getattr(Config, "DDPG_POPART", False))
     net = Network("gpu:0", "ddpg_step", A, (S,), max_batch=maxB, replay_capacity=max(maxB, 1024))
     rng = np.random.Generator(np.random.PCG64(1))
     net.replay_add(rng.uniform(-1, 1, (maxB, S)), rng.uniform(-1, 1, (maxB, A)), rng.uniform(-1, 0, maxB),
@@ -60,7 +68,8 @@ def main():
     for (mode, b), v in res.items():
         v = sorted(v)
         print(json.dumps({"step": "train_replay" if mode else "predict", "rows": b, "state_dim": S, "actions": A,
-                          "grad_clip": bool(args.clip), "launches": (6 if args.clip else 5) if mode else 1,
+                          "grad_clip": bool(args.clip), "launches": (6 if args.clip else 5) + popart if mode else 1,
+                          "critic_loss": Config.DDPG_CRITIC_LOSS, "popart": popart,
                           "nstep": args.nstep, "twin": bool(args.twin), "policy_delay": args.delay if args.twin else None,
                           "launches_off_policy_step": ((4 if args.clip else 3) if mode else 1) if args.twin else None,
                           "atoms": args.atoms if args.dist else None,
