@@ -4,6 +4,7 @@ Config (/root/reference/ga3c/Config.py:27-202) and overridable from argv as KEY=
 fixes for the 84x84x4 Atari path (the fork's own defaults target Pendulum), and the block at the
 end adds the knobs this engine needs (devices, transport, return mode).
 """
+import math
 import os
 
 
@@ -192,6 +193,19 @@ class Config:
                                         # Ornstein-Uhlenbeck process of its own, as the reference's predicting processes had,
                                         # stepped inside the predict kernel
     DEVICE_DDPG_NOISE_RESET = False     # True: under 'per_env' an environment's process restarts at 0 when its episode ends
+    # What "Pendulum-v0" means to the DEVICE_DDPG actors and evaluation episodes, option by option.  The defaults are the
+    # fork's wrapper, EnvironmentPend.Environment, which the agent processes keep whatever these say; gym's own task is
+    # ACTION_BOUND=clip TIME_LIMIT=truncate RESET_OBSERVATION=True REWARD_SCALE=1 REWARD_OFFSET=0.
+    DEVICE_DDPG_ACTION_BOUND = 'wrap'   # 'wrap': an action beyond [-1, 1] turns around, 1.1 -> -0.9 (check_bounds with turnaround);
+                                        # 'clip': it stops at the bound.  The ring keeps the action as predicted either way
+    DEVICE_DDPG_TIME_LIMIT = 'terminal'     # 'terminal': the transition that reaches step 200 is done, y = r; 'truncate': the episode
+                                        # ends and resets there all the same, but the row's done stays 0 and y bootstraps through
+                                        # the observation before the reset
+    DEVICE_DDPG_RESET_OBSERVATION = False   # True: after a reset the next transition starts from the reset state's observation;
+                                        # False: from the last observation of the episode before, as the fork's wrapper leaves it
+    DEVICE_DDPG_REWARD_SCALE = 0.005    # reward = -cost * DEVICE_DDPG_REWARD_SCALE + DEVICE_DDPG_REWARD_OFFSET (scale finite and > 0,
+    DEVICE_DDPG_REWARD_OFFSET = -1.0    # offset finite).  DDPG_V_MIN / DDPG_V_MAX are fitted to the defaults and are the user's to set
+                                        # for another reward: at (1, 0) the gamma = 0.99 return lies in about [-1650, 0]
 
 
 VECTOR_GAMES = ('Pendulum-v0', 'CartPole-v0')      # games whose state is a vector (Server.py:35-43 of the reference)
@@ -387,6 +401,39 @@ def _resolve_device_ddpg(n, pendulum):
                          "each environment" % (Config.add_OUnoise,))
     if not isinstance(Config.DEVICE_DDPG_NOISE_RESET, bool):
         raise ValueError("DEVICE_DDPG_NOISE_RESET=%r: True or False" % (Config.DEVICE_DDPG_NOISE_RESET,))
+    _resolve_device_ddpg_task()
+
+
+# The five keys of the device actors' task and their defaults: the fork's wrapper.
+DEVICE_DDPG_TASK_DEFAULTS = (("DEVICE_DDPG_ACTION_BOUND", 'wrap'), ("DEVICE_DDPG_TIME_LIMIT", 'terminal'),
+                             ("DEVICE_DDPG_RESET_OBSERVATION", False), ("DEVICE_DDPG_REWARD_SCALE", 0.005),
+                             ("DEVICE_DDPG_REWARD_OFFSET", -1.0))
+
+
+def _finite_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+
+
+def _resolve_device_ddpg_task():
+    if Config.DEVICE_DDPG_ACTION_BOUND not in ('wrap', 'clip'):
+        raise ValueError("DEVICE_DDPG_ACTION_BOUND=%r: 'wrap' or 'clip'" % (Config.DEVICE_DDPG_ACTION_BOUND,))
+    if Config.DEVICE_DDPG_TIME_LIMIT not in ('terminal', 'truncate'):
+        raise ValueError("DEVICE_DDPG_TIME_LIMIT=%r: 'terminal' or 'truncate'" % (Config.DEVICE_DDPG_TIME_LIMIT,))
+    if not isinstance(Config.DEVICE_DDPG_RESET_OBSERVATION, bool):
+        raise ValueError("DEVICE_DDPG_RESET_OBSERVATION=%r: True or False" % (Config.DEVICE_DDPG_RESET_OBSERVATION,))
+    if not _finite_number(Config.DEVICE_DDPG_REWARD_SCALE) or not Config.DEVICE_DDPG_REWARD_SCALE > 0:
+        raise ValueError("DEVICE_DDPG_REWARD_SCALE=%r: a finite number above 0" % (Config.DEVICE_DDPG_REWARD_SCALE,))
+    if not _finite_number(Config.DEVICE_DDPG_REWARD_OFFSET):
+        raise ValueError("DEVICE_DDPG_REWARD_OFFSET=%r: a finite number" % (Config.DEVICE_DDPG_REWARD_OFFSET,))
+
+
+def _refuse_task_without_device_ddpg():
+    """A non-default task key asks for the task of the DDPG handle's device actors."""
+    for key, default in DEVICE_DDPG_TASK_DEFAULTS:
+        value = getattr(Config, key, default)
+        if value != default:                  # the comparison NetworkDDPG makes before it attaches a task
+            raise ValueError("%s=%r needs DEVICE_DDPG (with DEVICE_AGENTS > 0): the task is that of the DDPG actors stepped on "
+                             "the device; the agent processes keep the fork's wrapper" % (key, value))
 
 
 def _refuse_eval_without_device_ddpg():
@@ -406,13 +453,14 @@ def _refuse_env_noise_without_device_ddpg():
 def resolve_device_agents(explicit=()):
     """What DEVICE_AGENTS > 0 cannot be combined with.  Call after resolve_action_space and resolve_ddpg.  With
     DEVICE_AGENTS = 0 nothing is checked and nothing changes, except that DEVICE_DDPG, which asks for them, raises, and so
-    do DEVICE_DDPG_EVAL_ENVS > 0 and DEVICE_DDPG_NOISE = 'per_env', which ask for DEVICE_DDPG."""
+    do DEVICE_DDPG_EVAL_ENVS > 0, DEVICE_DDPG_NOISE = 'per_env' and a non-default key of the task, which ask for DEVICE_DDPG."""
     n = int(Config.DEVICE_AGENTS)
     if n == 0:
         if getattr(Config, "DEVICE_DDPG", False):
             raise ValueError("DEVICE_DDPG needs DEVICE_AGENTS > 0: the number of environments on the device")
         _refuse_eval_without_device_ddpg()
         _refuse_env_noise_without_device_ddpg()
+        _refuse_task_without_device_ddpg()
         return
     if n < 0:
         raise ValueError("DEVICE_AGENTS=%d: 0 (off) or the number of environments on the device" % n)
@@ -422,6 +470,7 @@ def resolve_device_agents(explicit=()):
         return
     _refuse_eval_without_device_ddpg()
     _refuse_env_noise_without_device_ddpg()
+    _refuse_task_without_device_ddpg()
     if Config.USE_DDPG:
         raise ValueError("DEVICE_AGENTS with USE_DDPG is not supported: the device actors step CartPole-v0 only, or "
                          "Pendulum-v0 under the actor-critic network (DEVICE_PENDULUM); under DDPG they need DEVICE_DDPG=True")

@@ -16,6 +16,8 @@ good the actor is right now, with nothing of the training disturbed (Config.DEVI
 Under Config.DEVICE_DDPG_NOISE = 'per_env' every device actor has an Ornstein-Uhlenbeck process of its own, stepped in the predict
 kernel (envnoise_create).  Under Config.DDPG_POPART the critic regresses on normalised targets and the handle has
 two more variables, critic_popart/mu and /nu, the statistics that its output layer is rescaled with (popart_create).
+Under a non-default Config.DEVICE_DDPG_ACTION_BOUND, _TIME_LIMIT, _RESET_OBSERVATION, _REWARD_SCALE or _REWARD_OFFSET the device
+actors and the evaluation episodes step that task in the fork's wrapper's place (task_create).
 """
 import ctypes as C
 import os
@@ -23,7 +25,7 @@ import threading
 
 import numpy as np
 
-from Config import Config
+from Config import Config, DEVICE_DDPG_TASK_DEFAULTS
 from NetworkVP import _device_ordinal
 from NetworkVP_vecnet import DeviceActors, NativeHandle
 import _native as nat
@@ -39,6 +41,18 @@ VALUE, TARGET, SLOT_A, SLOT_B, GRAD = range(5)
 
 
 POPART_STATS = ("critic_popart/mu", "critic_popart/nu")      # of a handle with PopArt: not trainable, behind the 26
+
+# The task of the device actors: (bound, time_limit, reset_observation, reward_scale, reward_offset).  FORK_TASK is
+# EnvironmentPend.Environment's, what a handle without a task steps.
+TASK_BOUNDS = ('wrap', 'clip')
+TASK_TIME_LIMITS = ('terminal', 'truncate')
+FORK_TASK = tuple(default for _, default in DEVICE_DDPG_TASK_DEFAULTS)      # ('wrap', 'terminal', False, 0.005, -1.0)
+
+
+def config_task():
+    """Config's five DEVICE_DDPG task keys as a task tuple; a task is attached when it != FORK_TASK, which is Config's own test
+    of a non-default key (_refuse_task_without_device_ddpg)."""
+    return tuple(getattr(Config, key) for key, _ in DEVICE_DDPG_TASK_DEFAULTS)
 
 
 def param_shapes(state_dim, num_actions, twin=False, atoms=None, popart=False):
@@ -173,6 +187,9 @@ class Network(DeviceActors, NativeHandle):
         self.nstep = int(Config.DDPG_NSTEP)
         if self.nstep > 1:                      # before actors_create, which sizes the environments' windows
             self._call("nstep_create", self.nstep)
+        self.task = None                        # None: the fork's task, and nothing is asked of the library
+        if config_task() != FORK_TASK:          # before actors_create and eval_create, which choose their kernels
+            self.task_create(*config_task())
 
     # ---- variables: which = VALUE, TARGET, SLOT_A, SLOT_B (RMSProp ms / mom or Adam m / v), GRAD -----------------------
     def set_global_step(self, step):
@@ -377,6 +394,28 @@ class Network(DeviceActors, NativeHandle):
             raise ValueError("%d discounts for %d ring slots" % (disc.size, self.replay_capacity))
         self._call("nstep_set", nat.ptr(disc), disc.size)
 
+    # ---- the task (Config.DEVICE_DDPG_ACTION_BOUND .. _REWARD_OFFSET) ----------------------------------
+    def task_create(self, bound, time_limit, reset_observation, reward_scale, reward_offset):
+        """Attaches a task to a handle that has none and neither device actors nor evaluation episodes yet."""
+        if bound not in TASK_BOUNDS:
+            raise ValueError("bound=%r: 'wrap' or 'clip'" % (bound,))
+        if time_limit not in TASK_TIME_LIMITS:
+            raise ValueError("time_limit=%r: 'terminal' or 'truncate'" % (time_limit,))
+        self._call("task_create", TASK_BOUNDS.index(bound), TASK_TIME_LIMITS.index(time_limit), int(bool(reset_observation)),
+                   float(reward_scale), float(reward_offset))
+        self.task = self.task_info()
+
+    def task_info(self):
+        """-> (bound, time_limit, reset_observation, reward_scale, reward_offset) as the handle holds them."""
+        bound, limit, reset = C.c_int32(), C.c_int32(), C.c_int32()
+        scale, offset = C.c_double(), C.c_double()
+        self._call("task_info", C.byref(bound), C.byref(limit), C.byref(reset), C.byref(scale), C.byref(offset))
+        return TASK_BOUNDS[bound.value], TASK_TIME_LIMITS[limit.value], bool(reset.value), scale.value, offset.value
+
+    def task_destroy(self):
+        self._call("task_destroy")
+        self.task = None
+
     # ---- device actors (Config.DEVICE_DDPG, DESIGN.md 8l) ------------------------------------------------
     # what ga3c_ddpg_actors_get names (NetworkVP_vecnet.DeviceActors); "slots" has one row per row of a train step
     ACTOR_FIELDS = {"phys": (np.float64, 2), "elapsed": (np.int32, 1), "draws": (np.uint64, 1), "obs": (np.float32, 3),
@@ -474,14 +513,16 @@ class Network(DeviceActors, NativeHandle):
 
     def log_eval(self, training_step, totals, steps):
         """training_step, n, steps, mean, min, max, mean_gym_return appended to logs/<model>/eval.csv.  The last undoes the
-        wrapper's r * 0.005 - 1 per step: the return gym's Pendulum-v0 would report for the same episode."""
+        reward's scale and offset per step (the wrapper's r * 0.005 - 1 without a task): the return gym's Pendulum-v0 would
+        report for the same episode."""
         totals = np.asarray(totals, np.float64)
         mean = float(totals.mean())
+        scale, offset = (getattr(self, "task", None) or FORK_TASK)[3:]
         os.makedirs("logs/%s" % self.model_name, exist_ok=True)
         with self._log_lock:
             with open("logs/%s/eval.csv" % self.model_name, "a") as f:
                 f.write("%d,%d,%d,%.17g,%.17g,%.17g,%.17g\n" % (training_step, totals.size, steps, mean, float(totals.min()),
-                                                               float(totals.max()), (mean + steps) / 0.005))
+                                                               float(totals.max()), (mean - steps * offset) / scale))
 
     def compute(self, x, y_r, a, x2, done, stop_after, noise=None):
         s, a, r, d, s2, b = self._five(x, y_r, a, x2, done)

@@ -232,6 +232,10 @@ HIP_SIGNATURES = {
     "ga3c_ddpg_popart_create": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float]),
     "ga3c_ddpg_popart_destroy": (C.c_int, [C.c_void_p]),
     "ga3c_ddpg_popart_info": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p]),
+    # the task of a DDPG handle's device actors and evaluation episodes (Config.DEVICE_DDPG_ACTION_BOUND ..), include/ga3c_abi.h
+    "ga3c_ddpg_task_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double]),
+    "ga3c_ddpg_task_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_task_info": (C.c_int, [C.c_void_p, i32p, i32p, i32p, f64p, f64p]),
 }
 
 VECNET_SIGNATURES = {         # <prefix>_<entry> of both vector-state networks, handle first

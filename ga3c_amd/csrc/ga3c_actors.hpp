@@ -136,9 +136,10 @@ struct Pendulum {
     return m - pi;
   }
 
+  // gym's step without its wrapper: the physics move, `elapsed` counts, -> the cost.
   // T: float, the action vector itself; double (PendulumBounded below), the action as check_bounds hands it on
   template <class T>
-  __device__ static void step(double* s, const T* a, int* elapsed, double* reward, int* done) {
+  __device__ static double advance(double* s, const T* a, int* elapsed) {
 #pragma clang fp contract(off)
     const double pi = 3.141592653589793, dt = 0.05, max_speed = 8.0;
     const double th = s[0], thdot = s[1];
@@ -150,6 +151,13 @@ struct Pendulum {
     newthdot = newthdot < -max_speed ? -max_speed : (newthdot > max_speed ? max_speed : newthdot);   // after th' has used it
     s[0] = newth; s[1] = newthdot;
     *elapsed += 1;
+    return cost;
+  }
+
+  template <class T>
+  __device__ static void step(double* s, const T* a, int* elapsed, double* reward, int* done) {
+#pragma clang fp contract(off)
+    const double cost = advance(s, a, elapsed);
     *done = *elapsed >= 200 ? 1 : 0;
     *reward = -cost * 0.005 - 1.0;
   }
@@ -183,10 +191,43 @@ struct PendulumBounded : Pendulum {
     return v;
   }
 
+  // check_bounds(a, 1, -1, turnaround=False): 2 clip(a) is gym's clip(2 a, -2, 2) exactly, which stays absent here too
+  __device__ static double clip_bounds(float a) {
+    const double v = (double)a;
+    return v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v);
+  }
+
   __device__ static void step(double* s, const float* a, int* elapsed, double* reward, int* done) {
     const double bounded = check_bounds(a[0]);
     Pendulum::step(s, &bounded, elapsed, reward, done);
   }
+
+  // The step under a task (PendulumTask below): its bound, then Pendulum's physics and cost, its reward.  *ended:
+  // the time limit has been reached, whatever the task makes of that.
+  template <class Task>
+  __device__ static void step(double* s, const float* a, const Task& task, int* elapsed, double* reward, int* ended) {
+#pragma clang fp contract(off)
+    const double bounded = task.clip ? clip_bounds(a[0]) : check_bounds(a[0]);
+    const double cost = Pendulum::advance(s, &bounded, elapsed);
+    *ended = *elapsed >= 200 ? 1 : 0;
+    *reward = -cost * task.reward_scale + task.reward_offset;
+  }
+};
+
+// What "Pendulum-v0" means to the DDPG handle's device actors and evaluator (ga3c_ddpg_task_create, DESIGN.md 8t;
+// tests/ddpg_task_oracle.py is the same statement), by value in the arguments of the task kernels only.
+struct PendulumTask {
+  int clip;                  // the action is clipped to [-1, 1], not wrapped
+  int truncate;              // the time limit ends the episode and is no terminal state: the row's done stays 0
+  int reset_observation;     // a reset rewrites the observation from the reset physics
+  double reward_scale, reward_offset;      // reward = -cost scale + offset
+};
+
+// The fork's task, EnvironmentPend.Environment's, known to the compiler: the kernels of a handle without a task are
+// instantiated on it and are the kernels they were.
+struct ForkTask {
+  static constexpr int clip = 0, truncate = 0, reset_observation = 0;
+  static constexpr double reward_scale = 0.005, reward_offset = -1.0;
 };
 
 // The episodes a step finishes and the ring that keeps their records for the host: the part of the device state that the

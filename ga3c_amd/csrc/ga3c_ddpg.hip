@@ -63,6 +63,12 @@
 //                        arenas rescaled so that sigma n + mu stays what it was, and yn = (y - mu') / sigma' for the critic step
 // The target kernel de-normalises the target critic's output with the statistics it finds; every other kernel runs as it did, on
 // yn where y was.  A popart step is 6 launches (7 with clipping, + 3 prioritised).
+// The task (ga3c_ddpg_task_create, Config.DEVICE_DDPG_ACTION_BOUND and its four neighbours; tests/ddpg_task_oracle.py
+// is the same statement):
+//   ddpg_actors_task_step_kernel<Env>, ddpg_actors_task_nstep_kernel<Env>, ddpg_eval_task_kernel<Env>   the bodies of the three
+//                        kernels above with a PendulumTask from the arguments where they have ForkTask, the fork's wrapper as
+//                        constants: clip or wrap, the time limit as a truncation, the observation of the reset state, the
+//                        reward's scale and offset.  Launched in their places by a handle with a task; the launch counts stay.
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -1180,12 +1186,18 @@ struct ActState {
   ga3c_actors::Episodes ep;  // this step's finished episodes and the episode ring
 };
 
-// One step of environment i = the thread's index, the one statement of it for both kernels below.  first: the handle's first
+using ga3c_actors::ForkTask;
+using ga3c_actors::PendulumTask;
+
+// One step of environment i = the thread's index, the one statement of it for the kernels below.  first: the handle's first
 // ever step, the host's step(None): the zero action, nothing kept of the transition, its done not looked at.  Otherwise the
-// action is a.action's row and keep(i, obs, a, reward, done, obs') puts the transition where the kernel wants it, before the
-// episode's totals move.  The f64 physics must not contract; neither may a `keep` that does arithmetic.
-template <class Env, class Keep>
-__device__ __forceinline__ void actor_step(const ActState& a, int first, Keep keep) {
+// action is a.action's row and keep(i, obs, a, reward, ended, terminal, obs') puts the transition where the kernel wants it,
+// before the episode's totals move.  The f64 physics must not contract; neither may a `keep` that does arithmetic.
+// task: ForkTask, or a handle's PendulumTask.  `ended` is the time limit reached: a.done, the episode record, the
+// reset and its draws follow it; `terminal` is what a ring row calls done, `ended` unless the task truncates.  obs' is the
+// observation before any reset; under reset_observation a.obs then becomes the observation of the reset physics.
+template <class Env, class Task, class Keep>
+__device__ __forceinline__ void actor_step(const ActState& a, int first, const Task& task, Keep keep) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * ACT_THREADS + threadIdx.x;
   if (i >= a.N) return;
@@ -1200,7 +1212,7 @@ __device__ __forceinline__ void actor_step(const ActState& a, int first, Keep ke
   for (int k = 0; k < S; ++k) before[k] = obs[k];
   double reward;
   int done;
-  Env::step(s, av, &elapsed, &reward, &done);
+  Env::step(s, av, task, &elapsed, &reward, &done);
   Env::observe(s, after);
   for (int k = 0; k < S; ++k) obs[k] = after[k];
   a.reward[i] = reward;
@@ -1211,7 +1223,7 @@ __device__ __forceinline__ void actor_step(const ActState& a, int first, Keep ke
     ga3c_actors::store_physics<P>(a.phys, a.elapsed, i, s, elapsed);
     return;
   }
-  keep(i, before, av, reward, done, after);
+  keep(i, before, av, reward, done, (done && !task.truncate) ? 1 : 0, after);
   double total = a.total_reward[i] + reward;
   long long length = a.total_length[i] + 1;
   if (done) {                           // ProcessAgent.run's record of an episode shipped as one rollout: len(experiences) + 1
@@ -1219,6 +1231,11 @@ __device__ __forceinline__ void actor_step(const ActState& a, int first, Keep ke
     length += 1;
     ga3c_actors::finish_episode<Env>(a.ep, i, a.seed, total, length, draws, s, elapsed);
     a.draws[i] = draws;
+    if (task.reset_observation) {       // the next transition starts at the reset state
+      float fresh[S];
+      Env::observe(s, fresh);
+      for (int k = 0; k < S; ++k) obs[k] = fresh[k];
+    }
   }
   a.total_reward[i] = total;
   a.total_length[i] = length;
@@ -1228,24 +1245,41 @@ __device__ __forceinline__ void actor_step(const ActState& a, int first, Keep ke
 // actor_step with the transition obs | a | (f32) reward | done | obs' into ring slot (slot0 + i) mod cap (n <= cap: no two
 // threads share a slot).  With priorities that slot gets max_pa, which only per_update_kernel writes, earlier on this stream:
 // per_fill_kernel's value.
-template <class Env>
-__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState a, int first, float* __restrict__ ring, int64_t slot0,
-                                                                       int64_t cap, float* __restrict__ pa,
-                                                                       const float* __restrict__ max_pa) {
+// (The bodies take the kernels' arguments as they stand here, __restrict__ only on the kernels: spelt this way the two kernels
+// without a task compile to the listings they had, tools/asm_diff.py.)
+template <class Env, class Task>
+__device__ __forceinline__ void actors_step_body(ActState a, Task task, int first, float* ring, int64_t slot0, int64_t cap,
+                                                 float* pa, const float* max_pa) {
 #pragma clang fp contract(off)
   constexpr int S = Env::S, A = Env::A;
   constexpr int rowf = 2 * S + A + 2;
-  actor_step<Env>(a, first, [&](int i, const float* before, const float* av, double reward, int done, const float* after) {
+  actor_step<Env>(a, first, task,
+                  [&](int i, const float* before, const float* av, double reward, int, int terminal, const float* after) {
 #pragma clang fp contract(off)
     const int64_t slot = (slot0 + i) % cap;
     float* row = ring + slot * rowf;
     for (int k = 0; k < S; ++k) row[k] = before[k];
     for (int j = 0; j < A; ++j) row[S + j] = av[j];
     row[S + A] = (float)reward;
-    row[S + A + 1] = done ? 1.f : 0.f;
+    row[S + A + 1] = terminal ? 1.f : 0.f;
     for (int k = 0; k < S; ++k) row[S + A + 2 + k] = after[k];
     if (pa) pa[slot] = *max_pa;
   });
+}
+
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState a, int first, float* __restrict__ ring, int64_t slot0,
+                                                                       int64_t cap, float* __restrict__ pa,
+                                                                       const float* __restrict__ max_pa) {
+  actors_step_body<Env>(a, ForkTask{}, first, ring, slot0, cap, pa, max_pa);
+}
+
+// ... under a handle's task: the same body, the task read from the arguments.
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_task_step_kernel(ActState a, PendulumTask task, int first,
+                                                                            float* __restrict__ ring, int64_t slot0, int64_t cap,
+                                                                            float* __restrict__ pa, const float* __restrict__ max_pa) {
+  actors_step_body<Env>(a, task, first, ring, slot0, cap, pa, max_pa);
 }
 
 // The environments' windows of a handle with n-step returns: the last n transitions of each, entry-major and
@@ -1262,23 +1296,25 @@ struct NWindow {
 // slot (slot0 + i) mod cap: m = the first k in 1..n whose transition u + k - 1 is done, n if none; R = sum_{k<m} g_k r_{u+k} in
 // f64, ascending k, g_0 = 1 and g_{k+1} = g_k gamma64; the row is s_u | a_u | (f32) R | done_{u+m-1} | s2_{u+m-1} and
 // disc[slot] = (f32) g_m.  Nothing is summed across an episode's end; at n = 1 the row and gamma are ddpg_actors_step_kernel's.
-template <class Env>
-__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_nstep_kernel(ActState a, NWindow w, int first, int entry, int emit,
-                                                                        double gamma64, float* __restrict__ ring, int64_t slot0,
-                                                                        int64_t cap, float* __restrict__ disc,
-                                                                        float* __restrict__ pa, const float* __restrict__ max_pa) {
+// Under a task the window's done is `ended`, where the sum is cut; Pendulum ends at its time limit alone, so the
+// last summed transition's `terminal` is that flag, or 0 for every row when the task truncates.
+template <class Env, class Task>
+__device__ __forceinline__ void actors_nstep_body(const ActState& a, Task task, NWindow w, int first, int entry, int emit,
+                                                  double gamma64, float* ring, int64_t slot0, int64_t cap, float* disc, float* pa,
+                                                  const float* max_pa) {
 #pragma clang fp contract(off)
   constexpr int S = Env::S, A = Env::A;
   constexpr int rowf = 2 * S + A + 2, W = 2 * S + A + 1;
   const size_t N = (size_t)a.N;
-  actor_step<Env>(a, first, [&](int i, const float* before, const float* av, double reward, int done, const float* after) {
+  actor_step<Env>(a, first, task,
+                  [&](int i, const float* before, const float* av, double reward, int ended, int, const float* after) {
 #pragma clang fp contract(off)
     const int n = w.n;
     {
       float* e = w.f + (size_t)entry * W * N + i;
       for (int k = 0; k < S; ++k) e[k * N] = before[k];
       for (int j = 0; j < A; ++j) e[(S + j) * N] = av[j];
-      e[(S + A) * N] = done ? 1.f : 0.f;
+      e[(S + A) * N] = ended ? 1.f : 0.f;
       for (int k = 0; k < S; ++k) e[(S + A + 1 + k) * N] = after[k];
       w.r[(size_t)entry * N + i] = reward;
     }
@@ -1301,12 +1337,29 @@ __global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_nstep_kernel(ActState
       const float* el = w.f + (size_t)last * W * N + i;
       for (int k = 0; k < S + A; ++k) row[k] = eo[k * N];
       row[S + A] = (float)R;
-      row[S + A + 1] = d;
+      row[S + A + 1] = task.truncate ? 0.f : d;
       for (int k = 0; k < S; ++k) row[S + A + 2 + k] = el[(S + A + 1 + k) * N];
       disc[slot] = (float)g;
       if (pa) pa[slot] = *max_pa;
     }
   });
+}
+
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_nstep_kernel(ActState a, NWindow w, int first, int entry, int emit,
+                                                                        double gamma64, float* __restrict__ ring, int64_t slot0,
+                                                                        int64_t cap, float* __restrict__ disc,
+                                                                        float* __restrict__ pa, const float* __restrict__ max_pa) {
+  actors_nstep_body<Env>(a, ForkTask{}, w, first, entry, emit, gamma64, ring, slot0, cap, disc, pa, max_pa);
+}
+
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_task_nstep_kernel(ActState a, PendulumTask task, NWindow w, int first,
+                                                                             int entry, int emit, double gamma64,
+                                                                             float* __restrict__ ring, int64_t slot0, int64_t cap,
+                                                                             float* __restrict__ disc, float* __restrict__ pa,
+                                                                             const float* __restrict__ max_pa) {
+  actors_nstep_body<Env>(a, task, w, first, entry, emit, gamma64, ring, slot0, cap, disc, pa, max_pa);
 }
 
 // One workgroup: the step's finished episodes go to the episode ring in environment order (ga3c_actors.hpp).
@@ -1346,6 +1399,7 @@ struct EvalTrace {
 // the reward added in step order in f64.  Every episode starts from start[i] with elapsed = 0.  Env::step's wrap branch
 // cannot be reached after tanh; it is the training actors' statement, kept whole.  The loop is bounded by `steps` alone.
 // Reads th and start; writes total_out, phys_out and the trace: no ActState, no ring, no priorities, no windows.
+// ddpg_eval_task_kernel below is this text once more with a task in Env::step: whoever edits one edits the other.
 template <class Env>
 __global__ __launch_bounds__(THREADS) void ddpg_eval_kernel(Layout L, const float* __restrict__ th, int n, int steps,
                                                             const double* __restrict__ start, double* __restrict__ total_out,
@@ -1387,6 +1441,65 @@ __global__ __launch_bounds__(THREADS) void ddpg_eval_kernel(Layout L, const floa
       double reward;
       int done;
       Env::step(s, av, &elapsed, &reward, &done);
+      total = total + reward;
+      Env::observe(s, obs);
+      for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+      if (tr.phys) tr.reward[at] = reward;
+    }
+    __syncthreads();                                 // the next step's actor reads these observations
+  }
+  if (r < nrows) {
+    total_out[i] = total;
+    for (int k = 0; k < P; ++k) phys_out[i * P + k] = s[k];
+  }
+}
+
+// ddpg_eval_kernel under a handle's task: only the reward differs -- no bound is reached after tanh, and there is
+// no ring and no reset.  The text above once more and not a body shared with it: inlined from a shared function the compiler
+// orders ddpg_eval_kernel's last address computations differently, and that kernel is held to the listing it had.  The two are
+// edited together.  (`done` is Env::step's out-argument there and here: an evaluation is bounded by `steps` alone.)
+template <class Env>
+__global__ __launch_bounds__(THREADS) void ddpg_eval_task_kernel(Layout L, const float* __restrict__ th, int n, int steps,
+                                                                 PendulumTask task, const double* __restrict__ start,
+                                                                 double* __restrict__ total_out, double* __restrict__ phys_out,
+                                                                 EvalTrace tr) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  constexpr int S = Env::S, P = Env::P, A = Env::A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, n - row0);
+  const int r = threadIdx.x;
+  const size_t i = (size_t)row0 + r;                 // the thread's environment, r < nrows
+  double s[P];
+  double total = 0.0;
+  int elapsed = 0;
+  float obs[S];
+  if (r < TILE) {
+    for (int k = 0; k < S; ++k) obs[k] = 0.f;
+    if (r < nrows) {
+      for (int k = 0; k < P; ++k) s[k] = start[i * P + k];
+      Env::observe(s, obs);
+    }
+    for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+  }
+  __syncthreads();
+  for (int t = 0; t < steps; ++t) {
+    // ends in a barrier: act is whole, and no thread reads xin any more
+    actor_fwd(L, th, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    if (r < nrows) {
+      float av[A];
+      for (int j = 0; j < A; ++j) av[j] = act[j * TILE + r];
+      const size_t at = i * EVAL_MAX_STEPS + t;
+      if (tr.phys) {
+        for (int k = 0; k < P; ++k) tr.phys[at * P + k] = s[k];
+        for (int k = 0; k < S; ++k) tr.obs[at * S + k] = obs[k];
+        for (int j = 0; j < A; ++j) tr.action[at * A + j] = av[j];
+      }
+      double reward;
+      int done;
+      Env::step(s, av, task, &elapsed, &reward, &done);
       total = total + reward;
       Env::observe(s, obs);
       for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
@@ -1534,6 +1647,8 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   Eval* eval = nullptr;           // null: no evaluation episodes
   Pop* pop = nullptr;             // null: the critic's output is the return itself
   float* yn = nullptr;            // [B] its normalised targets, null without
+  bool has_task = false;          // false: the fork's task, and the actors' and the evaluator's kernels are the ones without
+  PendulumTask task{};            // (ga3c_ddpg_task_create): by value to the task kernels
   DistRows dw{};                  // the distributional critic's rows, null without
   std::vector<std::string> tnames;      // the target copies' names, by variable
 };
@@ -2934,6 +3049,61 @@ int ga3c_ddpg_nstep_set(ga3c_ddpg* m, const float* disc, int64_t count) {
   return GA3C_OK;
 }
 
+// ---- the task of the device actors and the evaluator
+
+namespace {
+int task_check(const ga3c_ddpg* m, const char* what, bool idle) {
+  if (!m->has_task) return fail(GA3C_ESTATE, "%s: the handle has no task (ga3c_ddpg_task_create)", what);
+  if (idle && (m->actors || m->eval))
+    return fail(GA3C_ESTATE, "%s: the handle's device actors or evaluation episodes step under its task (destroy them first)", what);
+  return GA3C_OK;
+}
+}  // namespace
+
+int ga3c_ddpg_task_create(ga3c_ddpg* m, int32_t bound, int32_t time_limit, int32_t reset_observation, double reward_scale,
+                          double reward_offset) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (bound != GA3C_DDPG_TASK_WRAP && bound != GA3C_DDPG_TASK_CLIP)
+    return fail(GA3C_EINVAL, "bound %d is neither GA3C_DDPG_TASK_WRAP nor GA3C_DDPG_TASK_CLIP", bound);
+  if (time_limit != GA3C_DDPG_TASK_TERMINAL && time_limit != GA3C_DDPG_TASK_TRUNCATE)
+    return fail(GA3C_EINVAL, "time_limit %d is neither GA3C_DDPG_TASK_TERMINAL nor GA3C_DDPG_TASK_TRUNCATE", time_limit);
+  if (reset_observation != 0 && reset_observation != 1)
+    return fail(GA3C_EINVAL, "reset_observation %d is neither 0 nor 1", reset_observation);
+  if (!std::isfinite(reward_scale) || !(reward_scale > 0.0)) return fail(GA3C_EINVAL, "reward_scale %g is not a finite number above 0", reward_scale);
+  if (!std::isfinite(reward_offset)) return fail(GA3C_EINVAL, "reward_offset %g is not finite", reward_offset);
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  if (m->has_task) return fail(GA3C_ESTATE, "the handle has a task already");
+  if (m->actors || m->eval)
+    return fail(GA3C_ESTATE, "the handle has device actors or evaluation episodes: they choose their kernels when they are made, so the task comes first");
+  m->task = PendulumTask{bound == GA3C_DDPG_TASK_CLIP, time_limit == GA3C_DDPG_TASK_TRUNCATE, reset_observation, reward_scale,
+                         reward_offset};
+  m->has_task = true;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_task_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  CHK(task_check(m, "task_destroy", true));
+  m->has_task = false;
+  m->task = PendulumTask{};
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_task_info(ga3c_ddpg* m, int32_t* bound, int32_t* time_limit, int32_t* reset_observation, double* reward_scale,
+                        double* reward_offset) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  CHK(task_check(m, "task_info", false));
+  const PendulumTask& t = m->task;
+  if (bound) *bound = t.clip ? GA3C_DDPG_TASK_CLIP : GA3C_DDPG_TASK_WRAP;
+  if (time_limit) *time_limit = t.truncate ? GA3C_DDPG_TASK_TRUNCATE : GA3C_DDPG_TASK_TERMINAL;
+  if (reset_observation) *reset_observation = t.reset_observation;
+  if (reward_scale) *reward_scale = t.reward_scale;
+  if (reward_offset) *reward_offset = t.reward_offset;
+  return GA3C_OK;
+}
+
 // ---- device actors
 
 using DEnv = ga3c_actors::PendulumBounded;
@@ -3027,10 +3197,19 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
     }
     const int wn = a->win.n;            // n-step returns: a row leaves the window from transition n - 1 on
     const bool emit = !first && a->count >= wn - 1;
-    if (wn)
+    if (wn && m->has_task)
+      hipLaunchKernelGGL(ddpg_actors_task_nstep_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st,
+                         d, m->task, a->win, first, (int)(a->count % wn), emit ? 1 : 0, (double)m->cfg.gamma, m->ring,
+                         m->ring_total % cap, cap, m->nstep->disc, m->per ? m->per->pa : nullptr,
+                         m->per ? (const float*)m->per->max_pa : nullptr);
+    else if (wn)
       hipLaunchKernelGGL(ddpg_actors_nstep_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
                          a->win, first, (int)(a->count % wn), emit ? 1 : 0, (double)m->cfg.gamma, m->ring, m->ring_total % cap, cap,
                          m->nstep->disc, m->per ? m->per->pa : nullptr, m->per ? (const float*)m->per->max_pa : nullptr);
+    else if (m->has_task)
+      hipLaunchKernelGGL(ddpg_actors_task_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st,
+                         d, m->task, first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
+                         m->per ? (const float*)m->per->max_pa : nullptr);
     else
       hipLaunchKernelGGL(ddpg_actors_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
                          first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
@@ -3288,8 +3467,13 @@ int ga3c_ddpg_eval_run(ga3c_ddpg* m, int32_t steps, int32_t target, double* tota
   {
     std::lock_guard<std::mutex> lk(m->mu);
     HIPCHK(hipEventRecord(m->t0, m->st));
-    hipLaunchKernelGGL(ddpg_eval_kernel<DEnv>, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[target ? 1 : 0],
-                       e->n, (int)steps, (const double*)e->start, e->total, e->phys, e->tr);
+    if (m->has_task)
+      hipLaunchKernelGGL(ddpg_eval_task_kernel<DEnv>, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L,
+                         (const float*)m->arena[target ? 1 : 0], e->n, (int)steps, m->task, (const double*)e->start, e->total, e->phys,
+                         e->tr);
+    else
+      hipLaunchKernelGGL(ddpg_eval_kernel<DEnv>, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[target ? 1 : 0],
+                         e->n, (int)steps, (const double*)e->start, e->total, e->phys, e->tr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->t1, m->st));
     HIPCHK(hipMemcpyAsync(e->h_total(), e->total, sizeof(double) * e->n, hipMemcpyDeviceToHost, m->st));

@@ -907,6 +907,39 @@ int ga3c_ddpg_popart_create(ga3c_ddpg* net, float beta, float sigma_min, float s
 int ga3c_ddpg_popart_destroy(ga3c_ddpg* net);
 int ga3c_ddpg_popart_info(ga3c_ddpg* net, float* beta, float* mu, float* nu, float* sigma);
 
+/* ---- The task of a DDPG handle's device actors and evaluation episodes (Config.DEVICE_DDPG_ACTION_BOUND, _TIME_LIMIT,
+ * _RESET_OBSERVATION, _REWARD_SCALE, _REWARD_OFFSET; tests/ddpg_task_oracle.py is the same statement in numpy).
+ * Without one they step the fork's wrapper, EnvironmentPend.Environment: (WRAP, TERMINAL, 0, 0.005, -1.0), as before and bit for
+ * bit.  With one, a non-first actor step of an environment, for the f32 action a as predicted:
+ *   bound     v = (f64) a; WRAP: check_bounds(a, 1, -1, turnaround) as before; CLIP: v < -1 -> -1, v > 1 -> 1.  Then the
+ *             physics and the cost on u = 2 v, unchanged.
+ *   reward    -cost * reward_scale + reward_offset in f64, in that order; at (0.005, -1.0) the same bits as before.
+ *   the end   ended = elapsed' >= 200; terminal = ended under TERMINAL, never under TRUNCATE.
+ *   the row   obs | a as predicted | (f32) reward | terminal ? 1 : 0 | obs', obs' the observation after the step and before
+ *             any reset: under TRUNCATE the state the bootstrap reads.
+ *   after it  the actor field "done", the episode record, the reset and its draws, and reset_on_done of the per-environment
+ *             noise follow `ended`.  With reset_observation the field "obs" then becomes the observation of the reset physics
+ *             and the next row starts there; without it the observation stays, as before.
+ *   n-step    the sum is cut at `ended`; the row's done is the terminal of the last transition summed: a row cut by a
+ *             truncating time limit is s_u | a_u | R | 0 | s2_{u+m-1} with disc = (f32) gamma^m.
+ *   evaluation episodes: only the reward differs.
+ * The train step reads r, done, s2 and the discount from the ring as before and does not know of the task; the support of a
+ * distributional critic is the caller's to fit to the reward.  No further launch per actor step, no flag, no field.
+ * create: GA3C_EINVAL for a bound or time_limit outside 0..1, reset_observation outside 0..1, a reward_scale that is not finite
+ * or not > 0, a reward_offset that is not finite; GA3C_ESTATE on a second create and on a handle that has device actors or
+ * evaluation episodes, which choose their kernels when they are made.
+ * destroy: GA3C_ESTATE without a task or with live actors or evaluation episodes; ga3c_ddpg_destroy drops the task.
+ * info: each pointer may be NULL; GA3C_ESTATE without a task. */
+#define GA3C_DDPG_TASK_WRAP 0      /* bound */
+#define GA3C_DDPG_TASK_CLIP 1
+#define GA3C_DDPG_TASK_TERMINAL 0  /* time_limit */
+#define GA3C_DDPG_TASK_TRUNCATE 1
+int ga3c_ddpg_task_create(ga3c_ddpg* net, int32_t bound, int32_t time_limit, int32_t reset_observation, double reward_scale,
+                          double reward_offset);
+int ga3c_ddpg_task_destroy(ga3c_ddpg* net);
+int ga3c_ddpg_task_info(ga3c_ddpg* net, int32_t* bound, int32_t* time_limit, int32_t* reset_observation, double* reward_scale,
+                        double* reward_offset);
+
 #ifdef __cplusplus
 }
 #endif

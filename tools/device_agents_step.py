@@ -10,9 +10,12 @@ train steps of --batch ring rows after every actor step, --prioritized for the d
 (Config.DDPG_NSTEP, DESIGN.md 8o; profiles/nstep_step.txt); the call waits once, at its end (profiles/device_agents_ddpg.txt);
 --eval-envs E --eval-every K for an evaluation of E noise-free episodes whenever the train steps pass a multiple of K, as
 ThreadDeviceAgents runs them under DEVICE_DDPG_EVAL_ENVS (DESIGN.md 8q; profiles/ddpg_eval.txt), inside the timed rounds;
---noise per_env for every environment's own noise process (Config.DEVICE_DDPG_NOISE; profiles/envnoise_step.txt).
+--noise per_env for every environment's own noise process (Config.DEVICE_DDPG_NOISE, DESIGN.md 8r; profiles/envnoise_step.txt);
+--action-bound, --time-limit, --reset-observation, --reward-scale, --reward-offset for the actors' task (Config.DEVICE_DDPG_ACTION_BOUND
+and its neighbours; profiles/ddpg_task_step.txt): any non-default one attaches a task, and the task kernels step.
 usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]
-       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1] [--eval-envs 0] [--eval-every 1000] [--noise shared|per_env]]"""
+       [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1] [--eval-envs 0] [--eval-every 1000] [--noise shared|per_env]
+        [--action-bound wrap|clip] [--time-limit terminal|truncate] [--reset-observation] [--reward-scale 0.005] [--reward-offset -1]]"""
 import argparse
 import json
 import os
@@ -41,6 +44,11 @@ def main():
     ap.add_argument("--eval-envs", type=int, default=0, help="--ddpg: evaluation environments (0: none)")
     ap.add_argument("--eval-every", type=int, default=1000, help="--ddpg: train steps between two evaluations")
     ap.add_argument("--noise", choices=("shared", "per_env"), default="shared", help="--ddpg: the actors' exploration noise")
+    ap.add_argument("--action-bound", choices=("wrap", "clip"), default="wrap", help="--ddpg: DEVICE_DDPG_ACTION_BOUND")
+    ap.add_argument("--time-limit", choices=("terminal", "truncate"), default="terminal", help="--ddpg: DEVICE_DDPG_TIME_LIMIT")
+    ap.add_argument("--reset-observation", action="store_true", help="--ddpg: DEVICE_DDPG_RESET_OBSERVATION")
+    ap.add_argument("--reward-scale", type=float, default=0.005, help="--ddpg: DEVICE_DDPG_REWARD_SCALE")
+    ap.add_argument("--reward-offset", type=float, default=-1.0, help="--ddpg: DEVICE_DDPG_REWARD_OFFSET")
     args = ap.parse_args()
     import ga3c_amd  # noqa: F401
     from Config import Config
@@ -52,6 +60,9 @@ def main():
         Config.PRIORITIZED_REPLAY = args.prioritized
         Config.DDPG_NSTEP = args.nstep
         Config.DEVICE_DDPG_NOISE = args.noise
+        Config.DEVICE_DDPG_ACTION_BOUND, Config.DEVICE_DDPG_TIME_LIMIT = args.action_bound, args.time_limit
+        Config.DEVICE_DDPG_RESET_OBSERVATION = args.reset_observation
+        Config.DEVICE_DDPG_REWARD_SCALE, Config.DEVICE_DDPG_REWARD_OFFSET = args.reward_scale, args.reward_offset
         if args.prioritized:
             Config.DDPG_CRITIC_LOSS = 'paired'
     elif args.game == "Pendulum-v0":
@@ -65,6 +76,7 @@ def main():
             net = Network("gpu:0", "device_agents_step", num_actions, state_dim, max_batch=max(n, args.batch), predict_lanes=1,
                           replay_capacity=args.capacity)
             net.learning_rate = Config.LEARNING_RATE_START
+            net_task = list(net.task) if net.task else None
             net.actors_create(n, seed=Config.RANDOM_SEED, updates=args.updates, batch=args.batch)
             if args.eval_envs:
                 net.eval_create(args.eval_envs)
@@ -89,7 +101,7 @@ def main():
         rates.sort()
         per_step_us = 1e6 * n / rates[len(rates) // 2]
         extra = ({"ddpg": True, "batch": args.batch, "updates": args.updates, "prioritized": args.prioritized, "nstep": args.nstep,
-                  "noise": args.noise,
+                  "noise": args.noise, "task": net_task,
                   "eval_envs": args.eval_envs, "eval_every": args.eval_every, "evaluations": evaluations,
                   "train_steps_per_s_median": round(sorted(train_rates)[len(train_rates) // 2])} if args.ddpg else {})
         print(json.dumps({**extra, "game": args.game, "agents": n, "time_max": args.time_max, "train": not args.no_train, "steps_per_call": args.steps,

@@ -5,8 +5,9 @@ actor step once the ring holds more than a batch), and every --every train steps
 of 200 steps from fixed start states (eval_run; one more before the first train step).  The variant is given as the product's
 own KEY=VALUE settings and checked by the product's resolvers; --noise per_env is DEVICE_DDPG_NOISE=per_env.  Writes <out-dir>/<name>.csv,
     training_step, n, steps, mean, min, max, mean_gym_return, wall_s
-(mean_gym_return = (mean + steps) / 0.005 undoes the wrapper's r * 0.005 - 1: gym's number for Pendulum-v0, 0 at best and about
--1200 to -1500 for a policy that does nothing), and prints one JSON line: the first evaluation, the best, the mean of the last
+(mean_gym_return = (mean - steps * offset) / scale undoes the reward's DEVICE_DDPG_REWARD_SCALE and _OFFSET, the wrapper's
+r * 0.005 - 1 at the defaults: gym's number for Pendulum-v0, 0 at best and about -1200 to -1500 for a policy that
+does nothing), and prints one JSON line: the first evaluation, the best, the mean of the last
 five, the wall time.  profiles/learning_curves.md is the record of the variants that exist.
 usage: python tools/learning_curve.py --name paired [--train-steps 60000] [--every 1000] [--actors 256] [--batch 64]
        [--eval-envs 64] [--noise shared|per_env] [--out-dir profiles/learning_curves] DDPG_CRITIC_LOSS=paired ..."""
@@ -44,7 +45,7 @@ def main():
         Config.DEVICE_DDPG_NOISE = args.noise
     GA3C.apply_argv(args.settings)              # the variant, coerced and resolved as the product does
     resolve_device_agents()
-    from NetworkDDPG import Network
+    from NetworkDDPG import FORK_TASK, Network
     net = Network("gpu:0", "learning_curve_" + args.name, 1, (3,), max_batch=max(args.actors, args.batch), predict_lanes=1)
     net.learning_rate = Config.LEARNING_RATE_START
     net.actors_create(args.actors)
@@ -56,7 +57,8 @@ def main():
     def evaluate(out):
         totals = net.eval_run(EVAL_STEPS, bool(Config.DEVICE_DDPG_EVAL_TARGET))
         mean = float(totals.mean())
-        rows.append((mean + EVAL_STEPS) / 0.005)
+        scale, offset = (net.task or FORK_TASK)[3:]       # what the handle holds, as log_eval reads it
+        rows.append((mean - EVAL_STEPS * offset) / scale)
         out.write("%d,%d,%d,%.17g,%.17g,%.17g,%.17g,%.3f\n" % (trained, totals.size, EVAL_STEPS, mean, float(totals.min()),
                                                               float(totals.max()), rows[-1], time.perf_counter() - t0))
         out.flush()
