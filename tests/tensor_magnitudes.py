@@ -53,6 +53,19 @@ def vector_net():
                ["B = %d" % b for b in sizes], [(n, [_cell(cols[b][n]) for b in sizes]) for n in names])
 
 
+def vector_saturated():
+    import mlp_oracle as m
+    import vector_limit_cases as vc
+    cols = {}
+    for S, A in vc.SATURATED:
+        x, y, a = vc.saturated_batch(S, A)
+        _, cols[S, A] = m.loss_and_grads(vc.saturated_params(S, A), *vc.f64(x, y, a), vc.BETA)
+    names = ("dv", "dz", "dd1", "dpd4", "dpd3", "dpd2", "dpd1") + m.PARAM_ORDER
+    _table("vector net with a saturated head (logits_p/out_x/w, out_y/w x %g), B = %d, the weights and rows of "
+           "test_gpu_vector_limits (max / rms)" % (vc.SAT_SCALE, vc.SAT_B), ["S = %d, A = %d" % sa for sa in vc.SATURATED],
+           [(n, [_cell(cols[sa][n]) for sa in vc.SATURATED]) for n in names])
+
+
 def ddpg():
     import ddpg_oracle as d
     import test_gpu_ddpg as td
@@ -76,4 +89,5 @@ def ddpg():
 if __name__ == "__main__":
     image_net()
     vector_net()
+    vector_saturated()
     ddpg()

@@ -23,6 +23,14 @@ SHAPES = [(4, 2, (10, 10, 10, 10), "fork"), (4, 2, (10, 10, 10, 10), "chained"),
 SHAPE_IDS = ["fork4x10", "chained4x10", "chained32_16", "one_action"]
 # the backward pass shares a row of W among P = 1, 1, 2, 64 and 256 threads at these widths (the shapes above reach 8 and 16)
 SPLIT_EDGES = (64, 32, (256, 129, 128, 3, 1), "chained")
+# all eight layers ga3c_dmlp_create admits (GA3C_DMLP_MAX_LAYERS) at the largest S and A, in both wirings: chained, every layer
+# is live; fork, only layer 8 is and 14 variables are dead.  256, 129 and small odd widths, a width of 1 in last place only (as
+# above); no compared tensor of the oracle is all zero (through eight sigmoid layers dh1 is down to 4e-7 .. 7e-7, which the
+# relative test holds to its own largest entry).  These two run at EIGHT_SIZES.
+EIGHT_WIDTHS = (256, 129, 7, 33, 5, 128, 3, 1)
+EIGHT = [(64, 32, EIGHT_WIDTHS, "chained"), (64, 32, EIGHT_WIDTHS, "fork")]
+EIGHT_IDS = ["chained8", "fork8"]
+EIGHT_SIZES = [1, 17, 132]
 HEADS = {"plain": dict(use_log_softmax=False, min_policy=0.0), "log_softmax": dict(use_log_softmax=True, min_policy=0.0),
          "min_policy": dict(use_log_softmax=False, min_policy=0.01)}
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ga3c_amd")
@@ -76,6 +84,10 @@ def _reset(net, params):
     net.set_arena(2, np.zeros(net.param_count, np.float32))
 
 
+def _sizes(shape):
+    return EIGHT_SIZES if shape in EIGHT else SIZES
+
+
 def _live_layers(layers, stack):
     return list(range(1, len(layers) + 1)) if stack == "chained" else [len(layers)]
 
@@ -90,7 +102,7 @@ def _f64(*arrays):
 
 
 @pytest.mark.parametrize("head", list(HEADS))
-@pytest.mark.parametrize("shape", SHAPES + [SPLIT_EDGES], ids=SHAPE_IDS + ["split_edges"])
+@pytest.mark.parametrize("shape", SHAPES + [SPLIT_EDGES] + EIGHT, ids=SHAPE_IDS + ["split_edges"] + EIGHT_IDS)
 def test_forward_losses_and_gradients_against_the_oracle(shape, head):
     S, A, layers, stack = shape
     kw = HEADS[head]
@@ -100,7 +112,7 @@ def test_forward_losses_and_gradients_against_the_oracle(shape, head):
         _reset(net, params)
         assert net.param_count == m.param_count(S, A, layers, stack)
         assert [n[:-2] for n in net.get_variables_names()] == list(m.param_order(layers))
-        for bsz in SIZES:
+        for bsz in _sizes(shape):
             x, y, a = _batch(bsz, S, A, 100 + bsz)
             x64, y64, a64 = _f64(x, y, a)
             f = m.forward(params, x64, stack, **kw)
@@ -128,13 +140,13 @@ def test_forward_losses_and_gradients_against_the_oracle(shape, head):
         assert set(net.dead) == set(m.dead_params(layers, stack))
         if net.dead:
             with pytest.raises(RuntimeError):
-                net.fetch("h1", SIZES[-1] * layers[0])              # a layer nothing reads has no rows
+                net.fetch("h1", _sizes(shape)[-1] * layers[0])              # a layer nothing reads has no rows
     finally:
         net.close()
 
 
 @pytest.mark.parametrize("head", list(HEADS))
-@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+@pytest.mark.parametrize("shape", SHAPES + EIGHT, ids=SHAPE_IDS + EIGHT_IDS)
 def test_backward_tensors_relative_to_their_largest_entry(shape, head):
     """Every delta and gradient once more with tests/closeness.py: max|got - want| / max|want| against max(16 x e32, 2^-20),
     e32 from the oracle run in float32 on the same rows.  A bias gradient of ONE element (logits_v/b) takes the larger of that
@@ -151,7 +163,7 @@ def test_backward_tensors_relative_to_their_largest_entry(shape, head):
         _reset(net, params)
         net.beta = 0.01
         failed = []
-        for bsz in SIZES:
+        for bsz in _sizes(shape):
             x, y, a = _batch(bsz, S, A, 100 + bsz)
             net.compute_grads(x, y, a)
             _, g = m.loss_and_grads(params, *_f64(x, y, a), 0.01, stack=stack, **kw)
@@ -170,8 +182,8 @@ def test_backward_tensors_relative_to_their_largest_entry(shape, head):
                 e32 = c.rel_err(g32[name], g[name])
                 if name == "logits_v/b":
                     e32 = max(e32, c.e32_of_row_sum(g32["dv"], g["dv"]))
-                err = c.report("dmlp %s %s B=%d" % (SHAPE_IDS[SHAPES.index(shape)], head, bsz), name, got[name], g[name], e32,
-                               c.bound(e32))
+                shape_id = (SHAPE_IDS + EIGHT_IDS)[(SHAPES + EIGHT).index(shape)]
+                err = c.report("dmlp %s %s B=%d" % (shape_id, head, bsz), name, got[name], g[name], e32, c.bound(e32))
                 if not err <= c.bound(e32):
                     failed.append((bsz, name, err, c.bound(e32)))
         assert not failed, failed

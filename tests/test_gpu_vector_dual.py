@@ -4,7 +4,6 @@ where the two must agree.  Parameters and batches are built as tests/test_gpu_ve
 777), widened head biases, and every batch away from the atan2 branch cut.  Absolute tolerance: 1e-4 x max(1, max|want|), as
 there; every per-cost tensor is also held relative to its own largest entry (tests/closeness.py), because the policy cost's
 tensors are small (norms 0.016 .. 0.45 at S = 3, B = 132 against 4.7 .. 214 for the value cost)."""
-import contextlib
 import ctypes as C
 import functools
 
@@ -14,6 +13,8 @@ import pytest
 import closeness as c
 import mlp_oracle as m
 import mlp_dual_oracle as d
+import vector_limit_cases as vc
+from vector_limit_cases import close as _close, config as _config, e32 as _e32, mask as _mask, reset as _reset
 
 pytestmark = pytest.mark.gpu
 
@@ -29,25 +30,6 @@ WIDTHS = {"dd1": 64, "dpd4": 100, "dpd3": 256, "dpd2": 256, "dpd1": 4}
 TENSOR_FACTOR = {}
 
 
-def _close(got, want, tol=TOL):
-    got, want = np.asarray(got, np.float64).reshape(-1), np.asarray(want, np.float64).reshape(-1)
-    return np.max(np.abs(got - want)) <= tol * max(1.0, np.max(np.abs(want)))
-
-
-@contextlib.contextmanager
-def _config(**kw):
-    import ga3c_amd  # noqa: F401
-    from Config import Config
-    saved = {k: getattr(Config, k) for k in kw}
-    for k, v in kw.items():
-        setattr(Config, k, v)
-    try:
-        yield Config
-    finally:
-        for k, v in saved.items():
-            setattr(Config, k, v)
-
-
 def _net(state_dim, num_actions, dual=True, **kw):
     import ga3c_amd  # noqa: F401  (puts the flat modules on sys.path)
     from NetworkVP_vector import Network
@@ -57,43 +39,16 @@ def _net(state_dim, num_actions, dual=True, **kw):
 
 @functools.lru_cache(maxsize=None)
 def _params(state_dim, num_actions):
-    p = m.init_params(state_dim, num_actions, seed=777)
-    rng = np.random.default_rng(5)
-    p["logits_p/out_x/b"] = rng.uniform(-1.5, 1.5, num_actions).astype(np.float32).astype(np.float64)
-    p["logits_p/out_y/b"] = rng.uniform(-1.5, 1.5, num_actions).astype(np.float32).astype(np.float64)
-    return p
+    return vc.params(state_dim, num_actions)
 
 
 @functools.lru_cache(maxsize=None)
 def _batch(bsz, state_dim, num_actions, seed):
-    params = _params(state_dim, num_actions)
-    rng = np.random.Generator(np.random.PCG64(seed))
-    x = rng.uniform(-1.5, 1.5, size=(3 * bsz + 16, state_dim)).astype(np.float32)
-    x = x[m.safe_rows(params, x.astype(np.float64), 1e-3)][:bsz]
-    assert x.shape[0] == bsz
-    a = rng.uniform(-1, 1, size=(bsz, num_actions)).astype(np.float32)
-    y = rng.uniform(-1, 1, size=bsz).astype(np.float32)
-    return x, y, a
+    return vc.batch(_params(state_dim, num_actions), bsz, state_dim, num_actions, seed)
 
 
 def _f64(x, y, a):
     return x.astype(np.float64), y.astype(np.float64), a.astype(np.float64)
-
-
-def _reset(net, params, dual=True):
-    net.set_arena(0, m.flat(params))
-    for w in (1, 4) if dual else (1,):
-        net.set_arena(w, np.ones(net.param_count, np.float32))
-    for w in (2, 5) if dual else (2,):
-        net.set_arena(w, np.zeros(net.param_count, np.float32))
-
-
-def _mask(net, names):
-    mask = np.zeros(net.param_count, bool)
-    for k in names:
-        off, size = net._offsets[k]
-        mask[off:off + size] = True
-    return mask
 
 
 def _no_slot_regions_untouched(net):
@@ -104,18 +59,6 @@ def _no_slot_regions_untouched(net):
 
 
 # ---- gradients against the dual oracle
-def _e32(name, got32, want64, head32, head64, num_actions):
-    """closeness's e32 of one per-cost tensor: the oracle in float32 against the oracle in float64; a bias gradient of ONE
-    element takes the larger of that single draw and what the float32 error of the delta it sums implies."""
-    e32 = c.rel_err(got32[name], want64[name])
-    sums = {"logits_v/b": ("dv", slice(None)), "logits_p/out_x/b": ("dz", (slice(None), slice(0, num_actions))),
-            "logits_p/out_y/b": ("dz", (slice(None), slice(num_actions, 2 * num_actions)))}
-    if name in sums and np.size(want64[name]) == 1:
-        key, sel = sums[name]
-        e32 = max(e32, c.e32_of_row_sum(np.asarray(head32[key])[sel], np.asarray(head64[key])[sel]))
-    return e32
-
-
 @pytest.mark.parametrize("state_dim,num_actions", SHAPES)
 def test_both_costs_deltas_and_gradients_against_the_oracle(state_dim, num_actions):
     S, A = state_dim, num_actions

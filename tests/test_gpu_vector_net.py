@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import mlp_oracle as m
+from vector_limit_cases import batch as _batch, params as _params      # shared with tests/test_gpu_vector_limits.py
 
 pytestmark = pytest.mark.gpu
 
@@ -42,24 +43,6 @@ def _net(state_dim, num_actions, max_batch=1024, **kw):
     from NetworkVP_vector import Network
     with _config(**kw):
         return Network("gpu:0", "vec", num_actions, (state_dim,), max_batch=max_batch)
-
-
-def _params(state_dim, num_actions):
-    p = m.init_params(state_dim, num_actions, seed=777)
-    rng = np.random.default_rng(5)
-    p["logits_p/out_x/b"] = rng.uniform(-1.5, 1.5, num_actions).astype(np.float32).astype(np.float64)
-    p["logits_p/out_y/b"] = rng.uniform(-1.5, 1.5, num_actions).astype(np.float32).astype(np.float64)
-    return p
-
-
-def _batch(params, bsz, state_dim, num_actions, seed):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    x = rng.uniform(-1.5, 1.5, size=(3 * bsz + 16, state_dim)).astype(np.float32)
-    x = x[m.safe_rows(params, x.astype(np.float64), 1e-3)][:bsz]
-    assert x.shape[0] == bsz
-    a = rng.uniform(-1, 1, size=(bsz, num_actions)).astype(np.float32)
-    y = rng.uniform(-1, 1, size=bsz).astype(np.float32)
-    return x, y, a
 
 
 def _reset(net, params):
