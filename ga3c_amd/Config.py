@@ -65,7 +65,8 @@ class Config:
     USE_DDPG = False                    # NetworkDDPG.py with ThreadReplay.py (needs CONTINUOUS_INPUT); resolve_ddpg() applies what
     USE_REPLAY_MEMORY = False           # it implies (the reference's Config.py:160-178): USE_REPLAY_MEMORY, DISCOUNTING = False
     add_OUnoise = True                  # (sic) Ornstein-Uhlenbeck noise on every prediction of NetworkDDPG, which alone reads it
-                                        # (the reference sets it True under USE_DDPG); switch off with `add_OUnoise=`
+                                        # (the reference sets it True under USE_DDPG); switch off with `add_OUnoise=`.  Not read
+                                        # under DDPG_SOFT: the stochastic policy's own sample is the exploration
     add_uncertainity = False            # (sic) an integer added to the prediction: not supported, raises
     REPLAY_BUFFER_SIZE = 1000000
     REPLAY_BUFFER_RANDOM_SEED = 12345
@@ -86,6 +87,15 @@ class Config:
     DDPG_POLICY_DELAY = 2               # a policy step every this many train steps (1..16)
     DDPG_TARGET_NOISE = 0.2             # sigma of the target smoothing: a~ = clip(actor_target(s2) + clip(sigma n, -c, c), -1, 1)
     DDPG_TARGET_NOISE_CLIP = 0.5        # ... and its c
+    DDPG_SOFT = False                   # DDPG_TWIN only: soft actor-critic (Haarnoja et al. 2018).  The actor's head gives a mean and a
+                                        # log standard deviation per action, the action is tanh of a Gaussian sample drawn in the
+                                        # kernels, alpha x the entropy enters the critics' target and the actor's loss, and alpha is
+                                        # learned towards DDPG_SOFT_TARGET_ENTROPY; num_actions <= 16
+    DDPG_SOFT_ALPHA = 0.2               # the temperature's first value (finite, > 0)
+    DDPG_SOFT_ALPHA_LR = 1.0            # factor on the annealed learning rate for log alpha's Adam, as actor_lr is (>= 0; 0 fixes alpha)
+    DDPG_SOFT_TARGET_ENTROPY = None     # None: -num_actions
+    DDPG_SOFT_LOG_STD_MIN = -20.0       # the head's log standard deviation is clamped into [DDPG_SOFT_LOG_STD_MIN, _MAX]
+    DDPG_SOFT_LOG_STD_MAX = 2.0
     DDPG_NSTEP = 1                      # DEVICE_DDPG only: the ring's rows carry n-step returns, R = sum_{k<m} gamma^k r_k cut at an
                                         # episode's end, and y = R + gamma^m q'(s_m) (1..16; 1: one-step rows, as without it)
     DDPG_DISTRIBUTIONAL = False         # USE_DDPG only: the critic predicts a categorical distribution over DDPG_ATOMS fixed returns,
@@ -254,9 +264,10 @@ def resolve_action_space(explicit=()):
     Config.DISCRATE_INPUT = not Config.CONTINUOUS_INPUT
 
 
-def resolve_ddpg(explicit=()):
+def resolve_ddpg(explicit=(), num_actions=None):
     """What USE_DDPG implies (the reference's Config.py:160-178) and what it cannot be combined with here.  Call after
-    resolve_action_space.  Without USE_DDPG nothing changes."""
+    resolve_action_space.  Without USE_DDPG nothing changes.  num_actions: the game's, where the caller knows it (DDPG_SOFT's
+    head limit; NetworkDDPG.Network checks it too)."""
     if not Config.USE_DDPG:
         if Config.PRIORITIZED_REPLAY:
             raise ValueError("PRIORITIZED_REPLAY needs USE_DDPG: only the DDPG handle keeps a replay memory")
@@ -266,6 +277,8 @@ def resolve_ddpg(explicit=()):
             raise ValueError("DDPG_DISTRIBUTIONAL needs USE_DDPG: the distributional critic is the DDPG handle's")
         if Config.DDPG_POPART:
             raise ValueError("DDPG_POPART needs USE_DDPG: the normalised critic is the DDPG handle's")
+        if Config.DDPG_SOFT:
+            raise ValueError("DDPG_SOFT needs USE_DDPG: the soft actor-critic is the DDPG handle's")
         _resolve_nstep()
         return
     if not Config.CONTINUOUS_INPUT:
@@ -337,9 +350,30 @@ def resolve_ddpg(explicit=()):
             raise ValueError("DDPG_POPART_BETA=%r outside [0, 1]" % (beta,))
         if isinstance(lo, bool) or isinstance(hi, bool) or not 0.0 < lo < hi < float("inf"):
             raise ValueError("DDPG_POPART_SIGMA_MIN / _MAX = %r / %r: two finite numbers, 0 < the first < the second" % (lo, hi))
+    if Config.DDPG_SOFT:
+        _resolve_soft(num_actions)
     _resolve_nstep()
     Config.USE_REPLAY_MEMORY = True
     Config.DISCOUNTING = False
+
+
+def _resolve_soft(num_actions=None):
+    """DDPG_SOFT on USE_DDPG.  num_actions: the game's, where the caller knows it (NetworkDDPG.Network does)."""
+    if not Config.DDPG_TWIN:
+        raise ValueError("DDPG_SOFT needs DDPG_TWIN: the soft actor-critic trains both critics on the smaller target value")
+    if num_actions is not None and int(num_actions) > 16:
+        raise ValueError("DDPG_SOFT with num_actions=%d is not supported: the Gaussian head has 2 x num_actions <= 32 columns"
+                         % int(num_actions))
+    alpha, rate, ent = Config.DDPG_SOFT_ALPHA, Config.DDPG_SOFT_ALPHA_LR, Config.DDPG_SOFT_TARGET_ENTROPY
+    lo, hi = Config.DDPG_SOFT_LOG_STD_MIN, Config.DDPG_SOFT_LOG_STD_MAX
+    if not _finite_number(alpha) or not alpha > 0:
+        raise ValueError("DDPG_SOFT_ALPHA=%r: a finite number above 0" % (alpha,))
+    if not _finite_number(rate) or rate < 0:
+        raise ValueError("DDPG_SOFT_ALPHA_LR=%r: a finite factor >= 0" % (rate,))
+    if ent is not None and not _finite_number(ent):
+        raise ValueError("DDPG_SOFT_TARGET_ENTROPY=%r: None (-num_actions) or a finite number" % (ent,))
+    if not _finite_number(lo) or not _finite_number(hi) or not lo < hi:
+        raise ValueError("DDPG_SOFT_LOG_STD_MIN / _MAX = %r / %r: two finite numbers, the first the smaller" % (lo, hi))
 
 
 def _resolve_nstep():
@@ -399,6 +433,9 @@ def _resolve_device_ddpg(n, pendulum):
     if mode == 'per_env' and not Config.add_OUnoise:
         raise ValueError("DEVICE_DDPG_NOISE='per_env' with add_OUnoise=%r is not supported: there is no noise process to give "
                          "each environment" % (Config.add_OUnoise,))
+    if mode == 'per_env' and Config.DDPG_SOFT:
+        raise ValueError("DEVICE_DDPG_NOISE='per_env' with DDPG_SOFT is not supported: the policy's own sampling is already per "
+                         "environment")
     if not isinstance(Config.DEVICE_DDPG_NOISE_RESET, bool):
         raise ValueError("DEVICE_DDPG_NOISE_RESET=%r: True or False" % (Config.DEVICE_DDPG_NOISE_RESET,))
     _resolve_device_ddpg_task()

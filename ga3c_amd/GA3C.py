@@ -15,6 +15,8 @@ def apply_argv(argv):
         current = getattr(Config, key)
         if isinstance(current, tuple):      # DENSE_LAYERS=64,64 -> (64, 64); tuple("64,64") would give characters
             setattr(Config, key, tuple(type(current[0])(v) for v in value.split(',') if v.strip()))
+        elif current is None:               # DDPG_SOFT_TARGET_ENTROPY: None stands for a number derived elsewhere
+            setattr(Config, key, float(value))
         else:
             setattr(Config, key, type(current)(value))
         given.add(key)

@@ -18,6 +18,9 @@ kernel (envnoise_create).  Under Config.DDPG_POPART the critic reg
 two more variables, critic_popart/mu and /nu, the statistics that its output layer is rescaled with (popart_create).
 Under a non-default Config.DEVICE_DDPG_ACTION_BOUND, _TIME_LIMIT, _RESET_OBSERVATION, _REWARD_SCALE or _REWARD_OFFSET the device
 actors and the evaluation episodes step that task in the fork's wrapper's place (task_create).
+Under Config.DDPG_SOFT (with DDPG_TWIN) the actor's head is [300, 2A], a mean and a log standard deviation per action, every
+prediction with the handle's own noise is tanh of a Gaussian sample drawn in the kernel, and the handle has one more variable,
+actor_soft/log_alpha, the learned temperature (soft_create).
 """
 import ctypes as C
 import os
@@ -25,7 +28,7 @@ import threading
 
 import numpy as np
 
-from Config import Config, DEVICE_DDPG_TASK_DEFAULTS
+from Config import Config, DEVICE_DDPG_TASK_DEFAULTS, _resolve_soft
 from NetworkVP import _device_ordinal
 from NetworkVP_vecnet import DeviceActors, NativeHandle
 import _native as nat
@@ -41,6 +44,7 @@ VALUE, TARGET, SLOT_A, SLOT_B, GRAD = range(5)
 
 
 POPART_STATS = ("critic_popart/mu", "critic_popart/nu")      # of a handle with PopArt: not trainable, behind the 26
+SOFT_LOG_ALPHA = "actor_soft/log_alpha"                      # of a handle with the soft actor-critic: trainable, behind the 38
 
 # The task of the device actors: (bound, time_limit, reset_observation, reward_scale, reward_offset).  FORK_TASK is
 # EnvironmentPend.Environment's, what a handle without a task steps.
@@ -55,8 +59,12 @@ def config_task():
     return tuple(getattr(Config, key) for key, _ in DEVICE_DDPG_TASK_DEFAULTS)
 
 
-def param_shapes(state_dim, num_actions, twin=False, atoms=None, popart=False):
+def param_shapes(state_dim, num_actions, twin=False, atoms=None, popart=False, soft=False):
     S, A = int(state_dim), int(num_actions)
+    if soft:                                # the Gaussian head and the temperature (on a twin handle)
+        shapes = param_shapes(S, A, twin)
+        shapes.update({"actor_output/W": (H2, 2 * A), "actor_output/b": (2 * A,), SOFT_LOG_ALPHA: (1,)})
+        return shapes
     if popart:                              # + the two statistics (never with a twin or an atom head)
         shapes = param_shapes(S, A)
         shapes.update({k: (1,) for k in POPART_STATS})
@@ -98,16 +106,16 @@ def _draw(rng, name, shape):
     return np.zeros(shape)
 
 
-def initial_arena(state_dim, num_actions, seed, tau=None, twin=False, atoms=None):
+def initial_arena(state_dim, num_actions, seed, tau=None, twin=False, atoms=None, soft=False):
     """-> (online, target): dicts of f32 arrays for the 20 trainable variables, drawn from one PCG64(seed) stream in variable
     order, the online networks first (actor, critic), then independently drawn targets in the same order.  The reference does
     not copy the online weights: it runs ONE soft update on those targets (NetworkDDPG.py:17-21), restated here.
     twin: critic 2's ten as well, drawn after all of those from the same stream (online, then targets), so that the 20 are
     what they are without it.  atoms: critic_output/W and /b at a distributional critic's shapes, drawn in their place of
-    the stream."""
+    the stream.  soft: actor_output/W and /b at the Gaussian head's shapes, drawn by the rule of that variable in its place."""
     tau = Config.tau if tau is None else tau
     rng = np.random.Generator(np.random.PCG64(seed))
-    shapes = param_shapes(state_dim, num_actions, twin, atoms)
+    shapes = param_shapes(state_dim, num_actions, twin, atoms, soft=soft)
     online, target = {}, {}
     for names in (TRAINABLE,) + ((TWIN_TRAINABLE,) if twin else ()):
         online.update({k: _draw(rng, k, shapes[k]).astype(np.float32) for k in names})
@@ -118,6 +126,7 @@ def initial_arena(state_dim, num_actions, seed, tau=None, twin=False, atoms=None
 
 class Network(DeviceActors, NativeHandle):
     PREFIX = "ga3c_ddpg"
+    soft = False                            # the handle has the soft actor-critic (set by __init__ from Config.DDPG_SOFT)
 
     def __init__(self, device, model_name, num_actions, state_dim, max_batch=None, predict_lanes=None, replay_capacity=None):
         self.device = device
@@ -148,7 +157,7 @@ class Network(DeviceActors, NativeHandle):
                      | (nat.DDPG_LOSS_PAIRED if Config.DDPG_CRITIC_LOSS == 'paired' else 0)
                      | (nat.DDPG_GRAD_CLIP if Config.USE_GRAD_CLIP else 0)
                      | (0 if Config.RMSPROP else nat.DDPG_CRITIC_ADAM)
-                     | (nat.DDPG_OU_NOISE if Config.add_OUnoise else 0))
+                     | (nat.DDPG_OU_NOISE if Config.add_OUnoise and not Config.DDPG_SOFT else 0))
         cfg.tau, cfg.gamma = Config.tau, Config.gamma
         cfg.actor_lr, cfg.critic_lr = Config.actor_lr, Config.critic_lr
         cfg.rmsprop_decay = Config.RMSPROP_DECAY
@@ -165,11 +174,18 @@ class Network(DeviceActors, NativeHandle):
         if self.twin:                           # before the initial values: it adds critic 2's variables
             self._call("twin_create", int(Config.DDPG_POLICY_DELAY), float(Config.DDPG_TARGET_NOISE),
                        float(Config.DDPG_TARGET_NOISE_CLIP), int(Config.RANDOM_SEED))
+        self.soft = bool(Config.DDPG_SOFT)
+        if self.soft:                           # after the twin, before the initial values: it widens the actor's head
+            _resolve_soft(self.num_actions)
+            ent = Config.DDPG_SOFT_TARGET_ENTROPY
+            self._call("soft_create", float(np.log(Config.DDPG_SOFT_ALPHA)), float(Config.DDPG_SOFT_ALPHA_LR),
+                       float(-self.num_actions if ent is None else ent), float(Config.DDPG_SOFT_LOG_STD_MIN),
+                       float(Config.DDPG_SOFT_LOG_STD_MAX), int(Config.RANDOM_SEED + 3))
         self.dist = bool(Config.DDPG_DISTRIBUTIONAL)
         if self.dist:                           # before the initial values: it reshapes the critic's head
             self._call("dist_create", int(Config.DDPG_ATOMS), float(Config.DDPG_V_MIN), float(Config.DDPG_V_MAX))
         online, target = initial_arena(self.S, self.num_actions, Config.RANDOM_SEED, twin=self.twin,
-                                       atoms=int(Config.DDPG_ATOMS) if self.dist else None)
+                                       atoms=int(Config.DDPG_ATOMS) if self.dist else None, soft=self.soft)
         for k in TRAINABLE + (TWIN_TRAINABLE if self.twin else ()):
             self.set_variable_value(k, online[k], VALUE)
             self.set_variable_value(k, target[k], TARGET)
@@ -360,6 +376,22 @@ class Network(DeviceActors, NativeHandle):
         self._call("dist_info", C.byref(n), C.byref(lo), C.byref(hi))
         return n.value, lo.value, hi.value
 
+    # ---- soft actor-critic (Config.DDPG_SOFT) -------------------------------------------------
+    def soft_info(self):
+        """-> (log_alpha, target_entropy, mean_logp, predictions): the temperature's logarithm as it stands, the entropy it is
+        steered to, the mean log-density of the last policy step's samples, and the count of predictions that drew their own noise."""
+        la, ent, lp, n = C.c_float(), C.c_float(), C.c_float(), C.c_int64()
+        self._call("soft_info", C.byref(la), C.byref(ent), C.byref(lp), C.byref(n))
+        return la.value, ent.value, lp.value, n.value
+
+    def log_soft(self, training_step):
+        """training_step, alpha, mean_logp appended to logs/<model>/soft.csv, beside eval.csv."""
+        la, _, lp, _ = self.soft_info()
+        os.makedirs("logs/%s" % self.model_name, exist_ok=True)
+        with self._log_lock:
+            with open("logs/%s/soft.csv" % self.model_name, "a") as f:
+                f.write("%d,%.9g,%.9g\n" % (training_step, float(np.exp(la)), lp))
+
     # ---- PopArt (Config.DDPG_POPART, DESIGN.md 8s) ----------------------------------------------------------
     def popart_info(self):
         """-> (beta, mu, nu, sigma): the step of the statistics, the targets' running first and second moment, and the scale
@@ -427,6 +459,8 @@ class Network(DeviceActors, NativeHandle):
     # too; the handle's own ACTOR_FIELDS / ACTOR_SCALARS list them while it has it: without it the library knows no such names
     NOISE_FIELDS = {"noise_x": (np.float32, "A"), "noise_n": (np.float32, "A")}
     NOISE_SCALARS = {"noise_count": np.int64}
+    # ... and on a handle with the soft actor-critic the actors' last draws
+    SOFT_FIELDS = {"soft_eps": (np.float32, "A")}
 
     def actors_create(self, n, time_max=None, discount=None, seed=None, updates=None, batch=None, draw_seed=None, noise=None,
                       noise_seed=None, noise_reset=None):
@@ -441,6 +475,8 @@ class Network(DeviceActors, NativeHandle):
         self.num_actors = int(n)
         self.actors_set("batch", min(self.max_batch, int(Config.TRAINING_MIN_BATCH_SIZE if batch is None else batch)))
         self.actors_set("draw_seed", Config.REPLAY_BUFFER_RANDOM_SEED if draw_seed is None else draw_seed)
+        if self.soft:
+            self.ACTOR_FIELDS = dict(type(self).ACTOR_FIELDS, **self.SOFT_FIELDS)
         if noise == 'per_env':
             self.envnoise_create(noise_seed, noise_reset)
 
@@ -548,3 +584,5 @@ class Network(DeviceActors, NativeHandle):
                 f.write("%d,%.8g,%.8g,%.8g\n" % (training_step, self.learning_rate, q_max, q_avg))
         if self.popart:                         # scalars.csv keeps its four columns; Q above is in return units
             self.log_popart(training_step)
+        if self.soft:
+            self.log_soft(training_step)

@@ -203,6 +203,10 @@ HIP_SIGNATURES = {
     # twin critics of a DDPG handle (Config.DDPG_TWIN), include/ga3c_abi.h
     "ga3c_ddpg_twin_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int64]),
     "ga3c_ddpg_twin_destroy": (C.c_int, [C.c_void_p]),
+    # soft actor-critic on a twin DDPG handle (Config.DDPG_SOFT), include/ga3c_abi.h: ga3c_ddpg_soft_*
+    "ga3c_ddpg_soft_create": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64]),
+    "ga3c_ddpg_soft_destroy": (C.c_int, [C.c_void_p]),
+    "ga3c_ddpg_soft_info": (C.c_int, [C.c_void_p, f32p, f32p, f32p, i64p]),
     # device actors of a DDPG handle (Config.DEVICE_DDPG), include/ga3c_abi.h: ga3c_ddpg_actors_*
     "ga3c_ddpg_actors_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),
     "ga3c_ddpg_actors_destroy": (C.c_int, [C.c_void_p]),

@@ -69,6 +69,16 @@
 //                        kernels above with a PendulumTask from the arguments where they have ForkTask, the fork's wrapper as
 //                        constants: clip or wrap, the time limit as a truncation, the observation of the reset state, the
 //                        reward's scale and offset.  Launched in their places by a handle with a task; the launch counts stay.
+// Soft actor-critic (ga3c_ddpg_soft_create, Config.DDPG_SOFT; tests/sac_oracle.py is the same statement), on a twin
+// handle whose actor head is [300, 2A]:
+//   ddpg_soft_target_kernel   the ONLINE actor's sample a2, logp2 at s2 (soft_actor_fwd: actor_fwd with the raw head), both target
+//                             critics there, y from min q' - alpha logp2
+//   ddpg_soft_actor_kernel    the sample a, logp at s, both updated critics one after the other in the same buffers, per row the
+//                             smaller one's dq/da, the gradient of (1/B) sum (alpha logp - q) through the sample, the actor's deltas
+//   ddpg_soft_wgrad_kernel    the actor's ddpg_wgrad_kernel<1, true> with log_alpha's Adam step riding in it
+//   ddpg_soft_predict_kernel  tanh(mu), or the sample under the caller's eps or the counter draws of the row's stream
+//   ddpg_soft_eval_kernel<Env, Task>   ddpg_eval_kernel / ddpg_eval_task_kernel under tanh(mu)
+// The critics' kernels are the twin's and the launch counts of a step are the twin's.
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -126,12 +136,14 @@ struct Layout {
 };
 
 // N: the outputs of the critic's head, 1 or the atoms of a distributional critic
-inline Layout make_layout(int S, int A, int N = 1) {
+// head: the columns of the actor's head, A, or 2 A for the Gaussian head of a soft handle (0: A)
+inline Layout make_layout(int S, int A, int N = 1, int head = 0) {
   Layout L;
   L.S = S;
   L.A = A;
+  const int HD = head ? head : A;
   const int r[NVARS] = {S, 0, 0, 0, H1, 0, 0, 0, H2, 0, S, 0, 0, 0, H1, 0, A, 0, H2, 0, 0, 0, 0, 0, 0, 0};
-  const int c[NVARS] = {H1, H1, H1, H1, H2, H2, H2, H2, A, A, H1, H1, H1, H1, H2, H2, H2, H2, N, N, H1, H1, H2, H2, H1, H1};
+  const int c[NVARS] = {H1, H1, H1, H1, H2, H2, H2, H2, HD, HD, H1, H1, H1, H1, H2, H2, H2, H2, N, N, H1, H1, H2, H2, H1, H1};
   int64_t o = 0;
   for (int v = 0; v < NVARS; ++v) {
     L.rows[v] = r[v];
@@ -1513,6 +1525,373 @@ __global__ __launch_bounds__(THREADS) void ddpg_eval_task_kernel(Layout L, const
   }
 }
 
+// ------------------------------------------------------------------ soft actor-critic
+constexpr int SOFT_MAX_A = MAX_A / 2;        // the head's LDS arrays hold MAX_A rows and the head has 2 A
+constexpr float SOFT_LN2 = 0.6931471805599453f, SOFT_HALF_LN_2PI = 0.9189385332046727f;
+
+// What every soft kernel reads of the handle's state, by value.
+struct SoftCfg {
+  float ls_min, ls_max;
+  int64_t la;                // where log_alpha lies in every arena
+  uint64_t seed;
+};
+
+// The rows a soft step writes beside Work's: eps2, a2, mu, ls, eps, u [B,A]; logp2, vt, logp, q1, q2 [B]; stat: {mean logp}.
+struct SoftRows {
+  float *eps2, *a2, *logp2, *vt;
+  float *mu, *ls, *eps, *u, *logp, *q1, *q2;
+  float* stat;
+};
+
+// 8n's Box-Muller draw j of `stream`, unclipped: n = sqrt(-2 ln u1) cos(2 pi u2) in f64 on uniforms 2j and 2j + 1, then f32
+__device__ __forceinline__ float soft_normal(uint64_t seed, uint64_t stream, uint64_t j) {
+  const double u1 = 1.0 - ga3c_uniform::actor_uniform(seed, stream, 2 * j);
+  const double u2 = ga3c_uniform::actor_uniform(seed, stream, 2 * j + 1);
+  return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+}
+
+// actor_fwd with the raw head of a soft handle: raw [2A][16] <- a2 W_o + b_o, W_o [300, 2A]; no tanh, nothing of the head kept.
+__device__ void soft_actor_fwd(const Layout& L, const float* __restrict__ th, const float* xin, float* bufA, float* bufB, float* raw,
+                               ActorKeep kp, int row0, int nrows) {
+  dense_fwd<THREADS>(th + L.off[A_W1], th + L.off[A_B1], L.S, H1, xin, nullptr, 0, nullptr, [&](int j, int r, float h) {
+    float n;
+    const float xh = bn_apply(th, L, A_MM1, A_MV1, A_BE1, A_GA1, j, h, &n);
+    const float a = fmaxf(n, 0.f);
+    bufA[j * TILE + r] = a;
+    if (kp.a1 && r < nrows) {
+      kp.xh1[(size_t)(row0 + r) * H1 + j] = xh;
+      kp.a1[(size_t)(row0 + r) * H1 + j] = a;
+    }
+  });
+  dense_fwd<THREADS>(th + L.off[A_W2], th + L.off[A_B2], H1, H2, bufA, nullptr, 0, nullptr, [&](int j, int r, float h) {
+    float n;
+    const float xh = bn_apply(th, L, A_MM2, A_MV2, A_BE2, A_GA2, j, h, &n);
+    const float a = fmaxf(n, 0.f);
+    bufB[j * TILE + r] = a;
+    if (kp.a2 && r < nrows) {
+      kp.xh2[(size_t)(row0 + r) * H2 + j] = xh;
+      kp.a2[(size_t)(row0 + r) * H2 + j] = a;
+    }
+  });
+  dense_fwd<THREADS>(th + L.off[A_WO], th + L.off[A_BO], H2, L.cols[A_WO], bufB, nullptr, 0, nullptr,
+                     [&](int j, int r, float h) { raw[j * TILE + r] = h; });
+}
+
+// The sample of the tile from raw [2A][16] and eps [A][16]: ls = clamp(raw[A + i]), sigma = exp(ls), u = fmaf(sigma, eps, mu),
+// act[i][r] = tanh(u); sg (may be null) <- sigma, ub <- u; then, by the thread of row r, in i order,
+// logp = sum_i (((-0.5 eps^2 - ls) - ln sqrt(2 pi)) - 2 ((ln 2 - |u|) - log1p(exp(-2 |u|)))): ln(1 - tanh^2 u) from u itself, which
+// stays finite where tanhf rounds to 1.  Ends in a barrier.
+__device__ __forceinline__ void soft_sample(int A, const SoftCfg& c, float* raw, const float* eps, float* act, float* ub, float* sg,
+                                            float* lp) {
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const float ls = fminf(fmaxf(raw[A * TILE + e], c.ls_min), c.ls_max);
+    const float sigma = expf(ls);
+    const float u = fmaf(sigma, eps[e], raw[e]);
+    if (sg) sg[e] = sigma;
+    ub[e] = u;
+    act[e] = tanhf(u);
+  }
+  __syncthreads();
+  if (threadIdx.x < TILE) {
+    const int r = threadIdx.x;
+    float s = 0.f;
+    for (int i = 0; i < A; ++i) {
+      const float n = eps[i * TILE + r], au = fabsf(ub[i * TILE + r]);
+      const float ls = fminf(fmaxf(raw[(A + i) * TILE + r], c.ls_min), c.ls_max);
+      const float l1 = 2.0f * ((SOFT_LN2 - au) - log1pf(expf(-2.0f * au)));
+      s += ((-0.5f * n * n - ls) - SOFT_HALF_LN_2PI) - l1;
+    }
+    lp[r] = s;
+  }
+  __syncthreads();
+}
+
+struct SoftTarget {
+  float *y, *qt, *qt1, *qt2;
+  uint64_t number;           // the draws' stream: 2 t
+};
+
+// Steps 1-2 of a soft step.  The ONLINE actor (th) samples a2, logp2 at s2 on stream `number`; both target critics (thT) read a2,
+// one after the other in the same buffers; q' = min, v' = q' - alpha logp2 with alpha = exp(log_alpha) as it stands, and
+// y = r on a done row or without `future`, else fmaf(g, v', r).  "qt" stays min q'.
+__global__ __launch_bounds__(THREADS) void ddpg_soft_target_kernel(PerCritic<Layout, 2> L, const float* __restrict__ th,
+                                                                   const float* __restrict__ thT, Rows src, int B, float gamma,
+                                                                   int future, SoftCfg cfg, SoftTarget t, SoftRows sr,
+                                                                   const float* __restrict__ disc, float* __restrict__ used) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float raw[MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float act[SOFT_MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float eps[SOFT_MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float ub[SOFT_MAX_A * TILE];
+  __shared__ float lp[TILE];
+  __shared__ float qv[2][TILE];
+  const int S = L.v[0].S, A = L.v[0].A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  if (future) {
+    load_rows(src, S + A + 2, S, xin, row0, nrows, nullptr);
+    for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+      const int i = e / TILE, r = e % TILE;
+      eps[e] = soft_normal(cfg.seed, t.number, (uint64_t)(row0 + r) * (uint64_t)A + (uint64_t)i);
+    }
+    __syncthreads();
+    soft_actor_fwd(L.v[0], th, xin, bufA, bufB, raw, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    soft_sample(A, cfg, raw, eps, act, ub, nullptr, lp);
+    for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+      const int i = e / TILE, r = e % TILE;
+      if (r < nrows) {
+        sr.eps2[(size_t)(row0 + r) * A + i] = eps[e];
+        sr.a2[(size_t)(row0 + r) * A + i] = act[e];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) critic_fwd(L.v[c], thT, xin, act, bufA, bufB, qv[c], CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+  }
+  if (threadIdx.x < nrows) {
+    const int r = threadIdx.x;
+    const int64_t slot = src.idx ? src.idx[row0 + r] : row0 + r;
+    const float rew = src.base[slot * src.rowf + S + A], done = src.base[slot * src.rowf + S + A + 1];
+    const float g = row_discount(disc, used, slot, row0 + r, gamma);
+    const float q1 = future ? qv[0][r] : 0.f, q2 = future ? qv[1][r] : 0.f;
+    const float qt = fminf(q1, q2);
+    float y = rew;
+    if (future) {
+      const float alpha = expf(th[cfg.la]);
+      const float vt = qt - alpha * lp[r];
+      if (done == 0.f) y = fmaf(g, vt, rew);
+      sr.logp2[row0 + r] = lp[r];
+      sr.vt[row0 + r] = vt;
+    }
+    t.y[row0 + r] = y;
+    t.qt[row0 + r] = qt;
+    t.qt1[row0 + r] = q1;
+    t.qt2[row0 + r] = q2;
+  }
+}
+
+// Steps 4-5 of a soft step, on policy steps.  The actor samples a, logp at s on stream `number` (2 t + 1); the two UPDATED critics
+// are evaluated one after the other in the same buffers, each leaving its q and its dq/da [A][16]; per row the smaller q selects
+// its critic, critic 1 on a tie, and with g its dq/da, c = 1 / B:
+//   du_i = c (2 alpha a_i - g_i (1 - a_i^2)), 1 - a^2 from u as actor_fwd's dact;  dmu_i = du_i;
+//   dls_i = du_i sigma_i eps_i - c alpha where the raw ls lies inside (ls_min, ls_max), else 0.
+// "do" = dmu | dls [B, 2A] goes back through the head and the trunk as actor_rows does it.
+__global__ __launch_bounds__(THREADS) void ddpg_soft_actor_kernel(PerCritic<Layout, 2> L, const float* __restrict__ th, Rows src, int B,
+                                                                  SoftCfg cfg, uint64_t number, Work w, SoftRows sr) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float raw[MAX_A * TILE];          // the raw head; later the delta at it
+  __shared__ __attribute__((aligned(16))) float act[SOFT_MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float eps[SOFT_MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float ub[SOFT_MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float sg[SOFT_MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float gq[2][SOFT_MAX_A * TILE];   // each critic's dq/da
+  __shared__ float lp[TILE];
+  __shared__ float qv[2][TILE];
+  const Layout& LA = L.v[0];
+  const int S = LA.S, A = LA.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  load_rows(src, 0, S, xin, row0, nrows, nullptr);
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const int i = e / TILE, r = e % TILE;
+    eps[e] = soft_normal(cfg.seed, number, (uint64_t)(row0 + r) * (uint64_t)A + (uint64_t)i);
+  }
+  __syncthreads();
+  soft_actor_fwd(LA, th, xin, bufA, bufB, raw, ActorKeep{w.a_xh1, w.a_a1, w.a_xh2, w.a_a2, nullptr}, row0, nrows);
+  // which raw ls lie inside the clamp, before soft_sample reads them: bit i of row r's mask
+  __shared__ unsigned inside[TILE];
+  if (threadIdx.x < TILE) {
+    unsigned mask = 0;
+    for (int i = 0; i < A; ++i) {
+      const float o = raw[(A + i) * TILE + threadIdx.x];
+      if (o > cfg.ls_min && o < cfg.ls_max) mask |= 1u << i;
+    }
+    inside[threadIdx.x] = mask;
+  }
+  soft_sample(A, cfg, raw, eps, act, ub, sg, lp);
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const int i = e / TILE, r = e % TILE;
+    if (r < nrows) {
+      const size_t at = (size_t)(row0 + r) * A + i;
+      sr.mu[at] = raw[e];
+      sr.ls[at] = fminf(fmaxf(raw[A * TILE + e], cfg.ls_min), cfg.ls_max);
+      sr.eps[at] = eps[e];
+      sr.u[at] = ub[e];
+      w.a_noisy[at] = act[e];
+    }
+  }
+  if (threadIdx.x < nrows) sr.logp[row0 + threadIdx.x] = lp[threadIdx.x];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const Layout& LC = L.v[c];
+    critic_fwd(LC, th, xin, act, bufA, bufB, qv[c], CriticKeep{nullptr, nullptr, nullptr}, row0, nrows);
+    const float* __restrict__ wo = th + LC.off[C_WO];
+    for (int e = threadIdx.x; e < H2 * TILE; e += THREADS) bufB[e] = bufB[e] > 0.f ? wo[e / TILE] : 0.f;
+    __syncthreads();
+    float* gc = gq[c];
+    dense_bwd(th + LC.off[C_WN], A, H2, bufB, [&](int i, int r, float g) { gc[i * TILE + r] = g; });
+  }
+  const float alpha = expf(th[cfg.la]), cB = 1.0f / (float)B;
+  if (threadIdx.x < nrows) {
+    sr.q1[row0 + threadIdx.x] = qv[0][threadIdx.x];
+    sr.q2[row0 + threadIdx.x] = qv[1][threadIdx.x];
+  }
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const int i = e / TILE, r = e % TILE;
+    const float g = qv[1][r] < qv[0][r] ? gq[1][e] : gq[0][e];
+    const float ex = expf(-2.0f * fabsf(ub[e]));
+    const float dact = 4.0f * ex / ((1.0f + ex) * (1.0f + ex));
+    float du = 0.f, dl = 0.f;
+    if (r < nrows) {
+      du = cB * (2.0f * alpha * act[e] - g * dact);
+      if ((inside[r] >> i) & 1u) dl = du * sg[e] * eps[e] - cB * alpha;
+      const size_t at = (size_t)(row0 + r) * (2 * A);
+      w.g[(size_t)(row0 + r) * A + i] = g;
+      w.dout[at + i] = du;
+      w.dout[at + A + i] = dl;
+    }
+    raw[e] = du;
+    raw[A * TILE + e] = dl;
+  }
+  __syncthreads();
+  dense_bwd(th + LA.off[A_WO], H2, 2 * A, raw, [&](int k, int r, float s) {
+    float d = 0.f;
+    if (r < nrows) {
+      d = w.a_a2[(size_t)(row0 + r) * H2 + k] > 0.f ? s : 0.f;
+      w.a_dn2[(size_t)(row0 + r) * H2 + k] = d;
+    }
+    const float dh = d * bn_scale(th, LA, A_MV2, A_GA2, k);
+    bufB[k * TILE + r] = dh;
+    if (r < nrows) w.a_dh2[(size_t)(row0 + r) * H2 + k] = dh;
+  });
+  dense_bwd(th + LA.off[A_W2], H1, H2, bufB, [&](int k, int r, float s) {
+    if (r < nrows) {
+      const float d = w.a_a1[(size_t)(row0 + r) * H1 + k] > 0.f ? s : 0.f;
+      w.a_dn1[(size_t)(row0 + r) * H1 + k] = d;
+      w.a_dh1[(size_t)(row0 + r) * H1 + k] = d * bn_scale(th, LA, A_MV1, A_GA1, k);
+    }
+  });
+}
+
+// The temperature's step, by the one thread that calls it: mean logp over the rows in row order, the gradient of
+// -log_alpha (mean logp + target_entropy), and ApplyAdam on the arenas' element `la` at `lr` (the annealed rate x alpha_lr, bias
+// corrected at the actor's count).
+struct SoftAlpha {
+  const float* logp;
+  float* stat;
+  int64_t la;
+  float target_entropy, lr;
+};
+
+// The actor's ddpg_wgrad_kernel<1, true> of a soft policy step, the temperature's step riding in it as q_stats rides in the
+// critics': nothing later in the step reads alpha, and the next step's target kernel is a later launch.
+__global__ __launch_bounds__(THREADS) void ddpg_soft_wgrad_kernel(Layout L, GradSrc src, int B, Opt o, SoftAlpha sa) {
+  wgrad_element<true>(L, src, 0, NACTOR, B, o);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    float s = 0.f;
+    for (int r = 0; r < B; ++r) s += sa.logp[r];
+    const float mean = s / (float)B;
+    const float g = -(mean + sa.target_entropy);
+    sa.stat[0] = mean;
+    o.grad[sa.la] = g;
+    if (o.apply) {
+      float m = o.sa[sa.la], v = o.sb[sa.la];
+      m += (g - m) * ADAM_OMB1;
+      v += (g * g - v) * ADAM_OMB2;
+      o.sa[sa.la] = m;
+      o.sb[sa.la] = v;
+      o.theta[sa.la] -= sa.lr * m / (sqrtf(v) + ADAM_EPS);
+    }
+  }
+}
+
+// ddpg_predict_kernel for a soft handle.  mode GA3C_DDPG_NOISE_NONE: a = tanh(mu), no wrap.  GIVEN: eps = nz.v for every row.
+// OWN: row r's eps[i] is draw count A + i of stream r under `seed` (the handle's seed + 1).  a = tanh(fmaf(sigma, eps, mu)).
+// eps_out (may be null): the draws, [B][A].
+__global__ __launch_bounds__(THREADS) void ddpg_soft_predict_kernel(Layout L, const float* __restrict__ th, Input in, int B,
+                                                                    SoftCfg cfg, int mode, Noise nz, uint64_t seed, uint64_t count,
+                                                                    float* __restrict__ a_out, float* __restrict__ eps_out) {
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float raw[MAX_A * TILE];
+  const int A = L.A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, B - row0);
+  load_input_tile<THREADS, false>(in, L.S, row0, nrows, xin, nullptr);
+  __syncthreads();
+  soft_actor_fwd(L, th, xin, bufA, bufB, raw, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+  for (int e = threadIdx.x; e < A * TILE; e += THREADS) {
+    const int i = e / TILE, r = e % TILE;
+    if (r >= nrows) continue;
+    const size_t at = (size_t)(row0 + r) * A + i;
+    float u = raw[e];
+    if (mode != GA3C_DDPG_NOISE_NONE) {
+      const float n = mode == GA3C_DDPG_NOISE_GIVEN ? nz.v[i] : soft_normal(seed, (uint64_t)(row0 + r), count * (uint64_t)A + (uint64_t)i);
+      const float ls = fminf(fmaxf(raw[A * TILE + e], cfg.ls_min), cfg.ls_max);
+      u = fmaf(expf(ls), n, u);
+      if (eps_out) eps_out[at] = n;
+    }
+    a_out[at] = tanhf(u);
+  }
+}
+
+// ddpg_eval_kernel / ddpg_eval_task_kernel for a soft handle: the same episode under a = tanh(mu).  Task: ForkTask, or the handle's
+// PendulumTask.  (One template for both: these have no earlier listing to keep.)
+template <class Env, class Task>
+__global__ __launch_bounds__(THREADS) void ddpg_soft_eval_kernel(Layout L, const float* __restrict__ th, int n, int steps, Task task,
+                                                                 const double* __restrict__ start, double* __restrict__ total_out,
+                                                                 double* __restrict__ phys_out, EvalTrace tr) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
+  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
+  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
+  __shared__ __attribute__((aligned(16))) float raw[MAX_A * TILE];
+  constexpr int S = Env::S, P = Env::P, A = Env::A;
+  const int row0 = blockIdx.x * TILE, nrows = min(TILE, n - row0);
+  const int r = threadIdx.x;
+  const size_t i = (size_t)row0 + r;                 // the thread's environment, r < nrows
+  double s[P];
+  double total = 0.0;
+  int elapsed = 0;
+  float obs[S];
+  if (r < TILE) {
+    for (int k = 0; k < S; ++k) obs[k] = 0.f;
+    if (r < nrows) {
+      for (int k = 0; k < P; ++k) s[k] = start[i * P + k];
+      Env::observe(s, obs);
+    }
+    for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+  }
+  __syncthreads();
+  for (int t = 0; t < steps; ++t) {
+    // ends in a barrier: raw is whole, and no thread reads xin any more
+    soft_actor_fwd(L, th, xin, bufA, bufB, raw, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    if (r < nrows) {
+      float av[A];
+      for (int j = 0; j < A; ++j) av[j] = tanhf(raw[j * TILE + r]);
+      const size_t at = i * EVAL_MAX_STEPS + t;
+      if (tr.phys) {
+        for (int k = 0; k < P; ++k) tr.phys[at * P + k] = s[k];
+        for (int k = 0; k < S; ++k) tr.obs[at * S + k] = obs[k];
+        for (int j = 0; j < A; ++j) tr.action[at * A + j] = av[j];
+      }
+      double reward;
+      int done;
+      Env::step(s, av, task, &elapsed, &reward, &done);
+      total = total + reward;
+      Env::observe(s, obs);
+      for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+      if (tr.phys) tr.reward[at] = reward;
+    }
+    __syncthreads();                                 // the next step's actor reads these observations
+  }
+  if (r < nrows) {
+    total_out[i] = total;
+    for (int k = 0; k < P; ++k) phys_out[i * P + k] = s[k];
+  }
+}
+
 // ------------------------------------------------------------------ host side
 // The handle is a ga3c_vecnet::Core (ga3c_vecnet.hpp): stream, lanes, arenas, variables by name, checkpoint and registered
 // segment are the shared ones.  Its own: the train step, the replay ring, the noise.
@@ -1607,6 +1986,17 @@ struct Pop {
   float* work_base = nullptr;           // the row "yn" of the handle's work table
 };
 
+// The soft actor-critic of a handle (ga3c_ddpg_soft_create).  The handle's Layout has 2 A columns in the actor's head and the
+// arenas hold log_alpha behind the twin's 38 variables while it lives.
+struct Soft {
+  SoftCfg cfg{};                        // ls_min, ls_max, log_alpha's place, the seed
+  float alpha_lr = 0.f, target_entropy = 0.f;
+  std::atomic<int64_t> predictions{0};  // GA3C_DDPG_NOISE_OWN predictions served: the c of the next one's draws
+  float* work_base = nullptr;           // the rows of the handle's SoftRows and its "do" [B, 2A]
+  float* core_dout = nullptr;           // the handle's own "do" [B, A], back in place at destroy
+  float* act_eps = nullptr;             // [max_batch, A] the device actors' last draws
+};
+
 // Evaluation episodes of a handle (ga3c_ddpg_eval_create).  block: the device buffers below; h_counts: the n f64 totals of the
 // last run, pinned.  Read and written under train_mu.
 struct Eval : ga3c_actors::ActorsCore {
@@ -1650,6 +2040,8 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   bool has_task = false;          // false: the fork's task, and the actors' and the evaluator's kernels are the ones without
   PendulumTask task{};            // (ga3c_ddpg_task_create): by value to the task kernels
   DistRows dw{};                  // the distributional critic's rows, null without
+  Soft* soft = nullptr;           // null: the deterministic actor
+  SoftRows sw{};                  // its rows, null without
   std::vector<std::string> tnames;      // the target copies' names, by variable
 };
 
@@ -1659,9 +2051,10 @@ int tiles(int B) { return (B + TILE - 1) / TILE; }
 
 // The rows of the train workspace by the name ga3c_ddpg_fetch knows them under.  tag: W_TWIN rows exist while the handle has twin
 // critics, W_DIST rows while it has a distributional critic, W_POP rows while it has PopArt, each kind in a block of its own
-// (Twin::work_base, Dist::work_base, Pop::work_base);
+// (Twin::work_base, Dist::work_base, Pop::work_base), W_SOFT rows while it has the soft actor-critic (Soft::work_base), where
+// "do" is one of them, [B, 2A];
 // the others live as long as the handle (work_base).
-enum WorkTag { W_CORE, W_TWIN, W_DIST, W_POP };
+enum WorkTag { W_CORE, W_TWIN, W_DIST, W_POP, W_SOFT };
 struct WorkRow {
   const char* name;
   float** ptr;
@@ -1675,17 +2068,22 @@ std::vector<WorkRow> work_table(ga3c_ddpg* m) {
   CriticRows &c = w.c[0], &d = w.c[1];
   DistRows& z = m->dw;
   const size_t N = m->dist ? (size_t)m->dist->z.n : 0;
+  SoftRows& sr = m->sw;
+  const WorkRow dout = m->soft ? WorkRow{"do", &w.dout, 2 * A, W_SOFT} : WorkRow{"do", &w.dout, A, W_CORE};
   return {{"y", &w.y, 1, W_CORE},           {"qt", &w.qt, 1, W_CORE},         {"q", &c.q, 1, W_CORE},           {"dq", &c.dq, 1, W_CORE},
           {"c_x", &w.c_x, S, W_CORE},       {"c_a", &w.c_a, A, W_CORE},       {"c_xh1", &c.xh1, H1, W_CORE},    {"c_c1", &c.c1, H1, W_CORE},
           {"c_dn1", &c.dn1, H1, W_CORE},    {"c_dh1", &c.dh1, H1, W_CORE},    {"c_c2", &c.c2, H2, W_CORE},      {"c_dt", &c.dt, H2, W_CORE},
           {"a_xh1", &w.a_xh1, H1, W_CORE},  {"a_a1", &w.a_a1, H1, W_CORE},    {"a_dn1", &w.a_dn1, H1, W_CORE},  {"a_dh1", &w.a_dh1, H1, W_CORE},
           {"a_xh2", &w.a_xh2, H2, W_CORE},  {"a_a2", &w.a_a2, H2, W_CORE},    {"a_dn2", &w.a_dn2, H2, W_CORE},  {"a_dh2", &w.a_dh2, H2, W_CORE},
-          {"a_out", &w.a_out, A, W_CORE},   {"a_noisy", &w.a_noisy, A, W_CORE}, {"g", &w.g, A, W_CORE},         {"do", &w.dout, A, W_CORE},
+          {"a_out", &w.a_out, A, W_CORE},   {"a_noisy", &w.a_noisy, A, W_CORE}, {"g", &w.g, A, W_CORE},         dout,
           {"qt1", &w.qt1, 1, W_TWIN},        {"qt2", &w.qt2, 1, W_TWIN},        {"q2", &d.q, 1, W_TWIN},           {"dq2", &d.dq, 1, W_TWIN},
           {"t_eps", &w.t_eps, A, W_TWIN},    {"t_a", &w.t_a, A, W_TWIN},        {"c2_xh1", &d.xh1, H1, W_TWIN},    {"c2_c1", &d.c1, H1, W_TWIN},
           {"c2_dn1", &d.dn1, H1, W_TWIN},    {"c2_dh1", &d.dh1, H1, W_TWIN},    {"c2_c2", &d.c2, H2, W_TWIN},      {"c2_dt", &d.dt, H2, W_TWIN},
           {"d_pt", &z.pt, N, W_DIST},      {"d_m", &z.m, N, W_DIST},        {"d_p", &z.p, N, W_DIST},        {"d_dz", &z.dz, N, W_DIST},
-          {"d_ce", &z.ce, 1, W_DIST},      {"yn", &m->yn, 1, W_POP}};
+          {"d_ce", &z.ce, 1, W_DIST},      {"yn", &m->yn, 1, W_POP},
+          {"s_eps2", &sr.eps2, A, W_SOFT}, {"s_a2", &sr.a2, A, W_SOFT},     {"s_logp2", &sr.logp2, 1, W_SOFT}, {"s_vt", &sr.vt, 1, W_SOFT},
+          {"s_mu", &sr.mu, A, W_SOFT},     {"s_ls", &sr.ls, A, W_SOFT},     {"s_eps", &sr.eps, A, W_SOFT},   {"s_u", &sr.u, A, W_SOFT},
+          {"s_logp", &sr.logp, 1, W_SOFT}, {"s_q1", &sr.q1, 1, W_SOFT},     {"s_q2", &sr.q2, 1, W_SOFT}};
 }
 
 // One zeroed block for the table's rows of one tag; *end: the four floats behind them.
@@ -1721,8 +2119,8 @@ GradSrc grad_src(ga3c_ddpg* m, int c) {
   set(A_B2, nullptr, 0, w.a_dh2, H2, nullptr);
   set(A_BE2, nullptr, 0, w.a_dn2, H2, nullptr);
   set(A_GA2, nullptr, 0, w.a_dn2, H2, w.a_xh2);
-  set(A_WO, w.a_a2, H2, w.dout, A, nullptr);
-  set(A_BO, nullptr, 0, w.dout, A, nullptr);
+  set(A_WO, w.a_a2, H2, w.dout, m->L.cols[A_WO], nullptr);      // (2 A on a soft handle)
+  set(A_BO, nullptr, 0, w.dout, m->L.cols[A_WO], nullptr);
   set(C_W1, w.c_x, S, cr.dh1, H1, nullptr);
   set(C_B1, nullptr, 0, cr.dh1, H1, nullptr);
   set(C_BE1, nullptr, 0, cr.dn1, H1, nullptr);
@@ -1854,7 +2252,55 @@ int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise
   return GA3C_OK;
 }
 
+// The step of a handle with the soft actor-critic: enqueue_step_nc<2>'s rule and launch counts with the soft
+// target kernel in the target kernel's place and, on a policy step, the soft actor kernel and the actor's weight-gradient launch
+// that carries the temperature's step.  The critics' three kernels are the twin's.  The draws of step t are streams 2 t (target)
+// and 2 t + 1 (policy) of the soft seed; no noise argument is read.
+int enqueue_soft(ga3c_ddpg* m, const Rows& rows, int B, float lr, int stop_after, const float* per_w) {
+  const ga3c_ddpg_config& c = m->cfg;
+  const Work& w = m->w;
+  const Soft& so = *m->soft;
+  const int64_t t = m->step.load() + 1;
+  const int delay = m->twin->delay;
+  const bool policy = t % delay == 0, full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
+  PerCritic<Layout, 2> L;
+  PerCritic<GradSrc, 2> gs;
+  L.v[0] = m->L;
+  L.v[1] = m->twin->view;
+  gs.v[0] = grad_src(m, 0);
+  gs.v[1] = grad_src(m, 1);
+  const dim3 grid(tiles(B)), gridc(tiles(B), 2), block(THREADS);
+  const int future = (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0;
+  float* used = m->nstep ? m->nstep->used : nullptr;
+  hipLaunchKernelGGL(ddpg_soft_target_kernel, grid, block, 0, m->st, L, (const float*)m->arena[0], (const float*)m->arena[1], rows, B,
+                     c.gamma, future, so.cfg, SoftTarget{w.y, w.qt, w.qt1, w.qt2, (uint64_t)(2 * t)}, m->sw, row_discounts(m, rows),
+                     used);
+  hipLaunchKernelGGL(ddpg_critic_kernel<2>, gridc, block, 0, m->st, L, (const float*)m->arena[0], rows, B, 1, per_w, w);
+  const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
+  const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
+  const Opt oc = make_opt(m, false, lr, t, true, full && policy);
+  if (clip) {
+    hipLaunchKernelGGL((ddpg_wgrad_kernel<2, false>), dim3(cblocks, 2), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
+    hipLaunchKernelGGL(ddpg_update_kernel<2>, dim3(2 * NCRITIC), block, 0, m->st, L, oc);
+  } else {
+    hipLaunchKernelGGL((ddpg_wgrad_kernel<2, true>), dim3(cblocks, 2), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
+  }
+  if (stop_after >= 4 && policy) {
+    hipLaunchKernelGGL(ddpg_soft_actor_kernel, grid, block, 0, m->st, L, (const float*)m->arena[0], rows, B, so.cfg,
+                       (uint64_t)(2 * t + 1), w, m->sw);
+    const Opt oa = make_opt(m, true, lr, t / delay, full, full);
+    // the temperature's Adam: the actor's bias correction on alpha_lr x the rate (oa.lr is that correction on actor_lr x the rate)
+    const double tt = (double)(t / delay);
+    const float lra = (float)((double)so.alpha_lr * (double)lr * std::sqrt(1.0 - std::pow(ADAM_B2, tt)) / (1.0 - std::pow(ADAM_B1, tt)));
+    hipLaunchKernelGGL(ddpg_soft_wgrad_kernel, dim3(ablocks), block, 0, m->st, m->L, gs.v[0], B, oa,
+                       SoftAlpha{(const float*)m->sw.logp, m->sw.stat, so.cfg.la, so.target_entropy, lra});
+  }
+  HIPCHK(hipGetLastError());
+  return GA3C_OK;
+}
+
 int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w = nullptr) {
+  if (m->soft) return enqueue_soft(m, rows, B, lr, stop_after, per_w);
   return m->twin ? enqueue_step_nc<2>(m, rows, B, lr, nz, stop_after, per_w) : enqueue_step_nc<1>(m, rows, B, lr, nz, stop_after, per_w);
 }
 
@@ -1917,9 +2363,37 @@ int step_host(ga3c_ddpg* m, const float* s, const float* a, const float* r, cons
   return GA3C_OK;
 }
 
+// The launch arguments of a soft handle's prediction in `mode`: the caller's eps for GA3C_DDPG_NOISE_GIVEN, and for
+// GA3C_DDPG_NOISE_OWN the handle's prediction count, which this call advances by one.
+int soft_predict_args(ga3c_ddpg* m, int mode, const float* given, Noise* nz, uint64_t* count) {
+  memset(nz, 0, sizeof *nz);
+  *count = 0;
+  if (mode == GA3C_DDPG_NOISE_GIVEN) {
+    if (!given) return fail(GA3C_EINVAL, "GA3C_DDPG_NOISE_GIVEN without a noise vector");
+    memcpy(nz->v, given, sizeof(float) * m->L.A);
+  } else if (mode == GA3C_DDPG_NOISE_OWN) {
+    *count = (uint64_t)m->soft->predictions.fetch_add(1);
+  } else if (mode != GA3C_DDPG_NOISE_NONE) {
+    return fail(GA3C_EINVAL, "noise_mode %d not in [0,2]", mode);
+  }
+  return GA3C_OK;
+}
+
+void launch_soft_predict(ga3c_ddpg* m, const Input& in, int B, int mode, const Noise& nz, uint64_t count, float* a_out, float* eps_out) {
+  hipLaunchKernelGGL(ddpg_soft_predict_kernel, dim3(tiles(B)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in, B,
+                     m->soft->cfg, mode, nz, m->soft->cfg.seed + 1, count, a_out, eps_out);
+}
+
 int predict_begin(ga3c_ddpg* m, const float* x, const int64_t* off, int B, int mode, const float* noise, int* ticket) {
   CHK(vn::predict_check(m, off, B));
   Noise nz;
+  if (m->soft) {
+    uint64_t count;
+    CHK(soft_predict_args(m, mode, noise, &nz, &count));
+    return vn::predict_begin(m, x, off, B, ticket, [&](const Input& in, vn::PLane& P) {
+      launch_soft_predict(m, in, B, mode, nz, count, P.out[0].d, nullptr);
+    });
+  }
   CHK(make_noise(m, mode, noise, &nz));        // before a lane is taken: one step of the process per call, whatever the batch
   return vn::predict_begin(m, x, off, B, ticket, [&](const Input& in, vn::PLane& P) {
     hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(B)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in, B, nz,
@@ -1973,7 +2447,9 @@ void fill_vars(ga3c_ddpg* m) {
 }
 
 // variable i of the handle's table is trainable: the 20, and critic 2's ten of a twin handle (PopArt's two are not)
-bool trainable_var(const ga3c_ddpg* m, int i) { return i >= 0 && (i < NTRAIN || (m->twin && i >= NVARS && i < NVARS + NCRITIC)); }
+bool trainable_var(const ga3c_ddpg* m, int i) {
+  return i >= 0 && (i < NTRAIN || (m->twin && i >= NVARS && i < NVARS + NCRITIC) || (m->soft && i == NVARS + NTWIN));      // log_alpha
+}
 
 const char* const POP_VAR_NAMES[2] = {"critic_popart/mu", "critic_popart/nu"};
 
@@ -2073,6 +2549,82 @@ void dist_free(ga3c_ddpg* m) {
   m->dist = nullptr;
 }
 
+// critic 2's twelve variables at the table's end, read through the twin's view
+void add_twin_vars(ga3c_ddpg* m) {
+  const Layout& V = m->twin->view;
+  for (int i = 0; i < NCRITIC; ++i) add_var(m, V, NACTOR + i, TWIN_VAR_NAMES[i]);
+  add_var(m, V, C_MM1, TWIN_VAR_NAMES[NCRITIC]);
+  add_var(m, V, C_MV1, TWIN_VAR_NAMES[NCRITIC + 1]);
+  m->n = V.off[NVARS];
+}
+
+const char* const SOFT_VAR_NAME = "actor_soft/log_alpha";
+
+// The five arenas of a twin handle re-laid for an actor head of `head` columns (2 A: the Gaussian head; A: back), with log_alpha
+// behind the 38 variables when `with_alpha`.  Every other variable keeps its value, target copy, slots and gradient;
+// actor_output/W and /b, whose shapes change, are as ga3c_ddpg_create leaves variables: zero everywhere (the actor's slots are
+// Adam's).  log_alpha: `log_alpha` in the value and the target arena, zero slots and gradient.  The twin's view and the variable
+// table are remade.  Caller holds train_mu and mu.
+int relay_soft(ga3c_ddpg* m, int head, bool with_alpha, float log_alpha) {
+  const Layout L0 = m->L, L1 = make_layout(L0.S, L0.A, 1, head);
+  const Layout V0 = twin_view(L0), V1 = twin_view(L1);
+  const int64_t n0 = m->n, n1 = V1.off[NVARS] + (with_alpha ? 1 : 0);
+  float* laid[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto build = [&]() -> int {
+    HIPCHK(hipStreamSynchronize(m->st));           // a prediction in flight has finished before its arena is freed
+    std::vector<float> a0((size_t)n0), a1((size_t)n1);
+    for (int a = 0; a < m->narena; ++a) {
+      HIPCHK(hipMemcpy(a0.data(), m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToHost));
+      std::fill(a1.begin(), a1.end(), 0.f);
+      for (int v = 0; v < NVARS; ++v)
+        if (v != A_WO && v != A_BO) std::copy(a0.begin() + L0.off[v], a0.begin() + L0.off[v + 1], a1.begin() + L1.off[v]);
+      std::copy(a0.begin() + L0.off[NVARS], a0.begin() + V0.off[NVARS], a1.begin() + L1.off[NVARS]);      // critic 2's twelve
+      if (with_alpha && a <= 1) a1[(size_t)n1 - 1] = log_alpha;
+      CHK(vn::dalloc(&laid[a], (size_t)n1));
+      HIPCHK(hipMemcpy(laid[a], a1.data(), sizeof(float) * n1, hipMemcpyHostToDevice));
+    }
+    return GA3C_OK;
+  };
+  const int rc = build();
+  if (rc != GA3C_OK) {
+    for (float* g : laid) (void)hipFree(g);
+    (void)hipGetLastError();
+    return rc;
+  }
+  for (int a = 0; a < m->narena; ++a) {
+    (void)hipFree(m->arena[a]);
+    m->arena[a] = laid[a];
+  }
+  m->L = L1;
+  m->twin->view = V1;
+  m->vars.clear();
+  m->tnames.clear();
+  fill_vars(m);
+  add_twin_vars(m);
+  if (with_alpha) {                  // f32 (1,), trainable: value, target copy and Adam's two slots in the checkpoint
+    const std::string name(SOFT_VAR_NAME);
+    vn::Var var{name, n1 - 1, 1, 1, {1, 0}, {}};
+    var.ckpt = {{name + ":0", 0}, {target_name(name) + ":0", 1}, {name + "/Adam:0", 2}, {name + "/Adam_1:0", 3}};
+    m->vars.push_back(std::move(var));
+    m->tnames.push_back(target_name(name));
+  }
+  m->n = n1;
+  return GA3C_OK;
+}
+
+// The state and its rows; the arenas stay as they are laid (soft_destroy re-lays them first, ga3c_ddpg_destroy frees them).
+void soft_free(ga3c_ddpg* m) {
+  Soft* s = m->soft;
+  if (!s) return;
+  (void)hipFree(s->work_base);
+  (void)hipFree(s->act_eps);
+  (void)hipGetLastError();
+  m->sw = SoftRows{};
+  if (s->core_dout) m->w.dout = s->core_dout;
+  delete s;
+  m->soft = nullptr;
+}
+
 void dactors_free(ga3c_ddpg* m) {
   ga3c_actors::actors_free(m->actors);
   m->actors = nullptr;
@@ -2091,6 +2643,7 @@ void free_all(ga3c_ddpg* m) {
   dactors_free(m);
   eval_free(m);
   per_free(m);
+  soft_free(m);
   twin_free(m);
   pop_free(m);
   nstep_free(m);
@@ -2304,19 +2857,27 @@ int ga3c_ddpg_set_step(ga3c_ddpg* m, int64_t step) {      // Adam's t: never bel
   return vn::set_step(m, step);
 }
 
-// A distributional handle's file also holds "dist_support", f32 [2]: vmin, vmax (the atoms are critic_output/W's columns).
+// A distributional handle's file also holds "dist_support", f32 [2]: vmin, vmax (the atoms are critic_output/W's columns); a soft
+// handle's "soft_config", f32 [3]: target_entropy, ls_min, ls_max.
 int ga3c_ddpg_save(ga3c_ddpg* m, const char* path) {
   if (!m || !path) return fail(GA3C_EINVAL, "null argument");
-  if (!m->dist) return vn::save(m, path);
+  if (!m->dist && !m->soft) return vn::save(m, path);
   ga3c_ckpt::Arenas arena;
   CHK(vn::read_arenas(m, &arena));
   std::vector<ga3c_ckpt::Member> members = ga3c_ckpt::pack_members(m->vars, m->step.load(), arena);
-  const float support[2] = {m->dist->z.vmin, m->dist->z.vmax};
+  float extra[3];
   ga3c_ckpt::Member mb;
-  mb.name = "dist_support";
+  if (m->dist) {
+    extra[0] = m->dist->z.vmin; extra[1] = m->dist->z.vmax;
+    mb.name = "dist_support";
+    mb.shape = {2};
+  } else {
+    extra[0] = m->soft->target_entropy; extra[1] = m->soft->cfg.ls_min; extra[2] = m->soft->cfg.ls_max;
+    mb.name = "soft_config";
+    mb.shape = {3};
+  }
   mb.descr = "<f4";
-  mb.shape = {2};
-  mb.bytes.assign(reinterpret_cast<const uint8_t*>(support), reinterpret_cast<const uint8_t*>(support) + sizeof support);
+  mb.bytes.assign(reinterpret_cast<const uint8_t*>(extra), reinterpret_cast<const uint8_t*>(extra) + sizeof(float) * (m->dist ? 2 : 3));
   members.insert(members.begin() + 1, std::move(mb));        // beside "step"
   std::string err;
   if (!ga3c_ckpt::write_npz(path, members, &err)) return fail(GA3C_ESTATE, "%s", err.c_str());
@@ -2344,6 +2905,18 @@ int ga3c_ddpg_load(ga3c_ddpg* m, const char* path) {
     memcpy(v, sup->second.bytes.data(), sizeof v);
     if (v[0] != m->dist->z.vmin || v[1] != m->dist->z.vmax)
       return fail(GA3C_ESTATE, "%s: support [%g, %g], this handle's is [%g, %g]", path, v[0], v[1], m->dist->z.vmin, m->dist->z.vmax);
+  }
+  const auto scf = members.find("soft_config");
+  if (!m->soft && (scf != members.end() || members.count(std::string(SOFT_VAR_NAME) + ":0")))
+    return fail(GA3C_ESTATE, "%s holds soft_config: the checkpoint of a handle with the soft actor-critic, which this one has not", path);
+  if (m->soft) {
+    float v[3];
+    if (scf == members.end() || scf->second.descr != "<f4" || scf->second.bytes.size() != sizeof v)
+      return fail(GA3C_ESTATE, "%s holds no f32 soft_config [3]: not the checkpoint of a handle with the soft actor-critic", path);
+    memcpy(v, scf->second.bytes.data(), sizeof v);
+    if (v[0] != m->soft->target_entropy || v[1] != m->soft->cfg.ls_min || v[2] != m->soft->cfg.ls_max)
+      return fail(GA3C_ESTATE, "%s: soft_config (%g, %g, %g), this handle's is (%g, %g, %g)", path, v[0], v[1], v[2],
+                  m->soft->target_entropy, m->soft->cfg.ls_min, m->soft->cfg.ls_max);
   }
   return vn::load(m, path, members);                          // another atom count is another shape of critic_output/W
 }
@@ -2565,6 +3138,7 @@ int ga3c_ddpg_fetch(ga3c_ddpg* m, const char* name, float* out, int64_t count) {
     if (r.tag == W_DIST && !m->dist)
       return fail(GA3C_ESTATE, "%s: the handle has no distributional critic (ga3c_ddpg_dist_create)", name);
     if (r.tag == W_POP && !m->pop) return fail(GA3C_ESTATE, "%s: the handle has no PopArt (ga3c_ddpg_popart_create)", name);
+    if (r.tag == W_SOFT && !m->soft) return fail(GA3C_ESTATE, "%s: the handle has no soft actor-critic (ga3c_ddpg_soft_create)", name);
     const int64_t want = (int64_t)r.width * m->last_B;
     if (count != want) return fail(GA3C_EINVAL, "%s of the last step is %lld floats, not %lld", name, (long long)want, (long long)count);
     HIPCHK(hipStreamSynchronize(m->st));
@@ -2591,8 +3165,10 @@ int ga3c_ddpg_time_resident(ga3c_ddpg* m, int32_t mode, int32_t batch, int32_t i
     const Input in{reinterpret_cast<const char*>(m->ring), nullptr, 4 * (int64_t)m->rowf};
     CHK(timed_loop(m, batch, iters, [&]() -> int {
       if (mode == 0) {
-        hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(batch)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in,
-                           batch, nz, m->w.a_out);
+        if (m->soft) launch_soft_predict(m, in, batch, GA3C_DDPG_NOISE_NONE, nz, 0, m->w.a_out, nullptr);
+        else
+          hipLaunchKernelGGL(ddpg_predict_kernel, dim3(tiles(batch)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0], in,
+                             batch, nz, m->w.a_out);
         return GA3C_OK;
       }
       CHK(enqueue_step(m, rows, batch, learning_rate, nz, 6));
@@ -2817,10 +3393,7 @@ int ga3c_ddpg_twin_create(ga3c_ddpg* m, int32_t policy_delay, float target_sigma
     (void)hipFree(m->arena[a]);
     m->arena[a] = grown[a];
   }
-  for (int i = 0; i < NCRITIC; ++i) add_var(m, V, NACTOR + i, TWIN_VAR_NAMES[i]);
-  add_var(m, V, C_MM1, TWIN_VAR_NAMES[NCRITIC]);
-  add_var(m, V, C_MV1, TWIN_VAR_NAMES[NCRITIC + 1]);
-  m->n = n1;
+  add_twin_vars(m);
   return GA3C_OK;
 }
 
@@ -2830,8 +3403,76 @@ int ga3c_ddpg_twin_destroy(ga3c_ddpg* m) {
   std::lock_guard<std::mutex> tl(m->train_mu);
   std::lock_guard<std::mutex> lk(m->mu);
   if (!m->twin) return fail(GA3C_ESTATE, "the handle has no twin critics (ga3c_ddpg_twin_create)");
+  if (m->soft) return fail(GA3C_ESTATE, "twin_destroy: the handle's soft actor-critic trains both critics (ga3c_ddpg_soft_destroy first)");
   HIPCHK(hipStreamSynchronize(m->st));
   twin_free(m);
+  return GA3C_OK;
+}
+
+// ---- soft actor-critic
+
+int ga3c_ddpg_soft_create(ga3c_ddpg* m, float log_alpha, float alpha_lr, float target_entropy, float ls_min, float ls_max, int64_t seed) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  if (2 * m->L.A > MAX_A) return fail(GA3C_EINVAL, "%d actions: the Gaussian head has 2 A columns and the head holds %d", m->L.A, MAX_A);
+  if (!std::isfinite(log_alpha) || !std::isfinite(alpha_lr) || !std::isfinite(target_entropy) || !std::isfinite(ls_min) ||
+      !std::isfinite(ls_max))
+    return fail(GA3C_EINVAL, "log_alpha %g, alpha_lr %g, target_entropy %g, log-std bounds [%g, %g]: finite numbers", log_alpha,
+                alpha_lr, target_entropy, ls_min, ls_max);
+  if (!(ls_min < ls_max)) return fail(GA3C_EINVAL, "log-std bounds [%g, %g]: the first the smaller", ls_min, ls_max);
+  if (!(alpha_lr >= 0.f)) return fail(GA3C_EINVAL, "alpha_lr %g: a factor >= 0", alpha_lr);
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (m->soft) return fail(GA3C_ESTATE, "the handle has the soft actor-critic already");
+  if (!m->twin) return fail(GA3C_ESTATE, "the soft actor-critic trains twin critics (ga3c_ddpg_twin_create first)");
+  if (m->actors || m->eval)
+    return fail(GA3C_ESTATE, "the handle has device actors or evaluation episodes: the order is twin, soft, then those");
+  Soft* s = new (std::nothrow) Soft();
+  if (!s) return fail(GA3C_EINVAL, "out of host memory");
+  s->cfg.ls_min = ls_min;
+  s->cfg.ls_max = ls_max;
+  s->cfg.seed = (uint64_t)seed;
+  s->alpha_lr = alpha_lr;
+  s->target_entropy = target_entropy;
+  s->core_dout = m->w.dout;
+  m->soft = s;                                     // work_table sizes "do" by it
+  int rc = carve_work(m, W_SOFT, &s->work_base, &m->sw.stat);
+  if (rc == GA3C_OK) rc = vn::dalloc(&s->act_eps, (size_t)m->cfg.max_batch * m->L.A);
+  if (rc == GA3C_OK && hipMemset(s->act_eps, 0, sizeof(float) * (size_t)m->cfg.max_batch * m->L.A) != hipSuccess)
+    rc = fail(GA3C_EHIP, "hipMemset failed");
+  if (rc == GA3C_OK) rc = relay_soft(m, 2 * m->L.A, true, log_alpha);
+  if (rc != GA3C_OK) {
+    soft_free(m);
+    return rc;
+  }
+  s->cfg.la = m->n - 1;
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_soft_destroy(ga3c_ddpg* m) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!m->soft) return fail(GA3C_ESTATE, "the handle has no soft actor-critic (ga3c_ddpg_soft_create)");
+  if (m->actors || m->eval)
+    return fail(GA3C_ESTATE, "soft_destroy: the handle's device actors or evaluation episodes step under its policy (destroy them first)");
+  CHK(relay_soft(m, m->L.A, false, 0.f));
+  soft_free(m);
+  return GA3C_OK;
+}
+
+int ga3c_ddpg_soft_info(ga3c_ddpg* m, float* log_alpha, float* target_entropy, float* mean_logp, int64_t* predictions) {
+  if (!m) return fail(GA3C_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> tl(m->train_mu);
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!m->soft) return fail(GA3C_ESTATE, "the handle has no soft actor-critic (ga3c_ddpg_soft_create)");
+  HIPCHK(hipStreamSynchronize(m->st));
+  if (log_alpha) HIPCHK(hipMemcpy(log_alpha, m->arena[0] + m->soft->cfg.la, sizeof(float), hipMemcpyDeviceToHost));
+  if (mean_logp) HIPCHK(hipMemcpy(mean_logp, m->sw.stat, sizeof(float), hipMemcpyDeviceToHost));
+  if (target_entropy) *target_entropy = m->soft->target_entropy;
+  if (predictions) *predictions = m->soft->predictions.load();
   return GA3C_OK;
 }
 
@@ -3185,7 +3826,11 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
     Noise nz;
     if (!first) {                       // step(None) asks for no prediction: no step of the noise process either
       const Input in{reinterpret_cast<const char*>(d.obs), nullptr, 4 * (int64_t)DEnv::S};
-      if (a->noise.x && noise_mode == GA3C_DDPG_NOISE_OWN) {      // 8r: every environment's own process, stepped by the kernel
+      if (m->soft) {                    // 8u: the policy's own sample, row = environment; the last draws stay readable
+        uint64_t count;
+        CHK(soft_predict_args(m, noise_mode, noise, &nz, &count));
+        launch_soft_predict(m, in, N, noise_mode, nz, count, d.action, m->soft->act_eps);
+      } else if (a->noise.x && noise_mode == GA3C_DDPG_NOISE_OWN) {      // 8r: every environment's own process, stepped by the kernel
         hipLaunchKernelGGL(ddpg_predict_envnoise_kernel, dim3(tiles(N)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[0],
                            in, N, a->noise, d.action);
         ++a->noise.count;
@@ -3305,6 +3950,13 @@ int dactors_access(ga3c_ddpg* m, const char* name, void* out, const void* in, in
     if (a->slots_rows) HIPCHK(hipMemcpy(out, m->per ? m->per->slots : a->slots, (size_t)bytes, hipMemcpyDeviceToHost));
     return GA3C_OK;
   }
+  if (nm == "soft_eps") {               // the last GA3C_DDPG_NOISE_OWN / _GIVEN prediction's draws, [N][A]
+    if (!m->soft) return fail(GA3C_ESTATE, "%s: the handle has no soft actor-critic (ga3c_ddpg_soft_create)", name);
+    if (!out) return fail(GA3C_EINVAL, "%s is read only", name);
+    CHK(sized(4 * (int64_t)d.N * m->L.A));
+    HIPCHK(hipMemcpy(out, m->soft->act_eps, (size_t)bytes, hipMemcpyDeviceToHost));
+    return GA3C_OK;
+  }
   if (nm == "noise_x" || nm == "noise_n" || nm == "noise_count") {      // per-environment noise
     EnvNoise& z = a->noise;
     if (!z.x) return fail(GA3C_ESTATE, "%s: the device actors have no per-environment noise (ga3c_ddpg_envnoise_create)", name);
@@ -3344,6 +3996,7 @@ int ga3c_ddpg_envnoise_create(ga3c_ddpg* m, int64_t seed, int32_t reset_on_done)
   DActors* a = m->actors;
   if (!a) return fail(GA3C_ESTATE, "envnoise_create: this network has no device actors, whose number sizes the noise state");
   if (a->noise.x) return fail(GA3C_ESTATE, "the device actors have per-environment noise already");
+  if (m->soft) return fail(GA3C_ESTATE, "envnoise_create: the soft actor-critic samples its own action for every environment");
   const ga3c_ddpg_config& c = m->cfg;
   if (!(c.flags & GA3C_DDPG_OU_NOISE))
     return fail(GA3C_ESTATE, "envnoise_create: the handle has no noise process to give each environment (GA3C_DDPG_OU_NOISE)");
@@ -3467,7 +4120,15 @@ int ga3c_ddpg_eval_run(ga3c_ddpg* m, int32_t steps, int32_t target, double* tota
   {
     std::lock_guard<std::mutex> lk(m->mu);
     HIPCHK(hipEventRecord(m->t0, m->st));
-    if (m->has_task)
+    if (m->soft && m->has_task)
+      hipLaunchKernelGGL((ddpg_soft_eval_kernel<DEnv, PendulumTask>), dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L,
+                         (const float*)m->arena[target ? 1 : 0], e->n, (int)steps, m->task, (const double*)e->start, e->total, e->phys,
+                         e->tr);
+    else if (m->soft)
+      hipLaunchKernelGGL((ddpg_soft_eval_kernel<DEnv, ForkTask>), dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L,
+                         (const float*)m->arena[target ? 1 : 0], e->n, (int)steps, ForkTask{}, (const double*)e->start, e->total,
+                         e->phys, e->tr);
+    else if (m->has_task)
       hipLaunchKernelGGL(ddpg_eval_task_kernel<DEnv>, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L,
                          (const float*)m->arena[target ? 1 : 0], e->n, (int)steps, m->task, (const double*)e->start, e->total, e->phys,
                          e->tr);

@@ -720,6 +720,48 @@ int ga3c_ddpg_time_prioritized(ga3c_ddpg* net, int32_t batch, int32_t iters, flo
 int ga3c_ddpg_twin_create(ga3c_ddpg* net, int32_t policy_delay, float target_sigma, float target_clip, int64_t seed);
 int ga3c_ddpg_twin_destroy(ga3c_ddpg* net);
 
+/* ---- Soft actor-critic on a twin handle (Config.DDPG_SOFT; tests/sac_oracle.py is the same statement in numpy):
+ * a tanh-Gaussian actor that explores by its own sample, an entropy term in the critics' target and in the actor's loss, and a
+ * learned temperature (Haarnoja et al. 2018).  A handle without it runs what it ran before.
+ *   Head: actor_output/W is [300, 2A], /b [2A].  With o the raw output, mu = o[:A], ls = clamp(o[A:], ls_min, ls_max),
+ *   sigma = exp(ls); no gradient reaches o[A+i] outside the open interval.  Sample: u = fmaf(sigma, eps, mu), a = tanh(u),
+ *   logp = sum_i (-eps_i^2 / 2 - ls_i - ln sqrt(2 pi) - ln(1 - a_i^2)) with ln(1 - tanh^2 u) = 2 (ln 2 - |u| - log1p(exp(-2 |u|)))
+ *   from u.  eps: 8n's Box-Muller draw, f32, unclipped, j = k A + i for row k and action i.
+ * With t = step + 1 every train-type call runs:
+ *   a2, logp2 sampled by the ONLINE actor at s2 on stream 2 t of `seed` (the target actor is kept and soft-updated, not read);
+ *   q' = min of the two target critics at (s2, a2); v' = q' - alpha logp2, alpha = exp(log_alpha) as it stands;
+ *   y = r on a done row or without GA3C_DDPG_FUTURE_REWARD, else fmaf(g, v', r), g the row's discount;
+ *   the twin's step of both critics on y.  Only when t % policy_delay == 0: a, logp sampled at s on stream 2 t + 1, both UPDATED
+ *   critics at (s, a), per row the smaller one selected (critic 1 on a tie) with g = its dq/da, and the gradient of
+ *   J = (1/B) sum_k (alpha logp_k - q_sel,k) -- a MEAN over the rows, where the plain step sums -- through the sample into the
+ *   actor; the actor's Adam at count t / policy_delay; then log_alpha's Adam step on -log_alpha (mean_k logp_k + target_entropy),
+ *   rows in order, at alpha_lr x learning_rate with the same count; the soft update of all three nets.
+ *   The noise arguments of train-type calls are not read, nor are the twin's target_sigma / target_clip.
+ * Launches: the twin's, 3 (4 with GA3C_DDPG_GRAD_CLIP), 5 (6) on a policy step, + 3 prioritised; log_alpha's step rides in the
+ * actor's weight-gradient launch.
+ * Predictions (predict, predict_gather*, actors_run): GA3C_DDPG_NOISE_NONE gives a = tanh(mu), unwrapped; _GIVEN takes the caller's
+ * eps[A] for every row; _OWN draws row r's eps[i] as draw c A + i of stream r under seed + 1, c the handle's count of _OWN
+ * predictions, which every such call advances by one (a device actor step is one call, its row the environment).  The device
+ * actors' last draws are actors_get's "soft_eps" [n][A].  Evaluation episodes act by tanh(mu).
+ * The handle then has 39 variables: the twin's 38 with the wider head, then actor_soft/log_alpha (1,), trainable, with Adam's
+ * slots.  which = 1 of log_alpha is the value given at create, kept so that every variable has its target copy and checkpoint
+ * member; no kernel reads or writes it.  A checkpoint also holds "soft_config", f32 [3]: target_entropy, ls_min, ls_max; a twin
+ * file in a soft handle, a soft file in a twin handle, or another soft_config is GA3C_ESTATE with the handle untouched.
+ * fetch also knows "s_eps2", "s_a2" [B,A], "s_logp2", "s_vt" [B] (the target) and "s_mu", "s_ls", "s_eps", "s_u" [B,A], "s_logp",
+ * "s_q1", "s_q2" [B] (the policy step); GA3C_ESTATE without it.  There "a_noisy" is the sampled action, "g" the selected critic's
+ * dq/da, "do" [B,2A] = dJ/dmu | dJ/dls, "qt" min q'; "a_out" is not written.
+ * create re-lays the arenas: every other variable keeps its value, target copy, slots and gradient, the head is as
+ * ga3c_ddpg_create leaves variables.  GA3C_EINVAL for 2A > 32, a NaN or an infinity, ls_min >= ls_max, alpha_lr < 0;
+ * GA3C_ESTATE on a second create, without twin critics, and on a handle that has device actors (so also per-environment noise) or
+ * evaluation episodes: the order is twin, soft, then those.  envnoise_create and twin_destroy on a soft handle are GA3C_ESTATE.
+ * destroy: the head is [300, A] again, zeroed, and log_alpha is gone (GA3C_ESTATE while device actors or evaluation episodes
+ * live); ga3c_ddpg_destroy does it too.
+ * info: log_alpha as it stands, target_entropy, the mean logp of the last policy step, the count of _OWN predictions. */
+int ga3c_ddpg_soft_create(ga3c_ddpg* net, float log_alpha, float alpha_lr, float target_entropy, float ls_min, float ls_max,
+                          int64_t seed);
+int ga3c_ddpg_soft_destroy(ga3c_ddpg* net);
+int ga3c_ddpg_soft_info(ga3c_ddpg* net, float* log_alpha, float* target_entropy, float* mean_logp, int64_t* predictions);
+
 /* ---- Device actors of a DDPG handle (Config.DEVICE_DDPG; tests/ddpg_actors_oracle.py is the same statement in
  * numpy): n Pendulum-v0 environments in HBM write their transitions into the handle's replay ring and the handle trains on rows
  * it draws from the ring itself, all on its one stream.  Attached to a created handle, as the priorities are.

@@ -6,10 +6,11 @@ predict 1, train_replay 5 (6 with USE_GRAD_CLIP).  --twin: the handle has twin c
 is not a policy step is 3 launches (4), so the time is the mean over --delay steps; --delay 1 times the policy step.
 --nstep N > 1: the handle has n-step state (DDPG_NSTEP) and the target kernel reads a discount per ring slot.
 --dist: the handle has a distributional critic (DDPG_DISTRIBUTIONAL) of --atoms atoms; the launches are the same.
+--soft: the twin handle has the soft actor-critic (DDPG_SOFT; implies --twin); the launches are the twin's.
 KEY=VALUE: the product's own settings, applied after the flags and checked by the product's resolvers, e.g. DDPG_CRITIC_LOSS=paired
 or DDPG_CRITIC_LOSS=paired DDPG_POPART=True (one more launch, a single workgroup).
 usage: python tools/ddpg_step.py [--predict 1 128] [--train 64 128 256] [--rounds 5] [--iters 200] [--clip] [--twin [--delay N]]
-       [--nstep N] [--dist [--atoms N]] [KEY=VALUE ...]"""
+       [--soft] [--nstep N] [--dist [--atoms N]] [KEY=VALUE ...]"""
 import argparse
 import json
 import os
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--twin", action="store_true")
     ap.add_argument("--delay", type=int, default=2)
+    ap.add_argument("--soft", action="store_true")
     ap.add_argument("--nstep", type=int, default=1)
     ap.add_argument("--dist", action="store_true")
     ap.add_argument("--atoms", type=int, default=51)
@@ -41,6 +43,8 @@ def main():
     from Config import Config
     from NetworkDDPG import Network
     Config.USE_GRAD_CLIP = args.clip
+    if args.soft:
+        args.twin, Config.DDPG_SOFT = True, True
     if args.twin:
         Config.DDPG_TWIN, Config.DDPG_CRITIC_LOSS, Config.DDPG_POLICY_DELAY = True, 'paired', args.delay
     Config.DDPG_NSTEP = args.nstep
@@ -70,7 +74,7 @@ def main():
         print(json.dumps({"step": "train_replay" if mode else "predict", "rows": b, "state_dim": S, "actions": A,
                           "grad_clip": bool(args.clip), "launches": (6 if args.clip else 5) + popart if mode else 1,
                           "critic_loss": Config.DDPG_CRITIC_LOSS, "popart": popart,
-                          "nstep": args.nstep, "twin": bool(args.twin), "policy_delay": args.delay if args.twin else None,
+                          "nstep": args.nstep, "twin": bool(args.twin), "soft": bool(args.soft), "policy_delay": args.delay if args.twin else None,
                           "launches_off_policy_step": ((4 if args.clip else 3) if mode else 1) if args.twin else None,
                           "atoms": args.atoms if args.dist else None,
                           "median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2), "max_us": round(v[-1], 2), "rounds": args.rounds,
