@@ -163,7 +163,7 @@ def forward(params, x, min_policy=0.0, use_log_softmax=False, keep=False):
 
 # ---------------------------------------------------------------- loss + grads
 def loss_and_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_log_softmax=False,
-                   adv_const=None, relu_on=None):
+                   adv_const=None, relu_on=None, f=None):
     """Sum-over-batch A3C loss of NetworkVP_discrate.py:61-85,100 and its gradient.
 
     Returns (losses, grads): losses = dict(cost_p_1_agg, cost_p_2_agg, cost_v, cost_all);
@@ -174,8 +174,10 @@ def loss_and_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_lo
     (default: those with a positive output).  A unit whose input lies within rounding of zero is on in one precision and
     off in another, and both are right: a comparison hands the oracle the units its counterpart had on
     (tests/closeness.py) instead of counting the unit's whole gradient as an error.
+    `f` = forward(params, x, min_policy, use_log_softmax, keep=True) where the caller has it already.
     """
-    f = forward(params, x, min_policy, use_log_softmax, keep=True)
+    if f is None:
+        f = forward(params, x, min_policy, use_log_softmax, keep=True)
     dt = f["z"].dtype
     y_r = np.asarray(y_r).astype(dt)
     a = np.asarray(a).astype(dt)

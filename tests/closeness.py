@@ -81,11 +81,14 @@ class OracleCase:
         f = o.forward(self.params, self.x.astype(np.float64), keep=True)
         self.pre = {k: f[k + "pre"].reshape(self.bsz, -1) for k in ACTS}
         self.on = {k: self.pre[k] > 0 for k in ACTS}
-        self.losses, self.g = self._grads(None)
+        self.losses, self.g = self._grads(None, f)
         # the float32 restatement: float32 throughout, or e32 would be a lower limit only
         p32 = f32_params(self.params)
         f32 = o.forward(p32, self.x, keep=True)
-        _, g32 = o.loss_and_grads(p32, self.x, self.y, self.a, self.beta)
+        _, g32 = o.loss_and_grads(p32, self.x, self.y, self.a, self.beta, f=f32)      # (each forward pass is run once)
+        # p, v, z of both runs, for the files that hold predictions to the same rule
+        self.fwd = {k: np.asarray(f[k]) for k in ("p", "v", "z")}
+        self.fwd32 = {k: np.asarray(f32[k]) for k in ("p", "v", "z")}
         for k in TENSORS:
             assert np.asarray(g32[k]).dtype == np.float32, (k, np.asarray(g32[k]).dtype)
         self.e32 = {k: rel_err(f32[k], f[k]) for k in ACTS}
@@ -99,9 +102,9 @@ class OracleCase:
                 self.e32[k] = 0.0
         self.g32 = {k: np.asarray(g32[k]) for k in TENSORS}
 
-    def _grads(self, relu_on):
+    def _grads(self, relu_on, f=None):
         losses, g = o.loss_and_grads(self.params, self.x.astype(np.float64), self.y.astype(np.float64),
-                                     self.a.astype(np.float64), self.beta, relu_on=relu_on)
+                                     self.a.astype(np.float64), self.beta, relu_on=relu_on, f=f)
         return losses, {k: np.asarray(g[k]) for k in TENSORS}
 
     def bound(self, name):

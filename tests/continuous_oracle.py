@@ -50,7 +50,8 @@ def forward(params, x, keep=False):
     n2pre, cols2 = o._conv_fwd(n1, params["conv12/w"], params["conv12/b"], o.CONV2)
     n2 = np.maximum(n2pre, 0)
     flat = n2.reshape(bsz, o.FLAT)
-    d1 = np.maximum(flat @ params["dense1/w"] + params["dense1/b"], 0)
+    d1pre = flat @ params["dense1/w"] + params["dense1/b"]
+    d1 = np.maximum(d1pre, 0)
     v = (d1 @ params["logits_v/w"] + params["logits_v/b"])[:, 0]
     hx = d1 @ params["logits_p/out_x/w"] + params["logits_p/out_x/b"]
     hy = d1 @ params["logits_p/out_y/w"] + params["logits_p/out_y/b"]
@@ -58,17 +59,22 @@ def forward(params, x, keep=False):
     X, Y = sx - 0.5, sy - 0.5
     out = dict(o=np.arctan2(Y, X) / np.pi, v=v, z=np.concatenate([hx, hy], axis=1))
     if keep:
-        out.update(cols1=cols1, n1=n1, cols2=cols2, n2=n2, flat=flat, d1=d1, sx=sx, sy=sy, X=X, Y=Y)
+        out.update(cols1=cols1, n1=n1, cols2=cols2, n2=n2, flat=flat, d1=d1, sx=sx, sy=sy, X=X, Y=Y,
+                   n1pre=n1pre, n2pre=n2pre, d1pre=d1pre)
     return out
 
 
-def loss_and_grads(params, x, y_r, a, beta, adv_const=None):
+def loss_and_grads(params, x, y_r, a, beta, adv_const=None, relu_on=None, f=None):
     """(losses, grads): losses = dict(cost_p_1_agg, cost_p_2_agg, cost_v, cost_all); grads keyed like params plus 'dz'
-    ([B,2A] = [dhx | dhy]), 'dv', 'dd1'.  adv_const freezes y_r - v for finite differences (tf.stop_gradient)."""
-    f = forward(params, x, keep=True)
-    y_r, a = np.asarray(y_r, np.float64), np.asarray(a, np.float64)
+    ([B,2A] = [dhx | dhy]), 'dv', 'dd1', 'dn2', 'dn1'.  adv_const freezes y_r - v for finite differences (tf.stop_gradient).
+    The dtype follows x / params (y_r and a are cast to it), so that a float32 run stays float32 throughout; relu_on is
+    oracle.loss_and_grads' (the units through which the backward pass flows, default: those with a positive output)."""
+    f = forward(params, x, keep=True) if f is None else f       # f: the caller's forward(params, x, keep=True)
+    dt = f["z"].dtype
+    y_r, a = np.asarray(y_r).astype(dt), np.asarray(a).astype(dt)
+    beta = dt.type(beta)
     out, v = f["o"], f["v"]
-    adv = y_r - v if adv_const is None else np.asarray(adv_const, np.float64)
+    adv = y_r - v if adv_const is None else np.asarray(adv_const).astype(dt)
     cost_p_1 = (out * a).sum(axis=1) * adv
     cost_p_2 = -beta * (out * out).sum(axis=1)
     g_o = -a * adv[:, None] + 2.0 * beta * out                 # d cost_p / d o
@@ -84,6 +90,7 @@ def loss_and_grads(params, x, y_r, a, beta, adv_const=None):
     losses = dict(cost_p_1_agg=c1, cost_p_2_agg=c2, cost_v=cost_v, cost_all=-(c1 + c2) + cost_v)
 
     d1, flat, n2, n1 = f["d1"], f["flat"], f["n2"], f["n1"]
+    on = {k: np.asarray(relu_on[k]).reshape(f[k].shape) if relu_on is not None else f[k] > 0 for k in ("d1", "n2", "n1")}
     g = {}
     g["logits_p/out_x/w"] = d1.T @ dhx
     g["logits_p/out_x/b"] = dhx.sum(axis=0)
@@ -92,14 +99,14 @@ def loss_and_grads(params, x, y_r, a, beta, adv_const=None):
     g["logits_v/w"] = d1.T @ dv[:, None]
     g["logits_v/b"] = dv.sum(keepdims=True)
     dd1 = (dhx @ params["logits_p/out_x/w"].T + dhy @ params["logits_p/out_y/w"].T +
-           dv[:, None] @ params["logits_v/w"].T) * (d1 > 0)
+           dv[:, None] @ params["logits_v/w"].T) * on["d1"]
     g["dense1/w"] = flat.T @ dd1
     g["dense1/b"] = dd1.sum(axis=0)
-    dn2 = (dd1 @ params["dense1/w"].T).reshape(n2.shape) * (n2 > 0)
+    dn2 = (dd1 @ params["dense1/w"].T).reshape(n2.shape) * on["n2"]
     g["conv12/w"], g["conv12/b"], dn1 = o._conv_bwd(dn2, f["cols2"], params["conv12/w"], o.CONV2, 21, True)
-    dn1 = dn1 * (n1 > 0)
+    dn1 = dn1 * on["n1"]
     g["conv11/w"], g["conv11/b"], _ = o._conv_bwd(dn1, f["cols1"], params["conv11/w"], o.CONV1, 84, False)
-    g["dz"], g["dv"], g["dd1"] = np.concatenate([dhx, dhy], axis=1), dv, dd1
+    g["dz"], g["dv"], g["dd1"], g["dn2"], g["dn1"] = np.concatenate([dhx, dhy], axis=1), dv, dd1, dn2, dn1
     return losses, g
 
 
@@ -131,8 +138,9 @@ def unflat(theta, num_actions):
     return out
 
 
-def safe_rows(params, x, min_abs_y=1e-4):
-    """Rows of x whose every action keeps away from the branch cut (X < 0, |Y| < min_abs_y) and from X = Y = 0."""
-    f = forward(params, x, keep=True)
+def safe_rows(params, x, min_abs_y=1e-4, f=None):
+    """Rows of x whose every action keeps away from the branch cut (X < 0, |Y| < min_abs_y) and from X = Y = 0.
+    f: forward(params, x, keep=True) where the caller has it already."""
+    f = forward(params, x, keep=True) if f is None else f
     bad = ((f["X"] < 0) & (np.abs(f["Y"]) < min_abs_y)) | (np.hypot(f["X"], f["Y"]) < min_abs_y)
     return ~bad.any(axis=1)

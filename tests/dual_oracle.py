@@ -17,21 +17,26 @@ HEAD_P = ("logits_p/w", "logits_p/b")
 HEAD_V = ("logits_v/w", "logits_v/b")
 
 
-def _trunk(params, f, dd1, g):
+def _trunk(params, f, dd1, g, on):
     """The trunk's gradient for the upstream gradient dd1 of the hidden layer (the lines of loss_and_grads, per cost)."""
     g["dense1/w"] = f["flat"].T @ dd1
     g["dense1/b"] = dd1.sum(axis=0)
-    dn2 = (dd1 @ params["dense1/w"].T).reshape(f["n2"].shape) * (f["n2"] > 0)
+    dn2 = (dd1 @ params["dense1/w"].T).reshape(f["n2"].shape) * on["n2"]
     g["conv12/w"], g["conv12/b"], dn1 = o._conv_bwd(dn2, f["cols2"], params["conv12/w"], o.CONV2, 21, True)
-    dn1 = dn1 * (f["n1"] > 0)
+    dn1 = dn1 * on["n1"]
     g["conv11/w"], g["conv11/b"], _ = o._conv_bwd(dn1, f["cols1"], params["conv11/w"], o.CONV1, 84, False)
+    g["dd1"], g["dn2"], g["dn1"] = dd1, dn2, dn1
 
 
-def dual_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_log_softmax=False):
-    """(losses, g_p, g_v): the gradients of cost_p and of cost_v, each keyed like params (zeros where a cost has no path)."""
+def dual_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_log_softmax=False, relu_on=None, f=None):
+    """(losses, g_p, g_v): the gradients of cost_p and of cost_v, each keyed like params (zeros where a cost has no path),
+    plus each cost's own 'dd1', 'dn2', 'dn1' and the head deltas 'dz' (g_p) and 'dv' (g_v).  The dtype follows x / params;
+    relu_on is oracle.loss_and_grads' (the units through which both backward passes flow)."""
+    if f is None:       # (f: the caller's forward(params, x, min_policy, use_log_softmax, keep=True); one pass serves both calls)
+        f = o.forward(params, x, min_policy, use_log_softmax, keep=True)
     losses, g = o.loss_and_grads(params, x, y_r, a, beta, log_eps=log_eps, min_policy=min_policy,
-                                 use_log_softmax=use_log_softmax)
-    f = o.forward(params, x, min_policy, use_log_softmax, keep=True)
+                                 use_log_softmax=use_log_softmax, relu_on=relu_on, f=f)
+    on = {k: np.asarray(relu_on[k]).reshape(f[k].shape) if relu_on is not None else f[k] > 0 for k in ("d1", "n2", "n1")}
     d1, dz, dv = f["d1"], g["dz"], g["dv"]
     gp = {k: np.zeros_like(params[k]) for k in HEAD_V}
     gv = {k: np.zeros_like(params[k]) for k in HEAD_P}
@@ -39,8 +44,9 @@ def dual_grads(params, x, y_r, a, beta, log_eps=1e-6, min_policy=0.0, use_log_so
     gp["logits_p/b"] = dz.sum(axis=0)
     gv["logits_v/w"] = d1.T @ dv[:, None]
     gv["logits_v/b"] = dv.sum(keepdims=True)
-    _trunk(params, f, (dz @ params["logits_p/w"].T) * (d1 > 0), gp)
-    _trunk(params, f, (dv[:, None] @ params["logits_v/w"].T) * (d1 > 0), gv)
+    _trunk(params, f, (dz @ params["logits_p/w"].T) * on["d1"], gp, on)
+    _trunk(params, f, (dv[:, None] @ params["logits_v/w"].T) * on["d1"], gv, on)
+    gp["dz"], gv["dv"] = dz, dv
     return losses, gp, gv
 
 
