@@ -35,7 +35,7 @@
 // A twin step is 3 launches (4 with clipping); a policy step, every policy_delay-th, adds ddpg_actor_kernel and the actor's
 // ddpg_wgrad_kernel<1>.  Critic 2's variables lie behind the 26 in every arena and are read through a second Layout whose
 // critic entries name them (twin_view), so the device functions of one critic serve both; the host's enqueue_step_nc is one
-// rule for both handles, a plain step being a twin's at delay 1.
+// rule for every handle, a plain step being a twin's at delay 1 and a soft step a twin's with three kernels exchanged.
 // An actor step is predict + 2 launches; every launch argument is known to the host, which waits once per actors_run.
 // n-step returns (ga3c_ddpg_nstep_create, Config.DDPG_NSTEP; tests/nstep_oracle.py is the same statement):
 //   ddpg_actors_nstep_kernel<Env>  actor_step too, the transition into the environment's window of n, and from
@@ -79,6 +79,12 @@
 //   ddpg_soft_predict_kernel  tanh(mu), or the sample under the caller's eps or the counter draws of the row's stream
 //   ddpg_soft_eval_kernel<Env, Task>   ddpg_eval_kernel / ddpg_eval_task_kernel under tanh(mu)
 // The critics' kernels are the twin's and the launch counts of a step are the twin's.
+// The variables: their names, Layout and twin_view, the table of whatever options a handle carries (make_table),
+// the value a variable starts from (initial_value) and the re-lay of an arena from one table to another (relay) are
+// ga3c_ddpg_vars.hpp's, host code that knows no device.  The handle keeps its Options; ga3c_ddpg_create and every option's create
+// and destroy state the Options they want, and set_table / relay_arenas below are the only code that writes the handle's table
+// or replaces its arenas.  Nothing finds a variable by its position: PopArt's statistics and log_alpha are looked up by name at
+// their create and kept as offsets.
 // The environment, the end of an episode, the episode scan and the host's block, episode queue and fields by name are
 // ga3c_actors.hpp's, shared with the rollout actors of ga3c_mlp / ga3c_dmlp; the ring write is this file's.
 #include <cmath>
@@ -86,6 +92,7 @@
 #include <new>
 
 #include "ga3c_actors.hpp"
+#include "ga3c_ddpg_vars.hpp"
 #include "ga3c_tile.hpp"
 #include "ga3c_uniform.hpp"
 #include "ga3c_vecnet.hpp"
@@ -100,77 +107,12 @@ constexpr int RED = 512;                     // the power of two above it: the l
 constexpr int MAX_S = 64;
 constexpr int MAX_A = 32;
 constexpr int MAX_B = 4096;                  // rows of a step: per_update_kernel holds their slots in LDS
-constexpr int H1 = 400;
-constexpr int H2 = 300;
 constexpr float BN_EPS = 1e-5f;
 // 1 - beta as the f32 nearest to the real number: 1.0f - 0.999f is off by 1.3e-5 of itself, which Adam's v would carry
 constexpr float ADAM_OMB1 = 0.1f, ADAM_OMB2 = 0.001f, ADAM_EPS = 1e-8f;
 constexpr double ADAM_B1 = 0.9, ADAM_B2 = 0.999;
 
-// Variables, arena order: the actor's trainable ones, the critic's, then the moving statistics.
-enum {
-  A_W1, A_B1, A_BE1, A_GA1, A_W2, A_B2, A_BE2, A_GA2, A_WO, A_BO,
-  C_W1, C_B1, C_BE1, C_GA1, C_W2, C_B2DEAD, C_WN, C_BN, C_WO, C_BO,
-  A_MM1, A_MV1, A_MM2, A_MV2, C_MM1, C_MV1, NVARS
-};
-constexpr int NTRAIN = 20;             // variables 0..19 are trainable
-constexpr int NACTOR = 10;             // ... 0..9 the actor's
-
-const char* const VAR_NAMES[NVARS] = {
-    "actor_fc1/W", "actor_fc1/b", "actor_norm1/beta", "actor_norm1/gamma", "actor_fc2/W", "actor_fc2/b", "actor_norm2/beta",
-    "actor_norm2/gamma", "actor_output/W", "actor_output/b",
-    "critic_fc1/W", "critic_fc1/b", "critic_norm1/beta", "critic_norm1/gamma", "critic_fc2/W", "critic_fc2/b", "critic_norm2/W",
-    "critic_norm2/b", "critic_output/W", "critic_output/b",
-    "actor_norm1/moving_mean", "actor_norm1/moving_variance", "actor_norm2/moving_mean", "actor_norm2/moving_variance",
-    "critic_norm1/moving_mean", "critic_norm1/moving_variance"};
-
-// ... and the twin's (ga3c_ddpg_twin_create): critic 2's, variables 26..37 of such a handle
-const char* const TWIN_VAR_NAMES[12] = {
-    "critic2_fc1/W", "critic2_fc1/b", "critic2_norm1/beta", "critic2_norm1/gamma", "critic2_fc2/W", "critic2_fc2/b", "critic2_norm2/W",
-    "critic2_norm2/b", "critic2_output/W", "critic2_output/b", "critic2_norm1/moving_mean", "critic2_norm1/moving_variance"};
-
-struct Layout {
-  int S, A;
-  int rows[NVARS], cols[NVARS];    // a vector has rows = 0
-  int64_t off[NVARS + 1];
-};
-
-// N: the outputs of the critic's head, 1 or the atoms of a distributional critic
-// head: the columns of the actor's head, A, or 2 A for the Gaussian head of a soft handle (0: A)
-inline Layout make_layout(int S, int A, int N = 1, int head = 0) {
-  Layout L;
-  L.S = S;
-  L.A = A;
-  const int HD = head ? head : A;
-  const int r[NVARS] = {S, 0, 0, 0, H1, 0, 0, 0, H2, 0, S, 0, 0, 0, H1, 0, A, 0, H2, 0, 0, 0, 0, 0, 0, 0};
-  const int c[NVARS] = {H1, H1, H1, H1, H2, H2, H2, H2, HD, HD, H1, H1, H1, H1, H2, H2, H2, H2, N, N, H1, H1, H2, H2, H1, H1};
-  int64_t o = 0;
-  for (int v = 0; v < NVARS; ++v) {
-    L.rows[v] = r[v];
-    L.cols[v] = c[v];
-    L.off[v] = o;
-    o += (int64_t)(r[v] ? r[v] : 1) * c[v];
-  }
-  L.off[NVARS] = o;
-  return L;
-}
-
-// The twin's twelve variables lie behind the 26, in the critic's order: its ten trainable ones, then its moving statistics.
-constexpr int NTWIN = 12;
-constexpr int NCRITIC = NTRAIN - NACTOR;
-
-// L with the critic's entries naming critic 2's variables: off[NACTOR .. NTRAIN] its trainable ones and their end, off[C_MM1],
-// off[C_MV1] its statistics.  The actor's statistics have no meaning in the view; no critic code reads them.
-inline Layout twin_view(const Layout& L) {
-  Layout V = L;
-  const int64_t shift = L.off[NVARS] - L.off[NACTOR];
-  for (int v = NACTOR; v <= NTRAIN; ++v) V.off[v] = L.off[v] + shift;
-  for (int v = NTRAIN + 1; v < C_MM1; ++v) V.off[v] = V.off[NTRAIN];
-  V.off[C_MM1] = V.off[NTRAIN];
-  V.off[C_MV1] = V.off[C_MM1] + H1;
-  V.off[NVARS] = V.off[C_MV1] + H1;
-  return V;
-}
+// The variables, their names, Layout, make_layout and twin_view: ga3c_ddpg_vars.hpp.
 
 template <class T, int NC>
 struct PerCritic { T v[NC]; };     // a kernel argument per critic of a handle with NC of them
@@ -1963,7 +1905,7 @@ struct Twin {
   int delay = 1;                        // a policy step when (step + 1) % delay == 0
   float sigma = 0.f, clip = 0.f;        // the target smoothing
   uint64_t seed = 0;                    // its draw at step + 1 = t is stream t of this seed
-  Layout view;                          // twin_view(L)
+  Layout view{};                        // twin_view(L), set with the handle's table (set_table)
   float* work_base = nullptr;           // the twin-only rows of the handle's Work
 };
 
@@ -1983,6 +1925,7 @@ struct Dist {
 // PopArt of a handle (ga3c_ddpg_popart_create).  The arenas hold two floats behind the 26 variables while it lives: mu, nu.
 struct Pop {
   float beta = 0.f, smin = 0.f, smax = 0.f;
+  int64_t stat = 0;                     // where mu lies in every arena, nu behind it
   float* work_base = nullptr;           // the row "yn" of the handle's work table
 };
 
@@ -2012,6 +1955,7 @@ struct Eval : ga3c_actors::ActorsCore {
 
 struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, gradient; a lane's one output is a[A]
   ga3c_ddpg_config cfg;
+  Options opt;                    // what fixes the variables: vars, tnames, n, L and the twin's view are make_table(opt)'s
   Layout L;
   int rowf = 0;
   std::mutex add_mu;              // one replay_add at a time (its own staging); mu also orders the ring's bookkeeping
@@ -2181,7 +2125,10 @@ const float* row_discounts(const ga3c_ddpg* m, const Rows& rows) {
 // Steps 1 .. stop_after of train_DDPG on `rows` for a handle with NC critics (caller holds train_mu and mu).  stop_after 6: the
 // whole step.  Twin critics: smoothed targets from the smaller of two target critics, both critics stepped on
 // them in the paired form, and only when t is a multiple of the delay the actor's step, at its own Adam count, and the soft
-// update of all three nets.  One critic is that rule at delay 1, with the loss form the handle's flag names.
+// update of all three nets.  One critic is that rule at delay 1, with the loss form the handle's flag names.  The soft
+// actor-critic is the twin's rule with the soft target kernel in the target kernel's place and, on a policy step,
+// the soft actor kernel and the actor's weight-gradient launch that carries the temperature's step; its draws at step t are
+// streams 2 t (target) and 2 t + 1 (policy) of the soft seed, and no noise argument is read.
 template <int NC>
 int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w) {
   const ga3c_ddpg_config& c = m->cfg;
@@ -2206,6 +2153,7 @@ int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise
   }
   const dim3 grid(tiles(B)), gridc(tiles(B), NC), block(THREADS);
   const Dist* ds = NC == 1 ? m->dist : nullptr;    // a distributional critic: its three kernels in the scalar ones' places
+  const Soft* so = NC == 2 ? m->soft : nullptr;
   const int future = (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0;
   float* used = m->nstep ? m->nstep->used : nullptr;
   if (ds) {
@@ -2217,15 +2165,22 @@ int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise
     // PopArt: the targets are de-normalised with the statistics as they stand, the one-workgroup kernel moves
     // them, rescales both output layers and leaves yn, and the critic step runs on yn where y was
     const Pop* pp = NC == 1 ? m->pop : nullptr;
-    float* stat = pp ? m->arena[0] + m->L.off[NVARS] : nullptr;
-    hipLaunchKernelGGL(ddpg_target_kernel<NC>, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma, future, tg,
-                       row_discounts(m, rows), used, PopStats{stat, pp ? (double)pp->smin : 0.0, pp ? (double)pp->smax : 0.0});
+    float* stat = pp ? m->arena[0] + pp->stat : nullptr;
+    if (so) {
+      if constexpr (NC == 2)
+        hipLaunchKernelGGL(ddpg_soft_target_kernel, grid, block, 0, m->st, L, (const float*)m->arena[0], (const float*)m->arena[1],
+                           rows, B, c.gamma, future, so->cfg, SoftTarget{w.y, w.qt, w.qt1, w.qt2, (uint64_t)(2 * t)}, m->sw,
+                           row_discounts(m, rows), used);
+    } else {
+      hipLaunchKernelGGL(ddpg_target_kernel<NC>, grid, block, 0, m->st, L, (const float*)m->arena[1], rows, B, c.gamma, future, tg,
+                         row_discounts(m, rows), used, PopStats{stat, pp ? (double)pp->smin : 0.0, pp ? (double)pp->smax : 0.0});
+    }
     Work wc = w;
     if (pp) {
       float *a0 = m->arena[0], *a1 = m->arena[1];
       const Layout& K = m->L;
       hipLaunchKernelGGL(ddpg_popart_kernel, dim3(1), block, 0, m->st,
-                         PopArt{stat, a1 + K.off[NVARS], a0 + K.off[C_WO], a0 + K.off[C_BO], a1 + K.off[C_WO], a1 + K.off[C_BO],
+                         PopArt{stat, a1 + pp->stat, a0 + K.off[C_WO], a0 + K.off[C_BO], a1 + K.off[C_WO], a1 + K.off[C_BO],
                                 (const float*)w.y, m->yn, w.qstat + 2, (double)pp->beta, (double)pp->smin, (double)pp->smax},
                          B);
       wc.y = m->yn;
@@ -2242,65 +2197,29 @@ int enqueue_step_nc(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise
     hipLaunchKernelGGL((ddpg_wgrad_kernel<NC, true>), dim3(cblocks, NC), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
   }
   if (stop_after >= 4 && policy) {
-    if (ds) hipLaunchKernelGGL(ddpg_dist_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w, ds->z);
-    else hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w);
     const Opt oa = make_opt(m, true, lr, t / delay, full, full);
-    hipLaunchKernelGGL((ddpg_wgrad_kernel<1, true>), dim3(ablocks), block, 0, m->st, PerCritic<Layout, 1>{{m->L}},
-                       PerCritic<GradSrc, 1>{{gs.v[0]}}, 0, NACTOR, B, oa, w);
-  }
-  HIPCHK(hipGetLastError());
-  return GA3C_OK;
-}
-
-// The step of a handle with the soft actor-critic: enqueue_step_nc<2>'s rule and launch counts with the soft
-// target kernel in the target kernel's place and, on a policy step, the soft actor kernel and the actor's weight-gradient launch
-// that carries the temperature's step.  The critics' three kernels are the twin's.  The draws of step t are streams 2 t (target)
-// and 2 t + 1 (policy) of the soft seed; no noise argument is read.
-int enqueue_soft(ga3c_ddpg* m, const Rows& rows, int B, float lr, int stop_after, const float* per_w) {
-  const ga3c_ddpg_config& c = m->cfg;
-  const Work& w = m->w;
-  const Soft& so = *m->soft;
-  const int64_t t = m->step.load() + 1;
-  const int delay = m->twin->delay;
-  const bool policy = t % delay == 0, full = stop_after >= 6, clip = (c.flags & GA3C_DDPG_GRAD_CLIP) != 0;
-  PerCritic<Layout, 2> L;
-  PerCritic<GradSrc, 2> gs;
-  L.v[0] = m->L;
-  L.v[1] = m->twin->view;
-  gs.v[0] = grad_src(m, 0);
-  gs.v[1] = grad_src(m, 1);
-  const dim3 grid(tiles(B)), gridc(tiles(B), 2), block(THREADS);
-  const int future = (c.flags & GA3C_DDPG_FUTURE_REWARD) ? 1 : 0;
-  float* used = m->nstep ? m->nstep->used : nullptr;
-  hipLaunchKernelGGL(ddpg_soft_target_kernel, grid, block, 0, m->st, L, (const float*)m->arena[0], (const float*)m->arena[1], rows, B,
-                     c.gamma, future, so.cfg, SoftTarget{w.y, w.qt, w.qt1, w.qt2, (uint64_t)(2 * t)}, m->sw, row_discounts(m, rows),
-                     used);
-  hipLaunchKernelGGL(ddpg_critic_kernel<2>, gridc, block, 0, m->st, L, (const float*)m->arena[0], rows, B, 1, per_w, w);
-  const int cblocks = (int)((m->L.off[NTRAIN] - m->L.off[NACTOR] + THREADS - 1) / THREADS);
-  const int ablocks = (int)((m->L.off[NACTOR] + THREADS - 1) / THREADS);
-  const Opt oc = make_opt(m, false, lr, t, true, full && policy);
-  if (clip) {
-    hipLaunchKernelGGL((ddpg_wgrad_kernel<2, false>), dim3(cblocks, 2), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
-    hipLaunchKernelGGL(ddpg_update_kernel<2>, dim3(2 * NCRITIC), block, 0, m->st, L, oc);
-  } else {
-    hipLaunchKernelGGL((ddpg_wgrad_kernel<2, true>), dim3(cblocks, 2), block, 0, m->st, L, gs, NACTOR, NTRAIN, B, oc, w);
-  }
-  if (stop_after >= 4 && policy) {
-    hipLaunchKernelGGL(ddpg_soft_actor_kernel, grid, block, 0, m->st, L, (const float*)m->arena[0], rows, B, so.cfg,
-                       (uint64_t)(2 * t + 1), w, m->sw);
-    const Opt oa = make_opt(m, true, lr, t / delay, full, full);
-    // the temperature's Adam: the actor's bias correction on alpha_lr x the rate (oa.lr is that correction on actor_lr x the rate)
-    const double tt = (double)(t / delay);
-    const float lra = (float)((double)so.alpha_lr * (double)lr * std::sqrt(1.0 - std::pow(ADAM_B2, tt)) / (1.0 - std::pow(ADAM_B1, tt)));
-    hipLaunchKernelGGL(ddpg_soft_wgrad_kernel, dim3(ablocks), block, 0, m->st, m->L, gs.v[0], B, oa,
-                       SoftAlpha{(const float*)m->sw.logp, m->sw.stat, so.cfg.la, so.target_entropy, lra});
+    if (so) {
+      if constexpr (NC == 2) {
+        hipLaunchKernelGGL(ddpg_soft_actor_kernel, grid, block, 0, m->st, L, (const float*)m->arena[0], rows, B, so->cfg,
+                           (uint64_t)(2 * t + 1), w, m->sw);
+        // the temperature's Adam: the actor's bias correction on alpha_lr x the rate (oa.lr is that correction on actor_lr x the rate)
+        const double tt = (double)(t / delay);
+        const float lra = (float)((double)so->alpha_lr * (double)lr * std::sqrt(1.0 - std::pow(ADAM_B2, tt)) / (1.0 - std::pow(ADAM_B1, tt)));
+        hipLaunchKernelGGL(ddpg_soft_wgrad_kernel, dim3(ablocks), block, 0, m->st, m->L, gs.v[0], B, oa,
+                           SoftAlpha{(const float*)m->sw.logp, m->sw.stat, so->cfg.la, so->target_entropy, lra});
+      }
+    } else {
+      if (ds) hipLaunchKernelGGL(ddpg_dist_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w, ds->z);
+      else hipLaunchKernelGGL(ddpg_actor_kernel, grid, block, 0, m->st, m->L, (const float*)m->arena[0], rows, B, nz, w);
+      hipLaunchKernelGGL((ddpg_wgrad_kernel<1, true>), dim3(ablocks), block, 0, m->st, PerCritic<Layout, 1>{{m->L}},
+                         PerCritic<GradSrc, 1>{{gs.v[0]}}, 0, NACTOR, B, oa, w);
+    }
   }
   HIPCHK(hipGetLastError());
   return GA3C_OK;
 }
 
 int enqueue_step(ga3c_ddpg* m, const Rows& rows, int B, float lr, const Noise& nz, int stop_after, const float* per_w = nullptr) {
-  if (m->soft) return enqueue_soft(m, rows, B, lr, stop_after, per_w);
   return m->twin ? enqueue_step_nc<2>(m, rows, B, lr, nz, stop_after, per_w) : enqueue_step_nc<1>(m, rows, B, lr, nz, stop_after, per_w);
 }
 
@@ -2414,70 +2333,82 @@ int predict_end(ga3c_ddpg* m, int ticket, int B, float* a, float* v) {
   return GA3C_OK;
 }
 
-// tflearn's name of the target copy: the layer's scope is made a second time, "actor_fc1" -> "actor_fc1_1" (the one place).
-std::string target_name(const std::string& s) {
-  const size_t slash = s.find('/');
-  return s.substr(0, slash) + "_1" + s.substr(slash);
+// The handle's variables become those of `opt` (ga3c_ddpg_vars.hpp's table, the one statement of them); the arenas are the
+// caller's business.  Caller holds train_mu and mu, or owns the handle alone.
+void set_table(ga3c_ddpg* m, const Options& opt) {
+  Table t = make_table(opt);
+  m->opt = opt;
+  m->L = t.L;
+  if (m->twin) m->twin->view = t.view;
+  m->vars = std::move(t.vars);
+  m->tnames = std::move(t.tnames);
+  m->n = t.n;
 }
 
-// The variable table: value and target copy of every variable are checkpoint members; the 20 trainable ones also have the
-// two slots of their optimizer, under Adam's names or RMSProp's.
-// `name` = variable i of layout `L` (a view: the critic's entries only) at the table's end
-void add_var(ga3c_ddpg* m, const Layout& L, int i, const char* vname) {
-  const std::string name(vname);
-  vn::Var var{name, L.off[i], (int64_t)(L.rows[i] ? L.rows[i] : 1) * L.cols[i], 1, {L.cols[i], 0}, {}};
-  if (L.rows[i]) {                                 // a matrix [rows, cols]; a vector has rows = 0
-    var.ndim = 2;
-    var.shape[0] = L.rows[i];
-    var.shape[1] = L.cols[i];
+// where the variable called `name` lies in every arena (a name of the table)
+int64_t var_offset(const ga3c_ddpg* m, const char* name) { return m->vars[(size_t)ga3c_ckpt::find_var(m->vars, name)].off; }
+
+// The five arenas re-laid for the variables of `to` (relay, on the host: a variable keeps its value, target copy, slots and
+// gradient where the handle has one of that name and shape, and starts as ga3c_ddpg_create would leave it otherwise), then the
+// handle's table set to it.  The old arenas are freed only after the last new one is allocated and written: on any failure the
+// handle is as it was.  Caller holds train_mu and mu.
+int relay_arenas(ga3c_ddpg* m, const Options& to, float log_alpha = 0.f) {
+  const Table from = make_table(m->opt), next = make_table(to);
+  float* laid[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto build = [&]() -> int {
+    HIPCHK(hipStreamSynchronize(m->st));           // a prediction in flight has finished before its arena is freed
+    std::vector<float> old((size_t)from.n);
+    for (int a = 0; a < m->narena; ++a) {
+      HIPCHK(hipMemcpy(old.data(), m->arena[a], sizeof(float) * from.n, hipMemcpyDeviceToHost));
+      const std::vector<float> image = relay(from, old, next, a, log_alpha);
+      CHK(vn::dalloc(&laid[a], (size_t)next.n));
+      HIPCHK(hipMemcpy(laid[a], image.data(), sizeof(float) * next.n, hipMemcpyHostToDevice));
+    }
+    return GA3C_OK;
+  };
+  const int rc = build();
+  if (rc != GA3C_OK) {
+    for (float* g : laid) (void)hipFree(g);
+    (void)hipGetLastError();
+    return rc;
   }
-  var.ckpt = {{name + ":0", 0}, {target_name(name) + ":0", 1}};
-  if (i < NTRAIN) {
-    const bool adam = i < NACTOR || (m->cfg.flags & GA3C_DDPG_CRITIC_ADAM);
-    var.ckpt.emplace_back(name + (adam ? "/Adam:0" : "/RMSProp:0"), 2);
-    var.ckpt.emplace_back(name + (adam ? "/Adam_1:0" : "/RMSProp_1:0"), 3);
+  for (int a = 0; a < m->narena; ++a) {
+    (void)hipFree(m->arena[a]);
+    m->arena[a] = laid[a];
   }
-  m->vars.push_back(std::move(var));
-  m->tnames.push_back(target_name(name));
+  set_table(m, to);
+  return GA3C_OK;
 }
 
-void fill_vars(ga3c_ddpg* m) {
-  for (int i = 0; i < NVARS; ++i) add_var(m, m->L, i, VAR_NAMES[i]);
-  m->n = m->L.off[NVARS];
+// The block of an option's work rows freed, and every row of that tag null again.
+void free_work(ga3c_ddpg* m, WorkTag tag, float* base) {
+  (void)hipFree(base);
+  (void)hipGetLastError();
+  for (const WorkRow& r : work_table(m))
+    if (r.tag == tag) *r.ptr = nullptr;
 }
 
-// variable i of the handle's table is trainable: the 20, and critic 2's ten of a twin handle (PopArt's two are not)
-bool trainable_var(const ga3c_ddpg* m, int i) {
-  return i >= 0 && (i < NTRAIN || (m->twin && i >= NVARS && i < NVARS + NCRITIC) || (m->soft && i == NVARS + NTWIN));      // log_alpha
-}
-
-const char* const POP_VAR_NAMES[2] = {"critic_popart/mu", "critic_popart/nu"};
-
+// The state, its rows and its variables' names; the arenas keep their size, and nothing names what lies behind the table's end.
 void pop_free(ga3c_ddpg* m) {
   Pop* p = m->pop;
   if (!p) return;
-  (void)hipFree(p->work_base);
-  (void)hipGetLastError();
-  m->yn = nullptr;
+  free_work(m, W_POP, p->work_base);
   delete p;
   m->pop = nullptr;
-  m->vars.resize(NVARS);            // the arenas keep their size: nothing names what lies behind the 26
-  m->tnames.resize(NVARS);
-  m->n = m->L.off[NVARS];
+  Options opt = m->opt;
+  opt.pop = false;
+  set_table(m, opt);
 }
 
 void twin_free(ga3c_ddpg* m) {
   Twin* t = m->twin;
   if (!t) return;
-  (void)hipFree(t->work_base);
-  (void)hipGetLastError();
-  for (const WorkRow& r : work_table(m))
-    if (r.tag == W_TWIN) *r.ptr = nullptr;
+  free_work(m, W_TWIN, t->work_base);
   delete t;
   m->twin = nullptr;
-  m->vars.resize(NVARS);            // the arenas keep their size: nothing names what lies behind the 26
-  m->tnames.resize(NVARS);
-  m->n = m->L.off[NVARS];
+  Options opt = m->opt;
+  opt.twin = false;
+  set_table(m, opt);
 }
 
 void per_free(ga3c_ddpg* m) {
@@ -2499,127 +2430,22 @@ void nstep_free(ga3c_ddpg* m) {
   m->nstep = nullptr;
 }
 
-// The five arenas re-laid for a critic head of `atoms` outputs (1: the scalar head).  Every variable keeps its value, target
-// copy, slots and gradient; critic_output/W and /b, whose shapes change, are as ga3c_ddpg_create leaves variables: zero, the
-// RMSProp ms slot one.  The variable table is refilled.  Caller holds train_mu and mu; the handle has no twin critics.
-int relay_head(ga3c_ddpg* m, int atoms) {
-  const Layout L0 = m->L, L1 = make_layout(L0.S, L0.A, atoms);
-  const int64_t n0 = L0.off[NVARS], n1 = L1.off[NVARS];
-  float* laid[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  auto build = [&]() -> int {
-    HIPCHK(hipStreamSynchronize(m->st));           // a prediction in flight has finished before its arena is freed
-    std::vector<float> a0((size_t)n0), a1((size_t)n1);
-    for (int a = 0; a < m->narena; ++a) {
-      HIPCHK(hipMemcpy(a0.data(), m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToHost));
-      const float head = a == 2 && !(m->cfg.flags & GA3C_DDPG_CRITIC_ADAM) ? 1.f : 0.f;
-      for (int v = 0; v < NVARS; ++v) {
-        if (v == C_WO || v == C_BO) std::fill(a1.begin() + L1.off[v], a1.begin() + L1.off[v + 1], head);
-        else std::copy(a0.begin() + L0.off[v], a0.begin() + L0.off[v + 1], a1.begin() + L1.off[v]);
-      }
-      CHK(vn::dalloc(&laid[a], (size_t)n1));
-      HIPCHK(hipMemcpy(laid[a], a1.data(), sizeof(float) * n1, hipMemcpyHostToDevice));
-    }
-    return GA3C_OK;
-  };
-  const int rc = build();
-  if (rc != GA3C_OK) {
-    for (float* g : laid) (void)hipFree(g);
-    (void)hipGetLastError();
-    return rc;
-  }
-  for (int a = 0; a < m->narena; ++a) {
-    (void)hipFree(m->arena[a]);
-    m->arena[a] = laid[a];
-  }
-  m->L = L1;
-  m->vars.clear();
-  m->tnames.clear();
-  fill_vars(m);
-  return GA3C_OK;
-}
-
 // The state and its rows; the arenas stay as they are laid (dist_destroy re-lays them first, ga3c_ddpg_destroy frees them).
 void dist_free(ga3c_ddpg* m) {
   Dist* d = m->dist;
   if (!d) return;
-  (void)hipFree(d->work_base);
-  (void)hipGetLastError();
-  m->dw = DistRows{};
+  free_work(m, W_DIST, d->work_base);
   delete d;
   m->dist = nullptr;
-}
-
-// critic 2's twelve variables at the table's end, read through the twin's view
-void add_twin_vars(ga3c_ddpg* m) {
-  const Layout& V = m->twin->view;
-  for (int i = 0; i < NCRITIC; ++i) add_var(m, V, NACTOR + i, TWIN_VAR_NAMES[i]);
-  add_var(m, V, C_MM1, TWIN_VAR_NAMES[NCRITIC]);
-  add_var(m, V, C_MV1, TWIN_VAR_NAMES[NCRITIC + 1]);
-  m->n = V.off[NVARS];
-}
-
-const char* const SOFT_VAR_NAME = "actor_soft/log_alpha";
-
-// The five arenas of a twin handle re-laid for an actor head of `head` columns (2 A: the Gaussian head; A: back), with log_alpha
-// behind the 38 variables when `with_alpha`.  Every other variable keeps its value, target copy, slots and gradient;
-// actor_output/W and /b, whose shapes change, are as ga3c_ddpg_create leaves variables: zero everywhere (the actor's slots are
-// Adam's).  log_alpha: `log_alpha` in the value and the target arena, zero slots and gradient.  The twin's view and the variable
-// table are remade.  Caller holds train_mu and mu.
-int relay_soft(ga3c_ddpg* m, int head, bool with_alpha, float log_alpha) {
-  const Layout L0 = m->L, L1 = make_layout(L0.S, L0.A, 1, head);
-  const Layout V0 = twin_view(L0), V1 = twin_view(L1);
-  const int64_t n0 = m->n, n1 = V1.off[NVARS] + (with_alpha ? 1 : 0);
-  float* laid[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  auto build = [&]() -> int {
-    HIPCHK(hipStreamSynchronize(m->st));           // a prediction in flight has finished before its arena is freed
-    std::vector<float> a0((size_t)n0), a1((size_t)n1);
-    for (int a = 0; a < m->narena; ++a) {
-      HIPCHK(hipMemcpy(a0.data(), m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToHost));
-      std::fill(a1.begin(), a1.end(), 0.f);
-      for (int v = 0; v < NVARS; ++v)
-        if (v != A_WO && v != A_BO) std::copy(a0.begin() + L0.off[v], a0.begin() + L0.off[v + 1], a1.begin() + L1.off[v]);
-      std::copy(a0.begin() + L0.off[NVARS], a0.begin() + V0.off[NVARS], a1.begin() + L1.off[NVARS]);      // critic 2's twelve
-      if (with_alpha && a <= 1) a1[(size_t)n1 - 1] = log_alpha;
-      CHK(vn::dalloc(&laid[a], (size_t)n1));
-      HIPCHK(hipMemcpy(laid[a], a1.data(), sizeof(float) * n1, hipMemcpyHostToDevice));
-    }
-    return GA3C_OK;
-  };
-  const int rc = build();
-  if (rc != GA3C_OK) {
-    for (float* g : laid) (void)hipFree(g);
-    (void)hipGetLastError();
-    return rc;
-  }
-  for (int a = 0; a < m->narena; ++a) {
-    (void)hipFree(m->arena[a]);
-    m->arena[a] = laid[a];
-  }
-  m->L = L1;
-  m->twin->view = V1;
-  m->vars.clear();
-  m->tnames.clear();
-  fill_vars(m);
-  add_twin_vars(m);
-  if (with_alpha) {                  // f32 (1,), trainable: value, target copy and Adam's two slots in the checkpoint
-    const std::string name(SOFT_VAR_NAME);
-    vn::Var var{name, n1 - 1, 1, 1, {1, 0}, {}};
-    var.ckpt = {{name + ":0", 0}, {target_name(name) + ":0", 1}, {name + "/Adam:0", 2}, {name + "/Adam_1:0", 3}};
-    m->vars.push_back(std::move(var));
-    m->tnames.push_back(target_name(name));
-  }
-  m->n = n1;
-  return GA3C_OK;
 }
 
 // The state and its rows; the arenas stay as they are laid (soft_destroy re-lays them first, ga3c_ddpg_destroy frees them).
 void soft_free(ga3c_ddpg* m) {
   Soft* s = m->soft;
   if (!s) return;
-  (void)hipFree(s->work_base);
   (void)hipFree(s->act_eps);
-  (void)hipGetLastError();
-  m->sw = SoftRows{};
+  free_work(m, W_SOFT, s->work_base);              // "do" among them: the handle's own is back in place below
+  m->sw.stat = nullptr;                            // (the floats behind the rows)
   if (s->core_dout) m->w.dout = s->core_dout;
   delete s;
   m->soft = nullptr;
@@ -2663,17 +2489,11 @@ int alloc_all(ga3c_ddpg* m) {
   const ga3c_ddpg_config& c = m->cfg;
   const size_t B = (size_t)c.max_batch, A = c.num_actions, rowf = (size_t)m->rowf;
   CHK(vn::alloc_core(m, c.predict_lanes));
-  // moving_variance = 1 in both copies; the RMSProp ms slot of the critic starts at 1 (TF-1 RMSPropOptimizer)
-  std::vector<float> init((size_t)m->n, 0.f);
-  for (int v : {(int)A_MV1, (int)A_MV2, (int)C_MV1})
-    for (int64_t i = m->L.off[v]; i < m->L.off[v + 1]; ++i) init[(size_t)i] = 1.f;
-  HIPCHK(hipMemcpy(m->arena[0], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(m->arena[1], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
-  if (!(c.flags & GA3C_DDPG_CRITIC_ADAM)) {
-    std::fill(init.begin(), init.end(), 0.f);
-    for (int64_t i = m->L.off[NACTOR]; i < m->L.off[NTRAIN]; ++i) init[(size_t)i] = 1.f;
-    HIPCHK(hipMemcpy(m->arena[2], init.data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
-  }
+  // every variable at its initial value (initial_value: moving_variance = 1 in both copies, the RMSProp ms slot of the critic 1);
+  // alloc_core left the slot b and gradient arenas zero, which is theirs
+  const Table table = make_table(m->opt);
+  for (int a = 0; a <= 2; ++a)
+    HIPCHK(hipMemcpy(m->arena[a], relay(Table{}, {}, table, a, 0.f).data(), sizeof(float) * m->n, hipMemcpyHostToDevice));
   CHK(carve_work(m, W_CORE, &m->work_base, &m->w.qstat));
   CHK(vn::dalloc(&m->ring, (size_t)c.replay_capacity * rowf));
   HIPCHK(hipMemset(m->ring, 0, sizeof(float) * (size_t)c.replay_capacity * rowf));
@@ -2803,8 +2623,11 @@ int ga3c_ddpg_create(const ga3c_ddpg_config* cfg, ga3c_ddpg** out) {
   m->out_widths = {cfg->num_actions};
   m->narena = 5;
   m->writable = {0, 1, 2, 3};
-  m->L = make_layout(cfg->state_dim, cfg->num_actions);
-  fill_vars(m);
+  Options opt;
+  opt.S = cfg->state_dim;
+  opt.A = cfg->num_actions;
+  opt.critic_adam = (cfg->flags & GA3C_DDPG_CRITIC_ADAM) != 0;
+  set_table(m, opt);
   m->rowf = 2 * cfg->state_dim + cfg->num_actions + 2;
   m->gen.seed((uint64_t)cfg->seed);
   m->ou_x.assign((size_t)cfg->num_actions, 0.f);
@@ -2836,7 +2659,7 @@ const char* ga3c_ddpg_target_name(ga3c_ddpg* m, int32_t index) {
 
 int ga3c_ddpg_param_info(ga3c_ddpg* m, const char* name, int64_t* count, int32_t* ndim, int64_t shape[4], int32_t* trainable) {
   CHK(vn::param_info(m, name, nullptr, count, ndim, shape));
-  if (trainable) *trainable = trainable_var(m, ga3c_ckpt::find_var(m->vars, name)) ? 1 : 0;
+  if (trainable) *trainable = ga3c_dd::trainable(m->vars[(size_t)ga3c_ckpt::find_var(m->vars, name)]) ? 1 : 0;
   return GA3C_OK;
 }
 
@@ -3358,43 +3181,15 @@ int ga3c_ddpg_twin_create(ga3c_ddpg* m, int32_t policy_delay, float target_sigma
   t->sigma = target_sigma;
   t->clip = target_clip;
   t->seed = (uint64_t)seed;
-  t->view = twin_view(m->L);
-  const Layout& V = t->view;
-  const int64_t n0 = m->L.off[NVARS], n1 = V.off[NVARS];
-  // Every arena grows by critic 2's variables, which start as ga3c_ddpg_create leaves the others: zero, the variance and the
-  // RMSProp ms slot one.  The 26 keep their values; a prediction in flight has finished before its arena is freed.
-  float* grown[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // Every arena grows by critic 2's variables, which start as ga3c_ddpg_create leaves the others; the 26 keep their values.
+  Options to = m->opt;
+  to.twin = true;
   m->twin = t;
-  auto build = [&]() -> int {
-    HIPCHK(hipStreamSynchronize(m->st));
-    std::vector<float> init((size_t)(n1 - n0));
-    for (int a = 0; a < m->narena; ++a) {
-      CHK(vn::dalloc(&grown[a], (size_t)n1));
-      HIPCHK(hipMemcpy(grown[a], m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToDevice));
-      std::fill(init.begin(), init.end(), 0.f);
-      if (a <= 1)
-        for (int64_t i = V.off[C_MV1]; i < V.off[NVARS]; ++i) init[(size_t)(i - n0)] = 1.f;
-      if (a == 2 && !(m->cfg.flags & GA3C_DDPG_CRITIC_ADAM))
-        for (int64_t i = V.off[NACTOR]; i < V.off[NTRAIN]; ++i) init[(size_t)(i - n0)] = 1.f;
-      HIPCHK(hipMemcpy(grown[a] + n0, init.data(), sizeof(float) * (n1 - n0), hipMemcpyHostToDevice));
-    }
-    float* end = nullptr;
-    CHK(carve_work(m, W_TWIN, &t->work_base, &end));
-    return GA3C_OK;
-  };
-  const int rc = build();
-  if (rc != GA3C_OK) {
-    for (float* g : grown) (void)hipFree(g);
-    (void)hipGetLastError();
-    twin_free(m);
-    return rc;
-  }
-  for (int a = 0; a < m->narena; ++a) {
-    (void)hipFree(m->arena[a]);
-    m->arena[a] = grown[a];
-  }
-  add_twin_vars(m);
-  return GA3C_OK;
+  float* end = nullptr;
+  int rc = carve_work(m, W_TWIN, &t->work_base, &end);
+  if (rc == GA3C_OK) rc = relay_arenas(m, to);
+  if (rc != GA3C_OK) twin_free(m);
+  return rc;
 }
 
 int ga3c_ddpg_twin_destroy(ga3c_ddpg* m) {
@@ -3440,12 +3235,16 @@ int ga3c_ddpg_soft_create(ga3c_ddpg* m, float log_alpha, float alpha_lr, float t
   if (rc == GA3C_OK) rc = vn::dalloc(&s->act_eps, (size_t)m->cfg.max_batch * m->L.A);
   if (rc == GA3C_OK && hipMemset(s->act_eps, 0, sizeof(float) * (size_t)m->cfg.max_batch * m->L.A) != hipSuccess)
     rc = fail(GA3C_EHIP, "hipMemset failed");
-  if (rc == GA3C_OK) rc = relay_soft(m, 2 * m->L.A, true, log_alpha);
+  // the Gaussian head's 2 A columns start as ga3c_ddpg_create leaves variables, log_alpha lies behind critic 2's twelve
+  Options to = m->opt;
+  to.soft = true;
+  to.head = 2 * m->L.A;
+  if (rc == GA3C_OK) rc = relay_arenas(m, to, log_alpha);
   if (rc != GA3C_OK) {
     soft_free(m);
     return rc;
   }
-  s->cfg.la = m->n - 1;
+  s->cfg.la = var_offset(m, SOFT_VAR_NAME);
   return GA3C_OK;
 }
 
@@ -3457,7 +3256,10 @@ int ga3c_ddpg_soft_destroy(ga3c_ddpg* m) {
   if (!m->soft) return fail(GA3C_ESTATE, "the handle has no soft actor-critic (ga3c_ddpg_soft_create)");
   if (m->actors || m->eval)
     return fail(GA3C_ESTATE, "soft_destroy: the handle's device actors or evaluation episodes step under its policy (destroy them first)");
-  CHK(relay_soft(m, m->L.A, false, 0.f));
+  Options to = m->opt;
+  to.soft = false;
+  to.head = 0;
+  CHK(relay_arenas(m, to));
   soft_free(m);
   return GA3C_OK;
 }
@@ -3500,7 +3302,9 @@ int ga3c_ddpg_dist_create(ga3c_ddpg* m, int32_t atoms, float vmin, float vmax) {
   m->dist = d;                                     // work_table sizes the rows by it
   float* end = nullptr;
   int rc = carve_work(m, W_DIST, &d->work_base, &end);
-  if (rc == GA3C_OK) rc = relay_head(m, atoms);
+  Options to = m->opt;                             // critic_output/W and /b, reshaped, start as ga3c_ddpg_create leaves variables
+  to.atoms = atoms;
+  if (rc == GA3C_OK) rc = relay_arenas(m, to);
   if (rc != GA3C_OK) dist_free(m);
   return rc;
 }
@@ -3511,7 +3315,9 @@ int ga3c_ddpg_dist_destroy(ga3c_ddpg* m) {
   std::lock_guard<std::mutex> tl(m->train_mu);
   std::lock_guard<std::mutex> lk(m->mu);
   if (!m->dist) return fail(GA3C_ESTATE, "the handle has no distributional critic (ga3c_ddpg_dist_create)");
-  CHK(relay_head(m, 1));
+  Options to = m->opt;
+  to.atoms = 1;
+  CHK(relay_arenas(m, to));
   dist_free(m);
   return GA3C_OK;
 }
@@ -3546,42 +3352,19 @@ int ga3c_ddpg_popart_create(ga3c_ddpg* m, float beta, float sigma_min, float sig
   p->beta = beta;
   p->smin = sigma_min;
   p->smax = sigma_max;
-  const int64_t n0 = m->L.off[NVARS], n1 = n0 + 2;
   // Every arena grows by the two statistics: mu = 0, nu = 1 in the value and the target arena, zero elsewhere.  The 26 keep
-  // their values; a prediction in flight has finished before its arena is freed.
-  float* grown[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // their values.
+  Options to = m->opt;
+  to.pop = true;
   m->pop = p;
-  auto build = [&]() -> int {
-    HIPCHK(hipStreamSynchronize(m->st));
-    for (int a = 0; a < m->narena; ++a) {
-      CHK(vn::dalloc(&grown[a], (size_t)n1));
-      HIPCHK(hipMemcpy(grown[a], m->arena[a], sizeof(float) * n0, hipMemcpyDeviceToDevice));
-      const float init[2] = {0.f, a <= 1 ? 1.f : 0.f};
-      HIPCHK(hipMemcpy(grown[a] + n0, init, sizeof init, hipMemcpyHostToDevice));
-    }
-    float* end = nullptr;
-    CHK(carve_work(m, W_POP, &p->work_base, &end));
-    return GA3C_OK;
-  };
-  const int rc = build();
+  float* end = nullptr;
+  int rc = carve_work(m, W_POP, &p->work_base, &end);
+  if (rc == GA3C_OK) rc = relay_arenas(m, to);
   if (rc != GA3C_OK) {
-    for (float* g : grown) (void)hipFree(g);
-    (void)hipGetLastError();
     pop_free(m);
     return rc;
   }
-  for (int a = 0; a < m->narena; ++a) {
-    (void)hipFree(m->arena[a]);
-    m->arena[a] = grown[a];
-  }
-  for (int i = 0; i < 2; ++i) {      // f32 (1,), not trainable: value and target copy in the checkpoint, no slots
-    const std::string name(POP_VAR_NAMES[i]);
-    vn::Var var{name, n0 + i, 1, 1, {1, 0}, {}};
-    var.ckpt = {{name + ":0", 0}, {target_name(name) + ":0", 1}};
-    m->vars.push_back(std::move(var));
-    m->tnames.push_back(target_name(name));
-  }
-  m->n = n1;
+  p->stat = var_offset(m, POP_VAR_NAMES[0]);
   return GA3C_OK;
 }
 
@@ -3604,7 +3387,7 @@ int ga3c_ddpg_popart_info(ga3c_ddpg* m, float* beta, float* mu, float* nu, float
   if (!m->pop) return fail(GA3C_ESTATE, "the handle has no PopArt (ga3c_ddpg_popart_create)");
   float stat[2];
   HIPCHK(hipStreamSynchronize(m->st));
-  HIPCHK(hipMemcpy(stat, m->arena[0] + m->L.off[NVARS], sizeof stat, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(stat, m->arena[0] + m->pop->stat, sizeof stat, hipMemcpyDeviceToHost));
   if (beta) *beta = m->pop->beta;
   if (mu) *mu = stat[0];
   if (nu) *nu = stat[1];
