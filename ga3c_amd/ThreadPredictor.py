@@ -37,26 +37,32 @@ class ThreadPredictor(Thread):
         self.seconds = {"pop": 0.0, "predict": 0.0, "respond": 0.0}     # where the loop's wall time went
         self.native = False
 
-    def _run_native(self, entry, handle, u8):
-        t, st = self.transport, nat.ServeStats()
+    def _serve_slices(self, serve_slice):
+        """The native loop (include/ga3c_host.h) in time slices: serve_slice(stats) is one call of the chosen entry; between
+        slices this thread looks at exit_flag and folds the counters."""
+        st = nat.ServeStats()
         self.native = True
+        while not self.exit_flag:
+            rc = serve_slice(st)
+            self.batches, self.served = st.batches, st.served
+            self.seconds = {"pop": st.ns_pop * 1e-9, "predict": st.ns_predict * 1e-9, "respond": st.ns_respond * 1e-9}
+            if rc < 0:
+                break                                   # transport shut down
+
+    def _run_native(self, entry, handle, u8):
+        t = self.transport
         # answering batch k beside the GPU's work on batch k+1 (ga3c_pq_serve_pipelined) when the model offers the split call
         split = getattr(self.server.model, "gather_entries_pipelined", None) if getattr(Config, "PIPELINED_PREDICTOR", True) else None
         begin_end = split() if split else None
         # ... and, with the engine's state cache in use, telling it each row's name (agent, request number)
         cached = getattr(self.server.model, "gather_entries_pipelined_cached", None) if getattr(self.server, "state_cache", False) else None
         cached = cached() if cached else None
-        while not self.exit_flag:
-            if cached:
-                rc = t.serve_pipelined_cached(cached[0], cached[1], handle, u8, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st)
-            elif begin_end:
-                rc = t.serve_pipelined(begin_end[0], begin_end[1], handle, u8, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st)
-            else:
-                rc = t.serve(entry, handle, u8, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st)
-            self.batches, self.served = st.batches, st.served
-            self.seconds = {"pop": st.ns_pop * 1e-9, "predict": st.ns_predict * 1e-9, "respond": st.ns_respond * 1e-9}
-            if rc < 0:
-                break                                   # transport shut down
+        if cached:
+            self._serve_slices(lambda st: t.serve_pipelined_cached(cached[0], cached[1], handle, u8, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st))
+        elif begin_end:
+            self._serve_slices(lambda st: t.serve_pipelined(begin_end[0], begin_end[1], handle, u8, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st))
+        else:
+            self._serve_slices(lambda st: t.serve(entry, handle, u8, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st))
 
     def _run_frames(self):
         """Device front-end: the popped slots hold raw emulator frames.  Push them into the agents' frame queues (the
@@ -66,8 +72,6 @@ class ThreadPredictor(Thread):
         entry = getattr(model, "frames_entry", None)
         if entry and getattr(Config, "NATIVE_PREDICTOR", True):     # the same loop in native code, one GPU round trip per batch
             fn, handle = entry()
-            st = nat.ServeStats()
-            self.native = True
             # Config.PIPELINED_FRAMES: answering batch k beside the GPU's work on batch k+1, the model's call in two halves
             # (ga3c_pq_serve_frames_pipelined; off by default -- it pays from ~500 agents per GPU on, DESIGN.md section 5;
             # the helper-thread modes of GA3C_RESPONDER belong to the one-piece loop)
@@ -77,15 +81,10 @@ class ThreadPredictor(Thread):
             if split and os.environ.get("GA3C_RESPONDER", "0") not in ("0", "3", ""):
                 split = None
             halves = split() if split else None
-            while not self.exit_flag:
-                if halves:
-                    rc = t.serve_frames_pipelined(halves[0], halves[1], halves[2], Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st)
-                else:
-                    rc = t.serve_frames(fn, handle, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st)
-                self.batches, self.served = st.batches, st.served
-                self.seconds = {"pop": st.ns_pop * 1e-9, "predict": st.ns_predict * 1e-9, "respond": st.ns_respond * 1e-9}
-                if rc < 0:
-                    break
+            if halves:
+                self._serve_slices(lambda st: t.serve_frames_pipelined(halves[0], halves[1], halves[2], Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st))
+            else:
+                self._serve_slices(lambda st: t.serve_frames(fn, handle, Config.PREDICTION_BATCH_SIZE, SERVE_SLICE_MS, st))
             return
         bmax = Config.PREDICTION_BATCH_SIZE
         ids = np.zeros(bmax, dtype=np.uint32)

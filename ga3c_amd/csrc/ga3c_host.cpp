@@ -940,42 +940,9 @@ int ga3c_pq_respond(ga3c_shm* shm, const uint32_t* ids, int32_t n, const float* 
   return GA3C_H_OK;
 }
 
-int ga3c_pq_serve(ga3c_shm* shm, ga3c_predict_rows_fn predict, void* net, int32_t u8, int32_t max_batch,
-                  int32_t slice_ms, ga3c_serve_stats* st) {
-  if (!shm || !predict || !st || max_batch < 1 || slice_ms < 1) return fail(GA3C_H_EINVAL, "bad argument");
-  name_this_thread("ga3c-predict");
-  Header* h = shm->hdr();
-  const int A = h->cfg.num_actions;
-  std::vector<uint32_t> ids((size_t)max_batch);
-  std::vector<int64_t> offs((size_t)max_batch);
-  std::vector<float> p((size_t)max_batch * A), v((size_t)max_batch);
-  const int64_t t_end = now_ns() + (int64_t)slice_ms * 1000000;
-  for (;;) {
-    const int64_t t0 = now_ns();
-    const int64_t left_ms = (t_end - t0 + 999999) / 1000000;
-    if (left_ms <= 0) return GA3C_H_OK;
-    const int n = ga3c_pq_pop_batch(shm, ids.data(), max_batch, (int)left_ms);
-    const int64_t t1 = now_ns();
-    st->ns_pop += t1 - t0;
-    if (n < 0) return n;
-    if (n == 0) continue;
-    for (int i = 0; i < n; ++i) {
-      if (ids[i] >= (uint32_t)h->cfg.max_agents) return fail(GA3C_H_EINVAL, "agent id %u out of range", ids[i]);
-      offs[i] = h->agents_off + (int64_t)ids[i] * h->agent_stride;
-    }
-    const int rc = predict(net, offs.data(), n, u8, p.data(), v.data(), nullptr);
-    if (rc < 0) return fail(GA3C_H_ECALLBACK, "predict callback failed with %d on a batch of %d", rc, n);
-    const int64_t t2 = now_ns();
-    const int rr = ga3c_pq_respond(shm, ids.data(), n, p.data(), v.data());
-    if (rr < 0) return rr;
-    const int64_t t3 = now_ns();
-    st->ns_predict += t2 - t1;
-    st->ns_respond += t3 - t2;
-    st->batches += 1;
-    st->served += n;
-    if (n > st->largest_batch) st->largest_batch = n;
-  }
-}
+}  // extern "C"
+
+namespace {
 
 // The answers of a batch handed to a helper thread, so that the loop below goes straight on to the next batch: answering
 // batch k itself, after it had popped and launched batch k+1, the loop woke k's agents ~19 us + their place in the
@@ -1051,282 +1018,222 @@ struct Responder {
   }
 };
 
-static int serve_pipelined_common(ga3c_shm* shm, ga3c_predict_begin_fn begin, ga3c_predict_begin_cached_fn begin_cached,
-                                  ga3c_predict_end_fn end, void* net, int32_t u8, int32_t max_batch, int32_t slice_ms,
-                                  ga3c_serve_stats* st) {
-  if (!shm || (!begin && !begin_cached) || !end || !st || max_batch < 1 || slice_ms < 1) return fail(GA3C_H_EINVAL, "bad argument");
+// ---- the native ThreadPredictor.run loop, once, behind the five ga3c_pq_serve* entries.  What an entry is (the same table
+// stands in include/ga3c_host.h):
+//
+//   entry                   rows named by                     call       GA3C_RESPONDER             batch k held over   served
+//                                                                                                   `begin` of k+1
+//   serve                   offsets                           one piece  ignored: answers at once   no                  rows
+//   serve_pipelined         offsets                           halves     0, 1, 2, 3                 mode 0              rows
+//   serve_pipelined_cached  offsets, agents, request numbers  halves     0, 1, 2, 3                 mode 0              rows
+//   serve_frames            offsets, agents, flags            one piece  1, 2; else at once         no                  predictions
+//   serve_frames_pipelined  offsets, agents, flags (to `end`  halves     3; else as 0               unless 3, and only  predictions
+//                           too)                                                                    with max_batch / 4
+//                                                                                                   requests queued (at
+//                                                                                                   least 1; GA3C_
+//                                                                                                   PIPELINE_MIN_QUEUED)
+//
+// (modes: the comment above.)  A one-piece call is the two-half form with an empty `begin`: pop, name the rows, call, answer
+// -- nothing is held, so the answering between the halves has nothing to do.  In every entry:
+//   - with a held batch only requests that are already queued are popped (timeout 0), otherwise the pop sleeps for the rest
+//     of the slice;
+//   - nothing is held when the call returns: at the slice's end, on a closed segment, an id out of range, a failing answer
+//     or a helper's error the held batch is answered first; a failing `begin` answers the held batch and not its own
+//     (GA3C_H_ECALLBACK); `end` runs after the held batch has been answered;
+//   - the helper's buffers stay untouched until it has finished (post() waits for the batch before, and there are two sets);
+//   - ns_pop is the time inside the pop; ns_predict runs from the pop's return to `begin`'s return, plus the time inside
+//     `end`; ns_respond is the time inside ga3c_pq_respond, the loop's or its helper's; largest_batch counts rows popped.
+struct ServeRows {                                           // what the engine's callables are given about a batch
+  const int64_t* offs;                                       // byte offset of each row's state slot
+  const int32_t* agents;                                     // NAME_REQUESTS, NAME_FLAGS
+  const int64_t* seqs;                                       // NAME_REQUESTS: request_number()
+  const uint32_t* flags;                                     // NAME_FLAGS: req_flags
+  int n;
+};
+enum RowNames { NAME_OFFSETS, NAME_REQUESTS, NAME_FLAGS };
+struct ServeEntry {                                          // the loop-invariant facts of an entry
+  RowNames names;
+  bool may_hold;                                             // batch k may be answered after `begin` of k+1 (GA3C_RESPONDER 3: never)
+  int hold_min_queued;                                       // ... only while this many requests are queued; 0 = no such rule
+  bool helper_modes;                                         // GA3C_RESPONDER 1 / 2 are honoured
+  bool served_predictions;                                   // `served` leaves out rows with GA3C_REQ_NO_PREDICT (NAME_FLAGS)
+  const char* begin_text;                                    // the callbacks' names in the failure texts
+  const char* end_text;
+};
+
+template <class Begin, class End>                            // int begin(const ServeRows&, int32_t* ticket), int end(const ServeRows&, int32_t ticket, float* p, float* v)
+int serve_loop(ga3c_shm* shm, const ServeEntry& e, Begin begin, End end, int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* st) {
+  if (!shm || !st || max_batch < 1 || slice_ms < 1) return fail(GA3C_H_EINVAL, "bad argument");
+  name_this_thread("ga3c-predict");
   Header* h = shm->hdr();
   const int A = h->cfg.num_actions;
-  // two batches in flight: `cur` is being computed while `prev` (results already fetched) is answered
-  std::vector<uint32_t> ids[2] = {std::vector<uint32_t>((size_t)max_batch), std::vector<uint32_t>((size_t)max_batch)};
-  std::vector<float> p[2] = {std::vector<float>((size_t)max_batch * A), std::vector<float>((size_t)max_batch * A)};
-  std::vector<float> v[2] = {std::vector<float>((size_t)max_batch), std::vector<float>((size_t)max_batch)};
-  std::vector<int64_t> offs((size_t)max_batch), seqs((size_t)max_batch);
-  std::vector<int32_t> agents((size_t)max_batch);
-  int cur = 0, n_prev = 0;
-  const int64_t t_end = now_ns() + (int64_t)slice_ms * 1000000;
-  name_this_thread("ga3c-predict");
+  const size_t mb = (size_t)max_batch;
+  // two sets of ids and results: `cur` is being computed while the other one (results already fetched) is held, or with the helper
+  std::vector<uint32_t> ids[2] = {std::vector<uint32_t>(mb), std::vector<uint32_t>(mb)};
+  std::vector<float> p[2] = {std::vector<float>(mb * A), std::vector<float>(mb * A)};
+  std::vector<float> v[2] = {std::vector<float>(mb), std::vector<float>(mb)};
+  std::vector<int64_t> offs(mb), seqs(mb);
+  std::vector<int32_t> agents(mb);
+  std::vector<uint32_t> flags(mb);
   const int mode = responder_mode();
-  const bool use_helper = mode == 1 || mode == 2;
+  const bool use_helper = e.helper_modes && (mode == 1 || mode == 2);
+  const bool hold = e.may_hold && !use_helper && mode != 3;
+  const int deep = hold ? e.hold_min_queued : 0;
   Responder helper;
   if (use_helper) {
     helper.shm = shm;
-    if (const char* e = getenv("GA3C_RESPONDER_SPIN_US")) helper.spin_us = atoi(e);
+    if (const char* s = getenv("GA3C_RESPONDER_SPIN_US")) helper.spin_us = atoi(s);
     helper.th = std::thread([&helper] { helper.run(); });
   }
   struct StopHelper {                                        // every return below: nothing is held across slices
     Responder& r; ga3c_serve_stats* st; bool on;
     ~StopHelper() { if (on) { r.stop(); st->ns_respond += r.ns; } }
   } stop_helper{helper, st, use_helper};
-  auto answer_prev = [&]() -> int {
-    if (n_prev == 0) return GA3C_H_OK;
-    const int64_t t0 = now_ns();
-    const int rr = ga3c_pq_respond(shm, ids[1 - cur].data(), n_prev, p[1 - cur].data(), v[1 - cur].data());
-    st->ns_respond += now_ns() - t0;
-    n_prev = 0;
+  int cur = 0, n_prev = 0;
+  // One clock reading ends a span and starts the next -- four a batch: after the pop, after `begin`, after `end`, after the
+  // answers -- so `now` is never older than the few instructions since the last span ended.
+  int64_t now = now_ns();
+  const int64_t t_end = now + (int64_t)slice_ms * 1000000;
+  auto lap = [&](int64_t& spent) {
+    const int64_t t = now_ns();
+    spent += t - now;
+    now = t;
+  };
+  auto respond = [&](int set, int cnt) -> int {
+    const int rr = ga3c_pq_respond(shm, ids[set].data(), cnt, p[set].data(), v[set].data());
+    lap(st->ns_respond);
     return rr;
   };
+  auto answer_prev = [&]() -> int {
+    const int cnt = n_prev;
+    n_prev = 0;
+    return cnt ? respond(1 - cur, cnt) : GA3C_H_OK;
+  };
   for (;;) {
-    const int64_t t0 = now_ns();
-    const int64_t left_ms = (t_end - t0 + 999999) / 1000000;
-    if (left_ms <= 0) return answer_prev();                  // nothing is held across slices
+    const int64_t left_ms = (t_end - now + 999999) / 1000000;
+    if (left_ms <= 0) return answer_prev();
     if (use_helper && helper.rc.load(std::memory_order_relaxed) < 0) return helper.rc.load();
-    // with a batch waiting to be answered only requests that are ALREADY queued are taken; otherwise sleep for one
+    // The held batch is answered beside the next one only when that next one is worth it: requests for at least `deep` rows
+    // are already queued.  With fewer the held answers go out first and the loop then sleeps for requests -- otherwise a
+    // closed population of agents splits into twice as many, half as large batches (256 native agents: 41 rows instead of
+    // 126), and what the overlap gives the fixed cost per batch takes back.
+    if (n_prev && deep > 0 && (int)ring_size(&h->req) < deep) {
+      const int rr = answer_prev();
+      if (rr < 0) return rr;
+    }
     const int n = ga3c_pq_pop_batch(shm, ids[cur].data(), max_batch, n_prev ? 0 : (int)left_ms);
-    const int64_t t1 = now_ns();
-    st->ns_pop += t1 - t0;
-    if (n < 0 && n != GA3C_H_ETIMEOUT) {
+    lap(st->ns_pop);
+    if (n < 0) {
       (void)answer_prev();
       return n;
     }
-    int ticket = -1;
+    const ServeRows rows{offs.data(), agents.data(), seqs.data(), flags.data(), n};
+    int ticket = -1, predicted = 0;
     if (n > 0) {
       for (int i = 0; i < n; ++i) {
-        if (ids[cur][i] >= (uint32_t)h->cfg.max_agents) {
+        const uint32_t id = ids[cur][i];
+        if (id >= (uint32_t)h->cfg.max_agents) {
           (void)answer_prev();
-          return fail(GA3C_H_EINVAL, "agent id %u out of range", ids[cur][i]);
+          return fail(GA3C_H_EINVAL, "agent id %u out of range", id);
         }
-        offs[i] = h->agents_off + (int64_t)ids[cur][i] * h->agent_stride;
-        if (begin_cached) {                                  // the row's name in the engine's state cache
-          agents[i] = (int32_t)ids[cur][i];
-          seqs[i] = request_number(shm->meta((int)ids[cur][i]));
+        offs[i] = h->agents_off + (int64_t)id * h->agent_stride;
+        if (e.names == NAME_OFFSETS) continue;
+        agents[i] = (int32_t)id;
+        if (e.names == NAME_REQUESTS) {                      // the row's name in the engine's state cache
+          seqs[i] = request_number(shm->meta((int)id));
+        } else {
+          flags[i] = shm->meta((int)id)->req_flags;
+          predicted += (flags[i] & GA3C_REQ_NO_PREDICT) ? 0 : 1;
         }
       }
-      const int rc = begin_cached ? begin_cached(net, offs.data(), agents.data(), seqs.data(), n, u8, &ticket)
-                                  : begin(net, offs.data(), n, u8, &ticket);
+      const int rc = begin(rows, &ticket);
       if (rc < 0) {
         (void)answer_prev();
-        return fail(GA3C_H_ECALLBACK, "predict callback (begin) failed with %d on a batch of %d", rc, n);
+        return fail(GA3C_H_ECALLBACK, "%s failed with %d on a batch of %d", e.begin_text, rc, n);
       }
+      lap(st->ns_predict);
     }
-    const int64_t t2 = now_ns();
-    st->ns_predict += t2 - t1;
-    const int rr = answer_prev();                            // beside the GPU's work on `cur` (helper: nothing left to answer)
+    int rr = answer_prev();                                  // beside the GPU's work on `cur`
     if (n > 0) {
-      const int64_t t3 = now_ns();
-      const int rc = end(net, ticket, n, p[cur].data(), v[cur].data());
-      st->ns_predict += now_ns() - t3;
-      if (rc < 0) return fail(GA3C_H_ECALLBACK, "predict callback (end) failed with %d on a batch of %d", rc, n);
+      const int rc = end(rows, ticket, p[cur].data(), v[cur].data());
+      lap(st->ns_predict);
+      if (rc < 0) return fail(GA3C_H_ECALLBACK, "%s failed with %d on a batch of %d", e.end_text, rc, n);
       st->batches += 1;
-      st->served += n;
+      st->served += e.served_predictions ? predicted : n;
       if (n > st->largest_batch) st->largest_batch = n;
-      if (mode == 3) {
-        const int64_t t4 = now_ns();
-        const int r3 = ga3c_pq_respond(shm, ids[cur].data(), n, p[cur].data(), v[cur].data());
-        st->ns_respond += now_ns() - t4;
-        if (r3 < 0) return r3;
-      } else if (use_helper) {
-        const int mine = (mode == 2 && n >= 8) ? n / 2 : 0;     // the buffers stay untouched until the helper has finished
-        helper.post(ids[cur].data() + mine, n - mine, p[cur].data() + (size_t)mine * A, v[cur].data() + mine);
-        if (mine) {
-          const int64_t t4 = now_ns();
-          const int r2 = ga3c_pq_respond(shm, ids[cur].data(), mine, p[cur].data(), v[cur].data());
-          st->ns_respond += now_ns() - t4;
-          if (r2 < 0) return r2;
-        }
-      } else {
+      if (hold) {
         n_prev = n;
+        cur = 1 - cur;
+      } else if (use_helper) {                               // (nothing was held: rr is GA3C_H_OK in these two branches)
+        const int mine = (mode == 2 && n >= 8) ? n / 2 : 0;  // mode 2: rows [0, n/2) the loop, [n/2, n) the helper
+        helper.post(ids[cur].data() + mine, n - mine, p[cur].data() + (size_t)mine * A, v[cur].data() + mine);
+        now = now_ns();                                      // (the wait inside post() is nobody's answering time)
+        if (mine) rr = respond(cur, mine);
+        cur = 1 - cur;
+      } else {
+        rr = respond(cur, n);
       }
-      cur = 1 - cur;
     }
     if (rr < 0) {
       (void)answer_prev();
       return rr;
     }
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ga3c_pq_serve(ga3c_shm* shm, ga3c_predict_rows_fn predict, void* net, int32_t u8, int32_t max_batch, int32_t slice_ms,
+                  ga3c_serve_stats* st) {
+  if (!predict) return fail(GA3C_H_EINVAL, "bad argument");
+  const ServeEntry e{NAME_OFFSETS, /*may_hold*/ false, 0, /*helper_modes*/ false, /*served_predictions*/ false, "", "predict callback"};
+  return serve_loop(shm, e, [](const ServeRows&, int32_t*) { return 0; },
+                    [=](const ServeRows& r, int32_t, float* p, float* v) { return predict(net, r.offs, r.n, u8, p, v, nullptr); },
+                    max_batch, slice_ms, st);
 }
 
 int ga3c_pq_serve_pipelined(ga3c_shm* shm, ga3c_predict_begin_fn begin, ga3c_predict_end_fn end, void* net, int32_t u8,
                             int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* st) {
-  if (!begin) return fail(GA3C_H_EINVAL, "bad argument");
-  return serve_pipelined_common(shm, begin, nullptr, end, net, u8, max_batch, slice_ms, st);
+  if (!begin || !end) return fail(GA3C_H_EINVAL, "bad argument");
+  const ServeEntry e{NAME_OFFSETS, /*may_hold*/ true, 0, /*helper_modes*/ true, /*served_predictions*/ false,
+                     "predict callback (begin)", "predict callback (end)"};
+  return serve_loop(shm, e, [=](const ServeRows& r, int32_t* ticket) { return begin(net, r.offs, r.n, u8, ticket); },
+                    [=](const ServeRows& r, int32_t ticket, float* p, float* v) { return end(net, ticket, r.n, p, v); },
+                    max_batch, slice_ms, st);
 }
 
 int ga3c_pq_serve_pipelined_cached(ga3c_shm* shm, ga3c_predict_begin_cached_fn begin, ga3c_predict_end_fn end, void* net,
                                    int32_t u8, int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* st) {
-  if (!begin) return fail(GA3C_H_EINVAL, "bad argument");
-  return serve_pipelined_common(shm, nullptr, begin, end, net, u8, max_batch, slice_ms, st);
+  if (!begin || !end) return fail(GA3C_H_EINVAL, "bad argument");
+  const ServeEntry e{NAME_REQUESTS, /*may_hold*/ true, 0, /*helper_modes*/ true, /*served_predictions*/ false,
+                     "predict callback (begin)", "predict callback (end)"};
+  return serve_loop(shm, e,
+                    [=](const ServeRows& r, int32_t* ticket) { return begin(net, r.offs, r.agents, r.seqs, r.n, u8, ticket); },
+                    [=](const ServeRows& r, int32_t ticket, float* p, float* v) { return end(net, ticket, r.n, p, v); },
+                    max_batch, slice_ms, st);
 }
 
 int ga3c_pq_serve_frames(ga3c_shm* shm, ga3c_serve_frames_fn serve, void* net, int32_t max_batch, int32_t slice_ms,
                          ga3c_serve_stats* st) {
-  if (!shm || !serve || !st || max_batch < 1 || slice_ms < 1) return fail(GA3C_H_EINVAL, "bad argument");
-  Header* h = shm->hdr();
-  const int A = h->cfg.num_actions;
-  // two sets of result buffers: the helper thread answers batch k out of one while batch k+1 is served into the other
-  std::vector<uint32_t> ids[2] = {std::vector<uint32_t>((size_t)max_batch), std::vector<uint32_t>((size_t)max_batch)};
-  std::vector<float> p[2] = {std::vector<float>((size_t)max_batch * A, 0.f), std::vector<float>((size_t)max_batch * A, 0.f)};
-  std::vector<float> v[2] = {std::vector<float>((size_t)max_batch, 0.f), std::vector<float>((size_t)max_batch, 0.f)};
-  std::vector<uint32_t> flags((size_t)max_batch);
-  std::vector<int32_t> agents((size_t)max_batch);
-  std::vector<int64_t> offs((size_t)max_batch);
-  const int64_t t_end = now_ns() + (int64_t)slice_ms * 1000000;
-  name_this_thread("ga3c-predict");
-  const int mode = responder_mode();
-  const bool use_helper = mode == 1 || mode == 2;
-  Responder helper;
-  if (use_helper) {
-    helper.shm = shm;
-    if (const char* e = getenv("GA3C_RESPONDER_SPIN_US")) helper.spin_us = atoi(e);
-    helper.th = std::thread([&helper] { helper.run(); });
-  }
-  struct StopHelper {
-    Responder& r; ga3c_serve_stats* st; bool on;
-    ~StopHelper() { if (on) { r.stop(); st->ns_respond += r.ns; } }
-  } stop_helper{helper, st, use_helper};
-  int cur = 0;
-  for (;;) {
-    const int64_t t0 = now_ns();
-    const int64_t left_ms = (t_end - t0 + 999999) / 1000000;
-    if (left_ms <= 0) return GA3C_H_OK;
-    if (use_helper && helper.rc.load(std::memory_order_relaxed) < 0) return helper.rc.load();
-    const int n = ga3c_pq_pop_batch(shm, ids[cur].data(), max_batch, (int)left_ms);
-    const int64_t t1 = now_ns();
-    st->ns_pop += t1 - t0;
-    if (n < 0) return n;
-    if (n == 0) continue;
-    int predicted = 0;
-    for (int i = 0; i < n; ++i) {
-      if (ids[cur][i] >= (uint32_t)h->cfg.max_agents) return fail(GA3C_H_EINVAL, "agent id %u out of range", ids[cur][i]);
-      offs[i] = h->agents_off + (int64_t)ids[cur][i] * h->agent_stride;
-      agents[i] = (int32_t)ids[cur][i];
-      flags[i] = shm->meta((int)ids[cur][i])->req_flags;
-      predicted += (flags[i] & GA3C_REQ_NO_PREDICT) ? 0 : 1;
-    }
-    const int rc = serve(net, offs.data(), agents.data(), flags.data(), n, p[cur].data(), v[cur].data());
-    if (rc < 0) return fail(GA3C_H_ECALLBACK, "serve callback failed with %d on a batch of %d", rc, n);
-    const int64_t t2 = now_ns();
-    st->ns_predict += t2 - t1;
-    if (use_helper) {
-      const int mine = (mode == 2 && n >= 8) ? n / 2 : 0;
-      helper.post(ids[cur].data() + mine, n - mine, p[cur].data() + (size_t)mine * A, v[cur].data() + mine);   // (waits for the answers of the batch before)
-      if (mine) {
-        const int rr = ga3c_pq_respond(shm, ids[cur].data(), mine, p[cur].data(), v[cur].data());
-        if (rr < 0) return rr;
-        st->ns_respond += now_ns() - t2;
-      }
-      cur = 1 - cur;
-    } else {
-      const int rr = ga3c_pq_respond(shm, ids[cur].data(), n, p[cur].data(), v[cur].data());
-      if (rr < 0) return rr;
-      st->ns_respond += now_ns() - t2;
-    }
-    st->batches += 1;
-    st->served += predicted;
-    if (n > st->largest_batch) st->largest_batch = n;
-  }
+  if (!serve) return fail(GA3C_H_EINVAL, "bad argument");
+  const ServeEntry e{NAME_FLAGS, /*may_hold*/ false, 0, /*helper_modes*/ true, /*served_predictions*/ true, "", "serve callback"};
+  return serve_loop(shm, e, [](const ServeRows&, int32_t*) { return 0; },
+                    [=](const ServeRows& r, int32_t, float* p, float* v) { return serve(net, r.offs, r.agents, r.flags, r.n, p, v); },
+                    max_batch, slice_ms, st);
 }
 
 int ga3c_pq_serve_frames_pipelined(ga3c_shm* shm, ga3c_serve_frames_begin_fn begin, ga3c_serve_frames_end_fn end, void* net,
                                    int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* st) {
-  if (!shm || !begin || !end || !st || max_batch < 1 || slice_ms < 1) return fail(GA3C_H_EINVAL, "bad argument");
-  Header* h = shm->hdr();
-  const int A = h->cfg.num_actions;
-  // `cur` is on the GPU while `prev` (results already fetched) is answered
-  std::vector<uint32_t> ids[2] = {std::vector<uint32_t>((size_t)max_batch), std::vector<uint32_t>((size_t)max_batch)};
-  std::vector<float> p[2] = {std::vector<float>((size_t)max_batch * A, 0.f), std::vector<float>((size_t)max_batch * A, 0.f)};
-  std::vector<float> v[2] = {std::vector<float>((size_t)max_batch, 0.f), std::vector<float>((size_t)max_batch, 0.f)};
-  std::vector<uint32_t> flags((size_t)max_batch);
-  std::vector<int32_t> agents((size_t)max_batch);
-  std::vector<int64_t> offs((size_t)max_batch);
-  const int64_t t_end = now_ns() + (int64_t)slice_ms * 1000000;
-  name_this_thread("ga3c-predict");
-  const bool at_once = responder_mode() == 3;                // answer a batch before the next pop
-  // The held batch is answered beside the next one only when that next one is worth it: requests for at least `deep` rows
-  // are already queued (a quarter of a full batch; GA3C_PIPELINE_MIN_QUEUED).  With fewer the held answers go out first and
-  // the loop then sleeps for requests -- otherwise a closed population of agents splits into twice as many, half as large
-  // batches (256 native agents: 41 rows instead of 126), and what the overlap gives the fixed cost per batch takes back.
-  int deep = max_batch / 4 > 1 ? max_batch / 4 : 1;
-  if (const char* e = getenv("GA3C_PIPELINE_MIN_QUEUED")) deep = atoi(e);
-  int cur = 0, n_prev = 0;
-  auto answer_prev = [&]() -> int {
-    if (n_prev == 0) return GA3C_H_OK;
-    const int64_t t0 = now_ns();
-    const int rr = ga3c_pq_respond(shm, ids[1 - cur].data(), n_prev, p[1 - cur].data(), v[1 - cur].data());
-    st->ns_respond += now_ns() - t0;
-    n_prev = 0;
-    return rr;
-  };
-  for (;;) {
-    const int64_t t0 = now_ns();
-    const int64_t left_ms = (t_end - t0 + 999999) / 1000000;
-    if (left_ms <= 0) return answer_prev();                  // nothing is held across slices
-    if (n_prev && (int)ring_size(&h->req) < deep) {
-      const int rr = answer_prev();
-      if (rr < 0) return rr;
-    }
-    const int64_t t0b = now_ns();
-    const int n = ga3c_pq_pop_batch(shm, ids[cur].data(), max_batch, n_prev ? 0 : (int)left_ms);
-    const int64_t t1 = now_ns();
-    st->ns_pop += t1 - t0b;
-    if (n < 0 && n != GA3C_H_ETIMEOUT) {
-      (void)answer_prev();
-      return n;
-    }
-    int ticket = -1, predicted = 0;
-    if (n > 0) {
-      for (int i = 0; i < n; ++i) {
-        if (ids[cur][i] >= (uint32_t)h->cfg.max_agents) {
-          (void)answer_prev();
-          return fail(GA3C_H_EINVAL, "agent id %u out of range", ids[cur][i]);
-        }
-        offs[i] = h->agents_off + (int64_t)ids[cur][i] * h->agent_stride;
-        agents[i] = (int32_t)ids[cur][i];
-        flags[i] = shm->meta((int)ids[cur][i])->req_flags;
-        predicted += (flags[i] & GA3C_REQ_NO_PREDICT) ? 0 : 1;
-      }
-      const int rc = begin(net, offs.data(), agents.data(), flags.data(), n, &ticket);
-      if (rc < 0) {
-        (void)answer_prev();
-        return fail(GA3C_H_ECALLBACK, "serve callback (begin) failed with %d on a batch of %d", rc, n);
-      }
-    }
-    const int64_t t2 = now_ns();
-    st->ns_predict += t2 - t1;
-    const int rr = answer_prev();                            // beside the GPU's work on `cur`
-    if (n > 0) {
-      const int64_t t3 = now_ns();
-      const int rc = end(net, ticket, flags.data(), n, p[cur].data(), v[cur].data());
-      st->ns_predict += now_ns() - t3;
-      if (rc < 0) return fail(GA3C_H_ECALLBACK, "serve callback (end) failed with %d on a batch of %d", rc, n);
-      st->batches += 1;
-      st->served += predicted;
-      if (n > st->largest_batch) st->largest_batch = n;
-      if (at_once) {
-        const int64_t t4 = now_ns();
-        const int r3 = ga3c_pq_respond(shm, ids[cur].data(), n, p[cur].data(), v[cur].data());
-        st->ns_respond += now_ns() - t4;
-        if (r3 < 0) return r3;
-      } else {
-        n_prev = n;
-        cur = 1 - cur;
-      }
-    }
-    if (rr < 0) {
-      (void)answer_prev();
-      return rr;
-    }
-  }
+  if (!begin || !end) return fail(GA3C_H_EINVAL, "bad argument");
+  int deep = max_batch / 4 > 1 ? max_batch / 4 : 1;          // a quarter of a full batch
+  if (const char* s = getenv("GA3C_PIPELINE_MIN_QUEUED")) deep = atoi(s);
+  const ServeEntry e{NAME_FLAGS, /*may_hold*/ true, deep, /*helper_modes*/ false, /*served_predictions*/ true,
+                     "serve callback (begin)", "serve callback (end)"};
+  return serve_loop(shm, e, [=](const ServeRows& r, int32_t* ticket) { return begin(net, r.offs, r.agents, r.flags, r.n, ticket); },
+                    [=](const ServeRows& r, int32_t ticket, float* p, float* v) { return end(net, ticket, r.flags, r.n, p, v); },
+                    max_batch, slice_ms, st);
 }
 
 int ga3c_tq_acquire(ga3c_shm* shm, int32_t timeout_ms) {

@@ -149,60 +149,72 @@ int ga3c_pq_respond(ga3c_shm* shm, const uint32_t* ids, int32_t n, const float* 
 int ga3c_pq_set_linger(ga3c_shm* shm, int32_t linger_us, int32_t min_batch);
 
 /* The whole ThreadPredictor.run loop (ThreadPredictor.py:46-66) in native code, so that a predictor thread holds no
- * interpreter lock between batches: pop_batch -> byte offsets of the popped agents' states -> `predict` (the
- * signature of ga3c_net_predict_gather, include/ga3c_abi.h) -> respond.  Runs for about `slice_ms`, then returns
- * GA3C_H_OK so the caller can look at its exit flag and fold `stats` (accumulated, never reset here) into its
- * counters; GA3C_H_ECLOSED once the segment is shut down; GA3C_H_ECALLBACK if `predict` fails (the requests
- * of that batch are NOT answered: the caller is expected to stop the server). */
-typedef int (*ga3c_predict_rows_fn)(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v,
-                                    float* z);
+ * interpreter lock between batches: pop_batch -> name the popped rows -> the engine's call -> respond.  One loop behind five
+ * entries; a call runs for about `slice_ms`, then returns GA3C_H_OK so that the caller can look at its exit flag and fold
+ * `stats` (accumulated, never reset here) into its counters; GA3C_H_ECLOSED once the segment is shut down; GA3C_H_ECALLBACK
+ * if a callback fails (the requests of that batch are NOT answered: the caller is expected to stop the server);
+ * GA3C_H_EINVAL for a null argument, max_batch < 1 or slice_ms < 1.  The callbacks have the signatures of the engine's calls
+ * (include/ga3c_abi.h): ga3c_net_predict_gather, ga3c_net_predict_gather_begin / _begin_cached / _end, ga3c_net_serve_frames,
+ * ga3c_net_serve_frames_begin / _end.
+ *
+ *   entry                   rows named by                     call       GA3C_RESPONDER             batch k held over   served
+ *                                                                                                   `begin` of k+1
+ *   serve                   offsets                           one piece  ignored: answers at once   no                  rows
+ *   serve_pipelined         offsets                           halves     0, 1, 2, 3                 mode 0              rows
+ *   serve_pipelined_cached  offsets, agents, request numbers  halves     0, 1, 2, 3                 mode 0              rows
+ *   serve_frames            offsets, agents, flags            one piece  1, 2; else at once         no                  predictions
+ *   serve_frames_pipelined  offsets, agents, flags (to `end`  halves     3; else as 0               unless 3, and only  predictions
+ *                           too)                                                                    with max_batch / 4
+ *                                                                                                   requests queued
+ *
+ * Rows: the byte offset of each popped agent's state slot; the agent's id and the number of the request that carried the
+ * state (ga3c_pq_request_seq), for an engine that keeps the states it reads (ga3c_net_state_cache_config); or the agent's id
+ * and its request's flags (ga3c_pq_submit_flags), for raw-frame requests.  `served` counts rows, or the predictions made
+ * (rows without GA3C_REQ_NO_PREDICT).
+ * Halves: the loop answers batch k (a futex wake per agent that is asleep, ~1 us each) after it has popped and ENQUEUED
+ * (`begin`) batch k+1, beside the GPU's work on it and before `end` of k+1; with nothing queued batch k is answered at once.
+ * While a batch is held only requests that are already queued are popped.  serve_frames_pipelined holds a batch only while
+ * requests for a quarter of max_batch (at least 1; GA3C_PIPELINE_MIN_QUEUED in the environment) are queued: with fewer the
+ * held answers go out first -- a small closed population of agents would otherwise travel as twice as many, half as large
+ * batches.
+ * GA3C_RESPONDER in the environment moves the answering where the table lists the value: 0 = the default above; 1 = to a
+ * helper thread of the call, as soon as the results are there (worth it only while wakes land on cold cores); 2 = loop and
+ * helper share a batch of 8 rows or more (the loop answers the first n/2); 3 = the loop, always before it pops the next
+ * batch.  A value an entry does not list behaves as 0 there.
+ * Nothing is held when a call returns: what the loop or its helper holds is answered first, on every path -- also when
+ * `begin` of the next batch fails (that batch is not answered).
+ * stats: ns_pop is the time inside the pop; ns_predict runs from the pop's return to `begin`'s return, plus the time inside
+ * `end` (a one-piece call is all `end`); ns_respond is the time inside ga3c_pq_respond, the loop's or its helper's;
+ * largest_batch counts rows popped. */
 typedef struct ga3c_serve_stats {
   int64_t batches, served;
   int64_t ns_pop, ns_predict, ns_respond;
   int64_t largest_batch, reserved[2];
 } ga3c_serve_stats;
-int ga3c_pq_serve(ga3c_shm* shm, ga3c_predict_rows_fn predict, void* net, int32_t u8, int32_t max_batch,
-                  int32_t slice_ms, ga3c_serve_stats* stats);
-/* The same loop with the answering off the GPU's critical path: the loop answers batch k (a futex wake per agent that is
- * asleep, ~1 us each) after it has popped and ENQUEUED (`begin`) batch k+1, beside the GPU's work on it; with nothing
- * queued batch k is answered at once.  GA3C_RESPONDER in the environment moves the answering: 1 = to a helper thread of the
- * call, as soon as `end` has returned the results (round 3's default, worth it only while wakes land on cold cores);
- * 2 = loop and helper share a batch; 3 = the loop, always before it pops the next batch; 0 = the default above.  Nothing
- * is held when the call returns.  `begin` / `end` have the signatures of ga3c_net_predict_gather_begin / _end
- * (include/ga3c_abi.h).  Same return values. */
+typedef int (*ga3c_predict_rows_fn)(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v,
+                                    float* z);
 typedef int (*ga3c_predict_begin_fn)(void* net, const int64_t* offsets, int32_t batch, int32_t u8, int32_t* ticket);
-typedef int (*ga3c_predict_end_fn)(void* net, int32_t ticket, int32_t batch, float* p, float* v);
-int ga3c_pq_serve_pipelined(ga3c_shm* shm, ga3c_predict_begin_fn begin, ga3c_predict_end_fn end, void* net, int32_t u8,
-                            int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* stats);
-/* ... and for an engine that keeps the states it reads (ga3c_net_state_cache_config, include/ga3c_abi.h): `begin` has the
- * signature of ga3c_net_predict_gather_begin_cached and also gets each row's name -- the agent's id and the number of the
- * request that carried the state.  ga3c_pq_request_seq: that number for the agent's newest request (in flight, or answered
- * last), which is how an agent names the state of an experience instead of shipping it (rollout rows of 16 bytes: request
- * number i64, agent id i32; ga3c_tq_collect's row_seq / row_agent). */
 typedef int (*ga3c_predict_begin_cached_fn)(void* net, const int64_t* offsets, const int32_t* agents, const int64_t* seqs,
                                             int32_t batch, int32_t u8, int32_t* ticket);
-int ga3c_pq_serve_pipelined_cached(ga3c_shm* shm, ga3c_predict_begin_cached_fn begin, ga3c_predict_end_fn end, void* net,
-                                   int32_t u8, int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* stats);
-int ga3c_pq_request_seq(ga3c_shm* shm, int32_t agent, int64_t* seq);
-/* The same loop for raw-frame requests (ga3c_pq_submit_flags): `serve` has the signature of ga3c_net_serve_frames
- * (include/ga3c_abi.h) and gets the popped slots' offsets, agent ids and request flags; stats->served counts the
- * predictions made (requests without GA3C_REQ_NO_PREDICT).  The loop answers a batch before it pops the next one
- * (GA3C_RESPONDER = 1 / 2: a helper thread of the call does, or shares it, as in ga3c_pq_serve_pipelined). */
+typedef int (*ga3c_predict_end_fn)(void* net, int32_t ticket, int32_t batch, float* p, float* v);
 typedef int (*ga3c_serve_frames_fn)(void* net, const int64_t* offsets, const int32_t* agents, const uint32_t* flags,
                                     int32_t n, float* p, float* v);
-int ga3c_pq_serve_frames(ga3c_shm* shm, ga3c_serve_frames_fn serve, void* net, int32_t max_batch, int32_t slice_ms,
-                         ga3c_serve_stats* stats);
-/* ... and with the engine's call in two halves (ga3c_net_serve_frames_begin / _end): the loop pops batch k + 1, begins it,
- * answers batch k -- a system call per sleeping agent, ~1.2 us a row, beside the GPU's work on k + 1 instead of in front of
- * it -- and ends k + 1, but only when requests for at least a quarter of max_batch are already queued (GA3C_PIPELINE_MIN_QUEUED):
- * with fewer the held answers go out first, as in the loop above -- a small closed population of agents would otherwise
- * travel as twice as many, half as large batches.  With a batch waiting to be answered only requests that are already
- * queued are popped.  What the loop holds is answered before it returns; GA3C_RESPONDER = 3 answers every batch at once. */
 typedef int (*ga3c_serve_frames_begin_fn)(void* net, const int64_t* offsets, const int32_t* agents, const uint32_t* flags,
                                           int32_t n, int32_t* ticket);
 typedef int (*ga3c_serve_frames_end_fn)(void* net, int32_t ticket, const uint32_t* flags, int32_t n, float* p, float* v);
+int ga3c_pq_serve(ga3c_shm* shm, ga3c_predict_rows_fn predict, void* net, int32_t u8, int32_t max_batch,
+                  int32_t slice_ms, ga3c_serve_stats* stats);
+int ga3c_pq_serve_pipelined(ga3c_shm* shm, ga3c_predict_begin_fn begin, ga3c_predict_end_fn end, void* net, int32_t u8,
+                            int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* stats);
+int ga3c_pq_serve_pipelined_cached(ga3c_shm* shm, ga3c_predict_begin_cached_fn begin, ga3c_predict_end_fn end, void* net,
+                                   int32_t u8, int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* stats);
+int ga3c_pq_serve_frames(ga3c_shm* shm, ga3c_serve_frames_fn serve, void* net, int32_t max_batch, int32_t slice_ms,
+                         ga3c_serve_stats* stats);
 int ga3c_pq_serve_frames_pipelined(ga3c_shm* shm, ga3c_serve_frames_begin_fn begin, ga3c_serve_frames_end_fn end, void* net,
                                    int32_t max_batch, int32_t slice_ms, ga3c_serve_stats* stats);
+/* The number of the agent's newest request (in flight, or answered last): how an agent names the state of an experience
+ * instead of shipping it (rollout rows of 16 bytes: request number i64, agent id i32; ga3c_tq_collect's row_seq / row_agent). */
+int ga3c_pq_request_seq(ga3c_shm* shm, int32_t agent, int64_t* seq);
 
 /* training queue: agent side (ProcessAgent.py:175), trainer side (ThreadTrainer.py:49-59) */
 int ga3c_tq_acquire(ga3c_shm* shm, int32_t timeout_ms);                 /* -> free slot id */

@@ -37,6 +37,33 @@ static int fake_end(void*, int32_t ticket, int32_t batch, float* p, float* v) {
   if (ticket != batch) return -1;
   return fake_predict_rows(nullptr, t_offs, batch, 1, p, v, nullptr);
 }
+// ... for ga3c_net_predict_gather_begin_cached (ga3c_pq_serve_pipelined_cached): every row must carry its agent's id and the
+// number of the request in flight
+static int fake_begin_cached(void*, const int64_t* offsets, const int32_t* agents, const int64_t* seqs, int32_t batch, int32_t,
+                             int32_t* ticket) {
+  for (int i = 0; i < batch; ++i) {
+    int64_t seq = -1;
+    if (offsets[i] != ga3c_shm_state_offset(g_shm, agents[i]) || ga3c_pq_request_seq(g_shm, agents[i], &seq) != 0 || seq != seqs[i])
+      return -1;
+  }
+  return fake_begin(nullptr, offsets, batch, 1, ticket);
+}
+// ... and for ga3c_net_serve_frames and its two halves (ga3c_pq_serve_frames, ga3c_pq_serve_frames_pipelined): the agents
+// here submit without flags, so every row is a prediction
+static int fake_frames_begin(void*, const int64_t* offsets, const int32_t* agents, const uint32_t* flags, int32_t n, int32_t* ticket) {
+  for (int i = 0; i < n; ++i)
+    if (offsets[i] != ga3c_shm_state_offset(g_shm, agents[i]) || flags[i] != 0) return -1;
+  return fake_begin(nullptr, offsets, n, 1, ticket);
+}
+static int fake_frames_end(void*, int32_t ticket, const uint32_t* flags, int32_t n, float* p, float* v) {
+  for (int i = 0; i < n; ++i)
+    if (flags[i] != 0) return -1;
+  return fake_end(nullptr, ticket, n, p, v);
+}
+static int fake_frames(void*, const int64_t* offsets, const int32_t* agents, const uint32_t* flags, int32_t n, float* p, float* v) {
+  int32_t ticket = -1;
+  return fake_frames_begin(nullptr, offsets, agents, flags, n, &ticket) < 0 ? -1 : fake_frames_end(nullptr, ticket, flags, n, p, v);
+}
 #define REQUIRE(c) do { if (!(c)) { std::fprintf(stderr, "FAILED %s line %d\n", #c, __LINE__); failures++; } } while (0)
 
 int main(int argc, char** argv) {
@@ -63,24 +90,25 @@ int main(int argc, char** argv) {
   }
   std::atomic<long> served{0}, trained_rows{0}, produced_rows{0};
   std::vector<std::thread> th;
-  th.emplace_back([&] {     // one predictor runs the native loop
-    ga3c_serve_stats st;
-    std::memset(&st, 0, sizeof st);
-    int rc;
-    while ((rc = ga3c_pq_serve(shm, fake_predict_rows, nullptr, 1, 8, 20, &st)) == GA3C_H_OK) {}
-    REQUIRE(rc == GA3C_H_ECLOSED);
-    REQUIRE(st.largest_batch <= 8);
-    served += st.served;
-  });
-  th.emplace_back([&] {     // ... and one the pipelined native loop (answers batch k after batch k+1 has been begun)
-    ga3c_serve_stats st;
-    std::memset(&st, 0, sizeof st);
-    int rc;
-    while ((rc = ga3c_pq_serve_pipelined(shm, fake_begin, fake_end, nullptr, 1, 8, 20, &st)) == GA3C_H_OK) {}
-    REQUIRE(rc == GA3C_H_ECLOSED);
-    REQUIRE(st.largest_batch <= 8);
-    served += st.served;
-  });
+  // one predictor thread per entry of the native loop: rows in one piece; pipelined (answers batch k after batch k+1 has been
+  // begun, or through its helper thread: GA3C_RESPONDER in the environment, tests/test_host_tsan.py); the same with named rows;
+  // raw-frame requests in one piece and pipelined
+  auto native = [&](auto slice) {
+    th.emplace_back([&, slice] {
+      ga3c_serve_stats st;
+      std::memset(&st, 0, sizeof st);
+      int rc;
+      while ((rc = slice(&st)) == GA3C_H_OK) {}
+      REQUIRE(rc == GA3C_H_ECLOSED);
+      REQUIRE(st.largest_batch <= 8);
+      served += st.served;
+    });
+  };
+  native([shm](ga3c_serve_stats* st) { return ga3c_pq_serve(shm, fake_predict_rows, nullptr, 1, 8, 20, st); });
+  native([shm](ga3c_serve_stats* st) { return ga3c_pq_serve_pipelined(shm, fake_begin, fake_end, nullptr, 1, 8, 20, st); });
+  native([shm](ga3c_serve_stats* st) { return ga3c_pq_serve_pipelined_cached(shm, fake_begin_cached, fake_end, nullptr, 1, 8, 20, st); });
+  native([shm](ga3c_serve_stats* st) { return ga3c_pq_serve_frames(shm, fake_frames, nullptr, 8, 20, st); });
+  native([shm](ga3c_serve_stats* st) { return ga3c_pq_serve_frames_pipelined(shm, fake_frames_begin, fake_frames_end, nullptr, 8, 20, st); });
   for (int p = 0; p < n_pred; ++p)
     th.emplace_back([&] {
       uint32_t ids[8];

@@ -18,7 +18,10 @@ def test_transport_stress_is_sanitizer_clean(tmp_path, sanitizer):
     subprocess.check_call(cmd)
     # several copies at once: CPU oversubscription deschedules threads inside the ring's claim/publish windows
     # (this is how the "ring momentarily full behind a descheduled consumer" case was found)
-    procs = [subprocess.Popen([exe, "300"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for _ in range(6)]
+    # ... each with its own GA3C_RESPONDER (include/ga3c_host.h), so that the native loops' helper thread runs here too
+    base = {k: v for k, v in os.environ.items() if k != "GA3C_RESPONDER"}
+    envs = [base] + [dict(base, GA3C_RESPONDER=mode) for mode in ("1", "2", "3", "2", "1")]
+    procs = [subprocess.Popen([exe, "300"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env) for env in envs]
     for pr in procs:
         out, err = pr.communicate(timeout=240)
         if sanitizer == "thread" and "FATAL: ThreadSanitizer" in err and "unexpected memory mapping" in err:
@@ -31,7 +34,7 @@ def test_transport_stress_is_sanitizer_clean(tmp_path, sanitizer):
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("sanitizer", ["thread", None])
 def test_a_herd_of_agents_behind_few_predictors(tmp_path, sanitizer):
-    """96 agent threads, 1 native predictor loop + 4 plain ones: every request answered once with its own values, every
+    """96 agent threads, the 5 native predictor loops + 4 plain ones: every request answered once with its own values, every
     rollout trained once.  The ring's push is a ticket (fetch_add) since a compare-and-swap loop collapsed under such herds
     (profiles/README.md); this holds it to the same invariants as the small case, with and without ThreadSanitizer."""
     exe = str(tmp_path / "queue_herd")

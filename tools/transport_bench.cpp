@@ -1,11 +1,12 @@
 // tools/transport_bench.cpp -- what one prediction costs the HOST, with the GPU replaced by a timer.
 // N agent threads speak the agent side of include/ga3c_host.h (state into the slot, submit, sleep on the slot's futex), K
-// predictor threads run the product's native serve loop (ga3c_pq_serve_pipelined) over begin / end callbacks that stand
-// in for the network: `end` returns `latency_us` after `begin` (spinning or sleeping, as the HIP runtime's wait would).
+// predictor threads run one of the product's five native serve entries (ga3c_pq_serve*, include/ga3c_host.h; the default is
+// ga3c_pq_serve_pipelined) over callbacks that stand in for the network: `end` returns `latency_us` after `begin` (spinning
+// or sleeping, as the HIP runtime's wait would); a one-piece entry's callback is the two in one.
 // Prints predictions/s, the mean batch and the CPU time per prediction split into agents / predictor loops / the rest
 // (answering helpers).  Runs without a GPU: a development aid for the transport, not part of the product.
 //   g++ -O2 -std=c++17 -pthread -I include -o tools/transport_bench tools/transport_bench.cpp -L ga3c_amd -lga3c_host -Wl,-rpath,$PWD/ga3c_amd
-//   tools/transport_bench <agents> <predictors> <seconds> <latency_us> [spin|sleep] [agent_work_us]
+//   tools/transport_bench <agents> <predictors> <seconds> <latency_us> [spin|sleep] [agent_work_us] [rows|pipelined|cached|frames|frames_pipelined]
 #include <sys/resource.h>
 #include <time.h>
 #include <unistd.h>
@@ -64,9 +65,28 @@ static int fake_end(void* net, int32_t ticket, int32_t batch, float* p, float* v
   }
   return 0;
 }
+// ... and the stand-ins of the other entries: named rows, raw-frame requests, and the one-piece calls (begin and end in one)
+static int fake_begin_cached(void* net, const int64_t* offsets, const int32_t*, const int64_t*, int32_t batch, int32_t u8, int32_t* ticket) {
+  return fake_begin(net, offsets, batch, u8, ticket);
+}
+static int fake_frames_begin(void* net, const int64_t* offsets, const int32_t*, const uint32_t*, int32_t n, int32_t* ticket) {
+  return fake_begin(net, offsets, n, 1, ticket);
+}
+static int fake_frames_end(void* net, int32_t ticket, const uint32_t*, int32_t n, float* p, float* v) { return fake_end(net, ticket, n, p, v); }
+static int fake_rows(void* net, const int64_t* offsets, int32_t batch, int32_t u8, float* p, float* v, float*) {
+  int32_t ticket = 0;
+  fake_begin(net, offsets, batch, u8, &ticket);
+  return fake_end(net, ticket, batch, p, v);
+}
+static int fake_frames(void* net, const int64_t* offsets, const int32_t*, const uint32_t*, int32_t n, float* p, float* v) {
+  return fake_rows(net, offsets, n, 1, p, v, nullptr);
+}
 
 int main(int argc, char** argv) {
-  if (argc < 5) { fprintf(stderr, "usage: %s <agents> <predictors> <seconds> <latency_us> [spin|sleep] [agent_work_us]\n", argv[0]); return 2; }
+  const char* usage = "usage: %s <agents> <predictors> <seconds> <latency_us> [spin|sleep] [agent_work_us] [rows|pipelined|cached|frames|frames_pipelined]\n";
+  if (argc < 5) { fprintf(stderr, usage, argv[0]); return 2; }
+  const std::string entry = argc > 7 ? argv[7] : "pipelined";
+  if (entry != "rows" && entry != "pipelined" && entry != "cached" && entry != "frames" && entry != "frames_pipelined") { fprintf(stderr, usage, argv[0]); return 2; }
   const int n = atoi(argv[1]), np = atoi(argv[2]);
   const double seconds = atof(argv[3]);
   const int latency = atoi(argv[4]);
@@ -114,7 +134,13 @@ int main(int argc, char** argv) {
       ga3c_serve_stats st;
       memset(&st, 0, sizeof st);
       while (!stop.load(std::memory_order_relaxed)) {
-        const int rc = ga3c_pq_serve_pipelined(shm, fake_begin, fake_end, &nets[k], 1, 128, 50, &st);
+        void* net = &nets[k];
+        const int rc = entry == "rows"     ? ga3c_pq_serve(shm, fake_rows, net, 1, 128, 50, &st)
+                       : entry == "cached" ? ga3c_pq_serve_pipelined_cached(shm, fake_begin_cached, fake_end, net, 1, 128, 50, &st)
+                       : entry == "frames" ? ga3c_pq_serve_frames(shm, fake_frames, net, 128, 50, &st)
+                       : entry == "frames_pipelined"
+                           ? ga3c_pq_serve_frames_pipelined(shm, fake_frames_begin, fake_frames_end, net, 128, 50, &st)
+                           : ga3c_pq_serve_pipelined(shm, fake_begin, fake_end, net, 1, 128, 50, &st);
         if (rc != 0) break;
       }
       batches.fetch_add(st.batches); served.fetch_add(st.served);
