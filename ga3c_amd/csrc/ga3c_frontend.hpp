@@ -52,7 +52,8 @@ __device__ __forceinline__ uint32_t fe_clip8(int32_t acc) {
 }
 
 constexpr int FE_MAXG = 10;        // pixel groups per thread: frames up to 4 * 10 * 1024 = 40,960 pixels (250 x 160 fits)
-constexpr int FE_MAXK = 8;         // taps per output the register-resident horizontal pass holds (downscale <= 3.5x)
+constexpr int FE_MAXK = 8;         // taps per output the register-resident horizontal pass holds; the tables' tap count is odd
+                                   // (2 * ceil(W / 84) + 1), so 7 is the most admitted: W <= 252, a downscale of 3.0x
 static_assert(FE_MAXK == 8, "the horizontal pass reads exactly two shifted dwords of source bytes per output");
 
 // 4 consecutive pixels' r, g, b out of their 12 (C = 3) or 16 (C = 4) contiguous bytes
