@@ -178,6 +178,18 @@ struct Pendulum {
   }
 };
 
+// What "Pendulum-v0" means to the DDPG handle's device actors and evaluator (ga3c_ddpg_task_create, DESIGN.md 8t, 8w;
+// tests/ddpg_task_oracle.py is the same statement), by value in the arguments of their kernels.
+struct PendulumTask {
+  int clip;                  // the action is clipped to [-1, 1], not wrapped
+  int truncate;              // the time limit ends the episode and is no terminal state: the row's done stays 0
+  int reset_observation;     // a reset rewrites the observation from the reset physics
+  double reward_scale, reward_offset;      // reward = -cost scale + offset
+
+  // The fork's task, EnvironmentPend.Environment's: what a handle steps under until ga3c_ddpg_task_create says otherwise.
+  static constexpr PendulumTask fork() { return {0, 0, 0, 0.005, -1.0}; }
+};
+
 // Pendulum under an action that can leave [-1, 1]: the DDPG actor's tanh output plus Ornstein-Uhlenbeck noise (Config.DEVICE_DDPG,
 // DESIGN.md 8l).  check_bounds(a, 1, -1, turnaround) is reachable there and is applied as EnvironmentPend.check_bounds applies
 // it, in f64 to the f32 action; its operands are positive, so fmod is Python's %.  What it returns lies in [-1, 1], so
@@ -197,37 +209,15 @@ struct PendulumBounded : Pendulum {
     return v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v);
   }
 
-  __device__ static void step(double* s, const float* a, int* elapsed, double* reward, int* done) {
-    const double bounded = check_bounds(a[0]);
-    Pendulum::step(s, &bounded, elapsed, reward, done);
-  }
-
-  // The step under a task (PendulumTask below): its bound, then Pendulum's physics and cost, its reward.  *ended:
+  // The step under a task (PendulumTask above): its bound, then Pendulum's physics and cost, its reward.  *ended:
   // the time limit has been reached, whatever the task makes of that.
-  template <class Task>
-  __device__ static void step(double* s, const float* a, const Task& task, int* elapsed, double* reward, int* ended) {
+  __device__ static void step(double* s, const float* a, const PendulumTask& task, int* elapsed, double* reward, int* ended) {
 #pragma clang fp contract(off)
     const double bounded = task.clip ? clip_bounds(a[0]) : check_bounds(a[0]);
     const double cost = Pendulum::advance(s, &bounded, elapsed);
     *ended = *elapsed >= 200 ? 1 : 0;
     *reward = -cost * task.reward_scale + task.reward_offset;
   }
-};
-
-// What "Pendulum-v0" means to the DDPG handle's device actors and evaluator (ga3c_ddpg_task_create, DESIGN.md 8t;
-// tests/ddpg_task_oracle.py is the same statement), by value in the arguments of the task kernels only.
-struct PendulumTask {
-  int clip;                  // the action is clipped to [-1, 1], not wrapped
-  int truncate;              // the time limit ends the episode and is no terminal state: the row's done stays 0
-  int reset_observation;     // a reset rewrites the observation from the reset physics
-  double reward_scale, reward_offset;      // reward = -cost scale + offset
-};
-
-// The fork's task, EnvironmentPend.Environment's, known to the compiler: the kernels of a handle without a task are
-// instantiated on it and are the kernels they were.
-struct ForkTask {
-  static constexpr int clip = 0, truncate = 0, reset_observation = 0;
-  static constexpr double reward_scale = 0.005, reward_offset = -1.0;
 };
 
 // The episodes a step finishes and the ring that keeps their records for the host: the part of the device state that the

@@ -25,8 +25,9 @@
 //   per_update_kernel     one workgroup: pa[slot] = (|y - q| + eps)^alpha from the critic kernel's y and q
 // A prioritised step is 8 launches (9 with clipping) and draws its own rows: no host draw, no stamp, nothing to lose.
 // Device actors (ga3c_ddpg_actors_create, Config.DEVICE_DDPG; tests/ddpg_actors_oracle.py is the same statement):
-//   ddpg_actors_step_kernel<Env>   one thread per environment: the step (actor_step, the one statement of it), its transition
-//                                  into the ring, the episode record
+//   ddpg_actors_step_kernel<Env, Fork>   one thread per environment: the step (actor_step, the one statement of it) under the
+//                                  handle's task, its transition into the ring, the episode record; Fork: the same text compiled
+//                                  on the fork's task, for a handle without one
 //   ddpg_actors_episodes_kernel    one workgroup: this step's episode records into the episode ring, environment order
 //   ddpg_uniform_slots_kernel      a train step's rows without priorities: a stratified draw in integers, on the device
 // Twin critics (ga3c_ddpg_twin_create, Config.DDPG_TWIN; tests/td3_oracle.py is the same statement):
@@ -51,8 +52,9 @@
 // They stand beside the scalar kernels, which compile from the source they had; the launch counts of a step are the same.
 // Evaluation episodes (ga3c_ddpg_eval_create, Config.DEVICE_DDPG_EVAL_ENVS; tests/ddpg_eval_oracle.py is the same
 // statement):
-//   ddpg_eval_kernel<Env>    one workgroup per 16 evaluation environments walks a whole episode: actor_fwd without noise, the
-//                            environment's step on the thread's registers, the f64 sum of the rewards; one launch per evaluation
+//   ddpg_eval_kernel<Env, Policy>   one workgroup per 16 evaluation environments walks a whole episode: the policy's forward
+//                            without noise (DetPolicy: actor_fwd), the environment's step under the handle's task on the thread's
+//                            registers, the f64 sum of the rewards; one launch per evaluation
 // Per-environment noise (ga3c_ddpg_envnoise_create, Config.DEVICE_DDPG_NOISE; tests/envnoise_oracle.py is the same
 // statement):
 //   ddpg_predict_envnoise_kernel  ddpg_predict_kernel's body with every environment's own OU step in its epilogue; launched in
@@ -63,12 +65,11 @@
 //                        arenas rescaled so that sigma n + mu stays what it was, and yn = (y - mu') / sigma' for the critic step
 // The target kernel de-normalises the target critic's output with the statistics it finds; every other kernel runs as it did, on
 // yn where y was.  A popart step is 6 launches (7 with clipping, + 3 prioritised).
-// The task (ga3c_ddpg_task_create, Config.DEVICE_DDPG_ACTION_BOUND and its four neighbours; tests/ddpg_task_oracle.py
-// is the same statement):
-//   ddpg_actors_task_step_kernel<Env>, ddpg_actors_task_nstep_kernel<Env>, ddpg_eval_task_kernel<Env>   the bodies of the three
-//                        kernels above with a PendulumTask from the arguments where they have ForkTask, the fork's wrapper as
-//                        constants: clip or wrap, the time limit as a truncation, the observation of the reset state, the
-//                        reward's scale and offset.  Launched in their places by a handle with a task; the launch counts stay.
+// The task (ga3c_ddpg_task_create, Config.DEVICE_DDPG_ACTION_BOUND and its four neighbours, DESIGN.md 8t, 8w;
+// tests/ddpg_task_oracle.py is the same statement): clip or wrap, the time limit as a truncation, the observation of the reset
+// state, the reward's scale and offset.  A PendulumTask in the arguments of the two actor step kernels and of the evaluation
+// kernel: a handle without a task passes the fork's values (PendulumTask::fork).  The n-step and the evaluation kernel have no
+// other form; the step kernel has a second instantiation that knows those values when it is compiled.
 // Soft actor-critic (ga3c_ddpg_soft_create, Config.DDPG_SOFT; tests/sac_oracle.py is the same statement), on a twin
 // handle whose actor head is [300, 2A]:
 //   ddpg_soft_target_kernel   the ONLINE actor's sample a2, logp2 at s2 (soft_actor_fwd: actor_fwd with the raw head), both target
@@ -77,7 +78,7 @@
 //                             smaller one's dq/da, the gradient of (1/B) sum (alpha logp - q) through the sample, the actor's deltas
 //   ddpg_soft_wgrad_kernel    the actor's ddpg_wgrad_kernel<1, true> with log_alpha's Adam step riding in it
 //   ddpg_soft_predict_kernel  tanh(mu), or the sample under the caller's eps or the counter draws of the row's stream
-//   ddpg_soft_eval_kernel<Env, Task>   ddpg_eval_kernel / ddpg_eval_task_kernel under tanh(mu)
+//   SoftPolicy                ddpg_eval_kernel's policy on such a handle: soft_actor_fwd, a = tanh(mu)
 // The critics' kernels are the twin's and the launch counts of a step are the twin's.
 // The variables: their names, Layout and twin_view, the table of whatever options a handle carries (make_table),
 // the value a variable starts from (initial_value) and the re-lay of an arena from one table to another (relay) are
@@ -1140,18 +1141,18 @@ struct ActState {
   ga3c_actors::Episodes ep;  // this step's finished episodes and the episode ring
 };
 
-using ga3c_actors::ForkTask;
 using ga3c_actors::PendulumTask;
 
 // One step of environment i = the thread's index, the one statement of it for the kernels below.  first: the handle's first
 // ever step, the host's step(None): the zero action, nothing kept of the transition, its done not looked at.  Otherwise the
 // action is a.action's row and keep(i, obs, a, reward, ended, terminal, obs') puts the transition where the kernel wants it,
 // before the episode's totals move.  The f64 physics must not contract; neither may a `keep` that does arithmetic.
-// task: ForkTask, or a handle's PendulumTask.  `ended` is the time limit reached: a.done, the episode record, the
-// reset and its draws follow it; `terminal` is what a ring row calls done, `ended` unless the task truncates.  obs' is the
-// observation before any reset; under reset_observation a.obs then becomes the observation of the reset physics.
-template <class Env, class Task, class Keep>
-__device__ __forceinline__ void actor_step(const ActState& a, int first, const Task& task, Keep keep) {
+// task: the handle's, the fork's values until it is given one.  `ended` is the time limit reached: a.done, the
+// episode record, the reset and its draws follow it; `terminal` is what a ring row calls done, `ended` unless the task
+// truncates.  obs' is the observation before any reset; under reset_observation a.obs then becomes the observation of the
+// reset physics.
+template <class Env, class Keep>
+__device__ __forceinline__ void actor_step(const ActState& a, int first, const PendulumTask& task, Keep keep) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * ACT_THREADS + threadIdx.x;
   if (i >= a.N) return;
@@ -1199,14 +1200,16 @@ __device__ __forceinline__ void actor_step(const ActState& a, int first, const T
 // actor_step with the transition obs | a | (f32) reward | done | obs' into ring slot (slot0 + i) mod cap (n <= cap: no two
 // threads share a slot).  With priorities that slot gets max_pa, which only per_update_kernel writes, earlier on this stream:
 // per_fill_kernel's value.
-// (The bodies take the kernels' arguments as they stand here, __restrict__ only on the kernels: spelt this way the two kernels
-// without a task compile to the listings they had, tools/asm_diff.py.)
-template <class Env, class Task>
-__device__ __forceinline__ void actors_step_body(ActState a, Task task, int first, float* ring, int64_t slot0, int64_t cap,
-                                                 float* pa, const float* max_pa) {
+// Fork: the task is known to be the fork's and `given` is not read, so the compiler folds the task's branches away; launched
+// for a handle without a task, because at N = 4096 the step under the run-time task measured 0.1 us above the mark.
+template <class Env, bool Fork>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState a, PendulumTask given, int first,
+                                                                       float* __restrict__ ring, int64_t slot0, int64_t cap,
+                                                                       float* __restrict__ pa, const float* __restrict__ max_pa) {
 #pragma clang fp contract(off)
   constexpr int S = Env::S, A = Env::A;
   constexpr int rowf = 2 * S + A + 2;
+  const PendulumTask task = Fork ? PendulumTask::fork() : given;
   actor_step<Env>(a, first, task,
                   [&](int i, const float* before, const float* av, double reward, int, int terminal, const float* after) {
 #pragma clang fp contract(off)
@@ -1219,21 +1222,6 @@ __device__ __forceinline__ void actors_step_body(ActState a, Task task, int firs
     for (int k = 0; k < S; ++k) row[S + A + 2 + k] = after[k];
     if (pa) pa[slot] = *max_pa;
   });
-}
-
-template <class Env>
-__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_step_kernel(ActState a, int first, float* __restrict__ ring, int64_t slot0,
-                                                                       int64_t cap, float* __restrict__ pa,
-                                                                       const float* __restrict__ max_pa) {
-  actors_step_body<Env>(a, ForkTask{}, first, ring, slot0, cap, pa, max_pa);
-}
-
-// ... under a handle's task: the same body, the task read from the arguments.
-template <class Env>
-__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_task_step_kernel(ActState a, PendulumTask task, int first,
-                                                                            float* __restrict__ ring, int64_t slot0, int64_t cap,
-                                                                            float* __restrict__ pa, const float* __restrict__ max_pa) {
-  actors_step_body<Env>(a, task, first, ring, slot0, cap, pa, max_pa);
 }
 
 // The environments' windows of a handle with n-step returns: the last n transitions of each, entry-major and
@@ -1252,10 +1240,11 @@ struct NWindow {
 // disc[slot] = (f32) g_m.  Nothing is summed across an episode's end; at n = 1 the row and gamma are ddpg_actors_step_kernel's.
 // Under a task the window's done is `ended`, where the sum is cut; Pendulum ends at its time limit alone, so the
 // last summed transition's `terminal` is that flag, or 0 for every row when the task truncates.
-template <class Env, class Task>
-__device__ __forceinline__ void actors_nstep_body(const ActState& a, Task task, NWindow w, int first, int entry, int emit,
-                                                  double gamma64, float* ring, int64_t slot0, int64_t cap, float* disc, float* pa,
-                                                  const float* max_pa) {
+template <class Env>
+__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_nstep_kernel(ActState a, PendulumTask task, NWindow w, int first,
+                                                                        int entry, int emit, double gamma64, float* __restrict__ ring,
+                                                                        int64_t slot0, int64_t cap, float* __restrict__ disc,
+                                                                        float* __restrict__ pa, const float* __restrict__ max_pa) {
 #pragma clang fp contract(off)
   constexpr int S = Env::S, A = Env::A;
   constexpr int rowf = 2 * S + A + 2, W = 2 * S + A + 1;
@@ -1299,23 +1288,6 @@ __device__ __forceinline__ void actors_nstep_body(const ActState& a, Task task, 
   });
 }
 
-template <class Env>
-__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_nstep_kernel(ActState a, NWindow w, int first, int entry, int emit,
-                                                                        double gamma64, float* __restrict__ ring, int64_t slot0,
-                                                                        int64_t cap, float* __restrict__ disc,
-                                                                        float* __restrict__ pa, const float* __restrict__ max_pa) {
-  actors_nstep_body<Env>(a, ForkTask{}, w, first, entry, emit, gamma64, ring, slot0, cap, disc, pa, max_pa);
-}
-
-template <class Env>
-__global__ __launch_bounds__(ACT_THREADS) void ddpg_actors_task_nstep_kernel(ActState a, PendulumTask task, NWindow w, int first,
-                                                                             int entry, int emit, double gamma64,
-                                                                             float* __restrict__ ring, int64_t slot0, int64_t cap,
-                                                                             float* __restrict__ disc, float* __restrict__ pa,
-                                                                             const float* __restrict__ max_pa) {
-  actors_nstep_body<Env>(a, task, w, first, entry, emit, gamma64, ring, slot0, cap, disc, pa, max_pa);
-}
-
 // One workgroup: the step's finished episodes go to the episode ring in environment order (ga3c_actors.hpp).
 __global__ __launch_bounds__(ga3c_actors::SCAN_THREADS) void ddpg_actors_episodes_kernel(ActState a) {
   __shared__ int sep[ga3c_actors::SCAN_THREADS];
@@ -1347,81 +1319,34 @@ struct EvalTrace {
   double* reward;            // [..]
 };
 
-// A whole noise-free episode of `steps` steps for environments row0 .. row0 + 15, one workgroup: thread r < nrows keeps
-// environment row0 + r's physics, step count and reward sum in registers; every step is actor_fwd on the tile's observations
-// (th: the value arena or the target arena), then Env::step and Env::observe by those threads, as actor_step states them, and
-// the reward added in step order in f64.  Every episode starts from start[i] with elapsed = 0.  Env::step's wrap branch
-// cannot be reached after tanh; it is the training actors' statement, kept whole.  The loop is bounded by `steps` alone.
-// Reads th and start; writes total_out, phys_out and the trace: no ActState, no ring, no priorities, no windows.
-// ddpg_eval_task_kernel below is this text once more with a task in Env::step: whoever edits one edits the other.
-template <class Env>
-__global__ __launch_bounds__(THREADS) void ddpg_eval_kernel(Layout L, const float* __restrict__ th, int n, int steps,
-                                                            const double* __restrict__ start, double* __restrict__ total_out,
-                                                            double* __restrict__ phys_out, EvalTrace tr) {
-#pragma clang fp contract(off)
-  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
-  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
-  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
-  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
-  constexpr int S = Env::S, P = Env::P, A = Env::A;
-  const int row0 = blockIdx.x * TILE, nrows = min(TILE, n - row0);
-  const int r = threadIdx.x;
-  const size_t i = (size_t)row0 + r;                 // the thread's environment, r < nrows
-  double s[P];
-  double total = 0.0;
-  int elapsed = 0;
-  float obs[S];
-  if (r < TILE) {
-    for (int k = 0; k < S; ++k) obs[k] = 0.f;
-    if (r < nrows) {
-      for (int k = 0; k < P; ++k) s[k] = start[i * P + k];
-      Env::observe(s, obs);
-    }
-    for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+// The deterministic actor as an evaluation's policy: its forward, which ends in a barrier, and how thread r reads action j from
+// the head's LDS buffer afterwards.  SoftPolicy (8u, below) is the soft actor's.
+struct DetPolicy {
+  __device__ static void fwd(const Layout& L, const float* th, const float* xin, float* bufA, float* bufB, float* head, int row0,
+                             int nrows) {
+    actor_fwd(L, th, xin, bufA, bufB, head, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
   }
-  __syncthreads();
-  for (int t = 0; t < steps; ++t) {
-    // ends in a barrier: act is whole, and no thread reads xin any more
-    actor_fwd(L, th, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
-    if (r < nrows) {
-      float av[A];
-      for (int j = 0; j < A; ++j) av[j] = act[j * TILE + r];
-      const size_t at = i * EVAL_MAX_STEPS + t;
-      if (tr.phys) {
-        for (int k = 0; k < P; ++k) tr.phys[at * P + k] = s[k];
-        for (int k = 0; k < S; ++k) tr.obs[at * S + k] = obs[k];
-        for (int j = 0; j < A; ++j) tr.action[at * A + j] = av[j];
-      }
-      double reward;
-      int done;
-      Env::step(s, av, &elapsed, &reward, &done);
-      total = total + reward;
-      Env::observe(s, obs);
-      for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
-      if (tr.phys) tr.reward[at] = reward;
-    }
-    __syncthreads();                                 // the next step's actor reads these observations
-  }
-  if (r < nrows) {
-    total_out[i] = total;
-    for (int k = 0; k < P; ++k) phys_out[i * P + k] = s[k];
-  }
-}
+  __device__ static float action(const float* head, int j, int r) { return head[j * TILE + r]; }
+};
 
-// ddpg_eval_kernel under a handle's task: only the reward differs -- no bound is reached after tanh, and there is
-// no ring and no reset.  The text above once more and not a body shared with it: inlined from a shared function the compiler
-// orders ddpg_eval_kernel's last address computations differently, and that kernel is held to the listing it had.  The two are
-// edited together.  (`done` is Env::step's out-argument there and here: an evaluation is bounded by `steps` alone.)
-template <class Env>
-__global__ __launch_bounds__(THREADS) void ddpg_eval_task_kernel(Layout L, const float* __restrict__ th, int n, int steps,
-                                                                 PendulumTask task, const double* __restrict__ start,
-                                                                 double* __restrict__ total_out, double* __restrict__ phys_out,
-                                                                 EvalTrace tr) {
+// A whole noise-free episode of `steps` steps for environments row0 .. row0 + 15, one workgroup: thread r < nrows keeps
+// environment row0 + r's physics, step count and reward sum in registers; every step is the policy's forward on the tile's
+// observations (th: the value arena or the target arena), then Env::step under the handle's task and Env::observe by those
+// threads, as actor_step states them, and the reward added in step order in f64.  Every episode starts from start[i] with
+// elapsed = 0.  Of the task only the reward matters here: no bound is reached after tanh (Env::step's wrap branch is the
+// training actors' statement, kept whole), and there is no ring and no reset; `done` is Env::step's out-argument, and the loop
+// is bounded by `steps` alone.
+// Reads th and start; writes total_out, phys_out and the trace: no ActState, no ring, no priorities, no windows.
+template <class Env, class Policy>
+__global__ __launch_bounds__(THREADS) void ddpg_eval_kernel(Layout L, const float* __restrict__ th, int n, int steps,
+                                                            PendulumTask task, const double* __restrict__ start,
+                                                            double* __restrict__ total_out, double* __restrict__ phys_out,
+                                                            EvalTrace tr) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
   __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
   __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
-  __shared__ __attribute__((aligned(16))) float act[MAX_A * TILE];
+  __shared__ __attribute__((aligned(16))) float head[MAX_A * TILE];
   constexpr int S = Env::S, P = Env::P, A = Env::A;
   const int row0 = blockIdx.x * TILE, nrows = min(TILE, n - row0);
   const int r = threadIdx.x;
@@ -1440,11 +1365,11 @@ __global__ __launch_bounds__(THREADS) void ddpg_eval_task_kernel(Layout L, const
   }
   __syncthreads();
   for (int t = 0; t < steps; ++t) {
-    // ends in a barrier: act is whole, and no thread reads xin any more
-    actor_fwd(L, th, xin, bufA, bufB, act, nullptr, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
+    // ends in a barrier: head is whole, and no thread reads xin any more
+    Policy::fwd(L, th, xin, bufA, bufB, head, row0, nrows);
     if (r < nrows) {
       float av[A];
-      for (int j = 0; j < A; ++j) av[j] = act[j * TILE + r];
+      for (int j = 0; j < A; ++j) av[j] = Policy::action(head, j, r);
       const size_t at = i * EVAL_MAX_STEPS + t;
       if (tr.phys) {
         for (int k = 0; k < P; ++k) tr.phys[at * P + k] = s[k];
@@ -1778,61 +1703,14 @@ __global__ __launch_bounds__(THREADS) void ddpg_soft_predict_kernel(Layout L, co
   }
 }
 
-// ddpg_eval_kernel / ddpg_eval_task_kernel for a soft handle: the same episode under a = tanh(mu).  Task: ForkTask, or the handle's
-// PendulumTask.  (One template for both: these have no earlier listing to keep.)
-template <class Env, class Task>
-__global__ __launch_bounds__(THREADS) void ddpg_soft_eval_kernel(Layout L, const float* __restrict__ th, int n, int steps, Task task,
-                                                                 const double* __restrict__ start, double* __restrict__ total_out,
-                                                                 double* __restrict__ phys_out, EvalTrace tr) {
-#pragma clang fp contract(off)
-  __shared__ __attribute__((aligned(16))) float xin[MAX_S * TILE];
-  __shared__ __attribute__((aligned(16))) float bufA[H1 * TILE];
-  __shared__ __attribute__((aligned(16))) float bufB[H2 * TILE];
-  __shared__ __attribute__((aligned(16))) float raw[MAX_A * TILE];
-  constexpr int S = Env::S, P = Env::P, A = Env::A;
-  const int row0 = blockIdx.x * TILE, nrows = min(TILE, n - row0);
-  const int r = threadIdx.x;
-  const size_t i = (size_t)row0 + r;                 // the thread's environment, r < nrows
-  double s[P];
-  double total = 0.0;
-  int elapsed = 0;
-  float obs[S];
-  if (r < TILE) {
-    for (int k = 0; k < S; ++k) obs[k] = 0.f;
-    if (r < nrows) {
-      for (int k = 0; k < P; ++k) s[k] = start[i * P + k];
-      Env::observe(s, obs);
-    }
-    for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
+// ddpg_eval_kernel's policy on a soft handle: the same episode under a = tanh(mu), mu the first A rows of the raw head.
+struct SoftPolicy {
+  __device__ static void fwd(const Layout& L, const float* th, const float* xin, float* bufA, float* bufB, float* head, int row0,
+                             int nrows) {
+    soft_actor_fwd(L, th, xin, bufA, bufB, head, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
   }
-  __syncthreads();
-  for (int t = 0; t < steps; ++t) {
-    // ends in a barrier: raw is whole, and no thread reads xin any more
-    soft_actor_fwd(L, th, xin, bufA, bufB, raw, ActorKeep{nullptr, nullptr, nullptr, nullptr, nullptr}, row0, nrows);
-    if (r < nrows) {
-      float av[A];
-      for (int j = 0; j < A; ++j) av[j] = tanhf(raw[j * TILE + r]);
-      const size_t at = i * EVAL_MAX_STEPS + t;
-      if (tr.phys) {
-        for (int k = 0; k < P; ++k) tr.phys[at * P + k] = s[k];
-        for (int k = 0; k < S; ++k) tr.obs[at * S + k] = obs[k];
-        for (int j = 0; j < A; ++j) tr.action[at * A + j] = av[j];
-      }
-      double reward;
-      int done;
-      Env::step(s, av, task, &elapsed, &reward, &done);
-      total = total + reward;
-      Env::observe(s, obs);
-      for (int k = 0; k < S; ++k) xin[k * TILE + r] = obs[k];
-      if (tr.phys) tr.reward[at] = reward;
-    }
-    __syncthreads();                                 // the next step's actor reads these observations
-  }
-  if (r < nrows) {
-    total_out[i] = total;
-    for (int k = 0; k < P; ++k) phys_out[i * P + k] = s[k];
-  }
-}
+  __device__ static float action(const float* head, int j, int r) { return tanhf(head[j * TILE + r]); }
+};
 
 // ------------------------------------------------------------------ host side
 // The handle is a ga3c_vecnet::Core (ga3c_vecnet.hpp): stream, lanes, arenas, variables by name, checkpoint and registered
@@ -1981,8 +1859,8 @@ struct ga3c_ddpg : vn::Core {     // arenas: value, target, slot a, slot b, grad
   Eval* eval = nullptr;           // null: no evaluation episodes
   Pop* pop = nullptr;             // null: the critic's output is the return itself
   float* yn = nullptr;            // [B] its normalised targets, null without
-  bool has_task = false;          // false: the fork's task, and the actors' and the evaluator's kernels are the ones without
-  PendulumTask task{};            // (ga3c_ddpg_task_create): by value to the task kernels
+  bool has_task = false;          // ga3c_ddpg_task_create has been called: what the task's ABI answers by, and selects no kernel
+  PendulumTask task = PendulumTask::fork();      // by value to the actors' and the evaluator's kernels; the fork's until created
   DistRows dw{};                  // the distributional critic's rows, null without
   Soft* soft = nullptr;           // null: the deterministic actor
   SoftRows sw{};                  // its rows, null without
@@ -3498,7 +3376,7 @@ int ga3c_ddpg_task_create(ga3c_ddpg* m, int32_t bound, int32_t time_limit, int32
   std::lock_guard<std::mutex> tl(m->train_mu);
   if (m->has_task) return fail(GA3C_ESTATE, "the handle has a task already");
   if (m->actors || m->eval)
-    return fail(GA3C_ESTATE, "the handle has device actors or evaluation episodes: they choose their kernels when they are made, so the task comes first");
+    return fail(GA3C_ESTATE, "the handle has device actors or evaluation episodes: they step under the task they were made with, so the task comes first");
   m->task = PendulumTask{bound == GA3C_DDPG_TASK_CLIP, time_limit == GA3C_DDPG_TASK_TRUNCATE, reset_observation, reward_scale,
                          reward_offset};
   m->has_task = true;
@@ -3510,7 +3388,7 @@ int ga3c_ddpg_task_destroy(ga3c_ddpg* m) {
   std::lock_guard<std::mutex> tl(m->train_mu);
   CHK(task_check(m, "task_destroy", true));
   m->has_task = false;
-  m->task = PendulumTask{};
+  m->task = PendulumTask::fork();
   return GA3C_OK;
 }
 
@@ -3581,6 +3459,26 @@ int ga3c_ddpg_actors_create(ga3c_ddpg* m, int32_t n, int32_t updates, int64_t se
 
 int ga3c_ddpg_actors_destroy(ga3c_ddpg* m) { return ga3c_actors::actors_destroy(m); }
 
+namespace {
+// The environments' step under the handle's task, one thread each: with a window of n the n-step kernel, from which a row
+// leaves when `emit` is set; without one the step kernel, compiled on the fork's task for a handle that has none (8w: the one
+// place has_task chooses code, kept for 0.1 us at N = 4096).
+void launch_actor_step(ga3c_ddpg* m, DActors* a, int first, bool emit) {
+  const ActState& d = a->d;
+  const dim3 grid((d.N + ACT_THREADS - 1) / ACT_THREADS), block(ACT_THREADS);
+  const int64_t cap = m->cfg.replay_capacity;
+  float* pa = m->per ? m->per->pa : nullptr;
+  const float* max_pa = m->per ? m->per->max_pa : nullptr;
+  if (const int wn = a->win.n)
+    hipLaunchKernelGGL(ddpg_actors_nstep_kernel<DEnv>, grid, block, 0, m->st, d, m->task, a->win, first, (int)(a->count % wn),
+                       emit ? 1 : 0, (double)m->cfg.gamma, m->ring, m->ring_total % cap, cap, m->nstep->disc, pa, max_pa);
+  else {
+    const auto kernel = m->has_task ? ddpg_actors_step_kernel<DEnv, false> : ddpg_actors_step_kernel<DEnv, true>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, m->st, d, m->task, first, m->ring, m->ring_total % cap, cap, pa, max_pa);
+  }
+}
+}  // namespace
+
 // `steps` actor steps, each followed, when `train` is set and the ring holds MORE than a batch, by `updates` train steps.
 // Everything is enqueued without a wait in between: the host knows every launch argument (N transitions per actor step, B rows
 // per train step).  One wait at the end, a second only when episodes finished and their records are fetched.
@@ -3597,7 +3495,6 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
   if (train && m->per) CHK(per_check_beta(beta_is));
   const ActState& d = a->d;
   const int N = d.N, B = a->batch;
-  const int64_t cap = m->cfg.replay_capacity;
   int64_t calls = 0;
   {
     std::lock_guard<std::mutex> lk(m->mu);
@@ -3623,25 +3520,8 @@ int ga3c_ddpg_actors_run(ga3c_ddpg* m, int32_t steps, float learning_rate, float
                            d.action);
       }
     }
-    const int wn = a->win.n;            // n-step returns: a row leaves the window from transition n - 1 on
-    const bool emit = !first && a->count >= wn - 1;
-    if (wn && m->has_task)
-      hipLaunchKernelGGL(ddpg_actors_task_nstep_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st,
-                         d, m->task, a->win, first, (int)(a->count % wn), emit ? 1 : 0, (double)m->cfg.gamma, m->ring,
-                         m->ring_total % cap, cap, m->nstep->disc, m->per ? m->per->pa : nullptr,
-                         m->per ? (const float*)m->per->max_pa : nullptr);
-    else if (wn)
-      hipLaunchKernelGGL(ddpg_actors_nstep_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
-                         a->win, first, (int)(a->count % wn), emit ? 1 : 0, (double)m->cfg.gamma, m->ring, m->ring_total % cap, cap,
-                         m->nstep->disc, m->per ? m->per->pa : nullptr, m->per ? (const float*)m->per->max_pa : nullptr);
-    else if (m->has_task)
-      hipLaunchKernelGGL(ddpg_actors_task_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st,
-                         d, m->task, first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
-                         m->per ? (const float*)m->per->max_pa : nullptr);
-    else
-      hipLaunchKernelGGL(ddpg_actors_step_kernel<DEnv>, dim3((N + ACT_THREADS - 1) / ACT_THREADS), dim3(ACT_THREADS), 0, m->st, d,
-                         first, m->ring, m->ring_total % cap, cap, m->per ? m->per->pa : nullptr,
-                         m->per ? (const float*)m->per->max_pa : nullptr);
+    const bool emit = !first && a->count >= a->win.n - 1;      // n-step returns: a row leaves the window from transition n - 1 on
+    launch_actor_step(m, a, first, emit);
     hipLaunchKernelGGL(ddpg_actors_episodes_kernel, dim3(1), dim3(ga3c_actors::SCAN_THREADS), 0, m->st, d);
     HIPCHK(hipGetLastError());
     a->started = true;
@@ -3890,6 +3770,16 @@ int ga3c_ddpg_eval_destroy(ga3c_ddpg* m) {
   return GA3C_OK;
 }
 
+namespace {
+// An episode of `steps` steps under the handle's task for every evaluation environment, by the handle's policy on the value
+// arena or the target arena.
+void launch_eval(ga3c_ddpg* m, Eval* e, int steps, bool target) {
+  const auto kernel = m->soft ? ddpg_eval_kernel<DEnv, SoftPolicy> : ddpg_eval_kernel<DEnv, DetPolicy>;
+  hipLaunchKernelGGL(kernel, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[target ? 1 : 0], e->n, steps,
+                     m->task, (const double*)e->start, e->total, e->phys, e->tr);
+}
+}  // namespace
+
 // One launch, one copy back, one wait.  The kernel stands on the handle's stream between whole train steps, so the arena it
 // reads is that of exactly one of them.
 int ga3c_ddpg_eval_run(ga3c_ddpg* m, int32_t steps, int32_t target, double* total_reward) {
@@ -3903,21 +3793,7 @@ int ga3c_ddpg_eval_run(ga3c_ddpg* m, int32_t steps, int32_t target, double* tota
   {
     std::lock_guard<std::mutex> lk(m->mu);
     HIPCHK(hipEventRecord(m->t0, m->st));
-    if (m->soft && m->has_task)
-      hipLaunchKernelGGL((ddpg_soft_eval_kernel<DEnv, PendulumTask>), dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L,
-                         (const float*)m->arena[target ? 1 : 0], e->n, (int)steps, m->task, (const double*)e->start, e->total, e->phys,
-                         e->tr);
-    else if (m->soft)
-      hipLaunchKernelGGL((ddpg_soft_eval_kernel<DEnv, ForkTask>), dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L,
-                         (const float*)m->arena[target ? 1 : 0], e->n, (int)steps, ForkTask{}, (const double*)e->start, e->total,
-                         e->phys, e->tr);
-    else if (m->has_task)
-      hipLaunchKernelGGL(ddpg_eval_task_kernel<DEnv>, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L,
-                         (const float*)m->arena[target ? 1 : 0], e->n, (int)steps, m->task, (const double*)e->start, e->total, e->phys,
-                         e->tr);
-    else
-      hipLaunchKernelGGL(ddpg_eval_kernel<DEnv>, dim3(tiles(e->n)), dim3(THREADS), 0, m->st, m->L, (const float*)m->arena[target ? 1 : 0],
-                         e->n, (int)steps, (const double*)e->start, e->total, e->phys, e->tr);
+    launch_eval(m, e, (int)steps, target != 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->t1, m->st));
     HIPCHK(hipMemcpyAsync(e->h_total(), e->total, sizeof(double) * e->n, hipMemcpyDeviceToHost, m->st));

@@ -1,6 +1,6 @@
 """Oracle of the task of the DDPG device actors and evaluation episodes (Config.DEVICE_DDPG_ACTION_BOUND, _TIME_LIMIT,
-_RESET_OBSERVATION, _REWARD_SCALE, _REWARD_OFFSET, ga3c_ddpg_task_*; the kernels are ddpg_actors_task_step_kernel,
-ddpg_actors_task_nstep_kernel and ddpg_eval_task_kernel of csrc/ga3c_ddpg.hip), restated in numpy on ddpg_actors_oracle and
+_RESET_OBSERVATION, _REWARD_SCALE, _REWARD_OFFSET, ga3c_ddpg_task_*; the kernels are ddpg_actors_step_kernel,
+ddpg_actors_nstep_kernel and ddpg_eval_kernel of csrc/ga3c_ddpg.hip, which take the task from their arguments, 8w), restated in numpy on ddpg_actors_oracle and
 device_pendulum_oracle.
 
 A task is Task(bound, time_limit, reset_observation, reward_scale, reward_offset); FORK = ('wrap', 'terminal', False, 0.005,

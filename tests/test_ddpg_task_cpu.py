@@ -1,4 +1,4 @@
-"""No GPU: tests/ddpg_task_oracle.py -- the statement the task kernels of the DDPG device actors are held to --
+"""No GPU: tests/ddpg_task_oracle.py -- the statement the DDPG device actors' kernels are held to under a task --
 against ddpg_actors_oracle and nstep_oracle at the fork's task, against EnvironmentPend.Pendulum (gym's Pendulum-v0 restated) at
 gym's task, and rule by rule in between; then the Config keys, the ABI entries and what NetworkDDPG asks of the library.
 

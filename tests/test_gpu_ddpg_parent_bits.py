@@ -145,7 +145,8 @@ def _nstep_case(twin):
         net.close()
 
 
-def _actors_case(N, n, kind):
+def _actors_case(N, n, kind, task=None):
+    """task: attached before the actors are made (tests/test_gpu_ddpg_task_eval_parent_bits.py); None here."""
     S, A, B, cap = 3, 1, 16, 1024
     cfg = dict(DDPG_CRITIC_LOSS="paired", DDPG_NSTEP=n)
     if kind == "twin":
@@ -154,6 +155,8 @@ def _actors_case(N, n, kind):
         cfg["PRIORITIZED_REPLAY"] = True
     net, rng, _ = _make(S, A, 5000 + N + n, max_batch=max(N, B), capacity=cap, rows=0, **cfg)
     try:
+        if task:
+            net.task_create(*task)
         net.actors_create(N, seed=77 + N, updates=2, batch=B, draw_seed=4242)
         elapsed = np.zeros(N, np.int32)             # episodes that end inside the run, on different steps
         for i in range(N):
@@ -196,8 +199,8 @@ CASES["actors_N5_n3_twin"] = (_actors_case, (5, 3, "twin"))
 CASES["actors_N257_n1_per"] = (_actors_case, (257, 1, "per"))
 
 
-def _run(case):
-    fn, args = CASES[case]
+def _run(case, cases=CASES):
+    fn, args = cases[case]
     return fn(*args)
 
 
@@ -218,7 +221,7 @@ def test_ddpg_bits_are_the_parents(parent_bits, case):
     assert not any(differ.values()), differ
 
 
-def _record(tree, out, commit):
+def _record(tree, out, commit, cases=CASES, what="after the last step of each case of tests/test_gpu_ddpg_parent_bits.py"):
     """Digests of the build in `tree` (a built checkout of the parent commit) -> the fixture."""
     tree = os.path.abspath(tree)
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -232,8 +235,8 @@ def _record(tree, out, commit):
         assert os.path.realpath(path).startswith(os.path.realpath(tree) + os.sep), (mod, path)
     assert os.path.exists(_native.HIP_LIB), "the parent checkout is not built"
     digests, unstable = {}, []
-    for case in sorted(CASES):
-        first, second = _run(case), _run(case)
+    for case in sorted(cases):
+        first, second = _run(case, cases), _run(case, cases)
         if first != second:
             unstable.append(case)
             print("LEFT OUT %s: the parent's own two runs differ" % case, flush=True)
@@ -241,18 +244,22 @@ def _record(tree, out, commit):
         digests[case] = first
         print("recorded %s" % case, flush=True)
     with open(out, "w") as f:
-        json.dump({"what": "sha256 of raw bytes after the last step of each case of tests/test_gpu_ddpg_parent_bits.py",
+        json.dump({"what": "sha256 of raw bytes " + what,
                    "recorded_from": "a build of the parent commit %s on an MI355X (gfx950)" % commit,
                    "left_out": unstable, "digests": digests}, f, indent=0, sort_keys=True)
         f.write("\n")
     print("recorded %d cases from %s, left out %d: %s" % (len(digests), tree, len(unstable), unstable))
 
 
-if __name__ == "__main__":
+def _main(**kw):
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", required=True)
     ap.add_argument("--record", required=True)
     ap.add_argument("--commit", required=True, help="the parent commit that --tree is a checkout of")
     args = ap.parse_args()
-    _record(args.tree, args.record, args.commit)
+    _record(args.tree, args.record, args.commit, **kw)
+
+
+if __name__ == "__main__":
+    _main()

@@ -1,6 +1,6 @@
 """-m gpu: the task of the DDPG device actors and evaluation episodes (Config.DEVICE_DDPG_ACTION_BOUND, _TIME_LIMIT,
-_RESET_OBSERVATION, _REWARD_SCALE, _REWARD_OFFSET, ga3c_ddpg_task_*; ddpg_actors_task_step_kernel,
-ddpg_actors_task_nstep_kernel, ddpg_eval_task_kernel) against tests/ddpg_task_oracle.py, which tests/test_ddpg_task_cpu.py holds
+_RESET_OBSERVATION, _REWARD_SCALE, _REWARD_OFFSET, ga3c_ddpg_task_*; ddpg_actors_step_kernel,
+ddpg_actors_nstep_kernel, ddpg_eval_kernel with the task in their arguments, 8w) against tests/ddpg_task_oracle.py, which tests/test_ddpg_task_cpu.py holds
 to ddpg_actors_oracle at the fork's task and to EnvironmentPend.Pendulum at gym's.  S = 3 and A = 1; N on both sides of the 16-row
 tile of the predict kernel, in one and in two workgroups of the step kernels.
 

@@ -12,7 +12,7 @@ train steps of --batch ring rows after every actor step, --prioritized for the d
 ThreadDeviceAgents runs them under DEVICE_DDPG_EVAL_ENVS (DESIGN.md 8q; profiles/ddpg_eval.txt), inside the timed rounds;
 --noise per_env for every environment's own noise process (Config.DEVICE_DDPG_NOISE, DESIGN.md 8r; profiles/envnoise_step.txt);
 --action-bound, --time-limit, --reset-observation, --reward-scale, --reward-offset for the actors' task (Config.DEVICE_DDPG_ACTION_BOUND
-and its neighbours; profiles/ddpg_task_step.txt): any non-default one attaches a task, and the task kernels step.
+and its neighbours; profiles/ddpg_task_step.txt): any non-default one attaches a task (without one the handle steps under the fork's values).
 usage: python tools/device_agents_step.py [--game CartPole-v0|Pendulum-v0] [--agents 256 4096] [--time-max 5] [--steps 64] [--calls 8] [--rounds 5] [--no-train]
        [--ddpg [--batch 64] [--updates 1] [--prioritized] [--capacity 1000000] [--nstep 1] [--eval-envs 0] [--eval-every 1000] [--noise shared|per_env]
         [--action-bound wrap|clip] [--time-limit terminal|truncate] [--reset-observation] [--reward-scale 0.005] [--reward-offset -1]]"""
