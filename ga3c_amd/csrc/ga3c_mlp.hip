@@ -282,28 +282,32 @@ struct GradSrc {
 };
 
 // Element e of variable v (a bias if v is odd): g[c] = its gradient under the deltas d[c], each summed over the rows in row
-// order; the NC chains share the row's input and are independent.
+// order; the NC chains share the row's input and are independent, in double and rounded once (ga3c_tile.hpp's sum_rows has
+// the reason).
 template <int NC>
 __device__ __forceinline__ void elem_grad(const Layout& L, const GradSrc& src, int v, int64_t e, const float* const (&d)[NC], int B,
                                           float (&g)[NC]) {
   const int l = v / 2, N = L.out[l], K = L.in[l], ld = src.d_ld[l];
+  double s[NC];
 #pragma unroll
-  for (int c = 0; c < NC; ++c) g[c] = 0.f;
+  for (int c = 0; c < NC; ++c) s[c] = 0.0;
   if (v & 1) {
     const int j = (int)(e - L.off[v]);
     for (int r = 0; r < B; ++r)
 #pragma unroll
-      for (int c = 0; c < NC; ++c) g[c] += d[c][(size_t)r * ld + j];
+      for (int c = 0; c < NC; ++c) s[c] += (double)d[c][(size_t)r * ld + j];
   } else {
     const int64_t loc = e - L.off[v];
     const int k = (int)(loc / N), j = (int)(loc % N);
     const float* __restrict__ x = src.in[l];
     for (int r = 0; r < B; ++r) {
-      const float xv = x[(size_t)r * K + k];
+      const double xv = (double)x[(size_t)r * K + k];
 #pragma unroll
-      for (int c = 0; c < NC; ++c) g[c] = fmaf(xv, d[c][(size_t)r * ld + j], g[c]);
+      for (int c = 0; c < NC; ++c) s[c] = fma(xv, (double)d[c][(size_t)r * ld + j], s[c]);
     }
   }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) g[c] = (float)s[c];
 }
 
 template <bool FUSED>

@@ -130,25 +130,29 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
 }
 
 // Sums over the batch rows, in row order.  The loads of ROWS_AHEAD rows are issued together and the additions stay one chain:
-// the bits of the plain loop at the latency of B / ROWS_AHEAD round trips to L2 instead of B.
+// the order of the plain loop at the latency of B / ROWS_AHEAD round trips to L2 instead of B.
 constexpr int ROWS_AHEAD = 16;
 
+// The chains are in double and rounded once.  A gradient or a loss column is a sum over up to 65536 rows, often of one sign:
+// where the terms are nearly equal a float chain rounds the same way at every addition (a loss of 2225.49 for 2226.92 at 65536
+// rows), and RMSProp's ms takes the square of the sum (the value head's bias sums v - y_r; with float chains two steps of 65536
+// rows left ms 1.1 to 1.3 times 1e-5 x max(ms) from the oracle).  tests/test_gpu_vector_batch.py holds both.
 __device__ __forceinline__ float sum_rows(const float* __restrict__ d, int ld, int B) {
-  float g = 0.f;
+  double g = 0.0;
   int r = 0;
   for (; r + ROWS_AHEAD <= B; r += ROWS_AHEAD) {
     float t[ROWS_AHEAD];
 #pragma unroll
     for (int i = 0; i < ROWS_AHEAD; ++i) t[i] = d[(size_t)(r + i) * ld];
 #pragma unroll
-    for (int i = 0; i < ROWS_AHEAD; ++i) g += t[i];
+    for (int i = 0; i < ROWS_AHEAD; ++i) g += (double)t[i];
   }
-  for (; r < B; ++r) g += d[(size_t)r * ld];
-  return g;
+  for (; r < B; ++r) g += (double)d[(size_t)r * ld];
+  return (float)g;
 }
 
 __device__ __forceinline__ float dot_rows(const float* __restrict__ x, int ldx, const float* __restrict__ d, int ldd, int B) {
-  float g = 0.f;
+  double g = 0.0;
   int r = 0;
   for (; r + ROWS_AHEAD <= B; r += ROWS_AHEAD) {
     float tx[ROWS_AHEAD], td[ROWS_AHEAD];
@@ -158,13 +162,13 @@ __device__ __forceinline__ float dot_rows(const float* __restrict__ x, int ldx, 
       td[i] = d[(size_t)(r + i) * ldd];
     }
 #pragma unroll
-    for (int i = 0; i < ROWS_AHEAD; ++i) g = fmaf(tx[i], td[i], g);
+    for (int i = 0; i < ROWS_AHEAD; ++i) g = fma((double)tx[i], (double)td[i], g);
   }
-  for (; r < B; ++r) g = fmaf(x[(size_t)r * ldx], d[(size_t)r * ldd], g);
-  return g;
+  for (; r < B; ++r) g = fma((double)x[(size_t)r * ldx], (double)d[(size_t)r * ldd], g);
+  return (float)g;
 }
 
-// losses[c] = sum over the rows of lossrow[r][c], c < 3: threads 0..2 of the one block that says `mine`, each in row order.
+// losses[c] = sum over the rows of lossrow[r][c], c < 3: threads 0..2 of the one block that says `mine`, each by sum_rows.
 __device__ __forceinline__ void loss_sums(const float* __restrict__ lossrow, float* __restrict__ losses, int B, bool mine = true) {
   if (mine && threadIdx.x < 3) losses[threadIdx.x] = sum_rows(lossrow + threadIdx.x, 3, B);
 }
